@@ -29,6 +29,11 @@ N > 1   (one process per GPU)  WEAK scaling of that same workload: every rank ho
         `--transport host` moves the all-reduce through the host (gloo) and lets the ranks share
         GPUs (rank r on device r mod device count): the whole N > 1 bench path on a one-GPU box.
 
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line can carry: the
+per-kernel table of all phases (a pass of its own after the timed steps), the all-reduce time per solve at N > 1, the public
+`optimize()` timing and, at N = 1, the CPU baseline, the SVD and depth-iteration legs and the config-4-shard and dense-visibility
+legs.  `--dump-outputs DIR` writes what the last timed step left committed (points, cameras, cost) as DIR/<name>.npy in fp64.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -503,6 +508,23 @@ def config1_default_scene():
         return {"error": repr(exc)}
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs stays under 64 MB with the .npy headers; a larger point set is written as a fixed, seeded sample of its rows
+
+
+def dump_outputs(out_dir, params, cost):
+    """What a caller of the timed path receives after its last step: the committed parameters (engine frame) and that
+    step's cost, fp64, one DIR/<name>.npy each.  Points beyond the size limit: the same seeded sample of rows in every run."""
+    X, f, u, t, R = params
+    arrays = {"cameras_f": f, "cameras_u": u, "cameras_t": t, "cameras_R": R, "cost": np.array([cost], dtype=np.float64)}
+    room = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // X[0].nbytes
+    if len(X) > room:
+        X = X[np.sort(np.random.default_rng(0).choice(len(X), room, replace=False))]
+    arrays["points_X"] = X
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def launcher_command(argv, n_gpus, port):
     """The command `python bench.py --gpus N ...` starts when no launcher started IT: one process
     per GPU under torch.distributed.run, same arguments (the driver's contract form)."""
@@ -562,13 +584,19 @@ def main():
     ap.add_argument("--config4-shard", action="store_true",
                     help="N=1: the per-GPU shard of config 4 when it is split over 8 GPUs (1.25M points x 500 cameras x 5 %%, 31M "
                          "observations, D = 4493) on the one GPU: per-kernel ms per solve and the roofline of its dominant kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything besides the headline figure: the per-kernel table of all "
+                         "phases, the all-reduce per solve, optimize() through the public API and, at N=1, the legs below")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters and cost the last timed step left committed to DIR/<name>.npy (fp64, rank 0)")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--cpu-workers", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--svd-rows", type=int, default=5_000_000, help="config-5 SVD rows (0 = skip)")
-    ap.add_argument("--depth-rows", type=int, default=5_000_000, help="points of the projective-depth iteration leg (0 = skip; 5 M x 8 images fp64 is the size DESIGN.md quotes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the SVD / depth legs")
+    ap.add_argument("--svd-rows", type=int, default=5_000_000, help="--full: config-5 SVD rows (0 = skip)")
+    ap.add_argument("--depth-rows", type=int, default=5_000_000, help="--full: points of the projective-depth iteration leg (0 = skip; 5 M x 8 images fp64 is the size DESIGN.md quotes)")
     ap.add_argument("--no-config4-shard-leg", action="store_true",
-                    help="N=1 default run: skip the short leg on config 4's per-GPU shard (~6 s: scene 1.7 s, create 0.3 s, 4 LM iterations)")
+                    help="--full at N=1: skip the legs on config 4's per-GPU shard (~6 s: scene 1.7 s, create 0.3 s, 4 LM iterations) "
+                         "and on the dense-visibility scene")
     ap.add_argument("--transport", choices=("rccl", "host"), default="rccl",
                     help="N>1: rccl = one GPU per rank, ncclAllReduce inside libmvba (default); host = the reduced system is "
                          "staged through the host and summed over gloo, ranks may share a GPU (one-GPU rehearsal of the N>1 path)")
@@ -701,32 +729,37 @@ def main():
         print("step_ms:", " ".join(f"{v:.3f}" for v in step_ms), file=sys.stderr)
     st = eng.stats()
     n_solves = eng.n_solves - solves0
-    # every phase timed, outside the timed region: TABLE_STEPS more steps of the same loop
-    TABLE_STEPS = 6
-    eng.set_profiling(True)
-    one_step()  # (creates the additional events)
-    eng.reset_stats()
-    solves_t0 = eng.n_solves
-    for _ in range(TABLE_STEPS):
-        one_step()
-    st_table = eng.stats()
-    table_solves = eng.n_solves - solves_t0
-    eng.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.get_params(), E_)
+    if args.full:
+        # every phase timed, outside the timed region: TABLE_STEPS more steps of the same loop
+        TABLE_STEPS = 6
+        eng.set_profiling(True)
+        one_step()  # (creates the additional events)
+        eng.reset_stats()
+        solves_t0 = eng.n_solves
+        for _ in range(TABLE_STEPS):
+            one_step()
+        phases = eng.stats()
+        table_solves = eng.n_solves - solves_t0
+        eng.set_profiling(False)
 
-    # The same schedule through the PUBLIC surface: BundleAdjuster.optimize(2.0, -1.0, 10)
-    # wall time -- includes the per-iteration print, the final get_params, the way back to the input
-    # frame and the set_params the reference's optimize ends with (ref :198-202).
-    eng.set_params(*state0)
-    API_ITERS = 10
-    fence()
-    ta = time.perf_counter()
-    with contextlib.redirect_stdout(io.StringIO()):
-        ba.optimize(2.0, -1.0, max_iter=API_ITERS)
-    fence()
-    t_api = time.perf_counter() - ta
+        # The same schedule through the PUBLIC surface: BundleAdjuster.optimize(2.0, -1.0, 10)
+        # wall time -- includes the per-iteration print, the final get_params, the way back to the input
+        # frame and the set_params the reference's optimize ends with (ref :198-202).
+        eng.set_params(*state0)
+        API_ITERS = 10
+        fence()
+        ta = time.perf_counter()
+        with contextlib.redirect_stdout(io.StringIO()):
+            ba.optimize(2.0, -1.0, max_iter=API_ITERS)
+        fence()
+        t_api = time.perf_counter() - ta
+    else:  # the kernels the timed region timed itself
+        phases = {k: st[k] for k in ("resid_jac", "schur")}
 
     if multi:
-        tt = torch.tensor([dt, t_api], dtype=torch.float64, device=cdev)
+        tt = torch.tensor([dt, t_api if args.full else 0.0], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt, t_api = float(tt[0].item()), float(tt[1].item())
         no = torch.tensor([sc.n_obs], dtype=torch.float64, device=cdev)
@@ -796,17 +829,17 @@ def main():
                 "ranks_per_device": (world / max(torch.cuda.device_count(), 1) if host_transport and multi else 1),
             },
             # C1: one all-reduce of the packed [A|b] per inner solve (+ the 16-byte cost/status all-gather)
-            "allreduce": ({"ms_per_solve": st_table["allreduce"]["ms"] / max(table_solves, 1),
+            "allreduce": ({"ms_per_solve": phases["allreduce"]["ms"] / max(table_solves, 1),
                            "bytes_per_solve": 8 * (81 * n_cams * (n_cams + 1) // 2 + 9 * n_cams), "ranks": world,
-                           "transport": args.transport} if multi else None),
+                           "transport": args.transport} if multi and args.full else None),
             "allreduce_model": allreduce_model(n_cams, max(world, 2)) if (multi or config4 or shard4) else None,
             "weak_scaling_model": weak_scaling_model(n_cams, ms_solve) if (world == 1 and scaling == "weak" and not shard4) else None,
             "resid_jac_gobs_per_s": n_obs_total / (k1_ms * 1e-3) / 1e9,
             "inner_solves": n_solves,
             "ms_per_inner_solve": ms_solve,
             "rmse_start": float(np.sqrt(E0 / n_obs_total)), "rmse_end": rmse,
-            "optimize_api": {"call": f"BundleAdjuster.optimize(2.0, -1.0, max_iter={API_ITERS})", "wall_s": t_api,
-                             "it_per_s": API_ITERS / t_api},
+            "optimize_api": ({"call": f"BundleAdjuster.optimize(2.0, -1.0, max_iter={API_ITERS})", "wall_s": t_api,
+                              "it_per_s": API_ITERS / t_api} if args.full else None),
             "roofline": roof_k3 if k3_ms >= k1_ms else roof_k1,
             "roofline_resid_jac": roof_k1,
             "roofline_schur": roof_k3,
@@ -823,31 +856,33 @@ def main():
             "step_ms": {"min": float(step_ms.min()), "median": float(np.median(step_ms)), "max": float(step_ms.max()),
                         "argmax": int(step_ms.argmax())},
             "kernel_ms_per_step": {k: (st[k]["ms"] / args.steps if k in ("resid_jac", "schur") else v["ms"] / TABLE_STEPS)
-                                   for k, v in st_table.items() if k != "counts"},
+                                   for k, v in phases.items() if k != "counts"},
             "kernel_ms_per_solve": {k: (st[k]["ms"] / max(n_solves, 1) if k in ("resid_jac", "schur") else v["ms"] / max(table_solves, 1))
-                                    for k, v in st_table.items() if k != "counts"},
-            "kernel_ms_per_step_source": f"resid_jac and schur: hipEvents inside the timed region; the other phases: a separate pass of "
-                                         f"{TABLE_STEPS} steps right after it with every phase timed (timing all of them costs ~3 % of a step)",
+                                    for k, v in phases.items() if k != "counts"},
+            "kernel_ms_per_step_source": ("resid_jac and schur: hipEvents inside the timed region; the other phases: " +
+                                          (f"a separate pass of {TABLE_STEPS} steps right after it with every phase timed (timing all of "
+                                           f"them costs ~3 % of a step)" if args.full else "not measured (--full)")),
         }
-        if not args.no_cpu_baseline and world == 1:  # CPU baseline and SVD leg: rank 0 at N = 1 only
-            eng.close()
-            out["cpu_baseline"] = cpu_baseline(sc, n_cams, iters=args.cpu_iters, workers=args.cpu_workers)
-            if args.svd_rows > 0:
-                out["factorization_svd_config5"] = svd_config5(args.svd_rows)
-            if args.depth_rows > 0:
-                out["depth_iteration"] = depth_iteration(args.depth_rows)
-            if args.svd_rows > 0:
-                out["factorization_svd_wide"] = svd_wide()
-        if world == 1 and not args.no_config4_shard_leg and not (shard4 or config4 or args.points or args.cams or args.vis):
-            eng.close()  # (idempotent) the config-3 engine's ~4 GB go back before the shard's ~11 GB are taken
-            try:
-                out["config4_shard"] = config4_shard_leg(device)
-            except Exception as exc:  # noqa: BLE001
-                out["config4_shard"] = {"error": repr(exc)}
-            try:
-                out["dense_visibility"] = dense_visibility_leg(device)
-            except Exception as exc:  # noqa: BLE001
-                out["dense_visibility"] = {"error": repr(exc)}
+        if args.full:
+            if not args.no_cpu_baseline and world == 1:  # CPU baseline and SVD leg: rank 0 at N = 1 only
+                eng.close()
+                out["cpu_baseline"] = cpu_baseline(sc, n_cams, iters=args.cpu_iters, workers=args.cpu_workers)
+                if args.svd_rows > 0:
+                    out["factorization_svd_config5"] = svd_config5(args.svd_rows)
+                if args.depth_rows > 0:
+                    out["depth_iteration"] = depth_iteration(args.depth_rows)
+                if args.svd_rows > 0:
+                    out["factorization_svd_wide"] = svd_wide()
+            if world == 1 and not args.no_config4_shard_leg and not (shard4 or config4 or args.points or args.cams or args.vis):
+                eng.close()  # (idempotent) the config-3 engine's ~4 GB go back before the shard's ~11 GB are taken
+                try:
+                    out["config4_shard"] = config4_shard_leg(device)
+                except Exception as exc:  # noqa: BLE001
+                    out["config4_shard"] = {"error": repr(exc)}
+                try:
+                    out["dense_visibility"] = dense_visibility_leg(device)
+                except Exception as exc:  # noqa: BLE001
+                    out["dense_visibility"] = {"error": repr(exc)}
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if multi:

@@ -28,7 +28,7 @@ def test_bench_gpus_2_starts_its_own_ranks_over_the_host_transport():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--strong", "--transport", "host", "--points", "200000",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -51,7 +51,7 @@ def test_bench_gpus_2_default_is_weak_scaling_of_the_headline_workload():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "host", "--points", "100000",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -77,7 +77,7 @@ def test_bench_gpus_3_non_power_of_two_split_over_the_host_transport():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--strong", "--transport", "host", "--points", "300000",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]

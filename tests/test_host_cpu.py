@@ -200,6 +200,30 @@ def test_bench_round5_helpers_cores_allreduce_model_and_shard_roofline(monkeypat
     assert dense["achieved"] == pytest.approx(1e6 * (0.75 * 28 + 6) * 2048 / 1.31e-3 / 1e12) and dense["frac"] == pytest.approx(dense["achieved"] / 78.6)
 
 
+def test_bench_dump_outputs_writes_fp64_and_a_fixed_sample_of_points_over_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as fp64 .npy, the whole point set while it fits, beyond the size limit the same
+    seeded sample of rows (in their order) in every run."""
+    import bench
+
+    assert bench.DUMP_BYTES < 64e6
+    rng = np.random.default_rng(7)
+    X = np.column_stack([np.arange(5000.0), rng.standard_normal((5000, 2))])
+    params = (X, rng.standard_normal(4), rng.standard_normal((4, 2)), rng.standard_normal((4, 3)), rng.standard_normal((4, 3, 3)))
+    bench.dump_outputs(str(tmp_path / "all"), params, 2.5)
+    names = ("points_X", "cameras_f", "cameras_u", "cameras_t", "cameras_R")
+    for name, v in zip(names, params):
+        got = np.load(tmp_path / "all" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    assert np.load(tmp_path / "all" / "cost.npy").tolist() == [2.5]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 24 * 1000 + 8 * (4 + 8 + 12 + 36 + 1))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), params, 2.5)
+    Xa, Xb = (np.load(tmp_path / r / "points_X.npy") for r in ("a", "b"))
+    assert Xa.shape == (1000, 3) and np.array_equal(Xa, Xb)
+    rows = Xa[:, 0].astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(Xa, X[rows])
+
+
 def test_full_visibility_fast_paths_equal_the_general_ones():
     """Round 5's host-side shortcuts for the all-visible case give exactly what the general code gives: the observation list of a
     dense array without a mask (no np.nonzero / gather: 0.24 s at 1 M x 12) and the data matrix filled in place."""
