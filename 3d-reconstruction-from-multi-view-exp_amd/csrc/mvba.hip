@@ -5,7 +5,7 @@
 //   K1  k_resid_jac      residual + 2x3 / 2x9 Jacobian rows per observation   (ref :291-427)
 //   K2  (fused into K1)  E_a = 2 sum JxT Jx, dP_a = 2 sum JxT e               (ref :429-469, :519-556)
 //   K3a k_point_inv      damped 3x3 inverse, v_a = E^-1 dP_a                  (ref :120-128)
-//   K3  k_schur_slots (up to ~100 cameras) / k_schur_pairs + k_schur_reduce (k_schur_strip behind MVBA_SCHUR=strip)
+//   K3  k_schur_slots (up to ~100 cameras) / k_schur_pairs + k_schur_reduce / k_schur_dense (full visibility)
 //                        A = G^ - sum F^T E^-1 F,  b = sum F^T E^-1 dP - dF   (ref :132-143, :471-517, :618-664)
 //   C1  ncclAllReduce    [A|b] across point shards                            
 //   K4  k_compact, k_chol_super / k_chol_trail64 / k_chol_trail32 / k_chol_backsolve_all (+ the k_lu_* rescue)
@@ -364,204 +364,17 @@ __global__ __launch_bounds__(256) void k_point_inv(long long npts, double c, con
 }
 
 // ------------------------------------------------------------------ K3
-// Block (k, chunk, seg): accumulates the block-row strip A[9k..9k+8][9 l_lo .. 9 l_hi)
-// (l >= k: upper block triangle only) in LDS over the points of `chunk` seen by
-// camera k, then flushes it once.  Each wave walks camera-major records
-// (obs, point, remaining-observations-in-row); the k-side operands are wave-uniform
-// (scalar loads), the l-side operands are per lane: lane = 9*slot + j handles
-// column j of the 9x9 block of the slot-th remaining observation of the point.
+// Per (point a, camera k, camera l >= k) item, the 9x9 block (upper block triangle only):
 //   -(F_ak^T E^-1 F_al)[i][j] = -Jc_k[:,i] . ( 2 Jx_k E^-1 ( 2 Jx_l^T Jc_l[:,j] ) )
 // The diagonal item (l == k) also adds G^_k (ref :618-664 with :123-125 damping)
 // and the right-hand side 2 Jc_k^T (Jx_k v_a - e_ak)   (ref :138-143, :471-517).
-// Wave-uniform operands are read through the constant address space so the
-// compiler issues scalar (SMEM) loads into SGPRs instead of 64 identical vector loads.
-
-// LDS strip layout: strip[(9 (l - l_lo) + j) * 9 + i]  (i fastest) so that the nine
-// accumulations of a lane are ONE address + immediate offsets; sb (rhs) follows.
-template <bool BIG, bool SEG>  // BIG: record byte offsets need 64 bits (n_obs * 128 >= 4 GiB); SEG: strips cut into 2..4 column segments
-__global__ __launch_bounds__(768, 6) void k_schur_strip(
-    int m, int nchunks, int lseg, int nsp, const long long *__restrict__ chunk_ptr, const int4 *__restrict__ csc,
-    const int *__restrict__ cam_idx, const double2 *__restrict__ rec, const double *__restrict__ PB, double c,
-    double f0, double *__restrict__ Afull, double *__restrict__ bfull) {
-  extern __shared__ double strip[];
-  const int k = blockIdx.x, chunk = blockIdx.y, seg = blockIdx.z;
-  const int l_lo = k + seg * lseg;
-  if (l_lo >= m) return;
-  const int l_hi = min(m, l_lo + lseg);
-  const int W = 9 * (l_hi - l_lo);
-  double *sb = strip + 9 * W;
-  for (int i = threadIdx.x; i < 9 * W + 9; i += blockDim.x) strip[i] = 0.0;
-  // Workgroup barrier WITHOUT a compiler-level memory fence: a fencing __syncthreads() here
-  // makes LLVM treat every later load as clobbered and turns the wave-uniform k-side loads
-  // back into 64-lane vector loads (+70 VGPRs).  The LDS writes above are drained first.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");  // LDS-only: the zero-fill may not sink below the barrier
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nw = __builtin_amdgcn_readfirstlane(blockDim.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / 9, j = lane - 9 * slot;
-  // J_C column j of an observation = alpha * record_slot[sel] + beta  (see file header);
-  // the factor 4 = 2 (F = 2 Jx^T Jc) * 2 (t = 2 Jx_k h) is folded in here.
-  const unsigned sel16 = 16u * ((j == 0) ? 3 : (j >= 6 ? j - 2 : (j >= 3 ? j - 3 : 0)));
-  const double cu = 1.0 / f0;
-  const double alpha = (j == 1 || j == 2) ? 0.0 : ((j >= 3 && j < 6) ? -4.0 : 4.0);
-  const double beta_x = (j == 1) ? 4.0 * cu : 0.0, beta_y = (j == 2) ? 4.0 * cu : 0.0;
-  const long long beg = chunk_ptr[(size_t)k * (nchunks + 1) + chunk];
-  const long long end = chunk_ptr[(size_t)k * (nchunks + 1) + chunk + 1];
-  // scalar views (plain int / double elements: HIP vector types do not cross address spaces)
-  const auto *csc_c = as_const(reinterpret_cast<const int *>(csc));
-  const auto *rec_c = as_const(reinterpret_cast<const double *>(rec));
-  const auto *PBc = as_const(PB);
-  const char *recb = reinterpret_cast<const char *>(rec);
-  auto load_rec = [&](long long i) { return make_int4(csc_c[4 * i], csc_c[4 * i + 1], csc_c[4 * i + 2], SEG ? csc_c[4 * i + 3] : 0); };
-  // SEG (strips cut into nsp = 2..4 column segments; more segments fall back to scanning): the remaining
-  // observations of an entry are sorted by camera, so this block's items are the index range
-  // [first, last) of them; csc.w packs the segment boundaries (10 bits each, built on the host).
-  auto seg_first = [&](const int4 &r) { return (SEG && seg > 0) ? ((r.w >> (10 * (seg - 1))) & 1023) : 0; };
-  auto seg_last = [&](const int4 &r) { return (SEG && seg + 1 < nsp) ? ((r.w >> (10 * seg)) & 1023) : r.z; };
-  auto line = [&](int ol) -> const char * {
-    if (BIG) return recb + ((size_t)ol << 7);
-    return recb + ((unsigned)ol << 7);  // scalar base + 32-bit lane offset
-  };
-
-  // ---- software-pipelined walk over (entry, pass) pairs --------------------------------
-  // Scalar loads (SMEM) and LDS atomics share lgkmcnt and SMEM returns out of order, so a
-  // wait for the k-side operands is always lgkmcnt(0) and would also wait for every LDS
-  // atomic still queued behind 31 other waves.  Order per iteration therefore:
-  //   compute(pass n) -> issue loads for pass n+1 (vector l-side, scalar k-side if the
-  //   entry changes) -> s_waitcnt lgkmcnt(0) -> issue the 9 atomics of pass n.
-  // The atomics then drain under the compute of pass n+1.
-  long long idx = beg + wave;
-  if (idx < end) {
-    int4 cur = load_rec(idx);
-    int4 nxt = (idx + nw < end) ? load_rec(idx + nw) : cur;
-    int base = seg_first(cur), last = seg_last(cur);
-    // k-side: ONE record line + the point block, wave-uniform scalar loads
-    const double MVBA_CONST_AS *qk = rec_c + (size_t)cur.x * (2 * REC);
-    const double MVBA_CONST_AS *pb = PBc + PBS * (size_t)cur.y;
-    double kx00 = qk[0], kx10 = qk[1], kx01 = qk[2], kx11 = qk[3], kx02 = qk[4], kx12 = qk[5];
-    double kf0 = qk[6], kf1 = qk[7];
-    double kw00 = qk[8], kw10 = qk[9], kw01 = qk[10], kw11 = qk[11], kw02 = qk[12], kw12 = qk[13];
-    double i00 = pb[0], i01 = pb[1], i02 = pb[2], i11 = pb[3], i12 = pb[4], i22 = pb[5];
-    const double *PBg = PB;
-    // l-side of the first pass
-    bool act = base + slot < last;
-    int ol = cur.x + (act ? base + slot : 0);
-    int l = cam_idx[ol];
-    const char *ql = line(ol);
-    double2 x0 = *reinterpret_cast<const double2 *>(ql), x1 = *reinterpret_cast<const double2 *>(ql + 16),
-            x2 = *reinterpret_cast<const double2 *>(ql + 32), cs = *reinterpret_cast<const double2 *>(ql + sel16);
-    // the diagonal item always lands on the same addresses for a given lane (slot 0, l == k):
-    // its rhs and Marquardt-damping terms accumulate in registers and are flushed once per wave
-    double bacc = 0.0, dacc = 0.0;
-    while (true) {
-      // ---------------- compute pass n
-      const bool valid = act && slot < 7 && l >= l_lo && l < l_hi;
-      double *dst = strip + (9 * (l - l_lo) + j) * 9;
-      const bool diag = valid && (base + slot == 0);
-      double val[9];
-      // a pass with no lane inside this block's column segment (strips cut into segments, m > 236)
-      // costs only its loads: wave-uniform skip of the arithmetic
-      if (__ballot(valid) != 0ull) {
-        const double cjx = alpha * cs.x + beta_x, cjy = alpha * cs.y + beta_y;  // 4 * Jc_l[:, j]
-        const double g0 = x0.x * cjx + x0.y * cjy;  // 2 * F_al[:, j]
-        const double g1 = x1.x * cjx + x1.y * cjy;
-        const double g2 = x2.x * cjx + x2.y * cjy;
-        const double h0 = i00 * g0 + i01 * g1 + i02 * g2;  // 2 * E^-1 F_al[:, j]
-        const double h1 = i01 * g0 + i11 * g1 + i12 * g2;
-        const double h2 = i02 * g0 + i12 * g1 + i22 * g2;
-        double t0 = kx00 * h0 + kx01 * h1 + kx02 * h2;  // 2 Jx_k E^-1 F_al[:, j]
-        double t1 = kx10 * h0 + kx11 * h1 + kx12 * h2;
-        if (diag) {
-          // diagonal item (l == k, Jc_l == Jc_k): G_k - S_kk = -Jc_k^T (t - 2 Jc_k[:, j]); the
-          // Marquardt factor (1+c) on G's diagonal is one extra accumulation on element (j, j);
-          // right-hand side 2 Jc_k[:, j] . (Jx_k E^-1 dP - e).  Rare operands come per lane.
-          const double d0 = 0.5 * cjx, d1 = 0.5 * cjy;  // 2 * Jc_k[:, j]
-          t0 -= d0;
-          t1 -= d1;
-          dacc += c * 0.125 * (cjx * cjx + cjy * cjy);  // c * 2 |Jc_k[:, j]|^2
-          const double *pv = PBg + PBS * (size_t)cur.y + 6;
-          const double2 ke = *reinterpret_cast<const double2 *>(line(cur.x) + 112);
-          const double w0 = kx00 * pv[0] + kx01 * pv[1] + kx02 * pv[2] - ke.x;
-          const double w1 = kx10 * pv[0] + kx11 * pv[1] + kx12 * pv[2] - ke.y;
-          bacc += d0 * w0 + d1 * w1;
-        }
-        // -(Jc_k[:, i] . t) for i = f, u, v, t(3), omega(3)   (t columns of Jc are -Jx)
-        val[0] = -(kf0 * t0 + kf1 * t1);
-        val[1] = -(cu * t0);
-        val[2] = -(cu * t1);
-        val[3] = kx00 * t0 + kx10 * t1;
-        val[4] = kx01 * t0 + kx11 * t1;
-        val[5] = kx02 * t0 + kx12 * t1;
-        val[6] = -(kw00 * t0 + kw10 * t1);
-        val[7] = -(kw01 * t0 + kw11 * t1);
-        val[8] = -(kw02 * t0 + kw12 * t1);
-      }
-      // ---------------- advance to pass n+1 and issue its loads
-      bool done = false;
-      if (base + 7 < last) {
-        base += 7;
-      } else {
-        idx += nw;
-        if (idx >= end) {
-          done = true;
-        } else {
-          cur = nxt;
-          base = seg_first(cur);
-          last = seg_last(cur);
-          if (idx + nw < end) nxt = load_rec(idx + nw);
-          qk = rec_c + (size_t)cur.x * (2 * REC);
-          pb = PBc + PBS * (size_t)cur.y;
-          kx00 = qk[0]; kx10 = qk[1]; kx01 = qk[2]; kx11 = qk[3]; kx02 = qk[4]; kx12 = qk[5];
-          kf0 = qk[6]; kf1 = qk[7];
-          kw00 = qk[8]; kw10 = qk[9]; kw01 = qk[10]; kw11 = qk[11]; kw02 = qk[12]; kw12 = qk[13];
-          i00 = pb[0]; i01 = pb[1]; i02 = pb[2]; i11 = pb[3]; i12 = pb[4]; i22 = pb[5];
-        }
-      }
-      if (!done) {
-        const int it = base + slot;
-        act = it < last;
-        ol = cur.x + (act ? it : 0);
-        l = cam_idx[ol];
-        ql = line(ol);
-        x0 = *reinterpret_cast<const double2 *>(ql); x1 = *reinterpret_cast<const double2 *>(ql + 16);
-        x2 = *reinterpret_cast<const double2 *>(ql + 32); cs = *reinterpret_cast<const double2 *>(ql + sel16);
-      }
-      // the scalar loads above must have landed BEFORE the atomics enter the LDS queue
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0) only
-      __builtin_amdgcn_sched_barrier(0);
-      // ---------------- the 9 accumulations of pass n (asynchronous from here on)
-      if (valid) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) unsafeAtomicAdd(dst + i, val[i]);  // ds_add_f64 (this kernel IS its LDS atomics)
-      }
-      if (done) break;
-    }
-    if (seg == 0 && lane < 9) {
-      unsafeAtomicAdd(strip + lane * 9 + lane, dacc);  // (1+c) damping of G_k's diagonal (ref :123-125)
-      unsafeAtomicAdd(&sb[lane], bacc);
-    }
-  }
-  __syncthreads();
-  double *Ak = Afull + strip_offset(k, m) + 9 * (size_t)(l_lo - k);  // packed strip k, first column of this segment
-  const int Wk = 9 * (m - k);
-  for (int q = threadIdx.x; q < 9 * W; q += blockDim.x) {
-    const int row = q / W, col = q - row * W;  // coalesced over the columns of A
-    const double val = strip[col * 9 + row];
-    if (val != 0.0) unsafeAtomicAdd(&Ak[(size_t)row * Wk + col], val);
-  }
-  if (seg == 0 && threadIdx.x < 9) unsafeAtomicAdd(&bfull[9 * k + threadIdx.x], sb[threadIdx.x]);
-}
 
 // ------------------------------------------------------------------ K3 (pair-major form)
-// The same sum, organised by OUTPUT block instead of by camera strip.  Every (point, camera k,
+// The sum above, organised by OUTPUT block instead of by camera strip (round 1).  Every (point, camera k,
 // camera l >= k) triple is an "item" (built once on the host, sorted by (k, l), then by point), a
 // "unit" is a contiguous run of one pair's items, and ONE WAVE owns a unit: it keeps its share of the
-// 9x9 block in registers for the whole run, so there is no scatter and no atomic at all -- the
-// strip kernel above spends 75 % of its cycles in the LDS atomic pipe.  Per item the block is the
+// 9x9 block in registers for the whole run, so there is no scatter and no atomic at all -- round 1's
+// camera-strip kernel spent 75 % of its cycles in the LDS atomic pipe.  Per item the block is the
 // rank-2 product  -4 Jc_k^T t Jc_l  with  t = Jx_k E^-1 Jx_l^T (2x2).
 //   lanes      lane = 3 item + cg: 21 items per step, column group cg owns columns 3cg..3cg+2 of
 //              the block (f,u,v | t | omega) = 27 accumulators; t is formed redundantly by the 3 lanes
@@ -581,40 +394,19 @@ __global__ __launch_bounds__(768, 6) void k_schur_strip(
 //              k-side record of one observation run at the same time on the same L2.
 //   output     partial[unit][104] (81 block, 9 damping, 9 rhs), summed per pair in unit order by
 //              k_schur_reduce into the packed strips: bitwise reproducible, no zero-fill of A.
-#if defined(MVBA_FS)  // (experimental build: the slot form with one lane per item, 64 lists per wave -- csrc/mvba_fs.h; the unit form is not usable in it)
-constexpr int PSTEP = 64;
-#else
 constexpr int PSTEP = 21;                       // items per wave step
-#endif
 constexpr int PROW = 7 * 16;                    // staged bytes per record (slots 0..6, or 1..7)
 constexpr int PWAVE_LDS = PSTEP * (2 * PROW + 5 * 16);  // k rows, l rows, point rows
 constexpr int UNIT_STRIDE = 104;                // doubles per unit partial
 constexpr int SLOT_BUF = PSTEP * (2 * PROW + 3 * 16);  // slot form: one packed staging buffer (k rows, l rows, 48-byte point rows)
-#if defined(MVBA_FS)
-constexpr int SLOT_IDX = 3 * PSTEP;             // k[64] | l[64] | a[64]: one 768-byte DMA row
-constexpr int SLOT_IDX_RING = 2;                // ... staged two steps deep in LDS
-#else
 constexpr int SLOT_IDX = 64;                    // slot form: ints per step in the index (k[21] | l[21] | a[21] | pad): ONE 256-byte DMA row
 constexpr int SLOT_IDX_RING = 3;                // ... staged three steps deep in LDS
-#endif
-#if defined(MVBA_HREC_TIMING)
-#ifndef MVBA_HREC_NBUF
-#define MVBA_HREC_NBUF 3
-#endif
-constexpr int PAIRS_LDS = 2 * (PSTEP * (80 + 144));
-constexpr int SLOT_LDS = MVBA_HREC_NBUF * (PSTEP * (80 + 144)) + MVBA_HREC_NBUF * SLOT_IDX * 4;  // (timing build of the h-in-the-record variant)
-#else
 constexpr int PAIRS_LDS = 2 * PWAVE_LDS;  // the unit form: two staging buffers per wave
 constexpr int SLOT_LDS = 3 * SLOT_BUF + SLOT_IDX_RING * SLOT_IDX * 4;  // three staging buffers + the index ring per wave: 17,904 B, nine waves per CU
 // (LDS is handed out in 512-byte granules: 9 x 17,920 = 161,280 of the 163,840 bytes.  16 bytes are all a wave could still have --
 // with 48 more, a CU holds eight waves, the range's 284 are no longer all resident and the launch spends 6 ms in pacing time-outs:
 // profiles/r05_pace_poll.txt)
-#if defined(MVBA_FS)
-static_assert(3 * ((SLOT_LDS + 511) / 512 * 512) <= 160 * 1024, "three waves per CU");
-#else
 static_assert(9 * ((SLOT_LDS + 511) / 512 * 512) <= 160 * 1024, "nine waves per CU");
-#endif
-#endif
 
 __device__ __forceinline__ void lds_dma16(const void *gsrc, void *lds_wave_uniform) {
   __builtin_amdgcn_global_load_lds(gsrc, (__attribute__((address_space(3))) void *)lds_wave_uniform, 16, 0, 0);
@@ -636,7 +428,6 @@ struct SlotPace {
   const int *seg_end;
   int *prog;
   int need, nseg, lag;
-  long long *trace;  // diagnostic builds (-DMVBA_SLOT_TRACE): 16 words per wave (8 general + the loop's phase sums in shader cycles)
 };
 // SLOTS (the slot-resident form below, k_schur_slots): the 21 item rows of a step belong to 21 DIFFERENT lists, each
 // 3-lane slot keeps its own block for the whole run and writes it to its own partial (`out` is then the array of
@@ -647,7 +438,7 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
                                                  const int *__restrict__ it_a, const double2 *__restrict__ rec,
                                                  const double *__restrict__ PB, const double c, const double cu,
                                                  double *__restrict__ out, const int *__restrict__ slot_unit = nullptr,
-                                                 const SlotPace pace = SlotPace{nullptr, nullptr, 0, 0, 2, nullptr}) {
+                                                 const SlotPace pace = SlotPace{nullptr, nullptr, 0, 0, 2}) {
   constexpr int NPS = DIAG ? 5 : 3;                      // staged 16-byte slots of a point row
   const int it = lane / 3, cg = lane - 3 * it;           // compute: item of the step, column group
   const int drow = lane / 7, dslot = lane - 7 * drow;    // record DMA: 9 rows x 7 slots per instruction
@@ -715,28 +506,14 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
   // (OFFDIAG: 7 DMA instructions, DIAG: 6 -- and as many index loads per step: the slot form's counted wait relies on it)
   auto issue = [&](char *buf, const int (&xk_)[3], const int (&xl_)[3], const int (&xa_)[2]) {
     char *kb = buf, *lb = buf + LB_OFF, *pb_ = buf + PB_OFF;
-#if defined(MVBA_KO_DMA)  // (timing-only knock-outs of the UNIT form, as for the slot form: no gathers / every row -> row 0 / the l side only / the point rows only)
-    (void)kb; (void)lb; (void)pb_; (void)xk_; (void)xl_; (void)xa_;
-    return;
-#endif
-#if defined(MVBA_KO_GATHER)
-    const int xk[3] = {0, 0, 0}, xl[3] = {0, 0, 0}, xa[2] = {0, 0};
-#elif defined(MVBA_KO_LSIDE)
-    const int xk[3] = {xk_[0], xk_[1], xk_[2]}, xl[3] = {0, 0, 0}, xa[2] = {xa_[0], xa_[1]};
-#elif defined(MVBA_KO_PROW)
-    const int xk[3] = {xk_[0], xk_[1], xk_[2]}, xl[3] = {xl_[0], xl_[1], xl_[2]}, xa[2] = {0, 0};
-#else
     const int (&xk)[3] = xk_, (&xl)[3] = xl_, (&xa)[2] = xa_;
-#endif
     if (lane < 63) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         lds_dma16(rec_at(xk[q], dslot), kb + q * (9 * PROW));
         if (!DIAG) lds_dma16(rec_at(xl[q], dslot), lb + q * (9 * PROW));
       }
-#ifndef MVBA_TIMING_NO_PB  // (timing-only build, -DMVBA_TIMING_NO_PB: what a record that also carried E^-1 would save -- wrong numbers)
       if (!DIAG) lds_dma16(pb_at(xa[0], pslot), pb_);
-#endif
     }
     if (lane < 7 * (PSTEP - 18)) {  // third chunk: rows 18..20 only (a buffer holds 21 rows)
       lds_dma16(rec_at(xk[2], dslot), kb + 2 * (9 * PROW));
@@ -757,12 +534,7 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
       const double *pb = reinterpret_cast<const double *>(pbuf + it * (16 * NPS));
       const double2 kx0 = kr[0], kx1 = kr[1], kx2 = kr[2], kf = kr[3], kw0 = kr[4], kw1 = kr[5], kw2 = kr[6];
       const double2 lx0 = lr[0], lx1 = lr[1], lx2 = lr[2];
-#ifdef MVBA_TIMING_NO_PB
-      const double i00 = DIAG ? pb[0] : 1.0, i01 = DIAG ? pb[1] : 0.0, i02 = DIAG ? pb[2] : 0.0, i11 = DIAG ? pb[3] : 1.0, i12 = DIAG ? pb[4] : 0.0,
-                   i22 = DIAG ? pb[5] : 1.0;
-#else
       const double i00 = pb[0], i01 = pb[1], i02 = pb[2], i11 = pb[3], i12 = pb[4], i22 = pb[5];
-#endif
       // h = E^-1 Jx_l^T (3x2), t = Jx_k h (2x2)
       const double h0x = i00 * lx0.x + i01 * lx1.x + i02 * lx2.x, h0y = i00 * lx0.y + i01 * lx1.y + i02 * lx2.y;
       const double h1x = i01 * lx0.x + i11 * lx1.x + i12 * lx2.x, h1y = i01 * lx0.y + i11 * lx1.y + i12 * lx2.y;
@@ -784,11 +556,6 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
         }
       }
       const double2 s0v = lr[sel0], s1v = lr[sel1], s2v = lr[sel2];
-#if defined(MVBA_KO_VALU)  // (timing-only knock-out: every LDS read stays, the arithmetic shrinks to a handful of additions)
-      acc[0][0] += (t00 + t01) + (t10 + t11) + (kf.x + kf.y) + (kw0.x + kw0.y) + (kw1.x + kw1.y) + (kw2.x + kw2.y) + (s0v.x + s0v.y) + (s1v.x + s1v.y) + (s2v.x + s2v.y) + w0 + w1;
-      if (false)
-#endif
-      {
       const double sx[3] = {s0v.x, al12 * s1v.x + bx1, al12 * s2v.x};
       const double sy[3] = {s0v.y, al12 * s1v.y, al12 * s2v.y + bx1};
 #pragma unroll
@@ -811,7 +578,6 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
           rb[q] += sx[q] * w0 + sy[q] * w1;
         }
       }
-      }
     }
     // the LDS reads above are complete (their values were consumed) before this buffer is refilled
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -821,18 +587,11 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
   // resident: somebody else holds the CUs) stops pacing and runs on.
   bool pacing = SLOTS && pace.prog != nullptr;
   int seg = 0, seg_stop = pacing ? as_const(pace.seg_end)[0] * PSTEP : 0x7fffffff;
-#ifdef MVBA_SLOT_TRACE
-  const long long tr_t0 = __builtin_amdgcn_s_memrealtime();
-  long long tr_wait = 0, tr_blocked = 0, tr_polls = 0;
-#endif
   auto pace_at = [&](const int s0) {
     while (s0 == seg_stop) {  // (wave-uniform) this wave has left segment `seg`
       if (lane == 0) __hip_atomic_fetch_add(pace.prog + PACE_STRIDE * seg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       ++seg;
       seg_stop = seg < pace.nseg ? as_const(pace.seg_end)[seg] * PSTEP : 0x7fffffff;
-#ifdef MVBA_SLOT_TRACE
-      const long long tr_a = __builtin_amdgcn_s_memrealtime();
-#endif
       if (seg >= pace.lag && pacing) {  // nobody enters segment j before everybody has left segment j - lag
         // (a waiting wave polls every ~3 us: hundreds of waves polling one word at full speed saturate the
         // fabric's atomic path and slow the arrivals they are waiting for -- 15 ms per launch, measured)
@@ -846,14 +605,7 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
         // dispatching the diagonal waves first; three priority levels or none: no better / 1.73)
         if (tries > 0) __builtin_amdgcn_s_setprio(0);
         else __builtin_amdgcn_s_setprio(2);
-#ifdef MVBA_SLOT_TRACE
-        tr_polls += tries + 1;
-        tr_blocked += tries > 0;
-#endif
       }
-#ifdef MVBA_SLOT_TRACE
-      tr_wait += __builtin_amdgcn_s_memrealtime() - tr_a;
-#endif
     }
   };
   if (!SLOTS) {
@@ -899,25 +651,14 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
     // (M0 is written in the SAME statement that uses it: it is compiler-reserved, an "m0" clobber only draws a warning, and
     // the compiler's own M0 users -- none in this kernel: check_isa.py fails the build if one appears -- set it themselves)
     auto dma = [&](int row, unsigned slot16, const void *base, unsigned lds) {  // 16 bytes per lane: base[row * 128 + slot16] -> LDS
-#if defined(MVBA_KO_GATHER)  // (timing-only knock-out: every gather fetches row 0 of its array -- one line, always in L2 -- instead of its row)
-      row = 0;
-#endif
-#if defined(MVBA_KO_DMA)     // (timing-only knock-out: no record / point-row gather at all; the counted waits are adjusted below)
-      (void)row; (void)slot16; (void)base; (void)lds;
-#else
       // (the byte offset row * 128 + slot16 is formed BETWEEN the write of M0 and the gather that reads it: the one wait state the
       // hardware asks for there was an s_nop in rounds 3-4 -- eight issue slots per step for nothing)
       unsigned o;
       asm volatile("s_mov_b32 m0, %4\n\tv_lshl_add_u32 %0, %1, 7, %2\n\tglobal_load_lds_dwordx4 %0, %3" : "=&v"(o) : "v"(row), "v"(slot16), "s"(base), "s"(lds) : "memory");
-#endif
     };
     const unsigned lane16 = (unsigned)min(lane, 15) << 4;
     auto dma_idx = [&](int st, unsigned ring_off) {  // the 256-byte index row of step st -> ring slot st % 3 = byte offset ring_off (lanes 0..15, 16 bytes each)
-#if defined(MVBA_KO_IDX)  // (timing-only knock-out: always the wave's FIRST index row -- in L2 after the first touch -- instead of a new line from HBM)
-      const int *src = xbase + (size_t)min(st & 1, last_st) * SLOT_IDX;
-#else
       const int *src = xbase + (size_t)min(st, last_st) * SLOT_IDX;  // wave-uniform
-#endif
       const unsigned dst = ldsx0 + ring_off;
       if (lane < 16) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane16), "s"(src), "s"(dst) : "memory");
     };
@@ -965,43 +706,16 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
     issue_step(last_st >= 1 ? RING_B : 0, BUFSZ);  // (a one-step wave: the clamped step 0 once more, into the buffer nobody reads)
     dma_idx(3, 0);
     unsigned b0 = 0, b1 = BUFSZ, b2 = 2 * BUFSZ, r0 = 0, r1 = RING_B, r2 = 2 * RING_B;  // offsets of step st, st + 1, st + 2
-#ifdef MVBA_SLOT_TRACE  // where a step's cycles go: one s_memtime stamp (with its own lgkmcnt(0): ~40 cycles) between the phases
-#define TR_STAMP(v) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-    unsigned long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0, ph4 = 0, tA, tB, tC, tD, tE, tF, tL0, tL1;
-    TR_STAMP(tL0);
-#else
-#define TR_STAMP(v)
-#endif
     for (int st = 0; st < nst; ++st) {
-      TR_STAMP(tA);
       // step st has landed and the indices of step st + 2 are in the ring: everything but the last iteration's operations is done
-#if defined(MVBA_KO_DMA)
-      asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-#else
       if (DIAG) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#endif
-      TR_STAMP(tB);
       pace_at(st * PSTEP);
-      TR_STAMP(tC);
       issue_step(r2, b2);  // step st + 2 (past the end: the ring slot holds the indices of the clamped last step, its rows land in a buffer nobody reads)
-      TR_STAMP(tD);
       dma_idx(st + 4, r1);  // (st + 4) % 3 = (st + 1) % 3: the slot whose indices were read an iteration ago
-      TR_STAMP(tE);
       compute(wbuf + b0, PSTEP);
       { const unsigned tb = b0, tr = r0; b0 = b1; b1 = b2; b2 = tb; r0 = r1; r1 = r2; r2 = tr; }
-#ifdef MVBA_SLOT_TRACE
-      TR_STAMP(tF);
-      ph0 += tB - tA; ph1 += tC - tB; ph2 += tD - tC; ph3 += tE - tD; ph4 += tF - tE;
-#endif
     }
-#ifdef MVBA_SLOT_TRACE
-    TR_STAMP(tL1);
-    if (pace.trace && lane == 0) {
-      pace.trace[8] = (long long)ph0; pace.trace[9] = (long long)ph1; pace.trace[10] = (long long)ph2; pace.trace[11] = (long long)ph3;
-      pace.trace[12] = (long long)ph4; pace.trace[13] = (long long)(tL1 - tL0);
-    }
-#endif
     static_assert(SLOT_OPS == (DIAG ? 7 : 8), "counted wait");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped gathers still in flight land in this wave's LDS
   }
@@ -1010,15 +724,6 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
   if (SLOTS) {  // every slot holds a finished block of its own: no sum over lanes
     if (pace.prog != nullptr && lane == 0)
       for (; seg < pace.nseg; ++seg) __hip_atomic_fetch_add(pace.prog + PACE_STRIDE * seg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef MVBA_SLOT_TRACE
-    if (pace.trace && lane == 0) {
-      int hwid, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-      pace.trace[0] = tr_t0; pace.trace[1] = __builtin_amdgcn_s_memrealtime(); pace.trace[2] = tr_wait; pace.trace[3] = tr_blocked;
-      pace.trace[4] = tr_polls; pace.trace[5] = hwid; pace.trace[6] = xcc; pace.trace[7] = n / PSTEP;
-    }
-#endif
     const int u = it < PSTEP ? slot_unit[it] : -1;
     if (u >= 0) {
       double *o = out + (size_t)u * UNIT_STRIDE;
@@ -1070,12 +775,6 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
   }
 }
 
-#if defined(MVBA_HREC_TIMING)  // timing-only variant of both kernels (round 5, measured and not built: see the header)
-#include "mvba_hrec_timing.h"
-#endif
-#if defined(MVBA_FS)
-#include "mvba_fs.h"
-#endif
 
 
 // One wave per block: a wave works alone, and in a wider block its LDS and wave slots stay taken until
@@ -1090,9 +789,9 @@ __device__ __forceinline__ void schur_pairs_wave(const int4 *__restrict__ units,
   extern __shared__ char smem_pairs[];
   const int lane = threadIdx.x;
   char *wbuf = smem_pairs;
-  // ---- take one unit.  Static (default, head == nullptr): block b takes entry b / 8 of queue b % 8 -- no
+  // ---- take one unit.  Static (head == nullptr, what mvba_create launches): block b takes entry b / 8 of queue b % 8 -- no
   // atomic on the critical path; it relies on the round-robin block -> XCD placement for locality
-  // only, never for correctness (1.90 -> 1.87 ms).  Dynamic (MVBA_PAIR_STATIC=0): own XCD's queue
+  // only, never for correctness (1.90 -> 1.87 ms).  Dynamic (round 2's, no longer launched): own XCD's queue
   // first (XCC_ID), then the others; every queue entry is taken exactly once, the grid has as many
   // waves as there are units and a wave takes at most one.
   int pos = -1;
@@ -1120,13 +819,8 @@ __device__ __forceinline__ void schur_pairs_wave(const int4 *__restrict__ units,
   const long long beg = ((long long)ud_y << 32) | (unsigned)ud_x;
   const int n = ud_z, cam_k = (int)((unsigned)ud_w >> 16), cam_l = ud_w & 0xffff;
   double *out = partial + (size_t)u * UNIT_STRIDE;
-#if defined(MVBA_HREC_TIMING)  // timing-only (wrong numbers): slot 7 of the records stands in for the residual array
-  if (cam_k == cam_l) schur_pairs_unit_hrec<true, BIG>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, rec + 7, PB, c, 1.0 / f0, out);
-  else schur_pairs_unit_hrec<false, BIG>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, rec + 7, PB, c, 1.0 / f0, out);
-#else
   if (cam_k == cam_l) schur_pairs_unit<true, BIG>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out);
   else schur_pairs_unit<false, BIG>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out);
-#endif
 }
 
 #define MVBA_PAIRS_ARGS                                                                                                   \
@@ -1163,7 +857,7 @@ __device__ __forceinline__ void schur_slots_wave(const int4 *__restrict__ wdesc,
                                                  const double *__restrict__ PB, double c, double f0,
                                                  double *__restrict__ partial, int *__restrict__ head, int nR, int wpr,
                                                  const int *__restrict__ seg_end, int *__restrict__ prog, int nseg, int lag,
-                                                 long long *__restrict__ trace, const long long *__restrict__ range_o0) {
+                                                 const long long *__restrict__ range_o0) {
   extern __shared__ char smem_pairs[];
   // which wave of which range: static (head == nullptr) block b IS wave b / nR of range b % nR; dynamic: the wave
   // reads the XCD it runs on and takes the next wave of a range of that XCD (r % 8 == XCC_ID), then of the others
@@ -1192,38 +886,20 @@ __device__ __forceinline__ void schur_slots_wave(const int4 *__restrict__ wdesc,
   // the record indices of the step rows are RELATIVE to the range's first observation: the 32-bit byte offsets of the
   // gathers then span a range's records (4 GiB = 33.5 M observations per range), not the scene's
   const double2 *rec_r = rec + (size_t)as_const(range_o0)[r] * REC;
-  SlotPace pace{nullptr, nullptr, 0, 0, 2, trace ? trace + 16 * (size_t)bid : nullptr};
-  if (prog) pace = SlotPace{seg_end + (size_t)bid * nseg, prog + ((size_t)round * nR + r) * nseg * PACE_STRIDE, live, nseg, lag, pace.trace};
-#if defined(MVBA_HREC_TIMING)  // timing-only: today's records read with the new access pattern and arithmetic -- wrong numbers
-  const double2 *res_r = rec_r + 7;  // (the residual "array": slot 7 of the records, 128-byte stride -> dma16 takes row << 4 ... see below)
-  if (flags & 1)
-    schur_slots_hrec<true>(smem_pairs, (int)threadIdx.x, beg, nsteps * PSTEP, it_k, rec_r, res_r, PB, c, 1.0 / f0, partial, su, pace, 0);
-  else
-    schur_slots_hrec<false>(smem_pairs, (int)threadIdx.x, beg, nsteps * PSTEP, it_k, rec_r, res_r, PB, c, 1.0 / f0, partial, su, pace, 0);
-#elif defined(MVBA_FS)
-  if (flags & 1) schur_slots_fs<true>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_k, rec_r, PB, c, 1.0 / f0, partial, su, pace);
-  else schur_slots_fs<false>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_k, rec_r, PB, c, 1.0 / f0, partial, su, pace);
-#else
+  SlotPace pace{nullptr, nullptr, 0, 0, 2};
+  if (prog) pace = SlotPace{seg_end + (size_t)bid * nseg, prog + ((size_t)round * nR + r) * nseg * PACE_STRIDE, live, nseg, lag};
   if (flags & 1)
     schur_pairs_unit<true, false, true>(smem_pairs, (int)threadIdx.x, beg, nsteps * PSTEP, it_k, it_l, it_a, rec_r, PB, c, 1.0 / f0, partial, su, pace);
   else
     schur_pairs_unit<false, false, true>(smem_pairs, (int)threadIdx.x, beg, nsteps * PSTEP, it_k, it_l, it_a, rec_r, PB, c, 1.0 / f0, partial, su, pace);
-#endif
 }
 #define MVBA_SLOTS_ARGS                                                                                                  \
   const int4 *__restrict__ wdesc, const int *__restrict__ wunits, const int *__restrict__ it_k, const int *__restrict__ it_l, \
       const int *__restrict__ it_a, const double2 *__restrict__ rec, const double *__restrict__ PB, double c, double f0,  \
       double *__restrict__ partial, int *__restrict__ head, int nR, int wpr, const int *__restrict__ seg_end,            \
-      int *__restrict__ prog, int nseg, int lag, long long *__restrict__ trace, const long long *__restrict__ range_o0
-#ifndef MVBA_SLOT_WAVES_PER_SIMD
-#if defined(MVBA_FS)
-#define MVBA_SLOT_WAVES_PER_SIMD 1
-#else
-#define MVBA_SLOT_WAVES_PER_SIMD 3
-#endif
-#endif
-__global__ __launch_bounds__(64, MVBA_SLOT_WAVES_PER_SIMD) void k_schur_slots(MVBA_SLOTS_ARGS) {
-  schur_slots_wave(wdesc, wunits, it_k, it_l, it_a, rec, PB, c, f0, partial, head, nR, wpr, seg_end, prog, nseg, lag, trace, range_o0);
+      int *__restrict__ prog, int nseg, int lag, const long long *__restrict__ range_o0
+__global__ __launch_bounds__(64, 3) void k_schur_slots(MVBA_SLOTS_ARGS) {
+  schur_slots_wave(wdesc, wunits, it_k, it_l, it_a, rec, PB, c, f0, partial, head, nR, wpr, seg_end, prog, nseg, lag, range_o0);
 }
 
 // One thread per element of a pair's block: the pair's unit partials in unit order -> packed strips.
@@ -1284,9 +960,6 @@ __global__ __launch_bounds__(128) void k_schur_reduce(int m, const int *__restri
 // cameras w, w + 4, ...  Partial tiles per workgroup, summed in workgroup order by k_schur_dense_finish: no atomics, bitwise
 // reproducible.  No index at all: mvba_create skips the pair-major index for such scenes.
 typedef double mvba_d4 __attribute__((ext_vector_type(4)));
-#ifndef MVBA_DENSE_KO
-#define MVBA_DENSE_KO 0  // (timing-only builds: bit 0 no main MFMAs, 1 no rows of G, 2 no per-observation phase, 3 no per-camera MFMAs)
-#endif
 // Points per chunk (= producer waves) and workgroups per CU.  Up to 7 tiles (12 cameras) the kernel needs at most 126 registers: four
 // waves fit a SIMD, so TWO 8-wave workgroups of 4-point chunks (~53 KB of LDS each) share a CU and fill each other's barrier waits
 // (1.335 -> 1.260 ms at 1 M x 12, 1.48 -> 1.32 at 2 M x 6; three workgroups: worse again).  8 tiles take 154 registers -- three waves
@@ -1299,10 +972,7 @@ __device__ __forceinline__ int dense_tile_elem(int row, int col) { return ((row 
 
 constexpr int dense_pair_ti(int p, int T) { int a = 0; while (p >= T - a) { p -= T - a; ++a; } return a; }
 constexpr int dense_pair_tj(int p, int T) { int a = 0; while (p >= T - a) { p -= T - a; ++a; } return a + p; }
-#ifndef MVBA_DENSE_NC_SMALL
-#define MVBA_DENSE_NC_SMALL 4
-#endif
-constexpr int dense_consumers(int T) { return T <= 8 ? MVBA_DENSE_NC_SMALL : 8; }  // consumer waves: at most ~10 tile pairs (40 accumulator doubles) each
+constexpr int dense_consumers(int T) { return T <= 8 ? 4 : 8; }  // consumer waves: at most ~10 tile pairs (40 accumulator doubles) each
 constexpr bool dense_tile_used(int u, int T, int wave) {  // does consumer wave `wave` own a pair with tile u?
   const int P = T * (T + 1) / 2, NC = dense_consumers(T);
   for (int p = wave; p < P; p += NC)
@@ -1351,13 +1021,6 @@ __device__ __forceinline__ void dense_main_mfma(const double *sG, const double *
 // among themselves.  (With every wave doing every phase in turn -- four barriers per chunk -- the workgroups of a CU ran in
 // lockstep and the phases never overlapped: 1.55 ms at 1 M x 12 for 0.81 ms of MFMA phase; with four producer waves of two points
 // each the producers were the longer role: 1.90 ms.)
-#ifdef MVBA_DENSE_TRACE  // (timing-only build, tools/dense_trace.sh: where a role's time goes -- work or the chunk barrier)
-__device__ long long g_dense_trace[1024 * 16 * 4];  // per workgroup and wave: role work, barrier wait, total, chunks (shader clock)
-#define DT_NOW() ((long long)__builtin_readcyclecounter())
-#define DT_BARRIER() do { const long long t0_ = DT_NOW(); __syncthreads(); dt_wait += DT_NOW() - t0_; } while (0)
-#else
-#define DT_BARRIER() __syncthreads()
-#endif
 template <int T, bool TABLE>  // TABLE: the records of a point through obs_of (missing observations), otherwise one contiguous range
 __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_schur_dense(const double2 *__restrict__ rec, const double *__restrict__ PB, const int *__restrict__ obs_of,
                                                      long long N, int m, double cu, double *__restrict__ part) {
@@ -1382,13 +1045,10 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
     // ---------------- producer: point pw of every chunk of this workgroup.  (Without the staging -- a lane per (camera, column)
     // fetching its four record slots itself -- the per-lane loads cost more than the staging saves: 1.82 against 1.40 ms.)
     const int pw = wave - NC;
-#ifndef MVBA_DENSE_PRIO
-#define MVBA_DENSE_PRIO 1
-#endif
-    // The producers are the longer role (tools/dense_trace.py: 5,350 cycles of work per chunk against the consumers' 4,480 + 1,400 at
+    // The producers are the longer role (role trace, profiles/r05_dense_form.txt: 5,350 cycles of work per chunk against the consumers' 4,480 + 1,400 at
     // the barrier, 1 M x 12) and, as the later-dispatched waves of their SIMD, the losers of its issue arbitration (older first at
     // equal priority): they ask for the higher priority once, here.
-    if (MVBA_DENSE_PRIO) __builtin_amdgcn_s_setprio(MVBA_DENSE_PRIO);
+    __builtin_amdgcn_s_setprio(1);
     double2 *sR = sScr + (size_t)pw * (m * REC + 8), *sP = sR + (size_t)m * REC;
     constexpr int NPRE = (MMAX * REC + 63) / 64, NIT = (MMAX * 10 + 63) / 64;
     // TWO chunks' records in flight per wave (sets A and B, used in turn): with one, a CU had 8 waves x 1.5 KB outstanding against
@@ -1455,7 +1115,7 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
 #pragma unroll
       for (int u = 0; u < NIT; ++u) {
         const int e = lane + 64 * u, k = e / 10, j = e - 10 * k;
-        if (e < 10 * m && !(MVBA_DENSE_KO & 2)) {
+        if (e < 10 * m) {
           const double2 *r = sR + (size_t)k * REC;
           const double2 x0 = r[0], x1 = r[1], x2 = r[2];
           const double2 cv = r[j == 0 ? 3 : (j < 6 ? (j < 3 ? 0 : j - 3) : (j < 9 ? j - 2 : 7))];
@@ -1486,11 +1146,7 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
     build(0, preA, oidA, prepbA, lvA);
     fetch(ch + 2 * gs, preA, oidA, prepbA, lvA);
     if (TABLE) fetch_ids(ch + 3 * gs);
-#ifdef MVBA_DENSE_TRACE
-    long long dt_wait = 0, dt_n = 0;
-    const long long dt_t0 = DT_NOW();
-#endif
-    DT_BARRIER();
+    __syncthreads();
     // One barrier per chunk, as the consumers; the sets alternate: B holds chunk ch + 1, A chunk ch + 2.  Nothing in the body is
     // conditional (behind `if (ch + gs < n_chunks)` the compiler lost count of the loads in flight and waited vmcnt(0) for both
     // sets): past the last chunk a build writes a chunk of zeros into the buffer nobody reads any more.
@@ -1498,28 +1154,15 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
       build(b ^ 1, preB, oidB, prepbB, lvB);
       fetch(ch + 3 * gs, preB, oidB, prepbB, lvB);
       if (TABLE) fetch_ids(ch + 4 * gs);
-      DT_BARRIER();
+      __syncthreads();
       ch += gs, b ^= 1;
-#ifdef MVBA_DENSE_TRACE
-      ++dt_n;
-#endif
       if (ch >= n_chunks) break;
       build(b ^ 1, preA, oidA, prepbA, lvA);
       fetch(ch + 3 * gs, preA, oidA, prepbA, lvA);
       if (TABLE) fetch_ids(ch + 4 * gs);
-      DT_BARRIER();
+      __syncthreads();
       ch += gs, b ^= 1;
-#ifdef MVBA_DENSE_TRACE
-      ++dt_n;
-#endif
     }
-#ifdef MVBA_DENSE_TRACE
-    if (lane == 0 && blockIdx.x < 1024) {
-      long long *tr = g_dense_trace + ((size_t)blockIdx.x * 16 + wave) * 4;
-      const long long tot = DT_NOW() - dt_t0;
-      tr[0] = tot - dt_wait; tr[1] = dt_wait; tr[2] = tot; tr[3] = dt_n;
-    }
-#endif
     return;
   }
   // ---------------- consumer: tile pairs NC q + wave of the upper triangle (row-major), cameras NC q + wave
@@ -1528,15 +1171,10 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
   for (int q = 0; q < NPW; ++q) acc[q] = mvba_d4{0, 0, 0, 0};
 #pragma unroll
   for (int q = 0; q < NCW; ++q) cacc[q] = mvba_d4{0, 0, 0, 0};
-#ifdef MVBA_DENSE_TRACE
-  long long dt_wait = 0, dt_n = 0;
-  const long long dt_t0 = DT_NOW();
-#endif
-  DT_BARRIER();  // chunk 0 is built
+  __syncthreads();  // chunk 0 is built
   int b = 0;
   for (long long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x, b ^= 1) {
     const double *bG = sG + (size_t)b * 3 * CH * W, *bB = sB + (size_t)b * CH * m * 32, *bS = sSgn + (size_t)b * 3 * CH;
-#if !(MVBA_DENSE_KO & 1)
     switch (wave) {  // (uniform)
       case 0: dense_main_mfma<T, 0, CH>(bG, bS, li, lk, acc); break;
       case 1: dense_main_mfma<T, 1, CH>(bG, bS, li, lk, acc); break;
@@ -1547,8 +1185,6 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
       case 6: dense_main_mfma<T, 6 % NC, CH>(bG, bS, li, lk, acc); break;
       default: dense_main_mfma<T, 7 % NC, CH>(bG, bS, li, lk, acc); break;
     }
-#endif
-#if !(MVBA_DENSE_KO & 8)
 #pragma unroll
     for (int g = 0; g < CH / 2; ++g) {  // the per-camera tiles: rows (point 2 g, x), (2 g, y), (2 g + 1, x), (2 g + 1, y)
       const int pa = 2 * g + (lk >> 1), d = lk & 1;
@@ -1559,19 +1195,8 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
         cacc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v, cacc[q], 0, 0, 0);
       }
     }
-#endif
-    DT_BARRIER();  // this chunk's buffers may be rebuilt, the next chunk's are complete
-#ifdef MVBA_DENSE_TRACE
-    ++dt_n;
-#endif
+    __syncthreads();  // this chunk's buffers may be rebuilt, the next chunk's are complete
   }
-#ifdef MVBA_DENSE_TRACE
-  if (lane == 0 && blockIdx.x < 1024) {
-    long long *tr = g_dense_trace + ((size_t)blockIdx.x * 16 + wave) * 4;
-    const long long tot = DT_NOW() - dt_t0;
-    tr[0] = tot - dt_wait; tr[1] = dt_wait; tr[2] = tot; tr[3] = dt_n;
-  }
-#endif
   double *out = part + (size_t)blockIdx.x * (P + m) * 256;
 #pragma unroll
   for (int q = 0; q < NPW; ++q) {
@@ -1721,9 +1346,6 @@ __device__ __forceinline__ int tix(int r, int c) { return r * (r + 1) / 2 + c; }
 //      B operands are both read from Xb (B operand of column tile ct = A operand of row tile ct)
 // 112 broadcast-FMAs + 32 MFMAs instead of 496 broadcast-FMAs: ~21k -> ~10k cycles per tile.
 constexpr int XBS = 9;  // padded row stride of the 64 x 8 panel buffer
-#ifndef FT_STAMP
-#define FT_STAMP(i)
-#endif
 __device__ __forceinline__ bool factor_tile(const double (*tile)[TS], double (*Zt)[TS], double *Xb, int lane, bool store,
                                             double *__restrict__ Ztile, int nvalid) {
   const int li = lane & 15, lk = lane >> 4;
@@ -1738,7 +1360,6 @@ __device__ __forceinline__ bool factor_tile(const double (*tile)[TS], double (*Z
         acc[rt][ct][q] = (rt < 2) ? tile[row][col] : ((row == col) ? 1.0 : 0.0);
       }
   bool bad = false;
-  FT_STAMP(0);
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     // a. panel columns 8p .. 8p+7: C/D layout -> one row per lane
@@ -1752,9 +1373,7 @@ __device__ __forceinline__ bool factor_tile(const double (*tile)[TS], double (*Z
     double bp[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) bp[j] = Xb[lane * XBS + j];
-    FT_STAMP(1 + 4 * p);
     // b. elimination inside the panel
-#ifndef MVBA_FACTOR_SINGLE  // (define it for the one-pivot-per-step elimination: tools/microbench/factor_tile_test.hip times both)
     // Two pivots per step: with a = B[k][k], b = B[k+1][k], c = B[k+1][k+1] the two reciprocal roots
     // 1/l11 = rsq(a) and 1/l22 = rsq(a c - b^2) * l11 do not depend on each other, so the serial chain
     // (rsq + two Newton steps + broadcast) is walked 16 times per tile instead of 32.  a c - b^2
@@ -1777,23 +1396,6 @@ __device__ __forceinline__ bool factor_tile(const double (*tile)[TS], double (*Z
       for (int j = k + 2; j < 8; ++j)
         bp[j] -= bp[k] * readlane_d(bp[k], 8 * p + j) + bp[k + 1] * readlane_d(bp[k + 1], 8 * p + j);
     }
-#else
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const double piv = readlane_d(bp[k], 8 * p + k);
-      bad |= !(piv > 0.0);
-      // 1/sqrt(piv): v_rsq_f64 seed + two Newton steps (full double precision) instead of the
-      // ~40-instruction sqrt and divide expansions, which sit on the serial path 32 times per tile
-      double y = __builtin_amdgcn_rsq(piv);
-      y = y * (1.5 - 0.5 * piv * y * y);
-      y = y * (1.5 - 0.5 * piv * y * y);
-      bp[k] = (lane == 8 * p + k) ? piv * y : bp[k] * y;
-      // entries above the diagonal (column > row) hold values that are never read: no predicate needed
-#pragma unroll
-      for (int j = k + 1; j < 8; ++j) bp[j] -= bp[k] * readlane_d(bp[k], 8 * p + j);
-    }
-#endif
-    FT_STAMP(2 + 4 * p);
     // c. finished columns back to Xb; rows 32..63 are rows of L^-T
 #pragma unroll
     for (int j = 0; j < 8; ++j) Xb[lane * XBS + j] = bp[j];
@@ -1808,7 +1410,6 @@ __device__ __forceinline__ bool factor_tile(const double (*tile)[TS], double (*Z
     }
     // d. all later columns: acc[rt][ct] -= B[16 rt .., panel] L[16 ct .., panel]^T
     wave_sync();
-    FT_STAMP(3 + 4 * p);
     if (p < 3) {
       double xa[4][2];
 #pragma unroll
@@ -1824,7 +1425,6 @@ __device__ __forceinline__ bool factor_tile(const double (*tile)[TS], double (*Z
             acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(-xa[rt][t], xa[ct][t], acc[rt][ct], 0, 0, 0);
       wave_sync();  // the next panel overwrites Xb
     }
-    FT_STAMP(4 + 4 * p);
   }
   return !bad;
 }
@@ -2328,41 +1928,15 @@ __global__ __launch_bounds__(256) void k_chol_backsolve(double *M, int ld, int D
   chol_backsolve_body(M, ld, D, m, gauge_axis, Ztiles, Lblk, dxi_full, jS, jE, jE2, blockIdx.x, threadIdx.x);
 }
 
-// Device-wide barrier of a persistent grid (every workgroup co-resident: at most one per CU).  Every
-// workgroup reaches every barrier (the counts depend on D only), and a barrier gives up after `max_polls`
-// polls (2^22 by default; flag bit 8 -> the host redoes the solve with one launch per super-block) instead of
-// spinning for ever, so the grid always drains.
-__device__ __forceinline__ void grid_barrier(unsigned *bar, unsigned target, int *flag, unsigned max_polls) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this wave's global writes are visible device-wide
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0;
-    while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > max_polls) {
-        atomicOr(flag, 8);
-        break;
-      }
-    }
-  }
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // and the other workgroups' writes are visible to this wave
-}
-
-#ifdef MVBA_BS_TRACE  // timing-only build (tools/bs_trace.py): 100 MHz stamps of every chain workgroup of the last launch
-__device__ long long g_bs_trace[8 * 256];
-#define BS_STAMP(s, i) do { if (threadIdx.x == 0) g_bs_trace[8 * (s) + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define BS_STAMP(s, i)
-#endif
-// Point-to-point version of the same (round 4): thread 0 of a workgroup waits until a progress word has reached `target`
-// (words only grow).  No device-wide fences: an agent-scope release / acquire pair is a write-back / invalidate of the whole
-// L2 of the XCD (1.7 + 1.5 us of an 11.6 us chain step with 140 workgroups doing the same, tools/bs_trace.py), and the only
+// Hand-overs between the workgroups of a persistent grid (every workgroup co-resident: at most one per CU), point to point
+// (round 4): thread 0 of a workgroup waits until a progress word has reached `target` (words only grow).  No device-wide
+// fences: an agent-scope release / acquire pair is a write-back / invalidate of the whole L2 of the XCD (1.7 + 1.5 us of an
+// 11.6 us chain step with 140 workgroups doing the same, profiles/r04_backsolve_chain_trace_d4493.txt), and the only
 // data that travels between workgroups here is the vector y.  So every access to y inside this kernel is an agent-scope
 // atomic (sc1: stores write through to memory, loads do not hit a stale line), a producer's waves wait for their stores
 // (s_waitcnt vmcnt(0)), meet at a barrier, and then thread 0 stores the word; the consumer polls it,
-// passes a barrier and loads.  Gives up like grid_barrier does (and at once when somebody else already has), so the grid drains.
+// passes a barrier and loads.  A wait gives up after `max_polls` polls (2^22 by default), and at once when somebody else already
+// has: flag bit 8, the host redoes the solve with one launch per super-block.  So the grid always drains.
 template <int SLEEP>
 __device__ __forceinline__ void flow_wait(const unsigned *word, unsigned target, int *flag, unsigned max_polls) {
   unsigned spins = 0;
@@ -2386,8 +1960,7 @@ __device__ __forceinline__ void flow_post(unsigned *word, unsigned value) {
 __device__ __forceinline__ double flow_load(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void flow_store(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// ---- L^T x = y for all super-blocks in ONE persistent launch (last block first), S - 1 device-wide
-// barriers instead of S launches.  Step s (x_{s+1} known):
+// ---- L^T x = y for all super-blocks in ONE persistent launch (last block first) instead of S launches.  Step s (x_{s+1} known):
 //   workgroup s ("chain" of block s)
 //       y_s -= (rows of the block above)^T x_{s+1}; then the block's four tiles from the bottom:
 //       x_t = Z_t y_t (Z = L_tt^-T from the factorisation), y_{t' < t} -= L[t][t']^T x_t.
@@ -2397,17 +1970,19 @@ __device__ __forceinline__ void flow_store(double *p, double v) { __hip_atomic_s
 //   workgroups >= S ("bulk")
 //       y[c] -= (rows of block s+1)^T x_{s+1} for the columns left of block s, 32 columns x 8 row
 //       chunks per workgroup: one batch of 16 loads per thread, LDS reduction.
-// One barrier per step: x_s must reach the next chain and the bulk workgroups, their updates the chain.
-// FLOW (round 4, the default): no device-wide barriers.  sync[0] = number of x blocks published (chain s posts S - s);
+// x_s must reach the next chain and the bulk workgroups, their updates the chain, with no device-wide barrier.  sync[0] = number of x blocks published (chain s posts S - s);
 // sync[1 + g] = number of x blocks applied to the 32-column group g, whose owner among the bulk workgroups applies them
 // last block first.  Chain s waits for x_{s+1} and for x_{s+2} on its own four groups -- applied a whole chain step
 // earlier, so it practically never waits for the bulk -- and a bulk workgroup for the x it is about to apply.  With nobody
 // else in a barrier the bulk can be one workgroup per group (140 at D = 4493 instead of 16: 11 us of a 14 us step were
 // their share of the matrix at ~25 GB/s each).
+// (FLOW = true is the only form: round 2's device-wide-barrier form, FLOW = false, is gone.  The parameter stays so that the
+// kernel keeps the symbol csrc/check_isa.py, the tests and the committed kernel profiles name: k_chol_backsolve_all<true>.)
 template <bool FLOW>
 __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M, int ld, int D, int m, int gauge_axis,
                                                                       const double *Ztiles, const double *Lblk_all, double *dxi_full,
                                                                       int *flag, unsigned *bar, unsigned max_polls) {
+  static_assert(FLOW, "only the point-to-point form of the back-substitution exists");
   extern __shared__ double lds[];
   const int G = gridDim.x, bid = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double *y = M + (size_t)D * ld;
@@ -2416,11 +1991,9 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
   double (*Ls)[NB][TS] = reinterpret_cast<double (*)[NB][TS]>(lds + 4 * NB * TS);  // [6]: in-block tile (r, c < r) at r (r - 1) / 2 + c
   double (*Tt)[TS] = reinterpret_cast<double (*)[TS]>(lds + 10 * NB * TS);        // scratch tile of the block inverse
   double *ys = lds + 11 * NB * TS, *part = ys + SBW, *xs = part + 3 * SBW;         // part[3][SBW]; bulk: red[8][32], then x
-  unsigned epoch = 0;
   if (bid < S) {
     // ================= chain of block s = bid
     const int s = bid, jS = s * SBW, jE = min(jS + SBW, D), jE2 = min(jE + SBW, D), ns = jE - jS, np = jE2 - jE;
-    BS_STAMP(s, 0);
     // ---- static operands, one batch.  Every load is "uniform base + one per-thread offset", so the
     // addresses live in SGPRs and the batch fits the register file.
     const double *Lblk = Lblk_all + (size_t)s * SBW * SBW;
@@ -2453,12 +2026,12 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
         const int w = tid + NT * ps;
         if (w < NB * NB) Zs[tile][w >> 5][w & 31] = zl[tile][ps];  // Ls follows Zs: tile 4 + e lands in Ls[e]
       }
-    // ---- FLOW, blocks with three chain steps of waiting ahead of them: the block's whole L_ss^-T instead of a walk over its
-    // four tiles at the step (2.8 of 5.7 us, tools/bs_trace.py).  From x_r = Z_r (y_r - sum_{c > r} L_cr^T x_c):
+    // ---- blocks with three chain steps of waiting ahead of them: the block's whole L_ss^-T instead of a walk over its
+    // four tiles at the step (2.8 of 5.7 us, profiles/r04_backsolve_chain_trace_d4493.txt).  From x_r = Z_r (y_r - sum_{c > r} L_cr^T x_c):
     //   x_r = sum_{c >= r} W_rc y_c,  W_rr = Z_r,  W_rc = -Z_r sum_{r < k <= c} L_kr^T W_kc,
     // six off-diagonal tiles, each two MFMA passes (the sum into the scratch tile, then -Z_r times it) on four waves, one
     // 16 x 16 quarter each; W_rc lands in the slot of L_cr, which nobody needs any more in this order.
-    const bool inverse = FLOW && (S - 1 - s) >= 3;
+    const bool inverse = (S - 1 - s) >= 3;
     if (inverse) {
       __syncthreads();  // the tiles are in LDS
       const int li = lane & 15, lk = lane >> 4, qi = (wave >> 1) & 1, qj = wave & 1;  // waves 0..3: quarter (qi, qj)
@@ -2507,31 +2080,24 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
       wrow[ct] = (ct < r) ? &Tt[ii][0] : (ct == r) ? &Zs[r][ii][0] : &Ls[ct * (ct - 1) / 2 + r][ii][0];
     }
     // ---- wait for the step
-    BS_STAMP(s, 1);
-    if (FLOW) {
-      if (s < S - 1) {
-        if (tid == 0) {
-          if (s + 2 <= S - 1)  // (posted a whole chain step ago: checked first, while x_{s+1} is still on its way)
-            for (int q = 0; q < 4; ++q) flow_wait<1>(bar + 1 + 4 * s + q, (unsigned)(S - (s + 2)), flag, max_polls);
-          flow_wait<0>(bar, (unsigned)(S - 1 - s), flag, max_polls);
-        }
-        BS_STAMP(s, 2);
-        __syncthreads();
-        BS_STAMP(s, 3);
+    if (s < S - 1) {
+      if (tid == 0) {
+        if (s + 2 <= S - 1)  // (posted a whole chain step ago: checked first, while x_{s+1} is still on its way)
+          for (int q = 0; q < 4; ++q) flow_wait<1>(bar + 1 + 4 * s + q, (unsigned)(S - (s + 2)), flag, max_polls);
+        flow_wait<0>(bar, (unsigned)(S - 1 - s), flag, max_polls);
       }
-    } else
-      for (int t = S - 1; t > s; --t) grid_barrier(bar, ++epoch * G, flag, max_polls);
-    // x_{s+1} (published by chain s+1 before the barrier) and y_s (complete but for the panel's share)
-    const double yv = (tid < ns) ? (FLOW ? flow_load(y + jS + tid) : y[jS + tid]) : 0.0;
-    if (FLOW) {  // one sc1 load per element of x_{s+1}, the rest reads LDS (43 sc1 loads per thread: 2.2 us of a step)
-      if (tid < SBW) xs[tid] = (tid < np) ? flow_load(y + jE + tid) : 0.0;
       __syncthreads();
     }
+    // x_{s+1} (published by chain s+1 before its progress word) and y_s (complete but for the panel's share)
+    const double yv = (tid < ns) ? flow_load(y + jS + tid) : 0.0;
+    // one sc1 load per element of x_{s+1}, the rest reads LDS (43 sc1 loads per thread: 2.2 us of a step)
+    if (tid < SBW) xs[tid] = (tid < np) ? flow_load(y + jE + tid) : 0.0;
+    __syncthreads();
     double sa = 0.0, sb = 0.0;
     if (np > 0) {
       double xv[NPN];
 #pragma unroll
-      for (int i = 0; i < NPN; ++i) xv[i] = (ph + 3 * i < np) ? (FLOW ? xs[ph + 3 * i] : y[jE + ph + 3 * i]) : 0.0;
+      for (int i = 0; i < NPN; ++i) xv[i] = (ph + 3 * i < np) ? xs[ph + 3 * i] : 0.0;
 #pragma unroll
       for (int i = 0; i + 1 < NPN; i += 2) {
         sa += pn[i] * xv[i];
@@ -2543,7 +2109,6 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
     __syncthreads();
     if (tid < SBW) ys[tid] = (tid < ns) ? yv - part[tid] - part[SBW + tid] - part[2 * SBW + tid] : 0.0;
     __syncthreads();
-    BS_STAMP(s, 4);
     if (inverse) {  // x = W y: row i = tid & 127, the columns c with c % 3 == tid / 128
       // (tile bases per thread, the column offsets compile-time constants -- one code path per third: 86 LDS reads with
       // immediate offsets and 43 FMAs; with the addresses computed per element this took as long as the walk it replaces)
@@ -2588,17 +2153,11 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
       __syncthreads();
     }
     if (tid < ns) {
-      if (FLOW) flow_store(y + jS + tid, ys[tid]);
-      else y[jS + tid] = ys[tid];
+      flow_store(y + jS + tid, ys[tid]);
       dxi_full[keep_index(jS + tid, gauge_axis)] = ys[tid];
     }
     if (s == 0 && tid < 7) dxi_full[tid < 6 ? 3 + tid : 12 + gauge_axis] = 0.0;  // the removed (gauge) parameters
-    BS_STAMP(s, 5);
-    if (FLOW) {
-      if (s > 0) flow_post(bar, (unsigned)(S - s));
-      BS_STAMP(s, 6);
-    } else
-      for (int t = s; t > 0; --t) grid_barrier(bar, ++epoch * G, flag, max_polls);
+    if (s > 0) flow_post(bar, (unsigned)(S - s));
     return;
   }
   // ================= bulk: at step s, columns left of block s, rows of block s+1
@@ -2607,14 +2166,13 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
   const int cj = tid & 31, ch = tid >> 5, nbulk = G - S;
   for (int s = S - 1; s >= 0; --s) {
     const int jS = s * SBW, jE = min(jS + SBW, D), jE2 = min(jE + SBW, D), np = jE2 - jE, ngrp = (jS + 31) / 32;
-    if (FLOW) {  // x_{s+1} -> the groups this workgroup owns, the rightmost (the next chain's) first
-      if (np <= 0 || bid - S >= ngrp) continue;  // (uniform; owned groups only become fewer as s falls)
-      if (tid == 0) flow_wait<8>(bar, (unsigned)(S - 1 - s), flag, max_polls);  // (the bulk has a chain step of slack: polls at leisure)
-      __syncthreads();
-    }
+    // x_{s+1} -> the groups this workgroup owns, the rightmost (the next chain's) first
+    if (np <= 0 || bid - S >= ngrp) continue;  // (uniform; owned groups only become fewer as s falls)
+    if (tid == 0) flow_wait<8>(bar, (unsigned)(S - 1 - s), flag, max_polls);  // (the bulk has a chain step of slack: polls at leisure)
+    __syncthreads();
     if (np > 0)
       for (int g0 = bid - S; g0 < ngrp; g0 += nbulk) {
-        const int g = FLOW ? (bid - S) + ((ngrp - 1 - (bid - S)) / nbulk) * nbulk - (g0 - (bid - S)) : g0;
+        const int g = (bid - S) + ((ngrp - 1 - (bid - S)) / nbulk) * nbulk - (g0 - (bid - S));
         const int c = 32 * g + cj;
         double lv[16], xv[16];
 #pragma unroll
@@ -2622,9 +2180,9 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
           const int r = 16 * ch + u;
           const bool ok = act && c < jS && r < np;
           lv[u] = ok ? M[(size_t)(jE + r) * ld + c] : 0.0;
-          xv[u] = ok ? (FLOW ? flow_load(y + jE + r) : y[jE + r]) : 0.0;
+          xv[u] = ok ? flow_load(y + jE + r) : 0.0;
         }
-        const double yc = (tid < 32 && c < jS) ? (FLOW ? flow_load(y + c) : y[c]) : 0.0;
+        const double yc = (tid < 32 && c < jS) ? flow_load(y + c) : 0.0;
         double s0 = 0.0, s1 = 0.0;
 #pragma unroll
         for (int u = 0; u < 16; u += 2) {
@@ -2637,13 +2195,11 @@ __global__ __launch_bounds__(SUPER_THREADS) void k_chol_backsolve_all(double *M,
           double tot = 0.0;
 #pragma unroll
           for (int k = 0; k < 8; ++k) tot += red[k * 32 + cj];
-          if (FLOW) flow_store(y + c, yc - tot);
-          else y[c] = yc - tot;
+          flow_store(y + c, yc - tot);
         }
-        if (FLOW) flow_post(bar + 1 + g, (unsigned)(S - 1 - s));
+        flow_post(bar + 1 + g, (unsigned)(S - 1 - s));
         __syncthreads();
       }
-    if (!FLOW && s > 0) grid_barrier(bar, ++epoch * G, flag, max_polls);
   }
 }
 
@@ -3085,7 +2641,7 @@ __global__ __launch_bounds__(64 * IDX_WAVES) void k_idx_count(long long N, int m
   }
   const long long a0 = w * chunk, a1 = min(N, a0 + chunk);
   for (long long ai = a0; ai < a1; ++ai) {
-    const long long a = order ? order[ai] : ai;  // (the sweep order of the points: see `point_order` in mvba_create)
+    const long long a = order ? order[ai] : ai;  // (a sweep order of the points; mvba_create sweeps them in their natural order and passes none)
     const long long o0 = pt_ptr[a];
     const int d = (int)(pt_ptr[a + 1] - o0);
     for (int i = 0; i < d; ++i) {
@@ -3245,18 +2801,17 @@ __global__ void k_idx_interleave(long long n_steps, const int *__restrict__ st_k
 }  // namespace
 
 // ------------------------------------------------------------------ host side
-enum { SCHUR_STRIP = 0, SCHUR_PAIRS = 1, SCHUR_SLOTS = 2, SCHUR_DENSE = 3 };
+enum { SCHUR_PAIRS = 1, SCHUR_SLOTS = 2, SCHUR_DENSE = 3 };  // (0 was round 1's camera-strip form: the values are mvba_get_info's)
 struct mvba_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   long long N = 0, nobs = 0;
-  int m = 0, gauge_axis = 0, D = 0, ld = 0, nsp = 0;
+  int m = 0, gauge_axis = 0, D = 0, ld = 0;
   double f0 = 1.0;
   // topology
   long long *d_pt_ptr = nullptr;
   int *d_cam = nullptr, *d_obs_pt = nullptr;
   double2 *d_xy = nullptr;
-  int4 *d_csc = nullptr;
   int *d_tiles = nullptr;  // K1 point-aligned wave tiles
   int *d_tile_slot = nullptr;      // points with more than 64 observations: slot of every piece tile in d_PLsplit,
   int4 *d_splits = nullptr;        // (point, first slot, pieces) per such point
@@ -3264,32 +2819,23 @@ struct mvba_handle {
   int n_splits = 0;
   int n_tiles = 0;
   bool any_split = false;
-  long long *d_chunk_ptr = nullptr;
-  int nchunks = 1, lseg = 0, nseg = 1, schur_threads = 768, k1_threads = 512;
+  int k1_threads = 512;
   // pair-major Schur index (k_schur_pairs): items sorted by (k, l, point), units, per-XCD work queues
-  bool use_pairs = true;              // pair-major index present (schur_mode != SCHUR_STRIP)
-  int schur_mode = 2;                 // SCHUR_STRIP / SCHUR_PAIRS / SCHUR_SLOTS (see k_schur_slots)
-  long long slot_skew = 12288;        // bounded skew of the slot form's step merge, in observations
-  long long slot_window = 1LL << 40;  // ... and the window in which all waves of a range take equally many steps (off)
+  bool use_pairs = true;              // pair-major index present (schur_mode != SCHUR_DENSE)
+  int schur_mode = 2;                 // SCHUR_PAIRS / SCHUR_SLOTS (see k_schur_slots) / SCHUR_DENSE
   long long n_items = 0, n_items_offdiag = 0, n_slot_items = 0;
   int n_units = 0, rccl_version = 0, q_max = 0, n_waves = 0, slot_nR = 8, slot_nseg = 0, slot_rounds = 1, slot_groups = 1;
   long long *d_range_o0 = nullptr;    // slot form: first observation of every point range (the record base of its waves)
-  long long slot_seg = 8192;          // pacing segment of the slot form, in observations
-  bool slot_pace = true;
-  int slot_lag = 4;                   // a wave enters segment j only when all waves of its range have left segment j - lag
   int *d_seg_end = nullptr, *d_prog = nullptr;
   bool check_solve = false;           // MVBA_CHECK_SOLVE=1: every accepted dense solve is checked on the host against the packed system it solved
   double check_solve_tol = 1e-8;      // (MVBA_CHECK_SOLVE=<t> with 0 < t < 1: that tolerance -- the tests ask for an impossible one to see the check fire)
   bool gcam = false;                  // more than LDS_CAMERAS cameras: the kernels read the camera tables from device memory (d_cam18, d_dxi10)
   double *d_cam18 = nullptr, *d_dxi10 = nullptr;
   bool index_on_device = false;       // the Schur index was built by the k_idx_* kernels (nothing to upload)
-  long long *d_trace = nullptr;       // -DMVBA_SLOT_TRACE builds with MVBA_SLOT_TRACE=<file>: per-wave timings of the last launch
   int4 *d_wdesc = nullptr;
   int *d_it_x = nullptr;              // slot form: the step-major index, 64 ints per step (k[21] | l[21] | a[21] | pad)
   int *d_wunits = nullptr;
-  // experiment knobs, read from the environment ONCE in mvba_create (tools/README.md lists them)
-  bool pair_static = true, force_big = false;
-  int backsub_lanes = 0;
+  bool force_big = false;             // MVBA_FORCE_BIG: the 64-bit-offset kernels at any size
   int *d_it_k = nullptr, *d_it_l = nullptr, *d_it_a = nullptr, *d_unit_ptr = nullptr, *d_q_ptr = nullptr, *d_q_units = nullptr,
       *d_q_head = nullptr;
   int4 *d_units = nullptr;
@@ -3318,9 +2864,8 @@ struct mvba_handle {
   unsigned *d_bar = nullptr;
   int n_cu = 1;
   bool chol_onepass = true;  // L^T x = y as one persistent launch (MVBA_CHOL=launches: one launch per super-block)
-  bool chol_flow = true;     // ... synchronised point to point (MVBA_CHOL=barriers: round 2's device-wide barriers)
   int trail64_min = 200;     // trailing updates of at least this many 64 x 64 workgroups run k_chol_trail64 (MVBA_TRAIL64_MIN)
-  unsigned barrier_polls = 1u << 22;  // what a device-wide barrier of that launch polls before it gives up (MVBA_CHOL_BARRIER_POLLS)
+  unsigned barrier_polls = 1u << 22;  // what a wait of that launch polls before it gives up (MVBA_CHOL_BARRIER_POLLS)
   // comm
   ncclComm_t comm = nullptr;
   mvba_host_allreduce_fn host_ar = nullptr;  // host-staged transport (mvba_comm_init_host) instead of RCCL
@@ -3511,20 +3056,55 @@ __global__ __launch_bounds__(256) void k_xy_from_planes(const double2 *__restric
   if (a < N) xy[a * m + k] = planes[(long long)k * N + a];
 }
 
+// Tuning of the slot form's host-built schedule (k_schur_slots), in observations of a point range
+constexpr long long SLOT_SKEW = 12288;  // bounded skew of the step merge
+constexpr long long SLOT_SEG = 8192;    // pacing segment
+constexpr int SLOT_LAG = 4;             // a wave enters segment j only when all waves of its range have left segment j - lag
+
+// The environment knobs of mvba_create (README.md lists them), read once.  Each pins a choice the engine otherwise makes
+// by itself, or turns on a diagnostic that changes no result.
+struct CreateKnobs {
+  bool schur_set = false;                      // MVBA_SCHUR set at all (any value keeps a fully visible scene off the dense form
+  bool schur_slots = false, schur_pairs = false, schur_dense = false;  // ... unless it is `dense`)
+  bool index_host = false, index_global = false;  // MVBA_INDEX=host | global: where the Schur index is built
+  bool force_big = false;                      // MVBA_FORCE_BIG
+  int slot_groups = 0;                         // MVBA_SLOT_GROUPS (0: by the L2 footprint)
+  bool chol_launches = false;                  // MVBA_CHOL=launches
+  int trail64_min = 200;                       // MVBA_TRAIL64_MIN
+  unsigned barrier_polls = 1u << 22;           // MVBA_CHOL_BARRIER_POLLS
+  bool check_solve = false;                    // MVBA_CHECK_SOLVE=1 (or a tolerance in (0, 1))
+  double check_solve_tol = 1e-8;
+  bool timing = false;                         // MVBA_CREATE_TIMING=1: wall time of mvba_create's stages on stderr
+};
+
+CreateKnobs read_create_knobs() {
+  CreateKnobs k;
+  auto is = [](const char *ev, const char *v) { return ev && !strcmp(ev, v); };
+  const char *schur = getenv("MVBA_SCHUR");
+  k.schur_set = schur != nullptr;
+  k.schur_slots = is(schur, "slots");
+  k.schur_pairs = is(schur, "pairs");
+  k.schur_dense = is(schur, "dense");
+  const char *index = getenv("MVBA_INDEX");
+  k.index_host = is(index, "host");
+  k.index_global = is(index, "global");
+  k.force_big = getenv("MVBA_FORCE_BIG") != nullptr;
+  if (const char *ev = getenv("MVBA_SLOT_GROUPS")) k.slot_groups = std::max(1, atoi(ev));
+  k.chol_launches = is(getenv("MVBA_CHOL"), "launches");
+  if (const char *ev = getenv("MVBA_TRAIL64_MIN")) k.trail64_min = std::max(0, atoi(ev));
+  if (const char *ev = getenv("MVBA_CHOL_BARRIER_POLLS")) k.barrier_polls = (unsigned)std::max(0LL, atoll(ev));
+  if (const char *ev = getenv("MVBA_CHECK_SOLVE")) {
+    const double v = atof(ev);
+    k.check_solve = v != 0.0;
+    if (v > 0.0 && v < 1.0) k.check_solve_tol = v;
+  }
+  k.timing = getenv("MVBA_CREATE_TIMING") != nullptr;
+  return k;
+}
+
 }  // namespace
 
 extern "C" {
-#ifdef MVBA_DENSE_TRACE
-int mvba_dense_trace_read(long long *out, int n) {  // (timing-only build)
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dense_trace), sizeof(long long) * n, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 3;
-}
-#endif
-#ifdef MVBA_BS_TRACE
-int mvba_debug_bs_trace(long long *out /* [8 * 256] */) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bs_trace), sizeof(long long) * 8 * 256) == hipSuccess ? 0 : 1;
-}
-#endif
-
 
 const char *mvba_version(void) { return "mvba 0.2 (gfx950)"; }
 const char *mvba_last_error(void) { return g_err.c_str(); }
@@ -3543,22 +3123,16 @@ int mvba_device_count(int32_t *count) {
 
 int mvba_create(const mvba_problem *p, mvba_handle **out) {
   if (!p || !out) return fail(MVBA_ERR_BADARG, "null argument");
-  // MVBA_CREATE_TRACE=1: wall time of this function's stages to stderr (tools/time_pipeline.py: the engine's construction is a
+  const CreateKnobs knobs = read_create_knobs();
+  // MVBA_CREATE_TIMING=1: wall time of this function's stages on stderr (tools/time_create.py; the engine's construction is a
   // third of the reference's pipeline at 1 M points x 12 images)
-  struct Trace {
-    bool on = getenv("MVBA_CREATE_TRACE") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    std::string s;
-    void mark(const char *label) {
-      if (!on) return;
-      const auto n = std::chrono::steady_clock::now();
-      char buf[96];
-      snprintf(buf, sizeof buf, " %s %.1f ms;", label, std::chrono::duration<double, std::milli>(n - t).count());
-      s += buf;
-      t = n;
-    }
-    ~Trace() { if (on) fprintf(stderr, "mvba_create:%s\n", s.c_str()); }
-  } trace;
+  auto t_last = std::chrono::steady_clock::now();
+  auto lap = [&](const char *what) {
+    if (!knobs.timing) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "mvba_create: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    t_last = now;
+  };
   if (p->n_points < 0 || p->n_images < 2 || p->n_obs < 0 || !p->pt_ptr || (p->n_obs && (!p->cam_idx || !p->xy)))
     return fail(MVBA_ERR_BADARG, "bad problem sizes or null arrays (need n_images >= 2)");
   if (p->gauge_axis != 0 && p->gauge_axis != 1) return fail(MVBA_ERR_BADARG, "gauge_axis must be 0 or 1");
@@ -3581,18 +3155,8 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     return fail(MVBA_ERR_BADARG, "n_obs and n_points per handle must be < 2^31");
   const long long N = p->n_points, nobs = p->n_obs;
   const int m = p->n_images;
-  // MVBA_CREATE_TIMING=1: phase times of this call on stderr (a diagnostic, read once here)
-  const bool timing = getenv("MVBA_CREATE_TIMING") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "mvba_create: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  // validate + build point-of-observation and the camera-major index
+  // validate + build point-of-observation
   std::vector<int> obs_pt(nobs);
-  std::vector<long long> csc_ptr(m + 1, 0);
   for (long long a = 0; a < N; ++a) {
     const long long o0 = p->pt_ptr[a], o1 = p->pt_ptr[a + 1];
     if (o1 < o0 || o1 > nobs) return fail(MVBA_ERR_BADARG, "pt_ptr not monotone / out of range");
@@ -3601,23 +3165,9 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       if (k < 0 || k >= m) return fail(MVBA_ERR_BADARG, "cam_idx out of range");
       if (o > o0 && p->cam_idx[o - 1] >= k) return fail(MVBA_ERR_BADARG, "cam_idx must ascend within a point");
       obs_pt[o] = (int)a;
-      csc_ptr[k + 1]++;
     }
   }
-  trace.mark("validation pass");
-  for (int k = 0; k < m; ++k) csc_ptr[k + 1] += csc_ptr[k];
-  // the camera-major index belongs to the strip kernel alone (round 1's K3: MVBA_SCHUR=strip, or more cameras than a
-  // pair id holds): 160 MB at config 3 that the other forms never read
-  const bool want_strip = (getenv("MVBA_SCHUR") && !strcmp(getenv("MVBA_SCHUR"), "strip")) || m > 65535;
-  std::vector<int4> csc(want_strip ? nobs : 0);
-  if (want_strip) {
-    std::vector<long long> fill(csc_ptr.begin(), csc_ptr.end() - 1);
-    for (long long a = 0; a < N; ++a)
-      for (long long o = p->pt_ptr[a]; o < p->pt_ptr[a + 1]; ++o)
-        csc[fill[p->cam_idx[o]]++] = make_int4((int)o, (int)a, (int)(p->pt_ptr[a + 1] - o), 0);
-  }
-
-  lap("validate, obs_pt, csc");
+  lap("validate, obs_pt");
   // K1 wave tiles: whole points packed greedily into <= 64 observations; a point with more than
   // 64 observations is cut into pieces whose tiles are flagged by a complemented (negative) start
   std::vector<int> tiles, tile_slot;
@@ -3660,7 +3210,6 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
   }
   h->N = N; h->nobs = nobs; h->m = m; h->gauge_axis = p->gauge_axis; h->f0 = p->f0; h->D = 9 * m - 7; h->ld = (h->D + 3) & ~3;
   h->gcam = m > LDS_CAMERAS;
-  trace.mark("K1 tiles, device");
 #define TRY(x) do { int rc_ = (x); if (rc_) { mvba_destroy(h); return rc_; } } while (0)
 #define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { mvba_destroy(h); return fail(MVBA_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
   // the topology goes up first: the Schur index is built from it on the device
@@ -3669,20 +3218,11 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
   TRY(dmalloc(&h->d_cam, nobs));
   TRYH(hipMemcpy(h->d_pt_ptr, p->pt_ptr, sizeof(long long) * (N + 1), hipMemcpyHostToDevice));
   if (nobs) TRYH(hipMemcpy(h->d_cam, p->cam_idx, sizeof(int) * nobs, hipMemcpyHostToDevice));
-
-  trace.mark("topology upload");
-  // Schur launch geometry (measured sweep at config 3, profiles/): ~800 camera-list entries per
-  // block is the optimum (tail balance vs strip flush); small problems still get >= 2048 blocks
-  // as long as a block keeps >= 128 entries.
-  const long long avg_len = std::max<long long>(1, nobs / m);
-  h->nchunks = (int)std::max<long long>(1, std::max<long long>(avg_len / 800,
-                                                               std::min<long long>((2048 + m - 1) / m, avg_len / 128)));
-  // tuning overrides (experiments only)
-  if (const char *ev = getenv("MVBA_SCHUR_THREADS")) h->schur_threads = std::max(64, std::min(768, atoi(ev) / 64 * 64));
+  lap("device, topology upload");
   {  // K1: the waves of a block share one camera table in LDS and bring 8 KiB of staging each.  Up to ~100 cameras two blocks
     // of 8 waves fill a CU (16 waves: the register limit); beyond that ONE block fits and its size decides the occupancy --
     // the smallest block that reaches the most waves per CU (200 cameras: 16 waves, 0.96 -> 0.70 ms at 1 M points x 10 %;
-    // 300: 14, 0.41 -> 0.32-0.37; 500: 11, config 4's shard 1.53-1.58 -> 1.32-1.36; tools/sweep_k1.sh)
+    // 300: 14, 0.41 -> 0.32-0.37; 500: 11, config 4's shard 1.53-1.58 -> 1.32-1.36)
     const size_t table = h->gcam ? 0 : (size_t)((m * CAM_LDS + 1) & ~1) * sizeof(double), per_wave = 64 * 2 * REC * sizeof(double);
     int best_w = 8, best_tot = 0;
     for (int w = 8; w <= 16; ++w) {
@@ -3693,50 +3233,12 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     }
     h->k1_threads = 64 * best_w;
   }
-  if (const char *ev = getenv("MVBA_K1_THREADS")) h->k1_threads = std::max(64, std::min(1024, atoi(ev) / 64 * 64));
-  if (const char *ev = getenv("MVBA_SCHUR_CHUNKS")) h->nchunks = std::max(1, atoi(ev));
-  const size_t lds_cap = 150 * 1024;
-  h->lseg = (int)std::min<size_t>(m, (lds_cap / 8 - 9) / 81);
-  if (const char *ev = getenv("MVBA_SCHUR_LSEG")) h->lseg = std::max(1, std::min(h->lseg, atoi(ev)));
-  h->nseg = (m + h->lseg - 1) / h->lseg;
-  h->nsp = (h->nseg >= 2 && h->nseg <= 4 && m < 1024) ? h->nseg : 0;
-  if (h->nsp && want_strip) {  // segment boundaries inside each entry's remaining (camera-sorted) observations
-    for (long long e = 0; e < nobs; ++e) {
-      const int *cb = p->cam_idx + csc[e].x, *ce = cb + csc[e].z;
-      int w = 0;
-      for (int sgi = 1; sgi < h->nsp; ++sgi)
-        w |= (int)(std::lower_bound(cb, ce, *cb + sgi * h->lseg) - cb) << (10 * (sgi - 1));
-      csc[e].w = w;
-    }
-  }
-  std::vector<long long> chunk_ptr(want_strip ? (size_t)m * (h->nchunks + 1) : 0);
-  for (int k = 0; k < m && want_strip; ++k) {
-    const int4 *b = csc.data() + csc_ptr[k], *e = csc.data() + csc_ptr[k + 1];
-    for (int c = 0; c <= h->nchunks; ++c) {
-      const long long a_lo = (long long)((__int128)N * c / h->nchunks);
-      const int4 *it = std::lower_bound(b, e, a_lo, [](const int4 &r, long long v) { return r.y < v; });
-      chunk_ptr[(size_t)k * (h->nchunks + 1) + c] = it - csc.data();
-    }
-  }
-
-  lap("strip chunk index");
   // ---- pair-major Schur index (see k_schur_pairs).  Items (obs of k, obs of l, point) for every
   // pair k <= l of a point's cameras, counting-sorted by pair, ascending point inside a pair.
-  if (const char *ev = getenv("MVBA_SCHUR"))
-    h->schur_mode = !strcmp(ev, "strip") ? SCHUR_STRIP : (!strcmp(ev, "pairs") ? SCHUR_PAIRS : SCHUR_SLOTS);
-  if (const char *ev = getenv("MVBA_SLOT_SKEW")) h->slot_skew = std::max(0LL, atoll(ev));
-  if (const char *ev = getenv("MVBA_SLOT_WINDOW")) h->slot_window = std::max(1LL, atoll(ev));
-  if (const char *ev = getenv("MVBA_SLOT_LAG")) h->slot_lag = std::max(1, atoi(ev));
-  if (const char *ev = getenv("MVBA_SLOT_SEG")) { h->slot_seg = std::max(1LL, atoll(ev)); h->slot_pace = atoll(ev) > 0; }
-  if (const char *ev = getenv("MVBA_PAIR_STATIC")) h->pair_static = atoi(ev) != 0;
-  if (const char *ev = getenv("MVBA_BACKSUB_LANES")) h->backsub_lanes = atoi(ev);
-  h->force_big = getenv("MVBA_FORCE_BIG") != nullptr;
-  if (const char *ev = getenv("MVBA_CHECK_SOLVE")) {
-    const double v = atof(ev);
-    h->check_solve = v != 0.0;
-    if (v > 0.0 && v < 1.0) h->check_solve_tol = v;
-  }
-  if (m > 65535) h->schur_mode = SCHUR_STRIP;
+  h->schur_mode = knobs.schur_pairs ? SCHUR_PAIRS : SCHUR_SLOTS;
+  h->force_big = knobs.force_big;
+  h->check_solve = knobs.check_solve;
+  h->check_solve_tol = knobs.check_solve_tol;
   std::vector<int> dense_obs;  // SCHUR_DENSE with missing observations: [N][m] observation of (point, camera) or -1
   {  // up to 21 cameras and most (point, camera) pairs observed: the dense form (no pair index).  Full visibility in camera order
      // (the reference's own scenes): a point's records are read as one contiguous range; otherwise through a table, a missing
@@ -3748,9 +3250,8 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       for (int k = 0; k < m; ++k)
         if (ci[k] != k) { full = false; break; }
     }
-    const char *ev = getenv("MVBA_SCHUR");
-    const bool forced = ev && !strcmp(ev, "dense");
-    bool masked = few && !full && (forced || (!ev && (double)nobs >= 0.6 * (double)N * m)) && (long long)N * m < (1LL << 31);
+    const bool forced = knobs.schur_dense;
+    bool masked = few && !full && (forced || (!knobs.schur_set && (double)nobs >= 0.6 * (double)N * m)) && (long long)N * m < (1LL << 31);
     if (masked) {
       dense_obs.assign((size_t)N * m, -1);
       for (long long a = 0; a < N && masked; ++a)
@@ -3761,10 +3262,10 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
         }
       if (!masked) dense_obs.clear();
     }
-    if ((full && (!ev || forced)) || masked) h->schur_mode = SCHUR_DENSE;
+    if ((full && (!knobs.schur_set || forced)) || masked) h->schur_mode = SCHUR_DENSE;
   }
-  trace.mark("form of K3");
-  h->use_pairs = h->schur_mode != SCHUR_STRIP && h->schur_mode != SCHUR_DENSE;
+  lap("form of K3");
+  h->use_pairs = h->schur_mode != SCHUR_DENSE;
   std::vector<int> it_k, it_l, it_a, unit_ptr, q_ptr(9, 0), q_units, st_k, st_l, st_a, wunits, seg_end;
   std::vector<int4> units, wdesc;
   if (h->use_pairs) {
@@ -3785,9 +3286,8 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     // points with a private pair histogram -- in LDS when P ints x 4 waves per block fit (up to ~138 cameras), else in
     // the wave's own row of a device buffer (at most 2 GiB of rows: 4096 waves at 500 cameras).  MVBA_INDEX=host keeps
     // the host threads, MVBA_INDEX=global forces the device-memory histogram (the tests that the builds are identical).
-    const char *idx_env = getenv("MVBA_INDEX");
-    const bool hist_lds = (size_t)P * sizeof(int) * IDX_WAVES <= 150 * 1024 && !(idx_env && !strcmp(idx_env, "global"));
-    bool dev_build = N > 0 && nobs > 0 && !(idx_env && !strcmp(idx_env, "host"));
+    const bool hist_lds = (size_t)P * sizeof(int) * IDX_WAVES <= 150 * 1024 && !knobs.index_global;
+    const bool dev_build = N > 0 && nobs > 0 && !knobs.index_host;
     const long long max_idx_waves = hist_lds ? 4096 : std::max<long long>(IDX_WAVES, std::min<long long>(4096, (2LL << 30) / (4 * P)));
     const int idx_chunk = (int)std::max<long long>(32, (N + max_idx_waves - 1) / max_idx_waves);  // points per wave
     const long long idx_waves = dev_build ? ((N + idx_chunk - 1) / idx_chunk + IDX_WAVES - 1) / IDX_WAVES * IDX_WAVES : 0;
@@ -3840,16 +3340,10 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     // (Two gathers in flight -- this form on the slot kernel's ring loop -- make it SLOWER, 15.5 ms: the wider window of
     // points misses L2 more often, profiles/r04_sweep_pairs_ring.txt.)
     const double pair_rate = N > 0 && P > m ? (double)(T - Tdiag) / ((double)(P - m) * (double)N) : 0.01;
-    long long unit_items = (long long)std::max(300.0, std::min(600.0, 200.0 + 4000.0 * std::sqrt(pair_rate)));
-    if (const char *ev = getenv("MVBA_PAIR_UNIT")) unit_items = std::max(21, atoi(ev));
+    const long long unit_items = (long long)std::max(300.0, std::min(600.0, 200.0 + 4000.0 * std::sqrt(pair_rate)));
     std::vector<int> S(P), vp_ptr(P + 1, 0);
-    // (MVBA_SLOT_DIAG_SCALE: the sub-lists of a pair much larger than the target -- the diagonal pairs -- are cut shorter by
-    // this factor: a diagonal step costs more instructions than an off-diagonal one, and the pace of a range is its slowest wave's)
-    double big_scale = 1.0;
-    if (const char *ev = getenv("MVBA_SLOT_DIAG_SCALE")) big_scale = std::max(0.25, std::min(4.0, atof(ev)));
     for (long long q = 0; q < P; ++q) {
       S[q] = (int)std::max<long long>(1, std::min<long long>(256, (cnt[q] + target / 2) / target));
-      if (S[q] >= 2 && big_scale != 1.0) S[q] = (int)std::max(1.0, std::min(256.0, std::floor((double)cnt[q] / (double)target * big_scale + 0.5)));
       vp_ptr[q + 1] = vp_ptr[q] + S[q];
     }
     const int VP = vp_ptr[P];
@@ -3863,11 +3357,7 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     // (ng + 1 times) instead of once per unit that needs it (the unit form: ~16 times from beyond the L2 at m = 500).
     int n_cu_dev = 256;
     hipDeviceGetAttribute(&n_cu_dev, hipDeviceAttributeMultiprocessorCount, h->device);
-#if defined(MVBA_HREC_TIMING)
-    const int xcd_waves = std::max(1, n_cu_dev / 8) * std::min(160 * 1024 / SLOT_LDS, 4 * MVBA_SLOT_WAVES_PER_SIMD);
-#else
     const int xcd_waves = std::max(1, n_cu_dev / 8) * (160 * 1024 / SLOT_LDS);  // 9 waves of 17,136 B of LDS per CU
-#endif
     int ng = 1, G = m, max_round_waves = 0;
     auto round_waves = [&](int G_, int g1, int g2) {  // waves (of 21 lists) of round (g1, g2): diagonal + off-diagonal
       long long ld = 0, lo = 0;
@@ -3877,7 +3367,7 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       }
       return (int)((ld + PSTEP - 1) / PSTEP + (lo + PSTEP - 1) / PSTEP);
     };
-    if (const char *ev = getenv("MVBA_SLOT_GROUPS")) ng = std::max(1, std::min(m, atoi(ev)));
+    if (knobs.slot_groups) ng = std::min(m, knobs.slot_groups);
     for (;; ++ng) {
       G = (m + ng - 1) / ng;
       max_round_waves = 0;
@@ -3888,26 +3378,18 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     ng = (m + G - 1) / G;  // (groups that hold a camera)
     // (below ~4 M items the launch is all prologue and pacing: the unit form's many short waves win -- config 2,
     // 10k points x 20 cameras: 0.095 against 0.124 ms; equal at 5.5 M items; MVBA_SCHUR=slots keeps the slot form)
-    const bool slots_forced = getenv("MVBA_SCHUR") && !strcmp(getenv("MVBA_SCHUR"), "slots");
+    const bool slots_forced = knobs.schur_slots;
     // (the gathers use 32-bit byte offsets: point rows from the array's start, records from their RANGE's first
     // observation -- checked below, once the ranges are known)
     // More than one round pays only while a list keeps enough items per L2 window for its wave's 21 lists to march in
     // step: at config 4 (500 cameras, 5 %: 390 items per list and range, ~10 per L2 window) the rounds cut the fabric
     // traffic 2.3x (742 M -> 328 M lines per launch) and still lose to the unit form, 18.1 against 14.3 ms -- 19-40 % padding
-    // rows and the pacing waits of 250 waves on lists that sparse (profiles/r04_sweep_c4_rounds.txt).  MVBA_SCHUR=slots forces them.
-    long long min_round_list = 1LL << 40;  // items per list and range, thinnest round
-    if (ng > 1) {
-      long long lists_total = 0;
-      for (long long q = 0; q < P; ++q) lists_total += S[q];
-      min_round_list = T / std::max<long long>(1, lists_total) / 8;
-    }
-    // ... and with denser lists as well (1 M points x 200 cameras x 10 %, 1250 items per list and range, three rounds: 8.9
-    // against 6.3 ms; 2 M x 150 x 10 %: 8.6 against 7.4; 1 M x 300 x 5 %: 5.3 against 4.3 -- profiles/r04_sweep_rounds_crossover.txt):
-    // more than one round runs only on request (MVBA_SCHUR=slots, or MVBA_SLOT_ROUND_MIN=<items per list and range>).
-    long long round_min_items = 1LL << 40;
-    if (const char *ev = getenv("MVBA_SLOT_ROUND_MIN")) round_min_items = std::max(0LL, atoll(ev));
+    // rows and the pacing waits of 250 waves on lists that sparse (profiles/r04_sweep_c4_rounds.txt) -- and with denser lists
+    // as well (1 M points x 200 cameras x 10 %, 1250 items per list and range, three rounds: 8.9 against 6.3 ms; 2 M x 150 x
+    // 10 %: 8.6 against 7.4; 1 M x 300 x 5 %: 5.3 against 4.3 -- profiles/r04_sweep_rounds_crossover.txt): more than one
+    // round runs only on request (MVBA_SCHUR=slots).
     if (h->schur_mode == SCHUR_SLOTS && (max_round_waves > xcd_waves || (N + 1) * 128LL >= (1LL << 32) || h->force_big || ng > 2047 ||
-                                         ((T < 4000000 || (ng > 1 && min_round_list < round_min_items)) && !slots_forced)))
+                                         ((T < 4000000 || ng > 1) && !slots_forced)))
       h->schur_mode = SCHUR_PAIRS;
     // point ranges.  Unit form: long runs for big problems, but small ones still get ~4096 units of >= 128 items.
     // Slot form: 8 ranges (one per XCD) -- 8 j while j ranges' worth of waves fit an XCD and a list keeps >= 64 items.
@@ -3951,126 +3433,21 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       }
     }
     const bool slots = h->schur_mode == SCHUR_SLOTS;
-    // ---- sweep order of the points inside a range (slot form).  The 21 lists of a wave march through the range in step
-    // and a slot whose next item lies beyond the skew window idles: with the points in their natural (random) order a
-    // list is a Poisson process -- 12.4 % padding rows at config 3, and the waves' steps per pacing segment scatter as
-    // widely, which is what they wait for at the crossings.  Any order is as good for the kernel (a record is a line of
-    // its own, the sums are per slot), so the index is built over a LOW-DISCREPANCY order: inside blocks of 8192 points
-    // the next point is the best of `cand` random candidates by the summed deficit of its pairs (expected minus actual
-    // count so far) -- the variance / mean of a pair's count per 2000-point window falls from 0.9 to ~0.25.  Deterministic
-    // (fixed seeds), host threads by block.  order[i] = point at sweep position i, rank = its inverse, pkey[a] =
-    // observations of the points swept before a, counted from the scene's start like a record index.
-    std::vector<int> order, rank;
-    std::vector<long long> pkey(N, 0);
-    {
-      const char *po = getenv("MVBA_POINT_ORDER");
-      int cand = 32;
-      if (const char *ev = getenv("MVBA_POINT_ORDER_CAND")) cand = std::max(1, atoi(ev));
-      // MEASURED at config 3 (profiles/r04_sweep_point_order.txt): padding rows 12.4 % -> 10.4 % (8 / 32 / 64 candidates alike),
-      // k_schur_slots 1.691 -> 1.677 ms, mvba_create 0.05 -> 0.17 s: the lists' unequal LENGTHS and the pacing, not their
-      // local irregularity, are what is left -- so the natural order stays the default and MVBA_POINT_ORDER=greedy asks for this one.
-      const bool reorder = slots && N > 0 && po && !strcmp(po, "greedy");
-      if (reorder) {
-        order.resize(N); rank.resize(N);
-        constexpr long long OB = 8192;
-        std::vector<std::pair<long long, long long>> blocks;
-        for (int r = 0; r < nR; ++r)
-          for (long long b0 = range_lo[r]; b0 < range_lo[r + 1]; b0 += OB) blocks.push_back({b0, std::min(range_lo[r + 1], b0 + OB)});
-        std::atomic<size_t> next{0};
-        const int nt = (int)std::max(1u, std::min({std::thread::hardware_concurrency(), 32u, (unsigned)blocks.size()}));
-        auto work = [&]() {
-          std::vector<int> count(P);
-          std::vector<double> R;
-          for (;;) {
-            const size_t bi = next.fetch_add(1);
-            if (bi >= blocks.size()) break;
-            const long long b0 = blocks[bi].first, b1 = blocks[bi].second, nb = b1 - b0;
-            std::fill(count.begin(), count.end(), 0);
-            R.assign(nb, 0.0);
-            int *ord = order.data() + b0;
-            for (long long i = 0; i < nb; ++i) {
-              ord[i] = (int)(b0 + i);
-              const int *cb = p->cam_idx + p->pt_ptr[b0 + i];
-              const int d = (int)(p->pt_ptr[b0 + i + 1] - p->pt_ptr[b0 + i]);
-              double rs = 0.0;
-              for (int x = 0; x < d; ++x)
-                for (int y = x; y < d; ++y) rs += (double)cnt[pair_id(cb[x], cb[y])];
-              R[i] = rs / (double)N;  // expected arrivals of this point's pairs per point swept
-            }
-            unsigned long long rng = 0x9E3779B97F4A7C15ull * (bi + 1);
-            for (long long t = 0; t < nb; ++t) {
-              long long best = t;
-              double best_s = -1e300;
-              for (int c = 0; c < cand; ++c) {
-                rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
-                const long long j = t + (long long)(rng % (unsigned long long)(nb - t));
-                const long long a = ord[j];
-                const int *cb = p->cam_idx + p->pt_ptr[a];
-                const int d = (int)(p->pt_ptr[a + 1] - p->pt_ptr[a]);
-                long long have = 0;
-                for (int x = 0; x < d; ++x) {
-                  const int *row = count.data() + pair_id(cb[x], cb[x]) - cb[x];
-                  for (int y = x; y < d; ++y) have += row[cb[y]];
-                }
-                const double sc = (double)t * R[a - b0] - (double)have;
-                if (sc > best_s) { best_s = sc; best = j; }
-              }
-              std::swap(ord[t], ord[best]);
-              const long long a = ord[t];
-              const int *cb = p->cam_idx + p->pt_ptr[a];
-              const int d = (int)(p->pt_ptr[a + 1] - p->pt_ptr[a]);
-              for (int x = 0; x < d; ++x) {
-                int *row = count.data() + pair_id(cb[x], cb[x]) - cb[x];
-                for (int y = x; y < d; ++y) row[cb[y]]++;
-              }
-            }
-          }
-        };
-        std::vector<std::thread> th;
-        for (int t = 1; t < nt; ++t) th.emplace_back(work);
-        work();
-        for (auto &x : th) x.join();
-        for (long long i = 0; i < N; ++i) rank[order[i]] = (int)i;
-      }
-      long long run = 0;
-      for (long long i = 0; i < N; ++i) {
-        const long long a = order.empty() ? i : order[i];
-        pkey[a] = run;
-        run += p->pt_ptr[a + 1] - p->pt_ptr[a];
-      }
-    }
-    lap("point order");
-    int *d_order = nullptr, *d_rank = nullptr;
-    long long *d_pkey = nullptr;
-    if (dev_build && slots) {
-      TRY(dmalloc(&d_pkey, (size_t)N));
-      TRYH(hipMemcpyAsync(d_pkey, pkey.data(), sizeof(long long) * N, hipMemcpyHostToDevice, h->stream));
-      if (!order.empty()) {
-        TRY(dmalloc(&d_order, (size_t)N)); TRY(dmalloc(&d_rank, (size_t)N));
-        TRYH(hipMemcpyAsync(d_order, order.data(), sizeof(int) * N, hipMemcpyHostToDevice, h->stream));
-        TRYH(hipMemcpyAsync(d_rank, rank.data(), sizeof(int) * N, hipMemcpyHostToDevice, h->stream));
-        // the per-wave start ranks again, in sweep order (the totals are the same)
-        if (!hist_lds) TRYH(hipMemsetAsync(d_hist, 0, sizeof(int) * (size_t)idx_waves * P, h->stream));
-        hipLaunchKernelGGL(hist_lds ? k_idx_count<false> : k_idx_count<true>, dim3((unsigned)(idx_waves / IDX_WAVES)), dim3(64 * IDX_WAVES), idx_lds,
-                           h->stream, N, m, (int)P, h->d_pt_ptr, h->d_cam, idx_chunk, d_hist, d_order);
-        hipLaunchKernelGGL(k_idx_scan, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (int)P, (int)idx_waves, d_hist, d_cnt);
-      }
-    }
+    // The points are swept in their natural order: an item's key (where its point sits in the sweep, in observations) is its
+    // point's first observation, pt_ptr[a].  (A low-discrepancy order -- round 4 -- cut the padding rows from 12.4 % to 10.4 %
+    // at config 3 but k_schur_slots only from 1.691 to 1.677 ms, for 0.12 s more of mvba_create: profiles/r04_sweep_point_order.txt.)
     std::vector<long long> vp_off(VP + 1, 0);
     for (long long q = 0; q < P; ++q)
       for (int sI = 0; sI < S[q]; ++sI) vp_off[vp_ptr[q] + sI + 1] = (cnt[q] - sI + S[q] - 1) / S[q];
     for (int v = 0; v < VP; ++v) vp_off[v + 1] += vp_off[v];
-    // the window-equalised merge (MVBA_SLOT_WINDOW, an experiment) exists on the host only
-    const bool dev_items = dev_build && (!slots || h->slot_window >= (1LL << 39));
     int *d_pk = nullptr, *d_pl = nullptr, *d_pa = nullptr, *d_S = nullptr, *d_vp_ptr = nullptr;
     long long *d_vp_off = nullptr;
     auto free_dev_tmp = [&]() {
-      for (void *q : {(void *)d_hist, (void *)d_cnt, (void *)d_pk, (void *)d_pl, (void *)d_pa, (void *)d_S, (void *)d_vp_ptr, (void *)d_vp_off,
-                      (void *)d_order, (void *)d_rank, (void *)d_pkey})
+      for (void *q : {(void *)d_hist, (void *)d_cnt, (void *)d_pk, (void *)d_pl, (void *)d_pa, (void *)d_S, (void *)d_vp_ptr, (void *)d_vp_off})
         if (q) hipFree(q);
-      d_hist = nullptr; d_cnt = nullptr; d_pk = d_pl = d_pa = d_S = d_vp_ptr = d_order = d_rank = nullptr; d_vp_off = d_pkey = nullptr;
+      d_hist = nullptr; d_cnt = nullptr; d_pk = d_pl = d_pa = d_S = d_vp_ptr = nullptr; d_vp_off = nullptr;
     };
-    if (dev_items) {
+    if (dev_build) {
       TRY(dmalloc(&d_pk, (size_t)T)); TRY(dmalloc(&d_pl, (size_t)T)); TRY(dmalloc(&d_pa, (size_t)T));
       TRY(dmalloc(&d_S, (size_t)P)); TRY(dmalloc(&d_vp_ptr, (size_t)P + 1)); TRY(dmalloc(&d_vp_off, (size_t)VP + 1));
       TRYH(hipMemcpyAsync(d_S, S.data(), sizeof(int) * P, hipMemcpyHostToDevice, h->stream));
@@ -4078,16 +3455,14 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       TRYH(hipMemcpyAsync(d_vp_off, vp_off.data(), sizeof(long long) * (VP + 1), hipMemcpyHostToDevice, h->stream));
       hipLaunchKernelGGL(hist_lds ? k_idx_fill<false> : k_idx_fill<true>, dim3((unsigned)(idx_waves / IDX_WAVES)), dim3(64 * IDX_WAVES), idx_lds,
                          h->stream, N, m, (int)P, h->d_pt_ptr, h->d_cam, idx_chunk, d_hist, d_S, d_vp_ptr, d_vp_off, d_pk, d_pl, d_pa,
-                         (const int *)d_order);
+                         (const int *)nullptr);
       TRYH(hipGetLastError());
     } else {
-      if (dev_build) { hipFree(d_hist); hipFree(d_cnt); d_hist = nullptr; d_cnt = nullptr; }
     it_k.resize(T); it_l.resize(T); it_a.resize(T);
     {
       std::vector<long long> run(P, 0);
       on_threads([&](int tid) {
-        for (long long ai = 0; ai < N; ++ai) {
-          const long long a = order.empty() ? ai : order[ai];
+        for (long long a = 0; a < N; ++a) {
           const long long o0 = p->pt_ptr[a];
           const int *cb = p->cam_idx + o0;
           const int d = (int)(p->pt_ptr[a + 1] - o0);
@@ -4110,12 +3485,12 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     unit_ptr.assign(P + 1, 0);
     std::vector<int> uid((size_t)VP * nR, -1);
     std::vector<long long> lo_tab;  // device build: lower bounds of every list at every range boundary
-    if (dev_items) {
+    if (dev_build) {
       long long *d_rl = nullptr, *d_lo = nullptr;
       TRY(dmalloc(&d_rl, (size_t)nR + 1)); TRY(dmalloc(&d_lo, (size_t)VP * (nR + 1)));
       TRYH(hipMemcpyAsync(d_rl, range_lo.data(), sizeof(long long) * (nR + 1), hipMemcpyHostToDevice, h->stream));
       const long long nt = (long long)VP * (nR + 1);
-      hipLaunchKernelGGL(k_idx_bounds, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, VP, nR, d_vp_off, d_rl, d_pa, d_lo, (const int *)d_rank);
+      hipLaunchKernelGGL(k_idx_bounds, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, VP, nR, d_vp_off, d_rl, d_pa, d_lo, (const int *)nullptr);
       lo_tab.resize(nt);
       TRYH(hipMemcpyAsync(lo_tab.data(), d_lo, sizeof(long long) * nt, hipMemcpyDeviceToHost, h->stream));
       TRYH(hipStreamSynchronize(h->stream));
@@ -4127,11 +3502,11 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
         unit_ptr[q] = (int)units.size();
         for (int sI = 0; sI < S[q]; ++sI) {
           const int v = vp_ptr[q] + sI;
-          const int *b = it_a.data() + (dev_items ? 0 : vp_off[v]), *e = it_a.data() + (dev_items ? 0 : vp_off[v + 1]);
+          const int *b = it_a.data() + (dev_build ? 0 : vp_off[v]), *e = it_a.data() + (dev_build ? 0 : vp_off[v + 1]);
           for (int r = 0; r < nR; ++r) {
-            auto before = [&](int a, long long key) { return (rank.empty() ? (long long)a : (long long)rank[a]) < key; };
-            const long long lo = dev_items ? lo_tab[(size_t)v * (nR + 1) + r] : std::lower_bound(b, e, range_lo[r], before) - it_a.data();
-            const long long hi = dev_items ? lo_tab[(size_t)v * (nR + 1) + r + 1] : std::lower_bound(b, e, range_lo[r + 1], before) - it_a.data();
+            auto before = [](int a, long long key) { return (long long)a < key; };
+            const long long lo = dev_build ? lo_tab[(size_t)v * (nR + 1) + r] : std::lower_bound(b, e, range_lo[r], before) - it_a.data();
+            const long long hi = dev_build ? lo_tab[(size_t)v * (nR + 1) + r + 1] : std::lower_bound(b, e, range_lo[r + 1], before) - it_a.data();
             if (hi <= lo) continue;
             uid[(size_t)v * nR + r] = (int)units.size();
             units.push_back(make_int4((int)(lo & 0xffffffffLL), (int)(lo >> 32), (int)(hi - lo), (k << 16) | l));
@@ -4178,19 +3553,10 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       // a round touches the records of 2 of ng camera groups only: its skew and pacing segments, counted in
       // observations of the range, stretch accordingly (the footprint in the L2 is what they bound)
       const long long stretch = std::max(1, ng / 2);
-      // Bounded-skew merge of a wave's lists into steps (see k_schur_slots), window by window: the observations of a
-      // range are cut into windows of `slot_window`, and every wave of the range is padded to the same number of
-      // steps per window (the slowest wave's), so that all waves of an XCD reach a window boundary at the same step
-      // index and cannot drift apart by more than their rate difference inside one window.
-      const long long skew = h->slot_skew * stretch, window = std::max<long long>(1, h->slot_window);
-      int nWin = 1;
-      for (int r = 0; r < nR; ++r)
-        nWin = std::max<long long>(nWin, (p->pt_ptr[range_lo[r + 1]] - p->pt_ptr[range_lo[r]] + window - 1) / window);
-      const bool equalize = h->slot_window < (1LL << 39);
-      std::vector<int> win_steps((size_t)n_waves * nWin, 0), win_max((size_t)n_rounds * nR * nWin, 0);
+      // Bounded-skew merge of a wave's lists into steps (see k_schur_slots)
+      const long long skew = SLOT_SKEW * stretch;
       // pacing segments: seg_end[b][j] = steps wave b has taken when its slowest slot leaves segment j of the range
-      // (no pacing, MVBA_SLOT_SEG=0: one segment -- the table has a row per wave and segment)
-      const long long segG = h->slot_pace ? std::max<long long>(1, h->slot_seg * stretch) : (1LL << 40);
+      const long long segG = SLOT_SEG * stretch;
       int nSeg = 1;
       for (int r = 0; r < nR; ++r)
         nSeg = std::max<long long>(nSeg, (p->pt_ptr[range_lo[r + 1]] - p->pt_ptr[range_lo[r]] + segG - 1) / segG);
@@ -4210,36 +3576,24 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
         long long steps = 0;
         const long long o_lo = p->pt_ptr[range_lo[r]];
         int sg = 0;
-        for (int j = 0; j < nWin; ++j) {
-          const long long limit = j + 1 < nWin ? o_lo + (j + 1) * window : (1LL << 62);
-          long long ws = 0;
-          while (true) {
-            long long lo = -1;
-            auto key_of = [&](int sl) { return pkey[it_a[cur[sl]]]; };  // where the item's point sits in the sweep, in observations
-            for (int sl = 0; sl < PSTEP; ++sl)
-              if (cur[sl] < end[sl] && key_of(sl) < limit && (lo < 0 || key_of(sl) < lo)) lo = key_of(sl);
-            if (fill && lo >= 0)
-              while (sg < nSeg && lo >= o_lo + (sg + 1) * segG) seg_end[(size_t)b * nSeg + sg++] = (int)(steps + ws);
-            if (lo < 0) break;
-            for (int sl = 0; sl < PSTEP; ++sl) {
-              const bool take = cur[sl] < end[sl] && key_of(sl) < limit && key_of(sl) <= lo + skew;
-              if (fill) {
-                const long long o = (base + steps + ws) * PSTEP + sl;
-                if (take) { st_k[o] = (int)(it_k[cur[sl]] - o_lo); st_l[o] = (int)(it_l[cur[sl]] - o_lo); st_a[o] = it_a[cur[sl]]; }
-                else { st_k[o] = st_l[o] = 0; st_a[o] = (int)N; }  // the range's first record (any finite one) x the all-zero point row
-              }
-              if (take) ++cur[sl];
+        auto key_of = [&](int sl) { return p->pt_ptr[it_a[cur[sl]]]; };  // where the item's point sits in the sweep, in observations
+        while (true) {
+          long long lo = -1;
+          for (int sl = 0; sl < PSTEP; ++sl)
+            if (cur[sl] < end[sl] && (lo < 0 || key_of(sl) < lo)) lo = key_of(sl);
+          if (fill && lo >= 0)
+            while (sg < nSeg && lo >= o_lo + (sg + 1) * segG) seg_end[(size_t)b * nSeg + sg++] = (int)steps;
+          if (lo < 0) break;
+          for (int sl = 0; sl < PSTEP; ++sl) {
+            const bool take = cur[sl] < end[sl] && key_of(sl) <= lo + skew;
+            if (fill) {
+              const long long o = (base + steps) * PSTEP + sl;
+              if (take) { st_k[o] = (int)(it_k[cur[sl]] - o_lo); st_l[o] = (int)(it_l[cur[sl]] - o_lo); st_a[o] = it_a[cur[sl]]; }
+              else { st_k[o] = st_l[o] = 0; st_a[o] = (int)N; }  // the range's first record (any finite one) x the all-zero point row
             }
-            ++ws;
+            if (take) ++cur[sl];
           }
-          if (!fill) { win_steps[(size_t)b * nWin + j] = (int)ws; steps += ws; continue; }
-          const long long target_ws = equalize ? win_max[round_range(b) * nWin + j] : ws;
-          for (; ws < target_ws; ++ws)
-            for (int sl = 0; sl < PSTEP; ++sl) {
-              const long long o = (base + steps + ws) * PSTEP + sl;
-              st_k[o] = st_l[o] = 0; st_a[o] = (int)N;
-            }
-          steps += target_ws;
+          ++steps;
         }
         if (fill)
           while (sg < nSeg) seg_end[(size_t)b * nSeg + sg++] = (int)steps;
@@ -4255,7 +3609,7 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
         TRYH(hipMemcpy(h->d_range_o0, ro0.data(), sizeof(long long) * nR, hipMemcpyHostToDevice));
         d_ro0 = h->d_range_o0;
       }
-      if (dev_items) {
+      if (dev_build) {
         std::vector<long long> sl_beg((size_t)n_waves * PSTEP, 0);
         std::vector<int> sl_len((size_t)n_waves * PSTEP, 0);
         for (long long b = 0; b < n_waves; ++b) {
@@ -4275,34 +3629,20 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
         TRYH(hipMemcpyAsync(d_sllen, sl_len.data(), sizeof(int) * sl_len.size(), hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_idx_merge<false>, dim3((unsigned)n_waves), dim3(64), 0, h->stream, n_waves, nR, nSeg, skew, segG, d_slbeg, d_sllen,
                            d_ro0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, (int *)nullptr, (int *)nullptr, (int *)nullptr,
-                           (int *)nullptr, (const long long *)d_pkey);
+                           (int *)nullptr, (const long long *)h->d_pt_ptr);
         std::vector<int> ws32(n_waves);
         TRYH(hipMemcpyAsync(ws32.data(), d_wsteps, sizeof(int) * n_waves, hipMemcpyDeviceToHost, h->stream));
         TRYH(hipStreamSynchronize(h->stream));  // (sl_beg / sl_len / ro0 live until here)
-        for (long long b = 0; b < n_waves; ++b) win_steps[(size_t)b * nWin] = ws32[b];
+        for (long long b = 0; b < n_waves; ++b) w_steps[b] = ws32[b];
       } else
       on_threads([&](int tid) {
-        for (long long b = tid; b < n_waves; b += n_thr) merge(b, 0, false);
+        for (long long b = tid; b < n_waves; b += n_thr) w_steps[b] = merge(b, 0, false);
       });
       lap("slot merge (count)");
-      for (long long b = 0; b < n_waves; ++b)
-        for (int j = 0; j < nWin; ++j) {
-          int &mx = win_max[round_range(b) * nWin + j];
-          mx = std::max(mx, win_steps[(size_t)b * nWin + j]);
-        }
-      for (long long b = 0; b < n_waves; ++b) {
-        long long t = 0;
-        bool any = false;
-        for (int j = 0; j < nWin; ++j) {
-          t += equalize ? win_max[round_range(b) * nWin + j] : win_steps[(size_t)b * nWin + j];
-          any |= win_steps[(size_t)b * nWin + j] > 0;
-        }
-        w_steps[b] = any ? t : 0;  // a wave without any item does not run at all
-      }
       for (long long b = 0; b < n_waves; ++b) w_beg[b + 1] = w_beg[b] + w_steps[b];
       const long long total_steps = w_beg[n_waves];
       if (total_steps * PSTEP >= (1LL << 40)) { mvba_destroy(h); return fail(MVBA_ERR_BADARG, "too many (point, camera pair) items"); }
-      {  // the step-major index -- its size follows the opt-in knobs (skew, window, groups: padding rows) -- against the memory that is
+      {  // the step-major index -- its size follows the padding rows (more of them with MVBA_SLOT_GROUPS) -- against the memory that is
         // there, BEFORE anything of it is allocated: three 4-byte arrays of step rows, then the interleaved 256-byte rows beside them
         const size_t need = (size_t)total_steps * PSTEP * 12 + (size_t)total_steps * SLOT_IDX * 4 + seg_end.size() * 4;
         size_t fr = 0, tot = 0;
@@ -4310,17 +3650,16 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
           mvba_destroy(h);
           return fail(MVBA_ERR_BADARG, "the slot-form Schur index needs " + std::to_string(need >> 20) + " MiB (" + std::to_string(total_steps * PSTEP) + " step rows for " +
                                            std::to_string(T) + " items: " + std::to_string(n_rounds) + " rounds x " + std::to_string(nR) + " ranges, skew " + std::to_string(skew) +
-                                           ", window " + std::to_string(h->slot_window) + (equalize ? " (equalised)" : "") + "), " + std::to_string(fr >> 20) +
-                                           " MiB of device memory are free: relax MVBA_SLOT_SKEW / MVBA_SLOT_WINDOW / MVBA_SLOT_GROUPS or use MVBA_SCHUR=pairs");
+                                           "), " + std::to_string(fr >> 20) + " MiB of device memory are free: relax MVBA_SLOT_GROUPS or use MVBA_SCHUR=pairs");
         }
       }
-      if (dev_items) {  // the step-major arrays are written where the kernel will read them
+      if (dev_build) {  // the step-major arrays are written where the kernel will read them
         const size_t rows = (size_t)total_steps * PSTEP;
         TRY(dmalloc(&h->d_it_k, rows)); TRY(dmalloc(&h->d_it_l, rows)); TRY(dmalloc(&h->d_it_a, rows));
         TRY(dmalloc(&h->d_seg_end, seg_end.size()));
         TRYH(hipMemcpyAsync(d_wbeg, w_beg.data(), sizeof(long long) * (n_waves + 1), hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_idx_merge<true>, dim3((unsigned)n_waves), dim3(64), 0, h->stream, n_waves, nR, nSeg, skew, segG, d_slbeg, d_sllen,
-                           d_ro0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, h->d_it_k, h->d_it_l, h->d_it_a, h->d_seg_end, (const long long *)d_pkey);
+                           d_ro0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, h->d_it_k, h->d_it_l, h->d_it_a, h->d_seg_end, (const long long *)h->d_pt_ptr);
         TRYH(hipGetLastError());
         TRYH(hipStreamSynchronize(h->stream));
         for (void *q : {(void *)d_slbeg, (void *)d_sllen, (void *)d_wsteps, (void *)d_wbeg}) hipFree(q);
@@ -4346,24 +3685,13 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       h->slot_groups = ng;
       h->n_waves = (int)n_waves;
       h->slot_nR = nR;
-#ifdef MVBA_SLOT_TRACE
-      if (const char *ev = getenv("MVBA_SLOT_DUMP"))  // diagnostic build: the pacing table (steps at each segment boundary)
-        if (FILE *f = fopen(ev, "wb")) {
-          const int hdr[4] = {(int)n_waves, nSeg, nR, wpr};  // (pacing is per (round, range): MVBA_SLOT_GROUPS=1 scenes for the replay tool)
-          fwrite(hdr, sizeof(int), 4, f);
-          fwrite(seg_end.data(), sizeof(int), seg_end.size(), f);
-          fclose(f);
-        }
-#endif
       h->n_slot_items = total_steps * PSTEP;
-      if (!dev_items) { it_k.swap(st_k); it_l.swap(st_l); it_a.swap(st_a); }  // what is uploaded below: the step-major arrays
+      if (!dev_build) { it_k.swap(st_k); it_l.swap(st_l); it_a.swap(st_a); }  // what is uploaded below: the step-major arrays
       std::vector<int>().swap(st_k); std::vector<int>().swap(st_l); std::vector<int>().swap(st_a);
     } else {
-    // work queues: strip k on XCD k % 8, inside a queue by (k, range, l, sub-list)
-    // range-major: every XCD sweeps the point ranges in the same order, so the l-side records of
-    // a range (needed once per strip, ~4.5 times in all) are re-read from the Infinity Cache while
-    // the whole chip is on that range: 2.28 -> 2.04 ms at config 3 (MVBA_PAIR_ORDER=kr: strip-major)
-    const bool range_major = !(getenv("MVBA_PAIR_ORDER") && !strcmp(getenv("MVBA_PAIR_ORDER"), "kr"));
+    // work queues: strip k on XCD k % 8, inside a queue by (range, k, l, sub-list) -- range-major: every XCD sweeps the
+    // point ranges in the same order, so the l-side records of a range (needed once per strip, ~4.5 times in all) are
+    // re-read from the Infinity Cache while the whole chip is on that range: 2.28 -> 2.04 ms at config 3 against strip-major
     for (int x = 0; x < 8; ++x) {
       auto push_group = [&](int k, int r) {
         for (int l = k; l < m; ++l) {
@@ -4374,16 +3702,11 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
           }
         }
       };
-      if (range_major) {
-        for (int r = 0; r < nR; ++r)
-          for (int k = x; k < m; k += 8) push_group(k, r);
-      } else {
-        for (int k = x; k < m; k += 8)
-          for (int r = 0; r < nR; ++r) push_group(k, r);
-      }
+      for (int r = 0; r < nR; ++r)
+        for (int k = x; k < m; k += 8) push_group(k, r);
       q_ptr[x + 1] = (int)q_units.size();
     }
-    if (dev_items) {  // the pair-major arrays stay where the fill kernel wrote them
+    if (dev_build) {  // the pair-major arrays stay where the fill kernel wrote them
       h->d_it_k = d_pk; h->d_it_l = d_pl; h->d_it_a = d_pa;
       d_pk = d_pl = d_pa = nullptr;
       free_dev_tmp();
@@ -4398,10 +3721,8 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
   h->cost_grid = (int)std::max<long long>(1, std::min<long long>(2048, (nobs + 255) / 256));
   h->n_partials = std::max(h->cost_grid, 4096);  // k_cost uses cost_grid blocks
 
-  trace.mark("K3 index");
   TRY(dmalloc(&h->d_obs_pt, nobs));
   TRY(dmalloc(&h->d_xy, nobs));
-  TRY(dmalloc(&h->d_csc, csc.size()));
   h->n_tiles = (int)tiles.size() - 1;
   h->any_split = any_split;
   if (any_split) {
@@ -4414,7 +3735,6 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     TRYH(hipMemcpy(h->d_splits, splits.data(), sizeof(int4) * splits.size(), hipMemcpyHostToDevice));
   }
   TRY(dmalloc(&h->d_tiles, tiles.size()));
-  TRY(dmalloc(&h->d_chunk_ptr, chunk_ptr.size()));
   for (int i = 0; i < 2; ++i) { TRY(dmalloc(&h->d_X[i], 3 * N)); TRY(dmalloc(&h->d_cam15[i], (size_t)CAM_IN * m)); }
   TRY(dmalloc(&h->d_rec, (size_t)REC * (nobs + 1)));  // + the all-zero record and point row the slot form's padding points at
   TRY(dmalloc(&h->d_PL, 9 * N));
@@ -4431,12 +3751,12 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
   TRY(dmalloc(&h->d_partials, h->n_partials));
   TRY(dmalloc(&h->d_cost, 2));
   TRY(dmalloc(&h->d_flag, 1));
-  TRY(dmalloc(&h->d_bar, 1 + 4 * (size_t)((9 * m + SBW - 1) / SBW)));  // barrier counter / progress words of the back-substitution
+  TRY(dmalloc(&h->d_bar, 1 + 4 * (size_t)((9 * m + SBW - 1) / SBW)));  // progress words of the back-substitution
   TRYH(hipHostMalloc((void **)&h->h_cost, 4 * sizeof(double), hipHostMallocMapped));
   memset(h->h_cost, 0, 4 * sizeof(double));
   if (hipHostGetDevicePointer((void **)&h->d_mail, h->h_cost, 0) != hipSuccess) h->d_mail = nullptr;  // (no mapping: copy + sync as before)
   h->h_flag = reinterpret_cast<int *>(h->h_cost + 1);  // cost and flags come back in one copy
-  trace.mark("allocations");
+  lap("allocations");
   if (nobs) {
     TRYH(hipMemcpy(h->d_obs_pt, obs_pt.data(), sizeof(int) * nobs, hipMemcpyHostToDevice));
     if (p->xy_layout == 1) {  // image planes [m][N][2], as a caller's stack of per-image arrays lies in memory: into observation order here
@@ -4453,12 +3773,10 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     } else {
       TRYH(hipMemcpy(h->d_xy, p->xy, sizeof(double2) * nobs, hipMemcpyHostToDevice));
     }
-    if (want_strip) TRYH(hipMemcpy(h->d_csc, csc.data(), sizeof(int4) * nobs, hipMemcpyHostToDevice));
   }
   TRYH(hipMemcpy(h->d_tiles, tiles.data(), sizeof(int) * tiles.size(), hipMemcpyHostToDevice));
   // points without observations are never written by K1: their blocks stay zero (-> singular, ref :128)
   TRYH(hipMemset(h->d_PL, 0, sizeof(double) * 9 * std::max<long long>(N, 1)));
-  if (want_strip) TRYH(hipMemcpy(h->d_chunk_ptr, chunk_ptr.data(), sizeof(long long) * chunk_ptr.size(), hipMemcpyHostToDevice));
   TRYH(hipMemset(h->d_flag, 0, sizeof(int)));
   if (h->schur_mode == SCHUR_DENSE) {  // partial tiles of k_schur_dense: (tile pairs + one per camera) x 256 doubles per workgroup
     const int T = (9 * m + 15) / 16;
@@ -4478,9 +3796,6 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     TRY(dmalloc(&h->d_units, units.size())); TRY(dmalloc(&h->d_unit_ptr, P1));
     TRY(dmalloc(&h->d_q_ptr, 9)); TRY(dmalloc(&h->d_q_units, q_units.size())); TRY(dmalloc(&h->d_q_head, 64));
     TRY(dmalloc(&h->d_wdesc, wdesc.size())); TRY(dmalloc(&h->d_wunits, wunits.size()));
-#ifdef MVBA_SLOT_TRACE
-    if (getenv("MVBA_SLOT_TRACE")) { TRY(dmalloc(&h->d_trace, 16 * std::max<size_t>(1, wdesc.size()))); TRYH(hipMemset(h->d_trace, 0, 128 * std::max<size_t>(1, wdesc.size()))); }
-#endif
     if (!h->index_on_device) TRY(dmalloc(&h->d_seg_end, seg_end.size()));
     TRY(dmalloc(&h->d_prog, (size_t)h->slot_rounds * h->slot_nR * std::max(1, h->slot_nseg) * PACE_STRIDE));
     if (!seg_end.empty() && !h->index_on_device) TRYH(hipMemcpy(h->d_seg_end, seg_end.data(), sizeof(int) * seg_end.size(), hipMemcpyHostToDevice));
@@ -4520,13 +3835,8 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     TRYH(hipMemset(h->d_q_head, 0, sizeof(int) * 64));
     TRYH(hipMemset(h->d_partial, 0, sizeof(double) * UNIT_STRIDE * std::max<size_t>(units.size(), 1)));
   }
-  trace.mark("uploads");
+  lap("uploads");
   // opt in to large dynamic LDS
-  const int strip_lds = (int)((81 * (size_t)h->lseg + 9) * sizeof(double));
-  TRYH(hipFuncSetAttribute((const void *)k_schur_strip<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, strip_lds));
-  TRYH(hipFuncSetAttribute((const void *)k_schur_strip<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, strip_lds));
-  TRYH(hipFuncSetAttribute((const void *)k_schur_strip<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, strip_lds));
-  TRYH(hipFuncSetAttribute((const void *)k_schur_strip<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, strip_lds));
   const int cam_lds = h->gcam ? 0 : (int)((size_t)m * (CAM_LDS + DXI_LDS) * sizeof(double));
   if (h->gcam) { TRY(dmalloc(&h->d_cam18, (size_t)m * CAM_LDS)); TRY(dmalloc(&h->d_dxi10, (size_t)m * DXI_LDS)); }
   for (const void *f : {(const void *)k_backsub<2>, (const void *)k_backsub<4>, (const void *)k_backsub<8>, (const void *)k_backsub<2, 512>,
@@ -4534,25 +3844,22 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
                         (const void *)k_backsub<4, 1024>, (const void *)k_backsub<8, 1024>})
     TRYH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
   TRYH(hipFuncSetAttribute((const void *)k_chol_super, hipFuncAttributeMaxDynamicSharedMemorySize, SUPER_LDS));
-  TRYH(hipFuncSetAttribute((const void *)k_chol_backsolve_all<false>, hipFuncAttributeMaxDynamicSharedMemorySize, BACKSOLVE_LDS));
   TRYH(hipFuncSetAttribute((const void *)k_chol_backsolve_all<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BACKSOLVE_LDS));
   {
     // the persistent back-substitution needs its whole grid resident: at most one workgroup per CU
     int per_cu = 0;
     TRYH(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
     TRYH(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_chol_backsolve_all<true>, SUPER_THREADS, BACKSOLVE_LDS));
-    h->chol_onepass = per_cu >= 1 && !(getenv("MVBA_CHOL") && !strcmp(getenv("MVBA_CHOL"), "launches"));
-    h->chol_flow = !(getenv("MVBA_CHOL") && !strcmp(getenv("MVBA_CHOL"), "barriers"));
-    if (const char *ev = getenv("MVBA_TRAIL64_MIN")) h->trail64_min = std::max(0, atoi(ev));
-    if (const char *ev = getenv("MVBA_CHOL_BARRIER_POLLS")) h->barrier_polls = (unsigned)std::max(0LL, atoll(ev));
+    h->chol_onepass = per_cu >= 1 && !knobs.chol_launches;
+    h->trail64_min = knobs.trail64_min;
+    h->barrier_polls = knobs.barrier_polls;
   }
   TRYH(hipFuncSetAttribute(h->gcam ? (const void *)k_resid_jac<true> : (const void *)k_resid_jac<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                            (int)((size_t)((h->gcam ? 0 : ((m * CAM_LDS + 1) & ~1)) + (h->k1_threads / 64) * 64 * 2 * REC) * sizeof(double))));
   TRYH(hipFuncSetAttribute((const void *)k_cost<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
 #undef TRY
 #undef TRYH
-  lap("device allocations + uploads");
-  trace.mark("attributes");
+  lap("attributes");
   *out = h;
   return MVBA_OK;
 }
@@ -4561,27 +3868,12 @@ void mvba_destroy(mvba_handle *h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-#ifdef MVBA_SLOT_TRACE
-  if (h->d_trace && getenv("MVBA_SLOT_TRACE")) {
-    std::vector<long long> tr(16 * (size_t)h->n_waves);
-    hipMemcpy(tr.data(), h->d_trace, sizeof(long long) * tr.size(), hipMemcpyDeviceToHost);
-    if (FILE *f = fopen(getenv("MVBA_SLOT_TRACE"), "w")) {
-      fprintf(f, "# block t0 t1 wait blocked polls hwid xcc nsteps (100 MHz ticks) | shader cycles summed over the steps: vmcnt-wait pace gather-issue index-dma compute loop-total - -; nR=%d lag=%d nseg=%d\n", h->slot_nR, h->slot_lag, h->slot_nseg);
-      for (int b = 0; b < h->n_waves; ++b) {
-        fprintf(f, "%d", b);
-        for (int q = 0; q < 16; ++q) fprintf(f, " %lld", tr[16 * (size_t)b + q]);
-        fprintf(f, "\n");
-      }
-      fclose(f);
-    }
-  }
-#endif
   if (h->comm) g_rccl.CommDestroy(h->comm);
-  void *ptrs[] = {h->d_pt_ptr, h->d_cam, h->d_obs_pt, h->d_xy, h->d_csc, h->d_tiles, h->d_tile_slot, h->d_splits, h->d_PLsplit, h->d_chunk_ptr, h->d_X[0], h->d_X[1],
+  void *ptrs[] = {h->d_pt_ptr, h->d_cam, h->d_obs_pt, h->d_xy, h->d_tiles, h->d_tile_slot, h->d_splits, h->d_PLsplit, h->d_X[0], h->d_X[1],
                   h->d_cam15[0], h->d_cam15[1], h->d_rec, h->d_PL, h->d_PB, h->d_Ab, h->d_Ared, h->d_Ztiles, h->d_Lblk, h->d_lu,
                   h->d_dxi, h->d_dX, h->d_partials, h->d_cost, h->d_flag, h->d_allcost, h->d_it_k, h->d_it_l, h->d_it_a,
                   h->d_units, h->d_unit_ptr, h->d_q_ptr, h->d_q_units, h->d_q_head, h->d_partial, h->d_dense_part, h->d_dense_obs, h->d_sim, h->d_bar, h->d_wdesc,
-                  h->d_wunits, h->d_seg_end, h->d_prog, h->d_trace, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10};
+                  h->d_wunits, h->d_seg_end, h->d_prog, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10};
   for (void *q : ptrs) if (q) hipFree(q);
   for (double *q : h->snap_slabs) hipFree(q);
   if (h->h_cost) hipHostFree(h->h_cost);
@@ -4694,7 +3986,7 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     const long long nAb = (long long)(nA + n9);
     const unsigned grid = (unsigned)std::max<long long>((h->N + 255) / 256, std::min<long long>((nAb + 1023) / 1024, 4096));
     hipLaunchKernelGGL(k_point_inv, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
-                       h->d_Ab, nAb, h->d_prog, h->slot_pace ? (long long)h->slot_rounds * h->slot_nR * h->slot_nseg * PACE_STRIDE : 0LL,
+                       h->d_Ab, nAb, h->d_prog, (long long)h->slot_rounds * h->slot_nR * h->slot_nseg * PACE_STRIDE,
                        h->schur_mode == SCHUR_DENSE ? 1 : 0);
   }
   if (h->use_pairs) {
@@ -4705,12 +3997,11 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
       if (h->n_waves)
         hipLaunchKernelGGL(k_schur_slots, dim3(h->n_waves), dim3(64), SLOT_LDS, h->stream, h->d_wdesc,
                            h->d_wunits, h->d_it_x, (const int *)nullptr, (const int *)nullptr, h->d_rec, h->d_PB, c, h->f0, h->d_partial,
-                           h->pair_static ? nullptr : h->d_q_head, h->slot_nR, h->n_waves / std::max(1, h->slot_nR), h->d_seg_end,
-                           h->slot_pace ? h->d_prog : nullptr, h->slot_nseg, h->slot_lag, h->d_trace, h->d_range_o0);
+                           (int *)nullptr, h->slot_nR, h->n_waves / std::max(1, h->slot_nR), h->d_seg_end, h->d_prog, h->slot_nseg, SLOT_LAG,
+                           h->d_range_o0);
     } else if (h->n_units) {
-      const bool stat = h->pair_static;
-      hipLaunchKernelGGL(big ? k_schur_pairs_big : k_schur_pairs, dim3(stat ? 8 * h->q_max : h->n_units), dim3(64),
-                         PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, stat ? nullptr : h->d_q_head, h->d_it_k,
+      hipLaunchKernelGGL(big ? k_schur_pairs_big : k_schur_pairs, dim3(8 * h->q_max), dim3(64),
+                         PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, (int *)nullptr, h->d_it_k,
                          h->d_it_l, h->d_it_a, h->d_rec, h->d_PB, c, h->f0, h->d_partial);
     }
     hipLaunchKernelGGL(k_schur_reduce, dim3((unsigned)((long long)m * (m + 1) / 2)), dim3(128), 0, h->stream, m, h->d_unit_ptr,
@@ -4741,14 +4032,6 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     const long long n_el = (long long)nA + 9 * m;
     hipLaunchKernelGGL(k_schur_dense_finish, dim3((unsigned)((n_el + 3) / 4)), dim3(256), 0, h->stream, m, T, h->dense_blocks,
                        (const double *)h->d_dense_part, c, d_A, d_b);
-  } else if (h->nobs) {
-    Timed t(h, MVBA_K_SCHUR);
-    const size_t lds = (81 * (size_t)h->lseg + 9) * sizeof(double);
-    const bool big = h->nobs * 128LL >= (1LL << 32) || h->force_big;  // (MVBA_FORCE_BIG: exercise the 64-bit-offset kernels at test sizes)
-    auto kern = h->nsp ? (big ? k_schur_strip<true, true> : k_schur_strip<false, true>)
-                       : (big ? k_schur_strip<true, false> : k_schur_strip<false, false>);
-    hipLaunchKernelGGL(kern, dim3(m, h->nchunks, h->nseg), dim3(h->schur_threads), lds, h->stream, m, h->nchunks, h->lseg, h->nsp,
-                       h->d_chunk_ptr, h->d_csc, h->d_cam, h->d_rec, h->d_PB, c, h->f0, d_A, d_b);
   }
   MVBA_HIP(hipGetLastError());
   if (h->comm) {
@@ -4787,13 +4070,9 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     }
     const int S = (D + SBW - 1) / SBW;
     if (onepass && (S == 1 || S < h->n_cu)) {  // one persistent pass for L^T x = y (see k_chol_backsolve_all)
-      // few bulk workgroups (each then takes several column groups per step): a barrier gets dearer with
-      // every workgroup -- its release/acquire writes back and invalidates that XCD's L2 for everybody on
-      // it.  D = 4493: 16 bulk workgroups 2.75 ms per solve, 64: 2.93, 220: 3.24 (tools/ab_solve.py).
-      // (point to point -- the default since round 4 -- nobody pays for anybody else: one bulk workgroup per column group)
-      const bool flow = h->chol_flow;
-      const int ngrp = ((S - 1) * SBW + 31) / 32, nbulk = S > 1 ? std::max(1, std::min(std::min(h->n_cu - S, flow ? ngrp : 16), ngrp)) : 0;
-      hipLaunchKernelGGL(flow ? k_chol_backsolve_all<true> : k_chol_backsolve_all<false>, dim3(S + nbulk), dim3(SUPER_THREADS),
+      // (point to point, nobody pays for anybody else: one bulk workgroup per column group)
+      const int ngrp = ((S - 1) * SBW + 31) / 32, nbulk = S > 1 ? std::max(1, std::min(h->n_cu - S, ngrp)) : 0;
+      hipLaunchKernelGGL(k_chol_backsolve_all<true>, dim3(S + nbulk), dim3(SUPER_THREADS),
                          BACKSOLVE_LDS, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles, h->d_Lblk, h->d_dxi, h->d_flag,
                          h->d_bar, h->barrier_polls);
     } else
@@ -4814,9 +4093,8 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     if (h->N) {
       const size_t lds = h->gcam ? 0 : (size_t)m * (CAM_LDS + DXI_LDS) * sizeof(double);
       cam_tables(h, h->d_cam15[h->cur], h->d_dxi);
-      const int lanes_env = h->backsub_lanes;  // (MVBA_BACKSUB_LANES at create; 0 = by mean degree)
-      const double deg = (double)h->nobs / (double)h->N;
-      const int G = lanes_env ? lanes_env : (deg <= 40.0 ? 2 : (deg <= 100.0 ? 4 : 8));
+      const double deg = (double)h->nobs / (double)h->N;  // lanes per point by mean degree
+      const int G = deg <= 40.0 ? 2 : (deg <= 100.0 ? 4 : 8);
       // (a camera table above half the LDS leaves one block per CU: 1024 threads then, so that the CU still holds 16 waves)
       // (16 waves per CU is what the registers allow: 256-thread blocks reach it while four of them fit -- tables up to 40 KiB,
       // ~180 cameras --, 512-thread blocks while two fit, one 1024-thread block beyond)
@@ -4842,9 +4120,9 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
   int rc = global_cost(h, E_trial);
   if (rc) return rc;
   if ((*h->h_flag & 8) && !(*h->h_flag & 1)) {
-    // A device-wide barrier of the persistent back-substitution gave up: its grid was not co-resident (another
+    // A wait of the persistent back-substitution gave up: its grid was not co-resident (another
     // process holds CUs -- e.g. ranks sharing a GPU).  Nothing is lost but time: the packed [A|b] is intact, so the
-    // solve is redone with one launch per super-block (no barrier), and this handle stays on that path.
+    // solve is redone with one launch per super-block (no waits), and this handle stays on that path.
     MVBA_HIP(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
     h->chol_onepass = false;
     h->stats.n_barrier_fallback++;
@@ -4888,7 +4166,7 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
   if (*h->h_flag) {
     const int fl = *h->h_flag;
     hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream);
-    if (fl & 8) return fail(MVBA_ERR_HIP, "k_chol_backsolve_all: a device-wide barrier timed out twice (is another process holding the CUs?)");
+    if (fl & 8) return fail(MVBA_ERR_HIP, "k_chol_backsolve_all: a wait for a progress word timed out twice (is another process holding the CUs?)");
     return fail(MVBA_ERR_SINGULAR, (fl & 1) ? "Singular matrix" : "Singular matrix (reduced camera system)");
   }
   if (h->check_solve) {

@@ -2778,9 +2778,7 @@ int mvsvd_create(int64_t max_rows, int32_t n_cols, int32_t dtype, int32_t device
   mvsvd_handle *h = new mvsvd_handle();
   MVBA_HIP(hipGetDevice(&h->device));
   h->dtype = dtype; h->n = n_cols; h->max_rows = max_rows;
-  // (MVSVD_WIDE_MIN: experiments -- the column count above which the block iteration takes over, never below its own width)
-  const int wide_min = getenv("MVSVD_WIDE_MIN") ? std::max(WB, atoi(getenv("MVSVD_WIDE_MIN"))) : WIDE_MIN;
-  const bool wide = n_cols > wide_min, dense = n_cols <= JACOBI_MAX;  // beyond JACOBI_MAX no n x n matrix at all: see run_wide
+  const bool wide = n_cols > WIDE_MIN, dense = n_cols <= JACOBI_MAX;  // beyond JACOBI_MAX no n x n matrix at all: see run_wide
   h->wide = wide;
   const size_t el = dtype ? 8 : 4, nn = dense ? (size_t)n_cols * n_cols : (size_t)WB * WB;
   const int gram_n = dense ? n_cols : WB;  // the Gram kernels run on the workspace's matrix and on the wide path's 32-column blocks

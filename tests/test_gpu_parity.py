@@ -375,8 +375,8 @@ def test_virtual_point_shards_sum_to_the_full_reduced_system():
 
 @pytest.mark.parametrize("n,m,p", [(40, 2, 1.0), (900, 300, 0.06), (3000, 646, 0.04), (3000, 647, 0.04), (2500, 1000, 0.03)])
 def test_extreme_camera_counts_vs_oracle(n, m, p):
-    """m = 2 (smallest legal gauge: D = 11), m = 300 (the LDS strip of one camera no longer fits and is cut into column
-    segments, the path BASELINE config 4 with m = 500 takes), m = 646 (the largest count whose camera tables fit one
+    """m = 2 (smallest legal gauge: D = 11), m = 300 (hundreds of cameras on the pair-major unit form, the path BASELINE
+    config 4 with m = 500 takes), m = 646 (the largest count whose camera tables fit one
     workgroup's LDS) and, since round 5, beyond it: 647 and 1000 cameras (K1 / K5 / K6 read the tables from device memory;
     the reference takes any count, ref :11-75)."""
     sc = make_scene(n, m, vis_p=p)
@@ -429,7 +429,7 @@ def test_indefinite_reduced_system_takes_the_lu_path_like_numpy(n, m, p):
 def test_config4_shape_500_cameras_8_virtual_shards():
     """BASELINE config 4's shape (500 cameras, 5 % visibility, points sharded 8 ways) at 1200 points:
     the partial reduced systems of the 8 shards add up to the unsharded one, which matches the
-    oracle, and one LM step on the full problem agrees with the oracle (D = 4493, 3 strip segments)."""
+    oracle, and one LM step on the full problem agrees with the oracle (D = 4493)."""
     from lib import _distributed as D
 
     m = 500
@@ -471,10 +471,9 @@ def test_config4_shape_500_cameras_8_virtual_shards():
 
 @pytest.mark.parametrize("n,m,p", [(600, 9, 0.6), (3000, 50, 0.3), (900, 300, 0.06)])
 def test_dense_solve_variants_agree(n, m, p, monkeypatch):
-    """The dense solve has three back-substitutions -- one persistent launch synchronised point to point (progress words,
-    sc1 atomics on y, the super-block's inverse applied at the step: the default), the same launch with round 2's
-    device-wide barriers (MVBA_CHOL=barriers), one launch per super-block (MVBA_CHOL=launches, also the fallback when the
-    persistent grid could not be co-resident) -- and two trailing updates (k_chol_trail64 from 200 workgroups up, which the
+    """The dense solve has two back-substitutions -- one persistent launch synchronised point to point (progress words,
+    sc1 atomics on y, the super-block's inverse applied at the step: the default) and one launch per super-block
+    (MVBA_CHOL=launches, also the fallback when the persistent grid could not be co-resident) -- and two trailing updates (k_chol_trail64 from 200 workgroups up, which the
     D = 2693 case reaches; k_chol_trail32 otherwise, everywhere with MVBA_TRAIL64_MIN set high).  All must give the camera
     step of the oracle's solve (D = 74, 443, 2693)."""
     sc = make_scene(n, m, vis_p=p)
@@ -487,8 +486,7 @@ def test_dense_solve_variants_agree(n, m, p, monkeypatch):
     ref = np.zeros(9 * m)
     ref[g.keep] = g.dxi_red
     got = {}
-    modes = {"default": {}, "launches": {"MVBA_CHOL": "launches"}, "barriers": {"MVBA_CHOL": "barriers"},
-             "trail32": {"MVBA_TRAIL64_MIN": "100000000"}}
+    modes = {"default": {}, "launches": {"MVBA_CHOL": "launches"}, "trail32": {"MVBA_TRAIL64_MIN": "100000000"}}
     for mode, env in modes.items():
         for k in ("MVBA_CHOL", "MVBA_TRAIL64_MIN"):
             monkeypatch.delenv(k, raising=False)
@@ -502,7 +500,7 @@ def test_dense_solve_variants_agree(n, m, p, monkeypatch):
         got[mode] = eng.debug_read("dxi")
         assert eng.stats()["counts"]["lu_fallback"] == 0 and eng.stats()["counts"]["barrier_fallback"] == 0
         np.testing.assert_allclose(got[mode], ref, rtol=0, atol=1e-9 * np.abs(ref).max())
-    for mode in ("launches", "barriers", "trail32"):
+    for mode in ("launches", "trail32"):
         np.testing.assert_allclose(got[mode], got["default"], rtol=0, atol=1e-12 * np.abs(ref).max())
 
 
@@ -524,12 +522,12 @@ def test_repeated_dense_solves_are_bitwise_identical():
     assert counts["barrier_fallback"] == 0 and counts["lu_fallback"] == 0
 
 
-@pytest.mark.parametrize("n,m,p,chol", [(4000, 30, 0.3, None), (20000, 120, 0.1, None), (3000, 300, 0.06, None), (3000, 300, 0.06, "barriers"),
+@pytest.mark.parametrize("n,m,p,chol", [(4000, 30, 0.3, None), (20000, 120, 0.1, None), (3000, 300, 0.06, None),
                                          (3000, 300, 0.06, "launches")])
 def test_dense_solve_residual_check_passes_on_every_back_substitution_variant(n, m, p, chol, monkeypatch):
     """MVBA_CHECK_SOLVE=1 (debug mode): after every dense solve the residual b - A dxi of the reduced camera system is formed on the
     host from the packed [A|b] and must be at rounding level -- here over LM runs at one and several super-blocks (D = 263 / 1073 /
-    2693) and on the three back-substitution variants (point-to-point hand-overs, device-wide barriers, one launch per super-block)."""
+    2693) and on both back-substitution variants (point-to-point hand-overs, one launch per super-block)."""
     from lib.bundle_adjustment import lm_loop
 
     monkeypatch.setenv("MVBA_CHECK_SOLVE", "1")
@@ -548,7 +546,7 @@ def test_dense_solve_residual_check_passes_on_every_back_substitution_variant(n,
 
 
 def test_barrier_timeout_of_the_persistent_back_substitution_is_redone_with_launches(monkeypatch):
-    """k_chol_backsolve_all's waits (on its progress words; device-wide barriers in the MVBA_CHOL=barriers form) give up
+    """k_chol_backsolve_all's waits (on its progress words) give up
     after a bounded number of polls (a grid that is not co-resident -- another process on the CUs -- must drain, not hang).
     The step then does NOT fail: the solve is redone with one launch per super-block from the intact packed system, counted
     in mvba_stats, and the handle stays on that path.  MVBA_CHOL_BARRIER_POLLS=0 makes every wait give up at once
@@ -572,18 +570,17 @@ def test_barrier_timeout_of_the_persistent_back_substitution_is_redone_with_laun
     assert E2 == pytest.approx(ref.try_step(1e-2), rel=1e-12)
 
 
-@pytest.mark.parametrize("n,m,p,form", [(3000, 14, 0.5, "strip"), (900, 300, 0.06, "strip"), (3000, 14, 0.5, "pairs"),
+@pytest.mark.parametrize("n,m,p,form", [(900, 300, 0.06, "pairs"), (3000, 14, 0.5, "pairs"),
                                          (3000, 14, 0.5, "slots"), (20000, 60, 0.15, "slots"), (20000, 60, 0.15, "pairs"),
                                          (3000, 14, 0.5, "slots:3"), (20000, 60, 0.15, "slots:4"), (2500, 300, 0.04, "slots"),
                                          (2000, 500, 0.03, "slots"), (3001, 12, 1.0, "dense"), (1003, 21, 1.0, "dense"), (50, 2, 1.0, "dense"),
                                          (3001, 12, 1.0, "pairs"), (999, 21, 1.0, "slots"), (3001, 14, 0.8, "dense"), (2003, 21, 0.65, "dense"),
                                          (1000, 6, 0.5, "dense")])
 def test_every_schur_kernel_form_matches_the_oracle(n, m, p, form, monkeypatch):
-    """The three forms of K3 -- the camera-strip kernel (round 1, plain and column-segmented), the
-    pair-major unit kernel (round 2) and the slot-resident kernel (round 3: one round of all camera pairs up to
+    """The forms of K3 -- the pair-major unit kernel (round 2) and the slot-resident kernel (round 3: one round of all camera pairs up to
     ~100 cameras; round 4: beyond that, one round per pair of camera GROUPS inside one launch -- "slots:g" forces
     g groups at a small camera count, m = 300 / 500 take 4 / 7 groups by themselves) -- each forced with
-    MVBA_SCHUR, the first two in their 64-bit-offset build (MVBA_FORCE_BIG; the slot form addresses its records
+    MVBA_SCHUR, the unit form in its 64-bit-offset build (MVBA_FORCE_BIG, also at 300 cameras; the slot form addresses its records
     relative to the point range instead), and the dense-visibility form (round 5: every point seen by every camera, up to 21
     cameras -- the rank-3N update of the whole reduced matrix on the matrix cores, no index; point counts that are not a multiple
     of its chunk, the largest and the smallest camera count, the pair-major forms on the same full-visibility scenes, and scenes
@@ -592,7 +589,6 @@ def test_every_schur_kernel_form_matches_the_oracle(n, m, p, form, monkeypatch):
     if ":" in form:
         form, groups = form.split(":")
         monkeypatch.setenv("MVBA_SLOT_GROUPS", groups)
-        monkeypatch.setenv("MVBA_POINT_ORDER", "greedy")  # (and the low-discrepancy sweep order of the points with them)
     if form not in ("slots", "dense"):
         monkeypatch.setenv("MVBA_FORCE_BIG", "1")
     monkeypatch.setenv("MVBA_SCHUR", form)
@@ -825,8 +821,6 @@ def test_schur_index_built_on_the_device_is_the_host_built_one(n, m, p, monkeypa
     threads.  The two builds must give the kernel the same arrays, entry for entry."""
     sc = make_scene(n, m, vis_p=p)
     monkeypatch.setenv("MVBA_SCHUR", "slots")  # (small scenes would take the unit form by default)
-    if m == 24:  # one case over the low-discrepancy sweep order of the points (MVBA_POINT_ORDER=greedy)
-        monkeypatch.setenv("MVBA_POINT_ORDER", "greedy")
 
     def build():
         ba = BundleAdjuster.from_observations(sc.n_points, m, sc.pt_ptr, sc.cam_idx, sc.xy, sc.init_X, sc.init_K,

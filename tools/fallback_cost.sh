@@ -1,6 +1,6 @@
 #!/bin/bash
-# what the co-residency fallbacks cost when they are taken (a shared GPU): the back-substitution as per-block launches / with
-# device-wide barriers instead of point-to-point words, the slot kernel without pacing -- config 3 and D = 4493 (config 4's shard)
+# what the co-residency fallback costs when it is taken (a shared GPU): the back-substitution as per-block launches instead of
+# point-to-point words, chosen up front / after every wait of the persistent launch gave up -- config 3 and D = 4493 (config 4's shard)
 cd "$(dirname "$0")/.."; export OUT=${OUT:-runs}; mkdir -p "$OUT"; export TMPDIR=/tmp
 line() {  # tag, env..., then bench args after --
   tag=$1; shift
@@ -12,8 +12,6 @@ print('$tag'.ljust(34), 'it/s', round(d['value'],1), 'ms/step', round(d['ms_per_
 }
 line c3_default -- --steps 20 --warmup 5
 line c3_backsub_launches MVBA_CHOL=launches -- --steps 20 --warmup 5
-line c3_backsub_barriers MVBA_CHOL=barriers -- --steps 20 --warmup 5
-line c3_backsub_barrier_fallback MVBA_CHOL=barriers MVBA_CHOL_BARRIER_POLLS=0 -- --steps 20 --warmup 5
-line c3_no_pacing MVBA_SLOT_SEG=0 -- --steps 20 --warmup 5
+line c3_backsub_fallback MVBA_CHOL_BARRIER_POLLS=0 -- --steps 20 --warmup 5
 line c4shard_default -- --config4-shard --steps 6 --warmup 2
 line c4shard_backsub_launches MVBA_CHOL=launches -- --config4-shard --steps 6 --warmup 2

@@ -29,7 +29,7 @@ out = {"n_obs": n_obs, "n_points": n_points, "commit": tag, "csrc_sha256": csrc_
        "source": "rocprofv3 --kernel-trace --pmc <one group per pass>, bench.py --steps 3 --warmup 1 --no-cpu-baseline, mean over the "
                  "launches; tools/final_profile.sh " + tag,
        "note": "gfx950 FETCH_SIZE tallies 128-byte requests at 64 bytes (MI355X_MICROARCH.md): traffic = (2*FETCH + WRITE) KiB"}
-for k in ("k_resid_jac", "k_schur_slots", "k_schur_pairs", "k_schur_strip"):
+for k in ("k_resid_jac", "k_schur_slots", "k_schur_pairs"):
     if k in acc:
         out["kernels"][k] = {names[c]: sum(v) / len(v) for c, v in acc[k].items() if c in names}
 print(json.dumps(out, indent=1))

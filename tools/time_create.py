@@ -1,8 +1,8 @@
-"""Wall time of mvba_create's stages (MVBA_CREATE_TRACE=1) for a fully visible scene handed over as image planes, and of the whole
+"""Wall time of mvba_create's stages (MVBA_CREATE_TIMING=1) for a fully visible scene handed over as image planes, and of the whole
 BundleAdjuster() around it.  python tools/time_create.py [points images]"""
 import os, sys, time
 
-os.environ["MVBA_CREATE_TRACE"] = "1"
+os.environ["MVBA_CREATE_TIMING"] = "1"
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "3d-reconstruction-from-multi-view-exp_amd"))
 import numpy as np
 from lib import _mvba

@@ -1,5 +1,5 @@
-"""K3 (Schur) launch time of a scene shape, robust to timing-only builds whose numbers are wrong (knock-out / h-in-the-record
-builds: the LM loop would fail on them): linearize once, then `try_step` n times, errors ignored, device time from the engine's
+"""K3 (Schur) launch time of a scene shape, robust to experimental builds whose numbers are wrong (the LM loop would fail on
+them): linearize once, then `try_step` n times, errors ignored, device time from the engine's
 own hipEvents.   usage: python tools/time_schur.py [points cams vis [reps]]      (MVBA_LIBRARY picks the build)"""
 import os
 import sys
