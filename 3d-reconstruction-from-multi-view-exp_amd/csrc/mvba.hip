@@ -585,7 +585,7 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
   // SLOTS pacing: the waves of a point range keep within `lag` segments of each other, so that what they gather at
   // any moment fits their XCD's L2.  A performance hint only: a wave that waits too long (its siblings are not
   // resident: somebody else holds the CUs) stops pacing and runs on.
-  bool pacing = SLOTS && pace.prog != nullptr;
+  bool pacing = SLOTS;
   int seg = 0, seg_stop = pacing ? as_const(pace.seg_end)[0] * PSTEP : 0x7fffffff;
   auto pace_at = [&](const int s0) {
     while (s0 == seg_stop) {  // (wave-uniform) this wave has left segment `seg`
@@ -722,7 +722,7 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
   // J_C row i = rs_i * (record columns): f | u,v (1/f0) | t (-Jx) | omega; the same factors per column
   const double cs0 = cg == 1 ? -1.0 : 1.0, cs12 = cg == 0 ? cu : cs0;
   if (SLOTS) {  // every slot holds a finished block of its own: no sum over lanes
-    if (pace.prog != nullptr && lane == 0)
+    if (lane == 0)
       for (; seg < pace.nseg; ++seg) __hip_atomic_fetch_add(pace.prog + PACE_STRIDE * seg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int u = it < PSTEP ? slot_unit[it] : -1;
     if (u >= 0) {
@@ -781,33 +781,20 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
 // the block's slowest wave has finished (4 waves per block: 1.945 ms, 2: 1.92, 1: 1.89 at config 3).
 template <bool BIG>
 __device__ __forceinline__ void schur_pairs_wave(const int4 *__restrict__ units, const int *__restrict__ q_ptr,
-                                                       const int *__restrict__ q_units, int *__restrict__ head,
-                                                       const int *__restrict__ it_k, const int *__restrict__ it_l,
-                                                       const int *__restrict__ it_a, const double2 *__restrict__ rec,
+                                                       const int *__restrict__ q_units, const int *__restrict__ it_k,
+                                                       const int *__restrict__ it_l, const int *__restrict__ it_a,
+                                                       const double2 *__restrict__ rec,
                                                        const double *__restrict__ PB, double c, double f0,
                                                        double *__restrict__ partial) {
   extern __shared__ char smem_pairs[];
   const int lane = threadIdx.x;
   char *wbuf = smem_pairs;
-  // ---- take one unit.  Static (head == nullptr, what mvba_create launches): block b takes entry b / 8 of queue b % 8 -- no
-  // atomic on the critical path; it relies on the round-robin block -> XCD placement for locality
-  // only, never for correctness (1.90 -> 1.87 ms).  Dynamic (round 2's, no longer launched): own XCD's queue
-  // first (XCC_ID), then the others; every queue entry is taken exactly once, the grid has as many
-  // waves as there are units and a wave takes at most one.
+  // ---- take one unit: block b takes entry b / 8 of queue b % 8 -- no atomic on the critical path; it relies on the
+  // round-robin block -> XCD placement for locality only, never for correctness (1.90 -> 1.87 ms against queues
+  // taken by atomics)
   int pos = -1;
-  if (!head) {
-    const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
-    if (q < q_ptr[x + 1] - q_ptr[x]) pos = q_ptr[x] + q;
-  } else if (lane == 0) {
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-    for (int t = 0; t < 8 && pos < 0; ++t) {
-      const int x = (xcc + t) & 7, len = q_ptr[x + 1] - q_ptr[x];
-      if (len <= 0) continue;
-      const int q = atomicAdd(&head[x], 1);
-      if (q < len) pos = q_ptr[x] + q;
-    }
-  }
+  const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
+  if (q < q_ptr[x + 1] - q_ptr[x]) pos = q_ptr[x] + q;
   pos = __builtin_amdgcn_readfirstlane(pos);
   if (pos < 0) return;
   // unit id (where its partial goes) and descriptor, both in queue order: two independent SCALAR loads
@@ -824,15 +811,15 @@ __device__ __forceinline__ void schur_pairs_wave(const int4 *__restrict__ units,
 }
 
 #define MVBA_PAIRS_ARGS                                                                                                   \
-  const int4 *__restrict__ units, const int *__restrict__ q_ptr, const int *__restrict__ q_units, int *__restrict__ head, \
+  const int4 *__restrict__ units, const int *__restrict__ q_ptr, const int *__restrict__ q_units,                        \
       const int *__restrict__ it_k, const int *__restrict__ it_l, const int *__restrict__ it_a,                          \
       const double2 *__restrict__ rec, const double *__restrict__ PB, double c, double f0, double *__restrict__ partial
 // (two plain kernels rather than one template, so that profiles show one stable name per variant)
 __global__ __launch_bounds__(64, 3) void k_schur_pairs(MVBA_PAIRS_ARGS) {
-  schur_pairs_wave<false>(units, q_ptr, q_units, head, it_k, it_l, it_a, rec, PB, c, f0, partial);
+  schur_pairs_wave<false>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial);
 }
 __global__ __launch_bounds__(64, 3) void k_schur_pairs_big(MVBA_PAIRS_ARGS) {  // 64-bit record / point-block offsets
-  schur_pairs_wave<true>(units, q_ptr, q_units, head, it_k, it_l, it_a, rec, PB, c, f0, partial);
+  schur_pairs_wave<true>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial);
 }
 
 // ------------------------------------------------------------------ K3 (slot-resident form)
@@ -855,39 +842,23 @@ __device__ __forceinline__ void schur_slots_wave(const int4 *__restrict__ wdesc,
                                                  const int *__restrict__ it_k, const int *__restrict__ it_l,
                                                  const int *__restrict__ it_a, const double2 *__restrict__ rec,
                                                  const double *__restrict__ PB, double c, double f0,
-                                                 double *__restrict__ partial, int *__restrict__ head, int nR, int wpr,
-                                                 const int *__restrict__ seg_end, int *__restrict__ prog, int nseg, int lag,
+                                                 double *__restrict__ partial, int nR, const int *__restrict__ seg_end,
+                                                 int *__restrict__ prog, int nseg, int lag,
                                                  const long long *__restrict__ range_o0) {
   extern __shared__ char smem_pairs[];
-  // which wave of which range: static (head == nullptr) block b IS wave b / nR of range b % nR; dynamic: the wave
-  // reads the XCD it runs on and takes the next wave of a range of that XCD (r % 8 == XCC_ID), then of the others
-  int bid = blockIdx.x;
-  if (head) {
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-    bid = -1;
-    if (threadIdx.x == 0) {
-      for (int t = 0; t < nR && bid < 0; ++t) {
-        const int r = ((xcc & 7) + t) % nR;
-        const int q = atomicAdd(&head[r], 1);
-        if (q < wpr) bid = nR * q + r;
-      }
-    }
-    bid = __builtin_amdgcn_readfirstlane(bid);
-    if (bid < 0) return;
-  }
+  // which wave of which range: block b IS wave b / nR of range b % nR
+  const int bid = blockIdx.x;
   const int MVBA_CONST_AS *dp = as_const(reinterpret_cast<const int *>(wdesc)) + 4 * (size_t)bid;
   const int d_x = dp[0], d_y = dp[1], nsteps = dp[2], flags = dp[3];
   if (nsteps <= 0) return;  // (wave-uniform) a wave whose lists are all empty in this range: no units, nothing to write
   const long long beg = ((long long)d_y << 32) | (unsigned)d_x;
   const int *su = wunits + (size_t)bid * PSTEP;
-  // flags: bit 0 diagonal wave | bits 8..19 live waves of this (round, range) | bits 20..30 round
-  const int r = bid % nR, live = (flags >> 8) & 0xfff, round = (flags >> 20) & 0x7ff;
+  // flags: bit 0 diagonal wave | bits 8..19 live waves of this range
+  const int r = bid % nR, live = (flags >> 8) & 0xfff;
   // the record indices of the step rows are RELATIVE to the range's first observation: the 32-bit byte offsets of the
   // gathers then span a range's records (4 GiB = 33.5 M observations per range), not the scene's
   const double2 *rec_r = rec + (size_t)as_const(range_o0)[r] * REC;
-  SlotPace pace{nullptr, nullptr, 0, 0, 2};
-  if (prog) pace = SlotPace{seg_end + (size_t)bid * nseg, prog + ((size_t)round * nR + r) * nseg * PACE_STRIDE, live, nseg, lag};
+  const SlotPace pace{seg_end + (size_t)bid * nseg, prog + (size_t)r * nseg * PACE_STRIDE, live, nseg, lag};
   if (flags & 1)
     schur_pairs_unit<true, false, true>(smem_pairs, (int)threadIdx.x, beg, nsteps * PSTEP, it_k, it_l, it_a, rec_r, PB, c, 1.0 / f0, partial, su, pace);
   else
@@ -896,10 +867,10 @@ __device__ __forceinline__ void schur_slots_wave(const int4 *__restrict__ wdesc,
 #define MVBA_SLOTS_ARGS                                                                                                  \
   const int4 *__restrict__ wdesc, const int *__restrict__ wunits, const int *__restrict__ it_k, const int *__restrict__ it_l, \
       const int *__restrict__ it_a, const double2 *__restrict__ rec, const double *__restrict__ PB, double c, double f0,  \
-      double *__restrict__ partial, int *__restrict__ head, int nR, int wpr, const int *__restrict__ seg_end,            \
-      int *__restrict__ prog, int nseg, int lag, const long long *__restrict__ range_o0
+      double *__restrict__ partial, int nR, const int *__restrict__ seg_end, int *__restrict__ prog,                      \
+      int nseg, int lag, const long long *__restrict__ range_o0
 __global__ __launch_bounds__(64, 3) void k_schur_slots(MVBA_SLOTS_ARGS) {
-  schur_slots_wave(wdesc, wunits, it_k, it_l, it_a, rec, PB, c, f0, partial, head, nR, wpr, seg_end, prog, nseg, lag, range_o0);
+  schur_slots_wave(wdesc, wunits, it_k, it_l, it_a, rec, PB, c, f0, partial, nR, seg_end, prog, nseg, lag, range_o0);
 }
 
 // One thread per element of a pair's block: the pair's unit partials in unit order -> packed strips.
@@ -908,8 +879,7 @@ __global__ __launch_bounds__(64, 3) void k_schur_slots(MVBA_SLOTS_ARGS) {
 // added in unit order, so the result does not depend on the schedule.
 __global__ __launch_bounds__(128) void k_schur_reduce(int m, const int *__restrict__ unit_ptr,
                                                       const double *__restrict__ partial, double *__restrict__ Afull,
-                                                      double *__restrict__ bfull, int *__restrict__ head) {
-  if (blockIdx.x == 0 && threadIdx.x < 64) head[threadIdx.x] = 0;  // work queues for the next launch
+                                                      double *__restrict__ bfull) {
   // pair index -> (k, l): pairs of strip k start at k m - k (k - 1) / 2
   const long long p = blockIdx.x;
   int k = (int)((2.0 * m + 1.0 - sqrt((2.0 * m + 1.0) * (2.0 * m + 1.0) - 8.0 * (double)p)) * 0.5);
@@ -2824,7 +2794,7 @@ struct mvba_handle {
   bool use_pairs = true;              // pair-major index present (schur_mode != SCHUR_DENSE)
   int schur_mode = 2;                 // SCHUR_PAIRS / SCHUR_SLOTS (see k_schur_slots) / SCHUR_DENSE
   long long n_items = 0, n_items_offdiag = 0, n_slot_items = 0;
-  int n_units = 0, rccl_version = 0, q_max = 0, n_waves = 0, slot_nR = 8, slot_nseg = 0, slot_rounds = 1, slot_groups = 1;
+  int n_units = 0, rccl_version = 0, q_max = 0, n_waves = 0, slot_nR = 8, slot_nseg = 0;
   long long *d_range_o0 = nullptr;    // slot form: first observation of every point range (the record base of its waves)
   int *d_seg_end = nullptr, *d_prog = nullptr;
   bool check_solve = false;           // MVBA_CHECK_SOLVE=1: every accepted dense solve is checked on the host against the packed system it solved
@@ -2836,8 +2806,7 @@ struct mvba_handle {
   int *d_it_x = nullptr;              // slot form: the step-major index, 64 ints per step (k[21] | l[21] | a[21] | pad)
   int *d_wunits = nullptr;
   bool force_big = false;             // MVBA_FORCE_BIG: the 64-bit-offset kernels at any size
-  int *d_it_k = nullptr, *d_it_l = nullptr, *d_it_a = nullptr, *d_unit_ptr = nullptr, *d_q_ptr = nullptr, *d_q_units = nullptr,
-      *d_q_head = nullptr;
+  int *d_it_k = nullptr, *d_it_l = nullptr, *d_it_a = nullptr, *d_unit_ptr = nullptr, *d_q_ptr = nullptr, *d_q_units = nullptr;
   int4 *d_units = nullptr;
   double *d_partial = nullptr;
   double *d_dense_part = nullptr;     // SCHUR_DENSE: partial tiles per workgroup
@@ -3068,7 +3037,6 @@ struct CreateKnobs {
   bool schur_slots = false, schur_pairs = false, schur_dense = false;  // ... unless it is `dense`)
   bool index_host = false, index_global = false;  // MVBA_INDEX=host | global: where the Schur index is built
   bool force_big = false;                      // MVBA_FORCE_BIG
-  int slot_groups = 0;                         // MVBA_SLOT_GROUPS (0: by the L2 footprint)
   bool chol_launches = false;                  // MVBA_CHOL=launches
   int trail64_min = 200;                       // MVBA_TRAIL64_MIN
   unsigned barrier_polls = 1u << 22;           // MVBA_CHOL_BARRIER_POLLS
@@ -3089,7 +3057,6 @@ CreateKnobs read_create_knobs() {
   k.index_host = is(index, "host");
   k.index_global = is(index, "global");
   k.force_big = getenv("MVBA_FORCE_BIG") != nullptr;
-  if (const char *ev = getenv("MVBA_SLOT_GROUPS")) k.slot_groups = std::max(1, atoi(ev));
   k.chol_launches = is(getenv("MVBA_CHOL"), "launches");
   if (const char *ev = getenv("MVBA_TRAIL64_MIN")) k.trail64_min = std::max(0, atoi(ev));
   if (const char *ev = getenv("MVBA_CHOL_BARRIER_POLLS")) k.barrier_polls = (unsigned)std::max(0LL, atoll(ev));
@@ -3349,47 +3316,26 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     const int VP = vp_ptr[P];
     // ---- which form of the kernel: the slot-resident one (k_schur_slots) needs all lists that sweep a point range
     // TOGETHER resident on one XCD at once -- 9 waves per CU (LDS) x n_cu / 8 CUs x 21 slots = 6048 lists.  Up to ~100
-    // cameras at 10 % visibility (4950 pairs + ~1000 sub-lists of the diagonal pairs) that is every list: one ROUND.
-    // Beyond that the cameras are cut into `ng` groups and a round holds the pairs of one group pair (g1 <= g2): its
-    // waves sweep the range's points together and touch only the records of the two groups' cameras, so the footprint
-    // per round still fits the L2; the rounds of a range follow each other inside ONE launch (the blocks of round
-    // r + 1 start as the waves of round r finish).  A record is then read once per round its camera's group is in
-    // (ng + 1 times) instead of once per unit that needs it (the unit form: ~16 times from beyond the L2 at m = 500).
+    // cameras at 10 % visibility (4950 pairs + ~1000 sub-lists of the diagonal pairs) that is every list.  Beyond that
+    // the engine takes the unit form (cutting the cameras into groups swept in rounds lost to it on every workload
+    // measured: DESIGN.md 3.1, "Round 4").
     int n_cu_dev = 256;
     hipDeviceGetAttribute(&n_cu_dev, hipDeviceAttributeMultiprocessorCount, h->device);
     const int xcd_waves = std::max(1, n_cu_dev / 8) * (160 * 1024 / SLOT_LDS);  // 9 waves of 17,136 B of LDS per CU
-    int ng = 1, G = m, max_round_waves = 0;
-    auto round_waves = [&](int G_, int g1, int g2) {  // waves (of 21 lists) of round (g1, g2): diagonal + off-diagonal
-      long long ld = 0, lo = 0;
-      for (int k = g1 * G_; k < std::min(m, (g1 + 1) * G_); ++k) {
-        if (g1 == g2) ld += S[pair_id(k, k)];
-        for (int l = std::max(k + 1, g2 * G_); l < std::min(m, (g2 + 1) * G_); ++l) lo += S[pair_id(k, l)];
-      }
-      return (int)((ld + PSTEP - 1) / PSTEP + (lo + PSTEP - 1) / PSTEP);
-    };
-    if (knobs.slot_groups) ng = std::min(m, knobs.slot_groups);
-    for (;; ++ng) {
-      G = (m + ng - 1) / ng;
-      max_round_waves = 0;
-      for (int g1 = 0; g1 * G < m; ++g1)
-        for (int g2 = g1; g2 * G < m; ++g2) max_round_waves = std::max(max_round_waves, round_waves(G, g1, g2));
-      if (max_round_waves <= xcd_waves || G == 1) break;
+    long long n_diag_lists = 0, n_off_lists = 0;
+    for (int k = 0; k < m; ++k) {
+      n_diag_lists += S[pair_id(k, k)];
+      for (int l = k + 1; l < m; ++l) n_off_lists += S[pair_id(k, l)];
     }
-    ng = (m + G - 1) / G;  // (groups that hold a camera)
+    // waves (of 21 lists) per range: diagonal + off-diagonal
+    const long long slot_waves = (n_diag_lists + PSTEP - 1) / PSTEP + (n_off_lists + PSTEP - 1) / PSTEP;
     // (below ~4 M items the launch is all prologue and pacing: the unit form's many short waves win -- config 2,
     // 10k points x 20 cameras: 0.095 against 0.124 ms; equal at 5.5 M items; MVBA_SCHUR=slots keeps the slot form)
     const bool slots_forced = knobs.schur_slots;
     // (the gathers use 32-bit byte offsets: point rows from the array's start, records from their RANGE's first
     // observation -- checked below, once the ranges are known)
-    // More than one round pays only while a list keeps enough items per L2 window for its wave's 21 lists to march in
-    // step: at config 4 (500 cameras, 5 %: 390 items per list and range, ~10 per L2 window) the rounds cut the fabric
-    // traffic 2.3x (742 M -> 328 M lines per launch) and still lose to the unit form, 18.1 against 14.3 ms -- 19-40 % padding
-    // rows and the pacing waits of 250 waves on lists that sparse (profiles/r04_sweep_c4_rounds.txt) -- and with denser lists
-    // as well (1 M points x 200 cameras x 10 %, 1250 items per list and range, three rounds: 8.9 against 6.3 ms; 2 M x 150 x
-    // 10 %: 8.6 against 7.4; 1 M x 300 x 5 %: 5.3 against 4.3 -- profiles/r04_sweep_rounds_crossover.txt): more than one
-    // round runs only on request (MVBA_SCHUR=slots).
-    if (h->schur_mode == SCHUR_SLOTS && (max_round_waves > xcd_waves || (N + 1) * 128LL >= (1LL << 32) || h->force_big || ng > 2047 ||
-                                         ((T < 4000000 || ng > 1) && !slots_forced)))
+    if (h->schur_mode == SCHUR_SLOTS && (slot_waves > xcd_waves || (N + 1) * 128LL >= (1LL << 32) || h->force_big ||
+                                         (T < 4000000 && !slots_forced)))
       h->schur_mode = SCHUR_PAIRS;
     // point ranges.  Unit form: long runs for big problems, but small ones still get ~4096 units of >= 128 items.
     // Slot form: 8 ranges (one per XCD) -- 8 j while j ranges' worth of waves fit an XCD and a list keeps >= 64 items.
@@ -3397,7 +3343,7 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     std::vector<long long> range_lo;
     auto make_ranges = [&]() {
       if (h->schur_mode == SCHUR_SLOTS) {
-        const long long j = std::max<long long>(1, std::min<long long>(xcd_waves / std::max(1, max_round_waves), target / (8 * 64)));
+        const long long j = std::max<long long>(1, std::min<long long>(xcd_waves / std::max(1LL, slot_waves), target / (8 * 64)));
         nR = (int)(8 * std::min<long long>(j, 8));
         range_lo.assign(nR + 1, 0);
         // equal ITEM counts: the ranges run side by side, one per XCD
@@ -3420,7 +3366,7 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     // (few cameras with dense visibility: a dozen cameras are 78 lists = 5 waves per range, 320 waves on the whole chip even with 64
     // ranges -- 1 M points x 12 cameras, all visible: 9.3 ms against 4.9 for the unit form; at 20 cameras, 704 waves, the slot form is
     // ahead again, 9.8 against 10.8: profiles/r05_sweep_few_cameras.txt)
-    if (h->schur_mode == SCHUR_SLOTS && !slots_forced && (long long)nR * max_round_waves < 512) {
+    if (h->schur_mode == SCHUR_SLOTS && !slots_forced && nR * slot_waves < 512) {
       h->schur_mode = SCHUR_PAIRS;
       make_ranges();
     }
@@ -3516,29 +3462,23 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     unit_ptr[P] = (int)units.size();
     lap("units");
     if (slots) {
-      // ---- waves of 21 lists, every wave once per range, round by round (one round up to ~100 cameras); inside a round
-      // the diagonal pairs' sub-lists come FIRST: a CU's SIMDs arbitrate by age, the blocks dispatched last share a
-      // SIMD three ways as its youngest wave and fall behind -- and a diagonal step is the dearer one
+      // ---- waves of 21 lists, every wave once per range; the diagonal pairs' sub-lists come FIRST: a CU's SIMDs
+      // arbitrate by age, the blocks dispatched last share a SIMD three ways as its youngest wave and fall behind --
+      // and a diagonal step is the dearer one
       std::vector<int> wl;                    // [wave of a range][21] list ids v = vp_ptr[pair] + sub-list, -1: none
-      std::vector<int> w_round, w_isdiag;     // per wave of a range
-      int n_rounds = 0;
-      for (int g1 = 0; g1 * G < m; ++g1)
-        for (int g2 = g1; g2 * G < m; ++g2, ++n_rounds) {
-          std::vector<int> ld, lo;
-          for (int k = g1 * G; k < std::min(m, (g1 + 1) * G); ++k) {
-            if (g1 == g2)
-              for (int sI = 0; sI < S[pair_id(k, k)]; ++sI) ld.push_back(vp_ptr[pair_id(k, k)] + sI);
-            for (int l = std::max(k + 1, g2 * G); l < std::min(m, (g2 + 1) * G); ++l)
-              for (int sI = 0; sI < S[pair_id(k, l)]; ++sI) lo.push_back(vp_ptr[pair_id(k, l)] + sI);
-          }
-          for (const std::vector<int> *src : {&ld, &lo})
-            for (size_t first = 0; first < src->size(); first += PSTEP) {
-              for (int sl = 0; sl < PSTEP; ++sl) wl.push_back(first + sl < src->size() ? (*src)[first + sl] : -1);
-              w_round.push_back(n_rounds);
-              w_isdiag.push_back(src == &ld);
-            }
+      std::vector<int> w_isdiag;              // per wave of a range
+      std::vector<int> diag_lists, off_lists;
+      for (int k = 0; k < m; ++k) {
+        for (int sI = 0; sI < S[pair_id(k, k)]; ++sI) diag_lists.push_back(vp_ptr[pair_id(k, k)] + sI);
+        for (int l = k + 1; l < m; ++l)
+          for (int sI = 0; sI < S[pair_id(k, l)]; ++sI) off_lists.push_back(vp_ptr[pair_id(k, l)] + sI);
+      }
+      for (const std::vector<int> *src : {&diag_lists, &off_lists})
+        for (size_t first = 0; first < src->size(); first += PSTEP) {
+          for (int sl = 0; sl < PSTEP; ++sl) wl.push_back(first + sl < src->size() ? (*src)[first + sl] : -1);
+          w_isdiag.push_back(src == &diag_lists);
         }
-      const int wpr = (int)w_round.size();    // waves per range
+      const int wpr = (int)w_isdiag.size();   // waves per range
       const long long n_waves = (long long)wpr * nR;
       wdesc.assign(n_waves, make_int4(0, 0, 0, 0));
       wunits.assign((size_t)n_waves * PSTEP, -1);
@@ -3549,14 +3489,10 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
         for (int sl = 0; sl < PSTEP; ++sl) vs[sl] = src[sl];
         return (int)(b % nR);
       };
-      auto round_range = [&](long long b) { return (size_t)w_round[b / nR] * nR + (size_t)(b % nR); };
-      // a round touches the records of 2 of ng camera groups only: its skew and pacing segments, counted in
-      // observations of the range, stretch accordingly (the footprint in the L2 is what they bound)
-      const long long stretch = std::max(1, ng / 2);
       // Bounded-skew merge of a wave's lists into steps (see k_schur_slots)
-      const long long skew = SLOT_SKEW * stretch;
+      const long long skew = SLOT_SKEW;
       // pacing segments: seg_end[b][j] = steps wave b has taken when its slowest slot leaves segment j of the range
-      const long long segG = SLOT_SEG * stretch;
+      const long long segG = SLOT_SEG;
       int nSeg = 1;
       for (int r = 0; r < nR; ++r)
         nSeg = std::max<long long>(nSeg, (p->pt_ptr[range_lo[r + 1]] - p->pt_ptr[range_lo[r]] + segG - 1) / segG);
@@ -3642,15 +3578,15 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       for (long long b = 0; b < n_waves; ++b) w_beg[b + 1] = w_beg[b] + w_steps[b];
       const long long total_steps = w_beg[n_waves];
       if (total_steps * PSTEP >= (1LL << 40)) { mvba_destroy(h); return fail(MVBA_ERR_BADARG, "too many (point, camera pair) items"); }
-      {  // the step-major index -- its size follows the padding rows (more of them with MVBA_SLOT_GROUPS) -- against the memory that is
+      {  // the step-major index -- its size follows the padding rows -- against the memory that is
         // there, BEFORE anything of it is allocated: three 4-byte arrays of step rows, then the interleaved 256-byte rows beside them
         const size_t need = (size_t)total_steps * PSTEP * 12 + (size_t)total_steps * SLOT_IDX * 4 + seg_end.size() * 4;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) == hipSuccess && need > fr) {
           mvba_destroy(h);
           return fail(MVBA_ERR_BADARG, "the slot-form Schur index needs " + std::to_string(need >> 20) + " MiB (" + std::to_string(total_steps * PSTEP) + " step rows for " +
-                                           std::to_string(T) + " items: " + std::to_string(n_rounds) + " rounds x " + std::to_string(nR) + " ranges, skew " + std::to_string(skew) +
-                                           "), " + std::to_string(fr >> 20) + " MiB of device memory are free: relax MVBA_SLOT_GROUPS or use MVBA_SCHUR=pairs");
+                                           std::to_string(T) + " items: " + std::to_string(nR) + " ranges, skew " + std::to_string(skew) + "), " +
+                                           std::to_string(fr >> 20) + " MiB of device memory are free: use MVBA_SCHUR=pairs");
         }
       }
       if (dev_build) {  // the step-major arrays are written where the kernel will read them
@@ -3673,16 +3609,14 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
       });
       }
       lap("slot merge (fill)");
-      std::vector<int> live((size_t)n_rounds * nR, 0);  // waves of a (round, range) that run at all: what a pacing counter has to reach
-      for (long long b = 0; b < n_waves; ++b) live[round_range(b)] += w_steps[b] > 0;
+      std::vector<int> live(nR, 0);  // waves of a range that run at all: what a pacing counter has to reach
+      for (long long b = 0; b < n_waves; ++b) live[b % nR] += w_steps[b] > 0;
       for (long long b = 0; b < n_waves; ++b) {
         const long long beg = w_beg[b];  // first step of the wave in the step-major index
-        // flags: bit 0 diagonal wave | bits 8..19 live waves of its (round, range) | bits 20..30 round
+        // flags: bit 0 diagonal wave | bits 8..19 live waves of its range
         wdesc[b] = make_int4((int)(beg & 0xffffffffLL), (int)(beg >> 32), (int)w_steps[b],
-                             (w_isdiag[b / nR] ? 1 : 0) | (live[round_range(b)] << 8) | (w_round[b / nR] << 20));
+                             (w_isdiag[b / nR] ? 1 : 0) | (live[b % nR] << 8));
       }
-      h->slot_rounds = n_rounds;
-      h->slot_groups = ng;
       h->n_waves = (int)n_waves;
       h->slot_nR = nR;
       h->n_slot_items = total_steps * PSTEP;
@@ -3794,10 +3728,10 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     const size_t P1 = (size_t)m * (m + 1) / 2 + 1;
     if (!h->index_on_device) { TRY(dmalloc(&h->d_it_k, it_k.size())); TRY(dmalloc(&h->d_it_l, it_l.size())); TRY(dmalloc(&h->d_it_a, it_a.size())); }
     TRY(dmalloc(&h->d_units, units.size())); TRY(dmalloc(&h->d_unit_ptr, P1));
-    TRY(dmalloc(&h->d_q_ptr, 9)); TRY(dmalloc(&h->d_q_units, q_units.size())); TRY(dmalloc(&h->d_q_head, 64));
+    TRY(dmalloc(&h->d_q_ptr, 9)); TRY(dmalloc(&h->d_q_units, q_units.size()));
     TRY(dmalloc(&h->d_wdesc, wdesc.size())); TRY(dmalloc(&h->d_wunits, wunits.size()));
     if (!h->index_on_device) TRY(dmalloc(&h->d_seg_end, seg_end.size()));
-    TRY(dmalloc(&h->d_prog, (size_t)h->slot_rounds * h->slot_nR * std::max(1, h->slot_nseg) * PACE_STRIDE));
+    TRY(dmalloc(&h->d_prog, (size_t)h->slot_nR * std::max(1, h->slot_nseg) * PACE_STRIDE));
     if (!seg_end.empty() && !h->index_on_device) TRYH(hipMemcpy(h->d_seg_end, seg_end.data(), sizeof(int) * seg_end.size(), hipMemcpyHostToDevice));
     if (!wdesc.empty()) {
       TRYH(hipMemcpy(h->d_wdesc, wdesc.data(), sizeof(int4) * wdesc.size(), hipMemcpyHostToDevice));
@@ -3832,7 +3766,6 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     }
     TRYH(hipMemcpy(h->d_unit_ptr, unit_ptr.data(), sizeof(int) * P1, hipMemcpyHostToDevice));
     TRYH(hipMemcpy(h->d_q_ptr, q_ptr.data(), sizeof(int) * 9, hipMemcpyHostToDevice));
-    TRYH(hipMemset(h->d_q_head, 0, sizeof(int) * 64));
     TRYH(hipMemset(h->d_partial, 0, sizeof(double) * UNIT_STRIDE * std::max<size_t>(units.size(), 1)));
   }
   lap("uploads");
@@ -3872,7 +3805,7 @@ void mvba_destroy(mvba_handle *h) {
   void *ptrs[] = {h->d_pt_ptr, h->d_cam, h->d_obs_pt, h->d_xy, h->d_tiles, h->d_tile_slot, h->d_splits, h->d_PLsplit, h->d_X[0], h->d_X[1],
                   h->d_cam15[0], h->d_cam15[1], h->d_rec, h->d_PL, h->d_PB, h->d_Ab, h->d_Ared, h->d_Ztiles, h->d_Lblk, h->d_lu,
                   h->d_dxi, h->d_dX, h->d_partials, h->d_cost, h->d_flag, h->d_allcost, h->d_it_k, h->d_it_l, h->d_it_a,
-                  h->d_units, h->d_unit_ptr, h->d_q_ptr, h->d_q_units, h->d_q_head, h->d_partial, h->d_dense_part, h->d_dense_obs, h->d_sim, h->d_bar, h->d_wdesc,
+                  h->d_units, h->d_unit_ptr, h->d_q_ptr, h->d_q_units, h->d_partial, h->d_dense_part, h->d_dense_obs, h->d_sim, h->d_bar, h->d_wdesc,
                   h->d_wunits, h->d_seg_end, h->d_prog, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10};
   for (void *q : ptrs) if (q) hipFree(q);
   for (double *q : h->snap_slabs) hipFree(q);
@@ -3986,7 +3919,7 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     const long long nAb = (long long)(nA + n9);
     const unsigned grid = (unsigned)std::max<long long>((h->N + 255) / 256, std::min<long long>((nAb + 1023) / 1024, 4096));
     hipLaunchKernelGGL(k_point_inv, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
-                       h->d_Ab, nAb, h->d_prog, (long long)h->slot_rounds * h->slot_nR * h->slot_nseg * PACE_STRIDE,
+                       h->d_Ab, nAb, h->d_prog, (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE,
                        h->schur_mode == SCHUR_DENSE ? 1 : 0);
   }
   if (h->use_pairs) {
@@ -3997,15 +3930,13 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
       if (h->n_waves)
         hipLaunchKernelGGL(k_schur_slots, dim3(h->n_waves), dim3(64), SLOT_LDS, h->stream, h->d_wdesc,
                            h->d_wunits, h->d_it_x, (const int *)nullptr, (const int *)nullptr, h->d_rec, h->d_PB, c, h->f0, h->d_partial,
-                           (int *)nullptr, h->slot_nR, h->n_waves / std::max(1, h->slot_nR), h->d_seg_end, h->d_prog, h->slot_nseg, SLOT_LAG,
-                           h->d_range_o0);
+                           h->slot_nR, h->d_seg_end, h->d_prog, h->slot_nseg, SLOT_LAG, h->d_range_o0);
     } else if (h->n_units) {
       hipLaunchKernelGGL(big ? k_schur_pairs_big : k_schur_pairs, dim3(8 * h->q_max), dim3(64),
-                         PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, (int *)nullptr, h->d_it_k,
-                         h->d_it_l, h->d_it_a, h->d_rec, h->d_PB, c, h->f0, h->d_partial);
+                         PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, h->d_it_k, h->d_it_l, h->d_it_a, h->d_rec, h->d_PB, c, h->f0, h->d_partial);
     }
     hipLaunchKernelGGL(k_schur_reduce, dim3((unsigned)((long long)m * (m + 1) / 2)), dim3(128), 0, h->stream, m, h->d_unit_ptr,
-                       h->d_partial, d_A, d_b, h->d_q_head);
+                       h->d_partial, d_A, d_b);
   } else if (h->schur_mode == SCHUR_DENSE) {
     Timed t(h, MVBA_K_SCHUR);
     const int T = (9 * m + 15) / 16;
@@ -4303,8 +4234,7 @@ int mvba_get_info(mvba_handle *h, int64_t *out8) {
   out8[0] = h->n_items;
   out8[1] = h->n_items_offdiag;
   out8[2] = h->n_units;
-  out8[3] = h->schur_mode | ((long long)(h->schur_mode == SCHUR_SLOTS ? h->slot_rounds : 0) << 8) |
-            ((long long)(h->schur_mode == SCHUR_SLOTS ? h->slot_groups : 0) << 32);
+  out8[3] = h->schur_mode;
   out8[4] = h->rccl_version;
   out8[5] = NCCL_VERSION_CODE;
   out8[6] = h->nranks;

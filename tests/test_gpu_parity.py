@@ -570,32 +570,13 @@ def test_barrier_timeout_of_the_persistent_back_substitution_is_redone_with_laun
     assert E2 == pytest.approx(ref.try_step(1e-2), rel=1e-12)
 
 
-@pytest.mark.parametrize("n,m,p,form", [(900, 300, 0.06, "pairs"), (3000, 14, 0.5, "pairs"),
-                                         (3000, 14, 0.5, "slots"), (20000, 60, 0.15, "slots"), (20000, 60, 0.15, "pairs"),
-                                         (3000, 14, 0.5, "slots:3"), (20000, 60, 0.15, "slots:4"), (2500, 300, 0.04, "slots"),
-                                         (2000, 500, 0.03, "slots"), (3001, 12, 1.0, "dense"), (1003, 21, 1.0, "dense"), (50, 2, 1.0, "dense"),
-                                         (3001, 12, 1.0, "pairs"), (999, 21, 1.0, "slots"), (3001, 14, 0.8, "dense"), (2003, 21, 0.65, "dense"),
-                                         (1000, 6, 0.5, "dense")])
-def test_every_schur_kernel_form_matches_the_oracle(n, m, p, form, monkeypatch):
-    """The forms of K3 -- the pair-major unit kernel (round 2) and the slot-resident kernel (round 3: one round of all camera pairs up to
-    ~100 cameras; round 4: beyond that, one round per pair of camera GROUPS inside one launch -- "slots:g" forces
-    g groups at a small camera count, m = 300 / 500 take 4 / 7 groups by themselves) -- each forced with
-    MVBA_SCHUR, the unit form in its 64-bit-offset build (MVBA_FORCE_BIG, also at 300 cameras; the slot form addresses its records
-    relative to the point range instead), and the dense-visibility form (round 5: every point seen by every camera, up to 21
-    cameras -- the rank-3N update of the whole reduced matrix on the matrix cores, no index; point counts that are not a multiple
-    of its chunk, the largest and the smallest camera count, the pair-major forms on the same full-visibility scenes, and scenes
-    with MISSING observations -- the records then come through a (point, camera) table and a missing one is a zero record),
-    against the oracle's reduced system."""
-    if ":" in form:
-        form, groups = form.split(":")
-        monkeypatch.setenv("MVBA_SLOT_GROUPS", groups)
-    if form not in ("slots", "dense"):
-        monkeypatch.setenv("MVBA_FORCE_BIG", "1")
-    monkeypatch.setenv("MVBA_SCHUR", form)
+def _reduced_system_matches_the_oracle(n, m, p, kernel):
+    """Build an engine on a random scene (with whatever MVBA_* knobs the caller set), check that it took Schur kernel form
+    `kernel`, and compare one trial step's reduced system and cost with the oracle's."""
     sc = make_scene(n, m, vis_p=p)
     ba = BundleAdjuster.from_observations(sc.n_points, m, sc.pt_ptr, sc.cam_idx, sc.xy, sc.init_X, sc.init_K,
                                           sc.init_R, sc.init_t, axis=sc.axis)
-    assert ba._engine.schur_info()["kernel"] == form
+    assert ba._engine.schur_info()["kernel"] == kernel
     g = O.OracleEngine(n, m, sc.pt_ptr, sc.cam_idx, sc.xy, 1.0, sc.axis)
     X, R, t = O.normalize_scene(sc.init_X, sc.init_R, sc.init_t, sc.axis)
     g.set_params(X, sc.init_K[:, 0, 0], sc.init_K[:, :2, 2], t, R)
@@ -609,6 +590,33 @@ def test_every_schur_kernel_form_matches_the_oracle(n, m, p, form, monkeypatch):
     np.testing.assert_allclose(eng.debug_read("A_full").reshape(m9, m9), A, rtol=0, atol=1e-11 * np.abs(A).max())
     np.testing.assert_allclose(eng.debug_read("b_full"), b, rtol=0, atol=1e-9 * np.abs(b).max())
     assert E1 == pytest.approx(E1o, rel=1e-7)
+
+
+@pytest.mark.parametrize("n,m,p,form", [(900, 300, 0.06, "pairs"), (3000, 14, 0.5, "pairs"),
+                                         (3000, 14, 0.5, "slots"), (20000, 60, 0.15, "slots"), (20000, 60, 0.15, "pairs"),
+                                         (3001, 12, 1.0, "dense"), (1003, 21, 1.0, "dense"), (50, 2, 1.0, "dense"),
+                                         (3001, 12, 1.0, "pairs"), (999, 21, 1.0, "slots"), (3001, 14, 0.8, "dense"),
+                                         (2003, 21, 0.65, "dense"), (1000, 6, 0.5, "dense")])
+def test_every_schur_kernel_form_matches_the_oracle(n, m, p, form, monkeypatch):
+    """The forms of K3 -- the pair-major unit kernel (round 2) and the slot-resident kernel (round 3: one round of all camera pairs up to
+    ~100 cameras) -- each forced with MVBA_SCHUR, the unit form in its 64-bit-offset build (MVBA_FORCE_BIG, also at 300 cameras;
+    the slot form addresses its records relative to the point range instead), and the dense-visibility form (round 5: every
+    point seen by every camera, up to 21 cameras -- the rank-3N update of the whole reduced matrix on the matrix cores, no index;
+    point counts that are not a multiple of its chunk, the largest and the smallest camera count, the pair-major forms on the same
+    full-visibility scenes, and scenes with MISSING observations -- the records then come through a (point, camera) table and a
+    missing one is a zero record), against the oracle's reduced system."""
+    if form not in ("slots", "dense"):
+        monkeypatch.setenv("MVBA_FORCE_BIG", "1")
+    monkeypatch.setenv("MVBA_SCHUR", form)
+    _reduced_system_matches_the_oracle(n, m, p, form)
+
+
+@pytest.mark.parametrize("n,m,p", [(2500, 300, 0.04), (2000, 500, 0.03)])
+def test_slots_request_beyond_one_round_takes_the_unit_form(n, m, p, monkeypatch):
+    """MVBA_SCHUR=slots where the camera pairs' lists do not fit one round of the slot form (m = 300 / 500): the engine falls
+    back to the unit form -- here in its 32-bit build -- and its reduced system matches the oracle's."""
+    monkeypatch.setenv("MVBA_SCHUR", "slots")
+    _reduced_system_matches_the_oracle(n, m, p, "pairs")
 
 
 def test_config3_full_size_properties():
@@ -814,7 +822,7 @@ def test_config4_in_full_on_one_gpu():
     full.close()
 
 
-@pytest.mark.parametrize("n,m,p", [(60_000, 24, 0.3), (4_000, 100, 0.1), (90, 70, 1.0), (3_000, 260, 0.05)])
+@pytest.mark.parametrize("n,m,p", [(60_000, 24, 0.3), (4_000, 100, 0.1), (90, 70, 1.0)])
 def test_schur_index_built_on_the_device_is_the_host_built_one(n, m, p, monkeypatch):
     """mvba_create builds the slot form's index with kernels (stable counting sort by pair, dealing into
     sub-lists, bounded-skew merge into step-major rows, pacing table); MVBA_INDEX=host keeps round 2's host
