@@ -2768,6 +2768,8 @@ __global__ void k_idx_interleave(long long n_steps, const int *__restrict__ st_k
   out[t] = which < 3 ? src[st * PSTEP + sl] : 0;
 }
 
+#include "mvba_cov.h"  // marginal covariances (mvba_covariance): S^-1 from the Cholesky factor and the point pass
+
 }  // namespace
 
 // ------------------------------------------------------------------ host side
@@ -2851,6 +2853,9 @@ struct mvba_handle {
   struct Ev { int kid; hipEvent_t a, b; };
   std::vector<Ev> pending;
   std::vector<hipEvent_t> pool;
+  // covariances (mvba_covariance), allocated on the first call: the camera-block table of S^-1, the two column panels of the
+  // triangular inverse, the point and camera blocks
+  double *d_cov_sig = nullptr, *d_cov_panel = nullptr, *d_cov_pts = nullptr, *d_cov_cam = nullptr;
 };
 
 namespace {
@@ -2866,7 +2871,7 @@ struct Timed {
   Timed(mvba_handle *h_, int kid_) : h(h_), kid(kid_) {
     // level 2: the two kernels a roofline is quoted for, nothing else (every timed phase is two marker packets on the
     // stream and ~10 us of a 2.5 ms step)
-    on = h->profiling == 1 || (h->profiling == 2 && (kid == MVBA_K_SCHUR || kid == MVBA_K_RESID_JAC));
+    on = kid >= 0 && (h->profiling == 1 || (h->profiling == 2 && (kid == MVBA_K_SCHUR || kid == MVBA_K_RESID_JAC)));  // (kid -1: never)
     if (!on) return;
     auto get = [&]() {
       hipEvent_t e;
@@ -3806,7 +3811,8 @@ void mvba_destroy(mvba_handle *h) {
                   h->d_cam15[0], h->d_cam15[1], h->d_rec, h->d_PL, h->d_PB, h->d_Ab, h->d_Ared, h->d_Ztiles, h->d_Lblk, h->d_lu,
                   h->d_dxi, h->d_dX, h->d_partials, h->d_cost, h->d_flag, h->d_allcost, h->d_it_k, h->d_it_l, h->d_it_a,
                   h->d_units, h->d_unit_ptr, h->d_q_ptr, h->d_q_units, h->d_partial, h->d_dense_part, h->d_dense_obs, h->d_sim, h->d_bar, h->d_wdesc,
-                  h->d_wunits, h->d_seg_end, h->d_prog, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10};
+                  h->d_wunits, h->d_seg_end, h->d_prog, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10,
+                  h->d_cov_sig, h->d_cov_panel, h->d_cov_pts, h->d_cov_cam};
   for (void *q : ptrs) if (q) hipFree(q);
   for (double *q : h->snap_slabs) hipFree(q);
   if (h->h_cost) hipHostFree(h->h_cost);
@@ -3882,48 +3888,38 @@ int mvba_cost(mvba_handle *h, double *E) {
   return global_cost(h, E);
 }
 
-int mvba_linearize(mvba_handle *h) {
-  if (!h) return fail(MVBA_ERR_BADARG, "null handle");
-  if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
-  MVBA_HIP(hipSetDevice(h->device));
-  if (h->nobs) {
-    Timed t(h, MVBA_K_RESID_JAC);  // K1 with K2 (per-point blocks) fused in
-    const int kt = h->k1_threads;  // 8 waves share one camera table: 2 blocks = 16 waves per CU
-    const size_t lds = (size_t)((h->gcam ? 0 : ((h->m * CAM_LDS + 1) & ~1)) + (kt / 64) * 64 * 2 * REC) * sizeof(double);
-    cam_tables(h, h->d_cam15[h->cur], nullptr);
-    const int wpb = kt / 64;
-    const int grid = std::max(1, std::min(2048 * 256 / kt, (h->n_tiles + wpb - 1) / wpb));
-    hipLaunchKernelGGL(h->gcam ? k_resid_jac<true> : k_resid_jac<false>, dim3(grid), dim3(kt), lds, h->stream, h->nobs, h->m, h->d_cam15[h->cur],
-                       h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
-                       h->d_tile_slot, h->d_PLsplit, h->d_cam18);
-    if (h->n_splits)
-      hipLaunchKernelGGL(k_sum_split, dim3((9 * h->n_splits + 255) / 256), dim3(256), 0, h->stream, h->n_splits, h->d_splits,
-                         h->d_PLsplit, h->d_PL);
-  }
-  MVBA_HIP(hipGetLastError());
-  h->linearized = true; h->have_trial = false;
-  h->stats.n_linearize++;
-  return MVBA_OK;
+namespace {
+// The launches the LM step shares with mvba_covariance.  The callers put their own Timed scopes around them, so that the
+// covariance does not add to the per-kernel statistics.
+void launch_resid_jac(mvba_handle *h) {  // K1 with K2 fused in, at the committed state
+  const int kt = h->k1_threads;  // 8 waves share one camera table: 2 blocks = 16 waves per CU
+  const size_t lds = (size_t)((h->gcam ? 0 : ((h->m * CAM_LDS + 1) & ~1)) + (kt / 64) * 64 * 2 * REC) * sizeof(double);
+  cam_tables(h, h->d_cam15[h->cur], nullptr);
+  const int wpb = kt / 64;
+  const int grid = std::max(1, std::min(2048 * 256 / kt, (h->n_tiles + wpb - 1) / wpb));
+  hipLaunchKernelGGL(h->gcam ? k_resid_jac<true> : k_resid_jac<false>, dim3(grid), dim3(kt), lds, h->stream, h->nobs, h->m, h->d_cam15[h->cur],
+                     h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
+                     h->d_tile_slot, h->d_PLsplit, h->d_cam18);
+  if (h->n_splits)
+    hipLaunchKernelGGL(k_sum_split, dim3((9 * h->n_splits + 255) / 256), dim3(256), 0, h->stream, h->n_splits, h->d_splits,
+                       h->d_PLsplit, h->d_PL);
 }
 
-int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
-  if (!h || !E_trial) return fail(MVBA_ERR_BADARG, "null argument");
-  if (!h->linearized) return fail(MVBA_ERR_STATE, "try_step before linearize");
-  MVBA_HIP(hipSetDevice(h->device));
-  const int m = h->m, D = h->D;
-  const size_t n9 = 9 * (size_t)m;
-  const size_t nA = strip_offset(m, m);  // packed upper block triangle
+void launch_point_inv(mvba_handle *h, double c) {  // K3a (also clears the packed [A|b] and the slot form's pacing counters)
+  const int m = h->m;
+  const size_t n9 = 9 * (size_t)m, nA = strip_offset(m, m);
+  const long long nAb = (long long)(nA + n9);
+  const unsigned grid = (unsigned)std::max<long long>((h->N + 255) / 256, std::min<long long>((nAb + 1023) / 1024, 4096));
+  hipLaunchKernelGGL(k_point_inv, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
+                     h->d_Ab, nAb, h->d_prog, (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE,
+                     h->schur_mode == SCHUR_DENSE ? 1 : 0);
+}
+
+void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b] of this rank's points
+  const int m = h->m;
+  const size_t nA = strip_offset(m, m);
   double *d_A = h->d_Ab, *d_b = h->d_Ab + nA;
-  {
-    Timed t(h, MVBA_K_POINT_INV);
-    const long long nAb = (long long)(nA + n9);
-    const unsigned grid = (unsigned)std::max<long long>((h->N + 255) / 256, std::min<long long>((nAb + 1023) / 1024, 4096));
-    hipLaunchKernelGGL(k_point_inv, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
-                       h->d_Ab, nAb, h->d_prog, (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE,
-                       h->schur_mode == SCHUR_DENSE ? 1 : 0);
-  }
   if (h->use_pairs) {
-    Timed t(h, MVBA_K_SCHUR);
     // 64-bit offsets only when the records or the point blocks (+ the padding row) span 4 GiB (MVBA_FORCE_BIG: at test sizes too)
     const bool big = (std::max<long long>(h->nobs, h->N) + 1) * 128LL >= (1LL << 32) || h->force_big;
     if (h->schur_mode == SCHUR_SLOTS) {
@@ -3938,7 +3934,6 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     hipLaunchKernelGGL(k_schur_reduce, dim3((unsigned)((long long)m * (m + 1) / 2)), dim3(128), 0, h->stream, m, h->d_unit_ptr,
                        h->d_partial, d_A, d_b);
   } else if (h->schur_mode == SCHUR_DENSE) {
-    Timed t(h, MVBA_K_SCHUR);
     const int T = (9 * m + 15) / 16;
     const int CH = dense_ch(T);
     const size_t lds = sizeof(double) * ((size_t)2 * 3 * CH * 16 * T + (size_t)2 * CH * m * 32) + sizeof(double2) * CH * ((size_t)m * REC + 8) + sizeof(double) * (CH * (size_t)m + 2 * 3 * CH);
@@ -3964,9 +3959,13 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     hipLaunchKernelGGL(k_schur_dense_finish, dim3((unsigned)((n_el + 3) / 4)), dim3(256), 0, h->stream, m, T, h->dense_blocks,
                        (const double *)h->d_dense_part, c, d_A, d_b);
   }
-  MVBA_HIP(hipGetLastError());
+}
+
+int allreduce_Ab(mvba_handle *h, bool timed) {  // C1: [A|b] summed over the ranks (RCCL or the host transport)
+  const int m = h->m;
+  const size_t n9 = 9 * (size_t)m, nA = strip_offset(m, m);
   if (h->comm) {
-    Timed t(h, MVBA_K_ALLREDUCE);
+    Timed t(h, timed ? MVBA_K_ALLREDUCE : -1);
     ncclResult_t r = g_rccl.AllReduce(h->d_Ab, h->d_Ab, nA + n9, ncclDouble, ncclSum, h->comm, h->stream);
     if (r != ncclSuccess) return fail(MVBA_ERR_RCCL, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
   } else if (h->host_ar) {  // host-staged transport: D2H, caller's sum, H2D (no RCCL; see mvba_comm_init_host)
@@ -3976,29 +3975,75 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     const auto t0 = std::chrono::steady_clock::now();  // the wait above belongs to the Schur kernel, not to the exchange
     if (h->host_ar(h->host_ar_user, h->host_buf.data(), (int64_t)(nA + n9))) return fail(MVBA_ERR_RCCL, "host all-reduce callback failed");
     MVBA_HIP(hipMemcpyAsync(h->d_Ab, h->host_buf.data(), sizeof(double) * (nA + n9), hipMemcpyHostToDevice, h->stream));
-    if (h->profiling) {  // host wall time of the exchange (callback + staging copy issue); the device path uses events
+    if (timed && h->profiling) {  // host wall time of the exchange (callback + staging copy issue); the device path uses events
       h->stats.ms[MVBA_K_ALLREDUCE] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       h->stats.launches[MVBA_K_ALLREDUCE] += 1;
     }
   }
+  return MVBA_OK;
+}
+
+void launch_factor(mvba_handle *h) {  // K4 without the back-substitution: gauge strip into d_Ared, blocked Cholesky of [A|b]
+  const int m = h->m, D = h->D;
+  double *d_A = h->d_Ab, *d_b = h->d_Ab + strip_offset(m, m);
+  const int ld = h->ld;
+  const int ntc = (D + NB - 1) / NB;
+  hipLaunchKernelGGL(k_compact, dim3(ntc * (ntc + 1) / 2 + (D + 255) / 256), dim3(256), 0, h->stream, D, ld, m, h->gauge_axis, ntc, d_A, d_b,
+                     h->d_Ared, h->d_bar, 1 + 4 * ((D + SBW - 1) / SBW));
+  for (int jS = 0; jS < D; jS += SBW) {
+    const int jE = std::min(jS + SBW, D);
+    hipLaunchKernelGGL(k_chol_super, dim3((D + 1 - jE + 63) / 64), dim3(SUPER_THREADS), SUPER_LDS, h->stream, h->d_Ared, ld, D, jS,
+                       h->d_Ztiles + (size_t)(jS / NB) * NB * NB, h->d_Lblk + (size_t)(jS / SBW) * SBW * SBW, h->d_flag);
+    if (jE < D) {
+      const int nt32 = (D + 1 - jE + NB - 1) / NB, nt64 = (D + 1 - jE + TB - 1) / TB;
+      if (jE - jS == SBW && nt64 * (nt64 + 1) / 2 >= h->trail64_min)
+        hipLaunchKernelGGL(k_chol_trail64, dim3(nt64 * (nt64 + 1) / 2), dim3(256), TRAIL64_LDS, h->stream, h->d_Ared, ld, D, jS, jE);
+      else
+        hipLaunchKernelGGL(k_chol_trail32, dim3(nt32 * (nt32 + 1) / 2), dim3(256), 0, h->stream, h->d_Ared, ld, D, jS, jE);
+    }
+  }
+}
+}  // namespace
+
+int mvba_linearize(mvba_handle *h) {
+  if (!h) return fail(MVBA_ERR_BADARG, "null handle");
+  if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
+  MVBA_HIP(hipSetDevice(h->device));
+  if (h->nobs) {
+    Timed t(h, MVBA_K_RESID_JAC);  // K1 with K2 (per-point blocks) fused in
+    launch_resid_jac(h);
+  }
+  MVBA_HIP(hipGetLastError());
+  h->linearized = true; h->have_trial = false;
+  h->stats.n_linearize++;
+  return MVBA_OK;
+}
+
+int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
+  if (!h || !E_trial) return fail(MVBA_ERR_BADARG, "null argument");
+  if (!h->linearized) return fail(MVBA_ERR_STATE, "try_step before linearize");
+  MVBA_HIP(hipSetDevice(h->device));
+  const int m = h->m, D = h->D;
+  const size_t n9 = 9 * (size_t)m;
+  const size_t nA = strip_offset(m, m);  // packed upper block triangle
+  double *d_A = h->d_Ab, *d_b = h->d_Ab + nA;
+  {
+    Timed t(h, MVBA_K_POINT_INV);
+    launch_point_inv(h, c);
+  }
+  if (h->use_pairs || h->schur_mode == SCHUR_DENSE) {
+    Timed t(h, MVBA_K_SCHUR);
+    launch_schur(h, c);
+  }
+  MVBA_HIP(hipGetLastError());
+  {
+    int rc_ = allreduce_Ab(h, true);
+    if (rc_) return rc_;
+  }
   auto launch_solve = [&](bool onepass) {  // K4: gauge strip, blocked Cholesky, back-substitution
     Timed t(h, MVBA_K_SOLVE);
+    launch_factor(h);
     const int ld = h->ld;
-    const int ntc = (D + NB - 1) / NB;
-    hipLaunchKernelGGL(k_compact, dim3(ntc * (ntc + 1) / 2 + (D + 255) / 256), dim3(256), 0, h->stream, D, ld, m, h->gauge_axis, ntc, d_A, d_b,
-                       h->d_Ared, h->d_bar, 1 + 4 * ((D + SBW - 1) / SBW));
-    for (int jS = 0; jS < D; jS += SBW) {
-      const int jE = std::min(jS + SBW, D);
-      hipLaunchKernelGGL(k_chol_super, dim3((D + 1 - jE + 63) / 64), dim3(SUPER_THREADS), SUPER_LDS, h->stream, h->d_Ared, ld, D, jS,
-                         h->d_Ztiles + (size_t)(jS / NB) * NB * NB, h->d_Lblk + (size_t)(jS / SBW) * SBW * SBW, h->d_flag);
-      if (jE < D) {
-        const int nt32 = (D + 1 - jE + NB - 1) / NB, nt64 = (D + 1 - jE + TB - 1) / TB;
-        if (jE - jS == SBW && nt64 * (nt64 + 1) / 2 >= h->trail64_min)
-          hipLaunchKernelGGL(k_chol_trail64, dim3(nt64 * (nt64 + 1) / 2), dim3(256), TRAIL64_LDS, h->stream, h->d_Ared, ld, D, jS, jE);
-        else
-          hipLaunchKernelGGL(k_chol_trail32, dim3(nt32 * (nt32 + 1) / 2), dim3(256), 0, h->stream, h->d_Ared, ld, D, jS, jE);
-      }
-    }
     const int S = (D + SBW - 1) / SBW;
     if (onepass && (S == 1 || S < h->n_cu)) {  // one persistent pass for L^T x = y (see k_chol_backsolve_all)
       // (point to point, nobody pays for anybody else: one bulk workgroup per column group)
@@ -4142,6 +4187,132 @@ int mvba_commit(mvba_handle *h) {
   h->cur = 1 - h->cur;
   h->have_trial = false; h->linearized = false;
   h->stats.n_commit++;
+  return MVBA_OK;
+}
+
+int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *cam_cov_full, double *timings_ms) {
+  if (!h) return fail(MVBA_ERR_BADARG, "null handle");
+  if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
+  MVBA_HIP(hipSetDevice(h->device));
+  const int m = h->m, D = h->D, ld = h->ld, nt = (D + NB - 1) / NB;
+  const size_t n_sig = sig_block(m, m, m);  // (the block index of (m, m) is the block count)
+  // First call: the camera-block table, the trtri panels, the point and camera blocks -- all four or none (a failed
+  // allocation frees what it got, so that a later call never runs with some of them missing)
+  auto free_cov = [&]() {
+    for (double **q : {&h->d_cov_sig, &h->d_cov_panel, &h->d_cov_pts, &h->d_cov_cam}) {
+      if (*q) hipFree(*q);
+      *q = nullptr;
+    }
+  };
+  int local_rc = MVBA_OK;
+  if (!h->d_cov_sig || !h->d_cov_panel || !h->d_cov_pts || !h->d_cov_cam) {
+    free_cov();
+    local_rc = dmalloc(&h->d_cov_sig, n_sig);
+    if (!local_rc) local_rc = dmalloc(&h->d_cov_panel, 2 * (size_t)D * NB);
+    if (!local_rc) local_rc = dmalloc(&h->d_cov_pts, 6 * (size_t)h->N);
+    if (!local_rc) local_rc = dmalloc(&h->d_cov_cam, 81 * (size_t)m);
+    if (local_rc) free_cov();
+  }
+  hipEvent_t ev[5] = {};
+  struct EvFree { hipEvent_t *e; ~EvFree() { for (int i = 0; i < 5; ++i) if (e[i]) hipEventDestroy(e[i]); } } ev_free{ev};
+  for (auto &e : ev)
+    if (!local_rc && hipEventCreate(&e) != hipSuccess) local_rc = fail(MVBA_ERR_HIP, "hipEventCreate failed");
+  const bool sharded = h->comm || h->host_ar;
+  if (local_rc && !sharded) return local_rc;
+  const std::string local_err = local_rc ? g_err : std::string();
+  double *d_b = h->d_Ab + strip_offset(m, m);
+  if (!local_rc) {
+    MVBA_HIP(hipEventRecord(ev[0], h->stream));
+    // 1-4: the LM step's launches at c = 0 (K1, K3a, K3 in the engine's form, the all-reduce of [A|b])
+    if (h->nobs) launch_resid_jac(h);
+    h->linearized = true; h->have_trial = false;
+    launch_point_inv(h, 0.0);
+    launch_schur(h, 0.0);
+    MVBA_HIP(hipGetLastError());
+  } else {
+    // A rank that could not set up still takes part in the collective (the others would wait in it for ever): it marks
+    // b[3] -- camera 0's t_x, a gauge slot the solve never reads -- with a NaN (all-ones bytes), so that every rank sees
+    // it in the sum and fails the call with it.
+    MVBA_HIP(hipMemsetAsync(d_b + 3, 0xFF, sizeof(double), h->stream));
+  }
+  {
+    int rc = allreduce_Ab(h, false);
+    if (rc) return rc;
+  }
+  if (sharded) {
+    double mark = 0.0;
+    MVBA_HIP(hipMemcpyAsync(&mark, d_b + 3, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MVBA_HIP(hipStreamSynchronize(h->stream));
+    if (local_rc) return fail(local_rc, local_err);
+    if (std::isnan(mark))
+      return fail(MVBA_ERR_HIP, "mvba_covariance: another rank could not allocate its covariance buffers (or the reduced system is not finite)");
+  }
+  MVBA_HIP(hipEventRecord(ev[1], h->stream));
+  // 5: gauge strip + blocked Cholesky of the undamped S
+  launch_factor(h);
+  MVBA_HIP(hipEventRecord(ev[2], h->stream));
+  // 6a: W = L^-1 in place in d_Ared, then Sigma = W^T W into the camera-block table (zeros at the gauge slots)
+  hipLaunchKernelGGL(k_cov_assemble, dim3(nt), dim3(256), 0, h->stream, h->d_Ared, ld, D, (const double *)h->d_Ztiles,
+                     (const double *)h->d_Lblk);
+  double *panel[2] = {h->d_cov_panel, h->d_cov_panel + (size_t)D * NB};
+  for (int J = nt - 1; J >= 0; --J) {
+    const int grid = (nt - 1 - J) + (J >= 1 ? nt - J : 0);
+    if (grid)
+      hipLaunchKernelGGL(k_cov_trtri, dim3(grid), dim3(256), 0, h->stream, h->d_Ared, ld, D, nt, J, (const double *)panel[J & 1],
+                         panel[(J + 1) & 1]);
+  }
+  MVBA_HIP(hipMemsetAsync(h->d_cov_sig, 0, sizeof(double) * n_sig, h->stream));
+  hipLaunchKernelGGL(k_cov_lauum, dim3(nt * (nt + 1) / 2), dim3(256), 0, h->stream, (const double *)h->d_Ared, ld, D, nt, m,
+                     h->gauge_axis, h->d_cov_sig);
+  MVBA_HIP(hipEventRecord(ev[3], h->stream));
+  // 6b: the point pass and the camera blocks
+  if (h->N && point_cov) {
+    const double pairs = h->N ? 0.5 * ((double)h->nobs / (double)h->N) * ((double)h->nobs / (double)h->N + 1.0) : 0.0;
+    const int G = pairs > 48.0 ? 64 : (pairs > 24.0 ? 32 : (pairs > 12.0 ? 16 : 8));  // lanes per point by mean pair count
+    const unsigned grid = (unsigned)std::min<long long>(8192, (h->N * G + 255) / 256);
+    auto kern = G == 64 ? k_point_cov<64> : (G == 32 ? k_point_cov<32> : (G == 16 ? k_point_cov<16> : k_point_cov<8>));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->stream, h->N, m, (const long long *)h->d_pt_ptr, (const int *)h->d_cam,
+                       (const double2 *)h->d_rec, (const double *)h->d_PL, (const double *)h->d_cov_sig, 1.0 / h->f0, h->d_cov_pts,
+                       h->d_flag);
+  }
+  if (cam_cov)
+    hipLaunchKernelGGL(k_cov_cam_diag, dim3((unsigned)((81LL * m + 255) / 256)), dim3(256), 0, h->stream, m,
+                       (const double *)h->d_cov_sig, h->d_cov_cam);
+  MVBA_HIP(hipGetLastError());
+  MVBA_HIP(hipEventRecord(ev[4], h->stream));
+  int fl = 0;
+  MVBA_HIP(hipMemcpyAsync(&fl, h->d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  MVBA_HIP(hipStreamSynchronize(h->stream));
+  if (fl) {
+    MVBA_HIP(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
+    MVBA_HIP(hipStreamSynchronize(h->stream));
+    if (fl & (1 | COV_FLAG_POINT)) return fail(MVBA_ERR_SINGULAR, "Singular matrix (a point block E_a is singular: a point seen once, or without parallax)");
+    return fail(MVBA_ERR_SINGULAR, "Singular matrix (the undamped reduced camera system is not positive definite)");
+  }
+  if (timings_ms)
+    for (int i = 0; i < 4; ++i) {
+      float ms = 0.f;
+      MVBA_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      timings_ms[i] = ms;
+    }
+  if (point_cov && h->N) MVBA_HIP(hipMemcpy(point_cov, h->d_cov_pts, sizeof(double) * 6 * h->N, hipMemcpyDeviceToHost));
+  if (cam_cov) MVBA_HIP(hipMemcpy(cam_cov, h->d_cov_cam, sizeof(double) * 81 * m, hipMemcpyDeviceToHost));
+  if (cam_cov_full) {  // the table, expanded on the host strip by strip (blocks (k, k..m-1) are contiguous): C = 2 S^-1, both triangles
+    std::vector<double> strip((size_t)SIG_BS * m);
+    const size_t n9 = 9 * (size_t)m;
+    for (int k = 0; k < m; ++k) {
+      MVBA_HIP(hipMemcpy(strip.data(), h->d_cov_sig + sig_block(k, k, m), sizeof(double) * SIG_BS * (m - k), hipMemcpyDeviceToHost));
+      for (int l = k; l < m; ++l) {
+        const double *b = strip.data() + (size_t)SIG_BS * (l - k);
+        for (int i = 0; i < 9; ++i)
+          for (int j = 0; j < 9; ++j) {
+            const double v = 2.0 * b[9 * i + j];
+            cam_cov_full[(9 * (size_t)k + i) * n9 + 9 * (size_t)l + j] = v;
+            cam_cov_full[(9 * (size_t)l + j) * n9 + 9 * (size_t)k + i] = v;
+          }
+      }
+    }
+  }
   return MVBA_OK;
 }
 

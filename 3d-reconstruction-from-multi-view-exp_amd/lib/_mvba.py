@@ -57,6 +57,7 @@ SIGNATURES = {
     "mvba_linearize": (C.c_int, [C.c_void_p]),
     "mvba_try_step": (C.c_int, [C.c_void_p, C.c_double, _dp]),
     "mvba_commit": (C.c_int, [C.c_void_p]),
+    "mvba_covariance": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "mvba_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
     "mvba_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "mvba_reset_stats": (C.c_int, [C.c_void_p]),
@@ -221,6 +222,28 @@ class HipEngine:
 
     def commit(self):
         raise_for(self.lib.mvba_commit(self._h), self.lib)
+
+    def covariance(self, points=True, cameras=True, full=False):
+        """Unit marginal covariances (J^T J)^-1 at the committed state, in the engine's frame, gauge parameters fixed
+        (zero rows / columns): ``points`` (N, 3, 3), ``cameras`` (m, 9, 9) (f, u, v, t, omega), ``cameras_full``
+        (9m, 9m) when ``full``, and ``timings_ms`` (linearise+Schur, factor, inverse, point pass).  Leaves the engine
+        linearised at the committed state.  Raises LinAlgError when J^T J is singular (a point seen once, a camera with
+        too few points)."""
+        P = np.empty((self.n, 6)) if points else None
+        Cc = np.empty((self.m, 9, 9)) if cameras else None
+        Cf = np.empty((9 * self.m, 9 * self.m)) if full else None
+        tm = np.zeros(4)
+        raise_for(self.lib.mvba_covariance(self._h, _ptr(P) if P is not None else None, _ptr(Cc) if Cc is not None else None,
+                                           _ptr(Cf) if Cf is not None else None, _ptr(tm)), self.lib)
+        out = {"timings_ms": dict(zip(("schur", "factor", "inverse", "points"), tm.tolist()))}
+        if P is not None:
+            i = np.array([[0, 1, 2], [1, 3, 4], [2, 4, 5]])
+            out["points"] = P[:, i]
+        if Cc is not None:
+            out["cameras"] = Cc
+        if Cf is not None:
+            out["cameras_full"] = Cf
+        return out
 
     # -- measurement / multi-GPU / test hooks
     def set_profiling(self, on):

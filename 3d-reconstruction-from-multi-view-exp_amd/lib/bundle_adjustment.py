@@ -71,6 +71,46 @@ def from_gauge_frame(camera0: dict[str, Any], X, R, t):
     return t0 + (length * X) @ R0.T, R0 @ R, t0 + (length * t) @ R0.T
 
 
+def from_gauge_frame_inverse(camera0: dict[str, Any], X, R, t):
+    """The exact inverse of ``from_gauge_frame``: the input frame back into the gauge frame BA works in."""
+    R0, t0, length = camera0["R"], camera0["t"], camera0["c0c1_len"]
+    return ((X - t0) @ R0) / length, R0.T @ R, ((t - t0) @ R0) / length
+
+
+def camera_frame_map(camera0: dict[str, Any]):
+    """T (9, 9): how one camera's parameter increments (f, u, v, t, omega) map from the gauge frame to the input frame.
+    f, u, v stay; t_in = t0 + L R0 t gives L R0; R_in = R0 R and R <- Rod(omega) R give omega_in = R0 omega."""
+    R0, length = np.asarray(camera0["R"], dtype=np.float64), float(camera0["c0c1_len"])
+    T = np.zeros((9, 9))
+    T[:3, :3] = np.eye(3)
+    T[3:6, 3:6] = length * R0
+    T[6:9, 6:9] = R0
+    return T
+
+
+def covariance_to_input_frame(camera0: dict[str, Any], points=None, cameras=None, cameras_full=None):
+    """Gauge-frame covariances -> the input frame: L^2 R0 C_a R0^T per point (N, 3, 3), T C_k T^T per camera (m, 9, 9),
+    and blockdiag(T) C blockdiag(T)^T for the joint (9m, 9m) camera covariance.  Returns the three (None stays None)."""
+    R0, length = np.asarray(camera0["R"], dtype=np.float64), float(camera0["c0c1_len"])
+    T = camera_frame_map(camera0)
+    P = None if points is None else length ** 2 * np.einsum("ij,ajk,lk->ail", R0, points, R0)
+    Cc = None if cameras is None else np.einsum("ij,kjl,ml->kim", T, cameras, T)
+    Cf = None
+    if cameras_full is not None:
+        m = cameras_full.shape[0] // 9
+        Cf = np.einsum("ij,kjlm,nm->kiln", T, cameras_full.reshape(m, 9, m, 9), T).reshape(9 * m, 9 * m)
+    return P, Cc, Cf
+
+
+def residual_variance(E: float, n_obs: int, n_points: int, n_images: int) -> float:
+    """sigma^2 = E / (2 n_obs - (3 N + 9 m - 7)): the residual variance per image coordinate (units x / f0) at the
+    solution; ValueError when the problem has no redundancy."""
+    dof = 2 * int(n_obs) - (3 * int(n_points) + 9 * int(n_images) - 7)
+    if dof <= 0:
+        raise ValueError(f"no redundancy: 2 n_obs - (3 N + 9 m - 7) = {dof}")
+    return float(E) / dof
+
+
 def intrinsics_from(f, u, f0: float):
     """K_k = [[f,0,u0],[0,f,v0],[0,0,f0]] (ref :283-289): K[2,2] is forced to f0."""
     m = len(f)
@@ -178,6 +218,7 @@ class BundleAdjuster:
         self._n_points, self._n_images = int(n_points), int(n_images)
         self._engine = self._make_engine(self._n_points, self._n_images, pt_ptr, cam_idx, xy, f0, axis, **engine_kw)
         self._engine.set_params(X, init_K[:, 0, 0], init_K[:, :2, 2], t, R)  # ref :45-48
+        self._engine_frame = "gauge"  # the frame of the engine's state: "input" once optimize() has applied the way back
         self._log: list[dict[str, npt.NDArray | float]] = []
 
     # -- the reference's public methods --------------------------------------
@@ -217,8 +258,50 @@ class BundleAdjuster:
         # the way back (:242-258) to its committed state on the device, then hands it over
         cam0 = self._init_camera0_params
         self._engine.apply_similarity(cam0["R"], cam0["t"], cam0["c0c1_len"])
+        self._engine_frame = "input"
         X, f, u, t, R = self._engine.get_params()
         return X, intrinsics_from(f, u, self._f0), R, t
+
+    def covariance(self, scale: str = "unit", frame: str = "input", full_cameras: bool = False) -> dict[str, Any]:
+        """Marginal covariances of the current estimate (after optimize(): the solution): ``points`` (N, 3, 3),
+        ``cameras`` (m, 9, 9) in the order f, u, v, t, omega, and ``cameras_full`` (9m, 9m) when ``full_cameras``.
+        Undamped, with the seven gauge parameters fixed (camera 0's t and omega, one component of camera 1's t: zero rows
+        and columns).  ``scale="unit"``: (J^T J)^-1 with J in units x / f0; ``"residual"``: times sigma^2 =
+        E / (2 n_obs - (3N + 9m - 7)) (also returned as ``sigma2``).  ``frame="gauge"``: the normalised frame BA works in;
+        ``"input"``: the caller's frame (omega as a rotation increment R <- Rod(omega) R in that frame).  The engine's
+        state is left bitwise as it was.  Raises LinAlgError for a degenerate problem (a point seen once, a camera with
+        too few points)."""
+        if scale not in ("unit", "residual") or frame not in ("input", "gauge"):
+            raise ValueError("scale must be 'unit' or 'residual', frame 'input' or 'gauge'")
+        eng, cam0 = self._engine, self._init_camera0_params
+        if scale == "residual":
+            residual_variance(0.0, eng.n_obs, self._n_points, self._n_images)  # (no redundancy: ValueError before any work)
+        saved = None
+        if self._engine_frame == "input":  # the covariance is taken in the gauge frame the parameterisation fixes
+            saved = eng.get_params()
+            X, f, u, t, R = saved
+            Xg, Rg, tg = from_gauge_frame_inverse(cam0, X, R, t)
+            eng.set_params(Xg, f, u, tg, Rg)
+        try:
+            E = eng.cost() if scale == "residual" else None
+            cov = eng.covariance(points=True, cameras=True, full=full_cameras)
+        finally:
+            if saved is not None:
+                eng.set_params(*saved)
+        out: dict[str, Any] = {"points": cov["points"], "cameras": cov["cameras"], "timings_ms": cov["timings_ms"]}
+        if full_cameras:
+            out["cameras_full"] = cov["cameras_full"]
+        if frame == "input":
+            out["points"], out["cameras"], Cf = covariance_to_input_frame(cam0, out["points"], out["cameras"], out.get("cameras_full"))
+            if full_cameras:
+                out["cameras_full"] = Cf
+        if scale == "residual":
+            s2 = residual_variance(E, eng.n_obs, self._n_points, self._n_images)
+            out["sigma2"] = s2
+            for k in ("points", "cameras", "cameras_full"):
+                if k in out:
+                    out[k] = out[k] * s2
+        return out
 
     def _fetch_log(self):
         """Device-resident log entries -> host dicts (in order), device log emptied."""

@@ -106,6 +106,17 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial);
 /* trial -> committed (ref :169-173). */
 int mvba_commit(mvba_handle *h);
 
+/* Marginal covariances at the COMMITTED state, undamped, gauge parameters fixed (zero rows/columns): the unit covariance
+ * C = (J^T J)^-1 = 2 H^-1 over the free parameters (J: the residual Jacobian, units x / f0), camera parameters in the order
+ * f, u, v, t[3], omega[3].  Runs K1, K3a at c = 0, the engine's K3 form, the all-reduce of [A|b] and K4's Cholesky, then
+ * S^-1 from the factor and one point-major pass.
+ * point_cov [n_points][6] (xx,xy,xz,yy,yz,zz), cam_cov [m][9][9], cam_cov_full [9m][9m]: each may be NULL.
+ * timings_ms [4] (may be NULL): linearise+Schur, factor, inverse, point pass.  Afterwards the handle is as
+ * mvba_linearize leaves it (no trial); the committed parameters are untouched.  MVBA_ERR_SINGULAR: a non-positive pivot of
+ * the undamped reduced camera system, or a numerically singular point block E_a (a Cholesky pivot below 1e-12 of its largest
+ * diagonal entry: a point seen once).  Sharded: every rank gets its own points' blocks and the same camera blocks.        */
+int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *cam_cov_full, double *timings_ms);
+
 /* The debug log of the reference's optimize(is_debug=True) (ref :89-98, :175-183: a copy of X, R, t per outer
  * iteration, normalised frame; read back by get_log(), :204-206).  mvba_snapshot appends the COMMITTED state to
  * a log kept in device memory -- one device-to-device copy on the engine's stream, nothing crosses PCIe and the
