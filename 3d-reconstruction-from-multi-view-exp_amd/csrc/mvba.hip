@@ -168,16 +168,21 @@ constexpr int LDS_CAMERAS = 646;  // cameras whose tables (K1: 18 doubles + the 
 // GCAM: beyond LDS_CAMERAS cameras the expanded camera table does not fit a workgroup's LDS next to its staging tiles; the
 // kernels then read the rows of a table in device memory (k_cam_tables; 144 bytes per camera, L2-resident) through the same
 // 16-byte loads.  One template parameter per kernel: the LDS form keeps its ds_read_b128, nothing is decided per access.
-template <bool GCAM>
-__global__ __launch_bounds__(1024, 4) void k_resid_jac(long long nobs, int m, const double *__restrict__ cam15,
-                                                   const double *__restrict__ X,
-                                                   const int *__restrict__ obs_pt,
-                                                   const int *__restrict__ cam_idx,
-                                                   const double2 *__restrict__ xy, double f0,
-                                                   const int *__restrict__ tile_start, int n_tiles,
-                                                   double2 *__restrict__ rec, double *__restrict__ PL,
-                                                   const int *__restrict__ tile_slot, double *__restrict__ PLsplit,
-                                                   const double *__restrict__ gcam) {
+// LOSS: a robust loss scales the observation's Jacobian rows and residual by sqrt(w) before they are stored
+// and summed -- the records, E_a and dP_a are then those of the weighted least-squares problem -- and writes sqrt(w) to `sqw`.
+#define MVBA_RESID_JAC_ARGS                                                                                                 \
+  long long nobs, int m, const double *__restrict__ cam15, const double *__restrict__ X, const int *__restrict__ obs_pt,   \
+      const int *__restrict__ cam_idx, const double2 *__restrict__ xy, double f0, const int *__restrict__ tile_start,     \
+      int n_tiles, double2 *__restrict__ rec, double *__restrict__ PL, const int *__restrict__ tile_slot,                 \
+      double *__restrict__ PLsplit, const double *__restrict__ gcam
+// Robust kernels take one trailing argument of this type (the squared instantiations none: their arguments and code are those of
+// the plain kernels).  b = (delta / f0)^2, sqw = sqrt(w) per observation.
+struct LossArgs {
+  double b;
+  double *sqw;
+};
+template <bool GCAM, int LOSS = LOSS_SQUARED, typename... Robust>
+__global__ __launch_bounds__(1024, 4) void k_resid_jac(MVBA_RESID_JAC_ARGS, Robust... robust) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double *s_cam = smem;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
@@ -214,6 +219,21 @@ __global__ __launch_bounds__(1024, 4) void k_resid_jac(long long nobs, int m, co
       const double *Xa = X + 3 * (size_t)a;
       ObsJ J;
       obs_math(Xa[0], Xa[1], Xa[2], GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS, z.x, z.y, f0, J);
+      if constexpr (LOSS != LOSS_SQUARED) {
+        const LossArgs la = (robust, ...);
+        const double sw = loss_sqrt_w<LOSS>(J.e0 * J.e0 + J.e1 * J.e1, la.b);
+        J.e0 *= sw;
+        J.e1 *= sw;
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+#pragma unroll
+          for (int i = 0; i < 3; ++i) J.jx[rr][i] *= sw;
+          J.jc[rr][0] *= sw;
+#pragma unroll
+          for (int i = 6; i < 9; ++i) J.jc[rr][i] *= sw;
+        }
+        la.sqw[o] = sw;
+      }
       // swizzled slot position (s ^ (lane & 7)): conflict-free ds_write_b128
       double2 *row = stage + lane * REC;
       const int sw = lane & 7;
@@ -432,13 +452,19 @@ struct SlotPace {
 // SLOTS (the slot-resident form below, k_schur_slots): the 21 item rows of a step belong to 21 DIFFERENT lists, each
 // 3-lane slot keeps its own block for the whole run and writes it to its own partial (`out` is then the array of
 // partials and `slot_unit` the 21 unit ids of this wave); padding rows point at the all-zero record / point row.
-template <bool DIAG, bool BIG, bool SLOTS = false>
+// ROBUST (unit form only): the records are scaled by sqrt(w) already (K1), the implied (u, v) columns are not --
+// each item takes sqrt(w) of its k-side and l-side observations from `sqw` into its u, v rows (k side) and its u, v columns
+// (l side).  The 21 + 21 values of a step are gathered with the step's rows (LDS-DMA, 4 bytes per lane, two lanes per value)
+// into staging space the squared form leaves unused: behind the 3-slot point rows (off-diagonal), behind the residuals (diagonal).
+template <bool DIAG, bool BIG, bool SLOTS = false, bool ROBUST = false>
 __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, const long long beg, const int n,
                                                  const int *__restrict__ it_k, const int *__restrict__ it_l,
                                                  const int *__restrict__ it_a, const double2 *__restrict__ rec,
                                                  const double *__restrict__ PB, const double c, const double cu,
                                                  double *__restrict__ out, const int *__restrict__ slot_unit = nullptr,
-                                                 const SlotPace pace = SlotPace{nullptr, nullptr, 0, 0, 2}) {
+                                                 const SlotPace pace = SlotPace{nullptr, nullptr, 0, 0, 2},
+                                                 const double *__restrict__ sqw = nullptr) {
+  static_assert(!(SLOTS && ROBUST), "the slot form has no robust build");
   constexpr int NPS = DIAG ? 5 : 3;                      // staged 16-byte slots of a point row
   const int it = lane / 3, cg = lane - 3 * it;           // compute: item of the step, column group
   const int drow = lane / 7, dslot = lane - 7 * drow;    // record DMA: 9 rows x 7 slots per instruction
@@ -461,7 +487,11 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
   constexpr int PB_OFF = LB_OFF + ((SLOTS && DIAG) ? PSTEP * 16 : PSTEP * PROW);
   constexpr int BUFSZ = SLOTS ? PB_OFF + PSTEP * 16 * NPS : PWAVE_LDS;
   static_assert(!SLOTS || BUFSZ <= SLOT_BUF, "slot form: staging buffer larger than the launch provides");
+  // ROBUST: the step's sqrt(w) values (k side, then l side), in space no DMA of the squared form writes
+  constexpr int W_OFF = DIAG ? LB_OFF + PSTEP * 16 : PB_OFF + PSTEP * 16 * NPS;
+  static_assert(!ROBUST || (DIAG ? W_OFF + PSTEP * 8 <= PB_OFF : W_OFF + 2 * PSTEP * 8 <= BUFSZ), "robust weights fit the staging buffer");
   int ixk[1][3], ixl[1][3], ixa[1][2];  // the next step's indices (the slot form has two pinned register sets of its own)
+  int ixw[2] = {0, 0};                  // ROBUST: the k-side and l-side observation of item lane / 2 of the next step
   auto load_idx = [&](int s0, int (&xk)[3], int (&xl)[3], int (&xa)[2]) {  // indices of the step starting at item s0 (to registers)
     // uniform base + unsigned 32-bit row: the saddr form again (written with int rows the clamps and the
     // address sums were done in 64 bits per lane: ~40 vector instructions per step for seven loads)
@@ -491,6 +521,10 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
     if (DIAG) xl[0] = at(pk, row_of(lane));  // the record whose residual slot this lane fetches
     xa[0] = at(pa, row_of(prow));
     if (DIAG) xa[1] = at(pa, row_of(prow2));
+    if (ROBUST) {
+      ixw[0] = at(pk, row_of(lane >> 1));
+      if (!DIAG) ixw[1] = at(pl, row_of(lane >> 1));
+    }
   };
   // Addresses as "uniform base + 32-bit byte offset" (the saddr form of the memory instructions: one
   // shift-add per address instead of a sign extension, a 64-bit shift and a 64-bit add); BIG: the
@@ -524,11 +558,23 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
       lds_dma16(pb_at(xa[0], pslot), pb_);
       if (lane < 5 * PSTEP - 64) lds_dma16(pb_at(xa[1], pslot2), pb_ + 1024);
     }
+    if (ROBUST && lane < 2 * PSTEP) {  // sqrt(w) of the step's k-side (and l-side) observations, one dword per lane
+      const char *wsrc = reinterpret_cast<const char *>(sqw) + (lane & 1) * 4;
+      __builtin_amdgcn_global_load_lds(wsrc + (size_t)ixw[0] * 8, (__attribute__((address_space(3))) void *)(buf + W_OFF), 4, 0, 0);
+      if (!DIAG)
+        __builtin_amdgcn_global_load_lds(wsrc + (size_t)ixw[1] * 8, (__attribute__((address_space(3))) void *)(buf + W_OFF + PSTEP * 8), 4, 0, 0);
+    }
   };
   // the arithmetic of one step on a landed buffer
   auto compute = [&](const char *buf, const int ns) {
     const char *kbuf = buf, *lbuf = buf + LB_OFF, *pbuf = buf + PB_OFF;
     if (it < ns) {
+      double swk = 1.0, swl = 1.0;
+      if (ROBUST) {
+        const double *wl = reinterpret_cast<const double *>(buf + W_OFF);
+        swk = wl[it];
+        swl = DIAG ? swk : wl[PSTEP + it];
+      }
       const double2 *kr = reinterpret_cast<const double2 *>(kbuf + it * PROW);
       const double2 *lr = DIAG ? kr : reinterpret_cast<const double2 *>(lbuf + it * PROW);
       const double *pb = reinterpret_cast<const double *>(pbuf + it * (16 * NPS));
@@ -556,16 +602,22 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
         }
       }
       const double2 s0v = lr[sel0], s1v = lr[sel1], s2v = lr[sel2];
-      const double sx[3] = {s0v.x, al12 * s1v.x + bx1, al12 * s2v.x};
-      const double sy[3] = {s0v.y, al12 * s1v.y, al12 * s2v.y + bx1};
+      const double bxw = ROBUST ? bx1 * swl : bx1;  // (u, v) columns: sqrt(w) of the l-side observation
+      const double sx[3] = {s0v.x, al12 * s1v.x + bxw, al12 * s2v.x};
+      const double sy[3] = {s0v.y, al12 * s1v.y, al12 * s2v.y + bxw};
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         const double v0 = t00 * sx[q] + t01 * sy[q], v1 = t10 * sx[q] + t11 * sy[q];
         // two chained FMAs into the accumulator per row (written out: `acc += a*b + c*d` compiles to
         // mul + fma + add, a third more fp64 instructions in a kernel whose VALU is 70 % busy)
         acc[0][q] = fma(kf.y, v1, fma(kf.x, v0, acc[0][q]));
-        acc[1][q] += v0;
-        acc[2][q] += v1;
+        if (ROBUST) {  // (u, v) rows: sqrt(w) of the k-side observation
+          acc[1][q] = fma(swk, v0, acc[1][q]);
+          acc[2][q] = fma(swk, v1, acc[2][q]);
+        } else {
+          acc[1][q] += v0;
+          acc[2][q] += v1;
+        }
         acc[3][q] = fma(kx0.y, v1, fma(kx0.x, v0, acc[3][q]));
         acc[4][q] = fma(kx1.y, v1, fma(kx1.x, v0, acc[4][q]));
         acc[5][q] = fma(kx2.y, v1, fma(kx2.x, v0, acc[5][q]));
@@ -779,13 +831,13 @@ __device__ __forceinline__ void schur_pairs_unit(char *wbuf, const int lane, con
 
 // One wave per block: a wave works alone, and in a wider block its LDS and wave slots stay taken until
 // the block's slowest wave has finished (4 waves per block: 1.945 ms, 2: 1.92, 1: 1.89 at config 3).
-template <bool BIG>
+template <bool BIG, bool ROBUST = false>
 __device__ __forceinline__ void schur_pairs_wave(const int4 *__restrict__ units, const int *__restrict__ q_ptr,
                                                        const int *__restrict__ q_units, const int *__restrict__ it_k,
                                                        const int *__restrict__ it_l, const int *__restrict__ it_a,
                                                        const double2 *__restrict__ rec,
                                                        const double *__restrict__ PB, double c, double f0,
-                                                       double *__restrict__ partial) {
+                                                       double *__restrict__ partial, const double *__restrict__ sqw = nullptr) {
   extern __shared__ char smem_pairs[];
   const int lane = threadIdx.x;
   char *wbuf = smem_pairs;
@@ -806,6 +858,12 @@ __device__ __forceinline__ void schur_pairs_wave(const int4 *__restrict__ units,
   const long long beg = ((long long)ud_y << 32) | (unsigned)ud_x;
   const int n = ud_z, cam_k = (int)((unsigned)ud_w >> 16), cam_l = ud_w & 0xffff;
   double *out = partial + (size_t)u * UNIT_STRIDE;
+  if (ROBUST) {
+    const SlotPace none{nullptr, nullptr, 0, 0, 2};
+    if (cam_k == cam_l) schur_pairs_unit<true, BIG, false, true>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out, nullptr, none, sqw);
+    else schur_pairs_unit<false, BIG, false, true>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out, nullptr, none, sqw);
+    return;
+  }
   if (cam_k == cam_l) schur_pairs_unit<true, BIG>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out);
   else schur_pairs_unit<false, BIG>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out);
 }
@@ -820,6 +878,13 @@ __global__ __launch_bounds__(64, 3) void k_schur_pairs(MVBA_PAIRS_ARGS) {
 }
 __global__ __launch_bounds__(64, 3) void k_schur_pairs_big(MVBA_PAIRS_ARGS) {  // 64-bit record / point-block offsets
   schur_pairs_wave<true>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial);
+}
+// robust losses: sqrt(w) per observation in `sqw`
+__global__ __launch_bounds__(64, 3) void k_schur_pairs_robust(MVBA_PAIRS_ARGS, const double *__restrict__ sqw) {
+  schur_pairs_wave<false, true>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial, sqw);
+}
+__global__ __launch_bounds__(64, 3) void k_schur_pairs_big_robust(MVBA_PAIRS_ARGS, const double *__restrict__ sqw) {
+  schur_pairs_wave<true, true>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial, sqw);
 }
 
 // ------------------------------------------------------------------ K3 (slot-resident form)
@@ -991,9 +1056,13 @@ __device__ __forceinline__ void dense_main_mfma(const double *sG, const double *
 // among themselves.  (With every wave doing every phase in turn -- four barriers per chunk -- the workgroups of a CU ran in
 // lockstep and the phases never overlapped: 1.55 ms at 1 M x 12 for 0.81 ms of MFMA phase; with four producer waves of two points
 // each the producers were the longer role: 1.90 ms.)
-template <int T, bool TABLE>  // TABLE: the records of a point through obs_of (missing observations), otherwise one contiguous range
-__global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_schur_dense(const double2 *__restrict__ rec, const double *__restrict__ PB, const int *__restrict__ obs_of,
-                                                     long long N, int m, double cu, double *__restrict__ part) {
+// ROBUST: the records are scaled by sqrt(w) (K1); the constant columns of an observation become sqrt(w) / f0
+// instead of 1 / f0 -- the per-(point, camera) factor sF takes sqrt(w) from `sqw`, fetched with the records.
+#define MVBA_DENSE_ARGS                                                                                                   \
+  const double2 *__restrict__ rec, const double *__restrict__ PB, const int *__restrict__ obs_of, long long N, int m, double cu, \
+      double *__restrict__ part
+template <int T, bool TABLE, bool ROBUST = false, typename... Robust>  // TABLE: the records of a point through obs_of (missing observations), otherwise one contiguous range
+__global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_schur_dense(MVBA_DENSE_ARGS, Robust... robust) {
   constexpr int NC = dense_consumers(T);           // consumer waves (4 + 8 producers up to 8 tiles, 8 + 4 beyond)
   constexpr int P = T * (T + 1) / 2, NPW = (P + NC - 1) / NC, W = 16 * T, NCW = ((16 * T) / 9 + NC - 1) / NC;
   constexpr int CH = dense_ch(T);       // points per chunk = producer waves (the double-buffered rows must fit the LDS beside each other)
@@ -1025,6 +1094,7 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
     // ~2 us of loaded memory latency -- 1.5 TB/s over the chip, which is where the kernel sat at every camera count (~1.0 ms per
     // million points x 12 cameras whatever the matrix cores had to do)
     double2 preA[NPRE], prepbA, preB[NPRE], prepbB;
+    double swA[NPRE], swB[NPRE];                   // ROBUST: sqrt(w) of the observation of every record slot a lane fetched
     bool lvA, lvB;
     int oidA[NPRE], oidB[NPRE], oid_next[NPRE];    // (obs_of != nullptr) the observations of a set's point / of the point fetched next
     double *sF = sFlag + (size_t)pw * m;
@@ -1037,7 +1107,7 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
         oid_next[u] = (got & msk) | ~msk;          // (-1 outside; the load itself is unconditional, see fetch)
       }
     };
-    auto fetch = [&](long long ch, double2 (&pre)[NPRE], int (&oid)[NPRE], double2 &prepb, bool &lv) {  // this wave's records and point row of chunk ch (zeros past the last point)
+    auto fetch = [&](long long ch, double2 (&pre)[NPRE], int (&oid)[NPRE], double2 &prepb, bool &lv, double (&sw)[NPRE]) {  // this wave's records and point row of chunk ch (zeros past the last point)
       // The loads are UNCONDITIONAL on clamped addresses and what must be zero (a missing observation, a point past the end) is
       // zeroed on the bit pattern in build(): behind a lane-dependent branch the compiler cannot count the loads in flight and
       // waits for all of them (vmcnt(0)) -- the other set's too, which is the one meant to stay in flight
@@ -1048,6 +1118,7 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
         for (int u = 0; u < NPRE; ++u) {
           oid[u] = oid_next[u];
           pre[u] = rec[(size_t)max(oid[u], 0) * REC + ((lane + 64 * u) & 7)];
+          if constexpr (ROBUST) sw[u] = (robust, ...).sqw[max(oid[u], 0)];
         }
       } else {
         const double2 *src = rec + (size_t)min(a, N - 1) * m * REC;
@@ -1055,6 +1126,7 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
         for (int u = 0; u < NPRE; ++u) {
           pre[u] = src[min(lane + 64 * u, m * REC - 1)];
           oid[u] = live ? 0 : -1;
+          if constexpr (ROBUST) sw[u] = (robust, ...).sqw[(size_t)min(a, N - 1) * m + min((lane + 64 * u) >> 3, m - 1)];
         }
       }
       prepb = reinterpret_cast<const double2 *>(PB + (size_t)min(a, N - 1) * PBS)[lane & 7];
@@ -1063,12 +1135,12 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
       const long long msk = c ? -1LL : 0LL;
       return double2{__longlong_as_double(__double_as_longlong(v.x) & msk), __longlong_as_double(__double_as_longlong(v.y) & msk)};
     };
-    auto build = [&](int buf, const double2 (&pre)[NPRE], const int (&oid)[NPRE], const double2 &prepb, bool lv) {  // registers -> the rows of G and the camera rows of this wave's point in buffer `buf`
+    auto build = [&](int buf, const double2 (&pre)[NPRE], const int (&oid)[NPRE], const double2 &prepb, bool lv, const double (&sw)[NPRE]) {  // registers -> the rows of G and the camera rows of this wave's point in buffer `buf`
 #pragma unroll
       for (int u = 0; u < NPRE; ++u) {
         const int e = lane + 64 * u;
         if (e < m * REC) sR[e] = keep(oid[u] >= 0, pre[u]);
-        if (e < m * REC && (e & 7) == 0) sF[e >> 3] = oid[u] >= 0 ? 1.0 : 0.0;
+        if (e < m * REC && (e & 7) == 0) sF[e >> 3] = oid[u] >= 0 ? (ROBUST ? sw[u] : 1.0) : 0.0;
       }
       sP[lane & 7] = keep(lv, prepb);             // (every lane, eight copies of each slot: a store under `lane < 8` drew a vmcnt(0))
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1109,26 +1181,26 @@ __global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_sch
     const long long gs = gridDim.x;
     // (a fetch past the last chunk loads nothing: zero records nobody reads; fetch_ids likewise -1)
     if (TABLE) fetch_ids(ch);
-    fetch(ch, preA, oidA, prepbA, lvA);
+    fetch(ch, preA, oidA, prepbA, lvA, swA);
     if (TABLE) fetch_ids(ch + gs);
-    fetch(ch + gs, preB, oidB, prepbB, lvB);
+    fetch(ch + gs, preB, oidB, prepbB, lvB, swB);
     if (TABLE) fetch_ids(ch + 2 * gs);
-    build(0, preA, oidA, prepbA, lvA);
-    fetch(ch + 2 * gs, preA, oidA, prepbA, lvA);
+    build(0, preA, oidA, prepbA, lvA, swA);
+    fetch(ch + 2 * gs, preA, oidA, prepbA, lvA, swA);
     if (TABLE) fetch_ids(ch + 3 * gs);
     __syncthreads();
     // One barrier per chunk, as the consumers; the sets alternate: B holds chunk ch + 1, A chunk ch + 2.  Nothing in the body is
     // conditional (behind `if (ch + gs < n_chunks)` the compiler lost count of the loads in flight and waited vmcnt(0) for both
     // sets): past the last chunk a build writes a chunk of zeros into the buffer nobody reads any more.
     for (int b = 0; ch < n_chunks;) {
-      build(b ^ 1, preB, oidB, prepbB, lvB);
-      fetch(ch + 3 * gs, preB, oidB, prepbB, lvB);
+      build(b ^ 1, preB, oidB, prepbB, lvB, swB);
+      fetch(ch + 3 * gs, preB, oidB, prepbB, lvB, swB);
       if (TABLE) fetch_ids(ch + 4 * gs);
       __syncthreads();
       ch += gs, b ^= 1;
       if (ch >= n_chunks) break;
-      build(b ^ 1, preA, oidA, prepbA, lvA);
-      fetch(ch + 3 * gs, preA, oidA, prepbA, lvA);
+      build(b ^ 1, preA, oidA, prepbA, lvA, swA);
+      fetch(ch + 3 * gs, preA, oidA, prepbA, lvA, swA);
       if (TABLE) fetch_ids(ch + 4 * gs);
       __syncthreads();
       ch += gs, b ^= 1;
@@ -2368,12 +2440,13 @@ __global__ void k_update_cams(int m, const double *__restrict__ cam15, const dou
 // The trial cost is k_cost on the trial state (K6).
 // BT threads per block: 256, or 1024 once the camera tables (m x 28 doubles) leave room for one block per CU only
 // (beyond ~230 cameras: four waves per CU then; config 4's shard 0.47 -> see profiles/r04_m_*)
-template <int G, int BT = 256, bool GCAM = false>
-__global__ __launch_bounds__(BT) void k_backsub(long long npts, int m, const long long *__restrict__ pt_ptr,
-                                                 const int *__restrict__ cam_idx, const double *__restrict__ PB,
-                                                 const double *__restrict__ dxi, const double *__restrict__ X,
-                                                 const double *__restrict__ cam15, double f0, double *__restrict__ Xt,
-                                                 double *__restrict__ dX, const double *__restrict__ gcam, const double *__restrict__ gdxi) {
+// ROBUST: F_ao of the weighted problem is w_o times the unweighted one: y_o is scaled by sqrt(w)^2 from `sqw`.
+#define MVBA_BACKSUB_ARGS                                                                                                    \
+  long long npts, int m, const long long *__restrict__ pt_ptr, const int *__restrict__ cam_idx, const double *__restrict__ PB, \
+      const double *__restrict__ dxi, const double *__restrict__ X, const double *__restrict__ cam15, double f0,               \
+      double *__restrict__ Xt, double *__restrict__ dX, const double *__restrict__ gcam, const double *__restrict__ gdxi
+template <int G, int BT = 256, bool GCAM = false, bool ROBUST = false, typename... Robust>
+__global__ __launch_bounds__(BT) void k_backsub(MVBA_BACKSUB_ARGS, Robust... robust) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double *s_dxi = smem, *s_cam = smem + DXI_LDS * m;
   if (!GCAM) {
@@ -2408,14 +2481,24 @@ __global__ __launch_bounds__(BT) void k_backsub(long long npts, int m, const lon
     // indices: one memory latency per point instead of one per observation), the rare rest one by one
     constexpr int PF = 4;
     int kk[PF];
+    double sw[PF];
     const long long olast = max(o1 - 1, o0);
 #pragma unroll
     for (int u = 0; u < PF; ++u) kk[u] = cam_idx[min(o0 + s + G * u, olast)];
+    if constexpr (ROBUST)
+#pragma unroll
+      for (int u = 0; u < PF; ++u) sw[u] = (robust, ...).sqw[min(o0 + s + G * u, olast)];
 #pragma unroll
     for (int u = 0; u < PF; ++u)
       if (o0 + s + G * u < o1) {
         double t0, t1, t2;
         obs_backsub(Xa0, Xa1, Xa2, GCAM ? gcam + (size_t)kk[u] * CAM_LDS : s_cam + kk[u] * CAM_LDS, GCAM ? gdxi + (size_t)DXI_LDS * kk[u] : s_dxi + DXI_LDS * kk[u], f0, t0, t1, t2);
+        if constexpr (ROBUST) {
+          const double w = sw[u] * sw[u];
+          t0 *= w;
+          t1 *= w;
+          t2 *= w;
+        }
         y0 += t0;
         y1 += t1;
         y2 += t2;
@@ -2424,6 +2507,12 @@ __global__ __launch_bounds__(BT) void k_backsub(long long npts, int m, const lon
       const int k = cam_idx[o];
       double t0, t1, t2;
       obs_backsub(Xa0, Xa1, Xa2, GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS, GCAM ? gdxi + (size_t)DXI_LDS * k : s_dxi + DXI_LDS * k, f0, t0, t1, t2);
+      if constexpr (ROBUST) {
+        const double so = (robust, ...).sqw[o], w = so * so;
+        t0 *= w;
+        t1 *= w;
+        t2 *= w;
+      }
       y0 += t0;
       y1 += t1;
       y2 += t2;
@@ -2457,11 +2546,13 @@ __global__ void k_cam_tables(int m, const double *__restrict__ cam15, const doub
 }
 
 // residual-only pass at a given state (initial cost, ref :85-87)
-template <bool GCAM>
-__global__ __launch_bounds__(512) void k_cost(long long nobs, int m, const double *__restrict__ cam15,
-                                              const double *__restrict__ X, const int *__restrict__ obs_pt,
-                                              const int *__restrict__ cam_idx, const double2 *__restrict__ xy,
-                                              double f0, double *__restrict__ partials, const double *__restrict__ gcam) {
+// LOSS: sum rho(|e|^2) instead, b = lb; same grid, same tree.
+#define MVBA_COST_ARGS                                                                                                   \
+  long long nobs, int m, const double *__restrict__ cam15, const double *__restrict__ X, const int *__restrict__ obs_pt, \
+      const int *__restrict__ cam_idx, const double2 *__restrict__ xy, double f0, double *__restrict__ partials,        \
+      const double *__restrict__ gcam
+template <bool GCAM, int LOSS = LOSS_SQUARED, typename... Robust>
+__global__ __launch_bounds__(512) void k_cost(MVBA_COST_ARGS, Robust... robust) {
   extern __shared__ __attribute__((aligned(16))) double s_cam[];
   __shared__ double s_red[16];
   if (!GCAM) {
@@ -2484,10 +2575,33 @@ __global__ __launch_bounds__(512) void k_cost(long long nobs, int m, const doubl
     a_n = obs_pt[on];
     k_n = cam_idx[on];
     z_n = xy[on];
-    cost += obs_cost(X0, X1, X2, GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS, z.x, z.y, f0);
+    const double so = obs_cost(X0, X1, X2, GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS, z.x, z.y, f0);
+    if constexpr (LOSS != LOSS_SQUARED) cost += loss_rho<LOSS>(so, (robust, ...).b);
+    else cost += so;
   }
   const double t = block_sum(cost, s_red);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// f0 e_o -- the residual in image units -- of every observation at a given state (mvba_residuals)
+template <bool GCAM>
+__global__ __launch_bounds__(256) void k_residuals(long long nobs, int m, const double *__restrict__ cam15, const double *__restrict__ X,
+                                                   const int *__restrict__ obs_pt, const int *__restrict__ cam_idx,
+                                                   const double2 *__restrict__ xy, double f0, double2 *__restrict__ out,
+                                                   const double *__restrict__ gcam) {
+  extern __shared__ __attribute__((aligned(16))) double s_cam[];
+  if (!GCAM) {
+    load_cams_to_lds(cam15, m, f0, s_cam);
+    __syncthreads();
+  }
+  for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < nobs; o += (long long)gridDim.x * blockDim.x) {
+    const int a = obs_pt[o], k = cam_idx[o];
+    const double2 z = xy[o];
+    double e0, e1;
+    obs_resid(X[3 * (size_t)a], X[3 * (size_t)a + 1], X[3 * (size_t)a + 2], GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS,
+              z.x, z.y, f0, e0, e1);
+    out[o] = make_double2(f0 * e0, f0 * e1);
+  }
 }
 
 // out[0] = cost; the status flags ride along in the next 8 bytes so that the host needs ONE
@@ -2856,6 +2970,12 @@ struct mvba_handle {
   // covariances (mvba_covariance), allocated on the first call: the camera-block table of S^-1, the two column panels of the
   // triangular inverse, the point and camera blocks
   double *d_cov_sig = nullptr, *d_cov_panel = nullptr, *d_cov_pts = nullptr, *d_cov_cam = nullptr;
+  // robust loss (mvba_create_robust), fixed for the engine's life: LOSS_* , b = (delta / f0)^2, and sqrt(w) of
+  // every observation at the last linearisation (K1 writes it, K3 and K5 read it)
+  int loss = LOSS_SQUARED;
+  double loss_b = 0.0;
+  double *d_sqw = nullptr;
+  double2 *d_resid = nullptr;  // mvba_residuals, allocated on the first call
 };
 
 namespace {
@@ -3001,6 +3121,18 @@ int global_cost(mvba_handle *h, double *E) {
   return MVBA_OK;
 }
 
+// the robust instantiations by loss; the squared loss keeps its own kernels
+typedef void (*ResidJacRobustFn)(MVBA_RESID_JAC_ARGS, LossArgs);
+typedef void (*CostRobustFn)(MVBA_COST_ARGS, LossArgs);
+ResidJacRobustFn resid_jac_robust(bool gcam, int loss) {
+  if (loss == LOSS_HUBER) return gcam ? k_resid_jac<true, LOSS_HUBER, LossArgs> : k_resid_jac<false, LOSS_HUBER, LossArgs>;
+  return gcam ? k_resid_jac<true, LOSS_CAUCHY, LossArgs> : k_resid_jac<false, LOSS_CAUCHY, LossArgs>;
+}
+CostRobustFn cost_robust(bool gcam, int loss) {
+  if (loss == LOSS_HUBER) return gcam ? k_cost<true, LOSS_HUBER, LossArgs> : k_cost<false, LOSS_HUBER, LossArgs>;
+  return gcam ? k_cost<true, LOSS_CAUCHY, LossArgs> : k_cost<false, LOSS_CAUCHY, LossArgs>;
+}
+
 // the camera tables in device memory for the kernels that cannot hold them in LDS (no-op up to LDS_CAMERAS cameras)
 void cam_tables(mvba_handle *h, const double *cam15, const double *dxi) {
   if (h->gcam) hipLaunchKernelGGL(k_cam_tables, dim3((h->m + 255) / 256), dim3(256), 0, h->stream, h->m, cam15, dxi, h->f0, h->d_cam18, h->d_dxi10);
@@ -3009,6 +3141,10 @@ void launch_cost_kernel(mvba_handle *h, const double *cam15, const double *X) {
   const size_t lds = h->gcam ? 0 : (size_t)h->m * CAM_LDS * sizeof(double);
   cam_tables(h, cam15, nullptr);
   // (512 threads once the camera table leaves room for two blocks per CU only: config 4's 500 cameras)
+  if (h->loss != LOSS_SQUARED)
+    hipLaunchKernelGGL(cost_robust(h->gcam, h->loss), dim3(h->cost_grid), dim3(lds > 40 * 1024 ? 512 : 256), lds, h->stream, h->nobs, h->m, cam15, X,
+                       h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_partials, h->d_cam18, LossArgs{h->loss_b, h->d_sqw});
+  else
   hipLaunchKernelGGL(h->gcam ? k_cost<true> : k_cost<false>, dim3(h->cost_grid), dim3(lds > 40 * 1024 ? 512 : 256), lds, h->stream, h->nobs, h->m, cam15, X,
                      h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_partials, h->d_cam18);
 }
@@ -3093,7 +3229,8 @@ int mvba_device_count(int32_t *count) {
   return MVBA_OK;
 }
 
-int mvba_create(const mvba_problem *p, mvba_handle **out) {
+namespace {
+int create_engine(const mvba_problem *p, int loss, double loss_b, mvba_handle **out) {
   if (!p || !out) return fail(MVBA_ERR_BADARG, "null argument");
   const CreateKnobs knobs = read_create_knobs();
   // MVBA_CREATE_TIMING=1: wall time of this function's stages on stderr (tools/time_create.py; the engine's construction is a
@@ -3181,6 +3318,7 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
     if (e != hipSuccess) { delete h; return fail(MVBA_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e)); }
   }
   h->N = N; h->nobs = nobs; h->m = m; h->gauge_axis = p->gauge_axis; h->f0 = p->f0; h->D = 9 * m - 7; h->ld = (h->D + 3) & ~3;
+  h->loss = loss; h->loss_b = loss_b;
   h->gcam = m > LDS_CAMERAS;
 #define TRY(x) do { int rc_ = (x); if (rc_) { mvba_destroy(h); return rc_; } } while (0)
 #define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { mvba_destroy(h); return fail(MVBA_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
@@ -3207,7 +3345,8 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
   }
   // ---- pair-major Schur index (see k_schur_pairs).  Items (obs of k, obs of l, point) for every
   // pair k <= l of a point's cameras, counting-sorted by pair, ascending point inside a pair.
-  h->schur_mode = knobs.schur_pairs ? SCHUR_PAIRS : SCHUR_SLOTS;
+  // (a robust loss never takes the slot form: the unit form then, as when the lists do not fit one round -- DESIGN.md §12)
+  h->schur_mode = knobs.schur_pairs || loss != LOSS_SQUARED ? SCHUR_PAIRS : SCHUR_SLOTS;
   h->force_big = knobs.force_big;
   h->check_solve = knobs.check_solve;
   h->check_solve_tol = knobs.check_solve_tol;
@@ -3676,6 +3815,10 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
   TRY(dmalloc(&h->d_tiles, tiles.size()));
   for (int i = 0; i < 2; ++i) { TRY(dmalloc(&h->d_X[i], 3 * N)); TRY(dmalloc(&h->d_cam15[i], (size_t)CAM_IN * m)); }
   TRY(dmalloc(&h->d_rec, (size_t)REC * (nobs + 1)));  // + the all-zero record and point row the slot form's padding points at
+  if (loss != LOSS_SQUARED) {
+    TRY(dmalloc(&h->d_sqw, nobs + 1));
+    TRYH(hipMemset(h->d_sqw, 0, sizeof(double) * (nobs + 1)));
+  }
   TRY(dmalloc(&h->d_PL, 9 * N));
   TRY(dmalloc(&h->d_PB, (size_t)PBS * (N + 1)));
   TRYH(hipMemset(h->d_rec + (size_t)REC * nobs, 0, sizeof(double2) * REC));
@@ -3795,11 +3938,36 @@ int mvba_create(const mvba_problem *p, mvba_handle **out) {
   TRYH(hipFuncSetAttribute(h->gcam ? (const void *)k_resid_jac<true> : (const void *)k_resid_jac<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                            (int)((size_t)((h->gcam ? 0 : ((m * CAM_LDS + 1) & ~1)) + (h->k1_threads / 64) * 64 * 2 * REC) * sizeof(double))));
   TRYH(hipFuncSetAttribute((const void *)k_cost<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
+  TRYH(hipFuncSetAttribute((const void *)k_residuals<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
+  if (loss != LOSS_SQUARED) {
+    for (const void *f : {(const void *)k_backsub<2, 256, false, true, LossArgs>, (const void *)k_backsub<4, 256, false, true, LossArgs>, (const void *)k_backsub<8, 256, false, true, LossArgs>,
+                          (const void *)k_backsub<2, 512, false, true, LossArgs>, (const void *)k_backsub<4, 512, false, true, LossArgs>, (const void *)k_backsub<8, 512, false, true, LossArgs>,
+                          (const void *)k_backsub<2, 1024, false, true, LossArgs>, (const void *)k_backsub<4, 1024, false, true, LossArgs>, (const void *)k_backsub<8, 1024, false, true, LossArgs>})
+      TRYH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
+    TRYH(hipFuncSetAttribute((const void *)resid_jac_robust(h->gcam, loss), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)((size_t)((h->gcam ? 0 : ((m * CAM_LDS + 1) & ~1)) + (h->k1_threads / 64) * 64 * 2 * REC) * sizeof(double))));
+    TRYH(hipFuncSetAttribute((const void *)cost_robust(false, loss), hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
+  }
 #undef TRY
 #undef TRYH
   lap("attributes");
   *out = h;
   return MVBA_OK;
+}
+}  // namespace
+
+int mvba_create(const mvba_problem *p, mvba_handle **out) { return create_engine(p, LOSS_SQUARED, 0.0, out); }
+
+int mvba_create_robust(const mvba_problem *p, int32_t loss, double scale, mvba_handle **out) {
+  if (!p || !out) return fail(MVBA_ERR_BADARG, "null argument");
+  if (loss == LOSS_SQUARED) return create_engine(p, LOSS_SQUARED, 0.0, out);
+  if (loss != LOSS_HUBER && loss != LOSS_CAUCHY)
+    return fail(MVBA_ERR_BADARG, "loss = " + std::to_string(loss) + " is not a loss (0 squared, 1 Huber, 2 Cauchy)");
+  if (!(scale > 0.0) || !std::isfinite(scale))
+    return fail(MVBA_ERR_BADARG, "loss scale = " + std::to_string(scale) + " must be finite and > 0 for a robust loss");
+  if (!(p->f0 > 0.0) || !std::isfinite(p->f0)) return fail(MVBA_ERR_BADARG, "a robust loss needs f0 > 0");
+  const double r = scale / p->f0;
+  return create_engine(p, loss, r * r, out);
 }
 
 void mvba_destroy(mvba_handle *h) {
@@ -3812,7 +3980,7 @@ void mvba_destroy(mvba_handle *h) {
                   h->d_dxi, h->d_dX, h->d_partials, h->d_cost, h->d_flag, h->d_allcost, h->d_it_k, h->d_it_l, h->d_it_a,
                   h->d_units, h->d_unit_ptr, h->d_q_ptr, h->d_q_units, h->d_partial, h->d_dense_part, h->d_dense_obs, h->d_sim, h->d_bar, h->d_wdesc,
                   h->d_wunits, h->d_seg_end, h->d_prog, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10,
-                  h->d_cov_sig, h->d_cov_panel, h->d_cov_pts, h->d_cov_cam};
+                  h->d_cov_sig, h->d_cov_panel, h->d_cov_pts, h->d_cov_cam, h->d_sqw, h->d_resid};
   for (void *q : ptrs) if (q) hipFree(q);
   for (double *q : h->snap_slabs) hipFree(q);
   if (h->h_cost) hipHostFree(h->h_cost);
@@ -3897,6 +4065,11 @@ void launch_resid_jac(mvba_handle *h) {  // K1 with K2 fused in, at the committe
   cam_tables(h, h->d_cam15[h->cur], nullptr);
   const int wpb = kt / 64;
   const int grid = std::max(1, std::min(2048 * 256 / kt, (h->n_tiles + wpb - 1) / wpb));
+  if (h->loss != LOSS_SQUARED)
+    hipLaunchKernelGGL(resid_jac_robust(h->gcam, h->loss), dim3(grid), dim3(kt), lds, h->stream, h->nobs, h->m, h->d_cam15[h->cur],
+                       h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
+                       h->d_tile_slot, h->d_PLsplit, h->d_cam18, LossArgs{h->loss_b, h->d_sqw});
+  else
   hipLaunchKernelGGL(h->gcam ? k_resid_jac<true> : k_resid_jac<false>, dim3(grid), dim3(kt), lds, h->stream, h->nobs, h->m, h->d_cam15[h->cur],
                      h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
                      h->d_tile_slot, h->d_PLsplit, h->d_cam18);
@@ -3927,6 +4100,10 @@ void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b]
         hipLaunchKernelGGL(k_schur_slots, dim3(h->n_waves), dim3(64), SLOT_LDS, h->stream, h->d_wdesc,
                            h->d_wunits, h->d_it_x, (const int *)nullptr, (const int *)nullptr, h->d_rec, h->d_PB, c, h->f0, h->d_partial,
                            h->slot_nR, h->d_seg_end, h->d_prog, h->slot_nseg, SLOT_LAG, h->d_range_o0);
+    } else if (h->n_units && h->loss != LOSS_SQUARED) {
+      hipLaunchKernelGGL(big ? k_schur_pairs_big_robust : k_schur_pairs_robust, dim3(8 * h->q_max), dim3(64),
+                         PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, h->d_it_k, h->d_it_l, h->d_it_a, h->d_rec, h->d_PB, c,
+                         h->f0, h->d_partial, (const double *)h->d_sqw);
     } else if (h->n_units) {
       hipLaunchKernelGGL(big ? k_schur_pairs_big : k_schur_pairs, dim3(8 * h->q_max), dim3(64),
                          PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, h->d_it_k, h->d_it_l, h->d_it_a, h->d_rec, h->d_PB, c, h->f0, h->d_partial);
@@ -3947,14 +4124,28 @@ void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b]
       hipLaunchKernelGGL(kern, dim3(h->dense_blocks), dim3(64 * (dense_consumers(T) + CH)), lds, h->stream, (const double2 *)h->d_rec, (const double *)h->d_PB, (const int *)h->d_dense_obs,
                          (long long)h->N, m, 1.0 / h->f0, h->d_dense_part);
     };
-    const bool table = h->d_dense_obs != nullptr;
-#define MVBA_DENSE_CASE(t) case t: if (table) launch(k_schur_dense<t, true>); else launch(k_schur_dense<t, false>); break;
+    auto launch_robust = [&](auto kern) {  // (the same, with sqrt(w) per observation)
+      if (!h->dense_attr_set) {
+        const int mm = 16 * T / 9;
+        const size_t lds_max = sizeof(double) * ((size_t)2 * 3 * CH * 16 * T + (size_t)2 * CH * mm * 32 + (size_t)CH * mm + 2 * 3 * CH) + sizeof(double2) * CH * ((size_t)mm * REC + 8);
+        hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+        h->dense_attr_set = true;
+      }
+      hipLaunchKernelGGL(kern, dim3(h->dense_blocks), dim3(64 * (dense_consumers(T) + CH)), lds, h->stream, (const double2 *)h->d_rec, (const double *)h->d_PB, (const int *)h->d_dense_obs,
+                         (long long)h->N, m, 1.0 / h->f0, h->d_dense_part, LossArgs{h->loss_b, h->d_sqw});
+    };
+    const bool table = h->d_dense_obs != nullptr, robust = h->loss != LOSS_SQUARED;
+#define MVBA_DENSE_LAUNCH(t) \
+  if (robust) { if (table) launch_robust(k_schur_dense<t, true, true, LossArgs>); else launch_robust(k_schur_dense<t, false, true, LossArgs>); } \
+  else if (table) launch(k_schur_dense<t, true>); else launch(k_schur_dense<t, false>);
+#define MVBA_DENSE_CASE(t) case t: MVBA_DENSE_LAUNCH(t) break;
     switch (T) {
       MVBA_DENSE_CASE(1) MVBA_DENSE_CASE(2) MVBA_DENSE_CASE(3) MVBA_DENSE_CASE(4) MVBA_DENSE_CASE(5) MVBA_DENSE_CASE(6)
       MVBA_DENSE_CASE(7) MVBA_DENSE_CASE(8) MVBA_DENSE_CASE(9) MVBA_DENSE_CASE(10) MVBA_DENSE_CASE(11)
-      default: if (table) launch(k_schur_dense<12, true>); else launch(k_schur_dense<12, false>); break;
+      default: MVBA_DENSE_LAUNCH(12) break;
     }
 #undef MVBA_DENSE_CASE
+#undef MVBA_DENSE_LAUNCH
     const long long n_el = (long long)nA + 9 * m;
     hipLaunchKernelGGL(k_schur_dense_finish, dim3((unsigned)((n_el + 3) / 4)), dim3(256), 0, h->stream, m, T, h->dense_blocks,
                        (const double *)h->d_dense_part, c, d_A, d_b);
@@ -4081,6 +4272,15 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
                   : wide ? (G == 2 ? k_backsub<2, 1024> : (G == 4 ? k_backsub<4, 1024> : k_backsub<8, 1024>))
                   : mid ? (G == 2 ? k_backsub<2, 512> : (G == 4 ? k_backsub<4, 512> : k_backsub<8, 512>))
                         : (G == 2 ? k_backsub<2> : (G == 4 ? k_backsub<4> : k_backsub<8>));
+      if (h->loss != LOSS_SQUARED) {
+        auto kr = h->gcam ? (G == 2 ? k_backsub<2, 256, true, true, LossArgs> : (G == 4 ? k_backsub<4, 256, true, true, LossArgs> : k_backsub<8, 256, true, true, LossArgs>))
+                  : wide ? (G == 2 ? k_backsub<2, 1024, false, true, LossArgs> : (G == 4 ? k_backsub<4, 1024, false, true, LossArgs> : k_backsub<8, 1024, false, true, LossArgs>))
+                  : mid ? (G == 2 ? k_backsub<2, 512, false, true, LossArgs> : (G == 4 ? k_backsub<4, 512, false, true, LossArgs> : k_backsub<8, 512, false, true, LossArgs>))
+                        : (G == 2 ? k_backsub<2, 256, false, true, LossArgs> : (G == 4 ? k_backsub<4, 256, false, true, LossArgs> : k_backsub<8, 256, false, true, LossArgs>));
+        hipLaunchKernelGGL(kr, dim3(nblk), dim3(bt), lds, h->stream, h->N, m, h->d_pt_ptr, h->d_cam, h->d_PB, h->d_dxi,
+                           h->d_X[h->cur], h->d_cam15[h->cur], h->f0, h->d_X[trial], h->d_dX, h->d_cam18, h->d_dxi10,
+                           LossArgs{h->loss_b, h->d_sqw});
+      } else
       hipLaunchKernelGGL(kern, dim3(nblk), dim3(bt), lds, h->stream, h->N, m, h->d_pt_ptr, h->d_cam, h->d_PB, h->d_dxi,
                          h->d_X[h->cur], h->d_cam15[h->cur], h->f0, h->d_X[trial], h->d_dX, h->d_cam18, h->d_dxi10);
     }
@@ -4190,8 +4390,31 @@ int mvba_commit(mvba_handle *h) {
   return MVBA_OK;
 }
 
+int mvba_residuals(mvba_handle *h, double *e) {
+  if (!h || !e) return fail(MVBA_ERR_BADARG, "null argument");
+  if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
+  MVBA_HIP(hipSetDevice(h->device));
+  if (!h->nobs) return MVBA_OK;
+  if (!h->d_resid) {
+    int rc = dmalloc(&h->d_resid, h->nobs);
+    if (rc) return rc;
+  }
+  const size_t lds = h->gcam ? 0 : (size_t)h->m * CAM_LDS * sizeof(double);
+  cam_tables(h, h->d_cam15[h->cur], nullptr);
+  const unsigned grid = (unsigned)std::min<long long>(4096, (h->nobs + 255) / 256);
+  hipLaunchKernelGGL(h->gcam ? k_residuals<true> : k_residuals<false>, dim3(grid), dim3(256), lds, h->stream, h->nobs, h->m,
+                     (const double *)h->d_cam15[h->cur], (const double *)h->d_X[h->cur], (const int *)h->d_obs_pt, (const int *)h->d_cam,
+                     (const double2 *)h->d_xy, h->f0, h->d_resid, (const double *)h->d_cam18);
+  MVBA_HIP(hipGetLastError());
+  MVBA_HIP(hipMemcpyAsync(e, h->d_resid, sizeof(double2) * h->nobs, hipMemcpyDeviceToHost, h->stream));
+  MVBA_HIP(hipStreamSynchronize(h->stream));
+  return MVBA_OK;
+}
+
 int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *cam_cov_full, double *timings_ms) {
   if (!h) return fail(MVBA_ERR_BADARG, "null handle");
+  if (h->loss != LOSS_SQUARED)
+    return fail(MVBA_ERR_BADARG, "mvba_covariance: the covariance is defined for the squared loss only (this engine has a robust loss)");
   if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
   MVBA_HIP(hipSetDevice(h->device));
   const int m = h->m, D = h->D, ld = h->ld, nt = (D + NB - 1) / NB;
@@ -4477,6 +4700,7 @@ int mvba_debug_read(mvba_handle *h, int32_t which, double *out, int64_t capacity
       cnt = h->schur_mode == SCHUR_SLOTS ? h->n_slot_items : (h->schur_mode == SCHUR_PAIRS ? h->n_items : 0);
       break;
     case MVBA_BUF_INDEX_SEG: cnt = h->schur_mode == SCHUR_SLOTS ? (long long)h->n_waves * h->slot_nseg : 0; break;
+    case MVBA_BUF_WEIGHT: cnt = h->nobs; break;
     default: return fail(MVBA_ERR_BADARG, "unknown buffer id");
   }
   *n = cnt;
@@ -4487,8 +4711,13 @@ int mvba_debug_read(mvba_handle *h, int32_t which, double *out, int64_t capacity
   if (which == MVBA_BUF_RESIDUAL || which == MVBA_BUF_JX || which == MVBA_BUF_JC) {
     std::vector<double> r((size_t)2 * REC * h->nobs);  // expand the records on the host
     MVBA_HIP(hipMemcpy(r.data(), h->d_rec, sizeof(double) * r.size(), hipMemcpyDeviceToHost));
-    const double cu = 1.0 / h->f0;
+    std::vector<double> sw;  // a robust loss: the implied (u, v) columns are sqrt(w) / f0, as the Schur kernels take them
+    if (h->loss != LOSS_SQUARED && which == MVBA_BUF_JC) {
+      sw.resize(h->nobs);
+      MVBA_HIP(hipMemcpy(sw.data(), h->d_sqw, sizeof(double) * sw.size(), hipMemcpyDeviceToHost));
+    }
     for (long long o = 0; o < h->nobs; ++o) {
+      const double cu = sw.empty() ? 1.0 / h->f0 : sw[o] / h->f0;
       const double *q = r.data() + (size_t)o * 2 * REC;  // slot s -> (q[2s], q[2s+1]) = (row0, row1)
       if (which == MVBA_BUF_RESIDUAL) {
         out[2 * o] = q[14]; out[2 * o + 1] = q[15];
@@ -4505,6 +4734,9 @@ int mvba_debug_read(mvba_handle *h, int32_t which, double *out, int64_t capacity
         }
       }
     }
+  } else if (which == MVBA_BUF_WEIGHT) {
+    if (h->loss != LOSS_SQUARED) MVBA_HIP(d2h(h->d_sqw, sizeof(double) * h->nobs));
+    else for (long long o = 0; o < h->nobs; ++o) out[o] = 1.0;
   } else if (which == MVBA_BUF_E || which == MVBA_BUF_DP) {
     std::vector<double> pl(9 * (size_t)h->N);
     MVBA_HIP(hipMemcpy(pl.data(), h->d_PL, sizeof(double) * pl.size(), hipMemcpyDeviceToHost));

@@ -147,6 +147,41 @@ __host__ __device__ __forceinline__ void obs_backsub(double X0, double X1, doubl
   y2 = sc * (R[6] * w0 + R[7] * w1 + R[8] * w2);
 }
 
+// Robust losses.  s = |e|^2 of an observation, b = (delta / f0)^2:
+//   squared  rho = s                                w = 1
+//   Huber    rho = s (s <= b), 2 sqrt(b s) - b        w = 1 (s <= b), sqrt(b / s)
+//   Cauchy   rho = b log1p(s / b)                    w = 1 / (1 + s / b)
+// with w = rho'(s), the IRLS weight of the observation's rows.  The kernels keep sqrt(w).
+enum { LOSS_SQUARED = 0, LOSS_HUBER = 1, LOSS_CAUCHY = 2 };
+template <int LOSS>
+__host__ __device__ __forceinline__ double loss_rho(double s, double b) {
+  if (LOSS == LOSS_HUBER) return s <= b ? s : 2.0 * sqrt(b * s) - b;
+  if (LOSS == LOSS_CAUCHY) return b * log1p(s / b);
+  return s;
+}
+template <int LOSS>
+__host__ __device__ __forceinline__ double loss_sqrt_w(double s, double b) {
+  if (LOSS == LOSS_HUBER) return s <= b ? 1.0 : sqrt(sqrt(b / s));
+  if (LOSS == LOSS_CAUCHY) return rsqrt(1.0 + s / b);
+  return 1.0;
+}
+
+// Residual only, in units of x / f0 (the residuals of mvba_residuals).
+__host__ __device__ __forceinline__ void obs_resid(double X0, double X1, double X2, const double *c, double x, double y,
+                                                   double f0, double &e0, double &e1) {
+  double cc[CAM_LDS];
+  load_row(c, cc);
+  c = cc;
+  const double d0 = X0 - c[3], d1 = X1 - c[4], d2 = X2 - c[5];
+  const double *R = c + 6;
+  const double c1 = R[0] * d0 + R[3] * d1 + R[6] * d2;
+  const double c2 = R[1] * d0 + R[4] * d1 + R[7] * d2;
+  const double c3 = R[2] * d0 + R[5] * d1 + R[8] * d2;
+  const double p = c[0] * c1 + c[1] * c3, q = c[0] * c2 + c[2] * c3, r = f0 * c3;
+  e0 = p / r - x / f0;
+  e1 = q / r - y / f0;
+}
+
 // Residual only (trial cost, ref :666-677).
 __host__ __device__ __forceinline__ double obs_cost(double X0, double X1, double X2, const double *c,
                                                     double x, double y, double f0) {

@@ -19,7 +19,26 @@ MVBA_OK, MVBA_ERR_BADARG, MVBA_ERR_SINGULAR, MVBA_ERR_HIP, MVBA_ERR_RCCL, MVBA_E
 
 KERNEL_IDS = ("resid_jac", "point_blocks", "point_inv", "schur", "allreduce", "solve", "backsub_cost", "cost")
 BUF = {"residual": 0, "JX": 1, "JC": 2, "E": 3, "dP": 4, "A_full": 5, "b_full": 6, "dxi": 7, "dX": 8,
-       "trial_X": 9, "trial_cam": 10, "index_k": 11, "index_l": 12, "index_a": 13, "index_seg": 14}
+       "trial_X": 9, "trial_cam": 10, "index_k": 11, "index_l": 12, "index_a": 13, "index_seg": 14, "weight": 15}
+LOSSES = {"squared": 0, "huber": 1, "cauchy": 2}  # mvba_create_robust's loss codes (MVBA_LOSS_*)
+
+
+def check_loss(loss, loss_scale):
+    """(loss code, scale) for mvba_create_robust; ValueError on a bad pair (before any library call).
+    ``loss_scale`` (delta, image units) is required for a robust loss and ignored for the squared one."""
+    if not isinstance(loss, str) or loss not in LOSSES:
+        raise ValueError(f"loss must be one of {sorted(LOSSES)}, got {loss!r}")
+    if loss == "squared":
+        return 0, 0.0
+    if loss_scale is None:
+        raise ValueError(f"loss={loss!r} needs loss_scale (delta in image units)")
+    try:
+        scale = float(loss_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"loss_scale must be a number, got {loss_scale!r}") from None
+    if not np.isfinite(scale) or scale <= 0.0:
+        raise ValueError(f"loss_scale must be finite and > 0, got {loss_scale!r}")
+    return LOSSES[loss], scale
 
 _dp = C.POINTER(C.c_double)
 
@@ -44,6 +63,7 @@ SIGNATURES = {
     "mvba_kernel_name": (C.c_char_p, [C.c_int32]),
     "mvba_device_count": (C.c_int, [C.POINTER(C.c_int32)]),
     "mvba_create": (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_void_p)]),
+    "mvba_create_robust": (C.c_int, [C.POINTER(Problem), C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
     "mvba_destroy": (None, [C.c_void_p]),
     "mvba_set_params": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp]),
     "mvba_get_params": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp]),
@@ -58,6 +78,7 @@ SIGNATURES = {
     "mvba_try_step": (C.c_int, [C.c_void_p, C.c_double, _dp]),
     "mvba_commit": (C.c_int, [C.c_void_p]),
     "mvba_covariance": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
+    "mvba_residuals": (C.c_int, [C.c_void_p, _dp]),
     "mvba_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
     "mvba_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "mvba_reset_stats": (C.c_int, [C.c_void_p]),
@@ -131,13 +152,17 @@ def device_count():
 
 class HipEngine:
     """Device-resident BA state + kernels.  Protocol (shared with the oracle's
-    engine): set_params / get_params / cost / linearize / try_step / commit."""
+    engine): set_params / get_params / cost / linearize / try_step / commit.
+    ``loss`` ("squared", "huber", "cauchy") and ``loss_scale`` (delta in image units) choose the robust loss, fixed
+    for the engine's life (include/mvba.h, mvba_create_robust)."""
 
-    def __init__(self, n_points, n_images, pt_ptr, cam_idx, xy, f0, axis, device=-1):
+    def __init__(self, n_points, n_images, pt_ptr, cam_idx, xy, f0, axis, device=-1, loss="squared", loss_scale=None):
         from .bundle_adjustment import AXES  # local import: avoid a cycle
 
         if axis not in AXES:
             raise ValueError()
+        loss_code, scale = check_loss(loss, loss_scale)
+        self.loss, self.loss_scale = loss, (scale if loss_code else None)
         self.lib = load_library()
         if device_count() < 1:
             raise RuntimeError("libmvba: no HIP device visible; the BA engine has no CPU fallback")
@@ -155,7 +180,10 @@ class HipEngine:
                        self._pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
                        self._cam.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(self._xy), float(f0), int(device), int(planes))
         h = C.c_void_p()
-        raise_for(self.lib.mvba_create(C.byref(prob), C.byref(h)), self.lib)
+        if loss_code or loss_scale is not None:  # (squared with a scale: through mvba_create_robust, which is mvba_create then)
+            raise_for(self.lib.mvba_create_robust(C.byref(prob), loss_code, scale, C.byref(h)), self.lib)
+        else:
+            raise_for(self.lib.mvba_create(C.byref(prob), C.byref(h)), self.lib)
         self._h = h
         self.n_solves = 0
 
@@ -244,6 +272,12 @@ class HipEngine:
         if Cf is not None:
             out["cameras_full"] = Cf
         return out
+
+    def residuals(self):
+        """(n_obs, 2) residuals f0 e_o in image units at the committed state, in the engine's observation order."""
+        e = np.empty((self.n_obs, 2))
+        raise_for(self.lib.mvba_residuals(self._h, _ptr(e)), self.lib)
+        return e
 
     # -- measurement / multi-GPU / test hooks
     def set_profiling(self, on):

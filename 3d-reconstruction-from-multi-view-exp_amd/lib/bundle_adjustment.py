@@ -20,6 +20,8 @@ from typing import Any
 import numpy as np
 import numpy.typing as npt
 
+from ._mvba import check_loss
+
 AXES = {"x-right_z-forward": 0, "x-up_z-forward": 1}
 
 
@@ -171,6 +173,19 @@ def lm_loop(engine, scale_factor, delta_tol, max_iter, on_state=None, verbose=Tr
     return E_
 
 
+def loss_weights(e_px, f0, loss, loss_scale):
+    """w = rho'(s) for residuals ``e_px`` (n, 2) in image units: s = |e / f0|^2, b = (loss_scale / f0)^2 (include/mvba.h)."""
+    code, scale = check_loss(loss, loss_scale)
+    e = np.asarray(e_px, np.float64).reshape(-1, 2) / f0
+    s = (e * e).sum(axis=1)
+    if code == 0:
+        return np.ones_like(s)
+    b = (scale / f0) ** 2
+    if code == 1:
+        return np.where(s <= b, 1.0, np.sqrt(b / np.maximum(s, b)))
+    return 1.0 / (1.0 + s / b)
+
+
 class BundleAdjuster:
     def __init__(
         self,
@@ -182,18 +197,27 @@ class BundleAdjuster:
         f0: float = 1.0,
         visibility_index: npt.NDArray | None = None,
         axis: str = "x-right_z-forward",
+        loss: str = "squared",
+        loss_scale: float | None = None,
     ):
+        """``loss``: "squared" (the reference's sum of squares), "huber" or "cauchy" -- a robust loss with scale
+        ``loss_scale`` (delta, in the units of ``x``: pixels), required for the robust ones."""
+        check_loss(loss, loss_scale)  # (ValueError before any work)
         x = np.asarray(x)
         pt_ptr, cam_idx, xy = dense_to_observations(x, visibility_index)
-        self._setup(x.shape[0], x.shape[1], pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis)
+        self._setup(x.shape[0], x.shape[1], pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, loss=loss,
+                    loss_scale=loss_scale)
 
     @classmethod
     def from_observations(cls, n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t,
-                          f0: float = 1.0, axis: str = "x-right_z-forward", **engine_kw):
+                          f0: float = 1.0, axis: str = "x-right_z-forward", loss: str = "squared",
+                          loss_scale: float | None = None, **engine_kw):
         """Extension for sizes where the dense (N,m,2) array cannot exist
-        (SURVEY 8f rank 1): observation list in CSR-by-point form."""
+        (SURVEY 8f rank 1): observation list in CSR-by-point form.  ``loss`` / ``loss_scale``: as for the constructor."""
+        check_loss(loss, loss_scale)
         self = cls.__new__(cls)
-        self._setup(n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, **engine_kw)
+        self._setup(n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, loss=loss,
+                    loss_scale=loss_scale, **engine_kw)
         return self
 
     # -- construction ------------------------------------------------------
@@ -202,7 +226,11 @@ class BundleAdjuster:
 
         return HipEngine(n_points, n_images, pt_ptr, cam_idx, xy, f0, axis, **kw)
 
-    def _setup(self, n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, **engine_kw):
+    def _setup(self, n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, loss="squared",
+               loss_scale=None, **engine_kw):
+        self._loss, self._loss_scale = loss, loss_scale
+        if loss != "squared":  # (the squared loss keeps the engine's plain constructor call)
+            engine_kw = dict(engine_kw, loss=loss, loss_scale=loss_scale)
         init_X, init_K = np.asarray(init_X, dtype=np.float64), np.asarray(init_K, dtype=np.float64)
         init_R, init_t = np.asarray(init_R, dtype=np.float64), np.asarray(init_t, dtype=np.float64)
         # camera-0 pose and baseline length for the way back (ref :23-33)
@@ -273,6 +301,8 @@ class BundleAdjuster:
         too few points)."""
         if scale not in ("unit", "residual") or frame not in ("input", "gauge"):
             raise ValueError("scale must be 'unit' or 'residual', frame 'input' or 'gauge'")
+        if self._loss != "squared":
+            raise NotImplementedError(f"covariance() is defined for the squared loss only (this adjuster uses loss={self._loss!r})")
         eng, cam0 = self._engine, self._init_camera0_params
         if scale == "residual":
             residual_variance(0.0, eng.n_obs, self._n_points, self._n_images)  # (no redundancy: ValueError before any work)
@@ -302,6 +332,17 @@ class BundleAdjuster:
                 if k in out:
                     out[k] = out[k] * s2
         return out
+
+    def residuals(self) -> npt.NDArray:
+        """(n_obs, 2) reprojection residuals in image units (projection minus observation) at the current estimate, in
+        the engine's observation order -- for the dense constructor the point-major order of dense_to_observations
+        (visible observations only).  The same in either frame."""
+        return self._engine.residuals()
+
+    def weights(self) -> npt.NDArray:
+        """(n_obs,) IRLS weights w_o = rho'(|e_o|^2) of the loss at the current estimate (1 for the squared loss):
+        below 1 where the robust loss discounts an observation, e.g. ``weights() > 0.5`` as an inlier mask."""
+        return loss_weights(self.residuals(), self._f0, self._loss, self._loss_scale)
 
     def _fetch_log(self):
         """Device-resident log entries -> host dicts (in order), device log emptied."""

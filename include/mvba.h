@@ -83,6 +83,17 @@ int mvba_device_count(int32_t *count);
 
 /* Copies the observation list to the device and builds the camera-major index. */
 int mvba_create(const mvba_problem *problem, mvba_handle **out);
+/* The same with a robust loss, fixed for the engine's life.  loss: MVBA_LOSS_*; scale: delta > 0 in image units (pixels).
+ * With s = |e|^2 (e in units of x / f0) and b = (delta / f0)^2 the cost is E = sum rho(s):
+ *   squared rho = s;  Huber rho = s (s <= b), 2 sqrt(b s) - b;  Cauchy rho = b log1p(s / b).
+ * The linearisation is IRLS: every row of an observation is scaled by sqrt(w), w = rho'(s) at the linearisation point.
+ * MVBA_LOSS_SQUARED behaves exactly as mvba_create (scale is ignored).  A robust engine never takes the slot form of K3
+ * (the unit form instead) and has no covariance (mvba_covariance: MVBA_ERR_BADARG).  MVBA_ERR_BADARG: an unknown loss,
+ * or a scale that is not finite and > 0. */
+#define MVBA_LOSS_SQUARED 0
+#define MVBA_LOSS_HUBER 1
+#define MVBA_LOSS_CAUCHY 2
+int mvba_create_robust(const mvba_problem *problem, int32_t loss, double scale, mvba_handle **out);
 void mvba_destroy(mvba_handle *h);
 
 /* Committed state, normalised frame: X [n_points][3], f [m], u [m][2], t [m][3],
@@ -116,6 +127,10 @@ int mvba_commit(mvba_handle *h);
  * the undamped reduced camera system, or a numerically singular point block E_a (a Cholesky pivot below 1e-12 of its largest
  * diagonal entry: a point seen once).  Sharded: every rank gets its own points' blocks and the same camera blocks.        */
 int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *cam_cov_full, double *timings_ms);
+
+/* e [n_obs][2]: f0 e_o, the residual of every observation in image units at the COMMITTED state, in the engine's
+ * observation order (this rank's observations when sharded).  Independent of the loss. */
+int mvba_residuals(mvba_handle *h, double *e);
 
 /* The debug log of the reference's optimize(is_debug=True) (ref :89-98, :175-183: a copy of X, R, t per outer
  * iteration, normalised frame; read back by get_log(), :204-206).  mvba_snapshot appends the COMMITTED state to
@@ -178,8 +193,11 @@ enum {
   MVBA_BUF_INDEX_K,      /* the Schur index as the kernel reads it: k-side observation of every item row */
   MVBA_BUF_INDEX_L,      /*   l-side observation                                                          */
   MVBA_BUF_INDEX_A,      /*   point (slot form: step-major rows incl. padding; unit form: pair-major)      */
-  MVBA_BUF_INDEX_SEG     /*   slot form: pacing table [waves][segments]                                   */
+  MVBA_BUF_INDEX_SEG,    /*   slot form: pacing table [waves][segments]                                   */
+  MVBA_BUF_WEIGHT        /* [n_obs] sqrt(w_o) of the last linearisation (robust loss; 1 for the squared loss)   */
 };
+/* (robust loss: RESIDUAL, JX and JC are the rows as K3 sees them -- scaled by sqrt(w_o), the implied (u, v) columns
+ * of JC sqrt(w_o) / f0) */
 int mvba_debug_read(mvba_handle *h, int32_t which, double *out, int64_t capacity, int64_t *n);
 
 /* Pinhole projection of an observation list on the device: xy[o] = inhomogeneous
