@@ -2198,6 +2198,7 @@ struct mvsvd_handle {
   int depth_group = 0;                // mvsvd_depth_begin: columns per image (3); 0 = no depth loop started
   bool cs_valid = false;              // fused depth iteration: the per-image scales of norm 2 belong to the depths in dz
   double *ddep = nullptr;             // depth iteration: error partials, 12 x 12 problems, vectors (one allocation)
+  size_t ddep_n = 0;                  // ... its size in doubles
   int *ddflag = nullptr;
   int chunks = 1, rank_cap = 0;
   // wide path (n > WIDE_MIN): bases Q, Z [n][WB], products B, B2 [max_rows][WB] (dBw / dB2), row-chunk partials of Z, small problems
@@ -2562,6 +2563,21 @@ constexpr size_t DEPTH_LDS_MAX = 148 * 1024;  // dynamic LDS the depth kernels m
 // rows k_dual_gram stages per pass: [rows][3 m | 1] normalised observations + [rows][4] right singular vectors in LDS
 inline int dual_gram_rows(int m) { return (int)std::max<size_t>(1, std::min<size_t>(DG_ROWS_MAX, DEPTH_LDS_MAX / (sizeof(double) * (size_t)(((3 * m) | 1) + 4)))); }
 
+// The depth iteration's scratch (ddep) of at least `need` doubles.  The two routes lay it out differently and one handle may take
+// both (a new base on the other side of the fused route's row threshold, MVSVD_DEPTH_UNFUSED read per call): it grows to the larger.
+int depth_scratch(mvsvd_handle *h, size_t need) {
+  if (h->ddep_n >= need) return MVBA_OK;
+  if (h->ddep) {
+    MVBA_HIP(hipStreamSynchronize(h->st));
+    MVBA_HIP(hipFree(h->ddep));
+    h->ddep = nullptr;
+    h->ddep_n = 0;
+  }
+  MVBA_HIP(hipMalloc((void **)&h->ddep, sizeof(double) * need));
+  h->ddep_n = need;
+  return MVBA_OK;
+}
+
 template <typename T>
 int depth_step(mvsvd_handle *h, int method, double f0, double *E, double *timings) {
   const int n = h->n, m = n / 3;
@@ -2577,7 +2593,7 @@ int depth_step(mvsvd_handle *h, int method, double f0, double *E, double *timing
   const long long rpb = (rows + dual_blocks - 1) / dual_blocks;
   const int gblocks = (int)((rows + rpb - 1) / rpb);
   const size_t need = (size_t)DEPTH_BLOCKS + 8 + (size_t)m * (144 + 144 + 12 + 12) + (size_t)dual_blocks * dsplit * 14 * m * 6;
-  if (!h->ddep) MVBA_HIP(hipMalloc((void **)&h->ddep, sizeof(double) * need));  // (m is the handle's: `need` never changes)
+  if ((rc = depth_scratch(h, need))) return rc;
   if (!h->ddflag) MVBA_HIP(hipMalloc((void **)&h->ddflag, sizeof(int) * (size_t)(m + 1)));
   double *Epart = h->ddep, *Eout = Epart + DEPTH_BLOCKS, *G12 = Eout + 8, *V12 = G12 + (size_t)m * 144, *colsum = V12 + (size_t)m * 144,
          *w12 = colsum + (size_t)m * 12, *gpart = w12 + (size_t)m * 12;
@@ -2637,13 +2653,7 @@ template <int M, int NORM>
 void launch_gram_xz(mvsvd_handle *h, bool rot, int chunks, const double *cs) {
   constexpr int n = 3 * M, m = M, MODE = n <= 16 ? 1 : (n <= 24 ? 2 : 3);
   constexpr int NP = MODE == 1 ? 1 : (MODE == 2 ? 2 : 3);
-  const size_t lds = std::max<size_t>(sizeof(double) * (size_t)GRAM_ROWS * ((rot ? 2 : 1) * n + 2 * m), (size_t)NP * 8192);
-  static bool attr_set = false;
-  if (!attr_set) {  // (the refinement form of 10 images stages 80 KiB)
-    hipFuncSetAttribute((const void *)k_gram_xz<M, NORM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEPTH_LDS_MAX);
-    hipFuncSetAttribute((const void *)k_gram_xz<M, NORM, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEPTH_LDS_MAX);
-    attr_set = true;
-  }
+  const size_t lds = std::max<size_t>(sizeof(double) * (size_t)GRAM_ROWS * ((rot ? 2 : 1) * n + 2 * m), (size_t)NP * 8192);  // (LDS limit: mvsvd_create)
   if (rot)
     hipLaunchKernelGGL((k_gram_xz<M, NORM, true>), dim3(1, chunks), dim3(256), lds, h->st, (const double *)h->dX, (const double *)h->dz, h->base_rows, n, m, cs,
                        (const double *)h->dV1, h->dpart);
@@ -2681,7 +2691,7 @@ int depth_step_fused(mvsvd_handle *h, int method, double f0, double *E, double *
   double *cs = h->dgs + (size_t)GS_BLOCKS * gs_stride;
   const size_t dual_part = (size_t)512 * 4 * m * 256;  // k_dual_gram_mfma: a 16 x 16 tile per wave and image, at most 512 workgroups
   const size_t need = (size_t)DEPTH_BLOCKS + 8 + (size_t)m * (144 + 144 + 12 + 12) + dual_part + (size_t)FZ_MAXM * DEPTH_BLOCKS;
-  if (!h->ddep) MVBA_HIP(hipMalloc((void **)&h->ddep, sizeof(double) * need));  // (the fused path is chosen per handle: `need` never changes)
+  if (int rc = depth_scratch(h, need)) return rc;
   if (!h->ddflag) MVBA_HIP(hipMalloc((void **)&h->ddflag, sizeof(int) * (size_t)(m + 1)));
   double *Epart = h->ddep, *Eout = Epart + DEPTH_BLOCKS, *G12 = Eout + 8, *V12 = G12 + (size_t)m * 144, *colsum = V12 + (size_t)m * 144,
          *w12 = colsum + (size_t)m * 12, *gpart = w12 + (size_t)m * 12, *gsum = gpart + dual_part;
@@ -2828,7 +2838,11 @@ int mvsvd_create(int64_t max_rows, int32_t n_cols, int32_t dtype, int32_t device
                         (const void *)k_dual_gram<float>, (const void *)k_dual_gram<double>, (const void *)k_primary_xz, (const void *)k_dual_gram_mfma<2>, (const void *)k_dual_gram_mfma<4>, (const void *)k_dual_gram_mfma<6>, (const void *)k_dual_gram_mfma<8>,
                         (const void *)k_dual_gram_mfma<10>,
                         (const void *)k_dual_apply_xz, (const void *)k_depth_primary_wide<float>, (const void *)k_depth_primary_wide<double>,
-                        (const void *)k_dual_apply_wide<float>, (const void *)k_dual_apply_wide<double>})
+                        (const void *)k_dual_apply_wide<float>, (const void *)k_dual_apply_wide<double>,
+                        // k_gram_xz of the fused depth iteration, every image count and norm (the refinement form of 10 images stages 80 KiB)
+#define GRAM_XZ_M(M) (const void *)k_gram_xz<M, 1, false>, (const void *)k_gram_xz<M, 1, true>, (const void *)k_gram_xz<M, 2, false>, (const void *)k_gram_xz<M, 2, true>
+                        GRAM_XZ_M(2), GRAM_XZ_M(4), GRAM_XZ_M(6), GRAM_XZ_M(8), GRAM_XZ_M(10)})
+#undef GRAM_XZ_M
     SVD_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEPTH_LDS_MAX));
 #undef SVD_TRY
   *out = h;
@@ -2920,6 +2934,8 @@ int mvsvd_load_base(mvsvd_handle *h, const void *X, int64_t n_rows) {
   MVBA_HIP(hipStreamSynchronize(h->st));
   h->base_rows = n_rows;
   h->base_loaded = true;
+  h->depth_group = 0;  // a new base ends a depth loop: its depths and norm-2 scales belong to the old one
+  h->cs_valid = false;
   h->wide_warm = h->wide_have_q = false;
   h->loaded = false;  // dW holds nothing derived from this base yet
   return MVBA_OK;
@@ -2949,6 +2965,8 @@ int mvsvd_load_base_images(mvsvd_handle *h, const double *const *xy, int32_t n_i
   MVBA_HIP(hipStreamSynchronize(h->st));
   h->base_rows = n_rows;
   h->base_loaded = true;
+  h->depth_group = 0;  // (as mvsvd_load_base)
+  h->cs_valid = false;
   h->wide_warm = h->wide_have_q = false;
   h->loaded = false;  // dW was the staging buffer
   return MVBA_OK;
@@ -3007,6 +3025,7 @@ int mvsvd_depth_step(mvsvd_handle *h, int32_t method, double f0, double *E, doub
   if (h->n < 6) return fail(MVBA_ERR_BADARG, "the rank-4 depth iteration needs at least 2 images (3 m >= 4 columns, as the reference's)");
   MVBA_HIP(hipSetDevice(h->device));
   if (fused_depth_ok(h)) return depth_step_fused(h, method, f0, E, timings_ms);
+  h->cs_valid = false;  // (the unfused route moves the depths without the fused route's norm-2 scales)
   return h->dtype == 0 ? depth_step<float>(h, method, f0, E, timings_ms) : depth_step<double>(h, method, f0, E, timings_ms);
 }
 

@@ -280,6 +280,7 @@ int mvsvd_run_scaled(mvsvd_handle *h, const void *z, int32_t group, int32_t norm
  * z <- xi / |x| (:124 / :220) and the reprojection error of :43-58 into *E.  Per iteration 8 bytes cross PCIe.
  * mvsvd_depth_begin (after mvsvd_load_base; group must be 3: homogeneous image coordinates, n_cols = 3 m) sets
  * z = 1 (:75 / :160); mvsvd_depth_read downloads the depths [n_rows][m] (the workspace's dtype), once, at the end.
+ * A new base (mvsvd_load_base / _images) ends the loop: step, read and run_scaled(z = NULL) give MVBA_ERR_STATE until depth_begin.
  * timings_ms (may be NULL) [6] as in mvsvd_run, except slot 0: device ms of the depth-update kernels.
  * MVBA_ERR_SINGULAR: the re-weighted matrix has rank < 4. */
 int mvsvd_depth_begin(mvsvd_handle *h, int32_t group);

@@ -9,6 +9,7 @@ import pytest
 
 from lib import _mvba
 from lib.factorization import factorization_method
+from oracle.depth_oracle import HostDepthLoop
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -675,3 +676,215 @@ def test_depth_iteration_at_a_million_points_properties(method):
     Es2, zs2 = run(2)  # (iv)
     assert Es2 == Es[:2]
     np.testing.assert_array_equal(zs2[2], zs[2])
+
+
+# ---------------------------------------------------------------- the fused depth iteration (fp64, even m <= 10, >= 256 points)
+def _scene_x(n_points, m):
+    from lib.perspective_camera_calibration import _create_data_matrix
+    from lib.synthetic import make_scene
+
+    xd, _vis = make_scene(n_points, m, vis_p=1.0).dense()
+    return _create_data_matrix([xd[:, k, :] for k in range(m)], 1.0)
+
+
+def _steps_vs_oracle(ws, g, methods, fused, f0=1.0, z_rel=None):
+    """Step the device loop and the oracle in the same order: E to 1e-9 relative, depths to 1e-9 (and, with `z_rel`, to z_rel of
+    the largest oracle depth); `fused`: the route the step must have taken (the fused one leaves project_ms at exactly 0)."""
+    for method in methods:
+        E, tm = ws.depth_step(method, f0)
+        Eo = g.step(method, f0)
+        assert E == pytest.approx(Eo, rel=1e-9, abs=1e-14)
+        z, zo = ws.depth_read(), g.depths()
+        np.testing.assert_allclose(z, zo, rtol=0, atol=1e-9)
+        if z_rel is not None:
+            assert np.abs(z - zo).max() <= z_rel * np.abs(zo).max()
+        assert (tm["project_ms"] == 0.0) == fused, tm
+
+
+@pytest.mark.parametrize("n_points,m,method", [(1500, m, method) for m in (2, 4, 6, 8, 10) for method in (1, 2)]
+                         + [(rows, m, method) for rows in (256, 257) for m in (2, 10) for method in (1, 2)]
+                         + [(255, 10, 1), (255, 10, 2)])
+def test_fused_depth_iteration_every_image_count_vs_oracle(n_points, m, method):
+    """Every instantiation of the fused route (k_gram_xz<M, NORM, rot> with its Gram MODE 1 / 2 / 3 from n = 3 m, k_dual_gram_mfma<M>,
+    k_primary_xz and k_dual_apply_xz sized from m) against oracle/depth_oracle.py per step, 1e-9: m = 2 ... 10 (10 is the dispatch's
+    `default:` case and the only one that needs the raised LDS limit: 80 KiB in the refinement pass), at 1500 points and at the
+    route's threshold -- 256 points, and 257: one row in the last 128-row step and one lane in the last 64-row wave tile.  255 points
+    of 10 images: the unfused side of the threshold."""
+    x = _scene_x(n_points, m)
+    g = HostDepthLoop(x)
+    ws = _mvba.SvdWorkspace(n_points, 3 * m, np.float64)
+    ws.load_base(x.reshape(n_points, 3 * m))
+    ws.depth_begin(3)
+    _steps_vs_oracle(ws, g, [method] * 3, fused=n_points >= 256)
+    ws.close()
+
+
+def _arc_scene(n, m, seed=5):
+    """Points in a unit cube seen by m cameras on an arc of radius 5 (as the million-point test's scene): (n, m, 3) homogeneous."""
+    rng = np.random.default_rng(seed)
+    X = rng.uniform(-1, 1, (n, 3))
+    x = np.empty((n, m, 3))
+    for k in range(m):
+        ph = 0.12 * k - 0.4
+        c = 5.0 * np.array([np.sin(ph), 0.0, -np.cos(ph)])
+        R = np.array([[np.cos(ph), 0, -np.sin(ph)], [0, 1, 0], [np.sin(ph), 0, np.cos(ph)]])
+        Xc = (X - c) @ R
+        x[:, k, 0], x[:, k, 1], x[:, k, 2] = Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2], 1.0
+    return x
+
+
+@pytest.mark.parametrize("method", [1, 2])
+def test_fused_depth_iteration_past_every_loop_threshold_vs_oracle(method):
+    """530,001 points x 10 images against the oracle, two steps: past 65,536 rows (k_dual_gram_mfma's 512 workgroups take more than
+    one 128-row step each), 262,144 (k_gram_xz's 2048 chunks likewise) and 524,288 (the 2048 x 256-row grid of k_primary_xz,
+    k_dual_apply_xz and k_depth_error loops), ending inside a tile.  The dual scheme's depths are per-image unit vectors over all
+    points (~1 / sqrt(N) in size), so there they are also held to 1e-9 of the largest depth."""
+    n, m = 530_001, 10
+    x = _arc_scene(n, m)
+    g = HostDepthLoop(x)
+    ws = _mvba.SvdWorkspace(n, 3 * m, np.float64)
+    ws.load_base(np.ascontiguousarray(x.reshape(n, 3 * m)))
+    ws.depth_begin(3)
+    _steps_vs_oracle(ws, g, [method] * 2, fused=True, z_rel=1e-9 if method == 2 else None)
+    ws.close()
+
+
+def test_fused_depth_iteration_method_order_vs_oracle():
+    """primary -> dual -> dual -> primary -> dual on one fused workspace (8 images), the oracle stepping in the same order: the
+    norm-2 scales are computed on the first dual step, carried from k_dual_apply_xz into the next dual step, dropped by a primary
+    step and computed again."""
+    x = _scene_x(2000, 8)
+    g = HostDepthLoop(x)
+    ws = _mvba.SvdWorkspace(2000, 24, np.float64)
+    ws.load_base(x.reshape(2000, 24))
+    ws.depth_begin(3)
+    _steps_vs_oracle(ws, g, [1, 2, 2, 1, 2], fused=True)
+    ws.close()
+
+
+@pytest.mark.parametrize("m,method", [(4, 1), (4, 2), (10, 1), (10, 2)])
+def test_fused_depth_iteration_equals_the_unfused_one(m, method, monkeypatch):
+    """MVSVD_DEPTH_UNFUSED=1 (read per call) takes the iteration that writes the re-weighted matrix: the same three steps agree with
+    the fused route to 1e-12."""
+    n = 1500
+    x = _scene_x(n, m).reshape(n, 3 * m)
+
+    def run():
+        ws = _mvba.SvdWorkspace(n, 3 * m, np.float64)
+        ws.load_base(x)
+        ws.depth_begin(3)
+        Es, zs = [], []
+        for _ in range(3):
+            E, tm = ws.depth_step(method, 1.0)
+            Es.append((E, tm["project_ms"]))
+            zs.append(ws.depth_read())
+        ws.close()
+        return Es, zs
+
+    Ef, zf = run()
+    monkeypatch.setenv("MVSVD_DEPTH_UNFUSED", "1")
+    Eu, zu = run()
+    for (ef, pf), (eu, pu), a, b in zip(Ef, Eu, zf, zu):
+        assert pf == 0.0 and pu > 0.0  # (the two routes did run)
+        assert eu == pytest.approx(ef, rel=1e-12)
+        np.testing.assert_allclose(b, a, rtol=0, atol=1e-12)
+
+
+def test_route_switch_inside_one_loop_vs_oracle(monkeypatch):
+    """One workspace, one loop, the route switched between steps by MVSVD_DEPTH_UNFUSED: the two routes lay out their scratch
+    differently (the unfused one needs more at 10 images) and only the fused one keeps the next dual step's norm-2 scales."""
+    n, m = 1500, 10
+    x = _scene_x(n, m)
+    g = HostDepthLoop(x)
+    ws = _mvba.SvdWorkspace(n, 3 * m, np.float64)
+    ws.load_base(x.reshape(n, 3 * m))
+    ws.depth_begin(3)
+    _steps_vs_oracle(ws, g, [2], fused=True)
+    monkeypatch.setenv("MVSVD_DEPTH_UNFUSED", "1")
+    _steps_vs_oracle(ws, g, [2, 1], fused=False)
+    monkeypatch.delenv("MVSVD_DEPTH_UNFUSED")
+    _steps_vs_oracle(ws, g, [2, 2], fused=True)
+    ws.close()
+
+
+@pytest.mark.parametrize("method", ["primary", "dual"])
+def test_reference_default_image_count_end_to_end(method, capsys):
+    """10 images (the reference's default scene) of 2000 points through the product's loop functions, device loop against
+    loop=HostDepthLoop(x): the printed errors of 8 forced iterations (tolerance 0) and the final depths; then the factorisation
+    perspective_self_calibration runs after the loop (`_DeviceDepthLoop.factorize(4)`: run_scaled(None, 3, 0, 4) on the fused
+    workspace, base assembled from the images) against numpy_svd4 of x o z_oracle."""
+    import re
+
+    from lib import perspective_camera_calibration as P
+    from lib.synthetic import make_scene
+    from oracle.depth_oracle import numpy_svd4
+
+    n, m, iters = 2000, 10, 8
+    xd, _vis = make_scene(n, m, vis_p=1.0).dense()
+    x_list = [np.ascontiguousarray(xd[:, k, :]) for k in range(m)]
+    x = P._create_data_matrix(x_list, 1.0)
+    fn = P._compute_projective_depth_primary_method if method == "primary" else P._compute_projective_depth_dual_method
+    capsys.readouterr()
+
+    def printed():
+        return [float(v) for v in re.findall(r"reprojection_error = (\S+)", capsys.readouterr().out)]
+
+    z = fn(x, 1.0, 0.0, max_iter=iters)
+    E = printed()
+    zo = fn(x, 1.0, 0.0, max_iter=iters, loop=HostDepthLoop(x))
+    Eo = printed()
+    assert len(E) == len(Eo) == iters
+    assert E == pytest.approx(Eo, rel=1e-9)
+    np.testing.assert_allclose(z, zo, rtol=0, atol=1e-9)
+    loop = P._DeviceDepthLoop.from_images(x_list, 1.0)
+    try:
+        P._depth_iterations(x, 1.0, 0.0, iters, 1 if method == "primary" else 2, loop, close=False)
+        M, S = loop.factorize(4)
+        np.testing.assert_allclose(loop.depths(), zo, rtol=0, atol=1e-9)
+    finally:
+        loop.close()
+    capsys.readouterr()
+    M_ref, sig_ref, S_ref = numpy_svd4(np.ascontiguousarray((x * zo[..., None]).reshape(n, 3 * m)))
+    sg = np.sign(np.sum(M * M_ref, axis=0))
+    np.testing.assert_allclose(np.linalg.norm(S, axis=1), sig_ref[:4], rtol=1e-8)
+    np.testing.assert_allclose(M * sg, M_ref, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(S * sg[:, None], S_ref, rtol=0, atol=1e-8 * np.abs(S_ref).max())
+
+
+@pytest.mark.parametrize("loader", ["load_base", "load_base_images"])
+def test_a_new_base_ends_the_depth_loop(loader):
+    """load_base(A), depth_begin, a dual step, then a new base B with MORE rows: the loop's depths (and norm-2 scales) belong to A --
+    B's rows past A's count were never written -- so depth_step, depth_read and run_scaled(None, ...) are refused until depth_begin;
+    after it, B's steps and final factorisation are bitwise those of a fresh workspace on B."""
+    m, na, nb = 8, 1000, 1500
+    xa, xb = _scene_x(nb, m)[:na].copy(), _arc_scene(nb, m)
+
+    def load(ws, x):
+        if loader == "load_base":
+            ws.load_base(x.reshape(len(x), 3 * m))
+        else:  # (x, y) of the image arrays with f0 = 1: the same base
+            ws.load_base_images([np.ascontiguousarray(x[:, k, :2]) for k in range(m)], 1.0)
+
+    ws = _mvba.SvdWorkspace(nb, 3 * m, np.float64)
+    load(ws, xa)
+    ws.depth_begin(3)
+    ws.depth_step(2, 1.0)
+    load(ws, xb)
+    with pytest.raises(RuntimeError):
+        ws.depth_step(1, 1.0)
+    with pytest.raises(RuntimeError):
+        ws.depth_read()
+    with pytest.raises(RuntimeError):
+        ws.run_scaled(None, 3, 0, 4)
+    fresh = _mvba.SvdWorkspace(nb, 3 * m, np.float64)
+    load(fresh, xb)
+    out = []
+    for w in (ws, fresh):
+        w.depth_begin(3)
+        Es = [w.depth_step(method, 1.0)[0] for method in (2, 2, 1)]
+        out.append((Es, w.depth_read(), w.run_scaled(None, 3, 0, 4)[:3]))
+        w.close()
+    (Ea, za, fa), (Eb, zb, fb) = out
+    assert Ea == Eb
+    assert np.array_equal(za, zb)
+    assert all(np.array_equal(u, v) for u, v in zip(fa, fb))
