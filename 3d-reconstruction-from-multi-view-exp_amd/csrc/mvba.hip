@@ -2883,6 +2883,7 @@ __global__ void k_idx_interleave(long long n_steps, const int *__restrict__ st_k
 }
 
 #include "mvba_cov.h"  // marginal covariances (mvba_covariance): S^-1 from the Cholesky factor and the point pass
+#include "mvba_map.h"  // parameter maps (mvba_set_parameter_map): the mapped gather into K4 and the way back
 
 }  // namespace
 
@@ -2976,6 +2977,19 @@ struct mvba_handle {
   double loss_b = 0.0;
   double *d_sqw = nullptr;
   double2 *d_resid = nullptr;  // mvba_residuals, allocated on the first call
+  // parameter map (mvba_set_parameter_map); mapped == false: the default map, none of this is touched.
+  // n_free unknowns, the first map_U of them untied; col / CSR transpose on the device (allocated on the first map), the
+  // scratch vector the back-substitution scatters x into, the scratch camera-block table of a mapped mvba_covariance
+  bool mapped = false;
+  int n_free = 0, map_ld = 0, map_U = 0;
+  std::vector<int> map_col, map_ptr, map_mem;
+  int *d_map_col = nullptr, *d_map_ptr = nullptr, *d_map_mem = nullptr;
+  double *d_map_x = nullptr, *d_cov_sigv = nullptr;
+  int2 *d_map_pairs = nullptr;  // the (i, j <= i) pairs of tied unknowns, n_map_pairs of them; map_nblk partial sums per pair
+  double *d_map_part = nullptr;
+  int n_map_pairs = 0, map_nblk = 1;
+  int solve_D() const { return mapped ? n_free : D; }     // order and row stride of the system K4 solves
+  int solve_ld() const { return mapped ? map_ld : ld; }
 };
 
 namespace {
@@ -3980,7 +3994,8 @@ void mvba_destroy(mvba_handle *h) {
                   h->d_dxi, h->d_dX, h->d_partials, h->d_cost, h->d_flag, h->d_allcost, h->d_it_k, h->d_it_l, h->d_it_a,
                   h->d_units, h->d_unit_ptr, h->d_q_ptr, h->d_q_units, h->d_partial, h->d_dense_part, h->d_dense_obs, h->d_sim, h->d_bar, h->d_wdesc,
                   h->d_wunits, h->d_seg_end, h->d_prog, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10,
-                  h->d_cov_sig, h->d_cov_panel, h->d_cov_pts, h->d_cov_cam, h->d_sqw, h->d_resid};
+                  h->d_cov_sig, h->d_cov_panel, h->d_cov_pts, h->d_cov_cam, h->d_sqw, h->d_resid,
+                  h->d_map_col, h->d_map_ptr, h->d_map_mem, h->d_map_x, h->d_cov_sigv, h->d_map_pairs, h->d_map_part};
   for (void *q : ptrs) if (q) hipFree(q);
   for (double *q : h->snap_slabs) hipFree(q);
   if (h->h_cost) hipHostFree(h->h_cost);
@@ -4174,11 +4189,29 @@ int allreduce_Ab(mvba_handle *h, bool timed) {  // C1: [A|b] summed over the ran
   return MVBA_OK;
 }
 
+// tied x tied entries of the mapped system into M (row stride ld; mirror: both triangles of the LU rescue's full matrix)
+void launch_map_tied(mvba_handle *h, double *M, int ld, int mirror) {
+  if (!h->n_map_pairs) return;
+  hipLaunchKernelGGL(k_map_tied, dim3(h->n_map_pairs, h->map_nblk), dim3(256), 0, h->stream, h->m, (const double *)h->d_Ab,
+                     (const int *)h->d_map_ptr, (const int *)h->d_map_mem, (const int2 *)h->d_map_pairs, h->d_map_part);
+  hipLaunchKernelGGL(k_map_tied_finish, dim3((h->n_map_pairs + 255) / 256), dim3(256), 0, h->stream, h->n_map_pairs, h->map_nblk, ld,
+                     mirror, (const int2 *)h->d_map_pairs, (const double *)h->d_map_part, M);
+}
+
 void launch_factor(mvba_handle *h) {  // K4 without the back-substitution: gauge strip into d_Ared, blocked Cholesky of [A|b]
-  const int m = h->m, D = h->D;
+  const int m = h->m, D = h->solve_D();
   double *d_A = h->d_Ab, *d_b = h->d_Ab + strip_offset(m, m);
-  const int ld = h->ld;
+  const int ld = h->solve_ld();
   const int ntc = (D + NB - 1) / NB;
+  if (h->mapped) {  // the mapped gather (mvba_map.h): the untied corner tile by tile, then the rows from the first tied unknown on
+    const int U = h->map_U, ntu = (U + NB - 1) / NB;
+    hipLaunchKernelGGL(k_map_compact, dim3(ntu * (ntu + 1) / 2 + (D + 255) / 256), dim3(256), 0, h->stream, D, ld, m, U, ntu, d_A, d_b,
+                       h->d_map_ptr, h->d_map_mem, h->d_Ared, h->d_bar, 1 + 4 * ((D + SBW - 1) / SBW));
+    if (U < D)
+      hipLaunchKernelGGL(k_map_rows, dim3((D + 63) / 64, D - U), dim3(256), 0, h->stream, D, ld, m, U, d_A, h->d_map_ptr, h->d_map_mem,
+                         h->d_Ared);
+    launch_map_tied(h, h->d_Ared, ld, 0);
+  } else
   hipLaunchKernelGGL(k_compact, dim3(ntc * (ntc + 1) / 2 + (D + 255) / 256), dim3(256), 0, h->stream, D, ld, m, h->gauge_axis, ntc, d_A, d_b,
                      h->d_Ared, h->d_bar, 1 + 4 * ((D + SBW - 1) / SBW));
   for (int jS = 0; jS < D; jS += SBW) {
@@ -4214,10 +4247,18 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
   if (!h || !E_trial) return fail(MVBA_ERR_BADARG, "null argument");
   if (!h->linearized) return fail(MVBA_ERR_STATE, "try_step before linearize");
   MVBA_HIP(hipSetDevice(h->device));
-  const int m = h->m, D = h->D;
+  const int m = h->m, D = h->solve_D();
   const size_t n9 = 9 * (size_t)m;
   const size_t nA = strip_offset(m, m);  // packed upper block triangle
   double *d_A = h->d_Ab, *d_b = h->d_Ab + nA;
+  // With a parameter map the solve kernels run on the D' x D' mapped system and scatter x (through keep_index, as ever) into a
+  // scratch vector; k_map_expand then writes dxi = P x.  D' = 0 (everything held): dxi = 0, no solve.
+  double *d_x = h->mapped ? h->d_map_x : h->d_dxi;
+  auto launch_expand = [&]() {
+    if (h->mapped && D > 0)
+      hipLaunchKernelGGL(k_map_expand, dim3((unsigned)((n9 + 255) / 256)), dim3(256), 0, h->stream, (int)n9, h->gauge_axis, h->d_map_col,
+                         h->d_map_x, h->d_dxi);
+  };
   {
     Timed t(h, MVBA_K_POINT_INV);
     launch_point_inv(h, c);
@@ -4233,22 +4274,27 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
   }
   auto launch_solve = [&](bool onepass) {  // K4: gauge strip, blocked Cholesky, back-substitution
     Timed t(h, MVBA_K_SOLVE);
+    if (D == 0) {  // (only with a map)
+      hipMemsetAsync(h->d_dxi, 0, sizeof(double) * n9, h->stream);
+      return;
+    }
     launch_factor(h);
-    const int ld = h->ld;
+    const int ld = h->solve_ld();
     const int S = (D + SBW - 1) / SBW;
     if (onepass && (S == 1 || S < h->n_cu)) {  // one persistent pass for L^T x = y (see k_chol_backsolve_all)
       // (point to point, nobody pays for anybody else: one bulk workgroup per column group)
       const int ngrp = ((S - 1) * SBW + 31) / 32, nbulk = S > 1 ? std::max(1, std::min(h->n_cu - S, ngrp)) : 0;
       hipLaunchKernelGGL(k_chol_backsolve_all<true>, dim3(S + nbulk), dim3(SUPER_THREADS),
-                         BACKSOLVE_LDS, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles, h->d_Lblk, h->d_dxi, h->d_flag,
+                         BACKSOLVE_LDS, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles, h->d_Lblk, d_x, h->d_flag,
                          h->d_bar, h->barrier_polls);
     } else
     for (int jS = ((D - 1) / SBW) * SBW; jS >= 0; jS -= SBW) {
       const int jE = std::min(jS + SBW, D), jE2 = std::min(jE + SBW, D);
       const int nwg = (jE == D) ? 1 : 1 + (jS + 255) / 256;
       hipLaunchKernelGGL(k_chol_backsolve, dim3(nwg), dim3(256), 0, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles,
-                         h->d_Lblk + (size_t)(jS / SBW) * SBW * SBW, h->d_dxi, jS, jE, jE2);
+                         h->d_Lblk + (size_t)(jS / SBW) * SBW * SBW, d_x, jS, jE, jE2);
     }
+    launch_expand();
   };
   launch_solve(h->chol_onepass);
   MVBA_HIP(hipGetLastError());
@@ -4313,14 +4359,18 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     // negative damping factor).  The reference's np.linalg.solve is LU with partial pivoting and
     // does not care, so redo the solve that way (slow path, rare) and the tail of the step.
     if (!h->d_lu) {
-      int rc_ = dmalloc(&h->d_lu, (size_t)D * (D + 1));
+      int rc_ = dmalloc(&h->d_lu, (size_t)h->D * (h->D + 1));  // (the default map's size: any map fits)
       if (rc_) return rc_;
-      rc_ = dmalloc(&h->d_ipiv, (size_t)D);
+      rc_ = dmalloc(&h->d_ipiv, (size_t)h->D);
       if (rc_) return rc_;
     }
     MVBA_HIP(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
     {
       Timed t(h, MVBA_K_SOLVE);
+      if (h->mapped) {
+        hipLaunchKernelGGL(k_map_full, dim3((D + 1 + 255) / 256, D), dim3(256), 0, h->stream, D, m, d_A, d_b, h->d_map_ptr, h->d_map_mem, h->d_lu);
+        launch_map_tied(h, h->d_lu, D + 1, 1);
+      } else
       hipLaunchKernelGGL(k_compact_full, dim3((D + 1 + 255) / 256, D), dim3(256), 0, h->stream, D, m, h->gauge_axis, d_A, d_b, h->d_lu);
       for (int j0 = 0; j0 < D; j0 += LU_NB) {
         const int nb = std::min(LU_NB, D - j0), right = D + 1 - (j0 + nb);  // columns right of the panel incl. the rhs
@@ -4331,7 +4381,8 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
         if (below > 0)
           hipLaunchKernelGGL(k_lu_gemm, dim3((right + 63) / 64, (below + 63) / 64), dim3(256), 0, h->stream, h->d_lu, D, j0, nb);
       }
-      hipLaunchKernelGGL(k_lu_backsub, dim3(1), dim3(1024), 0, h->stream, h->d_lu, D, m, h->gauge_axis, h->d_dxi);
+      hipLaunchKernelGGL(k_lu_backsub, dim3(1), dim3(1024), 0, h->stream, h->d_lu, D, m, h->gauge_axis, d_x);
+      launch_expand();
     }
     h->stats.n_lu_fallback++;
     launch_tail();
@@ -4368,6 +4419,17 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
         }
     }
     double worst = 0.0;
+    if (h->mapped) {  // the mapped system's residual P^T (b - A P x): x above is dxi = P x, rows summed over an unknown's members
+      for (int j = 0; j < D; ++j) {
+        double res = 0.0, scale = 0.0;
+        for (int q = h->map_ptr[j]; q < h->map_ptr[j + 1]; ++q) {
+          const size_t g = (size_t)h->map_mem[q];
+          res += Ab[nA + g] - r[g];
+          scale += an[g] + std::fabs(Ab[nA + g]);
+        }
+        worst = std::max(worst, scale > 0.0 ? std::fabs(res) / scale : 0.0);
+      }
+    } else
     for (size_t g = 0; g < n9; ++g)
       if (kept(g)) {
         const double bg = Ab[nA + g], scale = an[g] + std::fabs(bg);
@@ -4387,6 +4449,108 @@ int mvba_commit(mvba_handle *h) {
   h->cur = 1 - h->cur;
   h->have_trial = false; h->linearized = false;
   h->stats.n_commit++;
+  return MVBA_OK;
+}
+
+int mvba_set_parameter_map(mvba_handle *h, const int32_t *col, int32_t n_free) {
+  if (!h) return fail(MVBA_ERR_BADARG, "null handle");
+  MVBA_HIP(hipSetDevice(h->device));
+  const int m = h->m, n9 = 9 * m;
+  auto is_gauge = [&](int g) { return (g >= 3 && g <= 8) || g == 12 + h->gauge_axis; };
+  if (!col) {  // the default map: the seven gauge slots held, everything else free
+    h->mapped = false;
+    h->have_trial = false;
+    return MVBA_OK;
+  }
+  if (n_free < 0 || n_free > h->D)
+    return fail(MVBA_ERR_BADARG, "mvba_set_parameter_map: n_free = " + std::to_string(n_free) + " must be in 0 .. 9 n_images - 7 = " + std::to_string(h->D));
+  std::vector<int> cnt(n_free + 1, 0), first(n_free, -1);
+  for (int g = 0; g < n9; ++g) {
+    const int j = col[g];
+    if (j < -1 || j >= n_free)
+      return fail(MVBA_ERR_BADARG, "mvba_set_parameter_map: col[" + std::to_string(g) + "] = " + std::to_string(j) + " is neither -1 nor below n_free = " + std::to_string(n_free));
+    if (j >= 0 && is_gauge(g))
+      return fail(MVBA_ERR_BADARG, "mvba_set_parameter_map: col[" + std::to_string(g) + "] is a gauge slot and must be -1");
+    if (j < 0) continue;
+    if (first[j] < 0) first[j] = g;
+    else if (g % 9 != first[j] % 9 || g % 9 > 2)
+      return fail(MVBA_ERR_BADARG, "mvba_set_parameter_map: col[" + std::to_string(g) + "] ties slot " + std::to_string(g) + " to slot " + std::to_string(first[j]) +
+                                       " (unknown " + std::to_string(j) + "): only the same intrinsic parameter (f, u or v) of different cameras can be tied");
+    ++cnt[j];
+  }
+  for (int j = 0; j < n_free; ++j)
+    if (!cnt[j]) return fail(MVBA_ERR_BADARG, "mvba_set_parameter_map: unknown " + std::to_string(j) + " has no parameter slot");
+  bool is_default = n_free == h->D;
+  for (int g = 0, j = 0; is_default && g < n9; ++g) is_default = col[g] == (is_gauge(g) ? -1 : j++);
+  h->have_trial = false;
+  if (is_default) {  // spelled out: the engine runs exactly what it runs without a map
+    h->mapped = false;
+    return MVBA_OK;
+  }
+  std::vector<int> ptr(n_free + 1, 0), mem;
+  for (int j = 0; j < n_free; ++j) ptr[j + 1] = ptr[j] + cnt[j];
+  mem.resize(std::max(ptr[n_free], 1));
+  {
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int g = 0; g < n9; ++g)
+      if (col[g] >= 0) mem[fill[col[g]]++] = g;  // ascending g within an unknown
+  }
+  int U = 0;
+  while (U < n_free && cnt[U] == 1) ++U;
+  // the tied x tied entries of the lower triangle, and how many workgroups share one: eight of the row's members each, 64 at most
+  std::vector<int2> pairs;
+  int max_cnt = 1;
+  {
+    std::vector<int> tied;
+    for (int j = 0; j < n_free; ++j)
+      if (cnt[j] > 1) { tied.push_back(j); max_cnt = std::max(max_cnt, cnt[j]); }
+    for (size_t a = 0; a < tied.size(); ++a)
+      for (size_t b = 0; b <= a; ++b) pairs.push_back(make_int2(tied[a], tied[b]));
+  }
+  const int nblk = std::min(64, (max_cnt + 7) / 8);
+  int2 *d_pairs = nullptr;
+  double *d_part = nullptr;
+  if (!pairs.empty()) {
+    int rc = dmalloc(&d_pairs, pairs.size());
+    if (!rc) rc = dmalloc(&d_part, pairs.size() * (size_t)nblk);
+    if (rc) {
+      if (d_pairs) hipFree(d_pairs);
+      return rc;
+    }
+  }
+  if (!h->d_map_col) {
+    int rc = dmalloc(&h->d_map_col, (size_t)n9);
+    if (!rc) rc = dmalloc(&h->d_map_ptr, (size_t)h->D + 1);
+    if (!rc) rc = dmalloc(&h->d_map_mem, (size_t)n9);
+    if (!rc) rc = dmalloc(&h->d_map_x, (size_t)n9 + 16);  // (the back-substitution clears 9m slots, or slots 3..8 and 12 + axis)
+    if (rc) {
+      for (void **q : {(void **)&h->d_map_col, (void **)&h->d_map_ptr, (void **)&h->d_map_mem, (void **)&h->d_map_x}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+      }
+      if (d_pairs) hipFree(d_pairs);
+      if (d_part) hipFree(d_part);
+      return rc;
+    }
+  }
+  MVBA_HIP(hipStreamSynchronize(h->stream));  // nothing in flight reads the tables that are replaced now
+  if (h->d_map_pairs) hipFree(h->d_map_pairs);
+  if (h->d_map_part) hipFree(h->d_map_part);
+  h->d_map_pairs = d_pairs;
+  h->d_map_part = d_part;
+  h->n_map_pairs = (int)pairs.size();
+  h->map_nblk = nblk;
+  if (!pairs.empty()) MVBA_HIP(hipMemcpy(h->d_map_pairs, pairs.data(), sizeof(int2) * pairs.size(), hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(h->d_map_col, col, sizeof(int) * n9, hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(h->d_map_ptr, ptr.data(), sizeof(int) * (n_free + 1), hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(h->d_map_mem, mem.data(), sizeof(int) * mem.size(), hipMemcpyHostToDevice));
+  h->map_col.assign(col, col + n9);
+  h->map_ptr = ptr;
+  h->map_mem = mem;
+  h->n_free = n_free;
+  h->map_ld = (n_free + 3) & ~3;
+  h->map_U = U;
+  h->mapped = true;
   return MVBA_OK;
 }
 
@@ -4417,7 +4581,7 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
     return fail(MVBA_ERR_BADARG, "mvba_covariance: the covariance is defined for the squared loss only (this engine has a robust loss)");
   if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
   MVBA_HIP(hipSetDevice(h->device));
-  const int m = h->m, D = h->D, ld = h->ld, nt = (D + NB - 1) / NB;
+  const int m = h->m, D = h->solve_D(), ld = h->solve_ld(), nt = (D + NB - 1) / NB;
   const size_t n_sig = sig_block(m, m, m);  // (the block index of (m, m) is the block count)
   // First call: the camera-block table, the trtri panels, the point and camera blocks -- all four or none (a failed
   // allocation frees what it got, so that a later call never runs with some of them missing)
@@ -4431,7 +4595,7 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
   if (!h->d_cov_sig || !h->d_cov_panel || !h->d_cov_pts || !h->d_cov_cam) {
     free_cov();
     local_rc = dmalloc(&h->d_cov_sig, n_sig);
-    if (!local_rc) local_rc = dmalloc(&h->d_cov_panel, 2 * (size_t)D * NB);
+    if (!local_rc) local_rc = dmalloc(&h->d_cov_panel, 2 * (size_t)h->D * NB);
     if (!local_rc) local_rc = dmalloc(&h->d_cov_pts, 6 * (size_t)h->N);
     if (!local_rc) local_rc = dmalloc(&h->d_cov_cam, 81 * (size_t)m);
     if (local_rc) free_cov();
@@ -4440,6 +4604,10 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
   struct EvFree { hipEvent_t *e; ~EvFree() { for (int i = 0; i < 5; ++i) if (e[i]) hipEventDestroy(e[i]); } } ev_free{ev};
   for (auto &e : ev)
     if (!local_rc && hipEventCreate(&e) != hipSuccess) local_rc = fail(MVBA_ERR_HIP, "hipEventCreate failed");
+  // With a parameter map k_cov_lauum scatters Sigma' (D' x D') through keep_index into a scratch table of mv camera blocks per side
+  // (mv <= m); k_map_cov_expand then fills the real table with P Sigma' P^T.
+  const int mv = (D + 6) / 9 + 1;
+  if (!local_rc && h->mapped && D > 0 && !h->d_cov_sigv) local_rc = dmalloc(&h->d_cov_sigv, n_sig);
   const bool sharded = h->comm || h->host_ar;
   if (local_rc && !sharded) return local_rc;
   const std::string local_err = local_rc ? g_err : std::string();
@@ -4472,9 +4640,10 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
   }
   MVBA_HIP(hipEventRecord(ev[1], h->stream));
   // 5: gauge strip + blocked Cholesky of the undamped S
-  launch_factor(h);
+  if (D > 0) launch_factor(h);
   MVBA_HIP(hipEventRecord(ev[2], h->stream));
   // 6a: W = L^-1 in place in d_Ared, then Sigma = W^T W into the camera-block table (zeros at the gauge slots)
+  if (D > 0)
   hipLaunchKernelGGL(k_cov_assemble, dim3(nt), dim3(256), 0, h->stream, h->d_Ared, ld, D, (const double *)h->d_Ztiles,
                      (const double *)h->d_Lblk);
   double *panel[2] = {h->d_cov_panel, h->d_cov_panel + (size_t)D * NB};
@@ -4485,6 +4654,14 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
                          panel[(J + 1) & 1]);
   }
   MVBA_HIP(hipMemsetAsync(h->d_cov_sig, 0, sizeof(double) * n_sig, h->stream));
+  if (h->mapped) {
+    if (D > 0) {
+      hipLaunchKernelGGL(k_cov_lauum, dim3(nt * (nt + 1) / 2), dim3(256), 0, h->stream, (const double *)h->d_Ared, ld, D, nt, mv,
+                         h->gauge_axis, h->d_cov_sigv);
+      hipLaunchKernelGGL(k_map_cov_expand, dim3((unsigned)((81 * m + 255) / 256), m), dim3(256), 0, h->stream, m, mv, h->gauge_axis,
+                         (const int *)h->d_map_col, (const double *)h->d_cov_sigv, h->d_cov_sig);
+    }
+  } else
   hipLaunchKernelGGL(k_cov_lauum, dim3(nt * (nt + 1) / 2), dim3(256), 0, h->stream, (const double *)h->d_Ared, ld, D, nt, m,
                      h->gauge_axis, h->d_cov_sig);
   MVBA_HIP(hipEventRecord(ev[3], h->stream));

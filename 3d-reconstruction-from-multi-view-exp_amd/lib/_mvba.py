@@ -77,6 +77,7 @@ SIGNATURES = {
     "mvba_linearize": (C.c_int, [C.c_void_p]),
     "mvba_try_step": (C.c_int, [C.c_void_p, C.c_double, _dp]),
     "mvba_commit": (C.c_int, [C.c_void_p]),
+    "mvba_set_parameter_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mvba_covariance": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "mvba_residuals": (C.c_int, [C.c_void_p, _dp]),
     "mvba_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -186,6 +187,7 @@ class HipEngine:
             raise_for(self.lib.mvba_create(C.byref(prob), C.byref(h)), self.lib)
         self._h = h
         self.n_solves = 0
+        self.n_free = 9 * self.m - 7  # unknowns of the reduced camera system (set_parameter_map)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -250,6 +252,23 @@ class HipEngine:
 
     def commit(self):
         raise_for(self.lib.mvba_commit(self._h), self.lib)
+
+    def set_parameter_map(self, col, n_free=None):
+        """Which camera parameters a trial adjusts (include/mvba.h, mvba_set_parameter_map): ``col`` (9m,) int, slot
+        9k + p (p: f, u, v, t, omega) -> reduced unknown, -1 = held, equal entries = tied; ``None`` = the default map
+        (the seven gauge slots held).  ``n_free`` defaults to ``col.max() + 1``.  Voids the trial, keeps the
+        linearisation.  Sharded engines: every rank sets the same map."""
+        if col is None:
+            raise_for(self.lib.mvba_set_parameter_map(self._h, None, 0), self.lib)
+            self.n_free = 9 * self.m - 7
+            return
+        col = _as(col, np.int32).reshape(-1)
+        if col.shape != (9 * self.m,):
+            raise ValueError(f"col must have 9 n_images = {9 * self.m} entries, got {col.shape[0]}")
+        if n_free is None:
+            n_free = int(col.max()) + 1 if col.size else 0
+        raise_for(self.lib.mvba_set_parameter_map(self._h, col.ctypes.data_as(C.POINTER(C.c_int32)), int(n_free)), self.lib)
+        self.n_free = int(n_free)
 
     def covariance(self, points=True, cameras=True, full=False):
         """Unit marginal covariances (J^T J)^-1 at the committed state, in the engine's frame, gauge parameters fixed

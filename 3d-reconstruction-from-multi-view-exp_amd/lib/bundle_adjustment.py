@@ -104,13 +104,102 @@ def covariance_to_input_frame(camera0: dict[str, Any], points=None, cameras=None
     return P, Cc, Cf
 
 
-def residual_variance(E: float, n_obs: int, n_points: int, n_images: int) -> float:
+def residual_variance(E: float, n_obs: int, n_points: int, n_images: int, n_free: int | None = None) -> float:
     """sigma^2 = E / (2 n_obs - (3 N + 9 m - 7)): the residual variance per image coordinate (units x / f0) at the
-    solution; ValueError when the problem has no redundancy."""
-    dof = 2 * int(n_obs) - (3 * int(n_points) + 9 * int(n_images) - 7)
+    solution; ValueError when the problem has no redundancy.  ``n_free``: the number of free camera unknowns under a
+    parameter map (``parameter_map``), in the place of 9 m - 7."""
+    if n_free is None:
+        dof = 2 * int(n_obs) - (3 * int(n_points) + 9 * int(n_images) - 7)
+        if dof <= 0:
+            raise ValueError(f"no redundancy: 2 n_obs - (3 N + 9 m - 7) = {dof}")
+        return float(E) / dof
+    dof = 2 * int(n_obs) - (3 * int(n_points) + int(n_free))
     if dof <= 0:
-        raise ValueError(f"no redundancy: 2 n_obs - (3 N + 9 m - 7) = {dof}")
+        raise ValueError(f"no redundancy: 2 n_obs - (3 N + n_free) = {dof}")
     return float(E) / dof
+
+
+# ---- parameter maps: which camera parameters are adjusted (DESIGN.md §13) -------------------------------------
+# slots of one camera, in the engine's order: f | u, v | t | omega
+HOLD_NAMES = {"f": (0,), "u": (1, 2), "t": (3, 4, 5), "R": (6, 7, 8), "intrinsics": (0, 1, 2), "pose": (3, 4, 5, 6, 7, 8),
+              "cameras": tuple(range(9))}
+SHARE_NAMES = {"f": (0,), "u": (1, 2), "intrinsics": (0, 1, 2)}
+SLOT_LABELS = ("f", "u", "v", "t_x", "t_y", "t_z", "omega_x", "omega_y", "omega_z")
+
+
+def gauge_slots(axis: str):
+    """The seven slots 9 k + p the gauge fixes: camera 0's t and omega, one component of camera 1's t."""
+    if axis not in AXES:
+        raise ValueError(f"axis must be one of {sorted(AXES)}, got {axis!r}")
+    return np.array([3, 4, 5, 6, 7, 8, 12 + AXES[axis]])
+
+
+def _slot_names(arg, table, what):
+    names = [arg] if isinstance(arg, str) else list(arg)
+    slots: set[int] = set()
+    for nm in names:
+        if not isinstance(nm, str) or nm not in table:
+            raise ValueError(f"{what}: unknown name {nm!r} (known: {sorted(table)})")
+        slots.update(table[nm])
+    return slots
+
+
+def parameter_map(n_images: int, axis: str = "x-right_z-forward", hold=None, share=None, share_groups=None):
+    """(col, n_free) for ``HipEngine.set_parameter_map`` / ``mvba_set_parameter_map``: col (9 m,) int32, slot 9 k + p
+    (p: f, u, v, t_x, t_y, t_z, omega_x, omega_y, omega_z) -> reduced unknown, -1 where held.
+
+    ``hold``: names applied to every camera -- "f", "u" (both principal-point coordinates), "t", "R", "intrinsics"
+    (f, u), "pose" (t, R), "cameras" (everything) -- one or several, or a bool array (m, 9), True = held.  The seven
+    gauge slots are always held.  ``share``: names among "f", "u", "intrinsics": that parameter is ONE unknown for all
+    cameras of a group.  ``share_groups``: int array (m,), equal labels form a group (default: one group of all
+    cameras).  Order of the unknowns: the untied ones first, by ascending slot; the tied ones last, by (group label, p).
+    A pose is held in the gauge frame BA works in (relative to camera 0 and the camera-0/1 baseline).
+    ValueError: an unknown name, a slot both held by name and shared, a group some of whose members are held in a shared
+    slot and some not."""
+    m = int(n_images)
+    gauge = gauge_slots(axis)
+    held = np.zeros((m, 9), dtype=bool)
+    held_by_name: set[int] = set()
+    if hold is not None:
+        if isinstance(hold, str) or (len(hold) and all(isinstance(v, str) for v in hold)):
+            held_by_name = _slot_names(hold, HOLD_NAMES, "hold")
+            held[:, sorted(held_by_name)] = True
+        else:
+            mask = np.asarray(hold)
+            if mask.dtype != np.bool_ or mask.shape != (m, 9):
+                raise ValueError(f"hold: names or a bool array of shape ({m}, 9), got {mask.dtype} {mask.shape}")
+            held |= mask
+    shared = _slot_names(share, SHARE_NAMES, "share") if share is not None else set()
+    both = sorted(shared & held_by_name)
+    if both:
+        raise ValueError(f"slot {SLOT_LABELS[both[0]]!r} is both held and shared")
+    if share_groups is None:
+        labels = np.zeros(m, dtype=np.int64)
+    else:
+        labels = np.asarray(share_groups)
+        if labels.shape != (m,) or labels.dtype.kind not in "iu":
+            raise ValueError(f"share_groups: an int array of shape ({m},)")
+    held_flat = held.reshape(-1).copy()
+    held_flat[gauge[gauge < 9 * m]] = True  # (never in an intrinsic slot: sharing is not affected)
+    col = np.full(9 * m, -1, dtype=np.int32)
+    tied_sets = []  # (label, p, slots)
+    tied_mask = np.zeros(9 * m, dtype=bool)
+    for lab in np.unique(labels) if shared else ():
+        cams = np.nonzero(labels == lab)[0]
+        for p in sorted(shared):
+            h = held[cams, p]
+            if h.all():
+                continue
+            if h.any():
+                raise ValueError(f"group {int(lab)}: slot {SLOT_LABELS[p]!r} is held for some of its cameras and shared by the others")
+            if len(cams) > 1:  # (a group of one camera has nothing to tie: an ordinary unknown)
+                tied_sets.append((lab, p, 9 * cams + p))
+                tied_mask[9 * cams + p] = True
+    free = np.nonzero(~held_flat & ~tied_mask)[0]
+    col[free] = np.arange(len(free), dtype=np.int32)
+    for i, (_, _, slots) in enumerate(tied_sets):
+        col[slots] = len(free) + i
+    return col, len(free) + len(tied_sets)
 
 
 def intrinsics_from(f, u, f0: float):
@@ -199,11 +288,21 @@ class BundleAdjuster:
         axis: str = "x-right_z-forward",
         loss: str = "squared",
         loss_scale: float | None = None,
+        hold=None,
+        share=None,
+        share_groups=None,
     ):
         """``loss``: "squared" (the reference's sum of squares), "huber" or "cauchy" -- a robust loss with scale
-        ``loss_scale`` (delta, in the units of ``x``: pixels), required for the robust ones."""
+        ``loss_scale`` (delta, in the units of ``x``: pixels), required for the robust ones.
+        ``hold`` / ``share`` / ``share_groups``: which camera parameters are adjusted (``parameter_map``):
+        ``hold="intrinsics"`` for calibrated cameras, ``share="intrinsics"`` when one camera body took all the images
+        (``share_groups`` for a rig of several), ``hold="pose"`` / ``"cameras"`` to refine the structure only.  Tied
+        parameters must start equal (``init_K[:, 0, 0]``, ``init_K[:, :2, 2]`` within a group).  A held pose is held in
+        the gauge frame BA works in, i.e. relative to camera 0 and the camera-0/1 baseline: the output poses equal the
+        input poses up to the rounding of the frame change."""
         check_loss(loss, loss_scale)  # (ValueError before any work)
         x = np.asarray(x)
+        self._check_map(x.shape[1], axis, init_K, hold, share, share_groups)
         pt_ptr, cam_idx, xy = dense_to_observations(x, visibility_index)
         self._setup(x.shape[0], x.shape[1], pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, loss=loss,
                     loss_scale=loss_scale)
@@ -211,16 +310,47 @@ class BundleAdjuster:
     @classmethod
     def from_observations(cls, n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t,
                           f0: float = 1.0, axis: str = "x-right_z-forward", loss: str = "squared",
-                          loss_scale: float | None = None, **engine_kw):
+                          loss_scale: float | None = None, hold=None, share=None, share_groups=None, **engine_kw):
         """Extension for sizes where the dense (N,m,2) array cannot exist
-        (SURVEY 8f rank 1): observation list in CSR-by-point form.  ``loss`` / ``loss_scale``: as for the constructor."""
+        (SURVEY 8f rank 1): observation list in CSR-by-point form.  ``loss`` / ``loss_scale`` / ``hold`` / ``share`` /
+        ``share_groups``: as for the constructor."""
         check_loss(loss, loss_scale)
         self = cls.__new__(cls)
+        self._check_map(n_images, axis, init_K, hold, share, share_groups)
         self._setup(n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, loss=loss,
                     loss_scale=loss_scale, **engine_kw)
         return self
 
     # -- construction ------------------------------------------------------
+    _map = None  # (col, n_free) when hold / share were given (set by _check_map before any device work)
+
+    def _check_map(self, n_images, axis, init_K, hold, share, share_groups):
+        """parameter_map of the constructor's arguments and the check that tied parameters start equal: ValueErrors
+        before any device work."""
+        if hold is None and share is None:
+            if share_groups is not None:
+                raise ValueError("share_groups without share")
+            return
+        if axis not in AXES:
+            raise ValueError()
+        col, n_free = parameter_map(n_images, axis, hold, share, share_groups)
+        K = np.asarray(init_K, dtype=np.float64)
+        start = np.stack([K[:, 0, 0], K[:, 0, 2], K[:, 1, 2]], axis=1)  # (m, 3): f, u, v
+        labels = np.zeros(int(n_images), dtype=np.int64) if share_groups is None else np.asarray(share_groups)
+        for j in np.unique(col[col >= 0]):
+            slots = np.nonzero(col == j)[0]
+            if len(slots) > 1:
+                v = start[slots // 9, slots % 9]
+                if not np.all(v == v[0]):
+                    raise ValueError(f"group {int(labels[slots[0] // 9])}: shared {SLOT_LABELS[slots[0] % 9]!r} starts from different values "
+                                     f"({v.min()!r} .. {v.max()!r})")
+        self._map = (col, n_free)
+
+    @property
+    def n_free_camera_parameters(self) -> int:
+        """Unknowns of the reduced camera system: 9 m - 7 by default, fewer with hold / share."""
+        return 9 * self._n_images - 7 if self._map is None else int(self._map[1])
+
     def _make_engine(self, n_points, n_images, pt_ptr, cam_idx, xy, f0, axis, **kw):
         from ._mvba import HipEngine
 
@@ -246,6 +376,8 @@ class BundleAdjuster:
         self._n_points, self._n_images = int(n_points), int(n_images)
         self._engine = self._make_engine(self._n_points, self._n_images, pt_ptr, cam_idx, xy, f0, axis, **engine_kw)
         self._engine.set_params(X, init_K[:, 0, 0], init_K[:, :2, 2], t, R)  # ref :45-48
+        if self._map is not None:
+            self._engine.set_parameter_map(self._map[0], self._map[1])
         self._engine_frame = "gauge"  # the frame of the engine's state: "input" once optimize() has applied the way back
         self._log: list[dict[str, npt.NDArray | float]] = []
 
@@ -294,7 +426,8 @@ class BundleAdjuster:
         """Marginal covariances of the current estimate (after optimize(): the solution): ``points`` (N, 3, 3),
         ``cameras`` (m, 9, 9) in the order f, u, v, t, omega, and ``cameras_full`` (9m, 9m) when ``full_cameras``.
         Undamped, with the seven gauge parameters fixed (camera 0's t and omega, one component of camera 1's t: zero rows
-        and columns).  ``scale="unit"``: (J^T J)^-1 with J in units x / f0; ``"residual"``: times sigma^2 =
+        and columns).  With ``hold`` / ``share``: zero rows and columns for every held parameter, identical ones for tied
+        parameters, and sigma^2 with 3N + n_free unknowns.  ``scale="unit"``: (J^T J)^-1 with J in units x / f0; ``"residual"``: times sigma^2 =
         E / (2 n_obs - (3N + 9m - 7)) (also returned as ``sigma2``).  ``frame="gauge"``: the normalised frame BA works in;
         ``"input"``: the caller's frame (omega as a rotation increment R <- Rod(omega) R in that frame).  The engine's
         state is left bitwise as it was.  Raises LinAlgError for a degenerate problem (a point seen once, a camera with
@@ -304,8 +437,9 @@ class BundleAdjuster:
         if self._loss != "squared":
             raise NotImplementedError(f"covariance() is defined for the squared loss only (this adjuster uses loss={self._loss!r})")
         eng, cam0 = self._engine, self._init_camera0_params
+        nf = {} if self._map is None else {"n_free": self._map[1]}
         if scale == "residual":
-            residual_variance(0.0, eng.n_obs, self._n_points, self._n_images)  # (no redundancy: ValueError before any work)
+            residual_variance(0.0, eng.n_obs, self._n_points, self._n_images, **nf)  # (no redundancy: ValueError before any work)
         saved = None
         if self._engine_frame == "input":  # the covariance is taken in the gauge frame the parameterisation fixes
             saved = eng.get_params()
@@ -326,7 +460,7 @@ class BundleAdjuster:
             if full_cameras:
                 out["cameras_full"] = Cf
         if scale == "residual":
-            s2 = residual_variance(E, eng.n_obs, self._n_points, self._n_images)
+            s2 = residual_variance(E, eng.n_obs, self._n_points, self._n_images, **nf)
             out["sigma2"] = s2
             for k in ("points", "cameras", "cameras_full"):
                 if k in out:

@@ -117,6 +117,20 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial);
 /* trial -> committed (ref :169-173). */
 int mvba_commit(mvba_handle *h);
 
+/* Parameter map: which camera parameters a trial adjusts.  Parameter p of camera k is slot g = 9 k + p, p in the order
+ * f, u, v, t[3], omega[3] (the order of MVBA_BUF_DXI).  col [9 n_images]: -1 holds slot g (its increment is 0 in every
+ * step); j in 0 .. n_free-1 makes it the reduced unknown j, and slots with the same j are TIED (they get the same
+ * increment).  With P[g][col g] = 1 a trial solves (P^T A P) x = P^T b on the reduced camera system [A | b] it solves
+ * today and steps by dxi = P x; everything else is unchanged.  NULL restores the default map: the seven gauge slots (camera
+ * 0's t and omega, component gauge_axis of camera 1's t) held, all others free in ascending order, n_free = 9 n_images - 7.
+ * Rules (MVBA_ERR_BADARG, the message names the offending index): the gauge slots are -1; -1 <= col[g] < n_free; every
+ * unknown has a slot; tied slots are the same intrinsic parameter (p <= 2) of different cameras.  n_free = 0 is legal: the
+ * cameras stay, the points move by -E_a^-1 dP_a, no dense solve runs.  The caller gives tied parameters equal values; equal
+ * increments then keep them equal bit for bit.  May be called any time after mvba_create; keeps the linearisation, voids
+ * the trial (mvba_commit before the next mvba_try_step is MVBA_ERR_STATE).  mvba_covariance honours the map: Cov = P Sigma'
+ * P^T, zero rows and columns where held.  Sharded: every rank must set the same map (it acts after the all-reduce). */
+int mvba_set_parameter_map(mvba_handle *h, const int32_t *col, int32_t n_free);
+
 /* Marginal covariances at the COMMITTED state, undamped, gauge parameters fixed (zero rows/columns): the unit covariance
  * C = (J^T J)^-1 = 2 H^-1 over the free parameters (J: the residual Jacobian, units x / f0), camera parameters in the order
  * f, u, v, t[3], omega[3].  Runs K1, K3a at c = 0, the engine's K3 form, the all-reduce of [A|b] and K4's Cholesky, then
@@ -186,7 +200,7 @@ enum {
   MVBA_BUF_DP,           /* [n_points][3]                                    */
   MVBA_BUF_A_FULL,       /* [9m][9m] symmetric, before gauge removal         */
   MVBA_BUF_B_FULL,       /* [9m]                                             */
-  MVBA_BUF_DXI,          /* [9m] with zeros at the gauge slots               */
+  MVBA_BUF_DXI,          /* [9m] with zeros at the gauge slots (with a map: where held; equal where tied) */
   MVBA_BUF_DX,           /* [n_points][3]                                    */
   MVBA_BUF_TRIAL_X,      /* [n_points][3]                                    */
   MVBA_BUF_TRIAL_CAM,    /* [m][15]  f,u,v,t[3],R[9]                         */
