@@ -2888,10 +2888,57 @@ __global__ void k_idx_interleave(long long n_steps, const int *__restrict__ st_k
 }  // namespace
 
 // ------------------------------------------------------------------ host side
+// Device buffers with one owner.  Whatever alloc() hands out is freed when the owner goes: a DevBufs on the stack holds the
+// temporaries of one call (every early return frees them), the one inside mvba_handle holds the engine's buffers (mvba_destroy
+// frees them all: a new member of mvba_handle needs no second edit).  release() frees one buffer early; adopt() moves one over
+// from another owner.
+struct DevBufs {
+  std::vector<void *> bufs;
+  DevBufs() = default;
+  DevBufs(const DevBufs &) = delete;
+  DevBufs &operator=(const DevBufs &) = delete;
+  ~DevBufs() { release_all(); }
+  template <typename T>
+  int alloc(T **p, size_t n) {
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+    const hipError_t e = hipMalloc((void **)p, bytes);
+    if (e != hipSuccess) {  // say how much was asked for and how much there is: "out of memory" alone does not tell a scene from a knob
+      size_t fr = 0, tot = 0;
+      hipMemGetInfo(&fr, &tot);
+      *p = nullptr;
+      return fail(MVBA_ERR_HIP, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e) + " (" + std::to_string(fr >> 20) +
+                                    " MiB free of " + std::to_string(tot >> 20) + ")");
+    }
+    bufs.push_back(*p);
+    return MVBA_OK;
+  }
+  void own(void *q) { bufs.push_back(q); }  // a buffer the caller allocated itself
+  bool forget(void *q) {
+    auto it = std::find(bufs.begin(), bufs.end(), q);
+    if (it == bufs.end()) return false;
+    bufs.erase(it);
+    return true;
+  }
+  template <typename T>
+  void release(T *&p) {
+    if (p && forget(p)) hipFree(p);
+    p = nullptr;
+  }
+  template <typename T>
+  void adopt(DevBufs &from, T *p) {
+    if (p && from.forget(p)) bufs.push_back(p);
+  }
+  void release_all() {
+    for (void *q : bufs) hipFree(q);
+    bufs.clear();
+  }
+};
+
 enum { SCHUR_PAIRS = 1, SCHUR_SLOTS = 2, SCHUR_DENSE = 3 };  // (0 was round 1's camera-strip form: the values are mvba_get_info's)
 struct mvba_handle {
   int device = 0;
   hipStream_t stream = nullptr;
+  DevBufs mem;  // every device buffer below (h->mem.alloc): freed by mvba_destroy, or early by h->mem.release
   long long N = 0, nobs = 0;
   int m = 0, gauge_axis = 0, D = 0, ld = 0;
   double f0 = 1.0;
@@ -2929,7 +2976,6 @@ struct mvba_handle {
   double *d_dense_part = nullptr;     // SCHUR_DENSE: partial tiles per workgroup
   int *d_dense_obs = nullptr;         // ... and, with missing observations, the observation of every (point, camera) or -1
   int dense_blocks = 0, dense_tiles = 0;
-  bool dense_attr_set = false;
   // state: [cur] committed, [1-cur] trial
   double *d_X[2] = {nullptr, nullptr}, *d_cam15[2] = {nullptr, nullptr};
   int cur = 0;
@@ -3036,19 +3082,6 @@ void drain_events(mvba_handle *h) {  // call after a stream sync
   h->pending.clear();
 }
 
-template <typename T>
-int dmalloc(T **p, size_t n) {
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  const hipError_t e = hipMalloc((void **)p, bytes);
-  if (e != hipSuccess) {  // say how much was asked for and how much there is: "out of memory" alone does not tell a scene from a knob
-    size_t fr = 0, tot = 0;
-    hipMemGetInfo(&fr, &tot);
-    return fail(MVBA_ERR_HIP, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e) + " (" + std::to_string(fr >> 20) +
-                                  " MiB free of " + std::to_string(tot >> 20) + ")");
-  }
-  return MVBA_OK;
-}
-
 int sync_and_drain(mvba_handle *h) {
   MVBA_HIP(hipStreamSynchronize(h->stream));
   drain_events(h);
@@ -3135,55 +3168,99 @@ int global_cost(mvba_handle *h, double *E) {
   return MVBA_OK;
 }
 
-// the robust instantiations by loss; the squared loss keeps its own kernels
-typedef void (*ResidJacRobustFn)(MVBA_RESID_JAC_ARGS, LossArgs);
-typedef void (*CostRobustFn)(MVBA_COST_ARGS, LossArgs);
-ResidJacRobustFn resid_jac_robust(bool gcam, int loss) {
-  if (loss == LOSS_HUBER) return gcam ? k_resid_jac<true, LOSS_HUBER, LossArgs> : k_resid_jac<false, LOSS_HUBER, LossArgs>;
-  return gcam ? k_resid_jac<true, LOSS_CAUCHY, LossArgs> : k_resid_jac<false, LOSS_CAUCHY, LossArgs>;
+// ---- one launch path for squared and robust engines.  A robust instantiation takes the arguments of the squared
+// one and a trailing LossArgs; LossKernel holds the two, launch_loss() launches the engine's with the common arguments.  The
+// tables below are the only places that name an instantiation: the launch and the LDS attribute of mvba_create both go through them.
+template <typename... A>
+struct LossKernel {
+  void (*squared)(A...);
+  void (*robust)(A..., LossArgs);
+  const void *fn(bool rb) const { return rb ? (const void *)robust : (const void *)squared; }
+};
+template <typename... A>
+LossKernel<A...> loss_kernel(void (*squared)(A...), void (*robust)(A..., LossArgs)) { return {squared, robust}; }
+
+template <typename... A, typename... Args>
+void launch_loss(mvba_handle *h, LossKernel<A...> k, dim3 grid, dim3 block, size_t lds, Args... args) {
+  if (h->loss != LOSS_SQUARED) hipLaunchKernelGGL(k.robust, grid, block, lds, h->stream, args..., LossArgs{h->loss_b, h->d_sqw});
+  else hipLaunchKernelGGL(k.squared, grid, block, lds, h->stream, args...);
 }
-CostRobustFn cost_robust(bool gcam, int loss) {
-  if (loss == LOSS_HUBER) return gcam ? k_cost<true, LOSS_HUBER, LossArgs> : k_cost<false, LOSS_HUBER, LossArgs>;
-  return gcam ? k_cost<true, LOSS_CAUCHY, LossArgs> : k_cost<false, LOSS_CAUCHY, LossArgs>;
+
+// K1 and the cost pass: the robust instantiation is the one of the engine's loss (a squared engine never launches it)
+auto resid_jac_kernel(bool gcam, int loss) {
+  if (loss == LOSS_CAUCHY)
+    return gcam ? loss_kernel(k_resid_jac<true>, k_resid_jac<true, LOSS_CAUCHY, LossArgs>) : loss_kernel(k_resid_jac<false>, k_resid_jac<false, LOSS_CAUCHY, LossArgs>);
+  return gcam ? loss_kernel(k_resid_jac<true>, k_resid_jac<true, LOSS_HUBER, LossArgs>) : loss_kernel(k_resid_jac<false>, k_resid_jac<false, LOSS_HUBER, LossArgs>);
 }
+auto cost_kernel(bool gcam, int loss) {
+  if (loss == LOSS_CAUCHY)
+    return gcam ? loss_kernel(k_cost<true>, k_cost<true, LOSS_CAUCHY, LossArgs>) : loss_kernel(k_cost<false>, k_cost<false, LOSS_CAUCHY, LossArgs>);
+  return gcam ? loss_kernel(k_cost<true>, k_cost<true, LOSS_HUBER, LossArgs>) : loss_kernel(k_cost<false>, k_cost<false, LOSS_HUBER, LossArgs>);
+}
+// K5: G lanes per point, bt threads per block (256 whenever the camera tables are in device memory)
+template <int G>
+auto backsub_kernel_g(int bt, bool gcam) {
+  if (gcam) return loss_kernel(k_backsub<G, 256, true>, k_backsub<G, 256, true, true, LossArgs>);
+  if (bt == 1024) return loss_kernel(k_backsub<G, 1024>, k_backsub<G, 1024, false, true, LossArgs>);
+  if (bt == 512) return loss_kernel(k_backsub<G, 512>, k_backsub<G, 512, false, true, LossArgs>);
+  return loss_kernel(k_backsub<G>, k_backsub<G, 256, false, true, LossArgs>);
+}
+auto backsub_kernel(int G, int bt, bool gcam) {
+  return G == 2 ? backsub_kernel_g<2>(bt, gcam) : (G == 4 ? backsub_kernel_g<4>(bt, gcam) : backsub_kernel_g<8>(bt, gcam));
+}
+// K3, dense form: T tiles of 16 across the 9 m camera parameters; table: a point's records through d_dense_obs
+template <int T>
+auto dense_kernel_t(bool table) {
+  return table ? loss_kernel(k_schur_dense<T, true>, k_schur_dense<T, true, true, LossArgs>)
+               : loss_kernel(k_schur_dense<T, false>, k_schur_dense<T, false, true, LossArgs>);
+}
+auto dense_kernel(int T, bool table) {
+  switch (T) {
+    case 1: return dense_kernel_t<1>(table);
+    case 2: return dense_kernel_t<2>(table);
+    case 3: return dense_kernel_t<3>(table);
+    case 4: return dense_kernel_t<4>(table);
+    case 5: return dense_kernel_t<5>(table);
+    case 6: return dense_kernel_t<6>(table);
+    case 7: return dense_kernel_t<7>(table);
+    case 8: return dense_kernel_t<8>(table);
+    case 9: return dense_kernel_t<9>(table);
+    case 10: return dense_kernel_t<10>(table);
+    case 11: return dense_kernel_t<11>(table);
+    default: return dense_kernel_t<12>(table);
+  }
+}
+// its dynamic LDS for mm cameras (the launch: the engine's m; the attribute: the largest camera count of the instantiation)
+size_t dense_lds_bytes(int T, int mm) {
+  const int CH = dense_ch(T);
+  return sizeof(double) * ((size_t)2 * 3 * CH * 16 * T + (size_t)2 * CH * mm * 32) + sizeof(double2) * CH * ((size_t)mm * REC + 8) +
+         sizeof(double) * (CH * (size_t)mm + 2 * 3 * CH);
+}
+
+// dynamic LDS of K1 (the camera table, padded to 16 bytes, and 8 KiB of staging per wave) and of the kernels that hold the
+// camera table alone (k_cost, k_residuals) or beside the camera steps (k_backsub); nothing once the tables are in device memory
+size_t k1_lds_bytes(int m, bool gcam, int threads) {
+  return (size_t)((gcam ? 0 : ((m * CAM_LDS + 1) & ~1)) + (threads / 64) * 64 * 2 * REC) * sizeof(double);
+}
+size_t cam_lds_bytes(int m, bool gcam, bool with_dxi) { return gcam ? 0 : (size_t)m * (CAM_LDS + (with_dxi ? DXI_LDS : 0)) * sizeof(double); }
 
 // the camera tables in device memory for the kernels that cannot hold them in LDS (no-op up to LDS_CAMERAS cameras)
 void cam_tables(mvba_handle *h, const double *cam15, const double *dxi) {
   if (h->gcam) hipLaunchKernelGGL(k_cam_tables, dim3((h->m + 255) / 256), dim3(256), 0, h->stream, h->m, cam15, dxi, h->f0, h->d_cam18, h->d_dxi10);
 }
-void launch_cost_kernel(mvba_handle *h, const double *cam15, const double *X) {
-  const size_t lds = h->gcam ? 0 : (size_t)h->m * CAM_LDS * sizeof(double);
+// the cost pass at a given state and the sum of its partials (into d_cost, and the mailbox when there is one)
+int launch_cost(mvba_handle *h, const double *cam15, const double *X) {
+  const size_t lds = cam_lds_bytes(h->m, h->gcam, false);
   cam_tables(h, cam15, nullptr);
   // (512 threads once the camera table leaves room for two blocks per CU only: config 4's 500 cameras)
-  if (h->loss != LOSS_SQUARED)
-    hipLaunchKernelGGL(cost_robust(h->gcam, h->loss), dim3(h->cost_grid), dim3(lds > 40 * 1024 ? 512 : 256), lds, h->stream, h->nobs, h->m, cam15, X,
-                       h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_partials, h->d_cam18, LossArgs{h->loss_b, h->d_sqw});
-  else
-  hipLaunchKernelGGL(h->gcam ? k_cost<true> : k_cost<false>, dim3(h->cost_grid), dim3(lds > 40 * 1024 ? 512 : 256), lds, h->stream, h->nobs, h->m, cam15, X,
-                     h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_partials, h->d_cam18);
-}
-int launch_cost(mvba_handle *h, const double *cam15, const double *X) {
-  Timed t(h, MVBA_K_COST);
-  launch_cost_kernel(h, cam15, X);
+  launch_loss(h, cost_kernel(h->gcam, h->loss), dim3(h->cost_grid), dim3(lds > 40 * 1024 ? 512 : 256), lds, h->nobs, h->m, cam15, X,
+              h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_partials, h->d_cam18);
   double *mail = cost_mail(h);  // (advances cost_seq: sequenced before the launch reads it)
   const unsigned long long seq = h->cost_seq;
   hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, h->stream, h->d_partials, h->cost_grid, h->d_cost, h->d_flag, mail, seq);
   MVBA_HIP(hipGetLastError());
   return MVBA_OK;
 }
-
-// mvba_create, xy_layout 1: the observations of a fully visible scene arrive as image planes [m][N] and leave in observation
-// order [N][m] (a wave reads 1 KiB of one plane and writes 64 records m * 16 bytes apart; once per engine)
-__global__ __launch_bounds__(256) void k_xy_from_planes(const double2 *__restrict__ planes, long long N, int m, double2 *__restrict__ xy) {
-  const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int k = blockIdx.y;
-  if (a < N) xy[a * m + k] = planes[(long long)k * N + a];
-}
-
-// Tuning of the slot form's host-built schedule (k_schur_slots), in observations of a point range
-constexpr long long SLOT_SKEW = 12288;  // bounded skew of the step merge
-constexpr long long SLOT_SEG = 8192;    // pacing segment
-constexpr int SLOT_LAG = 4;             // a wave enters segment j only when all waves of its range have left segment j - lag
 
 // The environment knobs of mvba_create (README.md lists them), read once.  Each pins a choice the engine otherwise makes
 // by itself, or turns on a diagnostic that changes no result.
@@ -3224,6 +3301,8 @@ CreateKnobs read_create_knobs() {
   return k;
 }
 
+#include "mvba_create.h"  // engine creation as stages: create_engine()
+
 }  // namespace
 
 extern "C" {
@@ -3242,733 +3321,6 @@ int mvba_device_count(int32_t *count) {
   *count = n;
   return MVBA_OK;
 }
-
-namespace {
-int create_engine(const mvba_problem *p, int loss, double loss_b, mvba_handle **out) {
-  if (!p || !out) return fail(MVBA_ERR_BADARG, "null argument");
-  const CreateKnobs knobs = read_create_knobs();
-  // MVBA_CREATE_TIMING=1: wall time of this function's stages on stderr (tools/time_create.py; the engine's construction is a
-  // third of the reference's pipeline at 1 M points x 12 images)
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (!knobs.timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "mvba_create: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  if (p->n_points < 0 || p->n_images < 2 || p->n_obs < 0 || !p->pt_ptr || (p->n_obs && (!p->cam_idx || !p->xy)))
-    return fail(MVBA_ERR_BADARG, "bad problem sizes or null arrays (need n_images >= 2)");
-  if (p->gauge_axis != 0 && p->gauge_axis != 1) return fail(MVBA_ERR_BADARG, "gauge_axis must be 0 or 1");
-  if (p->xy_layout != 0 && p->xy_layout != 1) return fail(MVBA_ERR_BADARG, "xy_layout must be 0 (observation order) or 1 (image planes)");
-  if (p->xy_layout == 1 && p->n_obs != p->n_points * (int64_t)p->n_images)
-    return fail(MVBA_ERR_BADARG, "xy as image planes needs every point observed in every image (n_obs = n_points * n_images)");
-  // the kernels keep the whole camera table in LDS (K1: 18 doubles per camera + 8 x 8 KiB of wave
-  // tiles; back-substitution: 28 per camera): 160 KiB per workgroup caps the camera count.  (The documented limit is
-  // round 1's, from 19 doubles per camera; 18 would admit 682.)
-  static_assert(LDS_CAMERAS * CAM_LDS + 8 * 64 * 2 * 8 + 2 <= 160 * 1024 / 8 && LDS_CAMERAS * (CAM_LDS + DXI_LDS) <= 160 * 1024 / 8,
-                "the camera tables of LDS_CAMERAS cameras fit one workgroup's LDS");
-  // (beyond LDS_CAMERAS the same kernels read the tables from device memory -- round 5; what caps the count now is the dense
-  // reduced system: D = 9 m - 7 = 36,857 at 4096 cameras is 10.9 GB of matrix, and the unit descriptors keep camera ids in 16 bits)
-  constexpr int MAX_CAMERAS = 4096;
-  if (p->n_images > MAX_CAMERAS)
-    return fail(MVBA_ERR_BADARG, "n_images = " + std::to_string(p->n_images) + " exceeds the " + std::to_string(MAX_CAMERAS) +
-                                     " cameras this build solves a dense reduced system for");
-  if (p->pt_ptr[0] != 0 || p->pt_ptr[p->n_points] != p->n_obs) return fail(MVBA_ERR_BADARG, "pt_ptr does not span n_obs");
-  if (p->n_obs >= (1LL << 31) || p->n_points >= (1LL << 31))
-    return fail(MVBA_ERR_BADARG, "n_obs and n_points per handle must be < 2^31");
-  const long long N = p->n_points, nobs = p->n_obs;
-  const int m = p->n_images;
-  // validate + build point-of-observation
-  std::vector<int> obs_pt(nobs);
-  for (long long a = 0; a < N; ++a) {
-    const long long o0 = p->pt_ptr[a], o1 = p->pt_ptr[a + 1];
-    if (o1 < o0 || o1 > nobs) return fail(MVBA_ERR_BADARG, "pt_ptr not monotone / out of range");
-    for (long long o = o0; o < o1; ++o) {
-      const int k = p->cam_idx[o];
-      if (k < 0 || k >= m) return fail(MVBA_ERR_BADARG, "cam_idx out of range");
-      if (o > o0 && p->cam_idx[o - 1] >= k) return fail(MVBA_ERR_BADARG, "cam_idx must ascend within a point");
-      obs_pt[o] = (int)a;
-    }
-  }
-  lap("validate, obs_pt");
-  // K1 wave tiles: whole points packed greedily into <= 64 observations; a point with more than
-  // 64 observations is cut into pieces whose tiles are flagged by a complemented (negative) start
-  std::vector<int> tiles, tile_slot;
-  std::vector<int4> splits;
-  int n_split_slots = 0;
-  bool any_split = false;
-  {
-    long long cur0 = 0, fill = 0;
-    auto flush = [&](bool split_flag) { tiles.push_back(split_flag ? ~(int)cur0 : (int)cur0); };
-    for (long long a = 0; a < N; ++a) {
-      const long long d = p->pt_ptr[a + 1] - p->pt_ptr[a];
-      if (d > 64) {
-        if (fill) { flush(false); cur0 += fill; fill = 0; }
-        any_split = true;
-        splits.push_back(make_int4((int)a, n_split_slots, (int)((d + 63) / 64), 0));
-        for (long long q = 0; q < d; q += 64) {
-          tile_slot.resize(tiles.size() + 1, -1);
-          tile_slot[tiles.size()] = n_split_slots++;
-          flush(true);
-          cur0 += std::min<long long>(64, d - q);
-        }
-        continue;
-      }
-      if (fill + d > 64) { flush(false); cur0 += fill; fill = 0; }
-      fill += d;
-    }
-    if (fill) { flush(false); cur0 += fill; }
-    tiles.push_back((int)nobs);  // terminator (never negative: only its magnitude is used)
-  }
-
-  lap("K1 tiles");
-  mvba_handle *h = new mvba_handle();
-  if (p->device >= 0) {
-    hipError_t e = hipSetDevice(p->device);
-    if (e != hipSuccess) { delete h; return fail(MVBA_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)); }
-  }
-  {
-    hipError_t e = hipGetDevice(&h->device);
-    if (e != hipSuccess) { delete h; return fail(MVBA_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e)); }
-  }
-  h->N = N; h->nobs = nobs; h->m = m; h->gauge_axis = p->gauge_axis; h->f0 = p->f0; h->D = 9 * m - 7; h->ld = (h->D + 3) & ~3;
-  h->loss = loss; h->loss_b = loss_b;
-  h->gcam = m > LDS_CAMERAS;
-#define TRY(x) do { int rc_ = (x); if (rc_) { mvba_destroy(h); return rc_; } } while (0)
-#define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { mvba_destroy(h); return fail(MVBA_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-  // the topology goes up first: the Schur index is built from it on the device
-  TRYH(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  TRY(dmalloc(&h->d_pt_ptr, N + 1));
-  TRY(dmalloc(&h->d_cam, nobs));
-  TRYH(hipMemcpy(h->d_pt_ptr, p->pt_ptr, sizeof(long long) * (N + 1), hipMemcpyHostToDevice));
-  if (nobs) TRYH(hipMemcpy(h->d_cam, p->cam_idx, sizeof(int) * nobs, hipMemcpyHostToDevice));
-  lap("device, topology upload");
-  {  // K1: the waves of a block share one camera table in LDS and bring 8 KiB of staging each.  Up to ~100 cameras two blocks
-    // of 8 waves fill a CU (16 waves: the register limit); beyond that ONE block fits and its size decides the occupancy --
-    // the smallest block that reaches the most waves per CU (200 cameras: 16 waves, 0.96 -> 0.70 ms at 1 M points x 10 %;
-    // 300: 14, 0.41 -> 0.32-0.37; 500: 11, config 4's shard 1.53-1.58 -> 1.32-1.36)
-    const size_t table = h->gcam ? 0 : (size_t)((m * CAM_LDS + 1) & ~1) * sizeof(double), per_wave = 64 * 2 * REC * sizeof(double);
-    int best_w = 8, best_tot = 0;
-    for (int w = 8; w <= 16; ++w) {
-      const size_t per = table + w * per_wave;
-      if (per > 160 * 1024) break;
-      const int tot = std::min<int>(16, (int)(160 * 1024 / per) * w);
-      if (tot > best_tot) { best_tot = tot; best_w = w; }
-    }
-    h->k1_threads = 64 * best_w;
-  }
-  // ---- pair-major Schur index (see k_schur_pairs).  Items (obs of k, obs of l, point) for every
-  // pair k <= l of a point's cameras, counting-sorted by pair, ascending point inside a pair.
-  // (a robust loss never takes the slot form: the unit form then, as when the lists do not fit one round -- DESIGN.md §12)
-  h->schur_mode = knobs.schur_pairs || loss != LOSS_SQUARED ? SCHUR_PAIRS : SCHUR_SLOTS;
-  h->force_big = knobs.force_big;
-  h->check_solve = knobs.check_solve;
-  h->check_solve_tol = knobs.check_solve_tol;
-  std::vector<int> dense_obs;  // SCHUR_DENSE with missing observations: [N][m] observation of (point, camera) or -1
-  {  // up to 21 cameras and most (point, camera) pairs observed: the dense form (no pair index).  Full visibility in camera order
-     // (the reference's own scenes): a point's records are read as one contiguous range; otherwise through a table, a missing
-     // observation standing as a zero record (the matrix cores multiply the zeros: worth it from ~60 % visibility on)
-    bool few = m >= 1 && 9 * m <= 16 * DENSE_MAX_TILES && N > 0, full = few && nobs == N * (long long)m;
-    for (long long a = 0; a < N && full; ++a) {
-      if (p->pt_ptr[a + 1] - p->pt_ptr[a] != m) { full = false; break; }
-      const int *ci = p->cam_idx + p->pt_ptr[a];
-      for (int k = 0; k < m; ++k)
-        if (ci[k] != k) { full = false; break; }
-    }
-    const bool forced = knobs.schur_dense;
-    bool masked = few && !full && (forced || (!knobs.schur_set && (double)nobs >= 0.6 * (double)N * m)) && (long long)N * m < (1LL << 31);
-    if (masked) {
-      dense_obs.assign((size_t)N * m, -1);
-      for (long long a = 0; a < N && masked; ++a)
-        for (long long o = p->pt_ptr[a]; o < p->pt_ptr[a + 1]; ++o) {
-          int &slot = dense_obs[(size_t)a * m + p->cam_idx[o]];
-          if (slot >= 0) { masked = false; break; }  // (a camera twice in one point: the pair-major forms take such scenes)
-          slot = (int)o;
-        }
-      if (!masked) dense_obs.clear();
-    }
-    if ((full && (!knobs.schur_set || forced)) || masked) h->schur_mode = SCHUR_DENSE;
-  }
-  lap("form of K3");
-  h->use_pairs = h->schur_mode != SCHUR_DENSE;
-  std::vector<int> it_k, it_l, it_a, unit_ptr, q_ptr(9, 0), q_units, st_k, st_l, st_a, wunits, seg_end;
-  std::vector<int4> units, wdesc;
-  if (h->use_pairs) {
-    const long long P = (long long)m * (m + 1) / 2;
-    auto pair_id = [m](int k, int l) { return (long long)k * m - (long long)k * (k - 1) / 2 + (l - k); };
-    std::vector<long long> cnt(P, 0);
-    // Both passes over the points run on host threads that OWN strips (camera k belongs to thread
-    // k % n_thr): every thread scans the whole observation list but touches only its own pairs, so
-    // there is nothing to lock and the order inside a pair's list stays ascending by point.
-    const int n_thr = (int)std::max(1u, std::min({std::thread::hardware_concurrency(), 16u, (unsigned)m}));
-    auto on_threads = [&](auto body) {
-      std::vector<std::thread> th;
-      for (int t = 1; t < n_thr; ++t) th.emplace_back(body, t);
-      body(0);
-      for (auto &x : th) x.join();
-    };
-    // The index is built on the DEVICE (k_idx_*): a stable counting sort by pair, every wave walking its own chunk of
-    // points with a private pair histogram -- in LDS when P ints x 4 waves per block fit (up to ~138 cameras), else in
-    // the wave's own row of a device buffer (at most 2 GiB of rows: 4096 waves at 500 cameras).  MVBA_INDEX=host keeps
-    // the host threads, MVBA_INDEX=global forces the device-memory histogram (the tests that the builds are identical).
-    const bool hist_lds = (size_t)P * sizeof(int) * IDX_WAVES <= 150 * 1024 && !knobs.index_global;
-    const bool dev_build = N > 0 && nobs > 0 && !knobs.index_host;
-    const long long max_idx_waves = hist_lds ? 4096 : std::max<long long>(IDX_WAVES, std::min<long long>(4096, (2LL << 30) / (4 * P)));
-    const int idx_chunk = (int)std::max<long long>(32, (N + max_idx_waves - 1) / max_idx_waves);  // points per wave
-    const long long idx_waves = dev_build ? ((N + idx_chunk - 1) / idx_chunk + IDX_WAVES - 1) / IDX_WAVES * IDX_WAVES : 0;
-    const size_t idx_lds = hist_lds ? P * sizeof(int) * IDX_WAVES : 0;
-    int *d_hist = nullptr;
-    long long *d_cnt = nullptr;
-    if (dev_build) {
-      TRY(dmalloc(&d_hist, (size_t)idx_waves * P));
-      TRY(dmalloc(&d_cnt, (size_t)P));
-      if (hist_lds) {
-        TRYH(hipFuncSetAttribute((const void *)k_idx_count<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)idx_lds));
-        TRYH(hipFuncSetAttribute((const void *)k_idx_fill<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)idx_lds));
-      } else {
-        TRYH(hipMemsetAsync(d_hist, 0, sizeof(int) * (size_t)idx_waves * P, h->stream));
-      }
-      hipLaunchKernelGGL(hist_lds ? k_idx_count<false> : k_idx_count<true>, dim3((unsigned)(idx_waves / IDX_WAVES)), dim3(64 * IDX_WAVES), idx_lds,
-                         h->stream, N, m, (int)P, h->d_pt_ptr, h->d_cam, idx_chunk, d_hist, (const int *)nullptr);
-      hipLaunchKernelGGL(k_idx_scan, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, (int)P, (int)idx_waves, d_hist, d_cnt);
-      TRYH(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(long long) * P, hipMemcpyDeviceToHost, h->stream));
-      TRYH(hipStreamSynchronize(h->stream));
-    } else
-    on_threads([&](int tid) {
-      for (long long a = 0; a < N; ++a) {
-        const int *cb = p->cam_idx + p->pt_ptr[a];
-        const int d = (int)(p->pt_ptr[a + 1] - p->pt_ptr[a]);
-        for (int i = 0; i < d; ++i) {
-          if (cb[i] % n_thr != tid) continue;
-          long long *row = cnt.data() + pair_id(cb[i], cb[i]) - cb[i];  // row[l] = cnt[pair(k, l)]
-          for (int j = i; j < d; ++j) row[cb[j]]++;
-        }
-      }
-    });
-    lap("pair counts");
-    long long T = 0, Tdiag = 0;
-    for (int k = 0; k < m; ++k) Tdiag += cnt[pair_id(k, k)];
-    for (long long q = 0; q < P; ++q) T += cnt[q];
-    if (T >= (1LL << 40)) { mvba_destroy(h); return fail(MVBA_ERR_BADARG, "too many (point, camera pair) items"); }
-    // a pair much larger than the typical off-diagonal one (the diagonal pairs: every observation of
-    // the camera) is dealt round-robin into S sub-lists that sweep the points at the common pace
-    const long long target = std::max<long long>(1, (T - Tdiag) / std::max<long long>(1, P - m));
-    // items per unit (a wave's run): shorter units keep the sibling units of a strip closer together in time (more L2
-    // hits on the k side) but cost a serial prologue and a 27-value tree each.  With one-wave blocks and static
-    // assignment the best length is ~600 (config 3: 1.99 / 1.86 / 1.80 / 1.81 / 1.89 / 2.03 ms at 320 / 448 / 576 /
-    // 640 / 768 / 1024; with four-wave blocks and atomic queues it was 768)
-    // Round 4, re-swept where the unit form actually runs (beyond one round of the slot form): the sparser the pairs, the longer
-    // the stretch of points a unit of U items spans (U / p^2) and the further its siblings drift apart -- config 4's shard (5 %):
-    // 14.40 / 13.89 / 13.99 / 14.49 / 15.6 ms at 600 / 400 / 300 / 250 / 200 (L2 misses 743 M -> 553 M at 300, the per-unit
-    // prologue and tree eat the rest); 1 M x 200 x 10 %: 6.21 / 6.61 / 7.12 at 600 / 400 / 300; 300 k x 300 x 5 %: 1.37 / 1.23 / 1.23
-    // (profiles/r04_sweep_pairs_unit.txt).  So: 600 at one item per pair per 100 points, 400 at one per 400.
-    // (Two gathers in flight -- this form on the slot kernel's ring loop -- make it SLOWER, 15.5 ms: the wider window of
-    // points misses L2 more often, profiles/r04_sweep_pairs_ring.txt.)
-    const double pair_rate = N > 0 && P > m ? (double)(T - Tdiag) / ((double)(P - m) * (double)N) : 0.01;
-    const long long unit_items = (long long)std::max(300.0, std::min(600.0, 200.0 + 4000.0 * std::sqrt(pair_rate)));
-    std::vector<int> S(P), vp_ptr(P + 1, 0);
-    for (long long q = 0; q < P; ++q) {
-      S[q] = (int)std::max<long long>(1, std::min<long long>(256, (cnt[q] + target / 2) / target));
-      vp_ptr[q + 1] = vp_ptr[q] + S[q];
-    }
-    const int VP = vp_ptr[P];
-    // ---- which form of the kernel: the slot-resident one (k_schur_slots) needs all lists that sweep a point range
-    // TOGETHER resident on one XCD at once -- 9 waves per CU (LDS) x n_cu / 8 CUs x 21 slots = 6048 lists.  Up to ~100
-    // cameras at 10 % visibility (4950 pairs + ~1000 sub-lists of the diagonal pairs) that is every list.  Beyond that
-    // the engine takes the unit form (cutting the cameras into groups swept in rounds lost to it on every workload
-    // measured: DESIGN.md 3.1, "Round 4").
-    int n_cu_dev = 256;
-    hipDeviceGetAttribute(&n_cu_dev, hipDeviceAttributeMultiprocessorCount, h->device);
-    const int xcd_waves = std::max(1, n_cu_dev / 8) * (160 * 1024 / SLOT_LDS);  // 9 waves of 17,136 B of LDS per CU
-    long long n_diag_lists = 0, n_off_lists = 0;
-    for (int k = 0; k < m; ++k) {
-      n_diag_lists += S[pair_id(k, k)];
-      for (int l = k + 1; l < m; ++l) n_off_lists += S[pair_id(k, l)];
-    }
-    // waves (of 21 lists) per range: diagonal + off-diagonal
-    const long long slot_waves = (n_diag_lists + PSTEP - 1) / PSTEP + (n_off_lists + PSTEP - 1) / PSTEP;
-    // (below ~4 M items the launch is all prologue and pacing: the unit form's many short waves win -- config 2,
-    // 10k points x 20 cameras: 0.095 against 0.124 ms; equal at 5.5 M items; MVBA_SCHUR=slots keeps the slot form)
-    const bool slots_forced = knobs.schur_slots;
-    // (the gathers use 32-bit byte offsets: point rows from the array's start, records from their RANGE's first
-    // observation -- checked below, once the ranges are known)
-    if (h->schur_mode == SCHUR_SLOTS && (slot_waves > xcd_waves || (N + 1) * 128LL >= (1LL << 32) || h->force_big ||
-                                         (T < 4000000 && !slots_forced)))
-      h->schur_mode = SCHUR_PAIRS;
-    // point ranges.  Unit form: long runs for big problems, but small ones still get ~4096 units of >= 128 items.
-    // Slot form: 8 ranges (one per XCD) -- 8 j while j ranges' worth of waves fit an XCD and a list keeps >= 64 items.
-    int nR = 1;
-    std::vector<long long> range_lo;
-    auto make_ranges = [&]() {
-      if (h->schur_mode == SCHUR_SLOTS) {
-        const long long j = std::max<long long>(1, std::min<long long>(xcd_waves / std::max(1LL, slot_waves), target / (8 * 64)));
-        nR = (int)(8 * std::min<long long>(j, 8));
-        range_lo.assign(nR + 1, 0);
-        // equal ITEM counts: the ranges run side by side, one per XCD
-        std::vector<long long> pre(N + 1, 0);
-        for (long long a = 0; a < N; ++a) {
-          const long long d = p->pt_ptr[a + 1] - p->pt_ptr[a];
-          pre[a + 1] = pre[a] + d * (d + 1) / 2;
-        }
-        for (int r = 0; r <= nR; ++r)
-          range_lo[r] = std::lower_bound(pre.begin(), pre.end(), (long long)((__int128)pre[N] * r / nR)) - pre.begin();
-        range_lo[0] = 0; range_lo[nR] = N;
-      } else {
-        const long long nR_big = (target + unit_items / 2) / unit_items, nR_fill = std::min<long long>((4096 + VP - 1) / VP, target / 128);
-        nR = (int)std::max<long long>(1, std::min<long long>(64, std::max(nR_big, nR_fill)));
-        range_lo.assign(nR + 1, 0);
-        for (int r = 0; r <= nR; ++r) range_lo[r] = (long long)((__int128)N * r / nR);
-      }
-    };
-    make_ranges();
-    // (few cameras with dense visibility: a dozen cameras are 78 lists = 5 waves per range, 320 waves on the whole chip even with 64
-    // ranges -- 1 M points x 12 cameras, all visible: 9.3 ms against 4.9 for the unit form; at 20 cameras, 704 waves, the slot form is
-    // ahead again, 9.8 against 10.8: profiles/r05_sweep_few_cameras.txt)
-    if (h->schur_mode == SCHUR_SLOTS && !slots_forced && nR * slot_waves < 512) {
-      h->schur_mode = SCHUR_PAIRS;
-      make_ranges();
-    }
-    if (h->schur_mode == SCHUR_SLOTS) {
-      long long widest = 0;
-      for (int r = 0; r < nR; ++r) widest = std::max<long long>(widest, p->pt_ptr[range_lo[r + 1]] - p->pt_ptr[range_lo[r]]);
-      if ((widest + 1) * 128LL >= (1LL << 32)) {  // a range's records span 4 GiB: the unit form's 64-bit-offset build
-        h->schur_mode = SCHUR_PAIRS;
-        make_ranges();
-      }
-    }
-    const bool slots = h->schur_mode == SCHUR_SLOTS;
-    // The points are swept in their natural order: an item's key (where its point sits in the sweep, in observations) is its
-    // point's first observation, pt_ptr[a].  (A low-discrepancy order -- round 4 -- cut the padding rows from 12.4 % to 10.4 %
-    // at config 3 but k_schur_slots only from 1.691 to 1.677 ms, for 0.12 s more of mvba_create: profiles/r04_sweep_point_order.txt.)
-    std::vector<long long> vp_off(VP + 1, 0);
-    for (long long q = 0; q < P; ++q)
-      for (int sI = 0; sI < S[q]; ++sI) vp_off[vp_ptr[q] + sI + 1] = (cnt[q] - sI + S[q] - 1) / S[q];
-    for (int v = 0; v < VP; ++v) vp_off[v + 1] += vp_off[v];
-    int *d_pk = nullptr, *d_pl = nullptr, *d_pa = nullptr, *d_S = nullptr, *d_vp_ptr = nullptr;
-    long long *d_vp_off = nullptr;
-    auto free_dev_tmp = [&]() {
-      for (void *q : {(void *)d_hist, (void *)d_cnt, (void *)d_pk, (void *)d_pl, (void *)d_pa, (void *)d_S, (void *)d_vp_ptr, (void *)d_vp_off})
-        if (q) hipFree(q);
-      d_hist = nullptr; d_cnt = nullptr; d_pk = d_pl = d_pa = d_S = d_vp_ptr = nullptr; d_vp_off = nullptr;
-    };
-    if (dev_build) {
-      TRY(dmalloc(&d_pk, (size_t)T)); TRY(dmalloc(&d_pl, (size_t)T)); TRY(dmalloc(&d_pa, (size_t)T));
-      TRY(dmalloc(&d_S, (size_t)P)); TRY(dmalloc(&d_vp_ptr, (size_t)P + 1)); TRY(dmalloc(&d_vp_off, (size_t)VP + 1));
-      TRYH(hipMemcpyAsync(d_S, S.data(), sizeof(int) * P, hipMemcpyHostToDevice, h->stream));
-      TRYH(hipMemcpyAsync(d_vp_ptr, vp_ptr.data(), sizeof(int) * (P + 1), hipMemcpyHostToDevice, h->stream));
-      TRYH(hipMemcpyAsync(d_vp_off, vp_off.data(), sizeof(long long) * (VP + 1), hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(hist_lds ? k_idx_fill<false> : k_idx_fill<true>, dim3((unsigned)(idx_waves / IDX_WAVES)), dim3(64 * IDX_WAVES), idx_lds,
-                         h->stream, N, m, (int)P, h->d_pt_ptr, h->d_cam, idx_chunk, d_hist, d_S, d_vp_ptr, d_vp_off, d_pk, d_pl, d_pa,
-                         (const int *)nullptr);
-      TRYH(hipGetLastError());
-    } else {
-    it_k.resize(T); it_l.resize(T); it_a.resize(T);
-    {
-      std::vector<long long> run(P, 0);
-      on_threads([&](int tid) {
-        for (long long a = 0; a < N; ++a) {
-          const long long o0 = p->pt_ptr[a];
-          const int *cb = p->cam_idx + o0;
-          const int d = (int)(p->pt_ptr[a + 1] - o0);
-          for (int i = 0; i < d; ++i) {
-            if (cb[i] % n_thr != tid) continue;
-            const long long rowp = pair_id(cb[i], cb[i]) - cb[i];
-            for (int j = i; j < d; ++j) {
-              const long long q = rowp + cb[j], r = run[q]++;
-              const int sI = (int)(r % S[q]);
-              const long long pos = vp_off[vp_ptr[q] + sI] + r / S[q];
-              it_k[pos] = (int)(o0 + i); it_l[pos] = (int)(o0 + j); it_a[pos] = (int)a;
-            }
-          }
-        }
-      });
-    }
-    }
-    lap("items sorted by pair");
-    // units: (pair, sub-list, point range), numbered pair-major (k_schur_reduce sums them in this order)
-    unit_ptr.assign(P + 1, 0);
-    std::vector<int> uid((size_t)VP * nR, -1);
-    std::vector<long long> lo_tab;  // device build: lower bounds of every list at every range boundary
-    if (dev_build) {
-      long long *d_rl = nullptr, *d_lo = nullptr;
-      TRY(dmalloc(&d_rl, (size_t)nR + 1)); TRY(dmalloc(&d_lo, (size_t)VP * (nR + 1)));
-      TRYH(hipMemcpyAsync(d_rl, range_lo.data(), sizeof(long long) * (nR + 1), hipMemcpyHostToDevice, h->stream));
-      const long long nt = (long long)VP * (nR + 1);
-      hipLaunchKernelGGL(k_idx_bounds, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, VP, nR, d_vp_off, d_rl, d_pa, d_lo, (const int *)nullptr);
-      lo_tab.resize(nt);
-      TRYH(hipMemcpyAsync(lo_tab.data(), d_lo, sizeof(long long) * nt, hipMemcpyDeviceToHost, h->stream));
-      TRYH(hipStreamSynchronize(h->stream));
-      hipFree(d_rl); hipFree(d_lo);
-    }
-    for (int k = 0; k < m; ++k)
-      for (int l = k; l < m; ++l) {
-        const long long q = pair_id(k, l);
-        unit_ptr[q] = (int)units.size();
-        for (int sI = 0; sI < S[q]; ++sI) {
-          const int v = vp_ptr[q] + sI;
-          const int *b = it_a.data() + (dev_build ? 0 : vp_off[v]), *e = it_a.data() + (dev_build ? 0 : vp_off[v + 1]);
-          for (int r = 0; r < nR; ++r) {
-            auto before = [](int a, long long key) { return (long long)a < key; };
-            const long long lo = dev_build ? lo_tab[(size_t)v * (nR + 1) + r] : std::lower_bound(b, e, range_lo[r], before) - it_a.data();
-            const long long hi = dev_build ? lo_tab[(size_t)v * (nR + 1) + r + 1] : std::lower_bound(b, e, range_lo[r + 1], before) - it_a.data();
-            if (hi <= lo) continue;
-            uid[(size_t)v * nR + r] = (int)units.size();
-            units.push_back(make_int4((int)(lo & 0xffffffffLL), (int)(lo >> 32), (int)(hi - lo), (k << 16) | l));
-          }
-        }
-      }
-    unit_ptr[P] = (int)units.size();
-    lap("units");
-    if (slots) {
-      // ---- waves of 21 lists, every wave once per range; the diagonal pairs' sub-lists come FIRST: a CU's SIMDs
-      // arbitrate by age, the blocks dispatched last share a SIMD three ways as its youngest wave and fall behind --
-      // and a diagonal step is the dearer one
-      std::vector<int> wl;                    // [wave of a range][21] list ids v = vp_ptr[pair] + sub-list, -1: none
-      std::vector<int> w_isdiag;              // per wave of a range
-      std::vector<int> diag_lists, off_lists;
-      for (int k = 0; k < m; ++k) {
-        for (int sI = 0; sI < S[pair_id(k, k)]; ++sI) diag_lists.push_back(vp_ptr[pair_id(k, k)] + sI);
-        for (int l = k + 1; l < m; ++l)
-          for (int sI = 0; sI < S[pair_id(k, l)]; ++sI) off_lists.push_back(vp_ptr[pair_id(k, l)] + sI);
-      }
-      for (const std::vector<int> *src : {&diag_lists, &off_lists})
-        for (size_t first = 0; first < src->size(); first += PSTEP) {
-          for (int sl = 0; sl < PSTEP; ++sl) wl.push_back(first + sl < src->size() ? (*src)[first + sl] : -1);
-          w_isdiag.push_back(src == &diag_lists);
-        }
-      const int wpr = (int)w_isdiag.size();   // waves per range
-      const long long n_waves = (long long)wpr * nR;
-      wdesc.assign(n_waves, make_int4(0, 0, 0, 0));
-      wunits.assign((size_t)n_waves * PSTEP, -1);
-      std::vector<long long> w_steps(n_waves, 0), w_beg(n_waves + 1, 0);
-      // block b = nR w + r: wave w of range r runs on XCD r % 8
-      auto wave_lists = [&](long long b, int *vs) {  // the 21 list ids of block b (-1: none); returns the range
-        const int *src = wl.data() + (size_t)(b / nR) * PSTEP;
-        for (int sl = 0; sl < PSTEP; ++sl) vs[sl] = src[sl];
-        return (int)(b % nR);
-      };
-      // Bounded-skew merge of a wave's lists into steps (see k_schur_slots)
-      const long long skew = SLOT_SKEW;
-      // pacing segments: seg_end[b][j] = steps wave b has taken when its slowest slot leaves segment j of the range
-      const long long segG = SLOT_SEG;
-      int nSeg = 1;
-      for (int r = 0; r < nR; ++r)
-        nSeg = std::max<long long>(nSeg, (p->pt_ptr[range_lo[r + 1]] - p->pt_ptr[range_lo[r]] + segG - 1) / segG);
-      seg_end.assign((size_t)n_waves * nSeg, 0);
-      h->slot_nseg = nSeg;
-      auto merge = [&](long long b, long long base, bool fill) {
-        int vs[PSTEP];
-        const int r = wave_lists(b, vs);
-        long long cur[PSTEP], end[PSTEP];
-        for (int sl = 0; sl < PSTEP; ++sl) {
-          const int id = vs[sl] >= 0 ? uid[(size_t)vs[sl] * nR + r] : -1;
-          if (id < 0) { cur[sl] = end[sl] = 0; continue; }
-          cur[sl] = ((long long)units[id].y << 32) | (unsigned)units[id].x;
-          end[sl] = cur[sl] + units[id].z;
-          if (fill) wunits[(size_t)b * PSTEP + sl] = id;
-        }
-        long long steps = 0;
-        const long long o_lo = p->pt_ptr[range_lo[r]];
-        int sg = 0;
-        auto key_of = [&](int sl) { return p->pt_ptr[it_a[cur[sl]]]; };  // where the item's point sits in the sweep, in observations
-        while (true) {
-          long long lo = -1;
-          for (int sl = 0; sl < PSTEP; ++sl)
-            if (cur[sl] < end[sl] && (lo < 0 || key_of(sl) < lo)) lo = key_of(sl);
-          if (fill && lo >= 0)
-            while (sg < nSeg && lo >= o_lo + (sg + 1) * segG) seg_end[(size_t)b * nSeg + sg++] = (int)steps;
-          if (lo < 0) break;
-          for (int sl = 0; sl < PSTEP; ++sl) {
-            const bool take = cur[sl] < end[sl] && key_of(sl) <= lo + skew;
-            if (fill) {
-              const long long o = (base + steps) * PSTEP + sl;
-              if (take) { st_k[o] = (int)(it_k[cur[sl]] - o_lo); st_l[o] = (int)(it_l[cur[sl]] - o_lo); st_a[o] = it_a[cur[sl]]; }
-              else { st_k[o] = st_l[o] = 0; st_a[o] = (int)N; }  // the range's first record (any finite one) x the all-zero point row
-            }
-            if (take) ++cur[sl];
-          }
-          ++steps;
-        }
-        if (fill)
-          while (sg < nSeg) seg_end[(size_t)b * nSeg + sg++] = (int)steps;
-        return steps;
-      };
-      // device merge: the slots' list spans (from the units) go up, the step counts come back
-      long long *d_slbeg = nullptr, *d_ro0 = nullptr, *d_wbeg = nullptr;
-      int *d_sllen = nullptr, *d_wsteps = nullptr;
-      {  // first observation of every range: the merge kernels and k_schur_slots (its record base) read it
-        std::vector<long long> ro0(nR);
-        for (int r = 0; r < nR; ++r) ro0[r] = p->pt_ptr[range_lo[r]];
-        TRY(dmalloc(&h->d_range_o0, (size_t)nR));
-        TRYH(hipMemcpy(h->d_range_o0, ro0.data(), sizeof(long long) * nR, hipMemcpyHostToDevice));
-        d_ro0 = h->d_range_o0;
-      }
-      if (dev_build) {
-        std::vector<long long> sl_beg((size_t)n_waves * PSTEP, 0);
-        std::vector<int> sl_len((size_t)n_waves * PSTEP, 0);
-        for (long long b = 0; b < n_waves; ++b) {
-          int vs[PSTEP];
-          const int r = wave_lists(b, vs);
-          for (int sl = 0; sl < PSTEP; ++sl) {
-            const int id = vs[sl] >= 0 ? uid[(size_t)vs[sl] * nR + r] : -1;
-            wunits[(size_t)b * PSTEP + sl] = id;
-            if (id < 0) continue;
-            sl_beg[(size_t)b * PSTEP + sl] = ((long long)units[id].y << 32) | (unsigned)units[id].x;
-            sl_len[(size_t)b * PSTEP + sl] = units[id].z;
-          }
-        }
-        TRY(dmalloc(&d_slbeg, sl_beg.size())); TRY(dmalloc(&d_sllen, sl_len.size()));
-        TRY(dmalloc(&d_wsteps, (size_t)n_waves)); TRY(dmalloc(&d_wbeg, (size_t)n_waves + 1));
-        TRYH(hipMemcpyAsync(d_slbeg, sl_beg.data(), sizeof(long long) * sl_beg.size(), hipMemcpyHostToDevice, h->stream));
-        TRYH(hipMemcpyAsync(d_sllen, sl_len.data(), sizeof(int) * sl_len.size(), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_idx_merge<false>, dim3((unsigned)n_waves), dim3(64), 0, h->stream, n_waves, nR, nSeg, skew, segG, d_slbeg, d_sllen,
-                           d_ro0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, (int *)nullptr, (int *)nullptr, (int *)nullptr,
-                           (int *)nullptr, (const long long *)h->d_pt_ptr);
-        std::vector<int> ws32(n_waves);
-        TRYH(hipMemcpyAsync(ws32.data(), d_wsteps, sizeof(int) * n_waves, hipMemcpyDeviceToHost, h->stream));
-        TRYH(hipStreamSynchronize(h->stream));  // (sl_beg / sl_len / ro0 live until here)
-        for (long long b = 0; b < n_waves; ++b) w_steps[b] = ws32[b];
-      } else
-      on_threads([&](int tid) {
-        for (long long b = tid; b < n_waves; b += n_thr) w_steps[b] = merge(b, 0, false);
-      });
-      lap("slot merge (count)");
-      for (long long b = 0; b < n_waves; ++b) w_beg[b + 1] = w_beg[b] + w_steps[b];
-      const long long total_steps = w_beg[n_waves];
-      if (total_steps * PSTEP >= (1LL << 40)) { mvba_destroy(h); return fail(MVBA_ERR_BADARG, "too many (point, camera pair) items"); }
-      {  // the step-major index -- its size follows the padding rows -- against the memory that is
-        // there, BEFORE anything of it is allocated: three 4-byte arrays of step rows, then the interleaved 256-byte rows beside them
-        const size_t need = (size_t)total_steps * PSTEP * 12 + (size_t)total_steps * SLOT_IDX * 4 + seg_end.size() * 4;
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess && need > fr) {
-          mvba_destroy(h);
-          return fail(MVBA_ERR_BADARG, "the slot-form Schur index needs " + std::to_string(need >> 20) + " MiB (" + std::to_string(total_steps * PSTEP) + " step rows for " +
-                                           std::to_string(T) + " items: " + std::to_string(nR) + " ranges, skew " + std::to_string(skew) + "), " +
-                                           std::to_string(fr >> 20) + " MiB of device memory are free: use MVBA_SCHUR=pairs");
-        }
-      }
-      if (dev_build) {  // the step-major arrays are written where the kernel will read them
-        const size_t rows = (size_t)total_steps * PSTEP;
-        TRY(dmalloc(&h->d_it_k, rows)); TRY(dmalloc(&h->d_it_l, rows)); TRY(dmalloc(&h->d_it_a, rows));
-        TRY(dmalloc(&h->d_seg_end, seg_end.size()));
-        TRYH(hipMemcpyAsync(d_wbeg, w_beg.data(), sizeof(long long) * (n_waves + 1), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(k_idx_merge<true>, dim3((unsigned)n_waves), dim3(64), 0, h->stream, n_waves, nR, nSeg, skew, segG, d_slbeg, d_sllen,
-                           d_ro0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, h->d_it_k, h->d_it_l, h->d_it_a, h->d_seg_end, (const long long *)h->d_pt_ptr);
-        TRYH(hipGetLastError());
-        TRYH(hipStreamSynchronize(h->stream));
-        for (void *q : {(void *)d_slbeg, (void *)d_sllen, (void *)d_wsteps, (void *)d_wbeg}) hipFree(q);
-        free_dev_tmp();
-        h->index_on_device = true;
-      } else {
-      st_k.resize(total_steps * PSTEP); st_l.resize(total_steps * PSTEP); st_a.resize(total_steps * PSTEP);
-      on_threads([&](int tid) {
-        for (long long b = tid; b < n_waves; b += n_thr)
-          if (w_steps[b]) merge(b, w_beg[b], true);
-      });
-      }
-      lap("slot merge (fill)");
-      std::vector<int> live(nR, 0);  // waves of a range that run at all: what a pacing counter has to reach
-      for (long long b = 0; b < n_waves; ++b) live[b % nR] += w_steps[b] > 0;
-      for (long long b = 0; b < n_waves; ++b) {
-        const long long beg = w_beg[b];  // first step of the wave in the step-major index
-        // flags: bit 0 diagonal wave | bits 8..19 live waves of its range
-        wdesc[b] = make_int4((int)(beg & 0xffffffffLL), (int)(beg >> 32), (int)w_steps[b],
-                             (w_isdiag[b / nR] ? 1 : 0) | (live[b % nR] << 8));
-      }
-      h->n_waves = (int)n_waves;
-      h->slot_nR = nR;
-      h->n_slot_items = total_steps * PSTEP;
-      if (!dev_build) { it_k.swap(st_k); it_l.swap(st_l); it_a.swap(st_a); }  // what is uploaded below: the step-major arrays
-      std::vector<int>().swap(st_k); std::vector<int>().swap(st_l); std::vector<int>().swap(st_a);
-    } else {
-    // work queues: strip k on XCD k % 8, inside a queue by (range, k, l, sub-list) -- range-major: every XCD sweeps the
-    // point ranges in the same order, so the l-side records of a range (needed once per strip, ~4.5 times in all) are
-    // re-read from the Infinity Cache while the whole chip is on that range: 2.28 -> 2.04 ms at config 3 against strip-major
-    for (int x = 0; x < 8; ++x) {
-      auto push_group = [&](int k, int r) {
-        for (int l = k; l < m; ++l) {
-          const long long q = pair_id(k, l);
-          for (int sI = 0; sI < S[q]; ++sI) {
-            const int id = uid[(size_t)(vp_ptr[q] + sI) * nR + r];
-            if (id >= 0) q_units.push_back(id);
-          }
-        }
-      };
-      for (int r = 0; r < nR; ++r)
-        for (int k = x; k < m; k += 8) push_group(k, r);
-      q_ptr[x + 1] = (int)q_units.size();
-    }
-    if (dev_build) {  // the pair-major arrays stay where the fill kernel wrote them
-      h->d_it_k = d_pk; h->d_it_l = d_pl; h->d_it_a = d_pa;
-      d_pk = d_pl = d_pa = nullptr;
-      free_dev_tmp();
-      h->index_on_device = true;
-    }
-    }
-    h->n_items = T;
-    h->n_items_offdiag = T - Tdiag;
-    h->n_units = (int)units.size();
-  }
-  lap("queues / wave descriptors");
-  h->cost_grid = (int)std::max<long long>(1, std::min<long long>(2048, (nobs + 255) / 256));
-  h->n_partials = std::max(h->cost_grid, 4096);  // k_cost uses cost_grid blocks
-
-  TRY(dmalloc(&h->d_obs_pt, nobs));
-  TRY(dmalloc(&h->d_xy, nobs));
-  h->n_tiles = (int)tiles.size() - 1;
-  h->any_split = any_split;
-  if (any_split) {
-    tile_slot.resize(tiles.size(), -1);
-    h->n_splits = (int)splits.size();
-    TRY(dmalloc(&h->d_tile_slot, tile_slot.size()));
-    TRY(dmalloc(&h->d_splits, splits.size()));
-    TRY(dmalloc(&h->d_PLsplit, 9 * (size_t)n_split_slots));
-    TRYH(hipMemcpy(h->d_tile_slot, tile_slot.data(), sizeof(int) * tile_slot.size(), hipMemcpyHostToDevice));
-    TRYH(hipMemcpy(h->d_splits, splits.data(), sizeof(int4) * splits.size(), hipMemcpyHostToDevice));
-  }
-  TRY(dmalloc(&h->d_tiles, tiles.size()));
-  for (int i = 0; i < 2; ++i) { TRY(dmalloc(&h->d_X[i], 3 * N)); TRY(dmalloc(&h->d_cam15[i], (size_t)CAM_IN * m)); }
-  TRY(dmalloc(&h->d_rec, (size_t)REC * (nobs + 1)));  // + the all-zero record and point row the slot form's padding points at
-  if (loss != LOSS_SQUARED) {
-    TRY(dmalloc(&h->d_sqw, nobs + 1));
-    TRYH(hipMemset(h->d_sqw, 0, sizeof(double) * (nobs + 1)));
-  }
-  TRY(dmalloc(&h->d_PL, 9 * N));
-  TRY(dmalloc(&h->d_PB, (size_t)PBS * (N + 1)));
-  TRYH(hipMemset(h->d_rec + (size_t)REC * nobs, 0, sizeof(double2) * REC));
-  TRYH(hipMemset(h->d_PB + (size_t)PBS * N, 0, sizeof(double) * PBS));
-  const size_t n9 = 9 * (size_t)m;
-  TRY(dmalloc(&h->d_Ab, strip_offset(m, m) + n9));
-  TRY(dmalloc(&h->d_Ared, (size_t)(h->D + 1) * h->ld));
-  TRY(dmalloc(&h->d_Lblk, (size_t)((h->D + SBW - 1) / SBW) * SBW * SBW));
-  TRY(dmalloc(&h->d_Ztiles, (size_t)((h->D + NB - 1) / NB) * NB * NB));
-  TRY(dmalloc(&h->d_dxi, n9));
-  TRY(dmalloc(&h->d_dX, 3 * N));
-  TRY(dmalloc(&h->d_partials, h->n_partials));
-  TRY(dmalloc(&h->d_cost, 2));
-  TRY(dmalloc(&h->d_flag, 1));
-  TRY(dmalloc(&h->d_bar, 1 + 4 * (size_t)((9 * m + SBW - 1) / SBW)));  // progress words of the back-substitution
-  TRYH(hipHostMalloc((void **)&h->h_cost, 4 * sizeof(double), hipHostMallocMapped));
-  memset(h->h_cost, 0, 4 * sizeof(double));
-  if (hipHostGetDevicePointer((void **)&h->d_mail, h->h_cost, 0) != hipSuccess) h->d_mail = nullptr;  // (no mapping: copy + sync as before)
-  h->h_flag = reinterpret_cast<int *>(h->h_cost + 1);  // cost and flags come back in one copy
-  lap("allocations");
-  if (nobs) {
-    TRYH(hipMemcpy(h->d_obs_pt, obs_pt.data(), sizeof(int) * nobs, hipMemcpyHostToDevice));
-    if (p->xy_layout == 1) {  // image planes [m][N][2], as a caller's stack of per-image arrays lies in memory: into observation order here
-      double2 *planes = nullptr;  // (the host's strided gather of the same bytes: 0.1 s at 1 M points x 12 images)
-      TRYH(hipMalloc((void **)&planes, sizeof(double2) * nobs));
-      hipError_t e = hipMemcpy(planes, p->xy, sizeof(double2) * nobs, hipMemcpyHostToDevice);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_xy_from_planes, dim3((unsigned)((N + 255) / 256), m), dim3(256), 0, 0, planes, N, m, h->d_xy);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-      }
-      hipFree(planes);
-      TRYH(e);
-    } else {
-      TRYH(hipMemcpy(h->d_xy, p->xy, sizeof(double2) * nobs, hipMemcpyHostToDevice));
-    }
-  }
-  TRYH(hipMemcpy(h->d_tiles, tiles.data(), sizeof(int) * tiles.size(), hipMemcpyHostToDevice));
-  // points without observations are never written by K1: their blocks stay zero (-> singular, ref :128)
-  TRYH(hipMemset(h->d_PL, 0, sizeof(double) * 9 * std::max<long long>(N, 1)));
-  TRYH(hipMemset(h->d_flag, 0, sizeof(int)));
-  if (h->schur_mode == SCHUR_DENSE) {  // partial tiles of k_schur_dense: (tile pairs + one per camera) x 256 doubles per workgroup
-    const int T = (9 * m + 15) / 16;
-    int n_cu_dense = 256;
-    hipDeviceGetAttribute(&n_cu_dense, hipDeviceAttributeMultiprocessorCount, h->device);
-    h->dense_tiles = T * (T + 1) / 2 + m;
-    h->dense_blocks = (int)std::max<long long>(1, std::min<long long>((N + dense_ch(T) - 1) / dense_ch(T), (long long)n_cu_dense * dense_wgs(T)));  // dense_wgs workgroups per CU (LDS and registers: see dense_ch)
-    TRY(dmalloc(&h->d_dense_part, (size_t)h->dense_blocks * h->dense_tiles * 256));
-    if (!dense_obs.empty()) {
-      TRY(dmalloc(&h->d_dense_obs, dense_obs.size()));
-      TRYH(hipMemcpy(h->d_dense_obs, dense_obs.data(), sizeof(int) * dense_obs.size(), hipMemcpyHostToDevice));
-    }
-  }
-  if (h->use_pairs) {
-    const size_t P1 = (size_t)m * (m + 1) / 2 + 1;
-    if (!h->index_on_device) { TRY(dmalloc(&h->d_it_k, it_k.size())); TRY(dmalloc(&h->d_it_l, it_l.size())); TRY(dmalloc(&h->d_it_a, it_a.size())); }
-    TRY(dmalloc(&h->d_units, units.size())); TRY(dmalloc(&h->d_unit_ptr, P1));
-    TRY(dmalloc(&h->d_q_ptr, 9)); TRY(dmalloc(&h->d_q_units, q_units.size()));
-    TRY(dmalloc(&h->d_wdesc, wdesc.size())); TRY(dmalloc(&h->d_wunits, wunits.size()));
-    if (!h->index_on_device) TRY(dmalloc(&h->d_seg_end, seg_end.size()));
-    TRY(dmalloc(&h->d_prog, (size_t)h->slot_nR * std::max(1, h->slot_nseg) * PACE_STRIDE));
-    if (!seg_end.empty() && !h->index_on_device) TRYH(hipMemcpy(h->d_seg_end, seg_end.data(), sizeof(int) * seg_end.size(), hipMemcpyHostToDevice));
-    if (!wdesc.empty()) {
-      TRYH(hipMemcpy(h->d_wdesc, wdesc.data(), sizeof(int4) * wdesc.size(), hipMemcpyHostToDevice));
-      TRYH(hipMemcpy(h->d_wunits, wunits.data(), sizeof(int) * wunits.size(), hipMemcpyHostToDevice));
-    }
-    TRY(dmalloc(&h->d_partial, (size_t)UNIT_STRIDE * units.size()));
-    if (!it_k.empty()) {
-      TRYH(hipMemcpy(h->d_it_k, it_k.data(), sizeof(int) * it_k.size(), hipMemcpyHostToDevice));
-      TRYH(hipMemcpy(h->d_it_l, it_l.data(), sizeof(int) * it_l.size(), hipMemcpyHostToDevice));
-      TRYH(hipMemcpy(h->d_it_a, it_a.data(), sizeof(int) * it_a.size(), hipMemcpyHostToDevice));
-    }
-    if (!it_k.empty() || h->index_on_device) {
-      if (h->schur_mode == SCHUR_PAIRS) {
-        std::vector<int4> qdesc(units.size());  // descriptors in queue order (the kernel indexes both arrays by queue position)
-        for (size_t i = 0; i < q_units.size(); ++i) qdesc[i] = units[q_units[i]];
-        TRYH(hipMemcpy(h->d_units, qdesc.data(), sizeof(int4) * qdesc.size(), hipMemcpyHostToDevice));
-        int mx = 0;
-        for (int x = 0; x < 8; ++x) mx = std::max(mx, q_ptr[x + 1] - q_ptr[x]);
-        h->q_max = mx;
-      }
-      if (!q_units.empty()) TRYH(hipMemcpy(h->d_q_units, q_units.data(), sizeof(int) * q_units.size(), hipMemcpyHostToDevice));
-    }
-    if (h->schur_mode == SCHUR_SLOTS && h->n_slot_items) {  // the three step-major arrays -> one 256-byte row per step; they go
-      const long long n_steps = h->n_slot_items / PSTEP;
-      TRY(dmalloc(&h->d_it_x, (size_t)n_steps * SLOT_IDX));
-      hipLaunchKernelGGL(k_idx_interleave, dim3((unsigned)((n_steps * SLOT_IDX + 255) / 256)), dim3(256), 0, h->stream, n_steps, h->d_it_k, h->d_it_l,
-                         h->d_it_a, h->d_it_x);
-      TRYH(hipGetLastError());
-      TRYH(hipStreamSynchronize(h->stream));
-      hipFree(h->d_it_k); hipFree(h->d_it_l); hipFree(h->d_it_a);
-      h->d_it_k = h->d_it_l = h->d_it_a = nullptr;
-    }
-    TRYH(hipMemcpy(h->d_unit_ptr, unit_ptr.data(), sizeof(int) * P1, hipMemcpyHostToDevice));
-    TRYH(hipMemcpy(h->d_q_ptr, q_ptr.data(), sizeof(int) * 9, hipMemcpyHostToDevice));
-    TRYH(hipMemset(h->d_partial, 0, sizeof(double) * UNIT_STRIDE * std::max<size_t>(units.size(), 1)));
-  }
-  lap("uploads");
-  // opt in to large dynamic LDS
-  const int cam_lds = h->gcam ? 0 : (int)((size_t)m * (CAM_LDS + DXI_LDS) * sizeof(double));
-  if (h->gcam) { TRY(dmalloc(&h->d_cam18, (size_t)m * CAM_LDS)); TRY(dmalloc(&h->d_dxi10, (size_t)m * DXI_LDS)); }
-  for (const void *f : {(const void *)k_backsub<2>, (const void *)k_backsub<4>, (const void *)k_backsub<8>, (const void *)k_backsub<2, 512>,
-                        (const void *)k_backsub<4, 512>, (const void *)k_backsub<8, 512>, (const void *)k_backsub<2, 1024>,
-                        (const void *)k_backsub<4, 1024>, (const void *)k_backsub<8, 1024>})
-    TRYH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
-  TRYH(hipFuncSetAttribute((const void *)k_chol_super, hipFuncAttributeMaxDynamicSharedMemorySize, SUPER_LDS));
-  TRYH(hipFuncSetAttribute((const void *)k_chol_backsolve_all<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BACKSOLVE_LDS));
-  {
-    // the persistent back-substitution needs its whole grid resident: at most one workgroup per CU
-    int per_cu = 0;
-    TRYH(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-    TRYH(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_chol_backsolve_all<true>, SUPER_THREADS, BACKSOLVE_LDS));
-    h->chol_onepass = per_cu >= 1 && !knobs.chol_launches;
-    h->trail64_min = knobs.trail64_min;
-    h->barrier_polls = knobs.barrier_polls;
-  }
-  TRYH(hipFuncSetAttribute(h->gcam ? (const void *)k_resid_jac<true> : (const void *)k_resid_jac<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                           (int)((size_t)((h->gcam ? 0 : ((m * CAM_LDS + 1) & ~1)) + (h->k1_threads / 64) * 64 * 2 * REC) * sizeof(double))));
-  TRYH(hipFuncSetAttribute((const void *)k_cost<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
-  TRYH(hipFuncSetAttribute((const void *)k_residuals<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
-  if (loss != LOSS_SQUARED) {
-    for (const void *f : {(const void *)k_backsub<2, 256, false, true, LossArgs>, (const void *)k_backsub<4, 256, false, true, LossArgs>, (const void *)k_backsub<8, 256, false, true, LossArgs>,
-                          (const void *)k_backsub<2, 512, false, true, LossArgs>, (const void *)k_backsub<4, 512, false, true, LossArgs>, (const void *)k_backsub<8, 512, false, true, LossArgs>,
-                          (const void *)k_backsub<2, 1024, false, true, LossArgs>, (const void *)k_backsub<4, 1024, false, true, LossArgs>, (const void *)k_backsub<8, 1024, false, true, LossArgs>})
-      TRYH(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
-    TRYH(hipFuncSetAttribute((const void *)resid_jac_robust(h->gcam, loss), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)((size_t)((h->gcam ? 0 : ((m * CAM_LDS + 1) & ~1)) + (h->k1_threads / 64) * 64 * 2 * REC) * sizeof(double))));
-    TRYH(hipFuncSetAttribute((const void *)cost_robust(false, loss), hipFuncAttributeMaxDynamicSharedMemorySize, cam_lds));
-  }
-#undef TRY
-#undef TRYH
-  lap("attributes");
-  *out = h;
-  return MVBA_OK;
-}
-}  // namespace
 
 int mvba_create(const mvba_problem *p, mvba_handle **out) { return create_engine(p, LOSS_SQUARED, 0.0, out); }
 
@@ -3989,15 +3341,7 @@ void mvba_destroy(mvba_handle *h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->comm) g_rccl.CommDestroy(h->comm);
-  void *ptrs[] = {h->d_pt_ptr, h->d_cam, h->d_obs_pt, h->d_xy, h->d_tiles, h->d_tile_slot, h->d_splits, h->d_PLsplit, h->d_X[0], h->d_X[1],
-                  h->d_cam15[0], h->d_cam15[1], h->d_rec, h->d_PL, h->d_PB, h->d_Ab, h->d_Ared, h->d_Ztiles, h->d_Lblk, h->d_lu,
-                  h->d_dxi, h->d_dX, h->d_partials, h->d_cost, h->d_flag, h->d_allcost, h->d_it_k, h->d_it_l, h->d_it_a,
-                  h->d_units, h->d_unit_ptr, h->d_q_ptr, h->d_q_units, h->d_partial, h->d_dense_part, h->d_dense_obs, h->d_sim, h->d_bar, h->d_wdesc,
-                  h->d_wunits, h->d_seg_end, h->d_prog, h->d_ipiv, h->d_range_o0, h->d_it_x, h->d_cam18, h->d_dxi10,
-                  h->d_cov_sig, h->d_cov_panel, h->d_cov_pts, h->d_cov_cam, h->d_sqw, h->d_resid,
-                  h->d_map_col, h->d_map_ptr, h->d_map_mem, h->d_map_x, h->d_cov_sigv, h->d_map_pairs, h->d_map_part};
-  for (void *q : ptrs) if (q) hipFree(q);
-  for (double *q : h->snap_slabs) hipFree(q);
+  h->mem.release_all();
   if (h->h_cost) hipHostFree(h->h_cost);
   if (h->h_allcost) hipHostFree(h->h_allcost);
   for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
@@ -4049,7 +3393,7 @@ int mvba_apply_similarity(mvba_handle *h, const double *R0, const double *t0, do
   memcpy(T + 9, t0, 3 * sizeof(double));
   T[12] = scale;
   if (!h->d_sim) {
-    int rc = dmalloc(&h->d_sim, 13);
+    int rc = h->mem.alloc(&h->d_sim, 13);
     if (rc) return rc;
   }
   MVBA_HIP(hipMemcpyAsync(h->d_sim, T, sizeof(T), hipMemcpyHostToDevice, h->stream));
@@ -4066,8 +3410,11 @@ int mvba_cost(mvba_handle *h, double *E) {
   if (!h || !E) return fail(MVBA_ERR_BADARG, "null argument");
   if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
   MVBA_HIP(hipSetDevice(h->device));
-  int rc = launch_cost(h, h->d_cam15[h->cur], h->d_X[h->cur]);
-  if (rc) return rc;
+  {
+    Timed t(h, MVBA_K_COST);
+    int rc = launch_cost(h, h->d_cam15[h->cur], h->d_X[h->cur]);
+    if (rc) return rc;
+  }
   return global_cost(h, E);
 }
 
@@ -4076,18 +3423,12 @@ namespace {
 // covariance does not add to the per-kernel statistics.
 void launch_resid_jac(mvba_handle *h) {  // K1 with K2 fused in, at the committed state
   const int kt = h->k1_threads;  // 8 waves share one camera table: 2 blocks = 16 waves per CU
-  const size_t lds = (size_t)((h->gcam ? 0 : ((h->m * CAM_LDS + 1) & ~1)) + (kt / 64) * 64 * 2 * REC) * sizeof(double);
   cam_tables(h, h->d_cam15[h->cur], nullptr);
   const int wpb = kt / 64;
   const int grid = std::max(1, std::min(2048 * 256 / kt, (h->n_tiles + wpb - 1) / wpb));
-  if (h->loss != LOSS_SQUARED)
-    hipLaunchKernelGGL(resid_jac_robust(h->gcam, h->loss), dim3(grid), dim3(kt), lds, h->stream, h->nobs, h->m, h->d_cam15[h->cur],
-                       h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
-                       h->d_tile_slot, h->d_PLsplit, h->d_cam18, LossArgs{h->loss_b, h->d_sqw});
-  else
-  hipLaunchKernelGGL(h->gcam ? k_resid_jac<true> : k_resid_jac<false>, dim3(grid), dim3(kt), lds, h->stream, h->nobs, h->m, h->d_cam15[h->cur],
-                     h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
-                     h->d_tile_slot, h->d_PLsplit, h->d_cam18);
+  launch_loss(h, resid_jac_kernel(h->gcam, h->loss), dim3(grid), dim3(kt), k1_lds_bytes(h->m, h->gcam, kt), h->nobs, h->m, h->d_cam15[h->cur],
+              h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
+              h->d_tile_slot, h->d_PLsplit, h->d_cam18);
   if (h->n_splits)
     hipLaunchKernelGGL(k_sum_split, dim3((9 * h->n_splits + 255) / 256), dim3(256), 0, h->stream, h->n_splits, h->d_splits,
                        h->d_PLsplit, h->d_PL);
@@ -4115,52 +3456,20 @@ void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b]
         hipLaunchKernelGGL(k_schur_slots, dim3(h->n_waves), dim3(64), SLOT_LDS, h->stream, h->d_wdesc,
                            h->d_wunits, h->d_it_x, (const int *)nullptr, (const int *)nullptr, h->d_rec, h->d_PB, c, h->f0, h->d_partial,
                            h->slot_nR, h->d_seg_end, h->d_prog, h->slot_nseg, SLOT_LAG, h->d_range_o0);
-    } else if (h->n_units && h->loss != LOSS_SQUARED) {
-      hipLaunchKernelGGL(big ? k_schur_pairs_big_robust : k_schur_pairs_robust, dim3(8 * h->q_max), dim3(64),
-                         PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, h->d_it_k, h->d_it_l, h->d_it_a, h->d_rec, h->d_PB, c,
-                         h->f0, h->d_partial, (const double *)h->d_sqw);
-    } else if (h->n_units) {
-      hipLaunchKernelGGL(big ? k_schur_pairs_big : k_schur_pairs, dim3(8 * h->q_max), dim3(64),
-                         PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, h->d_it_k, h->d_it_l, h->d_it_a, h->d_rec, h->d_PB, c, h->f0, h->d_partial);
+    } else if (h->n_units) {  // (the robust kernels take sqrt(w) per observation as a plain trailing pointer)
+      auto launch = [&](auto kern, auto... robust) {
+        hipLaunchKernelGGL(kern, dim3(8 * h->q_max), dim3(64), PAIRS_LDS, h->stream, h->d_units, h->d_q_ptr, h->d_q_units, h->d_it_k, h->d_it_l,
+                           h->d_it_a, h->d_rec, h->d_PB, c, h->f0, h->d_partial, robust...);
+      };
+      if (h->loss != LOSS_SQUARED) launch(big ? k_schur_pairs_big_robust : k_schur_pairs_robust, (const double *)h->d_sqw);
+      else launch(big ? k_schur_pairs_big : k_schur_pairs);
     }
     hipLaunchKernelGGL(k_schur_reduce, dim3((unsigned)((long long)m * (m + 1) / 2)), dim3(128), 0, h->stream, m, h->d_unit_ptr,
                        h->d_partial, d_A, d_b);
   } else if (h->schur_mode == SCHUR_DENSE) {
     const int T = (9 * m + 15) / 16;
-    const int CH = dense_ch(T);
-    const size_t lds = sizeof(double) * ((size_t)2 * 3 * CH * 16 * T + (size_t)2 * CH * m * 32) + sizeof(double2) * CH * ((size_t)m * REC + 8) + sizeof(double) * (CH * (size_t)m + 2 * 3 * CH);
-    auto launch = [&](auto kern) {
-      if (!h->dense_attr_set) {  // (once per engine; the limit of the INSTANTIATION -- its largest camera count -- so that engines with other m share it)
-        const int mm = 16 * T / 9;
-        const size_t lds_max = sizeof(double) * ((size_t)2 * 3 * CH * 16 * T + (size_t)2 * CH * mm * 32 + (size_t)CH * mm + 2 * 3 * CH) + sizeof(double2) * CH * ((size_t)mm * REC + 8);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        h->dense_attr_set = true;
-      }
-      hipLaunchKernelGGL(kern, dim3(h->dense_blocks), dim3(64 * (dense_consumers(T) + CH)), lds, h->stream, (const double2 *)h->d_rec, (const double *)h->d_PB, (const int *)h->d_dense_obs,
-                         (long long)h->N, m, 1.0 / h->f0, h->d_dense_part);
-    };
-    auto launch_robust = [&](auto kern) {  // (the same, with sqrt(w) per observation)
-      if (!h->dense_attr_set) {
-        const int mm = 16 * T / 9;
-        const size_t lds_max = sizeof(double) * ((size_t)2 * 3 * CH * 16 * T + (size_t)2 * CH * mm * 32 + (size_t)CH * mm + 2 * 3 * CH) + sizeof(double2) * CH * ((size_t)mm * REC + 8);
-        hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        h->dense_attr_set = true;
-      }
-      hipLaunchKernelGGL(kern, dim3(h->dense_blocks), dim3(64 * (dense_consumers(T) + CH)), lds, h->stream, (const double2 *)h->d_rec, (const double *)h->d_PB, (const int *)h->d_dense_obs,
-                         (long long)h->N, m, 1.0 / h->f0, h->d_dense_part, LossArgs{h->loss_b, h->d_sqw});
-    };
-    const bool table = h->d_dense_obs != nullptr, robust = h->loss != LOSS_SQUARED;
-#define MVBA_DENSE_LAUNCH(t) \
-  if (robust) { if (table) launch_robust(k_schur_dense<t, true, true, LossArgs>); else launch_robust(k_schur_dense<t, false, true, LossArgs>); } \
-  else if (table) launch(k_schur_dense<t, true>); else launch(k_schur_dense<t, false>);
-#define MVBA_DENSE_CASE(t) case t: MVBA_DENSE_LAUNCH(t) break;
-    switch (T) {
-      MVBA_DENSE_CASE(1) MVBA_DENSE_CASE(2) MVBA_DENSE_CASE(3) MVBA_DENSE_CASE(4) MVBA_DENSE_CASE(5) MVBA_DENSE_CASE(6)
-      MVBA_DENSE_CASE(7) MVBA_DENSE_CASE(8) MVBA_DENSE_CASE(9) MVBA_DENSE_CASE(10) MVBA_DENSE_CASE(11)
-      default: MVBA_DENSE_LAUNCH(12) break;
-    }
-#undef MVBA_DENSE_CASE
-#undef MVBA_DENSE_LAUNCH
+    launch_loss(h, dense_kernel(T, h->d_dense_obs != nullptr), dim3(h->dense_blocks), dim3(64 * (dense_consumers(T) + dense_ch(T))), dense_lds_bytes(T, m),
+                (const double2 *)h->d_rec, (const double *)h->d_PB, (const int *)h->d_dense_obs, (long long)h->N, m, 1.0 / h->f0, h->d_dense_part);
     const long long n_el = (long long)nA + 9 * m;
     hipLaunchKernelGGL(k_schur_dense_finish, dim3((unsigned)((n_el + 3) / 4)), dim3(256), 0, h->stream, m, T, h->dense_blocks,
                        (const double *)h->d_dense_part, c, d_A, d_b);
@@ -4243,22 +3552,157 @@ int mvba_linearize(mvba_handle *h) {
   return MVBA_OK;
 }
 
+namespace {
+// The pieces of the LM trial (mvba_try_step below reads as the step).
+// With a parameter map the solve kernels run on the D' x D' mapped system and scatter x (through keep_index, as ever) into a
+// scratch vector; k_map_expand then writes dxi = P x.  D' = 0 (everything held): dxi = 0, no solve.
+double *solve_x(mvba_handle *h) { return h->mapped ? h->d_map_x : h->d_dxi; }
+void launch_expand(mvba_handle *h) {
+  const size_t n9 = 9 * (size_t)h->m;
+  if (h->mapped && h->solve_D() > 0)
+    hipLaunchKernelGGL(k_map_expand, dim3((unsigned)((n9 + 255) / 256)), dim3(256), 0, h->stream, (int)n9, h->gauge_axis, h->d_map_col,
+                       h->d_map_x, h->d_dxi);
+}
+
+void launch_solve(mvba_handle *h, bool onepass) {  // K4: gauge strip, blocked Cholesky, back-substitution
+  const int m = h->m, D = h->solve_D();
+  double *d_x = solve_x(h);
+  Timed t(h, MVBA_K_SOLVE);
+  if (D == 0) {  // (only with a map)
+    hipMemsetAsync(h->d_dxi, 0, sizeof(double) * 9 * (size_t)m, h->stream);
+    return;
+  }
+  launch_factor(h);
+  const int ld = h->solve_ld();
+  const int S = (D + SBW - 1) / SBW;
+  if (onepass && (S == 1 || S < h->n_cu)) {  // one persistent pass for L^T x = y (see k_chol_backsolve_all)
+    // (point to point, nobody pays for anybody else: one bulk workgroup per column group)
+    const int ngrp = ((S - 1) * SBW + 31) / 32, nbulk = S > 1 ? std::max(1, std::min(h->n_cu - S, ngrp)) : 0;
+    hipLaunchKernelGGL(k_chol_backsolve_all<true>, dim3(S + nbulk), dim3(SUPER_THREADS),
+                       BACKSOLVE_LDS, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles, h->d_Lblk, d_x, h->d_flag,
+                       h->d_bar, h->barrier_polls);
+  } else
+  for (int jS = ((D - 1) / SBW) * SBW; jS >= 0; jS -= SBW) {
+    const int jE = std::min(jS + SBW, D), jE2 = std::min(jE + SBW, D);
+    const int nwg = (jE == D) ? 1 : 1 + (jS + 255) / 256;
+    hipLaunchKernelGGL(k_chol_backsolve, dim3(nwg), dim3(256), 0, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles,
+                       h->d_Lblk + (size_t)(jS / SBW) * SBW * SBW, d_x, jS, jE, jE2);
+  }
+  launch_expand(h);
+}
+
+// The Cholesky met a non-positive pivot: the reduced system is not positive definite (e.g. a
+// negative damping factor).  The reference's np.linalg.solve is LU with partial pivoting and
+// does not care, so the solve is redone that way (slow path, rare).
+int launch_lu_solve(mvba_handle *h) {
+  const int m = h->m, D = h->solve_D();
+  double *d_A = h->d_Ab, *d_b = h->d_Ab + strip_offset(m, m), *d_x = solve_x(h);
+  if (!h->d_lu) {
+    int rc_ = h->mem.alloc(&h->d_lu, (size_t)h->D * (h->D + 1));  // (the default map's size: any map fits)
+    if (rc_) return rc_;
+    rc_ = h->mem.alloc(&h->d_ipiv, (size_t)h->D);
+    if (rc_) return rc_;
+  }
+  MVBA_HIP(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
+  Timed t(h, MVBA_K_SOLVE);
+  if (h->mapped) {
+    hipLaunchKernelGGL(k_map_full, dim3((D + 1 + 255) / 256, D), dim3(256), 0, h->stream, D, m, d_A, d_b, h->d_map_ptr, h->d_map_mem, h->d_lu);
+    launch_map_tied(h, h->d_lu, D + 1, 1);
+  } else
+  hipLaunchKernelGGL(k_compact_full, dim3((D + 1 + 255) / 256, D), dim3(256), 0, h->stream, D, m, h->gauge_axis, d_A, d_b, h->d_lu);
+  for (int j0 = 0; j0 < D; j0 += LU_NB) {
+    const int nb = std::min(LU_NB, D - j0), right = D + 1 - (j0 + nb);  // columns right of the panel incl. the rhs
+    hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(1024), 0, h->stream, h->d_lu, D, j0, nb, h->d_ipiv, h->d_flag);
+    hipLaunchKernelGGL(k_lu_swap, dim3((D + 1 - nb + 255) / 256), dim3(256), 0, h->stream, h->d_lu, D, j0, nb, h->d_ipiv);
+    if (right > 0) hipLaunchKernelGGL(k_lu_trsm, dim3((right + 255) / 256), dim3(256), 0, h->stream, h->d_lu, D, j0, nb);
+    const int below = D - (j0 + nb);
+    if (below > 0)
+      hipLaunchKernelGGL(k_lu_gemm, dim3((right + 63) / 64, (below + 63) / 64), dim3(256), 0, h->stream, h->d_lu, D, j0, nb);
+  }
+  hipLaunchKernelGGL(k_lu_backsub, dim3(1), dim3(1024), 0, h->stream, h->d_lu, D, m, h->gauge_axis, d_x);
+  launch_expand(h);
+  return MVBA_OK;
+}
+
+// K6a + K5/K6: trial cameras, back-substitution, trial cost -- and the cost read back (mailbox, or copy + sync)
+int launch_tail_and_cost(mvba_handle *h, double *E_trial) {
+  const int m = h->m, trial = 1 - h->cur;
+  {
+    Timed t(h, MVBA_K_BACKSUB_COST);
+    hipLaunchKernelGGL(k_update_cams, dim3((m + 63) / 64), dim3(64), 0, h->stream, m, h->d_cam15[h->cur], h->d_dxi,
+                       h->d_cam15[trial]);
+    if (h->N) {
+      const size_t lds = cam_lds_bytes(m, h->gcam, true);
+      cam_tables(h, h->d_cam15[h->cur], h->d_dxi);
+      const double deg = (double)h->nobs / (double)h->N;  // lanes per point by mean degree
+      const int G = deg <= 40.0 ? 2 : (deg <= 100.0 ? 4 : 8);
+      // (a camera table above half the LDS leaves one block per CU: 1024 threads then, so that the CU still holds 16 waves)
+      // (16 waves per CU is what the registers allow: 256-thread blocks reach it while four of them fit -- tables up to 40 KiB,
+      // ~180 cameras --, 512-thread blocks while two fit, one 1024-thread block beyond)
+      const int bt = lds > 80 * 1024 ? 1024 : (lds > 40 * 1024 ? 512 : 256);
+      const int nblk = (int)std::min<long long>(4096 * 256 / bt, (h->N * G + bt - 1) / bt);
+      launch_loss(h, backsub_kernel(G, bt, h->gcam), dim3(nblk), dim3(bt), lds, h->N, m, h->d_pt_ptr, h->d_cam, h->d_PB, h->d_dxi,
+                  h->d_X[h->cur], h->d_cam15[h->cur], h->f0, h->d_X[trial], h->d_dX, h->d_cam18, h->d_dxi10);
+    }
+    // K6: trial cost = the residual-only pass at the trial state (fixed grid, fixed tree: deterministic)
+    int rc = launch_cost(h, h->d_cam15[trial], h->d_X[trial]);
+    if (rc) return rc;
+  }
+  return global_cost(h, E_trial);
+}
+
+// Debug mode (MVBA_CHECK_SOLVE=1, read in mvba_create): the residual of the reduced system, b - A dxi over the kept parameters,
+// from the packed [A|b] the solve started from (it is intact: k_compact copied it) and the dxi it produced -- on the host, in
+// plain loops.  The persistent back-substitution orders its hand-overs with sc1 accesses and explicit waits, not with the
+// memory model's fences: a stale read there would be a silently wrong camera step, which this catches.
+int check_solve_residual(mvba_handle *h) {
+  const int m = h->m, D = h->solve_D();
+  const size_t n9 = 9 * (size_t)m, nA = strip_offset(m, m);
+  std::vector<double> Ab(nA + n9), x(n9);
+  MVBA_HIP(hipMemcpyAsync(Ab.data(), h->d_Ab, sizeof(double) * (nA + n9), hipMemcpyDeviceToHost, h->stream));
+  MVBA_HIP(hipMemcpyAsync(x.data(), h->d_dxi, sizeof(double) * n9, hipMemcpyDeviceToHost, h->stream));
+  MVBA_HIP(hipStreamSynchronize(h->stream));
+  auto kept = [&](size_t g) { return !((g >= 3 && g <= 8) || g == (size_t)(12 + h->gauge_axis)); };
+  std::vector<double> r(n9, 0.0), an(n9, 0.0);  // r = A x, an = |A| |x|  (rows of the full symmetric matrix from the packed upper strips)
+  for (int k = 0; k < m; ++k) {
+    const double *Ak = Ab.data() + strip_offset(k, m);
+    const int Wk = 9 * (m - k);
+    for (int i = 0; i < 9; ++i)
+      for (int c = 0; c < Wk; ++c) {
+        const size_t gi = 9 * (size_t)k + i, gj = 9 * (size_t)k + c;
+        const double a = Ak[(size_t)i * Wk + c];
+        r[gi] += a * x[gj]; an[gi] += std::fabs(a * x[gj]);
+        if (c >= 9) { r[gj] += a * x[gi]; an[gj] += std::fabs(a * x[gi]); }  // the mirror image below the diagonal blocks
+      }
+  }
+  double worst = 0.0;
+  if (h->mapped) {  // the mapped system's residual P^T (b - A P x): x above is dxi = P x, rows summed over an unknown's members
+    for (int j = 0; j < D; ++j) {
+      double res = 0.0, scale = 0.0;
+      for (int q = h->map_ptr[j]; q < h->map_ptr[j + 1]; ++q) {
+        const size_t g = (size_t)h->map_mem[q];
+        res += Ab[nA + g] - r[g];
+        scale += an[g] + std::fabs(Ab[nA + g]);
+      }
+      worst = std::max(worst, scale > 0.0 ? std::fabs(res) / scale : 0.0);
+    }
+  } else
+  for (size_t g = 0; g < n9; ++g)
+    if (kept(g)) {
+      const double bg = Ab[nA + g], scale = an[g] + std::fabs(bg);
+      worst = std::max(worst, scale > 0.0 ? std::fabs(bg - r[g]) / scale : 0.0);
+    }
+  if (!(worst <= h->check_solve_tol))
+    return fail(MVBA_ERR_STATE, "MVBA_CHECK_SOLVE: the dense solve left a relative residual of " + std::to_string(worst) +
+                                    " on the reduced camera system (a stale hand-over in the back-substitution?)");
+  return MVBA_OK;
+}
+}  // namespace
+
 int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
   if (!h || !E_trial) return fail(MVBA_ERR_BADARG, "null argument");
   if (!h->linearized) return fail(MVBA_ERR_STATE, "try_step before linearize");
   MVBA_HIP(hipSetDevice(h->device));
-  const int m = h->m, D = h->solve_D();
-  const size_t n9 = 9 * (size_t)m;
-  const size_t nA = strip_offset(m, m);  // packed upper block triangle
-  double *d_A = h->d_Ab, *d_b = h->d_Ab + nA;
-  // With a parameter map the solve kernels run on the D' x D' mapped system and scatter x (through keep_index, as ever) into a
-  // scratch vector; k_map_expand then writes dxi = P x.  D' = 0 (everything held): dxi = 0, no solve.
-  double *d_x = h->mapped ? h->d_map_x : h->d_dxi;
-  auto launch_expand = [&]() {
-    if (h->mapped && D > 0)
-      hipLaunchKernelGGL(k_map_expand, dim3((unsigned)((n9 + 255) / 256)), dim3(256), 0, h->stream, (int)n9, h->gauge_axis, h->d_map_col,
-                         h->d_map_x, h->d_dxi);
-  };
   {
     Timed t(h, MVBA_K_POINT_INV);
     launch_point_inv(h, c);
@@ -4268,78 +3712,12 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     launch_schur(h, c);
   }
   MVBA_HIP(hipGetLastError());
-  {
-    int rc_ = allreduce_Ab(h, true);
-    if (rc_) return rc_;
-  }
-  auto launch_solve = [&](bool onepass) {  // K4: gauge strip, blocked Cholesky, back-substitution
-    Timed t(h, MVBA_K_SOLVE);
-    if (D == 0) {  // (only with a map)
-      hipMemsetAsync(h->d_dxi, 0, sizeof(double) * n9, h->stream);
-      return;
-    }
-    launch_factor(h);
-    const int ld = h->solve_ld();
-    const int S = (D + SBW - 1) / SBW;
-    if (onepass && (S == 1 || S < h->n_cu)) {  // one persistent pass for L^T x = y (see k_chol_backsolve_all)
-      // (point to point, nobody pays for anybody else: one bulk workgroup per column group)
-      const int ngrp = ((S - 1) * SBW + 31) / 32, nbulk = S > 1 ? std::max(1, std::min(h->n_cu - S, ngrp)) : 0;
-      hipLaunchKernelGGL(k_chol_backsolve_all<true>, dim3(S + nbulk), dim3(SUPER_THREADS),
-                         BACKSOLVE_LDS, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles, h->d_Lblk, d_x, h->d_flag,
-                         h->d_bar, h->barrier_polls);
-    } else
-    for (int jS = ((D - 1) / SBW) * SBW; jS >= 0; jS -= SBW) {
-      const int jE = std::min(jS + SBW, D), jE2 = std::min(jE + SBW, D);
-      const int nwg = (jE == D) ? 1 : 1 + (jS + 255) / 256;
-      hipLaunchKernelGGL(k_chol_backsolve, dim3(nwg), dim3(256), 0, h->stream, h->d_Ared, ld, D, m, h->gauge_axis, h->d_Ztiles,
-                         h->d_Lblk + (size_t)(jS / SBW) * SBW * SBW, d_x, jS, jE, jE2);
-    }
-    launch_expand();
-  };
-  launch_solve(h->chol_onepass);
-  MVBA_HIP(hipGetLastError());
-  const int trial = 1 - h->cur;
-  auto launch_tail = [&]() {  // K6a + K5/K6: trial cameras, back-substitution, trial cost
-    Timed t(h, MVBA_K_BACKSUB_COST);
-    hipLaunchKernelGGL(k_update_cams, dim3((m + 63) / 64), dim3(64), 0, h->stream, m, h->d_cam15[h->cur], h->d_dxi,
-                       h->d_cam15[trial]);
-    if (h->N) {
-      const size_t lds = h->gcam ? 0 : (size_t)m * (CAM_LDS + DXI_LDS) * sizeof(double);
-      cam_tables(h, h->d_cam15[h->cur], h->d_dxi);
-      const double deg = (double)h->nobs / (double)h->N;  // lanes per point by mean degree
-      const int G = deg <= 40.0 ? 2 : (deg <= 100.0 ? 4 : 8);
-      // (a camera table above half the LDS leaves one block per CU: 1024 threads then, so that the CU still holds 16 waves)
-      // (16 waves per CU is what the registers allow: 256-thread blocks reach it while four of them fit -- tables up to 40 KiB,
-      // ~180 cameras --, 512-thread blocks while two fit, one 1024-thread block beyond)
-      const bool wide = lds > 80 * 1024, mid = !wide && lds > 40 * 1024;
-      const int bt = wide ? 1024 : (mid ? 512 : 256);
-      const int nblk = (int)std::min<long long>(4096 * 256 / bt, (h->N * G + bt - 1) / bt);
-      auto kern = h->gcam ? (G == 2 ? k_backsub<2, 256, true> : (G == 4 ? k_backsub<4, 256, true> : k_backsub<8, 256, true>))
-                  : wide ? (G == 2 ? k_backsub<2, 1024> : (G == 4 ? k_backsub<4, 1024> : k_backsub<8, 1024>))
-                  : mid ? (G == 2 ? k_backsub<2, 512> : (G == 4 ? k_backsub<4, 512> : k_backsub<8, 512>))
-                        : (G == 2 ? k_backsub<2> : (G == 4 ? k_backsub<4> : k_backsub<8>));
-      if (h->loss != LOSS_SQUARED) {
-        auto kr = h->gcam ? (G == 2 ? k_backsub<2, 256, true, true, LossArgs> : (G == 4 ? k_backsub<4, 256, true, true, LossArgs> : k_backsub<8, 256, true, true, LossArgs>))
-                  : wide ? (G == 2 ? k_backsub<2, 1024, false, true, LossArgs> : (G == 4 ? k_backsub<4, 1024, false, true, LossArgs> : k_backsub<8, 1024, false, true, LossArgs>))
-                  : mid ? (G == 2 ? k_backsub<2, 512, false, true, LossArgs> : (G == 4 ? k_backsub<4, 512, false, true, LossArgs> : k_backsub<8, 512, false, true, LossArgs>))
-                        : (G == 2 ? k_backsub<2, 256, false, true, LossArgs> : (G == 4 ? k_backsub<4, 256, false, true, LossArgs> : k_backsub<8, 256, false, true, LossArgs>));
-        hipLaunchKernelGGL(kr, dim3(nblk), dim3(bt), lds, h->stream, h->N, m, h->d_pt_ptr, h->d_cam, h->d_PB, h->d_dxi,
-                           h->d_X[h->cur], h->d_cam15[h->cur], h->f0, h->d_X[trial], h->d_dX, h->d_cam18, h->d_dxi10,
-                           LossArgs{h->loss_b, h->d_sqw});
-      } else
-      hipLaunchKernelGGL(kern, dim3(nblk), dim3(bt), lds, h->stream, h->N, m, h->d_pt_ptr, h->d_cam, h->d_PB, h->d_dxi,
-                         h->d_X[h->cur], h->d_cam15[h->cur], h->f0, h->d_X[trial], h->d_dX, h->d_cam18, h->d_dxi10);
-    }
-    // K6: trial cost = the residual-only pass at the trial state (fixed grid, fixed tree: deterministic)
-    launch_cost_kernel(h, h->d_cam15[trial], h->d_X[trial]);
-    double *mail = cost_mail(h);  // (advances cost_seq: sequenced before the launch reads it)
-    const unsigned long long seq = h->cost_seq;
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, h->stream, h->d_partials, h->cost_grid, h->d_cost, h->d_flag, mail, seq);
-  };
-  launch_tail();
+  int rc = allreduce_Ab(h, true);
+  if (rc) return rc;
+  launch_solve(h, h->chol_onepass);
   MVBA_HIP(hipGetLastError());
   h->stats.n_try_step++;
-  int rc = global_cost(h, E_trial);
+  rc = launch_tail_and_cost(h, E_trial);
   if (rc) return rc;
   if ((*h->h_flag & 8) && !(*h->h_flag & 1)) {
     // A wait of the persistent back-substitution gave up: its grid was not co-resident (another
@@ -4348,46 +3726,15 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     MVBA_HIP(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
     h->chol_onepass = false;
     h->stats.n_barrier_fallback++;
-    launch_solve(false);
-    launch_tail();
-    MVBA_HIP(hipGetLastError());
-    rc = global_cost(h, E_trial);
+    launch_solve(h, false);
+    rc = launch_tail_and_cost(h, E_trial);
     if (rc) return rc;
   }
-  if ((*h->h_flag & 2) && !(*h->h_flag & (1 | 8))) {
-    // The Cholesky met a non-positive pivot: the reduced system is not positive definite (e.g. a
-    // negative damping factor).  The reference's np.linalg.solve is LU with partial pivoting and
-    // does not care, so redo the solve that way (slow path, rare) and the tail of the step.
-    if (!h->d_lu) {
-      int rc_ = dmalloc(&h->d_lu, (size_t)h->D * (h->D + 1));  // (the default map's size: any map fits)
-      if (rc_) return rc_;
-      rc_ = dmalloc(&h->d_ipiv, (size_t)h->D);
-      if (rc_) return rc_;
-    }
-    MVBA_HIP(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
-    {
-      Timed t(h, MVBA_K_SOLVE);
-      if (h->mapped) {
-        hipLaunchKernelGGL(k_map_full, dim3((D + 1 + 255) / 256, D), dim3(256), 0, h->stream, D, m, d_A, d_b, h->d_map_ptr, h->d_map_mem, h->d_lu);
-        launch_map_tied(h, h->d_lu, D + 1, 1);
-      } else
-      hipLaunchKernelGGL(k_compact_full, dim3((D + 1 + 255) / 256, D), dim3(256), 0, h->stream, D, m, h->gauge_axis, d_A, d_b, h->d_lu);
-      for (int j0 = 0; j0 < D; j0 += LU_NB) {
-        const int nb = std::min(LU_NB, D - j0), right = D + 1 - (j0 + nb);  // columns right of the panel incl. the rhs
-        hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(1024), 0, h->stream, h->d_lu, D, j0, nb, h->d_ipiv, h->d_flag);
-        hipLaunchKernelGGL(k_lu_swap, dim3((D + 1 - nb + 255) / 256), dim3(256), 0, h->stream, h->d_lu, D, j0, nb, h->d_ipiv);
-        if (right > 0) hipLaunchKernelGGL(k_lu_trsm, dim3((right + 255) / 256), dim3(256), 0, h->stream, h->d_lu, D, j0, nb);
-        const int below = D - (j0 + nb);
-        if (below > 0)
-          hipLaunchKernelGGL(k_lu_gemm, dim3((right + 63) / 64, (below + 63) / 64), dim3(256), 0, h->stream, h->d_lu, D, j0, nb);
-      }
-      hipLaunchKernelGGL(k_lu_backsub, dim3(1), dim3(1024), 0, h->stream, h->d_lu, D, m, h->gauge_axis, d_x);
-      launch_expand();
-    }
+  if ((*h->h_flag & 2) && !(*h->h_flag & (1 | 8))) {  // not positive definite: LU with partial pivoting, and the tail again
+    rc = launch_lu_solve(h);
+    if (rc) return rc;
     h->stats.n_lu_fallback++;
-    launch_tail();
-    MVBA_HIP(hipGetLastError());
-    rc = global_cost(h, E_trial);
+    rc = launch_tail_and_cost(h, E_trial);
     if (rc) return rc;
   }
   if (*h->h_flag) {
@@ -4397,47 +3744,8 @@ int mvba_try_step(mvba_handle *h, double c, double *E_trial) {
     return fail(MVBA_ERR_SINGULAR, (fl & 1) ? "Singular matrix" : "Singular matrix (reduced camera system)");
   }
   if (h->check_solve) {
-    // Debug mode (MVBA_CHECK_SOLVE=1, read in mvba_create): the residual of the reduced system, b - A dxi over the kept parameters,
-    // from the packed [A|b] the solve started from (it is intact: k_compact copied it) and the dxi it produced -- on the host, in
-    // plain loops.  The persistent back-substitution orders its hand-overs with sc1 accesses and explicit waits, not with the
-    // memory model's fences: a stale read there would be a silently wrong camera step, which this catches.
-    std::vector<double> Ab(nA + n9), x(n9);
-    MVBA_HIP(hipMemcpyAsync(Ab.data(), h->d_Ab, sizeof(double) * (nA + n9), hipMemcpyDeviceToHost, h->stream));
-    MVBA_HIP(hipMemcpyAsync(x.data(), h->d_dxi, sizeof(double) * n9, hipMemcpyDeviceToHost, h->stream));
-    MVBA_HIP(hipStreamSynchronize(h->stream));
-    auto kept = [&](size_t g) { return !((g >= 3 && g <= 8) || g == (size_t)(12 + h->gauge_axis)); };
-    std::vector<double> r(n9, 0.0), an(n9, 0.0);  // r = A x, an = |A| |x|  (rows of the full symmetric matrix from the packed upper strips)
-    for (int k = 0; k < m; ++k) {
-      const double *Ak = Ab.data() + strip_offset(k, m);
-      const int Wk = 9 * (m - k);
-      for (int i = 0; i < 9; ++i)
-        for (int c = 0; c < Wk; ++c) {
-          const size_t gi = 9 * (size_t)k + i, gj = 9 * (size_t)k + c;
-          const double a = Ak[(size_t)i * Wk + c];
-          r[gi] += a * x[gj]; an[gi] += std::fabs(a * x[gj]);
-          if (c >= 9) { r[gj] += a * x[gi]; an[gj] += std::fabs(a * x[gi]); }  // the mirror image below the diagonal blocks
-        }
-    }
-    double worst = 0.0;
-    if (h->mapped) {  // the mapped system's residual P^T (b - A P x): x above is dxi = P x, rows summed over an unknown's members
-      for (int j = 0; j < D; ++j) {
-        double res = 0.0, scale = 0.0;
-        for (int q = h->map_ptr[j]; q < h->map_ptr[j + 1]; ++q) {
-          const size_t g = (size_t)h->map_mem[q];
-          res += Ab[nA + g] - r[g];
-          scale += an[g] + std::fabs(Ab[nA + g]);
-        }
-        worst = std::max(worst, scale > 0.0 ? std::fabs(res) / scale : 0.0);
-      }
-    } else
-    for (size_t g = 0; g < n9; ++g)
-      if (kept(g)) {
-        const double bg = Ab[nA + g], scale = an[g] + std::fabs(bg);
-        worst = std::max(worst, scale > 0.0 ? std::fabs(bg - r[g]) / scale : 0.0);
-      }
-    if (!(worst <= h->check_solve_tol))
-      return fail(MVBA_ERR_STATE, "MVBA_CHECK_SOLVE: the dense solve left a relative residual of " + std::to_string(worst) +
-                                      " on the reduced camera system (a stale hand-over in the back-substitution?)");
+    rc = check_solve_residual(h);
+    if (rc) return rc;
   }
   h->have_trial = true;
   return MVBA_OK;
@@ -4511,31 +3819,27 @@ int mvba_set_parameter_map(mvba_handle *h, const int32_t *col, int32_t n_free) {
   int2 *d_pairs = nullptr;
   double *d_part = nullptr;
   if (!pairs.empty()) {
-    int rc = dmalloc(&d_pairs, pairs.size());
-    if (!rc) rc = dmalloc(&d_part, pairs.size() * (size_t)nblk);
+    int rc = h->mem.alloc(&d_pairs, pairs.size());
+    if (!rc) rc = h->mem.alloc(&d_part, pairs.size() * (size_t)nblk);
     if (rc) {
-      if (d_pairs) hipFree(d_pairs);
+      h->mem.release(d_pairs);
       return rc;
     }
   }
   if (!h->d_map_col) {
-    int rc = dmalloc(&h->d_map_col, (size_t)n9);
-    if (!rc) rc = dmalloc(&h->d_map_ptr, (size_t)h->D + 1);
-    if (!rc) rc = dmalloc(&h->d_map_mem, (size_t)n9);
-    if (!rc) rc = dmalloc(&h->d_map_x, (size_t)n9 + 16);  // (the back-substitution clears 9m slots, or slots 3..8 and 12 + axis)
+    int rc = h->mem.alloc(&h->d_map_col, (size_t)n9);
+    if (!rc) rc = h->mem.alloc(&h->d_map_ptr, (size_t)h->D + 1);
+    if (!rc) rc = h->mem.alloc(&h->d_map_mem, (size_t)n9);
+    if (!rc) rc = h->mem.alloc(&h->d_map_x, (size_t)n9 + 16);  // (the back-substitution clears 9m slots, or slots 3..8 and 12 + axis)
     if (rc) {
-      for (void **q : {(void **)&h->d_map_col, (void **)&h->d_map_ptr, (void **)&h->d_map_mem, (void **)&h->d_map_x}) {
-        if (*q) hipFree(*q);
-        *q = nullptr;
-      }
-      if (d_pairs) hipFree(d_pairs);
-      if (d_part) hipFree(d_part);
+      h->mem.release(h->d_map_col); h->mem.release(h->d_map_ptr); h->mem.release(h->d_map_mem); h->mem.release(h->d_map_x);
+      h->mem.release(d_pairs); h->mem.release(d_part);
       return rc;
     }
   }
   MVBA_HIP(hipStreamSynchronize(h->stream));  // nothing in flight reads the tables that are replaced now
-  if (h->d_map_pairs) hipFree(h->d_map_pairs);
-  if (h->d_map_part) hipFree(h->d_map_part);
+  h->mem.release(h->d_map_pairs);
+  h->mem.release(h->d_map_part);
   h->d_map_pairs = d_pairs;
   h->d_map_part = d_part;
   h->n_map_pairs = (int)pairs.size();
@@ -4560,7 +3864,7 @@ int mvba_residuals(mvba_handle *h, double *e) {
   MVBA_HIP(hipSetDevice(h->device));
   if (!h->nobs) return MVBA_OK;
   if (!h->d_resid) {
-    int rc = dmalloc(&h->d_resid, h->nobs);
+    int rc = h->mem.alloc(&h->d_resid, h->nobs);
     if (rc) return rc;
   }
   const size_t lds = h->gcam ? 0 : (size_t)h->m * CAM_LDS * sizeof(double);
@@ -4586,18 +3890,15 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
   // First call: the camera-block table, the trtri panels, the point and camera blocks -- all four or none (a failed
   // allocation frees what it got, so that a later call never runs with some of them missing)
   auto free_cov = [&]() {
-    for (double **q : {&h->d_cov_sig, &h->d_cov_panel, &h->d_cov_pts, &h->d_cov_cam}) {
-      if (*q) hipFree(*q);
-      *q = nullptr;
-    }
+    for (double **q : {&h->d_cov_sig, &h->d_cov_panel, &h->d_cov_pts, &h->d_cov_cam}) h->mem.release(*q);
   };
   int local_rc = MVBA_OK;
   if (!h->d_cov_sig || !h->d_cov_panel || !h->d_cov_pts || !h->d_cov_cam) {
     free_cov();
-    local_rc = dmalloc(&h->d_cov_sig, n_sig);
-    if (!local_rc) local_rc = dmalloc(&h->d_cov_panel, 2 * (size_t)h->D * NB);
-    if (!local_rc) local_rc = dmalloc(&h->d_cov_pts, 6 * (size_t)h->N);
-    if (!local_rc) local_rc = dmalloc(&h->d_cov_cam, 81 * (size_t)m);
+    local_rc = h->mem.alloc(&h->d_cov_sig, n_sig);
+    if (!local_rc) local_rc = h->mem.alloc(&h->d_cov_panel, 2 * (size_t)h->D * NB);
+    if (!local_rc) local_rc = h->mem.alloc(&h->d_cov_pts, 6 * (size_t)h->N);
+    if (!local_rc) local_rc = h->mem.alloc(&h->d_cov_cam, 81 * (size_t)m);
     if (local_rc) free_cov();
   }
   hipEvent_t ev[5] = {};
@@ -4607,7 +3908,7 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
   // With a parameter map k_cov_lauum scatters Sigma' (D' x D') through keep_index into a scratch table of mv camera blocks per side
   // (mv <= m); k_map_cov_expand then fills the real table with P Sigma' P^T.
   const int mv = (D + 6) / 9 + 1;
-  if (!local_rc && h->mapped && D > 0 && !h->d_cov_sigv) local_rc = dmalloc(&h->d_cov_sigv, n_sig);
+  if (!local_rc && h->mapped && D > 0 && !h->d_cov_sigv) local_rc = h->mem.alloc(&h->d_cov_sigv, n_sig);
   const bool sharded = h->comm || h->host_ar;
   if (local_rc && !sharded) return local_rc;
   const std::string local_err = local_rc ? g_err : std::string();
@@ -4730,7 +4031,7 @@ int mvba_snapshot(mvba_handle *h) {
   const size_t slab = (size_t)(h->n_snap / SNAP_SLAB);
   if (slab >= h->snap_slabs.size()) {
     double *p = nullptr;
-    int rc = dmalloc(&p, stride * SNAP_SLAB);
+    int rc = h->mem.alloc(&p, stride * SNAP_SLAB);
     if (rc) return rc;
     h->snap_slabs.push_back(p);
   }
@@ -4843,7 +4144,7 @@ int mvba_comm_init(mvba_handle *h, const void *id128, int32_t rank, int32_t n_ra
   if (r != ncclSuccess) return fail(MVBA_ERR_RCCL, std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r));
   h->rank = rank; h->nranks = n_ranks;
   h->rccl_version = g_rccl.version;
-  int rc = dmalloc(&h->d_allcost, 2 * (size_t)n_ranks);
+  int rc = h->mem.alloc(&h->d_allcost, 2 * (size_t)n_ranks);
   if (rc) return rc;
   MVBA_HIP(hipHostMalloc((void **)&h->h_allcost, 2 * sizeof(double) * n_ranks));
   return MVBA_OK;
@@ -4983,20 +4284,20 @@ int mvba_project(const double *X, int64_t n_points, const double *K, const doubl
   double *dX = nullptr, *dK = nullptr, *dR = nullptr, *dt = nullptr;
   double2 *dxy = nullptr;
   int *dpt = nullptr, *dcam = nullptr;
-  auto cleanup = [&]() { for (void *q : {(void *)dX, (void *)dK, (void *)dR, (void *)dt, (void *)dxy, (void *)dpt, (void *)dcam}) if (q) hipFree(q); };
-#define PRJ(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(MVBA_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-  PRJ(hipMalloc((void **)&dX, sizeof(double) * 3 * std::max<int64_t>(n_points, 1)));
-  PRJ(hipMalloc((void **)&dK, sizeof(double) * 9 * n_images));
-  PRJ(hipMalloc((void **)&dR, sizeof(double) * 9 * n_images));
-  PRJ(hipMalloc((void **)&dt, sizeof(double) * 3 * n_images));
-  PRJ(hipMalloc((void **)&dxy, sizeof(double2) * n_obs));
+  DevBufs tmp;  // (freed on every return)
+#define PRJ(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MVBA_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+  PRJ(hipMalloc((void **)&dX, sizeof(double) * 3 * std::max<int64_t>(n_points, 1))); tmp.own(dX);
+  PRJ(hipMalloc((void **)&dK, sizeof(double) * 9 * n_images)); tmp.own(dK);
+  PRJ(hipMalloc((void **)&dR, sizeof(double) * 9 * n_images)); tmp.own(dR);
+  PRJ(hipMalloc((void **)&dt, sizeof(double) * 3 * n_images)); tmp.own(dt);
+  PRJ(hipMalloc((void **)&dxy, sizeof(double2) * n_obs)); tmp.own(dxy);
   PRJ(hipMemcpy(dX, X, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice));
   PRJ(hipMemcpy(dK, K, sizeof(double) * 9 * n_images, hipMemcpyHostToDevice));
   PRJ(hipMemcpy(dR, R, sizeof(double) * 9 * n_images, hipMemcpyHostToDevice));
   PRJ(hipMemcpy(dt, t, sizeof(double) * 3 * n_images, hipMemcpyHostToDevice));
   if (pt_ptr) {
-    PRJ(hipMalloc((void **)&dpt, sizeof(int) * n_obs));
-    PRJ(hipMalloc((void **)&dcam, sizeof(int) * n_obs));
+    PRJ(hipMalloc((void **)&dpt, sizeof(int) * n_obs)); tmp.own(dpt);
+    PRJ(hipMalloc((void **)&dcam, sizeof(int) * n_obs)); tmp.own(dcam);
     PRJ(hipMemcpy(dpt, obs_pt.data(), sizeof(int) * n_obs, hipMemcpyHostToDevice));
     PRJ(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
   }
@@ -5007,7 +4308,6 @@ int mvba_project(const double *X, int64_t n_points, const double *K, const doubl
   PRJ(hipGetLastError());
   PRJ(hipMemcpy(xy, dxy, sizeof(double2) * n_obs, hipMemcpyDeviceToHost));
 #undef PRJ
-  cleanup();
   return MVBA_OK;
 }
 
