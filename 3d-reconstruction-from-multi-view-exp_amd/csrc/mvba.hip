@@ -3023,6 +3023,7 @@ struct mvba_handle {
   double loss_b = 0.0;
   double *d_sqw = nullptr;
   double2 *d_resid = nullptr;  // mvba_residuals, allocated on the first call
+  double *d_init_cams = nullptr;  // mvba_triangulate_state, allocated on the first call: the committed cameras as K, R, t ([m][9 + 9 + 3])
   // parameter map (mvba_set_parameter_map); mapped == false: the default map, none of this is touched.
   // n_free unknowns, the first map_U of them untied; col / CSR transpose on the device (allocated on the first map), the
   // scratch vector the back-substitution scatters x into, the scratch camera-block table of a mapped mvba_covariance
@@ -4324,3 +4325,5 @@ int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2,
 }
 
 }  // extern "C"
+
+#include "mvba_init.h"  // initial estimates: mvba_triangulate, mvba_triangulate_state, mvba_resect

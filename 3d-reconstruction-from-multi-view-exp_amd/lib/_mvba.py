@@ -89,6 +89,11 @@ SIGNATURES = {
     "mvba_comm_init_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mvba_debug_read": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.c_int64, C.POINTER(C.c_int64)]),
     "mvba_host_obs_math": (C.c_int, [_dp, _dp, _dp, C.c_double, _dp]),
+    "mvba_triangulate": (C.c_int, [_dp, _dp, _dp, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64,
+                                   C.c_int32, _dp, _dp, C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_triangulate_state": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int32), _dp]),
+    "mvba_resect": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int32,
+                              C.POINTER(C.c_uint8), _dp, _dp, C.POINTER(C.c_int32), _dp, C.c_int32]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -292,6 +297,19 @@ class HipEngine:
             out["cameras_full"] = Cf
         return out
 
+    def triangulate(self, n_refine=2):
+        """Replace the committed points by their triangulation from the committed cameras and the engine's own
+        observations (mvba_triangulate_state: nothing is uploaded).  Returns ``(quality (n, 3), status (n,), timings_ms)``
+        as ``triangulate`` below (the RMS residual in the units of the engine's xy, whatever f0 is); a point whose status is
+        not 0 keeps its coordinates.  Voids the linearisation and the
+        trial.  Sharded engines: each rank triangulates its own points."""
+        q = np.empty((self.n, 3))
+        st = np.empty(self.n, np.int32)
+        tm = np.zeros(3)
+        raise_for(self.lib.mvba_triangulate_state(self._h, int(n_refine), _ptr(q), st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm)),
+                  self.lib)
+        return q, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+
     def residuals(self):
         """(n_obs, 2) residuals f0 e_o in image units at the committed state, in the engine's observation order."""
         e = np.empty((self.n_obs, 2))
@@ -381,6 +399,67 @@ def project(X, K, R, t, pt_ptr=None, cam_idx=None, device=-1):
                               cam_idx.ctypes.data_as(C.POINTER(C.c_int32)), cam_idx.shape[0], _ptr(out), int(device))
     raise_for(rc, lib)
     return out
+
+
+def triangulate(K, R, t, pt_ptr, cam_idx, xy, n_refine=2, device=-1):
+    """Device triangulation of every point from known cameras (mvba_triangulate), the inverse of ``project``.  With an
+    observation list (pt_ptr, cam_idx, xy (n_obs, 2)), or ``pt_ptr=None`` and xy (N, m, 2): the dense grid.  xy is in the
+    units K projects to: with raw image coordinates and the engine's f, u that is K[2, 2] = 1 (``intrinsics_from`` writes f0
+    there, which projects to x / f0).  Returns
+    ``X (N, 3), quality (N, 3), status (N,), timings_ms``: status 0 ok, 1 fewer than two observations, 2 no parallax,
+    3 at infinity / not finite (X is NaN then); quality = RMS reprojection residual, smallest depth, largest angle between
+    two viewing rays (radians).  No CPU fallback."""
+    lib = load_library()
+    if device_count() < 1:
+        raise RuntimeError("libmvba: no HIP device visible; mvba_triangulate has no CPU fallback")
+    K, R, t, xy = (_as(v, np.float64) for v in (K, R, t, xy))
+    m = K.shape[0]
+    assert K.shape == (m, 3, 3) and R.shape == (m, 3, 3) and t.shape == (m, 3)
+    if pt_ptr is None:
+        assert xy.ndim == 3 and xy.shape[1:] == (m, 2)
+        n, n_obs, pp, cp = xy.shape[0], xy.shape[0] * m, None, None
+    else:
+        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
+        xy = xy.reshape(-1, 2)
+        assert xy.shape[0] == cam_idx.shape[0]
+        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    X, q, st, tm = np.empty((n, 3)), np.empty((n, 3)), np.empty(n, np.int32), np.zeros(3)
+    raise_for(lib.mvba_triangulate(_ptr(K), _ptr(R), _ptr(t), m, n, pp, cp, _ptr(xy), n_obs, int(n_refine), _ptr(X), _ptr(q),
+                                   st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm), int(device)), lib)
+    return X, q, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+
+
+def resect(X, pt_ptr, cam_idx, xy, n_images, point_ok=None, device=-1):
+    """Device resection of every camera from known points (mvba_resect): the normalised DLT.  The list as for ``triangulate``
+    (``pt_ptr=None`` with xy (N, m, 2): the dense grid).  ``point_ok`` (N,) marks the points to use (default: those whose X
+    is finite).  Returns ``P (m, 3, 4)`` -- it projects to the units of the xy given -- with |P[2, :3]| = 1 and
+    det P[:, :3] > 0, ``quality (m, 2)`` (RMS reprojection residual, eigenvalue ratio), ``status (m,)`` (0 ok, 1 fewer than 6
+    usable observations, 2 degenerate; P is NaN then), ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    if device_count() < 1:
+        raise RuntimeError("libmvba: no HIP device visible; mvba_resect has no CPU fallback")
+    X, xy = _as(X, np.float64), _as(xy, np.float64)
+    n, m = X.shape[0], int(n_images)
+    assert X.shape == (n, 3)
+    if pt_ptr is None:
+        assert xy.shape == (n, m, 2)
+        n_obs, pp, cp = n * m, None, None
+    else:
+        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
+        xy = xy.reshape(-1, 2)
+        assert pt_ptr.shape == (n + 1,) and xy.shape[0] == cam_idx.shape[0]
+        n_obs = cam_idx.shape[0]
+        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    okp = None
+    if point_ok is not None:
+        ok = _as(np.asarray(point_ok) != 0, np.uint8)
+        assert ok.shape == (n,)
+        okp = ok.ctypes.data_as(C.POINTER(C.c_uint8))
+    P, q, st, tm = np.empty((m, 3, 4)), np.empty((m, 2)), np.empty(m, np.int32), np.zeros(3)
+    raise_for(lib.mvba_resect(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, _ptr(P), _ptr(q), st.ctypes.data_as(C.POINTER(C.c_int32)),
+                              _ptr(tm), int(device)), lib)
+    return P, q, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
 
 
 def host_obs_math(X3, cam15, xy2, f0):

@@ -279,7 +279,7 @@ class BundleAdjuster:
     def __init__(
         self,
         x: npt.NDArray,
-        init_X: npt.NDArray,
+        init_X: npt.NDArray | None,
         init_K: npt.NDArray,
         init_R: npt.NDArray,
         init_t: npt.NDArray,
@@ -299,7 +299,10 @@ class BundleAdjuster:
         (``share_groups`` for a rig of several), ``hold="pose"`` / ``"cameras"`` to refine the structure only.  Tied
         parameters must start equal (``init_K[:, 0, 0]``, ``init_K[:, :2, 2]`` within a group).  A held pose is held in
         the gauge frame BA works in, i.e. relative to camera 0 and the camera-0/1 baseline: the output poses equal the
-        input poses up to the rounding of the frame change."""
+        input poses up to the rounding of the frame change.
+        ``init_X=None``: the points start from their triangulation from the initial cameras, on the device
+        (``HipEngine.triangulate``); ValueError if a point cannot be triangulated (seen once, no parallax,
+        at infinity) -- ``lib.initialization.triangulate_points`` tells which, to filter the list first."""
         check_loss(loss, loss_scale)  # (ValueError before any work)
         x = np.asarray(x)
         self._check_map(x.shape[1], axis, init_K, hold, share, share_groups)
@@ -313,7 +316,7 @@ class BundleAdjuster:
                           loss_scale: float | None = None, hold=None, share=None, share_groups=None, **engine_kw):
         """Extension for sizes where the dense (N,m,2) array cannot exist
         (SURVEY 8f rank 1): observation list in CSR-by-point form.  ``loss`` / ``loss_scale`` / ``hold`` / ``share`` /
-        ``share_groups``: as for the constructor."""
+        ``share_groups`` / ``init_X=None``: as for the constructor."""
         check_loss(loss, loss_scale)
         self = cls.__new__(cls)
         self._check_map(n_images, axis, init_K, hold, share, share_groups)
@@ -361,7 +364,9 @@ class BundleAdjuster:
         self._loss, self._loss_scale = loss, loss_scale
         if loss != "squared":  # (the squared loss keeps the engine's plain constructor call)
             engine_kw = dict(engine_kw, loss=loss, loss_scale=loss_scale)
-        init_X, init_K = np.asarray(init_X, dtype=np.float64), np.asarray(init_K, dtype=np.float64)
+        triangulate = init_X is None  # (the gauge transform of the cameras needs cameras 0 and 1 alone)
+        init_X = np.zeros((0, 3)) if triangulate else np.asarray(init_X, dtype=np.float64)
+        init_K = np.asarray(init_K, dtype=np.float64)
         init_R, init_t = np.asarray(init_R, dtype=np.float64), np.asarray(init_t, dtype=np.float64)
         # camera-0 pose and baseline length for the way back (ref :23-33)
         if axis == "x-right_z-forward":
@@ -375,7 +380,17 @@ class BundleAdjuster:
         self._f0 = f0
         self._n_points, self._n_images = int(n_points), int(n_images)
         self._engine = self._make_engine(self._n_points, self._n_images, pt_ptr, cam_idx, xy, f0, axis, **engine_kw)
+        if triangulate:
+            X = np.zeros((self._n_points, 3))
         self._engine.set_params(X, init_K[:, 0, 0], init_K[:, :2, 2], t, R)  # ref :45-48
+        if triangulate:
+            _, status, _ = self._engine.triangulate()
+            bad = np.nonzero(np.asarray(status) != 0)[0]
+            if len(bad):
+                self._engine.close()  # (its device buffers go now, not at garbage collection)
+                raise ValueError(f"init_X=None: {len(bad)} of {self._n_points} points cannot be triangulated from the initial cameras "
+                                 f"(first: point {int(bad[0])}, status {int(status[bad[0]])}: 1 fewer than two observations, 2 no "
+                                 f"parallax, 3 at infinity); filter them with lib.initialization.triangulate_points")
         if self._map is not None:
             self._engine.set_parameter_map(self._map[0], self._map[1])
         self._engine_frame = "gauge"  # the frame of the engine's state: "input" once optimize() has applied the way back

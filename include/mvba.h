@@ -223,6 +223,53 @@ int mvba_debug_read(mvba_handle *h, int32_t which, double *out, int64_t capacity
 int mvba_project(const double *X, int64_t n_points, const double *K, const double *R, const double *t, int32_t n_images,
                  const int64_t *pt_ptr, const int32_t *cam_idx, int64_t n_obs, double *xy, int32_t device);
 
+/* ---- initial estimates (csrc/mvba_init.h): the two steps that extend a reconstruction ---------------
+ * mvba_triangulate: every point from known cameras, the inverse of mvba_project on noise-free data.  K, R, t, pt_ptr,
+ * cam_idx, xy mean what they mean there (P_k = K_k [R_k^T | -R_k^T t_k] formed in k_project_obs's order of operations,
+ * xy = (p0 / p2, p1 / p2): xy is in the units K projects to -- for raw image coordinates and the engine's f, u that is
+ * K[2][2] = 1, not f0 --); pt_ptr == NULL is the dense grid; the same argument checks (MVBA_ERR_BADARG, the message
+ * gives the offending number) and the same LDS camera table: at most 1704 cameras.
+ * Per point a, observations o in ascending order: the rows x_o P[2] - P[0] and y_o P[2] - P[1], each scaled to unit
+ * length, M_a = sum row^T row (4 x 4), X~ = the eigenvector of its smallest eigenvalue, X = X~[:3] / X~[3]; then n_refine
+ * >= 0 Gauss-Newton steps on sum_o |pi(P_k X) - xy_o|^2 (3 x 3 normal equations, Cholesky), a step taken only if it does
+ * not raise the point's cost, otherwise the point stops.
+ * status [n_points]: 0 ok; 1 fewer than two observations; 2 no parallax (second-smallest eigenvalue of M_a <= 1e-12 x the
+ * largest, the relative pivot rule of mvba_covariance); 3 at infinity (|X~[3]| <= 1e-12 |X~|) or a result that is not
+ * finite.  Where status != 0, X and quality are NaN.
+ * quality [n_points][3]: RMS reprojection residual at the returned X in units of xy; the smallest depth
+ * (R_k^T (X - t_k))_z over the point's cameras (<= 0: behind a camera); the largest angle in radians between two of the
+ * point's viewing rays (all pairs: deg^2 / 2 per point, skipped when quality is NULL).
+ * timings_ms [3]: upload, kernel, download.  quality, status, timings_ms may each be NULL.  One thread per point, sums in
+ * ascending observation order, no atomics: two calls give bitwise-identical output. */
+int mvba_triangulate(const double *K, const double *R, const double *t, int32_t n_images, int64_t n_points, const int64_t *pt_ptr,
+                     const int32_t *cam_idx, const double *xy, int64_t n_obs, int32_t n_refine, double *X, double *quality,
+                     int32_t *status, double *timings_ms, int32_t device);
+/* The same on the observations and the COMMITTED cameras the engine already holds (nothing is uploaded), with the BA
+ * camera model K = [[f,0,u],[0,f,v],[0,0,f0]] (which projects to x / f0; the engine's xy are the caller's x, so the rows are
+ * formed with the third row divided by f0, K[2][2] = 1: the same solution, and quality[0] is in the units of xy for any f0):
+ * replaces the committed points; a point with status != 0 keeps its old
+ * coordinates.  Voids the linearisation and the trial, as mvba_set_params does.  Independent of the loss.  Sharded: each
+ * rank does its own points, nothing is communicated.  MVBA_ERR_STATE before the first mvba_set_params; MVBA_ERR_BADARG
+ * above 1704 cameras. */
+int mvba_triangulate_state(mvba_handle *h, int32_t n_refine, double *quality, int32_t *status, double *timings_ms);
+/* mvba_resect: every camera from known points, the normalised DLT.  X [n_points][3]; the list as in mvba_project (pt_ptr ==
+ * NULL: the dense grid); point_ok [n_points] != 0 marks the points to use (NULL: those whose X is finite).
+ * The list is sorted camera-major on the host (a stable counting sort, ascending points inside a camera) and cut into chunks
+ * of 256 observations.  Device pass 1: per camera the count, centroid and mean squared distance of its 3-D points and of its
+ * image points (Hartley: scaled to mean squared distance 3 and 2).  Device pass 2: N_k = sum row^T row of the normalised DLT
+ * rows [X~^T, 0, -x X~^T], [0, X~^T, -y X~^T] -- its 78 unique entries are the 40 sums of (1, x, y, x^2 + y^2) X~ X~^T --
+ * a chunk by a fixed tree, the chunks of a camera in ascending order: two runs are bitwise equal.  The eigenvector of the
+ * smallest eigenvalue (cyclic Jacobi on the host: n_images problems of order 12), the two normalisations undone:
+ * P [n_images][12] row-major 3 x 4 (it projects to the units of the xy given), scaled so that |P[2][:3]| = 1 and det P[:, :3] > 0.
+ * status [n_images]: 0 ok; 1 fewer than 6 usable observations; 2 degenerate, e.g. coplanar points (second-smallest
+ * eigenvalue <= 1e-12 x the largest).  Where status != 0, P is NaN.
+ * quality [n_images][2]: RMS reprojection residual of the camera's used observations (a third device pass; NaN where status
+ * != 0); the eigenvalue ratio lambda_1 / lambda_2 (small: well determined; NaN where status = 1).
+ * timings_ms [3]: sort + upload, kernels, everything else (copies back, eigen-solves).  quality, status, timings_ms may be NULL. */
+int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
+                int32_t n_images, const uint8_t *point_ok, double *P, double *quality, int32_t *status, double *timings_ms,
+                int32_t device);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
