@@ -1,0 +1,387 @@
+// Starting a reconstruction from two views (mvba_covisibility, mvba_two_view) -- kernels and host code, gfx950.
+//
+// Included by mvba.hip after mvba_init.h: uses its sym_eig_jacobi, eig_extremes, init_check_list, init_check_cameras, InitClock
+// and EvGuard, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
+//
+// Co-visibility: ONE THREAD PER POINT walks the pairs of its own camera run (deg^2 / 2 increments) into an m x m table of
+// integer counters -- integer sums are exact in any order, so these are atomics: a per-workgroup table in LDS that is flushed
+// once while m^2 x 4 bytes fit 64 KiB (m <= 128), 64-bit atomics on device memory beyond.  Only k <= l is counted; the host
+// mirrors the triangle.
+//
+// Epipolar moments: one workgroup of 256 threads takes 256 consecutive points for one pair (blockIdx.y: the pair inside the
+// launch's tile of pairs).  A thread finds k and l in its point's ascending camera run by two binary searches, forms its
+// values (or zeros) and the workgroup sums them by the fixed tree of k_resect_chunk; k_twoview_combine adds a pair's chunk
+// partials in an order that depends on the chunk count alone.  No floating-point atomics: two runs are bitwise equal.  The
+// eigen-problems of order 9 are solved on the host (sym_eig_jacobi<9>), as mvba_resect solves its own of order 12.
+
+namespace {
+
+constexpr int TV_CHUNK = 256;                   // points per chunk = threads per workgroup
+constexpr int TV_NORM = 8;                      // per pair: centroid in k (2), scale in k, centroid in l (2), scale in l, count, unused
+constexpr int TV_MIN_SHARED = 8;                // the linear solution needs 8 rows
+constexpr size_t TV_PART_BYTES = 128u << 20;    // chunk partials of one launch: pairs are tiled to stay under this
+constexpr int CV_LDS_CAMERAS = 128;             // m^2 x 4 bytes <= 64 KiB: the co-visibility table lives in LDS
+
+// values per shared point of the four passes: 0 count and first moments, 1 squared distances to the centroids, 2 the 45
+// unique products of the epipolar row, 3 the squared Sampson distance
+__host__ __device__ constexpr int tv_values(int mode) { return mode == 0 ? 5 : (mode == 1 ? 2 : (mode == 2 ? 45 : 1)); }
+
+__global__ __launch_bounds__(256) void k_covisibility(long long npts, int m, const long long *__restrict__ pt_ptr,
+                                                      const int *__restrict__ cam_idx, unsigned long long *__restrict__ count,
+                                                      int use_lds) {
+  extern __shared__ unsigned int s_cv[];  // [m][m] when use_lds (a workgroup sees fewer than 2^31 points: 32 bits hold its counts)
+  if (use_lds) {
+    for (int e = threadIdx.x; e < m * m; e += blockDim.x) s_cv[e] = 0u;
+    __syncthreads();
+  }
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long a = (long long)blockIdx.x * blockDim.x + threadIdx.x; a < npts; a += stride) {
+    const long long o0 = pt_ptr ? pt_ptr[a] : a * m;
+    const int deg = pt_ptr ? (int)(pt_ptr[a + 1] - pt_ptr[a]) : m;
+    for (int i = 0; i < deg; ++i) {
+      const int ci = pt_ptr ? cam_idx[o0 + i] : i;
+      for (int j = i; j < deg; ++j) {
+        const int cj = pt_ptr ? cam_idx[o0 + j] : j;
+        const size_t e = (size_t)min(ci, cj) * m + max(ci, cj);
+        if (use_lds) atomicAdd(&s_cv[e], 1u);
+        else atomicAdd(&count[e], 1ull);
+      }
+    }
+  }
+  if (use_lds) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < m * m; e += blockDim.x) {
+      const unsigned int v = s_cv[e];
+      if (v) atomicAdd(&count[e], (unsigned long long)v);
+    }
+  }
+}
+
+// the observation of camera c in the ascending run cam[o0 .. o0 + deg), or -1; cam == nullptr: the dense grid
+__device__ __forceinline__ long long tv_find(const int *__restrict__ cam, long long o0, int deg, int c) {
+  if (!cam) return o0 + c;
+  int lo = 0, hi = deg;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cam[o0 + mid] < c) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < deg && cam[o0 + lo] == c) ? o0 + lo : -1;
+}
+
+// One workgroup per (chunk of 256 points, pair of the tile): the chunk's sums over the points both cameras see into
+// part[pair][chunk][NV].  aux (per pair of the tile): mode 1, 2 the TV_NORM table, mode 3 F [9].
+template <int MODE>
+__global__ __launch_bounds__(TV_CHUNK) void k_twoview_chunk(long long npts, int m, const long long *__restrict__ pt_ptr,
+                                                            const int *__restrict__ cam_idx, const double2 *__restrict__ xy,
+                                                            const int *__restrict__ pairs, const double *__restrict__ aux,
+                                                            double *__restrict__ part) {
+  constexpr int NV = tv_values(MODE);
+  __shared__ double s_w[TV_CHUNK / 64][NV];
+  const int p = blockIdx.y, i = threadIdx.x;
+  const long long a = (long long)blockIdx.x * TV_CHUNK + i;
+  const int k = pairs[2 * p], l = pairs[2 * p + 1];
+  double v[NV];
+#pragma unroll
+  for (int e = 0; e < NV; ++e) v[e] = 0.0;
+  long long ok = -1, ol = -1;
+  if (a < npts) {
+    const long long o0 = pt_ptr ? pt_ptr[a] : a * m;
+    const int deg = pt_ptr ? (int)(pt_ptr[a + 1] - pt_ptr[a]) : m;
+    const int *cam = pt_ptr ? cam_idx : nullptr;
+    ok = tv_find(cam, o0, deg, k);
+    if (ok >= 0) ol = tv_find(cam, o0, deg, l);
+  }
+  if (ok >= 0 && ol >= 0) {
+    const double2 zk = xy[ok], zl = xy[ol];
+    if constexpr (MODE == 0) {
+      v[0] = 1.0; v[1] = zk.x; v[2] = zk.y; v[3] = zl.x; v[4] = zl.y;
+    } else if constexpr (MODE == 1) {
+      const double *nm = aux + TV_NORM * (size_t)p;
+      const double d0 = zk.x - nm[0], d1 = zk.y - nm[1], e0 = zl.x - nm[3], e1 = zl.y - nm[4];
+      v[0] = d0 * d0 + d1 * d1;
+      v[1] = e0 * e0 + e1 * e1;
+    } else if constexpr (MODE == 2) {
+      const double *nm = aux + TV_NORM * (size_t)p;
+      const double xk = nm[2] * (zk.x - nm[0]), yk = nm[2] * (zk.y - nm[1]);
+      const double xl = nm[5] * (zl.x - nm[3]), yl = nm[5] * (zl.y - nm[4]);
+      const double r[9] = {xl * xk, xl * yk, xl, yl * xk, yl * yk, yl, xk, yk, 1.0};
+      int e = 0;
+#pragma unroll
+      for (int b = 0; b < 9; ++b)
+#pragma unroll
+        for (int c = b; c < 9; ++c, ++e) v[e] = r[b] * r[c];
+    } else {
+      const double *F = aux + 9 * (size_t)p;
+      const double f0 = F[0] * zk.x + F[1] * zk.y + F[2], f1 = F[3] * zk.x + F[4] * zk.y + F[5], f2 = F[6] * zk.x + F[7] * zk.y + F[8];
+      const double g0 = F[0] * zl.x + F[3] * zl.y + F[6], g1 = F[1] * zl.x + F[4] * zl.y + F[7];
+      const double r = zl.x * f0 + zl.y * f1 + f2;
+      v[0] = r * r / (f0 * f0 + f1 * f1 + g0 * g0 + g1 * g1);
+    }
+  }
+  // the fixed tree of k_resect_chunk: lanes l and l + off inside a wave, off = 32 .. 1, then the waves in ascending order
+#pragma unroll
+  for (int e = 0; e < NV; ++e) {
+    double x = v[e];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    if ((i & 63) == 0) s_w[i >> 6][e] = x;
+  }
+  __syncthreads();
+  if (i < NV) {
+    double x = s_w[0][i];
+#pragma unroll
+    for (int w = 1; w < TV_CHUNK / 64; ++w) x += s_w[w][i];
+    part[((size_t)p * gridDim.x + blockIdx.x) * NV + i] = x;
+  }
+}
+
+// out[p][e] = the sum of pair p's chunk partials: one wave per (p, e); lane j adds the chunks j, j + 64, ... in ascending
+// order, then the lanes are added by the shuffle tree -- an order that the chunk count fixes
+__global__ __launch_bounds__(256) void k_twoview_combine(int n_pairs, int nv, int n_chunks, const double *__restrict__ part,
+                                                         double *__restrict__ out, int out_stride) {
+  const long long w = (long long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+  if (w >= (long long)n_pairs * nv) return;  // (whole waves leave: the shuffles below see all 64 lanes)
+  const int p = (int)(w / nv), e = (int)(w - (long long)p * nv), lane = threadIdx.x & 63;
+  double x = 0.0;
+  for (int c = lane; c < n_chunks; c += 64) x += part[((size_t)p * n_chunks + c) * nv + e];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+  if (lane == 0) out[(size_t)p * out_stride + e] = x;
+}
+
+// stage 0: count and centroids from the first moments S [n_pairs][5]; stage 1: the two Hartley scales from S [n_pairs][2]
+__global__ __launch_bounds__(256) void k_twoview_norm(int n_pairs, int stage, const double *__restrict__ S, int s_stride,
+                                                      double *__restrict__ norm) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  double *nm = norm + TV_NORM * (size_t)p;
+  const double *s = S + (size_t)s_stride * p;
+  if (stage == 0) {
+    const double n = s[0];
+    nm[0] = s[1] / n; nm[1] = s[2] / n; nm[3] = s[3] / n; nm[4] = s[4] / n;
+    nm[2] = nm[5] = nm[7] = 0.0;
+    nm[6] = n;
+  } else {
+    nm[2] = sqrt(2.0) / sqrt(s[0] / nm[6]);
+    nm[5] = sqrt(2.0) / sqrt(s[1] / nm[6]);
+  }
+}
+
+// the 45 sums of one pair -> F (normalisation undone, |F| = 1, largest entry positive), status and lambda_1 / lambda_2
+int twoview_solve_pair(const double *S45, const double *nm, double *F, double *ratio) {
+  double A[9][9], V[9][9];
+  int e = 0;
+  for (int b = 0; b < 9; ++b)
+    for (int c = b; c < 9; ++c, ++e) A[b][c] = A[c][b] = S45[e];
+  sym_eig_jacobi<9>(A, V);
+  double l1, l2, lmax, f[9];
+  eig_extremes<9>(A, V, l1, l2, lmax, f);
+  *ratio = l1 / l2;
+  if (!(l2 > INIT_REL_PIVOT * lmax)) return 2;
+  // rank 2: F^ <- F^ (I - v v^T), v the right singular vector of the smallest singular value (eigenvector of F^^T F^)
+  double G[3][3], W[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) G[i][j] = f[i] * f[j] + f[3 + i] * f[3 + j] + f[6 + i] * f[6 + j];
+  sym_eig_jacobi<3>(G, W);
+  double m1, m2, mmax, v[3];
+  eig_extremes<3>(G, W, m1, m2, mmax, v);
+  double H[3][3];
+  for (int i = 0; i < 3; ++i) {
+    const double fv = f[3 * i] * v[0] + f[3 * i + 1] * v[1] + f[3 * i + 2] * v[2];
+    for (int j = 0; j < 3; ++j) H[i][j] = f[3 * i + j] - fv * v[j];
+  }
+  // F = T_l^T F^ T_k with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]]
+  const double ckx = nm[0], cky = nm[1], sk = nm[2], clx = nm[3], cly = nm[4], sl = nm[5];
+  double Q[3][3];
+  for (int i = 0; i < 3; ++i) {
+    Q[i][0] = sk * H[i][0];
+    Q[i][1] = sk * H[i][1];
+    Q[i][2] = H[i][2] - sk * (ckx * H[i][0] + cky * H[i][1]);
+  }
+  double nrm = 0.0, big = 0.0;
+  for (int j = 0; j < 3; ++j) {
+    F[j] = sl * Q[0][j];
+    F[3 + j] = sl * Q[1][j];
+    F[6 + j] = Q[2][j] - sl * (clx * Q[0][j] + cly * Q[1][j]);
+  }
+  for (int j = 0; j < 9; ++j) {
+    nrm += F[j] * F[j];
+    if (fabs(F[j]) > fabs(big)) big = F[j];
+  }
+  const double sc = (big < 0.0 ? -1.0 : 1.0) / sqrt(nrm);
+  bool ok = true;
+  for (int j = 0; j < 9; ++j) {
+    F[j] *= sc;
+    ok = ok && std::isfinite(F[j]);
+  }
+  return ok ? 0 : 2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvba_covisibility(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, int64_t n_obs,
+                      int64_t *count, double *timings_ms, int32_t device) {
+  if (!count) return fail(MVBA_ERR_BADARG, "null argument: count (argument 6)");
+  int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
+  if (rc) return rc;
+  if ((rc = init_check_cameras(n_images))) return rc;
+  if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = 0.0;
+  const int m = n_images;
+  const size_t mm = (size_t)m * m;
+  for (size_t e = 0; e < mm; ++e) count[e] = 0;
+  if (n_points == 0) return MVBA_OK;
+  if (device >= 0) MVBA_HIP(hipSetDevice(device));
+  InitClock clk;
+  DevBufs tmp;
+  long long *dptr = nullptr;
+  int *dcam = nullptr;
+  unsigned long long *dcount = nullptr;
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters come back as they are");
+  if ((rc = tmp.alloc(&dcount, mm))) return rc;
+  MVBA_HIP(hipMemset(dcount, 0, sizeof(unsigned long long) * mm));
+  if (pt_ptr) {
+    if ((rc = tmp.alloc(&dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(&dcam, (size_t)n_obs))) return rc;
+    MVBA_HIP(hipMemcpy(dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
+    if (n_obs) MVBA_HIP(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
+  }
+  if (timings_ms) timings_ms[0] = clk.lap();
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  EvGuard guard{ev, 2};
+  for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
+  const int use_lds = m <= CV_LDS_CAMERAS;
+  const int lds = use_lds ? (int)(sizeof(unsigned int) * mm) : 0;
+  MVBA_HIP(hipFuncSetAttribute((const void *)k_covisibility, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  const int grid = (int)std::max<long long>(1, std::min<long long>(2048, (n_points + 255) / 256));
+  hipEventRecord(ev[0], 0);
+  hipLaunchKernelGGL(k_covisibility, dim3(grid), dim3(256), lds, 0, (long long)n_points, m, dptr, dcam, dcount, use_lds);
+  hipEventRecord(ev[1], 0);
+  MVBA_HIP(hipGetLastError());
+  MVBA_HIP(hipMemcpy(count, dcount, sizeof(int64_t) * mm, hipMemcpyDeviceToHost));
+  for (int k = 0; k < m; ++k)
+    for (int l = k + 1; l < m; ++l) count[(size_t)l * m + k] = count[(size_t)k * m + l];
+  if (timings_ms) {
+    float f = 0.f;
+    hipEventElapsedTime(&f, ev[0], ev[1]);
+    timings_ms[1] = f;
+    timings_ms[2] = std::max(0.0, clk.lap() - (double)f);
+  }
+  return MVBA_OK;
+}
+
+int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
+                  const int32_t *pairs, int32_t n_pairs, double *F, double *quality, int64_t *n_shared, int32_t *status,
+                  double *timings_ms, int32_t device) {
+  if (n_pairs < 0) return fail(MVBA_ERR_BADARG, "n_pairs = " + std::to_string(n_pairs) + " must be >= 0");
+  if (!xy || (n_pairs > 0 && (!pairs || !F)))
+    return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!xy ? "xy" : (!pairs ? "pairs" : "F")) + " (argument " +
+                                     std::to_string(!xy ? 5 : (!pairs ? 7 : 9)) + ")");
+  int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
+  if (rc) return rc;
+  if ((rc = init_check_cameras(n_images))) return rc;
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    const int32_t k = pairs[2 * p], l = pairs[2 * p + 1];
+    if (k < 0 || k >= n_images || l < 0 || l >= n_images)
+      return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) +
+                                       "): camera index out of range, n_images = " + std::to_string(n_images));
+    if (k == l) return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) + "): the two cameras must differ");
+  }
+  if (pt_ptr)  // the kernels search a point's camera run: it must ascend
+    for (int64_t a = 0; a < n_points; ++a)
+      for (int64_t o = pt_ptr[a] + 1; o < pt_ptr[a + 1]; ++o)
+        if (cam_idx[o] <= cam_idx[o - 1])
+          return fail(MVBA_ERR_BADARG, "cam_idx is not ascending within point " + std::to_string(a) + ": cam_idx[" + std::to_string(o) + "] = " +
+                                           std::to_string(cam_idx[o]) + " after " + std::to_string(cam_idx[o - 1]));
+  if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = 0.0;
+  const int np = n_pairs;
+  std::vector<double> Fm(9 * (size_t)np, NAN), S((size_t)np * 45, 0.0), norm(TV_NORM * (size_t)np, 0.0), Sr((size_t)np, 0.0), ratio((size_t)np, NAN);
+  std::vector<int> st((size_t)np, 1);
+  if (np > 0 && n_points > 0) {
+    if (device >= 0) MVBA_HIP(hipSetDevice(device));
+    InitClock clk;
+    const long long n_ch = (n_points + TV_CHUNK - 1) / TV_CHUNK;
+    const int tile = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(np, 65535), (long long)(TV_PART_BYTES / (sizeof(double) * 45 * (size_t)n_ch))));
+    DevBufs tmp;
+    double2 *dxy = nullptr;
+    long long *dptr = nullptr;
+    int *dcam = nullptr, *dpairs = nullptr;
+    double *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dF = nullptr, *dS1 = nullptr;
+    if ((rc = tmp.alloc(&dxy, (size_t)n_obs)) || (rc = tmp.alloc(&dpairs, 2 * (size_t)np)) || (rc = tmp.alloc(&dpart, 45 * (size_t)n_ch * tile)) ||
+        (rc = tmp.alloc(&dS, 45 * (size_t)np)) || (rc = tmp.alloc(&dS1, 5 * (size_t)tile)) || (rc = tmp.alloc(&dnorm, TV_NORM * (size_t)np)) ||
+        (rc = tmp.alloc(&dF, 9 * (size_t)np)))
+      return rc;
+    if (n_obs) MVBA_HIP(hipMemcpy(dxy, xy, sizeof(double2) * n_obs, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dpairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice));
+    if (pt_ptr) {
+      if ((rc = tmp.alloc(&dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(&dcam, (size_t)n_obs))) return rc;
+      MVBA_HIP(hipMemcpy(dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
+      if (n_obs) MVBA_HIP(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
+    }
+    if (timings_ms) timings_ms[0] = clk.lap();
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    EvGuard guard{ev, 4};
+    for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
+    const dim3 b256(256);
+    auto combine = [&](int cnt, int nv, double *out, int stride) {
+      hipLaunchKernelGGL(k_twoview_combine, dim3((unsigned)(((long long)cnt * nv + 3) / 4)), b256, 0, 0, cnt, nv, (int)n_ch, dpart, out, stride);
+    };
+    hipEventRecord(ev[0], 0);
+    for (int p0 = 0; p0 < np; p0 += tile) {
+      const int cnt = std::min(tile, np - p0);
+      const dim3 grid((unsigned)n_ch, (unsigned)cnt), gp((cnt + 255) / 256);
+      const int *tp = dpairs + 2 * (size_t)p0;
+      double *tn = dnorm + TV_NORM * (size_t)p0;
+      hipLaunchKernelGGL(k_twoview_chunk<0>, grid, dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, (const double *)nullptr, dpart);
+      combine(cnt, 5, dS1, 5);
+      hipLaunchKernelGGL(k_twoview_norm, gp, b256, 0, 0, cnt, 0, dS1, 5, tn);
+      hipLaunchKernelGGL(k_twoview_chunk<1>, grid, dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, tn, dpart);
+      combine(cnt, 2, dS1, 2);
+      hipLaunchKernelGGL(k_twoview_norm, gp, b256, 0, 0, cnt, 1, dS1, 2, tn);
+      hipLaunchKernelGGL(k_twoview_chunk<2>, grid, dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, tn, dpart);
+      combine(cnt, 45, dS + 45 * (size_t)p0, 45);
+    }
+    hipEventRecord(ev[1], 0);
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipMemcpy(S.data(), dS, sizeof(double) * 45 * np, hipMemcpyDeviceToHost));
+    MVBA_HIP(hipMemcpy(norm.data(), dnorm, sizeof(double) * TV_NORM * np, hipMemcpyDeviceToHost));
+    for (int p = 0; p < np; ++p) {
+      if (!(norm[TV_NORM * (size_t)p + 6] >= TV_MIN_SHARED)) continue;  // status 1
+      st[p] = twoview_solve_pair(S.data() + 45 * (size_t)p, norm.data() + TV_NORM * (size_t)p, Fm.data() + 9 * (size_t)p, &ratio[p]);
+      if (st[p])
+        for (int j = 0; j < 9; ++j) Fm[9 * (size_t)p + j] = NAN;
+    }
+    MVBA_HIP(hipMemcpy(dF, Fm.data(), sizeof(double) * 9 * np, hipMemcpyHostToDevice));
+    hipEventRecord(ev[2], 0);
+    for (int p0 = 0; p0 < np; p0 += tile) {
+      const int cnt = std::min(tile, np - p0);
+      hipLaunchKernelGGL(k_twoview_chunk<3>, dim3((unsigned)n_ch, (unsigned)cnt), dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy,
+                         dpairs + 2 * (size_t)p0, dF + 9 * (size_t)p0, dpart);
+      combine(cnt, 1, dS + (size_t)p0, 1);
+    }
+    hipEventRecord(ev[3], 0);
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipMemcpy(Sr.data(), dS, sizeof(double) * np, hipMemcpyDeviceToHost));
+    if (timings_ms) {
+      float f1 = 0.f, f2 = 0.f;
+      hipEventElapsedTime(&f1, ev[0], ev[1]);
+      hipEventElapsedTime(&f2, ev[2], ev[3]);
+      timings_ms[1] = (double)f1 + f2;
+      timings_ms[2] = std::max(0.0, clk.lap() - timings_ms[1]);  // the copies back, the host's eigen-solves and the upload of F
+    }
+  }
+  for (int p = 0; p < np; ++p) {
+    const double n = norm[TV_NORM * (size_t)p + 6];
+    for (int j = 0; j < 9; ++j) F[9 * (size_t)p + j] = Fm[9 * (size_t)p + j];
+    if (n_shared) n_shared[p] = (int64_t)n;
+    if (status) status[p] = st[p];
+    if (quality) {
+      quality[2 * p] = st[p] == 0 ? sqrt(Sr[p] / n) : NAN;
+      quality[2 * p + 1] = st[p] == 0 ? ratio[p] : NAN;
+    }
+  }
+  return MVBA_OK;
+}
+
+}  // extern "C"

@@ -94,6 +94,10 @@ SIGNATURES = {
     "mvba_triangulate_state": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int32), _dp]),
     "mvba_resect": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int32,
                               C.POINTER(C.c_uint8), _dp, _dp, C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_covisibility": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64),
+                                    _dp, C.c_int32]),
+    "mvba_two_view": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.POINTER(C.c_int32),
+                                C.c_int32, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int32]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -460,6 +464,54 @@ def resect(X, pt_ptr, cam_idx, xy, n_images, point_ok=None, device=-1):
     raise_for(lib.mvba_resect(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, _ptr(P), _ptr(q), st.ctypes.data_as(C.POINTER(C.c_int32)),
                               _ptr(tm), int(device)), lib)
     return P, q, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+
+
+def covisibility(pt_ptr, cam_idx, n_images, n_points=None, device=-1):
+    """Co-visibility counts on the device (mvba_covisibility): ``count (m, m) int64``, count[k, l] = the number of points seen
+    in both k and l, count[k, k] = camera k's observation count.  ``pt_ptr=None`` with ``n_points``: the dense grid.  Returns
+    ``count, timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    if device_count() < 1:
+        raise RuntimeError("libmvba: no HIP device visible; mvba_covisibility has no CPU fallback")
+    m = int(n_images)
+    if pt_ptr is None:
+        assert n_points is not None
+        n, n_obs, pp, cp = int(n_points), int(n_points) * m, None, None
+    else:
+        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
+        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+        assert n_points is None or int(n_points) == n
+        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    count, tm = np.zeros((max(m, 0), max(m, 0)), np.int64), np.zeros(3)
+    raise_for(lib.mvba_covisibility(n, m, pp, cp, n_obs, count.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(tm), int(device)), lib)
+    return count, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+
+
+def two_view(pt_ptr, cam_idx, xy, n_images, pairs, device=-1):
+    """Fundamental matrices of camera pairs from the points they share (mvba_two_view): the normalised 8-point method.  The
+    list as for ``triangulate`` (``pt_ptr=None`` with xy (N, m, 2): the dense grid), ``pairs`` (P, 2) = (k, l).  Returns
+    ``F (P, 3, 3)`` -- x_l^T F x_k = 0 in the units of xy, rank 2, |F| = 1, largest entry positive --, ``quality (P, 2)`` (RMS
+    Sampson distance, eigenvalue ratio), ``n_shared (P,)``, ``status (P,)`` (0 ok, 1 fewer than 8 shared points, 2 degenerate;
+    F and quality are NaN then), ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    if device_count() < 1:
+        raise RuntimeError("libmvba: no HIP device visible; mvba_two_view has no CPU fallback")
+    xy, m = _as(xy, np.float64), int(n_images)
+    pairs = _as(pairs, np.int32).reshape(-1, 2)
+    if pt_ptr is None:
+        assert xy.ndim == 3 and xy.shape[1:] == (m, 2)
+        n, n_obs, pp, cp = xy.shape[0], xy.shape[0] * m, None, None
+    else:
+        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
+        xy = xy.reshape(-1, 2)
+        assert xy.shape[0] == cam_idx.shape[0]
+        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    P = pairs.shape[0]
+    F, q, ns, st, tm = np.empty((P, 3, 3)), np.empty((P, 2)), np.empty(P, np.int64), np.empty(P, np.int32), np.zeros(3)
+    raise_for(lib.mvba_two_view(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, _ptr(F), _ptr(q),
+                                ns.ctypes.data_as(C.POINTER(C.c_int64)), st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm), int(device)), lib)
+    return F, q, ns, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
 
 
 def host_obs_math(X3, cam15, xy2, f0):

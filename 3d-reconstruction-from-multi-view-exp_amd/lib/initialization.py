@@ -1,6 +1,11 @@
 """Initial estimates for bundle adjustment when visibility is sparse: triangulate every point from the cameras that
 are known, resect every camera from the points that are known -- the two steps that extend a reconstruction.  Both run
 on the MI355X (``mvba_triangulate``, ``mvba_resect``: csrc/mvba_init.h); there is no CPU fallback.
+
+And the step that starts one: co-visibility counts and the fundamental matrix of two views from the points they share
+(``mvba_covisibility``, ``mvba_two_view``: csrc/mvba_twoview.h), the relative pose out of it, and
+``bootstrap``, the incremental driver -- host control flow over the device calls -- that grows a start pair into an
+initial estimate for ``BundleAdjuster.from_observations``.
 """
 from __future__ import annotations
 
@@ -75,3 +80,188 @@ def resect_cameras(X, pt_ptr, cam_idx, xy, n_images: int, f0: float = 1.0, point
     if good.any():
         K[good], R[good], t[good] = decompose_projection(P[good], f0)
     return K, R, t, {"status": status, "quality": quality, "P": P, "timings_ms": tm}
+
+
+def covisibility(pt_ptr, cam_idx, n_images):
+    """count (m, m) int64: count[k, l] = the number of points observed in both k and l, count[k, k] = camera k's observation
+    count (``mvba_covisibility``)."""
+    return _mvba.covisibility(pt_ptr, cam_idx, n_images)[0]
+
+
+def fundamental_matrices(pt_ptr, cam_idx, xy, n_images, pairs):
+    """(F (P, 3, 3), info) of the camera pairs ``pairs`` (P, 2) = (k, l) from the points each pair shares: the normalised
+    8-point method (``mvba_two_view``): x_l^T F x_k = 0 with ``xy`` in any units -- F is for those units --, rank 2, Frobenius
+    norm 1, largest-magnitude entry positive.  ``info``: ``status`` (P,) -- 0 ok, 1 fewer than 8 shared points, 2 degenerate
+    (noise-free points in a plane, two cameras at one centre); F and quality are NaN where it is not 0 --, ``quality`` (P, 2) --
+    RMS Sampson distance in units of xy, eigenvalue ratio lambda_1 / lambda_2 (small: well determined) --, ``n_shared`` (P,)
+    and ``timings_ms``.  No RANSAC: a gross outlier moves F, and ``quality`` shows it."""
+    F, quality, n_shared, status, tm = _mvba.two_view(pt_ptr, cam_idx, xy, n_images, pairs)
+    return F, {"status": status, "quality": quality, "n_shared": n_shared, "timings_ms": tm}
+
+
+def restrict_observations(pt_ptr, cam_idx, xy, point_ok, camera_ok):
+    """The sub-list of the points and cameras marked: (pt_ptr, cam_idx, xy, point_ids, camera_ids) with points and cameras
+    renumbered in ascending order of their old indices (``point_ids``, ``camera_ids``: the old index of each new one)."""
+    pt_ptr, cam_idx = np.asarray(pt_ptr, np.int64), np.asarray(cam_idx, np.int32)
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    point_ok, camera_ok = np.asarray(point_ok, bool), np.asarray(camera_ok, bool)
+    point_ids, camera_ids = np.nonzero(point_ok)[0], np.nonzero(camera_ok)[0]
+    pt = np.repeat(np.arange(len(pt_ptr) - 1), np.diff(pt_ptr))
+    keep = point_ok[pt] & camera_ok[cam_idx]
+    new_cam = np.cumsum(camera_ok) - 1
+    new_pt = np.cumsum(point_ok) - 1
+    ptr = np.zeros(len(point_ids) + 1, np.int64)
+    np.cumsum(np.bincount(new_pt[pt[keep]], minlength=len(point_ids)), out=ptr[1:])
+    return ptr, new_cam[cam_idx[keep]].astype(np.int32), xy[keep], point_ids, camera_ids
+
+
+def pose_candidates(E):
+    """The four (R (3, 3), t (3,)) of the second camera that an essential matrix allows, the first at the origin with identity
+    pose: x_l ~ R^T (X - t), |t| = 1 (the conventions of ``_mvba.project``), from the SVD of E with both singular values set to
+    their mean, in the order (R_a, +), (R_a, -), (R_b, +), (R_b, -)."""
+    U, s, Vt = np.linalg.svd(E)
+    if np.linalg.det(U) < 0:
+        U = -U
+    if np.linalg.det(Vt) < 0:
+        Vt = -Vt
+    W = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    out = []
+    for Rrel in (U @ W @ Vt, U @ W.T @ Vt):  # x_l ~ Rrel x_k + tau, tau = +-U[:, 2]
+        for tau in (U[:, 2], -U[:, 2]):
+            out.append((Rrel.T, -Rrel.T @ tau))
+    return out
+
+
+def _pair_list(pt_ptr, cam_idx, xy, n_images, k, l):
+    """The two-camera sub-list over all points (the lower camera index becomes 0) and the positions of k and l in it."""
+    cam_ok = np.zeros(n_images, bool)
+    cam_ok[[k, l]] = True
+    ptr, cam, z, _, _ = restrict_observations(pt_ptr, cam_idx, xy, np.ones(len(pt_ptr) - 1, bool), cam_ok)
+    return ptr, cam, z, (0, 1) if k < l else (1, 0)
+
+
+def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2):
+    """(R (2, 3, 3), t (2, 3), X (N, 3), info): the pose of camera l = pair[1] relative to camera k = pair[0], which sits at the
+    origin with identity pose; |t_l| = 1.  ``K`` (m, 3, 3) projects to the units of ``xy`` (raw image coordinates:
+    ``engine_intrinsics(init_K)``, as for ``triangulate_points``).  F of the pair on the device, E = K_l^T F K_k, its four
+    (R, +-t) candidates, each triangulated on the device without refinement; the winner has the most points of status 0 and
+    smallest depth > 0, and is triangulated again with ``n_refine``.  ``X`` is NaN for points not shared, not triangulated or
+    behind a camera.  ``info``: ``n_front`` (4,), ``status`` -- 0 ok, the ``fundamental_matrices`` status otherwise, 3 when no
+    candidate puts more than half of the shared points in front of both cameras --, ``F``, ``n_shared``, ``two_view`` (the
+    quality of F) and the triangulation ``quality`` (N, 3)."""
+    K = np.asarray(K, np.float64)
+    k, l = int(pair[0]), int(pair[1])
+    n = len(pt_ptr) - 1
+    F, fi = fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)])
+    R, t, X = np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
+    info = {"n_front": np.zeros(4, np.int64), "status": int(fi["status"][0]), "F": F[0], "n_shared": int(fi["n_shared"][0]),
+            "two_view": fi["quality"][0], "quality": np.full((n, 3), np.nan)}
+    if info["status"] != 0:
+        return R, t, X, info
+    ptr, cam, z, (ik, il) = _pair_list(pt_ptr, cam_idx, xy, K.shape[0], k, l)
+    K2, R2, t2 = np.empty((2, 3, 3)), np.empty((2, 3, 3)), np.zeros((2, 3))
+    K2[ik], K2[il], R2[ik] = K[k], K[l], np.eye(3)
+    cands = pose_candidates(K[l].T @ F[0] @ K[k])
+
+    def tri(c, nr):
+        R2[il], t2[il] = cands[c]
+        Xc, q, st, _ = _mvba.triangulate(K2, R2, t2, ptr, cam, z, n_refine=nr)
+        return Xc, q, (st == 0) & (q[:, 1] > 0)
+
+    for c in range(4):
+        info["n_front"][c] = tri(c, 0)[2].sum()
+    best = int(np.argmax(info["n_front"]))
+    if not 2 * info["n_front"][best] > info["n_shared"]:
+        info["status"] = 3
+        return R, t, X, info
+    Xc, q, front = tri(best, n_refine)
+    X[front], info["quality"][front] = Xc[front], q[front]
+    R[0], t[0] = np.eye(3), 0.0
+    R[1], t[1] = cands[best]
+    return R, t, X, info
+
+
+def pose_for_intrinsics(P, K, c):
+    """(R, t) of a camera with the GIVEN intrinsics ``K`` (3, 3; it projects to the units P projects to) that images the
+    neighbourhood of the point ``c`` as the camera matrix ``P`` (3, 4) does: the rotation of ``decompose_projection``, and the
+    centre moved along the ray of ``c`` so that ``c`` keeps its image and its magnification f / depth.  The centre of P itself
+    belongs to P's own focal length -- the DLT trades the two against each other, a few percent at a noise of 1e-3 --, and
+    taken with another K it is off by that factor of the depth."""
+    Kd, R, td = decompose_projection(P, 1.0)
+    y = R.T @ (np.asarray(c, np.float64) - td)  # c in P's camera frame
+    x = Kd[0, 0] * y[:2] / y[2] + Kd[:2, 2]  # its image
+    d = y[2] * K[0, 0] / Kd[0, 0]
+    return R, c - R @ (d * np.array([(x[0] - K[0, 2]) / K[0, 0], (x[1] - K[1, 2]) / K[1, 1], 1.0]))
+
+
+def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min_points: int = 12, max_rms=None):
+    """(K, R, t, X, info): an initial estimate for ``BundleAdjuster.from_observations`` from feature tracks and rough
+    intrinsics, by incremental reconstruction.  ``xy`` are raw image coordinates, ``init_K`` (m, 3, 3) the adjuster's
+    [[f,0,u],[0,f,v],[0,0,f0]]; K comes back as ``init_K`` (no focal length is estimated).
+    Start pair (unless given): of the pairs in descending co-visibility, the first 16 with at least 8 shared points get
+    ``relative_pose``; the one with the largest median ray angle among those of status 0 starts.  Then, until no camera can
+    be added: ``resect_cameras`` on the current points; the unregistered camera with the most usable observations is
+    registered if its status is 0 and it has at least ``min_points`` -- its pose only, the one that belongs to ``init_K``
+    (``pose_for_intrinsics`` at the centroid of the points it sees) --; ``triangulate_points`` over the
+    registered cameras; a point is kept if its status is 0, its smallest depth > 0 and, with ``max_rms``, its RMS residual
+    (units of xy) is at most that.  No BA runs in between.
+    The output frame: camera 0 at the origin with identity pose, |t_1 - t_0| = 1.  ``info``: ``axis`` -- the gauge axis name
+    whose component of t_1 is larger in magnitude: pass it to ``BundleAdjuster`` --, ``camera_ok`` (m,), ``point_ok`` (N,),
+    ``order`` (the registration order), ``start_pair``.  Cameras and points not reached are NaN (``restrict_observations``
+    gives the list without them).  ValueError if no start pair has status 0, or if camera 0 or 1 could not be registered."""
+    pt_ptr, cam_idx = np.asarray(pt_ptr, np.int64), np.asarray(cam_idx, np.int32)
+    xy, init_K = np.asarray(xy, np.float64).reshape(-1, 2), np.asarray(init_K, np.float64)
+    m, n = init_K.shape[0], len(pt_ptr) - 1
+    Kxy = engine_intrinsics(init_K)
+    if start_pair is None:
+        count = covisibility(pt_ptr, cam_idx, m)
+        ks, ls = np.triu_indices(m, 1)
+        order = np.argsort(-count[ks, ls], kind="stable")
+        tried = [(int(ks[i]), int(ls[i])) for i in order if count[ks[i], ls[i]] >= 8][:16]
+    else:
+        tried = [(int(start_pair[0]), int(start_pair[1]))]
+    best = None
+    for pair in tried:
+        R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair)
+        if pi["status"] != 0:
+            continue
+        angle = float(np.nanmedian(pi["quality"][:, 2]))
+        if best is None or angle > best[0]:
+            best = (angle, pair, R2, t2, X2)
+    if best is None:
+        raise ValueError(f"bootstrap: no start pair with status 0 among {tried}")
+    _, pair, R2, t2, X = best
+    R, t = np.full((m, 3, 3), np.nan), np.full((m, 3), np.nan)
+    R[list(pair)], t[list(pair)] = R2, t2
+    camera_ok = np.zeros(m, bool)
+    camera_ok[list(pair)] = True
+    point_ok = np.isfinite(X).all(axis=1)
+    reg_order = [pair[0], pair[1]]
+    pt = np.repeat(np.arange(n), np.diff(pt_ptr))
+    all_points = np.ones(n, bool)
+    while not camera_ok.all():
+        ri = resect_cameras(X, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=point_ok)[3]
+        usable = np.bincount(cam_idx[point_ok[pt]], minlength=m)
+        cand = np.nonzero(~camera_ok & (ri["status"] == 0) & (usable >= min_points))[0]
+        if len(cand) == 0:
+            break
+        c = int(cand[np.argmax(usable[cand])])
+        sel = point_ok[pt] & (cam_idx == c)
+        R[c], t[c] = pose_for_intrinsics(ri["P"][c], Kxy[c], X[pt[sel]].mean(axis=0))
+        camera_ok[c] = True
+        reg_order.append(c)
+        ptr, cam, z, _, ids = restrict_observations(pt_ptr, cam_idx, xy, all_points, camera_ok)
+        X, ti = triangulate_points(ptr, cam, z, Kxy[ids], R[ids], t[ids])
+        point_ok = (ti["status"] == 0) & (ti["quality"][:, 1] > 0)
+        if max_rms is not None:
+            point_ok &= ti["quality"][:, 0] <= max_rms
+        X[~point_ok] = np.nan
+    for c in (0, 1):
+        if not camera_ok[c]:
+            raise ValueError(f"bootstrap: camera {c} could not be registered (the output frame is that of cameras 0 and 1); "
+                             f"registered: {reg_order}")
+    R0, t0, s = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
+    X, R, t = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s
+    axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
+    return init_K.copy(), R, t, X, {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order,
+                                    "start_pair": pair}

@@ -270,6 +270,37 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
                 int32_t n_images, const uint8_t *point_ok, double *P, double *quality, int32_t *status, double *timings_ms,
                 int32_t device);
 
+/* mvba_covisibility: count [n_images][n_images], count[k][l] = the number of points observed in both k and l (symmetric),
+ * count[k][k] = camera k's observation count.  The list as in mvba_project (pt_ptr == NULL: the dense grid, cam_idx unused); the
+ * argument checks and the camera cap (1704) are mvba_triangulate's.  One thread per point walks the pairs of its own camera run
+ * (deg^2 / 2 per point) into integer counters: exact in any order.  timings_ms [3] (may be NULL): upload, kernel, everything else. */
+int mvba_covisibility(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, int64_t n_obs,
+                      int64_t *count, double *timings_ms, int32_t device);
+
+/* mvba_two_view: the fundamental matrix of each requested camera pair from the points the two cameras share: the normalised
+ * 8-point method.  The list as in mvba_project (pt_ptr == NULL: the dense grid) with cam_idx strictly ascending within a point
+ * (MVBA_ERR_BADARG otherwise); xy [n_obs][2] in any units.  pairs [n_pairs][2] = (k, l), k != l.  For pair (k, l) the shared
+ * points are those with an observation in both images, in ascending point order; x_k, x_l are a shared point's two observations.
+ * Device pass 1: the count n, and per side the centroid c and the mean squared distance d to it (Hartley: x~ = s (x - c) with
+ * s = sqrt(2) / sqrt(d), mean squared distance 2 -- mvba_resect's convention for image points).  Device pass 2: M = sum a a^T
+ * of the rows a = (x~_l x~_k, x~_l y~_k, x~_l, y~_l x~_k, y~_l y~_k, y~_l, x~_k, y~_k, 1), its 45 unique sums -- a chunk of 256
+ * points by a fixed tree, a pair's chunks in an order the chunk count fixes, no floating-point atomics: two runs are bitwise
+ * equal.  Host: F^ (3 x 3 row-major) = the eigenvector of M's smallest eigenvalue (cyclic Jacobi, n_pairs problems of order 9),
+ * so that x~_l^T F^ x~_k = 0; rank 2 by zeroing F^'s smallest singular value; F = T_l^T F^ T_k with
+ * T = [[s, 0, -s c_x], [0, s, -s c_y], [0, 0, 1]]; scaled to Frobenius norm 1 with its largest-magnitude entry positive.
+ * F [n_pairs][9]: x_l^T F x_k = 0 in the units of xy.
+ * status [n_pairs]: 0 ok; 1 fewer than 8 shared points; 2 degenerate (second-smallest eigenvalue of M <= 1e-12 x the largest:
+ * noise-free points in a plane, two cameras at one centre).  Where status != 0, F and quality are NaN.
+ * quality [n_pairs][2]: the RMS Sampson distance of the shared points under the returned F, in the units of xy (a third device
+ * pass; squared distance (x_l^T F x_k)^2 / ((F x_k)_0^2 + (F x_k)_1^2 + (F^T x_l)_0^2 + (F^T x_l)_1^2)); lambda_1 / lambda_2
+ * of M (small: well determined).  n_shared [n_pairs]: the count.
+ * timings_ms [3]: check + upload, kernels, everything else (copies back, eigen-solves).  quality, n_shared, status and
+ * timings_ms may be NULL.  MVBA_ERR_BADARG (with the number in the message): a pair with k == l or an index outside
+ * 0 .. n_images - 1, n_pairs < 0, and whatever mvba_triangulate rejects of a list. */
+int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy,
+                  int64_t n_obs, const int32_t *pairs, int32_t n_pairs, double *F, double *quality, int64_t *n_shared,
+                  int32_t *status, double *timings_ms, int32_t device);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
