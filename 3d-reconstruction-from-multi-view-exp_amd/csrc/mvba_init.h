@@ -464,6 +464,12 @@ int init_check_cameras(int32_t n_images) {
 
 // the sums of one camera -> its matrix (unnormalised), status and eigenvalue ratio
 int resect_solve_camera(const double *S40, const double *nm, double *P, double *ratio) {
+  // coincident points: a Hartley scale of sqrt(.) / sqrt(0) = inf, then inf x 0 = NaN in the sums.  The Jacobi skips a NaN
+  // a_pq and eig_extremes orders NaN below nothing, so the "eigenvalues" of such a matrix would be those of its finite part:
+  // degenerate here, with no ratio
+  *ratio = NAN;
+  for (int e = 0; e < 40; ++e)
+    if (!std::isfinite(S40[e])) return 2;
   double A[12][12], V[12][12];
   for (int i = 0; i < 12; ++i)
     for (int j = 0; j < 12; ++j) A[i][j] = 0.0;

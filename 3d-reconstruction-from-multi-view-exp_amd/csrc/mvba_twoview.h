@@ -170,6 +170,9 @@ __global__ __launch_bounds__(256) void k_twoview_norm(int n_pairs, int stage, co
 
 // the 45 sums of one pair -> F (normalisation undone, |F| = 1, largest entry positive), status and lambda_1 / lambda_2
 int twoview_solve_pair(const double *S45, const double *nm, double *F, double *ratio) {
+  *ratio = NAN;
+  for (int e = 0; e < 45; ++e)  // coincident image points in k or l (an infinite Hartley scale): as resect_solve_camera
+    if (!std::isfinite(S45[e])) return 2;
   double A[9][9], V[9][9];
   int e = 0;
   for (int b = 0; b < 9; ++b)

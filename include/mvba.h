@@ -264,7 +264,8 @@ int mvba_triangulate_state(mvba_handle *h, int32_t n_refine, double *quality, in
  * status [n_images]: 0 ok; 1 fewer than 6 usable observations; 2 degenerate, e.g. coplanar points (second-smallest
  * eigenvalue <= 1e-12 x the largest).  Where status != 0, P is NaN.
  * quality [n_images][2]: RMS reprojection residual of the camera's used observations (a third device pass; NaN where status
- * != 0); the eigenvalue ratio lambda_1 / lambda_2 (small: well determined; NaN where status = 1).
+ * != 0); the eigenvalue ratio lambda_1 / lambda_2 (small: well determined; NaN where status = 1, and where the
+ * sums are not finite: points or image points that coincide exactly make a Hartley scale infinite, status 2).
  * timings_ms [3]: sort + upload, kernels, everything else (copies back, eigen-solves).  quality, status, timings_ms may be NULL. */
 int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
                 int32_t n_images, const uint8_t *point_ok, double *P, double *quality, int32_t *status, double *timings_ms,

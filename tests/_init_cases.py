@@ -12,8 +12,9 @@ from lib.synthetic import make_scene, project_obs
 # coordinates of order 1, camera matrices with |P[2, :3]| = 1).  A GPU parity assert gets 100 x its scene's figure, for
 # n_refine = 0 and 2 alike (a refined point is no better determined than the eigenvector it started from; after two steps
 # the two host routes agree to 4e-16, which measures the convergence, not the arithmetic).
-TRI_HOST_DIFF = {"300x8": 1.3e-14, "65x70": 1.6e-15, "257x2": 1.5e-14, "dense": 1.6e-15, "pixels": 1.2e-14}
-RESECT_HOST_DIFF = {"300x8": 2.5e-14, "5000x3": 1.2e-14, "six": 1.2e-13, "dense": 2.4e-14}
+TRI_HOST_DIFF = {"300x8": 1.3e-14, "65x70": 1.6e-15, "257x2": 1.5e-14, "dense": 1.6e-15, "pixels": 1.2e-14, "300x683": 8.2e-15,
+                 "300x1704": 1.2e-14}
+RESECT_HOST_DIFF = {"300x8": 2.5e-14, "5000x3": 1.2e-14, "six": 1.2e-13, "dense": 2.4e-14, "900x300": 4.5e-13, "edges": 4.9e-14}
 MARGIN = 100.0
 
 
@@ -30,6 +31,12 @@ def tri_scene(name):
         return make_scene(130, 5, vis_p=1.0, project="numpy")
     if name == "pixels":  # the 300 x 8 scene in pixel units: f0 = 600, f ~ 600, principal point (320, 240)
         return make_scene(300, 8, vis_p=0.5, project="numpy")
+    # the LDS camera table (96 B per camera) above 64 KiB and at its cap; vis_p = 0.02 leaves the reference alone with status
+    # 0 for 300 of 300 points in both (degrees 3 .. 23 and 18 .. 50)
+    if name == "300x683":  # 65 568 B; 7 points observe camera 682, the row that crosses 64 KiB
+        return make_scene(300, 683, vis_p=0.02, project="numpy")
+    if name == "300x1704":  # 163 584 B, the cap; 3 points observe camera 1703, 6 camera 682, 6 camera 683
+        return make_scene(300, 1704, vis_p=0.02, project="numpy")
     raise KeyError(name)
 
 
@@ -126,7 +133,75 @@ def resect_case(name):
         X = sc.X_gt.copy()
         X[:, 2] = 0.0
         return X, sc.pt_ptr, sc.cam_idx, exact_xy(sc, X), 3, np.full(3, 2, np.int32)
+    if name == "900x300":  # more than 256 cameras (k_resect_norm beyond one workgroup), 38 .. 76 observations each: none below 6
+        sc = make_scene(900, 300, vis_p=0.06, project="numpy")
+        return sc.X_gt, sc.pt_ptr, sc.cam_idx, sc.xy, 300, np.where(np.bincount(sc.cam_idx, minlength=300) < 6, 1, 0).astype(np.int32)
+    if name == "edges":  # 257 observations for camera 0 (a chunk of one after a full one), 256 for camera 1 (a full chunk), 255 for camera 2
+        sc = make_scene(257, 3, vis_p=1.0, project="numpy")
+        pt = np.repeat(np.arange(257), 3)
+        keep = ~(((sc.cam_idx == 1) & (pt >= 256)) | ((sc.cam_idx == 2) & (pt >= 255)))
+        pt_ptr = np.concatenate([[0], np.cumsum(np.bincount(pt[keep], minlength=257))]).astype(np.int64)
+        return sc.X_gt, pt_ptr, sc.cam_idx[keep], sc.xy[keep], 3, np.zeros(3, np.int32)
     raise KeyError(name)
+
+
+GRID_CAP = 2048 * 256  # the grid of k_triangulate and k_covisibility: at most 2048 workgroups of 256 threads, then grid-stride
+
+
+@functools.lru_cache(maxsize=None)
+def tiled_scene():
+    """The "300x8" list repeated along the point axis until it passes GRID_CAP by a few whole tiles (1754 tiles, 526 200
+    points): (reps, pt_ptr, cam_idx, xy).  The cameras stay those of tri_args("300x8")."""
+    sc = tri_scene("300x8")
+    reps = GRID_CAP // sc.n_points + 7
+    deg = np.tile(np.diff(sc.pt_ptr), reps)
+    pt_ptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    out = reps, pt_ptr, np.tile(sc.cam_idx, reps), np.tile(sc.xy, (reps, 1))
+    for v in out[1:]:
+        v.setflags(write=False)
+    return out
+
+
+EMPTY_CAMERAS = (1, 4, 10)
+
+
+def empty_camera_case():
+    """The "300x8" list re-indexed into m = 11 with cameras 1, 4 and 10 unobserved: (X, pt_ptr, cam_idx, xy, 11, kept) with
+    kept[j] the new index of the old camera j."""
+    X, pt_ptr, cam, xy, _, _ = resect_case("300x8")
+    kept = np.array([k for k in range(11) if k not in EMPTY_CAMERAS], np.int32)
+    return X, pt_ptr, kept[cam], xy, 11, kept
+
+
+COINCIDENT_CAMERA = 3
+# the image point a camera's observations are collapsed onto: sums of the first are exact in binary floating point (the
+# centroid is the point itself, the spread exactly 0, the Hartley scale infinite, inf x 0 = NaN in the second pass); the
+# second is not representable, so the centroid may miss it by one ulp (a finite scale of the order 1e17 and identical
+# normalised points: a null space of dimension 4 for the DLT, 6 for the epipolar rows)
+COINCIDENT_POINTS = {"exact": (0.25, -0.5), "inexact": (0.1, 0.3)}
+
+
+def coincident_xy(kind):
+    """The xy of "300x8" with every observation of COINCIDENT_CAMERA at one image point."""
+    sc = tri_scene("300x8")
+    xy = sc.xy.copy()
+    xy[sc.cam_idx == COINCIDENT_CAMERA] = COINCIDENT_POINTS[kind]
+    return xy
+
+
+def duplicate_observation_case():
+    """status_case() with point 5 observed by camera 2 twice, the same image point both times (no parallax: status 2); the
+    run [2, 2] does not ascend, which the stateless call does not ask for.  (K, R, t, pt_ptr, cam_idx, xy, expected)."""
+    K, R, t, pt_ptr, cam, xy, expect, _ = status_case()
+    keep = np.ones(len(cam), bool)
+    keep[pt_ptr[5]] = False  # drop camera 0; then camera 1 becomes the copy of camera 2
+    cam, xy = cam.copy(), xy.copy()
+    cam[pt_ptr[5] + 1], xy[pt_ptr[5] + 1] = 2, xy[pt_ptr[5] + 2]
+    deg = np.diff(pt_ptr)
+    deg[5] = 2
+    expect = expect.copy()
+    expect[5] = 2
+    return K, R, t, np.concatenate([[0], np.cumsum(deg)]).astype(np.int64), cam[keep], xy[keep], expect
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,7 +12,8 @@ from lib.synthetic import make_scene, project_obs
 # Host-versus-host max-abs difference of F (|F| = 1) over the pairs of status 0, measured by test_twoview_cpu.py on the very
 # scenes below.  A GPU parity assert gets MARGIN x its scene's figure; the Sampson RMS gets the same margin relative to its
 # own size (|dq| <= margin x q).  "65x12" has pairs with exactly 8 shared points and lambda_1 / lambda_2 up to 0.04.
-TWOVIEW_HOST_DIFF = {"300x8": 8.7e-14, "5000x3": 3.9e-15, "257x2": 2.1e-15, "65x12": 2.0e-11, "pixels": 9.2e-15}
+TWOVIEW_HOST_DIFF = {"300x8": 8.7e-14, "5000x3": 3.9e-15, "257x2": 2.1e-15, "65x12": 2.0e-11, "pixels": 9.2e-15,
+                     "16641x3": 3.0e-15}
 MARGIN = 100.0
 # The noise-free 300 x 8 scene, pair (0, 1): the reference's F against the ground-truth essential matrix, its relative pose
 # against the ground truth, and the host-versus-host difference of F there (all max abs, measured by test_twoview_cpu.py).
@@ -40,6 +41,8 @@ def scene(name):
         return make_scene(65, 12, vis_p=0.3, project="numpy")
     if name == "noise_free":
         return make_scene(300, 8, vis_p=0.5, noise=0.0, project="numpy")
+    if name == "16641x3":  # dense; 66 chunks of 256 points, the last of one point: lanes 0 and 1 of the combine add two chunks each
+        return make_scene(16641, 3, vis_p=1.0, project="numpy")
     raise KeyError(name)
 
 
@@ -53,6 +56,8 @@ def case(name):
     pairs = all_pairs(sc.n_images)
     if name == "300x8":
         pairs = np.concatenate([pairs, np.array([(5, 2), (7, 0)], np.int32)])
+    if name == "16641x3":  # the six ordered pairs
+        pairs = np.concatenate([pairs, pairs[:, ::-1]])
     return sc.pt_ptr, sc.cam_idx, sc.xy, sc.n_images, pairs
 
 
@@ -62,6 +67,26 @@ def reference(name, linear="eigh"):
     for v in out:
         v.setflags(write=False)
     return out
+
+
+TV_CHUNK, TV_PART_BYTES, TV_MAX_TILE = 256, 128 << 20, 65535  # csrc/mvba_twoview.h: points per chunk, bytes of partials per launch, gridDim.y
+
+
+def pair_tile(n_points, n_pairs):
+    """The number of pairs mvba_two_view takes per launch ("Partials")."""
+    n_chunks = -(-n_points // TV_CHUNK)
+    return max(1, min(n_pairs, TV_MAX_TILE, TV_PART_BYTES // (8 * 45 * n_chunks)))
+
+
+def cycled(pairs, n):
+    """The pair list repeated to length n."""
+    return np.ascontiguousarray(np.resize(pairs, (n, 2)))
+
+
+def no_shared_case():
+    """The "300x8" list with a ninth camera that observes nothing: pair (0, 8) shares no point.  (pt_ptr, cam_idx, xy, 9)."""
+    pt_ptr, cam, xy, _, _ = case("300x8")
+    return pt_ptr, cam, xy, 9
 
 
 def count_cases():

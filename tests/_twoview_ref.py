@@ -65,7 +65,7 @@ def fundamental(xk, xl, linear="eigh"):
             w, V = np.linalg.eigh(rows.T @ rows)
             f = V[:, 0]
         else:
-            _, s, Vt = np.linalg.svd(rows, full_matrices=True)
+            _, s, Vt = np.linalg.svd(rows, full_matrices=len(rows) < 9)  # (the full U of 16 641 rows would be 2 GB)
             w, f = np.concatenate([s, np.zeros(9 - len(s))])[::-1] ** 2, Vt[8]
         ratio = w[0] / w[1]
     if not w[1] > REL_PIVOT * w[8]:

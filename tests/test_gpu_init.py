@@ -186,9 +186,10 @@ def test_engine_triangulate_world_size_2_on_one_gpu():
     assert "DIST_INIT_OK" in out.stdout
 
 
-@pytest.mark.parametrize("name", ["300x8", "5000x3", "six", "dense", "coplanar"])
+@pytest.mark.parametrize("name", ["300x8", "5000x3", "six", "dense", "coplanar", "900x300", "edges"])
 def test_resect_parity(name):
     X, pt_ptr, cam, xy, m, expect = C.resect_case(name)
+    print(f"{name}: {int((expect == 1).sum())} of {m} cameras have fewer than 6 observations")
     if name == "dense":  # the dense grid from Python: no list, xy (N, m, 2)
         P, q, st, tm = _mvba.resect(X, None, None, xy.reshape(len(X), m, 2), m)
     else:

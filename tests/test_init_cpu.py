@@ -128,6 +128,56 @@ def test_status_rules_on_constructed_cases():
     assert ref.resect(Xn, pt_ptr, cam, xy, m)[2].tolist() == [0, 1, 1, 0]
 
 
+def test_limit_scenes_have_the_stated_properties():
+    """The premises of tests/test_gpu_init_limits.py that need no device."""
+    reps, pt_ptr, cam, xy = C.tiled_scene()
+    sc = C.tri_scene("300x8")
+    assert reps == 1754 and len(pt_ptr) - 1 == 526200 > C.GRID_CAP == 524288
+    np.testing.assert_array_equal(np.diff(pt_ptr).reshape(reps, 300), np.tile(np.diff(sc.pt_ptr), (reps, 1)))
+    assert pt_ptr[-1] == len(cam) == len(xy) == reps * sc.n_obs and np.array_equal(cam[-sc.n_obs:], sc.cam_idx)
+    for name, m, rows in (("300x683", 683, [682]), ("300x1704", 1704, [682, 683, 1703])):
+        sc = C.tri_scene(name)
+        assert sc.n_images == m and 12 * 8 * m > 65536 and all((sc.cam_idx == r).any() for r in rows)
+        assert (C.tri_reference(name, 0)[2] == 0).all() and (C.tri_reference(name, 2)[2] == 0).all()  # 300 of 300
+    assert 12 * 8 * 1704 == 163584 <= 160 * 1024 - 256 < 12 * 8 * 1705
+    X, pt_ptr, cam, xy, m, expect = C.resect_case("900x300")
+    st = C.resect_reference("900x300")[2]
+    print(f"900x300: {int((st == 1).sum())} cameras with fewer than 6 observations, {int((st == 0).sum())} of {m} resected")
+    assert m > 256 and (st == expect).all() and (st == 0).sum() >= 0.95 * m
+    X, pt_ptr, cam, xy, m, _ = C.resect_case("edges")
+    assert np.bincount(cam).tolist() == [257, 256, 255]
+
+
+def test_reference_defines_the_degenerate_inputs():
+    """The inputs of tests/test_gpu_init_limits.py that make a Hartley scale infinite or leave a camera without
+    observations: the reference gives them the statuses of include/mvba.h, by either linear route."""
+    K, R, t, pt_ptr, cam, xy, expect = C.duplicate_observation_case()
+    assert cam[pt_ptr[5]:pt_ptr[6]].tolist() == [2, 2] and (xy[pt_ptr[5]] == xy[pt_ptr[5] + 1]).all()
+    for linear in ("eigh", "svd"):
+        X, q, st = ref.triangulate(K, R, t, pt_ptr, cam, xy, 2, linear=linear)
+        np.testing.assert_array_equal(st, expect)
+        assert st[5] == 2 and np.isnan(X[5]).all() and np.isnan(q[5]).all()
+    X, pt_ptr, cam, xy0, m, _ = C.resect_case("300x8")
+    P0 = ref.resect(X, pt_ptr, cam, xy0, m)[0]
+    for kind in sorted(C.COINCIDENT_POINTS):
+        xy = C.coincident_xy(kind)
+        assert (xy[cam == C.COINCIDENT_CAMERA] == C.COINCIDENT_POINTS[kind]).all() and (xy[cam != C.COINCIDENT_CAMERA] == xy0[cam != C.COINCIDENT_CAMERA]).all()
+        for linear in ("eigh", "svd"):
+            P, q, st = ref.resect(X, pt_ptr, cam, xy, m, linear=linear)
+            assert st.tolist() == [0, 0, 0, 2, 0, 0, 0, 0] and np.isnan(P[3]).all() and np.isnan(q[3, 0])
+            if kind == "exact":  # the scale is sqrt(2) / sqrt(0): the rows are NaN, there is no eigenvalue ratio
+                assert np.isnan(q[3, 1])
+            if linear == "eigh":
+                np.testing.assert_array_equal(P[st == 0], P0[st == 0])
+    X, pt_ptr, cam, xy, m, kept = C.empty_camera_case()
+    P, q, st = ref.resect(X, pt_ptr, cam, xy, m)
+    assert np.nonzero(st == 1)[0].tolist() == list(C.EMPTY_CAMERAS) and np.isnan(P[st == 1]).all() and np.isnan(q[st == 1]).all()
+    np.testing.assert_array_equal(P[kept], P0)
+    for kw in ({"point_ok": np.zeros(len(X), bool)}, {}):
+        P, q, st = ref.resect(X if kw else np.full_like(X, np.nan), pt_ptr, cam, xy, m, **kw)
+        assert (st == 1).all() and np.isnan(P).all() and np.isnan(q).all()
+
+
 def test_init_X_none_fails_loudly_without_gpu(golden):
     """from_observations(init_X=None) on a box without a GPU fails as the product path does today (tests/test_host_cpu.py)."""
     from lib import _mvba

@@ -87,6 +87,30 @@ def test_degenerate_pairs_have_status_2():
             assert st[0] == 2 and np.isnan(F).all() and np.isnan(q).all() and ns[0] == len(pt_ptr) - 1
 
 
+def test_limit_cases_have_the_stated_sizes_and_statuses():
+    """The premises of tests/test_gpu_twoview_limits.py that need no device, and the statuses the reference defines for a
+    pair without shared points and for coincident image points (an infinite Hartley scale), by either linear route."""
+    pt_ptr, cam, xy, m, six = C.case("16641x3")
+    assert -(-(len(pt_ptr) - 1) // C.TV_CHUNK) == 66 and [tuple(p) for p in six] == [(0, 1), (0, 2), (1, 2), (1, 0), (2, 0), (2, 1)]
+    assert C.pair_tile(16641, 5700) == 5648 and C.pair_tile(300, 65600) == 65535 and C.pair_tile(300, 30) == 30
+    assert len(C.cycled(six, 5700)) == 5700 and (C.cycled(six, 5700)[5694:] == six).all()
+    pt_ptr, cam, xy, m = C.no_shared_case()
+    F, q, ns, st = T.two_view(pt_ptr, cam, xy, m, [(0, 8), (8, 3)])
+    assert ns.tolist() == [0, 0] and st.tolist() == [1, 1] and np.isnan(F).all() and np.isnan(q).all()
+    import _init_cases as IC
+
+    pt_ptr, cam, xy0, m, pairs = C.case("300x8")
+    hit = (pairs == IC.COINCIDENT_CAMERA).any(axis=1)
+    for kind in sorted(IC.COINCIDENT_POINTS):
+        for linear in ("eigh", "svd"):
+            F, q, ns, st = T.two_view(pt_ptr, cam, IC.coincident_xy(kind), m, pairs, linear)
+            np.testing.assert_array_equal(st, np.where(hit, 2, 0))
+            np.testing.assert_array_equal(ns, C.reference("300x8")[2])
+            assert np.isnan(F[hit]).all() and np.isnan(q[hit]).all()
+            if linear == "eigh":
+                np.testing.assert_array_equal(F[~hit], C.reference("300x8")[0][~hit])
+
+
 def test_host_helpers_of_the_product_agree_with_the_reference():
     sc = C.scene("300x8")
     po, co = np.arange(300) % 3 > 0, np.arange(8) != 4
