@@ -1,0 +1,650 @@
+// Robust two-view geometry (mvba_two_view_robust, mvba_ransac_sample): 8-point RANSAC for the fundamental matrix -- kernels
+// and host code, gfx950.
+//
+// Included by mvba.hip after mvba_twoview.h: uses its tv_find, k_twoview_combine, k_twoview_norm, twoview_solve_pair and
+// constants, mvba_init.h's checks, InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs
+// on the LM path.  
+//
+// Per pair of a tile (blockIdx.y or .z: the pair inside the tile): the shared observations are compacted into a dense array
+// of (x_k, y_k, x_l, y_l) in ascending point order (per-chunk counts, an exclusive scan over the pair's chunks, ballot and
+// prefix inside the workgroup); every later pass reads that array.  One THREAD per hypothesis draws its 8 indices, sums its
+// 9 x 9 moment matrix in registers (static indices) and diagonalises it by cyclic Jacobi with A and V in LDS, element-major
+// (element e of thread t at [e x 64 + t]: run-time row and column indices address LDS, not scratch, and a wave's 64 accesses
+// fall into 64 consecutive doubles).  The scoring kernel holds 64 hypothesis matrices in LDS, one compacted point per thread;
+// a hypothesis's count is ballot + popcount per wave, then integer atomics (LDS, then device memory): exact in any order.
+// Refits sum the moments of the compacted array under a byte mask by the fixed tree of k_twoview_chunk; the order-9
+// eigen-problem, the rank-2 step and the denormalisation are twoview_solve_pair's, on the host.  No floating-point atomics.
+
+namespace {
+
+constexpr int RS_HYP_BLOCK = 64;      // hypotheses per workgroup of k_ransac_hyp, and per LDS block of k_ransac_score
+constexpr int RS_MAX_HYP = 65536;     // n_hypotheses
+constexpr int RS_MAX_REFIT = 16;      // n_refit
+// device bytes one pair of a tile takes per point of the scene (32 compacted observation, 4 point id, 2 masks, 1 mask by
+// point, 1.42 chunk counts and partials) and per hypothesis (72 F^, 72 F, 4 count), rounded up: the tile's bound
+constexpr size_t RS_POINT_BYTES = 48, RS_HYP_BYTES = 160;
+enum { RS_CUR = 1, RS_ACTIVE = 2, RS_OK = 4 };  // per-pair state: the current mask buffer, still refitting, status 0
+
+__host__ __device__ __forceinline__ unsigned long long rs_mix(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// the 8 distinct indices below n (n >= 8) of hypothesis h of pair (k, l): a counter-based generator, rejection of repeats.
+// Every index of idx is a compile-time constant once the loops are unrolled (registers on the device).
+__host__ __device__ __forceinline__ void rs_sample(unsigned long long seed, int k, int l, int h, long long n, long long (&idx)[8]) {
+  unsigned long long s = rs_mix(rs_mix(rs_mix(seed) ^ (((unsigned long long)(unsigned int)k << 32) | (unsigned long long)(unsigned int)l)) ^
+                                (unsigned long long)(unsigned int)h);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    long long j;
+    bool dup;
+    do {
+      s = rs_mix(s);
+      j = (long long)(((s >> 32) * (unsigned long long)n) >> 32);  // (n < 2^31: the product is below 2^63)
+      dup = false;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (e < c && idx[e] == j) dup = true;
+    } while (dup);
+    idx[c] = j;
+  }
+}
+
+// the squared Sampson distance of k_twoview_chunk<3>
+__device__ __forceinline__ double rs_sampson(const double *F, double xk, double yk, double xl, double yl) {
+  const double f0 = F[0] * xk + F[1] * yk + F[2], f1 = F[3] * xk + F[4] * yk + F[5], f2 = F[6] * xk + F[7] * yk + F[8];
+  const double g0 = F[0] * xl + F[3] * yl + F[6], g1 = F[1] * xl + F[4] * yl + F[7];
+  const double r = xl * f0 + yl * f1 + f2;
+  return r * r / (f0 * f0 + f1 * f1 + g0 * g0 + g1 * g1);
+}
+
+// does point a see both cameras of the pair?  (its two observations in ok, ol)
+__device__ __forceinline__ bool rs_shared(long long a, long long npts, int m, const long long *__restrict__ pt_ptr,
+                                          const int *__restrict__ cam_idx, int k, int l, long long &ok, long long &ol) {
+  ok = ol = -1;
+  if (a < npts) {
+    const long long o0 = pt_ptr ? pt_ptr[a] : a * m;
+    const int deg = pt_ptr ? (int)(pt_ptr[a + 1] - pt_ptr[a]) : m;
+    const int *cam = pt_ptr ? cam_idx : nullptr;
+    ok = tv_find(cam, o0, deg, k);
+    if (ok >= 0) ol = tv_find(cam, o0, deg, l);
+  }
+  return ok >= 0 && ol >= 0;
+}
+
+// cnt[pair][chunk] = the number of shared points among the chunk's 256
+__global__ __launch_bounds__(TV_CHUNK) void k_ransac_count(long long npts, int m, const long long *__restrict__ pt_ptr,
+                                                           const int *__restrict__ cam_idx, const int *__restrict__ pairs,
+                                                           int *__restrict__ cnt) {
+  __shared__ int s_w[TV_CHUNK / 64];
+  const int p = blockIdx.y, i = threadIdx.x;
+  long long ok, ol;
+  const bool sh = rs_shared((long long)blockIdx.x * TV_CHUNK + i, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
+  const unsigned long long b = __ballot(sh);
+  if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
+  __syncthreads();
+  if (i == 0) {
+    int x = 0;
+#pragma unroll
+    for (int w = 0; w < TV_CHUNK / 64; ++w) x += s_w[w];
+    cnt[(size_t)p * gridDim.x + blockIdx.x] = x;
+  }
+}
+
+// one workgroup per pair: cnt[pair][.] -> its exclusive prefix sums, in place; ntot[pair] = the total.  Thread i takes a
+// contiguous run of chunks; thread 0 scans the 256 run sums.
+__global__ __launch_bounds__(256) void k_ransac_scan(int n_ch, int *__restrict__ cnt, int *__restrict__ ntot) {
+  __shared__ int s[256];
+  const int p = blockIdx.x, i = threadIdx.x;
+  int *c = cnt + (size_t)p * n_ch;
+  const int per = (n_ch + 255) / 256, a = min(n_ch, i * per), b = min(n_ch, a + per);
+  int sum = 0;
+  for (int e = a; e < b; ++e) sum += c[e];
+  s[i] = sum;
+  __syncthreads();
+  if (i == 0) {
+    int run = 0;
+    for (int t = 0; t < 256; ++t) {
+      const int v = s[t];
+      s[t] = run;
+      run += v;
+    }
+    ntot[p] = run;
+  }
+  __syncthreads();
+  int run = s[i];
+  for (int e = a; e < b; ++e) {
+    const int v = c[e];
+    c[e] = run;
+    run += v;
+  }
+}
+
+// comp[pair][j] = (x_k, y_k, x_l, y_l) and id[pair][j] = the point of the pair's j-th shared point, ascending
+__global__ __launch_bounds__(TV_CHUNK) void k_ransac_compact(long long npts, int m, const long long *__restrict__ pt_ptr,
+                                                             const int *__restrict__ cam_idx, const double2 *__restrict__ xy,
+                                                             const int *__restrict__ pairs, const int *__restrict__ off,
+                                                             double4 *__restrict__ comp, int *__restrict__ id) {
+  __shared__ int s_w[TV_CHUNK / 64];
+  const int p = blockIdx.y, i = threadIdx.x;
+  const long long a = (long long)blockIdx.x * TV_CHUNK + i;
+  long long ok, ol;
+  const bool sh = rs_shared(a, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
+  const unsigned long long b = __ballot(sh);
+  if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
+  __syncthreads();
+  if (!sh) return;
+  int j = off[(size_t)p * gridDim.x + blockIdx.x] + __popcll(b & ((1ull << (i & 63)) - 1ull));
+  for (int w = 0; w < (i >> 6); ++w) j += s_w[w];
+  const double2 zk = xy[ok], zl = xy[ol];
+  comp[(size_t)p * npts + j] = make_double4(zk.x, zk.y, zl.x, zl.y);  // (j < the pair's count <= npts)
+  id[(size_t)p * npts + j] = (int)a;
+}
+
+// the fixed tree of k_twoview_chunk: lanes l and l + off inside a wave, off = 32 .. 1, then the waves in ascending order
+template <int NV>
+__device__ __forceinline__ void rs_chunk_sum(const double (&v)[NV], double (&s_w)[TV_CHUNK / 64][NV], double *__restrict__ out) {
+  const int i = threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < NV; ++e) {
+    double x = v[e];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    if ((i & 63) == 0) s_w[i >> 6][e] = x;
+  }
+  __syncthreads();
+  if (i < NV) {
+    double x = s_w[0][i];
+#pragma unroll
+    for (int w = 1; w < TV_CHUNK / 64; ++w) x += s_w[w][i];
+    out[i] = x;
+  }
+}
+
+// The passes 0, 1, 2 of k_twoview_chunk over the compacted array: part[pair][chunk][NV] over the points j < ntot[pair] whose
+// byte in the pair's current mask is set (state == nullptr: every point).  A pair that is not RS_ACTIVE sums nothing.
+template <int MODE>
+__global__ __launch_bounds__(TV_CHUNK) void k_ransac_fit(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
+                                                         const double4 *__restrict__ comp, const unsigned char *__restrict__ inl0,
+                                                         const unsigned char *__restrict__ inl1, const double *__restrict__ aux,
+                                                         double *__restrict__ part) {
+  constexpr int NV = tv_values(MODE);
+  __shared__ double s_w[TV_CHUNK / 64][NV];
+  const int p = blockIdx.y, i = threadIdx.x;
+  const long long j = (long long)blockIdx.x * TV_CHUNK + i;
+  double v[NV];
+#pragma unroll
+  for (int e = 0; e < NV; ++e) v[e] = 0.0;
+  bool use = j < ntot[p];
+  if (state) {
+    const int st = state[p];
+    use = use && (st & RS_ACTIVE);
+    if (use) use = ((st & RS_CUR) ? inl1 : inl0)[(size_t)p * stride + j] != 0;
+  }
+  if (use) {
+    const double4 z = comp[(size_t)p * stride + j];
+    if constexpr (MODE == 0) {
+      v[0] = 1.0; v[1] = z.x; v[2] = z.y; v[3] = z.z; v[4] = z.w;
+    } else if constexpr (MODE == 1) {
+      const double *nm = aux + TV_NORM * (size_t)p;
+      const double d0 = z.x - nm[0], d1 = z.y - nm[1], e0 = z.z - nm[3], e1 = z.w - nm[4];
+      v[0] = d0 * d0 + d1 * d1;
+      v[1] = e0 * e0 + e1 * e1;
+    } else {
+      const double *nm = aux + TV_NORM * (size_t)p;
+      const double xk = nm[2] * (z.x - nm[0]), yk = nm[2] * (z.y - nm[1]);
+      const double xl = nm[5] * (z.z - nm[3]), yl = nm[5] * (z.w - nm[4]);
+      const double r[9] = {xl * xk, xl * yk, xl, yl * xk, yl * yk, yl, xk, yk, 1.0};
+      int e = 0;
+#pragma unroll
+      for (int b = 0; b < 9; ++b)
+#pragma unroll
+        for (int c = b; c < 9; ++c, ++e) v[e] = r[b] * r[c];
+    }
+  }
+  rs_chunk_sum<NV>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * NV);
+}
+
+// One thread per hypothesis: sample, M = sum of a a^T over the 8 normalised rows, cyclic Jacobi in LDS, F^ = the eigenvector
+// of the smallest eigenvalue -> hypf, F = T_l^T F^ T_k -> hypF; hyp_count = 0, or -1 (and NaN matrices) if degenerate.
+__global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, int H, unsigned long long seed, const int *__restrict__ pairs,
+                                                             const int *__restrict__ ntot, const double4 *__restrict__ comp,
+                                                             const double *__restrict__ norm, double *__restrict__ hypf,
+                                                             double *__restrict__ hypF, int *__restrict__ hyp_count) {
+  extern __shared__ double s_rs[];  // A [81][64], V [81][64]
+  const int p = blockIdx.y, tid = threadIdx.x, h = blockIdx.x * RS_HYP_BLOCK + tid;
+  if (h >= H) return;  // (no barrier below: a thread works on its own LDS column)
+  const size_t o9 = ((size_t)p * H + h) * 9;
+  const int n = ntot[p];
+  bool good = n >= TV_MIN_SHARED;  // (below 8 the rejection loop of rs_sample would not end)
+  double fh[9], F[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) fh[e] = F[e] = NAN;
+  if (good) {
+    double *sA = s_rs + tid, *sV = s_rs + 81 * RS_HYP_BLOCK + tid;
+    auto A = [&](int r, int c) -> double & { return sA[(r * 9 + c) * RS_HYP_BLOCK]; };
+    auto V = [&](int r, int c) -> double & { return sV[(r * 9 + c) * RS_HYP_BLOCK]; };
+    const double *nm = norm + TV_NORM * (size_t)p;
+    const double ckx = nm[0], cky = nm[1], sk = nm[2], clx = nm[3], cly = nm[4], sl = nm[5];
+    long long idx[8];
+    rs_sample(seed, pairs[2 * p], pairs[2 * p + 1], h, n, idx);
+    double M[45];
+#pragma unroll
+    for (int e = 0; e < 45; ++e) M[e] = 0.0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const double4 z = comp[(size_t)p * stride + idx[c]];
+      const double xk = sk * (z.x - ckx), yk = sk * (z.y - cky), xl = sl * (z.z - clx), yl = sl * (z.w - cly);
+      const double r[9] = {xl * xk, xl * yk, xl, yl * xk, yl * yk, yl, xk, yk, 1.0};
+      int e = 0;
+#pragma unroll
+      for (int b = 0; b < 9; ++b)
+#pragma unroll
+        for (int d = b; d < 9; ++d, ++e) M[e] += r[b] * r[d];
+    }
+    {
+      int e = 0;
+#pragma unroll
+      for (int b = 0; b < 9; ++b)
+#pragma unroll
+        for (int d = b; d < 9; ++d, ++e) {
+          good = good && isfinite(M[e]);
+          A(b, d) = M[e];
+          A(d, b) = M[e];
+        }
+    }
+    for (int e = 0; e < 81; ++e) sV[e * RS_HYP_BLOCK] = (e % 10 == 0) ? 1.0 : 0.0;
+    // sym_eig_jacobi's rotations and stopping rule, with run-time indices into LDS
+    for (int sweep = 0; sweep < 30 && good; ++sweep) {
+      bool any = false;
+      for (int a = 0; a < 8; ++a)
+        for (int b = a + 1; b < 9; ++b) {
+          const double apq = A(a, b), app = A(a, a), aqq = A(b, b);
+          const double g = fabs(apq);
+          if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
+            A(a, b) = A(b, a) = 0.0;
+            continue;
+          }
+          any = true;
+          const double theta = (aqq - app) / (2.0 * apq);
+          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+          A(a, a) = app - t * apq;
+          A(b, b) = aqq + t * apq;
+          A(a, b) = A(b, a) = 0.0;
+          for (int r = 0; r < 9; ++r) {
+            if (r != a && r != b) {
+              const double arp = A(r, a), arq = A(r, b);
+              A(r, a) = A(a, r) = arp - s * (arq + tau * arp);
+              A(r, b) = A(b, r) = arq + s * (arp - tau * arq);
+            }
+            const double vrp = V(r, a), vrq = V(r, b);
+            V(r, a) = vrp - s * (vrq + tau * vrp);
+            V(r, b) = vrq + s * (vrp - tau * vrq);
+          }
+        }
+      if (!any) break;
+    }
+    if (good) {
+      int best = 0;
+      double l1 = A(0, 0), lmax = A(0, 0), l2 = HUGE_VAL;
+      for (int e = 1; e < 9; ++e) {
+        const double d = A(e, e);
+        if (d < l1) { l1 = d; best = e; }
+        lmax = fmax(lmax, d);
+      }
+      for (int e = 0; e < 9; ++e)
+        if (e != best) l2 = fmin(l2, A(e, e));
+      good = l2 > INIT_REL_PIVOT * lmax;
+#pragma unroll
+      for (int e = 0; e < 9; ++e) fh[e] = V(e, best);
+      // F = T_l^T F^ T_k with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]] (twoview_solve_pair, without its rank-2 step)
+      double Q[3][3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        Q[r][0] = sk * fh[3 * r];
+        Q[r][1] = sk * fh[3 * r + 1];
+        Q[r][2] = fh[3 * r + 2] - sk * (ckx * fh[3 * r] + cky * fh[3 * r + 1]);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        F[c] = sl * Q[0][c];
+        F[3 + c] = sl * Q[1][c];
+        F[6 + c] = Q[2][c] - sl * (clx * Q[0][c] + cly * Q[1][c]);
+      }
+#pragma unroll
+      for (int e = 0; e < 9; ++e) good = good && isfinite(F[e]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    hypf[o9 + e] = good ? fh[e] : NAN;
+    hypF[o9 + e] = good ? F[e] : NAN;
+  }
+  hyp_count[(size_t)p * H + h] = good ? 0 : -1;
+}
+
+// Scoring: grid (chunks of compacted points, blocks of 64 hypotheses, pairs).  A thread holds one point and walks the block's
+// matrices in LDS (every lane reads the same address: a broadcast); a hypothesis's inliers of a wave are one ballot and one
+// popcount, kept by the lane of the hypothesis's number; then integer atomics.  A degenerate hypothesis is NaN: no point
+// passes, its count stays -1.
+__global__ __launch_bounds__(TV_CHUNK) void k_ransac_score(long long stride, int H, const int *__restrict__ ntot,
+                                                           const double4 *__restrict__ comp, const double *__restrict__ hypF,
+                                                           double thr2, int *__restrict__ hyp_count) {
+  __shared__ double s_F[RS_HYP_BLOCK * 9];
+  __shared__ int s_cnt[RS_HYP_BLOCK];
+  const int p = blockIdx.z, h0 = blockIdx.y * RS_HYP_BLOCK, i = threadIdx.x, lane = i & 63;
+  const int n = ntot[p];
+  const long long j = (long long)blockIdx.x * TV_CHUNK + i;
+  if (n < TV_MIN_SHARED || (long long)blockIdx.x * TV_CHUNK >= n) return;  // (the whole workgroup leaves)
+  const int nh = min(RS_HYP_BLOCK, H - h0);
+  for (int e = i; e < nh * 9; e += TV_CHUNK) s_F[e] = hypF[((size_t)p * H + h0) * 9 + e];
+  if (i < RS_HYP_BLOCK) s_cnt[i] = 0;
+  __syncthreads();
+  const bool live = j < n;
+  const double4 z = live ? comp[(size_t)p * stride + j] : make_double4(0.0, 0.0, 0.0, 0.0);
+  int mine = 0;
+  for (int hh = 0; hh < nh; ++hh) {
+    const double d2 = rs_sampson(s_F + 9 * hh, z.x, z.y, z.z, z.w);
+    const int c = __popcll(__ballot(live && d2 <= thr2));
+    if (lane == hh) mine = c;
+  }
+  if (mine) atomicAdd(&s_cnt[lane], mine);
+  __syncthreads();
+  if (i < nh && s_cnt[i]) atomicAdd(&hyp_count[(size_t)p * H + h0 + i], s_cnt[i]);
+}
+
+// Fcur[pair], fbest[pair] = the matrices of the pair's best hypothesis (best < 0: NaN)
+__global__ __launch_bounds__(256) void k_ransac_gather(int n_pairs, int H, const int *__restrict__ best, const double *__restrict__ hypF,
+                                                       const double *__restrict__ hypf, double *__restrict__ Fcur, double *__restrict__ fbest) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_pairs * 9) return;
+  const int p = t / 9, e = t - 9 * p, b = best[p];
+  Fcur[t] = b >= 0 ? hypF[((size_t)p * H + b) * 9 + e] : NAN;
+  fbest[t] = b >= 0 ? hypf[((size_t)p * H + b) * 9 + e] : NAN;
+}
+
+// The inlier set of F[pair] into the pair's OTHER mask buffer, and part[pair][chunk][2] = (count, sum of d^2 over it) by the
+// fixed tree (the count is exact in a double).  A pair that is not RS_ACTIVE writes nothing and sums nothing.
+__global__ __launch_bounds__(TV_CHUNK) void k_ransac_mask(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
+                                                          const double4 *__restrict__ comp, const double *__restrict__ F, double thr2,
+                                                          unsigned char *__restrict__ inl0, unsigned char *__restrict__ inl1,
+                                                          double *__restrict__ part) {
+  __shared__ double s_w[TV_CHUNK / 64][2];
+  const int p = blockIdx.y, i = threadIdx.x, st = state[p];
+  const long long j = (long long)blockIdx.x * TV_CHUNK + i;
+  double v[2] = {0.0, 0.0};
+  if ((st & RS_ACTIVE) && j < ntot[p]) {
+    const double4 z = comp[(size_t)p * stride + j];
+    const double d2 = rs_sampson(F + 9 * (size_t)p, z.x, z.y, z.z, z.w);
+    const bool in = d2 <= thr2;
+    ((st & RS_CUR) ? inl0 : inl1)[(size_t)p * stride + j] = in ? 1 : 0;
+    if (in) { v[0] = 1.0; v[1] = d2; }
+  }
+  rs_chunk_sum<2>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * 2);
+}
+
+// out[pair][point] = 1 for the points of the pair's current mask (pairs of status 0; out is zero beforehand)
+__global__ __launch_bounds__(TV_CHUNK) void k_ransac_scatter(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
+                                                             const int *__restrict__ id, const unsigned char *__restrict__ inl0,
+                                                             const unsigned char *__restrict__ inl1, unsigned char *__restrict__ out) {
+  const int p = blockIdx.y, st = state[p];
+  const long long j = (long long)blockIdx.x * TV_CHUNK + threadIdx.x;
+  if (!(st & RS_OK) || j >= ntot[p]) return;
+  if (((st & RS_CUR) ? inl1 : inl0)[(size_t)p * stride + j]) out[(size_t)p * stride + id[(size_t)p * stride + j]] = 1;
+}
+
+// F^ (unit, normalised units) -> F through twoview_solve_pair's own rank-2 step, denormalisation and scaling: the moment
+// matrix I - f f^T has f as the eigenvector of its one zero eigenvalue (the others are 1).
+int ransac_finish_hypothesis(const double *fh, const double *nm, double *F) {
+  double S45[45], ratio;
+  int e = 0;
+  for (int b = 0; b < 9; ++b)
+    for (int c = b; c < 9; ++c, ++e) S45[e] = (b == c ? 1.0 : 0.0) - fh[b] * fh[c];
+  return twoview_solve_pair(S45, nm, F, &ratio);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvba_ransac_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx8) {
+  if (!idx8) return fail(MVBA_ERR_BADARG, "null argument: idx8 (argument 6)");
+  if (n < TV_MIN_SHARED || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 8 .. 2^31 - 1");
+  if (k < 0 || l < 0 || h < 0)
+    return fail(MVBA_ERR_BADARG, "k = " + std::to_string(k) + ", l = " + std::to_string(l) + ", h = " + std::to_string(h) + ": negative index");
+  long long idx[8];
+  rs_sample(seed, k, l, h, n, idx);
+  for (int c = 0; c < 8; ++c) idx8[c] = idx[c];
+  return MVBA_OK;
+}
+
+int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
+                         const int32_t *pairs, int32_t n_pairs, double threshold, int32_t n_hypotheses, uint64_t seed, int32_t n_refit,
+                         double *F, double *quality, int64_t *n_shared, int64_t *n_inliers, int32_t *best, uint8_t *inlier,
+                         int32_t *hyp_count, int32_t *status, double *timings_ms, int32_t device) {
+  if (n_pairs < 0) return fail(MVBA_ERR_BADARG, "n_pairs = " + std::to_string(n_pairs) + " must be >= 0");
+  if (!xy || (n_pairs > 0 && (!pairs || !F)))
+    return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!xy ? "xy" : (!pairs ? "pairs" : "F")) + " (argument " +
+                                     std::to_string(!xy ? 5 : (!pairs ? 7 : 13)) + ")");
+  if (!std::isfinite(threshold) || !(threshold > 0.0))
+    return fail(MVBA_ERR_BADARG, "threshold = " + std::to_string(threshold) + " must be finite and > 0");
+  if (n_hypotheses < 1 || n_hypotheses > RS_MAX_HYP)
+    return fail(MVBA_ERR_BADARG, "n_hypotheses = " + std::to_string(n_hypotheses) + " must be in 1 .. " + std::to_string(RS_MAX_HYP));
+  if (n_refit < 0 || n_refit > RS_MAX_REFIT)
+    return fail(MVBA_ERR_BADARG, "n_refit = " + std::to_string(n_refit) + " must be in 0 .. " + std::to_string(RS_MAX_REFIT));
+  int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
+  if (rc) return rc;
+  if ((rc = init_check_cameras(n_images))) return rc;
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    const int32_t k = pairs[2 * p], l = pairs[2 * p + 1];
+    if (k < 0 || k >= n_images || l < 0 || l >= n_images)
+      return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) +
+                                       "): camera index out of range, n_images = " + std::to_string(n_images));
+    if (k == l) return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) + "): the two cameras must differ");
+  }
+  if (pt_ptr)  // the kernels search a point's camera run: it must ascend
+    for (int64_t a = 0; a < n_points; ++a)
+      for (int64_t o = pt_ptr[a] + 1; o < pt_ptr[a + 1]; ++o)
+        if (cam_idx[o] <= cam_idx[o - 1])
+          return fail(MVBA_ERR_BADARG, "cam_idx is not ascending within point " + std::to_string(a) + ": cam_idx[" + std::to_string(o) + "] = " +
+                                           std::to_string(cam_idx[o]) + " after " + std::to_string(cam_idx[o - 1]));
+  if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
+  const int np = n_pairs, H = n_hypotheses;
+  const double thr2 = threshold * threshold;
+  // the defaults are those of a pair without shared points: status 1
+  for (int p = 0; p < np; ++p) {
+    for (int j = 0; j < 9; ++j) F[9 * (size_t)p + j] = NAN;
+    if (quality) quality[2 * p] = quality[2 * p + 1] = NAN;
+    if (n_shared) n_shared[p] = 0;
+    if (n_inliers) n_inliers[p] = 0;
+    if (best) best[p] = -1;
+    if (status) status[p] = 1;
+  }
+  if (inlier) std::memset(inlier, 0, (size_t)np * (size_t)n_points);
+  if (hyp_count) std::fill(hyp_count, hyp_count + (size_t)np * H, -1);
+  if (np == 0 || n_points == 0) return MVBA_OK;
+
+  if (device >= 0) MVBA_HIP(hipSetDevice(device));
+  InitClock clk;
+  const long long n_ch = (n_points + TV_CHUNK - 1) / TV_CHUNK;
+  const long long stride = n_points;
+  const int tile = (int)std::max<long long>(
+      1, std::min<long long>(std::min<long long>(np, 65535), (long long)(TV_PART_BYTES / (RS_POINT_BYTES * (size_t)n_points + RS_HYP_BYTES * (size_t)H))));
+  DevBufs tmp;
+  double2 *dxy = nullptr;
+  long long *dptr = nullptr;
+  int *dcam = nullptr, *dpairs = nullptr, *doff = nullptr, *dntot = nullptr, *did = nullptr, *dstate = nullptr, *dbest = nullptr, *dhc = nullptr;
+  double4 *dcomp = nullptr;
+  unsigned char *dinl0 = nullptr, *dinl1 = nullptr, *dout = nullptr;
+  double *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dnorm2 = nullptr, *dF = nullptr, *dfb = nullptr, *dhypf = nullptr, *dhypF = nullptr;
+  const size_t ts = (size_t)tile * (size_t)stride;
+  if ((rc = tmp.alloc(&dxy, (size_t)n_obs)) || (rc = tmp.alloc(&dpairs, 2 * (size_t)np)) || (rc = tmp.alloc(&doff, (size_t)tile * n_ch)) ||
+      (rc = tmp.alloc(&dntot, (size_t)tile)) || (rc = tmp.alloc(&did, ts)) || (rc = tmp.alloc(&dstate, (size_t)tile)) ||
+      (rc = tmp.alloc(&dbest, (size_t)tile)) || (rc = tmp.alloc(&dhc, (size_t)tile * H)) || (rc = tmp.alloc(&dcomp, ts)) ||
+      (rc = tmp.alloc(&dinl0, ts)) || (rc = tmp.alloc(&dinl1, ts)) || (rc = tmp.alloc(&dpart, 45 * (size_t)n_ch * tile)) ||
+      (rc = tmp.alloc(&dS, 45 * (size_t)tile)) || (rc = tmp.alloc(&dnorm, TV_NORM * (size_t)tile)) || (rc = tmp.alloc(&dnorm2, TV_NORM * (size_t)tile)) ||
+      (rc = tmp.alloc(&dF, 9 * (size_t)tile)) || (rc = tmp.alloc(&dfb, 9 * (size_t)tile)) || (rc = tmp.alloc(&dhypf, 9 * (size_t)tile * H)) ||
+      (rc = tmp.alloc(&dhypF, 9 * (size_t)tile * H)))
+    return rc;
+  if (inlier && (rc = tmp.alloc(&dout, ts))) return rc;
+  if (n_obs) MVBA_HIP(hipMemcpy(dxy, xy, sizeof(double2) * n_obs, hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(dpairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice));
+  if (pt_ptr) {
+    if ((rc = tmp.alloc(&dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(&dcam, (size_t)n_obs))) return rc;
+    MVBA_HIP(hipMemcpy(dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
+    if (n_obs) MVBA_HIP(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
+  }
+  const int hyp_lds = (int)(sizeof(double) * 2 * 81 * RS_HYP_BLOCK);
+  MVBA_HIP(hipFuncSetAttribute((const void *)k_ransac_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, hyp_lds));
+  double t_up = clk.lap(), t_score = 0.0, t_refit = 0.0, t_rest = 0.0;
+
+  const dim3 b256(256), bch(TV_CHUNK);
+  std::vector<int> ntot((size_t)tile), hc((size_t)tile * H), bst((size_t)tile), state((size_t)tile), st((size_t)tile);
+  std::vector<long long> nin((size_t)tile);
+  std::vector<double> S((size_t)tile * 45), norm(TV_NORM * (size_t)tile), fb(9 * (size_t)tile), Fc(9 * (size_t)tile), Fn(9 * (size_t)tile),
+      S2(2 * (size_t)tile), ssq((size_t)tile), ratio((size_t)tile);
+  for (int p0 = 0; p0 < np; p0 += tile) {
+    const int cnt = std::min(tile, np - p0);
+    const dim3 grid((unsigned)n_ch, (unsigned)cnt), gp((cnt + 255) / 256);
+    const int *tp = dpairs + 2 * (size_t)p0;
+    auto combine = [&](int nv, double *out) {
+      hipLaunchKernelGGL(k_twoview_combine, dim3((unsigned)(((long long)cnt * nv + 3) / 4)), b256, 0, 0, cnt, nv, (int)n_ch, dpart, out, nv);
+    };
+    // the normalised 8-point sums of the pairs' current masks (st_dev == nullptr: of all shared points, passes 0 and 1 only)
+    auto fit = [&](const int *st_dev, double *nm_dev, bool moments) {
+      hipLaunchKernelGGL(k_ransac_fit<0>, grid, bch, 0, 0, stride, dntot, st_dev, dcomp, dinl0, dinl1, (const double *)nullptr, dpart);
+      combine(5, dS);
+      hipLaunchKernelGGL(k_twoview_norm, gp, b256, 0, 0, cnt, 0, dS, 5, nm_dev);
+      hipLaunchKernelGGL(k_ransac_fit<1>, grid, bch, 0, 0, stride, dntot, st_dev, dcomp, dinl0, dinl1, nm_dev, dpart);
+      combine(2, dS);
+      hipLaunchKernelGGL(k_twoview_norm, gp, b256, 0, 0, cnt, 1, dS, 2, nm_dev);
+      if (moments) {
+        hipLaunchKernelGGL(k_ransac_fit<2>, grid, bch, 0, 0, stride, dntot, st_dev, dcomp, dinl0, dinl1, nm_dev, dpart);
+        combine(45, dS);
+      }
+    };
+    // the inlier sets of dF under the pairs' states: counts and sums of d^2 into S2
+    auto mask = [&]() -> int {
+      MVBA_HIP(hipMemcpy(dstate, state.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(k_ransac_mask, grid, bch, 0, 0, stride, dntot, dstate, dcomp, dF, thr2, dinl0, dinl1, dpart);
+      combine(2, dS);
+      MVBA_HIP(hipGetLastError());
+      MVBA_HIP(hipMemcpy(S2.data(), dS, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost));
+      return MVBA_OK;
+    };
+
+    // compaction, normalisation over all shared points, hypotheses, scores
+    hipLaunchKernelGGL(k_ransac_count, grid, bch, 0, 0, (long long)n_points, n_images, dptr, dcam, tp, doff);
+    hipLaunchKernelGGL(k_ransac_scan, dim3(cnt), b256, 0, 0, (int)n_ch, doff, dntot);
+    hipLaunchKernelGGL(k_ransac_compact, grid, bch, 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, doff, dcomp, did);
+    fit(nullptr, dnorm, false);
+    hipLaunchKernelGGL(k_ransac_hyp, dim3((H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, cnt), dim3(RS_HYP_BLOCK), hyp_lds, 0, stride, H,
+                       (unsigned long long)seed, tp, dntot, dcomp, dnorm, dhypf, dhypF, dhc);
+    hipLaunchKernelGGL(k_ransac_score, dim3((unsigned)n_ch, (H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, cnt), bch, 0, 0, stride, H, dntot, dcomp,
+                       dhypF, thr2, dhc);
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipMemcpy(hc.data(), dhc, sizeof(int) * (size_t)cnt * H, hipMemcpyDeviceToHost));
+    MVBA_HIP(hipMemcpy(ntot.data(), dntot, sizeof(int) * cnt, hipMemcpyDeviceToHost));
+    MVBA_HIP(hipMemcpy(norm.data(), dnorm, sizeof(double) * TV_NORM * cnt, hipMemcpyDeviceToHost));
+    t_score += clk.lap();
+
+    // arg-max on the host: the largest count, the lowest h on ties
+    for (int p = 0; p < cnt; ++p) {
+      const int *c = hc.data() + (size_t)p * H;
+      int b = 0;
+      for (int h = 1; h < H; ++h)
+        if (c[h] > c[b]) b = h;
+      st[p] = ntot[p] < TV_MIN_SHARED ? 1 : (c[b] < 0 ? 2 : (c[b] < TV_MIN_SHARED ? 4 : 0));
+      bst[p] = c[b] < 0 ? -1 : b;  // (status 1 and 2: every count is -1)
+      state[p] = st[p] == 0 ? (RS_OK | RS_ACTIVE | RS_CUR) : 0;  // (the first mask goes into buffer 0)
+    }
+    MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_ransac_gather, dim3((cnt * 9 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhypF, dhypf, dF, dfb);
+    if ((rc = mask())) return rc;
+    MVBA_HIP(hipMemcpy(fb.data(), dfb, sizeof(double) * 9 * cnt, hipMemcpyDeviceToHost));
+    int n_active = 0;
+    for (int p = 0; p < cnt; ++p) {
+      if (st[p]) continue;
+      state[p] ^= RS_CUR;
+      nin[p] = (long long)S2[2 * p];
+      ssq[p] = S2[2 * p + 1];
+      ratio[p] = 0.0;  // (the moment matrix of a minimal sample has rank 8)
+      st[p] = ransac_finish_hypothesis(fb.data() + 9 * (size_t)p, norm.data() + TV_NORM * (size_t)p, Fc.data() + 9 * (size_t)p);
+      if (st[p]) state[p] = 0;
+      else ++n_active;
+    }
+    t_rest += clk.lap();
+
+    // refits: the full fit on the current inliers alone, kept while its own inlier set does not shrink
+    for (int r = 0; r < n_refit && n_active > 0; ++r) {
+      MVBA_HIP(hipMemcpy(dstate, state.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+      fit(dstate, dnorm2, true);
+      MVBA_HIP(hipGetLastError());
+      MVBA_HIP(hipMemcpy(S.data(), dS, sizeof(double) * 45 * cnt, hipMemcpyDeviceToHost));
+      MVBA_HIP(hipMemcpy(norm.data(), dnorm2, sizeof(double) * TV_NORM * cnt, hipMemcpyDeviceToHost));
+      std::vector<double> rt((size_t)cnt, NAN);
+      for (int p = 0; p < cnt; ++p) {
+        for (int j = 0; j < 9; ++j) Fn[9 * (size_t)p + j] = NAN;
+        if (!(state[p] & RS_ACTIVE)) continue;
+        if (twoview_solve_pair(S.data() + 45 * (size_t)p, norm.data() + TV_NORM * (size_t)p, Fn.data() + 9 * (size_t)p, &rt[p])) {
+          state[p] &= ~RS_ACTIVE;
+          --n_active;
+        }
+      }
+      if (n_active == 0) break;
+      MVBA_HIP(hipMemcpy(dF, Fn.data(), sizeof(double) * 9 * cnt, hipMemcpyHostToDevice));
+      if ((rc = mask())) return rc;
+      for (int p = 0; p < cnt; ++p) {
+        if (!(state[p] & RS_ACTIVE)) continue;
+        const long long c = (long long)S2[2 * p];
+        if (c >= nin[p]) {
+          state[p] ^= RS_CUR;
+          nin[p] = c;
+          ssq[p] = S2[2 * p + 1];
+          ratio[p] = rt[p];
+          for (int j = 0; j < 9; ++j) Fc[9 * (size_t)p + j] = Fn[9 * (size_t)p + j];
+        } else {
+          state[p] &= ~RS_ACTIVE;
+          --n_active;
+        }
+      }
+    }
+    t_refit += clk.lap();
+
+    if (inlier) {
+      MVBA_HIP(hipMemcpy(dstate, state.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+      MVBA_HIP(hipMemset(dout, 0, (size_t)cnt * stride));
+      hipLaunchKernelGGL(k_ransac_scatter, grid, bch, 0, 0, stride, dntot, dstate, did, dinl0, dinl1, dout);
+      MVBA_HIP(hipGetLastError());
+      MVBA_HIP(hipMemcpy(inlier + (size_t)p0 * stride, dout, (size_t)cnt * stride, hipMemcpyDeviceToHost));
+    }
+    for (int p = 0; p < cnt; ++p) {
+      const size_t g = (size_t)p0 + p;
+      if (n_shared) n_shared[g] = ntot[p];
+      if (status) status[g] = st[p];
+      if (best) best[g] = bst[p];
+      if (hyp_count) std::copy(hc.begin() + (size_t)p * H, hc.begin() + (size_t)(p + 1) * H, hyp_count + g * H);
+      if (st[p]) continue;
+      for (int j = 0; j < 9; ++j) F[9 * g + j] = Fc[9 * (size_t)p + j];
+      if (n_inliers) n_inliers[g] = nin[p];
+      if (quality) {
+        quality[2 * g] = sqrt(ssq[p] / (double)nin[p]);
+        quality[2 * g + 1] = ratio[p];
+      }
+    }
+    t_rest += clk.lap();
+  }
+  if (timings_ms) {
+    timings_ms[0] = t_up;
+    timings_ms[1] = t_score;
+    timings_ms[2] = t_refit;
+    timings_ms[3] = t_rest;
+  }
+  return MVBA_OK;
+}
+
+}  // extern "C"

@@ -98,6 +98,11 @@ SIGNATURES = {
                                     _dp, C.c_int32]),
     "mvba_two_view": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.POINTER(C.c_int32),
                                 C.c_int32, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_two_view_robust": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.POINTER(C.c_int32),
+                                       C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int32, _dp, _dp, C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_ransac_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -512,6 +517,57 @@ def two_view(pt_ptr, cam_idx, xy, n_images, pairs, device=-1):
     raise_for(lib.mvba_two_view(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, _ptr(F), _ptr(q),
                                 ns.ctypes.data_as(C.POINTER(C.c_int64)), st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm), int(device)), lib)
     return F, q, ns, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+
+
+def two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=512, seed=0, n_refit=2, return_inliers=True,
+                    return_counts=False, device=-1):
+    """Fundamental matrices by 8-point RANSAC on the device (mvba_two_view_robust).  The list and ``pairs`` as for ``two_view``;
+    ``threshold`` is a Sampson distance in the units of xy.  Returns a dict: ``F (P, 3, 3)``, ``quality (P, 2)`` (RMS Sampson
+    distance over the final inliers, eigenvalue ratio of the last kept refit), ``n_shared``, ``n_inliers``, ``best``, ``status``
+    (P,) (0 ok, 1 fewer than 8 shared points, 2 every hypothesis degenerate, 4 best count below 8; F and quality NaN then),
+    ``inlier (P, N) bool`` (``return_inliers``: P x N bytes on the host and on the device), ``hyp_count (P, H) int32``
+    (``return_counts``), ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    if device_count() < 1:
+        raise RuntimeError("libmvba: no HIP device visible; mvba_two_view_robust has no CPU fallback")
+    xy, m = _as(xy, np.float64), int(n_images)
+    pairs = _as(pairs, np.int32).reshape(-1, 2)
+    if pt_ptr is None:
+        assert xy.ndim == 3 and xy.shape[1:] == (m, 2)
+        n, n_obs, pp, cp = xy.shape[0], xy.shape[0] * m, None, None
+    else:
+        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
+        xy = xy.reshape(-1, 2)
+        assert xy.shape[0] == cam_idx.shape[0]
+        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    P, H = pairs.shape[0], int(n_hypotheses)
+    i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    F, q, tm = np.empty((P, 3, 3)), np.empty((P, 2)), np.zeros(4)
+    ns, ni, best, st = np.empty(P, np.int64), np.empty(P, np.int64), np.empty(P, np.int32), np.empty(P, np.int32)
+    inl = np.empty((P, n), np.uint8) if return_inliers else None
+    hc = np.empty((P, max(H, 0)), np.int32) if return_counts else None
+    raise_for(lib.mvba_two_view_robust(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(i32), P, float(threshold), H,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(F), _ptr(q), ns.ctypes.data_as(i64),
+                                       ni.ctypes.data_as(i64), best.ctypes.data_as(i32),
+                                       inl.ctypes.data_as(C.POINTER(C.c_uint8)) if return_inliers else None,
+                                       hc.ctypes.data_as(i32) if return_counts else None, st.ctypes.data_as(i32), _ptr(tm), int(device)), lib)
+    out = {"F": F, "quality": q, "n_shared": ns, "n_inliers": ni, "best": best, "status": st,
+           "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
+    if return_inliers:
+        out["inlier"] = inl.astype(bool)
+    if return_counts:
+        out["hyp_count"] = hc
+    return out
+
+
+def ransac_sample(seed, k, l, h, n):
+    """The 8 distinct indices below ``n`` that hypothesis ``h`` of pair (k, l) draws (mvba_ransac_sample: the host instance of
+    the function the kernel runs; no GPU needed)."""
+    lib = load_library()
+    idx = np.empty(8, np.int64)
+    raise_for(lib.mvba_ransac_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(l), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
+    return idx
 
 
 def host_obs_math(X3, cam15, xy2, f0):

@@ -5,7 +5,8 @@ on the MI355X (``mvba_triangulate``, ``mvba_resect``: csrc/mvba_init.h, DESIGN.m
 And the step that starts one: co-visibility counts and the fundamental matrix of two views from the points they share
 (``mvba_covisibility``, ``mvba_two_view``: csrc/mvba_twoview.h), the relative pose out of it, and
 ``bootstrap``, the incremental driver -- host control flow over the device calls -- that grows a start pair into an
-initial estimate for ``BundleAdjuster.from_observations``.
+initial estimate for ``BundleAdjuster.from_observations``.  With wrong matches among the tracks the first F comes from 8-point
+RANSAC on the device instead (``mvba_two_view_robust``: csrc/mvba_ransac.h): ``ransac_threshold``.
 """
 from __future__ import annotations
 
@@ -94,9 +95,37 @@ def fundamental_matrices(pt_ptr, cam_idx, xy, n_images, pairs):
     norm 1, largest-magnitude entry positive.  ``info``: ``status`` (P,) -- 0 ok, 1 fewer than 8 shared points, 2 degenerate
     (noise-free points in a plane, two cameras at one centre); F and quality are NaN where it is not 0 --, ``quality`` (P, 2) --
     RMS Sampson distance in units of xy, eigenvalue ratio lambda_1 / lambda_2 (small: well determined) --, ``n_shared`` (P,)
-    and ``timings_ms``.  No RANSAC: a gross outlier moves F, and ``quality`` shows it."""
+    and ``timings_ms``.  Every shared point enters the fit: a gross outlier moves F, and ``quality`` shows it;
+    ``robust_fundamental_matrices`` is the fit that tolerates them."""
     F, quality, n_shared, status, tm = _mvba.two_view(pt_ptr, cam_idx, xy, n_images, pairs)
     return F, {"status": status, "quality": quality, "n_shared": n_shared, "timings_ms": tm}
+
+
+def robust_fundamental_matrices(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses: int = 512, seed: int = 0,
+                                n_refit: int = 2, return_inliers: bool = True):
+    """(F (P, 3, 3), info): ``fundamental_matrices`` by 8-point RANSAC on the device (``mvba_two_view_robust``).  Per pair,
+    ``n_hypotheses`` minimal samples (a counter-based generator of ``seed``, the pair and the hypothesis number:
+    ``ransac_sample``) are solved and scored by the number of shared points whose Sampson distance is at most ``threshold``
+    (units of xy); the best hypothesis's inliers get the full normalised 8-point fit, ``n_refit`` times at most, each kept while
+    its own inlier set does not shrink.  ``info``: ``status`` (P,) -- 0 ok, 1 fewer than 8 shared points, 2 every hypothesis
+    degenerate, 4 the best hypothesis has fewer than 8 inliers; F and quality are NaN where it is not 0 --, ``n_shared``,
+    ``n_inliers``, ``best`` (P,), ``quality`` (P, 2) -- RMS Sampson distance over the final inliers, lambda_1 / lambda_2 of the
+    last kept refit --, ``inlier`` (P, N) bool (``return_inliers``; P x N bytes), ``confidence`` (P,) = 1 - (1 - w^8)^H with
+    w = n_inliers / n_shared -- the probability that one of H samples was all inliers -- and ``timings_ms``.  Two calls with
+    the same arguments return the same bits."""
+    out = _mvba.two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=n_hypotheses, seed=seed, n_refit=n_refit,
+                                return_inliers=return_inliers)
+    F = out.pop("F")
+    with np.errstate(all="ignore"):
+        w = out["n_inliers"] / np.maximum(out["n_shared"], 1)
+        out["confidence"] = np.where(out["status"] == 0, 1.0 - (1.0 - w ** 8) ** int(n_hypotheses), 0.0)
+    return F, out
+
+
+def ransac_sample(seed, k, l, h, n):
+    """The 8 distinct indices below ``n`` (of a pair's shared points in ascending point order) that hypothesis ``h`` of pair
+    (k, l) draws under ``seed`` -- the host instance of the function the kernel runs."""
+    return _mvba.ransac_sample(seed, k, l, h, n)
 
 
 def restrict_observations(pt_ptr, cam_idx, xy, point_ok, camera_ok):
@@ -132,15 +161,16 @@ def pose_candidates(E):
     return out
 
 
-def _pair_list(pt_ptr, cam_idx, xy, n_images, k, l):
-    """The two-camera sub-list over all points (the lower camera index becomes 0) and the positions of k and l in it."""
+def _pair_list(pt_ptr, cam_idx, xy, n_images, k, l, point_ok=None):
+    """The two-camera sub-list over all points, or over those marked (the lower camera index becomes 0), the old index of each
+    of its points and the positions of k and l in it."""
     cam_ok = np.zeros(n_images, bool)
     cam_ok[[k, l]] = True
-    ptr, cam, z, _, _ = restrict_observations(pt_ptr, cam_idx, xy, np.ones(len(pt_ptr) - 1, bool), cam_ok)
-    return ptr, cam, z, (0, 1) if k < l else (1, 0)
+    ptr, cam, z, ids, _ = restrict_observations(pt_ptr, cam_idx, xy, np.ones(len(pt_ptr) - 1, bool) if point_ok is None else point_ok, cam_ok)
+    return ptr, cam, z, ids, (0, 1) if k < l else (1, 0)
 
 
-def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2):
+def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2, ransac_threshold=None, n_hypotheses: int = 512, seed: int = 0):
     """(R (2, 3, 3), t (2, 3), X (N, 3), info): the pose of camera l = pair[1] relative to camera k = pair[0], which sits at the
     origin with identity pose; |t_l| = 1.  ``K`` (m, 3, 3) projects to the units of ``xy`` (raw image coordinates:
     ``engine_intrinsics(init_K)``, as for ``triangulate_points``).  F of the pair on the device, E = K_l^T F K_k, its four
@@ -148,17 +178,30 @@ def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2):
     smallest depth > 0, and is triangulated again with ``n_refine``.  ``X`` is NaN for points not shared, not triangulated or
     behind a camera.  ``info``: ``n_front`` (4,), ``status`` -- 0 ok, the ``fundamental_matrices`` status otherwise, 3 when no
     candidate puts more than half of the shared points in front of both cameras --, ``F``, ``n_shared``, ``two_view`` (the
-    quality of F) and the triangulation ``quality`` (N, 3)."""
+    quality of F) and the triangulation ``quality`` (N, 3).
+    With ``ransac_threshold`` (a Sampson distance in the units of xy) F is ``robust_fundamental_matrices``'s, with
+    ``n_hypotheses`` and ``seed``; only the pair's inliers are triangulated -- the other shared points stay NaN in X --, "more
+    than half" counts against the inliers, the status may also be 2 or 4 of that function, and ``info`` gains ``inlier`` (N,)
+    bool and ``n_inliers``."""
     K = np.asarray(K, np.float64)
     k, l = int(pair[0]), int(pair[1])
     n = len(pt_ptr) - 1
-    F, fi = fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)])
+    inlier = None
+    if ransac_threshold is None:
+        F, fi = fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)])
+    else:
+        F, fi = robust_fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)], ransac_threshold, n_hypotheses=n_hypotheses, seed=seed)
+        inlier = fi["inlier"][0]
     R, t, X = np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
     info = {"n_front": np.zeros(4, np.int64), "status": int(fi["status"][0]), "F": F[0], "n_shared": int(fi["n_shared"][0]),
             "two_view": fi["quality"][0], "quality": np.full((n, 3), np.nan)}
+    n_used = info["n_shared"]
+    if inlier is not None:
+        info["inlier"], info["n_inliers"] = inlier, int(fi["n_inliers"][0])
+        n_used = info["n_inliers"]
     if info["status"] != 0:
         return R, t, X, info
-    ptr, cam, z, (ik, il) = _pair_list(pt_ptr, cam_idx, xy, K.shape[0], k, l)
+    ptr, cam, z, ids, (ik, il) = _pair_list(pt_ptr, cam_idx, xy, K.shape[0], k, l, inlier)
     K2, R2, t2 = np.empty((2, 3, 3)), np.empty((2, 3, 3)), np.zeros((2, 3))
     K2[ik], K2[il], R2[ik] = K[k], K[l], np.eye(3)
     cands = pose_candidates(K[l].T @ F[0] @ K[k])
@@ -171,11 +214,11 @@ def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2):
     for c in range(4):
         info["n_front"][c] = tri(c, 0)[2].sum()
     best = int(np.argmax(info["n_front"]))
-    if not 2 * info["n_front"][best] > info["n_shared"]:
+    if not 2 * info["n_front"][best] > n_used:
         info["status"] = 3
         return R, t, X, info
     Xc, q, front = tri(best, n_refine)
-    X[front], info["quality"][front] = Xc[front], q[front]
+    X[ids[front]], info["quality"][ids[front]] = Xc[front], q[front]
     R[0], t[0] = np.eye(3), 0.0
     R[1], t[1] = cands[best]
     return R, t, X, info
@@ -194,7 +237,8 @@ def pose_for_intrinsics(P, K, c):
     return R, c - R @ (d * np.array([(x[0] - K[0, 2]) / K[0, 0], (x[1] - K[1, 2]) / K[1, 1], 1.0]))
 
 
-def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min_points: int = 12, max_rms=None):
+def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min_points: int = 12, max_rms=None, ransac_threshold=None,
+              n_hypotheses: int = 512, seed: int = 0):
     """(K, R, t, X, info): an initial estimate for ``BundleAdjuster.from_observations`` from feature tracks and rough
     intrinsics, by incremental reconstruction.  ``xy`` are raw image coordinates, ``init_K`` (m, 3, 3) the adjuster's
     [[f,0,u],[0,f,v],[0,0,f0]]; K comes back as ``init_K`` (no focal length is estimated).
@@ -204,7 +248,8 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     registered if its status is 0 and it has at least ``min_points`` -- its pose only, the one that belongs to ``init_K``
     (``pose_for_intrinsics`` at the centroid of the points it sees) --; ``triangulate_points`` over the
     registered cameras; a point is kept if its status is 0, its smallest depth > 0 and, with ``max_rms``, its RMS residual
-    (units of xy) is at most that.  No BA runs in between.
+    (units of xy) is at most that.  No BA runs in between.  ``ransac_threshold``, ``n_hypotheses`` and ``seed`` go to every
+    ``relative_pose`` (a robust first F; resection and triangulation stay as they are: ``max_rms`` is the filter there).
     The output frame: camera 0 at the origin with identity pose, |t_1 - t_0| = 1.  ``info``: ``axis`` -- the gauge axis name
     whose component of t_1 is larger in magnitude: pass it to ``BundleAdjuster`` --, ``camera_ok`` (m,), ``point_ok`` (N,),
     ``order`` (the registration order), ``start_pair``.  Cameras and points not reached are NaN (``restrict_observations``
@@ -222,7 +267,10 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
         tried = [(int(start_pair[0]), int(start_pair[1]))]
     best = None
     for pair in tried:
-        R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair)
+        if ransac_threshold is None:
+            R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair)
+        else:
+            R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed)
         if pi["status"] != 0:
             continue
         angle = float(np.nanmedian(pi["quality"][:, 2]))

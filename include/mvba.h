@@ -302,6 +302,41 @@ int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, con
                   int64_t n_obs, const int32_t *pairs, int32_t n_pairs, double *F, double *quality, int64_t *n_shared,
                   int32_t *status, double *timings_ms, int32_t device);
 
+/* mvba_two_view_robust: mvba_two_view with 8-point RANSAC in front of it.  The list, pairs, argument checks, camera cap and
+ * error messages are mvba_two_view's; further MVBA_ERR_BADARG (with the number in the message): threshold not finite or not
+ * > 0, n_hypotheses outside 1 .. 65536, n_refit outside 0 .. 16.  Per pair (k, l), the shared points in ascending point
+ * order numbered 0 .. n - 1 (compacted on the device into a dense array):
+ *   normalisation: centroids and Hartley scales over ALL shared points, as mvba_two_view defines them;
+ *   hypothesis h = 0 .. n_hypotheses - 1: the 8 distinct indices of mvba_ransac_sample(seed, k, l, h, n); M_h = sum a a^T over
+ *     their 8 normalised rows (mvba_two_view's row); F^_h = the eigenvector of its smallest eigenvalue (cyclic Jacobi on the
+ *     device); degenerate if lambda_2 <= 1e-12 lambda_max or anything is not finite; F_h = T_l^T F^_h T_k, no rank-2 step;
+ *   score: count_h = the number of shared points with squared Sampson distance (mvba_two_view's) <= threshold^2 under F_h, an
+ *     integer (ballots and integer atomics: exact in any order); -1 for a degenerate hypothesis; best = the largest count, the
+ *     lowest h on ties;
+ *   refit r = 1 .. n_refit: the full mvba_two_view fit (its own normalisation, fixed-order sums, the eigen-problem, the rank-2
+ *     step and the scaling on the host) on the current inlier set alone, I_0 being that of F_best; I_r = the points within the
+ *     threshold of that F.  A refit is kept if its status is 0 and |I_r| >= |I_r-1|; otherwise the loop stops with the
+ *     previous result.  If none is kept (n_refit = 0 too) F is F^_best made rank 2, denormalised and scaled by the same host step.
+ * F [n_pairs][9]: |F| = 1, largest-magnitude entry positive.  quality [n_pairs][2]: the RMS Sampson distance over the final
+ * inliers under the matrix that selected them (the last kept refit's F; F_best itself if none was kept), and lambda_1 /
+ * lambda_2 of the last kept refit (0 if none: a minimal sample's M has rank 8).  n_shared, n_inliers, best [n_pairs] (best =
+ * -1 where status = 1 or 2).  inlier [n_pairs][n_points] (n_pairs x n_points BYTES): 1 where the point is a final inlier of the pair.
+ * hyp_count [n_pairs][n_hypotheses]: the count table (all -1 where status = 1).
+ * status [n_pairs]: 0 ok; 1 fewer than 8 shared points; 2 every hypothesis degenerate (or the host step failed); 4 the best
+ * count is below 8.  Where status != 0, F and quality are NaN, n_inliers is 0 and the mask is 0.
+ * timings_ms [4]: check + upload; compaction, normalisation, hypotheses and scoring; refits; everything else (host clock, each
+ * phase ends in a blocking copy).  Every output but F may be NULL.  Pairs are taken in tiles of
+ * 128 MiB / (48 n_points + 160 n_hypotheses), at most 65535.  Two calls give bitwise-identical output. */
+int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy,
+                         int64_t n_obs, const int32_t *pairs, int32_t n_pairs, double threshold, int32_t n_hypotheses,
+                         uint64_t seed, int32_t n_refit, double *F, double *quality, int64_t *n_shared, int64_t *n_inliers,
+                         int32_t *best, uint8_t *inlier, int32_t *hyp_count, int32_t *status, double *timings_ms, int32_t device);
+/* Host only (no GPU needed): the 8 distinct indices below n that hypothesis h of pair (k, l) draws -- the function the kernel
+ * runs.  mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB;
+ * x ^ x >> 31.  s = mix(mix(mix(seed) ^ (k << 32 | l)) ^ h); repeat s = mix(s), j = ((s >> 32) * n) >> 32, keep j unless
+ * already drawn.  MVBA_ERR_BADARG: n outside 8 .. 2^31 - 1, a negative k, l or h. */
+int mvba_ransac_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx8);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
