@@ -4326,6 +4326,7 @@ int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2,
 
 }  // extern "C"
 
+#include "mvba_start.h"  // what the three headers below share: the Jacobi, the chunk tree, list checks and upload
 #include "mvba_init.h"  // initial estimates: mvba_triangulate, mvba_triangulate_state, mvba_resect
 #include "mvba_twoview.h"  // two-view start: mvba_covisibility, mvba_two_view
 #include "mvba_ransac.h"  // robust two-view start: mvba_two_view_robust, mvba_ransac_sample

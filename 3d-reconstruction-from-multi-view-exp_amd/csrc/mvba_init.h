@@ -1,7 +1,8 @@
 // Initial estimates for BA (mvba_triangulate, mvba_triangulate_state, mvba_resect) -- kernels and host code, gfx950.
 //
-// Included by mvba.hip after its C entry points: uses mvba_handle, DevBufs, fail and MVBA_HIP.  Nothing here runs on the
-// LM path, and nothing on the LM path calls into here.  
+// Included by mvba.hip after mvba_start.h: uses its sym_eig_jacobi, eig_extremes, chunk_sum, init_check_list,
+// init_check_cameras, upload_list, InitClock and EvGuard, and mvba.hip's mvba_handle, DevBufs, fail and MVBA_HIP.  Nothing
+// here runs on the LM path, and nothing on the LM path calls into here.  
 //
 // Triangulation: ONE THREAD PER POINT.  A point's observations are consecutive in the CSR list, so a thread walks them in
 // ascending order -- the order the sums are defined in, hence bitwise the same on every run, without atomics and without a
@@ -13,85 +14,12 @@
 //
 // Resection: the per-observation passes run on the device over a camera-major copy of the list (a stable counting sort on
 // the HOST, inside the pass that checks the indices and drops unusable points: the list crosses PCIe afterwards anyway), cut
-// into chunks of 256 observations of one camera.  One workgroup per chunk; a chunk's sums are taken by a fixed tree (a
+// into chunks of 256 observations of one camera.  One workgroup per chunk; a chunk's sums are taken by chunk_sum (a
 // shuffle tree inside a wave, waves in ascending order), a camera's chunks are summed in ascending order: two runs are
 // bitwise equal.  The m eigen-problems of order 12 are solved on the host by cyclic Jacobi (the same routine the
 // triangulation kernel instantiates at order 4): 40 doubles per camera come back (tens of microseconds of host time each: an estimate).
 
 namespace {
-
-constexpr double INIT_REL_PIVOT = 1e-12;  // the relative pivot rule of mvba_covariance
-constexpr int INIT_MAX_CAMERAS = 1704;    // (160 KiB - 256 B) / 96 B: the LDS camera table of k_project_obs
-
-// Eigen-decomposition of a symmetric N x N matrix by cyclic Jacobi (Rutishauser's rotations): A -> diagonal, V -> the
-// eigenvectors in its columns.  Every index is a compile-time constant once the loops are unrolled: on the device the
-// order-4 instance lives in registers (the form of mvsvd.hip's per-point solver).  A rotation is skipped once a_pq no
-// longer changes either diagonal entry in floating point.
-template <int N>
-__host__ __device__ __forceinline__ void sym_eig_jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    bool any = false;
-#pragma unroll
-    for (int p = 0; p < N - 1; ++p)
-#pragma unroll
-      for (int q = p + 1; q < N; ++q) {
-        const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
-        const double g = fabs(apq);
-        if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
-          A[p][q] = A[q][p] = 0.0;
-          continue;
-        }
-        any = true;
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-        A[p][p] = app - t * apq;
-        A[q][q] = aqq + t * apq;
-        A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-        for (int r = 0; r < N; ++r) {
-          if (r != p && r != q) {
-            const double arp = A[r][p], arq = A[r][q];
-            A[r][p] = A[p][r] = arp - s * (arq + tau * arp);
-            A[r][q] = A[q][r] = arq + s * (arp - tau * arq);
-          }
-          const double vrp = V[r][p], vrq = V[r][q];
-          V[r][p] = vrp - s * (vrq + tau * vrp);
-          V[r][q] = vrq + s * (vrp - tau * vrq);
-        }
-      }
-    if (!any) break;
-  }
-}
-
-// smallest, second-smallest and largest eigenvalue after sym_eig_jacobi, and the column of the smallest
-template <int N>
-__host__ __device__ __forceinline__ void eig_extremes(const double (&A)[N][N], const double (&V)[N][N], double &l1, double &l2,
-                                                      double &lmax, double (&v)[N]) {
-  int best = 0;
-  l1 = A[0][0];
-  lmax = A[0][0];
-#pragma unroll
-  for (int i = 1; i < N; ++i) {
-    if (A[i][i] < l1) { l1 = A[i][i]; best = i; }
-    lmax = fmax(lmax, A[i][i]);
-  }
-  l2 = HUGE_VAL;
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-    if (i != best) l2 = fmin(l2, A[i][i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double x = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) x = j == best ? V[i][j] : x;  // (selects: a run-time column index would put V into scratch)
-    v[i] = x;
-  }
-}
 
 // P_k = K_k [R_k^T | -R_k^T t_k] in the order of operations of k_project_obs
 __host__ __device__ __forceinline__ void init_camera_matrix(const double *Kk, const double *Rk, const double *tk, double *P) {
@@ -288,7 +216,6 @@ __global__ __launch_bounds__(256) void k_init_cams(int m, const double *__restri
 }
 
 // ---- resection -----------------------------------------------------------------------------------------------------
-constexpr int RS_CHUNK = 256;  // observations per chunk = threads per workgroup
 constexpr int RS_NORM = 8;     // per camera: centroid of its points (3), their scale, centroid of its image points (2), their scale, count
 
 // values per observation of the four passes: 0 count and first moments, 1 squared distances, 2 the 40 sums the normal
@@ -298,12 +225,12 @@ __host__ __device__ constexpr int rs_values(int mode) { return mode == 0 ? 6 : (
 // One workgroup per chunk (ch_cam, ch_start, ch_cnt): the chunk's sums into part[chunk][NV].  aux: mode 1, 2 the RS_NORM
 // table, mode 3 the camera matrices [m][12].
 template <int MODE>
-__global__ __launch_bounds__(RS_CHUNK) void k_resect_chunk(const int *__restrict__ ch_cam, const long long *__restrict__ ch_start,
+__global__ __launch_bounds__(START_CHUNK) void k_resect_chunk(const int *__restrict__ ch_cam, const long long *__restrict__ ch_start,
                                                            const int *__restrict__ ch_cnt, const int *__restrict__ cm_pt,
                                                            const double2 *__restrict__ cm_xy, const double *__restrict__ X,
                                                            const double *__restrict__ aux, double *__restrict__ part) {
   constexpr int NV = rs_values(MODE);
-  __shared__ double s_w[RS_CHUNK / 64][NV];
+  __shared__ double s_w[START_CHUNK / 64][NV];
   const int c = blockIdx.x, k = ch_cam[c], i = threadIdx.x;
   double v[NV];
 #pragma unroll
@@ -340,21 +267,7 @@ __global__ __launch_bounds__(RS_CHUNK) void k_resect_chunk(const int *__restrict
       v[0] = r0 * r0 + r1 * r1;
     }
   }
-  // the fixed tree: lanes l and l + off inside a wave, off = 32 .. 1, then the waves in ascending order
-#pragma unroll
-  for (int e = 0; e < NV; ++e) {
-    double x = v[e];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    if ((i & 63) == 0) s_w[i >> 6][e] = x;
-  }
-  __syncthreads();
-  if (i < NV) {
-    double x = s_w[0][i];
-#pragma unroll
-    for (int w = 1; w < RS_CHUNK / 64; ++w) x += s_w[w][i];
-    part[(size_t)c * NV + i] = x;
-  }
+  chunk_sum<NV>(v, s_w, part + (size_t)c * NV);
 }
 
 // out[k][e] = the sum of camera k's chunk partials in ascending chunk order
@@ -386,26 +299,6 @@ __global__ __launch_bounds__(256) void k_resect_norm(int m, int stage, const dou
   }
 }
 
-struct InitClock {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  double lap() {
-    const auto t1 = std::chrono::steady_clock::now();
-    const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-    return ms;
-  }
-};
-
-// events of one call: whatever was created is destroyed when the owner goes
-struct EvGuard {
-  hipEvent_t *e;
-  int n;
-  ~EvGuard() {
-    for (int i = 0; i < n; ++i)
-      if (e[i]) hipEventDestroy(e[i]);
-  }
-};
-
 // the launch of k_triangulate on `stream`, timed by events when ms != nullptr (the stream is idle afterwards)
 int launch_triangulate(hipStream_t stream, long long npts, int m, const double *K, const double *R, const double *t, const long long *pt_ptr,
                        const int *cam, const double2 *xy, int n_refine, double *X, double *quality, int *status, int keep_bad, double *ms) {
@@ -430,35 +323,6 @@ int launch_triangulate(hipStream_t stream, long long npts, int m, const double *
     *ms = f;
   }
   if (e != hipSuccess) return fail(MVBA_ERR_HIP, std::string("k_triangulate: ") + hipGetErrorString(e));
-  return MVBA_OK;
-}
-
-// the checks mvba_project makes of an observation list, with the offending number in the message
-int init_check_list(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, int64_t n_obs) {
-  if (n_points < 0 || n_obs < 0) return fail(MVBA_ERR_BADARG, "n_points = " + std::to_string(n_points) + ", n_obs = " + std::to_string(n_obs) + ": negative size");
-  if (n_images < 1) return fail(MVBA_ERR_BADARG, "n_images = " + std::to_string(n_images) + " must be at least 1");
-  if (n_points >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n_points = " + std::to_string(n_points) + " must be < 2^31");
-  if (!pt_ptr) {
-    if (n_obs != n_points * (int64_t)n_images)
-      return fail(MVBA_ERR_BADARG, "dense grid needs n_obs = n_points * n_images = " + std::to_string(n_points * (int64_t)n_images) + ", got " + std::to_string(n_obs));
-    return MVBA_OK;
-  }
-  if (!cam_idx) return fail(MVBA_ERR_BADARG, "null argument: cam_idx (with a pt_ptr)");
-  if (pt_ptr[0] != 0) return fail(MVBA_ERR_BADARG, "pt_ptr[0] = " + std::to_string(pt_ptr[0]) + " must be 0");
-  for (int64_t a = 0; a < n_points; ++a)
-    if (pt_ptr[a + 1] < pt_ptr[a] || pt_ptr[a + 1] > n_obs)
-      return fail(MVBA_ERR_BADARG, "pt_ptr[" + std::to_string(a + 1) + "] = " + std::to_string(pt_ptr[a + 1]) + " is not ascending within n_obs = " + std::to_string(n_obs));
-  if (pt_ptr[n_points] != n_obs)
-    return fail(MVBA_ERR_BADARG, "pt_ptr does not span n_obs: pt_ptr[n_points] = " + std::to_string(pt_ptr[n_points]) + ", n_obs = " + std::to_string(n_obs));
-  for (int64_t o = 0; o < n_obs; ++o)
-    if (cam_idx[o] < 0 || cam_idx[o] >= n_images)
-      return fail(MVBA_ERR_BADARG, "cam_idx out of range: cam_idx[" + std::to_string(o) + "] = " + std::to_string(cam_idx[o]) + ", n_images = " + std::to_string(n_images));
-  return MVBA_OK;
-}
-
-int init_check_cameras(int32_t n_images) {
-  if (n_images > INIT_MAX_CAMERAS)
-    return fail(MVBA_ERR_BADARG, "too many cameras for the LDS camera table: n_images = " + std::to_string(n_images) + " (max " + std::to_string(INIT_MAX_CAMERAS) + ")");
   return MVBA_OK;
 }
 
@@ -537,20 +401,14 @@ int mvba_triangulate(const double *K, const double *R, const double *t, int32_t 
   long long *dptr = nullptr;
   int *dcam = nullptr, *dst = nullptr;
   if ((rc = tmp.alloc(&dK, 9 * (size_t)n_images)) || (rc = tmp.alloc(&dR, 9 * (size_t)n_images)) || (rc = tmp.alloc(&dt, 3 * (size_t)n_images)) ||
-      (rc = tmp.alloc(&dX, 3 * (size_t)n_points)) || (rc = tmp.alloc(&dxy, (size_t)n_obs)))
+      (rc = tmp.alloc(&dX, 3 * (size_t)n_points)))
     return rc;
   if (quality && (rc = tmp.alloc(&dq, 3 * (size_t)n_points))) return rc;
   if (status && (rc = tmp.alloc(&dst, (size_t)n_points))) return rc;
   MVBA_HIP(hipMemcpy(dK, K, sizeof(double) * 9 * n_images, hipMemcpyHostToDevice));
   MVBA_HIP(hipMemcpy(dR, R, sizeof(double) * 9 * n_images, hipMemcpyHostToDevice));
   MVBA_HIP(hipMemcpy(dt, t, sizeof(double) * 3 * n_images, hipMemcpyHostToDevice));
-  if (n_obs) MVBA_HIP(hipMemcpy(dxy, xy, sizeof(double2) * n_obs, hipMemcpyHostToDevice));
-  if (pt_ptr) {
-    static_assert(sizeof(long long) == sizeof(int64_t), "pt_ptr goes to the device as it is");
-    if ((rc = tmp.alloc(&dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(&dcam, (size_t)n_obs))) return rc;
-    MVBA_HIP(hipMemcpy(dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
-    if (n_obs) MVBA_HIP(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
-  }
+  if ((rc = upload_list(tmp, n_points, n_obs, pt_ptr, cam_idx, xy, &dptr, &dcam, &dxy))) return rc;
   if (timings_ms) timings_ms[0] = clk.lap();
   double ms = 0.0;
   if ((rc = launch_triangulate(nullptr, n_points, n_images, dK, dR, dt, dptr, dcam, dxy, n_refine, dX, dq, dst, 0, timings_ms ? &ms : nullptr))) return rc;
@@ -632,10 +490,10 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
   std::vector<int> cam_ch_ptr((size_t)m + 1, 0), ch_cam, ch_cnt;
   std::vector<long long> ch_start;
   for (int k = 0; k < m; ++k) {
-    for (long long s = cam_ptr[k]; s < cam_ptr[k + 1]; s += RS_CHUNK) {
+    for (long long s = cam_ptr[k]; s < cam_ptr[k + 1]; s += START_CHUNK) {
       ch_cam.push_back(k);
       ch_start.push_back(s);
-      ch_cnt.push_back((int)std::min<long long>(RS_CHUNK, cam_ptr[k + 1] - s));
+      ch_cnt.push_back((int)std::min<long long>(START_CHUNK, cam_ptr[k + 1] - s));
     }
     cam_ch_ptr[k + 1] = (int)ch_cam.size();
   }
@@ -669,13 +527,13 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
     const dim3 gm((m + 255) / 256), b256(256);
     auto combine = [&](int nv) { hipLaunchKernelGGL(k_resect_combine, dim3((m * nv + 255) / 256), b256, 0, 0, m, nv, dcam_ch, dpart, dS); };
     hipEventRecord(ev[0], 0);
-    hipLaunchKernelGGL(k_resect_chunk<0>, dim3(n_ch), dim3(RS_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, (const double *)nullptr, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<0>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, (const double *)nullptr, dpart);
     combine(6);
     hipLaunchKernelGGL(k_resect_norm, gm, b256, 0, 0, m, 0, dS, dnorm);
-    hipLaunchKernelGGL(k_resect_chunk<1>, dim3(n_ch), dim3(RS_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dnorm, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<1>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dnorm, dpart);
     combine(2);
     hipLaunchKernelGGL(k_resect_norm, gm, b256, 0, 0, m, 1, dS, dnorm);
-    hipLaunchKernelGGL(k_resect_chunk<2>, dim3(n_ch), dim3(RS_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dnorm, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<2>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dnorm, dpart);
     combine(40);
     hipEventRecord(ev[1], 0);
     MVBA_HIP(hipGetLastError());
@@ -689,7 +547,7 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
     }
     MVBA_HIP(hipMemcpy(dP, Pm.data(), sizeof(double) * 12 * m, hipMemcpyHostToDevice));
     hipEventRecord(ev[2], 0);
-    hipLaunchKernelGGL(k_resect_chunk<3>, dim3(n_ch), dim3(RS_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dP, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<3>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dP, dpart);
     combine(1);
     hipEventRecord(ev[3], 0);
     MVBA_HIP(hipGetLastError());

@@ -1,9 +1,9 @@
 // Robust two-view geometry (mvba_two_view_robust, mvba_ransac_sample): 8-point RANSAC for the fundamental matrix -- kernels
 // and host code, gfx950.
 //
-// Included by mvba.hip after mvba_twoview.h: uses its tv_find, k_twoview_combine, k_twoview_norm, twoview_solve_pair and
-// constants, mvba_init.h's checks, InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs
-// on the LM path.  
+// Included by mvba.hip after mvba_twoview.h: uses its rs_shared, tv_pass, tv_row, rs_sampson, tv_denormalise, k_twoview_combine,
+// k_twoview_norm, twoview_solve_pair, tv_pair_tile, tv_combine and constants, mvba_start.h's chunk_sum, checks, upload_list,
+// InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
 //
 // Per pair of a tile (blockIdx.y or .z: the pair inside the tile): the shared observations are compacted into a dense array
 // of (x_k, y_k, x_l, y_l) in ascending point order (per-chunk counts, an exclusive scan over the pair's chunks, ballot and
@@ -12,7 +12,7 @@
 // (element e of thread t at [e x 64 + t]: run-time row and column indices address LDS, not scratch, and a wave's 64 accesses
 // fall into 64 consecutive doubles).  The scoring kernel holds 64 hypothesis matrices in LDS, one compacted point per thread;
 // a hypothesis's count is ballot + popcount per wave, then integer atomics (LDS, then device memory): exact in any order.
-// Refits sum the moments of the compacted array under a byte mask by the fixed tree of k_twoview_chunk; the order-9
+// Refits sum the moments of the compacted array under a byte mask by tv_pass and chunk_sum, as k_twoview_chunk does; the order-9
 // eigen-problem, the rank-2 step and the denormalisation are twoview_solve_pair's, on the host.  No floating-point atomics.
 
 namespace {
@@ -53,43 +53,21 @@ __host__ __device__ __forceinline__ void rs_sample(unsigned long long seed, int 
   }
 }
 
-// the squared Sampson distance of k_twoview_chunk<3>
-__device__ __forceinline__ double rs_sampson(const double *F, double xk, double yk, double xl, double yl) {
-  const double f0 = F[0] * xk + F[1] * yk + F[2], f1 = F[3] * xk + F[4] * yk + F[5], f2 = F[6] * xk + F[7] * yk + F[8];
-  const double g0 = F[0] * xl + F[3] * yl + F[6], g1 = F[1] * xl + F[4] * yl + F[7];
-  const double r = xl * f0 + yl * f1 + f2;
-  return r * r / (f0 * f0 + f1 * f1 + g0 * g0 + g1 * g1);
-}
-
-// does point a see both cameras of the pair?  (its two observations in ok, ol)
-__device__ __forceinline__ bool rs_shared(long long a, long long npts, int m, const long long *__restrict__ pt_ptr,
-                                          const int *__restrict__ cam_idx, int k, int l, long long &ok, long long &ol) {
-  ok = ol = -1;
-  if (a < npts) {
-    const long long o0 = pt_ptr ? pt_ptr[a] : a * m;
-    const int deg = pt_ptr ? (int)(pt_ptr[a + 1] - pt_ptr[a]) : m;
-    const int *cam = pt_ptr ? cam_idx : nullptr;
-    ok = tv_find(cam, o0, deg, k);
-    if (ok >= 0) ol = tv_find(cam, o0, deg, l);
-  }
-  return ok >= 0 && ol >= 0;
-}
-
 // cnt[pair][chunk] = the number of shared points among the chunk's 256
-__global__ __launch_bounds__(TV_CHUNK) void k_ransac_count(long long npts, int m, const long long *__restrict__ pt_ptr,
+__global__ __launch_bounds__(START_CHUNK) void k_ransac_count(long long npts, int m, const long long *__restrict__ pt_ptr,
                                                            const int *__restrict__ cam_idx, const int *__restrict__ pairs,
                                                            int *__restrict__ cnt) {
-  __shared__ int s_w[TV_CHUNK / 64];
+  __shared__ int s_w[START_CHUNK / 64];
   const int p = blockIdx.y, i = threadIdx.x;
   long long ok, ol;
-  const bool sh = rs_shared((long long)blockIdx.x * TV_CHUNK + i, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
+  const bool sh = rs_shared((long long)blockIdx.x * START_CHUNK + i, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
   const unsigned long long b = __ballot(sh);
   if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
   __syncthreads();
   if (i == 0) {
     int x = 0;
 #pragma unroll
-    for (int w = 0; w < TV_CHUNK / 64; ++w) x += s_w[w];
+    for (int w = 0; w < START_CHUNK / 64; ++w) x += s_w[w];
     cnt[(size_t)p * gridDim.x + blockIdx.x] = x;
   }
 }
@@ -124,13 +102,13 @@ __global__ __launch_bounds__(256) void k_ransac_scan(int n_ch, int *__restrict__
 }
 
 // comp[pair][j] = (x_k, y_k, x_l, y_l) and id[pair][j] = the point of the pair's j-th shared point, ascending
-__global__ __launch_bounds__(TV_CHUNK) void k_ransac_compact(long long npts, int m, const long long *__restrict__ pt_ptr,
+__global__ __launch_bounds__(START_CHUNK) void k_ransac_compact(long long npts, int m, const long long *__restrict__ pt_ptr,
                                                              const int *__restrict__ cam_idx, const double2 *__restrict__ xy,
                                                              const int *__restrict__ pairs, const int *__restrict__ off,
                                                              double4 *__restrict__ comp, int *__restrict__ id) {
-  __shared__ int s_w[TV_CHUNK / 64];
+  __shared__ int s_w[START_CHUNK / 64];
   const int p = blockIdx.y, i = threadIdx.x;
-  const long long a = (long long)blockIdx.x * TV_CHUNK + i;
+  const long long a = (long long)blockIdx.x * START_CHUNK + i;
   long long ok, ol;
   const bool sh = rs_shared(a, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
   const unsigned long long b = __ballot(sh);
@@ -144,37 +122,17 @@ __global__ __launch_bounds__(TV_CHUNK) void k_ransac_compact(long long npts, int
   id[(size_t)p * npts + j] = (int)a;
 }
 
-// the fixed tree of k_twoview_chunk: lanes l and l + off inside a wave, off = 32 .. 1, then the waves in ascending order
-template <int NV>
-__device__ __forceinline__ void rs_chunk_sum(const double (&v)[NV], double (&s_w)[TV_CHUNK / 64][NV], double *__restrict__ out) {
-  const int i = threadIdx.x;
-#pragma unroll
-  for (int e = 0; e < NV; ++e) {
-    double x = v[e];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    if ((i & 63) == 0) s_w[i >> 6][e] = x;
-  }
-  __syncthreads();
-  if (i < NV) {
-    double x = s_w[0][i];
-#pragma unroll
-    for (int w = 1; w < TV_CHUNK / 64; ++w) x += s_w[w][i];
-    out[i] = x;
-  }
-}
-
-// The passes 0, 1, 2 of k_twoview_chunk over the compacted array: part[pair][chunk][NV] over the points j < ntot[pair] whose
+// The passes 0, 1, 2 of k_twoview_chunk (tv_pass, chunk_sum) over the compacted array: part[pair][chunk][NV] over the points j < ntot[pair] whose
 // byte in the pair's current mask is set (state == nullptr: every point).  A pair that is not RS_ACTIVE sums nothing.
 template <int MODE>
-__global__ __launch_bounds__(TV_CHUNK) void k_ransac_fit(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
+__global__ __launch_bounds__(START_CHUNK) void k_ransac_fit(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
                                                          const double4 *__restrict__ comp, const unsigned char *__restrict__ inl0,
                                                          const unsigned char *__restrict__ inl1, const double *__restrict__ aux,
                                                          double *__restrict__ part) {
   constexpr int NV = tv_values(MODE);
-  __shared__ double s_w[TV_CHUNK / 64][NV];
+  __shared__ double s_w[START_CHUNK / 64][NV];
   const int p = blockIdx.y, i = threadIdx.x;
-  const long long j = (long long)blockIdx.x * TV_CHUNK + i;
+  const long long j = (long long)blockIdx.x * START_CHUNK + i;
   double v[NV];
 #pragma unroll
   for (int e = 0; e < NV; ++e) v[e] = 0.0;
@@ -186,26 +144,9 @@ __global__ __launch_bounds__(TV_CHUNK) void k_ransac_fit(long long stride, const
   }
   if (use) {
     const double4 z = comp[(size_t)p * stride + j];
-    if constexpr (MODE == 0) {
-      v[0] = 1.0; v[1] = z.x; v[2] = z.y; v[3] = z.z; v[4] = z.w;
-    } else if constexpr (MODE == 1) {
-      const double *nm = aux + TV_NORM * (size_t)p;
-      const double d0 = z.x - nm[0], d1 = z.y - nm[1], e0 = z.z - nm[3], e1 = z.w - nm[4];
-      v[0] = d0 * d0 + d1 * d1;
-      v[1] = e0 * e0 + e1 * e1;
-    } else {
-      const double *nm = aux + TV_NORM * (size_t)p;
-      const double xk = nm[2] * (z.x - nm[0]), yk = nm[2] * (z.y - nm[1]);
-      const double xl = nm[5] * (z.z - nm[3]), yl = nm[5] * (z.w - nm[4]);
-      const double r[9] = {xl * xk, xl * yk, xl, yl * xk, yl * yk, yl, xk, yk, 1.0};
-      int e = 0;
-#pragma unroll
-      for (int b = 0; b < 9; ++b)
-#pragma unroll
-        for (int c = b; c < 9; ++c, ++e) v[e] = r[b] * r[c];
-    }
+    tv_pass<MODE>(z.x, z.y, z.z, z.w, aux + tv_aux(MODE) * (size_t)p, v);
   }
-  rs_chunk_sum<NV>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * NV);
+  chunk_sum<NV>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * NV);
 }
 
 // One thread per hypothesis: sample, M = sum of a a^T over the 8 normalised rows, cyclic Jacobi in LDS, F^ = the eigenvector
@@ -228,7 +169,6 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, i
     auto A = [&](int r, int c) -> double & { return sA[(r * 9 + c) * RS_HYP_BLOCK]; };
     auto V = [&](int r, int c) -> double & { return sV[(r * 9 + c) * RS_HYP_BLOCK]; };
     const double *nm = norm + TV_NORM * (size_t)p;
-    const double ckx = nm[0], cky = nm[1], sk = nm[2], clx = nm[3], cly = nm[4], sl = nm[5];
     long long idx[8];
     rs_sample(seed, pairs[2 * p], pairs[2 * p + 1], h, n, idx);
     double M[45];
@@ -237,8 +177,8 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, i
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const double4 z = comp[(size_t)p * stride + idx[c]];
-      const double xk = sk * (z.x - ckx), yk = sk * (z.y - cky), xl = sl * (z.z - clx), yl = sl * (z.w - cly);
-      const double r[9] = {xl * xk, xl * yk, xl, yl * xk, yl * yk, yl, xk, yk, 1.0};
+      double r[9];
+      tv_row(nm, z.x, z.y, z.z, z.w, r);
       int e = 0;
 #pragma unroll
       for (int b = 0; b < 9; ++b)
@@ -301,20 +241,7 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, i
       good = l2 > INIT_REL_PIVOT * lmax;
 #pragma unroll
       for (int e = 0; e < 9; ++e) fh[e] = V(e, best);
-      // F = T_l^T F^ T_k with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]] (twoview_solve_pair, without its rank-2 step)
-      double Q[3][3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        Q[r][0] = sk * fh[3 * r];
-        Q[r][1] = sk * fh[3 * r + 1];
-        Q[r][2] = fh[3 * r + 2] - sk * (ckx * fh[3 * r] + cky * fh[3 * r + 1]);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        F[c] = sl * Q[0][c];
-        F[3 + c] = sl * Q[1][c];
-        F[6 + c] = Q[2][c] - sl * (clx * Q[0][c] + cly * Q[1][c]);
-      }
+      tv_denormalise(nm, fh, F);  // (no rank-2 step: a hypothesis is scored as the sample gives it)
 #pragma unroll
       for (int e = 0; e < 9; ++e) good = good && isfinite(F[e]);
     }
@@ -331,17 +258,17 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, i
 // matrices in LDS (every lane reads the same address: a broadcast); a hypothesis's inliers of a wave are one ballot and one
 // popcount, kept by the lane of the hypothesis's number; then integer atomics.  A degenerate hypothesis is NaN: no point
 // passes, its count stays -1.
-__global__ __launch_bounds__(TV_CHUNK) void k_ransac_score(long long stride, int H, const int *__restrict__ ntot,
+__global__ __launch_bounds__(START_CHUNK) void k_ransac_score(long long stride, int H, const int *__restrict__ ntot,
                                                            const double4 *__restrict__ comp, const double *__restrict__ hypF,
                                                            double thr2, int *__restrict__ hyp_count) {
   __shared__ double s_F[RS_HYP_BLOCK * 9];
   __shared__ int s_cnt[RS_HYP_BLOCK];
   const int p = blockIdx.z, h0 = blockIdx.y * RS_HYP_BLOCK, i = threadIdx.x, lane = i & 63;
   const int n = ntot[p];
-  const long long j = (long long)blockIdx.x * TV_CHUNK + i;
-  if (n < TV_MIN_SHARED || (long long)blockIdx.x * TV_CHUNK >= n) return;  // (the whole workgroup leaves)
+  const long long j = (long long)blockIdx.x * START_CHUNK + i;
+  if (n < TV_MIN_SHARED || (long long)blockIdx.x * START_CHUNK >= n) return;  // (the whole workgroup leaves)
   const int nh = min(RS_HYP_BLOCK, H - h0);
-  for (int e = i; e < nh * 9; e += TV_CHUNK) s_F[e] = hypF[((size_t)p * H + h0) * 9 + e];
+  for (int e = i; e < nh * 9; e += START_CHUNK) s_F[e] = hypF[((size_t)p * H + h0) * 9 + e];
   if (i < RS_HYP_BLOCK) s_cnt[i] = 0;
   __syncthreads();
   const bool live = j < n;
@@ -368,14 +295,14 @@ __global__ __launch_bounds__(256) void k_ransac_gather(int n_pairs, int H, const
 }
 
 // The inlier set of F[pair] into the pair's OTHER mask buffer, and part[pair][chunk][2] = (count, sum of d^2 over it) by the
-// fixed tree (the count is exact in a double).  A pair that is not RS_ACTIVE writes nothing and sums nothing.
-__global__ __launch_bounds__(TV_CHUNK) void k_ransac_mask(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
+// tree of chunk_sum (the count is exact in a double).  A pair that is not RS_ACTIVE writes nothing and sums nothing.
+__global__ __launch_bounds__(START_CHUNK) void k_ransac_mask(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
                                                           const double4 *__restrict__ comp, const double *__restrict__ F, double thr2,
                                                           unsigned char *__restrict__ inl0, unsigned char *__restrict__ inl1,
                                                           double *__restrict__ part) {
-  __shared__ double s_w[TV_CHUNK / 64][2];
+  __shared__ double s_w[START_CHUNK / 64][2];
   const int p = blockIdx.y, i = threadIdx.x, st = state[p];
-  const long long j = (long long)blockIdx.x * TV_CHUNK + i;
+  const long long j = (long long)blockIdx.x * START_CHUNK + i;
   double v[2] = {0.0, 0.0};
   if ((st & RS_ACTIVE) && j < ntot[p]) {
     const double4 z = comp[(size_t)p * stride + j];
@@ -384,15 +311,15 @@ __global__ __launch_bounds__(TV_CHUNK) void k_ransac_mask(long long stride, cons
     ((st & RS_CUR) ? inl0 : inl1)[(size_t)p * stride + j] = in ? 1 : 0;
     if (in) { v[0] = 1.0; v[1] = d2; }
   }
-  rs_chunk_sum<2>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * 2);
+  chunk_sum<2>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * 2);
 }
 
 // out[pair][point] = 1 for the points of the pair's current mask (pairs of status 0; out is zero beforehand)
-__global__ __launch_bounds__(TV_CHUNK) void k_ransac_scatter(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
+__global__ __launch_bounds__(START_CHUNK) void k_ransac_scatter(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
                                                              const int *__restrict__ id, const unsigned char *__restrict__ inl0,
                                                              const unsigned char *__restrict__ inl1, unsigned char *__restrict__ out) {
   const int p = blockIdx.y, st = state[p];
-  const long long j = (long long)blockIdx.x * TV_CHUNK + threadIdx.x;
+  const long long j = (long long)blockIdx.x * START_CHUNK + threadIdx.x;
   if (!(st & RS_OK) || j >= ntot[p]) return;
   if (((st & RS_CUR) ? inl1 : inl0)[(size_t)p * stride + j]) out[(size_t)p * stride + id[(size_t)p * stride + j]] = 1;
 }
@@ -439,19 +366,8 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
   int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
   if (rc) return rc;
   if ((rc = init_check_cameras(n_images))) return rc;
-  for (int32_t p = 0; p < n_pairs; ++p) {
-    const int32_t k = pairs[2 * p], l = pairs[2 * p + 1];
-    if (k < 0 || k >= n_images || l < 0 || l >= n_images)
-      return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) +
-                                       "): camera index out of range, n_images = " + std::to_string(n_images));
-    if (k == l) return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) + "): the two cameras must differ");
-  }
-  if (pt_ptr)  // the kernels search a point's camera run: it must ascend
-    for (int64_t a = 0; a < n_points; ++a)
-      for (int64_t o = pt_ptr[a] + 1; o < pt_ptr[a + 1]; ++o)
-        if (cam_idx[o] <= cam_idx[o - 1])
-          return fail(MVBA_ERR_BADARG, "cam_idx is not ascending within point " + std::to_string(a) + ": cam_idx[" + std::to_string(o) + "] = " +
-                                           std::to_string(cam_idx[o]) + " after " + std::to_string(cam_idx[o - 1]));
+  if ((rc = check_pairs(pairs, n_pairs, n_images))) return rc;
+  if ((rc = check_ascending(n_points, pt_ptr, cam_idx))) return rc;
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
   const int np = n_pairs, H = n_hypotheses;
   const double thr2 = threshold * threshold;
@@ -470,10 +386,9 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
 
   if (device >= 0) MVBA_HIP(hipSetDevice(device));
   InitClock clk;
-  const long long n_ch = (n_points + TV_CHUNK - 1) / TV_CHUNK;
+  const long long n_ch = (n_points + START_CHUNK - 1) / START_CHUNK;
   const long long stride = n_points;
-  const int tile = (int)std::max<long long>(
-      1, std::min<long long>(std::min<long long>(np, 65535), (long long)(TV_PART_BYTES / (RS_POINT_BYTES * (size_t)n_points + RS_HYP_BYTES * (size_t)H))));
+  const int tile = tv_pair_tile(np, RS_POINT_BYTES * (size_t)n_points + RS_HYP_BYTES * (size_t)H);
   DevBufs tmp;
   double2 *dxy = nullptr;
   long long *dptr = nullptr;
@@ -482,7 +397,7 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
   unsigned char *dinl0 = nullptr, *dinl1 = nullptr, *dout = nullptr;
   double *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dnorm2 = nullptr, *dF = nullptr, *dfb = nullptr, *dhypf = nullptr, *dhypF = nullptr;
   const size_t ts = (size_t)tile * (size_t)stride;
-  if ((rc = tmp.alloc(&dxy, (size_t)n_obs)) || (rc = tmp.alloc(&dpairs, 2 * (size_t)np)) || (rc = tmp.alloc(&doff, (size_t)tile * n_ch)) ||
+  if ((rc = upload_list(tmp, n_points, n_obs, pt_ptr, cam_idx, xy, &dptr, &dcam, &dxy)) || (rc = tmp.alloc(&dpairs, 2 * (size_t)np)) || (rc = tmp.alloc(&doff, (size_t)tile * n_ch)) ||
       (rc = tmp.alloc(&dntot, (size_t)tile)) || (rc = tmp.alloc(&did, ts)) || (rc = tmp.alloc(&dstate, (size_t)tile)) ||
       (rc = tmp.alloc(&dbest, (size_t)tile)) || (rc = tmp.alloc(&dhc, (size_t)tile * H)) || (rc = tmp.alloc(&dcomp, ts)) ||
       (rc = tmp.alloc(&dinl0, ts)) || (rc = tmp.alloc(&dinl1, ts)) || (rc = tmp.alloc(&dpart, 45 * (size_t)n_ch * tile)) ||
@@ -491,18 +406,12 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
       (rc = tmp.alloc(&dhypF, 9 * (size_t)tile * H)))
     return rc;
   if (inlier && (rc = tmp.alloc(&dout, ts))) return rc;
-  if (n_obs) MVBA_HIP(hipMemcpy(dxy, xy, sizeof(double2) * n_obs, hipMemcpyHostToDevice));
   MVBA_HIP(hipMemcpy(dpairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice));
-  if (pt_ptr) {
-    if ((rc = tmp.alloc(&dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(&dcam, (size_t)n_obs))) return rc;
-    MVBA_HIP(hipMemcpy(dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
-    if (n_obs) MVBA_HIP(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
-  }
   const int hyp_lds = (int)(sizeof(double) * 2 * 81 * RS_HYP_BLOCK);
   MVBA_HIP(hipFuncSetAttribute((const void *)k_ransac_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, hyp_lds));
   double t_up = clk.lap(), t_score = 0.0, t_refit = 0.0, t_rest = 0.0;
 
-  const dim3 b256(256), bch(TV_CHUNK);
+  const dim3 b256(256), bch(START_CHUNK);
   std::vector<int> ntot((size_t)tile), hc((size_t)tile * H), bst((size_t)tile), state((size_t)tile), st((size_t)tile);
   std::vector<long long> nin((size_t)tile);
   std::vector<double> S((size_t)tile * 45), norm(TV_NORM * (size_t)tile), fb(9 * (size_t)tile), Fc(9 * (size_t)tile), Fn(9 * (size_t)tile),
@@ -511,9 +420,7 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
     const int cnt = std::min(tile, np - p0);
     const dim3 grid((unsigned)n_ch, (unsigned)cnt), gp((cnt + 255) / 256);
     const int *tp = dpairs + 2 * (size_t)p0;
-    auto combine = [&](int nv, double *out) {
-      hipLaunchKernelGGL(k_twoview_combine, dim3((unsigned)(((long long)cnt * nv + 3) / 4)), b256, 0, 0, cnt, nv, (int)n_ch, dpart, out, nv);
-    };
+    auto combine = [&](int nv, double *out) { tv_combine(cnt, nv, n_ch, dpart, out, nv); };
     // the normalised 8-point sums of the pairs' current masks (st_dev == nullptr: of all shared points, passes 0 and 1 only)
     auto fit = [&](const int *st_dev, double *nm_dev, bool moments) {
       hipLaunchKernelGGL(k_ransac_fit<0>, grid, bch, 0, 0, stride, dntot, st_dev, dcomp, dinl0, dinl1, (const double *)nullptr, dpart);

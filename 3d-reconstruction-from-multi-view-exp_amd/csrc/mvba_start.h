@@ -1,0 +1,199 @@
+// What the entry points that start a reconstruction share (mvba_init.h, mvba_twoview.h, mvba_ransac.h) -- gfx950.
+//
+// Included by mvba.hip after its C entry points and before mvba_init.h: uses mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing
+// here runs on the LM path.  
+//
+// One copy each of: the cyclic Jacobi and its eigenvalue selection, the fixed reduction tree of a 256-thread chunk
+// (chunk_sum), the host clock and event guard, the checks of an observation list, of a pair list and of ascending camera
+// runs, and the upload of a list.  Every floating-point sum of these entry points is taken in an order that the sizes alone
+// fix: chunk_sum inside a chunk, then k_resect_combine (serial, ascending chunks) or k_twoview_combine (lane-strided, then
+// the shuffle tree) over a camera's or a pair's chunks -- two orders, on purpose.
+
+namespace {
+
+constexpr double INIT_REL_PIVOT = 1e-12;  // the relative pivot rule of mvba_covariance
+constexpr int INIT_MAX_CAMERAS = 1704;    // (160 KiB - 256 B) / 96 B: the LDS camera table of k_project_obs
+constexpr int START_CHUNK = 256;          // items (observations of a camera, points of a pair) per chunk = threads per workgroup
+
+// Eigen-decomposition of a symmetric N x N matrix by cyclic Jacobi (Rutishauser's rotations): A -> diagonal, V -> the
+// eigenvectors in its columns.  Every index is a compile-time constant once the loops are unrolled: on the device the
+// order-4 instance lives in registers (the form of mvsvd.hip's per-point solver).  A rotation is skipped once a_pq no
+// longer changes either diagonal entry in floating point.
+template <int N>
+__host__ __device__ __forceinline__ void sym_eig_jacobi(double (&A)[N][N], double (&V)[N][N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool any = false;
+#pragma unroll
+    for (int p = 0; p < N - 1; ++p)
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
+        const double g = fabs(apq);
+        if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
+          A[p][q] = A[q][p] = 0.0;
+          continue;
+        }
+        any = true;
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+        A[p][p] = app - t * apq;
+        A[q][q] = aqq + t * apq;
+        A[p][q] = A[q][p] = 0.0;
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+          if (r != p && r != q) {
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = A[p][r] = arp - s * (arq + tau * arp);
+            A[r][q] = A[q][r] = arq + s * (arp - tau * arq);
+          }
+          const double vrp = V[r][p], vrq = V[r][q];
+          V[r][p] = vrp - s * (vrq + tau * vrp);
+          V[r][q] = vrq + s * (vrp - tau * vrq);
+        }
+      }
+    if (!any) break;
+  }
+}
+
+// smallest, second-smallest and largest eigenvalue after sym_eig_jacobi, and the column of the smallest
+template <int N>
+__host__ __device__ __forceinline__ void eig_extremes(const double (&A)[N][N], const double (&V)[N][N], double &l1, double &l2,
+                                                      double &lmax, double (&v)[N]) {
+  int best = 0;
+  l1 = A[0][0];
+  lmax = A[0][0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) {
+    if (A[i][i] < l1) { l1 = A[i][i]; best = i; }
+    lmax = fmax(lmax, A[i][i]);
+  }
+  l2 = HUGE_VAL;
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    if (i != best) l2 = fmin(l2, A[i][i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double x = 0.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) x = j == best ? V[i][j] : x;  // (selects: a run-time column index would put V into scratch)
+    v[i] = x;
+  }
+}
+
+// The fixed tree of a chunk: the workgroup's START_CHUNK values v[e] summed into out[e] -- lanes l and l + off inside a wave,
+// off = 32 .. 1, then the waves in ascending order.  Every thread of the workgroup calls it (a barrier inside).
+template <int NV>
+__device__ __forceinline__ void chunk_sum(const double (&v)[NV], double (&s_w)[START_CHUNK / 64][NV], double *__restrict__ out) {
+  const int i = threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < NV; ++e) {
+    double x = v[e];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    if ((i & 63) == 0) s_w[i >> 6][e] = x;
+  }
+  __syncthreads();
+  if (i < NV) {
+    double x = s_w[0][i];
+#pragma unroll
+    for (int w = 1; w < START_CHUNK / 64; ++w) x += s_w[w][i];
+    out[i] = x;
+  }
+}
+
+struct InitClock {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double lap() {
+    const auto t1 = std::chrono::steady_clock::now();
+    const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+    return ms;
+  }
+};
+
+// events of one call: whatever was created is destroyed when the owner goes
+struct EvGuard {
+  hipEvent_t *e;
+  int n;
+  ~EvGuard() {
+    for (int i = 0; i < n; ++i)
+      if (e[i]) hipEventDestroy(e[i]);
+  }
+};
+
+// the checks mvba_project makes of an observation list, with the offending number in the message
+int init_check_list(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, int64_t n_obs) {
+  if (n_points < 0 || n_obs < 0) return fail(MVBA_ERR_BADARG, "n_points = " + std::to_string(n_points) + ", n_obs = " + std::to_string(n_obs) + ": negative size");
+  if (n_images < 1) return fail(MVBA_ERR_BADARG, "n_images = " + std::to_string(n_images) + " must be at least 1");
+  if (n_points >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n_points = " + std::to_string(n_points) + " must be < 2^31");
+  if (!pt_ptr) {
+    if (n_obs != n_points * (int64_t)n_images)
+      return fail(MVBA_ERR_BADARG, "dense grid needs n_obs = n_points * n_images = " + std::to_string(n_points * (int64_t)n_images) + ", got " + std::to_string(n_obs));
+    return MVBA_OK;
+  }
+  if (!cam_idx) return fail(MVBA_ERR_BADARG, "null argument: cam_idx (with a pt_ptr)");
+  if (pt_ptr[0] != 0) return fail(MVBA_ERR_BADARG, "pt_ptr[0] = " + std::to_string(pt_ptr[0]) + " must be 0");
+  for (int64_t a = 0; a < n_points; ++a)
+    if (pt_ptr[a + 1] < pt_ptr[a] || pt_ptr[a + 1] > n_obs)
+      return fail(MVBA_ERR_BADARG, "pt_ptr[" + std::to_string(a + 1) + "] = " + std::to_string(pt_ptr[a + 1]) + " is not ascending within n_obs = " + std::to_string(n_obs));
+  if (pt_ptr[n_points] != n_obs)
+    return fail(MVBA_ERR_BADARG, "pt_ptr does not span n_obs: pt_ptr[n_points] = " + std::to_string(pt_ptr[n_points]) + ", n_obs = " + std::to_string(n_obs));
+  for (int64_t o = 0; o < n_obs; ++o)
+    if (cam_idx[o] < 0 || cam_idx[o] >= n_images)
+      return fail(MVBA_ERR_BADARG, "cam_idx out of range: cam_idx[" + std::to_string(o) + "] = " + std::to_string(cam_idx[o]) + ", n_images = " + std::to_string(n_images));
+  return MVBA_OK;
+}
+
+int init_check_cameras(int32_t n_images) {
+  if (n_images > INIT_MAX_CAMERAS)
+    return fail(MVBA_ERR_BADARG, "too many cameras for the LDS camera table: n_images = " + std::to_string(n_images) + " (max " + std::to_string(INIT_MAX_CAMERAS) + ")");
+  return MVBA_OK;
+}
+
+// a list of camera pairs (k, l): both in range, and different
+int check_pairs(const int32_t *pairs, int32_t n_pairs, int32_t n_images) {
+  for (int32_t p = 0; p < n_pairs; ++p) {
+    const int32_t k = pairs[2 * p], l = pairs[2 * p + 1];
+    if (k < 0 || k >= n_images || l < 0 || l >= n_images)
+      return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) +
+                                       "): camera index out of range, n_images = " + std::to_string(n_images));
+    if (k == l) return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) + "): the two cameras must differ");
+  }
+  return MVBA_OK;
+}
+
+// the kernels that search a point's camera run (tv_find) need it to ascend; pt_ptr == nullptr: the dense grid does
+int check_ascending(int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx) {
+  if (!pt_ptr) return MVBA_OK;
+  for (int64_t a = 0; a < n_points; ++a)
+    for (int64_t o = pt_ptr[a] + 1; o < pt_ptr[a + 1]; ++o)
+      if (cam_idx[o] <= cam_idx[o - 1])
+        return fail(MVBA_ERR_BADARG, "cam_idx is not ascending within point " + std::to_string(a) + ": cam_idx[" + std::to_string(o) + "] = " +
+                                         std::to_string(cam_idx[o]) + " after " + std::to_string(cam_idx[o - 1]));
+  return MVBA_OK;
+}
+
+// An observation list to the device, owned by tmp: xy (unless nullptr) into *dxy, and pt_ptr and cam_idx into *dptr and
+// *dcam, which stay nullptr for the dense grid (pt_ptr == nullptr).
+int upload_list(DevBufs &tmp, int64_t n_points, int64_t n_obs, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy,
+                long long **dptr, int **dcam, double2 **dxy) {
+  static_assert(sizeof(long long) == sizeof(int64_t), "pt_ptr goes to the device as it is");
+  int rc;
+  if (xy) {
+    if ((rc = tmp.alloc(dxy, (size_t)n_obs))) return rc;
+    if (n_obs) MVBA_HIP(hipMemcpy(*dxy, xy, sizeof(double2) * n_obs, hipMemcpyHostToDevice));
+  }
+  if (pt_ptr) {
+    if ((rc = tmp.alloc(dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(dcam, (size_t)n_obs))) return rc;
+    MVBA_HIP(hipMemcpy(*dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
+    if (n_obs) MVBA_HIP(hipMemcpy(*dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
+  }
+  return MVBA_OK;
+}
+
+}  // namespace

@@ -1,7 +1,8 @@
 // Starting a reconstruction from two views (mvba_covisibility, mvba_two_view) -- kernels and host code, gfx950.
 //
-// Included by mvba.hip after mvba_init.h: uses its sym_eig_jacobi, eig_extremes, init_check_list, init_check_cameras, InitClock
-// and EvGuard, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
+// Included by mvba.hip after mvba_start.h and mvba_init.h: uses mvba_start.h's sym_eig_jacobi, eig_extremes, chunk_sum, the
+// list and pair checks, upload_list, InitClock and EvGuard, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on
+// the LM path.  
 //
 // Co-visibility: ONE THREAD PER POINT walks the pairs of its own camera run (deg^2 / 2 increments) into an m x m table of
 // integer counters -- integer sums are exact in any order, so these are atomics: a per-workgroup table in LDS that is flushed
@@ -10,13 +11,12 @@
 //
 // Epipolar moments: one workgroup of 256 threads takes 256 consecutive points for one pair (blockIdx.y: the pair inside the
 // launch's tile of pairs).  A thread finds k and l in its point's ascending camera run by two binary searches, forms its
-// values (or zeros) and the workgroup sums them by the fixed tree of k_resect_chunk; k_twoview_combine adds a pair's chunk
+// values (tv_pass, or zeros) and the workgroup sums them by chunk_sum; k_twoview_combine adds a pair's chunk
 // partials in an order that depends on the chunk count alone.  No floating-point atomics: two runs are bitwise equal.  The
 // eigen-problems of order 9 are solved on the host (sym_eig_jacobi<9>), as mvba_resect solves its own of order 12.
 
 namespace {
 
-constexpr int TV_CHUNK = 256;                   // points per chunk = threads per workgroup
 constexpr int TV_NORM = 8;                      // per pair: centroid in k (2), scale in k, centroid in l (2), scale in l, count, unused
 constexpr int TV_MIN_SHARED = 8;                // the linear solution needs 8 rows
 constexpr size_t TV_PART_BYTES = 128u << 20;    // chunk partials of one launch: pairs are tiled to stay under this
@@ -25,6 +25,8 @@ constexpr int CV_LDS_CAMERAS = 128;             // m^2 x 4 bytes <= 64 KiB: the 
 // values per shared point of the four passes: 0 count and first moments, 1 squared distances to the centroids, 2 the 45
 // unique products of the epipolar row, 3 the squared Sampson distance
 __host__ __device__ constexpr int tv_values(int mode) { return mode == 0 ? 5 : (mode == 1 ? 2 : (mode == 2 ? 45 : 1)); }
+// doubles per pair of what a pass reads besides the point: 0 nothing, 1 and 2 the TV_NORM record, 3 F
+__host__ __device__ constexpr int tv_aux(int mode) { return mode == 0 ? 0 : (mode == 3 ? 9 : TV_NORM); }
 
 __global__ __launch_bounds__(256) void k_covisibility(long long npts, int m, const long long *__restrict__ pt_ptr,
                                                       const int *__restrict__ cam_idx, unsigned long long *__restrict__ count,
@@ -69,22 +71,10 @@ __device__ __forceinline__ long long tv_find(const int *__restrict__ cam, long l
   return (lo < deg && cam[o0 + lo] == c) ? o0 + lo : -1;
 }
 
-// One workgroup per (chunk of 256 points, pair of the tile): the chunk's sums over the points both cameras see into
-// part[pair][chunk][NV].  aux (per pair of the tile): mode 1, 2 the TV_NORM table, mode 3 F [9].
-template <int MODE>
-__global__ __launch_bounds__(TV_CHUNK) void k_twoview_chunk(long long npts, int m, const long long *__restrict__ pt_ptr,
-                                                            const int *__restrict__ cam_idx, const double2 *__restrict__ xy,
-                                                            const int *__restrict__ pairs, const double *__restrict__ aux,
-                                                            double *__restrict__ part) {
-  constexpr int NV = tv_values(MODE);
-  __shared__ double s_w[TV_CHUNK / 64][NV];
-  const int p = blockIdx.y, i = threadIdx.x;
-  const long long a = (long long)blockIdx.x * TV_CHUNK + i;
-  const int k = pairs[2 * p], l = pairs[2 * p + 1];
-  double v[NV];
-#pragma unroll
-  for (int e = 0; e < NV; ++e) v[e] = 0.0;
-  long long ok = -1, ol = -1;
+// does point a see both cameras of the pair?  (its two observations in ok, ol)
+__device__ __forceinline__ bool rs_shared(long long a, long long npts, int m, const long long *__restrict__ pt_ptr,
+                                          const int *__restrict__ cam_idx, int k, int l, long long &ok, long long &ol) {
+  ok = ol = -1;
   if (a < npts) {
     const long long o0 = pt_ptr ? pt_ptr[a] : a * m;
     const int deg = pt_ptr ? (int)(pt_ptr[a + 1] - pt_ptr[a]) : m;
@@ -92,48 +82,87 @@ __global__ __launch_bounds__(TV_CHUNK) void k_twoview_chunk(long long npts, int 
     ok = tv_find(cam, o0, deg, k);
     if (ok >= 0) ol = tv_find(cam, o0, deg, l);
   }
+  return ok >= 0 && ol >= 0;
+}
+
+// the squared Sampson distance of (xk, yk) in k and (xl, yl) in l under F
+__device__ __forceinline__ double rs_sampson(const double *F, double xk, double yk, double xl, double yl) {
+  const double f0 = F[0] * xk + F[1] * yk + F[2], f1 = F[3] * xk + F[4] * yk + F[5], f2 = F[6] * xk + F[7] * yk + F[8];
+  const double g0 = F[0] * xl + F[3] * yl + F[6], g1 = F[1] * xl + F[4] * yl + F[7];
+  const double r = xl * f0 + yl * f1 + f2;
+  return r * r / (f0 * f0 + f1 * f1 + g0 * g0 + g1 * g1);
+}
+
+// the epipolar row of one correspondence in the normalised coordinates of the pair's TV_NORM record nm: r . f^ = 0
+__device__ __forceinline__ void tv_row(const double *nm, double zkx, double zky, double zlx, double zly, double (&r)[9]) {
+  const double xk = nm[2] * (zkx - nm[0]), yk = nm[2] * (zky - nm[1]);
+  const double xl = nm[5] * (zlx - nm[3]), yl = nm[5] * (zly - nm[4]);
+  r[0] = xl * xk; r[1] = xl * yk; r[2] = xl; r[3] = yl * xk; r[4] = yl * yk; r[5] = yl; r[6] = xk; r[7] = yk; r[8] = 1.0;
+}
+
+// The values of one shared point, (xk, yk) in k and (xl, yl) in l, in pass MODE.  aux (of the pair): mode 1, 2 its TV_NORM
+// record, mode 3 F [9] (tv_aux doubles).
+template <int MODE>
+__device__ __forceinline__ void tv_pass(double xk, double yk, double xl, double yl, const double *aux, double (&v)[tv_values(MODE)]) {
+  if constexpr (MODE == 0) {
+    v[0] = 1.0; v[1] = xk; v[2] = yk; v[3] = xl; v[4] = yl;
+  } else if constexpr (MODE == 1) {
+    const double d0 = xk - aux[0], d1 = yk - aux[1], e0 = xl - aux[3], e1 = yl - aux[4];
+    v[0] = d0 * d0 + d1 * d1;
+    v[1] = e0 * e0 + e1 * e1;
+  } else if constexpr (MODE == 2) {
+    double r[9];
+    tv_row(aux, xk, yk, xl, yl, r);
+    int e = 0;
+#pragma unroll
+    for (int b = 0; b < 9; ++b)
+#pragma unroll
+      for (int c = b; c < 9; ++c, ++e) v[e] = r[b] * r[c];
+  } else {
+    v[0] = rs_sampson(aux, xk, yk, xl, yl);
+  }
+}
+
+// F = T_l^T F^ T_k with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]]: f the row-major F^, nm the pair's TV_NORM record
+__host__ __device__ __forceinline__ void tv_denormalise(const double *nm, const double *f, double *F) {
+  const double ckx = nm[0], cky = nm[1], sk = nm[2], clx = nm[3], cly = nm[4], sl = nm[5];
+  double Q[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    Q[i][0] = sk * f[3 * i];
+    Q[i][1] = sk * f[3 * i + 1];
+    Q[i][2] = f[3 * i + 2] - sk * (ckx * f[3 * i] + cky * f[3 * i + 1]);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    F[j] = sl * Q[0][j];
+    F[3 + j] = sl * Q[1][j];
+    F[6 + j] = Q[2][j] - sl * (clx * Q[0][j] + cly * Q[1][j]);
+  }
+}
+
+// One workgroup per (chunk of 256 points, pair of the tile): the chunk's sums over the points both cameras see into
+// part[pair][chunk][NV].  aux (per pair of the tile): mode 1, 2 the TV_NORM table, mode 3 F [9].
+template <int MODE>
+__global__ __launch_bounds__(START_CHUNK) void k_twoview_chunk(long long npts, int m, const long long *__restrict__ pt_ptr,
+                                                            const int *__restrict__ cam_idx, const double2 *__restrict__ xy,
+                                                            const int *__restrict__ pairs, const double *__restrict__ aux,
+                                                            double *__restrict__ part) {
+  constexpr int NV = tv_values(MODE);
+  __shared__ double s_w[START_CHUNK / 64][NV];
+  const int p = blockIdx.y, i = threadIdx.x;
+  const long long a = (long long)blockIdx.x * START_CHUNK + i;
+  const double *nm = aux + tv_aux(MODE) * (size_t)p;
+  double v[NV];
+#pragma unroll
+  for (int e = 0; e < NV; ++e) v[e] = 0.0;
+  long long ok, ol;
+  rs_shared(a, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
   if (ok >= 0 && ol >= 0) {
     const double2 zk = xy[ok], zl = xy[ol];
-    if constexpr (MODE == 0) {
-      v[0] = 1.0; v[1] = zk.x; v[2] = zk.y; v[3] = zl.x; v[4] = zl.y;
-    } else if constexpr (MODE == 1) {
-      const double *nm = aux + TV_NORM * (size_t)p;
-      const double d0 = zk.x - nm[0], d1 = zk.y - nm[1], e0 = zl.x - nm[3], e1 = zl.y - nm[4];
-      v[0] = d0 * d0 + d1 * d1;
-      v[1] = e0 * e0 + e1 * e1;
-    } else if constexpr (MODE == 2) {
-      const double *nm = aux + TV_NORM * (size_t)p;
-      const double xk = nm[2] * (zk.x - nm[0]), yk = nm[2] * (zk.y - nm[1]);
-      const double xl = nm[5] * (zl.x - nm[3]), yl = nm[5] * (zl.y - nm[4]);
-      const double r[9] = {xl * xk, xl * yk, xl, yl * xk, yl * yk, yl, xk, yk, 1.0};
-      int e = 0;
-#pragma unroll
-      for (int b = 0; b < 9; ++b)
-#pragma unroll
-        for (int c = b; c < 9; ++c, ++e) v[e] = r[b] * r[c];
-    } else {
-      const double *F = aux + 9 * (size_t)p;
-      const double f0 = F[0] * zk.x + F[1] * zk.y + F[2], f1 = F[3] * zk.x + F[4] * zk.y + F[5], f2 = F[6] * zk.x + F[7] * zk.y + F[8];
-      const double g0 = F[0] * zl.x + F[3] * zl.y + F[6], g1 = F[1] * zl.x + F[4] * zl.y + F[7];
-      const double r = zl.x * f0 + zl.y * f1 + f2;
-      v[0] = r * r / (f0 * f0 + f1 * f1 + g0 * g0 + g1 * g1);
-    }
+    tv_pass<MODE>(zk.x, zk.y, zl.x, zl.y, nm, v);
   }
-  // the fixed tree of k_resect_chunk: lanes l and l + off inside a wave, off = 32 .. 1, then the waves in ascending order
-#pragma unroll
-  for (int e = 0; e < NV; ++e) {
-    double x = v[e];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    if ((i & 63) == 0) s_w[i >> 6][e] = x;
-  }
-  __syncthreads();
-  if (i < NV) {
-    double x = s_w[0][i];
-#pragma unroll
-    for (int w = 1; w < TV_CHUNK / 64; ++w) x += s_w[w][i];
-    part[((size_t)p * gridDim.x + blockIdx.x) * NV + i] = x;
-  }
+  chunk_sum<NV>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * NV);
 }
 
 // out[p][e] = the sum of pair p's chunk partials: one wave per (p, e); lane j adds the chunks j, j + 64, ... in ascending
@@ -189,25 +218,13 @@ int twoview_solve_pair(const double *S45, const double *nm, double *F, double *r
   sym_eig_jacobi<3>(G, W);
   double m1, m2, mmax, v[3];
   eig_extremes<3>(G, W, m1, m2, mmax, v);
-  double H[3][3];
+  double H[9];
   for (int i = 0; i < 3; ++i) {
     const double fv = f[3 * i] * v[0] + f[3 * i + 1] * v[1] + f[3 * i + 2] * v[2];
-    for (int j = 0; j < 3; ++j) H[i][j] = f[3 * i + j] - fv * v[j];
+    for (int j = 0; j < 3; ++j) H[3 * i + j] = f[3 * i + j] - fv * v[j];
   }
-  // F = T_l^T F^ T_k with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]]
-  const double ckx = nm[0], cky = nm[1], sk = nm[2], clx = nm[3], cly = nm[4], sl = nm[5];
-  double Q[3][3];
-  for (int i = 0; i < 3; ++i) {
-    Q[i][0] = sk * H[i][0];
-    Q[i][1] = sk * H[i][1];
-    Q[i][2] = H[i][2] - sk * (ckx * H[i][0] + cky * H[i][1]);
-  }
+  tv_denormalise(nm, H, F);
   double nrm = 0.0, big = 0.0;
-  for (int j = 0; j < 3; ++j) {
-    F[j] = sl * Q[0][j];
-    F[3 + j] = sl * Q[1][j];
-    F[6 + j] = Q[2][j] - sl * (clx * Q[0][j] + cly * Q[1][j]);
-  }
   for (int j = 0; j < 9; ++j) {
     nrm += F[j] * F[j];
     if (fabs(F[j]) > fabs(big)) big = F[j];
@@ -219,6 +236,16 @@ int twoview_solve_pair(const double *S45, const double *nm, double *F, double *r
     ok = ok && std::isfinite(F[j]);
   }
   return ok ? 0 : 2;
+}
+
+// pairs per launch: the tile's device bytes stay under TV_PART_BYTES, its count within gridDim.y
+int tv_pair_tile(int n_pairs, size_t bytes_per_pair) {
+  return (int)std::max<long long>(1, std::min<long long>(std::min<long long>(n_pairs, 65535), (long long)(TV_PART_BYTES / bytes_per_pair)));
+}
+
+// the launch of k_twoview_combine over the cnt pairs of a tile
+void tv_combine(int cnt, int nv, long long n_ch, const double *part, double *out, int stride) {
+  hipLaunchKernelGGL(k_twoview_combine, dim3((unsigned)(((long long)cnt * nv + 3) / 4)), dim3(256), 0, 0, cnt, nv, (int)n_ch, part, out, stride);
 }
 
 }  // namespace
@@ -245,11 +272,7 @@ int mvba_covisibility(int64_t n_points, int32_t n_images, const int64_t *pt_ptr,
   static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters come back as they are");
   if ((rc = tmp.alloc(&dcount, mm))) return rc;
   MVBA_HIP(hipMemset(dcount, 0, sizeof(unsigned long long) * mm));
-  if (pt_ptr) {
-    if ((rc = tmp.alloc(&dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(&dcam, (size_t)n_obs))) return rc;
-    MVBA_HIP(hipMemcpy(dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
-    if (n_obs) MVBA_HIP(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
-  }
+  if ((rc = upload_list(tmp, n_points, n_obs, pt_ptr, cam_idx, nullptr, &dptr, &dcam, nullptr))) return rc;
   if (timings_ms) timings_ms[0] = clk.lap();
   hipEvent_t ev[2] = {nullptr, nullptr};
   EvGuard guard{ev, 2};
@@ -284,19 +307,8 @@ int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, con
   int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
   if (rc) return rc;
   if ((rc = init_check_cameras(n_images))) return rc;
-  for (int32_t p = 0; p < n_pairs; ++p) {
-    const int32_t k = pairs[2 * p], l = pairs[2 * p + 1];
-    if (k < 0 || k >= n_images || l < 0 || l >= n_images)
-      return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) +
-                                       "): camera index out of range, n_images = " + std::to_string(n_images));
-    if (k == l) return fail(MVBA_ERR_BADARG, "pairs[" + std::to_string(p) + "] = (" + std::to_string(k) + ", " + std::to_string(l) + "): the two cameras must differ");
-  }
-  if (pt_ptr)  // the kernels search a point's camera run: it must ascend
-    for (int64_t a = 0; a < n_points; ++a)
-      for (int64_t o = pt_ptr[a] + 1; o < pt_ptr[a + 1]; ++o)
-        if (cam_idx[o] <= cam_idx[o - 1])
-          return fail(MVBA_ERR_BADARG, "cam_idx is not ascending within point " + std::to_string(a) + ": cam_idx[" + std::to_string(o) + "] = " +
-                                           std::to_string(cam_idx[o]) + " after " + std::to_string(cam_idx[o - 1]));
+  if ((rc = check_pairs(pairs, n_pairs, n_images))) return rc;
+  if ((rc = check_ascending(n_points, pt_ptr, cam_idx))) return rc;
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = 0.0;
   const int np = n_pairs;
   std::vector<double> Fm(9 * (size_t)np, NAN), S((size_t)np * 45, 0.0), norm(TV_NORM * (size_t)np, 0.0), Sr((size_t)np, 0.0), ratio((size_t)np, NAN);
@@ -304,45 +316,37 @@ int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, con
   if (np > 0 && n_points > 0) {
     if (device >= 0) MVBA_HIP(hipSetDevice(device));
     InitClock clk;
-    const long long n_ch = (n_points + TV_CHUNK - 1) / TV_CHUNK;
-    const int tile = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(np, 65535), (long long)(TV_PART_BYTES / (sizeof(double) * 45 * (size_t)n_ch))));
+    const long long n_ch = (n_points + START_CHUNK - 1) / START_CHUNK;
+    const int tile = tv_pair_tile(np, sizeof(double) * 45 * (size_t)n_ch);
     DevBufs tmp;
     double2 *dxy = nullptr;
     long long *dptr = nullptr;
     int *dcam = nullptr, *dpairs = nullptr;
     double *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dF = nullptr, *dS1 = nullptr;
-    if ((rc = tmp.alloc(&dxy, (size_t)n_obs)) || (rc = tmp.alloc(&dpairs, 2 * (size_t)np)) || (rc = tmp.alloc(&dpart, 45 * (size_t)n_ch * tile)) ||
+    if ((rc = upload_list(tmp, n_points, n_obs, pt_ptr, cam_idx, xy, &dptr, &dcam, &dxy)) || (rc = tmp.alloc(&dpairs, 2 * (size_t)np)) || (rc = tmp.alloc(&dpart, 45 * (size_t)n_ch * tile)) ||
         (rc = tmp.alloc(&dS, 45 * (size_t)np)) || (rc = tmp.alloc(&dS1, 5 * (size_t)tile)) || (rc = tmp.alloc(&dnorm, TV_NORM * (size_t)np)) ||
         (rc = tmp.alloc(&dF, 9 * (size_t)np)))
       return rc;
-    if (n_obs) MVBA_HIP(hipMemcpy(dxy, xy, sizeof(double2) * n_obs, hipMemcpyHostToDevice));
     MVBA_HIP(hipMemcpy(dpairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice));
-    if (pt_ptr) {
-      if ((rc = tmp.alloc(&dptr, (size_t)n_points + 1)) || (rc = tmp.alloc(&dcam, (size_t)n_obs))) return rc;
-      MVBA_HIP(hipMemcpy(dptr, pt_ptr, sizeof(int64_t) * (n_points + 1), hipMemcpyHostToDevice));
-      if (n_obs) MVBA_HIP(hipMemcpy(dcam, cam_idx, sizeof(int) * n_obs, hipMemcpyHostToDevice));
-    }
     if (timings_ms) timings_ms[0] = clk.lap();
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     EvGuard guard{ev, 4};
     for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
     const dim3 b256(256);
-    auto combine = [&](int cnt, int nv, double *out, int stride) {
-      hipLaunchKernelGGL(k_twoview_combine, dim3((unsigned)(((long long)cnt * nv + 3) / 4)), b256, 0, 0, cnt, nv, (int)n_ch, dpart, out, stride);
-    };
+    auto combine = [&](int cnt, int nv, double *out, int stride) { tv_combine(cnt, nv, n_ch, dpart, out, stride); };
     hipEventRecord(ev[0], 0);
     for (int p0 = 0; p0 < np; p0 += tile) {
       const int cnt = std::min(tile, np - p0);
       const dim3 grid((unsigned)n_ch, (unsigned)cnt), gp((cnt + 255) / 256);
       const int *tp = dpairs + 2 * (size_t)p0;
       double *tn = dnorm + TV_NORM * (size_t)p0;
-      hipLaunchKernelGGL(k_twoview_chunk<0>, grid, dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, (const double *)nullptr, dpart);
+      hipLaunchKernelGGL(k_twoview_chunk<0>, grid, dim3(START_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, (const double *)nullptr, dpart);
       combine(cnt, 5, dS1, 5);
       hipLaunchKernelGGL(k_twoview_norm, gp, b256, 0, 0, cnt, 0, dS1, 5, tn);
-      hipLaunchKernelGGL(k_twoview_chunk<1>, grid, dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, tn, dpart);
+      hipLaunchKernelGGL(k_twoview_chunk<1>, grid, dim3(START_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, tn, dpart);
       combine(cnt, 2, dS1, 2);
       hipLaunchKernelGGL(k_twoview_norm, gp, b256, 0, 0, cnt, 1, dS1, 2, tn);
-      hipLaunchKernelGGL(k_twoview_chunk<2>, grid, dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, tn, dpart);
+      hipLaunchKernelGGL(k_twoview_chunk<2>, grid, dim3(START_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, tn, dpart);
       combine(cnt, 45, dS + 45 * (size_t)p0, 45);
     }
     hipEventRecord(ev[1], 0);
@@ -359,7 +363,7 @@ int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, con
     hipEventRecord(ev[2], 0);
     for (int p0 = 0; p0 < np; p0 += tile) {
       const int cnt = std::min(tile, np - p0);
-      hipLaunchKernelGGL(k_twoview_chunk<3>, dim3((unsigned)n_ch, (unsigned)cnt), dim3(TV_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy,
+      hipLaunchKernelGGL(k_twoview_chunk<3>, dim3((unsigned)n_ch, (unsigned)cnt), dim3(START_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy,
                          dpairs + 2 * (size_t)p0, dF + 9 * (size_t)p0, dpart);
       combine(cnt, 1, dS + (size_t)p0, 1);
     }

@@ -165,6 +165,37 @@ def device_count():
     return n.value if rc == MVBA_OK else 0
 
 
+def _require_device(name):
+    if device_count() < 1:
+        raise RuntimeError(f"libmvba: no HIP device visible; {name} has no CPU fallback")
+
+
+def _obs_list(pt_ptr, cam_idx, xy, m, n_points=None):
+    """An observation list as the C entry points take it: ``(n, n_obs, pt_ptr pointer, cam_idx pointer, xy)``.  With
+    ``pt_ptr=None`` the dense grid (null pointers; xy (N, m, 2), or ``n_points`` where there is no xy); otherwise xy comes
+    back as (n_obs, 2).  ``n_points``, where the caller knows it, must agree."""
+    if pt_ptr is None:
+        if xy is None:
+            assert n_points is not None
+            n = int(n_points)
+        else:
+            assert xy.ndim == 3 and xy.shape[1:] == (m, 2) and n_points in (None, xy.shape[0])
+            n = xy.shape[0]
+        return n, n * m, None, None, xy
+    pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
+    n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
+    assert n_points is None or int(n_points) == n
+    if xy is not None:
+        xy = xy.reshape(-1, 2)
+        assert xy.shape[0] == n_obs
+    # (a ctypes pointer made by data_as keeps its array alive)
+    return n, n_obs, pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32)), xy
+
+
+def _timings3(tm):
+    return dict(zip(("upload", "kernel", "download"), tm.tolist()))
+
+
 class HipEngine:
     """Device-resident BA state + kernels.  Protocol (shared with the oracle's
     engine): set_params / get_params / cost / linearize / try_step / commit.
@@ -317,7 +348,7 @@ class HipEngine:
         tm = np.zeros(3)
         raise_for(self.lib.mvba_triangulate_state(self._h, int(n_refine), _ptr(q), st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm)),
                   self.lib)
-        return q, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+        return q, st, _timings3(tm)
 
     def residuals(self):
         """(n_obs, 2) residuals f0 e_o in image units at the committed state, in the engine's observation order."""
@@ -393,20 +424,13 @@ def project(X, K, R, t, pt_ptr=None, cam_idx=None, device=-1):
     """Device pinhole projection (mvba_project).  With an observation list (pt_ptr, cam_idx):
     (n_obs, 2); without: the dense grid (N, m, 2).  No CPU fallback."""
     lib = load_library()
-    if device_count() < 1:
-        raise RuntimeError("libmvba: no HIP device visible; mvba_project has no CPU fallback")
+    _require_device("mvba_project")
     X, K, R, t = (_as(v, np.float64) for v in (X, K, R, t))
     n, m = X.shape[0], K.shape[0]
     assert X.shape == (n, 3) and K.shape == (m, 3, 3) and R.shape == (m, 3, 3) and t.shape == (m, 3)
-    if pt_ptr is None:
-        out = np.empty((n, m, 2))
-        rc = lib.mvba_project(_ptr(X), n, _ptr(K), _ptr(R), _ptr(t), m, None, None, n * m, _ptr(out), int(device))
-    else:
-        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
-        out = np.empty((cam_idx.shape[0], 2))
-        rc = lib.mvba_project(_ptr(X), n, _ptr(K), _ptr(R), _ptr(t), m, pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                              cam_idx.ctypes.data_as(C.POINTER(C.c_int32)), cam_idx.shape[0], _ptr(out), int(device))
-    raise_for(rc, lib)
+    _, n_obs, pp, cp, _ = _obs_list(pt_ptr, cam_idx, None, m, n if pt_ptr is None else None)
+    out = np.empty((n, m, 2) if pt_ptr is None else (n_obs, 2))
+    raise_for(lib.mvba_project(_ptr(X), n, _ptr(K), _ptr(R), _ptr(t), m, pp, cp, n_obs, _ptr(out), int(device)), lib)
     return out
 
 
@@ -419,24 +443,15 @@ def triangulate(K, R, t, pt_ptr, cam_idx, xy, n_refine=2, device=-1):
     3 at infinity / not finite (X is NaN then); quality = RMS reprojection residual, smallest depth, largest angle between
     two viewing rays (radians).  No CPU fallback."""
     lib = load_library()
-    if device_count() < 1:
-        raise RuntimeError("libmvba: no HIP device visible; mvba_triangulate has no CPU fallback")
+    _require_device("mvba_triangulate")
     K, R, t, xy = (_as(v, np.float64) for v in (K, R, t, xy))
     m = K.shape[0]
     assert K.shape == (m, 3, 3) and R.shape == (m, 3, 3) and t.shape == (m, 3)
-    if pt_ptr is None:
-        assert xy.ndim == 3 and xy.shape[1:] == (m, 2)
-        n, n_obs, pp, cp = xy.shape[0], xy.shape[0] * m, None, None
-    else:
-        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
-        xy = xy.reshape(-1, 2)
-        assert xy.shape[0] == cam_idx.shape[0]
-        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
-        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
     X, q, st, tm = np.empty((n, 3)), np.empty((n, 3)), np.empty(n, np.int32), np.zeros(3)
     raise_for(lib.mvba_triangulate(_ptr(K), _ptr(R), _ptr(t), m, n, pp, cp, _ptr(xy), n_obs, int(n_refine), _ptr(X), _ptr(q),
                                    st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm), int(device)), lib)
-    return X, q, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+    return X, q, st, _timings3(tm)
 
 
 def resect(X, pt_ptr, cam_idx, xy, n_images, point_ok=None, device=-1):
@@ -446,20 +461,11 @@ def resect(X, pt_ptr, cam_idx, xy, n_images, point_ok=None, device=-1):
     det P[:, :3] > 0, ``quality (m, 2)`` (RMS reprojection residual, eigenvalue ratio), ``status (m,)`` (0 ok, 1 fewer than 6
     usable observations, 2 degenerate; P is NaN then), ``timings_ms``.  No CPU fallback."""
     lib = load_library()
-    if device_count() < 1:
-        raise RuntimeError("libmvba: no HIP device visible; mvba_resect has no CPU fallback")
+    _require_device("mvba_resect")
     X, xy = _as(X, np.float64), _as(xy, np.float64)
     n, m = X.shape[0], int(n_images)
     assert X.shape == (n, 3)
-    if pt_ptr is None:
-        assert xy.shape == (n, m, 2)
-        n_obs, pp, cp = n * m, None, None
-    else:
-        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
-        xy = xy.reshape(-1, 2)
-        assert pt_ptr.shape == (n + 1,) and xy.shape[0] == cam_idx.shape[0]
-        n_obs = cam_idx.shape[0]
-        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    _, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m, n)
     okp = None
     if point_ok is not None:
         ok = _as(np.asarray(point_ok) != 0, np.uint8)
@@ -468,7 +474,7 @@ def resect(X, pt_ptr, cam_idx, xy, n_images, point_ok=None, device=-1):
     P, q, st, tm = np.empty((m, 3, 4)), np.empty((m, 2)), np.empty(m, np.int32), np.zeros(3)
     raise_for(lib.mvba_resect(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, _ptr(P), _ptr(q), st.ctypes.data_as(C.POINTER(C.c_int32)),
                               _ptr(tm), int(device)), lib)
-    return P, q, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+    return P, q, st, _timings3(tm)
 
 
 def covisibility(pt_ptr, cam_idx, n_images, n_points=None, device=-1):
@@ -476,20 +482,12 @@ def covisibility(pt_ptr, cam_idx, n_images, n_points=None, device=-1):
     in both k and l, count[k, k] = camera k's observation count.  ``pt_ptr=None`` with ``n_points``: the dense grid.  Returns
     ``count, timings_ms``.  No CPU fallback."""
     lib = load_library()
-    if device_count() < 1:
-        raise RuntimeError("libmvba: no HIP device visible; mvba_covisibility has no CPU fallback")
+    _require_device("mvba_covisibility")
     m = int(n_images)
-    if pt_ptr is None:
-        assert n_points is not None
-        n, n_obs, pp, cp = int(n_points), int(n_points) * m, None, None
-    else:
-        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
-        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
-        assert n_points is None or int(n_points) == n
-        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    n, n_obs, pp, cp, _ = _obs_list(pt_ptr, cam_idx, None, m, n_points)
     count, tm = np.zeros((max(m, 0), max(m, 0)), np.int64), np.zeros(3)
     raise_for(lib.mvba_covisibility(n, m, pp, cp, n_obs, count.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(tm), int(device)), lib)
-    return count, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+    return count, _timings3(tm)
 
 
 def two_view(pt_ptr, cam_idx, xy, n_images, pairs, device=-1):
@@ -499,24 +497,15 @@ def two_view(pt_ptr, cam_idx, xy, n_images, pairs, device=-1):
     Sampson distance, eigenvalue ratio), ``n_shared (P,)``, ``status (P,)`` (0 ok, 1 fewer than 8 shared points, 2 degenerate;
     F and quality are NaN then), ``timings_ms``.  No CPU fallback."""
     lib = load_library()
-    if device_count() < 1:
-        raise RuntimeError("libmvba: no HIP device visible; mvba_two_view has no CPU fallback")
+    _require_device("mvba_two_view")
     xy, m = _as(xy, np.float64), int(n_images)
     pairs = _as(pairs, np.int32).reshape(-1, 2)
-    if pt_ptr is None:
-        assert xy.ndim == 3 and xy.shape[1:] == (m, 2)
-        n, n_obs, pp, cp = xy.shape[0], xy.shape[0] * m, None, None
-    else:
-        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
-        xy = xy.reshape(-1, 2)
-        assert xy.shape[0] == cam_idx.shape[0]
-        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
-        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
     P = pairs.shape[0]
     F, q, ns, st, tm = np.empty((P, 3, 3)), np.empty((P, 2)), np.empty(P, np.int64), np.empty(P, np.int32), np.zeros(3)
     raise_for(lib.mvba_two_view(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, _ptr(F), _ptr(q),
                                 ns.ctypes.data_as(C.POINTER(C.c_int64)), st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm), int(device)), lib)
-    return F, q, ns, st, dict(zip(("upload", "kernel", "download"), tm.tolist()))
+    return F, q, ns, st, _timings3(tm)
 
 
 def two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=512, seed=0, n_refit=2, return_inliers=True,
@@ -528,19 +517,10 @@ def two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypothese
     ``inlier (P, N) bool`` (``return_inliers``: P x N bytes on the host and on the device), ``hyp_count (P, H) int32``
     (``return_counts``), ``timings_ms``.  No CPU fallback."""
     lib = load_library()
-    if device_count() < 1:
-        raise RuntimeError("libmvba: no HIP device visible; mvba_two_view_robust has no CPU fallback")
+    _require_device("mvba_two_view_robust")
     xy, m = _as(xy, np.float64), int(n_images)
     pairs = _as(pairs, np.int32).reshape(-1, 2)
-    if pt_ptr is None:
-        assert xy.ndim == 3 and xy.shape[1:] == (m, 2)
-        n, n_obs, pp, cp = xy.shape[0], xy.shape[0] * m, None, None
-    else:
-        pt_ptr, cam_idx = _as(pt_ptr, np.int64), _as(cam_idx, np.int32)
-        xy = xy.reshape(-1, 2)
-        assert xy.shape[0] == cam_idx.shape[0]
-        n, n_obs = pt_ptr.shape[0] - 1, cam_idx.shape[0]
-        pp, cp = pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32))
+    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
     P, H = pairs.shape[0], int(n_hypotheses)
     i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
     F, q, tm = np.empty((P, 3, 3)), np.empty((P, 2)), np.zeros(4)
