@@ -16,7 +16,10 @@ THRESHOLD = 0.01  # the median Sampson distance of clean points on these scenes 
 # Host-versus-host max-abs difference of the final F (|F| = 1) over the pairs of status 0, measured by test_ransac_cpu.py on
 # the very cases below.  A GPU parity assert gets MARGIN x its case's figure; the Sampson RMS the same margin relative to
 # its own size.
-RANSAC_HOST_DIFF = {"300x8": 8.7e-14, "2000x3": 1.3e-14, "257x2": 7.8e-16, "dense130x3": 3.8e-15, "pixels": 9.2e-15}
+RANSAC_HOST_DIFF = {"300x8": 8.7e-14, "2000x3": 1.3e-14, "257x2": 7.8e-16, "dense130x3": 3.8e-15, "pixels": 9.2e-15,
+                    # the structural limits (LIMITS below)
+                    "scan257": 2.4e-15, "refits_1.5e-3": 4.0e-15, "refits_3e-3": 4.7e-15, "mixed": 5.1e-15, "mixed65": 3.6e-12,
+                    "partly_degenerate": 6.1e-15}
 # relative_pose on the contaminated 300x8 pair (0, 1): host-versus-host difference of the robust pose, the error of the
 # UNcontaminated plain pose against the ground truth, and the errors of the robust and of the plain pose on the contaminated
 # pair against the ground truth (all max abs over R_1 and t_1, measured by test_ransac_cpu.py)
@@ -90,6 +93,100 @@ def status_cases():
     pt_ptr, cam, xy, m, pairs = C.case("300x8")
     out["all_replaced"] = (pt_ptr, cam, contaminate(pt_ptr, cam, xy, 0, 1, 2.0)[0], m, pairs[:1], 0)
     return out
+
+
+# The structural limits ("Structural limits"): name: (n_hypotheses, seed, threshold, n_refit)
+LIMITS = {"scan257": (64, 1, THRESHOLD, 16), "refits_1.5e-3": (100, 1, 1.5e-3, 16), "refits_3e-3": (100, 1, 3e-3, 16),
+          "mixed": (64, 1, THRESHOLD, 2), "mixed65": (64, 1, THRESHOLD, 2), "partly_degenerate": (64, 1, THRESHOLD, 2)}
+SCAN_POINTS = 65_700  # 257 chunks of 256 points: k_ransac_scan gives a thread two chunks, thread 128 one, threads 129 .. 255 none
+MAX_HYP = 65536  # csrc/mvba_ransac.h: RS_MAX_HYP
+REFIT_COUNTS = (0, 1, 2, 3, 16)  # the n_refit at which the "refits" cases run on the device
+
+
+def scan_keep():
+    """(SCAN_POINTS,) bool: the points camera 1 of "scan257" keeps.  The 256-point chunks cycle through all kept, none kept,
+    the point at lane 255 alone, and a seeded random half (the last chunk, 164 points, is of the first kind)."""
+    kind = (np.arange(SCAN_POINTS) // 256) % 4
+    lane = np.arange(SCAN_POINTS) % 256
+    half = np.random.default_rng(11).random(SCAN_POINTS) < 0.5
+    return (kind == 0) | ((kind == 2) & (lane == 255)) | ((kind == 3) & half)
+
+
+def chunk_counts(pt_ptr, cam, xy, k, l):
+    """The number of shared points of pair (k, l) in each chunk of 256 points (cnt[] of k_ransac_count)."""
+    n = len(pt_ptr) - 1
+    ids = T.shared(pt_ptr, cam, np.asarray(xy).reshape(-1, 2), k, l)[0]
+    return np.bincount(ids // 256, minlength=-(-n // 256))
+
+
+@functools.lru_cache(maxsize=None)
+def limit_case(name):
+    """(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses, seed, n_refit) of a structural-limit case."""
+    H, seed, thr, n_refit = LIMITS[name]
+    if name == "scan257":
+        sc = make_scene(SCAN_POINTS, 3, vis_p=1.0, project="numpy")
+        keep = np.ones((SCAN_POINTS, 3), bool)
+        keep[:, 1] = scan_keep()
+        keep = keep.reshape(-1)
+        pt_ptr = np.concatenate([[0], np.cumsum(keep.reshape(-1, 3).sum(axis=1))]).astype(np.int64)
+        cam, xy, m = sc.cam_idx[keep], sc.xy.reshape(-1, 2)[keep], 3
+        pairs = np.array([(0, 1), (1, 2), (2, 1)], np.int32)  # ((0, 2) has a distance within 1e-7 of the threshold: left out)
+        xy = contaminate(pt_ptr, cam, xy, 0, 1, 0.3)[0]
+    elif name.startswith("refits"):  # the "2000x3" parity case at 16 refits and tighter thresholds: the inlier set moves
+        pt_ptr, cam, xy, m, pairs = case("2000x3")[:5]
+    elif name == "mixed":  # "300x8" plus an unobserved ninth camera, camera 3 collapsed onto one image point, pair (0, 1) contaminated
+        pt_ptr, cam, _, m = C.no_shared_case()
+        xy = contaminate(pt_ptr, cam, IC.coincident_xy("exact"), 0, 1, 0.3)[0]
+        c = IC.COINCIDENT_CAMERA
+        pairs = np.array([(0, 1), (0, 8), (c, 0), (5, 2), (8, 4), (1, c), (1, 2), (8, c), (c, 8), (6, 7), (c, 5), (4, 6), (7, 8), (2, 0)], np.int32)
+    elif name == "mixed65":  # 1 .. 11 shared points per pair: status 1 WITH shared points next to status 0
+        pt_ptr, cam, xy, m, all_ = C.case("65x12")
+        ns = C.reference("65x12")[2]
+        few, enough = all_[(ns >= 1) & (ns <= 7)], all_[ns >= 8]
+        pairs = np.empty((2 * len(enough), 2), np.int32)
+        pairs[0::2], pairs[1::2] = enough, few[np.linspace(0, len(few) - 1, len(enough)).astype(int)]
+        pairs[3] = pairs[3, ::-1]
+    elif name == "partly_degenerate":  # "300x8" pair (0, 2): 30 % of the shared points are copies of the first, in both images
+        pt_ptr, cam, xy, m, _ = C.case("300x8")
+        xy = np.array(xy, np.float64).reshape(-1, 2)
+        ids = T.shared(pt_ptr, cam, xy, 0, 2)[0]
+        dup = ids[np.random.default_rng(5).random(len(ids)) < 0.3]
+        pt = np.repeat(np.arange(len(pt_ptr) - 1), np.diff(pt_ptr))
+        for c in (0, 2):
+            obs = np.full(len(pt_ptr) - 1, -1)
+            obs[pt[cam == c]] = np.nonzero(cam == c)[0]
+            xy[obs[dup]] = xy[obs[ids[0]]]
+        pairs = np.array([(0, 2)], np.int32)
+    else:
+        raise KeyError(name)
+    xy = np.array(xy, np.float64)
+    xy.setflags(write=False)
+    return pt_ptr, cam, xy, m, pairs, thr, H, seed, n_refit
+
+
+@functools.lru_cache(maxsize=None)
+def limit_reference(name, linear="eigh", n_refit=None):
+    pt_ptr, cam, xy, m, pairs, thr, H, seed, r = limit_case(name)
+    return RR.two_view_robust(pt_ptr, cam, xy, m, pairs, thr, H, seed, r if n_refit is None else n_refit, linear)
+
+
+def max_hyp_sample():
+    """The h whose counts the n_hypotheses = MAX_HYP test compares with the reference: every 97th and the last 64."""
+    return np.union1d(np.arange(0, MAX_HYP, 97), np.arange(MAX_HYP - 64, MAX_HYP))
+
+
+@functools.lru_cache(maxsize=None)
+def max_hyp_reference(linear="eigh"):
+    """(h, counts, margin, pivot) of "300x8" pair (0, 1) at the h of max_hyp_sample()."""
+    pt_ptr, cam, xy, m, pairs, thr, _, seed, _ = case("300x8")
+    _, xk, xl = T.shared(pt_ptr, cam, np.asarray(xy).reshape(-1, 2), 0, 1)
+    hs = max_hyp_sample()
+    return (hs,) + RR.hypothesis_counts(xk, xl, 0, 1, thr, seed, hs, linear)
+
+
+def end_refit(ref, n_refit):
+    """The refit at which each pair of status 0 left the loop: the index of the rejected or failed one, or n_refit."""
+    return np.where(ref["end"] == "exhausted", n_refit, ref["n_accepted"])
 
 
 RS_POINT_BYTES, RS_HYP_BYTES = 48, 160  # csrc/mvba_ransac.h: device bytes per pair and point, per pair and hypothesis

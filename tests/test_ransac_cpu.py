@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import _init_cases as IC
 import _ransac_cases as RC
 import _ransac_ref as RR
 import _twoview_cases as C
@@ -183,3 +184,86 @@ def test_reference_bootstrap_registers_every_camera():
     d = max(np.abs(R - R2).max(), np.abs(t - t2).max(), np.abs(X[ok] - X2[ok]).max())
     print(f"bootstrap: {replaced.sum()} observations replaced, {ok.sum()} points kept, host-vs-host {d:.2e} (recorded {RC.BOOT_HOST_DIFF:.1e})")
     assert 0.5 * RC.BOOT_HOST_DIFF <= d <= RC.BOOT_HOST_DIFF and ok.sum() >= 50
+
+
+def _host_diff(a, b, name, scale_xy):
+    """The eigh-versus-SVD figures of a case: max |dF| inside the 0.5x .. 1x bracket of its record, the Sampson RMS (relative
+    to its own size; to the size of the observations where a minimal set is fitted exactly) and the ratio within the margin."""
+    ok = a["status"] == 0
+    d = np.abs(a["F"][ok] - b["F"][ok]).max()
+    scale = np.where(a["n_inliers"][ok] > 8, a["quality"][ok, 0], scale_xy)
+    rel = (np.abs(a["quality"][ok, 0] - b["quality"][ok, 0]) / scale).max()
+    dr = np.abs(a["quality"][ok, 1] - b["quality"][ok, 1]).max()
+    print(f"{name}: eigh vs SVD max |dF| = {d:.3e} (recorded {RC.RANSAC_HOST_DIFF[name]:.1e}), Sampson RMS relative {rel:.3e}, ratio {dr:.3e}")
+    assert 0.5 * RC.RANSAC_HOST_DIFF[name] <= d <= RC.RANSAC_HOST_DIFF[name]
+    assert rel <= RC.MARGIN * RC.RANSAC_HOST_DIFF[name] and dr <= RC.MARGIN * RC.RANSAC_HOST_DIFF[name]
+
+
+@pytest.mark.parametrize("name", sorted(RC.LIMITS))
+def test_limit_premises_and_host_versus_host_difference(name):
+    """The structural limits of DESIGN.md §17: the premises of exact parity, the host-versus-host difference of the very case,
+    and the structural premise that makes the case worth having -- asserted on the reference alone."""
+    pt_ptr, cam, xy, m, pairs, thr, H, seed, n_refit = RC.limit_case(name)
+    a, b = RC.limit_reference(name), RC.limit_reference(name, "svd")
+    _premises(a, b, name)
+    for key in ("n_accepted", "n_changed", "end"):
+        np.testing.assert_array_equal(a[key], b[key])
+    _host_diff(a, b, name, np.abs(xy).max())
+    st, hc = a["status"], a["hyp_count"]
+    print(f"{name}: status {st.tolist()}, accepted {a['n_accepted'].tolist()}, changed {a['n_changed'].tolist()}, end {a['end'].tolist()}")
+    assert ((a["end"] == "") == (st != 0)).all() and (a["n_changed"] <= a["n_accepted"]).all() and (a["n_accepted"] <= n_refit).all()
+    if name == "scan257":
+        n_ch = -(-(len(pt_ptr) - 1) // 256)
+        assert n_ch == 257 and -(-n_ch // 256) == 2  # per == 2: thread 128 owns one chunk, threads 129 .. 255 none
+        cnt = RC.chunk_counts(pt_ptr, cam, xy, 0, 1)
+        assert len(cnt) == 257 and {0, 1, 256} <= set(cnt.tolist()) and ((cnt > 1) & (cnt < 256)).any()
+        assert cnt[0::4].tolist() == [256] * 64 + [164] and not cnt[1::4].any() and (cnt[2::4] == 1).all() and ((cnt[3::4] > 64) & (cnt[3::4] < 192)).all()
+        assert (a["n_shared"] == cnt.sum()).all() and cnt.sum() % 256 != 0 and (st == 0).all()
+        assert pairs.tolist() == [[0, 1], [1, 2], [2, 1]]
+        # the two orders of a pair: other samples, other count tables, and -- here, at 16 refits -- one inlier set
+        assert not np.array_equal(hc[1], hc[2]) and np.array_equal(a["inlier"][1], a["inlier"][2]) and a["end"].tolist() == ["exhausted"] * 3
+    elif name == "refits_1.5e-3":
+        assert (st == 0).all()
+        assert ((a["n_changed"] >= 3) & (a["end"] == "rejected")).any()  # accepted changes, then a rejection: the other buffer is stale
+        assert len(set(RC.end_refit(a, n_refit).tolist())) == 3  # the pairs of one tile leave RS_ACTIVE at three different refits
+    elif name == "refits_3e-3":
+        assert (st == 0).all() and (a["end"] == "exhausted").any() and (a["end"] == "rejected").any()
+        assert ((a["end"] == "exhausted") & (a["n_changed"] >= 1) & (a["n_changed"] < a["n_accepted"])).any()  # a fixed point, kept to the end
+    elif name == "mixed":
+        assert st.tolist() == [0, 1, 2, 0, 1, 2, 0, 1, 1, 0, 2, 0, 1, 0] and not a["n_shared"][st == 1].any()
+        c = IC.COINCIDENT_CAMERA
+        assert all(s == (1 if 8 in p else (2 if c in p else 0)) for p, s in zip(pairs.tolist(), st)) and [c, 0] in pairs.tolist() and [1, c] in pairs.tolist()
+        assert (pairs[:, 0] > pairs[:, 1]).any() and (hc[st != 0] == -1).all() and (hc[st == 0] >= 8).all()
+    elif name == "mixed65":
+        ns = a["n_shared"]
+        assert st.tolist() == [0, 1] * (len(st) // 2) and {1, 7} <= set(ns[1::2].tolist()) <= set(range(1, 8)) and (ns[0::2] >= 8).all()
+    elif name == "partly_degenerate":
+        assert st.tolist() == [0] and (hc == -1).any() and (hc >= 8).any() and a["best"][0] > 0 and hc[0, 0] == -1
+        piv = a["pivot"][0]
+        print(f"{name}: {(hc == -1).sum()} degenerate (lambda_2 / lambda_max <= {piv[hc[0] == -1].max():.1e}), {(hc >= 8).sum()} good (>= {piv[hc[0] >= 8].min():.1e}), best {a['best'][0]}")
+    if name.startswith("refits"):  # the shorter loops the GPU test runs are prefixes of this one: their premises, their figures
+        for r in RC.REFIT_COUNTS[:-1]:
+            ar, br = RC.limit_reference(name, "eigh", r), RC.limit_reference(name, "svd", r)
+            _premises(ar, br, f"{name}, n_refit = {r}")
+            np.testing.assert_array_equal(ar["n_accepted"], np.minimum(a["n_accepted"], r))
+            np.testing.assert_array_equal(ar["end"], np.where(RC.end_refit(a, n_refit) >= r, "exhausted", a["end"]))
+
+
+def test_solver_failure_in_a_refit_is_not_reached():
+    """No case of the suite ends a refit loop by a failure of the eigen-problem (DESIGN.md §17 says why none was built)."""
+    for name in sorted(RC.LIMITS):
+        assert "solver" not in RC.limit_reference(name)["end"].tolist(), name
+
+
+def test_maximum_hypothesis_count_premises():
+    """n_hypotheses = 65 536 on "300x8" pair (0, 1): the hypotheses the GPU test compares meet the premises of exact counts, and
+    the helper that evaluates single h is the table of the full call."""
+    (hs, ca, ma, pa), (_, cb, mb, pb) = RC.max_hyp_reference(), RC.max_hyp_reference("svd")
+    assert hs[1] == 97 and hs[-64] == RC.MAX_HYP - 64 and hs[-1] == RC.MAX_HYP - 1 and len(hs) == 676 + 64 - 1  # (65 475 is in both)
+    np.testing.assert_array_equal(ca, cb)
+    piv = np.concatenate([pa, pb])
+    print(f"H = 65536 sample: smallest |d^2 / thr^2 - 1| {min(ma, mb):.2e}, lambda_2 / lambda_max in {piv.min():.2e} .. {piv.max():.2e}")
+    assert min(ma, mb) >= 1e-7 and not ((piv > 1e-14) & (piv < 1e-10)).any() and (ca >= 8).all()
+    full = RC.reference("300x8")["hyp_count"][0]  # H = 512
+    low = hs[hs < 512]
+    np.testing.assert_array_equal(ca[: len(low)], full[low])
