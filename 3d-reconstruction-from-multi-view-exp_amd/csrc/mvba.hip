@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "mvba_common.h"
+#include "mvba_host.h"
 
 namespace mvba {
 thread_local std::string g_err;
@@ -2888,52 +2889,6 @@ __global__ void k_idx_interleave(long long n_steps, const int *__restrict__ st_k
 }  // namespace
 
 // ------------------------------------------------------------------ host side
-// Device buffers with one owner.  Whatever alloc() hands out is freed when the owner goes: a DevBufs on the stack holds the
-// temporaries of one call (every early return frees them), the one inside mvba_handle holds the engine's buffers (mvba_destroy
-// frees them all: a new member of mvba_handle needs no second edit).  release() frees one buffer early; adopt() moves one over
-// from another owner.
-struct DevBufs {
-  std::vector<void *> bufs;
-  DevBufs() = default;
-  DevBufs(const DevBufs &) = delete;
-  DevBufs &operator=(const DevBufs &) = delete;
-  ~DevBufs() { release_all(); }
-  template <typename T>
-  int alloc(T **p, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    const hipError_t e = hipMalloc((void **)p, bytes);
-    if (e != hipSuccess) {  // say how much was asked for and how much there is: "out of memory" alone does not tell a scene from a knob
-      size_t fr = 0, tot = 0;
-      hipMemGetInfo(&fr, &tot);
-      *p = nullptr;
-      return fail(MVBA_ERR_HIP, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e) + " (" + std::to_string(fr >> 20) +
-                                    " MiB free of " + std::to_string(tot >> 20) + ")");
-    }
-    bufs.push_back(*p);
-    return MVBA_OK;
-  }
-  void own(void *q) { bufs.push_back(q); }  // a buffer the caller allocated itself
-  bool forget(void *q) {
-    auto it = std::find(bufs.begin(), bufs.end(), q);
-    if (it == bufs.end()) return false;
-    bufs.erase(it);
-    return true;
-  }
-  template <typename T>
-  void release(T *&p) {
-    if (p && forget(p)) hipFree(p);
-    p = nullptr;
-  }
-  template <typename T>
-  void adopt(DevBufs &from, T *p) {
-    if (p && from.forget(p)) bufs.push_back(p);
-  }
-  void release_all() {
-    for (void *q : bufs) hipFree(q);
-    bufs.clear();
-  }
-};
-
 enum { SCHUR_PAIRS = 1, SCHUR_SLOTS = 2, SCHUR_DENSE = 3 };  // (0 was round 1's camera-strip form: the values are mvba_get_info's)
 struct mvba_handle {
   int device = 0;

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "mvba_common.h"
+#include "mvba_host.h"
 
 using namespace mvba;
 
@@ -2188,6 +2189,7 @@ struct mvsvd_handle {
   long long max_rows = 0, n_rows = 0, base_rows = 0;  // rows of the loaded matrix (dW) / of the resident base (dX)
   hipStream_t st = nullptr;
   hipEvent_t ev[8] = {};
+  DevBufs mem;  // every device buffer below (h->mem.alloc): freed by mvsvd_destroy
   void *dW = nullptr, *dS = nullptr;
   double *dG = nullptr, *dV = nullptr, *dV1 = nullptr, *dsum = nullptr, *dMr = nullptr, *dmu = nullptr, *dpart = nullptr, *dpart2 = nullptr, *dB = nullptr;
   int *dsw = nullptr;
@@ -2256,6 +2258,80 @@ int chunks_for(long long n_rows, int n) {
                                                          n_tiles <= 2 ? 2048 : std::max(8, 4096 / n_pairs)));
 }
 
+// f(T()) with T the workspace's element type (or that of a caller's array)
+template <typename F>
+auto with_dtype(int dtype, F &&f) { return dtype == 0 ? f(float()) : f(double()); }
+size_t el_bytes(const mvsvd_handle *h) { return h->dtype ? 8 : 4; }
+
+// Device memory.  mvsvd_create allocates what every factorisation needs; the rest exists from its first use on (what is resident
+// when is part of the interface: a workspace that never takes a base pays for none).  A fixed-size buffer goes through alloc_once,
+// its size written once, below; the two that grow (dS with rank_cap, ddep with ddep_n) through regrow, which leaves a null pointer
+// and capacity 0 behind a failed allocation, so that the next call allocates again instead of launching onto the freed buffer.
+template <typename P>
+int alloc_once(mvsvd_handle *h, P *&p, size_t bytes) { return p ? MVBA_OK : h->mem.alloc((char **)&p, bytes); }
+template <typename P, typename C>
+int regrow(mvsvd_handle *h, P *&p, C &cap, C want, size_t bytes) {
+  if (cap >= want) return MVBA_OK;
+  MVBA_HIP(hipStreamSynchronize(h->st));
+  h->mem.release(p);
+  cap = 0;
+  if (int rc = h->mem.alloc((char **)&p, bytes)) return rc;
+  cap = want;
+  return MVBA_OK;
+}
+int need_refine_b(mvsvd_handle *h) { return alloc_once(h, h->dB, sizeof(double) * (size_t)h->max_rows * h->n); }
+int need_stage(mvsvd_handle *h) { return alloc_once(h, h->dstage, 16 * (size_t)h->max_rows); }
+int need_base(mvsvd_handle *h) { return alloc_once(h, h->dX, el_bytes(h) * (size_t)h->max_rows * h->n); }
+int need_depths(mvsvd_handle *h) { return alloc_once(h, h->dz, el_bytes(h) * (size_t)h->max_rows * h->n); }  // (room for any grouping: a later call may ask for a finer one)
+int need_depth_flags(mvsvd_handle *h) { return alloc_once(h, h->ddflag, sizeof(int) * (size_t)(h->n / 3 + 1)); }
+int need_rank(mvsvd_handle *h, int n_rank) { return regrow(h, h->dS, h->rank_cap, n_rank, el_bytes(h) * (size_t)h->max_rows * n_rank); }
+constexpr int GS_BLOCKS = 512;
+// dgs: the column groups' partial sums [GS_BLOCKS][gs_stride], and behind them their scales -> *cs
+int group_scales(mvsvd_handle *h, double **cs) {
+  const size_t gs_stride = (size_t)std::max(256, h->n);  // (room for the finest grouping: one group per column)
+  if (int rc = alloc_once(h, h->dgs, sizeof(double) * (size_t)(GS_BLOCKS + 1) * gs_stride)) return rc;
+  *cs = h->dgs + (size_t)GS_BLOCKS * gs_stride;
+  return MVBA_OK;
+}
+
+// timings[0 .. 5] of a call from its events: slot s is ev[p[s][0]] .. ev[p[s][1]] in ms, 0 where the caller names no pair (-1).
+// What a slot means is the interface's (include/mvba.h); which pass of a route goes into it is the caller's to say.
+double event_ms(mvsvd_handle *h, int a, int b) {
+  float ms = 0.f;
+  if (a >= 0) hipEventElapsedTime(&ms, h->ev[a], h->ev[b]);
+  return ms;
+}
+void read_timings(mvsvd_handle *h, double *timings, const int (&p)[6][2]) {
+  for (int s = 0; s < 6; ++s) timings[s] = event_ms(h, p[s][0], p[s][1]);
+}
+double jacobi_sweeps(mvsvd_handle *h) {  // of the last pass
+  int sw = 0;
+  hipMemcpy(&sw, h->dsw, sizeof(int), hipMemcpyDeviceToHost);
+  return sw;
+}
+
+// What the workspace holds, in one place each.  dW: a matrix a factorisation may run on (`loaded`); dX: the base of the depth
+// loops; depth_group / cs_valid: a depth loop and its norm-2 scales, which belong to one base; wide_warm / wide_have_q: the block
+// iteration may start from the previous factorisation's vectors, which holds only between re-weightings of one base.
+void matrix_replaced(mvsvd_handle *h, long long n_rows) {  // mvsvd_load, mvsvd_load_images
+  h->n_rows = n_rows;
+  h->loaded = true;
+  h->wide_warm = h->wide_have_q = false;  // a new matrix: the block iteration starts from its fixed block
+}
+void base_replaced(mvsvd_handle *h, long long n_rows) {  // mvsvd_load_base, mvsvd_load_base_images
+  h->base_rows = n_rows;
+  h->base_loaded = true;
+  h->depth_group = 0;  // a new base ends a depth loop: its depths and norm-2 scales belong to the old one
+  h->cs_valid = false;
+  h->wide_warm = h->wide_have_q = false;
+  h->loaded = false;  // dW holds nothing derived from this base yet (or was the staging buffer)
+}
+void base_scaled_into_w(mvsvd_handle *h) {  // scale_base_into_w
+  h->n_rows = h->base_rows;  // dW now holds the re-weighted base (a mvsvd_load in between may have changed n_rows)
+  h->loaded = true;
+  h->wide_warm = true;  // (the block iteration may start from the previous factorisation's vectors: the same base, other depths)
+}
+
 template <typename T>
 int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means, double *timings);
 
@@ -2282,7 +2358,7 @@ int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means,
   launch_jacobi(h, refine ? h->dV1 : h->dV, sizeof(T) == 8 ? 1e-15 : 1e-11);
   hipEventRecord(h->ev[3], st);
   if (refine) {
-    if (!h->dB) MVBA_HIP(hipMalloc((void **)&h->dB, sizeof(double) * (size_t)h->max_rows * n));
+    if (int rc = need_refine_b(h)) return rc;
     if (n <= 32 && n % 2 == 0 && (n * sizeof(T)) % 16 == 0 && n_rows >= 4096) {  // tall and narrow: the streaming form
       const int rgrid = (int)std::max<long long>(1, std::min<long long>(6 * 256, (n_rows + GRAM_ROWS - 1) / GRAM_ROWS));
       const size_t rlds = (size_t)GRAM_ROWS * n * sizeof(T);
@@ -2301,33 +2377,15 @@ int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means,
   MVBA_HIP(hipMemcpyAsync(hV.data(), h->dV, sizeof(double) * nn, hipMemcpyDeviceToHost, st));
   if (center) MVBA_HIP(hipMemcpyAsync(hmu.data(), h->dmu, sizeof(double) * n, hipMemcpyDeviceToHost, st));
   MVBA_HIP(hipStreamSynchronize(st));
-  for (int i = 0; i < n; ++i)  // (np.linalg.svd raises LinAlgError("SVD did not converge") on such input; max() and sort() below would swallow the NaN)
-    if (!std::isfinite(hG[(size_t)i * n + i])) return fail(MVBA_ERR_SINGULAR, "SVD did not converge (non-finite values in the measurement matrix)");
-  std::vector<int> order(n);
-  std::iota(order.begin(), order.end(), 0);
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return hG[(size_t)a * n + a] > hG[(size_t)b * n + b]; });
-  std::vector<double> Mr((size_t)n * n_rank);
-  for (int i = 0; i < n; ++i) sigma[i] = (T)std::sqrt(std::max(0.0, hG[(size_t)order[i] * n + order[i]]));
-  for (int i = 0; i < n_rank; ++i) {
-    const int col = order[i];
-    int big = 0;
-    for (int c = 1; c < n; ++c)
-      if (std::fabs(hV[(size_t)c * n + col]) > std::fabs(hV[(size_t)big * n + col])) big = c;
-    const double sg = hV[(size_t)big * n + col] < 0.0 ? -1.0 : 1.0;  // largest component positive
-    for (int c = 0; c < n; ++c) {
-      Mr[(size_t)c * n_rank + i] = sg * hV[(size_t)c * n + col];
-      M[(size_t)c * n_rank + i] = (T)Mr[(size_t)c * n_rank + i];
-    }
-  }
+  Basis basis;
+  if (int rc = select_basis(hG.data(), hV.data(), n, n, n_rank, basis)) return rc;
+  for (int i = 0; i < n; ++i) sigma[i] = (T)std::sqrt(std::max(0.0, hG[(size_t)basis.order[i] * n + basis.order[i]]));
+  for (int i = 0; i < n_rank; ++i)
+    for (int c = 0; c < n; ++c) M[(size_t)c * n_rank + i] = (T)basis_at(basis, hV.data(), n, c, i);
   if (means)
     for (int c = 0; c < n; ++c) means[c] = (T)hmu[c];
   // S = M^T W in groups of (up to) 4 basis vectors per pass over W
-  if (n_rank > h->rank_cap) {
-    if (h->dS) MVBA_HIP(hipFree(h->dS));
-    h->dS = nullptr;
-    MVBA_HIP(hipMalloc(&h->dS, sizeof(T) * (size_t)h->max_rows * n_rank));
-    h->rank_cap = n_rank;
-  }
+  if (int rc = need_rank(h, n_rank)) return rc;
   hipEventRecord(h->ev[4], st);
   const int pgrid = (int)std::max<long long>(1, std::min<long long>(4096, (n_rows + 255) / 256));
   const int ldt = std::min(n, PC) | 1;
@@ -2335,8 +2393,7 @@ int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means,
   std::vector<double> Mg((size_t)n * 4);
   for (int g0 = 0; g0 < n_rank; g0 += 4) {
     const int rg = std::min(4, n_rank - g0);
-    for (int c = 0; c < n; ++c)
-      for (int i = 0; i < 4; ++i) Mg[(size_t)c * 4 + i] = i < rg ? Mr[(size_t)c * n_rank + g0 + i] : 0.0;  // [n][4], zero padded
+    basis_block(basis, hV.data(), n, n, g0, n_rank, Mg.data());
     MVBA_HIP(hipMemcpyAsync(h->dMr, Mg.data(), sizeof(double) * (size_t)n * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_project<T>, dim3(pgrid), dim3(256), plds, st, dW, n_rows, n, rg, h->dMr, mu, (T *)h->dS + (size_t)g0 * n_rows);
     MVBA_HIP(hipStreamSynchronize(st));  // Mg is reused by the next group
@@ -2345,17 +2402,10 @@ int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means,
   if (S) MVBA_HIP(hipMemcpyAsync(S, h->dS, sizeof(T) * (size_t)n_rows * n_rank, hipMemcpyDeviceToHost, st));  // (null: S stays on the device)
   MVBA_HIP(hipStreamSynchronize(st));
   MVBA_HIP(hipGetLastError());
-  if (timings) {
-    float ms;
-    timings[0] = h->h2d_ms;                                                   // H2D of the last load
-    hipEventElapsedTime(&ms, h->ev[1], h->ev[2]); timings[1] = ms;            // means + Gram
-    hipEventElapsedTime(&ms, h->ev[2], h->ev[3]); timings[2] = ms;            // Jacobi (first pass)
-    hipEventElapsedTime(&ms, h->ev[4], h->ev[5]); timings[3] = ms;            // projection
-    int sw = 0;
-    hipMemcpy(&sw, h->dsw, sizeof(int), hipMemcpyDeviceToHost);
-    timings[4] = sw;                                                          // Jacobi sweeps (last pass)
-    if (refine) { hipEventElapsedTime(&ms, h->ev[3], h->ev[4]); timings[5] = ms; }  // refinement pass (rotate, Gram, Jacobi, V1 V2)
-    else timings[5] = 0.0;
+  if (timings) {  // means + Gram | Jacobi (first pass) | projection | refinement pass (rotate, Gram, Jacobi, V1 V2)
+    read_timings(h, timings, {{-1, -1}, {1, 2}, {2, 3}, {4, 5}, {-1, -1}, {refine ? 3 : -1, 4}});
+    timings[0] = h->h2d_ms;  // H2D of the last load
+    timings[4] = jacobi_sweeps(h);
   }
   return MVBA_OK;
 }
@@ -2440,8 +2490,7 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
         return fail(MVBA_ERR_SINGULAR, "SVD did not converge (non-finite values in the measurement matrix)");
     }
     int order[WB];
-    std::iota(order, order + WB, 0);
-    std::sort(order, order + WB, [&](int a, int b) { return theta[a] > theta[b]; });
+    descending_order(theta, 1, WB, order);
     const double tmax = std::max(theta[order[0]], 0.0);
     worst = rel = 0.0;
     for (int i = 0; i < n_rank; ++i) {
@@ -2473,34 +2522,23 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
   MVBA_HIP(hipMemcpyAsync(hQ.data(), h->dQ, sizeof(double) * (size_t)n * WB, hipMemcpyDeviceToHost, st));
   if (center) MVBA_HIP(hipMemcpyAsync(hmu.data(), h->dmu, sizeof(double) * n, hipMemcpyDeviceToHost, st));
   MVBA_HIP(hipStreamSynchronize(st));
-  int order[WB];
-  std::iota(order, order + WB, 0);
-  std::sort(order, order + WB, [&](int a, int b) { return hH[(size_t)a * WB + a] > hH[(size_t)b * WB + b]; });
+  Basis basis;
+  if (int rc = select_basis(hH.data(), hQ.data(), WB, n, n_rank, basis)) return rc;
+  const int *order = basis.order.data();
   for (int i = 0; i < n; ++i) sigma[i] = i < WB ? (T)std::sqrt(std::max(0.0, hH[(size_t)order[i] * WB + order[i]])) : (T)NAN;
   int hcol[WB] = {};
   double hsgn[WB] = {};
   for (int i = 0; i < n_rank; ++i) {
-    const int col = order[i];
-    int big = 0;
-    for (int c = 1; c < n; ++c)
-      if (std::fabs(hQ[(size_t)c * WB + col]) > std::fabs(hQ[(size_t)big * WB + col])) big = c;
-    const double sg = hQ[(size_t)big * WB + col] < 0.0 ? -1.0 : 1.0;  // largest component positive
-    for (int c = 0; c < n; ++c) M[(size_t)c * n_rank + i] = (T)(sg * hQ[(size_t)c * WB + col]);
-    hcol[i] = col;
-    hsgn[i] = sg;
+    for (int c = 0; c < n; ++c) M[(size_t)c * n_rank + i] = (T)basis_at(basis, hQ.data(), WB, c, i);
+    hcol[i] = order[i];
+    hsgn[i] = basis.sign[i];
   }
   if (means)
     for (int c = 0; c < n; ++c) means[c] = (T)hmu[c];
-  if (n_rank > h->rank_cap) {
-    if (h->dS) MVBA_HIP(hipFree(h->dS));
-    h->dS = nullptr;
-    MVBA_HIP(hipMalloc(&h->dS, sizeof(T) * (size_t)h->max_rows * n_rank));
-    h->rank_cap = n_rank;
-  }
+  if (int rc = need_rank(h, n_rank)) return rc;
   hipEventRecord(h->ev[4], st);
-  std::vector<double> Mg((size_t)n * 4, 0.0);  // the depth loops read the leading basis vectors as [n][4] from dMr, like after run()
-  for (int c = 0; c < n; ++c)
-    for (int i = 0; i < std::min(4, n_rank); ++i) Mg[(size_t)c * 4 + i] = hsgn[i] * hQ[(size_t)c * WB + hcol[i]];
+  std::vector<double> Mg((size_t)n * 4);  // the depth loops read the leading basis vectors as [n][4] from dMr, like after run()
+  basis_block(basis, hQ.data(), WB, n, 0, n_rank, Mg.data());
   MVBA_HIP(hipMemcpyAsync(h->dMr, Mg.data(), sizeof(double) * (size_t)n * 4, hipMemcpyHostToDevice, st));
   MVBA_HIP(hipMemcpyAsync(dcol, hcol, sizeof(int) * WB, hipMemcpyHostToDevice, st));
   MVBA_HIP(hipMemcpyAsync(dsgn, hsgn, sizeof(double) * WB, hipMemcpyHostToDevice, st));
@@ -2509,51 +2547,34 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
   if (S) MVBA_HIP(hipMemcpyAsync(S, h->dS, sizeof(T) * (size_t)N * n_rank, hipMemcpyDeviceToHost, st));  // (null: S stays on the device)
   MVBA_HIP(hipStreamSynchronize(st));  // (hcol / hsgn are read by the copies above)
   MVBA_HIP(hipGetLastError());
-  if (timings) {
-    float ms;
+  if (timings) {  // means | the iteration (in the eigen-solver's slot) | S out of B | final pass
+    read_timings(h, timings, {{-1, -1}, {1, 2}, {2, 3}, {4, 5}, {-1, -1}, {3, 4}});
     timings[0] = h->h2d_ms;
-    hipEventElapsedTime(&ms, h->ev[1], h->ev[2]); timings[1] = ms;  // means
-    hipEventElapsedTime(&ms, h->ev[2], h->ev[3]); timings[2] = ms;  // the iteration (in the eigen-solver's slot)
-    hipEventElapsedTime(&ms, h->ev[4], h->ev[5]); timings[3] = ms;  // S out of B
-    timings[4] = it;                                                // iterations (in the sweeps' slot)
-    hipEventElapsedTime(&ms, h->ev[3], h->ev[4]); timings[5] = ms;  // final pass
+    timings[4] = it;  // iterations (in the sweeps' slot)
   }
   return MVBA_OK;
 }
 
-constexpr int GS_BLOCKS = 512;
-
 // dW <- the resident base re-weighted by the depths in dz and normalised (see mvsvd_run_scaled)
 int scale_base_into_w(mvsvd_handle *h, int group, int norm) {
   const int ng = h->n / group;
-  const size_t gs_stride = (size_t)std::max(256, h->n);  // (room for the finest grouping: one group per column)
-  if (!h->dgs) MVBA_HIP(hipMalloc((void **)&h->dgs, sizeof(double) * (size_t)(GS_BLOCKS + 1) * gs_stride));
-  double *cs = h->dgs + (size_t)GS_BLOCKS * gs_stride;
+  double *cs;
+  if (int rc = group_scales(h, &cs)) return rc;
   const int sgrid = (int)std::max<long long>(1, std::min<long long>(4096, (h->base_rows + 255) / 256));
   const int gblocks = (int)std::max<long long>(1, std::min<long long>(GS_BLOCKS, h->base_rows / 64 + 1));
-  if (h->dtype == 0) {
+  with_dtype(h->dtype, [&](auto tag) {
+    using T = decltype(tag);
     if (norm == 2) {
-      hipLaunchKernelGGL(k_group_sumsq<float>, dim3(gblocks), dim3(256), 0, h->st, (const float *)h->dX, (const float *)h->dz, h->base_rows, h->n, group, h->dgs);
+      hipLaunchKernelGGL(k_group_sumsq<T>, dim3(gblocks), dim3(256), 0, h->st, (const T *)h->dX, (const T *)h->dz, h->base_rows, h->n, group, h->dgs);
       hipLaunchKernelGGL(k_group_scale, dim3((ng + 3) / 4), dim3(256), 0, h->st, h->dgs, gblocks, ng, cs);
     }
-    if (tile_fits<float>(h->n + ng))
-      hipLaunchKernelGGL(k_scale_rows_tiled<float>, dim3(sgrid), dim3(256), sizeof(float) * 4 * 64 * (size_t)((h->n + ng) | 1), h->st, (const float *)h->dX, (const float *)h->dz, h->base_rows, h->n, group, norm, cs, (float *)h->dW);
+    if (tile_fits<T>(h->n + ng))
+      hipLaunchKernelGGL(k_scale_rows_tiled<T>, dim3(sgrid), dim3(256), sizeof(T) * 4 * 64 * (size_t)((h->n + ng) | 1), h->st, (const T *)h->dX, (const T *)h->dz, h->base_rows, h->n, group, norm, cs, (T *)h->dW);
     else
-      hipLaunchKernelGGL(k_scale_rows_wide<float>, dim3(sgrid), dim3(256), 0, h->st, (const float *)h->dX, (const float *)h->dz, h->base_rows, h->n, group, norm, cs, (float *)h->dW);
-  } else {
-    if (norm == 2) {
-      hipLaunchKernelGGL(k_group_sumsq<double>, dim3(gblocks), dim3(256), 0, h->st, (const double *)h->dX, (const double *)h->dz, h->base_rows, h->n, group, h->dgs);
-      hipLaunchKernelGGL(k_group_scale, dim3((ng + 3) / 4), dim3(256), 0, h->st, h->dgs, gblocks, ng, cs);
-    }
-    if (tile_fits<double>(h->n + ng))
-      hipLaunchKernelGGL(k_scale_rows_tiled<double>, dim3(sgrid), dim3(256), sizeof(double) * 4 * 64 * (size_t)((h->n + ng) | 1), h->st, (const double *)h->dX, (const double *)h->dz, h->base_rows, h->n, group, norm, cs, (double *)h->dW);
-    else
-      hipLaunchKernelGGL(k_scale_rows_wide<double>, dim3(sgrid), dim3(256), 0, h->st, (const double *)h->dX, (const double *)h->dz, h->base_rows, h->n, group, norm, cs, (double *)h->dW);
-  }
+      hipLaunchKernelGGL(k_scale_rows_wide<T>, dim3(sgrid), dim3(256), 0, h->st, (const T *)h->dX, (const T *)h->dz, h->base_rows, h->n, group, norm, cs, (T *)h->dW);
+  });
   MVBA_HIP(hipGetLastError());
-  h->n_rows = h->base_rows;  // dW now holds the re-weighted base (a mvsvd_load in between may have changed n_rows)
-  h->loaded = true;
-  h->wide_warm = true;  // (the block iteration may start from the previous factorisation's vectors: the same base, other depths)
+  base_scaled_into_w(h);
   return MVBA_OK;
 }
 
@@ -2563,18 +2584,15 @@ constexpr size_t DEPTH_LDS_MAX = 148 * 1024;  // dynamic LDS the depth kernels m
 // rows k_dual_gram stages per pass: [rows][3 m | 1] normalised observations + [rows][4] right singular vectors in LDS
 inline int dual_gram_rows(int m) { return (int)std::max<size_t>(1, std::min<size_t>(DG_ROWS_MAX, DEPTH_LDS_MAX / (sizeof(double) * (size_t)(((3 * m) | 1) + 4)))); }
 
-// The depth iteration's scratch (ddep) of at least `need` doubles.  The two routes lay it out differently and one handle may take
-// both (a new base on the other side of the fused route's row threshold, MVSVD_DEPTH_UNFUSED read per call): it grows to the larger.
-int depth_scratch(mvsvd_handle *h, size_t need) {
-  if (h->ddep_n >= need) return MVBA_OK;
-  if (h->ddep) {
-    MVBA_HIP(hipStreamSynchronize(h->st));
-    MVBA_HIP(hipFree(h->ddep));
-    h->ddep = nullptr;
-    h->ddep_n = 0;
-  }
-  MVBA_HIP(hipMalloc((void **)&h->ddep, sizeof(double) * need));
-  h->ddep_n = need;
+// The depth iteration's scratch (ddep: DepthScratch) with `own` doubles behind the common part, and the dual method's flags.  The
+// two routes differ in `own` and one handle may take both (a new base on the other side of the fused route's row threshold,
+// MVSVD_DEPTH_UNFUSED read per call): ddep grows to the larger.
+int depth_scratch(mvsvd_handle *h, size_t own, DepthScratch *out) {
+  const int m = h->n / 3;
+  const size_t need = DepthScratch::prefix(DEPTH_BLOCKS, m) + own;
+  if (int rc = regrow(h, h->ddep, h->ddep_n, need, sizeof(double) * need)) return rc;
+  if (int rc = need_depth_flags(h)) return rc;
+  *out = DepthScratch(h->ddep, DEPTH_BLOCKS, m);
   return MVBA_OK;
 }
 
@@ -2587,16 +2605,13 @@ int depth_step(mvsvd_handle *h, int method, double f0, double *E, double *timing
   std::vector<T> M((size_t)n * 4), sigma(n);
   rc = run<T>(h, 4, 0, M.data(), sigma.data(), (T *)nullptr, (T *)nullptr, timings);  // dMr = M, dS = S stay on the device
   if (rc) return rc;
-  // ddep: [DEPTH_BLOCKS] error partials | [1] error | G12 [m][144] | V12 [m][144] | colsum [m][12] | w12 [m][12] | dual partials
   const int dsplit = dual_gram_split(m);  // thread groups of k_dual_gram, each with its own partial
   const int dual_blocks = std::max(64, std::min(DEPTH_BLOCKS, 95000 / m / dsplit));  // (blocks x groups partials of 14 m x 6 doubles: <= ~64 MB)
   const long long rpb = (rows + dual_blocks - 1) / dual_blocks;
   const int gblocks = (int)((rows + rpb - 1) / rpb);
-  const size_t need = (size_t)DEPTH_BLOCKS + 8 + (size_t)m * (144 + 144 + 12 + 12) + (size_t)dual_blocks * dsplit * 14 * m * 6;
-  if ((rc = depth_scratch(h, need))) return rc;
-  if (!h->ddflag) MVBA_HIP(hipMalloc((void **)&h->ddflag, sizeof(int) * (size_t)(m + 1)));
-  double *Epart = h->ddep, *Eout = Epart + DEPTH_BLOCKS, *G12 = Eout + 8, *V12 = G12 + (size_t)m * 144, *colsum = V12 + (size_t)m * 144,
-         *w12 = colsum + (size_t)m * 12, *gpart = w12 + (size_t)m * 12;
+  DepthScratch d;
+  if ((rc = depth_scratch(h, (size_t)dual_blocks * dsplit * 14 * m * 6, &d))) return rc;
+  double *Epart = d.Epart, *Eout = d.Eout, *G12 = d.G12, *V12 = d.V12, *colsum = d.colsum, *w12 = d.w12, *gpart = d.own;  // (own: the dual partials)
   const int pgrid = (int)std::max<long long>(1, std::min<long long>(DEPTH_BLOCKS, (rows + 255) / 256));
   const bool tiled = tile_fits<T>(n + m) && 24 * m * sizeof(double) <= 24 * 1024;  // the rows go through LDS tiles (coalesced) while they fit
   const size_t tile_bytes = sizeof(T) * 4 * 64 * (size_t)((n + m) | 1) + 16;
@@ -2637,11 +2652,7 @@ int depth_step(mvsvd_handle *h, int method, double f0, double *E, double *timing
   if (method == 2) MVBA_HIP(hipMemcpyAsync(&fl, h->ddflag, sizeof(int), hipMemcpyDeviceToHost, st));
   MVBA_HIP(hipStreamSynchronize(st));
   if (fl) return fail(MVBA_ERR_SINGULAR, "depth iteration: an image's 12 x 12 companion matrix has no positive eigenvalue");
-  if (timings) {
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, h->ev[6], h->ev[7]);
-    timings[0] = ms;  // (no upload in a depth step: slot 0 carries the depth-update kernels instead)
-  }
+  if (timings) timings[0] = event_ms(h, 6, 7);  // (no upload in a depth step: slot 0 carries the depth-update kernels instead)
   return MVBA_OK;
 }
 // The iteration without the re-weighted matrix (see k_gram_xz): fp64, n = 3 m <= 32 columns, n even.
@@ -2686,15 +2697,12 @@ int depth_step_fused(mvsvd_handle *h, int method, double f0, double *E, double *
   hipStream_t st = h->st;
   const double *dX = (const double *)h->dX;
   double *dz = (double *)h->dz;
-  const size_t gs_stride = (size_t)std::max(256, h->n);  // (room for the finest grouping: one group per column)
-  if (!h->dgs) MVBA_HIP(hipMalloc((void **)&h->dgs, sizeof(double) * (size_t)(GS_BLOCKS + 1) * gs_stride));
-  double *cs = h->dgs + (size_t)GS_BLOCKS * gs_stride;
+  double *cs;
+  if (int rc = group_scales(h, &cs)) return rc;
   const size_t dual_part = (size_t)512 * 4 * m * 256;  // k_dual_gram_mfma: a 16 x 16 tile per wave and image, at most 512 workgroups
-  const size_t need = (size_t)DEPTH_BLOCKS + 8 + (size_t)m * (144 + 144 + 12 + 12) + dual_part + (size_t)FZ_MAXM * DEPTH_BLOCKS;
-  if (int rc = depth_scratch(h, need)) return rc;
-  if (!h->ddflag) MVBA_HIP(hipMalloc((void **)&h->ddflag, sizeof(int) * (size_t)(m + 1)));
-  double *Epart = h->ddep, *Eout = Epart + DEPTH_BLOCKS, *G12 = Eout + 8, *V12 = G12 + (size_t)m * 144, *colsum = V12 + (size_t)m * 144,
-         *w12 = colsum + (size_t)m * 12, *gpart = w12 + (size_t)m * 12, *gsum = gpart + dual_part;
+  DepthScratch d;
+  if (int rc = depth_scratch(h, dual_part + (size_t)FZ_MAXM * DEPTH_BLOCKS, &d)) return rc;
+  double *Epart = d.Epart, *Eout = d.Eout, *G12 = d.G12, *V12 = d.V12, *colsum = d.colsum, *w12 = d.w12, *gpart = d.own, *gsum = gpart + dual_part;
   if (method == 2 && !h->cs_valid) {  // the per-image scales of the depths the loop holds (first dual step, or after primary steps)
     const int gb = (int)std::max<long long>(1, std::min<long long>(GS_BLOCKS, rows / 64 + 1));
     hipLaunchKernelGGL(k_group_sumsq<double>, dim3(gb), dim3(256), 0, st, dX, (const double *)dz, rows, n, 3, h->dgs);
@@ -2711,26 +2719,20 @@ int depth_step_fused(mvsvd_handle *h, int method, double f0, double *E, double *
   launch_jacobi(h, h->dMr, 1e-15);
   hipLaunchKernelGGL(k_rotate<double>, dim3((n + 63) / 64, (n + 63) / 64), dim3(256), 0, st, h->dV1, (long long)n, n, (const double *)nullptr, h->dMr, h->dV);
   hipEventRecord(h->ev[4], st);
-  // eigenvalues -> host, sort, the rank-4 basis with the same deterministic sign as mvsvd_run
+  // eigenvalues -> host, sort, the rank-4 basis (select_basis, as mvsvd_run)
   std::vector<double> hG(nn), hV(nn), Mg((size_t)n * 4);
   MVBA_HIP(hipMemcpyAsync(hG.data(), h->dG, sizeof(double) * nn, hipMemcpyDeviceToHost, st));
   MVBA_HIP(hipMemcpyAsync(hV.data(), h->dV, sizeof(double) * nn, hipMemcpyDeviceToHost, st));
   MVBA_HIP(hipStreamSynchronize(st));
-  std::vector<int> order(n);
-  std::iota(order.begin(), order.end(), 0);
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return hG[(size_t)a * n + a] > hG[(size_t)b * n + b]; });
+  Basis basis;
+  if (int rc = select_basis(hG.data(), hV.data(), n, n, 4, basis)) return rc;
   double is[4];
   for (int i = 0; i < 4; ++i) {
-    const int col = order[i];
-    const double sg2 = hG[(size_t)col * n + col];
+    const double sg2 = hG[(size_t)basis.order[i] * n + basis.order[i]];
     if (method == 2 && !(sg2 > 0.0)) return fail(MVBA_ERR_SINGULAR, "measurement matrix has rank < 4");
     is[i] = 1.0 / std::sqrt(std::max(sg2, 1e-300));
-    int big = 0;
-    for (int c = 1; c < n; ++c)
-      if (std::fabs(hV[(size_t)c * n + col]) > std::fabs(hV[(size_t)big * n + col])) big = c;
-    const double sg = hV[(size_t)big * n + col] < 0.0 ? -1.0 : 1.0;
-    for (int c = 0; c < n; ++c) Mg[(size_t)c * 4 + i] = sg * hV[(size_t)c * n + col];
   }
+  basis_block(basis, hV.data(), n, n, 0, 4, Mg.data());
   MVBA_HIP(hipMemcpyAsync(h->dMr, Mg.data(), sizeof(double) * (size_t)n * 4, hipMemcpyHostToDevice, st));
   const int pgrid = (int)std::max<long long>(1, std::min<long long>(DEPTH_BLOCKS, (rows + 255) / 256));
   const size_t tile_bytes = sizeof(double) * 4 * 64 * (size_t)((n + m) | 1) + 16;
@@ -2760,32 +2762,15 @@ int depth_step_fused(mvsvd_handle *h, int method, double f0, double *E, double *
   MVBA_HIP(hipStreamSynchronize(st));
   h->loaded = false;  // (no re-weighted matrix was written: dW holds nothing that belongs to these depths)
   if (fl) return fail(MVBA_ERR_SINGULAR, "depth iteration: an image's 12 x 12 companion matrix has no positive eigenvalue");
-  if (timings) {
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, h->ev[6], h->ev[7]); timings[0] = ms;  // depth update
-    hipEventElapsedTime(&ms, h->ev[1], h->ev[2]); timings[1] = ms;  // first Gram pass
-    hipEventElapsedTime(&ms, h->ev[2], h->ev[3]); timings[2] = ms;  // Jacobi (first pass)
-    timings[3] = 0.0;                                                // (no projection pass)
-    int sw = 0;
-    hipMemcpy(&sw, h->dsw, sizeof(int), hipMemcpyDeviceToHost);
-    timings[4] = sw;
-    hipEventElapsedTime(&ms, h->ev[3], h->ev[4]); timings[5] = ms;  // refinement pass (rotate + Gram fused, Jacobi, V1 V2)
+  if (timings) {  // depth update | first Gram pass | Jacobi (first pass) | (no projection pass) | refinement pass (rotate + Gram fused, Jacobi, V1 V2)
+    read_timings(h, timings, {{6, 7}, {1, 2}, {2, 3}, {-1, -1}, {-1, -1}, {3, 4}});
+    timings[4] = jacobi_sweeps(h);
   }
   return MVBA_OK;
 }
 
-}  // namespace
-
-
-extern "C" {
-
-int mvsvd_create(int64_t max_rows, int32_t n_cols, int32_t dtype, int32_t device, mvsvd_handle **out) {
-  if (!out) return fail(MVBA_ERR_BADARG, "null argument");
-  if (max_rows < 1 || n_cols < 1 || n_cols > MVSVD_MAX_COLS)
-    return fail(MVBA_ERR_BADARG, "need max_rows >= 1 and 1 <= n_cols <= " + std::to_string(MVSVD_MAX_COLS) + " (three rows of W per image at the engine's camera limit)");
-  if (dtype != 0 && dtype != 1) return fail(MVBA_ERR_BADARG, "dtype must be 0 (float32) or 1 (float64)");
-  if (device >= 0) MVBA_HIP(hipSetDevice(device));
-  mvsvd_handle *h = new mvsvd_handle();
+// mvsvd_create's work on a fresh handle.  Returns at the first failure: the caller destroys the handle, whatever it holds by then.
+int create_workspace(mvsvd_handle *h, int64_t max_rows, int32_t n_cols, int32_t dtype) {
   MVBA_HIP(hipGetDevice(&h->device));
   h->dtype = dtype; h->n = n_cols; h->max_rows = max_rows;
   const bool wide = n_cols > WIDE_MIN, dense = n_cols <= JACOBI_MAX;  // beyond JACOBI_MAX no n x n matrix at all: see run_wide
@@ -2800,39 +2785,40 @@ int mvsvd_create(int64_t max_rows, int32_t n_cols, int32_t dtype, int32_t device
     part_tiles = std::max(part_tiles, (size_t)3 * std::max(chunks_for(max_rows, WB), chunks_for(n_cols, WB)));
     part2_tiles = std::max(part2_tiles, (size_t)3 * GRAM_SLICES);
   }
-#define SVD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { mvsvd_destroy(h); return fail(MVBA_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-  SVD_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
-  for (auto &e : h->ev) SVD_TRY(hipEventCreate(&e));
-  SVD_TRY(hipMalloc(&h->dW, el * (size_t)max_rows * n_cols));
-  SVD_TRY(hipMalloc((void **)&h->dG, sizeof(double) * nn));
-  SVD_TRY(hipMalloc((void **)&h->dV, sizeof(double) * nn));
-  SVD_TRY(hipMalloc((void **)&h->dV1, sizeof(double) * nn));
-  SVD_TRY(hipMalloc((void **)&h->dMr, sizeof(double) * std::max(nn, (size_t)4 * n_cols)));
-  SVD_TRY(hipMalloc((void **)&h->dsum, sizeof(double) * n_cols * COLSUM_SLICES));
-  SVD_TRY(hipMalloc((void **)&h->dmu, sizeof(double) * n_cols));
-  SVD_TRY(hipMalloc((void **)&h->dsw, sizeof(int)));
-  SVD_TRY(hipMalloc((void **)&h->dpart, sizeof(double) * part_tiles * 256));
-  SVD_TRY(hipMalloc((void **)&h->dpart2, sizeof(double) * part2_tiles * 256));
+  MVBA_HIP(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
+  for (auto &e : h->ev) MVBA_HIP(hipEventCreate(&e));
+  int rc = alloc_once(h, h->dW, el * (size_t)max_rows * n_cols);
+  auto alloc = [&](auto *&p, size_t count) { if (!rc) rc = h->mem.alloc(&p, count); };  // (nothing more after the first failure)
+  alloc(h->dG, nn);
+  alloc(h->dV, nn);
+  alloc(h->dV1, nn);
+  alloc(h->dMr, std::max(nn, (size_t)4 * n_cols));
+  alloc(h->dsum, (size_t)n_cols * COLSUM_SLICES);
+  alloc(h->dmu, n_cols);
+  alloc(h->dsw, 1);
+  alloc(h->dpart, part_tiles * 256);
+  alloc(h->dpart2, part2_tiles * 256);
   if (wide) {
     const size_t nb = (size_t)n_cols * WB;
     // row chunks of Z = W^T B: enough workgroups for the chip beside the n / 64 column blocks, a multiple of 64 rows each
     const long long col_blocks = (n_cols + WT - 1) / WT, want = std::max<long long>(1, 2048 / col_blocks);
     h->zrows_per_chunk = std::max<long long>(WT, ((max_rows + want - 1) / want + WT - 1) / WT * WT);
     h->zchunks = (int)((max_rows + h->zrows_per_chunk - 1) / h->zrows_per_chunk);
-    SVD_TRY(hipMalloc((void **)&h->dQ, sizeof(double) * nb));
-    SVD_TRY(hipMalloc((void **)&h->dZ, sizeof(double) * nb));
-    SVD_TRY(hipMalloc((void **)&h->dQ2, sizeof(double) * nb));
-    SVD_TRY(hipMalloc((void **)&h->dBw, sizeof(double) * (size_t)max_rows * WB));
-    SVD_TRY(hipMalloc((void **)&h->dB2, sizeof(double) * (size_t)max_rows * WB));
-    SVD_TRY(hipMalloc((void **)&h->dzpart, sizeof(double) * (size_t)h->zchunks * nb));
-    SVD_TRY(hipMalloc((void **)&h->dsmall, sizeof(double) * ((size_t)5 * WB * WB + 2 * WB + (size_t)WB * ((n_cols + 255) / 256))));
-    SVD_TRY(hipMalloc((void **)&h->dwflag, sizeof(int) * 2 * WB));
+    alloc(h->dQ, nb);
+    alloc(h->dZ, nb);
+    alloc(h->dQ2, nb);
+    alloc(h->dBw, (size_t)max_rows * WB);
+    alloc(h->dB2, (size_t)max_rows * WB);
+    alloc(h->dzpart, (size_t)h->zchunks * nb);
+    alloc(h->dsmall, (size_t)5 * WB * WB + 2 * WB + (size_t)WB * ((n_cols + 255) / 256));
+    alloc(h->dwflag, 2 * WB);
   }
-  SVD_TRY(hipFuncSetAttribute((const void *)k_jacobi<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  SVD_TRY(hipFuncSetAttribute((const void *)k_project<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-  SVD_TRY(hipFuncSetAttribute((const void *)k_rotate_rows<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  SVD_TRY(hipFuncSetAttribute((const void *)k_rotate_rows<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  SVD_TRY(hipFuncSetAttribute((const void *)k_project<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
+  if (rc) return rc;
+  MVBA_HIP(hipFuncSetAttribute((const void *)k_jacobi<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+  MVBA_HIP(hipFuncSetAttribute((const void *)k_project<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
+  MVBA_HIP(hipFuncSetAttribute((const void *)k_rotate_rows<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+  MVBA_HIP(hipFuncSetAttribute((const void *)k_rotate_rows<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+  MVBA_HIP(hipFuncSetAttribute((const void *)k_project<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
   for (const void *f : {(const void *)k_scale_rows_tiled<float>, (const void *)k_scale_rows_tiled<double>, (const void *)k_depth_primary<float, true>,
                         (const void *)k_depth_primary<double, true>, (const void *)k_dual_apply<float, true>, (const void *)k_dual_apply<double, true>,
                         (const void *)k_dual_gram<float>, (const void *)k_dual_gram<double>, (const void *)k_primary_xz, (const void *)k_dual_gram_mfma<2>, (const void *)k_dual_gram_mfma<4>, (const void *)k_dual_gram_mfma<6>, (const void *)k_dual_gram_mfma<8>,
@@ -2843,8 +2829,25 @@ int mvsvd_create(int64_t max_rows, int32_t n_cols, int32_t dtype, int32_t device
 #define GRAM_XZ_M(M) (const void *)k_gram_xz<M, 1, false>, (const void *)k_gram_xz<M, 1, true>, (const void *)k_gram_xz<M, 2, false>, (const void *)k_gram_xz<M, 2, true>
                         GRAM_XZ_M(2), GRAM_XZ_M(4), GRAM_XZ_M(6), GRAM_XZ_M(8), GRAM_XZ_M(10)})
 #undef GRAM_XZ_M
-    SVD_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEPTH_LDS_MAX));
-#undef SVD_TRY
+    MVBA_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEPTH_LDS_MAX));
+  return MVBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvsvd_create(int64_t max_rows, int32_t n_cols, int32_t dtype, int32_t device, mvsvd_handle **out) {
+  if (!out) return fail(MVBA_ERR_BADARG, "null argument");
+  if (max_rows < 1 || n_cols < 1 || n_cols > MVSVD_MAX_COLS)
+    return fail(MVBA_ERR_BADARG, "need max_rows >= 1 and 1 <= n_cols <= " + std::to_string(MVSVD_MAX_COLS) + " (three rows of W per image at the engine's camera limit)");
+  if (dtype != 0 && dtype != 1) return fail(MVBA_ERR_BADARG, "dtype must be 0 (float32) or 1 (float64)");
+  if (device >= 0) MVBA_HIP(hipSetDevice(device));
+  mvsvd_handle *h = new mvsvd_handle();
+  if (int rc = create_workspace(h, max_rows, n_cols, dtype)) {
+    mvsvd_destroy(h);
+    return rc;
+  }
   *out = h;
   return MVBA_OK;
 }
@@ -2853,10 +2856,7 @@ void mvsvd_destroy(mvsvd_handle *h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->st) hipStreamSynchronize(h->st);
-  for (void *p : {h->dW, h->dS, (void *)h->dG, (void *)h->dV, (void *)h->dV1, (void *)h->dsum, (void *)h->dMr, (void *)h->dmu,
-                  (void *)h->dsw, (void *)h->dpart, (void *)h->dpart2, (void *)h->dB, h->dX, h->dz, h->dstage, (void *)h->dgs, (void *)h->ddep, (void *)h->ddflag,
-                  (void *)h->dQ, (void *)h->dZ, (void *)h->dQ2, (void *)h->dBw, (void *)h->dB2, (void *)h->dzpart, (void *)h->dsmall, (void *)h->dwflag})
-    if (p) hipFree(p);
+  h->mem.release_all();
   for (auto &e : h->ev)
     if (e) hipEventDestroy(e);
   if (h->st) hipStreamDestroy(h->st);
@@ -2868,15 +2868,11 @@ int mvsvd_load(mvsvd_handle *h, const void *Wt, int64_t n_rows) {
   if (n_rows < 1 || n_rows > h->max_rows) return fail(MVBA_ERR_BADARG, "n_rows outside the workspace (1 .. max_rows)");
   MVBA_HIP(hipSetDevice(h->device));
   hipEventRecord(h->ev[0], h->st);
-  MVBA_HIP(hipMemcpyAsync(h->dW, Wt, (h->dtype ? 8 : 4) * (size_t)n_rows * h->n, hipMemcpyHostToDevice, h->st));
+  MVBA_HIP(hipMemcpyAsync(h->dW, Wt, el_bytes(h) * (size_t)n_rows * h->n, hipMemcpyHostToDevice, h->st));
   hipEventRecord(h->ev[1], h->st);
   MVBA_HIP(hipStreamSynchronize(h->st));
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-  h->h2d_ms = ms;
-  h->n_rows = n_rows;
-  h->loaded = true;
-  h->wide_warm = h->wide_have_q = false;  // a new matrix: the block iteration starts from its fixed block
+  h->h2d_ms = event_ms(h, 0, 1);
+  matrix_replaced(h, n_rows);
   return MVBA_OK;
 }
 
@@ -2888,30 +2884,25 @@ int mvsvd_load_images(mvsvd_handle *h, const void *const *xy, int32_t n_images, 
   for (int k = 0; k < n_images; ++k)
     if (!xy[k]) return fail(MVBA_ERR_BADARG, "null image array");
   MVBA_HIP(hipSetDevice(h->device));
-  if (!h->dstage) MVBA_HIP(hipMalloc(&h->dstage, 16 * (size_t)h->max_rows));
+  if (int rc = need_stage(h)) return rc;
   const size_t bytes = (src_dtype ? 16 : 8) * (size_t)n_rows;
   const unsigned grid = (unsigned)((n_rows + 255) / 256);
   hipEventRecord(h->ev[0], h->st);
   for (int k = 0; k < n_images; ++k) {  // image after image in stream order through the one staging buffer
     MVBA_HIP(hipMemcpyAsync(h->dstage, xy[k], bytes, hipMemcpyHostToDevice, h->st));
-    if (src_dtype == 0 && h->dtype == 0)
-      hipLaunchKernelGGL((k_image_cols<float, float>), dim3(grid), dim3(256), 0, h->st, (const float *)h->dstage, (long long)n_rows, h->n, 2 * k, (float *)h->dW);
-    else if (src_dtype == 0)
-      hipLaunchKernelGGL((k_image_cols<float, double>), dim3(grid), dim3(256), 0, h->st, (const float *)h->dstage, (long long)n_rows, h->n, 2 * k, (double *)h->dW);
-    else if (h->dtype == 0)
-      hipLaunchKernelGGL((k_image_cols<double, float>), dim3(grid), dim3(256), 0, h->st, (const double *)h->dstage, (long long)n_rows, h->n, 2 * k, (float *)h->dW);
-    else
-      hipLaunchKernelGGL((k_image_cols<double, double>), dim3(grid), dim3(256), 0, h->st, (const double *)h->dstage, (long long)n_rows, h->n, 2 * k, (double *)h->dW);
+    with_dtype(src_dtype, [&](auto src) {
+      with_dtype(h->dtype, [&](auto dst) {
+        using S = decltype(src);
+        using T = decltype(dst);
+        hipLaunchKernelGGL((k_image_cols<S, T>), dim3(grid), dim3(256), 0, h->st, (const S *)h->dstage, (long long)n_rows, h->n, 2 * k, (T *)h->dW);
+      });
+    });
   }
   hipEventRecord(h->ev[1], h->st);
   MVBA_HIP(hipGetLastError());
   MVBA_HIP(hipStreamSynchronize(h->st));
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-  h->h2d_ms = ms;
-  h->n_rows = n_rows;
-  h->loaded = true;
-  h->wide_warm = h->wide_have_q = false;
+  h->h2d_ms = event_ms(h, 0, 1);
+  matrix_replaced(h, n_rows);
   return MVBA_OK;
 }
 
@@ -2920,24 +2911,20 @@ int mvsvd_run(mvsvd_handle *h, int32_t n_rank, int32_t center, void *M, void *si
   if (!h->loaded) return fail(MVBA_ERR_STATE, "mvsvd_run before mvsvd_load");
   if (n_rank < 1 || n_rank > h->n) return fail(MVBA_ERR_BADARG, "need 1 <= n_rank <= n_cols");
   MVBA_HIP(hipSetDevice(h->device));
-  if (h->dtype == 0) return run<float>(h, n_rank, center, (float *)M, (float *)sigma, (float *)S, (float *)means, timings_ms);
-  return run<double>(h, n_rank, center, (double *)M, (double *)sigma, (double *)S, (double *)means, timings_ms);
+  return with_dtype(h->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return run<T>(h, n_rank, center, (T *)M, (T *)sigma, (T *)S, (T *)means, timings_ms);
+  });
 }
 
 int mvsvd_load_base(mvsvd_handle *h, const void *X, int64_t n_rows) {
   if (!h || !X) return fail(MVBA_ERR_BADARG, "null argument");
   if (n_rows < 1 || n_rows > h->max_rows) return fail(MVBA_ERR_BADARG, "n_rows outside the workspace (1 .. max_rows)");
   MVBA_HIP(hipSetDevice(h->device));
-  const size_t el = h->dtype ? 8 : 4;
-  if (!h->dX) MVBA_HIP(hipMalloc(&h->dX, el * (size_t)h->max_rows * h->n));
-  MVBA_HIP(hipMemcpyAsync(h->dX, X, el * (size_t)n_rows * h->n, hipMemcpyHostToDevice, h->st));
+  if (int rc = need_base(h)) return rc;
+  MVBA_HIP(hipMemcpyAsync(h->dX, X, el_bytes(h) * (size_t)n_rows * h->n, hipMemcpyHostToDevice, h->st));
   MVBA_HIP(hipStreamSynchronize(h->st));
-  h->base_rows = n_rows;
-  h->base_loaded = true;
-  h->depth_group = 0;  // a new base ends a depth loop: its depths and norm-2 scales belong to the old one
-  h->cs_valid = false;
-  h->wide_warm = h->wide_have_q = false;
-  h->loaded = false;  // dW holds nothing derived from this base yet
+  base_replaced(h, n_rows);
   return MVBA_OK;
 }
 
@@ -2949,26 +2936,20 @@ int mvsvd_load_base_images(mvsvd_handle *h, const double *const *xy, int32_t n_i
   for (int k = 0; k < n_images; ++k)
     if (!xy[k]) return fail(MVBA_ERR_BADARG, "null image array");
   MVBA_HIP(hipSetDevice(h->device));
-  const size_t el = h->dtype ? 8 : 4;
-  if (!h->dX) MVBA_HIP(hipMalloc(&h->dX, el * (size_t)h->max_rows * h->n));
+  if (int rc = need_base(h)) return rc;
   // staged through dW (16 bytes a row <= el * n: there are at least 6 columns), image after image in stream order
-  if (el * (size_t)h->n < 16) return fail(MVBA_ERR_BADARG, "the workspace is too narrow to stage an image");
+  if (el_bytes(h) * (size_t)h->n < 16) return fail(MVBA_ERR_BADARG, "the workspace is too narrow to stage an image");
   const unsigned grid = (unsigned)((n_rows + 255) / 256);
   for (int k = 0; k < n_images; ++k) {
     MVBA_HIP(hipMemcpyAsync(h->dW, xy[k], 16 * (size_t)n_rows, hipMemcpyHostToDevice, h->st));
-    if (h->dtype)
-      hipLaunchKernelGGL(k_base_image<double>, dim3(grid), dim3(256), 0, h->st, (const double2 *)h->dW, (long long)n_rows, h->n, 3 * k, f0, (double *)h->dX);
-    else
-      hipLaunchKernelGGL(k_base_image<float>, dim3(grid), dim3(256), 0, h->st, (const double2 *)h->dW, (long long)n_rows, h->n, 3 * k, f0, (float *)h->dX);
+    with_dtype(h->dtype, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(k_base_image<T>, dim3(grid), dim3(256), 0, h->st, (const double2 *)h->dW, (long long)n_rows, h->n, 3 * k, f0, (T *)h->dX);
+    });
   }
   MVBA_HIP(hipGetLastError());
   MVBA_HIP(hipStreamSynchronize(h->st));
-  h->base_rows = n_rows;
-  h->base_loaded = true;
-  h->depth_group = 0;  // (as mvsvd_load_base)
-  h->cs_valid = false;
-  h->wide_warm = h->wide_have_q = false;
-  h->loaded = false;  // dW was the staging buffer
+  base_replaced(h, n_rows);
   return MVBA_OK;
 }
 
@@ -2983,20 +2964,19 @@ int mvsvd_run_scaled(mvsvd_handle *h, const void *z, int32_t group, int32_t norm
   if (n_rank < 1 || n_rank > h->n) return fail(MVBA_ERR_BADARG, "need 1 <= n_rank <= n_cols");
   const int ng = h->n / group;
   MVBA_HIP(hipSetDevice(h->device));
-  const size_t el = h->dtype ? 8 : 4;
-  if (!h->dz) MVBA_HIP(hipMalloc(&h->dz, el * (size_t)h->max_rows * h->n));  // (room for any grouping: a later call may ask for a finer one)
+  if (int rc = need_depths(h)) return rc;
   hipEventRecord(h->ev[0], h->st);
-  if (z) MVBA_HIP(hipMemcpyAsync(h->dz, z, el * (size_t)h->base_rows * ng, hipMemcpyHostToDevice, h->st));  // the only upload of the call
+  if (z) MVBA_HIP(hipMemcpyAsync(h->dz, z, el_bytes(h) * (size_t)h->base_rows * ng, hipMemcpyHostToDevice, h->st));  // the only upload of the call
   hipEventRecord(h->ev[1], h->st);
   if (z) h->depth_group = 0;  // (the caller's depths replace whatever a depth loop held)
   int rc = scale_base_into_w(h, group, norm);
   if (rc) return rc;
   MVBA_HIP(hipStreamSynchronize(h->st));
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-  h->h2d_ms = ms;
-  if (h->dtype == 0) return run<float>(h, n_rank, 0, (float *)M, (float *)sigma, (float *)S, (float *)nullptr, timings_ms);
-  return run<double>(h, n_rank, 0, (double *)M, (double *)sigma, (double *)S, (double *)nullptr, timings_ms);
+  h->h2d_ms = event_ms(h, 0, 1);
+  return with_dtype(h->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return run<T>(h, n_rank, 0, (T *)M, (T *)sigma, (T *)S, (T *)nullptr, timings_ms);
+  });
 }
 
 int mvsvd_depth_begin(mvsvd_handle *h, int32_t group) {
@@ -3005,13 +2985,14 @@ int mvsvd_depth_begin(mvsvd_handle *h, int32_t group) {
   if (group != 3 || h->n % 3) return fail(MVBA_ERR_BADARG, "the depth iteration works on homogeneous image coordinates: group = 3, n_cols = 3 m");
   if (h->n / 3 > DEPTH_MAX_IMAGES) return fail(MVBA_ERR_BADARG, "at most " + std::to_string(DEPTH_MAX_IMAGES) + " images in the device depth loop (two 12-double tables per image in a workgroup's LDS)");
   MVBA_HIP(hipSetDevice(h->device));
-  const size_t el = h->dtype ? 8 : 4;
   const int ng = h->n / 3;
-  if (!h->dz) MVBA_HIP(hipMalloc(&h->dz, el * (size_t)h->max_rows * h->n));  // (shared with mvsvd_run_scaled, whose groups may be finer)
+  if (int rc = need_depths(h)) return rc;  // (shared with mvsvd_run_scaled, whose groups may be finer)
   const long long cnt = h->base_rows * ng;
   const int grid = (int)std::max<long long>(1, std::min<long long>(4096, (cnt + 255) / 256));
-  if (h->dtype == 0) hipLaunchKernelGGL(k_fill<float>, dim3(grid), dim3(256), 0, h->st, (float *)h->dz, cnt, 1.0f);
-  else hipLaunchKernelGGL(k_fill<double>, dim3(grid), dim3(256), 0, h->st, (double *)h->dz, cnt, 1.0);
+  with_dtype(h->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_fill<T>, dim3(grid), dim3(256), 0, h->st, (T *)h->dz, cnt, (T)1);
+  });
   MVBA_HIP(hipGetLastError());
   h->depth_group = 3;
   h->cs_valid = false;
@@ -3026,14 +3007,14 @@ int mvsvd_depth_step(mvsvd_handle *h, int32_t method, double f0, double *E, doub
   MVBA_HIP(hipSetDevice(h->device));
   if (fused_depth_ok(h)) return depth_step_fused(h, method, f0, E, timings_ms);
   h->cs_valid = false;  // (the unfused route moves the depths without the fused route's norm-2 scales)
-  return h->dtype == 0 ? depth_step<float>(h, method, f0, E, timings_ms) : depth_step<double>(h, method, f0, E, timings_ms);
+  return with_dtype(h->dtype, [&](auto tag) { return depth_step<decltype(tag)>(h, method, f0, E, timings_ms); });
 }
 
 int mvsvd_depth_read(mvsvd_handle *h, void *z) {
   if (!h || !z) return fail(MVBA_ERR_BADARG, "null argument");
   if (!h->base_loaded || h->depth_group != 3) return fail(MVBA_ERR_STATE, "mvsvd_depth_read before mvsvd_depth_begin");
   MVBA_HIP(hipSetDevice(h->device));
-  MVBA_HIP(hipMemcpyAsync(z, h->dz, (h->dtype ? 8 : 4) * (size_t)h->base_rows * (h->n / 3), hipMemcpyDeviceToHost, h->st));
+  MVBA_HIP(hipMemcpyAsync(z, h->dz, el_bytes(h) * (size_t)h->base_rows * (h->n / 3), hipMemcpyDeviceToHost, h->st));
   MVBA_HIP(hipStreamSynchronize(h->st));
   return MVBA_OK;
 }

@@ -327,6 +327,37 @@ def test_any_rank_and_workspace_reuse(dtype):
     ws.close()
 
 
+def _narrow_600x9():
+    return _graded(600, 9, [9, 8, 7, 6, 5, 4, 3], seed=11, noise=1e-4), 1e-10, 1e-9, False  # (tol, and 10 tol of the product's largest entry: test_any_rank_and_workspace_reuse)
+
+
+def _wide_300x80():
+    rng = np.random.default_rng(80)  # (as test_wide_matrices_vs_lapack builds its input)
+    return rng.standard_normal((300, 4)) @ rng.standard_normal((4, 80)) + 1e-3 * rng.standard_normal((300, 80)), 1e-12, 1e-12, True  # (the product in units of sigma_1)
+
+
+@pytest.mark.parametrize("make,ranks", [(_narrow_600x9, (2, 5, 3)), (_wide_300x80, (2, 6, 3))], ids=["narrow", "wide"])
+def test_the_rank_grows_and_shrinks_on_one_workspace(make, ranks):
+    """The projection buffer follows the largest rank a workspace has seen (mvsvd.hip: regrow): a larger rank after a smaller one
+    allocates it anew, a smaller one after that runs in the larger buffer.  After every run sigma[:r] and M @ S against LAPACK,
+    with the tolerances of test_any_rank_and_workspace_reuse (Gram route, 9 columns) and of test_wide_matrices_vs_lapack (block
+    iteration, 80 columns)."""
+    Wt, tol_sigma, tol_prod, per_sigma1 = make()
+    U, s_ref, Vt = np.linalg.svd(Wt.T, full_matrices=False)
+    ws = _mvba.SvdWorkspace(Wt.shape[0], Wt.shape[1], np.float64)
+    ws.load(Wt)
+    for r in ranks:
+        M, sig, S, _, _ = ws.run(r)
+        assert M.shape == (Wt.shape[1], r) and S.shape == (r, Wt.shape[0])
+        err_sigma = np.abs(sig[:r] / s_ref[:r] - 1).max()
+        P_ref = (U[:, :r] * s_ref[:r]) @ Vt[:r]
+        err_prod = np.abs(M @ S - P_ref).max() / (s_ref[0] if per_sigma1 else np.abs(P_ref).max())
+        print(f"rank {r}: sigma {err_sigma:.3e} (<= {tol_sigma:g}), M @ S {err_prod:.3e} (< {tol_prod:g})")
+        np.testing.assert_allclose(sig[:r], s_ref[:r], rtol=tol_sigma)
+        assert err_prod < tol_prod
+    ws.close()
+
+
 def test_bad_arguments():
     with pytest.raises(ValueError):
         _mvba.svd_factorize(np.zeros((10, 4)), 5)
