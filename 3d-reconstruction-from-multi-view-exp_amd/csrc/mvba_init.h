@@ -222,6 +222,39 @@ constexpr int RS_NORM = 8;     // per camera: centroid of its points (3), their 
 // matrix consists of, 3 the squared reprojection residual
 __host__ __device__ constexpr int rs_values(int mode) { return mode == 0 ? 6 : (mode == 1 ? 2 : (mode == 2 ? 40 : 1)); }
 
+// What one observation (point Xa, image position z) of camera k adds to pass MODE.  aux: mode 1, 2 the camera's RS_NORM
+// record, mode 3 its matrix [12].
+template <int MODE>
+__device__ __forceinline__ void rs_pass(const double *Xa, double2 z, const double *aux, double (&v)[rs_values(MODE)]) {
+  if constexpr (MODE == 0) {
+    v[0] = 1.0; v[1] = Xa[0]; v[2] = Xa[1]; v[3] = Xa[2]; v[4] = z.x; v[5] = z.y;
+  } else if constexpr (MODE == 1) {
+    const double *nm = aux;
+    const double d0 = Xa[0] - nm[0], d1 = Xa[1] - nm[1], d2 = Xa[2] - nm[2], e0 = z.x - nm[4], e1 = z.y - nm[5];
+    v[0] = d0 * d0 + d1 * d1 + d2 * d2;
+    v[1] = e0 * e0 + e1 * e1;
+  } else if constexpr (MODE == 2) {
+    const double *nm = aux;
+    const double h[4] = {nm[3] * (Xa[0] - nm[0]), nm[3] * (Xa[1] - nm[1]), nm[3] * (Xa[2] - nm[2]), 1.0};
+    const double x = nm[6] * (z.x - nm[4]), y = nm[6] * (z.y - nm[5]), w = x * x + y * y;
+    int e = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = a; b < 4; ++b, ++e) {
+        const double hh = h[a] * h[b];
+        v[e] = hh; v[10 + e] = x * hh; v[20 + e] = y * hh; v[30 + e] = w * hh;
+      }
+  } else {
+    const double *P = aux;
+    const double p0 = Xa[0] * P[0] + Xa[1] * P[1] + Xa[2] * P[2] + P[3];
+    const double p1 = Xa[0] * P[4] + Xa[1] * P[5] + Xa[2] * P[6] + P[7];
+    const double p2 = Xa[0] * P[8] + Xa[1] * P[9] + Xa[2] * P[10] + P[11];
+    const double r0 = p0 / p2 - z.x, r1 = p1 / p2 - z.y;
+    v[0] = r0 * r0 + r1 * r1;
+  }
+}
+
 // One workgroup per chunk (ch_cam, ch_start, ch_cnt): the chunk's sums into part[chunk][NV].  aux: mode 1, 2 the RS_NORM
 // table, mode 3 the camera matrices [m][12].
 template <int MODE>
@@ -237,35 +270,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_resect_chunk(const int *__restr
   for (int e = 0; e < NV; ++e) v[e] = 0.0;
   if (i < ch_cnt[c]) {
     const long long o = ch_start[c] + i;
-    const double *Xa = X + 3 * (size_t)cm_pt[o];
-    const double2 z = cm_xy[o];
-    if constexpr (MODE == 0) {
-      v[0] = 1.0; v[1] = Xa[0]; v[2] = Xa[1]; v[3] = Xa[2]; v[4] = z.x; v[5] = z.y;
-    } else if constexpr (MODE == 1) {
-      const double *nm = aux + RS_NORM * (size_t)k;
-      const double d0 = Xa[0] - nm[0], d1 = Xa[1] - nm[1], d2 = Xa[2] - nm[2], e0 = z.x - nm[4], e1 = z.y - nm[5];
-      v[0] = d0 * d0 + d1 * d1 + d2 * d2;
-      v[1] = e0 * e0 + e1 * e1;
-    } else if constexpr (MODE == 2) {
-      const double *nm = aux + RS_NORM * (size_t)k;
-      const double h[4] = {nm[3] * (Xa[0] - nm[0]), nm[3] * (Xa[1] - nm[1]), nm[3] * (Xa[2] - nm[2]), 1.0};
-      const double x = nm[6] * (z.x - nm[4]), y = nm[6] * (z.y - nm[5]), w = x * x + y * y;
-      int e = 0;
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = a; b < 4; ++b, ++e) {
-          const double hh = h[a] * h[b];
-          v[e] = hh; v[10 + e] = x * hh; v[20 + e] = y * hh; v[30 + e] = w * hh;
-        }
-    } else {
-      const double *P = aux + 12 * (size_t)k;
-      const double p0 = Xa[0] * P[0] + Xa[1] * P[1] + Xa[2] * P[2] + P[3];
-      const double p1 = Xa[0] * P[4] + Xa[1] * P[5] + Xa[2] * P[6] + P[7];
-      const double p2 = Xa[0] * P[8] + Xa[1] * P[9] + Xa[2] * P[10] + P[11];
-      const double r0 = p0 / p2 - z.x, r1 = p1 / p2 - z.y;
-      v[0] = r0 * r0 + r1 * r1;
-    }
+    rs_pass<MODE>(X + 3 * (size_t)cm_pt[o], cm_xy[o], MODE == 0 ? aux : aux + (MODE == 3 ? 12 : RS_NORM) * (size_t)k, v);
   }
   chunk_sum<NV>(v, s_w, part + (size_t)c * NV);
 }
@@ -326,6 +331,71 @@ int launch_triangulate(hipStream_t stream, long long npts, int m, const double *
   return MVBA_OK;
 }
 
+// The usable observations of a list, camera-major: a point is usable if point_ok marks it (point_ok == nullptr: if its X is
+// finite); a stable counting sort by camera keeps ascending points inside a camera.  cam_ptr [m + 1] are the cameras' runs,
+// cm_pt and cm_xy the point and the image position of each sorted observation, cm_obs (want_obs) its index in the caller's list.
+struct ResectList {
+  std::vector<long long> cam_ptr, cm_obs;
+  std::vector<int> cm_pt;
+  std::vector<double> cm_xy;
+};
+
+void resect_build_list(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int m,
+                       const uint8_t *point_ok, bool want_obs, ResectList &L) {
+  std::vector<uint8_t> ok((size_t)n_points);
+  for (int64_t a = 0; a < n_points; ++a)
+    ok[a] = point_ok ? point_ok[a] != 0 : (std::isfinite(X[3 * a]) && std::isfinite(X[3 * a + 1]) && std::isfinite(X[3 * a + 2]));
+  std::vector<long long> &cam_ptr = L.cam_ptr;
+  cam_ptr.assign((size_t)m + 1, 0);
+  auto for_each_obs = [&](auto &&fn) {
+    for (int64_t a = 0; a < n_points; ++a) {
+      if (!ok[a]) continue;
+      const int64_t o0 = pt_ptr ? pt_ptr[a] : a * m, o1 = pt_ptr ? pt_ptr[a + 1] : (a + 1) * m;
+      for (int64_t o = o0; o < o1; ++o) fn(a, o, pt_ptr ? cam_idx[o] : (int)(o - o0));
+    }
+  };
+  for_each_obs([&](int64_t, int64_t, int k) { ++cam_ptr[k + 1]; });
+  for (int k = 0; k < m; ++k) cam_ptr[k + 1] += cam_ptr[k];
+  const long long n_used = cam_ptr[m];
+  L.cm_pt.resize((size_t)n_used);
+  L.cm_xy.resize(2 * (size_t)n_used);
+  if (want_obs) L.cm_obs.resize((size_t)n_used);
+  std::vector<long long> fill(cam_ptr.begin(), cam_ptr.end() - 1);
+  for_each_obs([&](int64_t a, int64_t o, int k) {
+    const long long d = fill[k]++;
+    L.cm_pt[d] = (int)a;
+    L.cm_xy[2 * d] = xy[2 * o];
+    L.cm_xy[2 * d + 1] = xy[2 * o + 1];
+    if (want_obs) L.cm_obs[d] = o;
+  });
+}
+
+// p (the DLT's unit eigenvector, normalised units) -> P in the units of the observations, |P[2, :3]| = 1, det P[:, :3] > 0;
+// false if P is not finite.  x~ = T2 x, X~ = T3 X: P = T2^-1 P~ T3 with T2^-1 = [[1/s2, 0, cx], [0, 1/s2, cy], [0, 0, 1]],
+// T3 = [[s3 I, -s3 c3], [0, 1]]; nm is the camera's RS_NORM record.
+__host__ __device__ __forceinline__ bool resect_denormalise(const double *p, const double *nm, double *P) {
+  const double s3 = nm[3], s2 = nm[6];
+  double Q[12];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) Q[4 * i + j] = s3 * p[4 * i + j];
+    Q[4 * i + 3] = p[4 * i + 3] - s3 * (p[4 * i] * nm[0] + p[4 * i + 1] * nm[1] + p[4 * i + 2] * nm[2]);
+  }
+  for (int j = 0; j < 4; ++j) {
+    P[j] = Q[j] / s2 + nm[4] * Q[8 + j];
+    P[4 + j] = Q[4 + j] / s2 + nm[5] * Q[8 + j];
+    P[8 + j] = Q[8 + j];
+  }
+  const double n3 = sqrt(P[8] * P[8] + P[9] * P[9] + P[10] * P[10]);
+  const double det = P[0] * (P[5] * P[10] - P[6] * P[9]) - P[1] * (P[4] * P[10] - P[6] * P[8]) + P[2] * (P[4] * P[9] - P[5] * P[8]);
+  const double sc = (det < 0.0 ? -1.0 : 1.0) / n3;
+  bool ok = true;
+  for (int j = 0; j < 12; ++j) {
+    P[j] *= sc;
+    ok = ok && init_finite(P[j]);
+  }
+  return ok;
+}
+
 // the sums of one camera -> its matrix (unnormalised), status and eigenvalue ratio
 int resect_solve_camera(const double *S40, const double *nm, double *P, double *ratio) {
   // coincident points: a Hartley scale of sqrt(.) / sqrt(0) = inf, then inf x 0 = NaN in the sums.  The Jacobi skips a NaN
@@ -354,27 +424,7 @@ int resect_solve_camera(const double *S40, const double *nm, double *P, double *
   eig_extremes<12>(A, V, l1, l2, lmax, p);
   *ratio = l1 / l2;
   if (!(l2 > INIT_REL_PIVOT * lmax)) return 2;
-  // x~ = T2 x, X~ = T3 X: P = T2^-1 P~ T3 with T2^-1 = [[1/s2, 0, cx], [0, 1/s2, cy], [0, 0, 1]], T3 = [[s3 I, -s3 c3], [0, 1]]
-  const double s3 = nm[3], s2 = nm[6];
-  double Q[12];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) Q[4 * i + j] = s3 * p[4 * i + j];
-    Q[4 * i + 3] = p[4 * i + 3] - s3 * (p[4 * i] * nm[0] + p[4 * i + 1] * nm[1] + p[4 * i + 2] * nm[2]);
-  }
-  for (int j = 0; j < 4; ++j) {
-    P[j] = Q[j] / s2 + nm[4] * Q[8 + j];
-    P[4 + j] = Q[4 + j] / s2 + nm[5] * Q[8 + j];
-    P[8 + j] = Q[8 + j];
-  }
-  const double n3 = sqrt(P[8] * P[8] + P[9] * P[9] + P[10] * P[10]);
-  const double det = P[0] * (P[5] * P[10] - P[6] * P[9]) - P[1] * (P[4] * P[10] - P[6] * P[8]) + P[2] * (P[4] * P[9] - P[5] * P[8]);
-  const double sc = (det < 0.0 ? -1.0 : 1.0) / n3;
-  bool ok = true;
-  for (int j = 0; j < 12; ++j) {
-    P[j] *= sc;
-    ok = ok && std::isfinite(P[j]);
-  }
-  return ok ? 0 : 2;
+  return resect_denormalise(p, nm, P) ? 0 : 2;
 }
 
 }  // namespace
@@ -461,32 +511,12 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = 0.0;
   const int m = n_images;
   InitClock clk;
-  // usable points, then the stable counting sort by camera: ascending points inside a camera
-  std::vector<uint8_t> ok((size_t)n_points);
-  for (int64_t a = 0; a < n_points; ++a)
-    ok[a] = point_ok ? point_ok[a] != 0 : (std::isfinite(X[3 * a]) && std::isfinite(X[3 * a + 1]) && std::isfinite(X[3 * a + 2]));
-  std::vector<long long> cam_ptr((size_t)m + 1, 0);
-  auto for_each_obs = [&](auto &&fn) {
-    for (int64_t a = 0; a < n_points; ++a) {
-      if (!ok[a]) continue;
-      const int64_t o0 = pt_ptr ? pt_ptr[a] : a * m, o1 = pt_ptr ? pt_ptr[a + 1] : (a + 1) * m;
-      for (int64_t o = o0; o < o1; ++o) fn(a, o, pt_ptr ? cam_idx[o] : (int)(o - o0));
-    }
-  };
-  for_each_obs([&](int64_t, int64_t, int k) { ++cam_ptr[k + 1]; });
-  for (int k = 0; k < m; ++k) cam_ptr[k + 1] += cam_ptr[k];
+  ResectList list;
+  resect_build_list(X, n_points, pt_ptr, cam_idx, xy, m, point_ok, false, list);
+  const std::vector<long long> &cam_ptr = list.cam_ptr;
+  const std::vector<int> &cm_pt = list.cm_pt;
+  const std::vector<double> &cm_xy = list.cm_xy;
   const long long n_used = cam_ptr[m];
-  std::vector<int> cm_pt((size_t)n_used);
-  std::vector<double> cm_xy(2 * (size_t)n_used);
-  {
-    std::vector<long long> fill(cam_ptr.begin(), cam_ptr.end() - 1);
-    for_each_obs([&](int64_t a, int64_t o, int k) {
-      const long long d = fill[k]++;
-      cm_pt[d] = (int)a;
-      cm_xy[2 * d] = xy[2 * o];
-      cm_xy[2 * d + 1] = xy[2 * o + 1];
-    });
-  }
   std::vector<int> cam_ch_ptr((size_t)m + 1, 0), ch_cam, ch_cnt;
   std::vector<long long> ch_start;
   for (int k = 0; k < m; ++k) {

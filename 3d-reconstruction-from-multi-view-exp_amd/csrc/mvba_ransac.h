@@ -32,13 +32,15 @@ __host__ __device__ __forceinline__ unsigned long long rs_mix(unsigned long long
   return x ^ (x >> 31);
 }
 
-// the 8 distinct indices below n (n >= 8) of hypothesis h of pair (k, l): a counter-based generator, rejection of repeats.
+// the NS distinct indices below n (n >= NS) of hypothesis h of pair (k, l): a counter-based generator, rejection of repeats;
+// the first draws do not depend on NS (8 for the fundamental matrix; 6, with l = k, for a camera matrix: mvba_resect_ransac.h).
 // Every index of idx is a compile-time constant once the loops are unrolled (registers on the device).
-__host__ __device__ __forceinline__ void rs_sample(unsigned long long seed, int k, int l, int h, long long n, long long (&idx)[8]) {
+template <int NS>
+__host__ __device__ __forceinline__ void rs_sample(unsigned long long seed, int k, int l, int h, long long n, long long (&idx)[NS]) {
   unsigned long long s = rs_mix(rs_mix(rs_mix(seed) ^ (((unsigned long long)(unsigned int)k << 32) | (unsigned long long)(unsigned int)l)) ^
                                 (unsigned long long)(unsigned int)h);
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < NS; ++c) {
     long long j;
     bool dup;
     do {
@@ -46,7 +48,7 @@ __host__ __device__ __forceinline__ void rs_sample(unsigned long long seed, int 
       j = (long long)(((s >> 32) * (unsigned long long)n) >> 32);  // (n < 2^31: the product is below 2^63)
       dup = false;
 #pragma unroll
-      for (int e = 0; e < 8; ++e)
+      for (int e = 0; e < NS; ++e)
         if (e < c && idx[e] == j) dup = true;
     } while (dup);
     idx[c] = j;

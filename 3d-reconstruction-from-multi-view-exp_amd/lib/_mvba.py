@@ -103,6 +103,11 @@ SIGNATURES = {
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), _dp, C.c_int32]),
     "mvba_ransac_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "mvba_resect_robust": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int32,
+                                     C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int32,
+                                     _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_resect_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -547,6 +552,56 @@ def ransac_sample(seed, k, l, h, n):
     lib = load_library()
     idx = np.empty(8, np.int64)
     raise_for(lib.mvba_ransac_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(l), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
+    return idx
+
+
+def resect_robust(X, pt_ptr, cam_idx, xy, n_images, threshold, point_ok=None, cameras=None, n_hypotheses=512, seed=0, n_refit=2,
+                  return_inliers=True, return_counts=False, device=-1):
+    """Camera matrices by 6-point RANSAC on the device (mvba_resect_robust).  X, the list and ``point_ok`` as for ``resect``;
+    ``cameras`` lists the cameras to solve (default: all; duplicates allowed) and every per-camera output is indexed by the
+    position in it; ``threshold`` is a reprojection distance in the units of xy.  Returns a dict: ``P (C, 3, 4)``,
+    ``quality (C, 2)`` (RMS reprojection residual over the final inliers, eigenvalue ratio of the last kept refit),
+    ``n_usable``, ``n_inliers``, ``best``, ``status`` (C,) (0 ok, 1 fewer than 6 usable observations, 2 every hypothesis
+    degenerate, 4 best count below 6; P and quality NaN then), ``inlier (n_obs,) bool`` in the order of the list given
+    (``return_inliers``), ``hyp_count (C, H) int32`` (``return_counts``), ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_resect_robust")
+    X, xy = _as(X, np.float64), _as(xy, np.float64)
+    n, m = X.shape[0], int(n_images)
+    assert X.shape == (n, 3)
+    _, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m, n)
+    i32, i64, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    okp = None
+    if point_ok is not None:
+        ok = _as(np.asarray(point_ok) != 0, np.uint8)
+        assert ok.shape == (n,)
+        okp = ok.ctypes.data_as(u8)
+    cams = None if cameras is None else _as(cameras, np.int32).reshape(-1)
+    nc, H = m if cams is None else cams.shape[0], int(n_hypotheses)
+    P, q, tm = np.empty((max(nc, 0), 3, 4)), np.empty((max(nc, 0), 2)), np.zeros(4)
+    nu, ni, best, st = np.empty(nc, np.int64), np.empty(nc, np.int64), np.empty(nc, np.int32), np.empty(nc, np.int32)
+    inl = np.empty(n_obs, np.uint8) if return_inliers else None
+    hc = np.empty((nc, max(H, 0)), np.int32) if return_counts else None
+    raise_for(lib.mvba_resect_robust(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, None if cams is None else cams.ctypes.data_as(i32), nc,
+                                     float(threshold), H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(P), _ptr(q),
+                                     nu.ctypes.data_as(i64), ni.ctypes.data_as(i64), best.ctypes.data_as(i32),
+                                     inl.ctypes.data_as(u8) if return_inliers else None, hc.ctypes.data_as(i32) if return_counts else None,
+                                     st.ctypes.data_as(i32), _ptr(tm), int(device)), lib)
+    out = {"P": P, "quality": q, "n_usable": nu, "n_inliers": ni, "best": best, "status": st,
+           "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
+    if return_inliers:
+        out["inlier"] = inl.astype(bool)
+    if return_counts:
+        out["hyp_count"] = hc
+    return out
+
+
+def resect_sample(seed, k, h, n):
+    """The 6 distinct indices below ``n`` that hypothesis ``h`` of camera ``k`` draws (mvba_resect_sample: the host instance of
+    the function the kernel runs; no GPU needed)."""
+    lib = load_library()
+    idx = np.empty(6, np.int64)
+    raise_for(lib.mvba_resect_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
     return idx
 
 

@@ -6,7 +6,8 @@ And the step that starts one: co-visibility counts and the fundamental matrix of
 (``mvba_covisibility``, ``mvba_two_view``: csrc/mvba_twoview.h), the relative pose out of it, and
 ``bootstrap``, the incremental driver -- host control flow over the device calls -- that grows a start pair into an
 initial estimate for ``BundleAdjuster.from_observations``.  With wrong matches among the tracks the first F comes from 8-point
-RANSAC on the device instead (``mvba_two_view_robust``: csrc/mvba_ransac.h): ``ransac_threshold``.
+RANSAC on the device instead (``mvba_two_view_robust``: csrc/mvba_ransac.h): ``ransac_threshold``; and every
+later camera from 6-point RANSAC (``mvba_resect_robust``: csrc/mvba_resect_ransac.h): ``resect_threshold``.
 """
 from __future__ import annotations
 
@@ -81,6 +82,40 @@ def resect_cameras(X, pt_ptr, cam_idx, xy, n_images: int, f0: float = 1.0, point
     if good.any():
         K[good], R[good], t[good] = decompose_projection(P[good], f0)
     return K, R, t, {"status": status, "quality": quality, "P": P, "timings_ms": tm}
+
+
+def robust_resect_cameras(X, pt_ptr, cam_idx, xy, n_images: int, threshold, f0: float = 1.0, point_ok=None, cameras=None,
+                          n_hypotheses: int = 512, seed: int = 0, n_refit: int = 2):
+    """(K, R, t, info): ``resect_cameras`` by 6-point RANSAC on the device (``mvba_resect_robust``), for the cameras listed in
+    ``cameras`` (default: all; K, R, t and every per-camera entry of ``info`` are indexed by the position in it).  Per camera,
+    ``n_hypotheses`` minimal samples of its usable observations (a counter-based generator of ``seed``, the camera and the
+    hypothesis number: ``resect_sample``) are solved and scored by the number of usable observations in front of the camera
+    whose reprojection distance is at most ``threshold`` (units of xy); the best hypothesis's inliers get the full normalised
+    DLT, ``n_refit`` times at most: the first is kept if it has 6 inliers of its own, a later one while its inlier set does not
+    shrink.  ``info``: ``status`` -- 0 ok, 1 fewer than 6 usable observations, 2 every hypothesis degenerate (e.g. coplanar
+    points), 4 the best hypothesis has fewer than 6 inliers; K, R, t, P and quality are NaN where it is not 0 --, ``quality``
+    (C, 2) -- RMS reprojection residual over the final inliers, lambda_1 / lambda_2 of the last kept refit --, ``P`` (C, 3, 4),
+    ``n_usable``, ``n_inliers``, ``best`` (C,), ``inlier`` (n_obs,) bool in the order of the list -- the final inliers of the
+    listed cameras of status 0 --, ``confidence`` (C,) = 1 - (1 - w^6)^H with w = n_inliers / n_usable, and ``timings_ms``.
+    Two calls with the same arguments return the same bits."""
+    out = _mvba.resect_robust(X, pt_ptr, cam_idx, xy, n_images, threshold, point_ok=point_ok, cameras=cameras, n_hypotheses=n_hypotheses,
+                              seed=seed, n_refit=n_refit)
+    P, status = out["P"], out["status"]
+    nc = P.shape[0]
+    K, R, t = np.full((nc, 3, 3), np.nan), np.full((nc, 3, 3), np.nan), np.full((nc, 3), np.nan)
+    good = status == 0
+    if good.any():
+        K[good], R[good], t[good] = decompose_projection(P[good], f0)
+    with np.errstate(all="ignore"):
+        w = out["n_inliers"] / np.maximum(out["n_usable"], 1)
+        out["confidence"] = np.where(good, 1.0 - (1.0 - w ** 6) ** int(n_hypotheses), 0.0)
+    return K, R, t, out
+
+
+def resect_sample(seed, k, h, n):
+    """The 6 distinct indices below ``n`` (of a camera's usable observations in ascending point order) that hypothesis ``h`` of
+    camera ``k`` draws under ``seed`` -- the host instance of the function the kernel runs."""
+    return _mvba.resect_sample(seed, k, h, n)
 
 
 def covisibility(pt_ptr, cam_idx, n_images):
@@ -237,8 +272,18 @@ def pose_for_intrinsics(P, K, c):
     return R, c - R @ (d * np.array([(x[0] - K[0, 2]) / K[0, 0], (x[1] - K[1, 2]) / K[1, 1], 1.0]))
 
 
+def _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok):
+    """``restrict_observations`` over all points and the cameras marked, without the observations ``obs_ok`` drops: (pt_ptr,
+    cam_idx, xy, camera_ids)."""
+    pt = np.repeat(np.arange(len(pt_ptr) - 1), np.diff(pt_ptr))
+    keep = obs_ok & camera_ok[cam_idx]
+    ptr = np.zeros(len(pt_ptr), np.int64)
+    np.cumsum(np.bincount(pt[keep], minlength=len(pt_ptr) - 1), out=ptr[1:])
+    return ptr, (np.cumsum(camera_ok) - 1)[cam_idx[keep]].astype(np.int32), xy[keep], np.nonzero(camera_ok)[0]
+
+
 def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min_points: int = 12, max_rms=None, ransac_threshold=None,
-              n_hypotheses: int = 512, seed: int = 0):
+              n_hypotheses: int = 512, seed: int = 0, resect_threshold=None):
     """(K, R, t, X, info): an initial estimate for ``BundleAdjuster.from_observations`` from feature tracks and rough
     intrinsics, by incremental reconstruction.  ``xy`` are raw image coordinates, ``init_K`` (m, 3, 3) the adjuster's
     [[f,0,u],[0,f,v],[0,0,f0]]; K comes back as ``init_K`` (no focal length is estimated).
@@ -250,6 +295,12 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     registered cameras; a point is kept if its status is 0, its smallest depth > 0 and, with ``max_rms``, its RMS residual
     (units of xy) is at most that.  No BA runs in between.  ``ransac_threshold``, ``n_hypotheses`` and ``seed`` go to every
     ``relative_pose`` (a robust first F; resection and triangulation stay as they are: ``max_rms`` is the filter there).
+    With ``resect_threshold`` (a reprojection distance in the units of xy) each round runs ``robust_resect_cameras`` on the
+    unregistered cameras instead, with ``n_hypotheses`` and ``seed``: the candidate is the one with the most inliers (status 0,
+    at least ``min_points`` of them, the lowest index on ties), its pose is ``pose_for_intrinsics`` at the centroid of its inlier
+    points, and its usable observations that are not inliers are dropped from every later triangulation and resection;
+    ``info`` gains ``obs_ok`` (n_obs,) bool, the observations still in use, and ``inlier`` (n_obs,) bool, the observations
+    the registered cameras were resected from.
     The output frame: camera 0 at the origin with identity pose, |t_1 - t_0| = 1.  ``info``: ``axis`` -- the gauge axis name
     whose component of t_1 is larger in magnitude: pass it to ``BundleAdjuster`` --, ``camera_ok`` (m,), ``point_ok`` (N,),
     ``order`` (the registration order), ``start_pair``.  Cameras and points not reached are NaN (``restrict_observations``
@@ -287,18 +338,38 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     reg_order = [pair[0], pair[1]]
     pt = np.repeat(np.arange(n), np.diff(pt_ptr))
     all_points = np.ones(n, bool)
+    if resect_threshold is not None:
+        obs_ok, inlier = np.ones(len(cam_idx), bool), np.zeros(len(cam_idx), bool)
     while not camera_ok.all():
-        ri = resect_cameras(X, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=point_ok)[3]
-        usable = np.bincount(cam_idx[point_ok[pt]], minlength=m)
-        cand = np.nonzero(~camera_ok & (ri["status"] == 0) & (usable >= min_points))[0]
-        if len(cand) == 0:
-            break
-        c = int(cand[np.argmax(usable[cand])])
-        sel = point_ok[pt] & (cam_idx == c)
-        R[c], t[c] = pose_for_intrinsics(ri["P"][c], Kxy[c], X[pt[sel]].mean(axis=0))
+        if resect_threshold is None:
+            ri = resect_cameras(X, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=point_ok)[3]
+            usable = np.bincount(cam_idx[point_ok[pt]], minlength=m)
+            cand = np.nonzero(~camera_ok & (ri["status"] == 0) & (usable >= min_points))[0]
+            if len(cand) == 0:
+                break
+            c = int(cand[np.argmax(usable[cand])])
+            sel = point_ok[pt] & (cam_idx == c)
+            Pc = ri["P"][c]
+        else:
+            todo = np.nonzero(~camera_ok)[0]
+            ri = robust_resect_cameras(X, pt_ptr, cam_idx, xy, m, resect_threshold, f0=f0, point_ok=point_ok, cameras=todo,
+                                       n_hypotheses=n_hypotheses, seed=seed)[3]
+            cand = np.nonzero((ri["status"] == 0) & (ri["n_inliers"] >= min_points))[0]
+            if len(cand) == 0:
+                break
+            i = int(cand[np.argmax(ri["n_inliers"][cand])])
+            c = int(todo[i])
+            sel = ri["inlier"] & (cam_idx == c)
+            Pc = ri["P"][i]
+            obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)
+            inlier |= sel
+        R[c], t[c] = pose_for_intrinsics(Pc, Kxy[c], X[pt[sel]].mean(axis=0))
         camera_ok[c] = True
         reg_order.append(c)
-        ptr, cam, z, _, ids = restrict_observations(pt_ptr, cam_idx, xy, all_points, camera_ok)
+        if resect_threshold is None:
+            ptr, cam, z, _, ids = restrict_observations(pt_ptr, cam_idx, xy, all_points, camera_ok)
+        else:
+            ptr, cam, z, ids = _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok)
         X, ti = triangulate_points(ptr, cam, z, Kxy[ids], R[ids], t[ids])
         point_ok = (ti["status"] == 0) & (ti["quality"][:, 1] > 0)
         if max_rms is not None:
@@ -311,5 +382,7 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     R0, t0, s = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
     X, R, t = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s
     axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
-    return init_K.copy(), R, t, X, {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order,
-                                    "start_pair": pair}
+    info = {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order, "start_pair": pair}
+    if resect_threshold is not None:
+        info["obs_ok"], info["inlier"] = obs_ok, inlier
+    return init_K.copy(), R, t, X, info

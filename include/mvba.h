@@ -337,6 +337,45 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
  * already drawn.  MVBA_ERR_BADARG: n outside 8 .. 2^31 - 1, a negative k, l or h. */
 int mvba_ransac_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx8);
 
+/* mvba_resect_robust: mvba_resect with 6-point RANSAC in front of it.  X, the list, point_ok, the usable-observation rule and
+ * the camera-major stable counting sort with chunks of 256 observations are mvba_resect's.  cameras [n_cameras]: the cameras to
+ * solve (NULL: all of them, n_cameras = n_images); duplicates are legal; every per-camera output is indexed by the position in
+ * cameras.  MVBA_ERR_BADARG (with the number in the message): a camera index outside 0 .. n_images - 1, n_cameras < 0,
+ * threshold not finite or not > 0, n_hypotheses outside 1 .. 65536, n_refit outside 0 .. 16, and whatever mvba_resect rejects.
+ * Per listed camera k, its usable observations in ascending point order numbered 0 .. n - 1 (a dense run after the sort):
+ *   normalisation: centroids and Hartley scales over ALL usable observations, as mvba_resect defines them;
+ *   hypothesis h = 0 .. n_hypotheses - 1: the 6 distinct indices of mvba_resect_sample(seed, k, h, n); the 12 x 12 moment
+ *     matrix of their 12 normalised DLT rows, from the 40 sums as in mvba_resect; p^_h = the eigenvector of its smallest
+ *     eigenvalue (cyclic Jacobi on the device); degenerate if lambda_2 <= 1e-12 lambda_max or anything is not finite; P_h = p^_h
+ *     denormalised and scaled to |P[2][:3]| = 1, det P[:, :3] > 0;
+ *   score: count_h = the number of usable observations with depth P[2] . (X, 1) > 0 and squared reprojection distance
+ *     |pi(P X) - xy|^2 <= threshold^2 under P_h, an integer (ballots and integer atomics: exact in any order); -1 for a
+ *     degenerate hypothesis; best = the largest count, the lowest h on ties;
+ *   refit r = 1 .. n_refit: the full mvba_resect fit (its own normalisation, fixed-order sums under a byte mask, the order-12
+ *     eigen-problem on the host) on the current inlier set alone, I_0 being that of P_best; I_r = the observations within the
+ *     threshold and in front of that P.  Refit 1 is kept if its status is 0 and |I_1| >= 6; refit r >= 2 if its status is 0
+ *     and |I_r| >= |I_r-1|; otherwise the loop stops with the previous result.  (Not mvba_two_view_robust's rule: a minimal
+ *     6-point DLT is far worse conditioned than a minimal 8-point F, and its count is no bar for the full fit.)  With
+ *     n_refit = 0, P is P_best.
+ * P [n_cameras][12].  quality [n_cameras][2]: the RMS reprojection residual over the final inliers under the matrix that
+ * selected them; lambda_1 / lambda_2 of the last kept refit (0 if none).  n_usable, n_inliers, best [n_cameras] (best = -1
+ * where status = 1 or 2).  inlier [n_obs] BYTES in the caller's observation order: 1 for a final inlier of a listed camera of
+ * status 0, 0 elsewhere.  hyp_count [n_cameras][n_hypotheses]: the count table (all -1 where status = 1 or 2).
+ * status [n_cameras]: 0 ok; 1 fewer than 6 usable observations; 2 every hypothesis degenerate; 4 the best count is below 6.
+ * Where status != 0, P and quality are NaN and n_inliers is 0.
+ * timings_ms [4]: sort + upload; normalisation, hypotheses and scoring; refits; everything else (host clock, each phase ends in
+ * a blocking copy).  Every output but P may be NULL.  Cameras are taken in tiles of 128 MiB / (100 n_hypotheses), at least 1
+ * and at most 65535; a camera's results do not depend on which other cameras are listed.  Two calls give bitwise-identical output. */
+int mvba_resect_robust(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy,
+                       int64_t n_obs, int32_t n_images, const uint8_t *point_ok, const int32_t *cameras, int32_t n_cameras,
+                       double threshold, int32_t n_hypotheses, uint64_t seed, int32_t n_refit, double *P, double *quality,
+                       int64_t *n_usable, int64_t *n_inliers, int32_t *best, uint8_t *inlier, int32_t *hyp_count, int32_t *status,
+                       double *timings_ms, int32_t device);
+/* Host only (no GPU needed): the 6 distinct indices below n that hypothesis h of camera k draws -- mvba_ransac_sample's
+ * generator with l = k and 6 draws: the first 6 of mvba_ransac_sample(seed, k, k, h, n) wherever n >= 8.  MVBA_ERR_BADARG: n
+ * outside 6 .. 2^31 - 1, a negative k or h. */
+int mvba_resect_sample(uint64_t seed, int32_t k, int32_t h, int64_t n, int64_t *idx6);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
