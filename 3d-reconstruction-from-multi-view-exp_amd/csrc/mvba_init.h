@@ -39,15 +39,31 @@ struct InitObs {
   long long o0;
   int deg;
   __host__ __device__ __forceinline__ int camera(int i) const { return cam ? cam[o0 + i] : i; }
+  static constexpr bool MASKED = false;                                  // every observation enters the sums,
+  __host__ __device__ __forceinline__ int count() const { return deg; }  // deg of them
+};
+
+// the same under a byte mask (one byte per observation of the list): the observations whose byte is set, n_used of them.
+// init_point_eval and init_triangulate_point take either form; with InitObs the mask tests are discarded statements
+// (if constexpr) and k_triangulate's code is, instruction for instruction, what it was.  (mvba_tri_ransac.h: the refits of
+// the robust triangulation.)
+struct InitObsMasked : InitObs {
+  static constexpr bool MASKED = true;
+  const unsigned char *mask;
+  int n_used;
+  __host__ __device__ __forceinline__ bool use(int i) const { return mask[o0 + i] != 0; }
+  __host__ __device__ __forceinline__ int count() const { return n_used; }
 };
 
 // E = sum |pi(P X) - xy|^2 with H = sum J^T J (xx,xy,xz,yy,yz,zz) and g = sum J^T r, in ascending observation order
-__host__ __device__ __forceinline__ void init_point_eval(const InitObs &ob, const double *sP, const double (&X)[3], double &E,
+template <class Obs>
+__host__ __device__ __forceinline__ void init_point_eval(const Obs &ob, const double *sP, const double (&X)[3], double &E,
                                                          double (&H)[6], double (&g)[3]) {
   E = 0.0;
   for (int i = 0; i < 6; ++i) H[i] = 0.0;
   for (int i = 0; i < 3; ++i) g[i] = 0.0;
   for (int i = 0; i < ob.deg; ++i) {
+    if constexpr (Obs::MASKED) { if (!ob.use(i)) continue; }
     const double *P = sP + 12 * ob.camera(i);
     const double2 z = ob.xy[ob.o0 + i];
     const double p0 = X[0] * P[0] + X[1] * P[1] + X[2] * P[2] + P[3];
@@ -92,19 +108,22 @@ __host__ __device__ __forceinline__ bool init_chol3_step(const double (&H)[6], c
   return true;
 }
 
-// One point: the linear step, n_refine Gauss-Newton steps, the quality figures.  Returns the status; X is NaN and q is NaN
-// where it is not 0.  R, t: the cameras' poses (global memory) for the depth and the viewing rays; q is filled when want_q.
-__host__ __device__ __forceinline__ int init_triangulate_point(const InitObs &ob, const double *sP, const double *R, const double *t,
+// One point, from all of its observations (InitObs) or from those whose mask byte is set (InitObsMasked): the linear step,
+// n_refine Gauss-Newton steps, the quality figures.  Returns the status; X is NaN and q is NaN where it is not 0.  R, t: the
+// cameras' poses (global memory) for the depth and the viewing rays; q is filled when want_q.
+template <class Obs>
+__host__ __device__ __forceinline__ int init_triangulate_point(const Obs &ob, const double *sP, const double *R, const double *t,
                                                                int n_refine, double (&X)[3], bool want_q, double (&q)[3]) {
   const double nan = NAN;
   X[0] = X[1] = X[2] = nan;
   q[0] = q[1] = q[2] = nan;
-  if (ob.deg < 2) return 1;
+  if (ob.count() < 2) return 1;
   double A[4][4], V[4][4];
   {
     double M[10];
     for (int e = 0; e < 10; ++e) M[e] = 0.0;
     for (int i = 0; i < ob.deg; ++i) {
+      if constexpr (Obs::MASKED) { if (!ob.use(i)) continue; }
       const double *P = sP + 12 * ob.camera(i);
       const double2 z = ob.xy[ob.o0 + i];
 #pragma unroll
@@ -153,18 +172,20 @@ __host__ __device__ __forceinline__ int init_triangulate_point(const InitObs &ob
   if (want_q) {
     double dmin = HUGE_VAL, amax = 0.0;
     for (int i = 0; i < ob.deg; ++i) {
+      if constexpr (Obs::MASKED) { if (!ob.use(i)) continue; }
       const int k = ob.camera(i);
       const double *Rk = R + 9 * (size_t)k, *tk = t + 3 * (size_t)k;
       const double a0 = Y[0] - tk[0], a1 = Y[1] - tk[1], a2 = Y[2] - tk[2];
       dmin = fmin(dmin, Rk[2] * a0 + Rk[5] * a1 + Rk[8] * a2);
       for (int j = i + 1; j < ob.deg; ++j) {
+        if constexpr (Obs::MASKED) { if (!ob.use(j)) continue; }
         const double *tl = t + 3 * (size_t)ob.camera(j);
         const double b0 = Y[0] - tl[0], b1 = Y[1] - tl[1], b2 = Y[2] - tl[2];
         const double c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
         amax = fmax(amax, atan2(sqrt(c0 * c0 + c1 * c1 + c2 * c2), a0 * b0 + a1 * b1 + a2 * b2));
       }
     }
-    q[0] = sqrt(E / ob.deg);
+    q[0] = sqrt(E / ob.count());
     q[1] = dmin;
     q[2] = amax;
   }

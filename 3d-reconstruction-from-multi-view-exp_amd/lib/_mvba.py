@@ -108,6 +108,11 @@ SIGNATURES = {
                                      _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_int32]),
     "mvba_resect_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "mvba_triangulate_robust": (C.c_int, [_dp, _dp, _dp, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64,
+                                          C.c_double, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _dp,
+                                          C.c_int32]),
+    "mvba_triangulate_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -602,6 +607,46 @@ def resect_sample(seed, k, h, n):
     lib = load_library()
     idx = np.empty(6, np.int64)
     raise_for(lib.mvba_resect_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
+    return idx
+
+
+def triangulate_robust(K, R, t, pt_ptr, cam_idx, xy, threshold, n_hypotheses=64, seed=0, n_refine=2, n_refit=2, return_counts=False,
+                       device=-1):
+    """Points by a two-view RANSAC per point on the device (mvba_triangulate_robust).  Cameras and list as for ``triangulate``;
+    ``threshold`` is a reprojection distance in the units of xy.  Returns a dict: ``X (N, 3)``, ``quality (N, 3)`` (RMS
+    reprojection residual, smallest depth and largest ray angle over the final inliers), ``status`` (N,) (0 ok, 1 fewer than two
+    observations, 2 every hypothesis degenerate, 4 best count below min(deg, 3); X and quality NaN then), ``n_inliers``,
+    ``best`` (N,), ``inlier (n_obs,) bool`` in the order of the list, ``hyp_count (N, H) int32`` (``return_counts``),
+    ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_triangulate_robust")
+    K, R, t, xy = (_as(v, np.float64) for v in (K, R, t, xy))
+    m, H = K.shape[0], int(n_hypotheses)
+    assert K.shape == (m, 3, 3) and R.shape == (m, 3, 3) and t.shape == (m, 3)
+    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
+    i32 = C.POINTER(C.c_int32)
+    X, q, tm = np.empty((n, 3)), np.empty((n, 3)), np.zeros(4)
+    st, ni, best, inl = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n_obs, np.uint8)
+    hc = np.empty((n, max(H, 0)), np.int32) if return_counts else None
+    raise_for(lib.mvba_triangulate_robust(_ptr(K), _ptr(R), _ptr(t), m, n, pp, cp, _ptr(xy), n_obs, float(threshold), H,
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refine), int(n_refit), _ptr(X), _ptr(q), st.ctypes.data_as(i32),
+                                          ni.ctypes.data_as(i32), best.ctypes.data_as(i32), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          hc.ctypes.data_as(i32) if return_counts else None, _ptr(tm), int(device)), lib)
+    out = {"X": X, "quality": q, "status": st, "n_inliers": ni, "best": best, "inlier": inl.astype(bool),
+           "timings_ms": dict(zip(("upload", "score", "refit", "download"), tm.tolist()))}
+    if return_counts:
+        out["hyp_count"] = hc
+    return out
+
+
+def triangulate_sample(seed, point, h, deg, n_hypotheses=64):
+    """The two observation numbers (i < j, below ``deg``) of hypothesis ``h`` of point ``point``, or (-1, -1) where the
+    exhaustive table has no entry ``h`` (mvba_triangulate_sample: the host instance of the function the kernel runs; no GPU
+    needed)."""
+    lib = load_library()
+    idx = np.empty(2, np.int64)
+    raise_for(lib.mvba_triangulate_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(point), int(h), int(deg), int(n_hypotheses),
+                                          idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
     return idx
 
 

@@ -7,7 +7,9 @@ And the step that starts one: co-visibility counts and the fundamental matrix of
 ``bootstrap``, the incremental driver -- host control flow over the device calls -- that grows a start pair into an
 initial estimate for ``BundleAdjuster.from_observations``.  With wrong matches among the tracks the first F comes from 8-point
 RANSAC on the device instead (``mvba_two_view_robust``: csrc/mvba_ransac.h): ``ransac_threshold``; and every
-later camera from 6-point RANSAC (``mvba_resect_robust``: csrc/mvba_resect_ransac.h): ``resect_threshold``.
+later camera from 6-point RANSAC (``mvba_resect_robust``: csrc/mvba_resect_ransac.h): ``resect_threshold``; and
+every point from a two-view RANSAC of its own (``mvba_triangulate_robust``: csrc/mvba_tri_ransac.h):
+``triangulate_threshold``.
 """
 from __future__ import annotations
 
@@ -29,6 +31,41 @@ def triangulate_points(pt_ptr, cam_idx, xy, K, R, t, n_refine: int = 2):
     ``BundleAdjuster.from_observations(init_X=None)``."""
     X, quality, status, tm = _mvba.triangulate(K, R, t, pt_ptr, cam_idx, xy, n_refine=n_refine)
     return X, {"status": status, "quality": quality, "timings_ms": tm}
+
+
+def robust_triangulate_points(pt_ptr, cam_idx, xy, K, R, t, threshold, n_hypotheses: int = 64, seed: int = 0, n_refine: int = 2,
+                              n_refit: int = 2):
+    """(X (N, 3), info): ``triangulate_points`` by a two-view RANSAC per point on the device (``mvba_triangulate_robust``).  A
+    hypothesis is two of the point's observations and its model the midpoint of their two viewing rays; a point with at most
+    ``n_hypotheses`` pairs tries every pair, any other ``n_hypotheses`` sampled ones (a counter-based generator of ``seed``, the
+    point and the hypothesis number: ``triangulate_sample``).  The score is the number of the point's observations in front of
+    their camera whose reprojection distance is at most ``threshold`` (units of xy); the best hypothesis's inliers get the
+    plain fit (the DLT, ``n_refine`` Gauss-Newton steps), ``n_refit`` times at most: the first is kept if it has min(deg, 3)
+    inliers of its own, a later one while its inlier set does not shrink.  ``info``: ``status`` (N,) -- 0 ok, 1 fewer than two
+    observations, 2 every hypothesis degenerate (no parallax), 4 the best hypothesis has fewer than min(deg, 3) inliers; X
+    and quality are NaN where it is not 0 --, ``quality`` (N, 3) -- the three figures of ``triangulate_points`` over the final
+    inliers --, ``n_inliers``, ``best`` (N,), ``inlier`` (n_obs,) bool in the order of the list, ``confidence`` (N,) -- 1 where
+    every pair was tried, 1 - (1 - w^2)^H with w = n_inliers / deg where they were sampled, 0 where the status is not 0 -- and
+    ``timings_ms``.  A point with three or more observations needs three that agree; a point with exactly TWO cannot be
+    verified: its one hypothesis is its own two observations, and a wrong match among them passes whenever the two rays come
+    within the threshold of each other.  Two calls with the same arguments return the same bits."""
+    out = _mvba.triangulate_robust(K, R, t, pt_ptr, cam_idx, xy, threshold, n_hypotheses=n_hypotheses, seed=seed, n_refine=n_refine,
+                                   n_refit=n_refit)
+    X = out.pop("X")
+    m = np.asarray(K).shape[0]
+    deg = np.full(len(X), m, np.int64) if pt_ptr is None else np.diff(np.asarray(pt_ptr, np.int64))
+    with np.errstate(all="ignore"):
+        w = out["n_inliers"] / np.maximum(deg, 1)
+        sampled = 1.0 - (1.0 - w ** 2) ** int(n_hypotheses)
+    out["confidence"] = np.where(out["status"] == 0, np.where(deg * (deg - 1) // 2 <= int(n_hypotheses), 1.0, sampled), 0.0)
+    return X, out
+
+
+def triangulate_sample(seed, point, h, deg, n_hypotheses: int = 64):
+    """The two observation numbers (i < j, below ``deg``) that hypothesis ``h`` of point ``point`` is made of under ``seed``, or
+    (-1, -1) where every pair fits into ``n_hypotheses`` and there is no pair ``h`` -- the host instance of the function the
+    kernel runs."""
+    return _mvba.triangulate_sample(seed, point, h, deg, n_hypotheses)
 
 
 def engine_intrinsics(K):
@@ -283,7 +320,7 @@ def _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok):
 
 
 def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min_points: int = 12, max_rms=None, ransac_threshold=None,
-              n_hypotheses: int = 512, seed: int = 0, resect_threshold=None):
+              n_hypotheses: int = 512, seed: int = 0, resect_threshold=None, triangulate_threshold=None):
     """(K, R, t, X, info): an initial estimate for ``BundleAdjuster.from_observations`` from feature tracks and rough
     intrinsics, by incremental reconstruction.  ``xy`` are raw image coordinates, ``init_K`` (m, 3, 3) the adjuster's
     [[f,0,u],[0,f,v],[0,0,f0]]; K comes back as ``init_K`` (no focal length is estimated).
@@ -301,6 +338,13 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     points, and its usable observations that are not inliers are dropped from every later triangulation and resection;
     ``info`` gains ``obs_ok`` (n_obs,) bool, the observations still in use, and ``inlier`` (n_obs,) bool, the observations
     the registered cameras were resected from.
+    With ``triangulate_threshold`` (a reprojection distance in the units of xy) every triangulation of the loop is
+    ``robust_triangulate_points`` over the observations of the registered cameras still in use, with ``n_hypotheses`` (4096 at
+    most) and ``seed``: a wrong match in ANY registered camera, 0 and 1 included, is left out of its point instead of moving it
+    (a point seen twice cannot be verified, see there).  The keep rule is the same (status 0, smallest depth > 0, ``max_rms``
+    over the point's inliers).  Triangulation drops nothing for good: each round decides again over the cameras registered
+    then.  ``relative_pose``'s own triangulation stays plain (two views have no redundancy).  ``info`` gains ``tri_inlier``
+    (n_obs,) bool, the observations the final points were triangulated from.
     The output frame: camera 0 at the origin with identity pose, |t_1 - t_0| = 1.  ``info``: ``axis`` -- the gauge axis name
     whose component of t_1 is larger in magnitude: pass it to ``BundleAdjuster`` --, ``camera_ok`` (m,), ``point_ok`` (N,),
     ``order`` (the registration order), ``start_pair``.  Cameras and points not reached are NaN (``restrict_observations``
@@ -340,6 +384,8 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     all_points = np.ones(n, bool)
     if resect_threshold is not None:
         obs_ok, inlier = np.ones(len(cam_idx), bool), np.zeros(len(cam_idx), bool)
+    if triangulate_threshold is not None:
+        tri_inlier = point_ok[pt] & camera_ok[cam_idx]  # (until the first round: what relative_pose triangulated from)
     while not camera_ok.all():
         if resect_threshold is None:
             ri = resect_cameras(X, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=point_ok)[3]
@@ -370,11 +416,20 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
             ptr, cam, z, _, ids = restrict_observations(pt_ptr, cam_idx, xy, all_points, camera_ok)
         else:
             ptr, cam, z, ids = _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok)
-        X, ti = triangulate_points(ptr, cam, z, Kxy[ids], R[ids], t[ids])
+        if triangulate_threshold is None:
+            X, ti = triangulate_points(ptr, cam, z, Kxy[ids], R[ids], t[ids])
+        else:
+            X, ti = robust_triangulate_points(ptr, cam, z, Kxy[ids], R[ids], t[ids], triangulate_threshold,
+                                              n_hypotheses=min(int(n_hypotheses), 4096), seed=seed)
         point_ok = (ti["status"] == 0) & (ti["quality"][:, 1] > 0)
         if max_rms is not None:
             point_ok &= ti["quality"][:, 0] <= max_rms
         X[~point_ok] = np.nan
+        if triangulate_threshold is not None:
+            kept = camera_ok[cam_idx] if resect_threshold is None else obs_ok & camera_ok[cam_idx]  # (the list just triangulated)
+            tri_inlier = np.zeros(len(cam_idx), bool)
+            tri_inlier[np.nonzero(kept)[0]] = ti["inlier"]
+            tri_inlier &= point_ok[pt]
     for c in (0, 1):
         if not camera_ok[c]:
             raise ValueError(f"bootstrap: camera {c} could not be registered (the output frame is that of cameras 0 and 1); "
@@ -385,4 +440,6 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     info = {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order, "start_pair": pair}
     if resect_threshold is not None:
         info["obs_ok"], info["inlier"] = obs_ok, inlier
+    if triangulate_threshold is not None:
+        info["tri_inlier"] = tri_inlier
     return init_K.copy(), R, t, X, info

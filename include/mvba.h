@@ -376,6 +376,44 @@ int mvba_resect_robust(const double *X, int64_t n_points, const int64_t *pt_ptr,
  * outside 6 .. 2^31 - 1, a negative k or h. */
 int mvba_resect_sample(uint64_t seed, int32_t k, int32_t h, int64_t n, int64_t *idx6);
 
+/* mvba_triangulate_robust: mvba_triangulate with a two-view RANSAC per point in front of it (csrc/mvba_tri_ransac.h, DESIGN.md
+ * 19).  Cameras, list, dense grid (pt_ptr == NULL), units, the argument checks and the limit of 1704 cameras are
+ * mvba_triangulate's; MVBA_ERR_BADARG also for a threshold that is not finite or not > 0, n_hypotheses outside 1 .. 4096 and
+ * n_refit outside 0 .. 16.  Nothing is launched before the checks have passed.
+ * Per point a, its deg observations numbered 0 .. deg - 1 in list order, n_pairs = deg (deg - 1) / 2:
+ *   hypothesis h = 0 .. n_hypotheses - 1: two observations i < j, those of mvba_triangulate_sample(seed, a, h, deg,
+ *     n_hypotheses) -- every pair once if n_pairs <= n_hypotheses, a seeded sample otherwise --; its model is the midpoint of
+ *     the two viewing rays in closed form: centre c = t_k, direction d = M^-1 (x, y, 1) scaled to unit length with M = P[:, :3]
+ *     inverted by its adjugate; b = c_2 - c_1, alpha = d_1 . d_2, s = (b . d_1 - alpha b . d_2) / (1 - alpha^2),
+ *     u = (alpha b . d_1 - b . d_2) / (1 - alpha^2), X_h = (c_1 + s d_1 + c_2 + u d_2) / 2; degenerate if 1 - alpha^2 <= 1e-12
+ *     or X_h is not finite;
+ *   score: count_h = the number of the point's observations with depth P[2] . (X_h, 1) > 0 and squared reprojection distance
+ *     |pi(P X_h) - xy|^2 <= threshold^2 (the test of mvba_resect_robust), an integer; -1 for a degenerate hypothesis and for a
+ *     table entry h >= n_pairs of an exhaustive point; best = the largest count, the lowest h on ties;
+ *   refit r = 1 .. n_refit: mvba_triangulate's fit (the DLT, then n_refine Gauss-Newton steps) on the current inlier set alone,
+ *     I_0 being that of X_best; I_r = the observations in front of their camera and within the threshold of that fit.  Refit 1
+ *     is kept if its status is 0 and |I_1| >= min(deg, 3); refit r >= 2 if its status is 0 and |I_r| >= |I_r-1|; otherwise the
+ *     loop stops with the previous result.  With n_refit = 0, X is X_best.
+ * status [n_points]: 0 ok; 1 fewer than two observations; 2 every hypothesis degenerate; 4 the best count is below
+ * min(deg, 3): a point with three or more observations needs three that agree.  A point with exactly two has one
+ * hypothesis, whose two observations are its own inliers whenever they lie within the threshold of the midpoint: such a point
+ * CANNOT be verified, and a wrong match in it passes if the two rays happen to come close.  Where status != 0, X and quality are NaN,
+ * n_inliers is 0 and none of the point's inlier bytes is set.
+ * X [n_points][3].  quality [n_points][3]: mvba_triangulate's three figures over the final inliers at the returned X.
+ * n_inliers, best [n_points] (best = -1 where status = 1 or 2).  inlier [n_obs] BYTES in list order: 1 for a final inlier.
+ * hyp_count [n_points][n_hypotheses]: the count table.  timings_ms [4]: upload; hypotheses and scores (k_tri_score, by
+ * events); refits and quality (k_tri_refit, by events); download.  Every output but X may be NULL.  A group of 16 lanes per
+ * point, integer counts, no atomics: two calls give bitwise-identical output. */
+int mvba_triangulate_robust(const double *K, const double *R, const double *t, int32_t n_images, int64_t n_points, const int64_t *pt_ptr,
+                            const int32_t *cam_idx, const double *xy, int64_t n_obs, double threshold, int32_t n_hypotheses,
+                            uint64_t seed, int32_t n_refine, int32_t n_refit, double *X, double *quality, int32_t *status,
+                            int32_t *n_inliers, int32_t *best, uint8_t *inlier, int32_t *hyp_count, double *timings_ms, int32_t device);
+/* Host only (no GPU needed): the two observation numbers idx2[0] < idx2[1] of hypothesis h of a point with deg observations --
+ * the function the kernel runs.  n_pairs <= n_hypotheses: the h-th pair (i, j), i < j, in lexicographic order, or (-1, -1) for
+ * h >= n_pairs.  Otherwise the first two draws of mvba_ransac_sample's generator with k = l = point and n = deg, sorted.
+ * MVBA_ERR_BADARG: deg outside 2 .. 2^31 - 1, n_hypotheses outside 1 .. 4096, a negative point or h, h >= n_hypotheses. */
+int mvba_triangulate_sample(uint64_t seed, int32_t point, int32_t h, int64_t deg, int32_t n_hypotheses, int64_t *idx2);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
