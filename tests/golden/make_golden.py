@@ -198,11 +198,30 @@ def small_scene(rng, n_pts, n_img, vis_p, pp_sigma, noise, perturb):
     return x, vis, X0, K0, R0, t0
 
 
-def linearization_dump(name, axis, seed):
-    """(3)/(5): every intermediate of one LM linearisation + one trial at c=1e-4."""
+def linearization_dump_px(name="linearize_60x7_px", axis="x-up_z-forward", seed=13, f0=600.0):
+    """(3) in pixel units: the 60 x 7 scene with f ~ 600, u ~ (320, 240) + N(0, 5) per camera, observations in pixels
+    and f0 = 600 handed to the reference -- the same fields as linearize_60x7_xup."""
     rng = np.random.default_rng(seed)
-    x, vis, X0, K0, R0, t0 = small_scene(rng, 60, 7, 0.6, 0.05, 0.002, 0.02)
-    ba = BundleAdjuster(x, X0, K0, R0, t0, f0=1.0, visibility_index=vis, axis=axis)
+    x, vis, X0, K0, R0, t0 = small_scene(rng, 60, 7, 0.6, 0.0, 0.002, 0.02)
+    m = x.shape[1]
+    u_px = np.array([320.0, 240.0]) + rng.normal(0, 5.0, (m, 2))  # the initial estimate
+    u_true = u_px + rng.normal(0, 1.5, (m, 2))  # where the images were taken: the u gradient is not zero
+    x = f0 * x + u_true[None]
+    K0 = K0.copy()
+    K0[:, 0, 0] *= f0
+    K0[:, 1, 1] = K0[:, 0, 0]
+    K0[:, :2, 2] = u_px
+    K0[:, 2, 2] = f0
+    linearization_dump(name, axis, None, scene=(x, vis, X0, K0, R0, t0), f0=f0)
+
+
+def linearization_dump(name, axis, seed, scene=None, f0=1.0):
+    """(3)/(5): every intermediate of one LM linearisation + one trial at c=1e-4."""
+    if scene is None:
+        rng = np.random.default_rng(seed)
+        scene = small_scene(rng, 60, 7, 0.6, 0.05, 0.002, 0.02)
+    x, vis, X0, K0, R0, t0 = scene
+    ba = BundleAdjuster(x, X0, K0, R0, t0, f0=f0, visibility_index=vis, axis=axis)
     nX, nR, nt = ba._X.copy(), ba._R.copy(), ba._t.copy()
     K = ba._get_K(ba._f, ba._u)
     P, p, q, r = ba._calc_pqr(ba._X, K, ba._R, ba._t)
@@ -235,7 +254,7 @@ def linearization_dump(name, axis, seed):
     _, tp, tq, tr = ba._calc_pqr(tX, tK, tR, tt)
     E1 = ba._calc_reprojection_error(tp, tq, tr)
     # and a short full optimisation from the same start
-    ba2 = BundleAdjuster(x, X0, K0, R0, t0, f0=1.0, visibility_index=vis, axis=axis)
+    ba2 = BundleAdjuster(x, X0, K0, R0, t0, f0=f0, visibility_index=vis, axis=axis)
     (Xo, Ko, Ro, to), txt, solves = _count_inner_solves(ba2, 10.0, 1e-8, max_iter=8, is_debug=True)
     _save(
         name,
@@ -423,6 +442,7 @@ if __name__ == "__main__":
     affine_default()
     linearization_dump("linearize_60x7_xup", "x-up_z-forward", 11)
     linearization_dump("linearize_60x7_xright", "x-right_z-forward", 12)
+    linearization_dump_px()
     visibility_scene()
     factorization_vectors()
     small_known_answers()

@@ -5,11 +5,11 @@ import pytest
 from oracle import ba_oracle as O
 
 
-def _engine_from(d, axis):
+def _engine_from(d, axis, f0=1.0):
     n, m = d["x"].shape[:2]
     vis = d["vis"] if "vis" in d.files else None
     pt_ptr, cam, xy = O.dense_to_observations(d["x"], vis)
-    g = O.OracleEngine(n, m, pt_ptr, cam, xy, 1.0, axis)
+    g = O.OracleEngine(n, m, pt_ptr, cam, xy, f0, axis)
     X, R, t = O.normalize_scene(d["init_X"], d["init_R"], d["init_t"], axis)
     g.set_params(X, d["init_K"][:, 0, 0], d["init_K"][:, :2, 2], t, R)
     return g
@@ -52,6 +52,69 @@ def test_one_linearisation_all_intermediates(golden, name, axis):
     np.testing.assert_allclose(g.tR, d["trial_R"], rtol=0, atol=1e-12)
     np.testing.assert_allclose(g.tt, d["trial_t"], rtol=0, atol=1e-11)
     assert abs(E1 - float(d["E1"])) < 1e-12
+
+
+def test_pixel_units_one_linearisation_and_trajectory(golden):
+    """The oracle's f0 handling against the reference's: linearize_60x7_px is the 60 x 7 scene in pixels (f ~ 600,
+    u ~ (320, 240), f0 = 600).  The bounds are those of test_one_linearisation_all_intermediates and test_full_trajectory on the
+    same fields, applied after scaling the camera columns by D (f0 at f, u, v; 1 at the pose): unscaled, the f / u block of A
+    lies f0^2 below max|A| and a bound relative to max|A| would not see it."""
+    d = golden("linearize_60x7_px")
+    axis, f0 = "x-up_z-forward", 600.0
+    assert str(d["axis"]) == axis and (d["init_K"][:, 2, 2] == f0).all()
+    g = _engine_from(d, axis, f0)
+    vis = d["vis"]
+    n, m = vis.shape
+    D = np.ones((m, 9))
+    D[:, :3] = f0
+    D = D.reshape(-1)
+    keep = g.keep
+    Dk = D[keep]
+    p, q, r, _ = O.project(g.X, g.f, g.u, g.t, g.R, f0, g.pt, g.cam)
+    for mine, ref in ((p, d["p"]), (q, d["q"]), (r, d["r"])):
+        np.testing.assert_allclose(mine / f0, ref[vis] / f0, rtol=1e-13, atol=1e-14)
+    assert abs(g.cost() - float(d["E0"])) < 1e-14
+    g.linearize()
+    np.testing.assert_allclose(g.dP.ravel(), d["d_P"], rtol=1e-11, atol=1e-13)
+    np.testing.assert_allclose(g.dF.ravel()[keep] * Dk, d["d_F"] * Dk, rtol=1e-11, atol=1e-12)
+    np.testing.assert_allclose(g.E, d["matE"], rtol=1e-11, atol=1e-13)
+    Fd = np.zeros((n, 3, 9 * m))
+    for o, (a, k) in enumerate(zip(g.pt, g.cam)):
+        Fd[a, :, 9 * k:9 * k + 9] = g.F[o]
+    np.testing.assert_allclose(Fd[:, :, keep] * Dk, d["matF"] * Dk, rtol=1e-11, atol=1e-13)
+    Gd = np.zeros((9 * m, 9 * m))
+    for k in range(m):
+        Gd[9 * k:9 * k + 9, 9 * k:9 * k + 9] = g.G[k]
+    DDk = np.outer(Dk, Dk)
+    np.testing.assert_allclose(Gd[np.ix_(keep, keep)] * DDk, d["matG"] * DDk, rtol=1e-11, atol=1e-11)
+    E1 = g.try_step(float(d["c"]))
+    A, Ar, b, br, dxi, dxir = g.A * DDk, d["A"] * DDk, g.b * Dk, d["b"] * Dk, g.dxi_red / Dk, d["dxi"] / Dk
+    print(f"px golden: |dA| / max = {np.abs(A - Ar).max() / np.abs(Ar).max():.3e} (1e-12), |db| / max = "
+          f"{np.abs(b - br).max() / np.abs(br).max():.3e} (1e-12), |ddxi| / max = {np.abs(dxi - dxir).max() / np.abs(dxir).max():.3e} (1e-10)")
+    np.testing.assert_allclose(A, Ar, rtol=0, atol=1e-12 * np.abs(Ar).max())
+    np.testing.assert_allclose(b, br, rtol=0, atol=1e-12 * np.abs(br).max())
+    np.testing.assert_allclose(dxi, dxir, rtol=0, atol=1e-10 * np.abs(dxir).max())
+    np.testing.assert_allclose(g.dX, d["dX"], rtol=0, atol=1e-10 * np.abs(d["dX"]).max())
+    np.testing.assert_allclose(g.tX, d["trial_X"], rtol=0, atol=1e-10 * np.abs(d["dX"]).max())
+    np.testing.assert_allclose(g.tf / f0, d["trial_f"] / f0, rtol=0, atol=1e-11)
+    np.testing.assert_allclose(g.tu / f0, d["trial_u"] / f0, rtol=0, atol=1e-11)
+    np.testing.assert_allclose(g.tR, d["trial_R"], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(g.tt, d["trial_t"], rtol=0, atol=1e-11)
+    assert abs(E1 - float(d["E1"])) < 1e-12
+    # the 8-iteration trajectory, bounds of test_full_trajectory (outputs 1e-6; K's f, u in units of f0)
+    ba = O.OracleBundleAdjuster(d["x"], d["init_X"], d["init_K"], d["init_R"], d["init_t"], f0=f0, visibility_index=vis, axis=axis)
+    X, K, R, t = ba.optimize(10.0, 1e-8, 8, is_debug=True, verbose=False)
+    E = np.array([e["reprojection_error"] for e in ba.get_log()])
+    assert len(E) == len(d["E_log"])
+    assert ba.engine.n_solves == int(d["n_solves"])
+    n_obs = ba.engine.xy.shape[0]
+    assert abs(np.sqrt(E[-1] / n_obs) - np.sqrt(d["E_log"][-1] / n_obs)) < 1e-9
+    np.testing.assert_allclose(E, d["E_log"], rtol=1e-6, atol=1e-12)
+    np.testing.assert_allclose(X, d["out_X"], rtol=0, atol=1e-6)
+    assert (K[:, 2, 2] == f0).all() and (d["out_K"][:, 2, 2] == f0).all()
+    np.testing.assert_allclose(K / f0, d["out_K"] / f0, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(R, d["out_R"], rtol=0, atol=1e-6)
+    np.testing.assert_allclose(t, d["out_t"], rtol=0, atol=1e-6)
 
 
 @pytest.mark.parametrize("name,axis,args", [
