@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build-time check of the generated ISA of k_schur_slots and of the point-to-point back-substitution (run by the Makefile on mvba.s: the build FAILS when it fails).
+"""Build-time check of the generated ISA of k_schur_slots, k_schur_lanes and of the point-to-point back-substitution (run by the Makefile on mvba.s: the build FAILS when it fails).
 
 The slot kernel keeps two gathers in flight with COUNTED `s_waitcnt vmcnt(N)`: every vector-memory
 operation of its loops is inline assembly the compiler knows nothing about, and N is their number per iteration.
@@ -13,13 +13,19 @@ Correctness therefore rests on properties of the generated code that no C++ rule
   3. M0 (the LDS-DMA destination base) is written by the gathers' own `s_mov_b32 m0, ...` only;
   4. the kernel fits three waves per SIMD (<= 168 VGPRs); registers it spills are touched outside the loops only
      (that is property 1).
+k_schur_lanes (one lane per item, the same loop with 13 / 17 gathers in flight) is checked for properties 1 and 2.
 Usage: check_isa.py mvba.s   (exit status 0 = all properties hold)."""
 import re
 import sys
 
 # kernel -> (counted wait, LDS-DMA operations per iteration) of its diagonal / off-diagonal loop: the gathers + the indices
 # (a step's indices are ONE 256-byte row; a kernel that adopts the loop -- the unit form tried it in round 4 -- adds a line)
-KERNELS = {"k_schur_slots": (("vmcnt(7)", 7), ("vmcnt(8)", 8))}
+KERNELS = {"k_schur_slots": (("vmcnt(7)", 7), ("vmcnt(8)", 8)),
+           # one lane per item: 13 / 17 gathers stay in flight behind the index row, 14 / 18 operations per iteration; the wait
+           # stands in the prologue too, outside every loop
+           "k_schur_lanes": (("vmcnt(13)", 14), ("vmcnt(17)", 18))}
+# properties 3 and 4 (M0, three waves per SIMD) are k_schur_slots' alone: k_schur_lanes is launched one wave per SIMD
+SLOTS_ONLY = "k_schur_slots"
 VM_LOOP_OPS = ("global_load_lds_dwordx4", "global_load_lds_dword ")
 
 
@@ -28,6 +34,15 @@ def kernel_lines(text, name="k_schur_slots"):
     if not m:
         return None
     return [ln.strip() for ln in m.group(1).splitlines()]
+
+
+def in_loop(lines, i):
+    """Whether line i stands in a block the compiler annotated as part of a loop."""
+    for k in range(i, -1, -1):
+        m = re.match(r"\.(LBB\w+):(.*)", lines[k])
+        if m:
+            return "Loop" in m.group(2)
+    return False
 
 
 def loop_blocks(lines, wait_index):
@@ -69,6 +84,8 @@ def check_kernel(text, name, counts):
         return [f"{name} not found in the ISA"]
     for count, n_ops in counts:
         idx = [i for i, ln in enumerate(lines) if ln.startswith("s_waitcnt " + count)]
+        if name != SLOTS_ONLY:  # (the prologue's copy of the wait stands before the loop)
+            idx = [i for i in idx if in_loop(lines, i)]
         if len(idx) != 1:
             errs.append(f"{name}: expected one `s_waitcnt {count}` (the loop's counted wait), found {len(idx)}")
             continue
@@ -87,6 +104,8 @@ def check_kernel(text, name, counts):
         stray = [ln for ln in inner if ln.startswith(VM_LOOP_OPS)]
         if stray:
             errs.append(f"{name} {count} loop: LDS-DMA inside the pacing block: {stray[:3]}")
+    if name != SLOTS_ONLY:
+        return errs
     for ln in lines:
         if re.match(r"\w+\s+m0\b", ln) and not ln.startswith("s_mov_b32 m0,"):
             errs.append(f"{name}: M0 written outside the gathers' asm statements: {ln}")

@@ -5,7 +5,7 @@
 //   K1  k_resid_jac      residual + 2x3 / 2x9 Jacobian rows per observation   (ref :291-427)
 //   K2  (fused into K1)  E_a = 2 sum JxT Jx, dP_a = 2 sum JxT e               (ref :429-469, :519-556)
 //   K3a k_point_inv      damped 3x3 inverse, v_a = E^-1 dP_a                  (ref :120-128)
-//   K3  k_schur_slots (up to ~100 cameras) / k_schur_pairs + k_schur_reduce / k_schur_dense (full visibility)
+//   K3  k_schur_slots | k_schur_lanes (up to ~100 cameras) / k_schur_pairs + k_schur_reduce / k_schur_dense (full visibility)
 //                        A = G^ - sum F^T E^-1 F,  b = sum F^T E^-1 dP - dF   (ref :132-143, :471-517, :618-664)
 //   C1  ncclAllReduce    [A|b] across point shards                            
 //   K4  k_compact, k_chol_super / k_chol_trail64 / k_chol_trail32 / k_chol_backsolve_all (+ the k_lu_* rescue)
@@ -937,6 +937,28 @@ __device__ __forceinline__ void schur_slots_wave(const int4 *__restrict__ wdesc,
       int nseg, int lag, const long long *__restrict__ range_o0
 __global__ __launch_bounds__(64, 3) void k_schur_slots(MVBA_SLOTS_ARGS) {
   schur_slots_wave(wdesc, wunits, it_k, it_l, it_a, rec, PB, c, f0, partial, nR, seg_end, prog, nseg, lag, range_o0);
+}
+
+#include "mvba_lanes.h"  // the slot form with one lane per item: schur_lanes_unit, 64 lists per wave
+constexpr int slot_idx_ints(int W) { return W == LANES_W ? LANES_IDX : SLOT_IDX; }  // ints of a step's index row at width W
+
+// The slot form at 64 lists per wave (mvba_lanes.h): block b IS wave b / nR of range b % nR as above, its index rows are
+// 768 bytes and its unit ids 64 per wave.  Not paced: no counters to clear, the pacing table of the index is not read.
+__global__ __launch_bounds__(64, 1) void k_schur_lanes(const int4 *__restrict__ wdesc, const int *__restrict__ wunits,
+                                                       const int *__restrict__ it_x, const double2 *__restrict__ rec,
+                                                       const double *__restrict__ PB, double c, double f0,
+                                                       double *__restrict__ partial, int nR,
+                                                       const long long *__restrict__ range_o0) {
+  extern __shared__ char smem_pairs[];
+  const int bid = blockIdx.x;
+  const int MVBA_CONST_AS *dp = as_const(reinterpret_cast<const int *>(wdesc)) + 4 * (size_t)bid;
+  const int d_x = dp[0], d_y = dp[1], nsteps = dp[2], flags = dp[3];
+  if (nsteps <= 0) return;  // (wave-uniform) a wave whose lists are all empty in this range
+  const long long beg = ((long long)d_y << 32) | (unsigned)d_x;
+  const int *su = wunits + (size_t)bid * LANES_W;
+  const double2 *rec_r = rec + (size_t)as_const(range_o0)[bid % nR] * REC;  // record indices are relative to the range's first observation
+  if (flags & 1) schur_lanes_unit<true>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec_r, PB, c, 1.0 / f0, partial, su);
+  else schur_lanes_unit<false>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec_r, PB, c, 1.0 / f0, partial, su);
 }
 
 // One thread per element of a pair's block: the pair's unit partials in unit order -> packed strips.
@@ -2817,11 +2839,11 @@ __global__ void k_idx_bounds(int VP, int nR, const long long *__restrict__ vp_of
   lo[t] = b;
 }
 
-// The bounded-skew merge of one wave's 21 lists (see k_schur_slots), lane = slot.  FILL = false: count the steps.
-// FILL = true: write the step-major rows (record indices RELATIVE to the range's first observation), the pacing table
+// The bounded-skew merge of one wave's W lists (W = 21: k_schur_slots, 64: k_schur_lanes), lane = slot.  FILL = false: count the
+// steps.  FILL = true: write the step-major rows (record indices RELATIVE to the range's first observation), the pacing table
 // (steps taken when the slowest slot leaves a segment) and the padding rows (`pad_obs` = 0: the range's first record,
 // any finite one will do, times `pad_pt` = N: the all-zero point row).
-template <bool FILL>
+template <bool FILL, int W>
 __global__ __launch_bounds__(64) void k_idx_merge(long long n_waves, int nR, int nSeg, long long skew, long long segG,
                                                   const long long *__restrict__ sl_beg, const int *__restrict__ sl_len,
                                                   const long long *__restrict__ range_o0, const int *__restrict__ it_k,
@@ -2829,11 +2851,12 @@ __global__ __launch_bounds__(64) void k_idx_merge(long long n_waves, int nR, int
                                                   const long long *__restrict__ w_beg, int pad_obs, int pad_pt,
                                                   int *__restrict__ w_steps, int *__restrict__ st_k, int *__restrict__ st_l,
                                                   int *__restrict__ st_a, int *__restrict__ seg_end, const long long *__restrict__ pkey) {
+  static_assert(W >= 1 && W <= 64, "one lane per slot");
   const long long b = blockIdx.x;
   const int lane = threadIdx.x;
-  const bool slot = lane < PSTEP;
-  long long cur = slot ? sl_beg[b * PSTEP + lane] : 0;
-  const long long end = slot ? cur + sl_len[b * PSTEP + lane] : 0;
+  const bool slot = lane < W;
+  long long cur = slot ? sl_beg[b * W + lane] : 0;
+  const long long end = slot ? cur + sl_len[b * W + lane] : 0;
   const long long o_lo = range_o0[b % nR];
   const long long base = FILL ? w_beg[b] : 0;
   constexpr long long NONE = 1LL << 40;
@@ -2852,7 +2875,7 @@ __global__ __launch_bounds__(64) void k_idx_merge(long long n_waves, int nR, int
     if (lo >= NONE) break;
     const bool take = k0 < NONE && k0 <= lo + skew;
     if (FILL && slot) {
-      const long long o = (base + steps) * PSTEP + lane;
+      const long long o = (base + steps) * W + lane;
       st_k[o] = take ? (int)(it_k[cur] - o_lo) : pad_obs;  // record indices relative to the range's first observation
       st_l[o] = take ? (int)(it_l[cur] - o_lo) : pad_obs;
       st_a[o] = take ? it_a[cur] : pad_pt;
@@ -2872,15 +2895,16 @@ __global__ __launch_bounds__(64) void k_idx_merge(long long n_waves, int nR, int
   }
 }
 
-// the slot kernel's index: one 256-byte row per step, k[21] | l[21] | a[21] | pad -- ONE LDS-DMA instruction per step
-__global__ void k_idx_interleave(long long n_steps, const int *__restrict__ st_k, const int *__restrict__ st_l, const int *__restrict__ st_a,
-                                 int *__restrict__ out) {
+// the slot kernels' index: one row of `row` ints per step, k[W] | l[W] | a[W] | pad -- ONE LDS-DMA instruction per step
+// (W = 21: 64 ints = 256 bytes with 1 int of padding; W = 64: 192 ints = 768 bytes)
+__global__ void k_idx_interleave(long long n_steps, int W, int row, const int *__restrict__ st_k, const int *__restrict__ st_l,
+                                 const int *__restrict__ st_a, int *__restrict__ out) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_steps * SLOT_IDX) return;
-  const long long st = t / SLOT_IDX;
-  const int e = (int)(t - st * SLOT_IDX), which = e / PSTEP, sl = e - which * PSTEP;
+  if (t >= n_steps * row) return;
+  const long long st = t / row;
+  const int e = (int)(t - st * row), which = e / W, sl = e - which * W;
   const int *src = which == 0 ? st_k : (which == 1 ? st_l : st_a);
-  out[t] = which < 3 ? src[st * PSTEP + sl] : 0;
+  out[t] = which < 3 ? src[st * W + sl] : 0;
 }
 
 #include "mvba_cov.h"  // marginal covariances (mvba_covariance): S^-1 from the Cholesky factor and the point pass
@@ -2914,6 +2938,7 @@ struct mvba_handle {
   int schur_mode = 2;                 // SCHUR_PAIRS / SCHUR_SLOTS (see k_schur_slots) / SCHUR_DENSE
   long long n_items = 0, n_items_offdiag = 0, n_slot_items = 0;
   int n_units = 0, rccl_version = 0, q_max = 0, n_waves = 0, slot_nR = 8, slot_nseg = 0;
+  int slot_w = PSTEP;                 // slot form: lists per wave = items per step (21: k_schur_slots, 64: k_schur_lanes, not paced)
   long long *d_range_o0 = nullptr;    // slot form: first observation of every point range (the record base of its waves)
   int *d_seg_end = nullptr, *d_prog = nullptr;
   bool check_solve = false;           // MVBA_CHECK_SOLVE=1: every accepted dense solve is checked on the host against the packed system it solved
@@ -3222,7 +3247,7 @@ int launch_cost(mvba_handle *h, const double *cam15, const double *X) {
 // by itself, or turns on a diagnostic that changes no result.
 struct CreateKnobs {
   bool schur_set = false;                      // MVBA_SCHUR set at all (any value keeps a fully visible scene off the dense form
-  bool schur_slots = false, schur_pairs = false, schur_dense = false;  // ... unless it is `dense`)
+  bool schur_slots = false, schur_lanes = false, schur_pairs = false, schur_dense = false;  // ... unless it is `dense`)
   bool index_host = false, index_global = false;  // MVBA_INDEX=host | global: where the Schur index is built
   bool force_big = false;                      // MVBA_FORCE_BIG
   bool chol_launches = false;                  // MVBA_CHOL=launches
@@ -3239,6 +3264,7 @@ CreateKnobs read_create_knobs() {
   const char *schur = getenv("MVBA_SCHUR");
   k.schur_set = schur != nullptr;
   k.schur_slots = is(schur, "slots");
+  k.schur_lanes = is(schur, "lanes");
   k.schur_pairs = is(schur, "pairs");
   k.schur_dense = is(schur, "dense");
   const char *index = getenv("MVBA_INDEX");
@@ -3396,7 +3422,7 @@ void launch_point_inv(mvba_handle *h, double c) {  // K3a (also clears the packe
   const long long nAb = (long long)(nA + n9);
   const unsigned grid = (unsigned)std::max<long long>((h->N + 255) / 256, std::min<long long>((nAb + 1023) / 1024, 4096));
   hipLaunchKernelGGL(k_point_inv, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
-                     h->d_Ab, nAb, h->d_prog, (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE,
+                     h->d_Ab, nAb, h->d_prog, h->slot_w == LANES_W ? 0 : (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE,
                      h->schur_mode == SCHUR_DENSE ? 1 : 0);
 }
 
@@ -3407,7 +3433,11 @@ void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b]
   if (h->use_pairs) {
     // 64-bit offsets only when the records or the point blocks (+ the padding row) span 4 GiB (MVBA_FORCE_BIG: at test sizes too)
     const bool big = (std::max<long long>(h->nobs, h->N) + 1) * 128LL >= (1LL << 32) || h->force_big;
-    if (h->schur_mode == SCHUR_SLOTS) {
+    if (h->schur_mode == SCHUR_SLOTS && h->slot_w == LANES_W) {
+      if (h->n_waves)
+        hipLaunchKernelGGL(k_schur_lanes, dim3(h->n_waves), dim3(64), LANES_LDS, h->stream, h->d_wdesc, h->d_wunits, h->d_it_x, h->d_rec, h->d_PB, c,
+                           h->f0, h->d_partial, h->slot_nR, h->d_range_o0);
+    } else if (h->schur_mode == SCHUR_SLOTS) {
       if (h->n_waves)
         hipLaunchKernelGGL(k_schur_slots, dim3(h->n_waves), dim3(64), SLOT_LDS, h->stream, h->d_wdesc,
                            h->d_wunits, h->d_it_x, (const int *)nullptr, (const int *)nullptr, h->d_rec, h->d_PB, c, h->f0, h->d_partial,
@@ -4062,7 +4092,7 @@ int mvba_get_info(mvba_handle *h, int64_t *out8) {
   out8[0] = h->n_items;
   out8[1] = h->n_items_offdiag;
   out8[2] = h->n_units;
-  out8[3] = h->schur_mode;
+  out8[3] = h->schur_mode | (h->schur_mode == SCHUR_SLOTS ? h->slot_w << 8 : 0);  // bits 8..15: the slot form's step width
   out8[4] = h->rccl_version;
   out8[5] = NCCL_VERSION_CODE;
   out8[6] = h->nranks;
@@ -4201,13 +4231,14 @@ int mvba_debug_read(mvba_handle *h, int32_t which, double *out, int64_t capacity
   } else if (which == MVBA_BUF_TRIAL_CAM) {
     MVBA_HIP(d2h(h->d_cam15[1 - h->cur], sizeof(double) * cnt));
   } else if (which >= MVBA_BUF_INDEX_K && which <= MVBA_BUF_INDEX_SEG) {  // the Schur index as the kernel reads it (ints, widened)
-    if (h->schur_mode == SCHUR_SLOTS && which != MVBA_BUF_INDEX_SEG) {  // one 64-int row per step: k[21] | l[21] | a[21] | pad
-      const long long n_steps = cnt / PSTEP;
-      std::vector<int> tmp((size_t)n_steps * SLOT_IDX);
+    if (h->schur_mode == SCHUR_SLOTS && which != MVBA_BUF_INDEX_SEG) {  // one row per step: k[W] | l[W] | a[W] | pad
+      const int W = h->slot_w, row = slot_idx_ints(W);
+      const long long n_steps = cnt / W;
+      std::vector<int> tmp((size_t)n_steps * row);
       if (cnt) MVBA_HIP(hipMemcpy(tmp.data(), h->d_it_x, sizeof(int) * tmp.size(), hipMemcpyDeviceToHost));
-      const int off = which == MVBA_BUF_INDEX_K ? 0 : (which == MVBA_BUF_INDEX_L ? PSTEP : 2 * PSTEP);
+      const int off = which == MVBA_BUF_INDEX_K ? 0 : (which == MVBA_BUF_INDEX_L ? W : 2 * W);
       for (long long st = 0; st < n_steps; ++st)
-        for (int sl = 0; sl < PSTEP; ++sl) out[st * PSTEP + sl] = (double)tmp[(size_t)st * SLOT_IDX + off + sl];
+        for (int sl = 0; sl < W; ++sl) out[st * W + sl] = (double)tmp[(size_t)st * row + off + sl];
       return MVBA_OK;
     }
     const int *src = which == MVBA_BUF_INDEX_K ? h->d_it_k : (which == MVBA_BUF_INDEX_L ? h->d_it_l : (which == MVBA_BUF_INDEX_A ? h->d_it_a : h->d_seg_end));

@@ -7,7 +7,7 @@
 //   validate_problem      argument checks, point of every observation
 //   build_k1_tiles        K1's wave tiles and the pieces of points with more than 64 observations
 //   k1_block_threads      K1's block size
-//   decide_schur_form     THE decision between the dense, slot and unit forms of K3, with the sub-list sizes and point ranges
+//   decide_schur_form     THE decision between the dense, slot (21 or 64 lists per wave) and unit forms of K3, with the sub-list sizes and point ranges
 //   build_index_host      the pair-major index on host threads (MVBA_INDEX=host)        } both fill one SchurIndex, entry for
 //   build_index_device    the same index by the k_idx_* kernels                         } entry the same (tests/test_schur_index*)
 //   alloc_engine_buffers, upload_engine, set_kernel_attributes
@@ -164,7 +164,9 @@ struct PairLists {
   std::vector<int> S, vp_ptr;
   int VP = 0;
   std::vector<long long> vp_off;
-  long long slot_waves = 0;    // slot form: waves (of 21 lists) per range, diagonal + off-diagonal
+  long long n_diag_lists = 0, n_off_lists = 0;
+  // slot form: waves (of W lists) per range, diagonal + off-diagonal
+  long long slot_waves(int W) const { return (n_diag_lists + W - 1) / W + (n_off_lists + W - 1) / W; }
 };
 
 int size_pair_lists(const IndexInput &in, PairLists &L) {
@@ -197,12 +199,10 @@ int size_pair_lists(const IndexInput &in, PairLists &L) {
     L.vp_ptr[q + 1] = L.vp_ptr[q] + L.S[q];
   }
   L.VP = L.vp_ptr[P];
-  long long n_diag_lists = 0, n_off_lists = 0;
   for (int k = 0; k < m; ++k) {
-    n_diag_lists += L.S[pair_id(m, k, k)];
-    for (int l = k + 1; l < m; ++l) n_off_lists += L.S[pair_id(m, k, l)];
+    L.n_diag_lists += L.S[pair_id(m, k, k)];
+    for (int l = k + 1; l < m; ++l) L.n_off_lists += L.S[pair_id(m, k, l)];
   }
-  L.slot_waves = (n_diag_lists + PSTEP - 1) / PSTEP + (n_off_lists + PSTEP - 1) / PSTEP;
   // The points are swept in their natural order: an item's key (where its point sits in the sweep, in observations) is its
   // point's first observation, pt_ptr[a].  (A low-discrepancy order -- round 4 -- cut the padding rows from 12.4 % to 10.4 %
   // at config 3 but k_schur_slots only from 1.691 to 1.677 ms, for 0.12 s more of mvba_create: profiles/r04_sweep_point_order.txt.)
@@ -220,11 +220,11 @@ struct PointRanges {
   std::vector<long long> lo;  // [nR + 1] first point of every range
 };
 
-PointRanges make_ranges(const IndexInput &in, const PairLists &L, bool slots, int xcd_waves) {
+PointRanges make_ranges(const IndexInput &in, const PairLists &L, bool slots, int xcd_waves, int W) {
   PointRanges R;
   const long long N = in.N;
   if (slots) {
-    const long long j = std::max<long long>(1, std::min<long long>(xcd_waves / std::max(1LL, L.slot_waves), L.target / (8 * 64)));
+    const long long j = std::max<long long>(1, std::min<long long>(xcd_waves / std::max(1LL, L.slot_waves(W)), L.target / (8 * 64)));
     R.nR = (int)(8 * std::min<long long>(j, 8));
     R.lo.assign(R.nR + 1, 0);
     // equal ITEM counts: the ranges run side by side, one per XCD
@@ -245,9 +245,17 @@ PointRanges make_ranges(const IndexInput &in, const PairLists &L, bool slots, in
   return R;
 }
 
+// Tuning of the slot form with one lane per item (k_schur_lanes), measured at config 3 and on its camera sweep (DESIGN.md §3.1,
+// profiles/r06_lanes_product.txt)
+constexpr long long LANES_SKEW = 12288;     // bounded skew of its step merge over 64 slots (twice that: fewer padding rows, slower)
+// taken by mvba_create itself from this many waves per point range on: 1 M points x 10 %, 90 cameras (78 waves) 1.40 against 1.44 ms for k_schur_slots,
+// 80 cameras (63 waves: a third of the XCD's 96 wave places stay empty) 1.32 against 1.19
+constexpr long long LANES_MIN_WAVES = 78;
+
 // What decide_schur_form answers: the form, and for the pair-major forms the lists and ranges the index is built from
 struct SchurPlan {
   int mode = SCHUR_SLOTS;
+  int W = PSTEP;               // SCHUR_SLOTS: lists per wave = items per step (PSTEP: k_schur_slots, LANES_W: k_schur_lanes)
   std::vector<int> dense_obs;  // SCHUR_DENSE with missing observations: [N][m] observation of (point, camera) or -1
   PairLists L;
   PointRanges R;
@@ -298,30 +306,44 @@ int decide_schur_form(const IndexInput &in, const CreateKnobs &knobs, int loss, 
   // TOGETHER resident on one XCD at once -- 9 waves per CU (LDS) x n_cu / 8 CUs x 21 slots = 6048 lists.  Up to ~100
   // cameras at 10 % visibility (4950 pairs + ~1000 sub-lists of the diagonal pairs) that is every list.  Beyond that
   // the engine takes the unit form (cutting the cameras into groups swept in rounds lost to it on every workload
-  // measured: DESIGN.md 3.1, "Round 4").
+  // measured: DESIGN.md 3.1, "Round 4").  The same form with one lane per item (k_schur_lanes, 64 lists per wave) has
+  // 3 waves per CU: 96 waves = 6144 lists per XCD.
   int n_cu_dev = 256;
   hipDeviceGetAttribute(&n_cu_dev, hipDeviceAttributeMultiprocessorCount, device);
-  const int xcd_waves = std::max(1, n_cu_dev / 8) * (160 * 1024 / SLOT_LDS);  // 9 waves of 17,136 B of LDS per CU
+  auto xcd_waves = [&](int W) { return std::max(1, n_cu_dev / 8) * (W == LANES_W ? 160 * 1024 / LANES_LDS : 160 * 1024 / SLOT_LDS); };
   // (below ~4 M items the launch is all prologue and pacing: the unit form's many short waves win -- config 2,
-  // 10k points x 20 cameras: 0.095 against 0.124 ms; equal at 5.5 M items; MVBA_SCHUR=slots keeps the slot form)
-  const bool slots_forced = knobs.schur_slots;
+  // 10k points x 20 cameras: 0.095 against 0.124 ms; equal at 5.5 M items; MVBA_SCHUR=slots | lanes keeps the slot form)
+  const bool slots_forced = knobs.schur_slots || knobs.schur_lanes;
   // (a robust loss never takes the slot form: the unit form then, as when the lists do not fit one round -- DESIGN.md §12)
   // (the gathers use 32-bit byte offsets: point rows from the array's start, records from their RANGE's first
-  // observation -- the latter checked in the loop, once the ranges are known)
-  const bool try_slots = !knobs.schur_pairs && loss == LOSS_SQUARED && !(L.slot_waves > xcd_waves || (N + 1) * 128LL >= (1LL << 32) || knobs.force_big ||
-                                                                         (L.T < 4000000 && !slots_forced));
-  // the slot form first where it may run; what only its ranges can tell demotes it to the unit form, whose ranges are then made
-  for (plan.mode = try_slots ? SCHUR_SLOTS : SCHUR_PAIRS;; plan.mode = SCHUR_PAIRS) {
-    plan.R = make_ranges(in, L, plan.mode == SCHUR_SLOTS, xcd_waves);
-    if (plan.mode == SCHUR_PAIRS) break;
+  // observation -- the latter checked per plan, once the ranges are known)
+  const bool may_slots = !knobs.schur_pairs && loss == LOSS_SQUARED && (N + 1) * 128LL < (1LL << 32) && !knobs.force_big && (L.T >= 4000000 || slots_forced);
+  // the slot form at W lists per wave: its point ranges, or false where it may not run
+  auto slot_plan = [&](int W, PointRanges &R) {
+    if (!may_slots || L.slot_waves(W) > xcd_waves(W)) return false;
+    R = make_ranges(in, L, true, xcd_waves(W), W);
     // (few cameras with dense visibility: a dozen cameras are 78 lists = 5 waves per range, 320 waves on the whole chip even with 64
     // ranges -- 1 M points x 12 cameras, all visible: 9.3 ms against 4.9 for the unit form; at 20 cameras, 704 waves, the slot form is
     // ahead again, 9.8 against 10.8: profiles/r05_sweep_few_cameras.txt)
-    if (!slots_forced && plan.R.nR * L.slot_waves < 512) continue;
+    if (W == PSTEP && !slots_forced && R.nR * L.slot_waves(W) < 512) return false;
     long long widest = 0;
-    for (int r = 0; r < plan.R.nR; ++r) widest = std::max<long long>(widest, p->pt_ptr[plan.R.lo[r + 1]] - p->pt_ptr[plan.R.lo[r]]);
-    if ((widest + 1) * 128LL >= (1LL << 32)) continue;  // a range's records span 4 GiB: the unit form's 64-bit-offset build
-    break;
+    for (int r = 0; r < R.nR; ++r) widest = std::max<long long>(widest, p->pt_ptr[R.lo[r + 1]] - p->pt_ptr[R.lo[r]]);
+    return (widest + 1) * 128LL < (1LL << 32);  // (a range's records span 4 GiB: the unit form's 64-bit-offset build)
+  };
+  // The slot form first where it may run, else the unit form.  One lane per item (W = 64) by itself only where k_schur_slots
+  // would run too and a range has LANES_MIN_WAVES .. 96 waves of 64 lists; MVBA_SCHUR=lanes asks for it wherever its own
+  // capacity holds and falls back to k_schur_slots, then to the unit form; MVBA_SCHUR=slots keeps k_schur_slots.
+  PointRanges R21, R64;
+  const bool fits21 = slot_plan(PSTEP, R21);
+  const bool lanes = knobs.schur_lanes ? slot_plan(LANES_W, R64)
+                                       : (fits21 && !knobs.schur_slots && L.slot_waves(LANES_W) >= LANES_MIN_WAVES && slot_plan(LANES_W, R64));
+  if (lanes) {
+    plan.mode = SCHUR_SLOTS; plan.W = LANES_W; plan.R = std::move(R64);
+  } else if (fits21) {
+    plan.mode = SCHUR_SLOTS; plan.W = PSTEP; plan.R = std::move(R21);
+  } else {
+    plan.mode = SCHUR_PAIRS;
+    plan.R = make_ranges(in, L, false, 0, PSTEP);
   }
   return MVBA_OK;
 }
@@ -334,9 +356,9 @@ struct SchurIndex {
   std::vector<int> unit_ptr;          // [P + 1] first unit of every pair
   std::vector<int> q_ptr = std::vector<int>(9, 0), q_units;  // unit form: the work queue of every XCD
   std::vector<int4> wdesc;            // slot form: (first step lo, hi, steps, flags) per wave
-  std::vector<int> wunits, seg_end;   // ... its 21 units, and the steps taken at the end of every pacing segment
+  std::vector<int> wunits, seg_end;   // ... its W units, and the steps taken at the end of every pacing segment
   long long n_items = 0, n_items_offdiag = 0, n_slot_items = 0;  // what mvba_get_info reports
-  int n_waves = 0, slot_nR = 8, slot_nseg = 0;
+  int n_waves = 0, slot_nR = 8, slot_nseg = 0, slot_w = PSTEP;
   bool on_device = false;
   int *d_it_k = nullptr, *d_it_l = nullptr, *d_it_a = nullptr, *d_seg_end = nullptr;
   long long *d_range_o0 = nullptr;    // slot form: first observation of every range
@@ -393,6 +415,7 @@ void build_work_queues(const IndexInput &in, const SchurPlan &plan, const std::v
 constexpr long long SLOT_SKEW = 12288;  // bounded skew of the step merge
 constexpr long long SLOT_SEG = 8192;    // pacing segment
 constexpr int SLOT_LAG = 4;             // a wave enters segment j only when all waves of its range have left segment j - lag
+constexpr long long slot_skew(int W) { return W == LANES_W ? LANES_SKEW : SLOT_SKEW; }
 
 // The slot form's waves: block b = nR w + r is wave w of range r and runs on XCD r % 8.  sl_beg / sl_len: the span of items
 // each of its 21 slots merges (from the units); w_steps / w_beg: the steps it takes and its first step, once merged.
@@ -404,14 +427,15 @@ struct SlotWaves {
   std::vector<int> sl_len;
 };
 
-// ---- waves of 21 lists, every wave once per range; the diagonal pairs' sub-lists come FIRST: a CU's SIMDs
+// ---- waves of W = 21 (64: k_schur_lanes) lists, every wave once per range; the diagonal pairs' sub-lists come FIRST: a CU's SIMDs
 // arbitrate by age, the blocks dispatched last share a SIMD three ways as its youngest wave and fall behind --
 // and a diagonal step is the dearer one
 SlotWaves make_slot_waves(const IndexInput &in, const SchurPlan &plan, const std::vector<int> &uid, SchurIndex &ix) {
   const int m = in.m, nR = plan.R.nR;
   const PairLists &L = plan.L;
+  const int W = plan.W;
   SlotWaves sw;
-  std::vector<int> wl;  // [wave of a range][21] list ids v = vp_ptr[pair] + sub-list, -1: none
+  std::vector<int> wl;  // [wave of a range][W] list ids v = vp_ptr[pair] + sub-list, -1: none
   std::vector<int> diag_lists, off_lists;
   for (int k = 0; k < m; ++k) {
     for (int sI = 0; sI < L.S[pair_id(m, k, k)]; ++sI) diag_lists.push_back(L.vp_ptr[pair_id(m, k, k)] + sI);
@@ -419,26 +443,26 @@ SlotWaves make_slot_waves(const IndexInput &in, const SchurPlan &plan, const std
       for (int sI = 0; sI < L.S[pair_id(m, k, l)]; ++sI) off_lists.push_back(L.vp_ptr[pair_id(m, k, l)] + sI);
   }
   for (const std::vector<int> *src : {&diag_lists, &off_lists})
-    for (size_t first = 0; first < src->size(); first += PSTEP) {
-      for (int sl = 0; sl < PSTEP; ++sl) wl.push_back(first + sl < src->size() ? (*src)[first + sl] : -1);
+    for (size_t first = 0; first < src->size(); first += W) {
+      for (int sl = 0; sl < W; ++sl) wl.push_back(first + sl < src->size() ? (*src)[first + sl] : -1);
       sw.w_isdiag.push_back(src == &diag_lists);
     }
   const long long n_waves = sw.n_waves = (long long)sw.w_isdiag.size() * nR;
   ix.wdesc.assign(n_waves, make_int4(0, 0, 0, 0));
-  ix.wunits.assign((size_t)n_waves * PSTEP, -1);
+  ix.wunits.assign((size_t)n_waves * W, -1);
   sw.w_steps.assign(n_waves, 0);
   sw.w_beg.assign(n_waves + 1, 0);
-  sw.sl_beg.assign((size_t)n_waves * PSTEP, 0);
-  sw.sl_len.assign((size_t)n_waves * PSTEP, 0);
+  sw.sl_beg.assign((size_t)n_waves * W, 0);
+  sw.sl_len.assign((size_t)n_waves * W, 0);
   for (long long b = 0; b < n_waves; ++b) {
-    const int *vs = wl.data() + (size_t)(b / nR) * PSTEP;
+    const int *vs = wl.data() + (size_t)(b / nR) * W;
     const int r = (int)(b % nR);
-    for (int sl = 0; sl < PSTEP; ++sl) {
+    for (int sl = 0; sl < W; ++sl) {
       const int id = vs[sl] >= 0 ? uid[(size_t)vs[sl] * nR + r] : -1;
-      ix.wunits[(size_t)b * PSTEP + sl] = id;
+      ix.wunits[(size_t)b * W + sl] = id;
       if (id < 0) continue;
-      sw.sl_beg[(size_t)b * PSTEP + sl] = ((long long)ix.units[id].y << 32) | (unsigned)ix.units[id].x;
-      sw.sl_len[(size_t)b * PSTEP + sl] = ix.units[id].z;
+      sw.sl_beg[(size_t)b * W + sl] = ((long long)ix.units[id].y << 32) | (unsigned)ix.units[id].x;
+      sw.sl_len[(size_t)b * W + sl] = ix.units[id].z;
     }
   }
   // pacing segments: seg_end[b][j] = steps wave b has taken when its slowest slot leaves segment j of the range
@@ -460,22 +484,23 @@ int upload_range_o0(const IndexInput &in, const PointRanges &R, DevBufs &engine,
 
 // the waves' first steps from their step counts; the size of the step-major index against what the device has
 int place_slot_steps(const SchurPlan &plan, SlotWaves &sw, const SchurIndex &ix, long long &total_steps) {
+  const int W = plan.W;
   for (long long b = 0; b < sw.n_waves; ++b) sw.w_beg[b + 1] = sw.w_beg[b] + sw.w_steps[b];
   total_steps = sw.w_beg[sw.n_waves];
-  if (total_steps * PSTEP >= (1LL << 40)) return fail(MVBA_ERR_BADARG, "too many (point, camera pair) items");
+  if (total_steps * W >= (1LL << 40)) return fail(MVBA_ERR_BADARG, "too many (point, camera pair) items");
   // the step-major index -- its size follows the padding rows -- against the memory that is
   // there, BEFORE anything of it is allocated: three 4-byte arrays of step rows, then the interleaved 256-byte rows beside them
-  const size_t need = (size_t)total_steps * PSTEP * 12 + (size_t)total_steps * SLOT_IDX * 4 + ix.seg_end.size() * 4;
+  const size_t need = (size_t)total_steps * W * 12 + (size_t)total_steps * slot_idx_ints(W) * 4 + ix.seg_end.size() * 4;
   size_t fr = 0, tot = 0;
   if (hipMemGetInfo(&fr, &tot) == hipSuccess && need > fr)
-    return fail(MVBA_ERR_BADARG, "the slot-form Schur index needs " + std::to_string(need >> 20) + " MiB (" + std::to_string(total_steps * PSTEP) + " step rows for " +
-                                     std::to_string(plan.L.T) + " items: " + std::to_string(plan.R.nR) + " ranges, skew " + std::to_string(SLOT_SKEW) + "), " +
+    return fail(MVBA_ERR_BADARG, "the slot-form Schur index needs " + std::to_string(need >> 20) + " MiB (" + std::to_string(total_steps * W) + " step rows for " +
+                                     std::to_string(plan.L.T) + " items: " + std::to_string(plan.R.nR) + " ranges, skew " + std::to_string(slot_skew(W)) + "), " +
                                      std::to_string(fr >> 20) + " MiB of device memory are free: use MVBA_SCHUR=pairs");
   return MVBA_OK;
 }
 
-void finish_slot_waves(const PointRanges &R, const SlotWaves &sw, long long total_steps, SchurIndex &ix) {
-  const int nR = R.nR;
+void finish_slot_waves(const SchurPlan &plan, const SlotWaves &sw, long long total_steps, SchurIndex &ix) {
+  const int nR = plan.R.nR, W = plan.W;
   std::vector<int> live(nR, 0);  // waves of a range that run at all: what a pacing counter has to reach
   for (long long b = 0; b < sw.n_waves; ++b) live[b % nR] += sw.w_steps[b] > 0;
   for (long long b = 0; b < sw.n_waves; ++b) {
@@ -486,7 +511,8 @@ void finish_slot_waves(const PointRanges &R, const SlotWaves &sw, long long tota
   }
   ix.n_waves = (int)sw.n_waves;
   ix.slot_nR = nR;
-  ix.n_slot_items = total_steps * PSTEP;
+  ix.n_slot_items = total_steps * W;
+  ix.slot_w = W;
 }
 
 // ---------------------------------------------------------------- the index on host threads (MVBA_INDEX=host)
@@ -544,15 +570,17 @@ int build_index_host(const IndexInput &in, const SchurPlan &plan, DevBufs &engin
   timer.lap("units");
   if (plan.mode == SCHUR_SLOTS) {
     SlotWaves sw = make_slot_waves(in, plan, uid, ix);
-    const int nSeg = sw.nSeg;
+    const int nSeg = sw.nSeg, W = plan.W;
+    const long long skew = slot_skew(W);
+    static_assert(PSTEP <= LANES_W, "the merge's cursors");
     std::vector<int> st_k, st_l, st_a;
     // Bounded-skew merge of a wave's lists into steps (see k_schur_slots)
     auto merge = [&](long long b, long long base, bool fill) {
       const int r = (int)(b % nR);
-      long long cur[PSTEP], end[PSTEP];
-      for (int sl = 0; sl < PSTEP; ++sl) {
-        cur[sl] = sw.sl_beg[(size_t)b * PSTEP + sl];
-        end[sl] = cur[sl] + sw.sl_len[(size_t)b * PSTEP + sl];
+      long long cur[LANES_W], end[LANES_W];
+      for (int sl = 0; sl < W; ++sl) {
+        cur[sl] = sw.sl_beg[(size_t)b * W + sl];
+        end[sl] = cur[sl] + sw.sl_len[(size_t)b * W + sl];
       }
       long long steps = 0;
       const long long o_lo = p->pt_ptr[R.lo[r]];
@@ -560,15 +588,15 @@ int build_index_host(const IndexInput &in, const SchurPlan &plan, DevBufs &engin
       auto key_of = [&](int sl) { return p->pt_ptr[it_a[cur[sl]]]; };  // where the item's point sits in the sweep, in observations
       while (true) {
         long long lo = -1;
-        for (int sl = 0; sl < PSTEP; ++sl)
+        for (int sl = 0; sl < W; ++sl)
           if (cur[sl] < end[sl] && (lo < 0 || key_of(sl) < lo)) lo = key_of(sl);
         if (fill && lo >= 0)
           while (sg < nSeg && lo >= o_lo + (sg + 1) * SLOT_SEG) ix.seg_end[(size_t)b * nSeg + sg++] = (int)steps;
         if (lo < 0) break;
-        for (int sl = 0; sl < PSTEP; ++sl) {
-          const bool take = cur[sl] < end[sl] && key_of(sl) <= lo + SLOT_SKEW;
+        for (int sl = 0; sl < W; ++sl) {
+          const bool take = cur[sl] < end[sl] && key_of(sl) <= lo + skew;
           if (fill) {
-            const long long o = (base + steps) * PSTEP + sl;
+            const long long o = (base + steps) * W + sl;
             if (take) { st_k[o] = (int)(it_k[cur[sl]] - o_lo); st_l[o] = (int)(it_l[cur[sl]] - o_lo); st_a[o] = it_a[cur[sl]]; }
             else { st_k[o] = st_l[o] = 0; st_a[o] = (int)N; }  // the range's first record (any finite one) x the all-zero point row
           }
@@ -587,13 +615,13 @@ int build_index_host(const IndexInput &in, const SchurPlan &plan, DevBufs &engin
     timer.lap("slot merge (count)");
     long long total_steps = 0;
     CR(place_slot_steps(plan, sw, ix, total_steps));
-    st_k.resize(total_steps * PSTEP); st_l.resize(total_steps * PSTEP); st_a.resize(total_steps * PSTEP);
+    st_k.resize(total_steps * W); st_l.resize(total_steps * W); st_a.resize(total_steps * W);
     on_threads(n_thr, [&](int tid) {
       for (long long b = tid; b < sw.n_waves; b += n_thr)
         if (sw.w_steps[b]) merge(b, sw.w_beg[b], true);
     });
     timer.lap("slot merge (fill)");
-    finish_slot_waves(R, sw, total_steps, ix);
+    finish_slot_waves(plan, sw, total_steps, ix);
     it_k.swap(st_k); it_l.swap(st_l); it_a.swap(st_a);  // what is uploaded: the step-major arrays
   } else {
     build_work_queues(in, plan, uid, ix);
@@ -684,7 +712,10 @@ int build_index_device(const IndexInput &in, const SchurPlan &plan, DeviceIndexB
     CR(tmp.alloc(&d_wsteps, (size_t)n_waves)); CR(tmp.alloc(&d_wbeg, (size_t)n_waves + 1));
     CRH(hipMemcpyAsync(d_slbeg, sw.sl_beg.data(), sizeof(long long) * sw.sl_beg.size(), hipMemcpyHostToDevice, stream));
     CRH(hipMemcpyAsync(d_sllen, sw.sl_len.data(), sizeof(int) * sw.sl_len.size(), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_idx_merge<false>, dim3((unsigned)n_waves), dim3(64), 0, stream, n_waves, nR, nSeg, SLOT_SKEW, SLOT_SEG, d_slbeg, d_sllen,
+    const int W = plan.W;
+    const auto merge_count = W == LANES_W ? k_idx_merge<false, LANES_W> : k_idx_merge<false, PSTEP>;
+    const auto merge_fill = W == LANES_W ? k_idx_merge<true, LANES_W> : k_idx_merge<true, PSTEP>;
+    hipLaunchKernelGGL(merge_count, dim3((unsigned)n_waves), dim3(64), 0, stream, n_waves, nR, nSeg, slot_skew(W), SLOT_SEG, d_slbeg, d_sllen,
                        ix.d_range_o0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, (int *)nullptr, (int *)nullptr, (int *)nullptr,
                        (int *)nullptr, (const long long *)in.d_pt_ptr);
     std::vector<int> ws32(n_waves);
@@ -695,16 +726,16 @@ int build_index_device(const IndexInput &in, const SchurPlan &plan, DeviceIndexB
     long long total_steps = 0;
     CR(place_slot_steps(plan, sw, ix, total_steps));
     // the step-major arrays are written where the kernel will read them
-    const size_t rows = (size_t)total_steps * PSTEP;
+    const size_t rows = (size_t)total_steps * W;
     CR(engine.alloc(&ix.d_it_k, rows)); CR(engine.alloc(&ix.d_it_l, rows)); CR(engine.alloc(&ix.d_it_a, rows));
     CR(engine.alloc(&ix.d_seg_end, ix.seg_end.size()));
     CRH(hipMemcpyAsync(d_wbeg, sw.w_beg.data(), sizeof(long long) * (n_waves + 1), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_idx_merge<true>, dim3((unsigned)n_waves), dim3(64), 0, stream, n_waves, nR, nSeg, SLOT_SKEW, SLOT_SEG, d_slbeg, d_sllen,
+    hipLaunchKernelGGL(merge_fill, dim3((unsigned)n_waves), dim3(64), 0, stream, n_waves, nR, nSeg, slot_skew(W), SLOT_SEG, d_slbeg, d_sllen,
                        ix.d_range_o0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, ix.d_it_k, ix.d_it_l, ix.d_it_a, ix.d_seg_end, (const long long *)in.d_pt_ptr);
     CRH(hipGetLastError());
     CRH(hipStreamSynchronize(stream));
     timer.lap("slot merge (fill)");
-    finish_slot_waves(R, sw, total_steps, ix);
+    finish_slot_waves(plan, sw, total_steps, ix);
   } else {
     build_work_queues(in, plan, uid, ix);
     // the pair-major arrays stay where the fill kernel wrote them
@@ -771,6 +802,7 @@ int upload_schur_index(mvba_handle *h, const SchurPlan &plan, SchurIndex &ix) {
   h->n_items_offdiag = plan.L.T - plan.L.Tdiag;
   h->n_units = (int)ix.units.size();
   h->n_waves = ix.n_waves; h->slot_nR = ix.slot_nR; h->slot_nseg = ix.slot_nseg; h->n_slot_items = ix.n_slot_items;
+  h->slot_w = ix.slot_w;
   h->index_on_device = ix.on_device;
   h->d_range_o0 = ix.d_range_o0;
   if (ix.on_device) { h->d_it_k = ix.d_it_k; h->d_it_l = ix.d_it_l; h->d_it_a = ix.d_it_a; h->d_seg_end = ix.d_seg_end; }
@@ -803,10 +835,11 @@ int upload_schur_index(mvba_handle *h, const SchurPlan &plan, SchurIndex &ix) {
     }
     if (!ix.q_units.empty()) CRH(hipMemcpy(h->d_q_units, ix.q_units.data(), sizeof(int) * ix.q_units.size(), hipMemcpyHostToDevice));
   }
-  if (h->schur_mode == SCHUR_SLOTS && h->n_slot_items) {  // the three step-major arrays -> one 256-byte row per step; they go
-    const long long n_steps = h->n_slot_items / PSTEP;
-    CR(h->mem.alloc(&h->d_it_x, (size_t)n_steps * SLOT_IDX));
-    hipLaunchKernelGGL(k_idx_interleave, dim3((unsigned)((n_steps * SLOT_IDX + 255) / 256)), dim3(256), 0, h->stream, n_steps, h->d_it_k, h->d_it_l,
+  if (h->schur_mode == SCHUR_SLOTS && h->n_slot_items) {  // the three step-major arrays -> one 256-byte (768: 64 slots) row per step; they go
+    const int W = h->slot_w, row = slot_idx_ints(W);
+    const long long n_steps = h->n_slot_items / W;
+    CR(h->mem.alloc(&h->d_it_x, (size_t)n_steps * row));
+    hipLaunchKernelGGL(k_idx_interleave, dim3((unsigned)((n_steps * row + 255) / 256)), dim3(256), 0, h->stream, n_steps, W, row, h->d_it_k, h->d_it_l,
                        h->d_it_a, h->d_it_x);
     CRH(hipGetLastError());
     CRH(hipStreamSynchronize(h->stream));

@@ -389,8 +389,10 @@ class HipEngine:
 
     def schur_info(self):
         i = self._info()
+        # slot form: step-major rows incl. the padding rows of the bounded-skew merge, and the step width = lists per wave
+        # (21: k_schur_slots, three lanes per item; 64: k_schur_lanes, one lane per item -- "slots" either way; 0: no slot form)
         return {"items": i[0], "offdiag_items": i[1], "units": i[2], "kernel": ("strip", "pairs", "slots", "dense")[i[3] & 0xff],
-                "slot_rows": i[7]}  # slot form: step-major rows incl. the padding rows of the bounded-skew merge
+                "slot_rows": i[7], "step_width": (i[3] >> 8) & 0xff}
 
     def rccl_version(self):
         i = self._info()
