@@ -108,6 +108,14 @@ SIGNATURES = {
                                      _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_int32]),
     "mvba_resect_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "mvba_pose_robust": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int32,
+                                   C.POINTER(C.c_uint8), _dp, C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_int32, C.c_uint64,
+                                   C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_pose_refine": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int32,
+                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _dp, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _dp, _dp,
+                                   _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_pose_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "mvba_triangulate_robust": (C.c_int, [_dp, _dp, _dp, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64,
                                           C.c_double, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _dp,
@@ -609,6 +617,87 @@ def resect_sample(seed, k, h, n):
     lib = load_library()
     idx = np.empty(6, np.int64)
     raise_for(lib.mvba_resect_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
+    return idx
+
+
+def _pose_args(X, pt_ptr, cam_idx, xy, K, point_ok, cameras):
+    """The arguments mvba_pose_robust and mvba_pose_refine share, as ctypes: (keep-alive tuple, n, n_obs, m, pp, cp, xy, okp, K,
+    camera pointer, n_cameras)."""
+    X, xy, K = _as(X, np.float64), _as(xy, np.float64), _as(K, np.float64)
+    n, m = X.shape[0], K.shape[0]
+    assert X.shape == (n, 3) and K.shape == (m, 3, 3)
+    _, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m, n)
+    ok, okp = None, None
+    if point_ok is not None:
+        ok = _as(np.asarray(point_ok) != 0, np.uint8)
+        assert ok.shape == (n,)
+        okp = ok.ctypes.data_as(C.POINTER(C.c_uint8))
+    cams = None if cameras is None else _as(cameras, np.int32).reshape(-1)
+    nc = m if cams is None else cams.shape[0]
+    return (X, ok, cams), n, n_obs, m, pp, cp, xy, okp, K, None if cams is None else cams.ctypes.data_as(C.POINTER(C.c_int32)), nc
+
+
+def pose_robust(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=None, cameras=None, n_hypotheses=512, seed=0, n_refine=5, n_refit=2,
+                return_inliers=True, return_counts=False, device=-1):
+    """Camera poses with known intrinsics by P3P RANSAC and a pose-only refit on the device (mvba_pose_robust).  X, the list,
+    ``point_ok`` and ``cameras`` as for ``resect_robust``; ``K (m, 3, 3)`` projects to the units of xy; ``threshold`` is a
+    reprojection distance in those units.  Returns a dict: ``R (C, 3, 3)`` (columns = the camera axes), ``t (C, 3)``,
+    ``quality (C, 2)`` (RMS reprojection residual over the final inliers, smallest relative Cholesky pivot of the last kept
+    refit), ``n_usable``, ``n_inliers``, ``best``, ``status`` (C,) (0 ok, 1 fewer than 4 usable observations, 2 every hypothesis
+    degenerate, 4 best count below 4; R, t and quality NaN then), ``inlier (n_obs,) bool`` (``return_inliers``), ``hyp_count
+    (C, H) int32`` (``return_counts``), ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_pose_robust")
+    keep, n, n_obs, m, pp, cp, xy, okp, K, camp, nc = _pose_args(X, pt_ptr, cam_idx, xy, K, point_ok, cameras)
+    i32, i64, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    H = int(n_hypotheses)
+    R, t, q, tm = np.empty((nc, 3, 3)), np.empty((nc, 3)), np.empty((nc, 2)), np.zeros(4)
+    nu, ni, best, st = np.empty(nc, np.int64), np.empty(nc, np.int64), np.empty(nc, np.int32), np.empty(nc, np.int32)
+    inl = np.empty(n_obs, np.uint8) if return_inliers else None
+    hc = np.empty((nc, max(H, 0)), np.int32) if return_counts else None
+    raise_for(lib.mvba_pose_robust(_ptr(keep[0]), n, pp, cp, _ptr(xy), n_obs, m, okp, _ptr(K), camp, nc, float(threshold), H,
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refine), int(n_refit), _ptr(R), _ptr(t), _ptr(q),
+                                   nu.ctypes.data_as(i64), ni.ctypes.data_as(i64), best.ctypes.data_as(i32),
+                                   inl.ctypes.data_as(u8) if return_inliers else None, hc.ctypes.data_as(i32) if return_counts else None,
+                                   st.ctypes.data_as(i32), _ptr(tm), int(device)), lib)
+    out = {"R": R, "t": t, "quality": q, "n_usable": nu, "n_inliers": ni, "best": best, "status": st,
+           "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
+    if return_inliers:
+        out["inlier"] = inl.astype(bool)
+    if return_counts:
+        out["hyp_count"] = hc
+    return out
+
+
+def pose_refine(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=None, obs_ok=None, cameras=None, n_steps=10, device=-1):
+    """Gauss-Newton on the poses ``R (C, 3, 3)``, ``t (C, 3)`` of the listed cameras against the fixed points X
+    (mvba_pose_refine: the refit of ``pose_robust`` alone); ``obs_ok (n_obs,)`` marks the observations to use.  Returns a dict:
+    ``R``, ``t`` (copies; the input pose where status is not 0), ``quality (C, 3)`` (RMS before, after, steps taken),
+    ``n_usable``, ``status`` (C,) (0 ok, 1 fewer than 3 observations, 2 singular at the first step or input not finite),
+    ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_pose_refine")
+    keep, n, n_obs, m, pp, cp, xy, okp, K, camp, nc = _pose_args(X, pt_ptr, cam_idx, xy, K, point_ok, cameras)
+    obp = None
+    if obs_ok is not None:
+        ob = _as(np.asarray(obs_ok) != 0, np.uint8).reshape(-1)
+        assert ob.shape == (n_obs,)
+        obp = ob.ctypes.data_as(C.POINTER(C.c_uint8))
+    R, t = np.array(R, np.float64, order="C").reshape(-1, 3, 3), np.array(t, np.float64, order="C").reshape(-1, 3)
+    assert R.shape[0] == nc and t.shape[0] == nc
+    q, tm, nu, st = np.empty((nc, 3)), np.zeros(3), np.empty(nc, np.int64), np.empty(nc, np.int32)
+    raise_for(lib.mvba_pose_refine(_ptr(keep[0]), n, pp, cp, _ptr(xy), n_obs, m, okp, obp, _ptr(K), camp, nc, int(n_steps), _ptr(R), _ptr(t),
+                                   _ptr(q), nu.ctypes.data_as(C.POINTER(C.c_int64)), st.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(tm),
+                                   int(device)), lib)
+    return {"R": R, "t": t, "quality": q, "n_usable": nu, "status": st, "timings_ms": dict(zip(("upload", "iterate", "other"), tm.tolist()))}
+
+
+def pose_sample(seed, k, h, n):
+    """The 4 distinct indices below ``n`` that hypothesis ``h`` of camera ``k`` draws (mvba_pose_sample: the host instance of
+    the function the kernel runs; no GPU needed)."""
+    lib = load_library()
+    idx = np.empty(4, np.int64)
+    raise_for(lib.mvba_pose_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
     return idx
 
 

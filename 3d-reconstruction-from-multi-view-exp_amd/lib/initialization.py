@@ -9,7 +9,9 @@ initial estimate for ``BundleAdjuster.from_observations``.  With wrong matches a
 RANSAC on the device instead (``mvba_two_view_robust``: csrc/mvba_ransac.h): ``ransac_threshold``; and every
 later camera from 6-point RANSAC (``mvba_resect_robust``: csrc/mvba_resect_ransac.h): ``resect_threshold``; and
 every point from a two-view RANSAC of its own (``mvba_triangulate_robust``: csrc/mvba_tri_ransac.h):
-``triangulate_threshold``.
+``triangulate_threshold``.  With the intrinsics known -- ``bootstrap`` is given them -- a later camera is better registered by
+its POSE alone: three-point RANSAC and a pose-only Gauss-Newton refit (``mvba_pose_robust``, ``mvba_pose_refine``:
+csrc/mvba_pose_ransac.h): ``pose_threshold``.
 """
 from __future__ import annotations
 
@@ -153,6 +155,50 @@ def resect_sample(seed, k, h, n):
     """The 6 distinct indices below ``n`` (of a camera's usable observations in ascending point order) that hypothesis ``h`` of
     camera ``k`` draws under ``seed`` -- the host instance of the function the kernel runs."""
     return _mvba.resect_sample(seed, k, h, n)
+
+
+def robust_pose_cameras(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=None, cameras=None, n_hypotheses: int = 512, seed: int = 0,
+                        n_refine: int = 5, n_refit: int = 2):
+    """(R, t, info): the poses of cameras whose intrinsics ``K`` (m, 3, 3) are KNOWN, from the points X (N, 3) they see, by
+    three-point RANSAC on the device (``mvba_pose_robust``), for the cameras listed in ``cameras`` (default: all; R, t and every
+    per-camera entry of ``info`` are indexed by the position in it).  ``K`` projects to the units of ``xy``:
+    ``engine_intrinsics(init_K)`` for raw image coordinates.  Per camera, ``n_hypotheses`` samples of four usable observations (a
+    counter-based generator of ``seed``, the camera and the hypothesis number: ``pose_sample``): the first three give up to
+    four poses (P3P), the fourth picks one; the score is the number of usable observations in front of the camera whose
+    reprojection distance is at most ``threshold`` (units of xy).  The best hypothesis's inliers get ``n_refine`` Gauss-Newton
+    steps on the reprojection error in the six pose unknowns, ``n_refit`` times at most, each kept while its inlier set does
+    not shrink.  Unlike ``robust_resect_cameras`` it needs 4 observations, not 6, coplanar points are no degeneracy, and the
+    pose belongs to the given K.  ``info``: ``status`` -- 0 ok, 1 fewer than 4 usable observations, 2 every hypothesis
+    degenerate (e.g. collinear points), 4 the best hypothesis has fewer than 4 inliers; R, t and quality are NaN where it is not
+    0 --, ``quality`` (C, 2) -- RMS reprojection residual over the final inliers, smallest relative Cholesky pivot of the last
+    kept refit --, ``n_usable``, ``n_inliers``, ``best`` (C,), ``inlier`` (n_obs,) bool in the order of the list,
+    ``confidence`` (C,) = 1 - (1 - w^4)^H with w = n_inliers / n_usable, and ``timings_ms``.  Two calls with the same arguments
+    return the same bits."""
+    out = _mvba.pose_robust(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=point_ok, cameras=cameras, n_hypotheses=n_hypotheses, seed=seed,
+                            n_refine=n_refine, n_refit=n_refit)
+    R, t = out.pop("R"), out.pop("t")
+    with np.errstate(all="ignore"):
+        w = out["n_inliers"] / np.maximum(out["n_usable"], 1)
+        out["confidence"] = np.where(out["status"] == 0, 1.0 - (1.0 - w ** 4) ** int(n_hypotheses), 0.0)
+    return R, t, out
+
+
+def refine_poses(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=None, obs_ok=None, cameras=None, n_steps: int = 10):
+    """(R, t, info): the poses ``R`` (C, 3, 3), ``t`` (C, 3) of the listed cameras (default: all) refined against the FIXED
+    points X by ``n_steps`` Gauss-Newton steps on the reprojection error (``mvba_pose_refine``: the refit of
+    ``robust_pose_cameras`` alone, without a threshold), over the observations of usable points that ``obs_ok`` (n_obs,) marks
+    (default: all of them).  A step that would raise the cost is not taken and ends the camera's iteration.  ``info``:
+    ``status`` -- 0 ok, 1 fewer than 3 observations, 2 singular at the first step or an input that is not finite; such a camera
+    keeps its input pose --, ``quality`` (C, 3) -- RMS reprojection residual before, after, steps taken --, ``n_usable`` and
+    ``timings_ms``."""
+    out = _mvba.pose_refine(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=point_ok, obs_ok=obs_ok, cameras=cameras, n_steps=n_steps)
+    return out.pop("R"), out.pop("t"), out
+
+
+def pose_sample(seed, k, h, n):
+    """The 4 distinct indices below ``n`` (of a camera's usable observations in ascending point order) that hypothesis ``h`` of
+    camera ``k`` draws under ``seed`` -- the host instance of the function the kernel runs."""
+    return _mvba.pose_sample(seed, k, h, n)
 
 
 def covisibility(pt_ptr, cam_idx, n_images):
@@ -320,7 +366,7 @@ def _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok):
 
 
 def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min_points: int = 12, max_rms=None, ransac_threshold=None,
-              n_hypotheses: int = 512, seed: int = 0, resect_threshold=None, triangulate_threshold=None):
+              n_hypotheses: int = 512, seed: int = 0, resect_threshold=None, triangulate_threshold=None, pose_threshold=None):
     """(K, R, t, X, info): an initial estimate for ``BundleAdjuster.from_observations`` from feature tracks and rough
     intrinsics, by incremental reconstruction.  ``xy`` are raw image coordinates, ``init_K`` (m, 3, 3) the adjuster's
     [[f,0,u],[0,f,v],[0,0,f0]]; K comes back as ``init_K`` (no focal length is estimated).
@@ -338,6 +384,11 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     points, and its usable observations that are not inliers are dropped from every later triangulation and resection;
     ``info`` gains ``obs_ok`` (n_obs,) bool, the observations still in use, and ``inlier`` (n_obs,) bool, the observations
     the registered cameras were resected from.
+    With ``pose_threshold`` (a reprojection distance in the units of xy) each round runs ``robust_pose_cameras`` on the
+    unregistered cameras with ``engine_intrinsics(init_K)`` instead: the calibrated form of the same step.  The candidate rule,
+    the dropping of usable observations that are not inliers, ``info["obs_ok"]`` and ``info["inlier"]`` are those of
+    ``resect_threshold``; the pose is taken as returned (it already belongs to ``init_K``: no ``pose_for_intrinsics``).  Giving
+    both thresholds is a ValueError.
     With ``triangulate_threshold`` (a reprojection distance in the units of xy) every triangulation of the loop is
     ``robust_triangulate_points`` over the observations of the registered cameras still in use, with ``n_hypotheses`` (4096 at
     most) and ``seed``: a wrong match in ANY registered camera, 0 and 1 included, is left out of its point instead of moving it
@@ -349,9 +400,12 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     whose component of t_1 is larger in magnitude: pass it to ``BundleAdjuster`` --, ``camera_ok`` (m,), ``point_ok`` (N,),
     ``order`` (the registration order), ``start_pair``.  Cameras and points not reached are NaN (``restrict_observations``
     gives the list without them).  ValueError if no start pair has status 0, or if camera 0 or 1 could not be registered."""
+    if pose_threshold is not None and resect_threshold is not None:
+        raise ValueError("bootstrap: pose_threshold and resect_threshold are two forms of one step: give one of them")
     pt_ptr, cam_idx = np.asarray(pt_ptr, np.int64), np.asarray(cam_idx, np.int32)
     xy, init_K = np.asarray(xy, np.float64).reshape(-1, 2), np.asarray(init_K, np.float64)
     m, n = init_K.shape[0], len(pt_ptr) - 1
+    drops = resect_threshold is not None or pose_threshold is not None  # (a robust registration drops observations for good)
     Kxy = engine_intrinsics(init_K)
     if start_pair is None:
         count = covisibility(pt_ptr, cam_idx, m)
@@ -382,12 +436,24 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     reg_order = [pair[0], pair[1]]
     pt = np.repeat(np.arange(n), np.diff(pt_ptr))
     all_points = np.ones(n, bool)
-    if resect_threshold is not None:
+    if drops:
         obs_ok, inlier = np.ones(len(cam_idx), bool), np.zeros(len(cam_idx), bool)
     if triangulate_threshold is not None:
         tri_inlier = point_ok[pt] & camera_ok[cam_idx]  # (until the first round: what relative_pose triangulated from)
     while not camera_ok.all():
-        if resect_threshold is None:
+        if pose_threshold is not None:
+            todo = np.nonzero(~camera_ok)[0]
+            Rp, tp, ri = robust_pose_cameras(X, pt_ptr, cam_idx, xy, Kxy, pose_threshold, point_ok=point_ok, cameras=todo,
+                                             n_hypotheses=n_hypotheses, seed=seed)
+            cand = np.nonzero((ri["status"] == 0) & (ri["n_inliers"] >= min_points))[0]
+            if len(cand) == 0:
+                break
+            i = int(cand[np.argmax(ri["n_inliers"][cand])])
+            c = int(todo[i])
+            sel = ri["inlier"] & (cam_idx == c)
+            obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)
+            inlier |= sel
+        elif resect_threshold is None:
             ri = resect_cameras(X, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=point_ok)[3]
             usable = np.bincount(cam_idx[point_ok[pt]], minlength=m)
             cand = np.nonzero(~camera_ok & (ri["status"] == 0) & (usable >= min_points))[0]
@@ -409,10 +475,13 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
             Pc = ri["P"][i]
             obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)
             inlier |= sel
-        R[c], t[c] = pose_for_intrinsics(Pc, Kxy[c], X[pt[sel]].mean(axis=0))
+        if pose_threshold is not None:
+            R[c], t[c] = Rp[i], tp[i]
+        else:
+            R[c], t[c] = pose_for_intrinsics(Pc, Kxy[c], X[pt[sel]].mean(axis=0))
         camera_ok[c] = True
         reg_order.append(c)
-        if resect_threshold is None:
+        if not drops:
             ptr, cam, z, _, ids = restrict_observations(pt_ptr, cam_idx, xy, all_points, camera_ok)
         else:
             ptr, cam, z, ids = _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok)
@@ -426,7 +495,7 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
             point_ok &= ti["quality"][:, 0] <= max_rms
         X[~point_ok] = np.nan
         if triangulate_threshold is not None:
-            kept = camera_ok[cam_idx] if resect_threshold is None else obs_ok & camera_ok[cam_idx]  # (the list just triangulated)
+            kept = obs_ok & camera_ok[cam_idx] if drops else camera_ok[cam_idx]  # (the list just triangulated)
             tri_inlier = np.zeros(len(cam_idx), bool)
             tri_inlier[np.nonzero(kept)[0]] = ti["inlier"]
             tri_inlier &= point_ok[pt]
@@ -438,7 +507,7 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     X, R, t = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s
     axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
     info = {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order, "start_pair": pair}
-    if resect_threshold is not None:
+    if drops:
         info["obs_ok"], info["inlier"] = obs_ok, inlier
     if triangulate_threshold is not None:
         info["tri_inlier"] = tri_inlier

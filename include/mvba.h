@@ -376,6 +376,70 @@ int mvba_resect_robust(const double *X, int64_t n_points, const int64_t *pt_ptr,
  * outside 6 .. 2^31 - 1, a negative k or h. */
 int mvba_resect_sample(uint64_t seed, int32_t k, int32_t h, int64_t n, int64_t *idx6);
 
+/* mvba_pose_robust: the poses of cameras with KNOWN intrinsics from known points -- three-point (P3P) RANSAC, then a pose-only
+ * Gauss-Newton refit on the inliers (csrc/mvba_pose_ransac.h).  X, the list, point_ok, cameras / n_cameras,
+ * threshold, n_hypotheses, seed, n_refit and device are mvba_resect_robust's, with the same checks and messages; K
+ * [n_images][3][3] projects to the units of xy (the conventions of mvba_project: x ~ K R^T (X - t)); n_refine in 0 .. 16
+ * (MVBA_ERR_BADARG with the number in the message otherwise, as for a NULL K).
+ * Per listed camera k, its usable observations in ascending point order numbered 0 .. n - 1 (a dense run after the sort):
+ *   hypothesis h = 0 .. n_hypotheses - 1: the 4 distinct indices (i0, i1, i2, i3) of mvba_pose_sample(seed, k, h, n); bearings
+ *     d_j = K^-1 (x, y, 1) scaled to unit length (K inverted by its adjugate); a = |X_1 - X_2|, b = |X_0 - X_2|, c = |X_0 - X_1|,
+ *     cos alpha = d_1 . d_2, cos beta = d_0 . d_2, cos gamma = d_0 . d_1; the depths s > 0 with s_1^2 + s_2^2 - 2 s_1 s_2 cos alpha
+ *     = a^2, s_0^2 + s_2^2 - 2 s_0 s_2 cos beta = b^2, s_0^2 + s_1^2 - 2 s_0 s_1 cos gamma = c^2: with u = s_1 / s_0, v = s_2 / s_0,
+ *     q = (a^2 - c^2) / b^2, W = 1 + v^2 - 2 v cos beta: u = (q W - v^2 + 1) / (2 (cos gamma - v cos alpha)), a quartic in v from
+ *     the third equation, s_0^2 = b^2 / W.  The quartic's real roots: monic and depressed (y^4 + p y^2 + g y + h), Ferrari's two
+ *     quadratics y^2 +- sqrt(2 m) y + p / 2 + m -+ g / (2 sqrt(2 m)) with m a positive root of m^3 + p m^2 + (p^2 / 4 - h) m -
+ *     g^2 / 8 (50 steps from the bracket 0 .. 1 + the largest coefficient magnitude, starting at its upper end: Newton's step
+ *     where it stays inside the bracket, the midpoint where it does not), a quadratic's two roots where its
+ *     discriminant is >= 0, each polished by 2 Newton steps on the quartic.  Every root with u, v, s_0 > 0 gets 3 Newton steps on
+ *     the three equations (a 3 x 3 solve) and is dropped unless the depths are positive and finite afterwards.  Its pose: Y_j =
+ *     s_j d_j; the orthonormal frames of the triangles (Y_0, Y_1, Y_2) and (X_0, X_1, X_2) by Gram-Schmidt (e_1 along 1 - 0, e_2
+ *     along 2 - 0 without its e_1 part, e_3 = e_1 x e_2); R_cw = F_Y F_X^T, R = R_cw^T, t = X_0 - R Y_0.  The hypothesis's pose is
+ *     the solution that puts X_i3 in front of the camera with the smallest squared reprojection distance at observation i3
+ *     (the smaller s_0 on a tie).  Degenerate (count -1): no such solution, anything not finite, or a triangle whose e_2
+ *     remainder has squared length <= 1e-12 x that of its 2 - 0 edge;
+ *   score: P_h = K [R^T | -R^T t]; count_h = the number of usable observations in front of P_h and within threshold^2 of it --
+ *     the test and the kernel of mvba_resect_robust --; best = the largest count, the lowest h on ties (on the host);
+ *   refit r = 1 .. n_refit: n_refine Gauss-Newton steps on sum |pi(K R^T (X - t)) - xy|^2 over the current inlier set, I_0
+ *     being that of the best hypothesis, in the six unknowns (delta t, omega) with t <- t + delta t, R <- Rod(omega) R (the
+ *     engine's convention).  One pass over the camera's chunks of 256 observations gives 29 sums (the 21 unique entries of
+ *     J^T J, the 6 of J^T e, the cost, the count): a chunk by a fixed tree, a camera's chunks in ascending order; their
+ *     combination, the 6 x 6 Cholesky, the accept rule and the pose update run on the device, one thread per camera: no host
+ *     round trip per step.  A pivot <= 1e-12 x the largest diagonal entry fails the refit.  A step is taken only if it does not
+ *     raise the cost; otherwise the camera keeps the previous pose and stops (the rule of mvba_triangulate).  I_r = the
+ *     observations in front of the refined pose and within the threshold of it.  A refit is kept if it did not fail and
+ *     |I_r| >= |I_r-1|; otherwise the loop ends with the previous result.  With n_refit = 0 the pose is the best hypothesis's.
+ * R [n_cameras][9] row-major (its columns are the camera axes), t [n_cameras][3] the centre.  quality [n_cameras][2]: the RMS
+ * reprojection residual over the final inliers under the pose that selected them; the smallest relative Cholesky pivot of the
+ * last kept refit's last step (0 if none was kept).  n_usable, n_inliers, best [n_cameras] (best = -1 where status = 1 or 2);
+ * inlier [n_obs] BYTES in the caller's observation order; hyp_count [n_cameras][n_hypotheses] (all -1 where status = 1 or 2).
+ * status [n_cameras]: 0 ok; 1 fewer than 4 usable observations; 2 every hypothesis degenerate; 4 the best count is below 4 (a
+ * sample guarantees 3 inliers only).  Where status != 0, R, t and quality are NaN and n_inliers is 0.
+ * timings_ms [4]: sort + upload; hypotheses and scoring; refits; everything else.  Every output but R and t may be NULL.
+ * Cameras are taken in tiles of 128 MiB / (196 n_hypotheses), at least 1 and at most 65535; a camera's results do not depend
+ * on which other cameras are listed.  Counts are integers and every sum has a fixed order: two calls give bitwise-identical output. */
+int mvba_pose_robust(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy,
+                     int64_t n_obs, int32_t n_images, const uint8_t *point_ok, const double *K, const int32_t *cameras,
+                     int32_t n_cameras, double threshold, int32_t n_hypotheses, uint64_t seed, int32_t n_refine, int32_t n_refit,
+                     double *R, double *t, double *quality, int64_t *n_usable, int64_t *n_inliers, int32_t *best, uint8_t *inlier,
+                     int32_t *hyp_count, int32_t *status, double *timings_ms, int32_t device);
+/* mvba_pose_refine: the refit of mvba_pose_robust alone -- the same kernels --, for given poses against fixed points: R
+ * [n_cameras][9], t [n_cameras][3] in and out per LISTED camera; K, X, the list, point_ok and cameras as above; obs_ok [n_obs]
+ * (may be NULL) != 0 marks the observations to use among the usable ones.  n_steps in 0 .. 64 Gauss-Newton steps over them; there
+ * is no threshold.  status [n_cameras]: 0 ok; 1 fewer than 3 such observations; 2 the normal matrix fails the pivot rule at the
+ * first step, or the input is not finite (a later failure of the rule ends the iteration at the pose reached).  A camera of
+ * status != 0 keeps its input pose.  quality [n_cameras][3]: RMS reprojection residual before, after, steps taken (NaN where
+ * status != 0).  n_usable [n_cameras]: the observations used.  timings_ms [3]: sort + upload, the iteration, everything else.
+ * quality, n_usable, status and timings_ms may be NULL. */
+int mvba_pose_refine(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy,
+                     int64_t n_obs, int32_t n_images, const uint8_t *point_ok, const uint8_t *obs_ok, const double *K,
+                     const int32_t *cameras, int32_t n_cameras, int32_t n_steps, double *R, double *t, double *quality,
+                     int64_t *n_usable, int32_t *status, double *timings_ms, int32_t device);
+/* Host only (no GPU needed): the 4 distinct indices below n that hypothesis h of camera k draws -- mvba_ransac_sample's
+ * generator with l = k and 4 draws: the first 4 of mvba_ransac_sample(seed, k, k, h, n) wherever n >= 8.  MVBA_ERR_BADARG: n
+ * outside 4 .. 2^31 - 1, a negative k or h. */
+int mvba_pose_sample(uint64_t seed, int32_t k, int32_t h, int64_t n, int64_t *idx4);
+
 /* mvba_triangulate_robust: mvba_triangulate with a two-view RANSAC per point in front of it (csrc/mvba_tri_ransac.h, DESIGN.md
  * 19).  Cameras, list, dense grid (pt_ptr == NULL), units, the argument checks and the limit of 1704 cameras are
  * mvba_triangulate's; MVBA_ERR_BADARG also for a threshold that is not finite or not > 0, n_hypotheses outside 1 .. 4096 and
