@@ -313,9 +313,16 @@ constexpr int PBS = 16;
 constexpr int PACE_STRIDE = 32;  // ints between two pacing counters: one 128-byte line each (they are hammered by ~300 waves)
 // Also clears the packed [A|b] the Schur kernel is about to accumulate into (one launch less on
 // the path; the grid is sized for whichever of the two jobs is larger).
+// Held points (mvba_set_point_hold): the instantiation with one trailing `const uint8_t *held` [npts] writes the
+// row of a point removed from the unknowns -- E^-1 = 0, v = 0, R = 0, the tenth double 1 (a point, sign code 0) -- and does not
+// test that point's determinant.  Without a mask the engine launches k_point_inv<>, whose arguments and body are the kernel's
+// as it was before there were masks.
+template <typename... Held>
 __global__ __launch_bounds__(256) void k_point_inv(long long npts, double c, const double *__restrict__ PL,
                                                    double *__restrict__ PB, int *__restrict__ flag,
-                                                   double *__restrict__ Ab, long long nAb, int *__restrict__ prog, long long nprog, int want_r) {
+                                                   double *__restrict__ Ab, long long nAb, int *__restrict__ prog, long long nprog, int want_r,
+                                                   Held... held) {
+  static_assert(sizeof...(Held) <= 1, "at most the held mask");
   // a block's 256 points are 18 KiB of PL and 32 KiB of PB, both contiguous: moved with coalesced
   // accesses through LDS (a thread reading its own 72-byte row / writing its own 128-byte line touches
   // 64 different lines per instruction)
@@ -341,7 +348,17 @@ __global__ __launch_bounds__(256) void k_point_inv(long long npts, double c, con
 #pragma unroll
   for (int i = 0; i < 9; ++i) in[i] = s_in[9 * min((int)threadIdx.x, np - 1) + i];
   __syncthreads();
-  if (threadIdx.x < np) {
+  bool free_pt = threadIdx.x < np;
+  if constexpr (sizeof...(Held) == 1) {
+    if (free_pt && (held, ...)[a] != 0) {  // (a < npts here)
+      free_pt = false;
+      double2 *out = s_out + 8 * threadIdx.x;
+      const int sw = threadIdx.x & 7;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) out[q ^ sw] = make_double2(0.0, q == 4 ? 1.0 : 0.0);
+    }
+  }
+  if (free_pt) {
     const double s = 1.0 + c;
     const double xx = in[0] * s, xy = in[1], xz = in[2], yy = in[3] * s, yz = in[4], zz = in[5] * s;
     const double c00 = yy * zz - yz * yz, c01 = xz * yz - xy * zz, c02 = xy * yz - xz * yy;
@@ -3015,6 +3032,10 @@ struct mvba_handle {
   int2 *d_map_pairs = nullptr;  // the (i, j <= i) pairs of tied unknowns, n_map_pairs of them; map_nblk partial sums per pair
   double *d_map_part = nullptr;
   int n_map_pairs = 0, map_nblk = 1;
+  // held points (mvba_set_point_hold): the mask as 0 / 1 bytes [N], allocated on the first mask with a held point;
+  // n_held == 0: no mask, none of this is touched
+  uint8_t *d_held = nullptr;
+  long long n_held = 0;
   int solve_D() const { return mapped ? n_free : D; }     // order and row stride of the system K4 solves
   int solve_ld() const { return mapped ? map_ld : ld; }
 };
@@ -3421,9 +3442,14 @@ void launch_point_inv(mvba_handle *h, double c) {  // K3a (also clears the packe
   const size_t n9 = 9 * (size_t)m, nA = strip_offset(m, m);
   const long long nAb = (long long)(nA + n9);
   const unsigned grid = (unsigned)std::max<long long>((h->N + 255) / 256, std::min<long long>((nAb + 1023) / 1024, 4096));
-  hipLaunchKernelGGL(k_point_inv, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
-                     h->d_Ab, nAb, h->d_prog, h->slot_w == LANES_W ? 0 : (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE,
-                     h->schur_mode == SCHUR_DENSE ? 1 : 0);
+  const long long nprog = h->slot_w == LANES_W ? 0 : (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE;
+  const int want_r = h->schur_mode == SCHUR_DENSE ? 1 : 0;
+  if (h->n_held)  // held points (mvba_set_point_hold): the masked form; without a mask the launch is the one it always was
+    hipLaunchKernelGGL(k_point_inv<const uint8_t *>, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
+                       h->d_Ab, nAb, h->d_prog, nprog, want_r, (const uint8_t *)h->d_held);
+  else
+    hipLaunchKernelGGL(k_point_inv<>, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
+                       h->d_Ab, nAb, h->d_prog, nprog, want_r);
 }
 
 void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b] of this rank's points
@@ -3844,6 +3870,28 @@ int mvba_set_parameter_map(mvba_handle *h, const int32_t *col, int32_t n_free) {
   return MVBA_OK;
 }
 
+int mvba_set_point_hold(mvba_handle *h, const uint8_t *held) {
+  if (!h) return fail(MVBA_ERR_BADARG, "null handle");
+  MVBA_HIP(hipSetDevice(h->device));
+  long long n_held = 0;
+  std::vector<uint8_t> mask;
+  if (held) {
+    mask.resize((size_t)h->N);
+    for (long long a = 0; a < h->N; ++a) n_held += (mask[(size_t)a] = held[a] ? 1 : 0);
+  }
+  if (n_held && !h->d_held) {
+    int rc = h->mem.alloc(&h->d_held, (size_t)h->N);
+    if (rc) return rc;
+  }
+  if (n_held) {
+    MVBA_HIP(hipStreamSynchronize(h->stream));  // nothing in flight reads the mask that is replaced now
+    MVBA_HIP(hipMemcpy(h->d_held, mask.data(), mask.size(), hipMemcpyHostToDevice));
+  }
+  h->n_held = n_held;  // (no held point, spelled out or NULL: the engine runs exactly what it runs without a mask)
+  h->have_trial = false;
+  return MVBA_OK;
+}
+
 int mvba_residuals(mvba_handle *h, double *e) {
   if (!h || !e) return fail(MVBA_ERR_BADARG, "null argument");
   if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
@@ -3957,10 +4005,16 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
     const double pairs = h->N ? 0.5 * ((double)h->nobs / (double)h->N) * ((double)h->nobs / (double)h->N + 1.0) : 0.0;
     const int G = pairs > 48.0 ? 64 : (pairs > 24.0 ? 32 : (pairs > 12.0 ? 16 : 8));  // lanes per point by mean pair count
     const unsigned grid = (unsigned)std::min<long long>(8192, (h->N * G + 255) / 256);
-    auto kern = G == 64 ? k_point_cov<64> : (G == 32 ? k_point_cov<32> : (G == 16 ? k_point_cov<16> : k_point_cov<8>));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->stream, h->N, m, (const long long *)h->d_pt_ptr, (const int *)h->d_cam,
-                       (const double2 *)h->d_rec, (const double *)h->d_PL, (const double *)h->d_cov_sig, 1.0 / h->f0, h->d_cov_pts,
-                       h->d_flag);
+    auto launch = [&](auto kern, auto... held) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->stream, h->N, m, (const long long *)h->d_pt_ptr, (const int *)h->d_cam,
+                         (const double2 *)h->d_rec, (const double *)h->d_PL, (const double *)h->d_cov_sig, 1.0 / h->f0, h->d_cov_pts,
+                         h->d_flag, held...);
+    };
+    if (h->n_held) {  // held points skip the pair loop and the pivot test: six zeros
+      using M = const uint8_t *;
+      launch(G == 64 ? k_point_cov<64, M> : (G == 32 ? k_point_cov<32, M> : (G == 16 ? k_point_cov<16, M> : k_point_cov<8, M>)), (M)h->d_held);
+    } else
+      launch(G == 64 ? k_point_cov<64> : (G == 32 ? k_point_cov<32> : (G == 16 ? k_point_cov<16> : k_point_cov<8>)));
   }
   if (cam_cov)
     hipLaunchKernelGGL(k_cov_cam_diag, dim3((unsigned)((81LL * m + 255) / 256)), dim3(256), 0, h->stream, m,

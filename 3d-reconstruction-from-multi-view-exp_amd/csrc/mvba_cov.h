@@ -185,15 +185,20 @@ __global__ __launch_bounds__(256) void k_cov_cam_diag(int m, const double *__res
 // symmetric part of Jx_i^T (Jc_i Sigma Jc_j^T) Jx_j (counted twice for i < j) in six registers; the group sums them with a
 // fixed butterfly and its first lane finishes C_a.  A point whose E_a has a Cholesky pivot below 1e-12 of its largest
 // diagonal entry (e.g. a point seen once) sets COV_FLAG_POINT.
-template <int G>
+// Held points (mvba_set_point_hold): the instantiation with one trailing `const uint8_t *held` [N] gives a held point no pairs
+// and no pivot test, and writes six zeros for it -- a point that is not an unknown has no covariance.
+template <int G, typename... Held>
 __global__ __launch_bounds__(256) void k_point_cov(long long N, int m, const long long *__restrict__ pt_ptr, const int *__restrict__ cam,
                                                    const double2 *__restrict__ rec, const double *__restrict__ PL,
                                                    const double *__restrict__ sig, double f0inv, double *__restrict__ out,
-                                                   int *__restrict__ flag) {
+                                                   int *__restrict__ flag, Held... held) {
+  static_assert(sizeof...(Held) <= 1, "at most the held mask");
   const int sub = threadIdx.x & (G - 1);
   const long long groups = (long long)gridDim.x * (256 / G);
   for (long long a = ((long long)blockIdx.x * 256 + threadIdx.x) / G; a < N; a += groups) {
-    const long long o0 = pt_ptr[a], d = pt_ptr[a + 1] - o0, npairs = d * (d + 1) / 2;
+    bool held_pt = false;  // (the same for the G lanes of a point)
+    if constexpr (sizeof...(Held) == 1) held_pt = (held, ...)[a] != 0;
+    const long long o0 = pt_ptr[a], d = pt_ptr[a + 1] - o0, npairs = held_pt ? 0 : d * (d + 1) / 2;
     double q6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (long long p = sub; p < npairs; p += G) {
       long long j = (long long)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
@@ -267,7 +272,10 @@ __global__ __launch_bounds__(256) void k_point_cov(long long N, int m, const lon
     for (int off = G / 2; off > 0; off >>= 1)
 #pragma unroll
       for (int c = 0; c < 6; ++c) q6[c] += __shfl_xor(q6[c], off, 64);
-    if (sub == 0) {
+    if (sub == 0 && held_pt) {
+      double *o = out + 6 * (size_t)a;
+      o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.0;
+    } else if (sub == 0) {
       const double *pl = PL + 9 * (size_t)a;
       const double xx = pl[0], xy = pl[1], xz = pl[2], yy = pl[3], yz = pl[4], zz = pl[5];
       const double c00 = yy * zz - yz * yz, c01 = xz * yz - xy * zz, c02 = xy * yz - xz * yy;

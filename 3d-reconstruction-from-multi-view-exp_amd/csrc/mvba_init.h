@@ -495,6 +495,9 @@ int mvba_triangulate_state(mvba_handle *h, int32_t n_refine, double *quality, in
   if (!h) return fail(MVBA_ERR_BADARG, "null argument: h (argument 1)");
   if (n_refine < 0) return fail(MVBA_ERR_BADARG, "n_refine = " + std::to_string(n_refine) + " must be >= 0");
   if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set: the cameras to triangulate from are the committed ones");
+  if (h->n_held)
+    return fail(MVBA_ERR_STATE, "mvba_triangulate_state: " + std::to_string(h->n_held) + " points are held (mvba_set_point_hold) and would be "
+                                "replaced by their triangulation: clear the mask first (mvba_set_point_hold(h, NULL))");
   int rc = init_check_cameras(h->m);
   if (rc) return rc;
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = 0.0;

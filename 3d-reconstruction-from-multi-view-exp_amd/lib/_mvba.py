@@ -78,6 +78,7 @@ SIGNATURES = {
     "mvba_try_step": (C.c_int, [C.c_void_p, C.c_double, _dp]),
     "mvba_commit": (C.c_int, [C.c_void_p]),
     "mvba_set_parameter_map": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    "mvba_set_point_hold": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)]),
     "mvba_covariance": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "mvba_residuals": (C.c_int, [C.c_void_p, _dp]),
     "mvba_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -251,6 +252,7 @@ class HipEngine:
         self._h = h
         self.n_solves = 0
         self.n_free = 9 * self.m - 7  # unknowns of the reduced camera system (set_parameter_map)
+        self.n_held_points = 0  # points that are not unknowns (set_point_hold)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -333,12 +335,27 @@ class HipEngine:
         raise_for(self.lib.mvba_set_parameter_map(self._h, col.ctypes.data_as(C.POINTER(C.c_int32)), int(n_free)), self.lib)
         self.n_free = int(n_free)
 
+    def set_point_hold(self, mask):
+        """Which points a trial adjusts (include/mvba.h, mvba_set_point_hold): ``mask`` (n_points,) bool, True = held (not
+        an unknown: its step is exactly 0, its residuals still count); ``None`` clears the mask.  Voids the trial, keeps
+        the linearisation.  ``triangulate()`` raises while a mask is set.  Sharded engines: the mask of this rank's points."""
+        if mask is None:
+            raise_for(self.lib.mvba_set_point_hold(self._h, None), self.lib)
+            self.n_held_points = 0
+            return
+        mask = np.asarray(mask)
+        if mask.dtype != np.bool_ or mask.shape != (self.n,):
+            raise ValueError(f"mask must be a bool array of shape ({self.n},), got {mask.dtype} {mask.shape}")
+        m8 = _as(mask, np.uint8)
+        raise_for(self.lib.mvba_set_point_hold(self._h, m8.ctypes.data_as(C.POINTER(C.c_uint8))), self.lib)
+        self.n_held_points = int(mask.sum())
+
     def covariance(self, points=True, cameras=True, full=False):
         """Unit marginal covariances (J^T J)^-1 at the committed state, in the engine's frame, gauge parameters fixed
         (zero rows / columns): ``points`` (N, 3, 3), ``cameras`` (m, 9, 9) (f, u, v, t, omega), ``cameras_full``
         (9m, 9m) when ``full``, and ``timings_ms`` (linearise+Schur, factor, inverse, point pass).  Leaves the engine
         linearised at the committed state.  Raises LinAlgError when J^T J is singular (a point seen once, a camera with
-        too few points)."""
+        too few points).  With held points (set_point_hold): zero blocks there, and they are never a reason for LinAlgError."""
         P = np.empty((self.n, 6)) if points else None
         Cc = np.empty((self.m, 9, 9)) if cameras else None
         Cf = np.empty((9 * self.m, 9 * self.m)) if full else None

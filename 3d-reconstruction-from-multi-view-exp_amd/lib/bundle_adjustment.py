@@ -104,16 +104,18 @@ def covariance_to_input_frame(camera0: dict[str, Any], points=None, cameras=None
     return P, Cc, Cf
 
 
-def residual_variance(E: float, n_obs: int, n_points: int, n_images: int, n_free: int | None = None) -> float:
+def residual_variance(E: float, n_obs: int, n_points: int, n_images: int, n_free: int | None = None, n_held: int = 0) -> float:
     """sigma^2 = E / (2 n_obs - (3 N + 9 m - 7)): the residual variance per image coordinate (units x / f0) at the
     solution; ValueError when the problem has no redundancy.  ``n_free``: the number of free camera unknowns under a
-    parameter map (``parameter_map``), in the place of 9 m - 7."""
+    parameter map (``parameter_map``), in the place of 9 m - 7.  ``n_held``: the number of held points (``hold_points``),
+    which are not unknowns: 3 (N - n_held) in the place of 3 N."""
+    n_pts = int(n_points) - int(n_held)
     if n_free is None:
-        dof = 2 * int(n_obs) - (3 * int(n_points) + 9 * int(n_images) - 7)
+        dof = 2 * int(n_obs) - (3 * n_pts + 9 * int(n_images) - 7)
         if dof <= 0:
             raise ValueError(f"no redundancy: 2 n_obs - (3 N + 9 m - 7) = {dof}")
         return float(E) / dof
-    dof = 2 * int(n_obs) - (3 * int(n_points) + int(n_free))
+    dof = 2 * int(n_obs) - (3 * n_pts + int(n_free))
     if dof <= 0:
         raise ValueError(f"no redundancy: 2 n_obs - (3 N + n_free) = {dof}")
     return float(E) / dof
@@ -200,6 +202,33 @@ def parameter_map(n_images: int, axis: str = "x-right_z-forward", hold=None, sha
     for i, (_, _, slots) in enumerate(tied_sets):
         col[slots] = len(free) + i
     return col, len(free) + len(tied_sets)
+
+
+def point_hold_mask(n_points: int, hold_points, init_X=None):
+    """``hold_points`` of ``BundleAdjuster`` as a bool mask (n_points,): a bool array (n_points,), True = held, or an integer
+    array of point indices (any order, duplicates allowed).  With ``init_X`` (n_points, 3): its held rows must be finite.
+    ValueError, the offending number in the message, for another dtype or shape, an index outside 0 .. n_points - 1, a held
+    row that is not finite."""
+    n = int(n_points)
+    hp = np.asarray(hold_points)
+    if hp.dtype == np.bool_:
+        if hp.shape != (n,):
+            raise ValueError(f"hold_points: a bool array must have shape ({n},), got {hp.shape}")
+        mask = hp.copy()
+    elif hp.dtype.kind in "iu" and hp.ndim == 1:
+        bad = np.nonzero((hp < 0) | (hp >= n))[0]
+        if len(bad):
+            raise ValueError(f"hold_points: index {int(hp[bad[0]])} (entry {int(bad[0])}) is outside 0 .. {n - 1}")
+        mask = np.zeros(n, dtype=bool)
+        mask[hp] = True
+    else:
+        raise ValueError(f"hold_points: a bool array of shape ({n},) or a 1-d integer array of point indices, got {hp.dtype} {hp.shape}")
+    if init_X is not None:
+        X = np.asarray(init_X, dtype=np.float64)
+        bad = np.nonzero(mask & ~np.isfinite(X).all(axis=1))[0]
+        if len(bad):
+            raise ValueError(f"hold_points: held point {int(bad[0])} starts from a position that is not finite ({len(bad)} such points)")
+    return mask
 
 
 def intrinsics_from(f, u, f0: float):
@@ -291,6 +320,7 @@ class BundleAdjuster:
         hold=None,
         share=None,
         share_groups=None,
+        hold_points=None,
     ):
         """``loss``: "squared" (the reference's sum of squares), "huber" or "cauchy" -- a robust loss with scale
         ``loss_scale`` (delta, in the units of ``x``: pixels), required for the robust ones.
@@ -300,11 +330,19 @@ class BundleAdjuster:
         parameters must start equal (``init_K[:, 0, 0]``, ``init_K[:, :2, 2]`` within a group).  A held pose is held in
         the gauge frame BA works in, i.e. relative to camera 0 and the camera-0/1 baseline: the output poses equal the
         input poses up to the rounding of the frame change.
+        ``hold_points``: points that are not adjusted -- control points, or the structure that is already
+        good when new cameras and points are adjusted against it: a bool array (N,), True = held, or an array of point
+        indices; ``hold="points"`` (alone or among the other names) holds all of them: the cameras are refined against
+        known structure.  Held points keep their ``init_X`` rows bit for bit, their observations still count in the cost,
+        and they are held whole (no per-coordinate mask).  They are held in the gauge frame as held poses are: camera 0 and
+        the camera-0/1 baseline component stay fixed however many points are held, so control points that disagree with
+        camera 0's initial pose cannot pull it.  Needs ``init_X``, finite at the held rows.
         ``init_X=None``: the points start from their triangulation from the initial cameras, on the device
         (``HipEngine.triangulate``); ValueError if a point cannot be triangulated (seen once, no parallax,
         at infinity) -- ``lib.initialization.triangulate_points`` tells which, to filter the list first."""
         check_loss(loss, loss_scale)  # (ValueError before any work)
         x = np.asarray(x)
+        hold = self._check_hold_points(x.shape[0], hold, hold_points, init_X)
         self._check_map(x.shape[1], axis, init_K, hold, share, share_groups)
         pt_ptr, cam_idx, xy = dense_to_observations(x, visibility_index)
         self._setup(x.shape[0], x.shape[1], pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, loss=loss,
@@ -313,12 +351,14 @@ class BundleAdjuster:
     @classmethod
     def from_observations(cls, n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t,
                           f0: float = 1.0, axis: str = "x-right_z-forward", loss: str = "squared",
-                          loss_scale: float | None = None, hold=None, share=None, share_groups=None, **engine_kw):
+                          loss_scale: float | None = None, hold=None, share=None, share_groups=None, hold_points=None,
+                          **engine_kw):
         """Extension for sizes where the dense (N,m,2) array cannot exist
         (SURVEY 8f rank 1): observation list in CSR-by-point form.  ``loss`` / ``loss_scale`` / ``hold`` / ``share`` /
-        ``share_groups`` / ``init_X=None``: as for the constructor."""
+        ``share_groups`` / ``hold_points`` / ``init_X=None``: as for the constructor."""
         check_loss(loss, loss_scale)
         self = cls.__new__(cls)
+        hold = self._check_hold_points(n_points, hold, hold_points, init_X)
         self._check_map(n_images, axis, init_K, hold, share, share_groups)
         self._setup(n_points, n_images, pt_ptr, cam_idx, xy, init_X, init_K, init_R, init_t, f0, axis, loss=loss,
                     loss_scale=loss_scale, **engine_kw)
@@ -326,6 +366,42 @@ class BundleAdjuster:
 
     # -- construction ------------------------------------------------------
     _map = None  # (col, n_free) when hold / share were given (set by _check_map before any device work)
+
+    _held = None  # bool (N,) when points are held (set by _check_hold_points before any device work)
+
+    def _check_hold_points(self, n_points, hold, hold_points, init_X):
+        """The point mask of ``hold_points`` and of the name "points" in ``hold``; returns ``hold`` without that name (None
+        if nothing is left), for parameter_map.  ValueErrors before any device work."""
+        names = None
+        if isinstance(hold, str):
+            names = [hold]
+        elif hold is not None and not isinstance(hold, np.ndarray) and len(hold) and all(isinstance(v, str) for v in hold):
+            names = list(hold)
+        all_points = names is not None and "points" in names
+        if all_points:
+            names = [nm for nm in names if nm != "points"]
+            hold = names if names else None
+        if hold_points is None and not all_points:
+            return hold
+        if init_X is None:
+            raise ValueError(f"hold_points with init_X=None: the {int(n_points)} points would start from their triangulation, and a "
+                             f"held point stays where init_X puts it")
+        X = np.asarray(init_X, dtype=np.float64)
+        if X.shape != (int(n_points), 3):
+            raise ValueError(f"hold_points: init_X must have shape ({int(n_points)}, 3), got {X.shape}")
+        mask = np.zeros(int(n_points), dtype=bool) if hold_points is None else point_hold_mask(n_points, hold_points)
+        if all_points:
+            mask[:] = True
+        mask = point_hold_mask(n_points, mask, X)  # (the finite check, on the union)
+        if mask.any():
+            self._held = mask
+            self._held_X = X[mask].copy()
+        return hold
+
+    @property
+    def n_held_points(self) -> int:
+        """Points that are not adjusted (``hold_points``)."""
+        return 0 if self._held is None else int(self._held.sum())
 
     def _check_map(self, n_images, axis, init_K, hold, share, share_groups):
         """parameter_map of the constructor's arguments and the check that tied parameters start equal: ValueErrors
@@ -393,6 +469,8 @@ class BundleAdjuster:
                                  f"parallax, 3 at infinity); filter them with lib.initialization.triangulate_points")
         if self._map is not None:
             self._engine.set_parameter_map(self._map[0], self._map[1])
+        if self._held is not None:
+            self._engine.set_point_hold(self._held)
         self._engine_frame = "gauge"  # the frame of the engine's state: "input" once optimize() has applied the way back
         self._log: list[dict[str, npt.NDArray | float]] = []
 
@@ -435,6 +513,9 @@ class BundleAdjuster:
         self._engine.apply_similarity(cam0["R"], cam0["t"], cam0["c0c1_len"])
         self._engine_frame = "input"
         X, f, u, t, R = self._engine.get_params()
+        if self._held is not None:
+            # held in the gauge frame, bit for bit; the way there and back costs rounding: the caller gets the rows it gave
+            X[self._held] = self._held_X
         return X, intrinsics_from(f, u, self._f0), R, t
 
     def covariance(self, scale: str = "unit", frame: str = "input", full_cameras: bool = False) -> dict[str, Any]:
@@ -442,17 +523,20 @@ class BundleAdjuster:
         ``cameras`` (m, 9, 9) in the order f, u, v, t, omega, and ``cameras_full`` (9m, 9m) when ``full_cameras``.
         Undamped, with the seven gauge parameters fixed (camera 0's t and omega, one component of camera 1's t: zero rows
         and columns).  With ``hold`` / ``share``: zero rows and columns for every held parameter, identical ones for tied
-        parameters, and sigma^2 with 3N + n_free unknowns.  ``scale="unit"``: (J^T J)^-1 with J in units x / f0; ``"residual"``: times sigma^2 =
+        parameters, and sigma^2 with 3N + n_free unknowns.  With ``hold_points``: zero 3 x 3 blocks at the held points, the
+        camera blocks of the problem with those points fixed, and sigma^2 with 3 (N - n_held) + n_free unknowns.  ``scale="unit"``: (J^T J)^-1 with J in units x / f0; ``"residual"``: times sigma^2 =
         E / (2 n_obs - (3N + 9m - 7)) (also returned as ``sigma2``).  ``frame="gauge"``: the normalised frame BA works in;
         ``"input"``: the caller's frame (omega as a rotation increment R <- Rod(omega) R in that frame).  The engine's
         state is left bitwise as it was.  Raises LinAlgError for a degenerate problem (a point seen once, a camera with
-        too few points)."""
+        too few points) -- a held point seen once is legal."""
         if scale not in ("unit", "residual") or frame not in ("input", "gauge"):
             raise ValueError("scale must be 'unit' or 'residual', frame 'input' or 'gauge'")
         if self._loss != "squared":
             raise NotImplementedError(f"covariance() is defined for the squared loss only (this adjuster uses loss={self._loss!r})")
         eng, cam0 = self._engine, self._init_camera0_params
         nf = {} if self._map is None else {"n_free": self._map[1]}
+        if self._held is not None:
+            nf["n_held"] = self.n_held_points
         if scale == "residual":
             residual_variance(0.0, eng.n_obs, self._n_points, self._n_images, **nf)  # (no redundancy: ValueError before any work)
         saved = None

@@ -131,6 +131,23 @@ int mvba_commit(mvba_handle *h);
  * P^T, zero rows and columns where held.  Sharded: every rank must set the same map (it acts after the all-reduce). */
 int mvba_set_parameter_map(mvba_handle *h, const int32_t *col, int32_t n_free);
 
+/* Held points: which points a trial adjusts.  held [n_points], nonzero = point a is not an unknown; NULL (or no nonzero
+ * entry) clears the mask.  A trial then solves the problem in the remaining 3 (n_points - n_held) + n_free unknowns: the
+ * normal equations with the held points' columns deleted and the same damping (1 + c) on the diagonals that remain.  K3a
+ * writes E_a^-1 = 0, v_a = 0 for a held point, so its -F^T E^-1 F terms vanish from the reduced camera system, b keeps its
+ * -2 Jc^T e term, and dX_a = 0: MVBA_BUF_DX is 0 and MVBA_BUF_TRIAL_X equals the committed X there, bit for bit.  The cost,
+ * the residuals and the robust weights run over every observation, those of held points included; MVBA_BUF_E /
+ * MVBA_BUF_DP stay the undamped sums they are.  E_a of a held point is never inverted: a held point seen once, or without
+ * parallax, is legal (MVBA_ERR_SINGULAR is for free points only).  Holding is per whole point, and in the frame the
+ * engine's state is in (the seven gauge slots stay held whatever the mask: holding three or more points does not free
+ * them).  May be called any time after mvba_create; keeps the linearisation, voids the trial (mvba_commit before the next
+ * mvba_try_step is MVBA_ERR_STATE).  Independent of the parameter map and of the loss.  mvba_covariance honours the mask:
+ * six zeros for a held point, no pivot test for it, and the camera blocks of the problem with those points fixed.
+ * mvba_triangulate_state with a mask set is MVBA_ERR_STATE: clear the mask first (a held point is not re-triangulated
+ * silently).  Sharded: the mask covers this rank's points, nothing is communicated.  Without a mask the engine issues the
+ * launches it issues today. */
+int mvba_set_point_hold(mvba_handle *h, const uint8_t *held);
+
 /* Marginal covariances at the COMMITTED state, undamped, gauge parameters fixed (zero rows/columns): the unit covariance
  * C = (J^T J)^-1 = 2 H^-1 over the free parameters (J: the residual Jacobian, units x / f0), camera parameters in the order
  * f, u, v, t[3], omega[3].  Runs K1, K3a at c = 0, the engine's K3 form, the all-reduce of [A|b] and K4's Cholesky, then
@@ -139,7 +156,7 @@ int mvba_set_parameter_map(mvba_handle *h, const int32_t *col, int32_t n_free);
  * timings_ms [4] (may be NULL): linearise+Schur, factor, inverse, point pass.  Afterwards the handle is as
  * mvba_linearize leaves it (no trial); the committed parameters are untouched.  MVBA_ERR_SINGULAR: a non-positive pivot of
  * the undamped reduced camera system, or a numerically singular point block E_a (a Cholesky pivot below 1e-12 of its largest
- * diagonal entry: a point seen once).  Sharded: every rank gets its own points' blocks and the same camera blocks.        */
+ * diagonal entry: a point seen once) of a point that is not held (mvba_set_point_hold).  Sharded: every rank gets its own points' blocks and the same camera blocks.        */
 int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *cam_cov_full, double *timings_ms);
 
 /* e [n_obs][2]: f0 e_o, the residual of every observation in image units at the COMMITTED state, in the engine's
@@ -201,8 +218,8 @@ enum {
   MVBA_BUF_A_FULL,       /* [9m][9m] symmetric, before gauge removal         */
   MVBA_BUF_B_FULL,       /* [9m]                                             */
   MVBA_BUF_DXI,          /* [9m] with zeros at the gauge slots (with a map: where held; equal where tied) */
-  MVBA_BUF_DX,           /* [n_points][3]                                    */
-  MVBA_BUF_TRIAL_X,      /* [n_points][3]                                    */
+  MVBA_BUF_DX,           /* [n_points][3]  (0 at held points)                */
+  MVBA_BUF_TRIAL_X,      /* [n_points][3]  (the committed X at held points)  */
   MVBA_BUF_TRIAL_CAM,    /* [m][15]  f,u,v,t[3],R[9]                         */
   MVBA_BUF_INDEX_K,      /* the Schur index as the kernel reads it: k-side observation of every item row */
   MVBA_BUF_INDEX_L,      /*   l-side observation                                                          */
@@ -249,8 +266,8 @@ int mvba_triangulate(const double *K, const double *R, const double *t, int32_t 
  * formed with the third row divided by f0, K[2][2] = 1: the same solution, and quality[0] is in the units of xy for any f0):
  * replaces the committed points; a point with status != 0 keeps its old
  * coordinates.  Voids the linearisation and the trial, as mvba_set_params does.  Independent of the loss.  Sharded: each
- * rank does its own points, nothing is communicated.  MVBA_ERR_STATE before the first mvba_set_params; MVBA_ERR_BADARG
- * above 1704 cameras. */
+ * rank does its own points, nothing is communicated.  MVBA_ERR_STATE before the first mvba_set_params, and while a point
+ * mask is set (mvba_set_point_hold: clear it first); MVBA_ERR_BADARG above 1704 cameras. */
 int mvba_triangulate_state(mvba_handle *h, int32_t n_refine, double *quality, int32_t *status, double *timings_ms);
 /* mvba_resect: every camera from known points, the normalised DLT.  X [n_points][3]; the list as in mvba_project (pt_ptr ==
  * NULL: the dense grid); point_ok [n_points] != 0 marks the points to use (NULL: those whose X is finite).
