@@ -1,5 +1,6 @@
-// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch) on hand-made inputs.  A program of
-// its own, meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
+// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch) and the host logic of a RANSAC
+// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks) on hand-made inputs.  A program of its own,
+// meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "mvba_host.h"
+#include "mvba_ransac_host.h"
 
 namespace mvba {
 thread_local std::string g_err;
@@ -84,6 +86,100 @@ int main() {
     CHECK(d.own == buf.data() + DepthScratch::prefix(blocks, m));
     for (double *p = d.Epart; p < d.own + 5; ++p) *p = 1.0;  // (every double of it is the vector's)
     CHECK(DepthScratch().own == nullptr);
+  }
+  {  // the pick of a count row: ties, all degenerate, below the minimum, a small item, H = 1
+    const int ON = RS_OK | RS_ACTIVE | RS_CUR;
+    const int tie[5] = {3, 9, -1, 9, 2};
+    RsPick k = rs_pick(tie, 5, 100, 8);
+    CHECK(k.best == 1 && k.status == 0 && k.state == ON);  // the first of the two nines
+    const int none[3] = {-1, -1, -1};
+    k = rs_pick(none, 3, 100, 6);
+    CHECK(k.best == -1 && k.status == 2 && k.state == 0);
+    const int low[4] = {-1, 5, 4, 5};
+    k = rs_pick(low, 4, 100, 6);
+    CHECK(k.best == 1 && k.status == 4 && k.state == 0);
+    CHECK(rs_pick(low, 4, 100, 4).status == 0);  // (the pose's minimum)
+    k = rs_pick(none, 3, 5, 6);  // an item below the minimum scores nothing: every count is -1
+    CHECK(k.best == -1 && k.status == 1 && k.state == 0);
+    CHECK(rs_pick(none, 3, 3, 4).status == 1 && rs_pick(none, 3, 7, 8).status == 1);
+    const int one[1] = {12};
+    k = rs_pick(one, 1, 12, 8);
+    CHECK(k.best == 0 && k.status == 0 && k.state == ON);
+    const int one_bad[1] = {-1};
+    CHECK(rs_pick(one_bad, 1, 12, 8).best == -1 && rs_pick(one_bad, 1, 12, 8).status == 2);
+  }
+  {  // the accept rule: two-view and pose have no first-refit minimum (0), the DLT's is 6
+    for (long long first_min : {0LL, 0LL, 6LL})
+      for (int r : {0, 1, 5}) {
+        if (first_min && r == 0) continue;  // (the DLT's first refit: below)
+        int st = RS_OK | RS_ACTIVE, n_active = 3;
+        CHECK(rs_accept(40, 40, r, first_min, st, n_active));  // an equal count is kept: the other buffer becomes current
+        CHECK(st == (RS_OK | RS_ACTIVE | RS_CUR) && n_active == 3);
+        CHECK(rs_accept(41, 40, r, first_min, st, n_active) && st == (RS_OK | RS_ACTIVE) && n_active == 3);
+        CHECK(!rs_accept(39, 40, r, first_min, st, n_active));  // one smaller: stops, on the buffer it had
+        CHECK(st == RS_OK && n_active == 2);
+      }
+    int st = RS_OK | RS_ACTIVE | RS_CUR, n_active = 1;
+    CHECK(rs_accept(6, 40, 0, 6, st, n_active) && st == (RS_OK | RS_ACTIVE) && n_active == 1);  // the DLT's first refit: 6 against 40
+    CHECK(!rs_accept(5, 40, 0, 6, st, n_active) && st == RS_OK && n_active == 0);
+    st = RS_OK | RS_ACTIVE; n_active = 1;
+    CHECK(!rs_accept(6, 40, 1, 6, st, n_active) && n_active == 0);  // its second is held to the kept count
+    st = RS_OK | RS_ACTIVE | RS_CUR; n_active = 2;
+    rs_stop(st, n_active);
+    CHECK(st == (RS_OK | RS_CUR) && n_active == 1);
+  }
+  {  // the chunk list: cameras with 0, 1, 256 and 257 observations, one listed twice; cameras = NULL
+    const long long cam_ptr[5] = {0, 0, 1, 257, 514};
+    const int32_t cams[5] = {3, 0, 2, 3, 1};
+    int64_t nu[5] = {-1, -1, -1, -1, -1};
+    CamChunks w;
+    CHECK(w.build(cam_ptr, cams, 5, 256, nu) == MVBA_OK);
+    const int want_n[5] = {257, 0, 256, 257, 1}, want_ch[6] = {0, 2, 2, 3, 5, 6};
+    const long long want_mask[5] = {0, 257, 257, 513, 770};
+    for (int c = 0; c < 5; ++c)
+      CHECK(w.cams[c] == cams[c] && w.lc_n[c] == want_n[c] && nu[c] == want_n[c] && w.lc_start[c] == cam_ptr[cams[c]] && w.lc_mask[c] == want_mask[c]);
+    for (int c = 0; c <= 5; ++c) CHECK(w.lc_ch[c] == want_ch[c]);
+    CHECK(w.n_ch == 6 && w.n_mask == 771 && w.ch_cam.size() == 6);
+    const int want_cam[6] = {0, 0, 2, 3, 3, 4}, want_cnt[6] = {256, 1, 256, 256, 1, 1};
+    const long long want_start[6] = {257, 513, 1, 257, 513, 0}, want_cmask[6] = {0, 256, 257, 513, 769, 770};
+    for (int i = 0; i < 6; ++i)
+      CHECK(w.ch_cam[i] == want_cam[i] && w.ch_cnt[i] == want_cnt[i] && w.ch_start[i] == want_start[i] && w.ch_mask[i] == want_cmask[i]);
+    CHECK(w.lc_mask[0] != w.lc_mask[3]);  // the camera listed twice has two mask ranges
+    CamChunks all;  // cameras = NULL: list position = camera, no n_usable
+    CHECK(all.build(cam_ptr, nullptr, 4, 256, nullptr) == MVBA_OK);
+    CHECK(all.n_ch == 4 && all.n_mask == 514 && all.lc_ch[1] == 0 && all.lc_ch[2] == 1 && all.lc_ch[3] == 2 && all.lc_ch[4] == 4);
+    for (int c = 0; c < 4; ++c) CHECK(all.cams[c] == c && all.lc_start[c] == cam_ptr[c] && all.lc_mask[c] == cam_ptr[c]);
+    CHECK(all.ch_cnt[3] == 1 && all.ch_start[3] == 513);
+    CamChunks small;  // another chunk size
+    CHECK(small.build(cam_ptr, nullptr, 4, 100, nullptr) == MVBA_OK && small.n_ch == 7 && small.ch_cnt[3] == 56 && small.ch_cnt[6] == 57);
+    CamChunks none;
+    CHECK(none.build(cam_ptr, cams, 0, 256, nullptr) == MVBA_OK && none.n_ch == 0 && none.n_mask == 0 && none.lc_ch.size() == 1);
+    const long long big_ptr[3] = {0, 5, 5 + (1LL << 31)};  // a run of 2^31: refused before anything of its size is made
+    CamChunks big;
+    g_err.clear();
+    CHECK(big.build(big_ptr, nullptr, 2, 256, nullptr) == MVBA_ERR_BADARG);
+    CHECK(g_err == "camera 1 has 2147483648 usable observations: must be < 2^31");
+    CHECK(big.n_ch == 0 && big.ch_cam.size() == 1);
+  }
+  {  // the argument checks, with their texts
+    CHECK(rs_check_search(0.01, 1) == MVBA_OK && rs_check_search(0.01, RS_MAX_HYP) == MVBA_OK && rs_check_refit(0) == MVBA_OK && rs_check_refit(RS_MAX_REFIT) == MVBA_OK);
+    CHECK(rs_check_search(0.0, 8) == MVBA_ERR_BADARG && g_err == "threshold = 0.000000 must be finite and > 0");
+    CHECK(rs_check_search(std::numeric_limits<double>::quiet_NaN(), 8) == MVBA_ERR_BADARG);
+    CHECK(rs_check_search(std::numeric_limits<double>::infinity(), 8) == MVBA_ERR_BADARG);
+    CHECK(rs_check_search(0.01, 0) == MVBA_ERR_BADARG && g_err == "n_hypotheses = 0 must be in 1 .. 65536");
+    CHECK(rs_check_search(0.01, 4097, 4096) == MVBA_ERR_BADARG && g_err == "n_hypotheses = 4097 must be in 1 .. 4096");
+    CHECK(rs_check_refit(17) == MVBA_ERR_BADARG && g_err == "n_refit = 17 must be in 0 .. 16");
+    CHECK(rs_check_refit(-1) == MVBA_ERR_BADARG);
+    const int32_t cams[3] = {0, 7, 8};
+    CHECK(check_camera_list(cams, 2, 8) == MVBA_OK && check_camera_list(nullptr, 8, 8) == MVBA_OK && check_camera_list(cams, 0, 8) == MVBA_OK);
+    CHECK(check_camera_list(cams, 3, 8) == MVBA_ERR_BADARG && g_err.rfind("cameras[2] = 8: ", 0) == 0 && g_err.find("n_images = 8") != std::string::npos);
+    CHECK(check_camera_list(nullptr, 3, 8) == MVBA_ERR_BADARG && g_err == "cameras = NULL lists every camera: n_cameras = 3 must be n_images = 8");
+    double tm[4] = {-1, -1, -1, -1};
+    RsLaps laps;
+    laps.upload = 1.0; laps.score += 2.0; laps.refit += 3.0; laps.other += 4.0;
+    laps.write(tm);
+    laps.write(nullptr);
+    CHECK(tm[0] == 1.0 && tm[1] == 2.0 && tm[2] == 3.0 && tm[3] == 4.0);
   }
   if (failures) return 1;
   std::printf("host_check ok\n");

@@ -36,6 +36,7 @@
 
 #include "mvba_common.h"
 #include "mvba_host.h"
+#include "mvba_ransac_host.h"
 
 namespace mvba {
 thread_local std::string g_err;

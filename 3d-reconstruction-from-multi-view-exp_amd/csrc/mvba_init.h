@@ -1,6 +1,6 @@
 // Initial estimates for BA (mvba_triangulate, mvba_triangulate_state, mvba_resect) -- kernels and host code, gfx950.
 //
-// Included by mvba.hip after mvba_start.h: uses its sym_eig_jacobi, eig_extremes, chunk_sum, init_check_list,
+// Included by mvba.hip after mvba_start.h: uses mvba_ransac_host.h's CamChunks, mvba_start.h's sym_eig_jacobi, eig_extremes, chunk_sum, init_check_list,
 // init_check_cameras, upload_list, InitClock and EvGuard, and mvba.hip's mvba_handle, DevBufs, fail and MVBA_HIP.  Nothing
 // here runs on the LM path, and nothing on the LM path calls into here.  
 //
@@ -361,6 +361,44 @@ struct ResectList {
   std::vector<double> cm_xy;
 };
 
+// The chunks of the listed cameras of such a list (CamChunks, chunks of START_CHUNK observations) with the list, the points
+// and the chunk arrays on the device.  K (the pose calls; [n_images][9]) goes up as the listed cameras' rows, or not at all.
+struct CamWork : CamChunks {
+  double *dX = nullptr, *dK = nullptr;
+  double2 *dxy = nullptr;
+  int *dpt = nullptr, *dcams = nullptr, *dlc_n = nullptr, *dlc_ch = nullptr, *dch_cam = nullptr, *dch_cnt = nullptr;
+  long long *dlc_start = nullptr, *dch_start = nullptr, *dch_mask = nullptr;
+
+  int upload(DevBufs &tmp, const ResectList &list, const double *X, int64_t n_points, const double *K) {
+    const int nl = (int)cams.size();
+    const long long n_used = list.cam_ptr.back();
+    int rc;
+    if ((rc = tmp.alloc(&dX, 3 * (size_t)n_points)) || (rc = tmp.alloc(&dxy, (size_t)n_used)) || (rc = tmp.alloc(&dpt, (size_t)n_used)) ||
+        (rc = tmp.alloc(&dcams, (size_t)nl)) || (rc = tmp.alloc(&dlc_n, (size_t)nl)) || (rc = tmp.alloc(&dlc_start, (size_t)nl)) ||
+        (rc = tmp.alloc(&dlc_ch, (size_t)nl + 1)) || (rc = tmp.alloc(&dch_cam, (size_t)n_ch)) || (rc = tmp.alloc(&dch_cnt, (size_t)n_ch)) ||
+        (rc = tmp.alloc(&dch_start, (size_t)n_ch)) || (rc = tmp.alloc(&dch_mask, (size_t)n_ch)))
+      return rc;
+    MVBA_HIP(hipMemcpy(dX, X, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dxy, list.cm_xy.data(), sizeof(double2) * n_used, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dpt, list.cm_pt.data(), sizeof(int) * n_used, hipMemcpyHostToDevice));
+    if (K) {
+      std::vector<double> Kl(9 * (size_t)nl);
+      for (int c = 0; c < nl; ++c) std::copy(K + 9 * (size_t)cams[c], K + 9 * (size_t)cams[c] + 9, Kl.begin() + 9 * (size_t)c);
+      if ((rc = tmp.alloc(&dK, 9 * (size_t)nl))) return rc;
+      MVBA_HIP(hipMemcpy(dK, Kl.data(), sizeof(double) * 9 * nl, hipMemcpyHostToDevice));
+    }
+    MVBA_HIP(hipMemcpy(dcams, cams.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dlc_n, lc_n.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dlc_start, lc_start.data(), sizeof(long long) * nl, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dlc_ch, lc_ch.data(), sizeof(int) * (nl + 1), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dch_cam, ch_cam.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dch_cnt, ch_cnt.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dch_start, ch_start.data(), sizeof(long long) * n_ch, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(dch_mask, ch_mask.data(), sizeof(long long) * n_ch, hipMemcpyHostToDevice));
+    return MVBA_OK;
+  }
+};
+
 void resect_build_list(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int m,
                        const uint8_t *point_ok, bool want_obs, ResectList &L) {
   std::vector<uint8_t> ok((size_t)n_points);
@@ -538,56 +576,33 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
   ResectList list;
   resect_build_list(X, n_points, pt_ptr, cam_idx, xy, m, point_ok, false, list);
   const std::vector<long long> &cam_ptr = list.cam_ptr;
-  const std::vector<int> &cm_pt = list.cm_pt;
-  const std::vector<double> &cm_xy = list.cm_xy;
-  const long long n_used = cam_ptr[m];
-  std::vector<int> cam_ch_ptr((size_t)m + 1, 0), ch_cam, ch_cnt;
-  std::vector<long long> ch_start;
-  for (int k = 0; k < m; ++k) {
-    for (long long s = cam_ptr[k]; s < cam_ptr[k + 1]; s += START_CHUNK) {
-      ch_cam.push_back(k);
-      ch_start.push_back(s);
-      ch_cnt.push_back((int)std::min<long long>(START_CHUNK, cam_ptr[k + 1] - s));
-    }
-    cam_ch_ptr[k + 1] = (int)ch_cam.size();
-  }
-  const int n_ch = (int)ch_cam.size();
+  CamWork w;  // (every camera: list position = camera)
+  if ((rc = w.build(cam_ptr.data(), nullptr, m, START_CHUNK, nullptr))) return rc;
+  const int n_ch = w.n_ch;
   std::vector<double> Pm(12 * (size_t)m, NAN), norm(RS_NORM * (size_t)m, 0.0), S40(40 * (size_t)m, 0.0), Sr((size_t)m, 0.0), ratio((size_t)m, NAN);
   std::vector<int> st((size_t)m, 1);
   double kernel_ms = 0.0;
   if (n_ch > 0) {
     if (device >= 0) MVBA_HIP(hipSetDevice(device));
     DevBufs tmp;
-    double *dX = nullptr, *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dP = nullptr;
-    double2 *dxy = nullptr;
-    int *dpt = nullptr, *dch_cam = nullptr, *dch_cnt = nullptr, *dcam_ch = nullptr;
-    long long *dch_start = nullptr;
-    if ((rc = tmp.alloc(&dX, 3 * (size_t)n_points)) || (rc = tmp.alloc(&dxy, (size_t)n_used)) || (rc = tmp.alloc(&dpt, (size_t)n_used)) ||
-        (rc = tmp.alloc(&dch_cam, (size_t)n_ch)) || (rc = tmp.alloc(&dch_cnt, (size_t)n_ch)) || (rc = tmp.alloc(&dch_start, (size_t)n_ch)) ||
-        (rc = tmp.alloc(&dcam_ch, (size_t)m + 1)) || (rc = tmp.alloc(&dpart, 40 * (size_t)n_ch)) || (rc = tmp.alloc(&dS, 40 * (size_t)m)) ||
+    double *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dP = nullptr;
+    if ((rc = w.upload(tmp, list, X, n_points, nullptr)) || (rc = tmp.alloc(&dpart, 40 * (size_t)n_ch)) || (rc = tmp.alloc(&dS, 40 * (size_t)m)) ||
         (rc = tmp.alloc(&dnorm, RS_NORM * (size_t)m)) || (rc = tmp.alloc(&dP, 12 * (size_t)m)))
       return rc;
-    MVBA_HIP(hipMemcpy(dX, X, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dxy, cm_xy.data(), sizeof(double2) * n_used, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dpt, cm_pt.data(), sizeof(int) * n_used, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dch_cam, ch_cam.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dch_cnt, ch_cnt.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dch_start, ch_start.data(), sizeof(long long) * n_ch, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dcam_ch, cam_ch_ptr.data(), sizeof(int) * (m + 1), hipMemcpyHostToDevice));
     if (timings_ms) timings_ms[0] = clk.lap();
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     EvGuard guard{ev, 4};
     for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
     const dim3 gm((m + 255) / 256), b256(256);
-    auto combine = [&](int nv) { hipLaunchKernelGGL(k_resect_combine, dim3((m * nv + 255) / 256), b256, 0, 0, m, nv, dcam_ch, dpart, dS); };
+    auto combine = [&](int nv) { hipLaunchKernelGGL(k_resect_combine, dim3((m * nv + 255) / 256), b256, 0, 0, m, nv, w.dlc_ch, dpart, dS); };
     hipEventRecord(ev[0], 0);
-    hipLaunchKernelGGL(k_resect_chunk<0>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, (const double *)nullptr, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<0>, dim3(n_ch), dim3(START_CHUNK), 0, 0, w.dch_cam, w.dch_start, w.dch_cnt, w.dpt, w.dxy, w.dX, (const double *)nullptr, dpart);
     combine(6);
     hipLaunchKernelGGL(k_resect_norm, gm, b256, 0, 0, m, 0, dS, dnorm);
-    hipLaunchKernelGGL(k_resect_chunk<1>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dnorm, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<1>, dim3(n_ch), dim3(START_CHUNK), 0, 0, w.dch_cam, w.dch_start, w.dch_cnt, w.dpt, w.dxy, w.dX, dnorm, dpart);
     combine(2);
     hipLaunchKernelGGL(k_resect_norm, gm, b256, 0, 0, m, 1, dS, dnorm);
-    hipLaunchKernelGGL(k_resect_chunk<2>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dnorm, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<2>, dim3(n_ch), dim3(START_CHUNK), 0, 0, w.dch_cam, w.dch_start, w.dch_cnt, w.dpt, w.dxy, w.dX, dnorm, dpart);
     combine(40);
     hipEventRecord(ev[1], 0);
     MVBA_HIP(hipGetLastError());
@@ -601,7 +616,7 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
     }
     MVBA_HIP(hipMemcpy(dP, Pm.data(), sizeof(double) * 12 * m, hipMemcpyHostToDevice));
     hipEventRecord(ev[2], 0);
-    hipLaunchKernelGGL(k_resect_chunk<3>, dim3(n_ch), dim3(START_CHUNK), 0, 0, dch_cam, dch_start, dch_cnt, dpt, dxy, dX, dP, dpart);
+    hipLaunchKernelGGL(k_resect_chunk<3>, dim3(n_ch), dim3(START_CHUNK), 0, 0, w.dch_cam, w.dch_start, w.dch_cnt, w.dpt, w.dxy, w.dX, dP, dpart);
     combine(1);
     hipEventRecord(ev[3], 0);
     MVBA_HIP(hipGetLastError());

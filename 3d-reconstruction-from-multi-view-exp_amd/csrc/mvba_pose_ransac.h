@@ -1,11 +1,12 @@
 // Calibrated robust resection (mvba_pose_robust, mvba_pose_refine, mvba_pose_sample): P3P RANSAC for camera poses with known
 // intrinsics and a pose-only Gauss-Newton refit against fixed points -- kernels and host code, gfx950.
 //
-// Included by mvba.hip after mvba_resect_ransac.h: uses its rr_inlier, k_resect_score, k_resect_gather, k_resect_mask and
-// k_resect_scatter as they are (a hypothesis is scored as the 12-double matrix K [R^T | -R^T t]), mvba_ransac.h's rs_sample,
-// RS_HYP_BLOCK, RS_MAX_HYP, RS_MAX_REFIT and state bits, mvba_twoview.h's tv_pair_tile, mvba_init.h's resect_build_list and
-// k_resect_combine, mvba_start.h's chunk_sum, init_check_list, InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and
-// MVBA_HIP.  Nothing here runs on the LM path.  
+// Included by mvba.hip after mvba_resect_ransac.h: uses its robust_cameras (the tile loop, with rr_inlier, k_resect_score,
+// k_resect_mask and k_resect_scatter as they are: a hypothesis is scored as the 12-double matrix K [R^T | -R^T t]) and
+// k_resect_gather, mvba_ransac.h's rs_sample and RS_HYP_BLOCK, mvba_ransac_host.h's argument checks, check_camera_list,
+// rs_stop and state bits, mvba_init.h's resect_build_list, CamWork and k_resect_combine, mvba_start.h's chunk_sum,
+// init_check_list, InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.
+// 
 //
 // The usable observations are sorted camera-major as for mvba_resect_robust; the listed cameras get their own list of
 // 256-observation chunks.  k_pose_hyp: one THREAD per hypothesis, registers only -- no LDS, no scratch: four observations,
@@ -401,15 +402,6 @@ __global__ __launch_bounds__(256) void k_pose_step(int cnt, int j, int n_steps, 
   for (int e = 0; e < 3; ++e) ps[9 + e] += x[e];
 }
 
-// pose[camera] = the pose of the camera's best hypothesis (best < 0: NaN), for the cnt cameras of a tile
-__global__ __launch_bounds__(256) void k_pose_gather(int cnt, int H, const int *__restrict__ best, const double *__restrict__ hypRt,
-                                                     double *__restrict__ pose) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= cnt * 12) return;
-  const int kl = t / 12, e = t - 12 * kl, b = best[kl];
-  pose[t] = b >= 0 ? hypRt[((size_t)kl * H + b) * 12 + e] : NAN;
-}
-
 // P[camera] = K [R^T | -R^T t] of the current poses of the cnt cameras of a tile
 __global__ __launch_bounds__(256) void k_pose_matrix(int cnt, const double *__restrict__ Kc, const double *__restrict__ pose, double *__restrict__ P) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -421,84 +413,9 @@ __global__ __launch_bounds__(256) void k_pose_matrix(int cnt, const double *__re
   for (int e = 0; e < 12; ++e) P[12 * (size_t)k + e] = Pk[e];
 }
 
-// The listed cameras' runs of a camera-major list and their chunks of 256 observations, on the host and on the device; a
-// listed camera's bytes in the mask buffers start at its offset in the concatenation of the listed runs.
-struct PoseWork {
-  std::vector<int> cams, lc_n, lc_ch, ch_cam, ch_cnt;
-  std::vector<long long> lc_start, lc_mask, ch_start, ch_mask;
-  long long n_mask = 0;
-  int n_ch = 0;
-  double *dX = nullptr, *dK = nullptr;
-  double2 *dxy = nullptr;
-  int *dpt = nullptr, *dcams = nullptr, *dlc_n = nullptr, *dlc_ch = nullptr, *dch_cam = nullptr, *dch_cnt = nullptr;
-  long long *dlc_start = nullptr, *dch_start = nullptr, *dch_mask = nullptr;
-
-  int build(const ResectList &list, const int32_t *cameras, int nl, int64_t *n_usable) {
-    cams.resize((size_t)nl); lc_n.resize((size_t)nl); lc_start.resize((size_t)nl); lc_mask.resize((size_t)nl);
-    lc_ch.assign((size_t)nl + 1, 0);
-    for (int c = 0; c < nl; ++c) {
-      const int k = cameras ? cameras[c] : c;
-      const long long n = list.cam_ptr[k + 1] - list.cam_ptr[k];
-      if (n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "camera " + std::to_string(k) + " has " + std::to_string(n) + " usable observations: must be < 2^31");
-      cams[c] = k;
-      lc_n[c] = (int)n;
-      lc_start[c] = list.cam_ptr[k];
-      lc_mask[c] = n_mask;
-      if (n_usable) n_usable[c] = n;
-      for (long long s = 0; s < n; s += START_CHUNK) {
-        ch_cam.push_back(c);
-        ch_start.push_back(list.cam_ptr[k] + s);
-        ch_mask.push_back(n_mask + s);
-        ch_cnt.push_back((int)std::min<long long>(START_CHUNK, n - s));
-      }
-      n_mask += n;
-      if (ch_cam.size() > (size_t)0x7fffffff) return fail(MVBA_ERR_BADARG, "too many chunks of 256 observations over the listed cameras");
-      lc_ch[c + 1] = (int)ch_cam.size();
-    }
-    n_ch = (int)ch_cam.size();
-    return MVBA_OK;
-  }
-
-  int upload(DevBufs &tmp, const ResectList &list, const double *X, int64_t n_points, const double *K) {
-    const int nl = (int)cams.size();
-    const long long n_used = list.cam_ptr.back();
-    int rc;
-    if ((rc = tmp.alloc(&dX, 3 * (size_t)n_points)) || (rc = tmp.alloc(&dxy, (size_t)n_used)) || (rc = tmp.alloc(&dpt, (size_t)n_used)) ||
-        (rc = tmp.alloc(&dK, 9 * (size_t)nl)) || (rc = tmp.alloc(&dcams, (size_t)nl)) || (rc = tmp.alloc(&dlc_n, (size_t)nl)) ||
-        (rc = tmp.alloc(&dlc_start, (size_t)nl)) || (rc = tmp.alloc(&dlc_ch, (size_t)nl + 1)) || (rc = tmp.alloc(&dch_cam, (size_t)n_ch)) ||
-        (rc = tmp.alloc(&dch_cnt, (size_t)n_ch)) || (rc = tmp.alloc(&dch_start, (size_t)n_ch)) || (rc = tmp.alloc(&dch_mask, (size_t)n_ch)))
-      return rc;
-    std::vector<double> Kl(9 * (size_t)nl);
-    for (int c = 0; c < nl; ++c) std::copy(K + 9 * (size_t)cams[c], K + 9 * (size_t)cams[c] + 9, Kl.begin() + 9 * (size_t)c);
-    MVBA_HIP(hipMemcpy(dX, X, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dxy, list.cm_xy.data(), sizeof(double2) * n_used, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dpt, list.cm_pt.data(), sizeof(int) * n_used, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dK, Kl.data(), sizeof(double) * 9 * nl, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dcams, cams.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dlc_n, lc_n.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dlc_start, lc_start.data(), sizeof(long long) * nl, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dlc_ch, lc_ch.data(), sizeof(int) * (nl + 1), hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dch_cam, ch_cam.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dch_cnt, ch_cnt.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dch_start, ch_start.data(), sizeof(long long) * n_ch, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dch_mask, ch_mask.data(), sizeof(long long) * n_ch, hipMemcpyHostToDevice));
-    return MVBA_OK;
-  }
-};
-
-// the checks mvba_resect_robust makes of its camera list, with the same messages
-int pose_check_cameras(const int32_t *cameras, int32_t n_cameras, int32_t m) {
-  if (!cameras && n_cameras != m)
-    return fail(MVBA_ERR_BADARG, "cameras = NULL lists every camera: n_cameras = " + std::to_string(n_cameras) + " must be n_images = " + std::to_string(m));
-  for (int32_t c = 0; cameras && c < n_cameras; ++c)
-    if (cameras[c] < 0 || cameras[c] >= m)
-      return fail(MVBA_ERR_BADARG, "cameras[" + std::to_string(c) + "] = " + std::to_string(cameras[c]) + ": camera index out of range, n_images = " + std::to_string(m));
-  return MVBA_OK;
-}
-
 // The Gauss-Newton passes 0 .. n_steps of the cnt cameras from list position c0 on, enqueued without a host round trip:
 // per pass the sums of the tile's chunks, a camera's chunks combined in ascending order, the step.
-void pose_iterate(const PoseWork &w, int c0, int cnt, int n_steps, const int *dstate, const unsigned char *dinl0, const unsigned char *dinl1,
+void pose_iterate(const CamWork &w, int c0, int cnt, int n_steps, const int *dstate, const unsigned char *dinl0, const unsigned char *dinl1,
                   double *dpose, double *dprev, double *dgn, int *dgflag, double *dpart, double *dS) {
   const int ch0 = w.lc_ch[c0], tch = w.lc_ch[c0 + cnt] - ch0;
   for (int j = 0; j <= n_steps; ++j) {
@@ -510,6 +427,65 @@ void pose_iterate(const PoseWork &w, int c0, int cnt, int n_steps, const int *ds
                        dprev + 12 * (size_t)c0, dgn + PG_SIZE * (size_t)c0, dgflag + c0);
   }
 }
+
+// The calibrated pose as a fit: nothing before the hypotheses, which also give (R, t); a refit is pose_iterate on the device.
+struct PoseFit {
+  static constexpr int MIN_OBS = PR_MIN_OBS, NV = PR_NV;
+  static constexpr size_t HYP_BYTES = PR_HYP_BYTES;
+  static constexpr long long FIRST_MIN = 0;  // (the first refit is held to the kept count as every later one)
+  double *R, *t;  // [n_cameras][9], [n_cameras][3], out
+  int n_refine;
+  double *dhypRt = nullptr, *dpose = nullptr, *dprev = nullptr, *dgn = nullptr;
+  int *dscore_n = nullptr, *dgflag = nullptr;
+  std::vector<double> Rc, Rn, gn, pivot;
+
+  int setup(DevBufs &tmp, const CamWork &w, int tile, int H) {
+    const size_t nl = w.cams.size();
+    int rc;
+    if ((rc = tmp.alloc(&dpose, 12 * nl)) || (rc = tmp.alloc(&dprev, 12 * nl)) || (rc = tmp.alloc(&dgn, PG_SIZE * nl)) || (rc = tmp.alloc(&dgflag, nl)) ||
+        (rc = tmp.alloc(&dscore_n, nl)) || (rc = tmp.alloc(&dhypRt, 12 * (size_t)tile * H)))
+      return rc;
+    // k_resect_score leaves a camera below ITS minimum alone: it is told 6 for every camera that has the 4 this one needs
+    std::vector<int> score_n(nl);
+    for (size_t c = 0; c < nl; ++c) score_n[c] = w.lc_n[c] >= PR_MIN_OBS ? std::max(w.lc_n[c], RR_MIN_OBS) : 0;
+    MVBA_HIP(hipMemcpy(dscore_n, score_n.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
+    Rc.resize(12 * (size_t)tile); Rn.resize(12 * (size_t)tile); gn.resize(PG_SIZE * (size_t)tile); pivot.resize((size_t)tile);
+    return MVBA_OK;
+  }
+  const int *score_n(const CamWork &) const { return dscore_n; }
+  void hypotheses(const CamTile &c) {
+    const CamWork &w = c.w;
+    hipLaunchKernelGGL(k_pose_hyp, dim3((c.H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, c.cnt), dim3(RS_HYP_BLOCK), 0, 0, c.c0, c.H, c.seed, w.dcams, w.dlc_start,
+                       w.dlc_n, w.dpt, w.dxy, w.dX, w.dK, c.dhypP, dhypRt, c.dhc);
+  }
+  void picked(const CamTile &c, const int *dbest) {
+    hipLaunchKernelGGL(k_resect_gather, dim3((c.cnt * 12 + 255) / 256), dim3(256), 0, 0, c.cnt, c.H, dbest, dhypRt, dpose + 12 * (size_t)c.c0);
+  }
+  int fetch(const CamTile &c, bool first) {
+    MVBA_HIP(hipMemcpy((first ? Rc : Rn).data(), dpose + 12 * (size_t)c.c0, sizeof(double) * 12 * c.cnt, hipMemcpyDeviceToHost));
+    if (first) std::fill(pivot.begin(), pivot.end(), 0.0);  // (no refit kept yet)
+    return MVBA_OK;
+  }
+  // n_refine Gauss-Newton steps over the current inliers, all on the device
+  int refit(const CamTile &c, int *tstate, int &n_active) {
+    pose_iterate(c.w, c.c0, c.cnt, n_refine, c.dstate, c.dinl0, c.dinl1, dpose, dprev, dgn, dgflag, c.dpart, c.dS);
+    hipLaunchKernelGGL(k_pose_matrix, c.gc, dim3(256), 0, 0, c.cnt, c.w.dK + 9 * (size_t)c.c0, dpose + 12 * (size_t)c.c0, c.dP + 12 * (size_t)c.c0);
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipMemcpy(gn.data(), dgn + PG_SIZE * (size_t)c.c0, sizeof(double) * PG_SIZE * c.cnt, hipMemcpyDeviceToHost));
+    for (int p = 0; p < c.cnt; ++p)
+      if ((tstate[p] & RS_ACTIVE) && gn[PG_SIZE * (size_t)p + PG_FAIL] >= 0.0) rs_stop(tstate[p], n_active);  // the pivot rule, or a pose that is not finite
+    return MVBA_OK;
+  }
+  void keep(int p) {
+    if (n_refine > 0) pivot[p] = gn[PG_SIZE * (size_t)p + PG_PIVOT];
+    for (int j = 0; j < 12; ++j) Rc[12 * (size_t)p + j] = Rn[12 * (size_t)p + j];
+  }
+  double output(int p, size_t g) const {
+    for (int j = 0; j < 9; ++j) R[9 * g + j] = Rc[12 * (size_t)p + j];
+    for (int j = 0; j < 3; ++j) t[3 * g + j] = Rc[12 * (size_t)p + 9 + j];
+    return pivot[p];
+  }
+};
 
 }  // namespace
 
@@ -534,195 +510,18 @@ int mvba_pose_robust(const double *X, int64_t n_points, const int64_t *pt_ptr, c
   if (!X || !xy || !K || (n_cameras > 0 && (!R || !t)))
     return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!X ? "X" : (!xy ? "xy" : (!K ? "K" : (!R ? "R" : "t")))) + " (argument " +
                                      std::to_string(!X ? 1 : (!xy ? 5 : (!K ? 9 : (!R ? 17 : 18)))) + ")");
-  if (!std::isfinite(threshold) || !(threshold > 0.0))
-    return fail(MVBA_ERR_BADARG, "threshold = " + std::to_string(threshold) + " must be finite and > 0");
-  if (n_hypotheses < 1 || n_hypotheses > RS_MAX_HYP)
-    return fail(MVBA_ERR_BADARG, "n_hypotheses = " + std::to_string(n_hypotheses) + " must be in 1 .. " + std::to_string(RS_MAX_HYP));
+  int rc;
+  if ((rc = rs_check_search(threshold, n_hypotheses))) return rc;
   if (n_refine < 0 || n_refine > PR_MAX_REFINE)
     return fail(MVBA_ERR_BADARG, "n_refine = " + std::to_string(n_refine) + " must be in 0 .. " + std::to_string(PR_MAX_REFINE));
-  if (n_refit < 0 || n_refit > RS_MAX_REFIT)
-    return fail(MVBA_ERR_BADARG, "n_refit = " + std::to_string(n_refit) + " must be in 0 .. " + std::to_string(RS_MAX_REFIT));
-  int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
-  if (rc) return rc;
-  const int m = n_images;
-  if ((rc = pose_check_cameras(cameras, n_cameras, m))) return rc;
-  if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
-  const int nl = n_cameras, H = n_hypotheses;
-  const double thr2 = threshold * threshold;
-  // the defaults are those of a camera without usable observations: status 1
-  for (int c = 0; c < nl; ++c) {
-    for (int j = 0; j < 9; ++j) R[9 * (size_t)c + j] = NAN;
-    for (int j = 0; j < 3; ++j) t[3 * (size_t)c + j] = NAN;
-    if (quality) quality[2 * c] = quality[2 * c + 1] = NAN;
-    if (n_usable) n_usable[c] = 0;
-    if (n_inliers) n_inliers[c] = 0;
-    if (best) best[c] = -1;
-    if (status) status[c] = 1;
-  }
-  if (inlier && n_obs) std::memset(inlier, 0, (size_t)n_obs);
-  if (hyp_count) std::fill(hyp_count, hyp_count + (size_t)nl * H, -1);
-  if (nl == 0) return MVBA_OK;
-
-  InitClock clk;
-  ResectList list;
-  resect_build_list(X, n_points, pt_ptr, cam_idx, xy, m, point_ok, inlier != nullptr, list);
-  const long long n_used = list.cam_ptr[m];
-  PoseWork w;
-  if ((rc = w.build(list, cameras, nl, n_usable))) return rc;
-  const int n_ch = w.n_ch;
-  if (n_ch == 0) {
-    if (timings_ms) timings_ms[0] = clk.lap();
-    return MVBA_OK;
-  }
-  // k_resect_score leaves a camera below ITS minimum alone: it is told 6 for every camera that has the 4 this one needs
-  std::vector<int> score_n((size_t)nl);
-  for (int c = 0; c < nl; ++c) score_n[c] = w.lc_n[c] >= PR_MIN_OBS ? std::max(w.lc_n[c], RR_MIN_OBS) : 0;
-
-  if (device >= 0) MVBA_HIP(hipSetDevice(device));
-  const int tile = tv_pair_tile(nl, PR_HYP_BYTES * (size_t)H);
-  DevBufs tmp;
-  double *dpart = nullptr, *dS = nullptr, *dP = nullptr, *dhypP = nullptr, *dhypRt = nullptr, *dpose = nullptr, *dprev = nullptr, *dgn = nullptr;
-  int *dscore_n = nullptr, *dstate = nullptr, *dbest = nullptr, *dhc = nullptr, *dgflag = nullptr;
-  long long *dobs = nullptr;
-  unsigned char *dinl0 = nullptr, *dinl1 = nullptr, *dout = nullptr;
-  if ((rc = w.upload(tmp, list, X, n_points, K))) return rc;
-  if ((rc = tmp.alloc(&dpart, PR_NV * (size_t)n_ch)) || (rc = tmp.alloc(&dS, PR_NV * (size_t)tile)) || (rc = tmp.alloc(&dP, 12 * (size_t)nl)) ||
-      (rc = tmp.alloc(&dpose, 12 * (size_t)nl)) || (rc = tmp.alloc(&dprev, 12 * (size_t)nl)) || (rc = tmp.alloc(&dgn, PG_SIZE * (size_t)nl)) ||
-      (rc = tmp.alloc(&dgflag, (size_t)nl)) || (rc = tmp.alloc(&dscore_n, (size_t)nl)) || (rc = tmp.alloc(&dstate, (size_t)nl)) ||
-      (rc = tmp.alloc(&dbest, (size_t)tile)) || (rc = tmp.alloc(&dhc, (size_t)tile * H)) || (rc = tmp.alloc(&dhypP, 12 * (size_t)tile * H)) ||
-      (rc = tmp.alloc(&dhypRt, 12 * (size_t)tile * H)) || (rc = tmp.alloc(&dinl0, (size_t)w.n_mask)) || (rc = tmp.alloc(&dinl1, (size_t)w.n_mask)))
+  if ((rc = rs_check_refit(n_refit)) || (rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs)) ||
+      (rc = check_camera_list(cameras, n_cameras, n_images)))
     return rc;
-  if (inlier && ((rc = tmp.alloc(&dout, (size_t)n_obs)) || (rc = tmp.alloc(&dobs, (size_t)n_used)))) return rc;
-  MVBA_HIP(hipMemcpy(dscore_n, score_n.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
-  if (inlier) {
-    MVBA_HIP(hipMemcpy(dobs, list.cm_obs.data(), sizeof(long long) * n_used, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemset(dout, 0, (size_t)n_obs));
-  }
-  double t_up = clk.lap(), t_score = 0.0, t_refit = 0.0, t_rest = 0.0;
-
-  const dim3 b256(256), bch(START_CHUNK);
-  const int hb = (H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK;
-  std::vector<int> hc((size_t)tile * H), bst((size_t)tile), state((size_t)nl, 0), st((size_t)tile);
-  std::vector<long long> nin((size_t)tile);
-  std::vector<double> Rc(12 * (size_t)tile), Rn(12 * (size_t)tile), gn(PG_SIZE * (size_t)tile), S2(2 * (size_t)tile), ssq((size_t)tile),
-      pivot((size_t)tile);
-  for (int c0 = 0; c0 < nl; c0 += tile) {
-    const int cnt = std::min(tile, nl - c0), ch0 = w.lc_ch[c0], tch = w.lc_ch[c0 + cnt] - ch0;
-    const dim3 gch((unsigned)std::max(tch, 1)), gc((cnt + 255) / 256);
-    const int *tcam = w.dch_cam + ch0, *tcnt = w.dch_cnt + ch0;
-    const long long *tstart = w.dch_start + ch0, *tmask = w.dch_mask + ch0;
-    int *tstate = state.data() + c0;
-    auto put_state = [&]() -> int {
-      MVBA_HIP(hipMemcpy(dstate + c0, tstate, sizeof(int) * cnt, hipMemcpyHostToDevice));
-      return MVBA_OK;
-    };
-    // the inlier sets of dP under the cameras' states: counts and sums of d^2 into S2
-    auto mask = [&]() -> int {
-      int r = put_state();
-      if (r) return r;
-      if (tch > 0) hipLaunchKernelGGL(k_resect_mask, gch, bch, 0, 0, tcam, tstart, tmask, tcnt, w.dpt, w.dxy, w.dX, dstate, dP, thr2, dinl0, dinl1, dpart + 2 * (size_t)ch0);
-      hipLaunchKernelGGL(k_resect_combine, dim3((cnt * 2 + 255) / 256), b256, 0, 0, cnt, 2, w.dlc_ch + c0, dpart, dS);
-      MVBA_HIP(hipGetLastError());
-      MVBA_HIP(hipMemcpy(S2.data(), dS, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost));
-      return MVBA_OK;
-    };
-
-    hipLaunchKernelGGL(k_pose_hyp, dim3(hb, cnt), dim3(RS_HYP_BLOCK), 0, 0, c0, H, (unsigned long long)seed, w.dcams, w.dlc_start, w.dlc_n, w.dpt, w.dxy,
-                       w.dX, w.dK, dhypP, dhypRt, dhc);
-    if (tch > 0)
-      hipLaunchKernelGGL(k_resect_score, dim3((unsigned)tch, hb), bch, 0, 0, c0, H, tcam, tstart, tcnt, dscore_n, w.dpt, w.dxy, w.dX, dhypP, thr2, dhc);
-    MVBA_HIP(hipGetLastError());
-    MVBA_HIP(hipMemcpy(hc.data(), dhc, sizeof(int) * (size_t)cnt * H, hipMemcpyDeviceToHost));
-    t_score += clk.lap();
-
-    // arg-max on the host: the largest count, the lowest h on ties
-    for (int p = 0; p < cnt; ++p) {
-      const int *c = hc.data() + (size_t)p * H;
-      int b = 0;
-      for (int h = 1; h < H; ++h)
-        if (c[h] > c[b]) b = h;
-      st[p] = w.lc_n[c0 + p] < PR_MIN_OBS ? 1 : (c[b] < 0 ? 2 : (c[b] < PR_MIN_OBS ? 4 : 0));
-      bst[p] = c[b] < 0 ? -1 : b;  // (status 1 and 2: every count is -1)
-      tstate[p] = st[p] == 0 ? (RS_OK | RS_ACTIVE | RS_CUR) : 0;  // (the first mask goes into buffer 0)
-    }
-    MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_resect_gather, dim3((cnt * 12 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhypP, dP + 12 * (size_t)c0);
-    hipLaunchKernelGGL(k_pose_gather, dim3((cnt * 12 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhypRt, dpose + 12 * (size_t)c0);
-    if ((rc = mask())) return rc;
-    MVBA_HIP(hipMemcpy(Rc.data(), dpose + 12 * (size_t)c0, sizeof(double) * 12 * cnt, hipMemcpyDeviceToHost));
-    int n_active = 0;
-    for (int p = 0; p < cnt; ++p) {
-      if (st[p]) continue;
-      tstate[p] ^= RS_CUR;
-      nin[p] = (long long)S2[2 * p];
-      ssq[p] = S2[2 * p + 1];
-      pivot[p] = 0.0;  // (no refit kept yet)
-      ++n_active;
-    }
-    t_rest += clk.lap();
-
-    // refits: n_refine Gauss-Newton steps over the current inliers, all on the device; kept while the set does not shrink
-    for (int r = 0; r < n_refit && n_active > 0; ++r) {
-      if ((rc = put_state())) return rc;
-      pose_iterate(w, c0, cnt, n_refine, dstate, dinl0, dinl1, dpose, dprev, dgn, dgflag, dpart, dS);
-      hipLaunchKernelGGL(k_pose_matrix, gc, b256, 0, 0, cnt, w.dK + 9 * (size_t)c0, dpose + 12 * (size_t)c0, dP + 12 * (size_t)c0);
-      MVBA_HIP(hipGetLastError());
-      MVBA_HIP(hipMemcpy(gn.data(), dgn + PG_SIZE * (size_t)c0, sizeof(double) * PG_SIZE * cnt, hipMemcpyDeviceToHost));
-      for (int p = 0; p < cnt; ++p)
-        if ((tstate[p] & RS_ACTIVE) && gn[PG_SIZE * (size_t)p + PG_FAIL] >= 0.0) {  // the pivot rule, or a pose that is not finite
-          tstate[p] &= ~RS_ACTIVE;
-          --n_active;
-        }
-      if (n_active == 0) break;
-      if ((rc = mask())) return rc;
-      MVBA_HIP(hipMemcpy(Rn.data(), dpose + 12 * (size_t)c0, sizeof(double) * 12 * cnt, hipMemcpyDeviceToHost));
-      for (int p = 0; p < cnt; ++p) {
-        if (!(tstate[p] & RS_ACTIVE)) continue;
-        const long long c = (long long)S2[2 * p];
-        if (c >= nin[p]) {
-          tstate[p] ^= RS_CUR;
-          nin[p] = c;
-          ssq[p] = S2[2 * p + 1];
-          if (n_refine > 0) pivot[p] = gn[PG_SIZE * (size_t)p + PG_PIVOT];
-          for (int j = 0; j < 12; ++j) Rc[12 * (size_t)p + j] = Rn[12 * (size_t)p + j];
-        } else {
-          tstate[p] &= ~RS_ACTIVE;
-          --n_active;
-        }
-      }
-    }
-    t_refit += clk.lap();
-
-    if (inlier && tch > 0) {
-      if ((rc = put_state())) return rc;
-      hipLaunchKernelGGL(k_resect_scatter, gch, bch, 0, 0, tcam, tstart, tmask, tcnt, dobs, dstate, dinl0, dinl1, dout);
-      MVBA_HIP(hipGetLastError());
-    }
-    for (int p = 0; p < cnt; ++p) {
-      const size_t g = (size_t)c0 + p;
-      if (status) status[g] = st[p];
-      if (best) best[g] = bst[p];
-      if (hyp_count) std::copy(hc.begin() + (size_t)p * H, hc.begin() + (size_t)(p + 1) * H, hyp_count + g * H);
-      if (st[p]) continue;
-      for (int j = 0; j < 9; ++j) R[9 * g + j] = Rc[12 * (size_t)p + j];
-      for (int j = 0; j < 3; ++j) t[3 * g + j] = Rc[12 * (size_t)p + 9 + j];
-      if (n_inliers) n_inliers[g] = nin[p];
-      if (quality) {
-        quality[2 * g] = sqrt(ssq[p] / (double)nin[p]);
-        quality[2 * g + 1] = pivot[p];
-      }
-    }
-    t_rest += clk.lap();
-  }
-  if (inlier) MVBA_HIP(hipMemcpy(inlier, dout, (size_t)n_obs, hipMemcpyDeviceToHost));
-  t_rest += clk.lap();
-  if (timings_ms) {
-    timings_ms[0] = t_up;
-    timings_ms[1] = t_score;
-    timings_ms[2] = t_refit;
-    timings_ms[3] = t_rest;
-  }
-  return MVBA_OK;
+  std::fill(R, R + 9 * (size_t)n_cameras, NAN);
+  std::fill(t, t + 3 * (size_t)n_cameras, NAN);
+  PoseFit fit{R, t, n_refine};
+  return robust_cameras(fit, X, n_points, pt_ptr, cam_idx, xy, n_obs, n_images, point_ok, K, cameras, n_cameras, threshold, n_hypotheses, seed, n_refit,
+                        quality, n_usable, n_inliers, best, inlier, hyp_count, status, timings_ms, device);
 }
 
 int mvba_pose_refine(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
@@ -738,7 +537,7 @@ int mvba_pose_refine(const double *X, int64_t n_points, const int64_t *pt_ptr, c
   int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
   if (rc) return rc;
   const int m = n_images, nl = n_cameras;
-  if ((rc = pose_check_cameras(cameras, n_cameras, m))) return rc;
+  if ((rc = check_camera_list(cameras, n_cameras, m))) return rc;
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = 0.0;
   for (int c = 0; c < nl; ++c) {
     if (quality) quality[3 * c] = quality[3 * c + 1] = quality[3 * c + 2] = NAN;
@@ -750,8 +549,8 @@ int mvba_pose_refine(const double *X, int64_t n_points, const int64_t *pt_ptr, c
   InitClock clk;
   ResectList list;
   resect_build_list(X, n_points, pt_ptr, cam_idx, xy, m, point_ok, obs_ok != nullptr, list);
-  PoseWork w;
-  if ((rc = w.build(list, cameras, nl, nullptr))) return rc;
+  CamWork w;
+  if ((rc = w.build(list.cam_ptr.data(), cameras, nl, START_CHUNK, nullptr))) return rc;
   // the byte mask over the listed runs: obs_ok in the sorted order; a camera needs three observations under it
   std::vector<unsigned char> msk((size_t)w.n_mask, 1);
   std::vector<int> state((size_t)nl, 0);

@@ -1,7 +1,8 @@
 // Robust two-view geometry (mvba_two_view_robust, mvba_ransac_sample): 8-point RANSAC for the fundamental matrix -- kernels
 // and host code, gfx950.
 //
-// Included by mvba.hip after mvba_twoview.h: uses its rs_shared, tv_pass, tv_row, rs_sampson, tv_denormalise, k_twoview_combine,
+// Included by mvba.hip after mvba_twoview.h: uses mvba_ransac_host.h's argument checks, rs_pick, rs_accept, RsLaps, limits and
+// state bits, mvba_twoview.h's rs_shared, tv_pass, tv_row, rs_sampson, tv_denormalise, k_twoview_combine,
 // k_twoview_norm, twoview_solve_pair, tv_pair_tile, tv_combine and constants, mvba_start.h's chunk_sum, checks, upload_list,
 // InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
 //
@@ -18,12 +19,63 @@
 namespace {
 
 constexpr int RS_HYP_BLOCK = 64;      // hypotheses per workgroup of k_ransac_hyp, and per LDS block of k_ransac_score
-constexpr int RS_MAX_HYP = 65536;     // n_hypotheses
-constexpr int RS_MAX_REFIT = 16;      // n_refit
 // device bytes one pair of a tile takes per point of the scene (32 compacted observation, 4 point id, 2 masks, 1 mask by
 // point, 1.42 chunk counts and partials) and per hypothesis (72 F^, 72 F, 4 count), rounded up: the tile's bound
 constexpr size_t RS_POINT_BYTES = 48, RS_HYP_BYTES = 160;
-enum { RS_CUR = 1, RS_ACTIVE = 2, RS_OK = 4 };  // per-pair state: the current mask buffer, still refitting, status 0
+
+// The eigenvector of the smallest eigenvalue of a thread's symmetric N x N matrix by cyclic Jacobi with A and V in LDS,
+// element-major: sA and sV are the thread's columns, element e at [e * RS_HYP_BLOCK].  A is filled by the caller, V is set
+// to the identity here.  false if not good (v is untouched then), or if the second-smallest eigenvalue fails the pivot rule.
+template <int N>
+__device__ __forceinline__ bool rs_lds_eig(double *sA, double *sV, bool good, double (&v)[N]) {
+  auto A = [&](int r, int c) -> double & { return sA[(r * N + c) * RS_HYP_BLOCK]; };
+  auto V = [&](int r, int c) -> double & { return sV[(r * N + c) * RS_HYP_BLOCK]; };
+  for (int e = 0; e < N * N; ++e) sV[e * RS_HYP_BLOCK] = (e % (N + 1) == 0) ? 1.0 : 0.0;
+  // sym_eig_jacobi's rotations and stopping rule, with run-time indices into LDS
+  for (int sweep = 0; sweep < 30 && good; ++sweep) {
+    bool any = false;
+    for (int a = 0; a < N - 1; ++a)
+      for (int b = a + 1; b < N; ++b) {
+        const double apq = A(a, b), app = A(a, a), aqq = A(b, b);
+        const double g = fabs(apq);
+        if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
+          A(a, b) = A(b, a) = 0.0;
+          continue;
+        }
+        any = true;
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+        A(a, a) = app - t * apq;
+        A(b, b) = aqq + t * apq;
+        A(a, b) = A(b, a) = 0.0;
+        for (int r = 0; r < N; ++r) {
+          if (r != a && r != b) {
+            const double arp = A(r, a), arq = A(r, b);
+            A(r, a) = A(a, r) = arp - s * (arq + tau * arp);
+            A(r, b) = A(b, r) = arq + s * (arp - tau * arq);
+          }
+          const double vrp = V(r, a), vrq = V(r, b);
+          V(r, a) = vrp - s * (vrq + tau * vrp);
+          V(r, b) = vrq + s * (vrp - tau * vrq);
+        }
+      }
+    if (!any) break;
+  }
+  if (!good) return false;
+  int best = 0;
+  double l1 = A(0, 0), lmax = A(0, 0), l2 = HUGE_VAL;
+  for (int e = 1; e < N; ++e) {
+    const double d = A(e, e);
+    if (d < l1) { l1 = d; best = e; }
+    lmax = fmax(lmax, d);
+  }
+  for (int e = 0; e < N; ++e)
+    if (e != best) l2 = fmin(l2, A(e, e));
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] = V(e, best);
+  return l2 > INIT_REL_PIVOT * lmax;
+}
 
 __host__ __device__ __forceinline__ unsigned long long rs_mix(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;
@@ -169,7 +221,6 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, i
   if (good) {
     double *sA = s_rs + tid, *sV = s_rs + 81 * RS_HYP_BLOCK + tid;
     auto A = [&](int r, int c) -> double & { return sA[(r * 9 + c) * RS_HYP_BLOCK]; };
-    auto V = [&](int r, int c) -> double & { return sV[(r * 9 + c) * RS_HYP_BLOCK]; };
     const double *nm = norm + TV_NORM * (size_t)p;
     long long idx[8];
     rs_sample(seed, pairs[2 * p], pairs[2 * p + 1], h, n, idx);
@@ -198,51 +249,8 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, i
           A(d, b) = M[e];
         }
     }
-    for (int e = 0; e < 81; ++e) sV[e * RS_HYP_BLOCK] = (e % 10 == 0) ? 1.0 : 0.0;
-    // sym_eig_jacobi's rotations and stopping rule, with run-time indices into LDS
-    for (int sweep = 0; sweep < 30 && good; ++sweep) {
-      bool any = false;
-      for (int a = 0; a < 8; ++a)
-        for (int b = a + 1; b < 9; ++b) {
-          const double apq = A(a, b), app = A(a, a), aqq = A(b, b);
-          const double g = fabs(apq);
-          if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
-            A(a, b) = A(b, a) = 0.0;
-            continue;
-          }
-          any = true;
-          const double theta = (aqq - app) / (2.0 * apq);
-          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-          A(a, a) = app - t * apq;
-          A(b, b) = aqq + t * apq;
-          A(a, b) = A(b, a) = 0.0;
-          for (int r = 0; r < 9; ++r) {
-            if (r != a && r != b) {
-              const double arp = A(r, a), arq = A(r, b);
-              A(r, a) = A(a, r) = arp - s * (arq + tau * arp);
-              A(r, b) = A(b, r) = arq + s * (arp - tau * arq);
-            }
-            const double vrp = V(r, a), vrq = V(r, b);
-            V(r, a) = vrp - s * (vrq + tau * vrp);
-            V(r, b) = vrq + s * (vrp - tau * vrq);
-          }
-        }
-      if (!any) break;
-    }
+    good = rs_lds_eig<9>(sA, sV, good, fh);
     if (good) {
-      int best = 0;
-      double l1 = A(0, 0), lmax = A(0, 0), l2 = HUGE_VAL;
-      for (int e = 1; e < 9; ++e) {
-        const double d = A(e, e);
-        if (d < l1) { l1 = d; best = e; }
-        lmax = fmax(lmax, d);
-      }
-      for (int e = 0; e < 9; ++e)
-        if (e != best) l2 = fmin(l2, A(e, e));
-      good = l2 > INIT_REL_PIVOT * lmax;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) fh[e] = V(e, best);
       tv_denormalise(nm, fh, F);  // (no rank-2 step: a hypothesis is scored as the sample gives it)
 #pragma unroll
       for (int e = 0; e < 9; ++e) good = good && isfinite(F[e]);
@@ -359,14 +367,9 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
   if (!xy || (n_pairs > 0 && (!pairs || !F)))
     return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!xy ? "xy" : (!pairs ? "pairs" : "F")) + " (argument " +
                                      std::to_string(!xy ? 5 : (!pairs ? 7 : 13)) + ")");
-  if (!std::isfinite(threshold) || !(threshold > 0.0))
-    return fail(MVBA_ERR_BADARG, "threshold = " + std::to_string(threshold) + " must be finite and > 0");
-  if (n_hypotheses < 1 || n_hypotheses > RS_MAX_HYP)
-    return fail(MVBA_ERR_BADARG, "n_hypotheses = " + std::to_string(n_hypotheses) + " must be in 1 .. " + std::to_string(RS_MAX_HYP));
-  if (n_refit < 0 || n_refit > RS_MAX_REFIT)
-    return fail(MVBA_ERR_BADARG, "n_refit = " + std::to_string(n_refit) + " must be in 0 .. " + std::to_string(RS_MAX_REFIT));
-  int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
-  if (rc) return rc;
+  int rc;
+  if ((rc = rs_check_search(threshold, n_hypotheses)) || (rc = rs_check_refit(n_refit))) return rc;
+  if ((rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs))) return rc;
   if ((rc = init_check_cameras(n_images))) return rc;
   if ((rc = check_pairs(pairs, n_pairs, n_images))) return rc;
   if ((rc = check_ascending(n_points, pt_ptr, cam_idx))) return rc;
@@ -411,7 +414,8 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
   MVBA_HIP(hipMemcpy(dpairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice));
   const int hyp_lds = (int)(sizeof(double) * 2 * 81 * RS_HYP_BLOCK);
   MVBA_HIP(hipFuncSetAttribute((const void *)k_ransac_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, hyp_lds));
-  double t_up = clk.lap(), t_score = 0.0, t_refit = 0.0, t_rest = 0.0;
+  RsLaps laps;
+  laps.upload = clk.lap();
 
   const dim3 b256(256), bch(START_CHUNK);
   std::vector<int> ntot((size_t)tile), hc((size_t)tile * H), bst((size_t)tile), state((size_t)tile), st((size_t)tile);
@@ -459,17 +463,13 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
     MVBA_HIP(hipMemcpy(hc.data(), dhc, sizeof(int) * (size_t)cnt * H, hipMemcpyDeviceToHost));
     MVBA_HIP(hipMemcpy(ntot.data(), dntot, sizeof(int) * cnt, hipMemcpyDeviceToHost));
     MVBA_HIP(hipMemcpy(norm.data(), dnorm, sizeof(double) * TV_NORM * cnt, hipMemcpyDeviceToHost));
-    t_score += clk.lap();
+    laps.score += clk.lap();
 
-    // arg-max on the host: the largest count, the lowest h on ties
     for (int p = 0; p < cnt; ++p) {
-      const int *c = hc.data() + (size_t)p * H;
-      int b = 0;
-      for (int h = 1; h < H; ++h)
-        if (c[h] > c[b]) b = h;
-      st[p] = ntot[p] < TV_MIN_SHARED ? 1 : (c[b] < 0 ? 2 : (c[b] < TV_MIN_SHARED ? 4 : 0));
-      bst[p] = c[b] < 0 ? -1 : b;  // (status 1 and 2: every count is -1)
-      state[p] = st[p] == 0 ? (RS_OK | RS_ACTIVE | RS_CUR) : 0;  // (the first mask goes into buffer 0)
+      const RsPick pick = rs_pick(hc.data() + (size_t)p * H, H, ntot[p], TV_MIN_SHARED);
+      st[p] = pick.status;
+      bst[p] = pick.best;
+      state[p] = pick.state;
     }
     MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_ransac_gather, dim3((cnt * 9 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhypF, dhypf, dF, dfb);
@@ -486,7 +486,7 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
       if (st[p]) state[p] = 0;
       else ++n_active;
     }
-    t_rest += clk.lap();
+    laps.other += clk.lap();
 
     // refits: the full fit on the current inliers alone, kept while its own inlier set does not shrink
     for (int r = 0; r < n_refit && n_active > 0; ++r) {
@@ -499,10 +499,7 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
       for (int p = 0; p < cnt; ++p) {
         for (int j = 0; j < 9; ++j) Fn[9 * (size_t)p + j] = NAN;
         if (!(state[p] & RS_ACTIVE)) continue;
-        if (twoview_solve_pair(S.data() + 45 * (size_t)p, norm.data() + TV_NORM * (size_t)p, Fn.data() + 9 * (size_t)p, &rt[p])) {
-          state[p] &= ~RS_ACTIVE;
-          --n_active;
-        }
+        if (twoview_solve_pair(S.data() + 45 * (size_t)p, norm.data() + TV_NORM * (size_t)p, Fn.data() + 9 * (size_t)p, &rt[p])) rs_stop(state[p], n_active);
       }
       if (n_active == 0) break;
       MVBA_HIP(hipMemcpy(dF, Fn.data(), sizeof(double) * 9 * cnt, hipMemcpyHostToDevice));
@@ -510,19 +507,14 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
       for (int p = 0; p < cnt; ++p) {
         if (!(state[p] & RS_ACTIVE)) continue;
         const long long c = (long long)S2[2 * p];
-        if (c >= nin[p]) {
-          state[p] ^= RS_CUR;
-          nin[p] = c;
-          ssq[p] = S2[2 * p + 1];
-          ratio[p] = rt[p];
-          for (int j = 0; j < 9; ++j) Fc[9 * (size_t)p + j] = Fn[9 * (size_t)p + j];
-        } else {
-          state[p] &= ~RS_ACTIVE;
-          --n_active;
-        }
+        if (!rs_accept(c, nin[p], r, 0, state[p], n_active)) continue;
+        nin[p] = c;
+        ssq[p] = S2[2 * p + 1];
+        ratio[p] = rt[p];
+        for (int j = 0; j < 9; ++j) Fc[9 * (size_t)p + j] = Fn[9 * (size_t)p + j];
       }
     }
-    t_refit += clk.lap();
+    laps.refit += clk.lap();
 
     if (inlier) {
       MVBA_HIP(hipMemcpy(dstate, state.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
@@ -545,14 +537,9 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
         quality[2 * g + 1] = ratio[p];
       }
     }
-    t_rest += clk.lap();
+    laps.other += clk.lap();
   }
-  if (timings_ms) {
-    timings_ms[0] = t_up;
-    timings_ms[1] = t_score;
-    timings_ms[2] = t_refit;
-    timings_ms[3] = t_rest;
-  }
+  laps.write(timings_ms);
   return MVBA_OK;
 }
 

@@ -1,9 +1,9 @@
 // Robust resection (mvba_resect_robust, mvba_resect_sample): 6-point RANSAC for camera matrices -- kernels and host code,
 // gfx950.
 //
-// Included by mvba.hip after mvba_ransac.h: uses its rs_sample, RS_HYP_BLOCK, RS_MAX_HYP, RS_MAX_REFIT and state bits,
-// mvba_twoview.h's tv_pair_tile, mvba_init.h's resect_build_list, rs_pass, k_resect_chunk, k_resect_combine, k_resect_norm,
-// resect_solve_camera and resect_denormalise, mvba_start.h's chunk_sum, init_check_list, InitClock and INIT_REL_PIVOT, and
+// Included by mvba.hip after mvba_ransac.h: uses its rs_sample, rs_lds_eig and RS_HYP_BLOCK, mvba_ransac_host.h's argument
+// checks, rs_pick, rs_accept, rs_stop, RsLaps and state bits, mvba_twoview.h's tv_pair_tile, mvba_init.h's resect_build_list,
+// CamWork, rs_pass, k_resect_chunk, k_resect_combine, k_resect_norm, resect_solve_camera and resect_denormalise, mvba_start.h's chunk_sum, init_check_list, InitClock and INIT_REL_PIVOT, and
 // mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
 //
 // The usable observations are sorted camera-major on the host as for mvba_resect, so a camera's observations are a dense run
@@ -74,7 +74,6 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_resect_hyp(int cam0, int H, un
   if (good) {
     double *sA = s_rr + tid, *sV = s_rr + 144 * RS_HYP_BLOCK + tid;
     auto A = [&](int r, int c) -> double & { return sA[(r * 12 + c) * RS_HYP_BLOCK]; };
-    auto V = [&](int r, int c) -> double & { return sV[(r * 12 + c) * RS_HYP_BLOCK]; };
     const double *nm = norm + RS_NORM * (size_t)k;
     long long idx[6];
     rs_sample(seed, cams[k], cams[k], h, n, idx);
@@ -91,10 +90,7 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_resect_hyp(int cam0, int H, un
     }
 #pragma unroll
     for (int e = 0; e < 40; ++e) good = good && isfinite(S[e]);
-    for (int e = 0; e < 144; ++e) {
-      sA[e * RS_HYP_BLOCK] = 0.0;
-      sV[e * RS_HYP_BLOCK] = (e % 13 == 0) ? 1.0 : 0.0;
-    }
+    for (int e = 0; e < 144; ++e) sA[e * RS_HYP_BLOCK] = 0.0;
     {  // resect_solve_camera's matrix from the 40 sums
       int e = 0;
 #pragma unroll
@@ -109,53 +105,9 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_resect_hyp(int cam0, int H, un
           A(8 + a, 8 + b) = wh; A(8 + b, 8 + a) = wh;
         }
     }
-    // sym_eig_jacobi's rotations and stopping rule, with run-time indices into LDS
-    for (int sweep = 0; sweep < 30 && good; ++sweep) {
-      bool any = false;
-      for (int a = 0; a < 11; ++a)
-        for (int b = a + 1; b < 12; ++b) {
-          const double apq = A(a, b), app = A(a, a), aqq = A(b, b);
-          const double g = fabs(apq);
-          if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
-            A(a, b) = A(b, a) = 0.0;
-            continue;
-          }
-          any = true;
-          const double theta = (aqq - app) / (2.0 * apq);
-          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-          A(a, a) = app - t * apq;
-          A(b, b) = aqq + t * apq;
-          A(a, b) = A(b, a) = 0.0;
-          for (int r = 0; r < 12; ++r) {
-            if (r != a && r != b) {
-              const double arp = A(r, a), arq = A(r, b);
-              A(r, a) = A(a, r) = arp - s * (arq + tau * arp);
-              A(r, b) = A(b, r) = arq + s * (arp - tau * arq);
-            }
-            const double vrp = V(r, a), vrq = V(r, b);
-            V(r, a) = vrp - s * (vrq + tau * vrp);
-            V(r, b) = vrq + s * (vrp - tau * vrq);
-          }
-        }
-      if (!any) break;
-    }
-    if (good) {
-      int best = 0;
-      double l1 = A(0, 0), lmax = A(0, 0), l2 = HUGE_VAL;
-      for (int e = 1; e < 12; ++e) {
-        const double d = A(e, e);
-        if (d < l1) { l1 = d; best = e; }
-        lmax = fmax(lmax, d);
-      }
-      for (int e = 0; e < 12; ++e)
-        if (e != best) l2 = fmin(l2, A(e, e));
-      good = l2 > INIT_REL_PIVOT * lmax;
-      double p[12];
-#pragma unroll
-      for (int e = 0; e < 12; ++e) p[e] = V(e, best);
-      good = resect_denormalise(p, nm, P) && good;
-    }
+    double p[12];
+    good = rs_lds_eig<12>(sA, sV, good, p);
+    if (good) good = resect_denormalise(p, nm, P);
   }
 #pragma unroll
   for (int e = 0; e < 12; ++e) hypP[oh * 12 + e] = good ? P[e] : NAN;
@@ -200,7 +152,8 @@ __global__ __launch_bounds__(START_CHUNK) void k_resect_score(int cam0, int H, c
   if (i < nh && s_cnt[i]) atomicAdd(&hyp_count[(size_t)kl * H + h0 + i], s_cnt[i]);
 }
 
-// Pcur[camera] = the matrix of the camera's best hypothesis (best < 0: NaN), for the cnt cameras of a tile
+// Pcur[camera] = the 12 doubles (a matrix; R and t of a pose) of the camera's best hypothesis (best < 0: NaN), for the cnt
+// cameras of a tile
 __global__ __launch_bounds__(256) void k_resect_gather(int cnt, int H, const int *__restrict__ best, const double *__restrict__ hypP,
                                                        double *__restrict__ Pcur) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -242,6 +195,265 @@ __global__ __launch_bounds__(START_CHUNK) void k_resect_scatter(const int *__res
   if (((st & RS_CUR) ? inl1 : inl0)[ch_mask[c] + i]) out[cm_obs[ch_start[c] + i]] = 1;
 }
 
+// What a fit sees of robust_cameras: the call, the current tile's cameras and chunks, and the buffers every fit uses (dP: the
+// camera matrices that k_resect_mask scores, per listed camera).
+struct CamTile {
+  const CamWork &w;
+  int H;
+  unsigned long long seed;
+  int c0, cnt, ch0, tch;
+  dim3 gch, gc;  // one workgroup per chunk of the tile (at least one), one thread per camera
+  const int *tcam, *tcnt;
+  const long long *tstart, *tmask;
+  double *dpart, *dS, *dP, *dhypP;
+  int *dstate, *dhc;
+  unsigned char *dinl0, *dinl1;
+  // (a tile's sums: dS [cnt][nv], of the chunk partials at their global place in dpart)
+  void combine(int nv) const { hipLaunchKernelGGL(k_resect_combine, dim3((cnt * nv + 255) / 256), dim3(256), 0, 0, cnt, nv, w.dlc_ch + c0, dpart, dS); }
+};
+
+// The robust fit of the listed cameras, tile by tile: hypotheses scored as camera matrices by k_resect_score, the best by
+// rs_pick, its inlier mask, up to n_refit refits under the two-buffer mask and rs_accept, the scatter of the final mask, the
+// per-camera outputs and the four laps.  A Fit (ResectFit below; PoseFit, mvba_pose_ransac.h) supplies
+//   MIN_OBS, FIRST_MIN, NV (doubles per chunk partial), HYP_BYTES (device bytes per hypothesis of a camera of a tile),
+//   setup: its own buffers;  hypotheses: whatever fills dhypP and dhc of a tile;  score_n: the counts k_resect_score goes by;
+//   picked: after dP holds the best hypotheses;  fetch: after a mask, the model behind dP to the host (first: the kept one);
+//   refit: one refit's model of the active cameras into dP, rs_stop for those that fail;  keep: refit model -> kept model;
+//   output: the kept model of tile camera p to list position g, returns quality[g][1].
+// The caller has checked its arguments and set the fit's own outputs to NaN.
+template <class Fit>
+int robust_cameras(Fit &fit, const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
+                   int m, const uint8_t *point_ok, const double *K, const int32_t *cameras, int nl, double threshold, int H, uint64_t seed,
+                   int n_refit, double *quality, int64_t *n_usable, int64_t *n_inliers, int32_t *best, uint8_t *inlier, int32_t *hyp_count,
+                   int32_t *status, double *timings_ms, int32_t device) {
+  if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
+  const double thr2 = threshold * threshold;
+  // the defaults are those of a camera without usable observations: status 1
+  for (int c = 0; c < nl; ++c) {
+    if (quality) quality[2 * c] = quality[2 * c + 1] = NAN;
+    if (n_usable) n_usable[c] = 0;
+    if (n_inliers) n_inliers[c] = 0;
+    if (best) best[c] = -1;
+    if (status) status[c] = 1;
+  }
+  if (inlier && n_obs) std::memset(inlier, 0, (size_t)n_obs);
+  if (hyp_count) std::fill(hyp_count, hyp_count + (size_t)nl * H, -1);
+  if (nl == 0) return MVBA_OK;
+
+  InitClock clk;
+  ResectList list;
+  resect_build_list(X, n_points, pt_ptr, cam_idx, xy, m, point_ok, inlier != nullptr, list);
+  const long long n_used = list.cam_ptr[m];
+  CamWork w;
+  int rc;
+  if ((rc = w.build(list.cam_ptr.data(), cameras, nl, START_CHUNK, n_usable))) return rc;
+  const int n_ch = w.n_ch;
+  if (n_ch == 0) {
+    if (timings_ms) timings_ms[0] = clk.lap();
+    return MVBA_OK;
+  }
+
+  if (device >= 0) MVBA_HIP(hipSetDevice(device));
+  const int tile = tv_pair_tile(nl, Fit::HYP_BYTES * (size_t)H);
+  DevBufs tmp;
+  CamTile t{w, H, (unsigned long long)seed};
+  int *dbest = nullptr;
+  long long *dobs = nullptr;
+  unsigned char *dout = nullptr;
+  if ((rc = w.upload(tmp, list, X, n_points, K)) || (rc = tmp.alloc(&t.dpart, Fit::NV * (size_t)n_ch)) || (rc = tmp.alloc(&t.dS, Fit::NV * (size_t)tile)) ||
+      (rc = tmp.alloc(&t.dP, 12 * (size_t)nl)) || (rc = tmp.alloc(&t.dstate, (size_t)nl)) || (rc = tmp.alloc(&dbest, (size_t)tile)) ||
+      (rc = tmp.alloc(&t.dhc, (size_t)tile * H)) || (rc = tmp.alloc(&t.dhypP, 12 * (size_t)tile * H)) || (rc = tmp.alloc(&t.dinl0, (size_t)w.n_mask)) ||
+      (rc = tmp.alloc(&t.dinl1, (size_t)w.n_mask)) || (rc = fit.setup(tmp, w, tile, H)))
+    return rc;
+  if (inlier && ((rc = tmp.alloc(&dout, (size_t)n_obs)) || (rc = tmp.alloc(&dobs, (size_t)n_used)))) return rc;
+  if (inlier) {
+    MVBA_HIP(hipMemcpy(dobs, list.cm_obs.data(), sizeof(long long) * n_used, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemset(dout, 0, (size_t)n_obs));
+  }
+  RsLaps laps;
+  laps.upload = clk.lap();
+
+  const dim3 b256(256), bch(START_CHUNK);
+  const int hb = (H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK;
+  std::vector<int> hc((size_t)tile * H), bst((size_t)tile), state((size_t)nl, 0), st((size_t)tile);
+  std::vector<long long> nin((size_t)tile);
+  std::vector<double> S2(2 * (size_t)tile), ssq((size_t)tile);
+  for (int c0 = 0; c0 < nl; c0 += tile) {
+    const int cnt = std::min(tile, nl - c0), ch0 = w.lc_ch[c0], tch = w.lc_ch[c0 + cnt] - ch0;
+    t.c0 = c0; t.cnt = cnt; t.ch0 = ch0; t.tch = tch;
+    t.gch = dim3((unsigned)std::max(tch, 1)); t.gc = dim3((cnt + 255) / 256);
+    t.tcam = w.dch_cam + ch0; t.tcnt = w.dch_cnt + ch0; t.tstart = w.dch_start + ch0; t.tmask = w.dch_mask + ch0;
+    int *tstate = state.data() + c0;
+    auto put_state = [&]() -> int {
+      MVBA_HIP(hipMemcpy(t.dstate + c0, tstate, sizeof(int) * cnt, hipMemcpyHostToDevice));
+      return MVBA_OK;
+    };
+    // the inlier sets of dP under the cameras' states: counts and sums of d^2 into S2
+    auto mask = [&]() -> int {
+      int r = put_state();
+      if (r) return r;
+      if (tch > 0)
+        hipLaunchKernelGGL(k_resect_mask, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tmask, t.tcnt, w.dpt, w.dxy, w.dX, t.dstate, t.dP, thr2, t.dinl0, t.dinl1,
+                           t.dpart + 2 * (size_t)ch0);
+      t.combine(2);
+      MVBA_HIP(hipGetLastError());
+      MVBA_HIP(hipMemcpy(S2.data(), t.dS, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost));
+      return MVBA_OK;
+    };
+
+    fit.hypotheses(t);
+    if (tch > 0)
+      hipLaunchKernelGGL(k_resect_score, dim3((unsigned)tch, hb), bch, 0, 0, c0, H, t.tcam, t.tstart, t.tcnt, fit.score_n(w), w.dpt, w.dxy, w.dX, t.dhypP,
+                         thr2, t.dhc);
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipMemcpy(hc.data(), t.dhc, sizeof(int) * (size_t)cnt * H, hipMemcpyDeviceToHost));
+    laps.score += clk.lap();
+
+    for (int p = 0; p < cnt; ++p) {
+      const RsPick pick = rs_pick(hc.data() + (size_t)p * H, H, w.lc_n[c0 + p], Fit::MIN_OBS);
+      st[p] = pick.status;
+      bst[p] = pick.best;
+      tstate[p] = pick.state;
+    }
+    MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_resect_gather, dim3((cnt * 12 + 255) / 256), b256, 0, 0, cnt, H, dbest, t.dhypP, t.dP + 12 * (size_t)c0);
+    fit.picked(t, dbest);
+    if ((rc = mask()) || (rc = fit.fetch(t, true))) return rc;
+    int n_active = 0;
+    for (int p = 0; p < cnt; ++p) {
+      if (st[p]) continue;
+      tstate[p] ^= RS_CUR;
+      nin[p] = (long long)S2[2 * p];
+      ssq[p] = S2[2 * p + 1];
+      ++n_active;
+    }
+    laps.other += clk.lap();
+
+    for (int r = 0; r < n_refit && n_active > 0; ++r) {
+      if ((rc = put_state()) || (rc = fit.refit(t, tstate, n_active))) return rc;
+      if (n_active == 0) break;
+      if ((rc = mask()) || (rc = fit.fetch(t, false))) return rc;
+      for (int p = 0; p < cnt; ++p) {
+        if (!(tstate[p] & RS_ACTIVE)) continue;
+        const long long c = (long long)S2[2 * p];
+        if (!rs_accept(c, nin[p], r, Fit::FIRST_MIN, tstate[p], n_active)) continue;
+        nin[p] = c;
+        ssq[p] = S2[2 * p + 1];
+        fit.keep(p);
+      }
+    }
+    laps.refit += clk.lap();
+
+    if (inlier && tch > 0) {
+      if ((rc = put_state())) return rc;
+      hipLaunchKernelGGL(k_resect_scatter, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tmask, t.tcnt, dobs, t.dstate, t.dinl0, t.dinl1, dout);
+      MVBA_HIP(hipGetLastError());
+    }
+    for (int p = 0; p < cnt; ++p) {
+      const size_t g = (size_t)c0 + p;
+      if (status) status[g] = st[p];
+      if (best) best[g] = bst[p];
+      if (hyp_count) std::copy(hc.begin() + (size_t)p * H, hc.begin() + (size_t)(p + 1) * H, hyp_count + g * H);
+      if (st[p]) continue;
+      const double q1 = fit.output(p, g);
+      if (n_inliers) n_inliers[g] = nin[p];
+      if (quality) {
+        quality[2 * g] = sqrt(ssq[p] / (double)nin[p]);
+        quality[2 * g + 1] = q1;
+      }
+    }
+    laps.other += clk.lap();
+  }
+  if (inlier) MVBA_HIP(hipMemcpy(inlier, dout, (size_t)n_obs, hipMemcpyDeviceToHost));
+  laps.other += clk.lap();
+  laps.write(timings_ms);
+  return MVBA_OK;
+}
+
+// The DLT as a fit: the normalisation over all usable observations before the hypotheses, a refit by mvba_resect's three
+// passes under the mask and resect_solve_camera on the host.
+struct ResectFit {
+  static constexpr int MIN_OBS = RR_MIN_OBS, NV = 40;
+  static constexpr size_t HYP_BYTES = RR_HYP_BYTES;
+  // the first refit is kept if it has 6 inliers of its own (the minimal 6-point matrix is too ill-conditioned to hold the
+  // full fit to its count), a later one while its set does not shrink
+  static constexpr long long FIRST_MIN = RR_MIN_OBS;
+  double *P;  // [n_cameras][12], out
+  double *dnorm = nullptr, *dnorm2 = nullptr;
+  int hyp_lds = 0;
+  std::vector<double> S, norm, Pc, Pn, ratio, rt;
+
+  int setup(DevBufs &tmp, const CamWork &w, int tile, int) {
+    const size_t nl = w.cams.size();
+    int rc;
+    if ((rc = tmp.alloc(&dnorm, RS_NORM * nl)) || (rc = tmp.alloc(&dnorm2, RS_NORM * nl))) return rc;
+    hyp_lds = (int)(sizeof(double) * 2 * 144 * RS_HYP_BLOCK);
+    MVBA_HIP(hipFuncSetAttribute((const void *)k_resect_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, hyp_lds));
+    S.resize(40 * (size_t)tile); norm.resize(RS_NORM * (size_t)tile); Pc.resize(12 * (size_t)tile); Pn.resize(12 * (size_t)tile);
+    ratio.resize((size_t)tile); rt.resize((size_t)tile);
+    return MVBA_OK;
+  }
+  const int *score_n(const CamWork &w) const { return w.dlc_n; }
+  // normalisation over all usable observations (mvba_resect's passes 0 and 1), hypotheses
+  void hypotheses(const CamTile &t) {
+    const CamWork &w = t.w;
+    const dim3 b256(256), bch(START_CHUNK);
+    if (t.tch > 0) {
+      hipLaunchKernelGGL(k_resect_chunk<0>, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tcnt, w.dpt, w.dxy, w.dX, (const double *)nullptr, t.dpart + 6 * (size_t)t.ch0);
+      t.combine(6);
+      hipLaunchKernelGGL(k_resect_norm, t.gc, b256, 0, 0, t.cnt, 0, t.dS, dnorm + RS_NORM * (size_t)t.c0);
+      hipLaunchKernelGGL(k_resect_chunk<1>, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tcnt, w.dpt, w.dxy, w.dX, dnorm, t.dpart + 2 * (size_t)t.ch0);
+      t.combine(2);
+      hipLaunchKernelGGL(k_resect_norm, t.gc, b256, 0, 0, t.cnt, 1, t.dS, dnorm + RS_NORM * (size_t)t.c0);
+    }
+    hipLaunchKernelGGL(k_resect_hyp, dim3((t.H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, t.cnt), dim3(RS_HYP_BLOCK), hyp_lds, 0, t.c0, t.H, t.seed, w.dcams,
+                       w.dlc_start, w.dlc_n, w.dpt, w.dxy, w.dX, dnorm, t.dhypP, t.dhc);
+  }
+  void picked(const CamTile &, const int *) {}
+  int fetch(const CamTile &t, bool first) {
+    if (!first) return MVBA_OK;  // (a refit's matrices came from the host)
+    MVBA_HIP(hipMemcpy(Pc.data(), t.dP + 12 * (size_t)t.c0, sizeof(double) * 12 * t.cnt, hipMemcpyDeviceToHost));
+    std::fill(ratio.begin(), ratio.end(), 0.0);  // (no refit kept yet)
+    return MVBA_OK;
+  }
+  // mvba_resect's fit on the current inliers alone
+  int refit(const CamTile &t, int *tstate, int &n_active) {
+    const CamWork &w = t.w;
+    const dim3 b256(256), bch(START_CHUNK);
+    double *tn = dnorm2 + RS_NORM * (size_t)t.c0;
+    hipLaunchKernelGGL(k_resect_fit<0>, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tmask, t.tcnt, w.dpt, w.dxy, w.dX, t.dstate, t.dinl0, t.dinl1,
+                       (const double *)nullptr, t.dpart + 6 * (size_t)t.ch0);
+    t.combine(6);
+    hipLaunchKernelGGL(k_resect_norm, t.gc, b256, 0, 0, t.cnt, 0, t.dS, tn);
+    hipLaunchKernelGGL(k_resect_fit<1>, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tmask, t.tcnt, w.dpt, w.dxy, w.dX, t.dstate, t.dinl0, t.dinl1, dnorm2,
+                       t.dpart + 2 * (size_t)t.ch0);
+    t.combine(2);
+    hipLaunchKernelGGL(k_resect_norm, t.gc, b256, 0, 0, t.cnt, 1, t.dS, tn);
+    hipLaunchKernelGGL(k_resect_fit<2>, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tmask, t.tcnt, w.dpt, w.dxy, w.dX, t.dstate, t.dinl0, t.dinl1, dnorm2,
+                       t.dpart + 40 * (size_t)t.ch0);
+    t.combine(40);
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipMemcpy(S.data(), t.dS, sizeof(double) * 40 * t.cnt, hipMemcpyDeviceToHost));
+    MVBA_HIP(hipMemcpy(norm.data(), tn, sizeof(double) * RS_NORM * t.cnt, hipMemcpyDeviceToHost));
+    std::fill(rt.begin(), rt.end(), NAN);
+    for (int p = 0; p < t.cnt; ++p) {
+      for (int j = 0; j < 12; ++j) Pn[12 * (size_t)p + j] = NAN;
+      if (!(tstate[p] & RS_ACTIVE)) continue;
+      if (resect_solve_camera(S.data() + 40 * (size_t)p, norm.data() + RS_NORM * (size_t)p, Pn.data() + 12 * (size_t)p, &rt[p])) rs_stop(tstate[p], n_active);
+    }
+    if (n_active > 0) MVBA_HIP(hipMemcpy(t.dP + 12 * (size_t)t.c0, Pn.data(), sizeof(double) * 12 * t.cnt, hipMemcpyHostToDevice));
+    return MVBA_OK;
+  }
+  void keep(int p) {
+    ratio[p] = rt[p];
+    for (int j = 0; j < 12; ++j) Pc[12 * (size_t)p + j] = Pn[12 * (size_t)p + j];
+  }
+  double output(int p, size_t g) const {
+    for (int j = 0; j < 12; ++j) P[12 * g + j] = Pc[12 * (size_t)p + j];
+    return ratio[p];
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -264,251 +476,14 @@ int mvba_resect_robust(const double *X, int64_t n_points, const int64_t *pt_ptr,
   if (n_cameras < 0) return fail(MVBA_ERR_BADARG, "n_cameras = " + std::to_string(n_cameras) + " must be >= 0");
   if (!X || !xy || (n_cameras > 0 && !P))
     return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!X ? "X" : (!xy ? "xy" : "P")) + " (argument " + std::to_string(!X ? 1 : (!xy ? 5 : 15)) + ")");
-  if (!std::isfinite(threshold) || !(threshold > 0.0))
-    return fail(MVBA_ERR_BADARG, "threshold = " + std::to_string(threshold) + " must be finite and > 0");
-  if (n_hypotheses < 1 || n_hypotheses > RS_MAX_HYP)
-    return fail(MVBA_ERR_BADARG, "n_hypotheses = " + std::to_string(n_hypotheses) + " must be in 1 .. " + std::to_string(RS_MAX_HYP));
-  if (n_refit < 0 || n_refit > RS_MAX_REFIT)
-    return fail(MVBA_ERR_BADARG, "n_refit = " + std::to_string(n_refit) + " must be in 0 .. " + std::to_string(RS_MAX_REFIT));
-  int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
-  if (rc) return rc;
-  const int m = n_images;
-  if (!cameras && n_cameras != m)
-    return fail(MVBA_ERR_BADARG, "cameras = NULL lists every camera: n_cameras = " + std::to_string(n_cameras) + " must be n_images = " + std::to_string(m));
-  for (int32_t c = 0; cameras && c < n_cameras; ++c)
-    if (cameras[c] < 0 || cameras[c] >= m)
-      return fail(MVBA_ERR_BADARG, "cameras[" + std::to_string(c) + "] = " + std::to_string(cameras[c]) + ": camera index out of range, n_images = " + std::to_string(m));
-  if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
-  const int nl = n_cameras, H = n_hypotheses;
-  const double thr2 = threshold * threshold;
-  // the defaults are those of a camera without usable observations: status 1
-  for (int c = 0; c < nl; ++c) {
-    for (int j = 0; j < 12; ++j) P[12 * (size_t)c + j] = NAN;
-    if (quality) quality[2 * c] = quality[2 * c + 1] = NAN;
-    if (n_usable) n_usable[c] = 0;
-    if (n_inliers) n_inliers[c] = 0;
-    if (best) best[c] = -1;
-    if (status) status[c] = 1;
-  }
-  if (inlier && n_obs) std::memset(inlier, 0, (size_t)n_obs);
-  if (hyp_count) std::fill(hyp_count, hyp_count + (size_t)nl * H, -1);
-  if (nl == 0) return MVBA_OK;
-
-  InitClock clk;
-  ResectList list;
-  resect_build_list(X, n_points, pt_ptr, cam_idx, xy, m, point_ok, inlier != nullptr, list);
-  const long long n_used = list.cam_ptr[m];
-  // the listed cameras' runs and chunks; a listed camera's bytes in the mask buffers start at its lc_mask
-  std::vector<int> cams((size_t)nl), lc_n((size_t)nl), lc_ch((size_t)nl + 1, 0), ch_cam, ch_cnt;
-  std::vector<long long> lc_start((size_t)nl), ch_start, ch_mask;
-  long long n_mask = 0;
-  for (int c = 0; c < nl; ++c) {
-    const int k = cameras ? cameras[c] : c;
-    const long long n = list.cam_ptr[k + 1] - list.cam_ptr[k];
-    if (n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "camera " + std::to_string(k) + " has " + std::to_string(n) + " usable observations: must be < 2^31");
-    cams[c] = k;
-    lc_n[c] = (int)n;
-    lc_start[c] = list.cam_ptr[k];
-    if (n_usable) n_usable[c] = n;
-    for (long long s = 0; s < n; s += START_CHUNK) {
-      ch_cam.push_back(c);
-      ch_start.push_back(list.cam_ptr[k] + s);
-      ch_mask.push_back(n_mask + s);
-      ch_cnt.push_back((int)std::min<long long>(START_CHUNK, n - s));
-    }
-    n_mask += n;
-    if (ch_cam.size() > (size_t)0x7fffffff) return fail(MVBA_ERR_BADARG, "too many chunks of 256 observations over the listed cameras");
-    lc_ch[c + 1] = (int)ch_cam.size();
-  }
-  const int n_ch = (int)ch_cam.size();
-  if (n_ch == 0) {
-    if (timings_ms) timings_ms[0] = clk.lap();
-    return MVBA_OK;
-  }
-
-  if (device >= 0) MVBA_HIP(hipSetDevice(device));
-  const int tile = tv_pair_tile(nl, RR_HYP_BYTES * (size_t)H);
-  DevBufs tmp;
-  double *dX = nullptr, *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dnorm2 = nullptr, *dP = nullptr, *dhypP = nullptr;
-  double2 *dxy = nullptr;
-  int *dpt = nullptr, *dcams = nullptr, *dlc_n = nullptr, *dlc_ch = nullptr, *dch_cam = nullptr, *dch_cnt = nullptr, *dstate = nullptr,
-      *dbest = nullptr, *dhc = nullptr;
-  long long *dlc_start = nullptr, *dch_start = nullptr, *dch_mask = nullptr, *dobs = nullptr;
-  unsigned char *dinl0 = nullptr, *dinl1 = nullptr, *dout = nullptr;
-  if ((rc = tmp.alloc(&dX, 3 * (size_t)n_points)) || (rc = tmp.alloc(&dxy, (size_t)n_used)) || (rc = tmp.alloc(&dpt, (size_t)n_used)) ||
-      (rc = tmp.alloc(&dcams, (size_t)nl)) || (rc = tmp.alloc(&dlc_n, (size_t)nl)) || (rc = tmp.alloc(&dlc_start, (size_t)nl)) ||
-      (rc = tmp.alloc(&dlc_ch, (size_t)nl + 1)) || (rc = tmp.alloc(&dch_cam, (size_t)n_ch)) || (rc = tmp.alloc(&dch_cnt, (size_t)n_ch)) ||
-      (rc = tmp.alloc(&dch_start, (size_t)n_ch)) || (rc = tmp.alloc(&dch_mask, (size_t)n_ch)) || (rc = tmp.alloc(&dpart, 40 * (size_t)n_ch)) ||
-      (rc = tmp.alloc(&dS, 40 * (size_t)tile)) || (rc = tmp.alloc(&dnorm, RS_NORM * (size_t)nl)) || (rc = tmp.alloc(&dnorm2, RS_NORM * (size_t)nl)) ||
-      (rc = tmp.alloc(&dP, 12 * (size_t)nl)) || (rc = tmp.alloc(&dstate, (size_t)nl)) || (rc = tmp.alloc(&dbest, (size_t)tile)) ||
-      (rc = tmp.alloc(&dhc, (size_t)tile * H)) || (rc = tmp.alloc(&dhypP, 12 * (size_t)tile * H)) || (rc = tmp.alloc(&dinl0, (size_t)n_mask)) ||
-      (rc = tmp.alloc(&dinl1, (size_t)n_mask)))
+  int rc;
+  if ((rc = rs_check_search(threshold, n_hypotheses)) || (rc = rs_check_refit(n_refit)) ||
+      (rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs)) || (rc = check_camera_list(cameras, n_cameras, n_images)))
     return rc;
-  if (inlier && ((rc = tmp.alloc(&dout, (size_t)n_obs)) || (rc = tmp.alloc(&dobs, (size_t)n_used)))) return rc;
-  MVBA_HIP(hipMemcpy(dX, X, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dxy, list.cm_xy.data(), sizeof(double2) * n_used, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dpt, list.cm_pt.data(), sizeof(int) * n_used, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dcams, cams.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dlc_n, lc_n.data(), sizeof(int) * nl, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dlc_start, lc_start.data(), sizeof(long long) * nl, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dlc_ch, lc_ch.data(), sizeof(int) * (nl + 1), hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dch_cam, ch_cam.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dch_cnt, ch_cnt.data(), sizeof(int) * n_ch, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dch_start, ch_start.data(), sizeof(long long) * n_ch, hipMemcpyHostToDevice));
-  MVBA_HIP(hipMemcpy(dch_mask, ch_mask.data(), sizeof(long long) * n_ch, hipMemcpyHostToDevice));
-  if (inlier) {
-    MVBA_HIP(hipMemcpy(dobs, list.cm_obs.data(), sizeof(long long) * n_used, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemset(dout, 0, (size_t)n_obs));
-  }
-  const int hyp_lds = (int)(sizeof(double) * 2 * 144 * RS_HYP_BLOCK);
-  MVBA_HIP(hipFuncSetAttribute((const void *)k_resect_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, hyp_lds));
-  double t_up = clk.lap(), t_score = 0.0, t_refit = 0.0, t_rest = 0.0;
-
-  const dim3 b256(256), bch(START_CHUNK);
-  const int hb = (H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK;
-  std::vector<int> hc((size_t)tile * H), bst((size_t)tile), state((size_t)nl, 0), st((size_t)tile);
-  std::vector<long long> nin((size_t)tile);
-  std::vector<double> S(40 * (size_t)tile), norm(RS_NORM * (size_t)tile), Pc(12 * (size_t)tile), Pn(12 * (size_t)tile), S2(2 * (size_t)tile),
-      ssq((size_t)tile), ratio((size_t)tile), rt((size_t)tile);
-  for (int c0 = 0; c0 < nl; c0 += tile) {
-    const int cnt = std::min(tile, nl - c0), ch0 = lc_ch[c0], tch = lc_ch[c0 + cnt] - ch0;
-    const dim3 gch((unsigned)std::max(tch, 1)), gc((cnt + 255) / 256);
-    const int *tcam = dch_cam + ch0, *tcnt = dch_cnt + ch0;
-    const long long *tstart = dch_start + ch0, *tmask = dch_mask + ch0;
-    int *tstate = state.data() + c0;
-    // (a tile's sums: dS [cnt][nv], of the chunk partials at their global place in dpart)
-    auto combine = [&](int nv) { hipLaunchKernelGGL(k_resect_combine, dim3((cnt * nv + 255) / 256), b256, 0, 0, cnt, nv, dlc_ch + c0, dpart, dS); };
-    auto put_state = [&]() -> int {
-      MVBA_HIP(hipMemcpy(dstate + c0, tstate, sizeof(int) * cnt, hipMemcpyHostToDevice));
-      return MVBA_OK;
-    };
-    // the inlier sets of dP under the cameras' states: counts and sums of d^2 into S2
-    auto mask = [&]() -> int {
-      int r = put_state();
-      if (r) return r;
-      if (tch > 0) hipLaunchKernelGGL(k_resect_mask, gch, bch, 0, 0, tcam, tstart, tmask, tcnt, dpt, dxy, dX, dstate, dP, thr2, dinl0, dinl1, dpart + 2 * (size_t)ch0);
-      combine(2);
-      MVBA_HIP(hipGetLastError());
-      MVBA_HIP(hipMemcpy(S2.data(), dS, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost));
-      return MVBA_OK;
-    };
-
-    // normalisation over all usable observations (mvba_resect's passes 0 and 1), hypotheses, scores
-    if (tch > 0) {
-      hipLaunchKernelGGL(k_resect_chunk<0>, gch, bch, 0, 0, tcam, tstart, tcnt, dpt, dxy, dX, (const double *)nullptr, dpart + 6 * (size_t)ch0);
-      combine(6);
-      hipLaunchKernelGGL(k_resect_norm, gc, b256, 0, 0, cnt, 0, dS, dnorm + RS_NORM * (size_t)c0);
-      hipLaunchKernelGGL(k_resect_chunk<1>, gch, bch, 0, 0, tcam, tstart, tcnt, dpt, dxy, dX, dnorm, dpart + 2 * (size_t)ch0);
-      combine(2);
-      hipLaunchKernelGGL(k_resect_norm, gc, b256, 0, 0, cnt, 1, dS, dnorm + RS_NORM * (size_t)c0);
-    }
-    hipLaunchKernelGGL(k_resect_hyp, dim3(hb, cnt), dim3(RS_HYP_BLOCK), hyp_lds, 0, c0, H, (unsigned long long)seed, dcams, dlc_start, dlc_n, dpt, dxy,
-                       dX, dnorm, dhypP, dhc);
-    if (tch > 0)
-      hipLaunchKernelGGL(k_resect_score, dim3((unsigned)tch, hb), bch, 0, 0, c0, H, tcam, tstart, tcnt, dlc_n, dpt, dxy, dX, dhypP, thr2, dhc);
-    MVBA_HIP(hipGetLastError());
-    MVBA_HIP(hipMemcpy(hc.data(), dhc, sizeof(int) * (size_t)cnt * H, hipMemcpyDeviceToHost));
-    t_score += clk.lap();
-
-    // arg-max on the host: the largest count, the lowest h on ties
-    for (int p = 0; p < cnt; ++p) {
-      const int *c = hc.data() + (size_t)p * H;
-      int b = 0;
-      for (int h = 1; h < H; ++h)
-        if (c[h] > c[b]) b = h;
-      st[p] = lc_n[c0 + p] < RR_MIN_OBS ? 1 : (c[b] < 0 ? 2 : (c[b] < RR_MIN_OBS ? 4 : 0));
-      bst[p] = c[b] < 0 ? -1 : b;  // (status 1 and 2: every count is -1)
-      tstate[p] = st[p] == 0 ? (RS_OK | RS_ACTIVE | RS_CUR) : 0;  // (the first mask goes into buffer 0)
-    }
-    MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_resect_gather, dim3((cnt * 12 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhypP, dP + 12 * (size_t)c0);
-    if ((rc = mask())) return rc;
-    MVBA_HIP(hipMemcpy(Pc.data(), dP + 12 * (size_t)c0, sizeof(double) * 12 * cnt, hipMemcpyDeviceToHost));
-    int n_active = 0;
-    for (int p = 0; p < cnt; ++p) {
-      if (st[p]) continue;
-      tstate[p] ^= RS_CUR;
-      nin[p] = (long long)S2[2 * p];
-      ssq[p] = S2[2 * p + 1];
-      ratio[p] = 0.0;  // (no refit kept yet)
-      ++n_active;
-    }
-    t_rest += clk.lap();
-
-    // refits: mvba_resect's fit on the current inliers alone.  The first is kept if it has 6 inliers of its own (the minimal
-    // 6-point matrix is too ill-conditioned to hold the full fit to its count), a later one while its set does not shrink
-    for (int r = 0; r < n_refit && n_active > 0; ++r) {
-      if ((rc = put_state())) return rc;
-      double *tn = dnorm2 + RS_NORM * (size_t)c0;
-      hipLaunchKernelGGL(k_resect_fit<0>, gch, bch, 0, 0, tcam, tstart, tmask, tcnt, dpt, dxy, dX, dstate, dinl0, dinl1, (const double *)nullptr, dpart + 6 * (size_t)ch0);
-      combine(6);
-      hipLaunchKernelGGL(k_resect_norm, gc, b256, 0, 0, cnt, 0, dS, tn);
-      hipLaunchKernelGGL(k_resect_fit<1>, gch, bch, 0, 0, tcam, tstart, tmask, tcnt, dpt, dxy, dX, dstate, dinl0, dinl1, dnorm2, dpart + 2 * (size_t)ch0);
-      combine(2);
-      hipLaunchKernelGGL(k_resect_norm, gc, b256, 0, 0, cnt, 1, dS, tn);
-      hipLaunchKernelGGL(k_resect_fit<2>, gch, bch, 0, 0, tcam, tstart, tmask, tcnt, dpt, dxy, dX, dstate, dinl0, dinl1, dnorm2, dpart + 40 * (size_t)ch0);
-      combine(40);
-      MVBA_HIP(hipGetLastError());
-      MVBA_HIP(hipMemcpy(S.data(), dS, sizeof(double) * 40 * cnt, hipMemcpyDeviceToHost));
-      MVBA_HIP(hipMemcpy(norm.data(), tn, sizeof(double) * RS_NORM * cnt, hipMemcpyDeviceToHost));
-      std::fill(rt.begin(), rt.end(), NAN);
-      for (int p = 0; p < cnt; ++p) {
-        for (int j = 0; j < 12; ++j) Pn[12 * (size_t)p + j] = NAN;
-        if (!(tstate[p] & RS_ACTIVE)) continue;
-        if (resect_solve_camera(S.data() + 40 * (size_t)p, norm.data() + RS_NORM * (size_t)p, Pn.data() + 12 * (size_t)p, &rt[p])) {
-          tstate[p] &= ~RS_ACTIVE;
-          --n_active;
-        }
-      }
-      if (n_active == 0) break;
-      MVBA_HIP(hipMemcpy(dP + 12 * (size_t)c0, Pn.data(), sizeof(double) * 12 * cnt, hipMemcpyHostToDevice));
-      if ((rc = mask())) return rc;
-      for (int p = 0; p < cnt; ++p) {
-        if (!(tstate[p] & RS_ACTIVE)) continue;
-        const long long c = (long long)S2[2 * p];
-        if (c >= (r == 0 ? (long long)RR_MIN_OBS : nin[p])) {
-          tstate[p] ^= RS_CUR;
-          nin[p] = c;
-          ssq[p] = S2[2 * p + 1];
-          ratio[p] = rt[p];
-          for (int j = 0; j < 12; ++j) Pc[12 * (size_t)p + j] = Pn[12 * (size_t)p + j];
-        } else {
-          tstate[p] &= ~RS_ACTIVE;
-          --n_active;
-        }
-      }
-    }
-    t_refit += clk.lap();
-
-    if (inlier && tch > 0) {
-      if ((rc = put_state())) return rc;
-      hipLaunchKernelGGL(k_resect_scatter, gch, bch, 0, 0, tcam, tstart, tmask, tcnt, dobs, dstate, dinl0, dinl1, dout);
-      MVBA_HIP(hipGetLastError());
-    }
-    for (int p = 0; p < cnt; ++p) {
-      const size_t g = (size_t)c0 + p;
-      if (status) status[g] = st[p];
-      if (best) best[g] = bst[p];
-      if (hyp_count) std::copy(hc.begin() + (size_t)p * H, hc.begin() + (size_t)(p + 1) * H, hyp_count + g * H);
-      if (st[p]) continue;
-      for (int j = 0; j < 12; ++j) P[12 * g + j] = Pc[12 * (size_t)p + j];
-      if (n_inliers) n_inliers[g] = nin[p];
-      if (quality) {
-        quality[2 * g] = sqrt(ssq[p] / (double)nin[p]);
-        quality[2 * g + 1] = ratio[p];
-      }
-    }
-    t_rest += clk.lap();
-  }
-  if (inlier) MVBA_HIP(hipMemcpy(inlier, dout, (size_t)n_obs, hipMemcpyDeviceToHost));
-  t_rest += clk.lap();
-  if (timings_ms) {
-    timings_ms[0] = t_up;
-    timings_ms[1] = t_score;
-    timings_ms[2] = t_refit;
-    timings_ms[3] = t_rest;
-  }
-  return MVBA_OK;
+  std::fill(P, P + 12 * (size_t)n_cameras, NAN);
+  ResectFit fit{P};
+  return robust_cameras(fit, X, n_points, pt_ptr, cam_idx, xy, n_obs, n_images, point_ok, nullptr, cameras, n_cameras, threshold, n_hypotheses, seed,
+                        n_refit, quality, n_usable, n_inliers, best, inlier, hyp_count, status, timings_ms, device);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Robust triangulation (mvba_triangulate_robust, mvba_triangulate_sample): per-point two-view RANSAC -- kernels and host code,
 // gfx950.
 //
-// Included by mvba.hip after mvba_resect_ransac.h: uses its rr_inlier, mvba_ransac.h's rs_sample and RS_MAX_REFIT, mvba_init.h's
+// Included by mvba.hip after mvba_resect_ransac.h: uses its rr_inlier, mvba_ransac.h's rs_sample, mvba_ransac_host.h's argument checks, mvba_init.h's
 // init_camera_matrix, InitObsMasked and init_triangulate_point, mvba_start.h's checks, upload_list, InitClock, EvGuard and
 // INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
 //
@@ -234,16 +234,10 @@ int mvba_triangulate_robust(const double *K, const double *R, const double *t, i
   if (!K || !R || !t || !xy || !X)
     return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!K ? "K" : (!R ? "R" : (!t ? "t" : (!xy ? "xy" : "X")))) + " (argument " +
                                      std::to_string(!K ? 1 : (!R ? 2 : (!t ? 3 : (!xy ? 8 : 15)))) + ")");
-  if (!std::isfinite(threshold) || !(threshold > 0.0))
-    return fail(MVBA_ERR_BADARG, "threshold = " + std::to_string(threshold) + " must be finite and > 0");
-  if (n_hypotheses < 1 || n_hypotheses > TR_MAX_HYP)
-    return fail(MVBA_ERR_BADARG, "n_hypotheses = " + std::to_string(n_hypotheses) + " must be in 1 .. " + std::to_string(TR_MAX_HYP));
+  int rc;
+  if ((rc = rs_check_search(threshold, n_hypotheses, TR_MAX_HYP))) return rc;
   if (n_refine < 0) return fail(MVBA_ERR_BADARG, "n_refine = " + std::to_string(n_refine) + " must be >= 0");
-  if (n_refit < 0 || n_refit > RS_MAX_REFIT)
-    return fail(MVBA_ERR_BADARG, "n_refit = " + std::to_string(n_refit) + " must be in 0 .. " + std::to_string(RS_MAX_REFIT));
-  int rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs);
-  if (rc) return rc;
-  if ((rc = init_check_cameras(n_images))) return rc;
+  if ((rc = rs_check_refit(n_refit)) || (rc = init_check_list(n_points, n_images, pt_ptr, cam_idx, n_obs)) || (rc = init_check_cameras(n_images))) return rc;
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
   if (n_points == 0) return MVBA_OK;
   if (device >= 0) MVBA_HIP(hipSetDevice(device));

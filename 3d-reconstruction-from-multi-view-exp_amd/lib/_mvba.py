@@ -545,6 +545,39 @@ def two_view(pt_ptr, cam_idx, xy, n_images, pairs, device=-1):
     return F, q, ns, st, _timings3(tm)
 
 
+def _robust_outputs(model, n_items, count_key, n_hypotheses, inlier_shape, return_counts):
+    """What the three ``*_robust`` calls share: the output arrays from ``quality`` on and the dict they come back in.  Returns
+    ``(tail, result)``: the C arguments quality, ``count_key`` (n_shared / n_usable), n_inliers, best, inlier, hyp_count, status,
+    timings_ms, and a function that builds the result from ``model`` (the call's own arrays) once the call has returned."""
+    i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    q, tm = np.empty((max(n_items, 0), 2)), np.zeros(4)
+    cnt, ni, best, st = np.empty(n_items, np.int64), np.empty(n_items, np.int64), np.empty(n_items, np.int32), np.empty(n_items, np.int32)
+    inl = None if inlier_shape is None else np.empty(inlier_shape, np.uint8)
+    hc = np.empty((n_items, max(n_hypotheses, 0)), np.int32) if return_counts else None
+    tail = (_ptr(q), cnt.ctypes.data_as(i64), ni.ctypes.data_as(i64), best.ctypes.data_as(i32),
+            None if inl is None else inl.ctypes.data_as(C.POINTER(C.c_uint8)), None if hc is None else hc.ctypes.data_as(i32),
+            st.ctypes.data_as(i32), _ptr(tm))
+
+    def result():
+        out = {**model, "quality": q, count_key: cnt, "n_inliers": ni, "best": best, "status": st,
+               "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
+        if inl is not None:
+            out["inlier"] = inl.astype(bool)
+        if hc is not None:
+            out["hyp_count"] = hc
+        return out
+
+    return tail, result
+
+
+def _sample(name, n_idx, seed, *index):
+    """The ``n_idx`` indices a ``*_sample`` entry point writes for ``seed`` (taken modulo 2^64) and its integer arguments."""
+    lib = load_library()
+    idx = np.empty(n_idx, np.int64)
+    raise_for(getattr(lib, name)(int(seed) & 0xFFFFFFFFFFFFFFFF, *(int(v) for v in index), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
+    return idx
+
+
 def two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=512, seed=0, n_refit=2, return_inliers=True,
                     return_counts=False, device=-1):
     """Fundamental matrices by 8-point RANSAC on the device (mvba_two_view_robust).  The list and ``pairs`` as for ``two_view``;
@@ -559,32 +592,17 @@ def two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypothese
     pairs = _as(pairs, np.int32).reshape(-1, 2)
     n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
     P, H = pairs.shape[0], int(n_hypotheses)
-    i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-    F, q, tm = np.empty((P, 3, 3)), np.empty((P, 2)), np.zeros(4)
-    ns, ni, best, st = np.empty(P, np.int64), np.empty(P, np.int64), np.empty(P, np.int32), np.empty(P, np.int32)
-    inl = np.empty((P, n), np.uint8) if return_inliers else None
-    hc = np.empty((P, max(H, 0)), np.int32) if return_counts else None
-    raise_for(lib.mvba_two_view_robust(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(i32), P, float(threshold), H,
-                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(F), _ptr(q), ns.ctypes.data_as(i64),
-                                       ni.ctypes.data_as(i64), best.ctypes.data_as(i32),
-                                       inl.ctypes.data_as(C.POINTER(C.c_uint8)) if return_inliers else None,
-                                       hc.ctypes.data_as(i32) if return_counts else None, st.ctypes.data_as(i32), _ptr(tm), int(device)), lib)
-    out = {"F": F, "quality": q, "n_shared": ns, "n_inliers": ni, "best": best, "status": st,
-           "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
-    if return_inliers:
-        out["inlier"] = inl.astype(bool)
-    if return_counts:
-        out["hyp_count"] = hc
-    return out
+    F = np.empty((P, 3, 3))
+    tail, result = _robust_outputs({"F": F}, P, "n_shared", H, (P, n) if return_inliers else None, return_counts)
+    raise_for(lib.mvba_two_view_robust(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, float(threshold), H,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(F), *tail, int(device)), lib)
+    return result()
 
 
 def ransac_sample(seed, k, l, h, n):
     """The 8 distinct indices below ``n`` that hypothesis ``h`` of pair (k, l) draws (mvba_ransac_sample: the host instance of
     the function the kernel runs; no GPU needed)."""
-    lib = load_library()
-    idx = np.empty(8, np.int64)
-    raise_for(lib.mvba_ransac_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(l), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
-    return idx
+    return _sample("mvba_ransac_sample", 8, seed, k, l, h, n)
 
 
 def resect_robust(X, pt_ptr, cam_idx, xy, n_images, threshold, point_ok=None, cameras=None, n_hypotheses=512, seed=0, n_refit=2,
@@ -602,39 +620,24 @@ def resect_robust(X, pt_ptr, cam_idx, xy, n_images, threshold, point_ok=None, ca
     n, m = X.shape[0], int(n_images)
     assert X.shape == (n, 3)
     _, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m, n)
-    i32, i64, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
     okp = None
     if point_ok is not None:
         ok = _as(np.asarray(point_ok) != 0, np.uint8)
         assert ok.shape == (n,)
-        okp = ok.ctypes.data_as(u8)
+        okp = ok.ctypes.data_as(C.POINTER(C.c_uint8))
     cams = None if cameras is None else _as(cameras, np.int32).reshape(-1)
     nc, H = m if cams is None else cams.shape[0], int(n_hypotheses)
-    P, q, tm = np.empty((max(nc, 0), 3, 4)), np.empty((max(nc, 0), 2)), np.zeros(4)
-    nu, ni, best, st = np.empty(nc, np.int64), np.empty(nc, np.int64), np.empty(nc, np.int32), np.empty(nc, np.int32)
-    inl = np.empty(n_obs, np.uint8) if return_inliers else None
-    hc = np.empty((nc, max(H, 0)), np.int32) if return_counts else None
-    raise_for(lib.mvba_resect_robust(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, None if cams is None else cams.ctypes.data_as(i32), nc,
-                                     float(threshold), H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(P), _ptr(q),
-                                     nu.ctypes.data_as(i64), ni.ctypes.data_as(i64), best.ctypes.data_as(i32),
-                                     inl.ctypes.data_as(u8) if return_inliers else None, hc.ctypes.data_as(i32) if return_counts else None,
-                                     st.ctypes.data_as(i32), _ptr(tm), int(device)), lib)
-    out = {"P": P, "quality": q, "n_usable": nu, "n_inliers": ni, "best": best, "status": st,
-           "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
-    if return_inliers:
-        out["inlier"] = inl.astype(bool)
-    if return_counts:
-        out["hyp_count"] = hc
-    return out
+    P = np.empty((max(nc, 0), 3, 4))
+    tail, result = _robust_outputs({"P": P}, nc, "n_usable", H, n_obs if return_inliers else None, return_counts)
+    raise_for(lib.mvba_resect_robust(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, None if cams is None else cams.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     nc, float(threshold), H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(P), *tail, int(device)), lib)
+    return result()
 
 
 def resect_sample(seed, k, h, n):
     """The 6 distinct indices below ``n`` that hypothesis ``h`` of camera ``k`` draws (mvba_resect_sample: the host instance of
     the function the kernel runs; no GPU needed)."""
-    lib = load_library()
-    idx = np.empty(6, np.int64)
-    raise_for(lib.mvba_resect_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
-    return idx
+    return _sample("mvba_resect_sample", 6, seed, k, h, n)
 
 
 def _pose_args(X, pt_ptr, cam_idx, xy, K, point_ok, cameras):
@@ -666,24 +669,12 @@ def pose_robust(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=None, cameras=Non
     lib = load_library()
     _require_device("mvba_pose_robust")
     keep, n, n_obs, m, pp, cp, xy, okp, K, camp, nc = _pose_args(X, pt_ptr, cam_idx, xy, K, point_ok, cameras)
-    i32, i64, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
     H = int(n_hypotheses)
-    R, t, q, tm = np.empty((nc, 3, 3)), np.empty((nc, 3)), np.empty((nc, 2)), np.zeros(4)
-    nu, ni, best, st = np.empty(nc, np.int64), np.empty(nc, np.int64), np.empty(nc, np.int32), np.empty(nc, np.int32)
-    inl = np.empty(n_obs, np.uint8) if return_inliers else None
-    hc = np.empty((nc, max(H, 0)), np.int32) if return_counts else None
+    R, t = np.empty((nc, 3, 3)), np.empty((nc, 3))
+    tail, result = _robust_outputs({"R": R, "t": t}, nc, "n_usable", H, n_obs if return_inliers else None, return_counts)
     raise_for(lib.mvba_pose_robust(_ptr(keep[0]), n, pp, cp, _ptr(xy), n_obs, m, okp, _ptr(K), camp, nc, float(threshold), H,
-                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refine), int(n_refit), _ptr(R), _ptr(t), _ptr(q),
-                                   nu.ctypes.data_as(i64), ni.ctypes.data_as(i64), best.ctypes.data_as(i32),
-                                   inl.ctypes.data_as(u8) if return_inliers else None, hc.ctypes.data_as(i32) if return_counts else None,
-                                   st.ctypes.data_as(i32), _ptr(tm), int(device)), lib)
-    out = {"R": R, "t": t, "quality": q, "n_usable": nu, "n_inliers": ni, "best": best, "status": st,
-           "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
-    if return_inliers:
-        out["inlier"] = inl.astype(bool)
-    if return_counts:
-        out["hyp_count"] = hc
-    return out
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refine), int(n_refit), _ptr(R), _ptr(t), *tail, int(device)), lib)
+    return result()
 
 
 def pose_refine(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=None, obs_ok=None, cameras=None, n_steps=10, device=-1):
@@ -712,10 +703,7 @@ def pose_refine(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=None, obs_ok=None, cam
 def pose_sample(seed, k, h, n):
     """The 4 distinct indices below ``n`` that hypothesis ``h`` of camera ``k`` draws (mvba_pose_sample: the host instance of
     the function the kernel runs; no GPU needed)."""
-    lib = load_library()
-    idx = np.empty(4, np.int64)
-    raise_for(lib.mvba_pose_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
-    return idx
+    return _sample("mvba_pose_sample", 4, seed, k, h, n)
 
 
 def triangulate_robust(K, R, t, pt_ptr, cam_idx, xy, threshold, n_hypotheses=64, seed=0, n_refine=2, n_refit=2, return_counts=False,
@@ -751,11 +739,7 @@ def triangulate_sample(seed, point, h, deg, n_hypotheses=64):
     """The two observation numbers (i < j, below ``deg``) of hypothesis ``h`` of point ``point``, or (-1, -1) where the
     exhaustive table has no entry ``h`` (mvba_triangulate_sample: the host instance of the function the kernel runs; no GPU
     needed)."""
-    lib = load_library()
-    idx = np.empty(2, np.int64)
-    raise_for(lib.mvba_triangulate_sample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(point), int(h), int(deg), int(n_hypotheses),
-                                          idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
-    return idx
+    return _sample("mvba_triangulate_sample", 2, seed, point, h, deg, n_hypotheses)
 
 
 def host_obs_math(X3, cam15, xy2, f0):

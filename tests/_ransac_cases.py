@@ -99,7 +99,7 @@ def status_cases():
 LIMITS = {"scan257": (64, 1, THRESHOLD, 16), "refits_1.5e-3": (100, 1, 1.5e-3, 16), "refits_3e-3": (100, 1, 3e-3, 16),
           "mixed": (64, 1, THRESHOLD, 2), "mixed65": (64, 1, THRESHOLD, 2), "partly_degenerate": (64, 1, THRESHOLD, 2)}
 SCAN_POINTS = 65_700  # 257 chunks of 256 points: k_ransac_scan gives a thread two chunks, thread 128 one, threads 129 .. 255 none
-MAX_HYP = 65536  # csrc/mvba_ransac.h: RS_MAX_HYP
+MAX_HYP = 65536  # csrc/mvba_ransac_host.h: RS_MAX_HYP
 REFIT_COUNTS = (0, 1, 2, 3, 16)  # the n_refit at which the "refits" cases run on the device
 
 

@@ -124,7 +124,7 @@ def refit_reference(n_refit, linear="eigh"):
     return QR.resect_robust(X, pt_ptr, cam, xy, m, REFIT_THRESHOLD, n_hyp=H, seed=seed, n_refit=n_refit, linear=linear)
 
 
-MAX_HYP = 65536  # csrc/mvba_ransac.h: RS_MAX_HYP
+MAX_HYP = 65536  # csrc/mvba_ransac_host.h: RS_MAX_HYP
 MAX_HYP_CAMERA = 0
 
 
