@@ -1,6 +1,7 @@
-"""Scenes shared by test_pose_ransac_cpu.py and test_gpu_pose_ransac.py, each built once: the shapes of tests/_init_cases.py with
-the contamination of tests/_resect_ransac_cases.py and the ground-truth intrinsics, and the host-versus-host figures (np.roots
-and the Cholesky step against the Ferrari factorisation and lstsq) that set the parity margins.  Test infrastructure only."""
+"""Scenes shared by test_pose_ransac_cpu.py, test_gpu_pose_ransac.py and test_gpu_pose_limits.py, each built once: the shapes
+of tests/_init_cases.py with the contamination of tests/_resect_ransac_cases.py and the ground-truth intrinsics, and the
+host-versus-host figures (np.roots and the Cholesky step against the Ferrari factorisation and lstsq) that set the parity
+margins.  Test infrastructure only."""
 import functools
 
 import numpy as np
@@ -193,3 +194,151 @@ def reference_bootstrap(roots="roots", solver="chol"):
     sc, xy, _ = QC.bootstrap_case()
     return PR.bootstrap(sc.pt_ptr, sc.cam_idx, xy, engine_intrinsics(sc.init_K), THRESHOLD, 512, 1, start_pair=(0, 1), max_rms=0.01, roots=roots,
                         solver=solver)
+
+
+# ---- The structural limits ("Structural limits"): test_gpu_pose_limits.py, premises in test_pose_ransac_cpu.py ----
+LIMIT_REFIT_COUNTS = (0, 1, 2, 3, 16)  # the n_refit at which the trace cases run on the device
+# name: (parity case that gives the scene, threshold, n_hypotheses, seed, n_refine, n_refit)
+LIMITS = {"refits_1.2e-3": ("5000x3", 1.2e-3, 100, 1, 5, 16), "refits_2.5e-3": ("5000x3", 2.5e-3, 100, 1, 5, 16),
+          "refits_3e-3": ("5000x3", 3e-3, 100, 1, 5, 16), "refine_0": ("5000x3", 2e-3, 100, 1, 0, 16), "refine_1": ("5000x3", 2e-3, 100, 1, 1, 16),
+          "refine_16": ("5000x3", 2e-3, 100, 1, 16, 16), "general_K": ("300x8", THRESHOLD, 512, 1, 5, 2)}
+TRACE_NAMES = tuple(n for n in LIMITS if n != "general_K")
+# the traces the issue lists, per camera (accepted, changed, end) at 16 refits
+LIMIT_TRACES = {"refits_1.2e-3": [(7, 7, "rejected"), (5, 5, "rejected"), (9, 9, "rejected")],
+                "refits_2.5e-3": [(16, 4, "exhausted"), (3, 3, "rejected"), (16, 5, "exhausted")],
+                "refits_3e-3": [(16, 2, "exhausted"), (1, 1, "rejected"), (2, 2, "rejected")],
+                "refine_0": [(16, 0, "exhausted")] * 3,
+                "refine_1": [(3, 3, "rejected"), (16, 6, "exhausted"), (3, 3, "rejected")],
+                "refine_16": [(3, 3, "rejected")] * 3}
+# Host-versus-host figure of a limit case (the rule of POSE_HOST_DIFF), measured by test_pose_ransac_cpu.py.  A trace case is ONE
+# case, the same iteration cut at five places: its figure is the largest over the n_refit of LIMIT_REFIT_COUNTS with refits
+# (REFIT_TRACE_DIFF's rule); without refits every trace case returns the same unrefitted best hypotheses: LIMIT_REFIT0_DIFF.
+# ("refine_0" never moves a pose: its refits keep that figure.)
+LIMIT_HOST_DIFF = {"refits_1.2e-3": 2.1e-10, "refits_2.5e-3": 1.5e-10, "refits_3e-3": 1.2e-10, "refine_0": 9.8e-15, "refine_1": 2.3e-10,
+                   "refine_16": 8.8e-10, "general_K": 1.2e-9}
+LIMIT_REFIT0_DIFF = 9.8e-15
+# the smallest |d^2 / threshold^2 - 1| of a limit case over both routes and, for a trace case, over LIMIT_REFIT_COUNTS
+LIMIT_MARGIN = {"refits_1.2e-3": 2.2e-5, "refits_2.5e-3": 1.1e-5, "refits_3e-3": 9.0e-6, "refine_0": 1.1e-5, "refine_1": 1.1e-5, "refine_16": 1.1e-5,
+                "general_K": 1.0e-4}
+Q_AXIS, K_SCALE = (0.2, -0.15, 0.1), 2.5  # "general_K": K' = 2.5 K Rod(Q_AXIS), a full matrix with K'[2][2] != 1
+# "general_K" against "300x8" on the reference: max |t' - t| and max |R' - R Q| (K' R'^T = 2.5 K R^T: one camera matrix up to scale)
+GENERAL_K_T_DIFF, GENERAL_K_R_DIFF = 5.3e-10, 9.7e-11
+
+
+def general_K(K):
+    return K_SCALE * (np.asarray(K) @ PR.rodrigues(np.array(Q_AXIS)))
+
+
+@functools.lru_cache(maxsize=None)
+def limit_case(name):
+    """(X, pt_ptr, cam_idx, xy, K, threshold, n_hypotheses, seed, n_refine, n_refit) of a structural-limit case."""
+    scene, thr, H, seed, n_refine, n_refit = LIMITS[name]
+    X, pt_ptr, cam, xy, K = case(scene)[:5]
+    if name == "general_K":
+        K = general_K(K)
+        K.setflags(write=False)
+    return X, pt_ptr, cam, xy, K, thr, H, seed, n_refine, n_refit
+
+
+@functools.lru_cache(maxsize=None)
+def limit_reference(name, roots="roots", solver="chol", n_refit=None):
+    X, pt_ptr, cam, xy, K, thr, H, seed, n_refine, r = limit_case(name)
+    return PR.pose_robust(X, pt_ptr, cam, xy, K, thr, n_hyp=H, seed=seed, n_refine=n_refine, n_refit=r if n_refit is None else n_refit,
+                          roots=roots, solver=solver)
+
+
+def limit_margin(name, n_refit):
+    """The parity margin of a limit case at ``n_refit``."""
+    return MARGIN * (LIMIT_REFIT0_DIFF if n_refit == 0 and name in TRACE_NAMES else LIMIT_HOST_DIFF[name])
+
+
+# "tiles_edges": the "edges" shape (257 / 256 / 255 observations: 2, 1 and 1 chunks) listed over and over at 65 536 hypotheses, so
+# that the second tile starts at an entry whose chunk offset is not its list position
+TILE_HYP = 65536
+TILE_CAMERAS = (0, 1, 2) * 4
+CHUNK, list_chunks, tile_sums = QC.CHUNK, QC.list_chunks, QC.tile_sums
+
+
+# mvba_pose_refine at its limits: name -> n_steps of refine_case(); chol against lstsq (REFINE_HOST_DIFF's rule)
+REFINE_STEP_COUNTS = (1, 2, 64)
+REFINE_LIMIT_HOST_DIFF = {"steps_1": 5.7e-15, "steps_2": 8.9e-16, "steps_64": 2.9e-10, "general_K": 2.9e-10, "masks": 3.4e-11,
+                          "masks_point_ok": 2.6e-11, "empty": 2.9e-10}
+# ("statuses_a" / "statuses_b": exact data at the ground truth; neither route accepts a step, the figure is 0 and sets no margin)
+MASK_STEPS = 10
+POINT_DROP = 0.3
+MASK_USABLE = {"masks": [1875, 1854, 1869], "masks_point_ok": [1414, 1411, 1411]}
+STATUS_PIVOT_BOUND = 1e-14  # the failing relative pivots of "statuses_a" are below this or negative (the rule is 1e-12)
+# measured on the reference: the failing pivot of the 40 collinear points (three collinear points: the factorisation meets a
+# pivot that is not positive), and the smallest relative pivot of the camera with three observations (status 0)
+STATUS_FAIL_PIVOT, STATUS_MIN_PIVOT = 1.6e-15, 1.2e-3
+
+
+def _perturbed(sc, m):
+    """Ground-truth poses perturbed as in refine_case()."""
+    rng = np.random.default_rng(5)
+    t0 = sc.t_gt + rng.normal(0.0, REFINE_PERTURBATION, sc.t_gt.shape)
+    R0 = np.stack([PR.rodrigues(w) for w in rng.normal(0.0, REFINE_PERTURBATION, (m, 3))]) @ sc.R_gt
+    return R0, t0
+
+
+def chunk_pattern(n, seed=11):
+    """(n,) bool over a camera's run: its 256-chunks cycle all / none / the last lane alone / a seeded half."""
+    kind, lane = (np.arange(n) // CHUNK) % 4, np.arange(n) % CHUNK
+    return (kind == 0) | ((kind == 2) & (lane == CHUNK - 1)) | ((kind == 3) & (np.random.default_rng(seed).random(n) < 0.5))
+
+
+@functools.lru_cache(maxsize=None)
+def refine_limit_case(name):
+    """(X, pt_ptr, cam_idx, xy, K, R0, t0, point_ok, obs_ok, n_steps) of a pose_refine limit case:
+    "steps_<n>": refine_case() at n_steps = n;  "general_K": refine_case() under K' = general_K(K), R0' = R0 Q;
+    "masks": the clean "5000x3" list, obs_ok by chunk_pattern over each camera's run (20 chunks, the last of 136);
+    "masks_point_ok": the same with a seeded 30 % of the points dropped by point_ok as well;
+    "statuses_a" / "statuses_b": 80 points x 3 cameras without noise, the first 40 on one line, ground-truth poses; obs_ok
+    leaves camera 0 everything, camera 1 the 40 collinear points / three points off the line, camera 2 three collinear / two points;
+    "empty": refine_case() re-indexed into 11 cameras with 1, 4 and 10 unobserved (identity K and pose there)."""
+    if name.startswith("steps_"):
+        return refine_case() + (None, None, int(name[6:]))
+    if name == "general_K":
+        X, pt_ptr, cam, xy, K, R0, t0 = refine_case()
+        return X, pt_ptr, cam, xy, general_K(K), R0 @ PR.rodrigues(np.array(Q_AXIS)), t0, None, None, REFINE_STEPS
+    if name in ("masks", "masks_point_ok"):
+        K, sc = true_K("5000x3")
+        R0, t0 = _perturbed(sc, 3)
+        pt = np.repeat(np.arange(sc.n_points), np.diff(sc.pt_ptr))
+        ok = None if name == "masks" else np.random.default_rng(13).random(sc.n_points) >= POINT_DROP
+        obs_ok = np.zeros(len(sc.cam_idx), bool)
+        for k in range(3):  # a camera's run: its usable observations in ascending point order
+            run = np.nonzero((sc.cam_idx == k) & (True if ok is None else ok[pt]))[0]
+            obs_ok[run] = chunk_pattern(len(run), 11 + k)
+        return sc.X_gt, sc.pt_ptr, sc.cam_idx, sc.xy, K, R0, t0, ok, obs_ok, MASK_STEPS
+    if name in ("statuses_a", "statuses_b"):
+        K, sc = true_K("coplanar")
+        X = sc.X_gt.copy()
+        X[:40] = sc.X_gt[0] + np.linspace(-1.0, 1.0, 40)[:, None] * np.array([0.3, 0.5, 0.2])
+        pt = np.repeat(np.arange(80), np.diff(sc.pt_ptr))
+        keep = {"statuses_a": (range(80), range(40), (3, 17, 31)), "statuses_b": (range(80), (40, 41, 42), (40, 41))}[name]
+        obs_ok = np.zeros(len(pt), bool)
+        for k in range(3):
+            obs_ok |= (sc.cam_idx == k) & np.isin(pt, list(keep[k]))
+        return X, sc.pt_ptr, sc.cam_idx, IC.exact_xy(sc, X), K, sc.R_gt, sc.t_gt, None, obs_ok, REFINE_STEPS
+    if name == "empty":
+        X, pt_ptr, cam, xy, m, kept = IC.empty_camera_case()
+        _, _, _, _, K8, R8, t8 = refine_case()
+        K, R0, t0 = np.tile(np.eye(3), (m, 1, 1)), np.tile(np.eye(3), (m, 1, 1)), np.zeros((m, 3))
+        K[kept], R0[kept], t0[kept] = K8, R8, t8
+        return X, pt_ptr, cam, xy, K, R0, t0, None, None, REFINE_STEPS
+    raise KeyError(name)
+
+
+REFINE_LIMIT_NAMES = ("steps_1", "steps_2", "steps_64", "general_K", "masks", "masks_point_ok", "statuses_a", "statuses_b", "empty")
+STATUS_WANT = {"statuses_a": [0, 2, 2], "statuses_b": [0, 0, 1]}
+
+
+@functools.lru_cache(maxsize=None)
+def refine_limit_reference(name, solver="chol"):
+    """(R, t, quality, n_usable, status, records) of the reference on a pose_refine limit case."""
+    X, pt_ptr, cam, xy, K, R0, t0, ok, obs_ok, n_steps = refine_limit_case(name)
+    out = PR.pose_refine(X, pt_ptr, cam, xy, K, R0, t0, point_ok=ok, obs_ok=obs_ok, n_steps=n_steps, solver=solver, trace=True)
+    for a in out[:5]:
+        a.setflags(write=False)
+    return out

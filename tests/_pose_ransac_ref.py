@@ -191,8 +191,9 @@ def pass_sums(K, R, t, Xk, xk):
 
 def gauss_newton(K, R, t, Xk, xk, n_steps, solver="chol"):
     """The iteration of k_pose_step: (R, t, record) with record = cost0, cost, steps, pivot, fail (the step whose normal matrix
-    failed the pivot rule, -1: none; 0 also for an input that is not finite)."""
-    rec = {"cost0": np.nan, "cost": np.nan, "steps": 0, "pivot": 0.0, "fail": -1}
+    failed the pivot rule, -1: none; 0 also for an input that is not finite) and fail_pivot (the smallest relative pivot of
+    that matrix; -1 where the factorisation met a pivot that is not positive)."""
+    rec = {"cost0": np.nan, "cost": np.nan, "steps": 0, "pivot": 0.0, "fail": -1, "fail_pivot": np.nan}
     with np.errstate(all="ignore"):
         cost, J, e = pass_sums(K, R, t, Xk, xk)
         rec["cost0"] = rec["cost"] = cost
@@ -209,7 +210,7 @@ def gauss_newton(K, R, t, Xk, xk, n_steps, solver="chol"):
             except np.linalg.LinAlgError:
                 piv = np.array([-1.0])
             if not (piv > ref.REL_PIVOT * dmax).all():
-                rec["fail"] = j
+                rec["fail"], rec["fail_pivot"] = j, float((piv / dmax).min())
                 break
             rec["pivot"] = float((piv / dmax).min())
             if solver == "chol":
@@ -304,8 +305,9 @@ def pose_robust(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=None, cameras=Non
     return out
 
 
-def pose_refine(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=None, obs_ok=None, cameras=None, n_steps=10, solver="chol"):
-    """(R, t, quality (C, 3), n_usable, status) of mvba_pose_refine."""
+def pose_refine(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=None, obs_ok=None, cameras=None, n_steps=10, solver="chol", trace=False):
+    """(R, t, quality (C, 3), n_usable, status) of mvba_pose_refine; with ``trace`` also the list of gauss_newton's records
+    (None for a camera of status 1)."""
     K = np.asarray(K, np.float64)
     m = len(K)
     X, cam_idx, xy, ok, pt = _usable(X, pt_ptr, cam_idx, xy, m, point_ok)
@@ -313,17 +315,19 @@ def pose_refine(X, pt_ptr, cam_idx, xy, K, R, t, point_ok=None, obs_ok=None, cam
     cameras = np.arange(m) if cameras is None else np.asarray(cameras)
     R, t = np.array(R, np.float64).reshape(-1, 3, 3), np.array(t, np.float64).reshape(-1, 3)
     q, nu, st = np.full((len(cameras), 3), np.nan), np.zeros(len(cameras), np.int64), np.ones(len(cameras), np.int32)
+    recs = [None] * len(cameras)
     for c, k in enumerate(cameras):
         obs = np.nonzero((cam_idx == k) & use)[0]
         nu[c] = len(obs)
         if len(obs) < MIN_REFINE_OBS:
             continue
         Rn, tn, rec = gauss_newton(K[k], R[c], t[c], X[pt[obs]], xy[obs], n_steps, solver)
+        recs[c] = rec
         st[c] = 2 if rec["fail"] == 0 else 0
         if st[c] == 0:
             R[c], t[c] = Rn, tn
             q[c] = np.sqrt(rec["cost0"] / len(obs)), np.sqrt(rec["cost"] / len(obs)), rec["steps"]
-    return R, t, q, nu, st
+    return (R, t, q, nu, st, recs) if trace else (R, t, q, nu, st)
 
 
 def bootstrap(pt_ptr, cam_idx, xy, K, pose_threshold, n_hyp=512, seed=0, start_pair=None, min_points=12, max_rms=None, roots="roots",

@@ -153,6 +153,38 @@ def camera_tile(n_cameras, n_hyp):
     return max(1, min(n_cameras, MAX_TILE, TV_PART_BYTES // (RR_HYP_BYTES * n_hyp)))
 
 
+# "tiles_edges" (DESIGN.md 18): the "edges" shape (257 / 256 / 255 observations: 2, 1 and 1 chunks) listed 7 times at 65 536
+# hypotheses -- 21 entries for a tile of 20, and the second tile starts at an entry whose chunk offset (27) is not its list
+# position (20).  The device test is tests/test_gpu_pose_limits.py::test_two_tiles_of_the_dlt.
+TILE_HYP = 65536
+TILE_CAMERAS = (0, 1, 2) * 7
+CHUNK = 256  # csrc/mvba_start.h: START_CHUNK
+
+
+def list_chunks(cameras, n_usable):
+    """lc_ch (len(cameras) + 1,) of CamChunks::build: the first chunk of each listed entry; n_usable is per camera of the scene."""
+    return np.concatenate([[0], np.cumsum([-(-int(n_usable[k]) // CHUNK) for k in cameras])])
+
+
+def tile_sums(cameras, n_usable, masks, tile, offset="chunk"):
+    """n_inliers per list entry as the tile loop gets them: k_resect_mask writes a (count) partial per chunk of the tile into ONE
+    buffer that the call keeps, from the tile's offset on, and k_resect_combine adds the entry's chunks lc_ch[c] .. lc_ch[c + 1]
+    of that buffer.  ``masks[k]`` is camera k's final mask; ``offset`` = "chunk" is the code as written (the tile's chunks start
+    at lc_ch[c0]), "camera" the deliberately wrong one (at c0) that test_pose_ransac_cpu.py shows the case to tell apart."""
+    lc = list_chunks(cameras, n_usable)
+    part, out = np.zeros(lc[-1] + len(cameras), np.int64), np.zeros(len(cameras), np.int64)
+    for c0 in range(0, len(cameras), tile):
+        c1 = min(c0 + tile, len(cameras))
+        at = lc[c0] if offset == "chunk" else c0
+        for c in range(c0, c1):
+            m = masks[cameras[c]]
+            for j in range(lc[c + 1] - lc[c]):
+                part[at + (lc[c] - lc[c0]) + j] = m[CHUNK * j: CHUNK * (j + 1)].sum()
+        for c in range(c0, c1):
+            out[c] = part[lc[c]: lc[c + 1]].sum()
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def bootstrap_case(frac=BOOT_FRACTION):
     """"300x8" with ``frac`` of the observations of cameras 2 .. 7 replaced by uniform positions: (scene, xy', replaced)."""

@@ -1,7 +1,8 @@
 """Calibrated robust resection, the part that needs no GPU: the sample generator libmvba.so exports is the
 reference's and the first 4 draws of the two-view one, the argument checks, the premises under which the GPU parity tests may
-ask for EXACT count tables (margins, fragile hypotheses), what the reference recovers, and the host-versus-host figures that
-tests/_pose_ransac_cases.py records."""
+ask for EXACT count tables (margins, fragile hypotheses), what the reference recovers, the host-versus-host figures that
+tests/_pose_ransac_cases.py records, and -- from _limit_premises on -- the premises of the structural-limit cases of
+tests/test_gpu_pose_limits.py, with what a deliberately wrong implementation would return on three of them."""
 import ctypes
 import os
 
@@ -254,3 +255,252 @@ def test_bootstrap_reference_on_contaminated_tracks():
     assert all(0.9 * r <= x <= r for x, r in zip(e, PC.BOOT_POSE_ERR))
     assert max(e) <= QC.BOOT_FACTOR * max(e_clean) and e[0] < e_clean[0]
     assert not (ia["inlier"] & hit).any() and not (ia["inlier"] & ~ia["obs_ok"]).any() and (hit & ~ia["obs_ok"]).sum() > 100
+
+
+# ---- the structural limits ("Structural limits"): premises of tests/test_gpu_pose_limits.py ----
+def _limit_premises(a, b, what):
+    """_premises without the bracket of the margin: returns the smallest |d^2 / thr^2 - 1| of the two routes."""
+    fr = PC.fragile(a, b)
+    for key in ("status", "best", "n_inliers", "inlier", "n_usable", "sizes", "end", "n_accepted", "n_changed"):
+        np.testing.assert_array_equal(a[key], b[key], err_msg=f"{what}: {key}")
+    assert fr.sum() <= PC.FRAGILE_CAP * fr.size
+    has = a["best"] >= 0
+    assert not fr[np.nonzero(has)[0], a["best"][has]].any()
+    return min(a["margin"].min(), b["margin"].min()), int(fr.sum())
+
+
+def _rt_difference(a, b):
+    assert (a["status"] == 0).all() and (b["status"] == 0).all()
+    return max(np.abs(a["R"] - b["R"]).max(), np.abs(a["t"] - b["t"]).max()), np.abs(a["quality"][:, 0] - b["quality"][:, 0]).max()
+
+
+@pytest.mark.parametrize("name", sorted(PC.LIMITS))
+def test_limit_premises_and_host_versus_host_difference(name):
+    """Both routes give one table of integers at every n_refit the device runs, the smallest premise (b) and the case's host figure
+    (a trace case: the largest over its n_refit with refits) are what tests/_pose_ransac_cases.py records."""
+    counts = PC.LIMIT_REFIT_COUNTS if name in PC.TRACE_NAMES else (PC.LIMITS[name][5],)
+    margin, worst = np.inf, 0.0
+    for r in counts:
+        a, b = PC.limit_reference(name, n_refit=r), PC.other(PC.limit_reference, name, n_refit=r)
+        m, n_fragile = _limit_premises(a, b, f"{name}, n_refit = {r}")
+        d, dq = _rt_difference(a, b)
+        print(f"{name}, n_refit = {r}: smallest |d^2 / thr^2 - 1| {m:.3e}, fragile {n_fragile}, host |d(R, t)| {d:.3e}, RMS {dq:.3e}")
+        margin = min(margin, m)
+        assert dq <= PC.limit_margin(name, r)
+        if r == 0:
+            assert 0.5 * PC.LIMIT_REFIT0_DIFF <= d <= PC.LIMIT_REFIT0_DIFF
+            np.testing.assert_array_equal(a["n_inliers"], a["hyp_count"].max(axis=1))
+        else:
+            worst = max(worst, d)
+    rec_m, rec_d = PC.LIMIT_MARGIN[name], PC.LIMIT_HOST_DIFF[name]
+    print(f"{name}: smallest premise (b) {margin:.3e} (recorded {rec_m:.1e}), host figure {worst:.3e} (recorded {rec_d:.1e})")
+    assert rec_m <= margin <= 1.25 * rec_m and rec_m >= 1e-7
+    assert 0.5 * rec_d <= worst <= rec_d
+
+
+def test_limit_refit_traces():
+    """The traces of "5000x3" at 16 refits that the device cases are built for: cameras of one tile that leave the loop at
+    different refits; a fixed point kept for all 16 refits with the set unchanged; a kept refit that leaves the set as it is and is
+    followed by a rejection; refits without a step (n_refine = 0), with one, with 16."""
+    for name in PC.TRACE_NAMES:
+        a = PC.limit_reference(name)
+        got = [(int(n), int(c), str(e)) for n, c, e in zip(a["n_accepted"], a["n_changed"], a["end"])]
+        assert got == PC.LIMIT_TRACES[name], (name, got)
+    a = PC.limit_reference("refits_1.2e-3")
+    assert len(set(a["n_accepted"].tolist())) == 3 and (a["n_accepted"] == a["n_changed"]).all()
+    a = PC.limit_reference("refits_2.5e-3")
+    assert a["sizes"][0, 4:].tolist() == [2915] * 13 and a["sizes"][0, 2:4].tolist() == [2914, 2914]
+    assert a["sizes"][1, :5].tolist() == [2587, 2846, 2854, 2854, 2853]
+    a = PC.limit_reference("refits_3e-3")
+    assert a["sizes"][2, :5].tolist() == [2762, 2932, 2932, 2931, -1] and a["sizes"][0, 2:].tolist() == [3007] * 15
+    # n_refine = 0: every refit is kept, none moves the pose or the set, no pivot is recorded
+    a, a0 = PC.limit_reference("refine_0"), PC.limit_reference("refine_0", n_refit=0)
+    assert a["R"].tobytes() == a0["R"].tobytes() and a["t"].tobytes() == a0["t"].tobytes() and (a["quality"][:, 1] == 0).all()
+    assert (a["sizes"] == a["sizes"][:, :1]).all() and np.array_equal(a["inlier"], a0["inlier"])
+    for name in ("refine_1", "refine_16"):  # (the hypotheses do not depend on n_refine)
+        np.testing.assert_array_equal(PC.limit_reference(name)["hyp_count"], a["hyp_count"])
+        assert (PC.limit_reference(name)["quality"][:, 1] > 1e-3).all()
+
+
+def _refit_loop(name, k, accept=">=", read="current"):
+    """A copy of the refit loop of _pose_ransac_ref.robust_pose_camera from the reference's best hypothesis of camera k on, with
+    the two mask buffers of the device written out and two places open to a deliberate alteration: the accept rule (">=": kept
+    while the set does not shrink) and the buffer the final mask is read from ("current"; "other": the one the last refit
+    wrote, right only if that refit was kept).  Returns (n_inliers, mask)."""
+    X, pt_ptr, cam, xy, K, thr, H, seed, n_refine, n_refit = PC.limit_case(name)
+    pt = np.repeat(np.arange(len(X)), np.diff(pt_ptr))
+    obs = np.nonzero(cam == k)[0]
+    Xk, xk = X[pt[obs]], np.asarray(xy)[obs]
+    idx = PR.sample(seed, k, int(PC.limit_reference(name)["best"][k]), len(Xk))[None]
+    Rh, th, Ph, _ = PR.hypotheses(K[k], Xk[idx], xk[idx])
+    d2, depth = QR.reprojection(Ph[0], Xk, xk)
+    buf, cur, R, t = [(depth > 0) & (d2 <= thr * thr), None], 0, Rh[0], th[0]
+    for _ in range(n_refit):
+        Rr, tr, rec = PR.gauss_newton(K[k], R, t, Xk[buf[cur]], xk[buf[cur]], n_refine)
+        assert rec["fail"] < 0
+        d2, depth = QR.reprojection(PR.camera_matrix(K[k], Rr, tr), Xk, xk)
+        buf[cur ^ 1] = (depth > 0) & (d2 <= thr * thr)
+        kept = buf[cur ^ 1].sum() >= buf[cur].sum() if accept == ">=" else buf[cur ^ 1].sum() > buf[cur].sum()
+        if not kept:
+            break
+        R, t, cur = Rr, tr, cur ^ 1
+    mask = buf[cur] if read == "current" else buf[cur ^ 1]
+    return int(mask.sum()), mask
+
+
+def test_the_2_5e_3_trace_tells_a_wrong_refit_loop_from_a_right_one():
+    """The copy as written reproduces the reference; with ">" for ">=" camera 0 stops at the first kept refit that leaves the
+    count as it is (2914, not 2915); with the final mask read from the buffer the rejected refit wrote, camera 1 returns the
+    rejected set (2853, not 2854).  Either changes n_inliers and the inlier bytes the device is asked for exactly."""
+    name = "refits_2.5e-3"
+    a, cam = PC.limit_reference(name), PC.limit_case(name)[2]
+    for k in range(3):
+        n, mask = _refit_loop(name, k)
+        assert n == a["n_inliers"][k] and np.array_equal(mask, a["inlier"][cam == k])
+    n, mask = _refit_loop(name, 0, accept=">")
+    assert n == 2914 != a["n_inliers"][0] and not np.array_equal(mask, a["inlier"][cam == 0])
+    n, mask = _refit_loop(name, 1, read="other")
+    assert n == 2853 != a["n_inliers"][1] and not np.array_equal(mask, a["inlier"][cam == 1])
+    assert _refit_loop(name, 1, accept=">")[0] == a["n_inliers"][1]  # (camera 1 alone would not tell the two rules apart)
+
+
+def test_tiles_edges_premises_and_what_a_wrong_chunk_offset_would_return():
+    """Four times the "edges" list at 65 536 hypotheses: two tiles, the second from entry 10 on, whose first chunk is 14.  A tile
+    loop that put the second tile's chunk partials at the camera offset (10) would hand entries 10 and 11 other sums: the expected
+    n_inliers change, so the case tells the two apart."""
+    cams, H = list(PC.TILE_CAMERAS), PC.TILE_HYP
+    a = PC.reference("edges_h65")
+    tile, lc = PC.camera_tile(len(cams), H), PC.list_chunks(cams, a["n_usable"])
+    assert tile == 10 and len(cams) == 12 and lc[10] == 14 != 10 and lc[-1] == 16 and a["n_usable"].tolist() == [257, 256, 255]
+    cam = PC.case("edges_h65")[2]
+    masks = [a["inlier"][cam == k] for k in range(3)]
+    want = a["n_inliers"][cams]
+    np.testing.assert_array_equal(PC.tile_sums(cams, a["n_usable"], masks, tile), want)
+    wrong = PC.tile_sums(cams, a["n_usable"], masks, tile, offset="camera")
+    assert (wrong[:10] == want[:10]).all() and (wrong[10:] != want[10:]).all()
+    np.testing.assert_array_equal(PC.tile_sums(cams, a["n_usable"], masks, 12, offset="camera"), want)  # (one tile: nothing to tell)
+    # the existing two-tile case has one chunk per entry: the wrong offset returns the right sums there
+    b, c8 = PC.reference("300x8"), PC.case("300x8")[2]
+    m8 = [b["inlier"][c8 == k] for k in range(8)]
+    np.testing.assert_array_equal(PC.tile_sums([5] * 11, b["n_usable"], m8, 10, offset="camera"), b["n_inliers"][[5] * 11])
+
+
+def test_general_K_is_the_plain_case_turned():
+    """K' = 2.5 K Q: the camera matrices K' R'^T = 2.5 K R^T are those of "300x8" up to scale, so every integer is, t is, and
+    R' = R Q -- within the host figure of the case."""
+    a, p = PC.reference("300x8"), PC.limit_reference("general_K")
+    K = PC.limit_case("general_K")[4]
+    assert (np.abs(K) > 1e-3).all() and (np.abs(K[:, 2, 2] - 1.0) > 0.1).all() and (p["status"] == 0).all()
+    firm = ~PC.fragile(a, PC.other(PC.reference, "300x8")) & ~PC.fragile(p, PC.other(PC.limit_reference, "general_K"))
+    np.testing.assert_array_equal(a["hyp_count"][firm], p["hyp_count"][firm])
+    for key in ("n_inliers", "best", "inlier", "n_usable", "sizes"):
+        np.testing.assert_array_equal(a[key], p[key], err_msg=key)
+    Q = PR.rodrigues(np.array(PC.Q_AXIS))
+    dt, dR = np.abs(a["t"] - p["t"]).max(), np.abs(a["R"] @ Q - p["R"]).max()
+    print(f"general_K: |t' - t| {dt:.3e} (recorded {PC.GENERAL_K_T_DIFF:.1e}), |R' - R Q| {dR:.3e} (recorded {PC.GENERAL_K_R_DIFF:.1e})")
+    assert 0.5 * PC.GENERAL_K_T_DIFF <= dt <= PC.GENERAL_K_T_DIFF <= PC.LIMIT_HOST_DIFF["general_K"]
+    assert 0.5 * PC.GENERAL_K_R_DIFF <= dR <= PC.GENERAL_K_R_DIFF <= PC.LIMIT_HOST_DIFF["general_K"]
+    np.testing.assert_allclose(PR.camera_matrix(K, p["R"], p["t"]), PC.K_SCALE * PR.camera_matrix(PC.case("300x8")[4], a["R"], a["t"]),
+                               rtol=0, atol=50 * PC.LIMIT_HOST_DIFF["general_K"])  # (|K'| <= 5, |t| <= 10)
+
+
+def _refine_difference(name):
+    A, B = PC.refine_limit_reference(name), PC.refine_limit_reference(name, "lstsq")
+    np.testing.assert_array_equal(A[4], B[4])
+    np.testing.assert_array_equal(A[3], B[3])
+    ok = A[4] == 0
+    d = max(np.abs(A[0][ok] - B[0][ok]).max(), np.abs(A[1][ok] - B[1][ok]).max())
+    print(f"refine {name}: chol vs lstsq {d:.3e}, steps {A[2][:, 2].tolist()} / {B[2][:, 2].tolist()}")
+    return A, B, d
+
+
+@pytest.mark.parametrize("name", sorted(PC.REFINE_LIMIT_HOST_DIFF))
+def test_refine_limit_host_versus_host_difference(name):
+    A, B, d = _refine_difference(name)
+    rec = PC.REFINE_LIMIT_HOST_DIFF[name]
+    assert 0.5 * rec <= d <= rec
+    ok = A[4] == 0
+    assert np.abs(A[2][ok, :2] - B[2][ok, :2]).max() <= PC.MARGIN * rec and (A[2][ok, 1] <= A[2][ok, 0]).all()
+
+
+def test_refine_step_count_premises():
+    """n_steps = 1 and 2: both routes take exactly 1 and 2 steps with every camera -- the last permitted step is accepted -- and
+    still lower the cost; at 64 the iteration ends by its own rule after 3 .. 6 steps."""
+    for n in (1, 2):
+        for solver in ("chol", "lstsq"):
+            q = PC.refine_limit_reference(f"steps_{n}", solver)[2]
+            assert (q[:, 2] == n).all() and (q[:, 1] < q[:, 0]).all()
+    q1, q2 = PC.refine_limit_reference("steps_1")[2], PC.refine_limit_reference("steps_2")[2]
+    assert (q2[:, 1] < q1[:, 1]).all()
+    for solver in ("chol", "lstsq"):
+        q = PC.refine_limit_reference("steps_64", solver)[2]
+        assert (q[:, 2] >= 3).all() and (q[:, 2] <= 6).all()
+    assert PC.refine_limit_reference("steps_64")[2][:, 2].tolist() == [4, 5, 3, 3, 3, 3, 4, 3]
+
+
+def test_refine_mask_premises_and_what_a_wrong_mask_index_would_return():
+    """obs_ok by chunk of each camera's run: 20 chunks per camera cycling all / none / lane 255 alone / a seeded half, the last
+    of 136 observations; with point_ok the runs shrink to about 3500 and both masks act together.  An implementation that read
+    the byte at the observation's place in the sorted run instead of its place in the caller's list would use other
+    observations: n_usable changes, so the case tells the two apart."""
+    for name in ("masks", "masks_point_ok"):
+        X, pt_ptr, cam, xy, K, R0, t0, ok, obs_ok, n_steps = PC.refine_limit_case(name)
+        pt = np.repeat(np.arange(len(X)), np.diff(pt_ptr))
+        usable = np.ones(len(cam), bool) if ok is None else ok[pt]
+        for k in range(3):
+            run = np.nonzero((cam == k) & usable)[0]
+            per = [int(obs_ok[run[i: i + 256]].sum()) for i in range(0, len(run), 256)]
+            if name == "masks":
+                assert len(run) == 5000 and len(per) == 20 and len(run) - 19 * 256 == 136
+            else:
+                assert 3400 < len(run) < 3600 and len(per) == 14 and not obs_ok[(cam == k) & ~usable].any()
+            assert per[0::4] == [256] * len(per[0::4]) and per[1::4] == [0] * len(per[1::4]) and per[2::4] == [1] * len(per[2::4])
+            assert all(obs_ok[run[i + 255]] for i in range(512, len(run) - 255, 1024)) and all(0.35 * 256 < c < 0.65 * 256 for c in per[3::4][:-1])
+            if name == "masks":  # the last chunk is partial and of the fourth kind (with point_ok it is of the second: nothing)
+                assert 0 < per[-1] < 136
+        A = PC.refine_limit_reference(name)
+        assert A[3].tolist() == PC.MASK_USABLE[name] == [int((obs_ok & usable & (cam == k)).sum()) for k in range(3)] and (A[4] == 0).all()
+        order = np.argsort(cam, kind="stable")  # the sorted list: camera-major, ascending points
+        wrong = np.zeros(len(cam), bool)
+        wrong[order] = obs_ok  # the observation at sorted position i gets the byte of the caller's position i
+        W = PR.pose_refine(X, pt_ptr, cam, xy, K, R0, t0, point_ok=ok, obs_ok=wrong, n_steps=n_steps)
+        assert (W[3] != A[3]).all(), (W[3], A[3])
+
+
+def test_refine_status_premises():
+    """Exact data at the ground truth.  Call a: everything (status 0), the 40 collinear points (the first normal matrix fails
+    the pivot rule: status 2), three collinear points (status 2).  Call b: three points off the line (status 0 at the minimum),
+    two points (status 1).  The failing pivots are below 1e-14 or negative, the passing one of the minimum far above 1e-12."""
+    for solver in ("chol", "lstsq"):
+        A, B = PC.refine_limit_reference("statuses_a", solver), PC.refine_limit_reference("statuses_b", solver)
+        assert A[4].tolist() == PC.STATUS_WANT["statuses_a"] and A[3].tolist() == [80, 40, 3]
+        assert B[4].tolist() == PC.STATUS_WANT["statuses_b"] and B[3].tolist() == [80, 3, 2] and B[5][2] is None
+        fp = [A[5][k]["fail_pivot"] for k in (1, 2)]
+        print(f"statuses ({solver}): failing relative pivots {fp[0]:.3e}, {fp[1]:.3e}; the three-observation camera's smallest {B[5][1]['pivot']:.3e}")
+        assert all(A[5][k]["fail"] == 0 for k in (1, 2)) and A[5][0]["fail"] == B[5][0]["fail"] == B[5][1]["fail"] == -1
+        assert 0 < fp[0] < PC.STATUS_PIVOT_BOUND and 0.5 * PC.STATUS_FAIL_PIVOT <= fp[0] <= PC.STATUS_FAIL_PIVOT and fp[1] < 0
+        assert 0.9 * PC.STATUS_MIN_PIVOT <= B[5][1]["pivot"] <= 1.1 * PC.STATUS_MIN_PIVOT
+        R0, t0 = PC.refine_limit_case("statuses_a")[5:7]
+        for out in (A, B):  # a camera of status != 0 keeps its pose, NaN quality
+            bad = out[4] != 0
+            assert out[0][bad].tobytes() == np.ascontiguousarray(R0[bad]).tobytes() and np.isnan(out[2][bad]).all() and np.isfinite(out[2][~bad]).all()
+    X = PC.refine_limit_case("statuses_a")[0]
+    assert np.linalg.matrix_rank(X[:40] - X[0], tol=1e-12) == 1 and np.linalg.matrix_rank(X[40:43] - X[40], tol=1e-6) == 2
+    A = PC.refine_limit_reference("empty")
+    assert A[4].tolist() == [0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 1] and (A[3][[1, 4, 10]] == 0).all()
+    full = PC.refine_reference()
+    assert A[0][A[4] == 0].tobytes() == full[0].tobytes() and A[1][A[4] == 0].tobytes() == full[1].tobytes()
+
+
+def test_guards_that_no_case_reaches():
+    """A pivot failure at a later step (PG_FAIL = j > 0) and a solver failure inside a pose refit (end == "solver") are reached by
+    no case of this file, on either route; none was built."""
+    for solver in ("chol", "lstsq"):
+        for name in PC.REFINE_LIMIT_NAMES:
+            assert all(r is None or r["fail"] <= 0 for r in PC.refine_limit_reference(name, solver)[5]), name
+    ends = []
+    for name in PC.LIMITS:
+        for r in (PC.LIMIT_REFIT_COUNTS if name in PC.TRACE_NAMES else (2,)):
+            ends += [PC.limit_reference(name, n_refit=r)["end"], PC.other(PC.limit_reference, name, n_refit=r)["end"]]
+    ends += [PC.reference(name)["end"] for name in PC.PARITY] + [PC.refit_reference(r)["end"] for r in PC.REFIT_COUNTS]
+    assert not (np.concatenate(ends) == "solver").any()

@@ -215,3 +215,19 @@ def test_bootstrap_reference_on_contaminated_tracks():
     assert not (ia["inlier"] & hit).any() and not (ia["inlier"] & ~ia["obs_ok"]).any() and (hit & ~ia["obs_ok"]).sum() > 100
     plain = QC.plain_bootstrap(True)
     assert plain[3]["camera_ok"].sum() == 4 and max(QC.pose_error(sc, plain[0], plain[1], plain[3]["camera_ok"])) > 1.0
+
+
+def test_tiles_edges_premises_and_what_a_wrong_chunk_offset_would_return():
+    """The DLT tile case of tests/test_gpu_pose_limits.py: seven times the "edges" list at 65 536 hypotheses is 21
+    entries for a tile of 20, and entry 20 starts at chunk 27.  A tile loop that put the second tile's chunk partials at the camera
+    offset would hand entry 20 another sum: the expected n_inliers changes."""
+    cams, H = list(QC.TILE_CAMERAS), QC.TILE_HYP
+    a = QC.reference("edges_h65")
+    tile, lc = QC.camera_tile(len(cams), H), QC.list_chunks(cams, a["n_usable"])
+    assert tile == 20 and len(cams) == 21 and lc[20] == 27 != 20 and lc[-1] == 28 and (a["status"] == 0).all()
+    cam = QC.case("edges_h65")[2]
+    masks = [a["inlier"][cam == k] for k in range(3)]
+    want = a["n_inliers"][cams]
+    np.testing.assert_array_equal(QC.tile_sums(cams, a["n_usable"], masks, tile), want)
+    wrong = QC.tile_sums(cams, a["n_usable"], masks, tile, offset="camera")
+    assert (wrong[:20] == want[:20]).all() and wrong[20] != want[20]
