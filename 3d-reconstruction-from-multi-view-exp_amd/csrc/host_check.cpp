@@ -1,5 +1,5 @@
 // The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch) and the host logic of a RANSAC
-// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks) on hand-made inputs.  A program of its own,
+// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*) on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
 #include <cmath>
 #include <cstdio>
@@ -160,6 +160,32 @@ int main() {
     CHECK(big.build(big_ptr, nullptr, 2, 256, nullptr) == MVBA_ERR_BADARG);
     CHECK(g_err == "camera 1 has 2147483648 usable observations: must be < 2^31");
     CHECK(big.n_ch == 0 && big.ch_cam.size() == 1);
+  }
+  {  // the homography's host arithmetic: adjugate, the returned form, the signs of the two mask matrices
+    const double M[9] = {2, 0, 1, 1, 3, 0, 0, 1, 4}, I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double A[9], P[9];
+    hg_adjugate(M, A);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        P[3 * i + j] = 0.0;
+        for (int e = 0; e < 3; ++e) P[3 * i + j] += M[3 * i + e] * A[3 * e + j];
+        CHECK(P[3 * i + j] == 25.0 * I9[3 * i + j]);  // det M = 25
+      }
+    double U[9] = {0, 3, 0, 0, 0, 0, 0, -4, 0};  // the largest entry is negative: the sign turns, |U| = 1
+    CHECK(hg_unit(U) && std::fabs(U[1] + 0.6) < 1e-15 && std::fabs(U[7] - 0.8) < 1e-15);
+    double T[9] = {2, 0, 0, 0, -2, 0, 0, 0, 1};  // equal magnitudes: the first decides
+    CHECK(hg_unit(T) && T[0] > 0.0 && T[4] < 0.0);
+    double Z[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, N[9] = {1, 0, 0, 0, std::numeric_limits<double>::quiet_NaN(), 0, 0, 0, 1};
+    CHECK(!hg_unit(Z) && !hg_unit(N) && Z[0] == 0.0 && N[0] == 1.0);
+    // a translation by (-500, 0) in pixels, returned with its largest entry positive: w = -1 everywhere, so part 0 turns back
+    const double Hp[9] = {-1, 0, 500, 0, -1, 0, 0, 0, -1}, nm[8] = {320, 240, 0.01, -180, 240, 0.01, 50, 0};
+    double m0[9], m1[9];
+    hg_mask_parts(Hp, nm, m0, m1);
+    CHECK(m0[8] == 1.0 && m0[2] == -500.0 && m0[0] == 1.0);
+    CHECK(m1[8] == 1.0 && m1[2] == 500.0 && m1[0] == 1.0);  // adj(Hp) = [[1, 0, 500], [0, 1, 0], [0, 0, 1]]: w = 1 > 0 already
+    const double Hq[9] = {1, 0, 0, 0, 1, 0, 0.01, 0, -1};  // w changes sign across the image: the centroid decides
+    hg_mask_parts(Hq, nm, m0, m1);
+    CHECK(m0[6] * nm[0] + m0[7] * nm[1] + m0[8] > 0.0 && m1[6] * nm[3] + m1[7] * nm[4] + m1[8] > 0.0);
   }
   {  // the argument checks, with their texts
     CHECK(rs_check_search(0.01, 1) == MVBA_OK && rs_check_search(0.01, RS_MAX_HYP) == MVBA_OK && rs_check_refit(0) == MVBA_OK && rs_check_refit(RS_MAX_REFIT) == MVBA_OK);

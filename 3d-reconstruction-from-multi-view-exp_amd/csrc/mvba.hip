@@ -4371,6 +4371,7 @@ int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2,
 #include "mvba_init.h"  // initial estimates: mvba_triangulate, mvba_triangulate_state, mvba_resect
 #include "mvba_twoview.h"  // two-view start: mvba_covisibility, mvba_two_view
 #include "mvba_ransac.h"  // robust two-view start: mvba_two_view_robust, mvba_ransac_sample
+#include "mvba_homography.h"  // planar scenes: mvba_homography_robust, mvba_homography_sample
 #include "mvba_resect_ransac.h"  // robust resection: mvba_resect_robust, mvba_resect_sample
 #include "mvba_pose_ransac.h"    // calibrated robust resection: mvba_pose_robust, mvba_pose_refine, mvba_pose_sample
 #include "mvba_tri_ransac.h"     // robust triangulation: mvba_triangulate_robust, mvba_triangulate_sample

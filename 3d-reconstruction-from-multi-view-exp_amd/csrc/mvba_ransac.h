@@ -15,6 +15,9 @@
 // a hypothesis's count is ballot + popcount per wave, then integer atomics (LDS, then device memory): exact in any order.
 // Refits sum the moments of the compacted array under a byte mask by tv_pass and chunk_sum, as k_twoview_chunk does; the order-9
 // eigen-problem, the rank-2 step and the denormalisation are twoview_solve_pair's, on the host.  No floating-point atomics.
+//
+// The host loop over tiles of pairs is robust_pairs<Fit>, and the scoring and mask kernels are templates over the model a Fit
+// names: the fundamental matrix here (FundFit, FundModel), the homography in mvba_homography.h.
 
 namespace {
 
@@ -264,29 +267,47 @@ __global__ __launch_bounds__(RS_HYP_BLOCK) void k_ransac_hyp(long long stride, i
   hyp_count[(size_t)p * H + h] = good ? 0 : -1;
 }
 
+// What the scoring and mask kernels test a point against: PARTS 3 x 3 matrices per hypothesis (part a of pair p of a tile of
+// cnt pairs at [(a cnt + p) ...]: the parts are whole arrays, one behind the other), the fewest points MIN a pair needs, and
+// inlier, the test the scoring kernel counts by, and dist2, the squared distance the mask pass sums and tests: a point is an
+// inlier there if it is <= threshold^2, and the two agree on every point (a model with a test of its own returns infinity from
+// dist2 where that fails).  The fundamental matrix: one part, the Sampson distance.  (The homography: mvba_homography.h.)
+struct FundModel {
+  static constexpr int PARTS = 1, MIN = TV_MIN_SHARED;
+  static __device__ __forceinline__ double dist2(const double *F, const double *, double xk, double yk, double xl, double yl, double) {
+    return rs_sampson(F, xk, yk, xl, yl);
+  }
+  static __device__ __forceinline__ bool inlier(const double *F, const double *, double xk, double yk, double xl, double yl, double thr2) {
+    return rs_sampson(F, xk, yk, xl, yl) <= thr2;
+  }
+};
+
 // Scoring: grid (chunks of compacted points, blocks of 64 hypotheses, pairs).  A thread holds one point and walks the block's
 // matrices in LDS (every lane reads the same address: a broadcast); a hypothesis's inliers of a wave are one ballot and one
 // popcount, kept by the lane of the hypothesis's number; then integer atomics.  A degenerate hypothesis is NaN: no point
 // passes, its count stays -1.
+template <class M>
 __global__ __launch_bounds__(START_CHUNK) void k_ransac_score(long long stride, int H, const int *__restrict__ ntot,
                                                            const double4 *__restrict__ comp, const double *__restrict__ hypF,
                                                            double thr2, int *__restrict__ hyp_count) {
-  __shared__ double s_F[RS_HYP_BLOCK * 9];
+  __shared__ double s_F[M::PARTS][RS_HYP_BLOCK * 9];
   __shared__ int s_cnt[RS_HYP_BLOCK];
   const int p = blockIdx.z, h0 = blockIdx.y * RS_HYP_BLOCK, i = threadIdx.x, lane = i & 63;
   const int n = ntot[p];
   const long long j = (long long)blockIdx.x * START_CHUNK + i;
-  if (n < TV_MIN_SHARED || (long long)blockIdx.x * START_CHUNK >= n) return;  // (the whole workgroup leaves)
+  if (n < M::MIN || (long long)blockIdx.x * START_CHUNK >= n) return;  // (the whole workgroup leaves)
   const int nh = min(RS_HYP_BLOCK, H - h0);
-  for (int e = i; e < nh * 9; e += START_CHUNK) s_F[e] = hypF[((size_t)p * H + h0) * 9 + e];
+  for (int e = i; e < nh * 9; e += START_CHUNK) s_F[0][e] = hypF[((size_t)p * H + h0) * 9 + e];
+  if constexpr (M::PARTS == 2)
+    for (int e = i; e < nh * 9; e += START_CHUNK) s_F[1][e] = hypF[(((size_t)gridDim.z + p) * H + h0) * 9 + e];
   if (i < RS_HYP_BLOCK) s_cnt[i] = 0;
   __syncthreads();
   const bool live = j < n;
   const double4 z = live ? comp[(size_t)p * stride + j] : make_double4(0.0, 0.0, 0.0, 0.0);
   int mine = 0;
   for (int hh = 0; hh < nh; ++hh) {
-    const double d2 = rs_sampson(s_F + 9 * hh, z.x, z.y, z.z, z.w);
-    const int c = __popcll(__ballot(live && d2 <= thr2));
+    const bool in = M::inlier(s_F[0] + 9 * hh, s_F[M::PARTS - 1] + 9 * hh, z.x, z.y, z.z, z.w, thr2);
+    const int c = __popcll(__ballot(live && in));
     if (lane == hh) mine = c;
   }
   if (mine) atomicAdd(&s_cnt[lane], mine);
@@ -304,8 +325,9 @@ __global__ __launch_bounds__(256) void k_ransac_gather(int n_pairs, int H, const
   fbest[t] = b >= 0 ? hypf[((size_t)p * H + b) * 9 + e] : NAN;
 }
 
-// The inlier set of F[pair] into the pair's OTHER mask buffer, and part[pair][chunk][2] = (count, sum of d^2 over it) by the
+// The inlier set of the pair's matrices F[part][pair] into the pair's OTHER mask buffer, and part[pair][chunk][2] = (count, sum of d^2 over it) by the
 // tree of chunk_sum (the count is exact in a double).  A pair that is not RS_ACTIVE writes nothing and sums nothing.
+template <class M>
 __global__ __launch_bounds__(START_CHUNK) void k_ransac_mask(long long stride, const int *__restrict__ ntot, const int *__restrict__ state,
                                                           const double4 *__restrict__ comp, const double *__restrict__ F, double thr2,
                                                           unsigned char *__restrict__ inl0, unsigned char *__restrict__ inl1,
@@ -316,7 +338,8 @@ __global__ __launch_bounds__(START_CHUNK) void k_ransac_mask(long long stride, c
   double v[2] = {0.0, 0.0};
   if ((st & RS_ACTIVE) && j < ntot[p]) {
     const double4 z = comp[(size_t)p * stride + j];
-    const double d2 = rs_sampson(F + 9 * (size_t)p, z.x, z.y, z.z, z.w);
+    const double *F0 = F + 9 * (size_t)p;
+    const double d2 = M::dist2(F0, F0 + (size_t)(M::PARTS - 1) * gridDim.y * 9, z.x, z.y, z.z, z.w, thr2);
     const bool in = d2 <= thr2;
     ((st & RS_CUR) ? inl0 : inl1)[(size_t)p * stride + j] = in ? 1 : 0;
     if (in) { v[0] = 1.0; v[1] = d2; }
@@ -344,28 +367,41 @@ int ransac_finish_hypothesis(const double *fh, const double *nm, double *F) {
   return twoview_solve_pair(S45, nm, F, &ratio);
 }
 
-}  // namespace
+// The model-specific steps of robust_pairs, for the fundamental matrix: the hypothesis kernel (F in part 0, F^ in part 1 of
+// hyp), the refit's moments (tv_pass mode 2) and eigen-solve, and what a hypothesis that no refit replaces becomes.
+struct FundFit {
+  using Model = FundModel;
+  static constexpr int MOMENTS = 2;
+  static constexpr size_t HYP_BYTES = RS_HYP_BYTES;
+  static constexpr const char *NAME = "F";
+  static constexpr int hyp_lds = (int)(sizeof(double) * 2 * 81 * RS_HYP_BLOCK);
+  static int prepare() {
+    MVBA_HIP(hipFuncSetAttribute((const void *)k_ransac_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, hyp_lds));
+    return MVBA_OK;
+  }
+  static void hypotheses(int cnt, long long stride, int H, unsigned long long seed, const int *pairs, const int *ntot, const double4 *comp,
+                         const double *norm, double *hyp, int *hyp_count) {
+    hipLaunchKernelGGL(k_ransac_hyp, dim3((H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, cnt), dim3(RS_HYP_BLOCK), hyp_lds, 0, stride, H, seed, pairs, ntot,
+                       comp, norm, hyp + 9 * (size_t)cnt * H, hyp, hyp_count);
+  }
+  // the pair's best hypothesis (part 0 and part 1 of it) -> the matrix the call returns if no refit is kept
+  static int finish(const double *, const double *fh, const double *nm, double *F) { return ransac_finish_hypothesis(fh, nm, F); }
+  static int solve(const double *S45, const double *nm, double *F, double *ratio) { return twoview_solve_pair(S45, nm, F, ratio); }
+  // a refit's matrix -> the parts the mask kernel tests against
+  static void mask_parts(const double *F, const double *, double *m0, double *) { std::copy(F, F + 9, m0); }
+};
 
-extern "C" {
-
-int mvba_ransac_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx8) {
-  if (!idx8) return fail(MVBA_ERR_BADARG, "null argument: idx8 (argument 6)");
-  if (n < TV_MIN_SHARED || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 8 .. 2^31 - 1");
-  if (k < 0 || l < 0 || h < 0)
-    return fail(MVBA_ERR_BADARG, "k = " + std::to_string(k) + ", l = " + std::to_string(l) + ", h = " + std::to_string(h) + ": negative index");
-  long long idx[8];
-  rs_sample(seed, k, l, h, n, idx);
-  for (int c = 0; c < 8; ++c) idx8[c] = idx[c];
-  return MVBA_OK;
-}
-
-int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
-                         const int32_t *pairs, int32_t n_pairs, double threshold, int32_t n_hypotheses, uint64_t seed, int32_t n_refit,
-                         double *F, double *quality, int64_t *n_shared, int64_t *n_inliers, int32_t *best, uint8_t *inlier,
-                         int32_t *hyp_count, int32_t *status, double *timings_ms, int32_t device) {
+// The pair-tile loop of a robust two-view fit, once: mvba_two_view_robust (FundFit) and mvba_homography_robust (HomogFit,
+// mvba_homography.h) are this function.  `F` is the model's matrix, whatever it is called.
+template <class Fit>
+int robust_pairs(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
+                 const int32_t *pairs, int32_t n_pairs, double threshold, int32_t n_hypotheses, uint64_t seed, int32_t n_refit,
+                 double *F, double *quality, int64_t *n_shared, int64_t *n_inliers, int32_t *best, uint8_t *inlier,
+                 int32_t *hyp_count, int32_t *status, double *timings_ms, int32_t device) {
+  using Model = typename Fit::Model;
   if (n_pairs < 0) return fail(MVBA_ERR_BADARG, "n_pairs = " + std::to_string(n_pairs) + " must be >= 0");
   if (!xy || (n_pairs > 0 && (!pairs || !F)))
-    return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!xy ? "xy" : (!pairs ? "pairs" : "F")) + " (argument " +
+    return fail(MVBA_ERR_BADARG, std::string("null argument: ") + (!xy ? "xy" : (!pairs ? "pairs" : Fit::NAME)) + " (argument " +
                                      std::to_string(!xy ? 5 : (!pairs ? 7 : 13)) + ")");
   int rc;
   if ((rc = rs_check_search(threshold, n_hypotheses)) || (rc = rs_check_refit(n_refit))) return rc;
@@ -393,41 +429,39 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
   InitClock clk;
   const long long n_ch = (n_points + START_CHUNK - 1) / START_CHUNK;
   const long long stride = n_points;
-  const int tile = tv_pair_tile(np, RS_POINT_BYTES * (size_t)n_points + RS_HYP_BYTES * (size_t)H);
+  const int tile = tv_pair_tile(np, RS_POINT_BYTES * (size_t)n_points + Fit::HYP_BYTES * (size_t)H);
   DevBufs tmp;
   double2 *dxy = nullptr;
   long long *dptr = nullptr;
   int *dcam = nullptr, *dpairs = nullptr, *doff = nullptr, *dntot = nullptr, *did = nullptr, *dstate = nullptr, *dbest = nullptr, *dhc = nullptr;
   double4 *dcomp = nullptr;
   unsigned char *dinl0 = nullptr, *dinl1 = nullptr, *dout = nullptr;
-  double *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dnorm2 = nullptr, *dF = nullptr, *dfb = nullptr, *dhypf = nullptr, *dhypF = nullptr;
+  double *dpart = nullptr, *dS = nullptr, *dnorm = nullptr, *dnorm2 = nullptr, *dF = nullptr, *dhyp = nullptr;
   const size_t ts = (size_t)tile * (size_t)stride;
   if ((rc = upload_list(tmp, n_points, n_obs, pt_ptr, cam_idx, xy, &dptr, &dcam, &dxy)) || (rc = tmp.alloc(&dpairs, 2 * (size_t)np)) || (rc = tmp.alloc(&doff, (size_t)tile * n_ch)) ||
       (rc = tmp.alloc(&dntot, (size_t)tile)) || (rc = tmp.alloc(&did, ts)) || (rc = tmp.alloc(&dstate, (size_t)tile)) ||
       (rc = tmp.alloc(&dbest, (size_t)tile)) || (rc = tmp.alloc(&dhc, (size_t)tile * H)) || (rc = tmp.alloc(&dcomp, ts)) ||
       (rc = tmp.alloc(&dinl0, ts)) || (rc = tmp.alloc(&dinl1, ts)) || (rc = tmp.alloc(&dpart, 45 * (size_t)n_ch * tile)) ||
       (rc = tmp.alloc(&dS, 45 * (size_t)tile)) || (rc = tmp.alloc(&dnorm, TV_NORM * (size_t)tile)) || (rc = tmp.alloc(&dnorm2, TV_NORM * (size_t)tile)) ||
-      (rc = tmp.alloc(&dF, 9 * (size_t)tile)) || (rc = tmp.alloc(&dfb, 9 * (size_t)tile)) || (rc = tmp.alloc(&dhypf, 9 * (size_t)tile * H)) ||
-      (rc = tmp.alloc(&dhypF, 9 * (size_t)tile * H)))
+      (rc = tmp.alloc(&dF, 18 * (size_t)tile)) || (rc = tmp.alloc(&dhyp, 18 * (size_t)tile * H)))
     return rc;
   if (inlier && (rc = tmp.alloc(&dout, ts))) return rc;
   MVBA_HIP(hipMemcpy(dpairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice));
-  const int hyp_lds = (int)(sizeof(double) * 2 * 81 * RS_HYP_BLOCK);
-  MVBA_HIP(hipFuncSetAttribute((const void *)k_ransac_hyp, hipFuncAttributeMaxDynamicSharedMemorySize, hyp_lds));
+  if ((rc = Fit::prepare())) return rc;
   RsLaps laps;
   laps.upload = clk.lap();
 
   const dim3 b256(256), bch(START_CHUNK);
   std::vector<int> ntot((size_t)tile), hc((size_t)tile * H), bst((size_t)tile), state((size_t)tile), st((size_t)tile);
   std::vector<long long> nin((size_t)tile);
-  std::vector<double> S((size_t)tile * 45), norm(TV_NORM * (size_t)tile), fb(9 * (size_t)tile), Fc(9 * (size_t)tile), Fn(9 * (size_t)tile),
+  std::vector<double> S((size_t)tile * 45), norm(TV_NORM * (size_t)tile), fb(18 * (size_t)tile), Fc(9 * (size_t)tile), Fn(9 * (size_t)tile), Mn(18 * (size_t)tile),
       S2(2 * (size_t)tile), ssq((size_t)tile), ratio((size_t)tile);
   for (int p0 = 0; p0 < np; p0 += tile) {
     const int cnt = std::min(tile, np - p0);
     const dim3 grid((unsigned)n_ch, (unsigned)cnt), gp((cnt + 255) / 256);
     const int *tp = dpairs + 2 * (size_t)p0;
     auto combine = [&](int nv, double *out) { tv_combine(cnt, nv, n_ch, dpart, out, nv); };
-    // the normalised 8-point sums of the pairs' current masks (st_dev == nullptr: of all shared points, passes 0 and 1 only)
+    // the normalised moment sums of the pairs' current masks (st_dev == nullptr: of all shared points, passes 0 and 1 only)
     auto fit = [&](const int *st_dev, double *nm_dev, bool moments) {
       hipLaunchKernelGGL(k_ransac_fit<0>, grid, bch, 0, 0, stride, dntot, st_dev, dcomp, dinl0, dinl1, (const double *)nullptr, dpart);
       combine(5, dS);
@@ -436,14 +470,14 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
       combine(2, dS);
       hipLaunchKernelGGL(k_twoview_norm, gp, b256, 0, 0, cnt, 1, dS, 2, nm_dev);
       if (moments) {
-        hipLaunchKernelGGL(k_ransac_fit<2>, grid, bch, 0, 0, stride, dntot, st_dev, dcomp, dinl0, dinl1, nm_dev, dpart);
+        hipLaunchKernelGGL(k_ransac_fit<Fit::MOMENTS>, grid, bch, 0, 0, stride, dntot, st_dev, dcomp, dinl0, dinl1, nm_dev, dpart);
         combine(45, dS);
       }
     };
     // the inlier sets of dF under the pairs' states: counts and sums of d^2 into S2
     auto mask = [&]() -> int {
       MVBA_HIP(hipMemcpy(dstate, state.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(k_ransac_mask, grid, bch, 0, 0, stride, dntot, dstate, dcomp, dF, thr2, dinl0, dinl1, dpart);
+      hipLaunchKernelGGL(k_ransac_mask<Model>, grid, bch, 0, 0, stride, dntot, dstate, dcomp, dF, thr2, dinl0, dinl1, dpart);
       combine(2, dS);
       MVBA_HIP(hipGetLastError());
       MVBA_HIP(hipMemcpy(S2.data(), dS, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost));
@@ -455,10 +489,9 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
     hipLaunchKernelGGL(k_ransac_scan, dim3(cnt), b256, 0, 0, (int)n_ch, doff, dntot);
     hipLaunchKernelGGL(k_ransac_compact, grid, bch, 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, doff, dcomp, did);
     fit(nullptr, dnorm, false);
-    hipLaunchKernelGGL(k_ransac_hyp, dim3((H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, cnt), dim3(RS_HYP_BLOCK), hyp_lds, 0, stride, H,
-                       (unsigned long long)seed, tp, dntot, dcomp, dnorm, dhypf, dhypF, dhc);
-    hipLaunchKernelGGL(k_ransac_score, dim3((unsigned)n_ch, (H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, cnt), bch, 0, 0, stride, H, dntot, dcomp,
-                       dhypF, thr2, dhc);
+    Fit::hypotheses(cnt, stride, H, (unsigned long long)seed, tp, dntot, dcomp, dnorm, dhyp, dhc);
+    hipLaunchKernelGGL(k_ransac_score<Model>, dim3((unsigned)n_ch, (H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK, cnt), bch, 0, 0, stride, H, dntot, dcomp,
+                       dhyp, thr2, dhc);
     MVBA_HIP(hipGetLastError());
     MVBA_HIP(hipMemcpy(hc.data(), dhc, sizeof(int) * (size_t)cnt * H, hipMemcpyDeviceToHost));
     MVBA_HIP(hipMemcpy(ntot.data(), dntot, sizeof(int) * cnt, hipMemcpyDeviceToHost));
@@ -466,15 +499,16 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
     laps.score += clk.lap();
 
     for (int p = 0; p < cnt; ++p) {
-      const RsPick pick = rs_pick(hc.data() + (size_t)p * H, H, ntot[p], TV_MIN_SHARED);
+      const RsPick pick = rs_pick(hc.data() + (size_t)p * H, H, ntot[p], Model::MIN);
       st[p] = pick.status;
       bst[p] = pick.best;
       state[p] = pick.state;
     }
     MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_ransac_gather, dim3((cnt * 9 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhypF, dhypf, dF, dfb);
+    // the two parts of the best hypothesis, one array behind the other: what the mask kernel reads
+    hipLaunchKernelGGL(k_ransac_gather, dim3((cnt * 9 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhyp, dhyp + 9 * (size_t)cnt * H, dF, dF + 9 * (size_t)cnt);
     if ((rc = mask())) return rc;
-    MVBA_HIP(hipMemcpy(fb.data(), dfb, sizeof(double) * 9 * cnt, hipMemcpyDeviceToHost));
+    MVBA_HIP(hipMemcpy(fb.data(), dF, sizeof(double) * 18 * cnt, hipMemcpyDeviceToHost));
     int n_active = 0;
     for (int p = 0; p < cnt; ++p) {
       if (st[p]) continue;
@@ -482,7 +516,7 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
       nin[p] = (long long)S2[2 * p];
       ssq[p] = S2[2 * p + 1];
       ratio[p] = 0.0;  // (the moment matrix of a minimal sample has rank 8)
-      st[p] = ransac_finish_hypothesis(fb.data() + 9 * (size_t)p, norm.data() + TV_NORM * (size_t)p, Fc.data() + 9 * (size_t)p);
+      st[p] = Fit::finish(fb.data() + 9 * (size_t)p, fb.data() + 9 * (size_t)(cnt + p), norm.data() + TV_NORM * (size_t)p, Fc.data() + 9 * (size_t)p);
       if (st[p]) state[p] = 0;
       else ++n_active;
     }
@@ -497,12 +531,14 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
       MVBA_HIP(hipMemcpy(norm.data(), dnorm2, sizeof(double) * TV_NORM * cnt, hipMemcpyDeviceToHost));
       std::vector<double> rt((size_t)cnt, NAN);
       for (int p = 0; p < cnt; ++p) {
-        for (int j = 0; j < 9; ++j) Fn[9 * (size_t)p + j] = NAN;
+        for (int j = 0; j < 9; ++j) Fn[9 * (size_t)p + j] = Mn[9 * (size_t)p + j] = Mn[9 * (size_t)(cnt + p) + j] = NAN;
         if (!(state[p] & RS_ACTIVE)) continue;
-        if (twoview_solve_pair(S.data() + 45 * (size_t)p, norm.data() + TV_NORM * (size_t)p, Fn.data() + 9 * (size_t)p, &rt[p])) rs_stop(state[p], n_active);
+        const double *nm = norm.data() + TV_NORM * (size_t)p;
+        if (Fit::solve(S.data() + 45 * (size_t)p, nm, Fn.data() + 9 * (size_t)p, &rt[p])) rs_stop(state[p], n_active);
+        else Fit::mask_parts(Fn.data() + 9 * (size_t)p, nm, Mn.data() + 9 * (size_t)p, Mn.data() + 9 * (size_t)(cnt + p));
       }
       if (n_active == 0) break;
-      MVBA_HIP(hipMemcpy(dF, Fn.data(), sizeof(double) * 9 * cnt, hipMemcpyHostToDevice));
+      MVBA_HIP(hipMemcpy(dF, Mn.data(), sizeof(double) * 9 * Model::PARTS * cnt, hipMemcpyHostToDevice));
       if ((rc = mask())) return rc;
       for (int p = 0; p < cnt; ++p) {
         if (!(state[p] & RS_ACTIVE)) continue;
@@ -541,6 +577,29 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
   }
   laps.write(timings_ms);
   return MVBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvba_ransac_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx8) {
+  if (!idx8) return fail(MVBA_ERR_BADARG, "null argument: idx8 (argument 6)");
+  if (n < TV_MIN_SHARED || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 8 .. 2^31 - 1");
+  if (k < 0 || l < 0 || h < 0)
+    return fail(MVBA_ERR_BADARG, "k = " + std::to_string(k) + ", l = " + std::to_string(l) + ", h = " + std::to_string(h) + ": negative index");
+  long long idx[8];
+  rs_sample(seed, k, l, h, n, idx);
+  for (int c = 0; c < 8; ++c) idx8[c] = idx[c];
+  return MVBA_OK;
+}
+
+int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,
+                         const int32_t *pairs, int32_t n_pairs, double threshold, int32_t n_hypotheses, uint64_t seed, int32_t n_refit,
+                         double *F, double *quality, int64_t *n_shared, int64_t *n_inliers, int32_t *best, uint8_t *inlier,
+                         int32_t *hyp_count, int32_t *status, double *timings_ms, int32_t device) {
+  return robust_pairs<FundFit>(n_points, n_images, pt_ptr, cam_idx, xy, n_obs, pairs, n_pairs, threshold, n_hypotheses, seed, n_refit, F, quality,
+                               n_shared, n_inliers, best, inlier, hyp_count, status, timings_ms, device);
 }
 
 }  // extern "C"

@@ -10,6 +10,12 @@
 
 #include "mvba_common.h"
 
+#if defined(__HIP__)
+#define RS_HD __host__ __device__  // a helper the kernels use too
+#else
+#define RS_HD
+#endif
+
 namespace mvba {
 
 constexpr int RS_MAX_HYP = 65536;  // n_hypotheses
@@ -70,6 +76,38 @@ inline bool rs_accept(long long count, long long kept, int r, long long first_mi
   }
   rs_stop(state, n_active);
   return false;
+}
+
+// The homography's host arithmetic between the kernels of mvba_homography_robust (row-major 3 x 3 matrices).
+// adj(M): M adj(M) = det(M) I -- the inverse up to scale, which is all a homography needs
+RS_HD inline void hg_adjugate(const double *m, double *a) {
+  a[0] = m[4] * m[8] - m[5] * m[7]; a[1] = m[2] * m[7] - m[1] * m[8]; a[2] = m[1] * m[5] - m[2] * m[4];
+  a[3] = m[5] * m[6] - m[3] * m[8]; a[4] = m[0] * m[8] - m[2] * m[6]; a[5] = m[2] * m[3] - m[0] * m[5];
+  a[6] = m[3] * m[7] - m[4] * m[6]; a[7] = m[1] * m[6] - m[0] * m[7]; a[8] = m[0] * m[4] - m[1] * m[3];
+}
+// the form a matrix is returned in: Frobenius norm 1, the largest-magnitude entry (the first of equals) positive.  false if
+// an entry is not finite or the matrix is zero (it is left as it is then).
+inline bool hg_unit(double *m) {
+  double nrm = 0.0, big = 0.0;
+  for (int j = 0; j < 9; ++j) {
+    nrm += m[j] * m[j];
+    if (std::fabs(m[j]) > std::fabs(big)) big = m[j];
+  }
+  if (!std::isfinite(nrm) || !(nrm > 0.0)) return false;
+  const double sc = (big < 0.0 ? -1.0 : 1.0) / std::sqrt(nrm);
+  for (int j = 0; j < 9; ++j) m[j] *= sc;
+  return true;
+}
+// The two matrices the inlier test reads, out of H (x_l ~ H x_k): the test asks for a positive third coordinate, so the sign
+// matters.  m0 = +-H and m1 = +-adj(H), each with the sign that makes the third coordinate positive at the centroid of the
+// points it is applied to -- (ckx, cky) in k, (clx, cly) in l: nm[0], nm[1], nm[3], nm[4] of the fit's TV_NORM record.
+inline void hg_mask_parts(const double *H, const double *nm, double *m0, double *m1) {
+  hg_adjugate(H, m1);
+  const double wk = H[6] * nm[0] + H[7] * nm[1] + H[8], wl = m1[6] * nm[3] + m1[7] * nm[4] + m1[8];
+  for (int j = 0; j < 9; ++j) {
+    m0[j] = wk < 0.0 ? -H[j] : H[j];
+    if (wl < 0.0) m1[j] = -m1[j];
+  }
 }
 
 // the four phases of a robust call, in milliseconds

@@ -23,8 +23,9 @@ constexpr size_t TV_PART_BYTES = 128u << 20;    // chunk partials of one launch:
 constexpr int CV_LDS_CAMERAS = 128;             // m^2 x 4 bytes <= 64 KiB: the co-visibility table lives in LDS
 
 // values per shared point of the four passes: 0 count and first moments, 1 squared distances to the centroids, 2 the 45
-// unique products of the epipolar row, 3 the squared Sampson distance
-__host__ __device__ constexpr int tv_values(int mode) { return mode == 0 ? 5 : (mode == 1 ? 2 : (mode == 2 ? 45 : 1)); }
+// unique products of the epipolar row, 3 the squared Sampson distance, 4 the 45 unique products of the two homography
+// (DLT) rows, summed over the two (mvba_homography.h)
+__host__ __device__ constexpr int tv_values(int mode) { return mode == 0 ? 5 : (mode == 1 ? 2 : (mode == 2 || mode == 4 ? 45 : 1)); }
 // doubles per pair of what a pass reads besides the point: 0 nothing, 1 and 2 the TV_NORM record, 3 F
 __host__ __device__ constexpr int tv_aux(int mode) { return mode == 0 ? 0 : (mode == 3 ? 9 : TV_NORM); }
 
@@ -100,8 +101,17 @@ __device__ __forceinline__ void tv_row(const double *nm, double zkx, double zky,
   r[0] = xl * xk; r[1] = xl * yk; r[2] = xl; r[3] = yl * xk; r[4] = yl * yk; r[5] = yl; r[6] = xk; r[7] = yk; r[8] = 1.0;
 }
 
+// the two rows of one correspondence x_l ~ H^ x_k in the normalised coordinates of the pair's TV_NORM record nm:
+// r1 . h^ = r2 . h^ = 0 (the third row of the cross product is a combination of the two)
+__device__ __forceinline__ void hg_rows(const double *nm, double zkx, double zky, double zlx, double zly, double (&r1)[9], double (&r2)[9]) {
+  const double xk = nm[2] * (zkx - nm[0]), yk = nm[2] * (zky - nm[1]);
+  const double xl = nm[5] * (zlx - nm[3]), yl = nm[5] * (zly - nm[4]);
+  r1[0] = xk; r1[1] = yk; r1[2] = 1.0; r1[3] = r1[4] = r1[5] = 0.0; r1[6] = -xl * xk; r1[7] = -xl * yk; r1[8] = -xl;
+  r2[0] = r2[1] = r2[2] = 0.0; r2[3] = xk; r2[4] = yk; r2[5] = 1.0; r2[6] = -yl * xk; r2[7] = -yl * yk; r2[8] = -yl;
+}
+
 // The values of one shared point, (xk, yk) in k and (xl, yl) in l, in pass MODE.  aux (of the pair): mode 1, 2 its TV_NORM
-// record, mode 3 F [9] (tv_aux doubles).
+// record, mode 3 F [9], mode 4 its TV_NORM record (tv_aux doubles).
 template <int MODE>
 __device__ __forceinline__ void tv_pass(double xk, double yk, double xl, double yl, const double *aux, double (&v)[tv_values(MODE)]) {
   if constexpr (MODE == 0) {
@@ -118,6 +128,14 @@ __device__ __forceinline__ void tv_pass(double xk, double yk, double xl, double 
     for (int b = 0; b < 9; ++b)
 #pragma unroll
       for (int c = b; c < 9; ++c, ++e) v[e] = r[b] * r[c];
+  } else if constexpr (MODE == 4) {
+    double r1[9], r2[9];
+    hg_rows(aux, xk, yk, xl, yl, r1, r2);
+    int e = 0;
+#pragma unroll
+    for (int b = 0; b < 9; ++b)
+#pragma unroll
+      for (int c = b; c < 9; ++c, ++e) v[e] = r1[b] * r1[c] + r2[b] * r2[c];
   } else {
     v[0] = rs_sampson(aux, xk, yk, xl, yl);
   }
@@ -138,6 +156,26 @@ __host__ __device__ __forceinline__ void tv_denormalise(const double *nm, const 
     F[j] = sl * Q[0][j];
     F[3 + j] = sl * Q[1][j];
     F[6 + j] = Q[2][j] - sl * (clx * Q[0][j] + cly * Q[1][j]);
+  }
+}
+
+// H = T_b^-1 H^ T_a with T^-1 = [[1/s, 0, cx], [0, 1/s, cy], [0, 0, 1]]: h the row-major H^ that maps the normalised points of
+// image a to those of image b; na, nb = (cx, cy, s) of the two images (nm, nm + 3 of a TV_NORM record, or the other way round
+// for the inverse map)
+__host__ __device__ __forceinline__ void hg_denormalise(const double *na, const double *nb, const double *h, double *H) {
+  double Q[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    Q[i][0] = na[2] * h[3 * i];
+    Q[i][1] = na[2] * h[3 * i + 1];
+    Q[i][2] = h[3 * i + 2] - na[2] * (na[0] * h[3 * i] + na[1] * h[3 * i + 1]);
+  }
+  const double inv = 1.0 / nb[2];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    H[j] = inv * Q[0][j] + nb[0] * Q[2][j];
+    H[3 + j] = inv * Q[1][j] + nb[1] * Q[2][j];
+    H[6 + j] = Q[2][j];
   }
 }
 
@@ -236,6 +274,25 @@ int twoview_solve_pair(const double *S45, const double *nm, double *F, double *r
     ok = ok && std::isfinite(F[j]);
   }
   return ok ? 0 : 2;
+}
+
+// the 45 sums of one pair (tv_pass mode 4) -> H = T_l^-1 H^ T_k (|H| = 1, largest entry positive), status and lambda_1 /
+// lambda_2: twoview_solve_pair without the rank-2 step
+int homography_solve_pair(const double *S45, const double *nm, double *H, double *ratio) {
+  *ratio = NAN;
+  for (int e = 0; e < 45; ++e)
+    if (!std::isfinite(S45[e])) return 2;
+  double A[9][9], V[9][9];
+  int e = 0;
+  for (int b = 0; b < 9; ++b)
+    for (int c = b; c < 9; ++c, ++e) A[b][c] = A[c][b] = S45[e];
+  sym_eig_jacobi<9>(A, V);
+  double l1, l2, lmax, h[9];
+  eig_extremes<9>(A, V, l1, l2, lmax, h);
+  *ratio = l1 / l2;
+  if (!(l2 > INIT_REL_PIVOT * lmax)) return 2;
+  hg_denormalise(nm, nm + 3, h, H);
+  return hg_unit(H) ? 0 : 2;
 }
 
 // pairs per launch: the tile's device bytes stay under TV_PART_BYTES, its count within gridDim.y

@@ -104,6 +104,11 @@ SIGNATURES = {
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), _dp, C.c_int32]),
     "mvba_ransac_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "mvba_homography_robust": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.POINTER(C.c_int32),
+                                         C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int32, _dp, _dp, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_homography_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "mvba_resect_robust": (C.c_int, [_dp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int32,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int32,
                                      _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
@@ -603,6 +608,32 @@ def ransac_sample(seed, k, l, h, n):
     """The 8 distinct indices below ``n`` that hypothesis ``h`` of pair (k, l) draws (mvba_ransac_sample: the host instance of
     the function the kernel runs; no GPU needed)."""
     return _sample("mvba_ransac_sample", 8, seed, k, l, h, n)
+
+
+def homography_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=512, seed=0, n_refit=2, return_inliers=True,
+                      return_counts=False, device=-1):
+    """Homographies by 4-point RANSAC on the device (mvba_homography_robust).  The arguments of ``two_view_robust``;
+    ``threshold`` is a transfer distance in the units of xy, held in both directions.  Returns its dict with ``H (P, 3, 3)`` --
+    x_l ~ H x_k, |H| = 1, largest entry positive -- in the place of F; ``quality (P, 2)`` is the RMS symmetric transfer distance
+    over the final inliers and the eigenvalue ratio of the last kept refit; ``status`` 0 ok, 1 fewer than 4 shared points, 2
+    every hypothesis degenerate, 4 best count below 4.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_homography_robust")
+    xy, m = _as(xy, np.float64), int(n_images)
+    pairs = _as(pairs, np.int32).reshape(-1, 2)
+    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
+    P, H = pairs.shape[0], int(n_hypotheses)
+    Hm = np.empty((P, 3, 3))
+    tail, result = _robust_outputs({"H": Hm}, P, "n_shared", H, (P, n) if return_inliers else None, return_counts)
+    raise_for(lib.mvba_homography_robust(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, float(threshold), H,
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(Hm), *tail, int(device)), lib)
+    return result()
+
+
+def homography_sample(seed, k, l, h, n):
+    """The 4 distinct indices below ``n`` that hypothesis ``h`` of pair (k, l) draws (mvba_homography_sample: the host instance
+    of the function the kernel runs; no GPU needed)."""
+    return _sample("mvba_homography_sample", 4, seed, k, l, h, n)
 
 
 def resect_robust(X, pt_ptr, cam_idx, xy, n_images, threshold, point_ok=None, cameras=None, n_hypotheses=512, seed=0, n_refit=2,

@@ -11,7 +11,9 @@ later camera from 6-point RANSAC (``mvba_resect_robust``: csrc/mvba_resect_ransa
 every point from a two-view RANSAC of its own (``mvba_triangulate_robust``: csrc/mvba_tri_ransac.h):
 ``triangulate_threshold``.  With the intrinsics known -- ``bootstrap`` is given them -- a later camera is better registered by
 its POSE alone: three-point RANSAC and a pose-only Gauss-Newton refit (``mvba_pose_robust``, ``mvba_pose_refine``:
-csrc/mvba_pose_ransac.h): ``pose_threshold``.
+csrc/mvba_pose_ransac.h): ``pose_threshold``.  A PLANAR scene has no fundamental matrix: its start pair comes from
+4-point RANSAC for the homography (``mvba_homography_robust``: csrc/mvba_homography.h) and the decomposition of it:
+``model``.
 """
 from __future__ import annotations
 
@@ -246,6 +248,35 @@ def ransac_sample(seed, k, l, h, n):
     return _mvba.ransac_sample(seed, k, l, h, n)
 
 
+def robust_homographies(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses: int = 512, seed: int = 0, n_refit: int = 2,
+                        return_inliers: bool = True):
+    """(H (P, 3, 3), info): the homography x_l ~ H x_k of each pair (k, l) by 4-point RANSAC on the device
+    (``mvba_homography_robust``) -- the two-view model of points in a plane, where the fundamental matrix is not determined.
+    Per pair, ``n_hypotheses`` samples of four shared points (``homography_sample``) are solved in closed form and scored by the
+    number of shared points that transfer within ``threshold`` (units of xy) in BOTH directions with a positive third
+    coordinate; the best hypothesis's inliers get the normalised DLT, ``n_refit`` times at most, each kept while its own inlier
+    set does not shrink.  H is in the units of xy, |H| = 1, largest-magnitude entry positive.  ``info``: ``status`` (P,) -- 0 ok,
+    1 fewer than 4 shared points, 2 every hypothesis degenerate (collinear points), 4 the best hypothesis has fewer than 4
+    inliers; H and quality are NaN where it is not 0 --, ``n_shared``, ``n_inliers``, ``best`` (P,), ``quality`` (P, 2) -- RMS
+    symmetric transfer distance over the final inliers, lambda_1 / lambda_2 of the last kept refit --, ``inlier`` (P, N) bool
+    (``return_inliers``), ``hyp_count`` (P, H), ``confidence`` (P,) = 1 - (1 - w^4)^H with w = n_inliers / n_shared, and
+    ``timings_ms``.  Two calls with the same arguments return the same bits."""
+    out = _mvba.homography_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=n_hypotheses, seed=seed, n_refit=n_refit,
+                                  return_inliers=return_inliers, return_counts=True)
+    H = out.pop("H")
+    with np.errstate(all="ignore"):
+        w = out["n_inliers"] / np.maximum(out["n_shared"], 1)
+        out["confidence"] = np.where(out["status"] == 0, 1.0 - (1.0 - w ** 4) ** int(n_hypotheses), 0.0)
+    return H, out
+
+
+def homography_sample(seed, k, l, h, n):
+    """The 4 distinct indices below ``n`` (of a pair's shared points in ascending point order) that hypothesis ``h`` of pair
+    (k, l) draws under ``seed`` -- the first four of ``ransac_sample`` wherever n >= 8; the host instance of the function the
+    kernel runs."""
+    return _mvba.homography_sample(seed, k, l, h, n)
+
+
 def restrict_observations(pt_ptr, cam_idx, xy, point_ok, camera_ok):
     """The sub-list of the points and cameras marked: (pt_ptr, cam_idx, xy, point_ids, camera_ids) with points and cameras
     renumbered in ascending order of their old indices (``point_ids``, ``camera_ids``: the old index of each new one)."""
@@ -279,6 +310,41 @@ def pose_candidates(E):
     return out
 
 
+def homography_pose_candidates(Hn):
+    """The four (R (3, 3), t (3,), n (3,)) that a calibrated homography ``Hn`` = K_l^-1 H K_k allows, in the conventions of
+    ``pose_candidates`` (the first camera at the origin with identity pose, x_l ~ R^T (X - t), |t| = 1): Hn ~ R^T (I + t n^T / d) for
+    points on the plane n . X = d of the first camera's frame; ``n`` comes back scaled by 1 / d, d in units of the baseline
+    (|n| = 1 / d).  Hn is scaled so that its middle singular value is 1 and its determinant positive; the candidates come from
+    the eigen-decomposition of Hn^T Hn (Faugeras and Lustman 1988, in the form of Ma, Soatto, Kosecka and Sastry 2004, 5.3): the
+    two unit vectors u in span(v_1, v_3) whose length Hn keeps (every eigenvector with its largest component positive: the order
+    of the list is defined), each with the rotation that takes (v_2, u, v_2 x u) to their images,
+    in the order (R_a, +), (R_a, -), (R_b, +), (R_b, -) of (t, n)'s sign.  If sigma_1 - sigma_3 <= 1e-12 sigma_2 the homography
+    is a rotation (no baseline, any plane): the list is empty."""
+    Hn = np.asarray(Hn, np.float64)
+    if not np.isfinite(Hn).all():
+        return []
+    sv = np.linalg.svd(Hn, compute_uv=False)
+    if not sv[1] > 0 or sv[0] - sv[2] <= 1e-12 * sv[1]:
+        return []
+    Hn = Hn / sv[1] * (1.0 if np.linalg.det(Hn) > 0 else -1.0)
+    w, V = np.linalg.eigh(Hn.T @ Hn)  # ascending: sigma_3^2, 1, sigma_1^2
+    V = V * np.where(V[np.abs(V).argmax(axis=0), np.arange(3)] < 0, -1.0, 1.0)  # each eigenvector: largest component positive
+    v1, v2, v3 = V[:, 2], V[:, 1], V[:, 0]
+    s1, s3 = max(w[2], 1.0), min(w[0], 1.0)
+    a, b = np.sqrt(1.0 - s3), np.sqrt(s1 - 1.0)
+    out = []
+    for u in ((a * v1 + b * v3) / np.sqrt(s1 - s3), (a * v1 - b * v3) / np.sqrt(s1 - s3)):
+        U = np.stack([v2, u, np.cross(v2, u)], axis=1)
+        W = np.stack([Hn @ v2, Hn @ u, np.cross(Hn @ v2, Hn @ u)], axis=1)
+        Rrel, nn = W @ U.T, np.cross(v2, u)  # x_l ~ Rrel x_k + tau / d (n . x_k)
+        tau = (Hn - Rrel) @ nn
+        d = 1.0 / np.linalg.norm(tau)  # the plane's distance in units of the baseline
+        t = -Rrel.T @ tau * d
+        for sgn in (1.0, -1.0):
+            out.append((Rrel.T, sgn * t, sgn * nn / d))
+    return out
+
+
 def _pair_list(pt_ptr, cam_idx, xy, n_images, k, l, point_ok=None):
     """The two-camera sub-list over all points, or over those marked (the lower camera index becomes 0), the old index of each
     of its points and the positions of k and l in it."""
@@ -288,7 +354,8 @@ def _pair_list(pt_ptr, cam_idx, xy, n_images, k, l, point_ok=None):
     return ptr, cam, z, ids, (0, 1) if k < l else (1, 0)
 
 
-def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2, ransac_threshold=None, n_hypotheses: int = 512, seed: int = 0):
+def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2, ransac_threshold=None, n_hypotheses: int = 512, seed: int = 0,
+                  model: str = "fundamental", homography_threshold=None, planar_ratio: float = 0.8, _candidate=None, _fit=None):
     """(R (2, 3, 3), t (2, 3), X (N, 3), info): the pose of camera l = pair[1] relative to camera k = pair[0], which sits at the
     origin with identity pose; |t_l| = 1.  ``K`` (m, 3, 3) projects to the units of ``xy`` (raw image coordinates:
     ``engine_intrinsics(init_K)``, as for ``triangulate_points``).  F of the pair on the device, E = K_l^T F K_k, its four
@@ -300,19 +367,53 @@ def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2, ransac_thresh
     With ``ransac_threshold`` (a Sampson distance in the units of xy) F is ``robust_fundamental_matrices``'s, with
     ``n_hypotheses`` and ``seed``; only the pair's inliers are triangulated -- the other shared points stay NaN in X --, "more
     than half" counts against the inliers, the status may also be 2 or 4 of that function, and ``info`` gains ``inlier`` (N,)
-    bool and ``n_inliers``."""
+    bool and ``n_inliers``.
+    ``model``: "fundamental" is all of the above.  "homography" is the start for a PLANAR scene (a wall, a floor, a document,
+    flat ground from the air), where F is not determined and the route above returns a wrong pose without saying so: H of the
+    pair by ``robust_homographies`` with ``homography_threshold`` (a transfer distance in the units of xy; default:
+    ``ransac_threshold``; one of the two is needed), ``homography_pose_candidates(K_l^-1 H K_k)``, each triangulated on the device
+    over the H inliers; the winner has the most points in front of both cameras, on a tie the lower RMS reprojection residual
+    of those points, then the lower index.  "auto" (needs ``ransac_threshold``) runs both
+    robust fits and takes the homography when n_inliers_H >= ``planar_ratio`` x n_inliers_F (a plane's points all fit one H, a
+    general scene's do not: measured ratios >= 0.9 against <= 0.2), the route above otherwise.  ``info`` gains
+    ``model`` (the one taken) and, where H was fitted, ``H``, ``n_inliers_H``; on the homography route also ``candidates`` (the
+    list of (R, t, n)), ``plane`` (n, d: unit normal in camera k's frame and distance in units of the baseline),
+    ``n_front`` and ``rms`` per candidate, ``best_candidate`` (the index taken), ``ambiguous`` -- True when a second candidate puts as many points in front: the data
+    of two views cannot tell the two, ``bootstrap`` tries both -- and ``inlier``, ``n_inliers`` of H.  Status 3 is also returned
+    when the candidate list is empty (a pure rotation); 1, 2, 4 are then ``robust_homographies``'s.
+    (``_candidate`` and ``_fit`` are ``bootstrap``'s and this function's own: the index of the homography candidate to take instead
+    of the winner, 0 .. 3, and the robust F fit "auto" has already made, so that the fundamental route does not repeat it.)"""
     K = np.asarray(K, np.float64)
     k, l = int(pair[0]), int(pair[1])
     n = len(pt_ptr) - 1
+    if model not in ("fundamental", "homography", "auto"):
+        raise ValueError(f"relative_pose: model = {model!r} must be 'fundamental', 'homography' or 'auto'")
+    if model != "fundamental":
+        thr_h = ransac_threshold if homography_threshold is None else homography_threshold
+        if thr_h is None or (model == "auto" and ransac_threshold is None):
+            raise ValueError(f"relative_pose: model = {model!r} needs ransac_threshold" + (" or homography_threshold" if model == "homography" else ""))
+        Hm, hi = robust_homographies(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)], thr_h, n_hypotheses=n_hypotheses, seed=seed)
+        extra = {"H": Hm[0], "n_inliers_H": int(hi["n_inliers"][0])}
+        if model == "auto":
+            fit = robust_fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)], ransac_threshold, n_hypotheses=n_hypotheses, seed=seed)
+            fi = fit[1]
+            extra["n_inliers_F"] = int(fi["n_inliers"][0])
+            planar = hi["status"][0] == 0 and (fi["status"][0] != 0 or extra["n_inliers_H"] >= planar_ratio * extra["n_inliers_F"])
+            if not planar:
+                R, t, X, info = relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine, ransac_threshold, n_hypotheses, seed, _fit=fit)
+                info.update(extra, model="fundamental")
+                return R, t, X, info
+        return _homography_pose(pt_ptr, cam_idx, xy, K, k, l, n_refine, Hm[0], hi, extra, _candidate)
     inlier = None
     if ransac_threshold is None:
         F, fi = fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)])
     else:
-        F, fi = robust_fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)], ransac_threshold, n_hypotheses=n_hypotheses, seed=seed)
+        F, fi = _fit if _fit is not None else robust_fundamental_matrices(pt_ptr, cam_idx, xy, K.shape[0], [(k, l)], ransac_threshold,
+                                                                          n_hypotheses=n_hypotheses, seed=seed)
         inlier = fi["inlier"][0]
     R, t, X = np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
     info = {"n_front": np.zeros(4, np.int64), "status": int(fi["status"][0]), "F": F[0], "n_shared": int(fi["n_shared"][0]),
-            "two_view": fi["quality"][0], "quality": np.full((n, 3), np.nan)}
+            "two_view": fi["quality"][0], "quality": np.full((n, 3), np.nan), "model": "fundamental"}
     n_used = info["n_shared"]
     if inlier is not None:
         info["inlier"], info["n_inliers"] = inlier, int(fi["n_inliers"][0])
@@ -342,6 +443,54 @@ def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2, ransac_thresh
     return R, t, X, info
 
 
+def _homography_pose(pt_ptr, cam_idx, xy, K, k, l, n_refine, H, hi, extra, candidate):
+    """``relative_pose``'s homography route from the fitted H (``hi``: the info of ``robust_homographies`` for the one pair)."""
+    n = len(pt_ptr) - 1
+    R, t, X = np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
+    inlier = hi["inlier"][0]
+    info = {"n_front": np.zeros(4, np.int64), "rms": np.full(4, np.inf), "status": int(hi["status"][0]), "F": np.full((3, 3), np.nan),
+            "n_shared": int(hi["n_shared"][0]), "two_view": hi["quality"][0], "quality": np.full((n, 3), np.nan), "model": "homography",
+            "inlier": inlier, "n_inliers": extra["n_inliers_H"], "candidates": [], "plane": None, "ambiguous": False, **extra}
+    if info["status"] != 0:
+        return R, t, X, info
+    cands = homography_pose_candidates(np.linalg.solve(K[l], H) @ K[k])
+    info["candidates"] = cands
+    if not cands:
+        info["status"] = 3
+        return R, t, X, info
+    ptr, cam, z, ids, (ik, il) = _pair_list(pt_ptr, cam_idx, xy, K.shape[0], k, l, inlier)
+    K2, R2, t2 = np.empty((2, 3, 3)), np.empty((2, 3, 3)), np.zeros((2, 3))
+    K2[ik], K2[il], R2[ik] = K[k], K[l], np.eye(3)
+
+    def tri(c, nr):
+        R2[il], t2[il] = cands[c][:2]
+        Xc, q, st, _ = _mvba.triangulate(K2, R2, t2, ptr, cam, z, n_refine=nr)
+        return Xc, q, (st == 0) & (q[:, 1] > 0)
+
+    for c in range(4):
+        _, q, front = tri(c, 0)
+        info["n_front"][c] = front.sum()
+        if front.any():
+            info["rms"][c] = np.sqrt(np.mean(q[front, 0] ** 2))
+    best = min(range(4), key=lambda c: (-info["n_front"][c], info["rms"][c], c))
+    info["ambiguous"] = bool((info["n_front"] >= info["n_front"][best]).sum() > 1)
+    if candidate is not None:
+        if not 0 <= int(candidate) < len(cands):
+            raise ValueError(f"relative_pose: _candidate = {candidate} must be in 0 .. {len(cands) - 1}")
+        best = int(candidate)
+    if not 2 * info["n_front"][best] > info["n_inliers"]:
+        info["status"] = 3
+        return R, t, X, info
+    Xc, q, front = tri(best, n_refine)
+    X[ids[front]], info["quality"][ids[front]] = Xc[front], q[front]
+    R[0], t[0] = np.eye(3), 0.0
+    R[1], t[1] = cands[best][:2]
+    nn = cands[best][2]
+    info["plane"] = (nn / np.linalg.norm(nn), 1.0 / np.linalg.norm(nn))
+    info["best_candidate"] = best
+    return R, t, X, info
+
+
 def pose_for_intrinsics(P, K, c):
     """(R, t) of a camera with the GIVEN intrinsics ``K`` (3, 3; it projects to the units P projects to) that images the
     neighbourhood of the point ``c`` as the camera matrix ``P`` (3, 4) does: the rotation of ``decompose_projection``, and the
@@ -355,6 +504,26 @@ def pose_for_intrinsics(P, K, c):
     return R, c - R @ (d * np.array([(x[0] - K[0, 2]) / K[0, 0], (x[1] - K[1, 2]) / K[1, 1], 1.0]))
 
 
+def _usable_counts(pt_ptr, cam_idx, point_ok, n_images):
+    """(m,) the observations each camera has of the points marked."""
+    pt = np.repeat(np.arange(len(pt_ptr) - 1), np.diff(pt_ptr))
+    return np.bincount(np.asarray(cam_idx)[np.asarray(point_ok, bool)[pt]], minlength=n_images)
+
+
+def _registration_count(status, count, min_points):
+    """What a registration round of ``bootstrap`` would take: the largest ``count`` (inliers, or usable observations in the plain
+    form) among the cameras of status 0 that have at least ``min_points``; 0 if there is none."""
+    status, count = np.asarray(status), np.asarray(count)
+    good = (status == 0) & (count >= min_points)
+    return int(count[good].max()) if good.any() else 0
+
+
+def _other_start_wins(first, other, other_status):
+    """``bootstrap`` with an ambiguous start pair: the second candidate replaces the first only if it was triangulated (status 0)
+    and the camera registered from its points has MORE inliers; a tie keeps the first."""
+    return other_status == 0 and other > first
+
+
 def _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok):
     """``restrict_observations`` over all points and the cameras marked, without the observations ``obs_ok`` drops: (pt_ptr,
     cam_idx, xy, camera_ids)."""
@@ -366,7 +535,8 @@ def _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok):
 
 
 def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min_points: int = 12, max_rms=None, ransac_threshold=None,
-              n_hypotheses: int = 512, seed: int = 0, resect_threshold=None, triangulate_threshold=None, pose_threshold=None):
+              n_hypotheses: int = 512, seed: int = 0, resect_threshold=None, triangulate_threshold=None, pose_threshold=None,
+              model: str = "fundamental", homography_threshold=None, planar_ratio: float = 0.8):
     """(K, R, t, X, info): an initial estimate for ``BundleAdjuster.from_observations`` from feature tracks and rough
     intrinsics, by incremental reconstruction.  ``xy`` are raw image coordinates, ``init_K`` (m, 3, 3) the adjuster's
     [[f,0,u],[0,f,v],[0,0,f0]]; K comes back as ``init_K`` (no focal length is estimated).
@@ -396,6 +566,10 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     over the point's inliers).  Triangulation drops nothing for good: each round decides again over the cameras registered
     then.  ``relative_pose``'s own triangulation stays plain (two views have no redundancy).  ``info`` gains ``tri_inlier``
     (n_obs,) bool, the observations the final points were triangulated from.
+    ``model``, ``homography_threshold`` and ``planar_ratio`` go to every ``relative_pose``: "homography" or "auto" start a planar
+    scene from H.  Where the winning pair's two-view data cannot tell two pose candidates apart (``ambiguous``), the first
+    registration round is run under each of the two, and the one whose registered camera has more inliers (more usable
+    observations without a robust registration) starts; the first on a tie.  ``info`` gains ``model``, the one the start pair took.
     The output frame: camera 0 at the origin with identity pose, |t_1 - t_0| = 1.  ``info``: ``axis`` -- the gauge axis name
     whose component of t_1 is larger in magnitude: pass it to ``BundleAdjuster`` --, ``camera_ok`` (m,), ``point_ok`` (N,),
     ``order`` (the registration order), ``start_pair``.  Cameras and points not reached are NaN (``restrict_observations``
@@ -416,7 +590,10 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
         tried = [(int(start_pair[0]), int(start_pair[1]))]
     best = None
     for pair in tried:
-        if ransac_threshold is None:
+        if model != "fundamental":
+            R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed,
+                                           model=model, homography_threshold=homography_threshold, planar_ratio=planar_ratio)
+        elif ransac_threshold is None:
             R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair)
         else:
             R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed)
@@ -424,10 +601,34 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
             continue
         angle = float(np.nanmedian(pi["quality"][:, 2]))
         if best is None or angle > best[0]:
-            best = (angle, pair, R2, t2, X2)
+            best = (angle, pair, R2, t2, X2, pi)
     if best is None:
         raise ValueError(f"bootstrap: no start pair with status 0 among {tried}")
-    _, pair, R2, t2, X = best
+    _, pair, R2, t2, X, pi = best
+    if pi.get("ambiguous"):  # two views of a plane allow two poses: the third camera decides
+        nf = pi["n_front"]
+        other = [c for c in range(4) if c != pi["best_candidate"] and nf[c] >= nf[pi["best_candidate"]]][0]
+        Ro, to, Xo, po = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed,
+                                       model="homography", homography_threshold=homography_threshold, _candidate=other)
+
+        def first_round(Xc):
+            """The inliers (usable observations) of the camera the first registration round would take from these points."""
+            ok = np.isfinite(Xc).all(axis=1)
+            todo = np.nonzero(~np.isin(np.arange(m), pair))[0]
+            if len(todo) == 0:
+                return 0
+            if pose_threshold is not None:
+                ri = robust_pose_cameras(Xc, pt_ptr, cam_idx, xy, Kxy, pose_threshold, point_ok=ok, cameras=todo, n_hypotheses=n_hypotheses, seed=seed)[2]
+            elif resect_threshold is not None:
+                ri = robust_resect_cameras(Xc, pt_ptr, cam_idx, xy, m, resect_threshold, f0=f0, point_ok=ok, cameras=todo, n_hypotheses=n_hypotheses,
+                                           seed=seed)[3]
+            else:
+                st = resect_cameras(Xc, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=ok)[3]["status"][todo]
+                return _registration_count(st, _usable_counts(pt_ptr, cam_idx, ok, m)[todo], min_points)
+            return _registration_count(ri["status"], ri["n_inliers"], min_points)
+
+        if _other_start_wins(first_round(X), first_round(Xo), po["status"]):
+            R2, t2, X, pi = Ro, to, Xo, po
     R, t = np.full((m, 3, 3), np.nan), np.full((m, 3), np.nan)
     R[list(pair)], t[list(pair)] = R2, t2
     camera_ok = np.zeros(m, bool)
@@ -506,7 +707,7 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     R0, t0, s = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
     X, R, t = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s
     axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
-    info = {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order, "start_pair": pair}
+    info = {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order, "start_pair": pair, "model": pi["model"]}
     if drops:
         info["obs_ok"], info["inlier"] = obs_ok, inlier
     if triangulate_threshold is not None:

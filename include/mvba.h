@@ -354,6 +354,33 @@ int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_p
  * already drawn.  MVBA_ERR_BADARG: n outside 8 .. 2^31 - 1, a negative k, l or h. */
 int mvba_ransac_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx8);
 
+/* mvba_homography_robust: the homography of each pair, x_l ~ H x_k in the units of xy, by 4-point RANSAC -- the model for points
+ * in a plane (and for two cameras at one centre), where the fundamental matrix is not determined.  The argument list, the
+ * checks, the compaction, the normalisation over all shared points, the count table, the refit loop and the tiles are
+ * mvba_two_view_robust's (one host loop and one set of scoring, mask and refit kernels serve both); H stands where F stands.
+ *   hypothesis h: the 4 indices of mvba_homography_sample(seed, k, l, h, n); the homography of the four normalised
+ *     correspondences in closed form, in registers: per image B = [l1 p1, l2 p2, l3 p3] with [p1 p2 p3] l = p4 (p = (x, y, 1);
+ *     Cramer's rule), H^ = B_l adj(B_k), H^^-1 ~ B_k adj(B_l); degenerate if one of the four point triples of either image has
+ *     |det [p_a p_b p_c]| <= 1e-12 |p_a| |p_b| |p_c|, or an entry is not finite; H = T_l^-1 H^ T_k and its inverse likewise;
+ *   inlier test, without a division: with (u, v, w) = H (x_k, y_k, 1): w > 0 and (u - x_l w)^2 + (v - y_l w)^2 <= threshold^2 w^2,
+ *     and the same with H^-1 from l to k.  The sign of a matrix matters to w > 0: H and H^-1 each carry the sign that makes w
+ *     positive at the centroid of the points they are applied to (of all shared points for a hypothesis, of the fitted inliers
+ *     for a refit);
+ *   refit: the normalised DLT on the current inliers -- the 45 moments of the two rows per correspondence, the order-9
+ *     eigen-problem on the host, degenerate if lambda_2 <= 1e-12 lambda_max; no rank step; H^-1 for its mask pass is adj(H).
+ *     Kept while the inlier set does not shrink.  If none is kept, H is the best hypothesis's as the sample gives it.
+ * H [n_pairs][9]: |H|_F = 1, largest-magnitude entry positive.  quality [n_pairs][2]: the RMS of the inliers' symmetric transfer
+ * distance sqrt(mean((d_kl^2 + d_lk^2) / 2)) under the matrix that selected them; lambda_1 / lambda_2 of the last kept refit (0 if
+ * none).  status [n_pairs]: 0 ok; 1 fewer than 4 shared points; 2 every hypothesis degenerate (collinear points); 4 the best
+ * count is below 4.  Tiles: 128 MiB / (48 n_points + 160 n_hypotheses) pairs.  Two calls give bitwise-identical output. */
+int mvba_homography_robust(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy,
+                           int64_t n_obs, const int32_t *pairs, int32_t n_pairs, double threshold, int32_t n_hypotheses,
+                           uint64_t seed, int32_t n_refit, double *H, double *quality, int64_t *n_shared, int64_t *n_inliers,
+                           int32_t *best, uint8_t *inlier, int32_t *hyp_count, int32_t *status, double *timings_ms, int32_t device);
+/* Host only (no GPU needed): the 4 distinct indices below n that hypothesis h of pair (k, l) draws -- the first 4 of
+ * mvba_ransac_sample(seed, k, l, h, n) wherever n >= 8.  MVBA_ERR_BADARG: n outside 4 .. 2^31 - 1, a negative k, l or h. */
+int mvba_homography_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx4);
+
 /* mvba_resect_robust: mvba_resect with 6-point RANSAC in front of it.  X, the list, point_ok, the usable-observation rule and
  * the camera-major stable counting sort with chunks of 256 observations are mvba_resect's.  cameras [n_cameras]: the cameras to
  * solve (NULL: all of them, n_cameras = n_images); duplicates are legal; every per-camera output is indexed by the position in
