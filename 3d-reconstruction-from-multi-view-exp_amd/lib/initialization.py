@@ -17,9 +17,19 @@ csrc/mvba_pose_ransac.h): ``pose_threshold``.  A PLANAR scene ha
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import numpy as np
 
 from . import _mvba
+
+
+def _confidence(out, count_key, sample_size, n_hypotheses):
+    """1 - (1 - w^s)^H with w = n_inliers / ``out[count_key]``, the probability that one of H samples of s was all inliers; 0 where
+    the status is not 0."""
+    with np.errstate(all="ignore"):
+        w = out["n_inliers"] / np.maximum(out[count_key], 1)
+        return np.where(out["status"] == 0, 1.0 - (1.0 - w ** sample_size) ** int(n_hypotheses), 0.0)
 
 
 def triangulate_points(pt_ptr, cam_idx, xy, K, R, t, n_refine: int = 2):
@@ -58,10 +68,8 @@ def robust_triangulate_points(pt_ptr, cam_idx, xy, K, R, t, threshold, n_hypothe
     X = out.pop("X")
     m = np.asarray(K).shape[0]
     deg = np.full(len(X), m, np.int64) if pt_ptr is None else np.diff(np.asarray(pt_ptr, np.int64))
-    with np.errstate(all="ignore"):
-        w = out["n_inliers"] / np.maximum(deg, 1)
-        sampled = 1.0 - (1.0 - w ** 2) ** int(n_hypotheses)
-    out["confidence"] = np.where(out["status"] == 0, np.where(deg * (deg - 1) // 2 <= int(n_hypotheses), 1.0, sampled), 0.0)
+    exhaustive = (out["status"] == 0) & (deg * (deg - 1) // 2 <= int(n_hypotheses))
+    out["confidence"] = np.where(exhaustive, 1.0, _confidence({**out, "deg": deg}, "deg", 2, n_hypotheses))
     return X, out
 
 
@@ -147,9 +155,7 @@ def robust_resect_cameras(X, pt_ptr, cam_idx, xy, n_images: int, threshold, f0: 
     good = status == 0
     if good.any():
         K[good], R[good], t[good] = decompose_projection(P[good], f0)
-    with np.errstate(all="ignore"):
-        w = out["n_inliers"] / np.maximum(out["n_usable"], 1)
-        out["confidence"] = np.where(good, 1.0 - (1.0 - w ** 6) ** int(n_hypotheses), 0.0)
+    out["confidence"] = _confidence(out, "n_usable", 6, n_hypotheses)
     return K, R, t, out
 
 
@@ -179,9 +185,7 @@ def robust_pose_cameras(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=None, cam
     out = _mvba.pose_robust(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=point_ok, cameras=cameras, n_hypotheses=n_hypotheses, seed=seed,
                             n_refine=n_refine, n_refit=n_refit)
     R, t = out.pop("R"), out.pop("t")
-    with np.errstate(all="ignore"):
-        w = out["n_inliers"] / np.maximum(out["n_usable"], 1)
-        out["confidence"] = np.where(out["status"] == 0, 1.0 - (1.0 - w ** 4) ** int(n_hypotheses), 0.0)
+    out["confidence"] = _confidence(out, "n_usable", 4, n_hypotheses)
     return R, t, out
 
 
@@ -236,9 +240,7 @@ def robust_fundamental_matrices(pt_ptr, cam_idx, xy, n_images, pairs, threshold,
     out = _mvba.two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=n_hypotheses, seed=seed, n_refit=n_refit,
                                 return_inliers=return_inliers)
     F = out.pop("F")
-    with np.errstate(all="ignore"):
-        w = out["n_inliers"] / np.maximum(out["n_shared"], 1)
-        out["confidence"] = np.where(out["status"] == 0, 1.0 - (1.0 - w ** 8) ** int(n_hypotheses), 0.0)
+    out["confidence"] = _confidence(out, "n_shared", 8, n_hypotheses)
     return F, out
 
 
@@ -264,9 +266,7 @@ def robust_homographies(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypot
     out = _mvba.homography_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=n_hypotheses, seed=seed, n_refit=n_refit,
                                   return_inliers=return_inliers, return_counts=True)
     H = out.pop("H")
-    with np.errstate(all="ignore"):
-        w = out["n_inliers"] / np.maximum(out["n_shared"], 1)
-        out["confidence"] = np.where(out["status"] == 0, 1.0 - (1.0 - w ** 4) ** int(n_hypotheses), 0.0)
+    out["confidence"] = _confidence(out, "n_shared", 4, n_hypotheses)
     return H, out
 
 
@@ -345,13 +345,43 @@ def homography_pose_candidates(Hn):
     return out
 
 
-def _pair_list(pt_ptr, cam_idx, xy, n_images, k, l, point_ok=None):
-    """The two-camera sub-list over all points, or over those marked (the lower camera index becomes 0), the old index of each
-    of its points and the positions of k and l in it."""
-    cam_ok = np.zeros(n_images, bool)
+def _pair_candidates(pt_ptr, cam_idx, xy, K, k, l, cands, point_ok, n_used, n_refine):
+    """The candidate selection both routes of ``relative_pose`` share.  ``cands``: four (R, t, ...) of camera l with camera k at the
+    origin; ``point_ok`` (N,): the points to triangulate over (None: all); ``n_used``: the count "more than half" is measured
+    against.  The two-camera sub-list is built once (the lower camera index becomes 0) and every candidate triangulated on the
+    device without refinement: (n_front (4,) -- the points of status 0 and smallest depth > 0 --, rms (4,) -- the RMS reprojection
+    residual of those points, inf where there are none --, take).  ``take(c, R, t, X, quality)``: False if candidate c does not
+    put more than half of ``n_used`` in front of both cameras; otherwise it is triangulated again with ``n_refine`` and written
+    into R (2, 3, 3), t (2, 3) and, for the points in front, into X and quality (N, 3)."""
+    cam_ok = np.zeros(K.shape[0], bool)
     cam_ok[[k, l]] = True
     ptr, cam, z, ids, _ = restrict_observations(pt_ptr, cam_idx, xy, np.ones(len(pt_ptr) - 1, bool) if point_ok is None else point_ok, cam_ok)
-    return ptr, cam, z, ids, (0, 1) if k < l else (1, 0)
+    ik, il = (0, 1) if k < l else (1, 0)
+    K2, R2, t2 = np.empty((2, 3, 3)), np.empty((2, 3, 3)), np.zeros((2, 3))
+    K2[ik], K2[il], R2[ik] = K[k], K[l], np.eye(3)
+
+    def tri(c, nr):
+        R2[il], t2[il] = cands[c][:2]
+        Xc, q, st, _ = _mvba.triangulate(K2, R2, t2, ptr, cam, z, n_refine=nr)
+        return Xc, q, (st == 0) & (q[:, 1] > 0)
+
+    n_front, rms = np.zeros(4, np.int64), np.full(4, np.inf)
+    for c in range(4):
+        _, q, front = tri(c, 0)
+        n_front[c] = front.sum()
+        if front.any():
+            rms[c] = np.sqrt(np.mean(q[front, 0] ** 2))
+
+    def take(c, R, t, X, quality):
+        if not 2 * n_front[c] > n_used:
+            return False
+        Xc, q, front = tri(c, n_refine)
+        X[ids[front]], quality[ids[front]] = Xc[front], q[front]
+        R[0], t[0] = np.eye(3), 0.0
+        R[1], t[1] = cands[c][:2]
+        return True
+
+    return n_front, rms, take
 
 
 def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2, ransac_threshold=None, n_hypotheses: int = 512, seed: int = 0,
@@ -420,26 +450,9 @@ def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine: int = 2, ransac_thresh
         n_used = info["n_inliers"]
     if info["status"] != 0:
         return R, t, X, info
-    ptr, cam, z, ids, (ik, il) = _pair_list(pt_ptr, cam_idx, xy, K.shape[0], k, l, inlier)
-    K2, R2, t2 = np.empty((2, 3, 3)), np.empty((2, 3, 3)), np.zeros((2, 3))
-    K2[ik], K2[il], R2[ik] = K[k], K[l], np.eye(3)
-    cands = pose_candidates(K[l].T @ F[0] @ K[k])
-
-    def tri(c, nr):
-        R2[il], t2[il] = cands[c]
-        Xc, q, st, _ = _mvba.triangulate(K2, R2, t2, ptr, cam, z, n_refine=nr)
-        return Xc, q, (st == 0) & (q[:, 1] > 0)
-
-    for c in range(4):
-        info["n_front"][c] = tri(c, 0)[2].sum()
-    best = int(np.argmax(info["n_front"]))
-    if not 2 * info["n_front"][best] > n_used:
+    info["n_front"], _, take = _pair_candidates(pt_ptr, cam_idx, xy, K, k, l, pose_candidates(K[l].T @ F[0] @ K[k]), inlier, n_used, n_refine)
+    if not take(int(np.argmax(info["n_front"])), R, t, X, info["quality"]):
         info["status"] = 3
-        return R, t, X, info
-    Xc, q, front = tri(best, n_refine)
-    X[ids[front]], info["quality"][ids[front]] = Xc[front], q[front]
-    R[0], t[0] = np.eye(3), 0.0
-    R[1], t[1] = cands[best]
     return R, t, X, info
 
 
@@ -458,33 +471,16 @@ def _homography_pose(pt_ptr, cam_idx, xy, K, k, l, n_refine, H, hi, extra, candi
     if not cands:
         info["status"] = 3
         return R, t, X, info
-    ptr, cam, z, ids, (ik, il) = _pair_list(pt_ptr, cam_idx, xy, K.shape[0], k, l, inlier)
-    K2, R2, t2 = np.empty((2, 3, 3)), np.empty((2, 3, 3)), np.zeros((2, 3))
-    K2[ik], K2[il], R2[ik] = K[k], K[l], np.eye(3)
-
-    def tri(c, nr):
-        R2[il], t2[il] = cands[c][:2]
-        Xc, q, st, _ = _mvba.triangulate(K2, R2, t2, ptr, cam, z, n_refine=nr)
-        return Xc, q, (st == 0) & (q[:, 1] > 0)
-
-    for c in range(4):
-        _, q, front = tri(c, 0)
-        info["n_front"][c] = front.sum()
-        if front.any():
-            info["rms"][c] = np.sqrt(np.mean(q[front, 0] ** 2))
+    info["n_front"], info["rms"], take = _pair_candidates(pt_ptr, cam_idx, xy, K, k, l, cands, inlier, info["n_inliers"], n_refine)
     best = min(range(4), key=lambda c: (-info["n_front"][c], info["rms"][c], c))
     info["ambiguous"] = bool((info["n_front"] >= info["n_front"][best]).sum() > 1)
     if candidate is not None:
         if not 0 <= int(candidate) < len(cands):
             raise ValueError(f"relative_pose: _candidate = {candidate} must be in 0 .. {len(cands) - 1}")
         best = int(candidate)
-    if not 2 * info["n_front"][best] > info["n_inliers"]:
+    if not take(best, R, t, X, info["quality"]):
         info["status"] = 3
         return R, t, X, info
-    Xc, q, front = tri(best, n_refine)
-    X[ids[front]], info["quality"][ids[front]] = Xc[front], q[front]
-    R[0], t[0] = np.eye(3), 0.0
-    R[1], t[1] = cands[best][:2]
     nn = cands[best][2]
     info["plane"] = (nn / np.linalg.norm(nn), 1.0 / np.linalg.norm(nn))
     info["best_candidate"] = best
@@ -513,9 +509,57 @@ def _usable_counts(pt_ptr, cam_idx, point_ok, n_images):
 def _registration_count(status, count, min_points):
     """What a registration round of ``bootstrap`` would take: the largest ``count`` (inliers, or usable observations in the plain
     form) among the cameras of status 0 that have at least ``min_points``; 0 if there is none."""
+    i = _registration_pick(status, count, min_points)
+    return 0 if i is None else int(np.asarray(count)[i])
+
+
+def _registration_pick(status, count, min_points):
+    """The selection rule of a registration round: the index of the largest ``count`` among the cameras of status 0 that have at
+    least ``min_points``, the lowest on ties; None if there is none."""
     status, count = np.asarray(status), np.asarray(count)
     good = (status == 0) & (count >= min_points)
-    return int(count[good].max()) if good.any() else 0
+    return int(np.argmax(np.where(good, count, -1))) if good.any() else None
+
+
+# The registration step of ``bootstrap`` in its three forms, one signature: (X, point_ok, camera_ok, s) with ``s`` the constant
+# inputs -> None when no unregistered camera qualifies, otherwise (c, R_c, t_c, sel, count): the camera, its pose, the (n_obs,)
+# mask of the observations it was registered from, and the count that ranked it.
+def _register_plain(X, point_ok, camera_ok, s):
+    """``resect_cameras``; ranked by usable observations, registered from all of them."""
+    todo = np.nonzero(~camera_ok)[0]
+    ri = resect_cameras(X, s.pt_ptr, s.cam_idx, s.xy, s.m, f0=s.f0, point_ok=point_ok)[3]
+    usable = _usable_counts(s.pt_ptr, s.cam_idx, point_ok, s.m)[todo]
+    i = _registration_pick(ri["status"][todo], usable, s.min_points)
+    if i is None:
+        return None
+    c = int(todo[i])
+    sel = point_ok[s.pt] & (s.cam_idx == c)
+    return (c, *pose_for_intrinsics(ri["P"][c], s.Kxy[c], X[s.pt[sel]].mean(axis=0)), sel, int(usable[i]))
+
+
+def _register_resect(X, point_ok, camera_ok, s):
+    """``robust_resect_cameras`` on the unregistered cameras (``resect_threshold``); ranked by inliers, registered from them."""
+    todo = np.nonzero(~camera_ok)[0]
+    ri = robust_resect_cameras(X, s.pt_ptr, s.cam_idx, s.xy, s.m, s.threshold, f0=s.f0, point_ok=point_ok, cameras=todo,
+                               n_hypotheses=s.n_hypotheses, seed=s.seed)[3]
+    i = _registration_pick(ri["status"], ri["n_inliers"], s.min_points)
+    if i is None:
+        return None
+    c = int(todo[i])
+    sel = ri["inlier"] & (s.cam_idx == c)
+    return (c, *pose_for_intrinsics(ri["P"][i], s.Kxy[c], X[s.pt[sel]].mean(axis=0)), sel, int(ri["n_inliers"][i]))
+
+
+def _register_pose(X, point_ok, camera_ok, s):
+    """``robust_pose_cameras`` on the unregistered cameras (``pose_threshold``); ranked by inliers, the pose taken as returned."""
+    todo = np.nonzero(~camera_ok)[0]
+    Rp, tp, ri = robust_pose_cameras(X, s.pt_ptr, s.cam_idx, s.xy, s.Kxy, s.threshold, point_ok=point_ok, cameras=todo,
+                                     n_hypotheses=s.n_hypotheses, seed=s.seed)
+    i = _registration_pick(ri["status"], ri["n_inliers"], s.min_points)
+    if i is None:
+        return None
+    c = int(todo[i])
+    return c, Rp[i], tp[i], ri["inlier"] & (s.cam_idx == c), int(ri["n_inliers"][i])
 
 
 def _other_start_wins(first, other, other_status):
@@ -579,8 +623,14 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     pt_ptr, cam_idx = np.asarray(pt_ptr, np.int64), np.asarray(cam_idx, np.int32)
     xy, init_K = np.asarray(xy, np.float64).reshape(-1, 2), np.asarray(init_K, np.float64)
     m, n = init_K.shape[0], len(pt_ptr) - 1
-    drops = resect_threshold is not None or pose_threshold is not None  # (a robust registration drops observations for good)
+    pt = np.repeat(np.arange(n), np.diff(pt_ptr))
     Kxy = engine_intrinsics(init_K)
+    drops = resect_threshold is not None or pose_threshold is not None  # (a robust registration drops observations for good)
+    register = _register_pose if pose_threshold is not None else _register_resect if resect_threshold is not None else _register_plain
+    s = SimpleNamespace(pt_ptr=pt_ptr, cam_idx=cam_idx, xy=xy, pt=pt, m=m, Kxy=Kxy, f0=f0, min_points=min_points, n_hypotheses=n_hypotheses,
+                        seed=seed, threshold=pose_threshold if pose_threshold is not None else resect_threshold)
+    start = dict(ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed, model=model, homography_threshold=homography_threshold,
+                 planar_ratio=planar_ratio)
     if start_pair is None:
         count = covisibility(pt_ptr, cam_idx, m)
         ks, ls = np.triu_indices(m, 1)
@@ -590,13 +640,7 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
         tried = [(int(start_pair[0]), int(start_pair[1]))]
     best = None
     for pair in tried:
-        if model != "fundamental":
-            R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed,
-                                           model=model, homography_threshold=homography_threshold, planar_ratio=planar_ratio)
-        elif ransac_threshold is None:
-            R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair)
-        else:
-            R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed)
+        R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, **start)
         if pi["status"] != 0:
             continue
         angle = float(np.nanmedian(pi["quality"][:, 2]))
@@ -605,87 +649,32 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     if best is None:
         raise ValueError(f"bootstrap: no start pair with status 0 among {tried}")
     _, pair, R2, t2, X, pi = best
+    camera_ok = np.zeros(m, bool)
+    camera_ok[list(pair)] = True
     if pi.get("ambiguous"):  # two views of a plane allow two poses: the third camera decides
         nf = pi["n_front"]
         other = [c for c in range(4) if c != pi["best_candidate"] and nf[c] >= nf[pi["best_candidate"]]][0]
-        Ro, to, Xo, po = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, ransac_threshold=ransac_threshold, n_hypotheses=n_hypotheses, seed=seed,
-                                       model="homography", homography_threshold=homography_threshold, _candidate=other)
-
-        def first_round(Xc):
-            """The inliers (usable observations) of the camera the first registration round would take from these points."""
-            ok = np.isfinite(Xc).all(axis=1)
-            todo = np.nonzero(~np.isin(np.arange(m), pair))[0]
-            if len(todo) == 0:
-                return 0
-            if pose_threshold is not None:
-                ri = robust_pose_cameras(Xc, pt_ptr, cam_idx, xy, Kxy, pose_threshold, point_ok=ok, cameras=todo, n_hypotheses=n_hypotheses, seed=seed)[2]
-            elif resect_threshold is not None:
-                ri = robust_resect_cameras(Xc, pt_ptr, cam_idx, xy, m, resect_threshold, f0=f0, point_ok=ok, cameras=todo, n_hypotheses=n_hypotheses,
-                                           seed=seed)[3]
-            else:
-                st = resect_cameras(Xc, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=ok)[3]["status"][todo]
-                return _registration_count(st, _usable_counts(pt_ptr, cam_idx, ok, m)[todo], min_points)
-            return _registration_count(ri["status"], ri["n_inliers"], min_points)
-
-        if _other_start_wins(first_round(X), first_round(Xo), po["status"]):
+        Ro, to, Xo, po = relative_pose(pt_ptr, cam_idx, xy, Kxy, pair, **{**start, "model": "homography"}, _candidate=other)
+        # the count (inliers, usable observations) of the camera the first registration round would take from each start's points
+        first, second = (None if camera_ok.all() else register(Xc, np.isfinite(Xc).all(axis=1), camera_ok, s) for Xc in (X, Xo))
+        if _other_start_wins(0 if first is None else first[4], 0 if second is None else second[4], po["status"]):
             R2, t2, X, pi = Ro, to, Xo, po
     R, t = np.full((m, 3, 3), np.nan), np.full((m, 3), np.nan)
     R[list(pair)], t[list(pair)] = R2, t2
-    camera_ok = np.zeros(m, bool)
-    camera_ok[list(pair)] = True
     point_ok = np.isfinite(X).all(axis=1)
     reg_order = [pair[0], pair[1]]
-    pt = np.repeat(np.arange(n), np.diff(pt_ptr))
-    all_points = np.ones(n, bool)
-    if drops:
-        obs_ok, inlier = np.ones(len(cam_idx), bool), np.zeros(len(cam_idx), bool)
-    if triangulate_threshold is not None:
-        tri_inlier = point_ok[pt] & camera_ok[cam_idx]  # (until the first round: what relative_pose triangulated from)
+    obs_ok, inlier = np.ones(len(cam_idx), bool), np.zeros(len(cam_idx), bool)  # (all in use until a robust registration drops some)
+    tri_inlier = point_ok[pt] & camera_ok[cam_idx]  # (until the first round: what relative_pose triangulated from)
     while not camera_ok.all():
-        if pose_threshold is not None:
-            todo = np.nonzero(~camera_ok)[0]
-            Rp, tp, ri = robust_pose_cameras(X, pt_ptr, cam_idx, xy, Kxy, pose_threshold, point_ok=point_ok, cameras=todo,
-                                             n_hypotheses=n_hypotheses, seed=seed)
-            cand = np.nonzero((ri["status"] == 0) & (ri["n_inliers"] >= min_points))[0]
-            if len(cand) == 0:
-                break
-            i = int(cand[np.argmax(ri["n_inliers"][cand])])
-            c = int(todo[i])
-            sel = ri["inlier"] & (cam_idx == c)
-            obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)
-            inlier |= sel
-        elif resect_threshold is None:
-            ri = resect_cameras(X, pt_ptr, cam_idx, xy, m, f0=f0, point_ok=point_ok)[3]
-            usable = np.bincount(cam_idx[point_ok[pt]], minlength=m)
-            cand = np.nonzero(~camera_ok & (ri["status"] == 0) & (usable >= min_points))[0]
-            if len(cand) == 0:
-                break
-            c = int(cand[np.argmax(usable[cand])])
-            sel = point_ok[pt] & (cam_idx == c)
-            Pc = ri["P"][c]
-        else:
-            todo = np.nonzero(~camera_ok)[0]
-            ri = robust_resect_cameras(X, pt_ptr, cam_idx, xy, m, resect_threshold, f0=f0, point_ok=point_ok, cameras=todo,
-                                       n_hypotheses=n_hypotheses, seed=seed)[3]
-            cand = np.nonzero((ri["status"] == 0) & (ri["n_inliers"] >= min_points))[0]
-            if len(cand) == 0:
-                break
-            i = int(cand[np.argmax(ri["n_inliers"][cand])])
-            c = int(todo[i])
-            sel = ri["inlier"] & (cam_idx == c)
-            Pc = ri["P"][i]
-            obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)
-            inlier |= sel
-        if pose_threshold is not None:
-            R[c], t[c] = Rp[i], tp[i]
-        else:
-            R[c], t[c] = pose_for_intrinsics(Pc, Kxy[c], X[pt[sel]].mean(axis=0))
+        reg = register(X, point_ok, camera_ok, s)
+        if reg is None:
+            break
+        c, R[c], t[c], sel, _ = reg
+        obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)  # (its usable observations it was not registered from: none in the plain form)
+        inlier |= sel
         camera_ok[c] = True
         reg_order.append(c)
-        if not drops:
-            ptr, cam, z, _, ids = restrict_observations(pt_ptr, cam_idx, xy, all_points, camera_ok)
-        else:
-            ptr, cam, z, ids = _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok)
+        ptr, cam, z, ids = _kept_list(pt_ptr, cam_idx, xy, obs_ok, camera_ok)
         if triangulate_threshold is None:
             X, ti = triangulate_points(ptr, cam, z, Kxy[ids], R[ids], t[ids])
         else:
@@ -696,16 +685,15 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
             point_ok &= ti["quality"][:, 0] <= max_rms
         X[~point_ok] = np.nan
         if triangulate_threshold is not None:
-            kept = obs_ok & camera_ok[cam_idx] if drops else camera_ok[cam_idx]  # (the list just triangulated)
             tri_inlier = np.zeros(len(cam_idx), bool)
-            tri_inlier[np.nonzero(kept)[0]] = ti["inlier"]
+            tri_inlier[np.nonzero(obs_ok & camera_ok[cam_idx])[0]] = ti["inlier"]  # (the list just triangulated)
             tri_inlier &= point_ok[pt]
     for c in (0, 1):
         if not camera_ok[c]:
             raise ValueError(f"bootstrap: camera {c} could not be registered (the output frame is that of cameras 0 and 1); "
                              f"registered: {reg_order}")
-    R0, t0, s = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
-    X, R, t = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s
+    R0, t0, scale = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
+    X, R, t = ((X - t0) @ R0) / scale, R0.T @ R, ((t - t0) @ R0) / scale
     axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
     info = {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": reg_order, "start_pair": pair, "model": pi["model"]}
     if drops:

@@ -4,7 +4,9 @@ the definitions written out plainly on tests/_ransac_ref.py and tests/_twoview_r
 solution: the closed form / ``np.linalg.eigh`` the library states, and the SVD of the stacked rows.  Test infrastructure only."""
 import numpy as np
 
+import _bootstrap_ref as B
 import _init_ref as ref
+import _pose_ransac_ref as PR
 import _ransac_ref as RR
 import _twoview_ref as T
 
@@ -264,43 +266,21 @@ def homography_pose(pt_ptr, cam_idx, xy, K, pair, threshold, n_hyp=512, seed=0, 
     r = robust_homography(xk, xl, int(k), int(l), threshold, n_hyp, seed, 2, route)
     inlier = np.zeros(n, bool)
     inlier[ids[r["mask"]]] = True
-    R, t, X = np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
     info = {"n_front": np.zeros(4, np.int64), "rms": np.full(4, np.inf), "status": int(r["status"]), "H": r["H"], "n_shared": len(ids),
             "inlier": inlier, "n_inliers": r["n_inliers"], "n_inliers_H": r["n_inliers"], "quality": np.full((n, 3), np.nan),
             "model": "homography", "candidates": [], "ambiguous": False, "plane": None}
     if r["status"] != 0:
-        return R, t, X, info
+        return (*T.no_pose(n), info)
     ids, xk, xl = ids[r["mask"]], xk[r["mask"]], xl[r["mask"]]
     cands = pose_candidates(np.linalg.solve(K[l], r["H"]) @ K[k], "eigh" if route == "closed" else "svd")
     info["candidates"] = cands
     if not cands:
         info["status"] = 3
-        return R, t, X, info
-    K2, z = np.stack([K[k], K[l]]), np.stack([xk, xl], axis=1)
-
-    def tri(c, nr):
-        R2, t2 = np.stack([np.eye(3), cands[c][0]]), np.stack([np.zeros(3), cands[c][1]])
-        Xc, q, s = ref.triangulate(K2, R2, t2, None, None, z, nr)
-        return Xc, q, (s == 0) & (q[:, 1] > 0)
-
-    for c in range(4):
-        _, q, front = tri(c, 0)
-        info["n_front"][c] = front.sum()
-        if front.any():
-            info["rms"][c] = np.sqrt(np.mean(q[front, 0] ** 2))
-    best = min(range(4), key=lambda c: (-info["n_front"][c], info["rms"][c], c))
-    info["ambiguous"] = bool((info["n_front"] >= info["n_front"][best]).sum() > 1)
-    if candidate is not None:
-        best = candidate
-    if not 2 * info["n_front"][best] > len(ids):
-        info["status"] = 3
-        return R, t, X, info
-    Xc, q, front = tri(best, n_refine)
-    X[ids[front]], info["quality"][ids[front]] = Xc[front], q[front]
-    R[0], t[0] = np.eye(3), 0.0
-    R[1], t[1] = cands[best][:2]
-    nn = cands[best][2]
-    info.update(plane=(nn / np.linalg.norm(nn), 1.0 / np.linalg.norm(nn)), best_candidate=best)
+        return (*T.no_pose(n), info)
+    R, t, X, best = T.choose_candidate(K, pair, cands, ids, xk, xl, info, n_refine, by_rms=True, candidate=candidate)
+    if best is not None:
+        nn = cands[best][2]
+        info.update(plane=(nn / np.linalg.norm(nn), 1.0 / np.linalg.norm(nn)), best_candidate=best)
     return R, t, X, info
 
 
@@ -343,40 +323,34 @@ def hypothesis_counts(xk, xl, k, l, threshold, seed, hs, route="closed"):
     return np.where(ok, inl.sum(axis=1), -1).astype(np.int32), guard, pivot
 
 
-def bootstrap(pt_ptr, cam_idx, xy, K, threshold, pose_threshold, model="auto", n_hyp=512, seed=0, route="closed", **kw):
-    """(R, t, X, info) as lib.initialization.bootstrap(model=, ransac_threshold=threshold, pose_threshold=): tests/_pose_ransac_ref.py's
-    driver with its relative_pose replaced by the one above (its name for the call is swapped for the duration); with an
-    ``ambiguous`` start the driver runs under each of the two candidates and the one whose FIRST registered camera has more
-    inliers is kept (the first on a tie).  info gains ``model`` and ``ambiguous``."""
-    import _pose_ransac_ref as PR
+def bootstrap(pt_ptr, cam_idx, xy, K, threshold, pose_threshold, model="auto", n_hyp=512, seed=0, route="closed", start_pair=None, min_points=12,
+              max_rms=None, roots="roots", solver="chol"):
+    """(R, t, X, info) as lib.initialization.bootstrap(model=, ransac_threshold=threshold, pose_threshold=): the driver of
+    tests/_bootstrap_ref.py with the relative_pose above as its start step, tests/_pose_ransac_ref.py's registration and the plain
+    triangulation; with an ``ambiguous`` start the WHOLE driver runs under each of the two candidates and the one whose first
+    registered camera has more inliers is kept (the first on a tie) -- the library decides by the first round alone.  info gains
+    ``model`` and ``ambiguous``."""
+    register = PR.register_robust(pt_ptr, cam_idx, xy, K, pose_threshold, min_points, n_hyp, seed, roots, solver)
 
-    plain, seen = PR.T.relative_pose, {}
-
-    def start(cand):
-        def rp(a, b, c, d, pair):
+    def run(cand):
+        """The driver from relative_pose's own choice (None) or from candidate ``cand``, and the start step's info."""
+        def start(pair):
             if cand is None:
-                out = relative_pose(a, b, c, d, pair, threshold, model, n_hyp=n_hyp, seed=seed, route=route)
-            else:
-                out = homography_pose(a, b, c, d, pair, threshold, n_hyp, seed, route=route, candidate=cand)
-            seen[cand] = out[3]
-            return out
-        PR.T.relative_pose = rp
-        try:
-            return PR.bootstrap(pt_ptr, cam_idx, xy, K, pose_threshold, n_hyp, seed, **kw)
-        finally:
-            PR.T.relative_pose = plain
+                return relative_pose(pt_ptr, cam_idx, xy, K, pair, threshold, model, n_hyp=n_hyp, seed=seed, route=route)
+            return homography_pose(pt_ptr, cam_idx, xy, K, pair, threshold, n_hyp, seed, route=route, candidate=cand)
+        R, t, X, info, trace = B.bootstrap(pt_ptr, cam_idx, xy, K, start, register, T.triangulate_plain, start_pair, max_rms)
+        return (R, t, X, {key: info[key] for key in B.ROBUST_KEYS}), trace["start"][3]
 
-    out = start(None)
-    pi = seen[None]
+    out, pi = run(None)
     if pi.get("ambiguous"):
         nf, b = pi["n_front"], pi["best_candidate"]
         other = [c for c in range(4) if c != b and nf[c] >= nf[b]][0]
-        alt = start(other)
+        alt, po = run(other)
 
         def first(o):  # the inliers of the first camera registered after the pair
             c = o[3]["order"][2] if len(o[3]["order"]) > 2 else None
             return 0 if c is None else int((o[3]["inlier"] & (np.asarray(cam_idx) == c)).sum())
-        if seen[other]["status"] == 0 and first(alt) > first(out):
+        if po["status"] == 0 and first(alt) > first(out):
             out = alt
     out[3].update(model=pi["model"], ambiguous=bool(pi.get("ambiguous")))
     return out

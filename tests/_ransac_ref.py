@@ -4,6 +4,7 @@ out plainly on tests/_twoview_ref.py, with ``np.linalg.eigh`` (or the SVD of the
 Jacobi.  Test infrastructure only."""
 import numpy as np
 
+import _bootstrap_ref as B
 import _init_ref as ref
 import _twoview_ref as T
 
@@ -172,39 +173,17 @@ def relative_pose(pt_ptr, cam_idx, xy, K, pair, threshold, n_hyp=512, seed=0, n_
     r = robust_fundamental(xk, xl, int(k), int(l), threshold, n_hyp, seed, 2, linear)
     inlier = np.zeros(n, bool)
     inlier[ids[r["mask"]]] = True
-    R, t, X = np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
     info = {"n_front": np.zeros(4, np.int64), "status": int(r["status"]), "F": r["F"], "n_shared": len(ids), "inlier": inlier,
             "n_inliers": r["n_inliers"], "quality": np.full((n, 3), np.nan)}
     if r["status"] != 0:
-        return R, t, X, info
+        return (*T.no_pose(n), info)
     ids, xk, xl = ids[r["mask"]], xk[r["mask"]], xl[r["mask"]]
-    cands = T.pose_candidates(K[l].T @ r["F"] @ K[k])
-    K2, z = np.stack([K[k], K[l]]), np.stack([xk, xl], axis=1)
-
-    def tri(c, nr):
-        R2, t2 = np.stack([np.eye(3), cands[c][0]]), np.stack([np.zeros(3), cands[c][1]])
-        Xc, q, s = ref.triangulate(K2, R2, t2, None, None, z, nr)
-        return Xc, q, (s == 0) & (q[:, 1] > 0)
-
-    for c in range(4):
-        info["n_front"][c] = tri(c, 0)[2].sum()
-    best = int(np.argmax(info["n_front"]))
-    if not 2 * info["n_front"][best] > len(ids):
-        info["status"] = 3
-        return R, t, X, info
-    Xc, q, front = tri(best, n_refine)
-    X[ids[front]], info["quality"][ids[front]] = Xc[front], q[front]
-    R[0], t[0] = np.eye(3), 0.0
-    R[1], t[1] = cands[best]
-    return R, t, X, info
+    return (*T.choose_candidate(K, pair, T.pose_candidates(K[l].T @ r["F"] @ K[k]), ids, xk, xl, info, n_refine)[:3], info)
 
 
-def bootstrap(pt_ptr, cam_idx, xy, K, threshold, n_hyp=512, seed=0, linear="eigh", **kw):
-    """tests/_twoview_ref.py's bootstrap with every relative_pose replaced by the robust one above (the driver is otherwise
-    the same: its name for the call is swapped for the duration)."""
-    plain = T.relative_pose
-    T.relative_pose = lambda a, b, c, d, pair: relative_pose(a, b, c, d, pair, threshold, n_hyp, seed, linear=linear)
-    try:
-        return T.bootstrap(pt_ptr, cam_idx, xy, K, **kw)
-    finally:
-        T.relative_pose = plain
+def bootstrap(pt_ptr, cam_idx, xy, K, threshold, n_hyp=512, seed=0, linear="eigh", start_pair=None, min_points=12, max_rms=None):
+    """(R, t, X, info) as lib.initialization.bootstrap with ``ransac_threshold``: the driver of tests/_bootstrap_ref.py with the
+    robust relative_pose above as its start step, and tests/_twoview_ref.py's plain registration and triangulation."""
+    R, t, X, info, _ = B.bootstrap(pt_ptr, cam_idx, xy, K, lambda pair: relative_pose(pt_ptr, cam_idx, xy, K, pair, threshold, n_hyp, seed, linear=linear),
+                                   T.register_plain(pt_ptr, cam_idx, xy, K, min_points), T.triangulate_plain, start_pair, max_rms)
+    return R, t, X, {key: info[key] for key in B.PLAIN_KEYS}

@@ -4,6 +4,7 @@ tests/_init_ref.py (hartley, dlt_rows, resect_camera) and tests/_ransac_ref.py (
 matrix (or the SVD of the stacked rows) where the device runs its own Jacobi.  Test infrastructure only."""
 import numpy as np
 
+import _bootstrap_ref as B
 import _init_ref as ref
 import _ransac_ref as RR
 import _twoview_ref as T
@@ -161,50 +162,29 @@ def resect_robust(X, pt_ptr, cam_idx, xy, n_images, threshold, point_ok=None, ca
 
 
 def bootstrap(pt_ptr, cam_idx, xy, K, resect_threshold, n_hyp=512, seed=0, start_pair=None, min_points=12, max_rms=None, linear="eigh"):
-    """(R, t, X, info) as lib.initialization.bootstrap with ``resect_threshold`` (and no ``ransac_threshold``), on the host:
-    tests/_twoview_ref.py's bootstrap with the robust resection of the unregistered cameras in each round.  ``K`` (m, 3, 3)
-    projects to the units of xy; ``start_pair`` is required."""
-    xy = np.asarray(xy, np.float64).reshape(-1, 2)
-    m, n = len(K), len(pt_ptr) - 1
-    pair = tuple(start_pair)
-    R2, t2, X, pi = T.relative_pose(pt_ptr, cam_idx, xy, K, pair)
-    if pi["status"] != 0:
-        raise ValueError("no start pair")
-    R, t = np.full((m, 3, 3), np.nan), np.full((m, 3), np.nan)
-    R[list(pair)], t[list(pair)] = R2, t2
-    camera_ok = np.zeros(m, bool)
-    camera_ok[list(pair)] = True
-    point_ok = np.isfinite(X).all(axis=1)
-    order = list(pair)
-    pt = np.repeat(np.arange(n), np.diff(pt_ptr))
-    obs_ok, inlier = np.ones(len(cam_idx), bool), np.zeros(len(cam_idx), bool)
-    while not camera_ok.all():
+    """(R, t, X, info) as lib.initialization.bootstrap with ``resect_threshold`` (and no ``ransac_threshold``), on the host: the
+    driver of tests/_bootstrap_ref.py with the robust resection below as its registration step, and tests/_twoview_ref.py's plain
+    relative_pose and triangulation.  ``K`` (m, 3, 3) projects to the units of xy."""
+    R, t, X, info, _ = B.bootstrap(pt_ptr, cam_idx, xy, K, lambda pair: T.relative_pose(pt_ptr, cam_idx, xy, K, pair),
+                                   register_robust(pt_ptr, cam_idx, xy, K, resect_threshold, min_points, n_hyp, seed, linear), T.triangulate_plain,
+                                   start_pair, max_rms)
+    return R, t, X, {key: info[key] for key in B.ROBUST_KEYS}
+
+
+def register_robust(pt_ptr, cam_idx, xy, K, threshold, min_points, n_hyp=512, seed=0, linear="eigh"):
+    """The registration step of tests/_bootstrap_ref.py with ``resect_threshold``: the robust resection of the unregistered
+    cameras, ``most_inliers`` of them, the pose from ``pose_for_intrinsics`` at the centroid of its inlier points."""
+    pt_ptr, cam_idx, xy = np.asarray(pt_ptr), np.asarray(cam_idx), np.asarray(xy, np.float64).reshape(-1, 2)
+    pt = np.repeat(np.arange(len(pt_ptr) - 1), np.diff(pt_ptr))
+
+    def register(X, point_ok, camera_ok):
         todo = np.nonzero(~camera_ok)[0]
-        ri = resect_robust(np.where(point_ok[:, None], X, 0.0), pt_ptr, cam_idx, xy, m, resect_threshold, point_ok=point_ok, cameras=todo,
+        ri = resect_robust(np.where(point_ok[:, None], X, 0.0), pt_ptr, cam_idx, xy, len(K), threshold, point_ok=point_ok, cameras=todo,
                            n_hyp=n_hyp, seed=seed, n_refit=2, linear=linear)
-        cand = np.nonzero((ri["status"] == 0) & (ri["n_inliers"] >= min_points))[0]
-        if len(cand) == 0:
-            break
-        i = int(cand[np.argmax(ri["n_inliers"][cand])])
-        c = int(todo[i])
-        sel = ri["inlier"] & (cam_idx == c)
-        obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)
-        inlier |= sel
-        R[c], t[c] = T.pose_for_intrinsics(ri["P"][i], K[c], X[pt[sel]].mean(axis=0))
-        camera_ok[c] = True
-        order.append(c)
-        keep = obs_ok & camera_ok[cam_idx]
-        ptr = np.concatenate([[0], np.cumsum(np.bincount(pt[keep], minlength=n))]).astype(np.int64)
-        ids = np.nonzero(camera_ok)[0]
-        X, q, s = ref.triangulate(K[ids], R[ids], t[ids], ptr, (np.cumsum(camera_ok) - 1)[cam_idx[keep]].astype(np.int32), xy[keep], 2)
-        point_ok = (s == 0) & (q[:, 1] > 0)
-        if max_rms is not None:
-            point_ok &= q[:, 0] <= max_rms
-        X[~point_ok] = np.nan
-    for c in (0, 1):
-        if not camera_ok[c]:
-            raise ValueError(f"camera {c} could not be registered")
-    R0, t0, s = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
-    X, R, t = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s
-    axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
-    return R, t, X, {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "obs_ok": obs_ok, "inlier": inlier, "order": order, "start_pair": pair}
+        pick = B.most_inliers(ri, todo, cam_idx, point_ok[pt], min_points)
+        if pick is None:
+            return None
+        i, c, sel, dropped = pick
+        return (c, *T.pose_for_intrinsics(ri["P"][i], K[c], X[pt[sel]].mean(axis=0)), sel, dropped)
+
+    return register

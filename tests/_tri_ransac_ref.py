@@ -5,6 +5,7 @@ Two host routes: ``linear`` = "eigh" or "svd" for the refits' linear step (as ev
 M^-1 by the adjugate) or "solve" (``np.linalg.solve``) for the viewing rays of the midpoint.  Test infrastructure only."""
 import numpy as np
 
+import _bootstrap_ref as B
 import _init_ref as ref
 import _ransac_ref as RR
 import _resect_ransac_ref as QR
@@ -203,77 +204,34 @@ def triangulate_robust(K, R, t, pt_ptr, cam_idx, xy, threshold, n_hyp=64, seed=0
 
 def bootstrap(pt_ptr, cam_idx, xy, K, ransac_threshold=None, resect_threshold=None, triangulate_threshold=None, n_hyp=512, seed=0,
               start_pair=None, min_points=12, max_rms=None, linear="eigh", rays="adjugate"):
-    """(R, t, X, info) as lib.initialization.bootstrap with any of its three thresholds, on the host: the robust references of
-    tests/_ransac_ref.py (the first F) and tests/_resect_ransac_ref.py (every later camera) and the robust triangulation above in
-    each round.  ``K`` (m, 3, 3) projects to the units of xy; ``start_pair`` is required.  ``info`` also has ``margin``: the
+    """(R, t, X, info) as lib.initialization.bootstrap with any of its three thresholds, on the host: the driver of
+    tests/_bootstrap_ref.py with, for each threshold given, the robust step of tests/_ransac_ref.py (the first F),
+    tests/_resect_ransac_ref.py (every later camera) and the robust triangulation above, and tests/_twoview_ref.py's plain step
+    otherwise.  ``K`` (m, 3, 3) projects to the units of xy.  ``info`` also has ``margin``: the
     smallest one over every robust triangulation of the run (inf without ``triangulate_threshold``), and ``alt_X`` (N, a, 3): the
     last round's points with the other outcomes of tied Gauss-Newton decisions (refine_candidates), in the output frame."""
-    xy = np.asarray(xy, np.float64).reshape(-1, 2)
-    m, n = len(K), len(pt_ptr) - 1
-    pair = tuple(start_pair)
     if ransac_threshold is None:
-        R2, t2, X, pi = T.relative_pose(pt_ptr, cam_idx, xy, K, pair)
+        def start(pair):
+            return T.relative_pose(pt_ptr, cam_idx, xy, K, pair)
     else:
-        R2, t2, X, pi = RR.relative_pose(pt_ptr, cam_idx, xy, K, pair, ransac_threshold, n_hyp, seed, linear=linear)
-    if pi["status"] != 0:
-        raise ValueError("no start pair")
-    R, t = np.full((m, 3, 3), np.nan), np.full((m, 3), np.nan)
-    R[list(pair)], t[list(pair)] = R2, t2
-    camera_ok = np.zeros(m, bool)
-    camera_ok[list(pair)] = True
-    point_ok = np.isfinite(X).all(axis=1)
-    order = list(pair)
-    pt = np.repeat(np.arange(n), np.diff(pt_ptr))
-    obs_ok, inlier = np.ones(len(cam_idx), bool), np.zeros(len(cam_idx), bool)
-    tri_inlier, margin, alt = point_ok[pt] & camera_ok[cam_idx], np.inf, X[:, None, :]
-    while not camera_ok.all():
-        Xz = np.where(point_ok[:, None], X, 0.0)
-        if resect_threshold is None:
-            P, _, st = ref.resect(Xz, pt_ptr, cam_idx, xy, m, point_ok=point_ok)
-            usable = np.bincount(cam_idx[point_ok[pt]], minlength=m)
-            cand = np.nonzero(~camera_ok & (st == 0) & (usable >= min_points))[0]
-            if len(cand) == 0:
-                break
-            c = int(cand[np.argmax(usable[cand])])
-            sel, Pc = point_ok[pt] & (cam_idx == c), P[c].reshape(3, 4)
-        else:
-            todo = np.nonzero(~camera_ok)[0]
-            ri = QR.resect_robust(Xz, pt_ptr, cam_idx, xy, m, resect_threshold, point_ok=point_ok, cameras=todo, n_hyp=n_hyp, seed=seed,
-                                  n_refit=2, linear=linear)
-            cand = np.nonzero((ri["status"] == 0) & (ri["n_inliers"] >= min_points))[0]
-            if len(cand) == 0:
-                break
-            i = int(cand[np.argmax(ri["n_inliers"][cand])])
-            c = int(todo[i])
-            sel, Pc = ri["inlier"] & (cam_idx == c), ri["P"][i]
-            obs_ok &= ~((cam_idx == c) & point_ok[pt] & ~sel)
-            inlier |= sel
-        R[c], t[c] = T.pose_for_intrinsics(Pc, K[c], X[pt[sel]].mean(axis=0))
-        camera_ok[c] = True
-        order.append(c)
-        keep = obs_ok & camera_ok[cam_idx]
-        ptr = np.concatenate([[0], np.cumsum(np.bincount(pt[keep], minlength=n))]).astype(np.int64)
-        ids, cam = np.nonzero(camera_ok)[0], (np.cumsum(camera_ok) - 1)[cam_idx[keep]].astype(np.int32)
+        def start(pair):
+            return RR.relative_pose(pt_ptr, cam_idx, xy, K, pair, ransac_threshold, n_hyp, seed, linear=linear)
+    if resect_threshold is None:
+        register = T.register_plain(pt_ptr, cam_idx, xy, K, min_points)
+    else:
+        register = QR.register_robust(pt_ptr, cam_idx, xy, K, resect_threshold, min_points, n_hyp, seed, linear)
+
+    def triangulate(Kr, Rr, tr, ptr, cam, z):
+        """With the threshold the robust triangulation above; ``extras``: the points before the keep rule with the other outcomes
+        of tied decisions, and the round's margin."""
         if triangulate_threshold is None:
-            X, q, s = ref.triangulate(K[ids], R[ids], t[ids], ptr, cam, xy[keep], 2)
-            used, alt = np.ones(int(keep.sum()), bool), X[:, None, :]
-        else:
-            ti = triangulate_robust(K[ids], R[ids], t[ids], ptr, cam, xy[keep], triangulate_threshold, min(n_hyp, MAX_HYP), seed, 2, 2,
-                                    linear, rays)
-            X, q, s, used, alt = ti["X"].copy(), ti["quality"], ti["status"], ti["inlier"], ti["alt_X"]
-            margin = min(margin, ti["margin"].min())
-        point_ok = (s == 0) & (q[:, 1] > 0)
-        if max_rms is not None:
-            point_ok &= q[:, 0] <= max_rms
-        X[~point_ok] = np.nan
-        tri_inlier = np.zeros(len(cam_idx), bool)
-        tri_inlier[np.nonzero(keep)[0]] = used
-        tri_inlier &= point_ok[pt]
-    for c in (0, 1):
-        if not camera_ok[c]:
-            raise ValueError(f"camera {c} could not be registered")
-    R0, t0, s = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
-    X, R, t, alt = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s, ((alt - t0) @ R0) / s
-    axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
-    return R, t, X, {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "obs_ok": obs_ok, "inlier": inlier, "tri_inlier": tri_inlier,
-                     "order": order, "start_pair": pair, "margin": margin, "alt_X": alt}
+            X, q, s, used, _ = T.triangulate_plain(Kr, Rr, tr, ptr, cam, z)
+            return X, q, s, used, {"alt_X": X[:, None, :]}  # (a view: it gets the keep rule's NaN with X)
+        ti = triangulate_robust(Kr, Rr, tr, ptr, cam, z, triangulate_threshold, min(n_hyp, MAX_HYP), seed, 2, 2, linear, rays)
+        return ti["X"].copy(), ti["quality"], ti["status"], ti["inlier"], {"alt_X": ti["alt_X"], "margin": ti["margin"].min()}
+
+    R, t, X, info, trace = B.bootstrap(pt_ptr, cam_idx, xy, K, start, register, triangulate, start_pair, max_rms)
+    R0, t0, s = trace["frame"]
+    alt = trace["extras"][-1]["alt_X"] if trace["extras"] else trace["start"][2][:, None, :]
+    info.update(margin=min([np.inf] + [e["margin"] for e in trace["extras"] if "margin" in e]), alt_X=((alt - t0) @ R0) / s)
+    return R, t, X, info

@@ -1,8 +1,10 @@
 """NumPy restatement of the two-view entry points (include/mvba.h: mvba_covisibility, mvba_two_view) and of the driver built
 on them (lib/initialization.py: relative_pose, bootstrap) -- the definitions written out plainly, with ``np.linalg.eigh`` where
-the library runs its Jacobi, and tests/_init_ref.py where the driver triangulates and resects.  Test infrastructure only."""
+the library runs its Jacobi, tests/_init_ref.py where the driver triangulates and resects, and the driver's control flow in
+tests/_bootstrap_ref.py.  Test infrastructure only."""
 import numpy as np
 
+import _bootstrap_ref as B
 import _init_ref as ref
 
 REL_PIVOT = 1e-12
@@ -110,22 +112,17 @@ def restrict(pt_ptr, cam_idx, xy, point_ok, camera_ok):
     return np.concatenate([[0], np.cumsum(deg)]).astype(np.int64), cam, xy[keep], pid, cid
 
 
-def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine=2, F=None):
-    """(R (2, 3, 3), t (2, 3), X (N, 3), info) as lib.initialization.relative_pose; ``F``: use this matrix."""
+def choose_candidate(K, pair, cands, ids, xk, xl, info, n_refine, by_rms=False, candidate=None):
+    """(R (2, 3, 3), t (2, 3), X (N, 3), best): the candidate selection of every relative_pose reference.  ``cands``: four
+    (R, t, ...) of camera l = pair[1] with camera k at the origin, each triangulated without refinement over the points ``ids``
+    alone (dense: camera 0 = k with ``xk``, 1 = l with ``xl``); info["n_front"] gets the points of status 0 and smallest depth > 0.
+    The winner is the first with the most of them; with ``by_rms`` (the homography's rule) the smallest (-n_front, rms, index),
+    info["rms"] and info["ambiguous"] -- a second candidate has as many -- are set, and ``candidate`` takes that one instead.  It
+    must put more than half of ``ids`` in front -- otherwise info["status"] = 3, best = None and all is NaN -- and is triangulated
+    again with ``n_refine`` into X and info["quality"]."""
     k, l = pair
-    n, m = len(pt_ptr) - 1, len(K)
-    xy = np.asarray(xy, np.float64).reshape(-1, 2)
-    ids, xk, xl = shared(pt_ptr, cam_idx, xy, k, l)
-    if F is None:
-        F, _, st = fundamental(xk, xl)
-    else:
-        st = 0
-    R, t, X = np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
-    info = {"n_front": np.zeros(4, np.int64), "status": int(st), "F": F, "n_shared": len(ids), "quality": np.full((n, 3), np.nan)}
-    if st != 0:
-        return R, t, X, info
-    cands = pose_candidates(K[l].T @ F @ K[k])
-    K2, z = np.stack([K[k], K[l]]), np.stack([xk, xl], axis=1)  # the shared points alone, dense: camera 0 = k, 1 = l
+    R, t, X = no_pose(len(info["quality"]))
+    K2, z = np.stack([K[k], K[l]]), np.stack([xk, xl], axis=1)
 
     def tri(c, nr):
         R2, t2 = np.stack([np.eye(3), cands[c][0]]), np.stack([np.zeros(3), cands[c][1]])
@@ -133,16 +130,45 @@ def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine=2, F=None):
         return Xc, q, (s == 0) & (q[:, 1] > 0)
 
     for c in range(4):
-        info["n_front"][c] = tri(c, 0)[2].sum()
+        _, q, front = tri(c, 0)
+        info["n_front"][c] = front.sum()
+        if by_rms and front.any():
+            info["rms"][c] = np.sqrt(np.mean(q[front, 0] ** 2))
     best = int(np.argmax(info["n_front"]))
+    if by_rms:
+        best = min(range(4), key=lambda c: (-info["n_front"][c], info["rms"][c], c))
+        info["ambiguous"] = bool((info["n_front"] >= info["n_front"][best]).sum() > 1)
+        if candidate is not None:
+            best = candidate
     if not 2 * info["n_front"][best] > len(ids):
         info["status"] = 3
-        return R, t, X, info
+        return R, t, X, None
     Xc, q, front = tri(best, n_refine)
     X[ids[front]], info["quality"][ids[front]] = Xc[front], q[front]
     R[0], t[0] = np.eye(3), 0.0
-    R[1], t[1] = cands[best]
-    return R, t, X, info
+    R[1], t[1] = cands[best][:2]
+    return R, t, X, best
+
+
+def no_pose(n):
+    """(R, t, X) of a relative pose that was not found: NaN."""
+    return np.full((2, 3, 3), np.nan), np.full((2, 3), np.nan), np.full((n, 3), np.nan)
+
+
+def relative_pose(pt_ptr, cam_idx, xy, K, pair, n_refine=2, F=None):
+    """(R (2, 3, 3), t (2, 3), X (N, 3), info) as lib.initialization.relative_pose; ``F``: use this matrix."""
+    k, l = pair
+    n = len(pt_ptr) - 1
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    ids, xk, xl = shared(pt_ptr, cam_idx, xy, k, l)
+    if F is None:
+        F, _, st = fundamental(xk, xl)
+    else:
+        st = 0
+    info = {"n_front": np.zeros(4, np.int64), "status": int(st), "F": F, "n_shared": len(ids), "quality": np.full((n, 3), np.nan)}
+    if st != 0:
+        return (*no_pose(n), info)
+    return (*choose_candidate(K, pair, pose_candidates(K[l].T @ F @ K[k]), ids, xk, xl, info, n_refine)[:3], info)
 
 
 def pose_for_intrinsics(P, K, c):
@@ -164,58 +190,37 @@ def pose_for_intrinsics(P, K, c):
 
 
 def bootstrap(pt_ptr, cam_idx, xy, K, start_pair=None, min_points=12, max_rms=None):
-    """(R, t, X, info) as lib.initialization.bootstrap, on the host; ``K`` (m, 3, 3) projects to the units of xy."""
-    xy = np.asarray(xy, np.float64).reshape(-1, 2)
-    m, n = len(K), len(pt_ptr) - 1
-    if start_pair is None:
-        count = covisibility(pt_ptr, cam_idx, m)
-        ks, ls = np.triu_indices(m, 1)
-        order = np.argsort(-count[ks, ls], kind="stable")
-        tried = [(int(ks[i]), int(ls[i])) for i in order if count[ks[i], ls[i]] >= 8][:16]
-    else:
-        tried = [tuple(start_pair)]
-    best = None
-    for pair in tried:
-        R2, t2, X2, pi = relative_pose(pt_ptr, cam_idx, xy, K, pair)
-        if pi["status"] == 0:
-            angle = float(np.nanmedian(pi["quality"][:, 2]))
-            if best is None or angle > best[0]:
-                best = (angle, pair, R2, t2, X2)
-    if best is None:
-        raise ValueError("no start pair")
-    _, pair, R2, t2, X = best
-    R, t = np.full((m, 3, 3), np.nan), np.full((m, 3), np.nan)
-    R[list(pair)], t[list(pair)] = R2, t2
-    camera_ok = np.zeros(m, bool)
-    camera_ok[list(pair)] = True
-    point_ok = np.isfinite(X).all(axis=1)
-    order = list(pair)
-    pt = np.repeat(np.arange(n), np.diff(pt_ptr))
-    seen = np.zeros((n, m), bool)
-    seen[pt, cam_idx] = True
-    while not camera_ok.all():
-        P, _, st = ref.resect(np.where(point_ok[:, None], X, 0.0), pt_ptr, cam_idx, xy, m, point_ok=point_ok)
-        usable = np.bincount(cam_idx[point_ok[pt]], minlength=m)
+    """(R, t, X, info) as lib.initialization.bootstrap without a threshold, on the host: the driver of tests/_bootstrap_ref.py with
+    the plain form of each step; ``K`` (m, 3, 3) projects to the units of xy."""
+    R, t, X, info, _ = B.bootstrap(pt_ptr, cam_idx, xy, K, lambda pair: relative_pose(pt_ptr, cam_idx, xy, K, pair),
+                                   register_plain(pt_ptr, cam_idx, xy, K, min_points), triangulate_plain, start_pair, max_rms)
+    return R, t, X, {key: info[key] for key in B.PLAIN_KEYS}
+
+
+def register_plain(pt_ptr, cam_idx, xy, K, min_points):
+    """The registration step of tests/_bootstrap_ref.py in its plain form: every camera resected from the current points; the
+    unregistered one of status 0 with the most usable observations (at least ``min_points``, the lowest index on ties) is taken,
+    its pose from ``pose_for_intrinsics`` at the centroid of the points it sees.  It verifies nothing: ``dropped`` is None."""
+    pt_ptr, cam_idx, xy = np.asarray(pt_ptr), np.asarray(cam_idx), np.asarray(xy, np.float64).reshape(-1, 2)
+    pt = np.repeat(np.arange(len(pt_ptr) - 1), np.diff(pt_ptr))
+
+    def register(X, point_ok, camera_ok):
+        P, _, st = ref.resect(np.where(point_ok[:, None], X, 0.0), pt_ptr, cam_idx, xy, len(K), point_ok=point_ok)
+        usable = np.bincount(cam_idx[point_ok[pt]], minlength=len(K))
         cand = np.nonzero(~camera_ok & (st == 0) & (usable >= min_points))[0]
         if len(cand) == 0:
-            break
+            return None
         c = int(cand[np.argmax(usable[cand])])
-        R[c], t[c] = pose_for_intrinsics(P[c].reshape(3, 4), K[c], X[point_ok & seen[:, c]].mean(axis=0))
-        camera_ok[c] = True
-        order.append(c)
-        ptr, cam, z, _, ids = restrict(pt_ptr, cam_idx, xy, np.ones(n, bool), camera_ok)
-        X, q, s = ref.triangulate(K[ids], R[ids], t[ids], ptr, cam, z, 2)
-        point_ok = (s == 0) & (q[:, 1] > 0)
-        if max_rms is not None:
-            point_ok &= q[:, 0] <= max_rms
-        X[~point_ok] = np.nan
-    for c in (0, 1):
-        if not camera_ok[c]:
-            raise ValueError(f"camera {c} could not be registered")
-    R0, t0, s = R[0].copy(), t[0].copy(), np.linalg.norm(t[1] - t[0])
-    X, R, t = ((X - t0) @ R0) / s, R0.T @ R, ((t - t0) @ R0) / s
-    axis = "x-right_z-forward" if abs(t[1, 0]) >= abs(t[1, 1]) else "x-up_z-forward"
-    return R, t, X, {"axis": axis, "camera_ok": camera_ok, "point_ok": point_ok, "order": order, "start_pair": pair}
+        sel = point_ok[pt] & (cam_idx == c)
+        return (c, *pose_for_intrinsics(P[c].reshape(3, 4), K[c], X[pt[sel]].mean(axis=0)), sel, None)
+
+    return register
+
+
+def triangulate_plain(K, R, t, ptr, cam, xy):
+    """The triangulation step of tests/_bootstrap_ref.py in its plain form: every observation of the list is used."""
+    X, q, s = ref.triangulate(K, R, t, ptr, cam, xy, 2)
+    return X, q, s, np.ones(len(cam), bool), {}
 
 
 def rms_reprojection(K, R, t, X, pt_ptr, cam_idx, xy):
