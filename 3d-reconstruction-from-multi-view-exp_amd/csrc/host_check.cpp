@@ -1,4 +1,4 @@
-// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch) and the host logic of a RANSAC
+// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas) and the host logic of a RANSAC
 // round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*) on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
 #include <cmath>
@@ -86,6 +86,43 @@ int main() {
     CHECK(d.own == buf.data() + DepthScratch::prefix(blocks, m));
     for (double *p = d.Epart; p < d.own + 5; ++p) *p = 1.0;  // (every double of it is the vector's)
     CHECK(DepthScratch().own == nullptr);
+  }
+  {  // the SVD workspace's LDS formulas at the largest arguments their routes admit, each within the limit its kernel is raised to
+    for (size_t el : {(size_t)4, (size_t)8}) {
+      for (int n = 1; n <= 32; ++n) CHECK(gram_mode(n) >= 1 && gram_pairs(n) == gram_mode(n) && gram_fused_lds(el, n) <= LDS_DEFAULT);
+      CHECK(gram_fused_lds(el, 32) == std::max<size_t>(el * 128 * 32, 3 * 8192));
+      CHECK(rotate_rows_lds(el, 32) <= ROTATE_LDS_MAX);  // the streaming form of mvsvd_run: n <= 32; the wide path: WB fp64 columns
+      CHECK(project_lds(el, JACOBI_MAX) <= PROJECT_LDS_MAX && project_lds(el, PC) == project_lds(el, JACOBI_MAX) - 5 * sizeof(double) * (JACOBI_MAX - PC));
+      int cols = 1;  // the widest rows that go through tiles
+      while (tile_fits(el, cols + 1)) ++cols;
+      CHECK(cols == (el == 8 ? 59 : 119) && !tile_fits(el, cols + 1) && row_tile_lds(el, cols) <= TILE_MAX_BYTES && row_tile_lds(el, cols) <= DEPTH_LDS_MAX);
+      int mt = 1;  // the most images whose depth update is tiled
+      while (depth_tiled(el, mt + 1)) ++mt;
+      CHECK(mt == cols / 4 && !depth_tiled(el, mt + 1));
+      CHECK(depth_primary_lds(el, mt) <= DEPTH_LDS_MAX && dual_apply_lds(el, mt) <= DEPTH_LDS_MAX);
+      CHECK(dual_apply_lds(el, mt) == 24 * 8 * (size_t)mt + row_tile_lds(el, 4 * mt) + 16);
+    }
+    CHECK(depth_tiled(8, 14) && !depth_tiled(8, 15) && depth_tiled(4, 29) && !depth_tiled(4, 30));
+    CHECK(gram_mode(33) == 0 && gram_pairs(33) == 6 && gram_pairs(JACOBI_MAX) == 136 && gram_tiles(17) == 2);
+    CHECK(rotate_rows_lds(8, WB) <= ROTATE_LDS_MAX);
+    CHECK(jacobi_lds(JW) == 0 && jacobi_lds(JW + 1) > 0);
+    CHECK(jacobi_lds(JACOBI_LDS_ORDER) == 8 * (3 * 32 + 2) + 16 + 16 * 64 * 64 && jacobi_lds(JACOBI_LDS_ORDER) <= JACOBI_LDS_MAX);  // k_jacobi<true>: above the default
+    CHECK(jacobi_lds(JACOBI_LDS_ORDER) > LDS_DEFAULT && jacobi_lds(JACOBI_LDS_ORDER + 1) < jacobi_lds(JACOBI_LDS_ORDER) && jacobi_lds(JACOBI_MAX) <= LDS_DEFAULT);
+    for (int m = 2; m <= FZ_MAXM; m += 2) {  // the fused depth iteration: fp64, its tiles are not asked whether they fit
+      CHECK(3 * m <= 32 && tile_fits(8, 4 * m));
+      for (bool rot : {false, true}) CHECK(gram_xz_lds(m, rot) <= DEPTH_LDS_MAX);
+      CHECK(depth_primary_lds(8, m) <= DEPTH_LDS_MAX && dual_apply_lds(8, m) <= DEPTH_LDS_MAX && dual_gram_mfma_lds(m) <= DEPTH_LDS_MAX);
+    }
+    CHECK(gram_xz_lds(FZ_MAXM, true) == 8 * 128 * 80 && gram_xz_lds(2, false) == 8 * 128 * 10 && gram_xz_lds(1, false) == 8192);
+    CHECK(dual_gram_mfma_lds(FZ_MAXM) == 8 * (120 + 4 * (32 * 44 + 4 * (32 * 11 + 8))));
+    CHECK(depth_primary_wide_lds(DEPTH_MAX_IMAGES) <= DEPTH_LDS_MAX && dual_apply_wide_lds(DEPTH_MAX_IMAGES) <= DEPTH_LDS_MAX);
+    CHECK(dual_apply_wide_lds(DEPTH_MAX_IMAGES) == 147456);
+    for (int m = 1; m <= DEPTH_MAX_IMAGES; ++m) {  // k_dual_gram: at least one row, and what it stages fits
+      const int rows = dual_gram_rows(m);
+      CHECK(rows >= 1 && rows <= DG_ROWS_MAX && dual_gram_lds(m, rows) <= DEPTH_LDS_MAX);
+      CHECK(rows == DG_ROWS_MAX || dual_gram_lds(m, rows + 1) > DEPTH_LDS_MAX);  // (as many as fit)
+    }
+    CHECK(dual_gram_rows(47) == 128 && dual_gram_rows(48) < 128 && dual_gram_rows(256) == 24);
   }
   {  // the pick of a count row: ties, all degenerate, below the minimum, a small item, H = 1
     const int ON = RS_OK | RS_ACTIVE | RS_CUR;

@@ -94,6 +94,69 @@ inline void basis_block(const Basis &b, const double *V, int k, int n, int g0, i
     for (int i = 0; i < 4; ++i) Mg[(size_t)c * 4 + i] = g0 + i < n_rank ? basis_at(b, V, k, c, g0 + i) : 0.0;
 }
 
+// ------------------------------------------------------------------ SVD workspace: tile sizes and dynamic LDS
+// The sizes the kernels of mvsvd.hip are written for, and for every kernel that takes dynamic LDS the ONE formula of its size (the
+// launch uses it) under the limit mvsvd_create raises the kernel to (set_lds_limits).  host_check.cpp holds every formula to its
+// limit at the largest arguments its route admits.  `el`: bytes of an element of the workspace's dtype (4 or 8).
+constexpr int GT = 16;             // Gram tile = one v_mfma_f64_16x16x4_f64 accumulator
+constexpr int ROWS_PER_STEP = 32;  // rows consumed per unrolled step (8 MFMA k-groups of 4 rows)
+constexpr int GRAM_ROWS = 4 * ROWS_PER_STEP;  // 128 rows per workgroup step
+constexpr int WIDE_MIN = 64;     // columns above which the implicit form takes over (n <= 64: the eigenproblem sits in LDS, 6 ms)
+constexpr int JACOBI_MAX = 256;  // columns up to which the Gram + Jacobi route stays available (n_rank > 16: 0.4 s of Jacobi there)
+constexpr int WB = 32;           // block width of the wide path (= the small solver's order)
+constexpr int JW = 32;           // max order of the small solver (k_jacobi_small: static LDS only)
+constexpr int JACOBI_LDS_ORDER = 64;  // max order at which k_jacobi keeps both n x n matrices in LDS
+constexpr int PC = 64;           // k_project: columns per LDS chunk
+constexpr int DG_ROWS_MAX = 128;  // rows staged per pass of k_dual_gram (fewer when 3 m columns of them do not fit the LDS: dual_gram_rows)
+constexpr int FZ_MAXM = 10;       // images on the fused depth path (n = 3 m <= 32)
+constexpr int DEPTH_MAX_IMAGES = 768;  // k_dual_apply_wide keeps U4 and w (24 doubles per image) in LDS: 147,456 B of DEPTH_LDS_MAX
+constexpr size_t LDS_DEFAULT = 64 * 1024;  // what a kernel may ask for without an attribute: the Gram forms, k_jacobi<false>
+constexpr size_t JACOBI_LDS_MAX = 96 * 1024;         // k_jacobi<true>
+constexpr size_t ROTATE_LDS_MAX = 64 * 1024;         // k_rotate_rows
+constexpr size_t PROJECT_LDS_MAX = 160 * 1024 - 64;  // k_project
+constexpr size_t DEPTH_LDS_MAX = 148 * 1024;  // the depth kernels, k_scale_rows_tiled, k_gram_xz (+ 2 KiB static in block_sum_to)
+constexpr size_t TILE_MAX_BYTES = 120 * 1024;  // LDS the four tiles of a block may take (plus the small operand tables: < 160 KiB)
+
+// The Gram forms of n <= 32 columns (k_gram_fused<T, MODE>, k_gram_xz): MODE 1 up to 16 columns, 2 (the packed tile) up to 24, 3
+// up to 32; 0 = tile pair by tile pair (k_gram_pair).  A form's partial tiles: as many as its mode, else every pair of tiles.
+inline int gram_mode(int n) { return n <= 16 ? 1 : (n <= 24 ? 2 : (n <= 32 ? 3 : 0)); }
+inline int gram_tiles(int n) { return (n + GT - 1) / GT; }
+inline int gram_pairs(int n) { return gram_mode(n) == 2 ? 2 : gram_tiles(n) * (gram_tiles(n) + 1) / 2; }
+// staged rows, or the 8 KiB per partial tile of gram_store_partial
+inline size_t gram_fused_lds(size_t el, int n) { return std::max<size_t>(el * GRAM_ROWS * n, (size_t)gram_pairs(n) * 8192); }
+// k_gram_xz of m images: GRAM_ROWS rows of sx [3 m] | sz [m] | sp [m] | (with the rotation) B = W V1 [3 m]
+inline size_t gram_xz_lds(int m, bool rot) {
+  return std::max<size_t>(sizeof(double) * (size_t)GRAM_ROWS * ((rot ? 2 : 1) * 3 * m + 2 * m), (size_t)gram_pairs(3 * m) * 8192);
+}
+// k_jacobi: the rotations of a step; up to JACOBI_LDS_ORDER also A and V
+inline size_t jacobi_lds(int n) {
+  const int np = (n + 1) & ~1;
+  if (n <= JW) return 0;
+  return sizeof(double) * (3 * (np / 2) + 2) + 16 + (n <= JACOBI_LDS_ORDER ? sizeof(double) * 2 * (size_t)n * n : 0);
+}
+inline size_t rotate_rows_lds(size_t el, int n) { return (size_t)GRAM_ROWS * n * el; }
+// k_project: 4 n doubles (unused), mu [n], four tiles of 64 rows x min(n, PC) columns at an odd stride
+inline size_t project_lds(size_t el, int n) { return sizeof(double) * (5 * (size_t)n) + el * 4 * 64 * (size_t)(std::min(n, PC) | 1) + 16; }
+// four wave tiles of 64 rows x cols elements at an odd stride: k_scale_rows_tiled (cols = n + groups), the tiled depth kernels (4 m)
+inline size_t row_tile_lds(size_t el, int cols) { return el * 4 * 64 * (size_t)(cols | 1); }
+inline bool tile_fits(size_t el, int cols) { return row_tile_lds(el, cols) <= TILE_MAX_BYTES; }
+// the depth update of m images goes through row tiles (coalesced) while they and the dual method's 24 doubles per image fit
+inline bool depth_tiled(size_t el, int m) { return tile_fits(el, 4 * m) && 24 * m * sizeof(double) <= 24 * 1024; }
+// k_depth_primary<T, true>, k_primary_xz: U [3 m][4] and the tiles; k_depth_primary_wide: U and per wave [64][10 sums | 4 components]
+inline size_t depth_primary_lds(size_t el, int m) { return sizeof(double) * 12 * m + row_tile_lds(el, 4 * m) + 16; }
+inline size_t depth_primary_wide_lds(int m) { return sizeof(double) * (12 * (size_t)m + 4 * 64 * 14); }
+// k_dual_apply<T, true>, k_dual_apply_xz: U4 [3 m][4], w [m][12] and the tiles; k_dual_apply_wide: the two tables alone
+inline size_t dual_apply_lds(size_t el, int m) { return sizeof(double) * 24 * m + row_tile_lds(el, 4 * m) + 16; }
+inline size_t dual_apply_wide_lds(int m) { return sizeof(double) * 24 * m; }
+// k_dual_gram stages [rows][3 m | 1] normalised observations + [rows][4] right singular vectors per pass
+inline int dual_gram_rows(int m) { return (int)std::max<size_t>(1, std::min<size_t>(DG_ROWS_MAX, DEPTH_LDS_MAX / (sizeof(double) * (size_t)(((3 * m) | 1) + 4)))); }
+inline size_t dual_gram_lds(int m, int rows) { return sizeof(double) * ((size_t)rows * (((3 * m) | 1) + 4)); }
+// k_dual_gram_mfma<M>: U [3 m][4]; per wave ROWS_PER_STEP rows of x [3 m] | z [m] | V4 [4] and the four planes [row][m | 1] + 8
+// of S's shares
+inline size_t dual_gram_mfma_lds(int m) {
+  return sizeof(double) * (12 * (size_t)m + 4 * ((size_t)ROWS_PER_STEP * (4 * m + 4) + 4 * ((size_t)ROWS_PER_STEP * (m | 1) + 8)));
+}
+
 // The depth iteration's scratch (ddep) for m images.  Both routes start it the same way,
 //   [blocks] error partials | [8] error | G12 [m][144] | V12 [m][144] | colsum [m][12] | w12 [m][12]
 // and keep their own partial sums behind that, from `own` on.

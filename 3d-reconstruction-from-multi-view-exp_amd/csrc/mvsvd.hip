@@ -23,6 +23,9 @@
 // (G - s s^T / N cancels when |mean| >> spread).
 // A workspace handle (mvsvd_create / load / run / destroy) keeps the matrix, every buffer, the
 // stream and the events resident across calls; mvsvd_factorize is the one-shot form.
+// The tile sizes the kernels share with the host (GT, GRAM_ROWS, WB, JW, PC, FZ_MAXM, ...) and the one formula of every kernel's
+// dynamic LDS are in mvba_host.h, host arithmetic that host_check.cpp holds to the limits; the host side after the kernels
+// (kernel tables, step pieces, state notes) is mapped in DESIGN.md §4.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -37,10 +40,8 @@ using namespace mvba;
 
 namespace {
 
-constexpr int GT = 16;             // Gram tile = one v_mfma_f64_16x16x4_f64 accumulator
 constexpr int GRAM_SLICES = 32;    // second level of the fixed-order Gram reduction
 constexpr int COLSUM_SLICES = 256;
-constexpr int ROWS_PER_STEP = 32;  // rows consumed per unrolled step (8 MFMA k-groups of 4 rows)
 typedef double svd_d4 __attribute__((ext_vector_type(4)));
 
 // G += Wt^T Wt on the f64 matrix cores.  For 4 consecutive rows r0..r3 and column tiles (ti,tj):
@@ -75,7 +76,6 @@ __device__ __forceinline__ void gram_store_partial(const svd_d4 *acc, int npairs
 // Wt, streamed with 16-byte loads by all 256 threads into LDS (a lane-per-element gather of the
 // MFMA operands straight from HBM ran at 1.8 TB/s), then every wave picks the operands of its
 // 32 rows out of LDS.  Rows past the end are zero-filled in LDS.
-constexpr int GRAM_ROWS = 4 * ROWS_PER_STEP;  // 128 rows per workgroup step
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void k_gram_fused(const T *__restrict__ Wt, long long n_rows, int n,
                                                     const double *__restrict__ mu, double *__restrict__ partial) {
@@ -410,10 +410,7 @@ __global__ __launch_bounds__(256) void k_rotate_rows(const T *__restrict__ Wt, l
 // eps sigma_1^2).  At the end B = (W - mu) Q once more: its Gram matrix is nearly diagonal and graded, a last Jacobi gives
 // sigma = sqrt(theta) and the final rotation, S is B's leading columns (S = M^T W by construction: no projection pass).
 // sigma[WB..] is not computed (NaN).
-constexpr int WIDE_MIN = 64;     // columns above which the implicit form takes over (n <= 64: the eigenproblem sits in LDS, 6 ms)
-constexpr int JACOBI_MAX = 256;  // columns up to which the Gram + Jacobi route stays available (n_rank > 16: 0.4 s of Jacobi there)
 constexpr int MVSVD_MAX_COLS = 3 * 4096;  // three rows of W per image at MAX_CAMERAS of the bundle-adjustment engine
-constexpr int WB = 32;       // block width (= the small solver's order)
 constexpr int WT = 64;       // tile edge of the two products
 
 // The two products share their staging: a 64 x 64 tile of W (kept in its own dtype; converted and centred as the MFMA operand is
@@ -811,7 +808,7 @@ __global__ __launch_bounds__(1024) void k_jacobi(double *__restrict__ Ag, double
 //    whole sweep that finds nothing to rotate.
 // The phantom index of an odd order is a zero row / column: its pivot a_pq is 0, so it is never rotated, wherever it sits.
 // After a sweep (np - 1 steps) every index is back in its seat.
-constexpr int JW = 32, JWS = JW + 1;  // max order and padded LDS stride of the small solver
+constexpr int JWS = JW + 1;  // padded LDS stride of the small solver (its max order JW: mvba_host.h)
 constexpr int JT = 768;               // its threads
 
 // Is a_pq worth a rotation?  Above the relative threshold tol sqrt(a_pp a_qq) (small eigenvalues keep their RELATIVE
@@ -950,7 +947,6 @@ __global__ __launch_bounds__(JT) void k_jacobi_small(double *__restrict__ Ag, do
 // S[i][row] = sum_c Mr[c][i] (Wt[row][c] - mu[c]).  A wave takes 64 consecutive rows: the 64 x n
 // tile is contiguous in memory, so it is loaded with fully coalesced accesses into a padded LDS
 // tile (odd stride -> conflict-free column reads), then each lane reduces its own row.
-constexpr int PC = 64;  // columns per LDS chunk
 template <typename T>
 __global__ __launch_bounds__(256) void k_project(const T *__restrict__ Wt, long long n_rows, int n, int r,
                                                  const double *__restrict__ Mr4 /*[n][4], zero padded beyond r*/, const double *__restrict__ mu,
@@ -1078,9 +1074,6 @@ __device__ __forceinline__ void tile_store(T *__restrict__ dst, long long base, 
       if (q0 + 64 * u < total) d[q0 + 64 * u] = v[u];
   }
 }
-constexpr size_t TILE_MAX_BYTES = 120 * 1024;  // LDS the four tiles of a block may take (plus the small operand tables: < 160 KiB)
-template <typename T>
-inline bool tile_fits(int cols) { return sizeof(T) * 4 * 64 * (size_t)(cols | 1) <= TILE_MAX_BYTES; }
 
 // ---- depth-weighted matrix from a resident base (mvsvd_run_scaled): W[a][j] = X[a][j] z[a][j / group] s,
 // s = 1 / |row a of X o z| (norm 1: every row to unit length, ref perspective_camera_calibration.py:86-87) or
@@ -1565,7 +1558,6 @@ __global__ __launch_bounds__(256) void k_dual_apply_wide(const T *__restrict__ X
 // seven multiply-adds, and the kernel ran at the LDS read rate: 1.76 ms at 1 M points x 30 images, this form 0.5.
 __constant__ int c_pair_i[10] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3};
 __constant__ int c_pair_j[10] = {0, 1, 2, 3, 1, 2, 3, 2, 3, 3};
-constexpr int DG_ROWS_MAX = 128;  // rows staged per pass of k_dual_gram (fewer when 3 m columns of them do not fit the LDS: dual_gram_rows)
 inline int dual_gram_split(int m) { return std::min(16, 256 / std::min(m, 256)); }  // thread groups (= partials) per block
 template <typename T>
 __global__ __launch_bounds__(256) void k_dual_gram(const T *__restrict__ X, const T *__restrict__ S, double is0, double is1, double is2,
@@ -1740,7 +1732,6 @@ __global__ __launch_bounds__(256) void k_dual_apply(const T *__restrict__ X, con
 //                 products) instead of read from a projection pass; the dual update also leaves the per-image sums of (x z)^2 of
 //                 the NEW depths behind (the next iteration's norm-2 scales), so k_group_sumsq runs once per loop, not once per step
 // Same arithmetic per entry as before up to the order of a few sums; oracle parity per step stays at 1e-9 (tests).
-constexpr int FZ_MAXM = 10;  // images on this path (n = 3 m <= 32)
 
 // Stage GRAM_ROWS rows of X ([rows][n]) and z ([rows][m]) and scale them in place: sx[r][c] <- x z[r][c / 3] s.
 // NORM 1: s = 1 / |row of X o z|; NORM 2: s = cs[c / 3].  Rows past the end become zeros.  sp: [GRAM_ROWS][m] scratch.
@@ -2216,41 +2207,90 @@ struct mvsvd_handle {
 
 namespace {
 
+// ---- kernel tables ("Map of the host side").  The only places that name an instantiation of a kernel that has
+// several forms or takes more than the default LDS: the launch and set_lds_limits (mvsvd_create) both go through them.  The
+// dynamic LDS of a launch is its kernel's one formula in mvba_host.h, where the limit it is raised to stands beside it.
+template <typename T>
+auto gram_fused_kernel(int mode) { return mode == 1 ? k_gram_fused<T, 1> : (mode == 2 ? k_gram_fused<T, 2> : k_gram_fused<T, 3>); }
+// the fused depth iteration's Gram pass: m images (2, 4, .. FZ_MAXM), the norm of the depth method, with or without the rotation by V1
+template <int M>
+auto gram_xz_kernel_m(int norm, bool rot) {
+  if (norm == 1) return rot ? k_gram_xz<M, 1, true> : k_gram_xz<M, 1, false>;
+  return rot ? k_gram_xz<M, 2, true> : k_gram_xz<M, 2, false>;
+}
+auto gram_xz_kernel(int m, int norm, bool rot) {
+  switch (m) {
+    case 2: return gram_xz_kernel_m<2>(norm, rot);
+    case 4: return gram_xz_kernel_m<4>(norm, rot);
+    case 6: return gram_xz_kernel_m<6>(norm, rot);
+    case 8: return gram_xz_kernel_m<8>(norm, rot);
+    default: return gram_xz_kernel_m<10>(norm, rot);
+  }
+}
+auto dual_gram_mfma_kernel(int m) {
+  return m == 2 ? k_dual_gram_mfma<2> : (m == 4 ? k_dual_gram_mfma<4> : (m == 6 ? k_dual_gram_mfma<6> : (m == 8 ? k_dual_gram_mfma<8> : k_dual_gram_mfma<10>)));
+}
+auto jacobi_kernel(int n) { return n <= JW ? k_jacobi_small : (n <= JACOBI_LDS_ORDER ? k_jacobi<true> : k_jacobi<false>); }
+template <typename T>
+auto rotate_rows_kernel() { return k_rotate_rows<T>; }
+template <typename T>
+auto project_kernel() { return k_project<T>; }
+// tiled: the rows go through LDS tiles (tile_fits / depth_tiled)
+template <typename T>
+auto scale_rows_kernel(bool tiled) { return tiled ? k_scale_rows_tiled<T> : k_scale_rows_wide<T>; }
+template <typename T>
+auto depth_primary_kernel(bool tiled) { return tiled ? k_depth_primary<T, true> : k_depth_primary_wide<T>; }
+template <typename T>
+auto dual_apply_kernel(bool tiled) { return tiled ? k_dual_apply<T, true> : k_dual_apply_wide<T>; }
+template <typename T>
+auto dual_gram_kernel() { return k_dual_gram<T>; }
+auto primary_xz_kernel() { return k_primary_xz; }
+auto dual_apply_xz_kernel() { return k_dual_apply_xz; }
+
+// the tail of every Gram form: the chunks' partial tiles summed in fixed order, then the full symmetric n x n matrix G
+void gram_reduce_finish(mvsvd_handle *h, int n, int chunks, double *G) {
+  const int n_pairs = gram_pairs(n), slices = std::min(chunks, GRAM_SLICES);
+  hipLaunchKernelGGL(k_gram_reduce, dim3(n_pairs, slices), dim3(256), 0, h->st, h->dpart, chunks, n_pairs, h->dpart2);
+  hipLaunchKernelGGL(k_gram_finish, dim3((n + 127) / 128, n), dim3(128), 0, h->st, h->dpart2, slices, n_pairs, gram_tiles(n), gram_mode(n) == 2 ? 1 : 0, G, n);
+}
 // G = (W - mu)^T (W - mu) of an n_rows x n matrix through the workspace's partial buffers (the workspace's own matrix, or -- the
 // wide path -- one of its n x 32 / N x 32 blocks)
 template <typename T>
 void launch_gram_n(mvsvd_handle *h, const T *W, long long n_rows, int n, const double *mu, int chunks, double *G) {
-  const int n_tiles = (n + GT - 1) / GT;
-  const bool packed = n > 16 && n <= 24;
-  const int n_pairs = packed ? 2 : n_tiles * (n_tiles + 1) / 2;
-  if (n <= 16)
-    hipLaunchKernelGGL((k_gram_fused<T, 1>), dim3(1, chunks), dim3(256), std::max<size_t>(sizeof(T) * GRAM_ROWS * n, 1 * 8192), h->st, W, n_rows, n, mu, h->dpart);
-  else if (packed)
-    hipLaunchKernelGGL((k_gram_fused<T, 2>), dim3(1, chunks), dim3(256), std::max<size_t>(sizeof(T) * GRAM_ROWS * n, 2 * 8192), h->st, W, n_rows, n, mu, h->dpart);
-  else if (n <= 32)
-    hipLaunchKernelGGL((k_gram_fused<T, 3>), dim3(1, chunks), dim3(256), std::max<size_t>(sizeof(T) * GRAM_ROWS * n, 3 * 8192), h->st, W, n_rows, n, mu, h->dpart);
+  if (const int mode = gram_mode(n))
+    hipLaunchKernelGGL(gram_fused_kernel<T>(mode), dim3(1, chunks), dim3(256), gram_fused_lds(sizeof(T), n), h->st, W, n_rows, n, mu, h->dpart);
   else
-    hipLaunchKernelGGL(k_gram_pair<T>, dim3(n_pairs, chunks), dim3(256), 0, h->st, W, n_rows, n, n_tiles, n_pairs, mu, h->dpart);
-  const int slices = std::min(chunks, GRAM_SLICES);
-  hipLaunchKernelGGL(k_gram_reduce, dim3(n_pairs, slices), dim3(256), 0, h->st, h->dpart, chunks, n_pairs, h->dpart2);
-  hipLaunchKernelGGL(k_gram_finish, dim3((n + 127) / 128, n), dim3(128), 0, h->st, h->dpart2, slices, n_pairs, n_tiles, packed ? 1 : 0, G, n);
+    hipLaunchKernelGGL(k_gram_pair<T>, dim3(gram_pairs(n), chunks), dim3(256), 0, h->st, W, n_rows, n, gram_tiles(n), gram_pairs(n), mu, h->dpart);
+  gram_reduce_finish(h, n, chunks, G);
 }
-template <typename T>
-void launch_gram(mvsvd_handle *h, const T *W, const double *mu, int chunks) { launch_gram_n<T>(h, W, h->n_rows, h->n, mu, chunks, h->dG); }
+// ... of the resident base re-weighted by the depths in dz (and, rot, rotated by dV1), which never leaves the LDS: m = n / 3 images
+void launch_gram_xz(mvsvd_handle *h, int norm, bool rot, int chunks, const double *cs) {
+  const int n = h->n, m = n / 3;
+  hipLaunchKernelGGL(gram_xz_kernel(m, norm, rot), dim3(1, chunks), dim3(256), gram_xz_lds(m, rot), h->st, (const double *)h->dX, (const double *)h->dz,
+                     h->base_rows, n, m, cs, rot ? (const double *)h->dV1 : (const double *)nullptr, h->dpart);
+  gram_reduce_finish(h, n, chunks, h->dG);
+}
 
+// `count` problems of order n (one workgroup each; more than one: n <= JW), the sweeps of the last pass -> *sweeps.
 // tol: rotate while |a_pq| > tol sqrt(|a_pp a_qq|).  1e-15 for float64 input; float32 input carries
 // 6e-8 of relative noise per entry, so its Gram matrix is diagonalised to 1e-11 (one or two sweeps fewer).
-void launch_jacobi_n(mvsvd_handle *h, double *dA, int n, double *dVout, double tol) {
+void launch_jacobi_n(mvsvd_handle *h, double *dA, int n, double *dVout, double tol, int count, int *sweeps) {
   const int np = (n + 1) & ~1;
-  const size_t nn = (size_t)n * n, jl = sizeof(double) * (3 * (np / 2) + 2) + 16;
-  if (n <= JW)
-    hipLaunchKernelGGL(k_jacobi_small, dim3(1), dim3(JHB * JHB + JW * (np / 2)), 0, h->st, dA, dVout, n, 60, tol, h->dsw);  // (A blocks + V pieces)
-  else if (n <= 64)
-    hipLaunchKernelGGL(k_jacobi<true>, dim3(1), dim3(256), jl + sizeof(double) * 2 * nn, h->st, dA, dVout, n, 60, tol, h->dsw);
-  else
-    hipLaunchKernelGGL(k_jacobi<false>, dim3(1), dim3(1024), jl, h->st, dA, dVout, n, 60, tol, h->dsw);
+  const int threads = n <= JW ? JHB * JHB + JW * (np / 2) /* A blocks + V pieces */ : (n <= JACOBI_LDS_ORDER ? 256 : 1024);
+  hipLaunchKernelGGL(jacobi_kernel(n), dim3(count), dim3(threads), jacobi_lds(n), h->st, dA, dVout, n, 60, tol, sweeps);
 }
-void launch_jacobi(mvsvd_handle *h, double *dVout, double tol) { launch_jacobi_n(h, h->dG, h->n, dVout, tol); }
+void launch_jacobi(mvsvd_handle *h, double *dVout, double tol) { launch_jacobi_n(h, h->dG, h->n, dVout, tol, 1, h->dsw); }
+
+// B = (W - 1 mu^T) V, V n x n: in 64 x 64 tiles, or -- tall and narrow -- streamed GRAM_ROWS rows at a time
+template <typename T>
+void launch_rotate(mvsvd_handle *h, const T *W, long long n_rows, int n, const double *mu, const double *V, double *B) {
+  hipLaunchKernelGGL(k_rotate<T>, dim3((unsigned)((n_rows + 63) / 64), (n + 63) / 64), dim3(256), 0, h->st, W, n_rows, n, mu, V, B);
+}
+template <typename T>
+void launch_rotate_rows(mvsvd_handle *h, const T *W, long long n_rows, int n, const double *mu, const double *V, double *B) {
+  const int grid = (int)std::max<long long>(1, std::min<long long>(6 * 256, (n_rows + GRAM_ROWS - 1) / GRAM_ROWS));
+  hipLaunchKernelGGL(rotate_rows_kernel<T>(), dim3(grid), dim3(256), rotate_rows_lds(sizeof(T), n), h->st, W, n_rows, n, mu, V, B);
+}
 
 int chunks_for(long long n_rows, int n) {
   const int n_tiles = (n + GT - 1) / GT, n_pairs = n_tiles * (n_tiles + 1) / 2;
@@ -2332,6 +2372,48 @@ void base_scaled_into_w(mvsvd_handle *h) {  // scale_base_into_w
   h->wide_warm = true;  // (the block iteration may start from the previous factorisation's vectors: the same base, other depths)
 }
 
+// ---- step pieces, each written once
+// the column means of the loaded matrix -> dmu: the rows are centred as they enter the products.  Null without centring.
+template <typename T>
+const double *column_means(mvsvd_handle *h, int center) {
+  if (!center) return nullptr;
+  const int n = h->n, cy = (int)std::max<long long>(1, std::min<long long>(COLSUM_SLICES, h->n_rows / 4096));
+  hipLaunchKernelGGL(k_colsum<T>, dim3(n, cy), dim3(256), 0, h->st, (const T *)h->dW, h->n_rows, n, h->dsum);
+  hipLaunchKernelGGL(k_mean_from_sum, dim3((n + 255) / 256), dim3(256), 0, h->st, h->dsum, cy, n, h->n_rows, h->dmu);
+  return h->dmu;
+}
+// the second, preconditioned pass on the Gram matrix of B = W V1 in dG: V2 (into dMr, n x n: sized for it), then V = V1 V2
+void second_jacobi(mvsvd_handle *h) {
+  launch_jacobi(h, h->dMr, 1e-15);
+  launch_rotate<double>(h, h->dV1, (long long)h->n, h->n, nullptr, h->dMr, h->dV);
+}
+// A diagonalised k x k matrix (dD: eigenvalues on its diagonal) and its n x k vectors (dV) -> host, with the means if asked for;
+// sort, the rank-r basis with a deterministic sign.  k = n after the Jacobi route, WB after the block iteration.
+struct HostBasis {
+  std::vector<double> D, V, mu;
+  Basis basis;
+};
+int read_basis(mvsvd_handle *h, const double *dD, const double *dV, int k, int n_rank, bool means, HostBasis &b) {
+  const int n = h->n;
+  b.D.resize((size_t)k * k);
+  b.V.resize((size_t)n * k);
+  b.mu.assign(n, 0.0);
+  MVBA_HIP(hipMemcpyAsync(b.D.data(), dD, sizeof(double) * b.D.size(), hipMemcpyDeviceToHost, h->st));
+  MVBA_HIP(hipMemcpyAsync(b.V.data(), dV, sizeof(double) * b.V.size(), hipMemcpyDeviceToHost, h->st));
+  if (means) MVBA_HIP(hipMemcpyAsync(b.mu.data(), h->dmu, sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
+  MVBA_HIP(hipStreamSynchronize(h->st));
+  return select_basis(b.D.data(), b.V.data(), k, n, n_rank, b.basis);
+}
+// ... handed to the caller: sigma (NaN beyond the k computed), M [n][n_rank], the means
+template <typename T>
+void write_basis(const HostBasis &b, int k, int n, int n_rank, T *sigma, T *M, T *means) {
+  for (int i = 0; i < n; ++i) sigma[i] = i < k ? (T)std::sqrt(std::max(0.0, b.D[(size_t)b.basis.order[i] * k + b.basis.order[i]])) : (T)NAN;
+  for (int i = 0; i < n_rank; ++i)
+    for (int c = 0; c < n; ++c) M[(size_t)c * n_rank + i] = (T)basis_at(b.basis, b.V.data(), k, c, i);
+  if (means)
+    for (int c = 0; c < n; ++c) means[c] = (T)b.mu[c];
+}
+
 template <typename T>
 int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means, double *timings);
 
@@ -2340,62 +2422,38 @@ int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means,
   if (h->wide && (n_rank <= WB / 2 || h->n > JACOBI_MAX)) return run_wide<T>(h, n_rank, center, M, sigma, S, means, timings);
   const int n = h->n;
   const long long n_rows = h->n_rows;
-  const size_t nn = (size_t)n * n;
   hipStream_t st = h->st;
   const T *dW = (const T *)h->dW;
   const int chunks = chunks_for(n_rows, n);
   const bool refine = sizeof(T) == 8;  // fp64 data: second, preconditioned pass (see the file header)
   hipEventRecord(h->ev[1], st);
-  const double *mu = nullptr;
-  if (center) {  // column means first: the rows are centred as they enter the products
-    const int cy = (int)std::max<long long>(1, std::min<long long>(COLSUM_SLICES, n_rows / 4096));
-    hipLaunchKernelGGL(k_colsum<T>, dim3(n, cy), dim3(256), 0, st, dW, n_rows, n, h->dsum);
-    hipLaunchKernelGGL(k_mean_from_sum, dim3((n + 255) / 256), dim3(256), 0, st, h->dsum, cy, n, n_rows, h->dmu);
-    mu = h->dmu;
-  }
-  launch_gram<T>(h, dW, mu, chunks);
+  const double *mu = column_means<T>(h, center);
+  launch_gram_n<T>(h, dW, n_rows, n, mu, chunks, h->dG);
   hipEventRecord(h->ev[2], st);
   launch_jacobi(h, refine ? h->dV1 : h->dV, sizeof(T) == 8 ? 1e-15 : 1e-11);
   hipEventRecord(h->ev[3], st);
   if (refine) {
     if (int rc = need_refine_b(h)) return rc;
-    if (n <= 32 && n % 2 == 0 && (n * sizeof(T)) % 16 == 0 && n_rows >= 4096) {  // tall and narrow: the streaming form
-      const int rgrid = (int)std::max<long long>(1, std::min<long long>(6 * 256, (n_rows + GRAM_ROWS - 1) / GRAM_ROWS));
-      const size_t rlds = (size_t)GRAM_ROWS * n * sizeof(T);
-      hipLaunchKernelGGL(k_rotate_rows<T>, dim3(rgrid), dim3(256), rlds, st, dW, n_rows, n, mu, h->dV1, h->dB);
-    } else
-    hipLaunchKernelGGL(k_rotate<T>, dim3((unsigned)((n_rows + 63) / 64), (n + 63) / 64), dim3(256), 0, st, dW, n_rows, n, mu, h->dV1, h->dB);
-    launch_gram<double>(h, h->dB, nullptr, chunks);
-    launch_jacobi(h, h->dMr /* V2, n x n: dMr is sized for it */, 1e-15);
-    // V = V1 V2
-    hipLaunchKernelGGL(k_rotate<double>, dim3((n + 63) / 64, (n + 63) / 64), dim3(256), 0, st, h->dV1, (long long)n, n, (const double *)nullptr,
-                       h->dMr, h->dV);
+    if (n <= 32 && n % 2 == 0 && (n * sizeof(T)) % 16 == 0 && n_rows >= 4096)  // tall and narrow: the streaming form
+      launch_rotate_rows<T>(h, dW, n_rows, n, mu, h->dV1, h->dB);
+    else
+      launch_rotate<T>(h, dW, n_rows, n, mu, h->dV1, h->dB);
+    launch_gram_n<double>(h, h->dB, n_rows, n, nullptr, chunks, h->dG);
+    second_jacobi(h);
   }
-  // eigenvalues -> host, sort, build the rank-r basis with a deterministic sign
-  std::vector<double> hG(nn), hV(nn), hmu(n, 0.0);
-  MVBA_HIP(hipMemcpyAsync(hG.data(), h->dG, sizeof(double) * nn, hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipMemcpyAsync(hV.data(), h->dV, sizeof(double) * nn, hipMemcpyDeviceToHost, st));
-  if (center) MVBA_HIP(hipMemcpyAsync(hmu.data(), h->dmu, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipStreamSynchronize(st));
-  Basis basis;
-  if (int rc = select_basis(hG.data(), hV.data(), n, n, n_rank, basis)) return rc;
-  for (int i = 0; i < n; ++i) sigma[i] = (T)std::sqrt(std::max(0.0, hG[(size_t)basis.order[i] * n + basis.order[i]]));
-  for (int i = 0; i < n_rank; ++i)
-    for (int c = 0; c < n; ++c) M[(size_t)c * n_rank + i] = (T)basis_at(basis, hV.data(), n, c, i);
-  if (means)
-    for (int c = 0; c < n; ++c) means[c] = (T)hmu[c];
+  HostBasis b;
+  if (int rc = read_basis(h, h->dG, h->dV, n, n_rank, center != 0, b)) return rc;
+  write_basis<T>(b, n, n, n_rank, sigma, M, means);
   // S = M^T W in groups of (up to) 4 basis vectors per pass over W
   if (int rc = need_rank(h, n_rank)) return rc;
   hipEventRecord(h->ev[4], st);
   const int pgrid = (int)std::max<long long>(1, std::min<long long>(4096, (n_rows + 255) / 256));
-  const int ldt = std::min(n, PC) | 1;
-  const size_t plds = sizeof(double) * (5 * (size_t)n) + sizeof(T) * 4 * 64 * (size_t)ldt + 16;
   std::vector<double> Mg((size_t)n * 4);
   for (int g0 = 0; g0 < n_rank; g0 += 4) {
     const int rg = std::min(4, n_rank - g0);
-    basis_block(basis, hV.data(), n, n, g0, n_rank, Mg.data());
+    basis_block(b.basis, b.V.data(), n, n, g0, n_rank, Mg.data());
     MVBA_HIP(hipMemcpyAsync(h->dMr, Mg.data(), sizeof(double) * (size_t)n * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_project<T>, dim3(pgrid), dim3(256), plds, st, dW, n_rows, n, rg, h->dMr, mu, (T *)h->dS + (size_t)g0 * n_rows);
+    hipLaunchKernelGGL(project_kernel<T>(), dim3(pgrid), dim3(256), project_lds(sizeof(T), n), st, dW, n_rows, n, rg, h->dMr, mu, (T *)h->dS + (size_t)g0 * n_rows);
     MVBA_HIP(hipStreamSynchronize(st));  // Mg is reused by the next group
   }
   hipEventRecord(h->ev[5], st);
@@ -2410,10 +2468,6 @@ int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means,
   return MVBA_OK;
 }
 
-}  // namespace
-
-namespace {
-
 // The factorisation of a wide matrix (n > WIDE_MIN columns): block power iteration with Rayleigh-Ritz, see the kernels' header.
 template <typename T>
 int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means, double *timings) {
@@ -2424,35 +2478,26 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
   if (n_rank > WB / 2)
     return fail(MVBA_ERR_BADARG, "n_cols > " + std::to_string(JACOBI_MAX) + ": the block iteration carries " + std::to_string(WB) + " vectors, n_rank <= " + std::to_string(WB / 2));
   hipEventRecord(h->ev[1], st);
-  const double *mu = nullptr;
-  if (center) {
-    const int cy = (int)std::max<long long>(1, std::min<long long>(COLSUM_SLICES, N / 4096));
-    hipLaunchKernelGGL(k_colsum<T>, dim3(n, cy), dim3(256), 0, st, dW, N, n, h->dsum);
-    hipLaunchKernelGGL(k_mean_from_sum, dim3((n + 255) / 256), dim3(256), 0, st, h->dsum, cy, n, N, h->dmu);
-    mu = h->dmu;
-  }
+  const double *mu = column_means<T>(h, center);
   hipEventRecord(h->ev[2], st);
   double *H = h->dsmall, *Y = H + WB * WB, *C = Y + WB * WB, *V = C + WB * WB, *Tm = V + WB * WB, *dres = Tm + WB * WB, *respart = dres + WB;
   int *dcol = h->dwflag + WB;                      // [WB] columns to take at the end
   double *dsgn = respart + (size_t)WB * ((n + 255) / 256);  // [WB] their signs
   const int chunksB = chunks_for(N, WB), chunksZ = chunks_for(n, WB);
   const int wgrid = (int)((N + WT - 1) / WT), ngrid = (int)(((long long)n * WB + 255) / 256), rgrid = (n + 255) / 256;
-  const int rot_grid_n = (int)std::max<long long>(1, std::min<long long>(6 * 256, (n + GRAM_ROWS - 1) / GRAM_ROWS));
-  const size_t rot_lds = (size_t)GRAM_ROWS * WB * sizeof(double);
-  const int bgrid = (int)std::max<long long>(1, std::min<long long>(6 * 256, (N + GRAM_ROWS - 1) / GRAM_ROWS));
   auto orth = [&](double *src, double *tmp, double *dst, const double *ritz, unsigned long long salt) {  // dst <- orthonormal basis of span(src), in Ritz order; src and tmp are scratch
     launch_gram_n<double>(h, src, n, WB, nullptr, chunksZ, C);
     hipLaunchKernelGGL(k_chol_orth, dim3(1), dim3(64), 0, st, C, ritz, Tm, h->dwflag);
-    hipLaunchKernelGGL(k_rotate_rows<double>, dim3(rot_grid_n), dim3(256), rot_lds, st, src, (long long)n, WB, (const double *)nullptr, Tm, tmp);
+    launch_rotate_rows<double>(h, src, n, WB, nullptr, Tm, tmp);
     hipLaunchKernelGGL(k_wide_refill, dim3(ngrid), dim3(256), 0, st, tmp, n, h->dwflag, salt);
     launch_gram_n<double>(h, tmp, n, WB, nullptr, chunksZ, C);
     hipLaunchKernelGGL(k_chol_orth, dim3(1), dim3(64), 0, st, C, (const double *)nullptr, Tm, h->dwflag);
-    hipLaunchKernelGGL(k_rotate_rows<double>, dim3(rot_grid_n), dim3(256), rot_lds, st, tmp, (long long)n, WB, (const double *)nullptr, Tm, dst);
+    launch_rotate_rows<double>(h, tmp, n, WB, nullptr, Tm, dst);
   };
   auto product_b = [&](const double *Q) {  // B = (W - mu) Q, H = B^T B, Jacobi: theta on H's diagonal, Y
     hipLaunchKernelGGL(k_wq<T>, dim3(wgrid), dim3(256), 0, st, dW, N, n, mu, Q, h->dBw);
     launch_gram_n<double>(h, h->dBw, N, WB, nullptr, chunksB, H);
-    launch_jacobi_n(h, H, WB, Y, 1e-15);
+    launch_jacobi_n(h, H, WB, Y, 1e-15, 1, h->dsw);
   };
   // start: a fixed pseudo-random block, orthonormalised -- or, inside a depth loop (the same base re-weighted by slightly different
   // depths, 50-200 times: mvsvd_run_scaled / mvsvd_depth_step), the Ritz vectors the previous factorisation ended with: one or two
@@ -2475,7 +2520,7 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
   bool converged = false;
   for (; it < max_iter; ++it) {
     product_b(h->dQ);
-    hipLaunchKernelGGL(k_rotate_rows<double>, dim3(bgrid), dim3(256), rot_lds, st, h->dBw, N, WB, (const double *)nullptr, Y, h->dB2);  // B Y = W (Q Y)
+    launch_rotate_rows<double>(h, h->dBw, N, WB, nullptr, Y, h->dB2);  // B Y = W (Q Y)
     hipLaunchKernelGGL(k_wtb<T>, dim3((n + WT - 1) / WT, h->zchunks), dim3(256), 0, st, dW, N, n, mu, h->dB2, h->zrows_per_chunk, h->dzpart);
     hipLaunchKernelGGL(k_sum_chunks, dim3(ngrid), dim3(256), 0, st, h->dzpart, h->zchunks, (long long)n * WB, h->dZ);
     hipLaunchKernelGGL(k_ritz, dim3(rgrid), dim3(256), 0, st, h->dQ, (const double *)h->dZ, n, Y, H, respart);
@@ -2516,29 +2561,18 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
   // final pass: Q holds the Ritz vectors; B = (W - mu) Q has a nearly diagonal, graded Gram matrix -> sigma and the last rotation
   product_b(h->dQ);
   hipLaunchKernelGGL(k_ritz, dim3(rgrid), dim3(256), 0, st, h->dQ, (const double *)nullptr, n, Y, H, (double *)nullptr);
-  hipLaunchKernelGGL(k_rotate_rows<double>, dim3(bgrid), dim3(256), rot_lds, st, h->dBw, N, WB, (const double *)nullptr, Y, h->dB2);
-  std::vector<double> hH((size_t)WB * WB), hQ((size_t)n * WB), hmu(n, 0.0);
-  MVBA_HIP(hipMemcpyAsync(hH.data(), H, sizeof(double) * WB * WB, hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipMemcpyAsync(hQ.data(), h->dQ, sizeof(double) * (size_t)n * WB, hipMemcpyDeviceToHost, st));
-  if (center) MVBA_HIP(hipMemcpyAsync(hmu.data(), h->dmu, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipStreamSynchronize(st));
-  Basis basis;
-  if (int rc = select_basis(hH.data(), hQ.data(), WB, n, n_rank, basis)) return rc;
-  const int *order = basis.order.data();
-  for (int i = 0; i < n; ++i) sigma[i] = i < WB ? (T)std::sqrt(std::max(0.0, hH[(size_t)order[i] * WB + order[i]])) : (T)NAN;
+  launch_rotate_rows<double>(h, h->dBw, N, WB, nullptr, Y, h->dB2);
+  HostBasis b;
+  if (int rc = read_basis(h, H, h->dQ, WB, n_rank, center != 0, b)) return rc;
+  write_basis<T>(b, WB, n, n_rank, sigma, M, means);
   int hcol[WB] = {};
   double hsgn[WB] = {};
-  for (int i = 0; i < n_rank; ++i) {
-    for (int c = 0; c < n; ++c) M[(size_t)c * n_rank + i] = (T)basis_at(basis, hQ.data(), WB, c, i);
-    hcol[i] = order[i];
-    hsgn[i] = basis.sign[i];
-  }
-  if (means)
-    for (int c = 0; c < n; ++c) means[c] = (T)hmu[c];
+  std::copy_n(b.basis.order.begin(), n_rank, hcol);
+  std::copy_n(b.basis.sign.begin(), n_rank, hsgn);
   if (int rc = need_rank(h, n_rank)) return rc;
   hipEventRecord(h->ev[4], st);
   std::vector<double> Mg((size_t)n * 4);  // the depth loops read the leading basis vectors as [n][4] from dMr, like after run()
-  basis_block(basis, hQ.data(), WB, n, 0, n_rank, Mg.data());
+  basis_block(b.basis, b.V.data(), WB, n, 0, n_rank, Mg.data());
   MVBA_HIP(hipMemcpyAsync(h->dMr, Mg.data(), sizeof(double) * (size_t)n * 4, hipMemcpyHostToDevice, st));
   MVBA_HIP(hipMemcpyAsync(dcol, hcol, sizeof(int) * WB, hipMemcpyHostToDevice, st));
   MVBA_HIP(hipMemcpyAsync(dsgn, hsgn, sizeof(double) * WB, hipMemcpyHostToDevice, st));
@@ -2555,23 +2589,26 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
   return MVBA_OK;
 }
 
+// cs[g] <- 1 / the squared norm of column group g of the base re-weighted by the depths in dz (norm 2), through dgs
+template <typename T>
+void launch_group_scales(mvsvd_handle *h, int group, double *cs) {
+  const int ng = h->n / group, gblocks = (int)std::max<long long>(1, std::min<long long>(GS_BLOCKS, h->base_rows / 64 + 1));
+  hipLaunchKernelGGL(k_group_sumsq<T>, dim3(gblocks), dim3(256), 0, h->st, (const T *)h->dX, (const T *)h->dz, h->base_rows, h->n, group, h->dgs);
+  hipLaunchKernelGGL(k_group_scale, dim3((ng + 3) / 4), dim3(256), 0, h->st, h->dgs, gblocks, ng, cs);
+}
+
 // dW <- the resident base re-weighted by the depths in dz and normalised (see mvsvd_run_scaled)
 int scale_base_into_w(mvsvd_handle *h, int group, int norm) {
-  const int ng = h->n / group;
+  const int cols = h->n + h->n / group;  // a row's values and its depths
   double *cs;
   if (int rc = group_scales(h, &cs)) return rc;
   const int sgrid = (int)std::max<long long>(1, std::min<long long>(4096, (h->base_rows + 255) / 256));
-  const int gblocks = (int)std::max<long long>(1, std::min<long long>(GS_BLOCKS, h->base_rows / 64 + 1));
   with_dtype(h->dtype, [&](auto tag) {
     using T = decltype(tag);
-    if (norm == 2) {
-      hipLaunchKernelGGL(k_group_sumsq<T>, dim3(gblocks), dim3(256), 0, h->st, (const T *)h->dX, (const T *)h->dz, h->base_rows, h->n, group, h->dgs);
-      hipLaunchKernelGGL(k_group_scale, dim3((ng + 3) / 4), dim3(256), 0, h->st, h->dgs, gblocks, ng, cs);
-    }
-    if (tile_fits<T>(h->n + ng))
-      hipLaunchKernelGGL(k_scale_rows_tiled<T>, dim3(sgrid), dim3(256), sizeof(T) * 4 * 64 * (size_t)((h->n + ng) | 1), h->st, (const T *)h->dX, (const T *)h->dz, h->base_rows, h->n, group, norm, cs, (T *)h->dW);
-    else
-      hipLaunchKernelGGL(k_scale_rows_wide<T>, dim3(sgrid), dim3(256), 0, h->st, (const T *)h->dX, (const T *)h->dz, h->base_rows, h->n, group, norm, cs, (T *)h->dW);
+    if (norm == 2) launch_group_scales<T>(h, group, cs);
+    const bool tiled = tile_fits(sizeof(T), cols);
+    hipLaunchKernelGGL(scale_rows_kernel<T>(tiled), dim3(sgrid), dim3(256), tiled ? row_tile_lds(sizeof(T), cols) : 0, h->st, (const T *)h->dX, (const T *)h->dz,
+                       h->base_rows, h->n, group, norm, cs, (T *)h->dW);
   });
   MVBA_HIP(hipGetLastError());
   base_scaled_into_w(h);
@@ -2579,10 +2616,7 @@ int scale_base_into_w(mvsvd_handle *h, int group, int norm) {
 }
 
 constexpr int DEPTH_BLOCKS = 2048;  // blocks of the per-point passes / of the dual Gram pass
-constexpr int DEPTH_MAX_IMAGES = 768;  // k_dual_apply_wide keeps U4 and w (24 doubles per image) in LDS: 147,456 B of DEPTH_LDS_MAX
-constexpr size_t DEPTH_LDS_MAX = 148 * 1024;  // dynamic LDS the depth kernels may ask for (+ 2 KiB static in block_sum_to)
-// rows k_dual_gram stages per pass: [rows][3 m | 1] normalised observations + [rows][4] right singular vectors in LDS
-inline int dual_gram_rows(int m) { return (int)std::max<size_t>(1, std::min<size_t>(DG_ROWS_MAX, DEPTH_LDS_MAX / (sizeof(double) * (size_t)(((3 * m) | 1) + 4)))); }
+inline int depth_grid(long long rows) { return (int)std::max<long long>(1, std::min<long long>(DEPTH_BLOCKS, (rows + 255) / 256)); }
 
 // The depth iteration's scratch (ddep: DepthScratch) with `own` doubles behind the common part, and the dual method's flags.  The
 // two routes differ in `own` and one handle may take both (a new base on the other side of the fused route's row threshold,
@@ -2596,6 +2630,40 @@ int depth_scratch(mvsvd_handle *h, size_t own, DepthScratch *out) {
   return MVBA_OK;
 }
 
+// is[i] = 1 / sigma_i of the leading four, which the dual method divides by: all of them must be positive
+int inverse_sigmas(const double (&sigma)[4], double (&is)[4]) {
+  for (int i = 0; i < 4; ++i) {
+    if (!(sigma[i] > 0.0)) return fail(MVBA_ERR_SINGULAR, "measurement matrix has rank < 4");
+    is[i] = 1.0 / sigma[i];
+  }
+  return MVBA_OK;
+}
+// The dual method's companion problems, from the `parts` partials per entry in d.own (mfma: in k_dual_gram_mfma's layout): their
+// sums in order -> G12, colsum; Jacobi on the m problems of order 12 -> V12; the images' vectors -> w12 (ddflag[0], cleared by the caller: set where an image has none)
+void dual_companion(mvsvd_handle *h, const DepthScratch &d, int m, bool mfma, int parts) {
+  if (mfma)
+    hipLaunchKernelGGL(k_dual_reduce_mfma, dim3((m * 90 + 3) / 4), dim3(256), 0, h->st, d.own, parts, m, d.G12, d.colsum);
+  else
+    hipLaunchKernelGGL(k_dual_reduce, dim3((14 * m * 6 + 3) / 4), dim3(256), 0, h->st, d.own, parts, m, d.G12, d.colsum);
+  launch_jacobi_n(h, d.G12, 12, d.V12, 1e-15, m, h->ddflag + 1);
+  hipLaunchKernelGGL(k_dual_vec, dim3((m + 63) / 64), dim3(64), 0, h->st, d.G12, d.V12, d.colsum, m, d.w12, h->ddflag);
+}
+// the end of a depth step: the error of the update from its `blocks` partials -> *E, event 7, the dual method's flag
+int finish_depth_step(mvsvd_handle *h, const DepthScratch &d, int blocks, int method, double f0, double *E) {
+  hipStream_t st = h->st;
+  hipLaunchKernelGGL(k_depth_error, dim3(1), dim3(64), 0, st, d.Epart, blocks, (double)h->base_rows * (double)(h->n / 3), f0, d.Eout);
+  hipEventRecord(h->ev[7], st);
+  MVBA_HIP(hipGetLastError());
+  int fl = 0;
+  MVBA_HIP(hipMemcpyAsync(E, d.Eout, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (method == 2) MVBA_HIP(hipMemcpyAsync(&fl, h->ddflag, sizeof(int), hipMemcpyDeviceToHost, st));
+  MVBA_HIP(hipStreamSynchronize(st));
+  if (fl) return fail(MVBA_ERR_SINGULAR, "depth iteration: an image's 12 x 12 companion matrix has no positive eigenvalue");
+  return MVBA_OK;
+}
+
+// A depth step: factorise the base re-weighted by the depths in dz, update the depths by the method, finish.  This form factorises
+// through dW (any dtype, any image count up to DEPTH_MAX_IMAGES) ...
 template <typename T>
 int depth_step(mvsvd_handle *h, int method, double f0, double *E, double *timings) {
   const int n = h->n, m = n / 3;
@@ -2610,90 +2678,37 @@ int depth_step(mvsvd_handle *h, int method, double f0, double *E, double *timing
   const long long rpb = (rows + dual_blocks - 1) / dual_blocks;
   const int gblocks = (int)((rows + rpb - 1) / rpb);
   DepthScratch d;
-  if ((rc = depth_scratch(h, (size_t)dual_blocks * dsplit * 14 * m * 6, &d))) return rc;
-  double *Epart = d.Epart, *Eout = d.Eout, *G12 = d.G12, *V12 = d.V12, *colsum = d.colsum, *w12 = d.w12, *gpart = d.own;  // (own: the dual partials)
-  const int pgrid = (int)std::max<long long>(1, std::min<long long>(DEPTH_BLOCKS, (rows + 255) / 256));
-  const bool tiled = tile_fits<T>(n + m) && 24 * m * sizeof(double) <= 24 * 1024;  // the rows go through LDS tiles (coalesced) while they fit
-  const size_t tile_bytes = sizeof(T) * 4 * 64 * (size_t)((n + m) | 1) + 16;
+  if ((rc = depth_scratch(h, (size_t)dual_blocks * dsplit * 14 * m * 6, &d))) return rc;  // (own: the dual partials)
+  const int pgrid = depth_grid(rows);
+  const bool tiled = depth_tiled(sizeof(T), m);
+  const T *dX = (const T *)h->dX, *dS = (const T *)h->dS;
   hipStream_t st = h->st;
   hipEventRecord(h->ev[6], st);
   if (method == 1) {
-    if (tiled)
-      hipLaunchKernelGGL((k_depth_primary<T, true>), dim3(pgrid), dim3(256), sizeof(double) * 12 * m + tile_bytes, st, (const T *)h->dX, h->dMr,
-                         (const T *)h->dS, rows, m, (T *)h->dz, Epart);
-    else
-      hipLaunchKernelGGL(k_depth_primary_wide<T>, dim3(pgrid), dim3(256), sizeof(double) * (12 * (size_t)m + 4 * 64 * 14), st, (const T *)h->dX, h->dMr,
-                         (const T *)h->dS, rows, m, (T *)h->dz, Epart);
+    hipLaunchKernelGGL(depth_primary_kernel<T>(tiled), dim3(pgrid), dim3(256), tiled ? depth_primary_lds(sizeof(T), m) : depth_primary_wide_lds(m), st, dX, h->dMr, dS,
+                       rows, m, (T *)h->dz, d.Epart);
   } else {
     double is[4];
-    for (int i = 0; i < 4; ++i) {
-      if (!((double)sigma[i] > 0.0)) return fail(MVBA_ERR_SINGULAR, "measurement matrix has rank < 4");
-      is[i] = 1.0 / (double)sigma[i];
-    }
+    if ((rc = inverse_sigmas({(double)sigma[0], (double)sigma[1], (double)sigma[2], (double)sigma[3]}, is))) return rc;
     MVBA_HIP(hipMemsetAsync(h->ddflag, 0, sizeof(int), st));
     const int dg_rows = dual_gram_rows(m);  // (128 up to 47 images, 24 at 256: the launch used to FAIL from 48 images on)
-    hipLaunchKernelGGL(k_dual_gram<T>, dim3(gblocks), dim3(256), sizeof(double) * ((size_t)dg_rows * ((n | 1) + 4)), st, (const T *)h->dX, (const T *)h->dS,
-                       is[0], is[1], is[2], is[3], rows, m, rpb, dg_rows, gpart);
-    hipLaunchKernelGGL(k_dual_reduce, dim3((14 * m * 6 + 3) / 4), dim3(256), 0, st, gpart, gblocks * dsplit, m, G12, colsum);
-    hipLaunchKernelGGL(k_jacobi_small, dim3(m), dim3(JHB * JHB + JW * 6), 0, st, G12, V12, 12, 60, 1e-15, h->ddflag + 1);
-    hipLaunchKernelGGL(k_dual_vec, dim3((m + 63) / 64), dim3(64), 0, st, G12, V12, colsum, m, w12, h->ddflag);
-    if (tiled)
-      hipLaunchKernelGGL((k_dual_apply<T, true>), dim3(pgrid), dim3(256), sizeof(double) * 24 * m + tile_bytes, st, (const T *)h->dX, (const T *)h->dS,
-                         is[0], is[1], is[2], is[3], h->dMr, w12, rows, m, (T *)h->dz, Epart);
-    else
-      hipLaunchKernelGGL(k_dual_apply_wide<T>, dim3(pgrid), dim3(256), sizeof(double) * 24 * m, st, (const T *)h->dX, (const T *)h->dS,
-                         is[0], is[1], is[2], is[3], h->dMr, w12, rows, m, (T *)h->dz, Epart);
+    hipLaunchKernelGGL(dual_gram_kernel<T>(), dim3(gblocks), dim3(256), dual_gram_lds(m, dg_rows), st, dX, dS, is[0], is[1], is[2], is[3], rows, m, rpb, dg_rows, d.own);
+    dual_companion(h, d, m, false, gblocks * dsplit);
+    hipLaunchKernelGGL(dual_apply_kernel<T>(tiled), dim3(pgrid), dim3(256), tiled ? dual_apply_lds(sizeof(T), m) : dual_apply_wide_lds(m), st, dX, dS,
+                       is[0], is[1], is[2], is[3], h->dMr, d.w12, rows, m, (T *)h->dz, d.Epart);
   }
-  hipLaunchKernelGGL(k_depth_error, dim3(1), dim3(64), 0, st, Epart, pgrid, (double)rows * (double)m, f0, Eout);
-  hipEventRecord(h->ev[7], st);
-  MVBA_HIP(hipGetLastError());
-  int fl = 0;
-  MVBA_HIP(hipMemcpyAsync(E, Eout, sizeof(double), hipMemcpyDeviceToHost, st));
-  if (method == 2) MVBA_HIP(hipMemcpyAsync(&fl, h->ddflag, sizeof(int), hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipStreamSynchronize(st));
-  if (fl) return fail(MVBA_ERR_SINGULAR, "depth iteration: an image's 12 x 12 companion matrix has no positive eigenvalue");
+  if ((rc = finish_depth_step(h, d, pgrid, method, f0, E))) return rc;
   if (timings) timings[0] = event_ms(h, 6, 7);  // (no upload in a depth step: slot 0 carries the depth-update kernels instead)
   return MVBA_OK;
 }
-// The iteration without the re-weighted matrix (see k_gram_xz): fp64, n = 3 m <= 32 columns, n even.
+
+// ... and this one never writes the re-weighted matrix (see k_gram_xz): fp64, n = 3 m <= 32 columns, n even.
 bool fused_depth_ok(const mvsvd_handle *h) {
   return h->dtype == 1 && h->n <= 32 && h->n % 2 == 0 && h->n / 3 <= FZ_MAXM && h->base_rows >= 256 && !getenv("MVSVD_DEPTH_UNFUSED");
 }
-
-template <int M, int NORM>
-void launch_gram_xz(mvsvd_handle *h, bool rot, int chunks, const double *cs) {
-  constexpr int n = 3 * M, m = M, MODE = n <= 16 ? 1 : (n <= 24 ? 2 : 3);
-  constexpr int NP = MODE == 1 ? 1 : (MODE == 2 ? 2 : 3);
-  const size_t lds = std::max<size_t>(sizeof(double) * (size_t)GRAM_ROWS * ((rot ? 2 : 1) * n + 2 * m), (size_t)NP * 8192);  // (LDS limit: mvsvd_create)
-  if (rot)
-    hipLaunchKernelGGL((k_gram_xz<M, NORM, true>), dim3(1, chunks), dim3(256), lds, h->st, (const double *)h->dX, (const double *)h->dz, h->base_rows, n, m, cs,
-                       (const double *)h->dV1, h->dpart);
-  else
-    hipLaunchKernelGGL((k_gram_xz<M, NORM, false>), dim3(1, chunks), dim3(256), lds, h->st, (const double *)h->dX, (const double *)h->dz, h->base_rows, n, m, cs,
-                       (const double *)nullptr, h->dpart);
-  const int n_tiles = (n + GT - 1) / GT, slices = std::min(chunks, GRAM_SLICES);
-  hipLaunchKernelGGL(k_gram_reduce, dim3(NP, slices), dim3(256), 0, h->st, h->dpart, chunks, NP, h->dpart2);
-  hipLaunchKernelGGL(k_gram_finish, dim3((n + 127) / 128, n), dim3(128), 0, h->st, h->dpart2, slices, NP, n_tiles, MODE == 2 ? 1 : 0, h->dG, n);
-}
-template <int NORM>
-void gram_xz_m(mvsvd_handle *h, bool rot, int chunks, const double *cs) {
-  switch (h->n / 3) {
-    case 2: launch_gram_xz<2, NORM>(h, rot, chunks, cs); break;
-    case 4: launch_gram_xz<4, NORM>(h, rot, chunks, cs); break;
-    case 6: launch_gram_xz<6, NORM>(h, rot, chunks, cs); break;
-    case 8: launch_gram_xz<8, NORM>(h, rot, chunks, cs); break;
-    default: launch_gram_xz<10, NORM>(h, rot, chunks, cs); break;
-  }
-}
-void gram_xz(mvsvd_handle *h, int norm, bool rot, int chunks, const double *cs) {
-  if (norm == 1) gram_xz_m<1>(h, rot, chunks, cs);
-  else gram_xz_m<2>(h, rot, chunks, cs);
-}
-
 int depth_step_fused(mvsvd_handle *h, int method, double f0, double *E, double *timings) {
   const int n = h->n, m = n / 3;
   const long long rows = h->base_rows;
-  const size_t nn = (size_t)n * n;
   hipStream_t st = h->st;
   const double *dX = (const double *)h->dX;
   double *dz = (double *)h->dz;
@@ -2702,70 +2717,79 @@ int depth_step_fused(mvsvd_handle *h, int method, double f0, double *E, double *
   const size_t dual_part = (size_t)512 * 4 * m * 256;  // k_dual_gram_mfma: a 16 x 16 tile per wave and image, at most 512 workgroups
   DepthScratch d;
   if (int rc = depth_scratch(h, dual_part + (size_t)FZ_MAXM * DEPTH_BLOCKS, &d)) return rc;
-  double *Epart = d.Epart, *Eout = d.Eout, *G12 = d.G12, *V12 = d.V12, *colsum = d.colsum, *w12 = d.w12, *gpart = d.own, *gsum = gpart + dual_part;
+  double *gsum = d.own + dual_part;  // (own: the dual partials, then the images' sums of the next scales)
   if (method == 2 && !h->cs_valid) {  // the per-image scales of the depths the loop holds (first dual step, or after primary steps)
-    const int gb = (int)std::max<long long>(1, std::min<long long>(GS_BLOCKS, rows / 64 + 1));
-    hipLaunchKernelGGL(k_group_sumsq<double>, dim3(gb), dim3(256), 0, st, dX, (const double *)dz, rows, n, 3, h->dgs);
-    hipLaunchKernelGGL(k_group_scale, dim3((m + 3) / 4), dim3(256), 0, st, h->dgs, gb, m, cs);
+    launch_group_scales<double>(h, 3, cs);
     h->cs_valid = true;
   }
   const int chunks = chunks_for(rows, n);
   hipEventRecord(h->ev[1], st);
-  gram_xz(h, method, false, chunks, cs);
+  launch_gram_xz(h, method, false, chunks, cs);
   hipEventRecord(h->ev[2], st);
   launch_jacobi(h, h->dV1, 1e-15);
   hipEventRecord(h->ev[3], st);
-  gram_xz(h, method, true, chunks, cs);  // B = W V1 never leaves the LDS
-  launch_jacobi(h, h->dMr, 1e-15);
-  hipLaunchKernelGGL(k_rotate<double>, dim3((n + 63) / 64, (n + 63) / 64), dim3(256), 0, st, h->dV1, (long long)n, n, (const double *)nullptr, h->dMr, h->dV);
+  launch_gram_xz(h, method, true, chunks, cs);  // B = W V1 never leaves the LDS
+  second_jacobi(h);
   hipEventRecord(h->ev[4], st);
-  // eigenvalues -> host, sort, the rank-4 basis (select_basis, as mvsvd_run)
-  std::vector<double> hG(nn), hV(nn), Mg((size_t)n * 4);
-  MVBA_HIP(hipMemcpyAsync(hG.data(), h->dG, sizeof(double) * nn, hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipMemcpyAsync(hV.data(), h->dV, sizeof(double) * nn, hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipStreamSynchronize(st));
-  Basis basis;
-  if (int rc = select_basis(hG.data(), hV.data(), n, n, 4, basis)) return rc;
-  double is[4];
-  for (int i = 0; i < 4; ++i) {
-    const double sg2 = hG[(size_t)basis.order[i] * n + basis.order[i]];
-    if (method == 2 && !(sg2 > 0.0)) return fail(MVBA_ERR_SINGULAR, "measurement matrix has rank < 4");
-    is[i] = 1.0 / std::sqrt(std::max(sg2, 1e-300));
-  }
-  basis_block(basis, hV.data(), n, n, 0, 4, Mg.data());
+  HostBasis b;
+  if (int rc = read_basis(h, h->dG, h->dV, n, 4, false, b)) return rc;
+  std::vector<double> Mg((size_t)n * 4);
+  double sigma[4], is[4];
+  for (int i = 0; i < 4; ++i) sigma[i] = std::sqrt(std::max(0.0, b.D[(size_t)b.basis.order[i] * n + b.basis.order[i]]));
+  if (method == 2)
+    if (int rc = inverse_sigmas(sigma, is)) return rc;
+  basis_block(b.basis, b.V.data(), n, n, 0, 4, Mg.data());
   MVBA_HIP(hipMemcpyAsync(h->dMr, Mg.data(), sizeof(double) * (size_t)n * 4, hipMemcpyHostToDevice, st));
-  const int pgrid = (int)std::max<long long>(1, std::min<long long>(DEPTH_BLOCKS, (rows + 255) / 256));
-  const size_t tile_bytes = sizeof(double) * 4 * 64 * (size_t)((n + m) | 1) + 16;
+  const int pgrid = depth_grid(rows);
   hipEventRecord(h->ev[6], st);
   if (method == 1) {
-    hipLaunchKernelGGL(k_primary_xz, dim3(pgrid), dim3(256), sizeof(double) * 12 * m + tile_bytes, st, dX, h->dMr, rows, m, dz, Epart);
+    hipLaunchKernelGGL(primary_xz_kernel(), dim3(pgrid), dim3(256), depth_primary_lds(sizeof(double), m), st, dX, h->dMr, rows, m, dz, d.Epart);
     h->cs_valid = false;
   } else {
     MVBA_HIP(hipMemsetAsync(h->ddflag, 0, sizeof(int), st));
     const int mblocks = (int)std::max<long long>(1, std::min<long long>(512, (rows + GRAM_ROWS - 1) / GRAM_ROWS));  // two workgroups per CU
-    const size_t mlds = sizeof(double) * (12 * (size_t)m + 4 * ((size_t)ROWS_PER_STEP * (n + m + 4) + 4 * ((size_t)ROWS_PER_STEP * (m | 1) + 8)));
-    auto dual_gram = m == 2 ? k_dual_gram_mfma<2> : (m == 4 ? k_dual_gram_mfma<4> : (m == 6 ? k_dual_gram_mfma<6> : (m == 8 ? k_dual_gram_mfma<8> : k_dual_gram_mfma<10>)));
-    hipLaunchKernelGGL(dual_gram, dim3(mblocks), dim3(256), mlds, st, dX, (const double *)dz, cs, h->dMr, is[0], is[1], is[2], is[3], rows, m, gpart);
-    hipLaunchKernelGGL(k_dual_reduce_mfma, dim3((m * 90 + 3) / 4), dim3(256), 0, st, gpart, mblocks * 4, m, G12, colsum);
-    hipLaunchKernelGGL(k_jacobi_small, dim3(m), dim3(JHB * JHB + JW * 6), 0, st, G12, V12, 12, 60, 1e-15, h->ddflag + 1);
-    hipLaunchKernelGGL(k_dual_vec, dim3((m + 63) / 64), dim3(64), 0, st, G12, V12, colsum, m, w12, h->ddflag);
-    hipLaunchKernelGGL(k_dual_apply_xz, dim3(pgrid), dim3(256), sizeof(double) * 24 * m + tile_bytes, st, dX, cs, is[0], is[1], is[2], is[3], h->dMr, w12, rows, m,
-                       dz, Epart, gsum);
+    hipLaunchKernelGGL(dual_gram_mfma_kernel(m), dim3(mblocks), dim3(256), dual_gram_mfma_lds(m), st, dX, (const double *)dz, cs, h->dMr, is[0], is[1], is[2], is[3], rows,
+                       m, d.own);
+    dual_companion(h, d, m, true, mblocks * 4);
+    hipLaunchKernelGGL(dual_apply_xz_kernel(), dim3(pgrid), dim3(256), dual_apply_lds(sizeof(double), m), st, dX, cs, is[0], is[1], is[2], is[3], h->dMr, d.w12, rows, m,
+                       dz, d.Epart, gsum);
     hipLaunchKernelGGL(k_group_scale_t, dim3((m + 3) / 4), dim3(256), 0, st, gsum, pgrid, m, cs);  // the next iteration's scales
   }
-  hipLaunchKernelGGL(k_depth_error, dim3(1), dim3(64), 0, st, Epart, pgrid, (double)rows * (double)m, f0, Eout);
-  hipEventRecord(h->ev[7], st);
-  MVBA_HIP(hipGetLastError());
-  int fl = 0;
-  MVBA_HIP(hipMemcpyAsync(E, Eout, sizeof(double), hipMemcpyDeviceToHost, st));
-  if (method == 2) MVBA_HIP(hipMemcpyAsync(&fl, h->ddflag, sizeof(int), hipMemcpyDeviceToHost, st));
-  MVBA_HIP(hipStreamSynchronize(st));
+  const int rc = finish_depth_step(h, d, pgrid, method, f0, E);
   h->loaded = false;  // (no re-weighted matrix was written: dW holds nothing that belongs to these depths)
-  if (fl) return fail(MVBA_ERR_SINGULAR, "depth iteration: an image's 12 x 12 companion matrix has no positive eigenvalue");
+  if (rc) return rc;
   if (timings) {  // depth update | first Gram pass | Jacobi (first pass) | (no projection pass) | refinement pass (rotate + Gram fused, Jacobi, V1 V2)
     read_timings(h, timings, {{6, 7}, {1, 2}, {2, 3}, {-1, -1}, {-1, -1}, {3, 4}});
     timings[4] = jacobi_sweeps(h);
   }
+  return MVBA_OK;
+}
+
+// mvsvd_create: every kernel that may ask for more than LDS_DEFAULT is raised to its limit (mvba_host.h), by walking the tables
+int set_lds_limits() {
+  auto raise = [](auto kernel, size_t limit) { return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit); };
+  MVBA_HIP(raise(jacobi_kernel(JACOBI_LDS_ORDER), JACOBI_LDS_MAX));
+  MVBA_HIP(raise(primary_xz_kernel(), DEPTH_LDS_MAX));
+  MVBA_HIP(raise(dual_apply_xz_kernel(), DEPTH_LDS_MAX));
+  for (int m = 2; m <= FZ_MAXM; m += 2) {
+    MVBA_HIP(raise(dual_gram_mfma_kernel(m), DEPTH_LDS_MAX));
+    for (int norm : {1, 2})
+      for (bool rot : {false, true}) MVBA_HIP(raise(gram_xz_kernel(m, norm, rot), DEPTH_LDS_MAX));
+  }
+  for (int dtype : {0, 1})
+    if (int rc = with_dtype(dtype, [&](auto tag) -> int {
+          using T = decltype(tag);
+          MVBA_HIP(raise(rotate_rows_kernel<T>(), ROTATE_LDS_MAX));
+          MVBA_HIP(raise(project_kernel<T>(), PROJECT_LDS_MAX));
+          MVBA_HIP(raise(scale_rows_kernel<T>(true), DEPTH_LDS_MAX));  // (the other form takes no dynamic LDS)
+          MVBA_HIP(raise(dual_gram_kernel<T>(), DEPTH_LDS_MAX));
+          for (bool tiled : {false, true}) {
+            MVBA_HIP(raise(depth_primary_kernel<T>(tiled), DEPTH_LDS_MAX));
+            MVBA_HIP(raise(dual_apply_kernel<T>(tiled), DEPTH_LDS_MAX));
+          }
+          return MVBA_OK;
+        }))
+      return rc;
   return MVBA_OK;
 }
 
@@ -2777,7 +2801,7 @@ int create_workspace(mvsvd_handle *h, int64_t max_rows, int32_t n_cols, int32_t 
   h->wide = wide;
   const size_t el = dtype ? 8 : 4, nn = dense ? (size_t)n_cols * n_cols : (size_t)WB * WB;
   const int gram_n = dense ? n_cols : WB;  // the Gram kernels run on the workspace's matrix and on the wide path's 32-column blocks
-  const int n_tiles = (gram_n + GT - 1) / GT, n_pairs = n_tiles * (n_tiles + 1) / 2;
+  const int n_pairs = gram_tiles(gram_n) * (gram_tiles(gram_n) + 1) / 2;
   h->chunks = chunks_for(max_rows, gram_n);
   // partial tiles of the Gram kernels: the workspace's own matrix and / or the wide path's blocks (N x 32 and n x 32: three tile pairs)
   size_t part_tiles = (size_t)h->chunks * n_pairs, part2_tiles = (size_t)GRAM_SLICES * n_pairs;
@@ -2814,22 +2838,23 @@ int create_workspace(mvsvd_handle *h, int64_t max_rows, int32_t n_cols, int32_t 
     alloc(h->dwflag, 2 * WB);
   }
   if (rc) return rc;
-  MVBA_HIP(hipFuncSetAttribute((const void *)k_jacobi<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-  MVBA_HIP(hipFuncSetAttribute((const void *)k_project<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-  MVBA_HIP(hipFuncSetAttribute((const void *)k_rotate_rows<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  MVBA_HIP(hipFuncSetAttribute((const void *)k_rotate_rows<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  MVBA_HIP(hipFuncSetAttribute((const void *)k_project<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-  for (const void *f : {(const void *)k_scale_rows_tiled<float>, (const void *)k_scale_rows_tiled<double>, (const void *)k_depth_primary<float, true>,
-                        (const void *)k_depth_primary<double, true>, (const void *)k_dual_apply<float, true>, (const void *)k_dual_apply<double, true>,
-                        (const void *)k_dual_gram<float>, (const void *)k_dual_gram<double>, (const void *)k_primary_xz, (const void *)k_dual_gram_mfma<2>, (const void *)k_dual_gram_mfma<4>, (const void *)k_dual_gram_mfma<6>, (const void *)k_dual_gram_mfma<8>,
-                        (const void *)k_dual_gram_mfma<10>,
-                        (const void *)k_dual_apply_xz, (const void *)k_depth_primary_wide<float>, (const void *)k_depth_primary_wide<double>,
-                        (const void *)k_dual_apply_wide<float>, (const void *)k_dual_apply_wide<double>,
-                        // k_gram_xz of the fused depth iteration, every image count and norm (the refinement form of 10 images stages 80 KiB)
-#define GRAM_XZ_M(M) (const void *)k_gram_xz<M, 1, false>, (const void *)k_gram_xz<M, 1, true>, (const void *)k_gram_xz<M, 2, false>, (const void *)k_gram_xz<M, 2, true>
-                        GRAM_XZ_M(2), GRAM_XZ_M(4), GRAM_XZ_M(6), GRAM_XZ_M(8), GRAM_XZ_M(10)})
-#undef GRAM_XZ_M
-    MVBA_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DEPTH_LDS_MAX));
+  return set_lds_limits();
+}
+
+// run() on the caller's arrays of the workspace's dtype
+int run_any(mvsvd_handle *h, int n_rank, int center, void *M, void *sigma, void *S, void *means, double *timings) {
+  return with_dtype(h->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return run<T>(h, n_rank, center, (T *)M, (T *)sigma, (T *)S, (T *)means, timings);
+  });
+}
+// argument checks the entry points share
+int check_rows(const mvsvd_handle *h, int64_t n_rows) {
+  return n_rows < 1 || n_rows > h->max_rows ? fail(MVBA_ERR_BADARG, "n_rows outside the workspace (1 .. max_rows)") : MVBA_OK;
+}
+int check_images(const void *const *xy, int n_images) {
+  for (int k = 0; k < n_images; ++k)
+    if (!xy[k]) return fail(MVBA_ERR_BADARG, "null image array");
   return MVBA_OK;
 }
 
@@ -2865,7 +2890,7 @@ void mvsvd_destroy(mvsvd_handle *h) {
 
 int mvsvd_load(mvsvd_handle *h, const void *Wt, int64_t n_rows) {
   if (!h || !Wt) return fail(MVBA_ERR_BADARG, "null argument");
-  if (n_rows < 1 || n_rows > h->max_rows) return fail(MVBA_ERR_BADARG, "n_rows outside the workspace (1 .. max_rows)");
+  if (int rc = check_rows(h, n_rows)) return rc;
   MVBA_HIP(hipSetDevice(h->device));
   hipEventRecord(h->ev[0], h->st);
   MVBA_HIP(hipMemcpyAsync(h->dW, Wt, el_bytes(h) * (size_t)n_rows * h->n, hipMemcpyHostToDevice, h->st));
@@ -2878,11 +2903,10 @@ int mvsvd_load(mvsvd_handle *h, const void *Wt, int64_t n_rows) {
 
 int mvsvd_load_images(mvsvd_handle *h, const void *const *xy, int32_t n_images, int64_t n_rows, int32_t src_dtype) {
   if (!h || !xy) return fail(MVBA_ERR_BADARG, "null argument");
-  if (n_rows < 1 || n_rows > h->max_rows) return fail(MVBA_ERR_BADARG, "n_rows outside the workspace (1 .. max_rows)");
+  if (int rc = check_rows(h, n_rows)) return rc;
   if (n_images < 1 || 2 * (long long)n_images != h->n) return fail(MVBA_ERR_BADARG, "the workspace must have 2 columns per image");
   if (src_dtype != 0 && src_dtype != 1) return fail(MVBA_ERR_BADARG, "src_dtype must be 0 (float32) or 1 (float64)");
-  for (int k = 0; k < n_images; ++k)
-    if (!xy[k]) return fail(MVBA_ERR_BADARG, "null image array");
+  if (int rc = check_images(xy, n_images)) return rc;
   MVBA_HIP(hipSetDevice(h->device));
   if (int rc = need_stage(h)) return rc;
   const size_t bytes = (src_dtype ? 16 : 8) * (size_t)n_rows;
@@ -2911,15 +2935,12 @@ int mvsvd_run(mvsvd_handle *h, int32_t n_rank, int32_t center, void *M, void *si
   if (!h->loaded) return fail(MVBA_ERR_STATE, "mvsvd_run before mvsvd_load");
   if (n_rank < 1 || n_rank > h->n) return fail(MVBA_ERR_BADARG, "need 1 <= n_rank <= n_cols");
   MVBA_HIP(hipSetDevice(h->device));
-  return with_dtype(h->dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return run<T>(h, n_rank, center, (T *)M, (T *)sigma, (T *)S, (T *)means, timings_ms);
-  });
+  return run_any(h, n_rank, center, M, sigma, S, means, timings_ms);
 }
 
 int mvsvd_load_base(mvsvd_handle *h, const void *X, int64_t n_rows) {
   if (!h || !X) return fail(MVBA_ERR_BADARG, "null argument");
-  if (n_rows < 1 || n_rows > h->max_rows) return fail(MVBA_ERR_BADARG, "n_rows outside the workspace (1 .. max_rows)");
+  if (int rc = check_rows(h, n_rows)) return rc;
   MVBA_HIP(hipSetDevice(h->device));
   if (int rc = need_base(h)) return rc;
   MVBA_HIP(hipMemcpyAsync(h->dX, X, el_bytes(h) * (size_t)n_rows * h->n, hipMemcpyHostToDevice, h->st));
@@ -2930,11 +2951,10 @@ int mvsvd_load_base(mvsvd_handle *h, const void *X, int64_t n_rows) {
 
 int mvsvd_load_base_images(mvsvd_handle *h, const double *const *xy, int32_t n_images, int64_t n_rows, double f0) {
   if (!h || !xy) return fail(MVBA_ERR_BADARG, "null argument");
-  if (n_rows < 1 || n_rows > h->max_rows) return fail(MVBA_ERR_BADARG, "n_rows outside the workspace (1 .. max_rows)");
+  if (int rc = check_rows(h, n_rows)) return rc;
   if (n_images < 1 || 3 * (long long)n_images != h->n) return fail(MVBA_ERR_BADARG, "the workspace must have 3 columns per image");
   if (!(f0 != 0.0) || !std::isfinite(f0)) return fail(MVBA_ERR_BADARG, "f0 must be finite and non-zero");
-  for (int k = 0; k < n_images; ++k)
-    if (!xy[k]) return fail(MVBA_ERR_BADARG, "null image array");
+  if (int rc = check_images((const void *const *)xy, n_images)) return rc;
   MVBA_HIP(hipSetDevice(h->device));
   if (int rc = need_base(h)) return rc;
   // staged through dW (16 bytes a row <= el * n: there are at least 6 columns), image after image in stream order
@@ -2973,10 +2993,7 @@ int mvsvd_run_scaled(mvsvd_handle *h, const void *z, int32_t group, int32_t norm
   if (rc) return rc;
   MVBA_HIP(hipStreamSynchronize(h->st));
   h->h2d_ms = event_ms(h, 0, 1);
-  return with_dtype(h->dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return run<T>(h, n_rank, 0, (T *)M, (T *)sigma, (T *)S, (T *)nullptr, timings_ms);
-  });
+  return run_any(h, n_rank, 0, M, sigma, S, nullptr, timings_ms);
 }
 
 int mvsvd_depth_begin(mvsvd_handle *h, int32_t group) {
