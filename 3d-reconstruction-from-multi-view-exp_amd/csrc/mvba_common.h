@@ -23,6 +23,28 @@ inline int fail(int code, const std::string &msg) {
       return ::mvba::fail(MVBA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
   } while (0)
 
+// The engine's status word (d_flag on the device, h_flag beside the cost on the host): kernels OR bits in, the host reads them
+// after the step and clears the word.  The ranks of a distributed run exchange the word, so the values are fixed.
+enum : int {
+  FLAG_POINT_SINGULAR = 1,  // k_point_inv: a point block E_a is singular
+  FLAG_NOT_POSDEF = 2,      // k_chol_super: a pivot is not positive -> the LU rescue
+  FLAG_LU_SINGULAR = 4,     // k_lu_panel: exactly singular (LAPACK's info > 0)
+  FLAG_WAIT_GAVE_UP = 8,    // k_chol_backsolve_all: a wait for a progress word gave up -> one launch per super-block
+  FLAG_COV_POINT = 16,      // k_point_cov: a numerically singular E_a in the covariance's point pass
+};
+static_assert(FLAG_POINT_SINGULAR == 1 && FLAG_NOT_POSDEF == 2 && FLAG_LU_SINGULAR == 4 && FLAG_WAIT_GAVE_UP == 8 && FLAG_COV_POINT == 16,
+              "the status bits travel between ranks and builds");
+
+// t-th tile of a lower triangle numbered row by row (t = row (row + 1) / 2 + col, col <= row): the float root is off by at
+// most one either way, the two loops correct it.
+__device__ __forceinline__ void tri_tile(int t, int &row, int &col) {
+  int r = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
+  while (r * (r + 1) / 2 > t) --r;
+  while ((r + 1) * (r + 2) / 2 <= t) ++r;
+  row = r;
+  col = t - r * (r + 1) / 2;
+}
+
 // Per-camera record as the kernels keep it in LDS.  18 doubles = 9 quad-words, rows 16-byte aligned: a lane takes its
 // camera's row in nine 16-byte reads (ds_read_b128), and nine being odd the rows of 16 different cameras start in 16
 // different bank quads.  (Rounds 1-3: 19 doubles read 8 bytes at a time -- 27 reads per observation in the

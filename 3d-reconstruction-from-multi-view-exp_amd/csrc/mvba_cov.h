@@ -1,7 +1,7 @@
 // Marginal covariances at the BA solution (mvba_covariance) -- kernels, gfx950.
 //
-// Included by mvba.hip inside its device-code namespace, after the K4 kernels: uses NB, SBW, strip_offset, keep_index,
-// mvba_d4, REC and the Cholesky factor k_chol_super leaves behind.  Nothing here runs on the LM path.
+// Included by mvba.hip inside its device-code namespace, after the K4 kernels (mvba_solve.h): uses NB, SBW, strip_offset, keep_index,
+// tri_tile, mvba_d4, REC and the Cholesky factor k_chol_super leaves behind.  Nothing here runs on the LM path.
 //
 // After K4's factorisation of the gauge-reduced S = L L^T (no back-substitution) the factor is spread over three places:
 //   M (d_Ared)   rows below each 128-column super-block: L
@@ -22,7 +22,6 @@
 // with the implied record columns (u, v) -> 1/f0, t -> -Jx.  No atomics on floating-point data: every sum has a fixed order.
 
 constexpr int SIG_BS = 82;  // doubles per camera block of the covariance table (81 + one pad)
-constexpr int COV_FLAG_POINT = 16;  // d_flag bit: a numerically singular E_a in the point pass
 
 __host__ __device__ __forceinline__ size_t sig_block(int k, int l, int m) {
   return (size_t)SIG_BS * ((size_t)k * m - (size_t)k * (k - 1) / 2 + (size_t)(l - k));
@@ -128,10 +127,8 @@ __global__ __launch_bounds__(256) void k_cov_lauum(const double *__restrict__ M,
                                                    double *__restrict__ sig) {
   __shared__ double part[4][NB][NB + 1];
   const int t = blockIdx.x, tid = threadIdx.x;
-  int J = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
-  while (J * (J + 1) / 2 > t) --J;
-  while ((J + 1) * (J + 2) / 2 <= t) ++J;
-  const int I = t - J * (J + 1) / 2;
+  int J, I;
+  tri_tile(t, J, I);
   const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   const mvba_d4 zero4 = {0.0, 0.0, 0.0, 0.0};
   mvba_d4 acc[2][2] = {{zero4, zero4}, {zero4, zero4}};
@@ -184,7 +181,7 @@ __global__ __launch_bounds__(256) void k_cov_cam_diag(int m, const double *__res
 // its point (pairs numbered j (j+1) / 2 + i), gathers the two records and the camera block Sigma_{k_i k_j}, and accumulates the
 // symmetric part of Jx_i^T (Jc_i Sigma Jc_j^T) Jx_j (counted twice for i < j) in six registers; the group sums them with a
 // fixed butterfly and its first lane finishes C_a.  A point whose E_a has a Cholesky pivot below 1e-12 of its largest
-// diagonal entry (e.g. a point seen once) sets COV_FLAG_POINT.
+// diagonal entry (e.g. a point seen once) sets FLAG_COV_POINT.
 // Held points (mvba_set_point_hold): the instantiation with one trailing `const uint8_t *held` [N] gives a held point no pairs
 // and no pivot test, and writes six zeros for it -- a point that is not an unknown has no covariance.
 template <int G, typename... Held>
@@ -283,7 +280,7 @@ __global__ __launch_bounds__(256) void k_point_cov(long long N, int m, const lon
       const double m2 = xx * yy - xy * xy;  // LDL^T pivots: xx, m2 / xx, det / m2
       const double big = fmax(xx, fmax(yy, zz)), tol = 1e-12 * big;
       const bool ok = isfinite(det) && xx > tol && m2 > tol * xx && det > tol * m2;
-      if (!ok) atomicOr(flag, COV_FLAG_POINT);
+      if (!ok) atomicOr(flag, FLAG_COV_POINT);
       const double id = 1.0 / det;
       const double e[3][3] = {{c00 * id, c01 * id, c02 * id},
                               {c01 * id, (xx * zz - xz * xz) * id, (xy * xz - xx * yz) * id},

@@ -1,6 +1,6 @@
 // Parameter maps (mvba_set_parameter_map) -- kernels, gfx950.
 //
-// Included by mvba.hip inside its device-code namespace, after mvba_cov.h: uses NB, strip_offset, keep_index, sig_block.
+// Included by mvba.hip inside its device-code namespace, after mvba_cov.h: uses NB, packed_sym, tri_tile, keep_index, sig_block.
 // Nothing here runs while the engine has the default map.
 //
 // A map sends parameter slot g = 9 k + p to a reduced unknown col[g] in [0, D') or holds it (-1); slots with the same
@@ -22,12 +22,6 @@
 //   k_map_cov_expand   Cov = P Sigma' P^T into the camera-block table, one thread per table entry
 // No atomics on floating-point data: every sum has a fixed order, two runs are bitwise equal.
 
-// element (g1, g2) of the symmetric 9m x 9m matrix from the packed upper strips
-__device__ __forceinline__ double map_sym(const double *__restrict__ A, int m, int g1, int g2) {
-  const int r = min(g1, g2), c = max(g1, g2), k = r / 9;
-  return A[strip_offset(k, m) + (size_t)(r - 9 * k) * (9 * (m - k)) + (c - 9 * k)];
-}
-
 // One workgroup per 32 x 32 tile of the lower triangle of the untied corner (nt = ceil(U / 32) tile rows), then one per 256
 // columns of the right-hand-side row.  As k_compact: the packed rows are read along their length and written through a
 // transposing LDS tile.
@@ -47,15 +41,13 @@ __global__ __launch_bounds__(256) void k_map_compact(int D, int ld, int m, int U
     }
     return;
   }
-  int I = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
-  while (I * (I + 1) / 2 > t) --I;
-  while ((I + 1) * (I + 2) / 2 <= t) ++I;
-  const int J = t - I * (I + 1) / 2;
+  int I, J;
+  tri_tile(t, I, J);
   const int gi = mem[mptr[min(NB * I + tx, U - 1)]];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int gj = mem[mptr[min(NB * J + ty + 8 * q, U - 1)]];
-    tile[ty + 8 * q][tx] = map_sym(Afull, m, gi, gj);
+    tile[ty + 8 * q][tx] = packed_sym(Afull, m, gi, gj);
   }
   __syncthreads();
 #pragma unroll
@@ -83,7 +75,7 @@ __global__ __launch_bounds__(256) void k_map_rows(int D, int ld, int m, int U, c
     if (mine)
     for (int q = q0 + s; q < q1; q += 4) {
       const int g = mem[q];
-      for (int p = p0; p < p1; ++p) acc += map_sym(Afull, m, g, mem[p]);
+      for (int p = p0; p < p1; ++p) acc += packed_sym(Afull, m, g, mem[p]);
     }
   }
   part[s][cj] = acc;
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(256) void k_map_tied(int m, const double *__restric
   double acc = 0.0;
   for (int q = blockIdx.y; q < nq; q += gridDim.y) {
     const int g = mem[q0 + q];
-    for (int p = threadIdx.x; p < np; p += 256) acc += map_sym(Afull, m, g, mem[p0 + p]);
+    for (int p = threadIdx.x; p < np; p += 256) acc += packed_sym(Afull, m, g, mem[p0 + p]);
   }
   const double t = block_sum(acc, s_red);
   if (threadIdx.x == 0) part[(size_t)blockIdx.x * gridDim.y + blockIdx.y] = t;
@@ -131,7 +123,7 @@ __global__ void k_map_full(int D, int m, const double *__restrict__ Apk, const d
   for (int q = mptr[i]; q < mptr[i + 1]; ++q) {
     const int g = mem[q];
     if (j == D) { acc += bfull[g]; continue; }
-    for (int p = mptr[j]; p < mptr[j + 1]; ++p) acc += map_sym(Apk, m, g, mem[p]);
+    for (int p = mptr[j]; p < mptr[j + 1]; ++p) acc += packed_sym(Apk, m, g, mem[p]);
   }
   F[(size_t)i * (D + 1) + j] = acc;
 }
