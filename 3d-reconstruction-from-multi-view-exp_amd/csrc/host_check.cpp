@@ -1,5 +1,5 @@
 // The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas) and the host logic of a RANSAC
-// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*) on hand-made inputs.  A program of its own,
+// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*, align_solve) on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
 #include <cmath>
 #include <cstdio>
@@ -243,6 +243,55 @@ int main() {
     laps.write(tm);
     laps.write(nullptr);
     CHECK(tm[0] == 1.0 && tm[1] == 2.0 && tm[2] == 3.0 && tm[3] == 4.0);
+  }
+  {  // align_solve: identity, a known similarity, collinear points, three points, rigid
+    // the moments of pts under y = s Q x + tau (Q: a quarter turn about z), as the two device passes sum them
+    auto moments = [](const double (*x)[3], int n, double s, bool turn, const double *tau, double (&mx)[3], double (&my)[3], double (&mom)[11]) {
+      std::vector<double> y((size_t)3 * n);
+      for (int i = 0; i < n; ++i) {
+        const double q[3] = {turn ? -x[i][1] : x[i][0], turn ? x[i][0] : x[i][1], x[i][2]};
+        for (int e = 0; e < 3; ++e) y[3 * i + e] = s * q[e] + tau[e];
+      }
+      for (int e = 0; e < 3; ++e) mx[e] = my[e] = 0.0;
+      for (int i = 0; i < n; ++i)
+        for (int e = 0; e < 3; ++e) { mx[e] += x[i][e] / n; my[e] += y[3 * i + e] / n; }
+      for (double &m : mom) m = 0.0;
+      for (int i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) {
+          const double xa = x[i][a] - mx[a], ya = y[3 * i + a] - my[a];
+          mom[0] += xa * xa;
+          mom[1] += ya * ya;
+          for (int b = 0; b < 3; ++b) mom[2 + 3 * a + b] += ya * (x[i][b] - mx[b]);
+        }
+    };
+    const double cube[5][3] = {{0, 0, 0}, {1, 0, 0}, {0, 2, 0}, {0, 0, 4}, {1, 1, 1}}, zero[3] = {0, 0, 0}, tau[3] = {10, -3, 4};
+    double mx[3], my[3], mom[11], sim[13], gap;
+    moments(cube, 5, 1.0, false, zero, mx, my, mom);
+    CHECK(align_solve(mx, my, mom, true, sim, gap) == 0 && gap > 0.1);
+    const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    CHECK(std::fabs(sim[0] - 1.0) < 1e-15);
+    for (int e = 0; e < 9; ++e) CHECK(std::fabs(sim[1 + e] - I9[e]) < 1e-15);
+    for (int e = 0; e < 3; ++e) CHECK(std::fabs(sim[10 + e]) < 1e-14);
+    moments(cube, 5, 2.5, true, tau, mx, my, mom);  // s = 2.5, a quarter turn, tau
+    CHECK(align_solve(mx, my, mom, true, sim, gap) == 0);
+    const double Qz[9] = {0, -1, 0, 1, 0, 0, 0, 0, 1};
+    CHECK(std::fabs(sim[0] - 2.5) < 1e-14);
+    for (int e = 0; e < 9; ++e) CHECK(std::fabs(sim[1 + e] - Qz[e]) < 1e-15);
+    for (int e = 0; e < 3; ++e) CHECK(std::fabs(sim[10 + e] - tau[e]) < 1e-13);
+    CHECK(align_solve(mx, my, mom, false, sim, gap) == 0 && sim[0] == 1.0);  // rigid: s is exactly 1, the rotation the same
+    for (int e = 0; e < 9; ++e) CHECK(std::fabs(sim[1 + e] - Qz[e]) < 1e-15);
+    for (int e = 0; e < 3; ++e) CHECK(std::fabs(sim[10 + e] - (my[e] - (Qz[3 * e] * mx[0] + Qz[3 * e + 1] * mx[1] + Qz[3 * e + 2] * mx[2]))) < 1e-14);
+    moments(cube, 3, 2.5, true, tau, mx, my, mom);  // three points: the minimal sample
+    CHECK(align_solve(mx, my, mom, true, sim, gap) == 0 && std::fabs(sim[0] - 2.5) < 1e-14 && std::fabs(sim[2] + 1.0) < 1e-15);
+    const double line[4][3] = {{0, 0.25, 1}, {0.5, 0.5, 0.875}, {1, 0.75, 0.75}, {-2, -0.75, 1.5}};  // on a line: the rotation about it is free
+    moments(line, 4, 2.5, true, tau, mx, my, mom);
+    CHECK(align_solve(mx, my, mom, true, sim, gap) == 2 && gap <= INIT_REL_PIVOT && std::isnan(sim[0]) && std::isnan(sim[12]));
+    const double same[3][3] = {{1, 2, 3}, {1, 2, 3}, {1, 2, 3}};  // coincident: no spread at all
+    moments(same, 3, 2.5, true, tau, mx, my, mom);
+    CHECK(align_solve(mx, my, mom, true, sim, gap) == 2 && std::isnan(gap));
+    moments(cube, 5, 2.5, true, tau, mx, my, mom);
+    mom[4] = std::numeric_limits<double>::quiet_NaN();  // a moment that is not finite
+    CHECK(align_solve(mx, my, mom, true, sim, gap) == 2 && std::isnan(sim[0]));
   }
   if (failures) return 1;
   std::printf("host_check ok\n");

@@ -3326,3 +3326,4 @@ int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2,
 #include "mvba_resect_ransac.h"  // robust resection: mvba_resect_robust, mvba_resect_sample
 #include "mvba_pose_ransac.h"    // calibrated robust resection: mvba_pose_robust, mvba_pose_refine, mvba_pose_sample
 #include "mvba_tri_ransac.h"     // robust triangulation: mvba_triangulate_robust, mvba_triangulate_sample
+#include "mvba_align.h"          // similarity alignment: mvba_align_robust, mvba_align, mvba_align_sample

@@ -1,6 +1,7 @@
 // The host logic of a RANSAC round, once: what mvba_two_view_robust, mvba_resect_robust and mvba_pose_robust decide on plain
 // integers between their kernels (mvba_ransac.h, mvba_resect_ransac.h, mvba_pose_ransac.h), and the chunk list of the
-// listed cameras (mvba_init.h's CamWork).  No HIP call in it: csrc/host_check.cpp runs it under the host sanitizers.
+// listed cameras (mvba_init.h's CamWork); the cyclic Jacobi the start headers share, and align_solve, the similarity fit of
+// mvba_align.h from centred moments.  No HIP call in it: csrc/host_check.cpp runs it under the host sanitizers.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -12,8 +13,10 @@
 
 #if defined(__HIP__)
 #define RS_HD __host__ __device__  // a helper the kernels use too
+#define RS_HD_INLINE __host__ __device__ __forceinline__
 #else
 #define RS_HD
+#define RS_HD_INLINE inline
 #endif
 
 namespace mvba {
@@ -78,6 +81,77 @@ inline bool rs_accept(long long count, long long kept, int r, long long first_mi
   return false;
 }
 
+constexpr double INIT_REL_PIVOT = 1e-12;  // the relative pivot rule of mvba_covariance
+
+// Eigen-decomposition of a symmetric N x N matrix by cyclic Jacobi (Rutishauser's rotations): A -> diagonal, V -> the
+// eigenvectors in its columns.  Every index is a compile-time constant once the loops are unrolled: on the device the
+// order-4 instance lives in registers (the form of mvsvd.hip's per-point solver).  A rotation is skipped once a_pq no
+// longer changes either diagonal entry in floating point.
+template <int N>
+RS_HD_INLINE void sym_eig_jacobi(double (&A)[N][N], double (&V)[N][N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool any = false;
+#pragma unroll
+    for (int p = 0; p < N - 1; ++p)
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
+        const double g = fabs(apq);
+        if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
+          A[p][q] = A[q][p] = 0.0;
+          continue;
+        }
+        any = true;
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+        A[p][p] = app - t * apq;
+        A[q][q] = aqq + t * apq;
+        A[p][q] = A[q][p] = 0.0;
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+          if (r != p && r != q) {
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = A[p][r] = arp - s * (arq + tau * arp);
+            A[r][q] = A[q][r] = arq + s * (arp - tau * arq);
+          }
+          const double vrp = V[r][p], vrq = V[r][q];
+          V[r][p] = vrp - s * (vrq + tau * vrp);
+          V[r][q] = vrq + s * (vrp - tau * vrq);
+        }
+      }
+    if (!any) break;
+  }
+}
+
+// smallest, second-smallest and largest eigenvalue after sym_eig_jacobi, and the column of the smallest
+template <int N>
+RS_HD_INLINE void eig_extremes(const double (&A)[N][N], const double (&V)[N][N], double &l1, double &l2, double &lmax, double (&v)[N]) {
+  int best = 0;
+  l1 = A[0][0];
+  lmax = A[0][0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) {
+    if (A[i][i] < l1) { l1 = A[i][i]; best = i; }
+    lmax = fmax(lmax, A[i][i]);
+  }
+  l2 = HUGE_VAL;
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    if (i != best) l2 = fmin(l2, A[i][i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double x = 0.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) x = j == best ? V[i][j] : x;  // (selects: a run-time column index would put V into scratch)
+    v[i] = x;
+  }
+}
+
 // The homography's host arithmetic between the kernels of mvba_homography_robust (row-major 3 x 3 matrices).
 // adj(M): M adj(M) = det(M) I -- the inverse up to scale, which is all a homography needs
 RS_HD inline void hg_adjugate(const double *m, double *a) {
@@ -108,6 +182,71 @@ inline void hg_mask_parts(const double *H, const double *nm, double *m0, double 
     m0[j] = wk < 0.0 ? -H[j] : H[j];
     if (wl < 0.0) m1[j] = -m1[j];
   }
+}
+
+// Absolute orientation, y ~ s Q x + tau, from centred moments (Horn's quaternion form): mx and my are the two centroids, mom =
+// (sum |x_c|^2, sum |y_c|^2, C row-major with C[a][b] = sum y_c[a] x_c[b]).  q = the eigenvector of the largest eigenvalue of
+// Horn's symmetric 4 x 4 matrix of C, by sym_eig_jacobi<4>: a unit quaternion is a proper rotation, there is no reflection to
+// repair.  s = sum y_c . (Q x_c) / sum |x_c|^2 (1 unless with_scale), tau = my - s Q mx.  sim13 = (s, Q row-major, tau); *gap =
+// (l1 - l2) / l1 of the two largest eigenvalues.  Returns 0, or 2 (sim13 NaN) where a moment is not finite, sum |x_c|^2 or
+// sum |y_c|^2 is not positive, l1 is not positive, the gap fails the relative pivot rule -- the source or the target lies on a
+// line: the rotation about it is free -- or the result is not finite or s is not positive.  In registers on the device: every
+// index is a compile-time constant.
+RS_HD_INLINE int align_solve(const double (&mx)[3], const double (&my)[3], const double (&mom)[11], bool with_scale, double (&sim13)[13],
+                             double &gap) {
+  gap = NAN;
+#pragma unroll
+  for (int e = 0; e < 13; ++e) sim13[e] = NAN;
+  bool fin = mom[0] > 0.0 && mom[1] > 0.0;  // (NaN fails)
+#pragma unroll
+  for (int e = 0; e < 11; ++e) fin = fin && fabs(mom[e]) < HUGE_VAL;
+  if (!fin) return 2;
+  // S[a][b] = sum x_c[a] y_c[b] = C[b][a]; the matrix is negated so that eig_extremes' smallest is Horn's largest
+  const double Sxx = mom[2], Sxy = mom[5], Sxz = mom[8], Syx = mom[3], Syy = mom[6], Syz = mom[9], Szx = mom[4], Szy = mom[7], Szz = mom[10];
+  double A[4][4], V[4][4];
+  A[0][0] = -(Sxx + Syy + Szz);
+  A[1][1] = -(Sxx - Syy - Szz);
+  A[2][2] = -(-Sxx + Syy - Szz);
+  A[3][3] = -(-Sxx - Syy + Szz);
+  A[0][1] = A[1][0] = -(Syz - Szy);
+  A[0][2] = A[2][0] = -(Szx - Sxz);
+  A[0][3] = A[3][0] = -(Sxy - Syx);
+  A[1][2] = A[2][1] = -(Sxy + Syx);
+  A[1][3] = A[3][1] = -(Szx + Sxz);
+  A[2][3] = A[3][2] = -(Syz + Szy);
+  sym_eig_jacobi<4>(A, V);
+  double l1, l2, lmax, q[4];
+  eig_extremes<4>(A, V, l1, l2, lmax, q);
+  l1 = -l1;
+  l2 = -l2;
+  if (!(l1 > 0.0)) return 2;
+  gap = (l1 - l2) / l1;
+  if (!(gap > INIT_REL_PIVOT)) return 2;
+  const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double w = q[0] / qn, x = q[1] / qn, y = q[2] / qn, z = q[3] / qn;
+  const double Q[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z),       2.0 * (x * z + w * y),
+                       2.0 * (x * y + w * z),       1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                       2.0 * (x * z - w * y),       2.0 * (y * z + w * x),       1.0 - 2.0 * (x * x + y * y)};
+  double s = 1.0;
+  if (with_scale) {
+    double num = 0.0;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) num += Q[e] * mom[2 + e];
+    s = num / mom[0];
+  }
+  double out[13];
+  out[0] = s;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) out[1 + e] = Q[e];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[10 + a] = my[a] - s * (Q[3 * a] * mx[0] + Q[3 * a + 1] * mx[1] + Q[3 * a + 2] * mx[2]);
+  fin = s > 0.0;
+#pragma unroll
+  for (int e = 0; e < 13; ++e) fin = fin && fabs(out[e]) < HUGE_VAL;
+  if (!fin) return 2;
+#pragma unroll
+  for (int e = 0; e < 13; ++e) sim13[e] = out[e];
+  return 0;
 }
 
 // the four phases of a robust call, in milliseconds

@@ -3,87 +3,16 @@
 // Included by mvba.hip after its C entry points and before mvba_init.h: uses mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing
 // here runs on the LM path.  
 //
-// One copy each of: the cyclic Jacobi and its eigenvalue selection, the fixed reduction tree of a 256-thread chunk
-// (chunk_sum), the host clock and event guard, the checks of an observation list, of a pair list and of ascending camera
+// One copy each of: the fixed reduction tree of a 256-thread chunk (chunk_sum; the cyclic Jacobi, its eigenvalue selection and
+// INIT_REL_PIVOT are mvba_ransac_host.h's, which the host-side solves use too), the host clock and event guard, the checks of an observation list, of a pair list and of ascending camera
 // runs, and the upload of a list.  Every floating-point sum of these entry points is taken in an order that the sizes alone
 // fix: chunk_sum inside a chunk, then k_resect_combine (serial, ascending chunks) or k_twoview_combine (lane-strided, then
 // the shuffle tree) over a camera's or a pair's chunks -- two orders, on purpose.
 
 namespace {
 
-constexpr double INIT_REL_PIVOT = 1e-12;  // the relative pivot rule of mvba_covariance
 constexpr int INIT_MAX_CAMERAS = 1704;    // (160 KiB - 256 B) / 96 B: the LDS camera table of k_project_obs
 constexpr int START_CHUNK = 256;          // items (observations of a camera, points of a pair) per chunk = threads per workgroup
-
-// Eigen-decomposition of a symmetric N x N matrix by cyclic Jacobi (Rutishauser's rotations): A -> diagonal, V -> the
-// eigenvectors in its columns.  Every index is a compile-time constant once the loops are unrolled: on the device the
-// order-4 instance lives in registers (the form of mvsvd.hip's per-point solver).  A rotation is skipped once a_pq no
-// longer changes either diagonal entry in floating point.
-template <int N>
-__host__ __device__ __forceinline__ void sym_eig_jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    bool any = false;
-#pragma unroll
-    for (int p = 0; p < N - 1; ++p)
-#pragma unroll
-      for (int q = p + 1; q < N; ++q) {
-        const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
-        const double g = fabs(apq);
-        if (!(g > 0.0) || (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq))) {
-          A[p][q] = A[q][p] = 0.0;
-          continue;
-        }
-        any = true;
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-        A[p][p] = app - t * apq;
-        A[q][q] = aqq + t * apq;
-        A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-        for (int r = 0; r < N; ++r) {
-          if (r != p && r != q) {
-            const double arp = A[r][p], arq = A[r][q];
-            A[r][p] = A[p][r] = arp - s * (arq + tau * arp);
-            A[r][q] = A[q][r] = arq + s * (arp - tau * arq);
-          }
-          const double vrp = V[r][p], vrq = V[r][q];
-          V[r][p] = vrp - s * (vrq + tau * vrp);
-          V[r][q] = vrq + s * (vrp - tau * vrq);
-        }
-      }
-    if (!any) break;
-  }
-}
-
-// smallest, second-smallest and largest eigenvalue after sym_eig_jacobi, and the column of the smallest
-template <int N>
-__host__ __device__ __forceinline__ void eig_extremes(const double (&A)[N][N], const double (&V)[N][N], double &l1, double &l2,
-                                                      double &lmax, double (&v)[N]) {
-  int best = 0;
-  l1 = A[0][0];
-  lmax = A[0][0];
-#pragma unroll
-  for (int i = 1; i < N; ++i) {
-    if (A[i][i] < l1) { l1 = A[i][i]; best = i; }
-    lmax = fmax(lmax, A[i][i]);
-  }
-  l2 = HUGE_VAL;
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-    if (i != best) l2 = fmin(l2, A[i][i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double x = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) x = j == best ? V[i][j] : x;  // (selects: a run-time column index would put V into scratch)
-    v[i] = x;
-  }
-}
 
 // The fixed tree of a chunk: the workgroup's START_CHUNK values v[e] summed into out[e] -- lanes l and l + off inside a wave,
 // off = 32 .. 1, then the waves in ascending order.  Every thread of the workgroup calls it (a barrier inside).

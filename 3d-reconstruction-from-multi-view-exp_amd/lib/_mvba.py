@@ -127,6 +127,12 @@ SIGNATURES = {
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _dp,
                                           C.c_int32]),
     "mvba_triangulate_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "mvba_align_robust": (C.c_int, [C.c_int64, _dp, _dp, C.POINTER(C.c_uint8), C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int32, _dp, _dp,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_int32]),
+    "mvba_align": (C.c_int, [C.c_int64, _dp, _dp, C.POINTER(C.c_uint8), C.c_int32, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                             C.c_int32]),
+    "mvba_align_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -771,6 +777,68 @@ def triangulate_sample(seed, point, h, deg, n_hypotheses=64):
     exhaustive table has no entry ``h`` (mvba_triangulate_sample: the host instance of the function the kernel runs; no GPU
     needed)."""
     return _sample("mvba_triangulate_sample", 2, seed, point, h, deg, n_hypotheses)
+
+
+def _align_args(src, dst, ok):
+    """(src, dst, ok bytes or None, ok pointer, n) as mvba_align_robust and mvba_align take them."""
+    src, dst = _as(src, np.float64), _as(dst, np.float64)
+    n = src.shape[0]
+    assert src.shape == (n, 3) and dst.shape == (n, 3)
+    okb, okp = None, None
+    if ok is not None:
+        okb = _as(np.asarray(ok) != 0, np.uint8)
+        assert okb.shape == (n,)
+        okp = okb.ctypes.data_as(C.POINTER(C.c_uint8))
+    return src, dst, okb, okp, n
+
+
+def _similarity(sim):
+    return {"s": float(sim[0]), "Q": sim[1:10].reshape(3, 3).copy(), "tau": sim[10:13].copy()}
+
+
+def align_robust(src, dst, threshold, ok=None, with_scale=True, n_hypotheses=512, seed=0, n_refit=2, return_counts=False, device=-1):
+    """The similarity ``dst ~ s Q src + tau`` by 3-point RANSAC on the device (mvba_align_robust).  ``src``, ``dst`` (n, 3); ``ok``
+    (n,) marks the rows to use (rows with a non-finite number are unusable anyway); ``threshold`` is a distance in the units of
+    dst.  Returns a dict: ``s``, ``Q (3, 3)``, ``tau (3,)``, ``quality (3,)`` (RMS residual over the final inliers, relative gap of
+    the two largest eigenvalues of the last kept refit, mean squared spread of the inliers' src), ``n_usable``, ``n_inliers``,
+    ``best``, ``status`` (0 ok, 1 fewer than 3 usable rows, 2 every hypothesis degenerate, 4 best count below 3; s, Q, tau and
+    quality NaN then), ``inlier (n,) bool``, ``hyp_count (H,) int32`` (``return_counts``), ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_align_robust")
+    src, dst, okb, okp, n = _align_args(src, dst, ok)
+    H = int(n_hypotheses)
+    i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    sim, q, tm = np.empty(13), np.empty(3), np.zeros(4)
+    nu, ni, best, st = C.c_int64(0), C.c_int64(0), C.c_int32(-1), C.c_int32(1)
+    inl = np.empty(n, np.uint8)
+    hc = np.empty(max(H, 0), np.int32) if return_counts else None
+    raise_for(lib.mvba_align_robust(n, _ptr(src), _ptr(dst), okp, int(bool(with_scale)), float(threshold), H, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    int(n_refit), _ptr(sim), _ptr(q), C.byref(nu), C.byref(ni), C.byref(best), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    None if hc is None else hc.ctypes.data_as(i32), C.byref(st), _ptr(tm), int(device)), lib)
+    out = {**_similarity(sim), "quality": q, "n_usable": nu.value, "n_inliers": ni.value, "best": best.value, "status": st.value,
+           "inlier": inl.astype(bool), "timings_ms": dict(zip(("upload", "score", "refit", "other"), tm.tolist()))}
+    if hc is not None:
+        out["hyp_count"] = hc
+    return out
+
+
+def align(src, dst, ok=None, with_scale=True, device=-1):
+    """The least-squares similarity ``dst ~ s Q src + tau`` of every usable row on the device (mvba_align).  Returns a dict: ``s``,
+    ``Q``, ``tau``, ``quality (3,)`` (RMS residual, eigenvalue gap, mean squared spread of src), ``n_usable``, ``status`` (0 ok, 1
+    fewer than 3 usable rows, 2 degenerate: src or dst on a line).  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_align")
+    src, dst, okb, okp, n = _align_args(src, dst, ok)
+    sim, q = np.empty(13), np.empty(3)
+    nu, st = C.c_int64(0), C.c_int32(1)
+    raise_for(lib.mvba_align(n, _ptr(src), _ptr(dst), okp, int(bool(with_scale)), _ptr(sim), _ptr(q), C.byref(nu), C.byref(st), int(device)), lib)
+    return {**_similarity(sim), "quality": q, "n_usable": nu.value, "status": st.value}
+
+
+def align_sample(seed, h, n):
+    """The 3 distinct indices below ``n`` that hypothesis ``h`` draws (mvba_align_sample: the host instance of the function the
+    kernel runs; no GPU needed)."""
+    return _sample("mvba_align_sample", 3, seed, h, n)
 
 
 def host_obs_math(X3, cam15, xy2, f0):

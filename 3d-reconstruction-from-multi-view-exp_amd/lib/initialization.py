@@ -14,6 +14,11 @@ its POSE alone: three-point RANSAC and a pose-only Gauss-Newton refit (``mvba_po
 csrc/mvba_pose_ransac.h): ``pose_threshold``.  A PLANAR scene has no fundamental matrix: its start pair comes from
 4-point RANSAC for the homography (``mvba_homography_robust``: csrc/mvba_homography.h) and the decomposition of it:
 ``model``.
+
+And the step that takes a reconstruction into another frame -- that of surveyed control points, or of a second map: the
+similarity between two point sets by 3-point RANSAC and by least squares (``mvba_align_robust``, ``mvba_align``:
+csrc/mvba_align.h): ``robust_similarity``, ``fit_similarity``, ``transform_reconstruction``,
+``align_to_control_points``.
 """
 from __future__ import annotations
 
@@ -275,6 +280,66 @@ def homography_sample(seed, k, l, h, n):
     (k, l) draws under ``seed`` -- the first four of ``ransac_sample`` wherever n >= 8; the host instance of the function the
     kernel runs."""
     return _mvba.homography_sample(seed, k, l, h, n)
+
+
+def fit_similarity(src, dst, ok=None, with_scale: bool = True):
+    """(s, Q, tau, info): the least-squares similarity ``dst ~ s Q src + tau`` of the rows ``ok`` allows whose six numbers are
+    finite, on the device (``mvba_align``: csrc/mvba_align.h) -- Q a proper rotation, s = 1 with
+    ``with_scale=False``.  ``info``: ``status`` (0 ok, 1 fewer than 3 usable rows, 2 src or dst on a line; s, Q, tau NaN where it
+    is not 0), ``n_usable``, ``quality`` (RMS residual, relative gap of the two largest eigenvalues, mean squared spread of
+    src).  One wrong row spoils it: ``robust_similarity``."""
+    out = _mvba.align(src, dst, ok=ok, with_scale=with_scale)
+    return out.pop("s"), out.pop("Q"), out.pop("tau"), out
+
+
+def robust_similarity(src, dst, threshold, ok=None, with_scale: bool = True, n_hypotheses: int = 512, seed: int = 0, n_refit: int = 2):
+    """(s, Q, tau, info): ``dst ~ s Q src + tau`` by 3-point RANSAC on the device (``mvba_align_robust``).  ``n_hypotheses``
+    samples of three usable rows (``align_sample``) are solved by Horn's quaternion method and scored by the number of usable
+    rows with ``|s Q x + tau - y| <= threshold`` (units of dst); the best hypothesis's inliers get the least-squares fit,
+    ``n_refit`` times at most, the first kept if it has three inliers of its own, a later one while its set does not shrink.
+    ``info``: ``status`` (0 ok, 1 fewer than 3 usable rows, 2 every hypothesis degenerate, 4 best count below 3), ``n_usable``,
+    ``n_inliers``, ``best``, ``quality`` (3,), ``inlier`` (n,) bool, ``hyp_count`` (H,), ``confidence`` = 1 - (1 - w^3)^H with
+    w = n_inliers / n_usable, and ``timings_ms``.  Two calls with the same arguments return the same bits."""
+    out = _mvba.align_robust(src, dst, threshold, ok=ok, with_scale=with_scale, n_hypotheses=n_hypotheses, seed=seed, n_refit=n_refit,
+                             return_counts=True)
+    out["confidence"] = float(_confidence({k: np.asarray(out[k]) for k in ("n_inliers", "n_usable", "status")}, "n_usable", 3, n_hypotheses))
+    return out.pop("s"), out.pop("Q"), out.pop("tau"), out
+
+
+def align_sample(seed, h, n):
+    """The 3 distinct indices below ``n`` (of the usable rows in ascending order) that hypothesis ``h`` draws under ``seed`` --
+    the first three of ``ransac_sample(seed, 0, 0, h, n)`` wherever n >= 8; the host instance of the function the kernel runs."""
+    return _mvba.align_sample(seed, h, n)
+
+
+def transform_reconstruction(s, Q, tau, X=None, R=None, t=None):
+    """(X', R', t'): a reconstruction under the similarity x -> s Q x + tau, in the camera convention K [R^T | -R^T t] (R is
+    camera-to-world, t the centre): ``X' = s X Q^T + tau``, ``t' = s t Q^T + tau``, ``R' = Q R``.  Reprojections do not change.
+    NaN rows stay NaN -- ``bootstrap``'s unreached cameras and points pass through --, an argument left out comes back None."""
+    Q, tau = np.asarray(Q, np.float64), np.asarray(tau, np.float64)
+    Xn = None if X is None else s * np.asarray(X, np.float64) @ Q.T + tau
+    tn = None if t is None else s * np.asarray(t, np.float64) @ Q.T + tau
+    Rn = None if R is None else Q @ np.asarray(R, np.float64)
+    return Xn, Rn, tn
+
+
+def align_to_control_points(X, R, t, point_ids, xyz, threshold, with_scale: bool = True, **search):
+    """(X', R', t', info): the reconstruction in the frame of its control points.  ``xyz[i]`` is the surveyed position of point
+    ``point_ids[i]``; ``robust_similarity`` runs from ``X[point_ids]`` to ``xyz`` (rows with a non-finite number are unusable;
+    ``threshold`` in the units of xyz; ``search``: n_hypotheses, seed, n_refit) and ``transform_reconstruction`` applies it.
+    ``info`` is ``robust_similarity``'s with ``s``, ``Q``, ``tau`` and ``held``: the point ids among the inliers, whose rows of X'
+    are set to their surveyed xyz -- ready for ``BundleAdjuster.from_observations(..., init_X=X', hold_points=info["held"])``.
+    Where the status is not 0 nothing is transformed: X, R, t come back as copies and ``held`` is empty."""
+    ids, xyz = np.asarray(point_ids, np.int64).reshape(-1), np.asarray(xyz, np.float64).reshape(-1, 3)
+    X, R, t = np.array(X, np.float64), np.array(R, np.float64), np.array(t, np.float64)
+    assert len(ids) == len(xyz)
+    s, Q, tau, info = robust_similarity(X[ids], xyz, threshold, with_scale=with_scale, **search)
+    info.update(s=s, Q=Q, tau=tau, held=ids[info["inlier"]] if info["status"] == 0 else ids[:0])
+    if info["status"] != 0:
+        return X, R, t, info
+    X, R, t = transform_reconstruction(s, Q, tau, X, R, t)
+    X[ids[info["inlier"]]] = xyz[info["inlier"]]
+    return X, R, t, info
 
 
 def restrict_observations(pt_ptr, cam_idx, xy, point_ok, camera_ok):

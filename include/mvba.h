@@ -522,6 +522,41 @@ int mvba_triangulate_robust(const double *K, const double *R, const double *t, i
  * MVBA_ERR_BADARG: deg outside 2 .. 2^31 - 1, n_hypotheses outside 1 .. 4096, a negative point or h, h >= n_hypotheses. */
 int mvba_triangulate_sample(uint64_t seed, int32_t point, int32_t h, int64_t deg, int32_t n_hypotheses, int64_t *idx2);
 
+/* mvba_align_robust: the similarity y ~ s Q x + tau between two point sets by 3-point RANSAC -- absolute orientation: a
+ * reconstruction into the frame of its control points, two maps onto each other.  src, dst [n][3]: row i of src corresponds to
+ * row i of dst; ok [n] (may be NULL: every row).  A correspondence is usable if ok allows it and its six numbers are finite; the
+ * usable ones are compacted in ascending order (chunks of 256, as mvba_two_view_robust compacts a pair's shared points).
+ * with_scale = 0: the rigid fit, s is exactly 1.
+ *   hypothesis h: the 3 indices of mvba_align_sample(seed, h, n_usable); both triples centred, Horn's symmetric 4 x 4 matrix
+ *     of their cross-covariance, q = the eigenvector of its largest eigenvalue (cyclic Jacobi in registers), Q = the rotation of
+ *     the unit quaternion q -- proper by construction: a reflection is never returned --, s = sum y_c . (Q x_c) / sum |x_c|^2,
+ *     tau = mean(y) - s Q mean(x).  Degenerate (count -1) if either triple has |(p1 - p0) x (p2 - p0)|^2 <= 1e-12 |p1 - p0|^2
+ *     |p2 - p0|^2 (collinear or coincident), the two largest eigenvalues differ by no more than 1e-12 of the largest, s is not
+ *     positive or a number is not finite;
+ *   count: the usable correspondences with |s Q x + tau - y|^2 <= threshold^2 (threshold in the units of dst; integer counts);
+ *   best: the largest count, the lowest h on ties;
+ *   refits: n_refit (0 .. 16) times at most the least-squares fit of the current inliers alone, in two passes (the centroids,
+ *     then the centred moments) and the same eigen-problem on the host; the first is kept if it has 3 inliers of its own, a later
+ *     one while its inlier set does not shrink (mvba_resect_robust's rule).
+ * sim13 = (s, Q row-major, tau).  quality [3]: the RMS residual over the final inliers; (l1 - l2) / l1 of the two largest
+ * eigenvalues of the last kept refit (0 if none); sum |x_c|^2 / count of the final inliers about their centroid.  inlier [n]
+ * bytes over the input rows, hyp_count [n_hypotheses] (both may be NULL, as may quality, n_usable, n_inliers, best, status and
+ * timings_ms [4]: upload, score, refit, other).  *status: 0 ok; 1 fewer than 3 usable correspondences; 2 every hypothesis
+ * degenerate; 4 the best count is below 3 -- sim13 and quality NaN, inlier zero, *best -1 (status 1, 2), *n_inliers 0 then.
+ * n_hypotheses 1 .. 65536, n < 2^31.  Every sum runs in an order the sizes alone fix: two calls give bitwise-identical output. */
+int mvba_align_robust(int64_t n, const double *src, const double *dst, const uint8_t *ok, int32_t with_scale, double threshold,
+                      int32_t n_hypotheses, uint64_t seed, int32_t n_refit, double *sim13, double *quality, int64_t *n_usable,
+                      int64_t *n_inliers, int32_t *best, uint8_t *inlier, int32_t *hyp_count, int32_t *status, double *timings_ms,
+                      int32_t device);
+/* The plain least-squares similarity of every usable correspondence: the refit of mvba_align_robust alone.  quality [3]: the RMS
+ * residual over the usable correspondences, the eigenvalue gap, sum |x_c|^2 / count.  *status: 0 ok; 1 fewer than 3 usable
+ * correspondences; 2 degenerate -- src or dst on a line (the gap is at most 1e-12), coincident, or s not positive. */
+int mvba_align(int64_t n, const double *src, const double *dst, const uint8_t *ok, int32_t with_scale, double *sim13, double *quality,
+               int64_t *n_usable, int32_t *status, int32_t device);
+/* Host only (no GPU needed): the 3 distinct indices below n that hypothesis h draws -- the first 3 of
+ * mvba_ransac_sample(seed, 0, 0, h, n) wherever n >= 8.  MVBA_ERR_BADARG: n outside 3 .. 2^31 - 1, a negative h. */
+int mvba_align_sample(uint64_t seed, int32_t h, int64_t n, int64_t *idx3);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
