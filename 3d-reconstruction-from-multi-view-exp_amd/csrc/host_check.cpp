@@ -1,5 +1,6 @@
 // The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas) and the host logic of a RANSAC
-// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*, align_solve) on hand-made inputs.  A program of its own,
+// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
+// builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify) on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
 #include <cmath>
 #include <cstdio>
@@ -10,6 +11,7 @@
 
 #include "mvba_host.h"
 #include "mvba_ransac_host.h"
+#include "mvba_tracks_host.h"
 
 namespace mvba {
 thread_local std::string g_err;
@@ -292,6 +294,52 @@ int main() {
     moments(cube, 5, 2.5, true, tau, mx, my, mom);
     mom[4] = std::numeric_limits<double>::quiet_NaN();  // a moment that is not finite
     CHECK(align_solve(mx, my, mom, true, sim, gap) == 2 && std::isnan(sim[0]));
+  }
+  {  // mvba_build_tracks: the class of a component from (size, min_length, n_images), the first rule that holds
+    CHECK(tracks_classify(1, 2, 8) == TRK_SINGLETON && tracks_classify(1, 2, 1) == TRK_SINGLETON && tracks_classify(0, 2, 8) == TRK_SINGLETON);
+    CHECK(tracks_classify(2, 2, 8) == TRK_CANDIDATE && tracks_classify(8, 2, 8) == TRK_CANDIDATE && tracks_classify(9, 2, 8) == TRK_OVERSIZE);
+    CHECK(tracks_classify(2, 3, 8) == TRK_SHORT && tracks_classify(3, 3, 8) == TRK_CANDIDATE);
+    CHECK(tracks_classify(2, 2, 1) == TRK_OVERSIZE);                                       // one image: every match is a conflict
+    CHECK(tracks_classify(5, 10, 3) == TRK_SHORT && tracks_classify(10, 10, 3) == TRK_OVERSIZE);  // short before oversize
+    CHECK(tracks_classify(2147483647, 2, 2147483647) == TRK_CANDIDATE && tracks_classify(2147483647, 2, 2147483646) == TRK_OVERSIZE);
+    for (int size = 1; size <= 12; ++size)
+      for (int ml = 2; ml <= 12; ++ml)
+        for (int m = 1; m <= 12; ++m) {
+          const int c = tracks_classify(size, ml, m);
+          CHECK((c == TRK_CANDIDATE) == (size >= 2 && size >= ml && size <= m));
+        }
+  }
+  {  // its checks, with their texts: kp_ptr, then the arguments in the order the entry point looks at them
+    const int64_t kp[4] = {0, 2, 2, 5}, down[4] = {0, 3, 2, 5}, off[3] = {1, 2, 3}, big[2] = {0, 1LL << 31}, most[2] = {0, (1LL << 31) - 1};
+    CHECK(tracks_check_kp_ptr(3, kp) == MVBA_OK && tracks_check_kp_ptr(1, most) == MVBA_OK);
+    CHECK(tracks_check_kp_ptr(0, kp) == MVBA_ERR_BADARG && g_err == "n_images = 0 must be at least 1");
+    CHECK(tracks_check_kp_ptr(2, off) == MVBA_ERR_BADARG && g_err == "kp_ptr[0] = 1 must be 0");
+    CHECK(tracks_check_kp_ptr(3, down) == MVBA_ERR_BADARG && g_err == "kp_ptr is not ascending: kp_ptr[2] = 2 after 3");
+    CHECK(tracks_check_kp_ptr(1, big) == MVBA_ERR_BADARG && g_err == "n_nodes = kp_ptr[n_images] = 2147483648 must be < 2^31");
+    const int32_t edges[6] = {0, 4, 3, 3, 4, 1}, high[4] = {0, 4, 5, 1}, low[4] = {0, 4, 2, -1};
+    const double kxy[10] = {0};
+    int64_t pt[3], counts[TRK_N_COUNTS];
+    int32_t cam[5], node[5], track[5];
+    double xy[10];
+    auto run = [&](const int64_t *kp_, const double *kxy_, const int32_t *e, int64_t ne, int32_t ml, int64_t *pt_, int32_t *cam_, int32_t *node_,
+                   double *xy_, int32_t *track_, int64_t *cnt_) { return tracks_check_args(3, kp_, kxy_, e, ne, ml, pt_, cam_, node_, xy_, track_, cnt_); };
+    CHECK(run(kp, kxy, edges, 3, 2, pt, cam, node, xy, track, counts) == MVBA_OK);
+    CHECK(run(kp, nullptr, edges, 3, 2, pt, cam, node, nullptr, track, counts) == MVBA_OK);  // no coordinates wanted
+    CHECK(run(kp, kxy, nullptr, 0, 2, pt, cam, node, xy, track, counts) == MVBA_OK);         // no edges: the pointer is not looked at
+    CHECK(run(nullptr, kxy, edges, 3, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "null argument: kp_ptr (argument 2)");
+    CHECK(run(kp, kxy, edges, 3, 2, nullptr, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "null argument: pt_ptr (argument 8)");
+    CHECK(run(kp, kxy, edges, 3, 2, pt, nullptr, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "null argument: cam_idx (argument 9)");
+    CHECK(run(kp, kxy, edges, 3, 2, pt, cam, nullptr, xy, track, counts) == MVBA_ERR_BADARG && g_err == "null argument: obs_node (argument 10)");
+    CHECK(run(kp, kxy, edges, 3, 2, pt, cam, node, xy, nullptr, counts) == MVBA_ERR_BADARG && g_err == "null argument: node_track (argument 12)");
+    CHECK(run(kp, kxy, edges, 3, 2, pt, cam, node, xy, track, nullptr) == MVBA_ERR_BADARG && g_err == "null argument: counts (argument 13)");
+    CHECK(run(kp, nullptr, edges, 3, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "null argument: kp_xy (argument 3) with an xy to fill");
+    CHECK(run(kp, kxy, edges, -1, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "n_edges = -1: negative size");
+    CHECK(run(kp, kxy, nullptr, 3, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "null argument: edges (argument 4) with n_edges = 3");
+    CHECK(run(kp, kxy, edges, 3, 1, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "min_length = 1 must be at least 2");
+    CHECK(run(down, kxy, edges, 3, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err.rfind("kp_ptr is not ascending", 0) == 0);
+    CHECK(run(kp, kxy, high, 2, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "edges[1][0] = 5: node id out of range, n_nodes = 5");
+    CHECK(run(kp, kxy, low, 2, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "edges[1][1] = -1: node id out of range, n_nodes = 5");
+    CHECK(run(kp, kxy, high, 1, 2, pt, cam, node, xy, track, counts) == MVBA_OK);  // (the bad edge is beyond n_edges)
   }
   if (failures) return 1;
   std::printf("host_check ok\n");

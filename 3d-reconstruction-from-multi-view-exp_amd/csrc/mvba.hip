@@ -37,6 +37,7 @@
 #include "mvba_common.h"
 #include "mvba_host.h"
 #include "mvba_ransac_host.h"
+#include "mvba_tracks_host.h"
 
 namespace mvba {
 thread_local std::string g_err;
@@ -3327,3 +3328,4 @@ int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2,
 #include "mvba_pose_ransac.h"    // calibrated robust resection: mvba_pose_robust, mvba_pose_refine, mvba_pose_sample
 #include "mvba_tri_ransac.h"     // robust triangulation: mvba_triangulate_robust, mvba_triangulate_sample
 #include "mvba_align.h"          // similarity alignment: mvba_align_robust, mvba_align, mvba_align_sample
+#include "mvba_tracks.h"         // feature tracks from pairwise matches: mvba_build_tracks

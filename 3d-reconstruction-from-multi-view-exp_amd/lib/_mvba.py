@@ -133,6 +133,9 @@ SIGNATURES = {
     "mvba_align": (C.c_int, [C.c_int64, _dp, _dp, C.POINTER(C.c_uint8), C.c_int32, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                              C.c_int32]),
     "mvba_align_sample": (C.c_int, [C.c_uint64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "mvba_build_tracks": (C.c_int, [C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_uint8), C.c_int32,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int64), _dp, C.c_int32]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -839,6 +842,44 @@ def align_sample(seed, h, n):
     """The 3 distinct indices below ``n`` that hypothesis ``h`` draws (mvba_align_sample: the host instance of the function the
     kernel runs; no GPU needed)."""
     return _sample("mvba_align_sample", 3, seed, h, n)
+
+
+TRACK_COUNTS = ("n_tracks", "n_obs", "n_components", "n_short", "n_conflicting", "n_conflicting_nodes", "n_oversize",
+                "n_oversize_nodes", "n_singletons", "n_rounds")  # counts [10] of mvba_build_tracks, in its order
+
+
+def build_tracks(kp_ptr, kp_xy, edges, edge_ok=None, min_length=2, device=-1):
+    """Feature tracks from pairwise matches on the device (mvba_build_tracks).  ``kp_ptr (m + 1,)``: keypoint j of image i is node
+    ``kp_ptr[i] + j``; ``kp_xy (n_nodes, 2)`` or None; ``edges (E, 2)`` node ids; ``edge_ok (E,)`` marks the edges to use.
+    Returns a dict: ``pt_ptr (T + 1,) int64``, ``cam_idx (n_obs,) int32``, ``obs_node (n_obs,) int32``, ``xy (n_obs, 2)`` (None
+    without kp_xy), ``node_track (n_nodes,) int32`` (>= 0 the track, -1 unmatched, -2 too short, -3 conflicting or oversize), the
+    ``TRACK_COUNTS`` by name, ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_build_tracks")
+    i32, i64, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    kp_ptr, edges = _as(kp_ptr, np.int64), _as(edges, np.int32).reshape(-1, 2)
+    m, E = kp_ptr.shape[0] - 1, edges.shape[0]
+    n = int(kp_ptr[-1]) if 0 <= int(kp_ptr[-1]) < 2 ** 31 else 0  # (a bad kp_ptr is refused before anything is written)
+    kxp = okb = okp = None
+    if kp_xy is not None:
+        kp_xy = _as(kp_xy, np.float64).reshape(-1, 2)
+        assert kp_xy.shape[0] == kp_ptr[-1]
+        kxp = _ptr(kp_xy)
+    if edge_ok is not None:
+        okb = _as(np.asarray(edge_ok) != 0, np.uint8)
+        assert okb.shape == (E,)
+        okp = okb.ctypes.data_as(u8)
+    pt_ptr, cam, node = np.empty(n // 2 + 1, np.int64), np.empty(n, np.int32), np.empty(n, np.int32)
+    xy = None if kp_xy is None else np.empty((n, 2))
+    track, counts, tm = np.empty(n, np.int32), np.zeros(len(TRACK_COUNTS), np.int64), np.zeros(4)
+    raise_for(lib.mvba_build_tracks(m, kp_ptr.ctypes.data_as(i64), kxp, edges.ctypes.data_as(i32), E, okp, int(min_length),
+                                    pt_ptr.ctypes.data_as(i64), cam.ctypes.data_as(i32), node.ctypes.data_as(i32),
+                                    None if xy is None else _ptr(xy), track.ctypes.data_as(i32), counts.ctypes.data_as(i64), _ptr(tm),
+                                    int(device)), lib)
+    T, n_obs = int(counts[0]), int(counts[1])
+    # (views of the buffers sized by n_nodes: the pages behind them that the call never wrote were never touched)
+    return {"pt_ptr": pt_ptr[:T + 1], "cam_idx": cam[:n_obs], "obs_node": node[:n_obs], "xy": None if xy is None else xy[:n_obs], "node_track": track, **dict(zip(TRACK_COUNTS, counts.tolist())),
+            "timings_ms": dict(zip(("upload", "labels", "layout", "download"), tm.tolist()))}
 
 
 def host_obs_math(X3, cam15, xy2, f0):

@@ -19,6 +19,11 @@ And the step that takes a reconstruction into another frame -- that of surveyed 
 similarity between two point sets by 3-point RANSAC and by least squares (``mvba_align_robust``, ``mvba_align``:
 csrc/mvba_align.h): ``robust_similarity``, ``fit_similarity``, ``transform_reconstruction``,
 ``align_to_control_points``.
+
+And the step in front of them all -- from what a matcher delivers, keypoints per image and matched keypoint pairs per image
+pair, to the tracks (``pt_ptr``, ``cam_idx``, ``xy``) everything above takes: the connected components of the match graph on the
+device (``mvba_build_tracks``: csrc/mvba_tracks.h): ``build_tracks``, with ``verify_matches`` -- the two-view RANSAC
+above, pair by pair -- to mark the matches worth using.
 """
 from __future__ import annotations
 
@@ -766,3 +771,122 @@ def bootstrap(pt_ptr, cam_idx, xy, init_K, f0: float = 1.0, start_pair=None, min
     if triangulate_threshold is not None:
         info["tri_inlier"] = tri_inlier
     return init_K.copy(), R, t, X, info
+
+
+# ---- feature tracks from pairwise matches ----------------------------------------------------------------
+def match_graph(keypoints, matches):
+    """(kp_ptr (m + 1,) int64, kp_xy (n_nodes, 2), edges (M, 2) int32, image_pairs (M, 2), kp_pairs (M, 2)) of a matcher's output, as
+    ``mvba_build_tracks`` takes it: keypoint j of image i is node ``kp_ptr[i] + j``.  ``keypoints``: a list of (n_i, 2) arrays, or the
+    tuple ``(kp_ptr, kp_xy)``.  ``matches``: a dict ``{(k, l): (n, 2) int array}`` of keypoint indices local to images k and l --
+    its matches are numbered in the dict's order --, or the tuple ``(image_pairs (M, 2), kp_pairs (M, 2))``.  ValueError for an
+    image or a keypoint index out of range, with the match named."""
+    if isinstance(keypoints, tuple) and len(keypoints) == 2 and np.ndim(keypoints[0]) == 1:
+        kp_ptr, kp_xy = np.asarray(keypoints[0], np.int64), np.asarray(keypoints[1], np.float64).reshape(-1, 2)
+    else:
+        arrays = [np.asarray(a, np.float64).reshape(-1, 2) for a in keypoints]
+        kp_ptr = np.concatenate([[0], np.cumsum([len(a) for a in arrays])]).astype(np.int64)
+        kp_xy = np.concatenate(arrays) if arrays else np.zeros((0, 2))
+    m = len(kp_ptr) - 1
+    if m < 1 or kp_ptr[0] != 0 or (np.diff(kp_ptr) < 0).any() or kp_ptr[-1] != len(kp_xy):
+        raise ValueError(f"match_graph: kp_ptr must ascend from 0 to the {len(kp_xy)} keypoints given, over at least one image")
+    if isinstance(matches, dict):
+        image_pairs = np.array([kl for kl, idx in matches.items() for _ in range(len(idx))], np.int64).reshape(-1, 2)
+        kp_pairs = np.concatenate([np.asarray(idx, np.int64).reshape(-1, 2) for idx in matches.values()] + [np.zeros((0, 2), np.int64)])
+    else:
+        image_pairs, kp_pairs = (np.asarray(a, np.int64).reshape(-1, 2) for a in matches)
+        if len(image_pairs) != len(kp_pairs):
+            raise ValueError(f"match_graph: {len(image_pairs)} image pairs for {len(kp_pairs)} keypoint pairs")
+    bad = np.nonzero(((image_pairs < 0) | (image_pairs >= m)).any(axis=1))[0]
+    if len(bad):
+        raise ValueError(f"match_graph: match {bad[0]} is between images {tuple(image_pairs[bad[0]].tolist())}: image index out of range, n_images = {m}")
+    count = np.diff(kp_ptr)[image_pairs]
+    bad = np.nonzero(((kp_pairs < 0) | (kp_pairs >= count)).any(axis=1))[0]
+    if len(bad):
+        raise ValueError(f"match_graph: match {bad[0]} joins keypoints {tuple(kp_pairs[bad[0]].tolist())} of images {tuple(image_pairs[bad[0]].tolist())}, "
+                         f"which have {tuple(count[bad[0]].tolist())} keypoints")
+    return kp_ptr, kp_xy, (kp_ptr[image_pairs] + kp_pairs).astype(np.int32), image_pairs, kp_pairs
+
+
+def _flat_match_mask(matches, match_ok, n_matches):
+    """``match_ok`` in the form of ``matches`` (a dict with its keys, or (M,)) as one (M,) bool array in the order of its matches."""
+    if match_ok is None:
+        return None
+    if isinstance(match_ok, dict):
+        if not isinstance(matches, dict) or set(match_ok) != set(matches):
+            raise ValueError("build_tracks: a dict match_ok must have the keys of the dict matches")
+        match_ok = np.concatenate([np.asarray(match_ok[kl]).reshape(-1) for kl in matches] + [np.zeros(0, bool)])
+    match_ok = np.asarray(match_ok).reshape(-1) != 0
+    if len(match_ok) != n_matches:
+        raise ValueError(f"build_tracks: match_ok has {len(match_ok)} entries for {n_matches} matches")
+    return match_ok
+
+
+def build_tracks(keypoints, matches, min_length: int = 2, match_ok=None):
+    """(pt_ptr, cam_idx, xy, info): feature tracks from pairwise matches, on the device (``mvba_build_tracks``) -- the list that
+    ``covisibility``, ``bootstrap`` and ``BundleAdjuster.from_observations`` take as it is.  ``keypoints`` and ``matches`` as for
+    ``match_graph``; ``match_ok`` marks the matches to use, in the form of ``matches`` (a dict with the same keys, or (M,); what
+    ``verify_matches`` returns).  A track is a connected component of the match graph of at least ``min_length`` keypoints with at
+    most one keypoint per image; a component with two keypoints of one image is dropped WHOLE (it is neither pruned nor
+    split), and so is one with more keypoints than there are images, which cannot be otherwise.  Tracks are numbered in ascending
+    order of their first keypoint (image-major), cameras ascend within a track, ``xy`` are the keypoints' coordinates, bit for bit.
+    ``info``: ``kp_idx`` (n_obs,) -- the keypoint of each observation, local to its image --, ``obs_node``, ``node_track``
+    (n_nodes,) -- >= 0 the keypoint's track, -1 unmatched, -2 its component is shorter than ``min_length``, -3 its component
+    conflicts or is oversize --, ``kp_ptr``, the counts ``n_tracks``, ``n_obs``, ``n_components``, ``n_short``, ``n_conflicting``,
+    ``n_conflicting_nodes``, ``n_oversize``, ``n_oversize_nodes``, ``n_singletons``, ``n_rounds`` (label rounds run) and
+    ``timings_ms`` (upload, labels, layout, download).  The result is a function of the SET of matches used: their order, their
+    orientation and duplicates change no bit of it, nor does a second call.  Limits: fewer than 2^31 keypoints in all."""
+    kp_ptr, kp_xy, edges, _, _ = match_graph(keypoints, matches)
+    out = _mvba.build_tracks(kp_ptr, kp_xy, edges, edge_ok=_flat_match_mask(matches, match_ok, len(edges)), min_length=min_length)
+    pt_ptr, cam_idx, xy = out.pop("pt_ptr"), out.pop("cam_idx"), out.pop("xy")
+    out["kp_idx"] = (out["obs_node"] - kp_ptr[cam_idx]).astype(np.int64)
+    out["kp_ptr"] = kp_ptr
+    return pt_ptr, cam_idx, xy, out
+
+
+def match_pair_lists(keypoints, matches):
+    """The matches of every image pair as a two-camera observation list, one "point" per match with its two observations in
+    cameras k < l (a match given as (l, k) is turned round; a match inside one image belongs to no pair).  Returns ``(pairs (P, 2)
+    ascending, lists, n_matches)``: ``lists[p] = (match ids (n,), pt_ptr (n + 1,), cam_idx (2 n,), xy (2 n, 2))`` with the ids in
+    the numbering of ``match_graph``."""
+    kp_ptr, kp_xy, edges, image_pairs, _ = match_graph(keypoints, matches)
+    turn = image_pairs[:, 0] > image_pairs[:, 1]
+    kl = np.where(turn[:, None], image_pairs[:, ::-1], image_pairs)
+    nodes = np.where(turn[:, None], edges[:, ::-1], edges)
+    ids = np.nonzero(kl[:, 0] != kl[:, 1])[0]
+    pairs, which = np.unique(kl[ids], axis=0, return_inverse=True)
+    which = which.reshape(-1)
+    lists = []
+    for p in range(len(pairs)):
+        sel = ids[which == p]
+        lists.append((sel, 2 * np.arange(len(sel) + 1, dtype=np.int64), np.tile(pairs[p].astype(np.int32), len(sel)), kp_xy[nodes[sel].reshape(-1)]))
+    return pairs.reshape(-1, 2), lists, len(edges)
+
+
+def verify_matches(keypoints, matches, threshold, model: str = "fundamental", n_hypotheses: int = 512, seed: int = 0):
+    """(match_ok, info): the matches that agree with a two-view model of their image pair, found by RANSAC on the device -- glue
+    over ``robust_fundamental_matrices`` (``model="fundamental"``: ``threshold`` is a Sampson distance) or ``robust_homographies``
+    ("homography": a transfer distance, both ways), in the units of the keypoints.  Per image pair the pair's matches become a
+    two-camera list (``match_pair_lists``) and the model's inlier mask comes back per match; a pair whose status is not 0 (too few
+    matches, every sample degenerate) keeps none, nor does a match inside one image.  ``match_ok`` has the form of ``matches`` (a
+    dict with its keys, or (M,) bool) and goes to ``build_tracks(match_ok=)``.  ``info``: ``pairs`` (P, 2), ``status``,
+    ``n_matches``, ``n_inliers`` (P,), ``model`` (P, 3, 3).  Limit: ONE device call per image pair, which keeps the (P, N) inlier
+    mask of the robust fits at one row -- thousands of pairs are thousands of small calls; and the camera cap of those fits."""
+    if model not in ("fundamental", "homography"):
+        raise ValueError(f"verify_matches: model must be 'fundamental' or 'homography', got {model!r}")
+    fit = robust_fundamental_matrices if model == "fundamental" else robust_homographies
+    pairs, lists, n_matches = match_pair_lists(keypoints, matches)
+    m = len(match_graph(keypoints, matches)[0]) - 1
+    ok = np.zeros(n_matches, bool)
+    P = len(pairs)
+    status, n_in, models = np.zeros(P, np.int32), np.zeros(P, np.int64), np.full((P, 3, 3), np.nan)
+    for p, (ids, ptr, cam, xy) in enumerate(lists):
+        M, fi = fit(ptr, cam, xy, m, pairs[p:p + 1], threshold, n_hypotheses=n_hypotheses, seed=seed)
+        status[p], models[p] = fi["status"][0], M[0]
+        if status[p] == 0:
+            ok[ids] = fi["inlier"][0]
+            n_in[p] = fi["n_inliers"][0]
+    info = {"pairs": pairs, "status": status, "n_matches": np.array([len(l[0]) for l in lists], np.int64), "n_inliers": n_in, "model": models}
+    if isinstance(matches, dict):
+        cut = np.cumsum([len(v) for v in matches.values()])[:-1]
+        return dict(zip(matches, np.split(ok, cut))), info
+    return ok, info

@@ -557,6 +557,39 @@ int mvba_align(int64_t n, const double *src, const double *dst, const uint8_t *o
  * mvba_ransac_sample(seed, 0, 0, h, n) wherever n >= 8.  MVBA_ERR_BADARG: n outside 3 .. 2^31 - 1, a negative h. */
 int mvba_align_sample(uint64_t seed, int32_t h, int64_t n, int64_t *idx3);
 
+/* mvba_build_tracks: feature tracks -- the observation list every entry point above takes -- from pairwise keypoint matches.
+ * Keypoint j of image i is NODE kp_ptr[i] + j: kp_ptr [n_images + 1] ascends from 0, n_nodes = kp_ptr[n_images] < 2^31; ids are
+ * image-major, so ascending node ids are ascending images.  kp_xy [n_nodes][2]: the keypoints' coordinates (any units; may be
+ * NULL where xy is).  edges [n_edges][2]: a match is a pair of node ids.  Duplicates, either orientation, u == v and edges between
+ * two keypoints of one image are all legal; edge_ok [n_edges] != 0 selects the edges to use (NULL: all of them).
+ *   1. labels: the connected components of the graph, label[v] = the smallest node id of v's component.  Rounds of two
+ *      launches -- every edge hooks the larger of its ends' roots under the smaller (atomicMin), then every node is pointed at
+ *      its root -- until a round changes nothing; the host reads one word per round.  parent[v] <= v throughout: no kernel
+ *      waits for, or retries on, another thread's write.
+ *   2. sizes (integer atomics) and classes.  A component of one node is a singleton; of fewer than min_length nodes, short;
+ *      of more than n_images nodes, oversize -- two of its nodes share an image whatever they are, and it is dropped without
+ *      being laid out (a few wrong matches chain thousands of tracks into one); the first of these that holds decides.  Every
+ *      other component is a candidate.
+ *   3. the candidates laid out (an exclusive scan of their sizes in ascending label order), each sorted by node id.  A
+ *      candidate with two nodes in one image is CONFLICTING and is dropped whole: it is neither pruned nor split.
+ *   4. the surviving tracks numbered in ascending order of their smallest node id:
+ * pt_ptr [n_tracks + 1], cam_idx [n_obs] (ascending within a track), obs_node [n_obs] (the node of every observation),
+ * xy [n_obs][2] = kp_xy[obs_node] (a copy made on the device; NULL: not wanted), node_track [n_nodes]: >= 0 the node's track,
+ * -1 unmatched (a singleton), -2 its component is shorter than min_length, -3 its component conflicts or is oversize.
+ * The caller sizes cam_idx, obs_node, xy and node_track by n_nodes, and pt_ptr by n_nodes / 2 + 1.
+ * counts [10]: tracks, observations, components of two nodes or more, short components, conflicting components, their nodes,
+ * oversize components, their nodes, singletons, rounds (the last, unchanging one included; 0 without edges).
+ * timings_ms [4] (may be NULL): upload (with the checks), labels, layout (steps 2 to 4), download and everything else.
+ * No floating-point arithmetic anywhere: the outputs are a function of the SET of used edges -- permuted, turned round or
+ * duplicated edges, and a second call, give bitwise equal arrays.
+ * MVBA_ERR_BADARG, before any device work and with the number in the message: a null kp_ptr, pt_ptr, cam_idx, obs_node,
+ * node_track or counts (named, with its position), kp_xy NULL with an xy, edges NULL with n_edges > 0; n_edges < 0;
+ * min_length < 2; n_images < 1; kp_ptr not ascending from 0; n_nodes >= 2^31; a node id outside 0 .. n_nodes - 1 (the edge
+ * and the id are named). */
+int mvba_build_tracks(int32_t n_images, const int64_t *kp_ptr, const double *kp_xy, const int32_t *edges, int64_t n_edges,
+                      const uint8_t *edge_ok, int32_t min_length, int64_t *pt_ptr, int32_t *cam_idx, int32_t *obs_node, double *xy,
+                      int32_t *node_track, int64_t *counts, double *timings_ms, int32_t device);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
