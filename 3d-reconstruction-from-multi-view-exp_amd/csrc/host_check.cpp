@@ -1,6 +1,7 @@
 // The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas) and the host logic of a RANSAC
 // round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
-// builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify) on hand-made inputs.  A program of its own,
+// builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify) and the matcher's (mvba_match_host.h: its argument
+// checks, the chunk rule, the ratio test) on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
 #include <cmath>
 #include <cstdio>
@@ -12,6 +13,7 @@
 #include "mvba_host.h"
 #include "mvba_ransac_host.h"
 #include "mvba_tracks_host.h"
+#include "mvba_match_host.h"
 
 namespace mvba {
 thread_local std::string g_err;
@@ -340,6 +342,67 @@ int main() {
     CHECK(run(kp, kxy, high, 2, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "edges[1][0] = 5: node id out of range, n_nodes = 5");
     CHECK(run(kp, kxy, low, 2, 2, pt, cam, node, xy, track, counts) == MVBA_ERR_BADARG && g_err == "edges[1][1] = -1: node id out of range, n_nodes = 5");
     CHECK(run(kp, kxy, high, 1, 2, pt, cam, node, xy, track, counts) == MVBA_OK);  // (the bad edge is beyond n_edges)
+  }
+  {  // mvba_match_descriptors: the ratio test on exact integers, and the rule that cuts the pair list into chunks
+    const double r2 = match_ratio2(0.8);
+    CHECK(r2 == 0.8 * 0.8 && match_ratio2(1.0) == 1.0);
+    CHECK(match_ambiguous(100, -1, r2) && match_ambiguous(0, -1, 1.0));              // no second: a single candidate passes no ratio test
+    CHECK(!match_ambiguous(63, 100, r2) && match_ambiguous(65, 100, r2));            // 0.64...: 63 < 64.0000...01, 65 is not
+    CHECK(match_ambiguous(100, 100, 1.0) && !match_ambiguous(99, 100, 1.0));         // equal distances are ambiguous at any ratio
+    CHECK(match_ambiguous(0, 0, 1.0) && !match_ambiguous(0, 1, r2));                 // two exact copies; one exact copy
+    CHECK(!match_ambiguous(33292799, 33292800, 1.0) && match_ambiguous(33292800, 33292800, 1.0));  // the largest distances there are
+    const int64_t kp[5] = {0, 10, 10, 40, 45};  // images of 10, 0, 30, 5 keypoints
+    const int32_t pr[10] = {0, 2, 2, 0, 1, 3, 3, 2, 0, 3};
+    CHECK(match_chunk_end(kp, pr, 5, 0, false, 1000) == 5 && match_chunk_end(kp, pr, 5, 0, true, 1000) == 5);
+    CHECK(match_chunk_end(kp, pr, 5, 0, false, 40) == 3);   // 10 + 30 + 0 queries fit, the 5 of pair 3 do not
+    CHECK(match_chunk_end(kp, pr, 5, 0, true, 40) == 1);    // with the reverse direction pair 0 alone has 40 rows
+    CHECK(match_chunk_end(kp, pr, 5, 1, true, 1) == 2);     // one pair at least, whatever its size
+    CHECK(match_chunk_end(kp, pr, 5, 2, false, 0) == 3 && match_chunk_end(kp, pr, 5, 3, false, 0) == 4);  // (a pair without queries still ends its chunk at budget 0)
+    CHECK(match_chunk_end(kp, pr, 5, 5, true, 10) == 5 && match_chunk_end(kp, pr, 0, 0, true, 10) == 0);
+    for (int32_t p0 = 0, guard = 0; p0 < 5 && guard < 10; ++guard) {  // the chunks tile the list
+      const int32_t p1 = match_chunk_end(kp, pr, 5, p0, true, 35);
+      CHECK(p1 > p0 && p1 <= 5);
+      p0 = p1;
+    }
+  }
+  {  // its checks, with their texts, in the order the entry point looks at its arguments
+    const int64_t kp[4] = {0, 2, 2, 5}, down[4] = {0, 3, 2, 5}, off[3] = {1, 2, 3}, big[2] = {0, 1LL << 31}, none[3] = {0, 0, 0};
+    const int64_t huge[3] = {0, 1LL << 30, (1LL << 30) + 1};
+    const uint8_t desc[5 * 32] = {0};
+    const int32_t pr[4] = {0, 2, 2, 0}, high[4] = {0, 2, 3, 0}, low[2] = {0, -1}, self[4] = {0, 2, 2, 2}, twice[4] = {0, 1, 0, 1}, empty[4] = {1, 0, 1, 2};
+    int64_t mp[3], counts[MATCH_N_COUNTS], Q = -1;
+    int32_t kpp[10], d2[5];
+    auto run = [&](int32_t m, const int64_t *kp_, const uint8_t *desc_, int32_t dim, const int32_t *pairs, int32_t np, double ratio, int64_t *mp_,
+                   int32_t *kpp_, int32_t *d2_, int64_t *cnt_) { return match_check_args(m, kp_, desc_, dim, pairs, np, ratio, mp_, kpp_, d2_, cnt_, &Q); };
+    CHECK(run(3, kp, desc, 32, pr, 2, 0.8, mp, kpp, d2, counts) == MVBA_OK && Q == 5);
+    CHECK(run(3, kp, desc, 512, pr, 2, 0.0, mp, kpp, d2, counts) == MVBA_OK && run(3, kp, desc, 16, pr, 2, 1.0, mp, kpp, d2, counts) == MVBA_OK);
+    CHECK(run(3, kp, desc, 32, nullptr, 0, 0.8, mp, kpp, d2, counts) == MVBA_OK && Q == 0);  // no pairs: the pointer is not looked at
+    CHECK(run(3, kp, desc, 32, empty, 2, 0.8, mp, kpp, d2, counts) == MVBA_OK && Q == 0);    // every query image is empty
+    CHECK(run(2, none, nullptr, 128, nullptr, 0, 0.8, mp, kpp, d2, counts) == MVBA_OK);      // no keypoints: desc is not looked at
+    CHECK(run(3, nullptr, desc, 32, pr, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "null argument: kp_ptr (argument 2)");
+    CHECK(run(3, kp, desc, 32, pr, 2, 0.8, nullptr, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "null argument: match_ptr (argument 10)");
+    CHECK(run(3, kp, desc, 32, pr, 2, 0.8, mp, nullptr, d2, counts) == MVBA_ERR_BADARG && g_err == "null argument: kp_pairs (argument 11)");
+    CHECK(run(3, kp, desc, 32, pr, 2, 0.8, mp, kpp, nullptr, counts) == MVBA_ERR_BADARG && g_err == "null argument: dist2 (argument 12)");
+    CHECK(run(3, kp, desc, 32, pr, 2, 0.8, mp, kpp, d2, nullptr) == MVBA_ERR_BADARG && g_err == "null argument: counts (argument 16)");
+    CHECK(run(3, kp, nullptr, 32, pr, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "null argument: desc (argument 3) with 5 keypoints");
+    CHECK(run(3, kp, desc, 32, nullptr, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "null argument: pairs (argument 5) with n_pairs = 2");
+    CHECK(run(3, kp, desc, 32, pr, -1, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "n_pairs = -1: negative size");
+    CHECK(run(0, kp, desc, 32, pr, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "n_images = 0 must be at least 1");
+    CHECK(run(2, off, desc, 32, pr, 0, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "kp_ptr[0] = 1 must be 0");
+    CHECK(run(3, down, desc, 32, pr, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "kp_ptr is not ascending: kp_ptr[2] = 2 after 3");
+    CHECK(run(1, big, desc, 32, pr, 0, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "n_nodes = kp_ptr[n_images] = 2147483648 must be < 2^31");
+    for (int32_t dim : {0, 8, 24, 520, 528, -16}) {
+      CHECK(run(3, kp, desc, dim, pr, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG);
+      CHECK(g_err == "dim = " + std::to_string(dim) + " must be a multiple of 16 in 16 .. 512");
+    }
+    CHECK(run(3, kp, desc, 32, pr, 2, -0.1, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "ratio = -0.100000 must be in (0, 1], or 0 for no ratio test");
+    CHECK(run(3, kp, desc, 32, pr, 2, 1.5, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "ratio = 1.500000 must be in (0, 1], or 0 for no ratio test");
+    CHECK(run(3, kp, desc, 32, pr, 2, std::numeric_limits<double>::quiet_NaN(), mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err.find("nan must be in") != std::string::npos);
+    CHECK(run(3, kp, desc, 32, high, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "pairs[1][0] = 3: image index out of range, n_images = 3");
+    CHECK(run(3, kp, desc, 32, low, 1, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "pairs[0][1] = -1: image index out of range, n_images = 3");
+    CHECK(run(3, kp, desc, 32, self, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "pairs[1] = (2, 2): an image is not matched with itself");
+    CHECK(run(2, huge, desc, 32, twice, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "Q = 2147483648 queries up to pair 1: the sum over the pairs must be < 2^31");
+    CHECK(run(2, huge, desc, 32, twice, 1, 0.8, mp, kpp, d2, counts) == MVBA_OK && Q == (1LL << 30));
   }
   if (failures) return 1;
   std::printf("host_check ok\n");

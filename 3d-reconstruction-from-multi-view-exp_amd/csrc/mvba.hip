@@ -38,6 +38,7 @@
 #include "mvba_host.h"
 #include "mvba_ransac_host.h"
 #include "mvba_tracks_host.h"
+#include "mvba_match_host.h"
 
 namespace mvba {
 thread_local std::string g_err;
@@ -3329,3 +3330,4 @@ int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2,
 #include "mvba_tri_ransac.h"     // robust triangulation: mvba_triangulate_robust, mvba_triangulate_sample
 #include "mvba_align.h"          // similarity alignment: mvba_align_robust, mvba_align, mvba_align_sample
 #include "mvba_tracks.h"         // feature tracks from pairwise matches: mvba_build_tracks
+#include "mvba_match.h"          // the matches themselves, from uint8 descriptors: mvba_match_descriptors

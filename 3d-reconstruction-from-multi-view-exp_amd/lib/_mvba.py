@@ -136,6 +136,10 @@ SIGNATURES = {
     "mvba_build_tracks": (C.c_int, [C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_uint8), C.c_int32,
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int64), _dp, C.c_int32]),
+    "mvba_match_descriptors": (C.c_int, [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                         C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), _dp,
+                                         C.c_int32]),
     "mvba_project": (C.c_int, [_dp, C.c_int64, _dp, _dp, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.c_int64, _dp, C.c_int32]),
     "mvsvd_factorize": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -880,6 +884,44 @@ def build_tracks(kp_ptr, kp_xy, edges, edge_ok=None, min_length=2, device=-1):
     # (views of the buffers sized by n_nodes: the pages behind them that the call never wrote were never touched)
     return {"pt_ptr": pt_ptr[:T + 1], "cam_idx": cam[:n_obs], "obs_node": node[:n_obs], "xy": None if xy is None else xy[:n_obs], "node_track": track, **dict(zip(TRACK_COUNTS, counts.tolist())),
             "timings_ms": dict(zip(("upload", "labels", "layout", "download"), tm.tolist()))}
+
+
+MATCH_COUNTS = ("n_matches", "n_queries", "n_no_candidate", "n_far", "n_ambiguous", "n_not_mutual")  # counts [6] of mvba_match_descriptors
+
+
+def match_descriptors(kp_ptr, desc, pairs, ratio=0.0, mutual=True, max_dist2=-1, want_nn=False, device=-1):
+    """Nearest-neighbour matching of uint8 descriptors on the device (mvba_match_descriptors).  ``kp_ptr (m + 1,)``: keypoint j of
+    image i is row ``kp_ptr[i] + j`` of ``desc (n_nodes, dim) uint8``; ``pairs (P, 2)``: (query image, candidate image); ``ratio`` in
+    (0, 1], 0 for no ratio test; ``max_dist2 < 0`` for no distance test.  Returns a dict: ``match_ptr (P + 1,) int64``,
+    ``kp_pairs (M, 2) int32`` (keypoints local to their images), ``dist2 (M,) int32``, with ``want_nn`` the per-query ``nn_best``,
+    ``nn_dist2``, ``nn_second2 (Q,) int32``, the ``MATCH_COUNTS`` by name, ``timings_ms``.  No CPU fallback."""
+    lib = load_library()
+    _require_device("mvba_match_descriptors")
+    i32, i64, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    desc = np.asarray(desc)
+    if desc.dtype != np.uint8 or desc.ndim != 2:
+        raise ValueError(f"match_descriptors: desc must be (n_nodes, dim) uint8, got {desc.dtype} {desc.shape}")
+    kp_ptr, desc, pairs = _as(kp_ptr, np.int64), _as(desc, np.uint8), _as(pairs, np.int32).reshape(-1, 2)
+    m, P, dim = kp_ptr.shape[0] - 1, pairs.shape[0], desc.shape[1]
+    assert m < 1 or desc.shape[0] == kp_ptr[-1]
+    count = np.diff(kp_ptr)
+    ok = m >= 1 and P > 0 and (count >= 0).all() and (pairs >= 0).all() and (pairs < m).all()
+    Q = int(count[pairs[:, 0]].sum()) if ok else 0  # (bad arguments are refused before anything is written)
+    Q = Q if Q < 2 ** 31 else 0
+    match_ptr, kp_pairs, dist2 = np.zeros(P + 1, np.int64), np.empty((Q, 2), np.int32), np.empty(Q, np.int32)
+    nn = [np.empty(Q, np.int32) for _ in range(3)] if want_nn else [None] * 3
+    counts, tm = np.zeros(len(MATCH_COUNTS), np.int64), np.zeros(4)
+    raise_for(lib.mvba_match_descriptors(m, kp_ptr.ctypes.data_as(i64), desc.ctypes.data_as(u8), dim, pairs.ctypes.data_as(i32), P,
+                                         float(ratio), int(bool(mutual)), int(max_dist2), match_ptr.ctypes.data_as(i64),
+                                         kp_pairs.ctypes.data_as(i32), dist2.ctypes.data_as(i32),
+                                         *(None if a is None else a.ctypes.data_as(i32) for a in nn), counts.ctypes.data_as(i64), _ptr(tm),
+                                         int(device)), lib)
+    M = int(counts[0])
+    out = {"match_ptr": match_ptr, "kp_pairs": kp_pairs[:M], "dist2": dist2[:M], **dict(zip(MATCH_COUNTS, counts.tolist())),
+           "timings_ms": dict(zip(("upload", "distances", "tests", "download"), tm.tolist()))}
+    if want_nn:
+        out.update(zip(("nn_best", "nn_dist2", "nn_second2"), nn))
+    return out
 
 
 def host_obs_math(X3, cam15, xy2, f0):

@@ -890,3 +890,70 @@ def verify_matches(keypoints, matches, threshold, model: str = "fundamental", n_
         cut = np.cumsum([len(v) for v in matches.values()])[:-1]
         return dict(zip(matches, np.split(ok, cut))), info
     return ok, info
+
+
+# ---- the matches themselves, from uint8 descriptors ------------------------------------------------------
+def descriptor_arrays(descriptors):
+    """(kp_ptr (m + 1,) int64, desc (n_nodes, dim) uint8) of ``descriptors``: a list of (n_i, dim) uint8 arrays, or the tuple
+    ``(kp_ptr, desc)``.  ValueError for a dtype other than uint8 -- nothing is cast silently --, for arrays of different ``dim`` and
+    for a kp_ptr that does not ascend from 0 to the rows given."""
+    def check(a, what):
+        a = np.asarray(a)
+        if a.dtype != np.uint8:
+            raise ValueError(f"match_descriptors: {what} has dtype {a.dtype}; descriptors must be uint8.  Quantise them yourself, as the SIFT "
+                             f"convention does for unit-norm floats: np.clip(np.rint(512 * d), 0, 255).astype(np.uint8)")
+        if a.ndim != 2:
+            raise ValueError(f"match_descriptors: {what} has shape {a.shape}; must be (n, dim)")
+        return a
+    if isinstance(descriptors, tuple) and len(descriptors) == 2 and np.ndim(descriptors[0]) == 1:
+        kp_ptr, desc = np.asarray(descriptors[0], np.int64), check(descriptors[1], "desc")
+    else:
+        arrays = [check(a, f"descriptors[{i}]") for i, a in enumerate(descriptors)]
+        dims = sorted({a.shape[1] for a in arrays})
+        if len(dims) > 1:
+            raise ValueError(f"match_descriptors: the images' descriptors have different dim: {dims}")
+        kp_ptr = np.concatenate([[0], np.cumsum([len(a) for a in arrays])]).astype(np.int64)
+        desc = np.concatenate(arrays) if arrays else np.zeros((0, 128), np.uint8)
+    if len(kp_ptr) < 2 or kp_ptr[0] != 0 or (np.diff(kp_ptr) < 0).any() or kp_ptr[-1] != len(desc):
+        raise ValueError(f"match_descriptors: kp_ptr must ascend from 0 to the {len(desc)} descriptors given, over at least one image")
+    return kp_ptr, np.ascontiguousarray(desc)
+
+
+def match_descriptors(descriptors, pairs=None, ratio=0.8, mutual: bool = True, max_distance=None, return_nn: bool = False):
+    """(matches, info): keypoint matches from uint8 descriptors, by brute force on the device (``mvba_match_descriptors``; the i8
+    matrix cores give every squared distance exactly).  ``descriptors`` as for ``descriptor_arrays``; ``pairs`` (P, 2) of (query
+    image k, candidate image l), None for every k < l.  For every keypoint a of k: its nearest candidate b in l by (squared
+    distance, index) -- a tie goes to the smaller index -- is its match unless, the first that holds: l has no keypoint; the
+    distance exceeds ``max_distance`` (descriptor units; None: no test); with ``ratio`` (None: no test) NOT d2_best < ratio^2
+    d2_second, or there is no second; with ``mutual`` the nearest keypoint of k to b is not a.  ``matches``: the dict ``{(k, l): (n, 2)
+    int64}`` that ``verify_matches``, ``match_graph`` and ``build_tracks`` take, keys in the order of ``pairs``, rows by ascending a.
+    ``info``: ``pairs``, ``distance2`` (the same keys: (n,) squared distances), ``n_matches``, ``n_queries``, ``n_no_candidate``,
+    ``n_far``, ``n_ambiguous``, ``n_not_mutual``, ``timings_ms``; with ``return_nn`` ``nn_best``, ``nn_distance2``,
+    ``nn_second2`` (the same keys: per query, before any test; -1 where there is none).  Integers throughout: the result is a
+    function of the input alone, bit for bit.  Limits: uint8 only, dim a multiple of 16 up to 512; brute force; the ratio is
+    tested in the forward direction only; a pair (l, k) is answered as given, and listing a pair twice is a ValueError here."""
+    kp_ptr, desc = descriptor_arrays(descriptors)
+    m = len(kp_ptr) - 1
+    if pairs is None:
+        pairs = [(k, l) for k in range(m) for l in range(k + 1, m)]
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    keys = [(int(k), int(l)) for k, l in pairs]
+    if len(set(keys)) != len(keys):
+        dup = next(kl for i, kl in enumerate(keys) if kl in keys[:i])
+        raise ValueError(f"match_descriptors: pair {dup} is listed twice; the dict of matches cannot hold it")
+    if ratio is not None and not 0.0 < float(ratio) <= 1.0:
+        raise ValueError(f"match_descriptors: ratio = {ratio} must be in (0, 1], or None for no ratio test")
+    if max_distance is not None and not float(max_distance) >= 0.0:
+        raise ValueError(f"match_descriptors: max_distance = {max_distance} must be >= 0, or None for no distance test")
+    max_dist2 = -1 if max_distance is None else int(min(np.floor(float(max_distance) ** 2), 2.0 ** 62))
+    out = _mvba.match_descriptors(kp_ptr, desc, pairs, ratio=0.0 if ratio is None else float(ratio), mutual=mutual, max_dist2=max_dist2,
+                                  want_nn=return_nn)
+    ptr = out["match_ptr"]
+    matches = {kl: out["kp_pairs"][ptr[i]:ptr[i + 1]].astype(np.int64) for i, kl in enumerate(keys)}
+    info = {"pairs": pairs, "distance2": {kl: out["dist2"][ptr[i]:ptr[i + 1]] for i, kl in enumerate(keys)}, "timings_ms": out["timings_ms"]}
+    info.update({k: out[k] for k in _mvba.MATCH_COUNTS})
+    if return_nn:
+        qptr = np.concatenate([[0], np.cumsum(np.diff(kp_ptr)[pairs[:, 0]])])
+        for name, key in (("nn_best", "nn_best"), ("nn_distance2", "nn_dist2"), ("nn_second2", "nn_second2")):
+            info[name] = {kl: out[key][qptr[i]:qptr[i + 1]] for i, kl in enumerate(keys)}
+    return matches, info

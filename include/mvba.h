@@ -590,6 +590,45 @@ int mvba_build_tracks(int32_t n_images, const int64_t *kp_ptr, const double *kp_
                       const uint8_t *edge_ok, int32_t min_length, int64_t *pt_ptr, int32_t *cam_idx, int32_t *obs_node, double *xy,
                       int32_t *node_track, int64_t *counts, double *timings_ms, int32_t device);
 
+/* mvba_match_descriptors: the matches that mvba_build_tracks takes, from uint8 descriptors, by brute force.  Keypoint j of image
+ * i is node kp_ptr[i] + j, as above; its descriptor is row kp_ptr[i] + j of desc [n_nodes][dim], dim unsigned bytes (SIFT as
+ * COLMAP and VisualSFM store it: dim = 128).  pairs [n_pairs][2]: for the pair (k, l), k is the QUERY image and l the CANDIDATE
+ * image.  For every keypoint a of k, over the keypoints b of l:
+ *   d2(a, b) = sum (desc_k[a] - desc_l[b])^2, an exact integer (below 2^25 at dim = 512; computed on the i8 matrix cores as
+ *     |a'|^2 + |b'|^2 - 2 a'.b' with every byte shifted by 128, which changes no distance);
+ *   best(a): the b with the smallest (d2, b) -- a tie in distance goes to the smaller index;
+ *   second(a): the smallest d2 over b != best(a); it may equal the best distance;
+ *   with n_l == 0 there is no best, with n_l == 1 no second (reported as -1).
+ * a is matched to best(a) unless, the first that holds (each is counted):
+ *   1. no candidate: n_l == 0;
+ *   2. far: max_dist2 >= 0 and d2_best > max_dist2;
+ *   3. ambiguous: ratio > 0 and there is no second, or NOT (double) d2_best < r2 * (double) d2_second, where r2 = ratio * ratio is
+ *      rounded once, in double, on the host; the device makes one double multiply and one compare (no addition: nothing to
+ *      contract).  A keypoint with a single candidate passes no ratio test;
+ *   4. not mutual: mutual != 0 and best(b), the nearest keypoint of image k to b = best(a) by the same rule with the roles
+ *      swapped (ties to the smaller index), is not a.  The reverse direction takes no ratio or distance test.
+ * ratio in (0, 1], or 0 for no ratio test; max_dist2 < 0 for no distance test.  Pairs are answered in the order given and each
+ * whatever the rest of the list: a duplicated pair is answered twice, a pair (l, k) with l > k is answered as given.
+ * Q = the sum of the query images' keypoint counts over the pairs.  match_ptr [n_pairs + 1]; kp_pairs [Q][2] and dist2 [Q] (sized
+ * by the caller; match_ptr[n_pairs] rows are written): the matches of pair p are rows match_ptr[p] .. match_ptr[p + 1] - 1,
+ * [a, b] local to their images, ascending a, with their d2.  nn_best, nn_dist2, nn_second2 [Q] (each may be NULL): in query
+ * order per pair, every query's best index (-1: none), best d2 (-1: none) and second d2 (-1: none), before any test.
+ * counts [6]: matches, queries (Q), no candidate, far, ambiguous, not mutual; the matches and the four rules' counts add up
+ * to Q.  timings_ms [4] (may be NULL): checks and upload; distances; tests and compaction; download and the rest.
+ * All descriptors go to the device once per call; the pairs are worked through in chunks of about 4 M query rows, so the
+ * per-query temporaries stay bounded.  One workgroup owns 128 queries of one direction of one pair and sweeps all candidates:
+ * many pairs fill the device, one small pair does not.  Integers only (but for the compare of rule 3) and no atomics: the outputs
+ * are a function of the input alone, bitwise equal from call to call.
+ * MVBA_ERR_BADARG, before any device work and with the number in the message: a null kp_ptr, match_ptr, kp_pairs, dist2 or
+ * counts (named, with its position); desc NULL with keypoints present; pairs NULL with n_pairs > 0; n_pairs < 0; n_images < 1;
+ * kp_ptr not ascending from 0; n_nodes >= 2^31; Q >= 2^31; dim not a multiple of 16 in 16 .. 512; ratio outside [0, 1] or NaN;
+ * an image index out of range (the pair and the index are named); a pair of an image with itself.  With n_pairs == 0, or every
+ * query image empty, MVBA_OK with a complete answer (match_ptr all 0, counts 0) and no device work. */
+int mvba_match_descriptors(int32_t n_images, const int64_t *kp_ptr, const uint8_t *desc, int32_t dim, const int32_t *pairs,
+                           int32_t n_pairs, double ratio, int32_t mutual, int64_t max_dist2, int64_t *match_ptr, int32_t *kp_pairs,
+                           int32_t *dist2, int32_t *nn_best, int32_t *nn_dist2, int32_t *nn_second2, int64_t *counts,
+                           double *timings_ms, int32_t device);
+
 /* Host-only check of the per-observation math the kernels use (no GPU needed):
  * cam15 = f,u,v,t[3],R[9]; out = e[2], JX[6], JC[18].                          */
 int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2, double f0,
