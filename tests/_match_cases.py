@@ -43,11 +43,11 @@ def _dim(dim):
     return _case([rng.integers(0, 256, (70, dim), dtype=np.uint8), rng.integers(0, 256, (45, dim), dtype=np.uint8)], [(0, 1), (1, 0)], ratio=0.95)
 
 
-def _flat(changed):
-    """All bytes 0 against all bytes 255 at dim 512; with ``changed`` one byte of candidate 17 is 254."""
-    A, B = np.zeros((40, 512), np.uint8), np.full((37, 512), 255, np.uint8)
+def _flat(changed, dim=512):
+    """All bytes 0 against all bytes 255 (at dim 512 unless said); with ``changed`` one byte of candidate 17 is 254."""
+    A, B = np.zeros((40, dim), np.uint8), np.full((37, dim), 255, np.uint8)
     if changed:
-        B[17, 300] = 254
+        B[17, 300 % dim] = 254
     return _case([A, B], [(0, 1), (1, 0)])
 
 
@@ -140,6 +140,136 @@ def reference(name):
 @functools.lru_cache(maxsize=None)
 def orientation_perm():
     return _orientation()[1]
+
+
+# ---- the structural limits of the kernels ("Limits pass") ---------------------------------------------------
+# Cases of their own, beside CASES: LARGEST keeps naming the largest members of CASES.
+LIMIT_DIMS = tuple(range(16, 513, 16))  # every dim the entry point takes: every k-step count, full and partial
+FLAT_DIMS = (16, 64, 256, 496, 512)     # the flat extremes: KS = 1, 2, 8, 16 (partial), 16
+
+
+def ksteps(dim):
+    """csrc/mvba_match.h: match_ksteps, the instantiation a dim runs -- the smallest power of two with 32 KS >= dim."""
+    ks = 1
+    while KSTEP * ks < dim:
+        ks *= 2
+    return ks
+
+
+def lane_of_row(row):
+    """(lane half, accumulator register) that holds candidate ``row`` of its image: the C/D map of DESIGN.md §25 inside the row's 32
+    of an MFMA tile, row = (reg & 3) + 8 (reg >> 2) + 4 half."""
+    r = row % 32
+    half, reg = (r >> 2) & 1, (r & 3) + 4 * (r >> 3)
+    assert r == (reg & 3) + 8 * (reg >> 2) + 4 * half
+    return half, reg
+
+
+TIE_NC = 300   # candidates of an image: LDS tiles of 128, 128 and 44
+TIE_NQ = 33    # queries of an image: waves 0 and 1 of the workgroup
+TIE_POS = (0, 1, 3, 4, 7, 8, 12, 15, 16, 28, 31, 32, 36, 63, 64, 127, 128, 132, 255, 256, 260, 299)
+# (byte 0 of row i raised by, byte 1 of row j lowered by), i < j: the two rows differ, and so do their norms
+TIE_VARIANTS = {"tie": (3, 3), "near_first": (3, 4), "near_last": (4, 3)}
+TIE_TRIPLES = ((4, 132, 260), (31, 128, 256), (127, 255, 299), (12, 200, 257))  # one row in each LDS tile
+TIE_TRIPLE_VARIANTS = {"tie3": (3, 3, 3), "mid3": (4, 3, 4)}  # byte 0 raised, byte 1 lowered, byte 2 raised
+TIE_FAR = 16   # every row that is not planted is farther than this from the query
+
+
+def tie_rounds():
+    """The 231 pairs i < j of TIE_POS as 21 rounds of 11 disjoint pairs (the circle method): a round is one candidate image."""
+    n = len(TIE_POS)
+    rounds = []
+    for r in range(n - 1):
+        ring = [n - 1] + [(r + k) % (n - 1) for k in range(n - 1)]
+        rounds.append([tuple(sorted((TIE_POS[ring[k]], TIE_POS[ring[n - 1 - k]]))) for k in range(n // 2)])
+    return rounds
+
+
+@functools.lru_cache(maxsize=None)
+def ties():
+    """(case, expect).  dim 16, no ratio, one way.  Query images 0 .. 20 (one per round of tie_rounds) and 21 (the triples), TIE_NQ
+    random rows each; then the candidate images, TIE_NC random rows each: per round one for every variant of TIE_VARIANTS, and one
+    for every variant of TIE_TRIPLE_VARIANTS.  In the image of (round, variant) the pair k = (i, j) of the round belongs to ONE query
+    row Z (the rows of a query image are dealt out by a permutation, so that planted queries fall into both waves): row i is Z
+    with byte 0 raised, row j is Z with byte 1 lowered, by the variant's amounts.  The other 22 query rows of that pair of images
+    meet random rows only.  expect: a list of (variant, planted rows, the query's row in the call's Q, best, best2, second2)."""
+    rng = np.random.default_rng(2)
+    rounds = tie_rounds()
+    n_q = len(rounds) + 1
+    queries = [rng.integers(8, 248, (TIE_NQ, 16)).astype(np.uint8) for _ in range(n_q)]
+    cands, pairs, expect = [], [], []
+
+    def image(name, q, slots, rows_of, amounts, bytes_sign):
+        B = rng.integers(0, 256, (TIE_NC, 16)).astype(np.uint8)
+        for k, rows in enumerate(rows_of):
+            a = int(slots[k])
+            Z = queries[q][a].astype(np.int64)
+            for row, amount, (byte, sign) in zip(rows, amounts, bytes_sign):
+                B[row] = Z
+                B[row, byte] = Z[byte] + sign * amount
+            d2 = sorted(amount * amount for amount in amounts)
+            best = rows[int(np.argmin(amounts))]  # (argmin: the first of equal amounts, the smaller row)
+            expect.append((name, tuple(rows), len(pairs) * TIE_NQ + a, best, d2[0], d2[1]))
+        pairs.append((q, n_q + len(cands)))
+        cands.append(B)
+
+    for q, rnd in enumerate(rounds):
+        slots = rng.permutation(TIE_NQ)
+        for v, (name, amounts) in enumerate(TIE_VARIANTS.items()):
+            image(name, q, slots[11 * v:11 * v + 11], rnd, amounts, ((0, 1), (1, -1)))
+    slots = rng.permutation(TIE_NQ)
+    for v, (name, amounts) in enumerate(TIE_TRIPLE_VARIANTS.items()):
+        image(name, n_q - 1, slots[4 * v:4 * v + 4], TIE_TRIPLES, amounts, ((0, 1), (1, -1), (2, 1)))
+    return _case(queries + cands, pairs, mutual=False), expect
+
+
+WAVE_NQ = (31, 32, 33, 63, 64, 65, 95, 96, 97)  # either side of every wave's 32 queries of a workgroup
+WAVE_NC = (1, 33, 129)
+
+
+def _waves():
+    """Images 0 .. 8 have WAVE_NQ keypoints, images 9 .. 11 WAVE_NC: all 27 pairs in one call, dim 128."""
+    rng = np.random.default_rng(33)
+    arrays = [rng.integers(0, 256, (n, 128), dtype=np.uint8) for n in WAVE_NQ + WAVE_NC]
+    return _case(arrays, [(i, len(WAVE_NQ) + j) for i in range(len(WAVE_NQ)) for j in range(len(WAVE_NC))], ratio=0.95)
+
+
+SCAN_BLOCK = 1024      # csrc/mvba_tracks.h: TRK_SCAN_BLOCK, the rows of a block of the scan
+SCAN_SUMS = 256        # block totals k_tracks_scan_sums takes per trip
+SCAN_NQ = (100_000, 0, 163_168, 1)  # 263 169 = 256 * 1024 + 1024 + 1 query rows: 258 blocks, the last holds the last image's one query
+SCAN_NC = 5
+
+
+@functools.lru_cache(maxsize=None)
+def _scan_arrays():
+    rng = np.random.default_rng(258)
+    arrays = [rng.integers(0, 256, (n, 16), dtype=np.uint8) for n in SCAN_NQ + (SCAN_NC,)]
+    arrays[4][2, 5] = 100
+    arrays[3][0] = arrays[4][2]  # the one query of block 257: candidate 2 with one byte raised by 1 -- kept under every rule
+    arrays[3][0, 5] = 101
+    return arrays
+
+
+def _scan(mutual):
+    """Query images 0 .. 3 of SCAN_NQ rows (image 1 is empty), each against image 4's SCAN_NC candidates, ratio 0.9, dim 16."""
+    return _case(_scan_arrays(), [(i, 4) for i in range(4)], ratio=0.9, mutual=mutual)
+
+
+LIMIT_CASES = {f"k{d:03d}": functools.partial(_dim, d) for d in LIMIT_DIMS}
+LIMIT_CASES.update({f"flat{d:03d}": functools.partial(_flat, False, d) for d in FLAT_DIMS})
+LIMIT_CASES.update({f"flat_one{d:03d}": functools.partial(_flat, True, d) for d in FLAT_DIMS})
+LIMIT_CASES.update({"ties": lambda: ties()[0], "waves": _waves, "scan258": lambda: _scan(False), "scan258_mutual": lambda: _scan(True)})
+
+
+@functools.lru_cache(maxsize=None)
+def limit_case(name):
+    return LIMIT_CASES[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def limit_reference(name):
+    kp_ptr, desc, pairs, kw = limit_case(name)
+    return MR.match_descriptors(kp_ptr, desc, pairs, **kw)
 
 
 # ---- end to end: a scene with descriptors ---------------------------------------------------------------------------------

@@ -134,6 +134,114 @@ def reference(name):
     return TR.build_tracks(kp_ptr, kp_xy, edges, ok, min_length)
 
 
+# ---- the structural limits of the kernels ("Limits pass") ---------------------------------------------------
+# Graphs of their own, beside GRAPHS.
+SCAN_BLOCK = 1024        # csrc/mvba_tracks.h: TRK_SCAN_BLOCK, the nodes of a block of the scan
+SCAN_SUMS = 256          # block totals k_tracks_scan_sums takes per trip: the second trip starts at node 262 144
+HOOK_EDGES = 8192 * 256  # TRK_HOOK_GRID workgroups of 256 threads: the grid stride of k_tracks_hook starts beyond
+BIG_M, BIG_T = 87_400, 1_100  # keypoints of images 0 .. 2 and of images 3 .. 5: the small images lie beyond node 262 144
+BIG_COPIES = 16          # the long form lists every edge this often, and once more turned round
+
+
+def _big_part(base, m, period):
+    """Tracks i = 0 .. m - 1 over three images of m keypoints from node ``base`` on: a = base + i, b = a + m, c = b + m.  By
+    k = i mod period: 7 -- a - b - c and b - (a + 1): two keypoints of one image, a conflict of 4 nodes; 8 -- no edge of its
+    own (its a is in the conflict before it, its b and c stay unmatched); 20 -- a - b alone, shorter than min_length = 3, c
+    unmatched; 30, 31, 32 -- three tracks chained c - (a + 1): 9 nodes, more than the 6 images; every other k -- the clean
+    track a - b - c."""
+    i = np.arange(m)
+    k = i % period
+    a, b, c = base + i, base + m + i, base + 2 * m + i
+    full = (k != 8) & (k != 20)
+    e = [np.stack([a[full], b[full]], axis=1), np.stack([c[full], b[full]], axis=1), np.stack([b[k == 20], a[k == 20]], axis=1),
+         np.stack([b[k == 7], a[k == 7] + 1], axis=1), np.stack([c[(k == 30) | (k == 31)], a[(k == 30) | (k == 31)] + 1], axis=1)]
+    assert i[k == 7].max() + 1 < m and i[k == 31].max() + 1 < m
+    return np.concatenate(e)
+
+
+@functools.lru_cache(maxsize=None)
+def _big_edges():
+    rng = np.random.default_rng(260)
+    e = np.concatenate([_big_part(0, BIG_M, 1000), _big_part(3 * BIG_M, BIG_T, 100)])
+    return rng.permutation(e, axis=0)
+
+
+def _big(long):
+    """Images of BIG_M, BIG_M, BIG_M, BIG_T, BIG_T, BIG_T keypoints: 265 500 nodes, 260 scan blocks, with _big_part's tracks over
+    the first three and over the last three (whose roots lie in scan blocks 256 and 257), min_length = 3.  ``long``: every edge
+    BIG_COPIES times and once turned round, in a random order -- more edges than one sweep of the hook kernel's grid takes."""
+    e = _big_edges()
+    if long:
+        e = np.random.default_rng(261).permutation(np.concatenate([e] * BIG_COPIES + [e[:, ::-1]]), axis=0)
+    return _graph([BIG_M] * 3 + [BIG_T] * 3, e, None, 3)
+
+
+SORT_M, SORT_N = 70, 300
+# candidate rank -> length: lanes 0, 62, 63 of wave 0; lanes 0, 1, 63 of wave 1; lane 0 of wave 2; lanes 8, 63 of wave 3; and
+# lanes 0 and 43 of the second workgroup.  (The last long track is the longest: whatever length a lane applies to the wrong
+# segment, it stays inside the buffer.)
+SORT_LONG = {0: 33, 62: 40, 63: 64, 64: 65, 65: 70, 127: 33, 128: 40, 200: 64, 255: 65, 256: 40, 299: 70}
+
+
+def _sort_waves():
+    """SORT_M images; image 0 has SORT_N keypoints and track c starts at its keypoint c, so candidate c IS track c.  The tracks
+    of SORT_LONG have 33 .. 70 keypoints, all others 2 or 3; each over a random set of images, joined by a random spanning tree,
+    the edges of all of them in one random order."""
+    rng = np.random.default_rng(300)
+    lengths = [SORT_LONG.get(c, 2 + int(rng.integers(2))) for c in range(SORT_N)]
+    images = [np.concatenate([[0], 1 + np.sort(rng.choice(SORT_M - 1, L - 1, replace=False))]) for L in lengths]
+    counts = np.bincount(np.concatenate(images), minlength=SORT_M)
+    kp_ptr = np.concatenate([[0], np.cumsum(counts)])
+    used = np.zeros(SORT_M, np.int64)
+    edges = []
+    for im in images:
+        nodes = kp_ptr[im] + used[im]
+        used[im] += 1
+        nodes = rng.permutation(nodes)
+        edges += [(nodes[i], nodes[rng.integers(i)]) for i in range(1, len(nodes))]
+    assert counts[0] == SORT_N and max(lengths) <= SORT_M
+    return _graph(counts, rng.permutation(np.array(edges), axis=0))
+
+
+def _ends():
+    """Images 0 .. 7 with 0, 2, 2, 0, 0, 2, 1, 0 keypoints: the first and the last image are empty, and two in the middle in a row.
+    Tracks {0, 2, 4} (images 1, 2, 5) and {1, 5, 6} (images 1, 5, 6); node 3 is unmatched."""
+    return _graph([0, 2, 2, 0, 0, 2, 1, 0], [(0, 2), (4, 2), (5, 1), (6, 5)])
+
+
+STAIR_K = 140  # candidates of two entries each: the boundary of candidates 127 | 128 is entry 255 | 256 of the sorted buffer
+
+
+def _stairs():
+    """Candidate k = {lo[k] in image k, hi[k] in image k + 1}, k = 0 .. STAIR_K - 1: in the sorted buffer the last entry of
+    candidate k and the first of candidate k + 1 are the two keypoints of image k + 1 -- neighbours in ONE image that belong to
+    two components.  (Which of the two comes first inside the image alternates.)  After them the one true conflict: x in image
+    STAIR_K, y and z both in image STAIR_K + 1."""
+    K = STAIR_K
+    counts = [1] + [2] * K + [2]
+    kp_ptr = np.concatenate([[0], np.cumsum(counts)])
+    lo = np.array([0] + [kp_ptr[k] + (k % 2) for k in range(1, K)])
+    hi = np.array([kp_ptr[k + 1] + (1 - (k + 1) % 2 if k + 1 < K else 0) for k in range(K)])
+    x, y, z = kp_ptr[K] + 1, kp_ptr[K + 1], kp_ptr[K + 1] + 1
+    return _graph(counts, [(h, l) for l, h in zip(lo, hi)] + [(x, y), (z, x)])
+
+
+LIMIT_GRAPHS = {"big": lambda: _big(False), "big_long": lambda: _big(True), "sort_waves": _sort_waves, "ends": _ends, "stairs": _stairs}
+LIMIT_NODE_TRACK = {"ends": [0, 1, 0, -1, 0, 1, 1]}
+LIMIT_CAM_IDX = {"ends": [1, 2, 5, 1, 5, 6]}
+
+
+@functools.lru_cache(maxsize=None)
+def limit_graph(name):
+    return LIMIT_GRAPHS[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def limit_reference(name):
+    kp_ptr, kp_xy, edges, ok, min_length = limit_graph(name)
+    return TR.build_tracks(kp_ptr, kp_xy, edges, ok, min_length)
+
+
 # ---- an observation list as a matcher would deliver it ------------------------------------------------------------------
 def matcher_output(pt_ptr, cam_idx, xy, n_images, seed, extra=5, edges="all", wrong=0.0):
     """Keypoints and matches of the list (pt_ptr, cam_idx, xy): every observation is a keypoint of its image, the keypoints of an

@@ -1,5 +1,5 @@
 """Descriptor matching on the device: mvba_match_descriptors against the NumPy reference (tests/_match_ref.py) on
-the cases of tests/_match_cases.py -- every comparison exact --, its independence of the rest of the pair list, its
+the cases of tests/_match_cases.py and on the limit cases beside them -- every comparison exact --, its independence of the rest of the pair list, its
 repeatability, and a scene's descriptors through match_descriptors, verify_matches, build_tracks, bootstrap and Huber bundle
 adjustment."""
 import numpy as np
@@ -18,8 +18,8 @@ pytestmark = pytest.mark.gpu
 ARRAYS = ("match_ptr", "kp_pairs", "dist2", "nn_best", "nn_dist2", "nn_second2")
 
 
-def _run(name, pairs=None):
-    kp_ptr, desc, all_pairs, kw = MC.case(name)
+def _run(name, pairs=None, case=MC.case):
+    kp_ptr, desc, all_pairs, kw = case(name)
     kw = dict(kw, ratio=0.0 if kw["ratio"] is None else kw["ratio"])
     return _mvba.match_descriptors(kp_ptr, desc, all_pairs if pairs is None else pairs, want_nn=True, **kw)
 
@@ -47,6 +47,31 @@ def test_case_matches_the_reference(name):
     kp_ptr, desc, pairs, kw = MC.case(name)
     bare = _mvba.match_descriptors(kp_ptr, desc, pairs, **dict(kw, ratio=kw["ratio"] or 0.0))
     assert "nn_best" not in bare and all(bare[k].tobytes() == got[k].tobytes() for k in ARRAYS[:3])
+
+
+@pytest.mark.parametrize("name", sorted(MC.LIMIT_CASES))
+def test_limit_case_matches_the_reference(name):
+    """The limits pass of DESIGN.md §25: every k-step count at its edges, the flat extremes per instantiation, ties and
+    orderings by the candidates' places in the wave, the wave edges of a query block, and more query rows than the scan's
+    second level takes in one trip.  What each case is for is asserted on the reference alone in tests/test_match_cpu.py."""
+    got = _run(name, case=MC.limit_case)
+    print(f"{name}: {got['n_matches']} matches of {got['n_queries']} queries, timings {got['timings_ms']}")
+    want = MC.limit_reference(name)
+    _same(got, want, name)
+    if name.startswith("flat"):
+        d = int(name[-3:])
+        assert (got["nn_second2"][:40] == d * 255 ** 2).all()
+        if name.startswith("flat_one"):
+            assert (got["nn_best"][:40] == 17).all() and (got["nn_dist2"][:40] == d * 255 ** 2 - 255 ** 2 + 254 ** 2).all()
+        else:
+            assert (got["nn_best"] == 0).all() and (got["nn_dist2"] == d * 255 ** 2).all() and (got["nn_second2"] == d * 255 ** 2).all()
+    if name == "ties":
+        for variant, rows, q, best, best2, second2 in MC.ties()[1]:
+            assert (got["nn_best"][q], got["nn_dist2"][q], got["nn_second2"][q]) == (best, best2, second2), (variant, rows, MC.lane_of_row(rows[0]),
+                                                                                                             MC.lane_of_row(rows[1]))
+    if name.startswith("scan258"):
+        assert got["match_ptr"][1] == got["match_ptr"][2] and got["match_ptr"][4] == got["match_ptr"][3] + 1  # the empty image; the last query
+        assert got["kp_pairs"][-1].tolist() == [0, 2] and got["dist2"][-1] == 1
 
 
 def test_a_pair_is_answered_whatever_the_rest_of_the_list():

@@ -1,5 +1,5 @@
 """Feature tracks from pairwise matches on the device: mvba_build_tracks against the NumPy reference
-(tests/_tracks_ref.py) on the hand-made graphs of tests/_tracks_cases.py -- every comparison exact: integers, and xy bit for bit --,
+(tests/_tracks_ref.py) on the hand-made graphs of tests/_tracks_cases.py and the limit graphs beside them -- every comparison exact: integers, and xy bit for bit --,
 its invariance under a restatement of the edge set, the recovery of a scene's observation list, and matches with wrong ones among
 them through verify_matches, build_tracks, bootstrap and Huber bundle adjustment."""
 import numpy as np
@@ -43,6 +43,29 @@ def test_hand_made_graph_matches_the_reference(name):
     # without coordinates: the same integers, and no xy
     bare = _mvba.build_tracks(kp_ptr, None, edges, edge_ok=ok, min_length=min_length)
     assert bare["xy"] is None and all(bare[k].tobytes() == got[k].tobytes() for k in ARRAYS if k != "xy")
+
+
+@pytest.mark.parametrize("name", sorted(TC.LIMIT_GRAPHS))
+def test_limit_graph_matches_the_reference(name):
+    """The limits pass of DESIGN.md §24: more nodes than the scan's second level takes in one trip and more edges than one sweep
+    of the hook kernel's grid, long tracks in every wave of the sort, empty images at both ends, and neighbouring segments that
+    meet in one image.  What each graph is for is asserted on the reference alone in tests/test_tracks_cpu.py."""
+    kp_ptr, kp_xy, edges, ok, min_length = TC.limit_graph(name)
+    got = _mvba.build_tracks(kp_ptr, kp_xy, edges, edge_ok=ok, min_length=min_length)
+    print(f"{name}: {len(edges)} edges, {got['n_rounds']} rounds, timings {got['timings_ms']}")
+    _same(got, TC.limit_reference(name), name)
+    np.testing.assert_array_equal(got["xy"], kp_xy[got["obs_node"]])
+    if name in TC.LIMIT_NODE_TRACK:
+        assert got["node_track"].tolist() == TC.LIMIT_NODE_TRACK[name] and got["cam_idx"].tolist() == TC.LIMIT_CAM_IDX[name]
+    if name == "big_long":  # the edge set of "big", restated: byte for byte the same answer
+        plain = TC.limit_reference("big")
+        assert all(got[k].tobytes() == plain[k].tobytes() for k in ARRAYS)
+    if name == "sort_waves":
+        assert got["n_tracks"] == TC.SORT_N
+        for a in range(got["n_tracks"]):
+            assert (np.diff(got["cam_idx"][got["pt_ptr"][a]:got["pt_ptr"][a + 1]]) > 0).all()
+    if name == "stairs":
+        assert (got["n_tracks"], got["n_conflicting"], got["n_conflicting_nodes"]) == (TC.STAIR_K, 1, 3)
 
 
 def test_no_edges_leaves_every_keypoint_unmatched():

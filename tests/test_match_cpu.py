@@ -19,9 +19,14 @@ def _independent(A, B, ratio, mutual, max_dist2):
     a stable argsort per query -- no expansion into norms and dot products, no argmin."""
     na, nb = len(A), len(B)
     D = np.zeros((na, nb))
-    for a in range(na):
-        diff = B.astype(np.float64) - A[a].astype(np.float64)
-        D[a] = (diff * diff).sum(axis=1)
+    if na <= nb:
+        for a in range(na):
+            diff = B.astype(np.float64) - A[a].astype(np.float64)
+            D[a] = (diff * diff).sum(axis=1)
+    else:  # (the same differences, a candidate at a time: the loop stays short with 10^5 queries of 5 candidates)
+        for b in range(nb):
+            diff = A.astype(np.float64) - B[b].astype(np.float64)
+            D[:, b] = (diff * diff).sum(axis=1)
     order = np.argsort(D, axis=1, kind="stable")  # by (distance, index)
     rows = np.arange(na)
     best = order[:, 0] if nb else np.full(na, -1)
@@ -39,8 +44,16 @@ def _independent(A, B, ratio, mutual, max_dist2):
 
 @pytest.mark.parametrize("name", sorted(MC.CASES))
 def test_reference_against_an_independent_formulation(name):
-    kp_ptr, desc, pairs, kw = MC.case(name)
-    ref = MC.reference(name)
+    _reference_against_independent(MC.case(name), MC.reference(name))
+
+
+@pytest.mark.parametrize("name", sorted(MC.LIMIT_CASES))
+def test_limit_reference_against_an_independent_formulation(name):
+    _reference_against_independent(MC.limit_case(name), MC.limit_reference(name))
+
+
+def _reference_against_independent(case, ref):
+    kp_ptr, desc, pairs, kw = case
     at = 0
     for i, (k, l) in enumerate(pairs):
         A, B = desc[kp_ptr[k]:kp_ptr[k + 1]], desc[kp_ptr[l]:kp_ptr[l + 1]]
@@ -103,6 +116,87 @@ def test_premises_of_the_cases():
     assert r["kp_pairs"].tolist() == [[i, b] for i, b in enumerate(MC.WIDTH_BEST)]
     assert max(MC.CASES, key=lambda n: MC.reference(n)["n_queries"]) == MC.LARGEST[0] and max(MC.CASES, key=lambda n: MC.case(n)[0][-1]) == MC.LARGEST[1]
     assert MC.CHUNK_PAIRS * (MC.WIDTH_N + 3) > MC.CHUNK_ROWS  # the list of test_a_long_pair_list_is_cut_into_chunks does not fit one chunk
+
+
+def test_premises_of_the_dim_and_flat_limit_cases():
+    """Every k-step count the kernel is instantiated for is run by a dim that fills its steps and by one that does not; the flat
+    extremes give dim x 255^2 in every instantiation they are stated for."""
+    ks = {d: MC.ksteps(d) for d in MC.LIMIT_DIMS}
+    assert MC.LIMIT_DIMS == tuple(range(16, 513, 16)) and set(ks.values()) == {1, 2, 4, 8, 16}
+    for k in (1, 2, 4, 8, 16):
+        assert ks[32 * k] == k and any(v == k and d < 32 * k for d, v in ks.items())  # full, and partial
+    assert [ks[d] for d in (64, 80, 144, 240, 256, 272)] == [2, 4, 8, 8, 8, 16]  # upper edges, and just above the one before
+    for d in MC.LIMIT_DIMS:
+        kp_ptr, desc, pairs, kw = MC.limit_case(f"k{d:03d}")
+        assert desc.shape == (115, d) and kp_ptr.tolist() == [0, 70, 115] and pairs.tolist() == [[0, 1], [1, 0]] and kw["ratio"] == 0.95 and kw["mutual"]
+    assert {MC.ksteps(d) for d in MC.FLAT_DIMS} == {1, 2, 8, 16} and 496 % MC.KSTEP
+    for d in MC.FLAT_DIMS:
+        r, top = MC.limit_reference(f"flat{d:03d}"), d * 255 ** 2
+        assert (r["nn_dist2"] == top).all() and (r["nn_second2"] == top).all() and (r["nn_best"] == 0).all()
+        assert r["kp_pairs"].tolist() == [[0, 0], [0, 0]]
+        r = MC.limit_reference(f"flat_one{d:03d}")
+        assert (r["nn_best"][:40] == 17).all() and (r["nn_dist2"][:40] == top - 255 ** 2 + 254 ** 2).all() and (r["nn_second2"][:40] == top).all()
+
+
+def test_premises_of_the_tie_case():
+    """On the reference alone: every planted query has exactly the nearest two it was built for, nothing else comes near, every
+    pair of TIE_POS occurs in every variant, and among the tied pairs are those the three merges of k_match_nn decide."""
+    (kp_ptr, desc, pairs, kw), expect = MC.ties()
+    r = MC.limit_reference("ties")
+    assert kw["ratio"] is None and not kw["mutual"] and desc.shape[1] == 16 and len(pairs) == 3 * 21 + 2
+    assert MC.TIE_NQ > 32 and (MC.TIE_NC + MC.TC - 1) // MC.TC == 3
+    by_variant = {}
+    for variant, rows, q, best, best2, second2 in expect:
+        assert (r["nn_best"][q], r["nn_dist2"][q], r["nn_second2"][q]) == (best, best2, second2), (variant, rows)
+        k, l = pairs[q // MC.TIE_NQ]
+        D = MR.distance2(desc[kp_ptr[k]:kp_ptr[k + 1]][q % MC.TIE_NQ][None], desc[kp_ptr[l]:kp_ptr[l + 1]])[0]
+        assert sorted(np.nonzero(D <= MC.TIE_FAR)[0].tolist()) == sorted(rows)  # the planted rows, and they alone
+        by_variant.setdefault(variant, []).append(rows)
+    every = sorted((i, j) for a, i in enumerate(MC.TIE_POS) for j in MC.TIE_POS[a + 1:])
+    assert len(every) == 231 and all(sorted(by_variant[v]) == every for v in MC.TIE_VARIANTS)
+    assert all(sorted(by_variant[v]) == sorted(MC.TIE_TRIPLES) for v in MC.TIE_TRIPLE_VARIANTS)
+    assert all(sorted(row // MC.TC for row in t) == [0, 1, 2] for t in MC.TIE_TRIPLES)
+    want = {"tie": (9, 9), "near_first": (9, 16), "near_last": (9, 16), "tie3": (9, 9), "mid3": (9, 16)}
+    for variant, rows, q, best, best2, second2 in expect:
+        assert (best2, second2) == want[variant]
+        assert best == {"tie": rows[0], "near_first": rows[0], "near_last": rows[1], "tie3": rows[0], "mid3": rows[1]}[variant]
+    waves = {(q % MC.TIE_NQ) // 32 for _, _, q, _, _, _ in expect}
+    assert waves == {0, 1}  # planted queries in both waves that take part
+    # where the two rows of a tied pair sit (DESIGN.md §25: the row-to-(half, register) map), i < j
+    same_tile = [(i, j) for i, j in every if i // 32 == j // 32]
+    quad = [(i, j) for i, j in same_tile if MC.lane_of_row(i)[0] == MC.lane_of_row(j)[0] and MC.lane_of_row(i)[1] >> 2 == MC.lane_of_row(j)[1] >> 2]
+    lane = [(i, j) for i, j in same_tile if MC.lane_of_row(i)[0] == MC.lane_of_row(j)[0] and MC.lane_of_row(i)[1] >> 2 != MC.lane_of_row(j)[1] >> 2]
+    upper = [(i, j) for i, j in same_tile if MC.lane_of_row(i)[0] == 1 and MC.lane_of_row(j)[0] == 0]
+    upper_far = [(i, j) for i, j in every if i // 32 != j // 32 and MC.lane_of_row(i)[0] == 1 and MC.lane_of_row(j)[0] == 0]
+    print(f"tied pairs: {len(quad)} in one register quad, {len(lane)} in one lane across quads, {len(upper)} + {len(upper_far)} with the smaller "
+          f"index in the upper half (inside one MFMA tile + across tiles)")
+    assert (0, 1) in quad and (4, 7) in quad and (12, 15) in quad and (0, 8) in lane
+    assert set(upper) == {(4, 8), (7, 8), (4, 16), (7, 16), (12, 16), (15, 16)} and {(4, 32), (31, 32), (63, 64), (127, 128), (255, 256)} <= set(upper_far)
+    assert {(31, 32), (127, 128), (255, 256)} <= set(every)
+    assert [MC.lane_of_row(x) for x in (0, 3, 4, 7, 8, 31)] == [(0, 0), (0, 3), (1, 0), (1, 3), (0, 4), (1, 15)]
+
+
+def test_premises_of_the_wave_and_scan_limit_cases():
+    kp_ptr, desc, pairs, kw = MC.limit_case("waves")
+    sizes = {(int(kp_ptr[k + 1] - kp_ptr[k]), int(kp_ptr[l + 1] - kp_ptr[l])) for k, l in pairs}
+    assert sizes == {(a, b) for a in MC.WAVE_NQ for b in MC.WAVE_NC} and len(pairs) == 27 and desc.shape[1] == 128
+    assert MC.WAVE_NQ == tuple(32 * w + e for w in (1, 2, 3) for e in (-1, 0, 1)) and kw["ratio"] == 0.95 and kw["mutual"]
+    r = MC.limit_reference("waves")
+    assert r["n_matches"] > 0 and r["n_ambiguous"] > 0 and r["n_not_mutual"] > 0
+    # more query rows than one trip of the scan's second level: 258 blocks, matches on both sides of block 256
+    kp_ptr, desc, pairs, kw = MC.limit_case("scan258")
+    r = MC.limit_reference("scan258")
+    Q = sum(MC.SCAN_NQ)
+    assert Q == r["n_queries"] == MC.SCAN_SUMS * MC.SCAN_BLOCK + MC.SCAN_BLOCK + 1 and (Q + MC.SCAN_BLOCK - 1) // MC.SCAN_BLOCK == 258
+    assert np.diff(kp_ptr).tolist() == list(MC.SCAN_NQ) + [MC.SCAN_NC] and desc.shape[1] == 16 and kw["ratio"] == 0.9 and not kw["mutual"]
+    kept = np.bincount(np.nonzero(r["code"] == MR.KEPT)[0] // MC.SCAN_BLOCK, minlength=258)
+    print(f"scan258: {r['n_matches']} matches, {r['n_ambiguous']} ambiguous; kept in blocks 254 .. 257: {kept[254:].tolist()}")
+    assert kept[255] > 0 and kept[256] > 0 and kept[257] == 1 and r["n_ambiguous"] > 0
+    assert r["match_ptr"][1] == r["match_ptr"][2] and r["match_ptr"][1] > 0  # the empty image repeats an entry
+    assert r["match_ptr"][4] == r["match_ptr"][3] + 1 and r["kp_pairs"][-1].tolist() == [0, 2] and r["dist2"][-1] == 1
+    m = MC.limit_reference("scan258_mutual")  # the same rows with the reverse direction: 5 queries against 100 000 and 163 168 candidates
+    assert MC.limit_case("scan258_mutual")[3]["mutual"] and m["n_not_mutual"] > 0 and 0 < m["n_matches"] <= 2 * MC.SCAN_NC + 1
+    assert m["kp_pairs"][-1].tolist() == [0, 2] and m["nn_best"].tobytes() == r["nn_best"].tobytes()
 
 
 def _call(lib, n_images, kp_ptr, desc, dim, pairs, n_pairs, ratio=0.8, mutual=1, max_dist2=-1, null=()):

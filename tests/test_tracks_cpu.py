@@ -26,6 +26,19 @@ def test_reference_labels_against_scipy(name):
         ok = None
     else:
         kp_ptr, _, edges, ok, _ = TC.graph(name)
+    _labels_against_scipy(csgraph, coo_matrix, kp_ptr, edges, ok)
+
+
+@pytest.mark.parametrize("name", sorted(TC.LIMIT_GRAPHS))
+def test_limit_reference_labels_against_scipy(name):
+    csgraph = pytest.importorskip("scipy.sparse.csgraph")
+    from scipy.sparse import coo_matrix
+
+    kp_ptr, _, edges, ok, _ = TC.limit_graph(name)
+    _labels_against_scipy(csgraph, coo_matrix, kp_ptr, edges, ok)
+
+
+def _labels_against_scipy(csgraph, coo_matrix, kp_ptr, edges, ok):
     n = int(kp_ptr[-1])
     used = edges if ok is None else edges[ok != 0]
     label = TR.labels(n, used)
@@ -62,6 +75,66 @@ def test_premises_of_the_hand_made_cases():
     assert r["pt_ptr"].tolist() == [0] and r["n_tracks"] == 0 and len(r["node_track"]) == 0
     r = TC.reference("path4096")
     assert r["pt_ptr"].tolist() == [0, 4096] and r["cam_idx"].tolist() == list(range(4096))
+
+
+def test_premises_of_the_big_limit_graphs():
+    """More than 256 scan blocks of nodes with roots of every class on both sides of node 262 144 (in both scans: candidates, and
+    survivors), and in the long form more edges than one sweep of the hook kernel's grid -- the same edge SET, the same answer."""
+    kp_ptr, _, edges, ok, min_length = TC.limit_graph("big")
+    _, _, long_edges, _, _ = TC.limit_graph("big_long")
+    n, second_trip = int(kp_ptr[-1]), TC.SCAN_SUMS * TC.SCAN_BLOCK
+    assert n > second_trip + TC.SCAN_BLOCK and len(kp_ptr) - 1 == 6 and min_length == 3 and ok is None
+    assert 0 < len(edges) < TC.HOOK_EDGES < len(long_edges) == (TC.BIG_COPIES + 1) * len(edges)
+    as_set = lambda e: np.unique(e.min(axis=1).astype(np.int64) * n + e.max(axis=1))
+    np.testing.assert_array_equal(as_set(edges), as_set(long_edges))
+    assert (long_edges[:, 0] < long_edges[:, 1]).any() and (long_edges[:, 0] > long_edges[:, 1]).any()
+    r, rl = TC.limit_reference("big"), TC.limit_reference("big_long")
+    for key in ("pt_ptr", "cam_idx", "obs_node", "xy", "node_track"):
+        assert r[key].tobytes() == rl[key].tobytes(), key
+    assert all(r[k] == rl[k] for k in TR.COUNTS) and all(r[k] > 0 for k in TR.COUNTS)
+    label, size = r["label"], np.bincount(r["label"], minlength=n)
+    roots = np.nonzero(label == np.arange(n))[0]
+    code = r["node_track"][roots]
+    classes = {"survivor": code >= 0, "conflict": (code == -3) & (size[roots] <= 6), "oversize": (code == -3) & (size[roots] > 6),
+               "short": code == -2, "singleton": code == -1}
+    block = roots // TC.SCAN_BLOCK
+    for name, of in classes.items():
+        counts = [int((of & (block < TC.SCAN_SUMS)).sum()), int((of & (block >= TC.SCAN_SUMS)).sum())]
+        print(f"big: {name} roots below node {second_trip}, from it on: {counts}")
+        assert min(counts) > 0, name
+
+
+def test_premises_of_the_small_limit_graphs():
+    # long tracks in every wave of the sort, at lanes 0 and 63, three of them in one wave among short ones
+    r = TC.limit_reference("sort_waves")
+    lengths = np.diff(r["pt_ptr"])
+    assert r["n_tracks"] == TC.SORT_N == len(lengths) and r["obs_node"][r["pt_ptr"][:-1]].tolist() == list(range(TC.SORT_N))  # candidate c is track c
+    assert all(lengths[c] == L for c, L in TC.SORT_LONG.items()) and set(TC.SORT_LONG.values()) == {33, 40, 64, 65, 70}
+    short = np.delete(lengths, list(TC.SORT_LONG))
+    assert set(short.tolist()) == {2, 3} and min(TC.SORT_LONG.values()) > TC.LANE_MAX
+    place = [(c // TC.BLOCK, c % TC.BLOCK // 64, c % 64) for c in TC.SORT_LONG]  # (workgroup, wave, lane)
+    assert {p[:2] for p in place} == {(0, 0), (0, 1), (0, 2), (0, 3), (1, 0)} and {0, 1, 62, 63} <= {p[2] for p in place}
+    assert sum(p[:2] == (0, 0) for p in place) == 3 and sum(p[:2] == (0, 1) for p in place) == 3
+    assert TC.SORT_LONG[max(TC.SORT_LONG)] == max(TC.SORT_LONG.values()) == TC.SORT_M
+    for a in range(r["n_tracks"]):
+        assert (np.diff(r["cam_idx"][r["pt_ptr"][a]:r["pt_ptr"][a + 1]]) > 0).all()
+    # empty images first, last, and two in a row
+    kp_ptr = TC.limit_graph("ends")[0]
+    r = TC.limit_reference("ends")
+    assert kp_ptr[0] == kp_ptr[1] and kp_ptr[3] == kp_ptr[4] == kp_ptr[5] and kp_ptr[-2] == kp_ptr[-1] and len(kp_ptr) - 1 == 8
+    assert r["node_track"].tolist() == TC.LIMIT_NODE_TRACK["ends"] and r["cam_idx"].tolist() == TC.LIMIT_CAM_IDX["ends"]
+    # neighbouring segments that meet in one image: the sorted buffer of the candidates, restated
+    kp_ptr, _, edges, _, _ = TC.limit_graph("stairs")
+    r = TC.limit_reference("stairs")
+    n = int(kp_ptr[-1])
+    label = r["label"]
+    buf = np.lexsort((np.arange(n), label))  # every component is a candidate here
+    image = np.searchsorted(kp_ptr, buf, side="right") - 1
+    meet = np.nonzero((image[1:] == image[:-1]) & (label[buf][1:] != label[buf][:-1]))[0] + 1  # p: entries p - 1 | p
+    assert meet.tolist() == list(range(2, 2 * TC.STAIR_K + 1, 2)) and TC.BLOCK in meet  # every boundary, entry 255 | 256 among them
+    assert (buf[meet] > buf[meet - 1]).any() and (buf[meet] < buf[meet - 1]).any()  # either order of the two inside their image
+    assert (r["n_tracks"], r["n_conflicting"], r["n_conflicting_nodes"], r["n_singletons"]) == (TC.STAIR_K, 1, 3, 0)
+    assert (r["node_track"][buf[-3:]] == -3).all() and (np.diff(r["pt_ptr"]) == 2).all()
 
 
 def _call(lib, n_images, kp_ptr, kp_xy, edges, n_edges, ok, min_length, null=()):
