@@ -142,10 +142,10 @@ inline size_t row_tile_lds(size_t el, int cols) { return el * 4 * 64 * (size_t)(
 inline bool tile_fits(size_t el, int cols) { return row_tile_lds(el, cols) <= TILE_MAX_BYTES; }
 // the depth update of m images goes through row tiles (coalesced) while they and the dual method's 24 doubles per image fit
 inline bool depth_tiled(size_t el, int m) { return tile_fits(el, 4 * m) && 24 * m * sizeof(double) <= 24 * 1024; }
-// k_depth_primary<T, true>, k_primary_xz: U [3 m][4] and the tiles; k_depth_primary_wide: U and per wave [64][10 sums | 4 components]
+// k_depth_primary, k_primary_xz: U [3 m][4] and the tiles; k_depth_primary_wide: U and per wave [64][10 sums | 4 components]
 inline size_t depth_primary_lds(size_t el, int m) { return sizeof(double) * 12 * m + row_tile_lds(el, 4 * m) + 16; }
 inline size_t depth_primary_wide_lds(int m) { return sizeof(double) * (12 * (size_t)m + 4 * 64 * 14); }
-// k_dual_apply<T, true>, k_dual_apply_xz: U4 [3 m][4], w [m][12] and the tiles; k_dual_apply_wide: the two tables alone
+// k_dual_apply, k_dual_apply_xz: U4 [3 m][4], w [m][12] and the tiles; k_dual_apply_wide: the two tables alone
 inline size_t dual_apply_lds(size_t el, int m) { return sizeof(double) * 24 * m + row_tile_lds(el, 4 * m) + 16; }
 inline size_t dual_apply_wide_lds(int m) { return sizeof(double) * 24 * m; }
 // k_dual_gram stages [rows][3 m | 1] normalised observations + [rows][4] right singular vectors per pass

@@ -481,7 +481,7 @@ def test_depth_iteration_on_the_device_equals_the_oracle_per_step(method):
 def test_depth_iteration_image_counts_vs_oracle(n_points, m, method):
     """Image counts at the edges of the device depth loop's kernel variants, against oracle/depth_oracle.py per step (1e-9): two and
     three views (the reference's loops only need 3 m >= 4 columns; the device loop refused fewer than four until round 5), 16 images
-    in fp64 (the rows no longer fit the LDS tiles: the per-lane variants of k_depth_primary / k_dual_apply, which no test ran before),
+    in fp64 (the rows no longer fit the LDS tiles: k_depth_primary_wide / k_dual_apply_wide with 16 lanes per point),
     64 images (k_dual_gram stages fewer than 128 rows per pass there -- its launch used to fail from 48 images on -- and walks its
     14 m = 896 tasks in more than one batch per thread), 100 and 128 images (300 / 384 columns: the factorisation inside the step is
     the wide path's block iteration, `test_wide_matrices_vs_lapack`), 30 / 300 / 768 images (the depth updates with the lanes of a wave
@@ -577,24 +577,34 @@ def test_a_failed_regrow_does_not_leave_a_closed_workspace_in_the_cache(monkeypa
     _mvba.svd_cache_clear()
 
 
-def test_depth_iteration_in_float32():
-    """The same iteration on a float32 workspace: depths good to float32."""
+def _depth_iteration_in_float32(n_points, m):
     from lib.perspective_camera_calibration import _create_data_matrix
     from lib.synthetic import make_scene
     from oracle.depth_oracle import HostDepthLoop
 
-    sc = make_scene(2000, 5, vis_p=1.0)
+    sc = make_scene(n_points, m, vis_p=1.0)
     xd, _vis = sc.dense()
-    x = _create_data_matrix([xd[:, k, :] for k in range(5)], 1.0)
+    x = _create_data_matrix([xd[:, k, :] for k in range(m)], 1.0)
     g = HostDepthLoop(x)
-    ws = _mvba.SvdWorkspace(2000, 15, np.float32)
-    ws.load_base(x.reshape(2000, 15).astype(np.float32))
+    ws = _mvba.SvdWorkspace(n_points, 3 * m, np.float32)
+    ws.load_base(x.reshape(n_points, 3 * m).astype(np.float32))
     ws.depth_begin(3)
     for method in (1, 2):
         E, _ = ws.depth_step(method, 1.0)
         assert E == pytest.approx(g.step(method, 1.0), rel=1e-3)
         np.testing.assert_allclose(ws.depth_read(), g.depths(), rtol=0, atol=2e-4)
     ws.close()
+
+
+def test_depth_iteration_in_float32():
+    """The same iteration on a float32 workspace: depths good to float32."""
+    _depth_iteration_in_float32(2000, 5)
+
+
+def test_depth_iteration_in_float32_lanes_across_images():
+    """... at 40 images, past the 29 whose float32 rows fit the LDS tiles: the float forms of k_depth_primary_wide and
+    k_dual_apply_wide (64 lanes per point), which no other test runs.  The same oracle, the same tolerances."""
+    _depth_iteration_in_float32(400, 40)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compare the device code of two builds of csrc/mvba.s (`make asm`), kernel by kernel.
+"""Compare the device code of two builds of csrc/mvba.s or csrc/mvsvd.s (`make asm`), kernel by kernel.
 
     python tools/compare_asm.py OLD.s NEW.s
 
