@@ -106,1778 +106,16 @@ int rccl_load() {
 }
 }  // namespace
 
-// ------------------------------------------------------------------ device helpers
+// ------------------------------------------------------------------ device code, one header per stage
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;  // lane 0 holds the sum; fixed tree -> deterministic
-}
-
-// Deterministic block sum (fixed tree); result valid in thread 0.
-__device__ __forceinline__ double block_sum(double v, double *s_red /*[16]*/) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) s_red[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int i = 0; i < nw; ++i) t += s_red[i];
-  }
-  return t;
-}
-
-__device__ __forceinline__ void load_cams_to_lds(const double *__restrict__ cam15, int m, double f0,
-                                                 double *s_cam) {
-  for (int k = threadIdx.x; k < m; k += blockDim.x) expand_cam(cam15 + (size_t)k * CAM_IN, f0, s_cam + k * CAM_LDS);
-}
-
-// Reduced system storage: the upper block triangle of A packed strip by strip -- strip k is a
-// row-major 9 x 9(m-k) block (cameras l >= k) at offset 81 (k m - k (k-1) / 2) -- followed by b
-// (9m).  81 m (m+1) / 2 + 9m doubles: half of the dense 9m x 9m, and what the all-reduce ships.
-__host__ __device__ __forceinline__ size_t strip_offset(int k, int m) {
-  return 81 * ((size_t)k * m - (size_t)k * (k - 1) / 2);
-}
-
-__device__ __forceinline__ int keep_index(int i, int gauge_axis) {
-  // i-th kept parameter -> global parameter index; removed = {3..8, 12+axis} (ref :62-72)
-  if (i < 3) return i;
-  return (i + 6 < 12 + gauge_axis) ? i + 6 : i + 7;
-}
-
-// Wave-uniform operands are read through the constant address space so that the compiler issues scalar (SMEM)
-// loads into SGPRs instead of 64 identical vector loads.
-#define MVBA_CONST_AS __attribute__((address_space(4)))
-template <typename T>
-__device__ __forceinline__ const T MVBA_CONST_AS *as_const(const T *p) {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-  return (const T MVBA_CONST_AS *)p;
-#pragma clang diagnostic pop
-}
-
-// ------------------------------------------------------------------ K1
-// One thread per observation, grid-stride over 256-observation tiles; camera table
-// staged once per block.  Each wave transposes its 64 records through LDS so that
-// every global store instruction writes 1 KiB contiguous (8 whole lines).
-// K2 is fused in: the per-point blocks E_a = 2 sum Jx^T Jx (6 unique) and dP_a = 2 sum Jx^T e
-// (ref :429-469, :519-556) are formed by a wave-level segmented sum over the (point-sorted)
-// observations -- PL[a][9] = Exx,Exy,Exz,Eyy,Eyz,Ezz,dP0..2 -- so the records are not re-read.
-// Algorithmic traffic: 24 B in + 128 B out per observation + (24 in + 72 out) B per point.
-constexpr int REC = 8;  // double2 slots per observation record (128 B)
-constexpr int LDS_CAMERAS = 646;  // cameras whose tables (K1: 18 doubles + the waves' staging tiles; K5: 28 doubles) fit one workgroup's LDS
-
-// GCAM: beyond LDS_CAMERAS cameras the expanded camera table does not fit a workgroup's LDS next to its staging tiles; the
-// kernels then read the rows of a table in device memory (k_cam_tables; 144 bytes per camera, L2-resident) through the same
-// 16-byte loads.  One template parameter per kernel: the LDS form keeps its ds_read_b128, nothing is decided per access.
-// LOSS: a robust loss scales the observation's Jacobian rows and residual by sqrt(w) before they are stored
-// and summed -- the records, E_a and dP_a are then those of the weighted least-squares problem -- and writes sqrt(w) to `sqw`.
-#define MVBA_RESID_JAC_ARGS                                                                                                 \
-  long long nobs, int m, const double *__restrict__ cam15, const double *__restrict__ X, const int *__restrict__ obs_pt,   \
-      const int *__restrict__ cam_idx, const double2 *__restrict__ xy, double f0, const int *__restrict__ tile_start,     \
-      int n_tiles, double2 *__restrict__ rec, double *__restrict__ PL, const int *__restrict__ tile_slot,                 \
-      double *__restrict__ PLsplit, const double *__restrict__ gcam
-// Robust kernels take one trailing argument of this type (the squared instantiations none: their arguments and code are those of
-// the plain kernels).  b = (delta / f0)^2, sqw = sqrt(w) per observation.
-struct LossArgs {
-  double b;
-  double *sqw;
-};
-template <bool GCAM, int LOSS = LOSS_SQUARED, typename... Robust>
-__global__ __launch_bounds__(1024, 4) void k_resid_jac(MVBA_RESID_JAC_ARGS, Robust... robust) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  double *s_cam = smem;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-  // per-wave 8 KiB staging tile, 16-byte aligned behind the camera table
-  double2 *stage = reinterpret_cast<double2 *>(smem + (GCAM ? 0 : ((m * CAM_LDS + 1) & ~1))) + wave * (64 * REC);
-  // the same 8 KiB is reused for the per-point sums: contrib[9][CS] doubles (odd stride: the nine
-  // components of one observation sit in nine different banks), then seg_start[65], pt[64]
-  constexpr int CS = 65;
-  double *contrib = reinterpret_cast<double *>(stage);
-  int *seg_start = reinterpret_cast<int *>(contrib + 9 * CS), *seg_pt = seg_start + 66;
-  if (!GCAM) {
-    load_cams_to_lds(cam15, m, f0, s_cam);
-    __syncthreads();
-  }
-  // Wave tiles are POINT-ALIGNED (built once on the host): whole points packed greedily into at
-  // most 64 observations, so every per-point sum below is complete inside one wave -> plain
-  // stores, no atomics, bitwise-reproducible E_a / dP_a.  Only a point with more than 64
-  // observations is split over tiles (tile_start < 0 marks such a tile: it holds ONE piece of ONE point, whose sums
-  // go to slot tile_slot[tile] of a side buffer; k_sum_split adds a point's pieces in tile order afterwards).
-  for (int tile = blockIdx.x * nwave + wave; tile < n_tiles; tile += gridDim.x * nwave) {
-    const int ts0 = tile_start[tile], ts1 = tile_start[tile + 1];
-    const bool split = ts0 < 0;
-    const int slot = split ? as_const(tile_slot)[tile] : 0;  // (wave-uniform: a scalar load)
-    const long long wbase = split ? ~ts0 : ts0;  // first observation of this wave's tile
-    const int n = (int)((ts1 < 0 ? ~ts1 : ts1) - wbase);
-    const long long o = wbase + lane;
-    const bool live = lane < n;
-    int a = -1;
-    double c9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (live) {
-      a = obs_pt[o];
-      const int k = cam_idx[o];
-      const double2 z = xy[o];
-      const double *Xa = X + 3 * (size_t)a;
-      ObsJ J;
-      obs_math(Xa[0], Xa[1], Xa[2], GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS, z.x, z.y, f0, J);
-      if constexpr (LOSS != LOSS_SQUARED) {
-        const LossArgs la = (robust, ...);
-        const double sw = loss_sqrt_w<LOSS>(J.e0 * J.e0 + J.e1 * J.e1, la.b);
-        J.e0 *= sw;
-        J.e1 *= sw;
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-#pragma unroll
-          for (int i = 0; i < 3; ++i) J.jx[rr][i] *= sw;
-          J.jc[rr][0] *= sw;
-#pragma unroll
-          for (int i = 6; i < 9; ++i) J.jc[rr][i] *= sw;
-        }
-        la.sqw[o] = sw;
-      }
-      // swizzled slot position (s ^ (lane & 7)): conflict-free ds_write_b128
-      double2 *row = stage + lane * REC;
-      const int sw = lane & 7;
-      row[0 ^ sw] = make_double2(J.jx[0][0], J.jx[1][0]);
-      row[1 ^ sw] = make_double2(J.jx[0][1], J.jx[1][1]);
-      row[2 ^ sw] = make_double2(J.jx[0][2], J.jx[1][2]);
-      row[3 ^ sw] = make_double2(J.jc[0][0], J.jc[1][0]);
-      row[4 ^ sw] = make_double2(J.jc[0][6], J.jc[1][6]);
-      row[5 ^ sw] = make_double2(J.jc[0][7], J.jc[1][7]);
-      row[6 ^ sw] = make_double2(J.jc[0][8], J.jc[1][8]);
-      row[7 ^ sw] = make_double2(J.e0, J.e1);
-      // K2 fused: this observation's share of E_a = 2 sum Jx^T Jx and dP_a = 2 sum Jx^T e
-      c9[0] = 2.0 * (J.jx[0][0] * J.jx[0][0] + J.jx[1][0] * J.jx[1][0]);
-      c9[1] = 2.0 * (J.jx[0][0] * J.jx[0][1] + J.jx[1][0] * J.jx[1][1]);
-      c9[2] = 2.0 * (J.jx[0][0] * J.jx[0][2] + J.jx[1][0] * J.jx[1][2]);
-      c9[3] = 2.0 * (J.jx[0][1] * J.jx[0][1] + J.jx[1][1] * J.jx[1][1]);
-      c9[4] = 2.0 * (J.jx[0][1] * J.jx[0][2] + J.jx[1][1] * J.jx[1][2]);
-      c9[5] = 2.0 * (J.jx[0][2] * J.jx[0][2] + J.jx[1][2] * J.jx[1][2]);
-      c9[6] = 2.0 * (J.jx[0][0] * J.e0 + J.jx[1][0] * J.e1);
-      c9[7] = 2.0 * (J.jx[0][1] * J.e0 + J.jx[1][1] * J.e1);
-      c9[8] = 2.0 * (J.jx[0][2] * J.e0 + J.jx[1][2] * J.e1);
-    }
-    wave_sync();  // wave-synchronous hand-over through LDS (in-order DS queue)
-#pragma unroll
-    for (int q = 0; q < REC; ++q) {
-      const int ol = q * 8 + (lane >> 3), pos = lane & 7;  // local observation, stored position
-      const double2 v = stage[ol * REC + pos];
-      if (ol < n) rec[(wbase + ol) * REC + (pos ^ (ol & 7))] = v;
-    }
-    wave_sync();
-    // ---- per-point sums (wave-level segmented reduction; observations are sorted by point)
-    const int a_prev = __shfl_up(a, 1, 64);
-    const bool head = live && (lane == 0 || a != a_prev);
-    const unsigned long long heads = __ballot(head);
-    const int nseg = __popcll(heads);
-#pragma unroll
-    for (int q = 0; q < 9; ++q) contrib[q * CS + lane] = c9[q];
-    if (head) {
-      const int rank = __popcll(heads & ((1ull << lane) - 1ull));
-      seg_start[rank] = lane;
-      seg_pt[rank] = a;
-    }
-    if (lane == 0) seg_start[nseg] = n;
-    wave_sync();
-    const int sl = lane / 9, comp = lane - 9 * sl;
-    for (int s0 = 0; s0 < nseg; s0 += 7) {
-      const int sg = s0 + sl;
-      if (sl < 7 && sg < nseg) {
-        const int i0 = seg_start[sg], i1 = seg_start[sg + 1];
-        double acc = 0.0;
-        for (int i = i0; i < i1; ++i) acc += contrib[comp * CS + i];
-        // (split: a piece of a > 64-observation point -> its slot of the side buffer; wave-uniform choice)
-        if (split) PLsplit[9 * (size_t)slot + comp] = acc;
-        else PL[9 * (size_t)seg_pt[sg] + comp] = acc;
-      }
-    }
-    wave_sync();
-  }
-}
-
-// The per-point blocks of points with more than 64 observations: their pieces in tile order (fixed order: no atomics).
-__global__ void k_sum_split(int n_split, const int4 *__restrict__ splits /* point, first slot, pieces */,
-                            const double *__restrict__ PLsplit, double *__restrict__ PL) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x, sp = t / 9, comp = t - 9 * sp;
-  if (sp >= n_split) return;
-  const int4 d = splits[sp];
-  double v = 0.0;
-  for (int q = 0; q < d.z; ++q) v += PLsplit[9 * (size_t)(d.y + q) + comp];
-  PL[9 * (size_t)d.x + comp] = v;
-}
-
-// ------------------------------------------------------------------ K3a
-// PB[a][PBS] = inverse of E_a with diagonal*(1+c) (6 unique), v_a = E^-1 dP_a (3), pad: one
-// 128-byte line per point, so a gather of the inverse touches one 64-byte sector.
-constexpr int PBS = 16;
-constexpr int PACE_STRIDE = 32;  // ints between two pacing counters: one 128-byte line each (they are hammered by ~300 waves)
-// Also clears the packed [A|b] the Schur kernel is about to accumulate into (one launch less on
-// the path; the grid is sized for whichever of the two jobs is larger).
-// Held points (mvba_set_point_hold): the instantiation with one trailing `const uint8_t *held` [npts] writes the
-// row of a point removed from the unknowns -- E^-1 = 0, v = 0, R = 0, the tenth double 1 (a point, sign code 0) -- and does not
-// test that point's determinant.  Without a mask the engine launches k_point_inv<>, whose arguments and body are the kernel's
-// as it was before there were masks.
-template <typename... Held>
-__global__ __launch_bounds__(256) void k_point_inv(long long npts, double c, const double *__restrict__ PL,
-                                                   double *__restrict__ PB, int *__restrict__ flag,
-                                                   double *__restrict__ Ab, long long nAb, int *__restrict__ prog, long long nprog, int want_r,
-                                                   Held... held) {
-  static_assert(sizeof...(Held) <= 1, "at most the held mask");
-  // a block's 256 points are 18 KiB of PL and 32 KiB of PB, both contiguous: moved with coalesced
-  // accesses through LDS (a thread reading its own 72-byte row / writing its own 128-byte line touches
-  // 64 different lines per instruction)
-  // (one buffer for both directions -- a thread takes its nine inputs into registers before anybody writes a result: 32 KiB per
-  // block = four blocks per CU instead of three at 50 KiB)
-  __shared__ double2 s_out[256 * 8];
-  double *s_in = reinterpret_cast<double *>(s_out);
-  const long long a0 = (long long)blockIdx.x * 256, a = a0 + threadIdx.x;
-  for (long long i = a; i < nAb; i += (long long)gridDim.x * blockDim.x) Ab[i] = 0.0;
-  for (long long i = a; i < nprog; i += (long long)gridDim.x * blockDim.x) prog[i] = 0;  // pacing counters of k_schur_slots
-  if (a0 >= npts) return;  // (uniform)
-  const int np = (int)min<long long>(256, npts - a0);
-  {  // nine independent loads per thread, then their stores (one load and one store per trip waits for every load in turn)
-    double t[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) t[i] = PL[9 * a0 + min((int)threadIdx.x + 256 * i, 9 * np - 1)];
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-      if ((int)threadIdx.x + 256 * i < 9 * np) s_in[threadIdx.x + 256 * i] = t[i];
-  }
-  __syncthreads();
-  double in[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) in[i] = s_in[9 * min((int)threadIdx.x, np - 1) + i];
-  __syncthreads();
-  bool free_pt = threadIdx.x < np;
-  if constexpr (sizeof...(Held) == 1) {
-    if (free_pt && (held, ...)[a] != 0) {  // (a < npts here)
-      free_pt = false;
-      double2 *out = s_out + 8 * threadIdx.x;
-      const int sw = threadIdx.x & 7;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) out[q ^ sw] = make_double2(0.0, q == 4 ? 1.0 : 0.0);
-    }
-  }
-  if (free_pt) {
-    const double s = 1.0 + c;
-    const double xx = in[0] * s, xy = in[1], xz = in[2], yy = in[3] * s, yz = in[4], zz = in[5] * s;
-    const double c00 = yy * zz - yz * yz, c01 = xz * yz - xy * zz, c02 = xy * yz - xz * yy;
-    const double det = xx * c00 + xy * c01 + xz * c02;
-    if (!(det != 0.0) || !isfinite(det)) atomicOr(flag, FLAG_POINT_SINGULAR);  // singular 3x3 (ref :128 raises LinAlgError)
-    const double id = 1.0 / det;
-    const double i00 = c00 * id, i01 = c01 * id, i02 = c02 * id;
-    const double i11 = (xx * zz - xz * xz) * id, i12 = (xy * xz - xx * yz) * id, i22 = (xx * yy - xy * xy) * id;
-    const double g0 = in[6], g1 = in[7], g2 = in[8];
-    // slot s of point p sits at s_out[8 p + (s ^ (p & 7))]: conflict-free 16-byte LDS stores, undone on the way out
-    double2 *out = s_out + 8 * threadIdx.x;
-    const int sw = threadIdx.x & 7;
-    out[0 ^ sw] = make_double2(i00, i01);
-    out[1 ^ sw] = make_double2(i02, i11);
-    out[2 ^ sw] = make_double2(i12, i22);
-    out[3 ^ sw] = make_double2(i00 * g0 + i01 * g1 + i02 * g2, i01 * g0 + i11 * g1 + i12 * g2);
-    out[4 ^ sw] = make_double2(i02 * g0 + i12 * g1 + i22 * g2, 1.0);  // tenth double: 1 = a point (row N, the padding row, stays 0)
-    if (want_r) {
-      // the dense-visibility Schur form reads E^-1 = R S R^T from the row's last three slots: R lower triangular, S = diag(+-1) --
-      // L D L^T with |D|^1/2 folded into the columns; S = I for the positive definite inverse of every LM step, but the damped
-      // blocks of a NEGATIVE damping factor (the LU-path test; np.linalg.solve takes any system) are indefinite.  The signs ride in
-      // the tenth double: 1 + (d0 < 0) + 2 (d1 < 0) + 4 (d2 < 0)  (nobody else reads it in this mode)
-      const double d0 = i00, q0 = d0 != 0.0 ? 1.0 / d0 : 0.0, l10 = i01 * q0, l20 = i02 * q0;
-      const double d1 = i11 - l10 * i01, q1 = d1 != 0.0 ? 1.0 / d1 : 0.0, l21 = (i12 - l20 * i01) * q1;
-      const double d2 = i22 - l20 * i02 - l21 * l21 * d1;
-      const double a0 = sqrt(fabs(d0)), a1 = sqrt(fabs(d1)), a2 = sqrt(fabs(d2));
-      out[4 ^ sw].y = 1.0 + (d0 < 0.0 ? 1.0 : 0.0) + (d1 < 0.0 ? 2.0 : 0.0) + (d2 < 0.0 ? 4.0 : 0.0);
-      out[5 ^ sw] = make_double2(a0, l10 * a0);
-      out[6 ^ sw] = make_double2(l20 * a0, a1);
-      out[7 ^ sw] = make_double2(l21 * a1, a2);
-    } else {
-      out[5 ^ sw] = out[6 ^ sw] = out[7 ^ sw] = make_double2(0.0, 0.0);
-    }
-  }
-  __syncthreads();
-  double2 *dst = reinterpret_cast<double2 *>(PB + PBS * a0);
-  for (int e = threadIdx.x; e < 8 * np; e += 256) {
-    const int p = e >> 3, sl = e & 7;
-    dst[e] = s_out[8 * p + (sl ^ (p & 7))];
-  }
-}
-
-// ------------------------------------------------------------------ K3
-// Per (point a, camera k, camera l >= k) item, the 9x9 block (upper block triangle only):
-//   -(F_ak^T E^-1 F_al)[i][j] = -Jc_k[:,i] . ( 2 Jx_k E^-1 ( 2 Jx_l^T Jc_l[:,j] ) )
-// The diagonal item (l == k) also adds G^_k (ref :618-664 with :123-125 damping)
-// and the right-hand side 2 Jc_k^T (Jx_k v_a - e_ak)   (ref :138-143, :471-517).
-
-// ------------------------------------------------------------------ K3 (pair-major form)
-// The sum above, organised by OUTPUT block instead of by camera strip (round 1).  Every (point, camera k,
-// camera l >= k) triple is an "item" (built once on the host, sorted by (k, l), then by point), a
-// "unit" is a contiguous run of one pair's items, and ONE WAVE owns a unit: it keeps its share of the
-// 9x9 block in registers for the whole run, so there is no scatter and no atomic at all -- round 1's
-// camera-strip kernel spent 75 % of its cycles in the LDS atomic pipe.  Per item the block is the
-// rank-2 product  -4 Jc_k^T t Jc_l  with  t = Jx_k E^-1 Jx_l^T (2x2).
-//   lanes      lane = 3 item + cg: 21 items per step, column group cg owns columns 3cg..3cg+2 of
-//              the block (f,u,v | t | omega) = 27 accumulators; t is formed redundantly by the 3 lanes
-//   operands   whole 128-byte lines gathered by LDS-DMA (global_load_lds_dwordx4, 8 lanes -> 7 of the
-//              8 slots of a record): the k-side record, the l-side record and the point block of the
-//              21 items land in wave-private LDS as 112-byte rows (28-dword stride: the 16 lanes of a
-//              ds_read_b128 group hit 16 different bank quads).  Per-lane loads out of 64 different
-//              lines are bound by the L1 tag rate (1 line per clock: tools/microbench/gather_lines.hip,
-//              297 vs 720 lines/us/CU from L2).
-//   diagonal   a (k,k) pair adds G_k (t - I/2 instead of t), the Marquardt term c * diag(G_k) and
-//              the right-hand side 2 Jc_k^T (Jx_k E^-1 dP - e); its l-side DMA fetches slots 1..7 of
-//              the SAME record (the residual is slot 7) and the point row is 5 slots (E^-1 dP behind
-//              the inverse).  Diagonal pairs hold ~10x the items of an off-diagonal pair and are dealt
-//              round-robin into sub-lists, so that all units of a strip sweep the points at one pace.
-//   placement  the units of strip k run on XCD k % 8 (work queues per XCD, the wave reads its
-//              XCC_ID and pulls from that queue first, then steals): the ~5.5 units that need the
-//              k-side record of one observation run at the same time on the same L2.
-//   output     partial[unit][104] (81 block, 9 damping, 9 rhs), summed per pair in unit order by
-//              k_schur_reduce into the packed strips: bitwise reproducible, no zero-fill of A.
-//
-// The gather forms of K3 (DESIGN.md §3.1 has the map): the unit form above (schur_unit_run: k_schur_pairs*), the slot form
-// with three lanes per item (schur_slots_run: k_schur_slots) and with one lane per item (schur_lanes_run in mvba_lanes.h:
-// k_schur_lanes).  What they share comes first and is written once.
-constexpr int PSTEP = 21;                       // items per wave step of the 3-lanes-per-item forms
-constexpr int PROW = 7 * 16;                    // staged bytes per record (slots 0..6, or 1..7)
-constexpr int UNIT_STRIDE = 104;                // doubles per unit partial
-constexpr int SLOT_IDX = 64;                    // slot form: ints per step in the index (k[21] | l[21] | a[21] | pad): ONE 256-byte DMA row
-constexpr int SLOT_IDX_RING = 3;                // ... staged three steps deep in LDS
-
-// ---- the staging buffer of one step of W item rows: the ONE statement of its layout (every form takes its offsets from
-// here, every launch its LDS bytes)
-//   k rows [W][112 B] | l rows [W][112 B] | point rows [W][16 NPS B]      NPS = 3 slots (E^-1), DIAG: 5 (E^-1, E^-1 dP, weight)
-// A diagonal step needs of its l side (the SAME record) only the residual, slot 7: [W][16 B] at the head of the l region.
-// PACKED (the slot forms: three buffers in a tight LDS budget) sizes the l region and the point rows for the step at hand;
-// unpacked (the unit form: a wave meets both kinds of unit) keeps the full l region and five point slots whatever the step,
-// and its robust build gathers the step's sqrt(w) values (8 bytes per item: k side, then l side) at SQW, into what the
-// squared build leaves unused: behind the residuals (DIAG), behind the 3-slot point rows (off-diagonal).
-template <int W, bool DIAG, bool PACKED>
-struct SchurStage {
-  static constexpr int NPS = DIAG ? 5 : 3;
-  static constexpr int L = W * PROW;
-  static constexpr int P = L + ((PACKED && DIAG) ? W * 16 : W * PROW);
-  static constexpr int SIZE = P + W * 16 * (PACKED ? NPS : 5);
-  static constexpr int SQW = DIAG ? L + W * 16 : P + W * 16 * NPS;
-  static constexpr int SQW_END = SQW + (DIAG ? 1 : 2) * W * 8;
-};
-constexpr int PWAVE_LDS = SchurStage<PSTEP, false, false>::SIZE;  // the unit form's buffer
-constexpr int SLOT_BUF = SchurStage<PSTEP, false, true>::SIZE;    // the slot form's (the off-diagonal step is the larger one)
-constexpr int PAIRS_LDS = 2 * PWAVE_LDS;                          // the unit form: two staging buffers per wave
-constexpr int SLOT_LDS = 3 * SLOT_BUF + SLOT_IDX_RING * SLOT_IDX * 4;  // three staging buffers + the index ring per wave: nine waves per CU
-static_assert(PWAVE_LDS == 6384 && SLOT_BUF == 5712 && SLOT_LDS == 17904, "the launches' LDS bytes");
-static_assert(SchurStage<PSTEP, true, false>::SIZE == PWAVE_LDS && SchurStage<PSTEP, true, true>::SIZE <= SLOT_BUF, "a diagonal step fits the buffer");
-static_assert(SchurStage<PSTEP, true, false>::SQW_END <= SchurStage<PSTEP, true, false>::P && SchurStage<PSTEP, false, false>::SQW_END <= PWAVE_LDS,
-              "robust weights fit the staging buffer");
-// (LDS is handed out in 512-byte granules: 9 x 17,920 = 161,280 of the 163,840 bytes.  16 bytes are all a wave could still have --
-// with 48 more, a CU holds eight waves, the range's 284 are no longer all resident and the launch spends 6 ms in pacing time-outs:
-// profiles/r05_pace_poll.txt)
-static_assert(9 * ((SLOT_LDS + 511) / 512 * 512) <= 160 * 1024, "nine waves per CU");
-
-// ---- LDS-DMA.  lds_dma16: the compiler's builtin, for the unit form, whose waits the compiler counts.
-__device__ __forceinline__ void lds_dma16(const void *gsrc, void *lds_wave_uniform) {
-  __builtin_amdgcn_global_load_lds(gsrc, (__attribute__((address_space(3))) void *)lds_wave_uniform, 16, 0, 0);
-}
-// The slot forms keep the gathers of two steps in flight over COUNTED waits, which hipcc cannot be left to place: it drains
-// the queue -- vmcnt(0) -- before any LDS read that might alias a DMA in flight.  So every vector-memory operation of their
-// loops is one of the two asm statements below, which the compiler knows nothing about, and the `s_waitcnt vmcnt(N)` of the
-// loops are the only waits (csrc/check_isa.py checks that on the generated code).  vmcnt retires in issue order: N = the
-// operations of the last iteration, all of them unconditional (a masked-off lane still counts; a skipped instruction
-// would not), none returning data to a register.
-// M0 (the LDS destination base) is written in the SAME statement that uses it: it is compiler-reserved, an "m0" clobber only
-// draws a warning, and the compiler's own M0 users -- none in k_schur_slots: check_isa.py fails the build if one appears --
-// set it themselves.
-// lds_gather16: 16 bytes per lane, base[row * 128 + slot16] -> LDS at `lds` (wave-uniform; the lanes land 16 bytes apart).
-// The byte offset is formed BETWEEN the write of M0 and the gather that reads it: that is the one wait state the hardware
-// asks for there.
-__device__ __forceinline__ void lds_gather16(int row, unsigned slot16, const void *base, unsigned lds) {
-  unsigned o;
-  asm volatile("s_mov_b32 m0, %4\n\tv_lshl_add_u32 %0, %1, 7, %2\n\tglobal_load_lds_dwordx4 %0, %3" : "=&v"(o) : "v"(row), "v"(slot16), "s"(base), "s"(lds) : "memory");
-}
-// lds_index_row: a step's index row (at the wave-uniform `src`) -> LDS at `dst`, 16 bytes per lane at `lane16`; the caller
-// masks off the lanes past the row (and clamps their lane16)
-__device__ __forceinline__ void lds_index_row(unsigned lane16, const int *src, unsigned dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane16), "s"(src), "s"(dst) : "memory");
-}
-// the LDS reads of a step are complete (their values were consumed) before its buffer is refilled
-__device__ __forceinline__ void lds_reads_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// ---- J_C row (and column) i = jc_sign(i) * (record columns): f | u, v (1/f0 = cu) | t (-J_X) | omega.  The accumulators hold
-// the products of the record columns; every epilogue applies the factors once, at the end.
-__device__ __forceinline__ constexpr double jc_sign(int i, double cu) { return (i == 1 || i == 2) ? cu : ((i >= 3 && i < 6) ? -1.0 : 1.0); }
-
-// ---- the arithmetic of one item: t = J_Xk E^-1 J_Xl^T (2x2) -- h = E^-1 J_Xl^T (3x2), t = J_Xk h -- and for a diagonal item
-// t - I/2 (the block is then G_k) and w = J_Xk E^-1 dP - e (the right-hand side).  `pb` = the item's point row, the residual is slot
-// `row` of the buffer's l region (DIAG only).  PADDED (slot forms): the point row's tenth double is 1 for a point and 0 for the padding row,
-// which stands next to a real record (its range's first): the I/2 and w terms must vanish with it, like the diag(G_k) term
-// in the callers.
-template <bool DIAG, bool PADDED>
-__device__ __forceinline__ void schur_item(const double2 kx0, const double2 kx1, const double2 kx2, const double2 lx0, const double2 lx1,
-                                           const double2 lx2, const double *pb, const char *buf, const int l_off, const int row, double &t00, double &t01,
-                                           double &t10, double &t11, double &w0, double &w1, double &wgt) {
-  const double i00 = pb[0], i01 = pb[1], i02 = pb[2], i11 = pb[3], i12 = pb[4], i22 = pb[5];
-  const double h0x = i00 * lx0.x + i01 * lx1.x + i02 * lx2.x, h0y = i00 * lx0.y + i01 * lx1.y + i02 * lx2.y;
-  const double h1x = i01 * lx0.x + i11 * lx1.x + i12 * lx2.x, h1y = i01 * lx0.y + i11 * lx1.y + i12 * lx2.y;
-  const double h2x = i02 * lx0.x + i12 * lx1.x + i22 * lx2.x, h2y = i02 * lx0.y + i12 * lx1.y + i22 * lx2.y;
-  t00 = kx0.x * h0x + kx1.x * h1x + kx2.x * h2x, t01 = kx0.x * h0y + kx1.x * h1y + kx2.x * h2y;
-  t10 = kx0.y * h0x + kx1.y * h1x + kx2.y * h2x, t11 = kx0.y * h0y + kx1.y * h1y + kx2.y * h2y;
-  w0 = 0.0, w1 = 0.0;
-  wgt = (DIAG && PADDED) ? pb[9] : 1.0;
-  if (DIAG) {
-    t00 -= PADDED ? 0.5 * wgt : 0.5;
-    t11 -= PADDED ? 0.5 * wgt : 0.5;
-    const double2 e = reinterpret_cast<const double2 *>(buf + l_off)[row];
-    w0 = kx0.x * pb[6] + kx1.x * pb[7] + kx2.x * pb[8] - e.x;
-    w1 = kx0.y * pb[6] + kx1.y * pb[7] + kx2.y * pb[8] - e.y;
-    if (PADDED) {
-      w0 *= wgt;
-      w1 *= wgt;
-    }
-  }
-}
-
-// ---- the 3-lane column-group step of the 21-wide forms: lane = 3 item + cg (`it`, item row of the step), column group cg owns
-// columns 3 cg .. 3 cg + 2 of the item's block (f, u, v | t | omega): 27 accumulators of the block (acc), 3 + 3 of the
-// diagonal's damping (dg) and right-hand side (rb).  Column q of this lane = al12 * (l-row slot sel_q) + unit vector (bx1);
-// sign and 1/f0 are applied at the end.
-// One step on a landed buffer laid out as S; `ns` = its item rows.  ROBUST (unit form): the records are
-// scaled by sqrt(w) already (K1), the implied (u, v) columns are not -- each item takes sqrt(w) of its k-side and l-side
-// observations into its u, v rows (k side) and its u, v columns (l side)
-template <class S, bool DIAG, bool PADDED, bool ROBUST>
-__device__ __forceinline__ void schur_colgroup_step(const int it, const int sel0, const int sel1, const int sel2, const double al12,
-                                                    const double bx1, const char *buf, const int ns,
-                                                    double (&acc)[9][3], double (&dg)[3], double (&rb)[3]) {
-  const char *kbuf = buf, *lbuf = buf + S::L, *pbuf = buf + S::P;
-  if (it < ns) {
-    double swk = 1.0, swl = 1.0;
-    if (ROBUST) {
-      const double *wl = reinterpret_cast<const double *>(buf + S::SQW);
-      swk = wl[it];
-      swl = DIAG ? swk : wl[PSTEP + it];
-    }
-    const double2 *kr = reinterpret_cast<const double2 *>(kbuf + it * PROW);
-    const double2 *lr = DIAG ? kr : reinterpret_cast<const double2 *>(lbuf + it * PROW);
-    const double *pb = reinterpret_cast<const double *>(pbuf + it * (16 * S::NPS));
-    const double2 kx0 = kr[0], kx1 = kr[1], kx2 = kr[2], kf = kr[3], kw0 = kr[4], kw1 = kr[5], kw2 = kr[6];
-    const double2 lx0 = lr[0], lx1 = lr[1], lx2 = lr[2];
-    double t00, t01, t10, t11, w0, w1, wgt;
-    schur_item<DIAG, PADDED>(kx0, kx1, kx2, lx0, lx1, lx2, pb, buf, S::L, it, t00, t01, t10, t11, w0, w1, wgt);
-    const double2 s0v = lr[sel0], s1v = lr[sel1], s2v = lr[sel2];
-    const double bxw = ROBUST ? bx1 * swl : bx1;  // (u, v) columns: sqrt(w) of the l-side observation
-    const double sx[3] = {s0v.x, al12 * s1v.x + bxw, al12 * s2v.x};
-    const double sy[3] = {s0v.y, al12 * s1v.y, al12 * s2v.y + bxw};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const double v0 = t00 * sx[q] + t01 * sy[q], v1 = t10 * sx[q] + t11 * sy[q];
-      // two chained FMAs into the accumulator per row (written out: `acc += a*b + c*d` compiles to
-      // mul + fma + add, a third more fp64 instructions in a kernel whose VALU is 70 % busy)
-      acc[0][q] = fma(kf.y, v1, fma(kf.x, v0, acc[0][q]));
-      if (ROBUST) {  // (u, v) rows: sqrt(w) of the k-side observation
-        acc[1][q] = fma(swk, v0, acc[1][q]);
-        acc[2][q] = fma(swk, v1, acc[2][q]);
-      } else {
-        acc[1][q] += v0;
-        acc[2][q] += v1;
-      }
-      acc[3][q] = fma(kx0.y, v1, fma(kx0.x, v0, acc[3][q]));
-      acc[4][q] = fma(kx1.y, v1, fma(kx1.x, v0, acc[4][q]));
-      acc[5][q] = fma(kx2.y, v1, fma(kx2.x, v0, acc[5][q]));
-      acc[6][q] = fma(kw0.y, v1, fma(kw0.x, v0, acc[6][q]));
-      acc[7][q] = fma(kw1.y, v1, fma(kw1.x, v0, acc[7][q]));
-      acc[8][q] = fma(kw2.y, v1, fma(kw2.x, v0, acc[8][q]));
-      if (DIAG) {
-        if (PADDED) dg[q] = fma(wgt, sx[q] * sx[q] + sy[q] * sy[q], dg[q]);
-        else dg[q] += sx[q] * sx[q] + sy[q] * sy[q];
-        rb[q] += sx[q] * w0 + sy[q] * w1;
-      }
-    }
-  }
-  lds_reads_done();
-}
-
-// ------------------------------------------------------------------ K3, unit form: one unit (n items from `beg`) on one wave
-// DIAG: the unit belongs to a (k,k) pair.  prologue: indices to registers, first gathers | loop: wait, issue the next step,
-// compute this one | epilogue: the fixed-order tree over the 21 item lanes, lanes 0..2 write the partial.
-// Two LDS buffers per wave: the DMA of step n+1 is issued before step n is computed, with indices
-// that were loaded one step earlier still (vmcnt counts in issue order, so one wait per step covers
-// both).  12 waves x 6 KB in flight per CU is what a random-line gather needs to run at the HBM
-// rate (Little: 6.4 TB/s x ~2.5 us / 256 CUs).
-// ROBUST: sqrt(w) per observation in `sqw`; the 21 + 21 values of a step are gathered with the step's rows (LDS-DMA, 4 bytes
-// per lane, two lanes per value) to SchurStage::SQW.
-template <bool DIAG, bool BIG, bool ROBUST>
-__device__ __forceinline__ void schur_unit_run(char *wbuf, const int lane, const long long beg, const int n,
-                                               const int *__restrict__ it_k, const int *__restrict__ it_l,
-                                               const int *__restrict__ it_a, const double2 *__restrict__ rec,
-                                               const double *__restrict__ PB, const double c, const double cu,
-                                               double *__restrict__ out, const double *__restrict__ sqw) {
-  using S = SchurStage<PSTEP, DIAG, false>;
-  constexpr int NPS = S::NPS;
-  const int it = lane / 3, cg = lane - 3 * it;           // compute: item of the step, column group
-  const int drow = lane / 7, dslot = lane - 7 * drow;    // record DMA: 9 rows x 7 slots per instruction
-  const int prow = lane / NPS, pslot = lane - NPS * prow;
-  const int prow2 = (64 + lane) / 5, pslot2 = (64 + lane) - 5 * prow2;  // DIAG: second point-row DMA
-  const int sel0 = cg == 0 ? 3 : (cg == 1 ? 0 : 4);
-  const int sel1 = cg == 0 ? 0 : sel0 + 1, sel2 = cg == 0 ? 0 : sel0 + 2;
-  const double al12 = cg == 0 ? 0.0 : 1.0, bx1 = cg == 0 ? 1.0 : 0.0;
-  double acc[9][3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) acc[i][q] = 0.0;
-  double dg[3] = {0.0, 0.0, 0.0}, rb[3] = {0.0, 0.0, 0.0};
-
-  // Loads and DMAs are unconditional (rows past the end of the unit are clamped to its last item and land in LDS rows
-  // nobody reads): a load under a data-dependent branch makes hipcc wait vmcnt(0) per load, and so does a spilled register
-  // reloaded between two DMAs -- either drains the DMAs in flight.
-  int ixk[1][3], ixl[1][3], ixa[1][2];  // the next step's indices
-  int ixw[2] = {0, 0};                  // ROBUST: the k-side and l-side observation of item lane / 2 of the next step
-  auto load_idx = [&](int s0, int (&xk)[3], int (&xl)[3], int (&xa)[2]) {  // indices of the step starting at item s0 (to registers)
-    // uniform base + unsigned 32-bit row: the saddr form again (written with int rows the clamps and the
-    // address sums were done in 64 bits per lane: ~40 vector instructions per step for seven loads)
-    // (the bases go through readfirstlane and the rows through an empty asm so that the compiler can neither
-    // split the uniform sum into per-lane 64-bit additions nor widen the clamp to 64 bits)
-    const unsigned last = (unsigned)(min(PSTEP, n - s0) - 1);
-    typedef const int __attribute__((address_space(1))) *gint_p;  // (a plain pointer rebuilt from integers would be a FLAT one)
-    auto uni = [](const int *p) {
-      const unsigned long long v = (unsigned long long)p;
-      const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-      return (gint_p)(((unsigned long long)hi << 32) | lo);
-    };
-    typedef const char __attribute__((address_space(1))) *gchar_p;
-    auto row_of = [&](int r) {  // BYTE offset of the clamped row
-      unsigned off = min((unsigned)r, last) << 2;
-      asm("" : "+v"(off));
-      return off;
-    };
-    auto at = [](gint_p base, unsigned off) { return *(gint_p)((gchar_p)base + off); };
-    const gint_p pk = uni(it_k + (beg + s0)), pl = DIAG ? pk : uni(it_l + (beg + s0)), pa = uni(it_a + (beg + s0));
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const unsigned row = row_of(9 * q + drow);
-      xk[q] = at(pk, row);
-      if (!DIAG) xl[q] = at(pl, row);
-    }
-    if (DIAG) xl[0] = at(pk, row_of(lane));  // the record whose residual slot this lane fetches
-    xa[0] = at(pa, row_of(prow));
-    if (DIAG) xa[1] = at(pa, row_of(prow2));
-    if (ROBUST) {
-      ixw[0] = at(pk, row_of(lane >> 1));
-      if (!DIAG) ixw[1] = at(pl, row_of(lane >> 1));
-    }
-  };
-  // Addresses as "uniform base + 32-bit byte offset" (the saddr form of the memory instructions: one
-  // shift-add per address instead of a sign extension, a 64-bit shift and a 64-bit add); BIG: the
-  // records or the point blocks span 4 GiB or more and the offsets need 64 bits.
-  auto rec_at = [&](int obs, int slot) -> const void * {
-    if (BIG) return rec + (size_t)obs * REC + slot;
-    return reinterpret_cast<const char *>(rec) + (((unsigned)obs << 7) + ((unsigned)slot << 4));
-  };
-  auto pb_at = [&](int a, int slot) -> const void * {
-    if (BIG) return PB + (size_t)a * PBS + 2 * slot;
-    return reinterpret_cast<const char *>(PB) + (((unsigned)a << 7) + ((unsigned)slot << 4));
-  };
-  auto issue = [&](char *buf, const int (&xk_)[3], const int (&xl_)[3], const int (&xa_)[2]) {
-    char *kb = buf, *lb = buf + S::L, *pb_ = buf + S::P;
-    const int (&xk)[3] = xk_, (&xl)[3] = xl_, (&xa)[2] = xa_;
-    if (lane < 63) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        lds_dma16(rec_at(xk[q], dslot), kb + q * (9 * PROW));
-        if (!DIAG) lds_dma16(rec_at(xl[q], dslot), lb + q * (9 * PROW));
-      }
-      if (!DIAG) lds_dma16(pb_at(xa[0], pslot), pb_);
-    }
-    if (lane < 7 * (PSTEP - 18)) {  // third chunk: rows 18..20 only (a buffer holds 21 rows)
-      lds_dma16(rec_at(xk[2], dslot), kb + 2 * (9 * PROW));
-      if (!DIAG) lds_dma16(rec_at(xl[2], dslot), lb + 2 * (9 * PROW));
-    }
-    if (DIAG) {  // l-side == k-side: only the residual (slot 7) is fetched, 16 bytes per item
-      if (lane < PSTEP) lds_dma16(rec_at(xl[0], 7), lb);
-      lds_dma16(pb_at(xa[0], pslot), pb_);
-      if (lane < 5 * PSTEP - 64) lds_dma16(pb_at(xa[1], pslot2), pb_ + 1024);
-    }
-    if (ROBUST && lane < 2 * PSTEP) {  // sqrt(w) of the step's k-side (and l-side) observations, one dword per lane
-      const char *wsrc = reinterpret_cast<const char *>(sqw) + (lane & 1) * 4;
-      __builtin_amdgcn_global_load_lds(wsrc + (size_t)ixw[0] * 8, (__attribute__((address_space(3))) void *)(buf + S::SQW), 4, 0, 0);
-      if (!DIAG)
-        __builtin_amdgcn_global_load_lds(wsrc + (size_t)ixw[1] * 8, (__attribute__((address_space(3))) void *)(buf + S::SQW + PSTEP * 8), 4, 0, 0);
-    }
-  };
-  auto compute = [&](const char *buf, const int ns) { schur_colgroup_step<S, DIAG, false, ROBUST>(it, sel0, sel1, sel2, al12, bx1, buf, ns, acc, dg, rb); };
-  load_idx(0, ixk[0], ixl[0], ixa[0]);
-  issue(wbuf, ixk[0], ixl[0], ixa[0]);
-  if (PSTEP < n) load_idx(PSTEP, ixk[0], ixl[0], ixa[0]);
-  for (int s0 = 0, par = 0; s0 < n; s0 += PSTEP, par ^= 1) {
-    const int ns = min(PSTEP, n - s0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this step's rows have landed, the next step's indices too
-    if (s0 + PSTEP < n) {
-      issue(wbuf + (par ^ 1) * S::SIZE, ixk[0], ixl[0], ixa[0]);
-      if (s0 + 2 * PSTEP < n) load_idx(s0 + 2 * PSTEP, ixk[0], ixl[0], ixa[0]);
-    }
-    compute(wbuf + par * S::SIZE, ns);
-  }
-  // J_C row i = rs_i * (record columns): f | u,v (1/f0) | t (-Jx) | omega; the same factors per column
-  const double cs0 = cg == 1 ? -1.0 : 1.0, cs12 = cg == 0 ? cu : cs0;
-  // ---- sum over the 21 item lanes of each column group (fixed tree), lanes 0..2 write the partial
-  auto tree = [&](double v) {
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {
-      const double o = __shfl_down(v, 3 * off, 64);
-      if (it < off && it + off < PSTEP) v += o;
-    }
-    return v;
-  };
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const double rs = jc_sign(i, cu);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const double v = tree(acc[i][q]);
-      if (lane < 3) out[9 * i + 3 * cg + q] = -4.0 * rs * (q == 0 ? cs0 : cs12) * v;
-    }
-  }
-  if (DIAG) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const double d = tree(dg[q]), r = tree(rb[q]);
-      const double cs = q == 0 ? cs0 : cs12;
-      if (lane < 3) {
-        out[81 + 3 * cg + q] = 2.0 * c * cs * cs * d;  // c * diag(G_k)   (ref :123-125)
-        out[90 + 3 * cg + q] = 2.0 * cs * r;           // 2 Jc_k^T (Jx_k E^-1 dP - e)
-      }
-    }
-  }
-}
-
-// One wave per block: a wave works alone, and in a wider block its LDS and wave slots stay taken until
-// the block's slowest wave has finished (4 waves per block: 1.945 ms, 2: 1.92, 1: 1.89 at config 3).
-template <bool BIG, bool ROBUST>
-__device__ __forceinline__ void schur_pairs_wave(const int4 *__restrict__ units, const int *__restrict__ q_ptr,
-                                                       const int *__restrict__ q_units, const int *__restrict__ it_k,
-                                                       const int *__restrict__ it_l, const int *__restrict__ it_a,
-                                                       const double2 *__restrict__ rec,
-                                                       const double *__restrict__ PB, double c, double f0,
-                                                       double *__restrict__ partial, const double *__restrict__ sqw) {
-  extern __shared__ char smem_pairs[];
-  const int lane = threadIdx.x;
-  char *wbuf = smem_pairs;
-  // ---- take one unit: block b takes entry b / 8 of queue b % 8 -- no atomic on the critical path; it relies on the
-  // round-robin block -> XCD placement for locality only, never for correctness (1.90 -> 1.87 ms against queues
-  // taken by atomics)
-  int pos = -1;
-  const int x = blockIdx.x & 7, q = blockIdx.x >> 3;
-  if (q < q_ptr[x + 1] - q_ptr[x]) pos = q_ptr[x] + q;
-  pos = __builtin_amdgcn_readfirstlane(pos);
-  if (pos < 0) return;
-  // unit id (where its partial goes) and descriptor, both in queue order: two independent SCALAR loads
-  // (pos is wave-uniform; read through the constant address space so that beg and n live in SGPRs and
-  // the per-step index bases are scalar arithmetic)
-  const int u = as_const(q_units)[pos];
-  const int MVBA_CONST_AS *udp = as_const(reinterpret_cast<const int *>(units)) + 4 * (size_t)pos;
-  const int ud_x = udp[0], ud_y = udp[1], ud_z = udp[2], ud_w = udp[3];
-  const long long beg = ((long long)ud_y << 32) | (unsigned)ud_x;
-  const int n = ud_z, cam_k = (int)((unsigned)ud_w >> 16), cam_l = ud_w & 0xffff;
-  double *out = partial + (size_t)u * UNIT_STRIDE;
-  if (cam_k == cam_l) schur_unit_run<true, BIG, ROBUST>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out, sqw);
-  else schur_unit_run<false, BIG, ROBUST>(wbuf, lane, beg, n, it_k, it_l, it_a, rec, PB, c, 1.0 / f0, out, sqw);
-}
-
-#define MVBA_PAIRS_ARGS                                                                                                   \
-  const int4 *__restrict__ units, const int *__restrict__ q_ptr, const int *__restrict__ q_units,                        \
-      const int *__restrict__ it_k, const int *__restrict__ it_l, const int *__restrict__ it_a,                          \
-      const double2 *__restrict__ rec, const double *__restrict__ PB, double c, double f0, double *__restrict__ partial
-// (two plain kernels rather than one template, so that profiles show one stable name per variant)
-__global__ __launch_bounds__(64, 3) void k_schur_pairs(MVBA_PAIRS_ARGS) {
-  schur_pairs_wave<false, false>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial, nullptr);
-}
-__global__ __launch_bounds__(64, 3) void k_schur_pairs_big(MVBA_PAIRS_ARGS) {  // 64-bit record / point-block offsets
-  schur_pairs_wave<true, false>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial, nullptr);
-}
-// robust losses: sqrt(w) per observation in `sqw`
-__global__ __launch_bounds__(64, 3) void k_schur_pairs_robust(MVBA_PAIRS_ARGS, const double *__restrict__ sqw) {
-  schur_pairs_wave<false, true>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial, sqw);
-}
-__global__ __launch_bounds__(64, 3) void k_schur_pairs_big_robust(MVBA_PAIRS_ARGS, const double *__restrict__ sqw) {
-  schur_pairs_wave<true, true>(units, q_ptr, q_units, it_k, it_l, it_a, rec, PB, c, f0, partial, sqw);
-}
-
-// ------------------------------------------------------------------ K3 (slot-resident form)
-// The pair-major kernel above reads every record ~5 times from beyond its L2 (89 M line misses for 10 M records at
-// config 3): a unit sweeps 1/16 of the points for ONE pair, so what the ~300 units in flight on an XCD touch at
-// any moment is spread over 80 MB of records.  Here the roles of the 21 item rows of a step are transposed:
-//   slot     a 3-lane slot (item row `it`) owns ONE list -- the items of one (pair, sub-list) inside one point
-//            range -- for the whole launch and keeps that pair's 9x9 block in its 27 registers per lane: still no
-//            scatter, no atomic, no cross-lane sum at all (the fixed-order tree is gone), one partial per list
-//   range    the points are cut into 8 ranges of equal item count, range r = the blocks b with b % 8 == r = XCD r
-//            under the round-robin block placement (locality only, never correctness): a record is needed by ONE
-//            XCD, and ALL lists of the range (m (m+1) / 2 pairs + the diagonal pairs' sub-lists: 5.9 k slots =
-//            284 waves at m = 100) are resident on that XCD at once and sweep the range's points together
-//   steps    built once on the host (mvba_create): the 21 lists of a wave are merged into steps with a bounded skew --
-//            a slot whose next item lies more than `skew` observations ahead of the wave's slowest slot idles
-//            for a step (its row points at the all-zero record / point row: the arithmetic runs and adds
-//            exact zeros) -- so that what a wave touches at any moment fits its XCD's L2 next to its siblings'
-// Same staging (LDS-DMA of whole lines), same arithmetic and the same partial -> k_schur_reduce path as above.
-
-// ---- pacing of k_schur_slots: the waves of a point range keep within `lag` segments of each other, so that what they gather
-// at any moment fits their XCD's L2.  `seg_end[j]` = the step at which this wave has left segment j of its point range,
-// `prog[j]` = how many waves of the range have left segment j, `need` = how many there are.  A performance hint only: a wave
-// that waits too long (its siblings are not resident: somebody else holds the CUs) stops pacing and runs on.  The state
-// (`pacing`, `seg`, `seg_stop`) and the two places that use it (pace_at per step, the last arrivals in the epilogue) live in
-// schur_slots_run: as one object with methods the loop compiled to other code (map of K3).
-struct SlotPace {
-  const int *seg_end;
-  int *prog;
-  int need, nseg, lag;
-};
-
-// ------------------------------------------------------------------ K3, slot form, three lanes per item: one wave's `nst` steps
-// The 21 item rows of a step belong to 21 DIFFERENT lists: each 3-lane slot keeps its own block for the whole run and writes
-// it to its own partial (`out` is the array of partials, `slot_unit` the 21 unit ids of this wave); padding rows point at
-// the all-zero point row.  prologue: two index rows, the gathers of steps 0 and 1 | loop: wait / pace / issue / compute /
-// rotate | epilogue: drain, the pacing's last arrivals, one partial per slot.
-// Three buffers, the gathers of TWO steps in flight: a wave of this form is one serial chain of ~1400 steps
-// for the whole launch and 9 of them share a CU, so what bounds it is steps-in-flight x latency, not
-// throughput (per-wave stamps: 1.18 us per step with one step in flight, every wave alike).
-// The step's INDEX -- 21 k-side, 21 l-side record indices and 21 points, one 256-byte row of the step-major index --
-// travels through LDS too, three rows deep: ONE LDS-DMA instruction per step, read back by ordinary ds_read after the counted
-// wait that covers it.
-// What the counted wait covers: iteration s issues the gathers of step s + 2, then the index row of step s + 4 (into the
-// ring slot whose indices, those of step s + 1, were read an iteration ago) -- 7 operations (DIAG) or 8, every one
-// unconditional, steps past the end clamped to the last one.  "All but the last iteration's operations" at the top of
-// iteration s = step s has landed and the indices of step s + 2 are in LDS, while step s + 1 and the indices of s + 3 stay
-// in flight.
-// 32-bit byte offsets only: with 64-bit per-lane addresses this loop needs more than the 168 registers of three waves per
-// SIMD, and a spill's scratch access would be a vector-memory operation the counted waits do not know about.
-template <bool DIAG>
-__device__ __forceinline__ void schur_slots_run(char *wbuf, const int lane, const long long beg, const int nst,
-                                                const int *__restrict__ it_x, const double2 *__restrict__ rec,
-                                                const double *__restrict__ PB, const double c, const double cu,
-                                                double *__restrict__ out, const int *__restrict__ slot_unit, const SlotPace pace) {
-  using S = SchurStage<PSTEP, DIAG, true>;
-  constexpr int NPS = S::NPS;
-  constexpr unsigned BUFSZ = S::SIZE;
-  const int it = lane / 3, cg = lane - 3 * it;           // compute: item of the step, column group
-  const int drow = lane / 7, dslot = lane - 7 * drow;    // record DMA: 9 rows x 7 slots per instruction
-  const int prow = lane / NPS, pslot = lane - NPS * prow;
-  const int prow2 = (64 + lane) / 5, pslot2 = (64 + lane) - 5 * prow2;  // DIAG: second point-row DMA
-  const int sel0 = cg == 0 ? 3 : (cg == 1 ? 0 : 4);
-  const int sel1 = cg == 0 ? 0 : sel0 + 1, sel2 = cg == 0 ? 0 : sel0 + 2;
-  const double al12 = cg == 0 ? 0.0 : 1.0, bx1 = cg == 0 ? 1.0 : 0.0;
-  double acc[9][3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) acc[i][q] = 0.0;
-  double dg[3] = {0.0, 0.0, 0.0}, rb[3] = {0.0, 0.0, 0.0};
-
-  auto compute = [&](const char *buf, const int ns) { schur_colgroup_step<S, DIAG, true, false>(it, sel0, sel1, sel2, al12, bx1, buf, ns, acc, dg, rb); };
-  bool pacing = true;
-  int seg = 0, seg_stop = as_const(pace.seg_end)[0] * PSTEP;
-  auto pace_at = [&](const int s0) {
-    while (s0 == seg_stop) {  // (wave-uniform) this wave has left segment `seg`
-      if (lane == 0) __hip_atomic_fetch_add(pace.prog + PACE_STRIDE * seg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ++seg;
-      seg_stop = seg < pace.nseg ? as_const(pace.seg_end)[seg] * PSTEP : 0x7fffffff;
-      if (seg >= pace.lag && pacing) {  // nobody enters segment j before everybody has left segment j - lag
-        // (a waiting wave polls every ~3 us: hundreds of waves polling one word at full speed saturate the
-        // fabric's atomic path and slow the arrivals they are waiting for -- 15 ms per launch, measured)
-        int tries = 0;
-        while (__hip_atomic_fetch_add(pace.prog + PACE_STRIDE * (seg - pace.lag), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pace.need) {
-          if (++tries > 1024) { pacing = false; break; }  // ~2 ms: the siblings are not running
-          __builtin_amdgcn_s_sleep(127);
-        }
-        // a wave that had to wait is ahead of the pack, one that did not is among those the pack waits for: the
-        // SIMD's issue arbitration (priority, then age) should favour the latter
-        if (tries > 0) __builtin_amdgcn_s_setprio(0);
-        else __builtin_amdgcn_s_setprio(2);
-      }
-    }
-  };
-  constexpr int SLOT_OPS = DIAG ? 7 : 8;
-  const int last_st = nst - 1;
-  const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)wbuf;
-  const unsigned ldsx0 = lds0 + 3 * SLOT_BUF;             // the index ring
-  const int *xring = reinterpret_cast<const int *>(wbuf + 3 * SLOT_BUF);
-  const int *xbase = it_x + beg * SLOT_IDX;               // (`beg` = first STEP of this wave; wave-uniform)
-  const unsigned lane16 = (unsigned)min(lane, 15) << 4;
-  auto index_row = [&](int st, unsigned ring_off) {  // the 256-byte index row of step st -> ring slot st % 3 = byte offset ring_off
-    const int *src = xbase + (size_t)min(st, last_st) * SLOT_IDX;  // wave-uniform
-    const unsigned dst = ldsx0 + ring_off;
-    if (lane < 16) lds_index_row(lane16, src, dst);
-  };
-  const unsigned ds16 = (unsigned)dslot << 4, ps16 = (unsigned)pslot << 4, ps16b = (unsigned)pslot2 << 4;
-  const int xr0 = min(drow, PSTEP - 1), xr1 = min(9 + drow, PSTEP - 1), xr2 = min(18 + drow, PSTEP - 1);  // this lane's rows of a step
-  const int xa0 = 2 * PSTEP + min(prow, PSTEP - 1), xa1 = 2 * PSTEP + min(prow2, PSTEP - 1), xl = min(lane, PSTEP - 1);
-  auto issue_step = [&](unsigned ring_off, unsigned buf_off) {  // gathers of a step from its indices in the ring (landed: the caller's wait saw to it)
-    const int *x = reinterpret_cast<const int *>(reinterpret_cast<const char *>(xring) + ring_off);
-    const unsigned buf = lds0 + buf_off;
-    const unsigned kb = buf, lb = buf + S::L, pb_ = buf + S::P;
-    const int k0 = x[xr0], k1 = x[xr1], k2 = x[xr2];
-    if (!DIAG) {
-      const int l0 = x[PSTEP + xr0], l1 = x[PSTEP + xr1], l2 = x[PSTEP + xr2], a0 = x[xa0];
-      if (lane < 63) {
-        lds_gather16(k0, ds16, rec, kb);
-        lds_gather16(l0, ds16, rec, lb);
-        lds_gather16(k1, ds16, rec, kb + 9 * PROW);
-        lds_gather16(l1, ds16, rec, lb + 9 * PROW);
-        lds_gather16(a0, ps16, PB, pb_);
-      }
-      if (lane < 7 * (PSTEP - 18)) {
-        lds_gather16(k2, ds16, rec, kb + 18 * PROW);
-        lds_gather16(l2, ds16, rec, lb + 18 * PROW);
-      }
-    } else {
-      const int kl = x[xl], a0 = x[xa0], a1 = x[xa1];
-      if (lane < 63) {
-        lds_gather16(k0, ds16, rec, kb);
-        lds_gather16(k1, ds16, rec, kb + 9 * PROW);
-      }
-      if (lane < 7 * (PSTEP - 18)) lds_gather16(k2, ds16, rec, kb + 18 * PROW);
-      if (lane < PSTEP) lds_gather16(kl, 7u << 4, rec, lb);  // l-side == k-side: only the residual (slot 7) is fetched
-      lds_gather16(a0, ps16, PB, pb_);
-      if (lane < 5 * PSTEP - 64) lds_gather16(a1, ps16b, PB, pb_ + 1024);
-    }
-  };
-  constexpr unsigned RING_B = SLOT_IDX * 4;
-  index_row(0, 0);
-  index_row(1, RING_B);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  issue_step(0, 0);
-  index_row(2, 2 * RING_B);
-  issue_step(last_st >= 1 ? RING_B : 0, BUFSZ);  // (a one-step wave: the clamped step 0 once more, into the buffer nobody reads)
-  index_row(3, 0);
-  unsigned b0 = 0, b1 = BUFSZ, b2 = 2 * BUFSZ, r0 = 0, r1 = RING_B, r2 = 2 * RING_B;  // offsets of step st, st + 1, st + 2
-  for (int st = 0; st < nst; ++st) {
-    // step st has landed and the indices of step st + 2 are in the ring: everything but the last iteration's operations is done
-    if (DIAG) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    pace_at(st * PSTEP);
-    issue_step(r2, b2);  // step st + 2 (past the end: the ring slot holds the indices of the clamped last step, its rows land in a buffer nobody reads)
-    index_row(st + 4, r1);  // (st + 4) % 3 = (st + 1) % 3: the slot whose indices were read an iteration ago
-    compute(wbuf + b0, PSTEP);
-    // rotate: which buffer / ring slot a step uses -- step % 3 -- is carried as byte offsets (the remainders cost a dozen scalar
-    // instructions a step); written out here and in schur_lanes_run: through a shared helper both loops compiled to other code
-    { const unsigned tb = b0, tr = r0; b0 = b1; b1 = b2; b2 = tb; r0 = r1; r1 = r2; r2 = tr; }
-  }
-  static_assert(SLOT_OPS == (DIAG ? 7 : 8), "counted wait");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped gathers still in flight land in this wave's LDS
-  // J_C row i = rs_i * (record columns): f | u,v (1/f0) | t (-Jx) | omega; the same factors per column
-  const double cs0 = cg == 1 ? -1.0 : 1.0, cs12 = cg == 0 ? cu : cs0;
-  if (lane == 0)
-    for (; seg < pace.nseg; ++seg) __hip_atomic_fetch_add(pace.prog + PACE_STRIDE * seg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int u = it < PSTEP ? slot_unit[it] : -1;
-  if (u >= 0) {
-    double *o = out + (size_t)u * UNIT_STRIDE;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      const double rs = jc_sign(i, cu);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) o[9 * i + 3 * cg + q] = -4.0 * rs * (q == 0 ? cs0 : cs12) * acc[i][q];
-    }
-    if (DIAG) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const double cs = q == 0 ? cs0 : cs12;
-        o[81 + 3 * cg + q] = 2.0 * c * cs * cs * dg[q];
-        o[90 + 3 * cg + q] = 2.0 * cs * rb[q];
-      }
-    }
-  }
-}
-__device__ __forceinline__ void schur_slots_wave(const int4 *__restrict__ wdesc, const int *__restrict__ wunits,
-                                                 const int *__restrict__ it_k, const int *__restrict__ it_l,
-                                                 const int *__restrict__ it_a, const double2 *__restrict__ rec,
-                                                 const double *__restrict__ PB, double c, double f0,
-                                                 double *__restrict__ partial, int nR, const int *__restrict__ seg_end,
-                                                 int *__restrict__ prog, int nseg, int lag,
-                                                 const long long *__restrict__ range_o0) {
-  extern __shared__ char smem_pairs[];
-  // which wave of which range: block b IS wave b / nR of range b % nR
-  const int bid = blockIdx.x;
-  const int MVBA_CONST_AS *dp = as_const(reinterpret_cast<const int *>(wdesc)) + 4 * (size_t)bid;
-  const int d_x = dp[0], d_y = dp[1], nsteps = dp[2], flags = dp[3];
-  if (nsteps <= 0) return;  // (wave-uniform) a wave whose lists are all empty in this range: no units, nothing to write
-  const long long beg = ((long long)d_y << 32) | (unsigned)d_x;
-  const int *su = wunits + (size_t)bid * PSTEP;
-  // flags: bit 0 diagonal wave | bits 8..19 live waves of this range
-  const int r = bid % nR, live = (flags >> 8) & 0xfff;
-  // the record indices of the step rows are RELATIVE to the range's first observation: the 32-bit byte offsets of the
-  // gathers then span a range's records (4 GiB = 33.5 M observations per range), not the scene's
-  const double2 *rec_r = rec + (size_t)as_const(range_o0)[r] * REC;
-  const SlotPace pace{seg_end + (size_t)bid * nseg, prog + (size_t)r * nseg * PACE_STRIDE, live, nseg, lag};
-  if (flags & 1)
-    schur_slots_run<true>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_k, rec_r, PB, c, 1.0 / f0, partial, su, pace);
-  else
-    schur_slots_run<false>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_k, rec_r, PB, c, 1.0 / f0, partial, su, pace);
-}
-#define MVBA_SLOTS_ARGS                                                                                                  \
-  const int4 *__restrict__ wdesc, const int *__restrict__ wunits, const int *__restrict__ it_k, const int *__restrict__ it_l, \
-      const int *__restrict__ it_a, const double2 *__restrict__ rec, const double *__restrict__ PB, double c, double f0,  \
-      double *__restrict__ partial, int nR, const int *__restrict__ seg_end, int *__restrict__ prog,                      \
-      int nseg, int lag, const long long *__restrict__ range_o0
-__global__ __launch_bounds__(64, 3) void k_schur_slots(MVBA_SLOTS_ARGS) {
-  schur_slots_wave(wdesc, wunits, it_k, it_l, it_a, rec, PB, c, f0, partial, nR, seg_end, prog, nseg, lag, range_o0);
-}
-
-#include "mvba_lanes.h"  // the slot form with one lane per item: schur_lanes_run, 64 lists per wave
-constexpr int slot_idx_ints(int W) { return W == LANES_W ? LANES_IDX : SLOT_IDX; }  // ints of a step's index row at width W
-
-// The slot form at 64 lists per wave (mvba_lanes.h): block b IS wave b / nR of range b % nR as above, its index rows are
-// 768 bytes and its unit ids 64 per wave.  Not paced: no counters to clear, the pacing table of the index is not read.
-__global__ __launch_bounds__(64, 1) void k_schur_lanes(const int4 *__restrict__ wdesc, const int *__restrict__ wunits,
-                                                       const int *__restrict__ it_x, const double2 *__restrict__ rec,
-                                                       const double *__restrict__ PB, double c, double f0,
-                                                       double *__restrict__ partial, int nR,
-                                                       const long long *__restrict__ range_o0) {
-  extern __shared__ char smem_pairs[];
-  const int bid = blockIdx.x;
-  const int MVBA_CONST_AS *dp = as_const(reinterpret_cast<const int *>(wdesc)) + 4 * (size_t)bid;
-  const int d_x = dp[0], d_y = dp[1], nsteps = dp[2], flags = dp[3];
-  if (nsteps <= 0) return;  // (wave-uniform) a wave whose lists are all empty in this range
-  const long long beg = ((long long)d_y << 32) | (unsigned)d_x;
-  const int *su = wunits + (size_t)bid * LANES_W;
-  const double2 *rec_r = rec + (size_t)as_const(range_o0)[bid % nR] * REC;  // record indices are relative to the range's first observation
-  if (flags & 1) schur_lanes_run<true>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec_r, PB, c, 1.0 / f0, partial, su);
-  else schur_lanes_run<false>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec_r, PB, c, 1.0 / f0, partial, su);
-}
-
-// One thread per element of a pair's block: the pair's unit partials in unit order -> packed strips.
-// One block per PAIR (blockIdx.x = packed pair index); the partials are loaded eight at a time (one
-// memory latency per eight units instead of one per unit: a diagonal pair has ~130 of them) and
-// added in unit order, so the result does not depend on the schedule.
-__global__ __launch_bounds__(128) void k_schur_reduce(int m, const int *__restrict__ unit_ptr,
-                                                      const double *__restrict__ partial, double *__restrict__ Afull,
-                                                      double *__restrict__ bfull) {
-  // pair index -> (k, l): pairs of strip k start at k m - k (k - 1) / 2
-  const long long p = blockIdx.x;
-  int k = (int)((2.0 * m + 1.0 - sqrt((2.0 * m + 1.0) * (2.0 * m + 1.0) - 8.0 * (double)p)) * 0.5);
-  while ((long long)k * m - (long long)k * (k - 1) / 2 > p) --k;
-  while ((long long)(k + 1) * m - (long long)(k + 1) * k / 2 <= p) ++k;
-  const int l = k + (int)(p - ((long long)k * m - (long long)k * (k - 1) / 2));
-  const int u0 = unit_ptr[p], u1 = unit_ptr[p + 1];
-  const int e = threadIdx.x;
-  if (e >= (k == l ? 99 : 81)) return;
-  auto ordered_sum = [&](int off) {
-    double v = 0.0;
-    int uu = u0;
-    for (; uu + 8 <= u1; uu += 8) {
-      double t[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t[q] = partial[(size_t)(uu + q) * UNIT_STRIDE + off];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v += t[q];
-    }
-    for (; uu < u1; ++uu) v += partial[(size_t)uu * UNIT_STRIDE + off];
-    return v;
-  };
-  const double v = ordered_sum(e);
-  double *Ak = Afull + strip_offset(k, m);
-  const int Wk = 9 * (m - k);
-  if (e < 81) {
-    const int i = e / 9, j = e - 9 * i;
-    const double d = (k == l && i == j) ? ordered_sum(81 + i) : 0.0;  // Marquardt damping of G_k's diagonal
-    Ak[(size_t)i * Wk + 9 * (l - k) + j] = v + d;
-  } else if (e >= 90) {
-    bfull[9 * k + (e - 90)] = v;
-  }
-}
-
-// ------------------------------------------------------------------ K3 (dense visibility: every point seen by every camera)
-// The reference's own scenes (euclidiean_reconstruction.py, affine_reconstruction.py, BASELINE config 2) and the pipeline test at
-// 1 M points x 12 images have FULL visibility and a dozen or two cameras.  The pair-major forms above then walk m (m + 1) / 2 items
-// per point through gathers and an index of their own (78 items and 0.9 GB of index per million points at 12 cameras: 4.9 ms per
-// solve, 63 ps per item against 30 at config 3) although a point's m records are ONE contiguous range and every pair is present.
-// With E_a^-1 = R_a R_a^T (3 x 3 Cholesky) and the scaled camera Jacobian J~_ak (2 x 9: f | u, v (1 / f0) | t (-J_X) | omega)
-//   G_a = [R_a^T J_Xak^T J~_ak]_k   (3 x 9m),        A = blockdiag(2 H_k + c diag(2 H_k)) - 4 sum_a G_a^T G_a,
-//   H_k = sum_a J~_ak^T J~_ak,                        b_k = 2 sum_a J~_ak^T (J_Xak E_a^-1 dP_a - e_ak)
-// -- one symmetric rank-3N update of a 9m x 9m matrix: a GEMM, on the f64 matrix cores, over records streamed ONCE.
-// A workgroup takes a chunk of points (dense_ch: 4 or 8) at a time: their records and point rows go into LDS with contiguous 16-byte loads; a thread per
-// observation forms J_X R and the right-hand-side vector w; the rows of G are written to LDS once (each is read by up to T tile
-// pairs); wave w then owns the 16 x 16 tile pairs w, w + 4, ... of the upper triangle (four consecutive rows of G -- of whichever
-// points -- are one v_mfma_f64_16x16x4: no padding of K) and the per-camera tiles [J~ | w]^T [J~ | w] (two points per MFMA) of the
-// cameras w, w + 4, ...  Partial tiles per workgroup, summed in workgroup order by k_schur_dense_finish: no atomics, bitwise
-// reproducible.  No index at all: mvba_create skips the pair-major index for such scenes.
-typedef double mvba_d4 __attribute__((ext_vector_type(4)));
-// Points per chunk (= producer waves) and workgroups per CU.  Up to 7 tiles (12 cameras) the kernel needs at most 126 registers: four
-// waves fit a SIMD, so TWO 8-wave workgroups of 4-point chunks (~53 KB of LDS each) share a CU and fill each other's barrier waits
-// (1.335 -> 1.260 ms at 1 M x 12, 1.48 -> 1.32 at 2 M x 6; three workgroups: worse again).  8 tiles take 154 registers -- three waves
-// per SIMD -- and stay with one 12-wave workgroup of 8-point chunks (two of the small ones cannot both be resident: 1.65 -> 1.82 ms
-// at 14 cameras); beyond that eight consumer + four producer waves.  (tools/dense_ch.sh, profiles/r05_dense_form.txt)
-constexpr int dense_ch(int T) { return T == 8 ? 8 : 4; }
-constexpr int dense_wgs(int T) { return T <= 7 ? 2 : 1; }
-constexpr int DENSE_MAX_TILES = 12;  // 9 m <= 192: m <= 21 cameras (78 tile pairs: 20 accumulators of 4 doubles per lane)
-__device__ __forceinline__ int dense_tile_elem(int row, int col) { return ((row >> 2) << 6) | ((row & 3) << 4) | col; }  // C/D layout: col = l & 15, row = (l >> 4) + 4 reg
-
-constexpr int dense_pair_ti(int p, int T) { int a = 0; while (p >= T - a) { p -= T - a; ++a; } return a; }
-constexpr int dense_pair_tj(int p, int T) { int a = 0; while (p >= T - a) { p -= T - a; ++a; } return a + p; }
-constexpr int dense_consumers(int T) { return T <= 8 ? 4 : 8; }  // consumer waves: at most ~10 tile pairs (40 accumulator doubles) each
-constexpr bool dense_tile_used(int u, int T, int wave) {  // does consumer wave `wave` own a pair with tile u?
-  const int P = T * (T + 1) / 2, NC = dense_consumers(T);
-  for (int p = wave; p < P; p += NC)
-    if (dense_pair_ti(p, T) == u || dense_pair_tj(p, T) == u) return true;
-  // (its spare slots repeat the last pair)
-  return (P + NC - 1) / NC * NC - NC + wave >= P && (dense_pair_ti(P - 1, T) == u || dense_pair_tj(P - 1, T) == u);
-}
-// the main products of one chunk for consumer wave WAVE: its tile pairs p = NC q + WAVE are known at compile time, so the operand of a
-// tile is read from LDS ONCE per four rows of G and used from its register by every pair that needs it (two reads per MFMA, with
-// the tiles indexed at run time, kept the LDS half busy under the matrix cores).  (The pair -> tile arithmetic goes through class
-// templates: called as constexpr FUNCTIONS inside the unrolled loops it was evaluated at run time, with the registers indexed
-// through s_set_gpr_idx.)
-template <int T, int WAVE, int Q>
-struct DensePair {
-  static constexpr int P = T * (T + 1) / 2, NC = dense_consumers(T);
-  static constexpr int p = NC * Q + WAVE < P ? NC * Q + WAVE : P - 1;  // (a spare slot repeats the last pair: computed, never stored)
-  static constexpr int ti = dense_pair_ti(p, T), tj = dense_pair_tj(p, T);
-};
-template <int T, int WAVE, int U>
-struct DenseUsed { static constexpr bool v = dense_tile_used(U, T, WAVE); };
-template <int T, int WAVE, int... U>
-__device__ __forceinline__ void dense_load_tiles(const double *row, double (&t)[T], std::integer_sequence<int, U...>) {
-  ((t[U] = DenseUsed<T, WAVE, U>::v ? row[16 * U] : 0.0), ...);
-}
-template <int T, int WAVE, int... Q>
-__device__ __forceinline__ void dense_mfma_pairs(const double (&ts)[T], const double (&t)[T], mvba_d4 *acc, std::integer_sequence<int, Q...>) {
-  ((acc[Q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ts[DensePair<T, WAVE, Q>::ti], t[DensePair<T, WAVE, Q>::tj], acc[Q], 0, 0, 0)), ...);
-}
-template <int T, int WAVE, int CH>
-__device__ __forceinline__ void dense_main_mfma(const double *sG, const double *sSgn, int li, int lk, mvba_d4 *acc) {
-  constexpr int P = T * (T + 1) / 2, NC = dense_consumers(T), NPW = (P + NC - 1) / NC, W = 16 * T;
-#pragma unroll
-  for (int g = 0; g < 3 * CH / 4; ++g) {  // four rows of G per MFMA: sum_r s_r g_r^T g_r (s = +-1: E^-1 = R S R^T), the sign on the left operand
-    double t[T], ts[T];
-    dense_load_tiles<T, WAVE>(sG + (size_t)(4 * g + lk) * W + li, t, std::make_integer_sequence<int, T>{});
-    const double sg = sSgn[4 * g + lk];
-#pragma unroll
-    for (int u = 0; u < T; ++u) ts[u] = t[u] * sg;
-    dense_mfma_pairs<T, WAVE>(ts, t, acc, std::make_integer_sequence<int, NPW>{});
-  }
-}
-
-// Two roles in a workgroup, one barrier per chunk: waves 0-3 multiply chunk i (main pairs and camera tiles out of the buffers of
-// parity i & 1) while the producer waves -- one per point of a chunk -- build chunk i + 1 into the other buffers, each taking its
-// point from its records (fetched into registers a chunk earlier) to the rows of G on its own, so the producers need no barrier
-// among themselves.  (With every wave doing every phase in turn -- four barriers per chunk -- the workgroups of a CU ran in
-// lockstep and the phases never overlapped: 1.55 ms at 1 M x 12 for 0.81 ms of MFMA phase; with four producer waves of two points
-// each the producers were the longer role: 1.90 ms.)
-// ROBUST: the records are scaled by sqrt(w) (K1); the constant columns of an observation become sqrt(w) / f0
-// instead of 1 / f0 -- the per-(point, camera) factor sF takes sqrt(w) from `sqw`, fetched with the records.
-#define MVBA_DENSE_ARGS                                                                                                   \
-  const double2 *__restrict__ rec, const double *__restrict__ PB, const int *__restrict__ obs_of, long long N, int m, double cu, \
-      double *__restrict__ part
-template <int T, bool TABLE, bool ROBUST = false, typename... Robust>  // TABLE: the records of a point through obs_of (missing observations), otherwise one contiguous range
-__global__ __launch_bounds__(64 * (dense_consumers(T) + dense_ch(T))) void k_schur_dense(MVBA_DENSE_ARGS, Robust... robust) {
-  constexpr int NC = dense_consumers(T);           // consumer waves (4 + 8 producers up to 8 tiles, 8 + 4 beyond)
-  constexpr int P = T * (T + 1) / 2, NPW = (P + NC - 1) / NC, W = 16 * T, NCW = ((16 * T) / 9 + NC - 1) / NC;
-  constexpr int CH = dense_ch(T);       // points per chunk = producer waves (the double-buffered rows must fit the LDS beside each other)
-  constexpr int MMAX = (16 * T) / 9;               // cameras at most
-  constexpr int NTHR = 64 * (NC + CH);
-  extern __shared__ double2 dsm[];
-  double *sG = reinterpret_cast<double *>(dsm);                     // [2][3 CH][W]
-  double *sB = sG + (size_t)2 * 3 * CH * W;                         // [2][CH m][2][16]: rows x, y of [J~ (9) | w | 0 ...]
-  double2 *sScr = reinterpret_cast<double2 *>(sB + (size_t)2 * CH * m * 32);  // per producer wave: records [m][8], point row [8]
-  double *sFlag = reinterpret_cast<double *>(sScr + (size_t)CH * (m * REC + 8));  // per producer wave: [m] 1 for an observation, 0 for a missing one
-  double *sSgn = sFlag + (size_t)CH * m;                            // [2][3 CH]: the signs of the rows of G
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;  // (wave through readfirstlane -- scalar address arithmetic for the producers -- made every shape slower: 1.36 -> 1.55 ms at 1 M x 12, 2.95 -> 12.6 at 20 cameras)
-  const long long n_chunks = (N + CH - 1) / CH;
-  // what no phase ever writes stays zero: the columns of G beyond 9 m, the columns 10..15 of the camera rows
-  for (int e = threadIdx.x; e < 2 * 3 * CH * W; e += NTHR) sG[e] = 0.0;
-  for (int e = threadIdx.x; e < 2 * CH * m * 32; e += NTHR) sB[e] = 0.0;
-  __syncthreads();
-  if (wave >= NC) {
-    // ---------------- producer: point pw of every chunk of this workgroup.  (Without the staging -- a lane per (camera, column)
-    // fetching its four record slots itself -- the per-lane loads cost more than the staging saves: 1.82 against 1.40 ms.)
-    const int pw = wave - NC;
-    // The producers are the longer role (role trace, profiles/r05_dense_form.txt: 5,350 cycles of work per chunk against the consumers' 4,480 + 1,400 at
-    // the barrier, 1 M x 12) and, as the later-dispatched waves of their SIMD, the losers of its issue arbitration (older first at
-    // equal priority): they ask for the higher priority once, here.
-    __builtin_amdgcn_s_setprio(1);
-    double2 *sR = sScr + (size_t)pw * (m * REC + 8), *sP = sR + (size_t)m * REC;
-    constexpr int NPRE = (MMAX * REC + 63) / 64, NIT = (MMAX * 10 + 63) / 64;
-    // TWO chunks' records in flight per wave (sets A and B, used in turn): with one, a CU had 8 waves x 1.5 KB outstanding against
-    // ~2 us of loaded memory latency -- 1.5 TB/s over the chip, which is where the kernel sat at every camera count (~1.0 ms per
-    // million points x 12 cameras whatever the matrix cores had to do)
-    double2 preA[NPRE], prepbA, preB[NPRE], prepbB;
-    double swA[NPRE], swB[NPRE];                   // ROBUST: sqrt(w) of the observation of every record slot a lane fetched
-    bool lvA, lvB;
-    int oidA[NPRE], oidB[NPRE], oid_next[NPRE];    // (obs_of != nullptr) the observations of a set's point / of the point fetched next
-    double *sF = sFlag + (size_t)pw * m;
-    auto fetch_ids = [&](long long ch) {           // the table row of chunk ch's point (one entry per record: eight lanes share it)
-      const long long a = ch * CH + pw;
-#pragma unroll
-      for (int u = 0; u < NPRE; ++u) {
-        const int e = lane + 64 * u;
-        const int got = obs_of[(size_t)min(a, N - 1) * m + min(e >> 3, m - 1)], msk = (a < N && e < m * REC) ? -1 : 0;
-        oid_next[u] = (got & msk) | ~msk;          // (-1 outside; the load itself is unconditional, see fetch)
-      }
-    };
-    auto fetch = [&](long long ch, double2 (&pre)[NPRE], int (&oid)[NPRE], double2 &prepb, bool &lv, double (&sw)[NPRE]) {  // this wave's records and point row of chunk ch (zeros past the last point)
-      // The loads are UNCONDITIONAL on clamped addresses and what must be zero (a missing observation, a point past the end) is
-      // zeroed on the bit pattern in build(): behind a lane-dependent branch the compiler cannot count the loads in flight and
-      // waits for all of them (vmcnt(0)) -- the other set's too, which is the one meant to stay in flight
-      const long long a = ch * CH + pw;
-      const bool live = lv = a < N;
-      if (TABLE) {                                 // through the table read a chunk earlier
-#pragma unroll
-        for (int u = 0; u < NPRE; ++u) {
-          oid[u] = oid_next[u];
-          pre[u] = rec[(size_t)max(oid[u], 0) * REC + ((lane + 64 * u) & 7)];
-          if constexpr (ROBUST) sw[u] = (robust, ...).sqw[max(oid[u], 0)];
-        }
-      } else {
-        const double2 *src = rec + (size_t)min(a, N - 1) * m * REC;
-#pragma unroll
-        for (int u = 0; u < NPRE; ++u) {
-          pre[u] = src[min(lane + 64 * u, m * REC - 1)];
-          oid[u] = live ? 0 : -1;
-          if constexpr (ROBUST) sw[u] = (robust, ...).sqw[(size_t)min(a, N - 1) * m + min((lane + 64 * u) >> 3, m - 1)];
-        }
-      }
-      prepb = reinterpret_cast<const double2 *>(PB + (size_t)min(a, N - 1) * PBS)[lane & 7];
-    };
-    auto keep = [](bool c, double2 v) -> double2 {  // c ? v : 0 without a branch the load could sink under
-      const long long msk = c ? -1LL : 0LL;
-      return double2{__longlong_as_double(__double_as_longlong(v.x) & msk), __longlong_as_double(__double_as_longlong(v.y) & msk)};
-    };
-    auto build = [&](int buf, const double2 (&pre)[NPRE], const int (&oid)[NPRE], const double2 &prepb, bool lv, const double (&sw)[NPRE]) {  // registers -> the rows of G and the camera rows of this wave's point in buffer `buf`
-#pragma unroll
-      for (int u = 0; u < NPRE; ++u) {
-        const int e = lane + 64 * u;
-        if (e < m * REC) sR[e] = keep(oid[u] >= 0, pre[u]);
-        if (e < m * REC && (e & 7) == 0) sF[e >> 3] = oid[u] >= 0 ? (ROBUST ? sw[u] : 1.0) : 0.0;
-      }
-      sP[lane & 7] = keep(lv, prepb);             // (every lane, eight copies of each slot: a store under `lane < 8` drew a vmcnt(0))
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      // point row: E^-1 (6) | E^-1 dP (3) | sign code | R lower triangular (r00 r10 r20 r11 r21 r22) of E^-1 = R S R^T (k_point_inv), the same for every lane
-      const double *pb = reinterpret_cast<const double *>(sP);
-      const double d0 = pb[6], d1 = pb[7], d2 = pb[8];
-      const double r00 = pb[10], r10 = pb[11], r20 = pb[12], r11 = pb[13], r21 = pb[14], r22 = pb[15];
-      double *gB = sB + ((size_t)buf * CH + pw) * m * 32;
-      double *gG = sG + ((size_t)buf * 3 * CH + (size_t)3 * pw) * W;
-      if (lane < 3) sSgn[(size_t)buf * 3 * CH + 3 * pw + lane] = (((int)pb[9] - 1) >> lane) & 1 ? -1.0 : 1.0;
-      // a lane per (camera k, column j <= 9): column j of J~ (f | u, v (1 / f0) | t (-J_X) | omega) into the two camera rows and
-      // G[r][9 k + j] = (J_X R)[:, r] . J~[:, j] (E^-1 = R R^T); j = 9: w = J_X E^-1 dP - e, the tenth column of the camera rows
-#pragma unroll
-      for (int u = 0; u < NIT; ++u) {
-        const int e = lane + 64 * u, k = e / 10, j = e - 10 * k;
-        if (e < 10 * m) {
-          const double2 *r = sR + (size_t)k * REC;
-          const double2 x0 = r[0], x1 = r[1], x2 = r[2];
-          const double2 cv = r[j == 0 ? 3 : (j < 6 ? (j < 3 ? 0 : j - 3) : (j < 9 ? j - 2 : 7))];
-          if (j == 9) {
-            gB[(size_t)k * 32 + 9] = x0.x * d0 + x1.x * d1 + x2.x * d2 - cv.x;
-            gB[(size_t)k * 32 + 25] = x0.y * d0 + x1.y * d1 + x2.y * d2 - cv.y;
-          } else {
-            const double sg = (j >= 3 && j < 6) ? -1.0 : 1.0, live = sF[k] * cu;  // (the constant columns 1 / f0 of an observation that exists)
-            const double jx = j == 1 ? live : (j == 2 ? 0.0 : sg * cv.x), jy = j == 2 ? live : (j == 1 ? 0.0 : sg * cv.y);
-            gB[(size_t)k * 32 + j] = jx;
-            gB[(size_t)k * 32 + 16 + j] = jy;
-            double *g = gG + 9 * k + j;
-            g[0] = (x0.x * r00 + x1.x * r10 + x2.x * r20) * jx + (x0.y * r00 + x1.y * r10 + x2.y * r20) * jy;
-            g[W] = (x1.x * r11 + x2.x * r21) * jx + (x1.y * r11 + x2.y * r21) * jy;
-            g[2 * W] = (x2.x * r22) * jx + (x2.y * r22) * jy;
-          }
-        }
-      }
-    };
-    long long ch = blockIdx.x;
-    const long long gs = gridDim.x;
-    // (a fetch past the last chunk loads nothing: zero records nobody reads; fetch_ids likewise -1)
-    if (TABLE) fetch_ids(ch);
-    fetch(ch, preA, oidA, prepbA, lvA, swA);
-    if (TABLE) fetch_ids(ch + gs);
-    fetch(ch + gs, preB, oidB, prepbB, lvB, swB);
-    if (TABLE) fetch_ids(ch + 2 * gs);
-    build(0, preA, oidA, prepbA, lvA, swA);
-    fetch(ch + 2 * gs, preA, oidA, prepbA, lvA, swA);
-    if (TABLE) fetch_ids(ch + 3 * gs);
-    __syncthreads();
-    // One barrier per chunk, as the consumers; the sets alternate: B holds chunk ch + 1, A chunk ch + 2.  Nothing in the body is
-    // conditional (behind `if (ch + gs < n_chunks)` the compiler lost count of the loads in flight and waited vmcnt(0) for both
-    // sets): past the last chunk a build writes a chunk of zeros into the buffer nobody reads any more.
-    for (int b = 0; ch < n_chunks;) {
-      build(b ^ 1, preB, oidB, prepbB, lvB, swB);
-      fetch(ch + 3 * gs, preB, oidB, prepbB, lvB, swB);
-      if (TABLE) fetch_ids(ch + 4 * gs);
-      __syncthreads();
-      ch += gs, b ^= 1;
-      if (ch >= n_chunks) break;
-      build(b ^ 1, preA, oidA, prepbA, lvA, swA);
-      fetch(ch + 3 * gs, preA, oidA, prepbA, lvA, swA);
-      if (TABLE) fetch_ids(ch + 4 * gs);
-      __syncthreads();
-      ch += gs, b ^= 1;
-    }
-    return;
-  }
-  // ---------------- consumer: tile pairs NC q + wave of the upper triangle (row-major), cameras NC q + wave
-  mvba_d4 acc[NPW], cacc[NCW];
-#pragma unroll
-  for (int q = 0; q < NPW; ++q) acc[q] = mvba_d4{0, 0, 0, 0};
-#pragma unroll
-  for (int q = 0; q < NCW; ++q) cacc[q] = mvba_d4{0, 0, 0, 0};
-  __syncthreads();  // chunk 0 is built
-  int b = 0;
-  for (long long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x, b ^= 1) {
-    const double *bG = sG + (size_t)b * 3 * CH * W, *bB = sB + (size_t)b * CH * m * 32, *bS = sSgn + (size_t)b * 3 * CH;
-    switch (wave) {  // (uniform)
-      case 0: dense_main_mfma<T, 0, CH>(bG, bS, li, lk, acc); break;
-      case 1: dense_main_mfma<T, 1, CH>(bG, bS, li, lk, acc); break;
-      case 2: dense_main_mfma<T, 2, CH>(bG, bS, li, lk, acc); break;
-      case 3: dense_main_mfma<T, 3, CH>(bG, bS, li, lk, acc); break;
-      case 4: dense_main_mfma<T, 4 % NC, CH>(bG, bS, li, lk, acc); break;  // (cases 4..7 exist with eight consumers only)
-      case 5: dense_main_mfma<T, 5 % NC, CH>(bG, bS, li, lk, acc); break;
-      case 6: dense_main_mfma<T, 6 % NC, CH>(bG, bS, li, lk, acc); break;
-      default: dense_main_mfma<T, 7 % NC, CH>(bG, bS, li, lk, acc); break;
-    }
-#pragma unroll
-    for (int g = 0; g < CH / 2; ++g) {  // the per-camera tiles: rows (point 2 g, x), (2 g, y), (2 g + 1, x), (2 g + 1, y)
-      const int pa = 2 * g + (lk >> 1), d = lk & 1;
-#pragma unroll
-      for (int q = 0; q < NCW; ++q) {
-        const int k = min(NC * q + wave, m - 1);
-        const double v = bB[(size_t)(pa * m + k) * 32 + 16 * d + li];
-        cacc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v, cacc[q], 0, 0, 0);
-      }
-    }
-    __syncthreads();  // this chunk's buffers may be rebuilt, the next chunk's are complete
-  }
-  double *out = part + (size_t)blockIdx.x * (P + m) * 256;
-#pragma unroll
-  for (int q = 0; q < NPW; ++q) {
-    const int p = NC * q + wave;
-    if (p < P)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) out[(size_t)p * 256 + r * 64 + lane] = acc[q][r];
-  }
-#pragma unroll
-  for (int q = 0; q < NCW; ++q) {
-    const int k = NC * q + wave;
-    if (k < m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) out[(size_t)(P + k) * 256 + r * 64 + lane] = cacc[q][r];
-  }
-}
-
-// One wave per element of the packed strips [A | b]: the workgroups' partial tiles summed in workgroup order (lane l takes the
-// workgroups l, l + 64, ... in order, then a fixed tree).
-__global__ __launch_bounds__(256) void k_schur_dense_finish(int m, int T, int blocks, const double *__restrict__ part, double c,
-                                                            double *__restrict__ Afull, double *__restrict__ bfull) {
-  const long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63, P = T * (T + 1) / 2;
-  const long long nA = (long long)strip_offset(m, m);
-  if (e >= nA + 9 * m) return;
-  const size_t bstride = (size_t)(P + m) * 256;
-  auto total = [&](int tile, int elem) {
-    double t = 0.0;
-    for (int b = lane; b < blocks; b += 64) t += part[(size_t)b * bstride + (size_t)tile * 256 + elem];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
-    return t;  // (valid in lane 0)
-  };
-  if (e < nA) {
-    int k = 0;
-    while (k + 1 < m && (long long)strip_offset(k + 1, m) <= e) ++k;
-    const int Wk = 9 * (m - k), rem = (int)(e - (long long)strip_offset(k, m)), i = rem / Wk, cr = rem - i * Wk, l = k + cr / 9, j = cr - 9 * (l - k);
-    const int gi = 9 * k + i, gj = 9 * l + j, lo = min(gi, gj), hi = max(gi, gj), ti = lo >> 4, tj = hi >> 4;
-    double v = -4.0 * total(ti * T - ti * (ti - 1) / 2 + (tj - ti), dense_tile_elem(lo & 15, hi & 15));
-    if (k == l) {
-      const double hk = total(P + k, dense_tile_elem(i, j));
-      v += 2.0 * hk * (i == j ? 1.0 + c : 1.0);  // G_k and its Marquardt term c diag(G_k)   (ref :123-125)
-    }
-    if (lane == 0) Afull[e] = v;
-  } else {
-    const int q = (int)(e - nA), k = q / 9, j = q - 9 * k;
-    const double v = 2.0 * total(P + k, dense_tile_elem(j, 9));  // 2 Jc_k^T (Jx_k E^-1 dP - e)
-    if (lane == 0) bfull[q] = v;
-  }
-}
-
+#include "mvba_device.h"     // what the stages share: fixed-order sums, the camera table in LDS, packed strips, REC / PBS
+#include "mvba_linearize.h"  // K1 (+ K2), K3a: k_resid_jac, k_sum_split, k_point_inv
+#include "mvba_schur.h"      // K3, the gather forms: k_schur_pairs*, k_schur_slots, k_schur_lanes (mvba_lanes.h), k_schur_reduce
+#include "mvba_dense.h"      // K3, full visibility: k_schur_dense, k_schur_dense_finish
 #include "mvba_solve.h"  // K4, device side: gauge strip, blocked Cholesky, the two back-substitutions, the pivoted-LU rescue
-
-// ------------------------------------------------------------------ K6a: trial cameras (ref :263-281, utils.py:10-29)
-__global__ void k_update_cams(int m, const double *__restrict__ cam15, const double *__restrict__ dxi,
-                              double *__restrict__ out15) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= m) return;
-  const double *in = cam15 + (size_t)k * CAM_IN, *d = dxi + 9 * (size_t)k;
-  double *o = out15 + (size_t)k * CAM_IN;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) o[i] = in[i] + d[i];
-  const double w0 = d[6], w1 = d[7], w2 = d[8];
-  if (w0 == 0.0 && w1 == 0.0 && w2 == 0.0) {  // exact-zero shortcut (utils.py:14-15)
-#pragma unroll
-    for (int i = 0; i < 9; ++i) o[6 + i] = in[6 + i];
-    return;
-  }
-  const double th = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-  const double n0 = w0 / th, n1 = w1 / th, n2 = w2 / th;
-  const double cs = cos(th), sn = sin(th), oc = 1.0 - cs;
-  const double Q[9] = {oc * n0 * n0 + cs,      oc * n0 * n1 - sn * n2, oc * n0 * n2 + sn * n1,
-                       oc * n1 * n0 + sn * n2, oc * n1 * n1 + cs,      oc * n1 * n2 - sn * n0,
-                       oc * n2 * n0 - sn * n1, oc * n2 * n1 + sn * n0, oc * n2 * n2 + cs};
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc)
-      o[6 + 3 * r + cc] = Q[3 * r] * in[6 + cc] + Q[3 * r + 1] * in[9 + cc] + Q[3 * r + 2] * in[12 + cc];
-}
-
-// ------------------------------------------------------------------ K5
-// dX_a = -E_a^-1 (sum_o F_ao dxi_k + dP_a), X' = X + dX  (ref :152, :260-261).  Eight lanes per
-// point, one observation per lane.  y_o = 2 Jx^T (Jc dxi_k) is RECOMPUTED from the committed point
-// and the committed camera (LDS table) instead of re-reading the 128-byte records: the kernel then
-// moves 24 B/point + 4 B/observation instead of 128 B/observation (1.7 GB -> 0.25 GB at config 3),
-// and it is evaluated as a directional derivative (obs_backsub: ~75 fp64 operations, the Jacobian rows
-// are never formed) -- the same linear map the Schur kernel assembled, implied columns included.
-// The trial cost is k_cost on the trial state (K6).
-// BT threads per block: 256, or 1024 once the camera tables (m x 28 doubles) leave room for one block per CU only
-// (beyond ~230 cameras: four waves per CU then; config 4's shard 0.47 -> see profiles/r04_m_*)
-// ROBUST: F_ao of the weighted problem is w_o times the unweighted one: y_o is scaled by sqrt(w)^2 from `sqw`.
-#define MVBA_BACKSUB_ARGS                                                                                                    \
-  long long npts, int m, const long long *__restrict__ pt_ptr, const int *__restrict__ cam_idx, const double *__restrict__ PB, \
-      const double *__restrict__ dxi, const double *__restrict__ X, const double *__restrict__ cam15, double f0,               \
-      double *__restrict__ Xt, double *__restrict__ dX, const double *__restrict__ gcam, const double *__restrict__ gdxi
-template <int G, int BT = 256, bool GCAM = false, bool ROBUST = false, typename... Robust>
-__global__ __launch_bounds__(BT) void k_backsub(MVBA_BACKSUB_ARGS, Robust... robust) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  double *s_dxi = smem, *s_cam = smem + DXI_LDS * m;
-  if (!GCAM) {
-  for (int i0 = threadIdx.x; i0 < 9 * m; i0 += 4 * blockDim.x) {  // (loads in batches of four: see k_point_inv)
-    double t[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) t[u] = dxi[min(i0 + u * (int)blockDim.x, 9 * m - 1)];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + u * (int)blockDim.x;
-      if (i < 9 * m) s_dxi[(i / 9) * DXI_LDS + i % 9] = t[u];
-    }
-  }
-  load_cams_to_lds(cam15, m, f0, s_cam);
-  __syncthreads();
-  }
-  // G lanes per point (template).  Measured with 2 / 4 / 8 lanes: config 3 (10 observations per point)
-  // 0.198 / 0.207 / 0.235 ms, config-4 shard (25 per point) 0.783 / 0.816 / 0.873 ms; one lane: 0.208
-  const int s = threadIdx.x & (G - 1), grp = threadIdx.x / G;
-  const long long a_first = (long long)blockIdx.x * (BT / G) + grp, a_step = (long long)gridDim.x * (BT / G);
-  long long nx0 = 0, nx1 = 0;  // observation range of the NEXT point of this group, requested one iteration ahead
-  if (a_first < npts) { nx0 = pt_ptr[a_first]; nx1 = pt_ptr[a_first + 1]; }
-  for (long long a = a_first; a < npts; a += a_step) {
-    const long long o0 = nx0, o1 = nx1;
-    if (a + a_step < npts) { nx0 = pt_ptr[a + a_step]; nx1 = pt_ptr[a + a_step + 1]; }
-    const double *pb = PB + PBS * a;
-    const double pb0 = pb[0], pb1 = pb[1], pb2 = pb[2], pb3 = pb[3], pb4 = pb[4], pb5 = pb[5], pb6 = pb[6], pb7 = pb[7],
-                 pb8 = pb[8];
-    const double Xa0 = X[3 * a], Xa1 = X[3 * a + 1], Xa2 = X[3 * a + 2];
-    double y0 = 0.0, y1 = 0.0, y2 = 0.0;
-    // the camera ids of this lane's first PF observations in ONE batch (unconditional loads on clamped
-    // indices: one memory latency per point instead of one per observation), the rare rest one by one
-    constexpr int PF = 4;
-    int kk[PF];
-    double sw[PF];
-    const long long olast = max(o1 - 1, o0);
-#pragma unroll
-    for (int u = 0; u < PF; ++u) kk[u] = cam_idx[min(o0 + s + G * u, olast)];
-    if constexpr (ROBUST)
-#pragma unroll
-      for (int u = 0; u < PF; ++u) sw[u] = (robust, ...).sqw[min(o0 + s + G * u, olast)];
-#pragma unroll
-    for (int u = 0; u < PF; ++u)
-      if (o0 + s + G * u < o1) {
-        double t0, t1, t2;
-        obs_backsub(Xa0, Xa1, Xa2, GCAM ? gcam + (size_t)kk[u] * CAM_LDS : s_cam + kk[u] * CAM_LDS, GCAM ? gdxi + (size_t)DXI_LDS * kk[u] : s_dxi + DXI_LDS * kk[u], f0, t0, t1, t2);
-        if constexpr (ROBUST) {
-          const double w = sw[u] * sw[u];
-          t0 *= w;
-          t1 *= w;
-          t2 *= w;
-        }
-        y0 += t0;
-        y1 += t1;
-        y2 += t2;
-      }
-    for (long long o = o0 + s + G * PF; o < o1; o += G) {
-      const int k = cam_idx[o];
-      double t0, t1, t2;
-      obs_backsub(Xa0, Xa1, Xa2, GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS, GCAM ? gdxi + (size_t)DXI_LDS * k : s_dxi + DXI_LDS * k, f0, t0, t1, t2);
-      if constexpr (ROBUST) {
-        const double so = (robust, ...).sqw[o], w = so * so;
-        t0 *= w;
-        t1 *= w;
-        t2 *= w;
-      }
-      y0 += t0;
-      y1 += t1;
-      y2 += t2;
-    }
-#pragma unroll
-    for (int msk = 1; msk < G; msk <<= 1) {  // fixed butterfly: every lane ends with the group sum
-      y0 += __shfl_xor(y0, msk, G);
-      y1 += __shfl_xor(y1, msk, G);
-      y2 += __shfl_xor(y2, msk, G);
-    }
-    if (s == 0) {
-      const double d0 = -(pb0 * y0 + pb1 * y1 + pb2 * y2) - pb6;
-      const double d1 = -(pb1 * y0 + pb3 * y1 + pb4 * y2) - pb7;
-      const double d2 = -(pb2 * y0 + pb4 * y1 + pb5 * y2) - pb8;
-      dX[3 * a] = d0; dX[3 * a + 1] = d1; dX[3 * a + 2] = d2;
-      Xt[3 * a] = Xa0 + d0; Xt[3 * a + 1] = Xa1 + d1; Xt[3 * a + 2] = Xa2 + d2;
-    }
-  }
-}
-
-// Beyond LDS_CAMERAS: the expanded camera rows (and, for the back-substitution, the padded update rows) in device memory
-__global__ void k_cam_tables(int m, const double *__restrict__ cam15, const double *__restrict__ dxi, double f0, double *__restrict__ cam18,
-                             double *__restrict__ dxi10) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= m) return;
-  expand_cam(cam15 + (size_t)k * CAM_IN, f0, cam18 + (size_t)k * CAM_LDS);
-  if (dxi) {
-    for (int i = 0; i < 9; ++i) dxi10[(size_t)k * DXI_LDS + i] = dxi[9 * (size_t)k + i];
-    dxi10[(size_t)k * DXI_LDS + 9] = 0.0;
-  }
-}
-
-// residual-only pass at a given state (initial cost, ref :85-87)
-// LOSS: sum rho(|e|^2) instead, b = lb; same grid, same tree.
-#define MVBA_COST_ARGS                                                                                                   \
-  long long nobs, int m, const double *__restrict__ cam15, const double *__restrict__ X, const int *__restrict__ obs_pt, \
-      const int *__restrict__ cam_idx, const double2 *__restrict__ xy, double f0, double *__restrict__ partials,        \
-      const double *__restrict__ gcam
-template <bool GCAM, int LOSS = LOSS_SQUARED, typename... Robust>
-__global__ __launch_bounds__(512) void k_cost(MVBA_COST_ARGS, Robust... robust) {
-  extern __shared__ __attribute__((aligned(16))) double s_cam[];
-  __shared__ double s_red[16];
-  if (!GCAM) {
-    load_cams_to_lds(cam15, m, f0, s_cam);
-    __syncthreads();
-  }
-  double cost = 0.0;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  // two dependent memory latencies per observation (its indices, then its point): the next
-  // observation's indices are requested before this one is evaluated (clamped, unconditional loads)
-  long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long olast = nobs - 1;
-  int a_n = obs_pt[min(o, olast)], k_n = cam_idx[min(o, olast)];
-  double2 z_n = xy[min(o, olast)];
-  for (; o < nobs; o += stride) {
-    const int a = a_n, k = k_n;
-    const double2 z = z_n;
-    const double X0 = X[3 * (size_t)a], X1 = X[3 * (size_t)a + 1], X2 = X[3 * (size_t)a + 2];
-    const long long on = min(o + stride, olast);
-    a_n = obs_pt[on];
-    k_n = cam_idx[on];
-    z_n = xy[on];
-    const double so = obs_cost(X0, X1, X2, GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS, z.x, z.y, f0);
-    if constexpr (LOSS != LOSS_SQUARED) cost += loss_rho<LOSS>(so, (robust, ...).b);
-    else cost += so;
-  }
-  const double t = block_sum(cost, s_red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-
-// f0 e_o -- the residual in image units -- of every observation at a given state (mvba_residuals)
-template <bool GCAM>
-__global__ __launch_bounds__(256) void k_residuals(long long nobs, int m, const double *__restrict__ cam15, const double *__restrict__ X,
-                                                   const int *__restrict__ obs_pt, const int *__restrict__ cam_idx,
-                                                   const double2 *__restrict__ xy, double f0, double2 *__restrict__ out,
-                                                   const double *__restrict__ gcam) {
-  extern __shared__ __attribute__((aligned(16))) double s_cam[];
-  if (!GCAM) {
-    load_cams_to_lds(cam15, m, f0, s_cam);
-    __syncthreads();
-  }
-  for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < nobs; o += (long long)gridDim.x * blockDim.x) {
-    const int a = obs_pt[o], k = cam_idx[o];
-    const double2 z = xy[o];
-    double e0, e1;
-    obs_resid(X[3 * (size_t)a], X[3 * (size_t)a + 1], X[3 * (size_t)a + 2], GCAM ? gcam + (size_t)k * CAM_LDS : s_cam + k * CAM_LDS,
-              z.x, z.y, f0, e0, e1);
-    out[o] = make_double2(f0 * e0, f0 * e1);
-  }
-}
-
-// out[0] = cost; the status flags ride along in the next 8 bytes so that the host needs ONE
-// 16-byte device-to-host copy per trial step.
-// `mail` (may be null): the same two words once more in pinned HOST memory, then -- behind a system-scope fence -- the
-// sequence number the host is spinning on: the cost reaches the LM loop without a copy kernel and without waking a
-// thread that sleeps in hipStreamSynchronize (~35 us between the last kernel of a step and the first of the next).
-__global__ __launch_bounds__(1024) void k_sum_partials(const double *__restrict__ partials, int n,
-                                                       double *__restrict__ out, const int *__restrict__ flag,
-                                                       double *mail, unsigned long long seq) {
-  __shared__ double s_red[16];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) v += partials[i];
-  const double t = block_sum(v, s_red);
-  if (threadIdx.x == 0) {
-    const int fl = *flag;
-    out[0] = t;
-    reinterpret_cast<int *>(out + 1)[0] = fl;
-    if (mail) {
-      mail[0] = t;
-      reinterpret_cast<int *>(mail + 1)[0] = fl;
-      __threadfence_system();
-      __hip_atomic_store(reinterpret_cast<unsigned long long *>(mail + 2), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-
-// ------------------------------------------------------------------ projection (scene side of BA)
-// x_o = K_k [R_k^T | -R_k^T t_k] [X_a; 1], inhomogeneous (ref lib/camera.py:13-14 get_camera_matrix,
-// :30-34 project_points, :74-81 calc_projected_points) for an observation list.  The 3x4 camera
-// matrices are formed once per block in LDS in the reference's order of operations (K times the
-// stacked [R^T, -R^T t]); one thread per observation, coalesced reads of the index arrays and a
-// coalesced 16-byte store.  obs_pt == nullptr: dense grid, observation o = point * m + camera.
-__global__ __launch_bounds__(256) void k_project_obs(long long nobs, int m, const double *__restrict__ X,
-                                                     const double *__restrict__ K, const double *__restrict__ R,
-                                                     const double *__restrict__ t, const int *__restrict__ obs_pt,
-                                                     const int *__restrict__ cam_idx, double2 *__restrict__ xy) {
-  extern __shared__ double sP[];  // [m][12]
-  for (int k = threadIdx.x; k < m; k += blockDim.x) {
-    const double *Kk = K + 9 * (size_t)k, *Rk = R + 9 * (size_t)k, *tk = t + 3 * (size_t)k;
-    double Rt[3][4];
-    for (int i = 0; i < 3; ++i) {
-      for (int j = 0; j < 3; ++j) Rt[i][j] = Rk[3 * j + i];
-      Rt[i][3] = -(Rt[i][0] * tk[0] + Rt[i][1] * tk[1] + Rt[i][2] * tk[2]);
-    }
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 4; ++j) sP[12 * k + 4 * i + j] = Kk[3 * i] * Rt[0][j] + Kk[3 * i + 1] * Rt[1][j] + Kk[3 * i + 2] * Rt[2][j];
-  }
-  __syncthreads();
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < nobs; o += stride) {
-    const long long a = obs_pt ? obs_pt[o] : o / m;
-    const int k = cam_idx ? cam_idx[o] : (int)(o - a * m);
-    const double *Xa = X + 3 * a, *P = sP + 12 * k;
-    const double p0 = Xa[0] * P[0] + Xa[1] * P[1] + Xa[2] * P[2] + P[3];
-    const double p1 = Xa[0] * P[4] + Xa[1] * P[5] + Xa[2] * P[6] + P[7];
-    const double p2 = Xa[0] * P[8] + Xa[1] * P[9] + Xa[2] * P[10] + P[11];
-    xy[o] = make_double2(p0 / p2, p1 / p2);
-  }
-}
-
-// ------------------------------------------------------------------ way back to the input frame (ref :242-258)
-// X <- s X R0^T + t0, t <- s t R0^T + t0, R <- R0 R on the committed state, in place: what the
-// reference's optimize() does on the host before it returns (:198-200), without moving 48 MB of
-// points across PCIe and through NumPy temporaries (8.5 ms at config 3, a quarter of a 10-iteration
-// optimize()).
-__global__ __launch_bounds__(256) void k_similarity(long long npts, int m, double *__restrict__ X, double *__restrict__ cam15,
-                                                    const double *__restrict__ T13) {
-  const double *R0 = T13, *t0 = T13 + 9;
-  const double s = T13[12];
-  const long long a = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a < npts) {
-    double *x = X + 3 * a;
-    const double x0 = s * x[0], x1 = s * x[1], x2 = s * x[2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) x[i] = x0 * R0[3 * i] + x1 * R0[3 * i + 1] + x2 * R0[3 * i + 2] + t0[i];
-  }
-  if (a < m) {
-    double *c = cam15 + (size_t)a * CAM_IN;
-    const double p0 = s * c[3], p1 = s * c[4], p2 = s * c[5];
-    double Rn[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Rn[3 * i + j] = R0[3 * i] * c[6 + j] + R0[3 * i + 1] * c[9 + j] + R0[3 * i + 2] * c[12 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c[3 + i] = p0 * R0[3 * i] + p1 * R0[3 * i + 1] + p2 * R0[3 * i + 2] + t0[i];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) c[6 + i] = Rn[i];
-  }
-}
-
-// ------------------------------------------------------------------ Schur index on the device (mvba_create)
-// The slot form's index -- every (point, camera pair) item, counting-sorted by pair with ascending points inside a
-// pair, dealt into sub-lists, then merged wave by wave into step-major rows -- built by kernels instead of 16 host
-// threads (0.7 s of a 0.83 s mvba_create at config 3).  A STABLE counting sort: wave w owns a contiguous chunk of
-// points and walks them in order, its lanes taking the items of one (point, first camera) row at a time -- distinct
-// pairs, so the wave's private histogram in LDS needs no atomics and an item's rank inside its pair is
-// [items of earlier waves] + [items of this wave so far]: exactly the position the host's sequential pass gives it.
-constexpr int IDX_WAVES = 4;  // waves per block of the counting / filling kernels (one P-int histogram each in LDS)
-
-__device__ __forceinline__ int idx_pair_id(int k, int l, int m) { return k * m - k * (k - 1) / 2 + (l - k); }
-
-// hist[w][q] = items of pair q among the points of wave w's chunk.
-// GLOBAL: the pair histogram does not fit LDS (more than ~138 cameras: 125 k pairs at 500) -- the wave counts in its
-// own row of `hist` in device memory instead (zeroed by the caller).  Same walk, same ranks; a row visit is then a
-// dependent round trip to L2 (agent-scope accesses: a later visit of the same pair, possibly from another lane of
-// this wave, must see the count), ~1-2 us per (point, first camera) row instead of ~0.1.
-template <bool GLOBAL>
-__global__ __launch_bounds__(64 * IDX_WAVES) void k_idx_count(long long N, int m, int P, const long long *__restrict__ pt_ptr,
-                                                              const int *__restrict__ cam_idx, int chunk,
-                                                              int *__restrict__ hist, const int *__restrict__ order) {
-  extern __shared__ int s_hist_all[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long w = (long long)blockIdx.x * IDX_WAVES + wv;
-  int *s_hist = GLOBAL ? hist + (size_t)w * P : s_hist_all + (size_t)wv * P;
-  if (!GLOBAL) {
-    for (int q = lane; q < P; q += 64) s_hist[q] = 0;
-    wave_sync();
-  }
-  const long long a0 = w * chunk, a1 = min(N, a0 + chunk);
-  for (long long ai = a0; ai < a1; ++ai) {
-    const long long a = order ? order[ai] : ai;  // (a sweep order of the points; mvba_create sweeps them in their natural order and passes none)
-    const long long o0 = pt_ptr[a];
-    const int d = (int)(pt_ptr[a + 1] - o0);
-    for (int i = 0; i < d; ++i) {
-      const int k = cam_idx[o0 + i];
-      for (int j = i + lane; j < d; j += 64) {  // distinct pairs per instruction
-        int *c = s_hist + idx_pair_id(k, cam_idx[o0 + j], m);
-        if (GLOBAL) __hip_atomic_store(c, __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *c += 1;
-      }
-      wave_sync();
-    }
-  }
-  if (!GLOBAL)
-    for (int q = lane; q < P; q += 64) hist[(size_t)w * P + q] = s_hist[q];
-}
-
-// exclusive prefix over the waves, per pair (in place); cnt[q] = total
-__global__ void k_idx_scan(int P, int n_waves, int *__restrict__ hist, long long *__restrict__ cnt) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= P) return;
-  long long run = 0;
-  for (int w = 0; w < n_waves; ++w) {
-    const int v = hist[(size_t)w * P + q];
-    hist[(size_t)w * P + q] = (int)run;
-    run += v;
-  }
-  cnt[q] = run;
-}
-
-// the same walk again: item r of pair q goes to sub-list r % S[q], position r / S[q] (the host's dealing)
-// (GLOBAL: the running ranks live in the wave's row of `hist` itself, which the scan has turned into start ranks)
-template <bool GLOBAL>
-__global__ __launch_bounds__(64 * IDX_WAVES) void k_idx_fill(long long N, int m, int P, const long long *__restrict__ pt_ptr,
-                                                             const int *__restrict__ cam_idx, int chunk,
-                                                             int *__restrict__ hist, const int *__restrict__ S,
-                                                             const int *__restrict__ vp_ptr, const long long *__restrict__ vp_off,
-                                                             int *__restrict__ it_k, int *__restrict__ it_l, int *__restrict__ it_a,
-                                                             const int *__restrict__ order) {
-  extern __shared__ int s_hist_all[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long w = (long long)blockIdx.x * IDX_WAVES + wv;
-  int *s_rank = GLOBAL ? hist + (size_t)w * P : s_hist_all + (size_t)wv * P;
-  if (!GLOBAL) {
-    for (int q = lane; q < P; q += 64) s_rank[q] = hist[(size_t)w * P + q];  // items of earlier waves
-    wave_sync();
-  }
-  const long long a0 = w * chunk, a1 = min(N, a0 + chunk);
-  for (long long ai = a0; ai < a1; ++ai) {
-    const long long a = order ? order[ai] : ai;
-    const long long o0 = pt_ptr[a];
-    const int d = (int)(pt_ptr[a + 1] - o0);
-    for (int i = 0; i < d; ++i) {
-      const int k = cam_idx[o0 + i];
-      for (int j = i + lane; j < d; j += 64) {
-        const int q = idx_pair_id(k, cam_idx[o0 + j], m);
-        int r;
-        if (GLOBAL) {
-          r = __hip_atomic_load(s_rank + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(s_rank + q, r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          r = s_rank[q];
-          s_rank[q] = r + 1;
-        }
-        const int sq = S[q];
-        const long long pos = vp_off[vp_ptr[q] + (r % sq)] + r / sq;
-        it_k[pos] = (int)(o0 + i);
-        it_l[pos] = (int)(o0 + j);
-        it_a[pos] = (int)a;
-      }
-      wave_sync();
-    }
-  }
-}
-
-// lo[v][r] = first item of list v whose point is >= range_lo[r]  (r = 0 .. nR: the last column is the list's end)
-__global__ void k_idx_bounds(int VP, int nR, const long long *__restrict__ vp_off, const long long *__restrict__ range_lo,
-                             const int *__restrict__ it_a, long long *__restrict__ lo, const int *__restrict__ rank) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long long)VP * (nR + 1)) return;
-  const int v = (int)(t / (nR + 1)), r = (int)(t - (long long)v * (nR + 1));
-  long long b = vp_off[v], e = vp_off[v + 1];
-  const long long key = range_lo[r];
-  while (b < e) {  // lower_bound
-    const long long mid = (b + e) >> 1;
-    if ((rank ? rank[it_a[mid]] : it_a[mid]) < key) b = mid + 1;  // (a list is ascending in sweep order; ranges are contiguous in it)
-    else e = mid;
-  }
-  lo[t] = b;
-}
-
-// The bounded-skew merge of one wave's W lists (W = 21: k_schur_slots, 64: k_schur_lanes), lane = slot.  FILL = false: count the
-// steps.  FILL = true: write the step-major rows (record indices RELATIVE to the range's first observation), the pacing table
-// (steps taken when the slowest slot leaves a segment) and the padding rows (`pad_obs` = 0: the range's first record,
-// any finite one will do, times `pad_pt` = N: the all-zero point row).
-template <bool FILL, int W>
-__global__ __launch_bounds__(64) void k_idx_merge(long long n_waves, int nR, int nSeg, long long skew, long long segG,
-                                                  const long long *__restrict__ sl_beg, const int *__restrict__ sl_len,
-                                                  const long long *__restrict__ range_o0, const int *__restrict__ it_k,
-                                                  const int *__restrict__ it_l, const int *__restrict__ it_a,
-                                                  const long long *__restrict__ w_beg, int pad_obs, int pad_pt,
-                                                  int *__restrict__ w_steps, int *__restrict__ st_k, int *__restrict__ st_l,
-                                                  int *__restrict__ st_a, int *__restrict__ seg_end, const long long *__restrict__ pkey) {
-  static_assert(W >= 1 && W <= 64, "one lane per slot");
-  const long long b = blockIdx.x;
-  const int lane = threadIdx.x;
-  const bool slot = lane < W;
-  long long cur = slot ? sl_beg[b * W + lane] : 0;
-  const long long end = slot ? cur + sl_len[b * W + lane] : 0;
-  const long long o_lo = range_o0[b % nR];
-  const long long base = FILL ? w_beg[b] : 0;
-  constexpr long long NONE = 1LL << 40;
-  int steps = 0, sg = 0;
-  // an item's key = where its point sits in the sweep, in observations (pkey[a] = observations of the points swept
-  // before a; with the natural order that is a's first observation); the k-side record index is what goes into the row
-  // two keys ahead in registers: the next step's key never waits for a load issued in this step
-  auto key_at = [&](long long c) -> long long { return pkey[it_a[c]]; };
-  long long k0 = cur < end ? key_at(cur) : NONE, k1 = cur + 1 < end ? key_at(cur + 1) : NONE;
-  while (true) {
-    long long lo = k0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) lo = min(lo, __shfl_xor(lo, off, 64));
-    if (FILL && lo < NONE && lane == 0)
-      while (sg < nSeg && lo >= o_lo + (sg + 1) * segG) seg_end[b * nSeg + sg++] = steps;
-    if (lo >= NONE) break;
-    const bool take = k0 < NONE && k0 <= lo + skew;
-    if (FILL && slot) {
-      const long long o = (base + steps) * W + lane;
-      st_k[o] = take ? (int)(it_k[cur] - o_lo) : pad_obs;  // record indices relative to the range's first observation
-      st_l[o] = take ? (int)(it_l[cur] - o_lo) : pad_obs;
-      st_a[o] = take ? it_a[cur] : pad_pt;
-    }
-    if (take) {
-      ++cur;
-      k0 = k1;
-      k1 = cur + 1 < end ? key_at(cur + 1) : NONE;
-    }
-    ++steps;
-  }
-  if (FILL) {
-    if (lane == 0)
-      while (sg < nSeg) seg_end[b * nSeg + sg++] = steps;
-  } else if (lane == 0) {
-    w_steps[b] = steps;
-  }
-}
-
-// the slot kernels' index: one row of `row` ints per step, k[W] | l[W] | a[W] | pad -- ONE LDS-DMA instruction per step
-// (W = 21: 64 ints = 256 bytes with 1 int of padding; W = 64: 192 ints = 768 bytes)
-__global__ void k_idx_interleave(long long n_steps, int W, int row, const int *__restrict__ st_k, const int *__restrict__ st_l,
-                                 const int *__restrict__ st_a, int *__restrict__ out) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_steps * row) return;
-  const long long st = t / row;
-  const int e = (int)(t - st * row), which = e / W, sl = e - which * W;
-  const int *src = which == 0 ? st_k : (which == 1 ? st_l : st_a);
-  out[t] = which < 3 ? src[st * W + sl] : 0;
-}
-
+#include "mvba_tail.h"       // K5, K6 and the state kernels: k_backsub, k_cost, k_update_cams, k_cam_tables, k_residuals, ...
+#include "mvba_index.h"      // the Schur index on the device: k_idx_*
 #include "mvba_cov.h"  // marginal covariances (mvba_covariance): S^-1 from the Cholesky factor and the point pass
 #include "mvba_map.h"  // parameter maps (mvba_set_parameter_map): the mapped gather into K4 and the way back
 
@@ -2307,16 +545,31 @@ void mvba_destroy(mvba_handle *h) {
   delete h;
 }
 
-int mvba_set_params(mvba_handle *h, const double *X, const double *f, const double *u, const double *t, const double *R) {
-  if (!h || !X || !f || !u || !t || !R) return fail(MVBA_ERR_BADARG, "null argument");
-  MVBA_HIP(hipSetDevice(h->device));
-  std::vector<double> cam((size_t)h->m * CAM_IN);
-  for (int k = 0; k < h->m; ++k) {
-    double *c = cam.data() + (size_t)k * CAM_IN;
+// ---- cam15, the engine's camera row: f | u (2) | t (3) | R (9, row-major) -- to and from the C interface's arrays
+namespace {
+void pack_cam15(int m, const double *f, const double *u, const double *t, const double *R, double *cam /*[m][CAM_IN]*/) {
+  for (int k = 0; k < m; ++k) {
+    double *c = cam + (size_t)k * CAM_IN;
     c[0] = f[k]; c[1] = u[2 * k]; c[2] = u[2 * k + 1];
     for (int i = 0; i < 3; ++i) c[3 + i] = t[3 * k + i];
     for (int i = 0; i < 9; ++i) c[6 + i] = R[9 * k + i];
   }
+}
+void unpack_cam15(const double *cam /*[m][CAM_IN]*/, int m, double *f, double *u, double *t, double *R) {
+  for (int k = 0; k < m; ++k) {
+    const double *c = cam + (size_t)k * CAM_IN;
+    f[k] = c[0]; u[2 * k] = c[1]; u[2 * k + 1] = c[2];
+    for (int i = 0; i < 3; ++i) t[3 * k + i] = c[3 + i];
+    for (int i = 0; i < 9; ++i) R[9 * k + i] = c[6 + i];
+  }
+}
+}  // namespace
+
+int mvba_set_params(mvba_handle *h, const double *X, const double *f, const double *u, const double *t, const double *R) {
+  if (!h || !X || !f || !u || !t || !R) return fail(MVBA_ERR_BADARG, "null argument");
+  MVBA_HIP(hipSetDevice(h->device));
+  std::vector<double> cam((size_t)h->m * CAM_IN);
+  pack_cam15(h->m, f, u, t, R, cam.data());
   MVBA_HIP(hipMemcpyAsync(h->d_X[h->cur], X, sizeof(double) * 3 * h->N, hipMemcpyHostToDevice, h->stream));
   MVBA_HIP(hipMemcpyAsync(h->d_cam15[h->cur], cam.data(), sizeof(double) * cam.size(), hipMemcpyHostToDevice, h->stream));
   MVBA_HIP(hipStreamSynchronize(h->stream));
@@ -2332,12 +585,7 @@ int mvba_get_params(mvba_handle *h, double *X, double *f, double *u, double *t, 
   MVBA_HIP(hipMemcpyAsync(X, h->d_X[h->cur], sizeof(double) * 3 * h->N, hipMemcpyDeviceToHost, h->stream));
   MVBA_HIP(hipMemcpyAsync(cam.data(), h->d_cam15[h->cur], sizeof(double) * cam.size(), hipMemcpyDeviceToHost, h->stream));
   MVBA_HIP(hipStreamSynchronize(h->stream));
-  for (int k = 0; k < h->m; ++k) {
-    const double *c = cam.data() + (size_t)k * CAM_IN;
-    f[k] = c[0]; u[2 * k] = c[1]; u[2 * k + 1] = c[2];
-    for (int i = 0; i < 3; ++i) t[3 * k + i] = c[3 + i];
-    for (int i = 0; i < 9; ++i) R[9 * k + i] = c[6 + i];
-  }
+  unpack_cam15(cam.data(), h->m, f, u, t, R);
   return MVBA_OK;
 }
 
@@ -2855,7 +1103,7 @@ int mvba_residuals(mvba_handle *h, double *e) {
     int rc = h->mem.alloc(&h->d_resid, h->nobs);
     if (rc) return rc;
   }
-  const size_t lds = h->gcam ? 0 : (size_t)h->m * CAM_LDS * sizeof(double);
+  const size_t lds = cam_lds_bytes(h->m, h->gcam, false);
   cam_tables(h, h->d_cam15[h->cur], nullptr);
   const unsigned grid = (unsigned)std::min<long long>(4096, (h->nobs + 255) / 256);
   hipLaunchKernelGGL(h->gcam ? k_residuals<true> : k_residuals<false>, dim3(grid), dim3(256), lds, h->stream, h->nobs, h->m,
@@ -3015,21 +1263,21 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
 namespace {
 constexpr int SNAP_SLAB = 8;  // log entries per device allocation
 size_t snap_stride(const mvba_handle *h) { return (3 * (size_t)h->N + (size_t)CAM_IN * h->m + 1) & ~(size_t)1; }
+// log entry i: points [3 N], then cameras [m][CAM_IN] (its slab must exist)
+double *snap_entry(const mvba_handle *h, long long i) { return h->snap_slabs[(size_t)(i / SNAP_SLAB)] + snap_stride(h) * (size_t)(i % SNAP_SLAB); }
 }  // namespace
 
 int mvba_snapshot(mvba_handle *h) {
   if (!h) return fail(MVBA_ERR_BADARG, "null handle");
   if (!h->have_params) return fail(MVBA_ERR_STATE, "no parameters set");
   MVBA_HIP(hipSetDevice(h->device));
-  const size_t stride = snap_stride(h);
-  const size_t slab = (size_t)(h->n_snap / SNAP_SLAB);
-  if (slab >= h->snap_slabs.size()) {
+  if ((size_t)(h->n_snap / SNAP_SLAB) >= h->snap_slabs.size()) {
     double *p = nullptr;
-    int rc = h->mem.alloc(&p, stride * SNAP_SLAB);
+    int rc = h->mem.alloc(&p, snap_stride(h) * SNAP_SLAB);
     if (rc) return rc;
     h->snap_slabs.push_back(p);
   }
-  double *dst = h->snap_slabs[slab] + stride * (size_t)(h->n_snap % SNAP_SLAB);
+  double *dst = snap_entry(h, h->n_snap);
   // same stream as the kernels: ordered after everything that wrote the committed state and before whatever
   // overwrites it; the host does not wait
   MVBA_HIP(hipMemcpyAsync(dst, h->d_X[h->cur], sizeof(double) * 3 * h->N, hipMemcpyDeviceToDevice, h->stream));
@@ -3048,17 +1296,12 @@ int mvba_snapshot_read(mvba_handle *h, int64_t i, double *X, double *f, double *
   if (!h || !X || !f || !u || !t || !R) return fail(MVBA_ERR_BADARG, "null argument");
   if (i < 0 || i >= h->n_snap) return fail(MVBA_ERR_BADARG, "no such log entry");
   MVBA_HIP(hipSetDevice(h->device));
-  const double *src = h->snap_slabs[(size_t)(i / SNAP_SLAB)] + snap_stride(h) * (size_t)(i % SNAP_SLAB);
+  const double *src = snap_entry(h, i);
   std::vector<double> cam((size_t)h->m * CAM_IN);
   MVBA_HIP(hipMemcpyAsync(X, src, sizeof(double) * 3 * h->N, hipMemcpyDeviceToHost, h->stream));
   MVBA_HIP(hipMemcpyAsync(cam.data(), src + 3 * h->N, sizeof(double) * cam.size(), hipMemcpyDeviceToHost, h->stream));
   MVBA_HIP(hipStreamSynchronize(h->stream));
-  for (int k = 0; k < h->m; ++k) {
-    const double *c = cam.data() + (size_t)k * CAM_IN;
-    f[k] = c[0]; u[2 * k] = c[1]; u[2 * k + 1] = c[2];
-    for (int q = 0; q < 3; ++q) t[3 * k + q] = c[3 + q];
-    for (int q = 0; q < 9; ++q) R[9 * k + q] = c[6 + q];
-  }
+  unpack_cam15(cam.data(), h->m, f, u, t, R);
   return MVBA_OK;
 }
 
@@ -3066,7 +1309,7 @@ int mvba_snapshot_restore(mvba_handle *h, int64_t i) {
   if (!h) return fail(MVBA_ERR_BADARG, "null handle");
   if (i < 0 || i >= h->n_snap) return fail(MVBA_ERR_BADARG, "no such log entry");
   MVBA_HIP(hipSetDevice(h->device));
-  const double *src = h->snap_slabs[(size_t)(i / SNAP_SLAB)] + snap_stride(h) * (size_t)(i % SNAP_SLAB);
+  const double *src = snap_entry(h, i);
   // what mvba_set_params does, from device memory: the committed state is replaced, linearisation and trial are void
   MVBA_HIP(hipMemcpyAsync(h->d_X[h->cur], src, sizeof(double) * 3 * h->N, hipMemcpyDeviceToDevice, h->stream));
   MVBA_HIP(hipMemcpyAsync(h->d_cam15[h->cur], src + 3 * h->N, sizeof(double) * CAM_IN * h->m, hipMemcpyDeviceToDevice, h->stream));

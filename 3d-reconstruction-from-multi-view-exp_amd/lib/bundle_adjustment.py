@@ -9,7 +9,7 @@ What stays in Python, exactly as the reference does it:
     (strict), ``c *= s`` / ``c /= s``, stop on ``|dE| <= tol`` or ``max_iter``,
     the per-iteration print and the debug log (:100-195).
 Everything numerical per observation / point / reduced system runs in
-``libmvba.so`` (hand-written HIP, see csrc/mvba.hip) through ``_mvba.HipEngine``.
+``libmvba.so`` (hand-written HIP, see csrc/mvba.hip and its kernel headers csrc/mvba_*.h) through ``_mvba.HipEngine``.
 There is no CPU fallback.
 """
 from __future__ import annotations

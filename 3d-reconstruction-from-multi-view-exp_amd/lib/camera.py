@@ -44,7 +44,7 @@ def calc_projected_points(X, K, R, t):
 
 
 def calc_projected_points_gpu(X, K, R, t, device=-1):
-    """``calc_projected_points`` on the MI355X (``mvba_project``, csrc/mvba.hip): same list of (N,2)
+    """``calc_projected_points`` on the MI355X (``mvba_project``, k_project_obs in csrc/mvba_tail.h): same list of (N,2)
     arrays, one launch for the whole (point, camera) grid."""
     from ._mvba import project
 

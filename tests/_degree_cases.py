@@ -3,7 +3,8 @@ tests/_visibility_cases.py (test_degree_cases_cpu.py proves their regimes on the
   tall  a few points seen by 64 .. 300 cameras in a sea of band points of degree 2 .. 5: K1's split tiles beside packed ones,
         and the kernels that are sized by the MEAN degree (K5 at two lanes per point, k_point_cov at eight) on an outlier
   wide  iid visibility with a mean degree above 40 and above 100 at every block size of K5
-The selection rules of csrc/mvba.hip and csrc/mvba_create.h are restated here in NumPy.  Test infrastructure only."""
+The selection rules of csrc/mvba.hip (the launch side; the kernels are in csrc/mvba_linearize.h and csrc/mvba_tail.h) and
+csrc/mvba_create.h are restated here in NumPy.  Test infrastructure only."""
 import functools
 
 import numpy as np
@@ -54,6 +55,14 @@ WIDE = {  # name: (n, m, p); the K5 cell of each: K5_CELL below
     "wide_200x647_10": (200, 647, 0.1),  # 85 of its 200 points are split: a second mixed tile layout
 }
 CASES = tuple(TALL) + tuple(WIDE)
+# iid scenes for the robust twins alone (ROBUST_CASES below), kept out of CASES: the robust (G, bt) cells of k_backsub that no
+# case above reaches with a Huber twin inside ROBUST_SELF_DIFF_BOUND (tall_6000x300 gives 1.12e-11, wide_80x400_20 1.04e-11)
+ROBUST_WIDE = {  # name: (n, m, p); point degrees, fewest observations of a camera
+    "wide_60x90_60": (60, 90, 0.6),     # 43 .. 65, 26
+    "wide_300x200_10": (300, 200, 0.1),  # 8 .. 33, 19
+    "wide_300x400_05": (300, 400, 0.05),  # 10 .. 34, 5
+    "wide_120x400_15": (120, 400, 0.15),  # 41 .. 77, 7
+}
 MIN_CAMERA_DEGREE = 5  # the undamped reduced system (covariance) wants a few observations per camera
 
 
@@ -65,7 +74,7 @@ def case(name):
         n, m, tall, w, w_min = TALL[name]
         keep = tall_mask(n, m, tall, w, w_min)
     else:
-        n, m, p = WIDE[name]
+        n, m, p = WIDE[name] if name in WIDE else ROBUST_WIDE[name]
         keep = wide_mask(n, m, p)
     sc = make_scene(n, m, vis_p=1.0, project="numpy")
     out = (sc,) + V.masked(sc, keep)
@@ -115,7 +124,8 @@ def tile_ranges(tiles):
     return start[:-1], start[1:], tiles[:-1] < 0
 
 
-# ---------------------------------------------------------------- csrc/mvba.hip: the width rules, restated
+# ---------------------------------------------------------------- csrc/mvba.hip (launch_tail_and_cost, mvba_covariance;
+# LDS_CAMERAS: csrc/mvba_device.h): the width rules, restated
 CAM_LDS, DXI_LDS, LDS_CAMERAS = 18, 10, 646
 K5_G_LIMITS = (40.0, 100.0)       # mean degree: two lanes per point up to 40, four up to 100, eight beyond
 COV_G_LIMITS = (12.0, 24.0, 48.0)  # mean pair count 0.5 d (d + 1): 8 lanes up to 12, 16 up to 24, 32 up to 48, 64 beyond
@@ -144,6 +154,7 @@ K5_CELL = {  # what every case must reach (test_degree_cases_cpu.py asserts it f
     "wide_40x110": (8, 256), "wide_60x200_60": (8, 512), "wide_60x400_35": (8, 1024), "wide_80x647_20": (8, GCAM),
     "wide_60x200_35": (4, 512), "wide_80x400_20": (4, 1024), "wide_200x647_10": (4, GCAM),
 }
+ROBUST_WIDE_K5_CELL = {"wide_60x90_60": (4, 256), "wide_300x200_10": (2, 512), "wide_300x400_05": (2, 1024), "wide_120x400_15": (4, 1024)}
 ALL_K5_CELLS = {(G, bt) for G in (2, 4, 8) for bt in (256, 512, 1024, GCAM)}
 # The iid scenes (n, m, vis_p) of tests/test_gpu_parity.py that reach the cells these families do not: (90, 70, 1.0) is the
 # only one with four lanes, the two of test_extreme_camera_counts_vs_oracle have two lanes at 1024 threads and with GCAM
@@ -193,7 +204,10 @@ def problem(name, xy=None):
             sc.init_K[:, :2, 2], t, R)
 
 
-ROBUST_CASES = ("tall_2000x130", "wide_40x110", "wide_80x647_20", "wide_60x200_35")
+# Every robust (G, bt) cell of k_backsub but (2, 256) and (2, GCAM), which tests/test_gpu_robust.py runs: K5_CELL and
+# ROBUST_WIDE_K5_CELL name the cell of each.
+ROBUST_CASES = ("tall_2000x130", "wide_40x110", "wide_80x647_20", "wide_60x200_35", "wide_60x200_60", "wide_60x400_35",
+                "wide_200x647_10") + tuple(ROBUST_WIDE)
 ROBUST_LOSSES = (("huber", 3.0), ("cauchy", 2.0))
 
 
@@ -220,8 +234,9 @@ def reversed_inside_points(pt_ptr, *per_obs):
 # update of wide_80x647_20 reaches 139 (radians, among others), the trial cost is 14 x the cost it started from, and the
 # ORACLE's trial cost differs from its own by 7.2e-10 relative when the sums inside every point are taken in reversed order --
 # at _check_step's bound of 1e-9, with dX equal to 3e-14.  At 1e-2 the same figure is 7.4e-12 (tall_2000x130 3.9e-12,
-# wide_40x110 5.6e-13, wide_60x200_35 6.7e-14, every Cauchy twin below 1e-15): 100 x below the bound, which
-# test_degree_cases_cpu.py asserts for every twin.
+# wide_40x110 5.6e-13, wide_60x200_35 6.7e-14, wide_60x200_60 2.9e-15, wide_60x400_35 3.8e-13, wide_200x647_10 3.7e-12,
+# wide_60x90_60 5.0e-12, wide_300x200_10 2.5e-13, wide_300x400_05 1.0e-12, wide_120x400_15 6.4e-14, every Cauchy twin below
+# 1e-15): 100 x below the bound, which test_degree_cases_cpu.py asserts for every twin.
 ROBUST_C = 1e-2
 ROBUST_SELF_DIFF_BOUND = 1e-11
 MARGIN = 100.0  # a GPU assert gets MARGIN x the host-versus-host figure of its case (tests/_init_cases.py)

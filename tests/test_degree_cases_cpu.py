@@ -1,6 +1,6 @@
 """The degree families of tests/_degree_cases.py reach the code they are named for -- K1's split tiles in every layout, every
 (lanes, block) cell of K5, k_point_cov at eight lanes on points of thousands of pairs -- shown on the host from the case's
-observation list and the restated rules of csrc/mvba_create.h and csrc/mvba.hip alone; the oracle's damped reduced system on
+observation list and the restated rules of csrc/mvba_create.h and csrc/mvba.hip (the launch side) alone; the oracle's damped reduced system on
 them is positive definite; and the figures the GPU margins of tests/test_gpu_degree.py are 100 x of are re-measured here."""
 import numpy as np
 import pytest
@@ -174,6 +174,19 @@ def test_every_case_reaches_its_k5_cell_and_covariance_width():
     assert D.cov_lanes(4400, 40) == 64  # wide_40x110
     # the camera counts sit where the issue puts them: 256 threads up to 182 cameras, 512 up to 365, 1024 up to 646
     assert [D.k5_cell(10, 1, m)[1] for m in (182, 183, 365, 366, 646, 647)] == [256, 512, 512, 1024, 1024, D.GCAM]
+
+
+def test_robust_only_scenes_reach_their_k5_cells_and_leave_every_camera_enough():
+    """The scenes of ROBUST_WIDE, from their observation lists: the (G, bt) cell of k_backsub each is there for, and every
+    camera with MIN_CAMERA_DEGREE observations.  With them ROBUST_CASES and the two cells of tests/test_gpu_robust.py cover
+    all twelve."""
+    for name, cell in D.ROBUST_WIDE_K5_CELL.items():
+        n, m, pt_ptr, cam, _ = _lists(name)
+        assert (n, m) == D.ROBUST_WIDE[name][:2] and D.k5_cell(len(cam), n, m) == cell, name
+        assert np.bincount(cam, minlength=m).min() >= D.MIN_CAMERA_DEGREE, name
+    assert set(D.ROBUST_WIDE_K5_CELL) == set(D.ROBUST_WIDE) and not set(D.ROBUST_WIDE) & set(D.CASES)
+    cells = {{**D.K5_CELL, **D.ROBUST_WIDE_K5_CELL}[name] for name in D.ROBUST_CASES}
+    assert cells | {(2, 256), (2, D.GCAM)} == D.ALL_K5_CELLS
 
 
 def test_mean_degrees_are_five_percent_clear_of_every_threshold():

@@ -245,7 +245,7 @@ def test_affine_driver_runs(golden, capsys):
 
 
 def test_device_projection_matches_lib_camera(golden):
-    """mvba_project (csrc/mvba.hip k_project_obs) vs the host camera model on the reference's own
+    """mvba_project (csrc/mvba_tail.h k_project_obs) vs the host camera model on the reference's own
     default scene: the fixture's noise-free projections x_clean were produced by the reference's
     calc_projected_points (ref lib/camera.py:74-81); dense grid and observation-list forms."""
     from lib import _mvba

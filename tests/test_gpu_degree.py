@@ -13,17 +13,23 @@ What each test is the first to run:
                                         the point inverse of a point cut into pieces
   test_*_index_built_on_the_device...   k_idx_count / k_idx_fill's row loop beyond two trips (rows of 65 .. 300), with the
                                         histogram in LDS and in device memory (300 cameras: device memory by itself)
-  test_robust_twins                     robust k_resid_jac on split tiles; k_backsub<8, 256, false, true>,
-                                        k_backsub<8, 256, true, true>, k_backsub<4, 512, false, true> (the prefetch of sqw on
-                                        clamped indices at widths 4 and 8)
+  test_robust_twins                     robust k_resid_jac on split tiles; the robust k_backsub<G, bt, GCAM, true> at every
+                                        (G, bt) but (2, 256) and (2, GCAM) (the prefetch of sqw on clamped indices at widths
+                                        2, 4 and 8; the table below has the case of each cell)
   test_covariance                       k_point_cov<8> on points of 3 240 / 8 515 pairs (the sqrt pair decode far from the
                                         pair counts it is sized for), k_point_cov<64> at degree 110
   test_held_points_on_split_tiles       k_point_inv with a mask over points whose sums come from k_sum_split
   test_engine_triangulation_...         k_triangulate's per-point loops at degree 300 inside the engine
   test_two_engines_... / test_short_... run-to-run identity and five LM iterations of all of the above
 
-Robust (G, bt) cells of k_backsub NOT run, here or in tests/test_gpu_robust.py: (4, 256), (4, 1024), (4, GCAM), (8, 512),
-(8, 1024) and (2, 512), (2, 1024).  Run: (2, 256) and (2, GCAM) by tests/test_gpu_robust.py, (8, 256), (8, GCAM), (4, 512) here."""
+Every robust (G, bt) cell of k_backsub is run, by the case of test_robust_twins named here (the last four are the iid scenes
+of _degree_cases.ROBUST_WIDE, which only the robust twins use) or by tests/test_gpu_robust.py:
+  bt        G = 2                         G = 4                 G = 8
+  256       tests/test_gpu_robust.py      wide_60x90_60         wide_40x110
+            (and tall_2000x130)
+  512       wide_300x200_10               wide_60x200_35        wide_60x200_60
+  1024      wide_300x400_05               wide_120x400_15       wide_60x400_35
+  GCAM      tests/test_gpu_robust.py      wide_200x647_10       wide_80x647_20"""
 import functools
 
 import numpy as np
