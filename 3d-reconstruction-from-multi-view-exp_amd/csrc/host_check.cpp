@@ -1,5 +1,5 @@
 // The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas) and the host logic of a RANSAC
-// round (mvba_ransac_host.h: rs_pick, rs_accept, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
+// round (mvba_ransac_host.h: rs_pick, rs_accept, rs_current and rs_other, RsTile, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
 // builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify) and the matcher's (mvba_match_host.h: its argument
 // checks, the chunk rule, the ratio test) on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
@@ -168,6 +168,102 @@ int main() {
     st = RS_OK | RS_ACTIVE | RS_CUR; n_active = 2;
     rs_stop(st, n_active);
     CHECK(st == (RS_OK | RS_CUR) && n_active == 1);
+  }
+  {  // the two mask buffers under the state: the first mask goes to buffer 0, a toggle makes it current, a refit writes the other
+    unsigned char b0[1], b1[1];
+    const unsigned char *c0 = b0, *c1 = b1;
+    const int nine[1] = {9};
+    int st = rs_pick(nine, 1, 9, 8).state;
+    CHECK(rs_other(st, b0, b1) == b0 && rs_current(st, c0, c1) == c1);
+    st ^= RS_CUR;
+    CHECK(rs_current(st, b0, b1) == b0 && rs_other(st, b0, b1) == b1 && rs_current(st, c0, c1) == c0);
+    int n_active = 1;
+    CHECK(rs_accept(9, 9, 0, 0, st, n_active) && rs_current(st, b0, b1) == b1 && rs_other(st, b0, b1) == b0);  // kept: the other became current
+    CHECK(!rs_accept(8, 9, 1, 0, st, n_active) && rs_current(st, b0, b1) == b1);                                 // stopped: it stays
+  }
+  {  // RsTile: a tile of four items with the statuses 1, 2, 4 and 0, three hypotheses each
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const int ON = RS_OK | RS_ACTIVE | RS_CUR;
+    const int H = 3, hc[12] = {-1, -1, -1, -1, -1, -1, -1, 5, 4, 7, 9, 9}, n_item[4] = {5, 100, 100, 100};
+    int32_t status[5], best[5], hyp_count[15];
+    int64_t n_it[5], n_inl[5];
+    double quality[10];
+    for (int g = 0; g < 5; ++g) { status[g] = best[g] = 77; n_it[g] = n_inl[g] = 77; quality[2 * g] = quality[2 * g + 1] = 77.0; }
+    for (int &c : hyp_count) c = 77;
+    RsTile::defaults(5, H, status, best, hyp_count, n_it, n_inl, quality);
+    for (int g = 0; g < 5; ++g)
+      CHECK(status[g] == 1 && best[g] == -1 && n_it[g] == 0 && n_inl[g] == 0 && std::isnan(quality[2 * g]) && std::isnan(quality[2 * g + 1]));
+    for (int c : hyp_count) CHECK(c == -1);
+    RsTile t(4);
+    int state[4] = {77, 77, 77, 77};
+    t.pick(4, state, hc, H, n_item, 6);
+    const int want_st[4] = {1, 2, 4, 0}, want_best[4] = {-1, -1, 1, 1}, want_state[4] = {0, 0, 0, ON};
+    for (int p = 0; p < 4; ++p) CHECK(t.st[p] == want_st[p] && t.best[p] == want_best[p] && state[p] == want_state[p]);
+    const double S2[8] = {nan, nan, nan, nan, nan, nan, 9.0, 36.0};  // (the mask pass sums nothing for an item that is out)
+    int calls = 0;
+    CHECK(t.first(S2, [&](int p) { ++calls; CHECK(p == 3); return 0; }) == 1 && calls == 1 && t.n_active == 1);
+    CHECK(state[0] == 0 && state[1] == 0 && state[2] == 0 && state[3] == (RS_OK | RS_ACTIVE) && t.nin[3] == 9 && t.ssq[3] == 36.0);
+    calls = 0;
+    t.write(1, status, best, hyp_count, n_inl, quality, [&](int p) { ++calls; CHECK(p == 3); return 0.25; });  // the tile starts at item 1
+    CHECK(calls == 1 && status[0] == 1 && best[0] == -1 && hyp_count[0] == -1);  // (item 0 is not the tile's)
+    for (int p = 0; p < 4; ++p) {
+      CHECK(status[1 + p] == want_st[p] && best[1 + p] == want_best[p]);
+      for (int h = 0; h < H; ++h) CHECK(hyp_count[(1 + p) * H + h] == hc[p * H + h]);
+      if (p < 3) CHECK(n_inl[1 + p] == 0 && std::isnan(quality[2 * (1 + p)]) && std::isnan(quality[2 * (1 + p) + 1]));  // the defaults stay
+    }
+    CHECK(n_inl[4] == 9 && quality[8] == 2.0 && quality[9] == 0.25);
+
+    // a finish that fails for one of two items of status 0: it is out with finish's status, the other goes on
+    const int hc2[6] = {8, 3, 1, 2, 9, 9}, n2[2] = {50, 50};
+    int state2[2];
+    RsTile u(3);  // (a tile may be shorter than the one the vectors were made for)
+    u.pick(2, state2, hc2, H, n2, 6);
+    CHECK(u.st[0] == 0 && u.st[1] == 0 && u.best[0] == 0 && u.best[1] == 1 && state2[0] == ON && state2[1] == ON);
+    const double S2b[4] = {8.0, 2.0, 9.0, 4.5};
+    CHECK(u.first(S2b, [](int p) { return p == 0 ? 2 : 0; }) == 1);
+    CHECK(u.st[0] == 2 && state2[0] == 0 && u.st[1] == 0 && state2[1] == (RS_OK | RS_ACTIVE) && u.nin[1] == 9);
+    int kept = 0;
+    u.accept(0, std::vector<double>{nan, nan, 9.0, 4.0}.data(), 0, [&](int p) { ++kept; CHECK(p == 1); });  // item 0 is not asked again
+    CHECK(kept == 1 && state2[0] == 0 && u.n_active == 1);
+
+    // accept: an equal count is kept and the buffer toggles; one fewer stops on the buffer it had
+    u.pick(2, state2, hc2, H, n2, 6);
+    CHECK(u.first(S2b, [](int) { return 0; }) == 2);
+    kept = 0;
+    u.accept(0, std::vector<double>{8.0, 1.0, 8.0, 1.0}.data(), 0, [&](int p) { ++kept; CHECK(p == 0); });
+    CHECK(kept == 1 && u.n_active == 1 && state2[0] == ON && u.nin[0] == 8 && u.ssq[0] == 1.0);
+    CHECK(state2[1] == RS_OK && u.nin[1] == 9 && u.ssq[1] == 4.5);
+    u.accept(1, std::vector<double>{9.0, 3.0, 50.0, 0.0}.data(), 0, [&](int p) { ++kept; CHECK(p == 0); });  // (a stopped item's sums are not looked at)
+    CHECK(kept == 2 && state2[0] == (RS_OK | RS_ACTIVE) && u.nin[0] == 9 && u.ssq[0] == 3.0 && state2[1] == RS_OK && u.nin[1] == 9);
+
+    // a first_min: refit 0 is held to it, not to the kept count; refit 1 to the count refit 0 left
+    u.pick(2, state2, hc2, H, n2, 6);
+    u.first(std::vector<double>{40.0, 1.0, 40.0, 1.0}.data(), [](int) { return 0; });
+    kept = 0;
+    u.accept(0, std::vector<double>{6.0, 0.5, 5.0, 0.5}.data(), 6, [&](int p) { ++kept; CHECK(p == 0); });
+    CHECK(kept == 1 && u.nin[0] == 6 && state2[0] == ON && u.nin[1] == 40 && state2[1] == RS_OK && u.n_active == 1);
+    u.accept(1, std::vector<double>{6.0, 0.25, nan, nan}.data(), 6, [&](int) { ++kept; });
+    CHECK(kept == 2 && u.nin[0] == 6 && u.ssq[0] == 0.25 && state2[0] == (RS_OK | RS_ACTIVE) && u.n_active == 1);
+    u.accept(2, std::vector<double>{5.0, 0.125, nan, nan}.data(), 6, [&](int) { ++kept; });
+    CHECK(kept == 2 && u.nin[0] == 6 && u.ssq[0] == 0.25 && state2[0] == RS_OK && u.n_active == 0);
+
+    // n_refit = 0: what first took is what write gives, and the first mask -- buffer 0 -- is the current one; every optional
+    // output null: q1 is still called; H = 1
+    const int one[2] = {12, -1}, n1[2] = {12, 12};
+    RsTile v(2);
+    v.pick(2, state2, one, 1, n1, 8);
+    CHECK(v.st[0] == 0 && v.best[0] == 0 && v.st[1] == 2 && v.best[1] == -1);
+    CHECK(v.first(std::vector<double>{12.0, 48.0, nan, nan}.data(), [](int) { return 0; }) == 1);
+    unsigned char b0[1], b1[1];
+    CHECK(rs_current(state2[0], b0, b1) == b0 && (state2[0] & RS_OK) && state2[1] == 0);
+    RsTile::defaults(2, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    calls = 0;
+    v.write(0, nullptr, nullptr, nullptr, nullptr, nullptr, [&](int p) { ++calls; CHECK(p == 0); return 0.0; });
+    CHECK(calls == 1);
+    int32_t st1[2] = {77, 77}, hc1[2] = {77, 77};
+    double q[4] = {77, 77, 77, 77};
+    v.write(0, st1, nullptr, hc1, nullptr, q, [](int) { return 0.5; });
+    CHECK(st1[0] == 0 && st1[1] == 2 && hc1[0] == 12 && hc1[1] == -1 && q[0] == 2.0 && q[1] == 0.5 && q[2] == 77 && q[3] == 77);
   }
   {  // the chunk list: cameras with 0, 1, 256 and 257 observations, one listed twice; cameras = NULL
     const long long cam_ptr[5] = {0, 0, 1, 257, 514};

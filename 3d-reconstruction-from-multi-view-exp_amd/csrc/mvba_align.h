@@ -1,10 +1,11 @@
 // Similarity alignment of two point sets (mvba_align_robust, mvba_align, mvba_align_sample): y ~ s Q x + tau by 3-point RANSAC and
 // by plain least squares -- kernels and host code, gfx950.
 //
-// Included by mvba.hip after mvba_tri_ransac.h: uses mvba_ransac_host.h's align_solve, argument checks, rs_pick, rs_accept, RsLaps
-// and state bits, mvba_ransac.h's rs_sample, k_ransac_scan and RS_HYP_BLOCK, mvba_twoview.h's tv_combine, mvba_init.h's init_finite,
-// mvba_start.h's chunk_sum, InitClock and START_CHUNK, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM
-// path.  
+// Included by mvba.hip after mvba_tri_ransac.h: uses mvba_ransac_host.h's align_solve, argument checks, RsTile (the call is a tile
+// of one item), rs_stop, rs_current, rs_other, RsLaps and state bits, mvba_ransac.h's rs_sample, sample_entry, rs_score_block,
+// rs_score_add, k_ransac_scan and RS_HYP_BLOCK, mvba_twoview.h's tv_combine, mvba_init.h's init_finite, mvba_start.h's chunk_sum,
+// chunk_ballot, chunk_total, chunk_rank, mask_step, InitClock and START_CHUNK, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing
+// here runs on the LM path.  
 //
 // The usable correspondences (ok allows them, six finite numbers) are compacted into a dense array of (x, y), 48 bytes each, in
 // ascending order -- chunk counts, k_ransac_scan, ballot and prefix -- with their row numbers beside them; every later pass reads
@@ -91,15 +92,8 @@ __global__ __launch_bounds__(START_CHUNK) void k_align_count(long long n, const 
   __shared__ int s_w[START_CHUNK / 64];
   const int i = threadIdx.x;
   double z[6];
-  const unsigned long long b = __ballot(al_usable((long long)blockIdx.x * START_CHUNK + i, n, src, dst, ok, z));
-  if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
-  __syncthreads();
-  if (i == 0) {
-    int x = 0;
-#pragma unroll
-    for (int w = 0; w < START_CHUNK / 64; ++w) x += s_w[w];
-    cnt[blockIdx.x] = x;
-  }
+  chunk_ballot(al_usable((long long)blockIdx.x * START_CHUNK + i, n, src, dst, ok, z), s_w);
+  if (i == 0) cnt[blockIdx.x] = chunk_total(s_w);
 }
 
 // comp[j] = (x, y) and id[j] = the row of the j-th usable correspondence, ascending (off: the exclusive scan of the chunk counts)
@@ -111,12 +105,9 @@ __global__ __launch_bounds__(START_CHUNK) void k_align_compact(long long n, cons
   const long long a = (long long)blockIdx.x * START_CHUNK + i;
   double z[6];
   const bool use = al_usable(a, n, src, dst, ok, z);
-  const unsigned long long b = __ballot(use);
-  if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
-  __syncthreads();
+  const unsigned long long b = chunk_ballot(use, s_w);
   if (!use) return;
-  long long j = off[blockIdx.x] + __popcll(b & ((1ull << (i & 63)) - 1ull));
-  for (int w = 0; w < (i >> 6); ++w) j += s_w[w];
+  const long long j = off[blockIdx.x] + chunk_rank(b, s_w);
   comp[3 * j] = make_double2(z[0], z[1]);  // (j < the usable count <= n)
   comp[3 * j + 1] = make_double2(z[2], z[3]);
   comp[3 * j + 2] = make_double2(z[4], z[5]);
@@ -174,14 +165,9 @@ __global__ __launch_bounds__(START_CHUNK) void k_align_score(int H, const int *_
     for (int e = i; e < nh * 12; e += START_CHUNK) s_m[e] = hyp[12 * (size_t)h0 + e];
     if (i < RS_HYP_BLOCK) s_cnt[i] = 0;
     __syncthreads();
-    int mine = 0;
-    for (int hh = 0; hh < nh; ++hh) {
-      const int c = __popcll(__ballot(live && al_dist2(s_m + 12 * hh, z) <= thr2));
-      if (lane == hh) mine = c;
-    }
-    if (mine) atomicAdd(&s_cnt[lane], mine);
-    __syncthreads();  // (also: every read of s_m is done before the next block is staged; s_cnt[i] is read and reset by thread i)
-    if (i < nh && s_cnt[i]) atomicAdd(&hyp_count[h0 + i], s_cnt[i]);
+    const int mine = rs_score_block(nh, lane, live, [&](int hh) { return al_dist2(s_m + 12 * hh, z) <= thr2; });
+    // (its barrier also: every read of s_m is done before the next block is staged; s_cnt[i] is read and reset by thread i)
+    rs_score_add(mine, nh, lane, s_cnt, hyp_count + h0);
   }
 }
 
@@ -197,9 +183,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_align_mask(const int *__restric
     double z[6];
     al_load(comp, j, z);
     const double d2 = al_dist2(m, z);
-    const bool in = d2 <= thr2;
-    inl[j] = in ? 1 : 0;
-    if (in) { v[0] = 1.0; v[1] = d2; }
+    mask_step(d2 <= thr2, d2, &inl[j], v);
   }
   chunk_sum<2>(v, s_w, part + (size_t)blockIdx.x * 2);
 }
@@ -320,15 +304,10 @@ struct AlignDev {
     return MVBA_OK;
   }
 
-  // the inliers of the model `m` on the device (sQ, tau) into inl: their number and their sum of d^2
-  int mask(const double *m, double thr2, unsigned char *inl, long long &count, double &ssq) {
-    double s2[2];
-    int rc;
+  // the inliers of the model `m` on the device (sQ, tau) into inl: s2 = (their number, their sum of d^2)
+  int mask(const double *m, double thr2, unsigned char *inl, double (&s2)[2]) {
     hipLaunchKernelGGL(k_align_mask, dim3(n_ch), dim3(START_CHUNK), 0, 0, dntot, dcomp, m, thr2, inl, dpart);
-    if ((rc = sums(2, s2))) return rc;
-    count = (long long)s2[0];
-    ssq = s2[1];
-    return MVBA_OK;
+    return sums(2, s2);
   }
 
   // sim13 -> the 12 doubles the mask kernel reads, at dmodel
@@ -354,13 +333,7 @@ int align_check(int64_t n, const double *src, const double *dst, const double *s
 extern "C" {
 
 int mvba_align_sample(uint64_t seed, int32_t h, int64_t n, int64_t *idx3) {
-  if (!idx3) return fail(MVBA_ERR_BADARG, "null argument: idx3 (argument 4)");
-  if (n < AL_MIN || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 3 .. 2^31 - 1");
-  if (h < 0) return fail(MVBA_ERR_BADARG, "h = " + std::to_string(h) + ": negative index");
-  long long idx[AL_MIN];
-  rs_sample(seed, 0, 0, h, n, idx);
-  for (int c = 0; c < AL_MIN; ++c) idx3[c] = idx[c];
-  return MVBA_OK;
+  return sample_entry<AL_MIN>(seed, "h", 0, 0, h, n, idx3, "idx3", 4);
 }
 
 int mvba_align_robust(int64_t n, const double *src, const double *dst, const uint8_t *ok, int32_t with_scale, double threshold,
@@ -373,13 +346,9 @@ int mvba_align_robust(int64_t n, const double *src, const double *dst, const uin
   const double thr2 = threshold * threshold;
   // the defaults are those of a call without usable correspondences: status 1
   for (int e = 0; e < 13; ++e) sim13[e] = NAN;
-  if (quality) quality[0] = quality[1] = quality[2] = NAN;
-  if (n_usable) *n_usable = 0;
-  if (n_inliers) *n_inliers = 0;
-  if (best) *best = -1;
-  if (status) *status = 1;
+  if (quality) quality[0] = quality[1] = quality[2] = NAN;  // (three figures, not RsTile's two: written here)
+  RsTile::defaults(1, H, status, best, hyp_count, n_usable, n_inliers, nullptr);
   if (inlier) std::memset(inlier, 0, (size_t)n);
-  if (hyp_count) std::fill(hyp_count, hyp_count + H, -1);
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
   if (n == 0) return MVBA_OK;
 
@@ -403,50 +372,55 @@ int mvba_align_robust(int64_t n, const double *src, const double *dst, const uin
   MVBA_HIP(hipGetLastError());
   std::vector<int> hc((size_t)H);
   MVBA_HIP(hipMemcpy(hc.data(), dhc, sizeof(int) * H, hipMemcpyDeviceToHost));
-  if (hyp_count) std::copy(hc.begin(), hc.end(), hyp_count);
   laps.score = clk.lap();
 
-  const RsPick pick = rs_pick(hc.data(), H, d.n_usable, AL_MIN);
-  if (status) *status = pick.status;
-  if (best) *best = pick.best;
-  if (pick.status) {
+  // the call is a tile of one item
+  RsTile t(1);
+  int state = 0;
+  double sim[13], gap = 0.0, s2[2];
+  auto write = [&]() {
+    t.write(0, status, best, hyp_count, n_inliers, nullptr, [&](int) {
+      std::copy(sim, sim + 13, sim13);
+      return gap;
+    });
+  };
+  t.pick(1, &state, hc.data(), H, &d.n_usable, AL_MIN);
+  if (t.st[0]) {
+    write();
     laps.other = clk.lap();
     laps.write(timings_ms);
     return MVBA_OK;
   }
-  // the best hypothesis as the device holds it: its mask goes into buffer 0 (RS_CUR set: the current mask is dinl[1] once toggled)
-  double sim[13], m12[12], gap = 0.0, ssq;
-  long long nin;
-  MVBA_HIP(hipMemcpy(m12, dhyp + 12 * (size_t)pick.best, sizeof(m12), hipMemcpyDeviceToHost));
-  MVBA_HIP(hipMemcpy(&sim[0], dhs + pick.best, sizeof(double), hipMemcpyDeviceToHost));
+  // the best hypothesis as the device holds it
+  double m12[12];
+  const double *dbest = dhyp + 12 * (size_t)t.best[0];
+  MVBA_HIP(hipMemcpy(m12, dbest, sizeof(m12), hipMemcpyDeviceToHost));
+  MVBA_HIP(hipMemcpy(&sim[0], dhs + t.best[0], sizeof(double), hipMemcpyDeviceToHost));
   for (int e = 0; e < 9; ++e) sim[1 + e] = m12[e] / sim[0];
   for (int e = 0; e < 3; ++e) sim[10 + e] = m12[9 + e];
-  if ((rc = d.mask(dhyp + 12 * (size_t)pick.best, thr2, d.dinl[0], nin, ssq))) return rc;
-  int state = pick.state ^ RS_CUR, n_active = 1;  // (RS_CUR clear: the current mask is dinl[0])
+  if ((rc = d.mask(dbest, thr2, rs_other(state, d.dinl[0], d.dinl[1]), s2))) return rc;
+  t.first(s2, [](int) { return 0; });
   laps.other = clk.lap();
 
   // refits: the least-squares fit of the current inliers alone; the first is kept if it has three inliers of its own, a later
   // one while its set does not shrink
-  for (int r = 0; r < n_refit && n_active > 0; ++r) {
-    const int cur = (state & RS_CUR) ? 1 : 0;
-    double simr[13], gr, sr;
-    long long c;
+  for (int r = 0; r < n_refit && t.n_active > 0; ++r) {
+    double simr[13], gr;
     int st;
-    if ((rc = d.fit(d.dinl[cur], with_scale != 0, simr, gr, &st))) return rc;
+    if ((rc = d.fit(rs_current(state, d.dinl[0], d.dinl[1]), with_scale != 0, simr, gr, &st))) return rc;
     if (st) {
-      rs_stop(state, n_active);
+      rs_stop(state, t.n_active);
       break;
     }
-    if ((rc = d.set_model(simr)) || (rc = d.mask(d.dmodel, thr2, d.dinl[1 - cur], c, sr))) return rc;
-    if (!rs_accept(c, nin, r, AL_MIN, state, n_active)) break;
-    nin = c;
-    ssq = sr;
-    gap = gr;
-    std::copy(simr, simr + 13, sim);
+    if ((rc = d.set_model(simr)) || (rc = d.mask(d.dmodel, thr2, rs_other(state, d.dinl[0], d.dinl[1]), s2))) return rc;
+    t.accept(r, s2, AL_MIN, [&](int) {
+      gap = gr;
+      std::copy(simr, simr + 13, sim);
+    });
   }
   laps.refit = clk.lap();
 
-  const unsigned char *fin = d.dinl[(state & RS_CUR) ? 1 : 0];
+  const unsigned char *fin = rs_current(state, d.dinl[0], d.dinl[1]);
   double count, mom[11];
   AlCentre ctr;
   if ((rc = d.moments(fin, count, ctr, mom))) return rc;  // the spread of the final inliers
@@ -457,10 +431,9 @@ int mvba_align_robust(int64_t n, const double *src, const double *dst, const uin
     MVBA_HIP(hipGetLastError());
     MVBA_HIP(hipMemcpy(inlier, dout, (size_t)n, hipMemcpyDeviceToHost));
   }
-  std::copy(sim, sim + 13, sim13);
-  if (n_inliers) *n_inliers = nin;
+  write();
   if (quality) {
-    quality[0] = sqrt(ssq / (double)nin);
+    quality[0] = sqrt(t.ssq[0] / (double)t.nin[0]);
     quality[1] = gap;
     quality[2] = mom[0] / count;
   }
@@ -483,7 +456,7 @@ int mvba_align(int64_t n, const double *src, const double *dst, const uint8_t *o
   if ((rc = d.upload(n, src, dst, ok)) || (rc = d.compact(n, false))) return rc;
   if (n_usable) *n_usable = d.n_usable;
   if (d.n_usable < AL_MIN) return MVBA_OK;
-  double count, mom[11], sim[13], gap, ssq;
+  double count, mom[11], sim[13], gap, s2[2];
   AlCentre c;
   if ((rc = d.moments(nullptr, count, c, mom))) return rc;
   const int st = align_solve(c.x, c.y, mom, with_scale != 0, sim, gap);
@@ -491,11 +464,10 @@ int mvba_align(int64_t n, const double *src, const double *dst, const uint8_t *o
   if (st) return MVBA_OK;
   // the residual of every usable correspondence: the mask pass with no threshold
   unsigned char *dall = nullptr;
-  long long nin;
-  if ((rc = d.tmp.alloc(&dall, (size_t)d.n_usable)) || (rc = d.set_model(sim)) || (rc = d.mask(d.dmodel, HUGE_VAL, dall, nin, ssq))) return rc;
+  if ((rc = d.tmp.alloc(&dall, (size_t)d.n_usable)) || (rc = d.set_model(sim)) || (rc = d.mask(d.dmodel, HUGE_VAL, dall, s2))) return rc;
   std::copy(sim, sim + 13, sim13);
   if (quality) {
-    quality[0] = sqrt(ssq / count);
+    quality[0] = sqrt(s2[1] / count);
     quality[1] = gap;
     quality[2] = mom[0] / count;
   }

@@ -2,7 +2,8 @@
 // and host code, gfx950.
 //
 // Included by mvba.hip after mvba_ransac.h: the call IS mvba_ransac.h's robust_pairs -- its compaction, normalisation, scoring,
-// mask, refit, gather and scatter kernels and its host loop -- with the model below in place of the fundamental matrix:
+// mask, refit, gather and scatter kernels, its host loop and its sample_entry -- with the model below in place of the
+// fundamental matrix:
 // HomogModel, the inlier test of k_ransac_score and k_ransac_mask; k_homog_hyp, the hypothesis kernel; tv_pass mode 4, the
 // refit's moments (mvba_twoview.h); homography_solve_pair (mvba_twoview.h) and hg_mask_parts (mvba_ransac_host.h), the host
 // steps.  Nothing here runs on the LM path.  
@@ -144,14 +145,7 @@ struct HomogFit {
 extern "C" {
 
 int mvba_homography_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx4) {
-  if (!idx4) return fail(MVBA_ERR_BADARG, "null argument: idx4 (argument 6)");
-  if (n < HomogModel::MIN || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 4 .. 2^31 - 1");
-  if (k < 0 || l < 0 || h < 0)
-    return fail(MVBA_ERR_BADARG, "k = " + std::to_string(k) + ", l = " + std::to_string(l) + ", h = " + std::to_string(h) + ": negative index");
-  long long idx[4];
-  rs_sample(seed, k, l, h, n, idx);
-  for (int c = 0; c < 4; ++c) idx4[c] = idx[c];
-  return MVBA_OK;
+  return sample_entry<HomogModel::MIN>(seed, "klh", k, l, h, n, idx4, "idx4", 6);
 }
 
 int mvba_homography_robust(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,

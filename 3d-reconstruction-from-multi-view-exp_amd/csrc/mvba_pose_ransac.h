@@ -3,8 +3,8 @@
 //
 // Included by mvba.hip after mvba_resect_ransac.h: uses its robust_cameras (the tile loop, with rr_inlier, k_resect_score,
 // k_resect_mask and k_resect_scatter as they are: a hypothesis is scored as the 12-double matrix K [R^T | -R^T t]) and
-// k_resect_gather, mvba_ransac.h's rs_sample and RS_HYP_BLOCK, mvba_ransac_host.h's argument checks, check_camera_list,
-// rs_stop and state bits, mvba_init.h's resect_build_list, CamWork and k_resect_combine, mvba_start.h's chunk_sum,
+// k_resect_gather, mvba_ransac.h's rs_sample, sample_entry and RS_HYP_BLOCK, mvba_ransac_host.h's argument checks,
+// check_camera_list, rs_stop, rs_current and state bits, mvba_init.h's resect_build_list, CamWork and k_resect_combine, mvba_start.h's chunk_sum,
 // init_check_list, InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.
 // 
 //
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_pose_fit(int first, const int *
   double v[PR_NV];
 #pragma unroll
   for (int e = 0; e < PR_NV; ++e) v[e] = 0.0;
-  if ((st & RS_ACTIVE) && (first || !gflag[k]) && i < ch_cnt[c] && ((st & RS_CUR) ? inl1 : inl0)[ch_mask[c] + i]) {
+  if ((st & RS_ACTIVE) && (first || !gflag[k]) && i < ch_cnt[c] && rs_current(st, inl0, inl1)[ch_mask[c] + i]) {
     const long long o = ch_start[c] + i;
     double Kk[9], Rt[12];
 #pragma unroll
@@ -492,13 +492,7 @@ struct PoseFit {
 extern "C" {
 
 int mvba_pose_sample(uint64_t seed, int32_t k, int32_t h, int64_t n, int64_t *idx4) {
-  if (!idx4) return fail(MVBA_ERR_BADARG, "null argument: idx4 (argument 5)");
-  if (n < PR_MIN_OBS || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 4 .. 2^31 - 1");
-  if (k < 0 || h < 0) return fail(MVBA_ERR_BADARG, "k = " + std::to_string(k) + ", h = " + std::to_string(h) + ": negative index");
-  long long idx[4];
-  rs_sample(seed, k, k, h, n, idx);
-  for (int c = 0; c < 4; ++c) idx4[c] = idx[c];
-  return MVBA_OK;
+  return sample_entry<PR_MIN_OBS>(seed, "kh", k, k, h, n, idx4, "idx4", 5);
 }
 
 int mvba_pose_robust(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,

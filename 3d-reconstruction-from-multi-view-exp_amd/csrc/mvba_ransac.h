@@ -1,10 +1,14 @@
 // Robust two-view geometry (mvba_two_view_robust, mvba_ransac_sample): 8-point RANSAC for the fundamental matrix -- kernels
 // and host code, gfx950.
 //
-// Included by mvba.hip after mvba_twoview.h: uses mvba_ransac_host.h's argument checks, rs_pick, rs_accept, RsLaps, limits and
-// state bits, mvba_twoview.h's rs_shared, tv_pass, tv_row, rs_sampson, tv_denormalise, k_twoview_combine,
-// k_twoview_norm, twoview_solve_pair, tv_pair_tile, tv_combine and constants, mvba_start.h's chunk_sum, checks, upload_list,
-// InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
+// Included by mvba.hip after mvba_twoview.h: uses mvba_ransac_host.h's argument checks, RsTile, rs_stop, rs_current, rs_other,
+// RsLaps, limits and state bits, mvba_twoview.h's rs_shared, tv_pass, tv_row, rs_sampson, tv_denormalise, k_twoview_combine,
+// k_twoview_norm, twoview_solve_pair, tv_pair_tile, tv_combine and constants, mvba_start.h's chunk_sum, chunk_ballot,
+// chunk_total, chunk_rank, mask_step, checks, upload_list, InitClock and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and
+// MVBA_HIP.  Nothing here runs on the LM path.  
+//
+// What the later robust fits take from here (mvba_homography.h, mvba_resect_ransac.h, mvba_pose_ransac.h, mvba_align.h):
+// rs_lds_eig, rs_sample and sample_entry, and the scoring loop of a block of hypotheses, rs_score_block and rs_score_add.
 //
 // Per pair of a tile (blockIdx.y or .z: the pair inside the tile): the shared observations are compacted into a dense array
 // of (x_k, y_k, x_l, y_l) in ascending point order (per-chunk counts, an exclusive scan over the pair's chunks, ballot and
@@ -25,6 +29,28 @@ constexpr int RS_HYP_BLOCK = 64;      // hypotheses per workgroup of k_ransac_hy
 // device bytes one pair of a tile takes per point of the scene (32 compacted observation, 4 point id, 2 masks, 1 mask by
 // point, 1.42 chunk counts and partials) and per hypothesis (72 F^, 72 F, 4 count), rounded up: the tile's bound
 constexpr size_t RS_POINT_BYTES = 48, RS_HYP_BYTES = 160;
+
+// The scoring loop of a thread over a block of nh <= RS_HYP_BLOCK hypotheses: in(hh) says whether the thread's item is an
+// inlier of hypothesis hh of the block (live: the thread has an item); a hypothesis's inliers of a wave are one ballot and one
+// popcount, kept by the lane of the hypothesis's number.  Returns that lane's count.  Every thread of the wave calls it.
+template <class In>
+__device__ __forceinline__ int rs_score_block(int nh, int lane, bool live, In in) {
+  int mine = 0;
+  for (int hh = 0; hh < nh; ++hh) {
+    const int c = __popcll(__ballot(live && in(hh)));
+    if (lane == hh) mine = c;
+  }
+  return mine;
+}
+
+// The waves' counts of rs_score_block into hyp_count[0 .. nh), the block's counts in device memory: an LDS atomic per wave and
+// hypothesis into s_cnt (zero beforehand), a barrier, one device atomic per hypothesis.  Integer sums: exact in any order.
+__device__ __forceinline__ void rs_score_add(int mine, int nh, int lane, int (&s_cnt)[RS_HYP_BLOCK], int *__restrict__ hyp_count) {
+  const int i = threadIdx.x;
+  if (mine) atomicAdd(&s_cnt[lane], mine);
+  __syncthreads();
+  if (i < nh && s_cnt[i]) atomicAdd(&hyp_count[i], s_cnt[i]);
+}
 
 // The eigenvector of the smallest eigenvalue of a thread's symmetric N x N matrix by cyclic Jacobi with A and V in LDS,
 // element-major: sA and sV are the thread's columns, element e at [e * RS_HYP_BLOCK].  A is filled by the caller, V is set
@@ -110,6 +136,25 @@ __host__ __device__ __forceinline__ void rs_sample(unsigned long long seed, int 
   }
 }
 
+// The body of the *_sample entry points that rs_sample serves: the NS indices of hypothesis h of item (k, l) among n, for a
+// test to draw what the kernels draw.  `keys` names the indices the entry point takes ("klh", "kh", "h"), for its message; out
+// is its argument number `arg`, called `name`.
+template <int NS>
+int sample_entry(uint64_t seed, const char *keys, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *out, const char *name, int arg) {
+  if (!out) return fail(MVBA_ERR_BADARG, std::string("null argument: ") + name + " (argument " + std::to_string(arg) + ")");
+  if (n < NS || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in " + std::to_string(NS) + " .. 2^31 - 1");
+  if (k < 0 || l < 0 || h < 0) {
+    std::string msg;
+    for (const char *c = keys; *c; ++c)
+      msg += std::string(c == keys ? "" : ", ") + *c + " = " + std::to_string(*c == 'k' ? k : (*c == 'l' ? l : h));
+    return fail(MVBA_ERR_BADARG, msg + ": negative index");
+  }
+  long long idx[NS];
+  rs_sample(seed, k, l, h, n, idx);
+  for (int c = 0; c < NS; ++c) out[c] = idx[c];
+  return MVBA_OK;
+}
+
 // cnt[pair][chunk] = the number of shared points among the chunk's 256
 __global__ __launch_bounds__(START_CHUNK) void k_ransac_count(long long npts, int m, const long long *__restrict__ pt_ptr,
                                                            const int *__restrict__ cam_idx, const int *__restrict__ pairs,
@@ -118,15 +163,8 @@ __global__ __launch_bounds__(START_CHUNK) void k_ransac_count(long long npts, in
   const int p = blockIdx.y, i = threadIdx.x;
   long long ok, ol;
   const bool sh = rs_shared((long long)blockIdx.x * START_CHUNK + i, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
-  const unsigned long long b = __ballot(sh);
-  if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
-  __syncthreads();
-  if (i == 0) {
-    int x = 0;
-#pragma unroll
-    for (int w = 0; w < START_CHUNK / 64; ++w) x += s_w[w];
-    cnt[(size_t)p * gridDim.x + blockIdx.x] = x;
-  }
+  chunk_ballot(sh, s_w);
+  if (i == 0) cnt[(size_t)p * gridDim.x + blockIdx.x] = chunk_total(s_w);
 }
 
 // one workgroup per pair: cnt[pair][.] -> its exclusive prefix sums, in place; ntot[pair] = the total.  Thread i takes a
@@ -168,12 +206,9 @@ __global__ __launch_bounds__(START_CHUNK) void k_ransac_compact(long long npts, 
   const long long a = (long long)blockIdx.x * START_CHUNK + i;
   long long ok, ol;
   const bool sh = rs_shared(a, npts, m, pt_ptr, cam_idx, pairs[2 * p], pairs[2 * p + 1], ok, ol);
-  const unsigned long long b = __ballot(sh);
-  if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
-  __syncthreads();
+  const unsigned long long b = chunk_ballot(sh, s_w);
   if (!sh) return;
-  int j = off[(size_t)p * gridDim.x + blockIdx.x] + __popcll(b & ((1ull << (i & 63)) - 1ull));
-  for (int w = 0; w < (i >> 6); ++w) j += s_w[w];
+  const int j = off[(size_t)p * gridDim.x + blockIdx.x] + chunk_rank(b, s_w);
   const double2 zk = xy[ok], zl = xy[ol];
   comp[(size_t)p * npts + j] = make_double4(zk.x, zk.y, zl.x, zl.y);  // (j < the pair's count <= npts)
   id[(size_t)p * npts + j] = (int)a;
@@ -197,7 +232,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_ransac_fit(long long stride, co
   if (state) {
     const int st = state[p];
     use = use && (st & RS_ACTIVE);
-    if (use) use = ((st & RS_CUR) ? inl1 : inl0)[(size_t)p * stride + j] != 0;
+    if (use) use = rs_current(st, inl0, inl1)[(size_t)p * stride + j] != 0;
   }
   if (use) {
     const double4 z = comp[(size_t)p * stride + j];
@@ -304,15 +339,10 @@ __global__ __launch_bounds__(START_CHUNK) void k_ransac_score(long long stride, 
   __syncthreads();
   const bool live = j < n;
   const double4 z = live ? comp[(size_t)p * stride + j] : make_double4(0.0, 0.0, 0.0, 0.0);
-  int mine = 0;
-  for (int hh = 0; hh < nh; ++hh) {
-    const bool in = M::inlier(s_F[0] + 9 * hh, s_F[M::PARTS - 1] + 9 * hh, z.x, z.y, z.z, z.w, thr2);
-    const int c = __popcll(__ballot(live && in));
-    if (lane == hh) mine = c;
-  }
-  if (mine) atomicAdd(&s_cnt[lane], mine);
-  __syncthreads();
-  if (i < nh && s_cnt[i]) atomicAdd(&hyp_count[(size_t)p * H + h0 + i], s_cnt[i]);
+  const int mine = rs_score_block(nh, lane, live, [&](int hh) {
+    return M::inlier(s_F[0] + 9 * hh, s_F[M::PARTS - 1] + 9 * hh, z.x, z.y, z.z, z.w, thr2);
+  });
+  rs_score_add(mine, nh, lane, s_cnt, hyp_count + (size_t)p * H + h0);
 }
 
 // Fcur[pair], fbest[pair] = the matrices of the pair's best hypothesis (best < 0: NaN)
@@ -340,9 +370,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_ransac_mask(long long stride, c
     const double4 z = comp[(size_t)p * stride + j];
     const double *F0 = F + 9 * (size_t)p;
     const double d2 = M::dist2(F0, F0 + (size_t)(M::PARTS - 1) * gridDim.y * 9, z.x, z.y, z.z, z.w, thr2);
-    const bool in = d2 <= thr2;
-    ((st & RS_CUR) ? inl0 : inl1)[(size_t)p * stride + j] = in ? 1 : 0;
-    if (in) { v[0] = 1.0; v[1] = d2; }
+    mask_step(d2 <= thr2, d2, &rs_other(st, inl0, inl1)[(size_t)p * stride + j], v);
   }
   chunk_sum<2>(v, s_w, part + ((size_t)p * gridDim.x + blockIdx.x) * 2);
 }
@@ -354,7 +382,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_ransac_scatter(long long stride
   const int p = blockIdx.y, st = state[p];
   const long long j = (long long)blockIdx.x * START_CHUNK + threadIdx.x;
   if (!(st & RS_OK) || j >= ntot[p]) return;
-  if (((st & RS_CUR) ? inl1 : inl0)[(size_t)p * stride + j]) out[(size_t)p * stride + id[(size_t)p * stride + j]] = 1;
+  if (rs_current(st, inl0, inl1)[(size_t)p * stride + j]) out[(size_t)p * stride + id[(size_t)p * stride + j]] = 1;
 }
 
 // F^ (unit, normalised units) -> F through twoview_solve_pair's own rank-2 step, denormalisation and scaling: the moment
@@ -413,16 +441,9 @@ int robust_pairs(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, cons
   const int np = n_pairs, H = n_hypotheses;
   const double thr2 = threshold * threshold;
   // the defaults are those of a pair without shared points: status 1
-  for (int p = 0; p < np; ++p) {
-    for (int j = 0; j < 9; ++j) F[9 * (size_t)p + j] = NAN;
-    if (quality) quality[2 * p] = quality[2 * p + 1] = NAN;
-    if (n_shared) n_shared[p] = 0;
-    if (n_inliers) n_inliers[p] = 0;
-    if (best) best[p] = -1;
-    if (status) status[p] = 1;
-  }
+  if (np > 0) std::fill(F, F + 9 * (size_t)np, NAN);
+  RsTile::defaults((size_t)np, H, status, best, hyp_count, n_shared, n_inliers, quality);
   if (inlier) std::memset(inlier, 0, (size_t)np * (size_t)n_points);
-  if (hyp_count) std::fill(hyp_count, hyp_count + (size_t)np * H, -1);
   if (np == 0 || n_points == 0) return MVBA_OK;
 
   if (device >= 0) MVBA_HIP(hipSetDevice(device));
@@ -452,10 +473,10 @@ int robust_pairs(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, cons
   laps.upload = clk.lap();
 
   const dim3 b256(256), bch(START_CHUNK);
-  std::vector<int> ntot((size_t)tile), hc((size_t)tile * H), bst((size_t)tile), state((size_t)tile), st((size_t)tile);
-  std::vector<long long> nin((size_t)tile);
+  std::vector<int> ntot((size_t)tile), hc((size_t)tile * H), state((size_t)tile);
+  RsTile t(tile);
   std::vector<double> S((size_t)tile * 45), norm(TV_NORM * (size_t)tile), fb(18 * (size_t)tile), Fc(9 * (size_t)tile), Fn(9 * (size_t)tile), Mn(18 * (size_t)tile),
-      S2(2 * (size_t)tile), ssq((size_t)tile), ratio((size_t)tile);
+      S2(2 * (size_t)tile), ratio((size_t)tile);
   for (int p0 = 0; p0 < np; p0 += tile) {
     const int cnt = std::min(tile, np - p0);
     const dim3 grid((unsigned)n_ch, (unsigned)cnt), gp((cnt + 255) / 256);
@@ -498,32 +519,20 @@ int robust_pairs(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, cons
     MVBA_HIP(hipMemcpy(norm.data(), dnorm, sizeof(double) * TV_NORM * cnt, hipMemcpyDeviceToHost));
     laps.score += clk.lap();
 
-    for (int p = 0; p < cnt; ++p) {
-      const RsPick pick = rs_pick(hc.data() + (size_t)p * H, H, ntot[p], Model::MIN);
-      st[p] = pick.status;
-      bst[p] = pick.best;
-      state[p] = pick.state;
-    }
-    MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+    t.pick(cnt, state.data(), hc.data(), H, ntot.data(), Model::MIN);
+    MVBA_HIP(hipMemcpy(dbest, t.best.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
     // the two parts of the best hypothesis, one array behind the other: what the mask kernel reads
     hipLaunchKernelGGL(k_ransac_gather, dim3((cnt * 9 + 255) / 256), b256, 0, 0, cnt, H, dbest, dhyp, dhyp + 9 * (size_t)cnt * H, dF, dF + 9 * (size_t)cnt);
     if ((rc = mask())) return rc;
     MVBA_HIP(hipMemcpy(fb.data(), dF, sizeof(double) * 18 * cnt, hipMemcpyDeviceToHost));
-    int n_active = 0;
-    for (int p = 0; p < cnt; ++p) {
-      if (st[p]) continue;
-      state[p] ^= RS_CUR;
-      nin[p] = (long long)S2[2 * p];
-      ssq[p] = S2[2 * p + 1];
+    t.first(S2.data(), [&](int p) {
       ratio[p] = 0.0;  // (the moment matrix of a minimal sample has rank 8)
-      st[p] = Fit::finish(fb.data() + 9 * (size_t)p, fb.data() + 9 * (size_t)(cnt + p), norm.data() + TV_NORM * (size_t)p, Fc.data() + 9 * (size_t)p);
-      if (st[p]) state[p] = 0;
-      else ++n_active;
-    }
+      return Fit::finish(fb.data() + 9 * (size_t)p, fb.data() + 9 * (size_t)(cnt + p), norm.data() + TV_NORM * (size_t)p, Fc.data() + 9 * (size_t)p);
+    });
     laps.other += clk.lap();
 
     // refits: the full fit on the current inliers alone, kept while its own inlier set does not shrink
-    for (int r = 0; r < n_refit && n_active > 0; ++r) {
+    for (int r = 0; r < n_refit && t.n_active > 0; ++r) {
       MVBA_HIP(hipMemcpy(dstate, state.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
       fit(dstate, dnorm2, true);
       MVBA_HIP(hipGetLastError());
@@ -534,21 +543,16 @@ int robust_pairs(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, cons
         for (int j = 0; j < 9; ++j) Fn[9 * (size_t)p + j] = Mn[9 * (size_t)p + j] = Mn[9 * (size_t)(cnt + p) + j] = NAN;
         if (!(state[p] & RS_ACTIVE)) continue;
         const double *nm = norm.data() + TV_NORM * (size_t)p;
-        if (Fit::solve(S.data() + 45 * (size_t)p, nm, Fn.data() + 9 * (size_t)p, &rt[p])) rs_stop(state[p], n_active);
+        if (Fit::solve(S.data() + 45 * (size_t)p, nm, Fn.data() + 9 * (size_t)p, &rt[p])) rs_stop(state[p], t.n_active);
         else Fit::mask_parts(Fn.data() + 9 * (size_t)p, nm, Mn.data() + 9 * (size_t)p, Mn.data() + 9 * (size_t)(cnt + p));
       }
-      if (n_active == 0) break;
+      if (t.n_active == 0) break;
       MVBA_HIP(hipMemcpy(dF, Mn.data(), sizeof(double) * 9 * Model::PARTS * cnt, hipMemcpyHostToDevice));
       if ((rc = mask())) return rc;
-      for (int p = 0; p < cnt; ++p) {
-        if (!(state[p] & RS_ACTIVE)) continue;
-        const long long c = (long long)S2[2 * p];
-        if (!rs_accept(c, nin[p], r, 0, state[p], n_active)) continue;
-        nin[p] = c;
-        ssq[p] = S2[2 * p + 1];
+      t.accept(r, S2.data(), 0, [&](int p) {
         ratio[p] = rt[p];
         for (int j = 0; j < 9; ++j) Fc[9 * (size_t)p + j] = Fn[9 * (size_t)p + j];
-      }
+      });
     }
     laps.refit += clk.lap();
 
@@ -559,20 +563,11 @@ int robust_pairs(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, cons
       MVBA_HIP(hipGetLastError());
       MVBA_HIP(hipMemcpy(inlier + (size_t)p0 * stride, dout, (size_t)cnt * stride, hipMemcpyDeviceToHost));
     }
-    for (int p = 0; p < cnt; ++p) {
-      const size_t g = (size_t)p0 + p;
-      if (n_shared) n_shared[g] = ntot[p];
-      if (status) status[g] = st[p];
-      if (best) best[g] = bst[p];
-      if (hyp_count) std::copy(hc.begin() + (size_t)p * H, hc.begin() + (size_t)(p + 1) * H, hyp_count + g * H);
-      if (st[p]) continue;
-      for (int j = 0; j < 9; ++j) F[9 * g + j] = Fc[9 * (size_t)p + j];
-      if (n_inliers) n_inliers[g] = nin[p];
-      if (quality) {
-        quality[2 * g] = sqrt(ssq[p] / (double)nin[p]);
-        quality[2 * g + 1] = ratio[p];
-      }
-    }
+    if (n_shared) std::copy(ntot.begin(), ntot.begin() + cnt, n_shared + p0);
+    t.write((size_t)p0, status, best, hyp_count, n_inliers, quality, [&](int p) {
+      for (int j = 0; j < 9; ++j) F[9 * ((size_t)p0 + p) + j] = Fc[9 * (size_t)p + j];
+      return ratio[p];
+    });
     laps.other += clk.lap();
   }
   laps.write(timings_ms);
@@ -584,14 +579,7 @@ int robust_pairs(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, cons
 extern "C" {
 
 int mvba_ransac_sample(uint64_t seed, int32_t k, int32_t l, int32_t h, int64_t n, int64_t *idx8) {
-  if (!idx8) return fail(MVBA_ERR_BADARG, "null argument: idx8 (argument 6)");
-  if (n < TV_MIN_SHARED || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 8 .. 2^31 - 1");
-  if (k < 0 || l < 0 || h < 0)
-    return fail(MVBA_ERR_BADARG, "k = " + std::to_string(k) + ", l = " + std::to_string(l) + ", h = " + std::to_string(h) + ": negative index");
-  long long idx[8];
-  rs_sample(seed, k, l, h, n, idx);
-  for (int c = 0; c < 8; ++c) idx8[c] = idx[c];
-  return MVBA_OK;
+  return sample_entry<TV_MIN_SHARED>(seed, "klh", k, l, h, n, idx8, "idx8", 6);
 }
 
 int mvba_two_view_robust(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,

@@ -1,7 +1,10 @@
-// The host logic of a RANSAC round, once: what mvba_two_view_robust, mvba_resect_robust and mvba_pose_robust decide on plain
-// integers between their kernels (mvba_ransac.h, mvba_resect_ransac.h, mvba_pose_ransac.h), and the chunk list of the
-// listed cameras (mvba_init.h's CamWork); the cyclic Jacobi the start headers share, and align_solve, the similarity fit of
-// mvba_align.h from centred moments.  No HIP call in it: csrc/host_check.cpp runs it under the host sanitizers.
+// The host logic of a RANSAC round, once: what mvba_two_view_robust, mvba_homography_robust, mvba_resect_robust,
+// mvba_pose_robust and mvba_align_robust decide on plain integers between their kernels (mvba_ransac.h, mvba_resect_ransac.h,
+// mvba_pose_ransac.h, mvba_align.h) -- the three decisions rs_pick, rs_accept and rs_stop, the loops over a tile's items
+// around them (RsTile) and the choice between the two mask buffers (rs_current, rs_other: the kernels use it too) -- and the
+// chunk list of the listed cameras (mvba_init.h's CamWork); the cyclic Jacobi the start headers share, and align_solve, the
+// similarity fit of mvba_align.h from centred moments.  No HIP call in it: csrc/host_check.cpp runs it under the host
+// sanitizers.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -24,6 +27,19 @@ namespace mvba {
 constexpr int RS_MAX_HYP = 65536;  // n_hypotheses
 constexpr int RS_MAX_REFIT = 16;   // n_refit
 enum { RS_CUR = 1, RS_ACTIVE = 2, RS_OK = 4 };  // per-item state: the current mask buffer, still refitting, status 0
+
+// The two mask buffers of an item under its state: RS_CUR names the CURRENT one, the inlier set of the model the item keeps;
+// a mask pass writes the OTHER one.  rs_pick hands an item out with RS_CUR set, so the first mask -- the best hypothesis's --
+// goes to buffer 0; the toggle that follows makes it current.  A refit sums over the current buffer and masks into the other;
+// rs_accept toggles if the refit is kept, and otherwise the current buffer stays what it was.  (T: const or not.)
+template <class T>
+RS_HD_INLINE T *rs_current(int st, T *inl0, T *inl1) {
+  return (st & RS_CUR) ? inl1 : inl0;
+}
+template <class T>
+RS_HD_INLINE T *rs_other(int st, T *inl0, T *inl1) {
+  return (st & RS_CUR) ? inl0 : inl1;
+}
 
 inline int rs_check_search(double threshold, int32_t n_hypotheses, int max_hyp = RS_MAX_HYP) {
   if (!std::isfinite(threshold) || !(threshold > 0.0))
@@ -80,6 +96,99 @@ inline bool rs_accept(long long count, long long kept, int r, long long first_mi
   rs_stop(state, n_active);
   return false;
 }
+
+// The rounds of one tile of items on the host, between the kernels: the pairs of robust_pairs, the cameras of
+// robust_cameras, the one alignment of mvba_align_robust.  The caller runs the kernels and brings S2 [item][2] = (inlier
+// count, sum of d^2) of each mask pass; the tile holds what the items keep and moves their state bits:
+//   defaults, once per call;  per tile: pick -> the first mask -> first -> per refit (the fit, rs_stop where it fails, the
+//   mask, accept) -> write.
+struct RsTile {
+  std::vector<int> st, best;   // per item: the status, the best hypothesis (-1: none)
+  std::vector<long long> nin;  // the inliers of the model the item keeps
+  std::vector<double> ssq;     // their sum of d^2
+  int *state = nullptr;        // the items' states, the caller's array (robust_cameras keeps one over its whole list)
+  const int *hc = nullptr;     // [cnt][H]: the counts pick went by
+  int cnt = 0, H = 0, n_active = 0;
+
+  explicit RsTile(int tile) : st((size_t)tile), best((size_t)tile), nin((size_t)tile), ssq((size_t)tile) {}
+
+  // What a call writes before any work, for n items of H hypotheses: those of an item without observations, status 1.  n_item
+  // is the output of the items' sizes (n_shared, n_usable); every pointer may be null.
+  static void defaults(size_t n, int H, int32_t *status, int32_t *best, int32_t *hyp_count, int64_t *n_item, int64_t *n_inliers,
+                       double *quality) {
+    for (size_t g = 0; g < n; ++g) {
+      if (quality) quality[2 * g] = quality[2 * g + 1] = NAN;
+      if (n_item) n_item[g] = 0;
+      if (n_inliers) n_inliers[g] = 0;
+      if (best) best[g] = -1;
+      if (status) status[g] = 1;
+    }
+    if (hyp_count) std::fill(hyp_count, hyp_count + n * (size_t)H, -1);
+  }
+
+  // rs_pick per item of a tile of cnt_ items (at most the tile the constructor was given): hyp_count [cnt_][H_] as the scoring
+  // kernel left it, n_item the items' sizes, state_ where their states go
+  void pick(int cnt_, int *state_, const int *hyp_count, int H_, const int *n_item, int n_min) {
+    cnt = cnt_; state = state_; hc = hyp_count; H = H_; n_active = 0;
+    for (int p = 0; p < cnt; ++p) {
+      const RsPick k = rs_pick(hc + (size_t)p * H, H, n_item[p], n_min);
+      st[p] = k.status;
+      best[p] = k.best;
+      state[p] = k.state;
+    }
+  }
+
+  // After the first mask: the best hypothesis's inlier set becomes the current one of every item of status 0, and finish(p)
+  // -> its status says whether the hypothesis is a model the item can keep (non-zero: the item is out, its state 0).  Returns
+  // the number of items that go into the refits.
+  template <class Finish>
+  int first(const double *S2, Finish finish) {
+    n_active = 0;
+    for (int p = 0; p < cnt; ++p) {
+      if (st[p]) continue;
+      state[p] ^= RS_CUR;
+      nin[p] = (long long)S2[2 * p];
+      ssq[p] = S2[2 * p + 1];
+      st[p] = finish(p);
+      if (st[p]) state[p] = 0;
+      else ++n_active;
+    }
+    return n_active;
+  }
+
+  // After the mask of refit r (from 0): rs_accept per active item; keep(p) for those whose refit becomes the kept model
+  template <class Keep>
+  void accept(int r, const double *S2, long long first_min, Keep keep) {
+    for (int p = 0; p < cnt; ++p) {
+      if (!(state[p] & RS_ACTIVE)) continue;
+      const long long c = (long long)S2[2 * p];
+      if (!rs_accept(c, nin[p], r, first_min, state[p], n_active)) continue;
+      nin[p] = c;
+      ssq[p] = S2[2 * p + 1];
+      keep(p);
+    }
+  }
+
+  // The tile's outputs, item p at g0 + p (every pointer may be null): status, best and the counts of every item; of an item of
+  // status 0 also n_inliers and quality = (the RMS distance of its inliers, q1(p)).  q1 is called once per item of status 0,
+  // wanted or not: it is where the caller writes the item's model.
+  template <class Q1>
+  void write(size_t g0, int32_t *status, int32_t *best_out, int32_t *hyp_count, int64_t *n_inliers, double *quality, Q1 q1) const {
+    for (int p = 0; p < cnt; ++p) {
+      const size_t g = g0 + p;
+      if (status) status[g] = st[p];
+      if (best_out) best_out[g] = best[p];
+      if (hyp_count) std::copy(hc + (size_t)p * H, hc + (size_t)(p + 1) * H, hyp_count + g * H);
+      if (st[p]) continue;
+      const double q = q1(p);
+      if (n_inliers) n_inliers[g] = nin[p];
+      if (quality) {
+        quality[2 * g] = sqrt(ssq[p] / (double)nin[p]);
+        quality[2 * g + 1] = q;
+      }
+    }
+  }
+};
 
 constexpr double INIT_REL_PIVOT = 1e-12;  // the relative pivot rule of mvba_covariance
 

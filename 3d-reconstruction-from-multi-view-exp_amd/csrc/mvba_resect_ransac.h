@@ -1,10 +1,11 @@
 // Robust resection (mvba_resect_robust, mvba_resect_sample): 6-point RANSAC for camera matrices -- kernels and host code,
 // gfx950.
 //
-// Included by mvba.hip after mvba_ransac.h: uses its rs_sample, rs_lds_eig and RS_HYP_BLOCK, mvba_ransac_host.h's argument
-// checks, rs_pick, rs_accept, rs_stop, RsLaps and state bits, mvba_twoview.h's tv_pair_tile, mvba_init.h's resect_build_list,
-// CamWork, rs_pass, k_resect_chunk, k_resect_combine, k_resect_norm, resect_solve_camera and resect_denormalise, mvba_start.h's chunk_sum, init_check_list, InitClock and INIT_REL_PIVOT, and
-// mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
+// Included by mvba.hip after mvba_ransac.h: uses its rs_sample, sample_entry, rs_lds_eig, rs_score_block, rs_score_add and
+// RS_HYP_BLOCK, mvba_ransac_host.h's argument checks, RsTile, rs_stop, rs_current, rs_other, RsLaps and state bits,
+// mvba_twoview.h's tv_pair_tile, mvba_init.h's resect_build_list, CamWork, rs_pass, k_resect_chunk, k_resect_combine,
+// k_resect_norm, resect_solve_camera and resect_denormalise, mvba_start.h's chunk_sum, mask_step, init_check_list, InitClock
+// and INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
 //
 // The usable observations are sorted camera-major on the host as for mvba_resect, so a camera's observations are a dense run
 // in ascending point order: sample index j of camera k is entry cam_ptr[k] + j.  The listed cameras (duplicates allowed) get
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_resect_fit(const int *__restric
   double v[NV];
 #pragma unroll
   for (int e = 0; e < NV; ++e) v[e] = 0.0;
-  if ((st & RS_ACTIVE) && i < ch_cnt[c] && ((st & RS_CUR) ? inl1 : inl0)[ch_mask[c] + i]) {
+  if ((st & RS_ACTIVE) && i < ch_cnt[c] && rs_current(st, inl0, inl1)[ch_mask[c] + i]) {
     const long long o = ch_start[c] + i;
     rs_pass<MODE>(X + 3 * (size_t)cm_pt[o], cm_xy[o], MODE == 0 ? aux : aux + RS_NORM * (size_t)k, v);
   }
@@ -140,16 +141,11 @@ __global__ __launch_bounds__(START_CHUNK) void k_resect_score(int cam0, int H, c
     Xa[0] = Xp[0]; Xa[1] = Xp[1]; Xa[2] = Xp[2];
     z = cm_xy[o];
   }
-  int mine = 0;
-  for (int hh = 0; hh < nh; ++hh) {
+  const int mine = rs_score_block(nh, lane, live, [&](int hh) {
     double d2;
-    const bool in = rr_inlier(s_P + 12 * hh, Xa, z, thr2, d2);
-    const int cnt = __popcll(__ballot(live && in));
-    if (lane == hh) mine = cnt;
-  }
-  if (mine) atomicAdd(&s_cnt[lane], mine);
-  __syncthreads();
-  if (i < nh && s_cnt[i]) atomicAdd(&hyp_count[(size_t)kl * H + h0 + i], s_cnt[i]);
+    return rr_inlier(s_P + 12 * hh, Xa, z, thr2, d2);
+  });
+  rs_score_add(mine, nh, lane, s_cnt, hyp_count + (size_t)kl * H + h0);
 }
 
 // Pcur[camera] = the 12 doubles (a matrix; R and t of a pose) of the camera's best hypothesis (best < 0: NaN), for the cnt
@@ -177,8 +173,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_resect_mask(const int *__restri
     const long long o = ch_start[c] + i;
     double d2;
     const bool in = rr_inlier(P + 12 * (size_t)k, X + 3 * (size_t)cm_pt[o], cm_xy[o], thr2, d2);
-    ((st & RS_CUR) ? inl0 : inl1)[ch_mask[c] + i] = in ? 1 : 0;
-    if (in) { v[0] = 1.0; v[1] = d2; }
+    mask_step(in, d2, &rs_other(st, inl0, inl1)[ch_mask[c] + i], v);
   }
   chunk_sum<2>(v, s_w, part + (size_t)c * 2);
 }
@@ -192,7 +187,7 @@ __global__ __launch_bounds__(START_CHUNK) void k_resect_scatter(const int *__res
                                                                 unsigned char *__restrict__ out) {
   const int c = blockIdx.x, i = threadIdx.x, st = state[ch_cam[c]];
   if (!(st & RS_OK) || i >= ch_cnt[c]) return;
-  if (((st & RS_CUR) ? inl1 : inl0)[ch_mask[c] + i]) out[cm_obs[ch_start[c] + i]] = 1;
+  if (rs_current(st, inl0, inl1)[ch_mask[c] + i]) out[cm_obs[ch_start[c] + i]] = 1;
 }
 
 // What a fit sees of robust_cameras: the call, the current tile's cameras and chunks, and the buffers every fit uses (dP: the
@@ -229,15 +224,8 @@ int robust_cameras(Fit &fit, const double *X, int64_t n_points, const int64_t *p
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
   const double thr2 = threshold * threshold;
   // the defaults are those of a camera without usable observations: status 1
-  for (int c = 0; c < nl; ++c) {
-    if (quality) quality[2 * c] = quality[2 * c + 1] = NAN;
-    if (n_usable) n_usable[c] = 0;
-    if (n_inliers) n_inliers[c] = 0;
-    if (best) best[c] = -1;
-    if (status) status[c] = 1;
-  }
+  RsTile::defaults((size_t)nl, H, status, best, hyp_count, n_usable, n_inliers, quality);
   if (inlier && n_obs) std::memset(inlier, 0, (size_t)n_obs);
-  if (hyp_count) std::fill(hyp_count, hyp_count + (size_t)nl * H, -1);
   if (nl == 0) return MVBA_OK;
 
   InitClock clk;
@@ -275,9 +263,9 @@ int robust_cameras(Fit &fit, const double *X, int64_t n_points, const int64_t *p
 
   const dim3 b256(256), bch(START_CHUNK);
   const int hb = (H + RS_HYP_BLOCK - 1) / RS_HYP_BLOCK;
-  std::vector<int> hc((size_t)tile * H), bst((size_t)tile), state((size_t)nl, 0), st((size_t)tile);
-  std::vector<long long> nin((size_t)tile);
-  std::vector<double> S2(2 * (size_t)tile), ssq((size_t)tile);
+  std::vector<int> hc((size_t)tile * H), state((size_t)nl, 0);
+  RsTile rt(tile);
+  std::vector<double> S2(2 * (size_t)tile);
   for (int c0 = 0; c0 < nl; c0 += tile) {
     const int cnt = std::min(tile, nl - c0), ch0 = w.lc_ch[c0], tch = w.lc_ch[c0 + cnt] - ch0;
     t.c0 = c0; t.cnt = cnt; t.ch0 = ch0; t.tch = tch;
@@ -309,38 +297,19 @@ int robust_cameras(Fit &fit, const double *X, int64_t n_points, const int64_t *p
     MVBA_HIP(hipMemcpy(hc.data(), t.dhc, sizeof(int) * (size_t)cnt * H, hipMemcpyDeviceToHost));
     laps.score += clk.lap();
 
-    for (int p = 0; p < cnt; ++p) {
-      const RsPick pick = rs_pick(hc.data() + (size_t)p * H, H, w.lc_n[c0 + p], Fit::MIN_OBS);
-      st[p] = pick.status;
-      bst[p] = pick.best;
-      tstate[p] = pick.state;
-    }
-    MVBA_HIP(hipMemcpy(dbest, bst.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+    rt.pick(cnt, tstate, hc.data(), H, w.lc_n.data() + c0, Fit::MIN_OBS);
+    MVBA_HIP(hipMemcpy(dbest, rt.best.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_resect_gather, dim3((cnt * 12 + 255) / 256), b256, 0, 0, cnt, H, dbest, t.dhypP, t.dP + 12 * (size_t)c0);
     fit.picked(t, dbest);
     if ((rc = mask()) || (rc = fit.fetch(t, true))) return rc;
-    int n_active = 0;
-    for (int p = 0; p < cnt; ++p) {
-      if (st[p]) continue;
-      tstate[p] ^= RS_CUR;
-      nin[p] = (long long)S2[2 * p];
-      ssq[p] = S2[2 * p + 1];
-      ++n_active;
-    }
+    rt.first(S2.data(), [](int) { return 0; });  // (a hypothesis is a model as it is)
     laps.other += clk.lap();
 
-    for (int r = 0; r < n_refit && n_active > 0; ++r) {
-      if ((rc = put_state()) || (rc = fit.refit(t, tstate, n_active))) return rc;
-      if (n_active == 0) break;
+    for (int r = 0; r < n_refit && rt.n_active > 0; ++r) {
+      if ((rc = put_state()) || (rc = fit.refit(t, tstate, rt.n_active))) return rc;
+      if (rt.n_active == 0) break;
       if ((rc = mask()) || (rc = fit.fetch(t, false))) return rc;
-      for (int p = 0; p < cnt; ++p) {
-        if (!(tstate[p] & RS_ACTIVE)) continue;
-        const long long c = (long long)S2[2 * p];
-        if (!rs_accept(c, nin[p], r, Fit::FIRST_MIN, tstate[p], n_active)) continue;
-        nin[p] = c;
-        ssq[p] = S2[2 * p + 1];
-        fit.keep(p);
-      }
+      rt.accept(r, S2.data(), Fit::FIRST_MIN, [&](int p) { fit.keep(p); });
     }
     laps.refit += clk.lap();
 
@@ -349,19 +318,7 @@ int robust_cameras(Fit &fit, const double *X, int64_t n_points, const int64_t *p
       hipLaunchKernelGGL(k_resect_scatter, t.gch, bch, 0, 0, t.tcam, t.tstart, t.tmask, t.tcnt, dobs, t.dstate, t.dinl0, t.dinl1, dout);
       MVBA_HIP(hipGetLastError());
     }
-    for (int p = 0; p < cnt; ++p) {
-      const size_t g = (size_t)c0 + p;
-      if (status) status[g] = st[p];
-      if (best) best[g] = bst[p];
-      if (hyp_count) std::copy(hc.begin() + (size_t)p * H, hc.begin() + (size_t)(p + 1) * H, hyp_count + g * H);
-      if (st[p]) continue;
-      const double q1 = fit.output(p, g);
-      if (n_inliers) n_inliers[g] = nin[p];
-      if (quality) {
-        quality[2 * g] = sqrt(ssq[p] / (double)nin[p]);
-        quality[2 * g + 1] = q1;
-      }
-    }
+    rt.write((size_t)c0, status, best, hyp_count, n_inliers, quality, [&](int p) { return fit.output(p, (size_t)c0 + p); });
     laps.other += clk.lap();
   }
   if (inlier) MVBA_HIP(hipMemcpy(inlier, dout, (size_t)n_obs, hipMemcpyDeviceToHost));
@@ -459,13 +416,7 @@ struct ResectFit {
 extern "C" {
 
 int mvba_resect_sample(uint64_t seed, int32_t k, int32_t h, int64_t n, int64_t *idx6) {
-  if (!idx6) return fail(MVBA_ERR_BADARG, "null argument: idx6 (argument 5)");
-  if (n < RR_MIN_OBS || n >= (1LL << 31)) return fail(MVBA_ERR_BADARG, "n = " + std::to_string(n) + " must be in 6 .. 2^31 - 1");
-  if (k < 0 || h < 0) return fail(MVBA_ERR_BADARG, "k = " + std::to_string(k) + ", h = " + std::to_string(h) + ": negative index");
-  long long idx[6];
-  rs_sample(seed, k, k, h, n, idx);
-  for (int c = 0; c < 6; ++c) idx6[c] = idx[c];
-  return MVBA_OK;
+  return sample_entry<RR_MIN_OBS>(seed, "kh", k, k, h, n, idx6, "idx6", 5);
 }
 
 int mvba_resect_robust(const double *X, int64_t n_points, const int64_t *pt_ptr, const int32_t *cam_idx, const double *xy, int64_t n_obs,

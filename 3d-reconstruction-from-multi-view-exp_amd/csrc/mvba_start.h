@@ -4,7 +4,9 @@
 // here runs on the LM path.  
 //
 // One copy each of: the fixed reduction tree of a 256-thread chunk (chunk_sum; the cyclic Jacobi, its eigenvalue selection and
-// INIT_REL_PIVOT are mvba_ransac_host.h's, which the host-side solves use too), the host clock and event guard, the checks of an observation list, of a pair list and of ascending camera
+// INIT_REL_PIVOT are mvba_ransac_host.h's, which the host-side solves use too), the flags of a chunk counted and ranked
+// (chunk_ballot, chunk_total, chunk_rank: the compactions of mvba_ransac.h and mvba_align.h), the mask step of a robust fit
+// (mask_step), the host clock and event guard, the checks of an observation list, of a pair list and of ascending camera
 // runs, and the upload of a list.  Every floating-point sum of these entry points is taken in an order that the sizes alone
 // fix: chunk_sum inside a chunk, then k_resect_combine (serial, ascending chunks) or k_twoview_combine (lane-strided, then
 // the shuffle tree) over a camera's or a pair's chunks -- two orders, on purpose.
@@ -33,6 +35,40 @@ __device__ __forceinline__ void chunk_sum(const double (&v)[NV], double (&s_w)[S
     for (int w = 1; w < START_CHUNK / 64; ++w) x += s_w[w][i];
     out[i] = x;
   }
+}
+
+// The flags of a chunk, one per thread: the wave's ballot, with every wave's popcount in s_w.  Every thread of the workgroup
+// calls it (a barrier inside); chunk_total and chunk_rank read s_w after it.
+__device__ __forceinline__ unsigned long long chunk_ballot(bool flag, int (&s_w)[START_CHUNK / 64]) {
+  const int i = threadIdx.x;
+  const unsigned long long b = __ballot(flag);
+  if ((i & 63) == 0) s_w[i >> 6] = __popcll(b);
+  __syncthreads();
+  return b;
+}
+
+// the number of set flags of the chunk
+__device__ __forceinline__ int chunk_total(const int (&s_w)[START_CHUNK / 64]) {
+  int x = 0;
+#pragma unroll
+  for (int w = 0; w < START_CHUNK / 64; ++w) x += s_w[w];
+  return x;
+}
+
+// the number of set flags below this thread's: the lower lanes of its wave's ballot b, and the lower waves
+__device__ __forceinline__ int chunk_rank(unsigned long long b, const int (&s_w)[START_CHUNK / 64]) {
+  const int i = threadIdx.x;
+  int j = __popcll(b & ((1ull << (i & 63)) - 1ull));
+  for (int w = 0; w < (i >> 6); ++w) j += s_w[w];
+  return j;
+}
+
+// The mask step of a robust fit, for one item with a model to test it against: the inlier byte, and v = (1, d2) for an inlier
+// -- what chunk_sum<2> then adds up to (count, sum of d^2); v is (0, 0) beforehand, and stays so for an outlier and for a
+// thread without an item.
+__device__ __forceinline__ void mask_step(bool in, double d2, unsigned char *byte, double (&v)[2]) {
+  *byte = in ? 1 : 0;
+  if (in) { v[0] = 1.0; v[1] = d2; }
 }
 
 struct InitClock {

@@ -229,6 +229,21 @@ def _obs_list(pt_ptr, cam_idx, xy, m, n_points=None):
     return n, n_obs, pt_ptr.ctypes.data_as(C.POINTER(C.c_int64)), cam_idx.ctypes.data_as(C.POINTER(C.c_int32)), xy
 
 
+def _point_ok_ptr(point_ok, n):
+    """``point_ok`` (n,) as bytes and the pointer a call takes: ``(array, pointer)``, both None for ``point_ok=None``.  The
+    array comes back with the pointer because it has to stay alive until the call has returned."""
+    if point_ok is None:
+        return None, None
+    ok = _as(np.asarray(point_ok) != 0, np.uint8)
+    assert ok.shape == (n,)
+    return ok, ok.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _seed64(seed):
+    """A seed as the C interface takes it: modulo 2^64."""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
 def _timings3(tm):
     return dict(zip(("upload", "kernel", "download"), tm.tolist()))
 
@@ -521,11 +536,7 @@ def resect(X, pt_ptr, cam_idx, xy, n_images, point_ok=None, device=-1):
     n, m = X.shape[0], int(n_images)
     assert X.shape == (n, 3)
     _, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m, n)
-    okp = None
-    if point_ok is not None:
-        ok = _as(np.asarray(point_ok) != 0, np.uint8)
-        assert ok.shape == (n,)
-        okp = ok.ctypes.data_as(C.POINTER(C.c_uint8))
+    ok, okp = _point_ok_ptr(point_ok, n)
     P, q, st, tm = np.empty((m, 3, 4)), np.empty((m, 2)), np.empty(m, np.int32), np.zeros(3)
     raise_for(lib.mvba_resect(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, _ptr(P), _ptr(q), st.ctypes.data_as(C.POINTER(C.c_int32)),
                               _ptr(tm), int(device)), lib)
@@ -592,8 +603,24 @@ def _sample(name, n_idx, seed, *index):
     """The ``n_idx`` indices a ``*_sample`` entry point writes for ``seed`` (taken modulo 2^64) and its integer arguments."""
     lib = load_library()
     idx = np.empty(n_idx, np.int64)
-    raise_for(getattr(lib, name)(int(seed) & 0xFFFFFFFFFFFFFFFF, *(int(v) for v in index), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
+    raise_for(getattr(lib, name)(_seed64(seed), *(int(v) for v in index), idx.ctypes.data_as(C.POINTER(C.c_int64))), lib)
     return idx
+
+
+def _pairs_robust(entry, key, pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses, seed, n_refit, return_inliers, return_counts,
+                  device):
+    """``two_view_robust`` and ``homography_robust``: the C entry point ``entry``, whose matrices come back under ``key``."""
+    lib = load_library()
+    _require_device(entry)
+    xy, m = _as(xy, np.float64), int(n_images)
+    pairs = _as(pairs, np.int32).reshape(-1, 2)
+    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
+    P, H = pairs.shape[0], int(n_hypotheses)
+    M = np.empty((P, 3, 3))
+    tail, result = _robust_outputs({key: M}, P, "n_shared", H, (P, n) if return_inliers else None, return_counts)
+    raise_for(getattr(lib, entry)(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, float(threshold), H,
+                                  _seed64(seed), int(n_refit), _ptr(M), *tail, int(device)), lib)
+    return result()
 
 
 def two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses=512, seed=0, n_refit=2, return_inliers=True,
@@ -604,17 +631,8 @@ def two_view_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypothese
     (P,) (0 ok, 1 fewer than 8 shared points, 2 every hypothesis degenerate, 4 best count below 8; F and quality NaN then),
     ``inlier (P, N) bool`` (``return_inliers``: P x N bytes on the host and on the device), ``hyp_count (P, H) int32``
     (``return_counts``), ``timings_ms``.  No CPU fallback."""
-    lib = load_library()
-    _require_device("mvba_two_view_robust")
-    xy, m = _as(xy, np.float64), int(n_images)
-    pairs = _as(pairs, np.int32).reshape(-1, 2)
-    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
-    P, H = pairs.shape[0], int(n_hypotheses)
-    F = np.empty((P, 3, 3))
-    tail, result = _robust_outputs({"F": F}, P, "n_shared", H, (P, n) if return_inliers else None, return_counts)
-    raise_for(lib.mvba_two_view_robust(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, float(threshold), H,
-                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(F), *tail, int(device)), lib)
-    return result()
+    return _pairs_robust("mvba_two_view_robust", "F", pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses, seed, n_refit,
+                         return_inliers, return_counts, device)
 
 
 def ransac_sample(seed, k, l, h, n):
@@ -630,17 +648,8 @@ def homography_robust(pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypothe
     x_l ~ H x_k, |H| = 1, largest entry positive -- in the place of F; ``quality (P, 2)`` is the RMS symmetric transfer distance
     over the final inliers and the eigenvalue ratio of the last kept refit; ``status`` 0 ok, 1 fewer than 4 shared points, 2
     every hypothesis degenerate, 4 best count below 4.  No CPU fallback."""
-    lib = load_library()
-    _require_device("mvba_homography_robust")
-    xy, m = _as(xy, np.float64), int(n_images)
-    pairs = _as(pairs, np.int32).reshape(-1, 2)
-    n, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m)
-    P, H = pairs.shape[0], int(n_hypotheses)
-    Hm = np.empty((P, 3, 3))
-    tail, result = _robust_outputs({"H": Hm}, P, "n_shared", H, (P, n) if return_inliers else None, return_counts)
-    raise_for(lib.mvba_homography_robust(n, m, pp, cp, _ptr(xy), n_obs, pairs.ctypes.data_as(C.POINTER(C.c_int32)), P, float(threshold), H,
-                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(Hm), *tail, int(device)), lib)
-    return result()
+    return _pairs_robust("mvba_homography_robust", "H", pt_ptr, cam_idx, xy, n_images, pairs, threshold, n_hypotheses, seed, n_refit,
+                         return_inliers, return_counts, device)
 
 
 def homography_sample(seed, k, l, h, n):
@@ -664,17 +673,13 @@ def resect_robust(X, pt_ptr, cam_idx, xy, n_images, threshold, point_ok=None, ca
     n, m = X.shape[0], int(n_images)
     assert X.shape == (n, 3)
     _, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m, n)
-    okp = None
-    if point_ok is not None:
-        ok = _as(np.asarray(point_ok) != 0, np.uint8)
-        assert ok.shape == (n,)
-        okp = ok.ctypes.data_as(C.POINTER(C.c_uint8))
+    ok, okp = _point_ok_ptr(point_ok, n)
     cams = None if cameras is None else _as(cameras, np.int32).reshape(-1)
     nc, H = m if cams is None else cams.shape[0], int(n_hypotheses)
     P = np.empty((max(nc, 0), 3, 4))
     tail, result = _robust_outputs({"P": P}, nc, "n_usable", H, n_obs if return_inliers else None, return_counts)
     raise_for(lib.mvba_resect_robust(_ptr(X), n, pp, cp, _ptr(xy), n_obs, m, okp, None if cams is None else cams.ctypes.data_as(C.POINTER(C.c_int32)),
-                                     nc, float(threshold), H, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refit), _ptr(P), *tail, int(device)), lib)
+                                     nc, float(threshold), H, _seed64(seed), int(n_refit), _ptr(P), *tail, int(device)), lib)
     return result()
 
 
@@ -691,11 +696,7 @@ def _pose_args(X, pt_ptr, cam_idx, xy, K, point_ok, cameras):
     n, m = X.shape[0], K.shape[0]
     assert X.shape == (n, 3) and K.shape == (m, 3, 3)
     _, n_obs, pp, cp, xy = _obs_list(pt_ptr, cam_idx, xy, m, n)
-    ok, okp = None, None
-    if point_ok is not None:
-        ok = _as(np.asarray(point_ok) != 0, np.uint8)
-        assert ok.shape == (n,)
-        okp = ok.ctypes.data_as(C.POINTER(C.c_uint8))
+    ok, okp = _point_ok_ptr(point_ok, n)
     cams = None if cameras is None else _as(cameras, np.int32).reshape(-1)
     nc = m if cams is None else cams.shape[0]
     return (X, ok, cams), n, n_obs, m, pp, cp, xy, okp, K, None if cams is None else cams.ctypes.data_as(C.POINTER(C.c_int32)), nc
@@ -717,7 +718,7 @@ def pose_robust(X, pt_ptr, cam_idx, xy, K, threshold, point_ok=None, cameras=Non
     R, t = np.empty((nc, 3, 3)), np.empty((nc, 3))
     tail, result = _robust_outputs({"R": R, "t": t}, nc, "n_usable", H, n_obs if return_inliers else None, return_counts)
     raise_for(lib.mvba_pose_robust(_ptr(keep[0]), n, pp, cp, _ptr(xy), n_obs, m, okp, _ptr(K), camp, nc, float(threshold), H,
-                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refine), int(n_refit), _ptr(R), _ptr(t), *tail, int(device)), lib)
+                                   _seed64(seed), int(n_refine), int(n_refit), _ptr(R), _ptr(t), *tail, int(device)), lib)
     return result()
 
 
@@ -769,7 +770,7 @@ def triangulate_robust(K, R, t, pt_ptr, cam_idx, xy, threshold, n_hypotheses=64,
     st, ni, best, inl = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n_obs, np.uint8)
     hc = np.empty((n, max(H, 0)), np.int32) if return_counts else None
     raise_for(lib.mvba_triangulate_robust(_ptr(K), _ptr(R), _ptr(t), m, n, pp, cp, _ptr(xy), n_obs, float(threshold), H,
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_refine), int(n_refit), _ptr(X), _ptr(q), st.ctypes.data_as(i32),
+                                          _seed64(seed), int(n_refine), int(n_refit), _ptr(X), _ptr(q), st.ctypes.data_as(i32),
                                           ni.ctypes.data_as(i32), best.ctypes.data_as(i32), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
                                           hc.ctypes.data_as(i32) if return_counts else None, _ptr(tm), int(device)), lib)
     out = {"X": X, "quality": q, "status": st, "n_inliers": ni, "best": best, "inlier": inl.astype(bool),
@@ -791,11 +792,7 @@ def _align_args(src, dst, ok):
     src, dst = _as(src, np.float64), _as(dst, np.float64)
     n = src.shape[0]
     assert src.shape == (n, 3) and dst.shape == (n, 3)
-    okb, okp = None, None
-    if ok is not None:
-        okb = _as(np.asarray(ok) != 0, np.uint8)
-        assert okb.shape == (n,)
-        okp = okb.ctypes.data_as(C.POINTER(C.c_uint8))
+    okb, okp = _point_ok_ptr(ok, n)
     return src, dst, okb, okp, n
 
 
@@ -819,7 +816,7 @@ def align_robust(src, dst, threshold, ok=None, with_scale=True, n_hypotheses=512
     nu, ni, best, st = C.c_int64(0), C.c_int64(0), C.c_int32(-1), C.c_int32(1)
     inl = np.empty(n, np.uint8)
     hc = np.empty(max(H, 0), np.int32) if return_counts else None
-    raise_for(lib.mvba_align_robust(n, _ptr(src), _ptr(dst), okp, int(bool(with_scale)), float(threshold), H, int(seed) & 0xFFFFFFFFFFFFFFFF,
+    raise_for(lib.mvba_align_robust(n, _ptr(src), _ptr(dst), okp, int(bool(with_scale)), float(threshold), H, _seed64(seed),
                                     int(n_refit), _ptr(sim), _ptr(q), C.byref(nu), C.byref(ni), C.byref(best), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
                                     None if hc is None else hc.ctypes.data_as(i32), C.byref(st), _ptr(tm), int(device)), lib)
     out = {**_similarity(sim), "quality": q, "n_usable": nu.value, "n_inliers": ni.value, "best": best.value, "status": st.value,
