@@ -13,7 +13,8 @@ Correctness therefore rests on properties of the generated code that no C++ rule
   3. M0 (the LDS-DMA destination base) is written by the gathers' own `s_mov_b32 m0, ...` only;
   4. the kernel fits three waves per SIMD (<= 168 VGPRs); registers it spills are touched outside the loops only
      (that is property 1).
-k_schur_lanes (one lane per item, the same loop with 13 / 17 gathers in flight) is checked for properties 1 and 2.
+k_schur_lanes (one lane per item, the same loop with 13 / 17 gathers in flight) and k_schur_lanes_compact (12 / 13) are checked
+for properties 1 and 2.
 Usage: check_isa.py mvba.s   (exit status 0 = all properties hold)."""
 import re
 import sys
@@ -23,7 +24,9 @@ import sys
 KERNELS = {"k_schur_slots": (("vmcnt(7)", 7), ("vmcnt(8)", 8)),
            # one lane per item: 13 / 17 gathers stay in flight behind the index row, 14 / 18 operations per iteration; the wait
            # stands in the prologue too, outside every loop
-           "k_schur_lanes": (("vmcnt(13)", 14), ("vmcnt(17)", 18))}
+           "k_schur_lanes": (("vmcnt(13)", 14), ("vmcnt(17)", 18)),
+           # the same on the compact record: 4 + 1 + 7 = 12 / 4 + 4 + 5 = 13 gathers
+           "k_schur_lanes_compact": (("vmcnt(12)", 13), ("vmcnt(13)", 14))}
 # properties 3 and 4 (M0, three waves per SIMD) are k_schur_slots' alone: k_schur_lanes is launched one wave per SIMD
 SLOTS_ONLY = "k_schur_slots"
 VM_LOOP_OPS = ("global_load_lds_dwordx4", "global_load_lds_dword ")

@@ -1,4 +1,5 @@
-// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas) and the host logic of a RANSAC
+// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas; also its
+// expand_compact_record, the compact linearisation record as mvba_debug_read expands it) and the host logic of a RANSAC
 // round (mvba_ransac_host.h: rs_pick, rs_accept, rs_current and rs_other, RsTile, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
 // builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify) and the matcher's (mvba_match_host.h: its argument
 // checks, the chunk rule, the ratio test) on hand-made inputs.  A program of its own,
@@ -499,6 +500,29 @@ int main() {
     CHECK(run(3, kp, desc, 32, self, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "pairs[1] = (2, 2): an image is not matched with itself");
     CHECK(run(2, huge, desc, 32, twice, 2, 0.8, mp, kpp, d2, counts) == MVBA_ERR_BADARG && g_err == "Q = 2147483648 queries up to pair 1: the sum over the pairs must be < 2^31");
     CHECK(run(2, huge, desc, 32, twice, 1, 0.8, mp, kpp, d2, counts) == MVBA_OK && Q == (1LL << 30));
+  }
+  {  // the compact record expanded for mvba_debug_read (expand_compact_record) against obs_math's own rows: slots 0..3 and the
+     // residual pass through, J_omega = (row of J_X) x (X - t) to 1e-14 of the largest entry; a unit case by hand
+    const double f0 = 600.0, th = 0.3;
+    const double cam[CAM_IN] = {1.1 * f0, 7.0, -5.0, 0.4, -0.2, -3.0, cos(th), 0.0, sin(th), 0.0, 1.0, 0.0, -sin(th), 0.0, cos(th)};
+    alignas(16) double c18[CAM_LDS];
+    expand_cam(cam, f0, c18);
+    const double X[3] = {0.7, -0.4, 2.5};
+    ObsJ J;
+    obs_math(X[0], X[1], X[2], c18, 31.0, -12.0, f0, J);
+    double c8[8], e2[2] = {J.e0, J.e1}, full[16];
+    for (int i = 0; i < 3; ++i) { c8[2 * i] = J.jx[0][i]; c8[2 * i + 1] = J.jx[1][i]; }
+    c8[6] = J.jc[0][0]; c8[7] = J.jc[1][0];
+    expand_compact_record(c8, e2, X, cam + 3, full);
+    for (int i = 0; i < 8; ++i) CHECK(full[i] == c8[i]);
+    CHECK(full[14] == J.e0 && full[15] == J.e1);
+    double big = 0.0;
+    for (int rr = 0; rr < 2; ++rr) for (int i = 6; i < 9; ++i) big = std::max(big, std::fabs(J.jc[rr][i]));
+    CHECK(big > 0.0);
+    for (int rr = 0; rr < 2; ++rr) for (int i = 0; i < 3; ++i) CHECK(std::fabs(full[8 + 2 * i + rr] - J.jc[rr][6 + i]) <= 1e-14 * big);
+    const double jx[8] = {1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0}, zero[3] = {0.0, 0.0, 0.0}, d[3] = {2.0, 3.0, 5.0};
+    expand_compact_record(jx, e2, d, zero, full);  // rows e_x, e_y; d = (2, 3, 5): e_x x d = (0, -5, 3), e_y x d = (5, 0, -2)
+    CHECK(full[8] == 0.0 && full[10] == -5.0 && full[12] == 3.0 && full[9] == 5.0 && full[11] == 0.0 && full[13] == -2.0);
   }
   if (failures) return 1;
   std::printf("host_check ok\n");

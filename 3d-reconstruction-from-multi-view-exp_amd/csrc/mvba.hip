@@ -171,6 +171,11 @@ struct mvba_handle {
   bool have_params = false, linearized = false, have_trial = false;
   // linearisation
   double2 *d_rec = nullptr;  // [n_obs][8] double2: one 128-B line per observation
+  // the compact record (decided by mvba_create: lane form, squared loss, camera table in LDS, not MVBA_REC=full):
+  // d_rec is [n_obs + 1][REC_C] -- J_X and d/df --, the residuals are d_res [n_obs + 1], PB carries X_a; d_rec_full is the full-layout
+  // buffer mvba_covariance re-linearises into for its point pass, allocated on its first call
+  bool rec_compact = false;
+  double2 *d_res = nullptr, *d_rec_full = nullptr;
   double *d_PL = nullptr, *d_PB = nullptr;
   // reduced system: [A (9m x 9m) | b (9m)] contiguous for the all-reduce
   double *d_Ab = nullptr, *d_Ared = nullptr, *d_Ztiles = nullptr, *d_Lblk = nullptr, *d_dxi = nullptr, *d_dX = nullptr, *d_lu = nullptr;
@@ -463,6 +468,7 @@ struct CreateKnobs {
   bool schur_slots = false, schur_lanes = false, schur_pairs = false, schur_dense = false;  // ... unless it is `dense`)
   bool index_host = false, index_global = false;  // MVBA_INDEX=host | global: where the Schur index is built
   bool force_big = false;                      // MVBA_FORCE_BIG
+  bool rec_full = false;                       // MVBA_REC=full: the 128-byte record on a lane-form engine too
   bool chol_launches = false;                  // MVBA_CHOL=launches
   int trail64_min = 200;                       // MVBA_TRAIL64_MIN
   unsigned barrier_polls = 1u << 22;           // MVBA_CHOL_BARRIER_POLLS
@@ -484,6 +490,7 @@ CreateKnobs read_create_knobs() {
   k.index_host = is(index, "host");
   k.index_global = is(index, "global");
   k.force_big = getenv("MVBA_FORCE_BIG") != nullptr;
+  k.rec_full = is(getenv("MVBA_REC"), "full");
   k.chol_launches = is(getenv("MVBA_CHOL"), "launches");
   if (const char *ev = getenv("MVBA_TRAIL64_MIN")) k.trail64_min = std::max(0, atoi(ev));
   if (const char *ev = getenv("MVBA_CHOL_BARRIER_POLLS")) k.barrier_polls = (unsigned)std::max(0LL, atoll(ev));
@@ -626,13 +633,19 @@ int mvba_cost(mvba_handle *h, double *E) {
 namespace {
 // The launches the LM step shares with mvba_covariance.  The callers put their own Timed scopes around them, so that the
 // covariance does not add to the per-kernel statistics.
-void launch_resid_jac(mvba_handle *h) {  // K1 with K2 fused in, at the committed state
+// `full_rec`: a compact engine's full-layout buffer for mvba_covariance's point pass (null: the engine's own records, in its layout)
+void launch_resid_jac(mvba_handle *h, double2 *full_rec = nullptr) {  // K1 with K2 fused in, at the committed state
   const int kt = h->k1_threads;  // 8 waves share one camera table: 2 blocks = 16 waves per CU
   cam_tables(h, h->d_cam15[h->cur], nullptr);
   const int wpb = kt / 64;
   const int grid = std::max(1, std::min(2048 * 256 / kt, (h->n_tiles + wpb - 1) / wpb));
+  if (h->rec_compact && !full_rec)  // (squared loss, camera table in LDS: mvba_create)
+    hipLaunchKernelGGL((k_resid_jac<false, LOSS_SQUARED, CompactRec>), dim3(grid), dim3(kt), k1_lds_bytes(h->m, false, kt), h->stream, h->nobs, h->m,
+                       h->d_cam15[h->cur], h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
+                       h->d_tile_slot, h->d_PLsplit, h->d_cam18, CompactRec{h->d_res});
+  else
   launch_loss(h, resid_jac_kernel(h->gcam, h->loss), dim3(grid), dim3(kt), k1_lds_bytes(h->m, h->gcam, kt), h->nobs, h->m, h->d_cam15[h->cur],
-              h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, h->d_rec, h->d_PL,
+              h->d_X[h->cur], h->d_obs_pt, h->d_cam, h->d_xy, h->f0, h->d_tiles, h->n_tiles, full_rec ? full_rec : h->d_rec, h->d_PL,
               h->d_tile_slot, h->d_PLsplit, h->d_cam18);
   if (h->n_splits)
     hipLaunchKernelGGL(k_sum_split, dim3((9 * h->n_splits + 255) / 256), dim3(256), 0, h->stream, h->n_splits, h->d_splits,
@@ -646,12 +659,13 @@ void launch_point_inv(mvba_handle *h, double c) {  // K3a (also clears the packe
   const unsigned grid = (unsigned)std::max<long long>((h->N + 255) / 256, std::min<long long>((nAb + 1023) / 1024, 4096));
   const long long nprog = h->slot_w == LANES_W ? 0 : (long long)h->slot_nR * h->slot_nseg * PACE_STRIDE;
   const int want_r = h->schur_mode == SCHUR_DENSE ? 1 : 0;
+  const double *Xc = h->rec_compact ? h->d_X[h->cur] : nullptr;  // a compact engine's point rows carry X_a (the state K1 linearised at)
   if (h->n_held)  // held points (mvba_set_point_hold): the masked form; without a mask the launch is the one it always was
     hipLaunchKernelGGL(k_point_inv<const uint8_t *>, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
-                       h->d_Ab, nAb, h->d_prog, nprog, want_r, (const uint8_t *)h->d_held);
+                       h->d_Ab, nAb, h->d_prog, nprog, want_r, Xc, (const uint8_t *)h->d_held);
   else
     hipLaunchKernelGGL(k_point_inv<>, dim3(std::max(grid, 1u)), dim3(256), 0, h->stream, h->N, c, h->d_PL, h->d_PB, h->d_flag,
-                       h->d_Ab, nAb, h->d_prog, nprog, want_r);
+                       h->d_Ab, nAb, h->d_prog, nprog, want_r, Xc);
 }
 
 void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b] of this rank's points
@@ -662,7 +676,10 @@ void launch_schur(mvba_handle *h, double c) {  // K3 in the engine's form: [A|b]
     // 64-bit offsets only when the records or the point blocks (+ the padding row) span 4 GiB (MVBA_FORCE_BIG: at test sizes too)
     const bool big = (std::max<long long>(h->nobs, h->N) + 1) * 128LL >= (1LL << 32) || h->force_big;
     if (h->schur_mode == SCHUR_SLOTS && h->slot_w == LANES_W) {
-      if (h->n_waves)
+      if (h->n_waves && h->rec_compact)
+        hipLaunchKernelGGL(k_schur_lanes_compact, dim3(h->n_waves), dim3(64), LANES_LDS_C, h->stream, h->d_wdesc, h->d_wunits, h->d_it_x, h->d_rec,
+                           h->d_PB, c, h->f0, h->d_partial, h->slot_nR, h->d_range_o0, h->d_res, h->d_units, h->d_cam15[h->cur]);
+      else if (h->n_waves)
         hipLaunchKernelGGL(k_schur_lanes, dim3(h->n_waves), dim3(64), LANES_LDS, h->stream, h->d_wdesc, h->d_wunits, h->d_it_x, h->d_rec, h->d_PB, c,
                            h->f0, h->d_partial, h->slot_nR, h->d_range_o0);
     } else if (h->schur_mode == SCHUR_SLOTS) {
@@ -1145,6 +1162,9 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
   // (mv <= m); k_map_cov_expand then fills the real table with P Sigma' P^T.
   const int mv = (D + 6) / 9 + 1;
   if (!local_rc && h->mapped && D > 0 && !h->d_cov_sigv) local_rc = h->mem.alloc(&h->d_cov_sigv, n_sig);
+  // A compact engine: the point pass reads J_omega of both observations of a pair -- it gets full-layout records of its own, from a
+  // second K1 launch below (the same E_a and dP_a once more), rather than a second layout of k_point_cov
+  if (!local_rc && h->rec_compact && point_cov && h->nobs && !h->d_rec_full) local_rc = h->mem.alloc(&h->d_rec_full, (size_t)REC * h->nobs);
   const bool sharded = h->comm || h->host_ar;
   if (local_rc && !sharded) return local_rc;
   const std::string local_err = local_rc ? g_err : std::string();
@@ -1152,6 +1172,7 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
   if (!local_rc) {
     MVBA_HIP(hipEventRecord(ev[0], h->stream));
     // 1-4: the LM step's launches at c = 0 (K1, K3a, K3 in the engine's form, the all-reduce of [A|b])
+    if (h->nobs && h->rec_compact && point_cov) launch_resid_jac(h, h->d_rec_full);
     if (h->nobs) launch_resid_jac(h);
     h->linearized = true; h->have_trial = false;
     launch_point_inv(h, 0.0);
@@ -1209,7 +1230,7 @@ int mvba_covariance(mvba_handle *h, double *point_cov, double *cam_cov, double *
     const unsigned grid = (unsigned)std::min<long long>(8192, (h->N * G + 255) / 256);
     auto launch = [&](auto kern, auto... held) {
       hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->stream, h->N, m, (const long long *)h->d_pt_ptr, (const int *)h->d_cam,
-                         (const double2 *)h->d_rec, (const double *)h->d_PL, (const double *)h->d_cov_sig, 1.0 / h->f0, h->d_cov_pts,
+                         (const double2 *)(h->rec_compact ? h->d_rec_full : h->d_rec), (const double *)h->d_PL, (const double *)h->d_cov_sig, 1.0 / h->f0, h->d_cov_pts,
                          h->d_flag, held...);
     };
     if (h->n_held) {  // held points skip the pair loop and the pivot test: six zeros
@@ -1343,7 +1364,8 @@ int mvba_get_info(mvba_handle *h, int64_t *out8) {
   out8[0] = h->n_items;
   out8[1] = h->n_items_offdiag;
   out8[2] = h->n_units;
-  out8[3] = h->schur_mode | (h->schur_mode == SCHUR_SLOTS ? h->slot_w << 8 : 0);  // bits 8..15: the slot form's step width
+  // bits 8..15: the slot form's step width; bit 16: the engine linearises into the compact record
+  out8[3] = h->schur_mode | (h->schur_mode == SCHUR_SLOTS ? h->slot_w << 8 : 0) | (h->rec_compact ? 1 << 16 : 0);
   out8[4] = h->rccl_version;
   out8[5] = NCCL_VERSION_CODE;
   out8[6] = h->nranks;
@@ -1425,6 +1447,19 @@ int mvba_debug_read(mvba_handle *h, int32_t which, double *out, int64_t capacity
   auto d2h = [&](const void *src, size_t bytes) { return hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost); };
   if (which == MVBA_BUF_RESIDUAL || which == MVBA_BUF_JX || which == MVBA_BUF_JC) {
     std::vector<double> r((size_t)2 * REC * h->nobs);  // expand the records on the host
+    if (h->rec_compact) {  // ... from the compact ones, the residuals, the committed points and centres (where K1 linearised)
+      const size_t no = (size_t)h->nobs;
+      std::vector<double> c8(2 * REC_C * no), e2(2 * no), X(3 * (size_t)h->N), cam((size_t)CAM_IN * h->m);
+      std::vector<int> pt(no), ck(no);
+      MVBA_HIP(hipMemcpy(c8.data(), h->d_rec, sizeof(double) * c8.size(), hipMemcpyDeviceToHost));
+      MVBA_HIP(hipMemcpy(e2.data(), h->d_res, sizeof(double) * e2.size(), hipMemcpyDeviceToHost));
+      MVBA_HIP(hipMemcpy(X.data(), h->d_X[h->cur], sizeof(double) * X.size(), hipMemcpyDeviceToHost));
+      MVBA_HIP(hipMemcpy(cam.data(), h->d_cam15[h->cur], sizeof(double) * cam.size(), hipMemcpyDeviceToHost));
+      MVBA_HIP(hipMemcpy(pt.data(), h->d_obs_pt, sizeof(int) * no, hipMemcpyDeviceToHost));
+      MVBA_HIP(hipMemcpy(ck.data(), h->d_cam, sizeof(int) * no, hipMemcpyDeviceToHost));
+      for (size_t o = 0; o < no; ++o)
+        expand_compact_record(&c8[2 * REC_C * o], &e2[2 * o], &X[3 * (size_t)pt[o]], &cam[(size_t)CAM_IN * ck[o] + 3], &r[2 * REC * o]);
+    } else
     MVBA_HIP(hipMemcpy(r.data(), h->d_rec, sizeof(double) * r.size(), hipMemcpyDeviceToHost));
     std::vector<double> sw;  // a robust loss: the implied (u, v) columns are sqrt(w) / f0, as the Schur kernels take them
     if (h->loss != LOSS_SQUARED && which == MVBA_BUF_JC) {

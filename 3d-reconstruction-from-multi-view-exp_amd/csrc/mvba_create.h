@@ -768,14 +768,19 @@ int alloc_engine_buffers(mvba_handle *h, K1Tiles &t) {
   }
   CR(h->mem.alloc(&h->d_tiles, t.tiles.size()));
   for (int i = 0; i < 2; ++i) { CR(h->mem.alloc(&h->d_X[i], 3 * N)); CR(h->mem.alloc(&h->d_cam15[i], (size_t)CAM_IN * m)); }
-  CR(h->mem.alloc(&h->d_rec, (size_t)REC * (nobs + 1)));  // + the all-zero record and point row the slot form's padding points at
+  const int rec_slots = h->rec_compact ? REC_C : REC;
+  CR(h->mem.alloc(&h->d_rec, (size_t)rec_slots * (nobs + 1)));  // + the all-zero record and point row the slot form's padding points at
+  if (h->rec_compact) {  // the residuals beside the compact records, the padding record's among them
+    CR(h->mem.alloc(&h->d_res, (size_t)nobs + 1));
+    CRH(hipMemset(h->d_res + nobs, 0, sizeof(double2)));
+  }
   if (h->loss != LOSS_SQUARED) {
     CR(h->mem.alloc(&h->d_sqw, nobs + 1));
     CRH(hipMemset(h->d_sqw, 0, sizeof(double) * (nobs + 1)));
   }
   CR(h->mem.alloc(&h->d_PL, 9 * N));
   CR(h->mem.alloc(&h->d_PB, (size_t)PBS * (N + 1)));
-  CRH(hipMemset(h->d_rec + (size_t)REC * nobs, 0, sizeof(double2) * REC));
+  CRH(hipMemset(h->d_rec + (size_t)rec_slots * nobs, 0, sizeof(double2) * rec_slots));
   CRH(hipMemset(h->d_PB + (size_t)PBS * N, 0, sizeof(double) * PBS));
   const size_t n9 = 9 * (size_t)m;
   CR(h->mem.alloc(&h->d_Ab, strip_offset(m, m) + n9));
@@ -835,6 +840,8 @@ int upload_schur_index(mvba_handle *h, const SchurPlan &plan, SchurIndex &ix) {
     }
     if (!ix.q_units.empty()) CRH(hipMemcpy(h->d_q_units, ix.q_units.data(), sizeof(int) * ix.q_units.size(), hipMemcpyHostToDevice));
   }
+  // the compact lane form: the descriptors in UNIT order -- a lane takes its pair's cameras (w = k << 16 | l) from its unit's
+  if (h->rec_compact && !ix.units.empty()) CRH(hipMemcpy(h->d_units, ix.units.data(), sizeof(int4) * ix.units.size(), hipMemcpyHostToDevice));
   if (h->schur_mode == SCHUR_SLOTS && h->n_slot_items) {  // the three step-major arrays -> one 256-byte (768: 64 slots) row per step; they go
     const int W = h->slot_w, row = slot_idx_ints(W);
     const long long n_steps = h->n_slot_items / W;
@@ -917,6 +924,7 @@ int set_kernel_attributes(mvba_handle *h, const CreateKnobs &knobs) {
   }
   const size_t k1_lds = k1_lds_bytes(m, h->gcam, h->k1_threads);
   CRH(set_lds(resid_jac_kernel(h->gcam, h->loss).fn(false), k1_lds));
+  if (h->rec_compact) CRH(set_lds((const void *)k_resid_jac<false, LOSS_SQUARED, CompactRec>, k1_lds));
   CRH(set_lds(cost_kernel(false, h->loss).fn(false), cam_lds));
   CRH(set_lds((const void *)k_residuals<false>, cam_lds));
   if (robust) {
@@ -957,6 +965,9 @@ int build_engine(mvba_handle *h, const mvba_problem *p, const CreateKnobs &knobs
   }, plan, timer));
   h->schur_mode = plan.mode;
   h->use_pairs = plan.mode != SCHUR_DENSE;
+  // The record layout is the engine's: compact exactly where K3 takes the lane form -- the one form with arithmetic to
+  // spare for the omega rows --, the loss is squared and K1 holds the camera table in LDS; MVBA_REC=full keeps the 128-byte record
+  h->rec_compact = plan.mode == SCHUR_SLOTS && plan.W == LANES_W && h->loss == LOSS_SQUARED && !h->gcam && !knobs.rec_full;
   if (h->use_pairs) CR(dev_build ? build_index_device(in, plan, dv, h->mem, ix, timer) : build_index_host(in, plan, h->mem, ix, timer));
   timer.lap("queues / wave descriptors");
 

@@ -1,7 +1,7 @@
 // What the stages of the BA device code share -- gfx950: the fixed-order sums (wave_sum, block_sum), the camera table in LDS
 // or in device memory (load_cams_to_lds, stage_cams, cam_row, dxi_row), the packed strips of the reduced system (strip_offset),
 // the gauge's kept parameters (keep_index), scalar loads of wave-uniform operands (MVBA_CONST_AS / as_const), and the constants
-// of the buffers that more than one stage touches (REC, LDS_CAMERAS, PBS, PACE_STRIDE, LossArgs).
+// of the buffers that more than one stage touches (REC, REC_C, CompactRec, LDS_CAMERAS, PBS, PACE_STRIDE, LossArgs).
 //
 // Included by mvba.hip first inside its device-code namespace: uses expand_cam, CAM_IN, CAM_LDS and DXI_LDS of mvba_common.h.
 // The stage headers after it (mvba_linearize.h, mvba_schur.h, mvba_dense.h, mvba_solve.h, mvba_tail.h, mvba_cov.h, mvba_map.h)
@@ -57,6 +57,17 @@ __device__ __forceinline__ const T MVBA_CONST_AS *as_const(const T *p) {
 }
 
 constexpr int REC = 8;  // double2 slots per observation record (128 B)
+// The compact record of a lane-form engine: slots 0..3 of the full one -- J_X and d/df, 64 B -- and the residual in
+// an array of its own; the omega rows are (row of J_X) x (X - t) and K3 forms them again.  K1's compact instantiation takes one
+// trailing argument of this type, as the robust ones take LossArgs (the full-layout instantiations none: their code is unchanged).
+constexpr int REC_C = 4;
+struct CompactRec {
+  double2 *res;  // [n_obs + 1] residuals, the last one the padding record's zeros
+};
+template <typename... T>
+struct is_compact_rec { static constexpr bool value = false; };
+template <>
+struct is_compact_rec<CompactRec> { static constexpr bool value = true; };
 constexpr int LDS_CAMERAS = 646;  // cameras whose tables (K1: 18 doubles + the waves' staging tiles; K5: 28 doubles) fit one workgroup's LDS
 
 // GCAM: beyond LDS_CAMERAS cameras the expanded camera table does not fit a workgroup's LDS next to its staging tiles; the

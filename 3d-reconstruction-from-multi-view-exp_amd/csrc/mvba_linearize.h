@@ -15,6 +15,10 @@
 // Algorithmic traffic: 24 B in + 128 B out per observation + (24 in + 72 out) B per point.
 // LOSS: a robust loss scales the observation's Jacobian rows and residual by sqrt(w) before they are stored
 // and summed -- the records, E_a and dP_a are then those of the weighted least-squares problem -- and writes sqrt(w) to `sqw`.
+// COMPACT (a squared instantiation with one trailing CompactRec): the record is slots 0..3 -- 64 B, `rec` is
+// [n_obs][REC_C] -- and the residual goes to CompactRec::res; a store instruction of the transpose still writes 1 KiB contiguous
+// (16 records), the residuals of a wave are 1 KiB contiguous as they are.  104 B instead of 152 B per observation; E_a and dP_a
+// are the same sums of the same values.
 #define MVBA_RESID_JAC_ARGS                                                                                                 \
   long long nobs, int m, const double *__restrict__ cam15, const double *__restrict__ X, const int *__restrict__ obs_pt,   \
       const int *__restrict__ cam_idx, const double2 *__restrict__ xy, double f0, const int *__restrict__ tile_start,     \
@@ -23,6 +27,10 @@
 template <bool GCAM, int LOSS = LOSS_SQUARED, typename... Robust>
 __global__ __launch_bounds__(1024, 4) void k_resid_jac(MVBA_RESID_JAC_ARGS, Robust... robust) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
+  constexpr bool COMPACT = is_compact_rec<Robust...>::value;
+  static_assert(!COMPACT || LOSS == LOSS_SQUARED, "the compact record is the squared loss's");
+  constexpr int RS = COMPACT ? REC_C : REC;  // slots of a record
+  auto swz = [](int row) { return COMPACT ? (row >> 1) & 3 : row & 7; };
   double *s_cam = smem;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
   // per-wave 8 KiB staging tile, 16-byte aligned behind the camera table
@@ -70,17 +78,23 @@ __global__ __launch_bounds__(1024, 4) void k_resid_jac(MVBA_RESID_JAC_ARGS, Robu
         }
         la.sqw[o] = sw;
       }
-      // swizzled slot position (s ^ (lane & 7)): conflict-free ds_write_b128
-      double2 *row = stage + lane * REC;
-      const int sw = lane & 7;
+      // swizzled slot position (s ^ swz(lane)): conflict-free ds_write_b128 (128-byte rows: lane & 7; 64-byte rows: eight
+      // consecutive lanes cover the instruction's 128-byte bank window with (lane >> 1) & 3)
+      double2 *row = stage + lane * RS;
+      const int sw = swz(lane);
       row[0 ^ sw] = make_double2(J.jx[0][0], J.jx[1][0]);
       row[1 ^ sw] = make_double2(J.jx[0][1], J.jx[1][1]);
       row[2 ^ sw] = make_double2(J.jx[0][2], J.jx[1][2]);
       row[3 ^ sw] = make_double2(J.jc[0][0], J.jc[1][0]);
-      row[4 ^ sw] = make_double2(J.jc[0][6], J.jc[1][6]);
-      row[5 ^ sw] = make_double2(J.jc[0][7], J.jc[1][7]);
-      row[6 ^ sw] = make_double2(J.jc[0][8], J.jc[1][8]);
-      row[7 ^ sw] = make_double2(J.e0, J.e1);
+      if constexpr (COMPACT) {
+        const CompactRec cr = (robust, ...);
+        cr.res[o] = make_double2(J.e0, J.e1);  // (a wave's residuals: 1 KiB contiguous as they are)
+      } else {
+        row[4 ^ sw] = make_double2(J.jc[0][6], J.jc[1][6]);
+        row[5 ^ sw] = make_double2(J.jc[0][7], J.jc[1][7]);
+        row[6 ^ sw] = make_double2(J.jc[0][8], J.jc[1][8]);
+        row[7 ^ sw] = make_double2(J.e0, J.e1);
+      }
       // K2 fused: this observation's share of E_a = 2 sum Jx^T Jx and dP_a = 2 sum Jx^T e
       c9[0] = 2.0 * (J.jx[0][0] * J.jx[0][0] + J.jx[1][0] * J.jx[1][0]);
       c9[1] = 2.0 * (J.jx[0][0] * J.jx[0][1] + J.jx[1][0] * J.jx[1][1]);
@@ -94,10 +108,10 @@ __global__ __launch_bounds__(1024, 4) void k_resid_jac(MVBA_RESID_JAC_ARGS, Robu
     }
     wave_sync();  // wave-synchronous hand-over through LDS (in-order DS queue)
 #pragma unroll
-    for (int q = 0; q < REC; ++q) {
-      const int ol = q * 8 + (lane >> 3), pos = lane & 7;  // local observation, stored position
-      const double2 v = stage[ol * REC + pos];
-      if (ol < n) rec[(wbase + ol) * REC + (pos ^ (ol & 7))] = v;
+    for (int q = 0; q < RS; ++q) {
+      const int ol = q * (64 / RS) + lane / RS, pos = lane % RS;  // local observation, stored position
+      const double2 v = stage[ol * RS + pos];
+      if (ol < n) rec[(wbase + ol) * RS + (pos ^ swz(ol))] = v;
     }
     wave_sync();
     // ---- per-point sums (wave-level segmented reduction; observations are sorted by point)
@@ -150,11 +164,15 @@ __global__ void k_sum_split(int n_split, const int4 *__restrict__ splits /* poin
 // row of a point removed from the unknowns -- E^-1 = 0, v = 0, R = 0, the tenth double 1 (a point, sign code 0) -- and does not
 // test that point's determinant.  Without a mask the engine launches k_point_inv<>, whose arguments and body are the kernel's
 // as it was before there were masks.
+// `Xc` (a compact-record engine, else null): the committed points; X_a goes into slots 6 and 7 of the row -- (X0, X1), (X2, 0) --
+// which the dense form's R does not need there (want_r and Xc exclude each other).  Read as a ring, slots 6, 7, 0, 1, 2 are the
+// ONE run k_schur_lanes_compact gathers for an off-diagonal item, 6, 7, 0 .. 4 for a diagonal one.  Held points get theirs too:
+// their omega columns still enter c diag(G_k).
 template <typename... Held>
 __global__ __launch_bounds__(256) void k_point_inv(long long npts, double c, const double *__restrict__ PL,
                                                    double *__restrict__ PB, int *__restrict__ flag,
                                                    double *__restrict__ Ab, long long nAb, int *__restrict__ prog, long long nprog, int want_r,
-                                                   Held... held) {
+                                                   const double *__restrict__ Xc, Held... held) {
   static_assert(sizeof...(Held) <= 1, "at most the held mask");
   // a block's 256 points are 18 KiB of PL and 32 KiB of PB, both contiguous: moved with coalesced
   // accesses through LDS (a thread reading its own 72-byte row / writing its own 128-byte line touches
@@ -189,6 +207,10 @@ __global__ __launch_bounds__(256) void k_point_inv(long long npts, double c, con
       const int sw = threadIdx.x & 7;
 #pragma unroll
       for (int q = 0; q < 8; ++q) out[q ^ sw] = make_double2(0.0, q == 4 ? 1.0 : 0.0);
+      if (Xc) {
+        out[6 ^ sw] = make_double2(Xc[3 * a], Xc[3 * a + 1]);
+        out[7 ^ sw] = make_double2(Xc[3 * a + 2], 0.0);
+      }
     }
   }
   if (free_pt) {
@@ -224,6 +246,10 @@ __global__ __launch_bounds__(256) void k_point_inv(long long npts, double c, con
       out[7 ^ sw] = make_double2(l21 * a1, a2);
     } else {
       out[5 ^ sw] = out[6 ^ sw] = out[7 ^ sw] = make_double2(0.0, 0.0);
+      if (Xc) {
+        out[6 ^ sw] = make_double2(Xc[3 * a], Xc[3 * a + 1]);
+        out[7 ^ sw] = make_double2(Xc[3 * a + 2], 0.0);
+      }
     }
   }
   __syncthreads();

@@ -1,6 +1,6 @@
 // K3, the gather forms -- kernels, gfx950: the unit form (k_schur_pairs, _big, _robust, _big_robust), the slot form with three
-// lanes per item (k_schur_slots) and with one lane per item (k_schur_lanes; its step is mvba_lanes.h, included below), and
-// k_schur_reduce, which sums the unit partials into the packed strips.
+// lanes per item (k_schur_slots) and with one lane per item (k_schur_lanes, and k_schur_lanes_compact on the compact record; their
+// step is mvba_lanes.h, included below), and k_schur_reduce, which sums the unit partials into the packed strips.
 //
 // Included by mvba.hip inside its device-code namespace, after mvba_linearize.h: uses REC, PBS, PACE_STRIDE, strip_offset and
 // as_const / MVBA_CONST_AS of mvba_device.h.  The host launch (launch_schur) is in mvba.hip; the index these
@@ -55,11 +55,15 @@ constexpr int SLOT_IDX_RING = 3;                // ... staged three steps deep i
 // unpacked (the unit form: a wave meets both kinds of unit) keeps the full l region and five point slots whatever the step,
 // and its robust build gathers the step's sqrt(w) values (8 bytes per item: k side, then l side) at SQW, into what the
 // squared build leaves unused: behind the residuals (DIAG), behind the 3-slot point rows (off-diagonal).
-template <int W, bool DIAG, bool PACKED>
+// COMPACT (the lane form on the compact record, mvba_lanes.h): record rows of 4 slots (J_X, d/df: 64 B) and point rows that
+// carry X_a in two more slots -- 5 (X, E^-1), DIAG: 7 (X, E^-1, E^-1 dP, weight).
+template <int W, bool DIAG, bool PACKED, bool COMPACT = false>
 struct SchurStage {
-  static constexpr int NPS = DIAG ? 5 : 3;
-  static constexpr int L = W * PROW;
-  static constexpr int P = L + ((PACKED && DIAG) ? W * 16 : W * PROW);
+  static_assert(!COMPACT || PACKED, "the compact rows are the slot forms'");
+  static constexpr int ROW = COMPACT ? 4 * 16 : PROW;
+  static constexpr int NPS = (DIAG ? 5 : 3) + (COMPACT ? 2 : 0);
+  static constexpr int L = W * ROW;
+  static constexpr int P = L + ((PACKED && DIAG) ? W * 16 : W * ROW);
   static constexpr int SIZE = P + W * 16 * (PACKED ? NPS : 5);
   static constexpr int SQW = DIAG ? L + W * 16 : P + W * 16 * NPS;
   static constexpr int SQW_END = SQW + (DIAG ? 1 : 2) * W * 8;
@@ -642,6 +646,27 @@ __global__ __launch_bounds__(64, 1) void k_schur_lanes(const int4 *__restrict__ 
   const double2 *rec_r = rec + (size_t)as_const(range_o0)[bid % nR] * REC;  // record indices are relative to the range's first observation
   if (flags & 1) schur_lanes_run<true>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec_r, PB, c, 1.0 / f0, partial, su);
   else schur_lanes_run<false>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec_r, PB, c, 1.0 / f0, partial, su);
+}
+// The same on the compact record (mvba_lanes.h, COMPACT): `rec` is [n_obs + 1][REC_C], the residuals are `res` [n_obs + 1]; `units`
+// (in unit order) and the committed cameras give a lane the centres of its pair.  A kernel of its own name, like the variants
+// of the unit form.
+__global__ __launch_bounds__(64, 1) void k_schur_lanes_compact(const int4 *__restrict__ wdesc, const int *__restrict__ wunits,
+                                                               const int *__restrict__ it_x, const double2 *__restrict__ rec,
+                                                               const double *__restrict__ PB, double c, double f0,
+                                                               double *__restrict__ partial, int nR,
+                                                               const long long *__restrict__ range_o0, const double2 *__restrict__ res,
+                                                               const int4 *__restrict__ units, const double *__restrict__ cam15) {
+  extern __shared__ char smem_pairs[];
+  const int bid = blockIdx.x;
+  const int MVBA_CONST_AS *dp = as_const(reinterpret_cast<const int *>(wdesc)) + 4 * (size_t)bid;
+  const int d_x = dp[0], d_y = dp[1], nsteps = dp[2], flags = dp[3];
+  if (nsteps <= 0) return;  // (wave-uniform) a wave whose lists are all empty in this range
+  const long long beg = ((long long)d_y << 32) | (unsigned)d_x;
+  const int *su = wunits + (size_t)bid * LANES_W;
+  const long long o0 = as_const(range_o0)[bid % nR];  // record indices are relative to the range's first observation
+  const LanesCompact cx{res + o0, units, cam15};
+  if (flags & 1) schur_lanes_run<true, true>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec + (size_t)o0 * REC_C, PB, c, 1.0 / f0, partial, su, cx);
+  else schur_lanes_run<false, true>(smem_pairs, (int)threadIdx.x, beg, nsteps, it_x, rec + (size_t)o0 * REC_C, PB, c, 1.0 / f0, partial, su, cx);
 }
 
 // One thread per element of a pair's block: the pair's unit partials in unit order -> packed strips.

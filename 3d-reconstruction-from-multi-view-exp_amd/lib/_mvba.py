@@ -450,7 +450,9 @@ class HipEngine:
         # slot form: step-major rows incl. the padding rows of the bounded-skew merge, and the step width = lists per wave
         # (21: k_schur_slots, three lanes per item; 64: k_schur_lanes, one lane per item -- "slots" either way; 0: no slot form)
         return {"items": i[0], "offdiag_items": i[1], "units": i[2], "kernel": ("strip", "pairs", "slots", "dense")[i[3] & 0xff],
-                "slot_rows": i[7], "step_width": (i[3] >> 8) & 0xff}
+                "slot_rows": i[7], "step_width": (i[3] >> 8) & 0xff,
+                # the linearisation record: "compact" (64 B: J_X and d/df; lane form, squared loss) or "full" (128 B)
+                "record": "compact" if (i[3] >> 16) & 1 else "full"}
 
     def rccl_version(self):
         i = self._info()
