@@ -13,20 +13,23 @@ def _scaled(col_scale, m):
     return D
 
 
-def check_one_step(eng, g, c, tight=1e-11, col_scale=None, dxi_tol=1e-9):
+def check_one_step(eng, g, c, tight=1e-11, col_scale=None, dxi_tol=1e-9, linearize=True):
     """Every kernel's output at one linearisation point + one trial.  ``col_scale`` (9m,): the vector D of a problem in
     pixel units (tests/_pixel_cases.py), f0 at (f, u, v) and 1 at the pose slots: JC, A_full, b_full, dxi and the trial
     f, u of the engine AND of the oracle go to the unit twin's scale (JC D, D A D, D b, dxi / D, f / f0, u / f0) before the
     same asserts with the same numbers -- unscaled, the f / u block of A is f0^2 below max|A| and a bound relative to
     max|A| does not see it.  ``dxi_tol``: the bound on dxi as a fraction of max|dxi|, 1e-9 unless the caller has a written reason
-    (tests/_pixel_cases.py::ORACLE_TWIN_DXI: the ORACLE's LU solve of the unscaled system at 647 cameras)."""
+    (tests/_pixel_cases.py::ORACLE_TWIN_DXI: the ORACLE's LU solve of the unscaled system at 647 cameras).
+    ``linearize=False``: both are linearised at one state already and stay so -- a further trial on that linearisation (the LM
+    retry, tests/_lanes_sequence.py); the linearisation is read and compared all the same, the committed cost is not asked for."""
     D = _scaled(col_scale, g.m)
     d9, f0 = (1.0, 1.0) if D is None else (D[:9], D[0])
     Dv = 1.0 if D is None else D
     DD = 1.0 if D is None else np.outer(D, D)
-    assert eng.cost() == pytest.approx(g.cost(), rel=1e-13)
-    eng.linearize()
-    g.linearize()
+    if linearize:
+        assert eng.cost() == pytest.approx(g.cost(), rel=1e-13)
+        eng.linearize()
+        g.linearize()
     n_obs = g.xy.shape[0]
     np.testing.assert_allclose(eng.debug_read("residual").reshape(n_obs, 2), g.e, rtol=1e-12, atol=1e-14)
     np.testing.assert_allclose(eng.debug_read("JX").reshape(n_obs, 2, 3), g.JX, rtol=1e-12, atol=1e-13)
@@ -68,11 +71,13 @@ def check_one_step(eng, g, c, tight=1e-11, col_scale=None, dxi_tol=1e-9):
     return E1
 
 
-def check_reduced_system(eng, A, b, E1o, c=1e-2, col_scale=None):
+def check_reduced_system(eng, A, b, E1o, c=1e-2, col_scale=None, linearize=True):
     """One linearisation and one trial at damping c on `eng` against the oracle's reduced system (A, b) and trial cost E1o at the
     same state and damping: A_full to 1e-11 max|A|, b_full to 1e-9 max|b|, the trial cost to 1e-7 relative.  Returns the measured
-    max|A_full - A| / max|A|.  ``col_scale``: as for check_one_step, D A D and D b on both sides first."""
-    eng.linearize()
+    max|A_full - A| / max|A|.  ``col_scale``: as for check_one_step, D A D and D b on both sides first.  ``linearize=False``: the
+    trial alone, on the linearisation `eng` already has."""
+    if linearize:
+        eng.linearize()
     E1 = eng.try_step(c)
     m9 = A.shape[0]
     D = _scaled(col_scale, m9 // 9)

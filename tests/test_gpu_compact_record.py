@@ -1,6 +1,6 @@
 """The compact 64-byte linearisation record of the lane-form engines (k_resid_jac<.., CompactRec>,
 k_schur_lanes_compact): against the oracle, against the same engine on the full record (MVBA_REC=full), and through the other
-readers of the record -- debug reads, covariances, held points, parameter maps, snapshots.  Every engine here is forced into
+readers of the record -- debug reads, covariances, held points, parameter maps, snapshots, two sharded ranks.  Every engine here is forced into
 the lane form (MVBA_SCHUR=lanes) and asserts which record it runs on: schur_info()["record"].
 
 Tolerances.  Against the oracle: tests/_parity_checks.py::check_reduced_system (A 1e-11 max|A|, b 1e-9 max|b|, trial cost 1e-7),
@@ -195,6 +195,52 @@ def test_hold_only_parameter_map():
     got = _trial(c)
     _same_step(got, _trial(f))
     assert (got["dxi"].reshape(-1, 9)[:, :3] == 0).all()
+
+
+def test_two_thread_ranks_host_transport():
+    """Sharded engines in the lane form (as tests/test_gpu_covariance.py::test_two_thread_ranks_host_transport shards: two ranks
+    as threads over the host transport, partition_points / slice_observations), every rank on the compact record: one trial's
+    summed [A | b] on rank 0 against the single compact engine's, both ranks' dxi bit for bit equal, and the single engine
+    against the oracle (check_reduced_system).  Bounds: the ranks sum the same items as the single engine in another order -- per
+    rank in list order, then over the ranks -- which is what _same_step's bounds are for (two engines, each within the oracle
+    bound of 1e-11 max|A| and 1e-9 max|b|, so 2e-11 and 2e-9 between them; tests/test_gpu_schur_lanes.py compares k_schur_lanes
+    with k_schur_slots at the same)."""
+    from lib import _distributed as D
+    from lib._mvba import HipEngine
+    from oracle import ba_oracle as O
+
+    n, m, p = 3000, 30, 0.3
+    sc = _scene(n, m, p)
+    X, R, t = O.normalize_scene(sc.init_X, sc.init_R, sc.init_t, sc.axis)
+    f, u = sc.init_K[:, 0, 0].copy(), sc.init_K[:, :2, 2].copy()
+    one = _engine(sc, "compact")
+    check_reduced_system(one, *_oracle_system(_oracle(sc)), C)
+    ref = _trial(one)
+    parts = D.partition_points(sc.pt_ptr, 2)
+
+    def body(rank, g):
+        lo, hi = parts[rank]
+        p2, c2, x2 = D.slice_observations(sc.pt_ptr, sc.cam_idx, sc.xy, lo, hi)
+        eng = HipEngine(hi - lo, m, p2, c2, x2, 1.0, sc.axis)  # (MVBA_SCHUR=lanes is set around the whole group: one environment)
+        info = eng.schur_info()
+        assert info["kernel"] == "slots" and info["step_width"] == 64 and info["record"] == "compact", info
+        g.attach(eng, rank)
+        eng.set_params(X[lo:hi], f, u, t, R)
+        return _trial(eng), info
+
+    with _env(MVBA_SCHUR="lanes"):
+        res = D.InProcessGroup(2).run(body)
+    for rank, (_, info) in enumerate(res):
+        print(f"rank {rank}: points {parts[rank]}, form {info['kernel']}, step width {info['step_width']}, record {info['record']}")
+    got = res[0][0]
+    dev_A, dev_b = np.abs(got["A"] - ref["A"]).max() / np.abs(ref["A"]).max(), np.abs(got["b"] - ref["b"]).max() / np.abs(ref["b"]).max()
+    print(f"two ranks vs one engine: |dA| / max|A| = {dev_A:.3e} (2e-11), |db| / max|b| = {dev_b:.3e} (2e-9), trial cost rel. "
+          f"{abs(got['E1'] - ref['E1']) / ref['E1']:.3e} (1e-9)")
+    assert dev_A <= 2e-11 and dev_b <= 2e-9
+    assert got["E1"] == pytest.approx(ref["E1"], rel=1e-9)
+    np.testing.assert_array_equal(res[0][0]["dxi"], res[1][0]["dxi"])
+    np.testing.assert_array_equal(res[0][0]["A"], res[1][0]["A"])
+    assert np.abs(got["dxi"]).max() > 0
 
 
 def test_snapshot_restore_then_a_step():

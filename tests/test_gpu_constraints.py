@@ -115,6 +115,7 @@ def test_one_step_for_every_kind_of_map(golden, scene):
 # ---------------------------------------------------------------- 2: every route into the solve
 ROUTES = [("pairs", (3000, 14, 0.5), {"MVBA_SCHUR": "pairs", "MVBA_FORCE_BIG": "1"}),
           ("slots", (3000, 14, 0.5), {"MVBA_SCHUR": "slots"}),
+          ("lanes", (3000, 14, 0.5), {"MVBA_SCHUR": "lanes"}),  # one lane per item on the compact record (k_schur_lanes_compact)
           ("dense", (3001, 12, 1.0), {"MVBA_SCHUR": "dense"}),
           ("gcam647", (3000, 647, 0.04), {}),
           ("launches", (3000, 50, 0.3), {"MVBA_CHOL": "launches"}),
@@ -132,6 +133,10 @@ def test_every_route_into_the_solve(route, shape, env, kind, monkeypatch):
     eng, ref = _pair(*prob)
     if route in ("pairs", "slots", "dense"):
         assert eng.schur_info()["kernel"] == route
+    if route == "lanes":  # (reported as "slots"; step width 21 would be k_schur_slots, the fall-back)
+        info = eng.schur_info()
+        assert info["kernel"] == "slots" and info["step_width"] == 64 and info["record"] == "compact", info
+        print(f"form {info['kernel']}, step width {info['step_width']}, record {info['record']}", end=" ")
     col, n_free = _maps(m, axis)[kind]
     eng.set_parameter_map(col, n_free)
     ref.set_parameter_map(col, n_free)

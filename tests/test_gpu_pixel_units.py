@@ -9,6 +9,10 @@ Two comparisons, both in the units of the problem's unit twin (xy / f0, f0 = 1, 
             tests/test_oracle_golden.py), with the bounds of the existing test of each quantity on the column-scaled values:
             this pins the convention and shows that nothing relies on exactness.
 
+The one-lane-per-item engines (rows "lanes", "lanes_full": k_schur_lanes_compact with the compact K1, k_schur_lanes) take f0 in
+one place, jc_sign(i, cu) on the rows and columns of the 81 accumulators and cs * cs on the damping diagonal; at 512 they are
+bitwise like every other form: the omega rows come from J_X, X_a and t, none of which scale, and cu, rs, cs are powers of two.
+
 Left out on purpose: the indefinite-system shapes that take the LU rescue.  Partial pivoting compares magnitudes across
 columns, so it is not covariant under the column scaling D and neither comparison applies to it."""
 import contextlib
@@ -37,9 +41,15 @@ FORMS = [
     ("dense_table", (400, 14, 0.8), {"MVBA_SCHUR": "dense"}, "dense"),  # missing observations: the table form
     ("gcam", (3000, 647, 0.04), {}, "pairs"),  # camera tables in device memory
     ("deg70", (90, 70, 1.0), {}, None),  # 70 observations per point > one 64-lane tile
+    # one lane per item (k_schur_lanes_compact / k_schur_lanes): "slots" with step width 64, the record in LANE_RECORD;
+    # three waves of 64 lists per range, the second off-diagonal wave with 2 of its 64 lists
+    ("lanes", (3000, 12, 0.5), {"MVBA_SCHUR": "lanes"}, "slots"),
+    ("lanes_full", (3000, 12, 0.5), {"MVBA_SCHUR": "lanes", "MVBA_REC": "full"}, "slots"),
 ]
 FORM = {f[0]: f for f in FORMS}
 IDS = [f[0] for f in FORMS]
+LANE_RECORD = {"lanes": "compact", "lanes_full": "full"}  # the rows that must run the lane form, and on which record
+LANES_ENV = FORM["lanes"][2]
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,6 +67,18 @@ def _hip(prob, **kw):
 def _set_env(monkeypatch, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
+
+
+def _assert_form(name, kernel, *engines):
+    """Every engine runs the form the row names; a lane row that fell back to k_schur_slots (step width 21), to the unit form
+    or to the other record fails here.  Returns the text the tests print."""
+    for eng in engines:
+        info = eng.schur_info()
+        if kernel:
+            assert info["kernel"] == kernel, info
+        if name in LANE_RECORD:
+            assert info["step_width"] == 64 and info["record"] == LANE_RECORD[name], info
+    return f"form {info['kernel']}, step width {info['step_width']}, record {info['record']}"
 
 
 def _close(a, b, tol, what, scale=None):
@@ -85,9 +107,7 @@ def test_twin_at_512_is_bitwise_in_every_form(monkeypatch, name, shape, env, ker
     _set_env(monkeypatch, env)
     px, twin, D = _problem(*shape, 512.0)
     a, b = _hip(px), _hip(twin)
-    if kernel:
-        assert a.schur_info()["kernel"] == b.schur_info()["kernel"] == kernel
-    print(f"{name} {shape} f0 = 512, form {a.schur_info()['kernel']}")
+    print(f"{name} {shape} f0 = 512, {_assert_form(name, kernel, a, b)}")
     assert_twin(engine_outputs(a, 1e-4), engine_outputs(b, 1e-4), D, exact=True)
     fa, fb = _final_state(a), _final_state(b)
     assert fa["lu_fallback"] == 0 and fb["lu_fallback"] == 0
@@ -100,9 +120,7 @@ def test_oracle_at_600_in_every_form(monkeypatch, name, shape, env, kernel):
     _set_env(monkeypatch, env)
     px, _, D = _problem(*shape, 600.0)
     eng = _hip(px)
-    if kernel:
-        assert eng.schur_info()["kernel"] == kernel
-    print(f"{name} {shape} f0 = 600, form {eng.schur_info()['kernel']}")
+    print(f"{name} {shape} f0 = 600, {_assert_form(name, kernel, eng)}")
     # (647 cameras and 90 x 70: the ORACLE's LU solve of the unscaled system is 1.4e-9 / 2.4e-9 from its own twin's -- measured on
     # the CPU, _pixel_cases.ORACLE_TWIN_DXI; the bound on dxi is MARGIN times that there, the existing 1e-9 everywhere else)
     check_one_step(eng, make_engine(O.OracleEngine, px), 1e-4, col_scale=D, dxi_tol=dxi_bound(shape))
@@ -204,10 +222,25 @@ def _map(kind, m, axis):
     return parameter_map(m, axis, **({"hold": "intrinsics"} if kind == "hold_intr" else {"share": "intrinsics"}))
 
 
-@pytest.mark.parametrize("kind", ["hold_intr", "share_intr", "random_mask"])
+KINDS = ["hold_intr", "share_intr", "random_mask"]
+
+
+@pytest.mark.parametrize("kind", KINDS)
 def test_parameter_maps(kind):
     """The mapped solve: dxi, dX and the trial state bit for bit against the twin at 512; at 600 against
     ConstrainedOracleEngine with the bounds of tests/test_gpu_constraints.py::_check_step, dxi in the twin's units."""
+    _check_parameter_maps(kind)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_parameter_maps_in_the_lane_form(monkeypatch, kind):
+    """test_parameter_maps once more, same shape and bounds, with every engine in the lane form on the compact record
+    (k_schur_lanes_compact feeds the mapped gather): shared intrinsics and a random hold mask as well as held intrinsics."""
+    _set_env(monkeypatch, LANES_ENV)
+    _check_parameter_maps(kind, form="lanes")
+
+
+def _check_parameter_maps(kind, form=None):
     shape = (2000, 30, 0.3)
     m = shape[1]
     keys = ("dxi", "dX", "trial_X", "trial_cam", "trial_cost")
@@ -215,13 +248,14 @@ def test_parameter_maps(kind):
     col, n_free = _map(kind, m, px[6])
     a, b = _hip(px), _hip(twin)
     a.set_parameter_map(col, n_free), b.set_parameter_map(col, n_free)
-    print(f"{kind} {shape} f0 = 512, n_free {n_free}")
+    print(f"{kind} {shape} f0 = 512, n_free {n_free}, {_assert_form(form, None, a, b)}")
     assert_twin(engine_outputs(a, 1e-4, keys), engine_outputs(b, 1e-4, keys), D, exact=True)
     assert a.stats()["counts"]["lu_fallback"] == 0 and b.stats()["counts"]["lu_fallback"] == 0
     del a, b
     px, _, D = _problem(*shape, 600.0, one_body=True)
     f0 = 600.0
     eng, ref = _hip(px), make_engine(ConstrainedOracleEngine, px)
+    _assert_form(form, None, eng)
     eng.set_parameter_map(col, n_free), ref.set_parameter_map(col, n_free)
     eng.linearize(), ref.linearize()
     E, Eo = eng.try_step(1e-4), ref.try_step(1e-4)
@@ -245,29 +279,62 @@ def test_parameter_maps(kind):
     assert eng.stats()["counts"]["lu_fallback"] == 0
 
 
+# ---------------------------------------------------------------- the compact record's other reader
+def test_debug_reads_of_the_compact_record_at_600(monkeypatch):
+    """tests/test_gpu_compact_record.py::test_debug_reads_expand_the_compact_record away from f0 = 1: mvba_debug_read expands the
+    64-byte record on the host (expand_compact_record; the u, v columns are implied).  Against the full-record engine on the same
+    pixel problem: residual, J_X and the f, u, v, t columns of J_C bit for bit (K1 stores the same values in either layout), the
+    omega columns -- (row of J_X) x (X - t) on the host against K1's own -- within that test's 1e-12 of max|J_C|; and the u, v
+    columns are exactly 1 / 600 and 0 where the model says so."""
+    shape = FORM["lanes"][1]
+    px, _, D = _problem(*shape, 600.0)
+    _set_env(monkeypatch, FORM["lanes"][2])
+    c = _hip(px)
+    _set_env(monkeypatch, FORM["lanes_full"][2])
+    f = _hip(px)
+    print(f"{shape} f0 = 600: {_assert_form('lanes', 'slots', c)} against {_assert_form('lanes_full', 'slots', f)}")
+    c.linearize(), f.linearize()
+    np.testing.assert_array_equal(c.debug_read("residual"), f.debug_read("residual"))
+    np.testing.assert_array_equal(c.debug_read("JX"), f.debug_read("JX"))
+    Jc, Jf = c.debug_read("JC").reshape(-1, 2, 9), f.debug_read("JC").reshape(-1, 2, 9)
+    np.testing.assert_array_equal(Jc[:, :, :6], Jf[:, :, :6])
+    for J in (Jc, Jf):
+        assert (J[:, 0, 1] == 1.0 / 600.0).all() and (J[:, 1, 2] == 1.0 / 600.0).all()
+        assert (J[:, 0, 2] == 0.0).all() and (J[:, 1, 1] == 0.0).all()
+    assert np.abs(Jf[:, :, 0]).max() > 0
+    # (max|J_C| in the twin's units, J_C D, as everywhere in this file: unscaled the pose columns are the largest all the same)
+    dev = np.abs(Jc - Jf).max() / np.abs(Jf).max()
+    dev_twin = np.abs((Jc - Jf) * D[:9]).max() / np.abs(Jf * D[:9]).max()
+    print(f"  J_C compact vs full: max|d| / max|J_C| = {dev:.3e}, column-scaled {dev_twin:.3e} (bound 1e-12)")
+    assert np.abs(Jf[:, :, 6:]).max() > 0 and dev <= 1e-12 and dev_twin <= 1e-12
+
+
 # ---------------------------------------------------------------- covariances
 def _cov(eng):
     got = eng.covariance(full=True)
     return {"cov_points": got["points"], "cov_cameras": got["cameras"], "cov_full": got["cameras_full"]}
 
 
-@pytest.mark.parametrize("name", ["pairs", "dense_full", "gcam"])
+@pytest.mark.parametrize("name", ["pairs", "dense_full", "gcam", "lanes"])
 def test_covariances(monkeypatch, name):
     """The point pass is handed 1 / f0 and the camera blocks come from the inverse of the unscaled S: at 512 the points are
     bitwise the twin's and the camera blocks bitwise the twin's times D_i D_j; at 600 the rule of
     test_every_schur_form_and_the_646_camera_boundary after scaling -- 1e-8 against the reference formulas on the engine's own S,
-    1e-7 against schur_covariance."""
+    1e-7 against schur_covariance.  "lanes": on the compact record mvba_covariance linearises a second time, into a full-layout
+    buffer of its own, and its point pass reads that one.  (Its 7e-9 against the 1e-8 is the reference's share: cond(S) = 1.2e11
+    on that scene, and np.linalg.inv of the oracle's own S moves by 6.0e-9 of its largest entry under one refinement step in
+    extended precision -- DESIGN.md §5.)"""
     _, shape, env, kernel = FORM[name]
     _set_env(monkeypatch, env)
     m = shape[1]
     px, twin, D = _problem(*shape, 512.0)
     a, b = _hip(px), _hip(twin)
-    assert a.schur_info()["kernel"] == kernel
-    print(f"{name} {shape} covariance f0 = 512")
+    print(f"{name} {shape} covariance f0 = 512, {_assert_form(name, kernel, a, b)}")
     assert_twin(_cov(a), _cov(b), D, exact=True)
     del a, b
     px, _, D = _problem(*shape, 600.0)
     eng = _hip(px)
+    _assert_form(name, kernel, eng)
     got = {k: to_twin_units(k, v, D) for k, v in _cov(eng).items()}
     A = eng.debug_read("A_full").reshape(9 * m, 9 * m)
     A = (np.triu(A) + np.triu(A, 1).T) * np.outer(D, D)  # the engine's own undamped S, in the twin's units
