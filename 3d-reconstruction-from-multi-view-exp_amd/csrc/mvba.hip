@@ -1364,8 +1364,9 @@ int mvba_get_info(mvba_handle *h, int64_t *out8) {
   out8[0] = h->n_items;
   out8[1] = h->n_items_offdiag;
   out8[2] = h->n_units;
-  // bits 8..15: the slot form's step width; bit 16: the engine linearises into the compact record
-  out8[3] = h->schur_mode | (h->schur_mode == SCHUR_SLOTS ? h->slot_w << 8 : 0) | (h->rec_compact ? 1 << 16 : 0);
+  // bits 8..15: the slot form's step width; bit 16: the engine linearises into the compact record; bits 32..: the dense form's workgroups
+  out8[3] = h->schur_mode | (h->schur_mode == SCHUR_SLOTS ? h->slot_w << 8 : 0) | (h->rec_compact ? 1 << 16 : 0) |
+            (h->schur_mode == SCHUR_DENSE ? (int64_t)h->dense_blocks << 32 : 0);
   out8[4] = h->rccl_version;
   out8[5] = NCCL_VERSION_CODE;
   out8[6] = h->nranks;

@@ -452,7 +452,9 @@ class HipEngine:
         return {"items": i[0], "offdiag_items": i[1], "units": i[2], "kernel": ("strip", "pairs", "slots", "dense")[i[3] & 0xff],
                 "slot_rows": i[7], "step_width": (i[3] >> 8) & 0xff,
                 # the linearisation record: "compact" (64 B: J_X and d/df; lane form, squared loss) or "full" (128 B)
-                "record": "compact" if (i[3] >> 16) & 1 else "full"}
+                "record": "compact" if (i[3] >> 16) & 1 else "full",
+                # dense form: the workgroups of k_schur_dense = min(chunks, CUs x workgroups per CU); 0 in the other forms
+                "workgroups": i[3] >> 32}
 
     def rccl_version(self):
         i = self._info()

@@ -188,7 +188,8 @@ int mvba_reset_stats(mvba_handle *h);
  * 1 = pair-major units (round 2), 2 = slot-resident (round 3), 3 = dense visibility (round 5: at most 21 cameras and at least
  * 60 % of the (point, camera) pairs observed: no pair index, out[0..2] = 0) in bits 0..7; bits 8..15: the slot form's step
  * width = lists per wave (21: three lanes per item, 64: one lane per item; 0 in the other forms); bit 16: the engine linearises
- * into the compact 64-byte record (lane form, squared loss, at most 646 cameras, not MVBA_REC=full), out[4] ncclGetVersion() of the librccl
+ * into the compact 64-byte record (lane form, squared loss, at most 646 cameras, not MVBA_REC=full); bits 32..63: the dense form's
+ * launch, the workgroups of k_schur_dense = min(chunks of points, CUs x workgroups per CU) (0 in the other forms), out[4] ncclGetVersion() of the librccl
  * actually loaded (0 without a communicator), out[5] the NCCL_VERSION_CODE the library was compiled
  * against, out[6] ranks, out[7] slot form: step-major item rows including the padding rows. */
 int mvba_get_info(mvba_handle *h, int64_t *out8);
