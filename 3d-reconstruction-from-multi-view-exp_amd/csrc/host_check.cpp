@@ -1,17 +1,21 @@
-// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas; also its
-// expand_compact_record, the compact linearisation record as mvba_debug_read expands it) and the host logic of a RANSAC
+// The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas), the BA engine's host
+// logic (mvba_engine_host.h: build_parameter_map, reduced_system_residual, expand_packed_A, expand_compact_record and the record_to_*
+// fills of mvba_debug_read, the cam15 row, the width rules of K5, the cost pass and the covariance) and the host logic of a RANSAC
 // round (mvba_ransac_host.h: rs_pick, rs_accept, rs_current and rs_other, RsTile, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
 // builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify) and the matcher's (mvba_match_host.h: its argument
 // checks, the chunk rule, the ratio test) on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <iterator>
 #include <limits>
 #include <string>
 #include <vector>
 
 #include "mvba_host.h"
+#include "mvba_engine_host.h"
 #include "mvba_ransac_host.h"
 #include "mvba_tracks_host.h"
 #include "mvba_match_host.h"
@@ -523,6 +527,257 @@ int main() {
     const double jx[8] = {1.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0}, zero[3] = {0.0, 0.0, 0.0}, d[3] = {2.0, 3.0, 5.0};
     expand_compact_record(jx, e2, d, zero, full);  // rows e_x, e_y; d = (2, 3, 5): e_x x d = (0, -5, 3), e_y x d = (5, 0, -2)
     CHECK(full[8] == 0.0 && full[10] == -5.0 && full[12] == 3.0 && full[9] == 5.0 && full[11] == 0.0 && full[13] == -2.0);
+  }
+  // ---------------------------------------------------------------- the BA engine's host logic (mvba_engine_host.h)
+  auto default_map = [](int m, int axis) {
+    std::vector<int32_t> col(9 * m);
+    for (int g = 0, j = 0; g < 9 * m; ++g) col[g] = is_gauge_slot(g, axis) ? -1 : j++;
+    return col;
+  };
+  auto transpose_ok = [](const std::vector<int32_t> &col, int n_free, const ParameterMap &pm) {  // ptr / mem against a transpose written here
+    if ((int)pm.ptr.size() != n_free + 1 || pm.ptr[0] != 0) return false;
+    for (int j = 0; j < n_free; ++j) {
+      std::vector<int> slots;
+      for (int g = 0; g < (int)col.size(); ++g)
+        if (col[g] == j) slots.push_back(g);
+      if (pm.ptr[j + 1] - pm.ptr[j] != (int)slots.size()) return false;
+      for (size_t q = 0; q < slots.size(); ++q)
+        if (pm.mem[pm.ptr[j] + q] != slots[q]) return false;
+    }
+    return (int)pm.mem.size() == std::max(pm.ptr[n_free], 1);
+  };
+  // every f of m cameras one unknown (the last), everything else as the default map numbers it
+  auto shared_f_map = [&](int m, int axis, int &n_free) {
+    std::vector<int32_t> col(9 * m);
+    int j = 0;
+    for (int g = 0; g < 9 * m; ++g) col[g] = (is_gauge_slot(g, axis) || g % 9 == 0) ? -1 : j++;
+    for (int k = 0; k < m; ++k) col[9 * k] = j;
+    n_free = j + 1;
+    return col;
+  };
+  {  // parameter maps at m = 3: 27 slots, D = 20
+    const int m = 3, D = 20;
+    for (int axis = 0; axis < 3; ++axis) {
+      ParameterMap pm;
+      std::vector<int32_t> col = default_map(m, axis);
+      CHECK(is_gauge_slot(3, axis) && is_gauge_slot(8, axis) && is_gauge_slot(12 + axis, axis) && !is_gauge_slot(2, axis) && !is_gauge_slot(9, axis) &&
+            !is_gauge_slot(12 + (axis + 1) % 3, axis));
+      CHECK(build_parameter_map(col.data(), m, axis, D, D, pm) == MVBA_OK && pm.is_default);  // spelled out: recognised as the default
+      std::vector<int32_t> none(27, -1);  // everything held
+      CHECK(build_parameter_map(none.data(), m, axis, 0, D, pm) == MVBA_OK && !pm.is_default);
+      CHECK(pm.ptr.size() == 1 && pm.ptr[0] == 0 && pm.mem.size() == 1 && pm.U == 0 && pm.pairs.empty() && pm.nblk == 1);
+      {  // f of cameras 0 and 2 tied, as the last unknown
+        std::vector<int32_t> c(27);
+        int j = 0;
+        for (int g = 0; g < 27; ++g) c[g] = (is_gauge_slot(g, axis) || g == 0 || g == 18) ? -1 : j++;
+        c[0] = c[18] = j;
+        const int n_free = j + 1;
+        CHECK(n_free == D - 1);
+        CHECK(build_parameter_map(c.data(), m, axis, n_free, D, pm) == MVBA_OK && !pm.is_default);
+        CHECK(pm.U == n_free - 1 && pm.pairs.size() == 1 && pm.pairs[0].x == n_free - 1 && pm.pairs[0].y == n_free - 1 && pm.nblk == 1);
+        CHECK(transpose_ok(c, n_free, pm));
+        CHECK(pm.ptr[n_free] == D && pm.mem[pm.ptr[n_free - 1]] == 0 && pm.mem[pm.ptr[n_free - 1] + 1] == 18);
+      }
+      {  // a tied unknown (u of cameras 1 and 2) numbered 2, before untied ones: U stops at it
+        std::vector<int32_t> c(27);
+        int j = 0;
+        for (int g = 0; g < 27; ++g) c[g] = is_gauge_slot(g, axis) ? -1 : (g == 19 ? -2 : j++);
+        c[19] = c[10];
+        CHECK(c[10] > 2);
+        for (int g = 0; g < 27; ++g)  // renumber: unknown c[10] <-> unknown 2
+          if (c[g] == c[10] && g != 10 && g != 19) c[g] = -3;
+        const int tied = c[10];
+        for (int g = 0; g < 27; ++g) c[g] = c[g] == 2 ? tied : (c[g] == tied ? 2 : c[g]);
+        CHECK(c[10] == 2 && c[19] == 2);
+        CHECK(build_parameter_map(c.data(), m, axis, j, D, pm) == MVBA_OK && pm.U == 2 && pm.pairs.size() == 1 && pm.pairs[0].x == 2 && pm.nblk == 1);
+        CHECK(transpose_ok(c, j, pm));
+      }
+      // the refusals, with their texts
+      g_err.clear();
+      CHECK(build_parameter_map(col.data(), m, axis, D + 1, D, pm) == MVBA_ERR_BADARG && g_err == "mvba_set_parameter_map: n_free = 21 must be in 0 .. 9 n_images - 7 = 20");
+      CHECK(build_parameter_map(col.data(), m, axis, -1, D, pm) == MVBA_ERR_BADARG && g_err == "mvba_set_parameter_map: n_free = -1 must be in 0 .. 9 n_images - 7 = 20");
+      std::vector<int32_t> bad = col;
+      bad[0] = D;
+      CHECK(build_parameter_map(bad.data(), m, axis, D, D, pm) == MVBA_ERR_BADARG && g_err == "mvba_set_parameter_map: col[0] = 20 is neither -1 nor below n_free = 20");
+      bad[0] = -2;
+      CHECK(build_parameter_map(bad.data(), m, axis, D, D, pm) == MVBA_ERR_BADARG && g_err == "mvba_set_parameter_map: col[0] = -2 is neither -1 nor below n_free = 20");
+      bad = col; bad[3] = 0;
+      CHECK(build_parameter_map(bad.data(), m, axis, D, D, pm) == MVBA_ERR_BADARG && g_err == "mvba_set_parameter_map: col[3] is a gauge slot and must be -1");
+      bad = col; bad[12 + axis] = 0;
+      CHECK(build_parameter_map(bad.data(), m, axis, D, D, pm) == MVBA_ERR_BADARG &&
+            g_err == "mvba_set_parameter_map: col[" + std::to_string(12 + axis) + "] is a gauge slot and must be -1");
+      bad = col; bad[1] = bad[0];  // f tied to u
+      CHECK(build_parameter_map(bad.data(), m, axis, D, D, pm) == MVBA_ERR_BADARG &&
+            g_err == "mvba_set_parameter_map: col[1] ties slot 1 to slot 0 (unknown 0): only the same intrinsic parameter (f, u or v) of different cameras can be tied");
+      bad = col; bad[24] = bad[15];  // an omega of camera 2 tied to the same omega of camera 1: not an intrinsic
+      CHECK(build_parameter_map(bad.data(), m, axis, D, D, pm) == MVBA_ERR_BADARG &&
+            g_err == "mvba_set_parameter_map: col[24] ties slot 24 to slot 15 (unknown " + std::to_string(col[15]) +
+                         "): only the same intrinsic parameter (f, u or v) of different cameras can be tied");
+      bad = col; bad[0] = -1;
+      CHECK(build_parameter_map(bad.data(), m, axis, D, D, pm) == MVBA_ERR_BADARG && g_err == "mvba_set_parameter_map: unknown 0 has no parameter slot");
+    }
+  }
+  for (int m : {9, 513}) {  // all f shared: nblk = 2 at nine members, 64 (the cap) at 513
+    int n_free = 0;
+    const std::vector<int32_t> col = shared_f_map(m, 1, n_free);
+    ParameterMap pm;
+    CHECK(n_free == 9 * m - 7 - m + 1);
+    CHECK(build_parameter_map(col.data(), m, 1, n_free, 9 * m - 7, pm) == MVBA_OK && !pm.is_default);
+    CHECK(pm.nblk == (m == 9 ? 2 : 64) && pm.U == n_free - 1 && pm.pairs.size() == 1 && pm.ptr[n_free] - pm.ptr[n_free - 1] == m);
+    CHECK(transpose_ok(col, n_free, pm));
+  }
+  {  // the residual of the reduced system: packed strips from a dense SPD matrix, x from a plain Gaussian elimination
+    auto solve = [](std::vector<double> A, std::vector<double> b, int n) {  // partial pivoting, A row-major n x n
+      for (int c = 0; c < n; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < n; ++r)
+          if (std::fabs(A[(size_t)r * n + c]) > std::fabs(A[(size_t)piv * n + c])) piv = r;
+        for (int j = 0; j < n; ++j) std::swap(A[(size_t)c * n + j], A[(size_t)piv * n + j]);
+        std::swap(b[c], b[piv]);
+        for (int r = c + 1; r < n; ++r) {
+          const double f = A[(size_t)r * n + c] / A[(size_t)c * n + c];
+          for (int j = c; j < n; ++j) A[(size_t)r * n + j] -= f * A[(size_t)c * n + j];
+          b[r] -= f * b[c];
+        }
+      }
+      for (int r = n - 1; r >= 0; --r) {
+        for (int j = r + 1; j < n; ++j) b[r] -= A[(size_t)r * n + j] * b[j];
+        b[r] /= A[(size_t)r * n + r];
+      }
+      return b;
+    };
+    for (int m : {2, 3})
+      for (int axis = 0; axis < 3; ++axis) {
+        const int n9 = 9 * m;
+        unsigned long long seed = 12345 + 7 * m + axis;
+        auto rnd = [&]() { seed = seed * 6364136223846793005ULL + 1442695040888963407ULL; return (double)(seed >> 11) / (double)(1ULL << 53) - 0.5; };
+        std::vector<double> B((size_t)n9 * n9), M((size_t)n9 * n9, 0.0), b(n9);
+        for (double &v : B) v = rnd();
+        for (int i = 0; i < n9; ++i)
+          for (int j = 0; j < n9; ++j) {
+            for (int k = 0; k < n9; ++k) M[(size_t)i * n9 + j] += B[(size_t)i * n9 + k] * B[(size_t)j * n9 + k];
+            if (i == j) M[(size_t)i * n9 + j] += 1.0;
+          }
+        for (double &v : b) v = rnd();
+        const size_t nA = strip_offset(m, m);
+        std::vector<double> Ab(nA + n9);
+        for (int k = 0; k < m; ++k)
+          for (int i = 0; i < 9; ++i)
+            for (int c = 0; c < 9 * (m - k); ++c) Ab[strip_offset(k, m) + (size_t)i * 9 * (m - k) + c] = M[(size_t)(9 * k + i) * n9 + 9 * k + c];
+        for (int g = 0; g < n9; ++g) Ab[nA + g] = is_gauge_slot(g, axis) ? 1e30 : b[g];  // the gauge rows must not enter
+        // the default form: the system over the kept slots
+        std::vector<int> kept;
+        for (int g = 0; g < n9; ++g)
+          if (!is_gauge_slot(g, axis)) kept.push_back(g);
+        const int D = (int)kept.size();
+        CHECK(D == n9 - 7);
+        std::vector<double> Mk((size_t)D * D), bk(D);
+        for (int i = 0; i < D; ++i) {
+          bk[i] = b[kept[i]];
+          for (int j = 0; j < D; ++j) Mk[(size_t)i * D + j] = M[(size_t)kept[i] * n9 + kept[j]];
+        }
+        const std::vector<double> xk = solve(Mk, bk, D);
+        std::vector<double> x(n9, 0.0);
+        for (int i = 0; i < D; ++i) x[kept[i]] = xk[i];
+        double worst = reduced_system_residual(Ab.data(), x.data(), m, axis, nullptr, nullptr, D);
+        CHECK(worst < 1e-12);
+        x[kept[D / 2]] += 1e-3;
+        worst = reduced_system_residual(Ab.data(), x.data(), m, axis, nullptr, nullptr, D);
+        CHECK(worst > 1e-8);
+        if (m < 3) continue;
+        // the mapped form with one tie: f of cameras 0 and 2 one unknown, M' = P^T M P, b' = P^T b, dxi = P x'
+        std::vector<int32_t> col(n9);
+        int j = 0;
+        for (int g = 0; g < n9; ++g) col[g] = (is_gauge_slot(g, axis) || g == 0 || g == 18) ? -1 : j++;
+        col[0] = col[18] = j;
+        const int n_free = j + 1;
+        ParameterMap pm;
+        CHECK(build_parameter_map(col.data(), m, axis, n_free, D, pm) == MVBA_OK);
+        std::vector<double> Mp((size_t)n_free * n_free, 0.0), bp(n_free, 0.0);
+        for (int g = 0; g < n9; ++g) {
+          if (col[g] < 0) continue;
+          bp[col[g]] += b[g];
+          for (int g2 = 0; g2 < n9; ++g2)
+            if (col[g2] >= 0) Mp[(size_t)col[g] * n_free + col[g2]] += M[(size_t)g * n9 + g2];
+        }
+        const std::vector<double> xp = solve(Mp, bp, n_free);
+        std::vector<double> dxi(n9, 0.0);
+        for (int g = 0; g < n9; ++g)
+          if (col[g] >= 0) dxi[g] = xp[col[g]];
+        CHECK(dxi[0] == dxi[18]);
+        worst = reduced_system_residual(Ab.data(), dxi.data(), m, axis, pm.ptr.data(), pm.mem.data(), n_free);
+        CHECK(worst < 1e-12);
+        dxi[1] += 1e-3;
+        worst = reduced_system_residual(Ab.data(), dxi.data(), m, axis, pm.ptr.data(), pm.mem.data(), n_free);
+        CHECK(worst > 1e-8);
+      }
+  }
+  {  // the packed strips expanded: diagonal blocks as stored (they are not symmetric here), the others mirrored
+    const int m = 3, n9 = 27;
+    std::vector<double> pk(strip_offset(m, m)), out((size_t)n9 * n9, -1.0);
+    CHECK(pk.size() == 486);
+    for (size_t i = 0; i < pk.size(); ++i) pk[i] = 1.0 + (double)i;
+    expand_packed_A(pk.data(), m, out.data());
+    for (int k = 0; k < m; ++k)
+      for (int l = k; l < m; ++l)
+        for (int i = 0; i < 9; ++i)
+          for (int jj = 0; jj < 9; ++jj) {
+            const double stored = pk[strip_offset(k, m) + (size_t)i * 9 * (m - k) + 9 * (l - k) + jj];
+            CHECK(out[(size_t)(9 * k + i) * n9 + 9 * l + jj] == stored);
+            if (l > k) CHECK(out[(size_t)(9 * l + jj) * n9 + 9 * k + i] == stored);
+          }
+    CHECK(out[1] != out[n9]);  // (0, 1) and (1, 0) of the first diagonal block: both halves kept as computed
+  }
+  {  // a record as the C interface's rows
+    double q[16], e[2], jx[6], jc[18];
+    for (int i = 0; i < 16; ++i) q[i] = 1.0 + i;
+    record_to_residual(q, e);
+    CHECK(e[0] == 15.0 && e[1] == 16.0);
+    record_to_JX(q, jx);
+    const double want_jx[6] = {1, 3, 5, 2, 4, 6};
+    for (int i = 0; i < 6; ++i) CHECK(jx[i] == want_jx[i]);
+    for (double f0 : {1.0, 600.0})
+      for (double sqw : {1.0, 0.5}) {  // cu = 1 / f0, and sqrt(w) / f0 with w = 1 / 4
+        const double cu = sqw == 1.0 ? 1.0 / f0 : sqw / f0;
+        record_to_JC(q, cu, jc);
+        const double want[18] = {7, cu, 0, -1, -3, -5, 9, 11, 13, 8, 0, cu, -2, -4, -6, 10, 12, 14};
+        for (int i = 0; i < 18; ++i) CHECK(jc[i] == want[i]);
+        for (int rr = 0; rr < 2; ++rr) for (int i = 0; i < 3; ++i) CHECK(jc[9 * rr + 3 + i] == -jx[3 * rr + i]);  // the -J_X columns
+      }
+  }
+  {  // cam15: a round trip at m = 2, all 15 entries of a row distinct
+    const int m = 2;
+    double f[2], u[4], t[6], R[18], cam[2 * CAM_IN], f2[2], u2[4], t2[6], R2[18];
+    for (int k = 0; k < m; ++k) {
+      f[k] = 100 + k;
+      for (int i = 0; i < 2; ++i) u[2 * k + i] = 200 + 2 * k + i;
+      for (int i = 0; i < 3; ++i) t[3 * k + i] = 300 + 3 * k + i;
+      for (int i = 0; i < 9; ++i) R[9 * k + i] = 400 + 9 * k + i;
+    }
+    pack_cam15(m, f, u, t, R, cam);
+    for (int k = 0; k < m; ++k) {
+      const double *c = cam + CAM_IN * k;
+      CHECK(c[0] == f[k] && c[1] == u[2 * k] && c[2] == u[2 * k + 1] && c[3] == t[3 * k] && c[5] == t[3 * k + 2] && c[6] == R[9 * k] && c[14] == R[9 * k + 8]);
+    }
+    unpack_cam15(cam, m, f2, u2, t2, R2);
+    CHECK(!memcmp(f, f2, sizeof f) && !memcmp(u, u2, sizeof u) && !memcmp(t, t2, sizeof t) && !memcmp(R, R2, sizeof R));
+  }
+  {  // the width rules.  Table bytes: 8 * 28 * m for K5 (camera row + update row), 8 * 18 * m for the cost pass
+    auto k5_bytes = [](int m) { return sizeof(double) * (size_t)(CAM_LDS + DXI_LDS) * m; };
+    auto cost_threads = [](int m) { return std::min(512, table_block_threads(sizeof(double) * (size_t)CAM_LDS * m)); };
+    CHECK(k5_bytes(182) == 40768 && k5_bytes(183) == 40992 && k5_bytes(365) == 81760 && k5_bytes(366) == 81984);
+    CHECK(table_block_threads(k5_bytes(182)) == 256 && table_block_threads(k5_bytes(183)) == 512);
+    CHECK(table_block_threads(k5_bytes(365)) == 512 && table_block_threads(k5_bytes(366)) == 1024);
+    CHECK(table_block_threads(40 * 1024) == 256 && table_block_threads(80 * 1024) == 512 && table_block_threads(0) == 256);
+    CHECK(cost_threads(284) == 256 && cost_threads(285) == 512 && cost_threads(646) == 512);
+    CHECK(k5_lanes(40.0) == 2 && k5_lanes(std::nextafter(40.0, 41.0)) == 4 && k5_lanes(100.0) == 4 && k5_lanes(std::nextafter(100.0, 101.0)) == 8 && k5_lanes(1.0) == 2);
+    CHECK(cov_lanes(12.0) == 8 && cov_lanes(std::nextafter(12.0, 13.0)) == 16 && cov_lanes(24.0) == 16 && cov_lanes(std::nextafter(24.0, 25.0)) == 32);
+    CHECK(cov_lanes(48.0) == 32 && cov_lanes(std::nextafter(48.0, 49.0)) == 64 && cov_lanes(0.0) == 8);
+    auto in = [](auto &dom, int v) { return std::find(std::begin(dom), std::end(dom), v) != std::end(dom); };  // the domain beside the rule
+    for (double d : {1.0, 40.0, 41.0, 100.0, 101.0, 1e6}) CHECK(in(K5_LANES, k5_lanes(d)));
+    for (size_t by : {(size_t)0, (size_t)40961, (size_t)81921, (size_t)160 * 1024}) CHECK(in(TABLE_BLOCK_THREADS, table_block_threads(by)));
+    for (double pr : {0.0, 13.0, 25.0, 49.0, 1e6}) CHECK(in(COV_LANES, cov_lanes(pr)));
+    CHECK(std::size(K5_LANES) == 3 && std::size(TABLE_BLOCK_THREADS) == 3 && std::size(COV_LANES) == 4);
   }
   if (failures) return 1;
   std::printf("host_check ok\n");

@@ -35,6 +35,13 @@ enum : int {
 static_assert(FLAG_POINT_SINGULAR == 1 && FLAG_NOT_POSDEF == 2 && FLAG_LU_SINGULAR == 4 && FLAG_WAIT_GAVE_UP == 8 && FLAG_COV_POINT == 16,
               "the status bits travel between ranks and builds");
 
+// Reduced system storage: the upper block triangle of A packed strip by strip -- strip k is a
+// row-major 9 x 9(m-k) block (cameras l >= k) at offset 81 (k m - k (k-1) / 2) -- followed by b
+// (9m).  81 m (m+1) / 2 + 9m doubles: half of the dense 9m x 9m, and what the all-reduce ships.
+__host__ __device__ __forceinline__ size_t strip_offset(int k, int m) {
+  return 81 * ((size_t)k * m - (size_t)k * (k - 1) / 2);
+}
+
 // t-th tile of a lower triangle numbered row by row (t = row (row + 1) / 2 + col, col <= row): the float root is off by at
 // most one either way, the two loops correct it.
 __device__ __forceinline__ void tri_tile(int t, int &row, int &col) {

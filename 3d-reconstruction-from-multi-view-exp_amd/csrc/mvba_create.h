@@ -1,7 +1,7 @@
 // Engine creation (mvba_create, mvba_create_robust) -- host code, gfx950.
 //
-// Included by mvba.hip inside its host-side namespace, after mvba_handle, DevBufs, CreateKnobs and the kernel tables
-// (resid_jac_kernel, cost_kernel, backsub_kernel, dense_kernel, k1_lds_bytes, cam_lds_bytes).  create_engine() at the end is the
+// Included by mvba.hip inside its host-side namespace, after mvba_engine.h: uses its mvba_handle, CreateKnobs and kernel tables
+// (resid_jac_kernel, cost_kernel, backsub_kernel, dense_kernel, k1_lds_bytes, cam_lds_bytes), DevBufs and MVBA_HIP.  create_engine() at the end is the
 // table of contents; the stages above it stand in the order it calls them:
 //
 //   validate_problem      argument checks, point of every observation
@@ -24,7 +24,6 @@ __global__ __launch_bounds__(256) void k_xy_from_planes(const double2 *__restric
 }
 
 #define CR(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-#define CRH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(MVBA_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 // MVBA_CREATE_TIMING=1: wall time of mvba_create's stages on stderr (tools/time_create.py; the engine's construction is a
 // third of the reference's pipeline at 1 M points x 12 images)
@@ -478,7 +477,7 @@ int upload_range_o0(const IndexInput &in, const PointRanges &R, DevBufs &engine,
   std::vector<long long> ro0(R.nR);
   for (int r = 0; r < R.nR; ++r) ro0[r] = in.p->pt_ptr[R.lo[r]];
   CR(engine.alloc(&ix.d_range_o0, (size_t)R.nR));
-  CRH(hipMemcpy(ix.d_range_o0, ro0.data(), sizeof(long long) * R.nR, hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(ix.d_range_o0, ro0.data(), sizeof(long long) * R.nR, hipMemcpyHostToDevice));
   return MVBA_OK;
 }
 
@@ -654,16 +653,16 @@ int count_pairs_device(const IndexInput &in, const CreateKnobs &knobs, DeviceInd
   CR(dv.mem.alloc(&dv.d_hist, (size_t)dv.idx_waves * P));
   CR(dv.mem.alloc(&dv.d_cnt, (size_t)P));
   if (dv.hist_lds) {
-    CRH(hipFuncSetAttribute((const void *)k_idx_count<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv.idx_lds));
-    CRH(hipFuncSetAttribute((const void *)k_idx_fill<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv.idx_lds));
+    MVBA_HIP(hipFuncSetAttribute((const void *)k_idx_count<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv.idx_lds));
+    MVBA_HIP(hipFuncSetAttribute((const void *)k_idx_fill<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dv.idx_lds));
   } else {
-    CRH(hipMemsetAsync(dv.d_hist, 0, sizeof(int) * (size_t)dv.idx_waves * P, in.stream));
+    MVBA_HIP(hipMemsetAsync(dv.d_hist, 0, sizeof(int) * (size_t)dv.idx_waves * P, in.stream));
   }
   hipLaunchKernelGGL(dv.hist_lds ? k_idx_count<false> : k_idx_count<true>, dim3((unsigned)(dv.idx_waves / IDX_WAVES)), dim3(64 * IDX_WAVES), dv.idx_lds,
                      in.stream, N, in.m, (int)P, in.d_pt_ptr, in.d_cam, dv.idx_chunk, dv.d_hist, (const int *)nullptr);
   hipLaunchKernelGGL(k_idx_scan, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, in.stream, (int)P, (int)dv.idx_waves, dv.d_hist, dv.d_cnt);
-  CRH(hipMemcpyAsync(cnt.data(), dv.d_cnt, sizeof(long long) * P, hipMemcpyDeviceToHost, in.stream));
-  CRH(hipStreamSynchronize(in.stream));
+  MVBA_HIP(hipMemcpyAsync(cnt.data(), dv.d_cnt, sizeof(long long) * P, hipMemcpyDeviceToHost, in.stream));
+  MVBA_HIP(hipStreamSynchronize(in.stream));
   return MVBA_OK;
 }
 
@@ -678,23 +677,23 @@ int build_index_device(const IndexInput &in, const SchurPlan &plan, DeviceIndexB
   long long *d_vp_off = nullptr;
   CR(tmp.alloc(&d_pk, (size_t)L.T)); CR(tmp.alloc(&d_pl, (size_t)L.T)); CR(tmp.alloc(&d_pa, (size_t)L.T));
   CR(tmp.alloc(&d_S, (size_t)P)); CR(tmp.alloc(&d_vp_ptr, (size_t)P + 1)); CR(tmp.alloc(&d_vp_off, (size_t)VP + 1));
-  CRH(hipMemcpyAsync(d_S, L.S.data(), sizeof(int) * P, hipMemcpyHostToDevice, stream));
-  CRH(hipMemcpyAsync(d_vp_ptr, L.vp_ptr.data(), sizeof(int) * (P + 1), hipMemcpyHostToDevice, stream));
-  CRH(hipMemcpyAsync(d_vp_off, L.vp_off.data(), sizeof(long long) * (VP + 1), hipMemcpyHostToDevice, stream));
+  MVBA_HIP(hipMemcpyAsync(d_S, L.S.data(), sizeof(int) * P, hipMemcpyHostToDevice, stream));
+  MVBA_HIP(hipMemcpyAsync(d_vp_ptr, L.vp_ptr.data(), sizeof(int) * (P + 1), hipMemcpyHostToDevice, stream));
+  MVBA_HIP(hipMemcpyAsync(d_vp_off, L.vp_off.data(), sizeof(long long) * (VP + 1), hipMemcpyHostToDevice, stream));
   hipLaunchKernelGGL(dv.hist_lds ? k_idx_fill<false> : k_idx_fill<true>, dim3((unsigned)(dv.idx_waves / IDX_WAVES)), dim3(64 * IDX_WAVES), dv.idx_lds,
                      stream, N, m, (int)P, in.d_pt_ptr, in.d_cam, dv.idx_chunk, dv.d_hist, d_S, d_vp_ptr, d_vp_off, d_pk, d_pl, d_pa,
                      (const int *)nullptr);
-  CRH(hipGetLastError());
+  MVBA_HIP(hipGetLastError());
   timer.lap("items sorted by pair");
   std::vector<long long> lo_tab((size_t)VP * (nR + 1));  // lower bounds of every list at every range boundary
   {
     long long *d_rl = nullptr, *d_lo = nullptr;
     CR(tmp.alloc(&d_rl, (size_t)nR + 1)); CR(tmp.alloc(&d_lo, lo_tab.size()));
-    CRH(hipMemcpyAsync(d_rl, R.lo.data(), sizeof(long long) * (nR + 1), hipMemcpyHostToDevice, stream));
+    MVBA_HIP(hipMemcpyAsync(d_rl, R.lo.data(), sizeof(long long) * (nR + 1), hipMemcpyHostToDevice, stream));
     const long long nt = (long long)lo_tab.size();
     hipLaunchKernelGGL(k_idx_bounds, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, stream, VP, nR, d_vp_off, d_rl, d_pa, d_lo, (const int *)nullptr);
-    CRH(hipMemcpyAsync(lo_tab.data(), d_lo, sizeof(long long) * nt, hipMemcpyDeviceToHost, stream));
-    CRH(hipStreamSynchronize(stream));
+    MVBA_HIP(hipMemcpyAsync(lo_tab.data(), d_lo, sizeof(long long) * nt, hipMemcpyDeviceToHost, stream));
+    MVBA_HIP(hipStreamSynchronize(stream));
     tmp.release(d_rl); tmp.release(d_lo);
   }
   std::vector<int> uid;
@@ -710,8 +709,8 @@ int build_index_device(const IndexInput &in, const SchurPlan &plan, DeviceIndexB
     int *d_sllen = nullptr, *d_wsteps = nullptr;
     CR(tmp.alloc(&d_slbeg, sw.sl_beg.size())); CR(tmp.alloc(&d_sllen, sw.sl_len.size()));
     CR(tmp.alloc(&d_wsteps, (size_t)n_waves)); CR(tmp.alloc(&d_wbeg, (size_t)n_waves + 1));
-    CRH(hipMemcpyAsync(d_slbeg, sw.sl_beg.data(), sizeof(long long) * sw.sl_beg.size(), hipMemcpyHostToDevice, stream));
-    CRH(hipMemcpyAsync(d_sllen, sw.sl_len.data(), sizeof(int) * sw.sl_len.size(), hipMemcpyHostToDevice, stream));
+    MVBA_HIP(hipMemcpyAsync(d_slbeg, sw.sl_beg.data(), sizeof(long long) * sw.sl_beg.size(), hipMemcpyHostToDevice, stream));
+    MVBA_HIP(hipMemcpyAsync(d_sllen, sw.sl_len.data(), sizeof(int) * sw.sl_len.size(), hipMemcpyHostToDevice, stream));
     const int W = plan.W;
     const auto merge_count = W == LANES_W ? k_idx_merge<false, LANES_W> : k_idx_merge<false, PSTEP>;
     const auto merge_fill = W == LANES_W ? k_idx_merge<true, LANES_W> : k_idx_merge<true, PSTEP>;
@@ -719,8 +718,8 @@ int build_index_device(const IndexInput &in, const SchurPlan &plan, DeviceIndexB
                        ix.d_range_o0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, (int *)nullptr, (int *)nullptr, (int *)nullptr,
                        (int *)nullptr, (const long long *)in.d_pt_ptr);
     std::vector<int> ws32(n_waves);
-    CRH(hipMemcpyAsync(ws32.data(), d_wsteps, sizeof(int) * n_waves, hipMemcpyDeviceToHost, stream));
-    CRH(hipStreamSynchronize(stream));  // (sl_beg / sl_len live until here)
+    MVBA_HIP(hipMemcpyAsync(ws32.data(), d_wsteps, sizeof(int) * n_waves, hipMemcpyDeviceToHost, stream));
+    MVBA_HIP(hipStreamSynchronize(stream));  // (sl_beg / sl_len live until here)
     for (long long b = 0; b < n_waves; ++b) sw.w_steps[b] = ws32[b];
     timer.lap("slot merge (count)");
     long long total_steps = 0;
@@ -729,11 +728,11 @@ int build_index_device(const IndexInput &in, const SchurPlan &plan, DeviceIndexB
     const size_t rows = (size_t)total_steps * W;
     CR(engine.alloc(&ix.d_it_k, rows)); CR(engine.alloc(&ix.d_it_l, rows)); CR(engine.alloc(&ix.d_it_a, rows));
     CR(engine.alloc(&ix.d_seg_end, ix.seg_end.size()));
-    CRH(hipMemcpyAsync(d_wbeg, sw.w_beg.data(), sizeof(long long) * (n_waves + 1), hipMemcpyHostToDevice, stream));
+    MVBA_HIP(hipMemcpyAsync(d_wbeg, sw.w_beg.data(), sizeof(long long) * (n_waves + 1), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(merge_fill, dim3((unsigned)n_waves), dim3(64), 0, stream, n_waves, nR, nSeg, slot_skew(W), SLOT_SEG, d_slbeg, d_sllen,
                        ix.d_range_o0, d_pk, d_pl, d_pa, d_wbeg, 0, (int)N, d_wsteps, ix.d_it_k, ix.d_it_l, ix.d_it_a, ix.d_seg_end, (const long long *)in.d_pt_ptr);
-    CRH(hipGetLastError());
-    CRH(hipStreamSynchronize(stream));
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipStreamSynchronize(stream));
     timer.lap("slot merge (fill)");
     finish_slot_waves(plan, sw, total_steps, ix);
   } else {
@@ -763,8 +762,8 @@ int alloc_engine_buffers(mvba_handle *h, K1Tiles &t) {
     CR(h->mem.alloc(&h->d_tile_slot, t.tile_slot.size()));
     CR(h->mem.alloc(&h->d_splits, t.splits.size()));
     CR(h->mem.alloc(&h->d_PLsplit, 9 * (size_t)t.n_split_slots));
-    CRH(hipMemcpy(h->d_tile_slot, t.tile_slot.data(), sizeof(int) * t.tile_slot.size(), hipMemcpyHostToDevice));
-    CRH(hipMemcpy(h->d_splits, t.splits.data(), sizeof(int4) * t.splits.size(), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_tile_slot, t.tile_slot.data(), sizeof(int) * t.tile_slot.size(), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_splits, t.splits.data(), sizeof(int4) * t.splits.size(), hipMemcpyHostToDevice));
   }
   CR(h->mem.alloc(&h->d_tiles, t.tiles.size()));
   for (int i = 0; i < 2; ++i) { CR(h->mem.alloc(&h->d_X[i], 3 * N)); CR(h->mem.alloc(&h->d_cam15[i], (size_t)CAM_IN * m)); }
@@ -772,28 +771,27 @@ int alloc_engine_buffers(mvba_handle *h, K1Tiles &t) {
   CR(h->mem.alloc(&h->d_rec, (size_t)rec_slots * (nobs + 1)));  // + the all-zero record and point row the slot form's padding points at
   if (h->rec_compact) {  // the residuals beside the compact records, the padding record's among them
     CR(h->mem.alloc(&h->d_res, (size_t)nobs + 1));
-    CRH(hipMemset(h->d_res + nobs, 0, sizeof(double2)));
+    MVBA_HIP(hipMemset(h->d_res + nobs, 0, sizeof(double2)));
   }
   if (h->loss != LOSS_SQUARED) {
     CR(h->mem.alloc(&h->d_sqw, nobs + 1));
-    CRH(hipMemset(h->d_sqw, 0, sizeof(double) * (nobs + 1)));
+    MVBA_HIP(hipMemset(h->d_sqw, 0, sizeof(double) * (nobs + 1)));
   }
   CR(h->mem.alloc(&h->d_PL, 9 * N));
   CR(h->mem.alloc(&h->d_PB, (size_t)PBS * (N + 1)));
-  CRH(hipMemset(h->d_rec + (size_t)rec_slots * nobs, 0, sizeof(double2) * rec_slots));
-  CRH(hipMemset(h->d_PB + (size_t)PBS * N, 0, sizeof(double) * PBS));
-  const size_t n9 = 9 * (size_t)m;
-  CR(h->mem.alloc(&h->d_Ab, strip_offset(m, m) + n9));
+  MVBA_HIP(hipMemset(h->d_rec + (size_t)rec_slots * nobs, 0, sizeof(double2) * rec_slots));
+  MVBA_HIP(hipMemset(h->d_PB + (size_t)PBS * N, 0, sizeof(double) * PBS));
+  CR(h->mem.alloc(&h->d_Ab, h->n_Ab()));
   CR(h->mem.alloc(&h->d_Ared, (size_t)(h->D + 1) * h->ld));
   CR(h->mem.alloc(&h->d_Lblk, (size_t)((h->D + SBW - 1) / SBW) * SBW * SBW));
   CR(h->mem.alloc(&h->d_Ztiles, (size_t)((h->D + NB - 1) / NB) * NB * NB));
-  CR(h->mem.alloc(&h->d_dxi, n9));
+  CR(h->mem.alloc(&h->d_dxi, h->n9()));
   CR(h->mem.alloc(&h->d_dX, 3 * N));
   CR(h->mem.alloc(&h->d_partials, h->n_partials));
   CR(h->mem.alloc(&h->d_cost, 2));
   CR(h->mem.alloc(&h->d_flag, 1));
   CR(h->mem.alloc(&h->d_bar, 1 + 4 * (size_t)((9 * m + SBW - 1) / SBW)));  // progress words of the back-substitution
-  CRH(hipHostMalloc((void **)&h->h_cost, 4 * sizeof(double), hipHostMallocMapped));
+  MVBA_HIP(hipHostMalloc((void **)&h->h_cost, 4 * sizeof(double), hipHostMallocMapped));
   memset(h->h_cost, 0, 4 * sizeof(double));
   if (hipHostGetDevicePointer((void **)&h->d_mail, h->h_cost, 0) != hipSuccess) h->d_mail = nullptr;  // (no mapping: copy + sync as before)
   h->h_flag = reinterpret_cast<int *>(h->h_cost + 1);  // cost and flags come back in one copy
@@ -818,43 +816,43 @@ int upload_schur_index(mvba_handle *h, const SchurPlan &plan, SchurIndex &ix) {
   CR(h->mem.alloc(&h->d_wdesc, ix.wdesc.size())); CR(h->mem.alloc(&h->d_wunits, ix.wunits.size()));
   if (!ix.on_device) CR(h->mem.alloc(&h->d_seg_end, ix.seg_end.size()));
   CR(h->mem.alloc(&h->d_prog, (size_t)h->slot_nR * std::max(1, h->slot_nseg) * PACE_STRIDE));
-  if (!ix.seg_end.empty() && !ix.on_device) CRH(hipMemcpy(h->d_seg_end, ix.seg_end.data(), sizeof(int) * ix.seg_end.size(), hipMemcpyHostToDevice));
+  if (!ix.seg_end.empty() && !ix.on_device) MVBA_HIP(hipMemcpy(h->d_seg_end, ix.seg_end.data(), sizeof(int) * ix.seg_end.size(), hipMemcpyHostToDevice));
   if (!ix.wdesc.empty()) {
-    CRH(hipMemcpy(h->d_wdesc, ix.wdesc.data(), sizeof(int4) * ix.wdesc.size(), hipMemcpyHostToDevice));
-    CRH(hipMemcpy(h->d_wunits, ix.wunits.data(), sizeof(int) * ix.wunits.size(), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_wdesc, ix.wdesc.data(), sizeof(int4) * ix.wdesc.size(), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_wunits, ix.wunits.data(), sizeof(int) * ix.wunits.size(), hipMemcpyHostToDevice));
   }
   CR(h->mem.alloc(&h->d_partial, (size_t)UNIT_STRIDE * ix.units.size()));
   if (!ix.it_k.empty()) {
-    CRH(hipMemcpy(h->d_it_k, ix.it_k.data(), sizeof(int) * ix.it_k.size(), hipMemcpyHostToDevice));
-    CRH(hipMemcpy(h->d_it_l, ix.it_l.data(), sizeof(int) * ix.it_l.size(), hipMemcpyHostToDevice));
-    CRH(hipMemcpy(h->d_it_a, ix.it_a.data(), sizeof(int) * ix.it_a.size(), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_it_k, ix.it_k.data(), sizeof(int) * ix.it_k.size(), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_it_l, ix.it_l.data(), sizeof(int) * ix.it_l.size(), hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_it_a, ix.it_a.data(), sizeof(int) * ix.it_a.size(), hipMemcpyHostToDevice));
   }
   if (!ix.it_k.empty() || ix.on_device) {
     if (h->schur_mode == SCHUR_PAIRS) {
       std::vector<int4> qdesc(ix.units.size());  // descriptors in queue order (the kernel indexes both arrays by queue position)
       for (size_t i = 0; i < ix.q_units.size(); ++i) qdesc[i] = ix.units[ix.q_units[i]];
-      CRH(hipMemcpy(h->d_units, qdesc.data(), sizeof(int4) * qdesc.size(), hipMemcpyHostToDevice));
+      MVBA_HIP(hipMemcpy(h->d_units, qdesc.data(), sizeof(int4) * qdesc.size(), hipMemcpyHostToDevice));
       int mx = 0;
       for (int x = 0; x < 8; ++x) mx = std::max(mx, ix.q_ptr[x + 1] - ix.q_ptr[x]);
       h->q_max = mx;
     }
-    if (!ix.q_units.empty()) CRH(hipMemcpy(h->d_q_units, ix.q_units.data(), sizeof(int) * ix.q_units.size(), hipMemcpyHostToDevice));
+    if (!ix.q_units.empty()) MVBA_HIP(hipMemcpy(h->d_q_units, ix.q_units.data(), sizeof(int) * ix.q_units.size(), hipMemcpyHostToDevice));
   }
   // the compact lane form: the descriptors in UNIT order -- a lane takes its pair's cameras (w = k << 16 | l) from its unit's
-  if (h->rec_compact && !ix.units.empty()) CRH(hipMemcpy(h->d_units, ix.units.data(), sizeof(int4) * ix.units.size(), hipMemcpyHostToDevice));
+  if (h->rec_compact && !ix.units.empty()) MVBA_HIP(hipMemcpy(h->d_units, ix.units.data(), sizeof(int4) * ix.units.size(), hipMemcpyHostToDevice));
   if (h->schur_mode == SCHUR_SLOTS && h->n_slot_items) {  // the three step-major arrays -> one 256-byte (768: 64 slots) row per step; they go
     const int W = h->slot_w, row = slot_idx_ints(W);
     const long long n_steps = h->n_slot_items / W;
     CR(h->mem.alloc(&h->d_it_x, (size_t)n_steps * row));
     hipLaunchKernelGGL(k_idx_interleave, dim3((unsigned)((n_steps * row + 255) / 256)), dim3(256), 0, h->stream, n_steps, W, row, h->d_it_k, h->d_it_l,
                        h->d_it_a, h->d_it_x);
-    CRH(hipGetLastError());
-    CRH(hipStreamSynchronize(h->stream));
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipStreamSynchronize(h->stream));
     h->mem.release(h->d_it_k); h->mem.release(h->d_it_l); h->mem.release(h->d_it_a);
   }
-  CRH(hipMemcpy(h->d_unit_ptr, ix.unit_ptr.data(), sizeof(int) * P1, hipMemcpyHostToDevice));
-  CRH(hipMemcpy(h->d_q_ptr, ix.q_ptr.data(), sizeof(int) * 9, hipMemcpyHostToDevice));
-  CRH(hipMemset(h->d_partial, 0, sizeof(double) * UNIT_STRIDE * std::max<size_t>(ix.units.size(), 1)));
+  MVBA_HIP(hipMemcpy(h->d_unit_ptr, ix.unit_ptr.data(), sizeof(int) * P1, hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(h->d_q_ptr, ix.q_ptr.data(), sizeof(int) * 9, hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemset(h->d_partial, 0, sizeof(double) * UNIT_STRIDE * std::max<size_t>(ix.units.size(), 1)));
   return MVBA_OK;
 }
 
@@ -862,11 +860,11 @@ int upload_engine(mvba_handle *h, const mvba_problem *p, const std::vector<int> 
   const long long N = h->N, nobs = h->nobs;
   const int m = h->m;
   if (nobs) {
-    CRH(hipMemcpy(h->d_obs_pt, obs_pt.data(), sizeof(int) * nobs, hipMemcpyHostToDevice));
+    MVBA_HIP(hipMemcpy(h->d_obs_pt, obs_pt.data(), sizeof(int) * nobs, hipMemcpyHostToDevice));
     if (p->xy_layout == 1) {  // image planes [m][N][2], as a caller's stack of per-image arrays lies in memory: into observation order here
       DevBufs tmp;
       double2 *planes = nullptr;  // (the host's strided gather of the same bytes: 0.1 s at 1 M points x 12 images)
-      CRH(hipMalloc((void **)&planes, sizeof(double2) * nobs));
+      MVBA_HIP(hipMalloc((void **)&planes, sizeof(double2) * nobs));
       tmp.own(planes);
       hipError_t e = hipMemcpy(planes, p->xy, sizeof(double2) * nobs, hipMemcpyHostToDevice);
       if (e == hipSuccess) {
@@ -874,15 +872,15 @@ int upload_engine(mvba_handle *h, const mvba_problem *p, const std::vector<int> 
         e = hipGetLastError();
         if (e == hipSuccess) e = hipDeviceSynchronize();
       }
-      CRH(e);
+      MVBA_HIP(e);
     } else {
-      CRH(hipMemcpy(h->d_xy, p->xy, sizeof(double2) * nobs, hipMemcpyHostToDevice));
+      MVBA_HIP(hipMemcpy(h->d_xy, p->xy, sizeof(double2) * nobs, hipMemcpyHostToDevice));
     }
   }
-  CRH(hipMemcpy(h->d_tiles, t.tiles.data(), sizeof(int) * t.tiles.size(), hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(h->d_tiles, t.tiles.data(), sizeof(int) * t.tiles.size(), hipMemcpyHostToDevice));
   // points without observations are never written by K1: their blocks stay zero (-> singular, ref :128)
-  CRH(hipMemset(h->d_PL, 0, sizeof(double) * 9 * std::max<long long>(N, 1)));
-  CRH(hipMemset(h->d_flag, 0, sizeof(int)));
+  MVBA_HIP(hipMemset(h->d_PL, 0, sizeof(double) * 9 * std::max<long long>(N, 1)));
+  MVBA_HIP(hipMemset(h->d_flag, 0, sizeof(int)));
   if (h->schur_mode == SCHUR_DENSE) {  // partial tiles of k_schur_dense: (tile pairs + one per camera) x 256 doubles per workgroup
     const int T = (9 * m + 15) / 16;
     int n_cu_dense = 256;
@@ -892,7 +890,7 @@ int upload_engine(mvba_handle *h, const mvba_problem *p, const std::vector<int> 
     CR(h->mem.alloc(&h->d_dense_part, (size_t)h->dense_blocks * h->dense_tiles * 256));
     if (!plan.dense_obs.empty()) {
       CR(h->mem.alloc(&h->d_dense_obs, plan.dense_obs.size()));
-      CRH(hipMemcpy(h->d_dense_obs, plan.dense_obs.data(), sizeof(int) * plan.dense_obs.size(), hipMemcpyHostToDevice));
+      MVBA_HIP(hipMemcpy(h->d_dense_obs, plan.dense_obs.data(), sizeof(int) * plan.dense_obs.size(), hipMemcpyHostToDevice));
     }
   }
   if (h->use_pairs) CR(upload_schur_index(h, plan, ix));
@@ -906,34 +904,34 @@ int set_kernel_attributes(mvba_handle *h, const CreateKnobs &knobs) {
   auto set_lds = [](const void *f, size_t bytes) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
   const size_t cam_lds = cam_lds_bytes(m, h->gcam, true);
   if (h->gcam) { CR(h->mem.alloc(&h->d_cam18, (size_t)m * CAM_LDS)); CR(h->mem.alloc(&h->d_dxi10, (size_t)m * DXI_LDS)); }
-  for (int G : {2, 4, 8})
-    for (int bt : {256, 512, 1024}) {
-      CRH(set_lds(backsub_kernel(G, bt, false).fn(false), cam_lds));
-      if (robust) CRH(set_lds(backsub_kernel(G, bt, false).fn(true), cam_lds));
+  for (int G : K5_LANES)  // every cell of K5's width rules (mvba_engine_host.h)
+    for (int bt : TABLE_BLOCK_THREADS) {
+      MVBA_HIP(set_lds(backsub_kernel(G, bt, false).fn(false), cam_lds));
+      if (robust) MVBA_HIP(set_lds(backsub_kernel(G, bt, false).fn(true), cam_lds));
     }
-  CRH(set_lds((const void *)k_chol_super, SUPER_LDS));
-  CRH(set_lds((const void *)k_chol_backsolve_all<true>, BACKSOLVE_LDS));
+  MVBA_HIP(set_lds((const void *)k_chol_super, SUPER_LDS));
+  MVBA_HIP(set_lds((const void *)k_chol_backsolve_all<true>, BACKSOLVE_LDS));
   {
     // the persistent back-substitution needs its whole grid resident: at most one workgroup per CU
     int per_cu = 0;
-    CRH(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-    CRH(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_chol_backsolve_all<true>, SUPER_THREADS, BACKSOLVE_LDS));
+    MVBA_HIP(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+    MVBA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_chol_backsolve_all<true>, SUPER_THREADS, BACKSOLVE_LDS));
     h->chol_onepass = per_cu >= 1 && !knobs.chol_launches;
     h->trail64_min = knobs.trail64_min;
     h->barrier_polls = knobs.barrier_polls;
   }
   const size_t k1_lds = k1_lds_bytes(m, h->gcam, h->k1_threads);
-  CRH(set_lds(resid_jac_kernel(h->gcam, h->loss).fn(false), k1_lds));
-  if (h->rec_compact) CRH(set_lds((const void *)k_resid_jac<false, LOSS_SQUARED, CompactRec>, k1_lds));
-  CRH(set_lds(cost_kernel(false, h->loss).fn(false), cam_lds));
-  CRH(set_lds((const void *)k_residuals<false>, cam_lds));
+  MVBA_HIP(set_lds(resid_jac_kernel(h->gcam, h->loss).fn(false), k1_lds));
+  if (h->rec_compact) MVBA_HIP(set_lds((const void *)k_resid_jac<false, LOSS_SQUARED, CompactRec>, k1_lds));
+  MVBA_HIP(set_lds(cost_kernel(false, h->loss).fn(false), cam_lds));
+  MVBA_HIP(set_lds((const void *)k_residuals<false>, cam_lds));
   if (robust) {
-    CRH(set_lds(resid_jac_kernel(h->gcam, h->loss).fn(true), k1_lds));
-    CRH(set_lds(cost_kernel(false, h->loss).fn(true), cam_lds));
+    MVBA_HIP(set_lds(resid_jac_kernel(h->gcam, h->loss).fn(true), k1_lds));
+    MVBA_HIP(set_lds(cost_kernel(false, h->loss).fn(true), cam_lds));
   }
   if (h->schur_mode == SCHUR_DENSE) {  // the limit of the INSTANTIATION -- its largest camera count -- so that engines with other m share it
     const int T = (9 * m + 15) / 16;
-    CRH(set_lds(dense_kernel(T, h->d_dense_obs != nullptr).fn(robust), dense_lds_bytes(T, 16 * T / 9)));
+    MVBA_HIP(set_lds(dense_kernel(T, h->d_dense_obs != nullptr).fn(robust), dense_lds_bytes(T, 16 * T / 9)));
   }
   return MVBA_OK;
 }
@@ -942,14 +940,14 @@ int set_kernel_attributes(mvba_handle *h, const CreateKnobs &knobs) {
 int build_engine(mvba_handle *h, const mvba_problem *p, const CreateKnobs &knobs, const std::vector<int> &obs_pt, K1Tiles &tiles, CreateTimer &timer) {
   const long long N = h->N, nobs = h->nobs;
   const int m = h->m;
-  if (p->device >= 0) CRH(hipSetDevice(p->device));
-  CRH(hipGetDevice(&h->device));
+  if (p->device >= 0) MVBA_HIP(hipSetDevice(p->device));
+  MVBA_HIP(hipGetDevice(&h->device));
   // the topology goes up first: the Schur index is built from it on the device
-  CRH(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  MVBA_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   CR(h->mem.alloc(&h->d_pt_ptr, N + 1));
   CR(h->mem.alloc(&h->d_cam, nobs));
-  CRH(hipMemcpy(h->d_pt_ptr, p->pt_ptr, sizeof(long long) * (N + 1), hipMemcpyHostToDevice));
-  if (nobs) CRH(hipMemcpy(h->d_cam, p->cam_idx, sizeof(int) * nobs, hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(h->d_pt_ptr, p->pt_ptr, sizeof(long long) * (N + 1), hipMemcpyHostToDevice));
+  if (nobs) MVBA_HIP(hipMemcpy(h->d_cam, p->cam_idx, sizeof(int) * nobs, hipMemcpyHostToDevice));
   timer.lap("device, topology upload");
   h->k1_threads = k1_block_threads(m, h->gcam);
 
@@ -1009,4 +1007,3 @@ int create_engine(const mvba_problem *p, int loss, double loss_b, mvba_handle **
 }
 
 #undef CR
-#undef CRH

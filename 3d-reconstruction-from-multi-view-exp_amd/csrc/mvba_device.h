@@ -1,9 +1,9 @@
 // What the stages of the BA device code share -- gfx950: the fixed-order sums (wave_sum, block_sum), the camera table in LDS
-// or in device memory (load_cams_to_lds, stage_cams, cam_row, dxi_row), the packed strips of the reduced system (strip_offset),
+// or in device memory (load_cams_to_lds, stage_cams, cam_row, dxi_row),
 // the gauge's kept parameters (keep_index), scalar loads of wave-uniform operands (MVBA_CONST_AS / as_const), and the constants
 // of the buffers that more than one stage touches (REC, REC_C, CompactRec, LDS_CAMERAS, PBS, PACE_STRIDE, LossArgs).
 //
-// Included by mvba.hip first inside its device-code namespace: uses expand_cam, CAM_IN, CAM_LDS and DXI_LDS of mvba_common.h.
+// Included by mvba.hip first inside its device-code namespace: uses expand_cam, strip_offset, CAM_IN, CAM_LDS and DXI_LDS of mvba_common.h.
 // The stage headers after it (mvba_linearize.h, mvba_schur.h, mvba_dense.h, mvba_solve.h, mvba_tail.h, mvba_cov.h, mvba_map.h)
 // each use something from here.
 
@@ -30,13 +30,6 @@ __device__ __forceinline__ double block_sum(double v, double *s_red /*[16]*/) {
 __device__ __forceinline__ void load_cams_to_lds(const double *__restrict__ cam15, int m, double f0,
                                                  double *s_cam) {
   for (int k = threadIdx.x; k < m; k += blockDim.x) expand_cam(cam15 + (size_t)k * CAM_IN, f0, s_cam + k * CAM_LDS);
-}
-
-// Reduced system storage: the upper block triangle of A packed strip by strip -- strip k is a
-// row-major 9 x 9(m-k) block (cameras l >= k) at offset 81 (k m - k (k-1) / 2) -- followed by b
-// (9m).  81 m (m+1) / 2 + 9m doubles: half of the dense 9m x 9m, and what the all-reduce ships.
-__host__ __device__ __forceinline__ size_t strip_offset(int k, int m) {
-  return 81 * ((size_t)k * m - (size_t)k * (k - 1) / 2);
 }
 
 __device__ __forceinline__ int keep_index(int i, int gauge_axis) {

@@ -57,20 +57,6 @@ struct DevBufs {
   }
 };
 
-// The full 128-byte record of an observation (16 doubles: slot s = (row 0, row 1) at [2 s], [2 s + 1]; J_X 0..2, d/df 3, J_omega 4..6,
-// residual 7) from the compact one (`c8`: slots 0..3), its residual, its point and its camera's centre, as mvba_debug_read hands
-// it out: J_omega = (row of J_X) x (X - t), the expression of obs_math and of k_schur_lanes_compact.
-inline void expand_compact_record(const double *c8, const double *e2, const double *X3, const double *t3, double *full16) {
-  for (int i = 0; i < 8; ++i) full16[i] = c8[i];
-  const double d[3] = {X3[0] - t3[0], X3[1] - t3[1], X3[2] - t3[2]};
-  for (int i = 0; i < 3; ++i) {
-    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
-    for (int rr = 0; rr < 2; ++rr) full16[8 + 2 * i + rr] = c8[2 * i1 + rr] * d[i2] - c8[2 * i2 + rr] * d[i1];
-  }
-  full16[14] = e2[0];
-  full16[15] = e2[1];
-}
-
 // ------------------------------------------------------------------ SVD workspace, host arithmetic only
 // order[0 .. k) <- the indices of v[0], v[stride], ..., v[(k - 1) stride], largest value first
 inline void descending_order(const double *v, size_t stride, int k, int *order) {

@@ -124,8 +124,9 @@ def tile_ranges(tiles):
     return start[:-1], start[1:], tiles[:-1] < 0
 
 
-# ---------------------------------------------------------------- csrc/mvba.hip (launch_tail_and_cost, mvba_covariance;
-# LDS_CAMERAS: csrc/mvba_device.h): the width rules, restated
+# ---------------------------------------------------------------- csrc/mvba_engine_host.h (k5_lanes, table_block_threads, cov_lanes;
+# launched by launch_tail_and_cost in csrc/mvba_step.h and cov_blocks in csrc/mvba_cov_host.h; LDS_CAMERAS: csrc/mvba_device.h): the
+# width rules, restated
 CAM_LDS, DXI_LDS, LDS_CAMERAS = 18, 10, 646
 K5_G_LIMITS = (40.0, 100.0)       # mean degree: two lanes per point up to 40, four up to 100, eight beyond
 COV_G_LIMITS = (12.0, 24.0, 48.0)  # mean pair count 0.5 d (d + 1): 8 lanes up to 12, 16 up to 24, 32 up to 48, 64 beyond
