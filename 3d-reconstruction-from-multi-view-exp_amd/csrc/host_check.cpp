@@ -2,8 +2,8 @@
 // logic (mvba_engine_host.h: build_parameter_map, reduced_system_residual, expand_packed_A, expand_compact_record and the record_to_*
 // fills of mvba_debug_read, the cam15 row, the width rules of K5, the cost pass and the covariance) and the host logic of a RANSAC
 // round (mvba_ransac_host.h: rs_pick, rs_accept, rs_current and rs_other, RsTile, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
-// builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify) and the matcher's (mvba_match_host.h: its argument
-// checks, the chunk rule, the ratio test) on hand-made inputs.  A program of its own,
+// builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify, trk_grid) and the matcher's (mvba_match_host.h: its
+// argument checks, the chunk rule, the ratio test, the plan of a call and the block lists of a chunk) and lap_rest on hand-made inputs.  A program of its own,
 // meant for the host sanitizers (`make host_check`); it makes no HIP call and needs no GPU.
 #include <algorithm>
 #include <cmath>
@@ -465,6 +465,87 @@ int main() {
       CHECK(p1 > p0 && p1 <= 5);
       p0 = p1;
     }
+  }
+  {  // its plan and its chunk lists, at budgets of a few dozen rows so that hand-made inputs cross chunk boundaries
+    auto check_plan = [&](const std::vector<int64_t> &kp, const std::vector<int32_t> &pr, bool mutual, int64_t budget) {
+      const int32_t np = (int32_t)(pr.size() / 2);
+      auto size = [&](int im) { return (int)(kp[im + 1] - kp[im]); };
+      const MatchPlan pl = match_plan(kp.data(), pr.data(), np, mutual, budget);
+      // the cuts are repeated match_chunk_end and cover 0 .. n_pairs exactly
+      CHECK(pl.cut.front() == 0 && pl.cut.back() == np && (np > 0 || pl.cut.size() == 1));
+      for (size_t c = 0; c + 1 < pl.cut.size(); ++c)
+        CHECK(pl.cut[c + 1] > pl.cut[c] && pl.cut[c + 1] == match_chunk_end(kp.data(), pr.data(), np, pl.cut[c], mutual, budget));
+      CHECK(pl.max_blocks == (pl.max_q + pl.max_r) / MATCH_TQ + 2 * pl.max_p + 1);
+      CHECK(pl.max_dec == (pl.max_q + 255) / 256 && pl.max_sb == (pl.max_q + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK);
+      if (!mutual) CHECK(pl.max_r == 0);
+      MatchLists L;  // (one for all chunks, as the entry point keeps it)
+      size_t seen_q = 0, seen_r = 0, seen_p = 0;
+      for (size_t c = 0; c + 1 < pl.cut.size(); ++c) {
+        const int32_t p0 = pl.cut[c], P = pl.cut[c + 1] - p0;
+        match_chunk_lists(kp.data(), pr.data(), p0, pl.cut[c + 1], mutual, L);
+        CHECK(L.P == P && L.qoff.size() == (size_t)P + 1 && L.roff.size() == (size_t)P + 1 && L.ncand.size() == (size_t)P);
+        CHECK(L.qoff[0] == 0 && L.roff[0] == 0 && L.Qc == L.qoff[P]);
+        // the bounds the buffers were sized by
+        CHECK(L.fwd.size() + L.rev.size() <= pl.max_blocks && (size_t)L.Qc <= pl.max_q && (size_t)L.roff[P] <= pl.max_r && (size_t)P <= pl.max_p);
+        seen_q = std::max(seen_q, (size_t)L.Qc), seen_r = std::max(seen_r, (size_t)L.roff[P]), seen_p = std::max(seen_p, (size_t)P);
+        if (!mutual) CHECK(L.rev.empty() && std::all_of(L.roff.begin(), L.roff.end(), [](int x) { return x == 0; }));
+        // every row of either direction belongs to one block, which asks for the row's own query against the pair's other image
+        for (int dir = 0; dir < (mutual ? 2 : 1); ++dir) {
+          const std::vector<int> &off = dir ? L.roff : L.qoff;
+          std::vector<int> node((size_t)off[P]), c0((size_t)off[P]), nc((size_t)off[P]), hits((size_t)off[P], 0);
+          for (int i = 0; i < P; ++i) {
+            const int q = pr[2 * (p0 + i) + dir], cnd = pr[2 * (p0 + i) + 1 - dir];
+            CHECK(off[i + 1] - off[i] == size(q));
+            if (!dir) CHECK(L.ncand[i] == size(cnd));
+            for (int j = 0; j < size(q); ++j) node[off[i] + j] = (int)kp[q] + j, c0[off[i] + j] = (int)kp[cnd], nc[off[i] + j] = size(cnd);
+          }
+          for (const MatchBlock &b : dir ? L.rev : L.fwd) {
+            CHECK(b.nq >= 1 && b.nq <= MATCH_TQ && b.out0 >= 0 && b.out0 + b.nq <= off[P]);
+            if (!(b.nq >= 1 && b.out0 >= 0 && b.out0 + b.nq <= off[P])) continue;
+            for (int j = 0; j < b.nq; ++j) {
+              ++hits[b.out0 + j];
+              CHECK(node[b.out0 + j] == b.q0 + j && c0[b.out0 + j] == b.c0 && nc[b.out0 + j] == b.nc);
+            }
+          }
+          CHECK(std::all_of(hits.begin(), hits.end(), [](int x) { return x == 1; }));
+        }
+      }
+      CHECK(seen_q == pl.max_q && seen_r == pl.max_r && seen_p == pl.max_p);  // the largest, not merely a bound
+      return pl;
+    };
+    // images of 10, 0, 30, 5, 1, TQ - 1, TQ, TQ + 1 and 300 keypoints; pair (1, 3) has no queries, (0, 1) and (3, 1) no candidates,
+    // (8, 2) alone is larger than every small budget
+    std::vector<int64_t> kp{0};
+    for (int s : {10, 0, 30, 5, 1, MATCH_TQ - 1, MATCH_TQ, MATCH_TQ + 1, 300}) kp.push_back(kp.back() + s);
+    const std::vector<int32_t> pr{0, 2, 1, 3, 2, 0, 0, 1, 8, 2, 3, 1, 5, 4, 6, 4, 7, 4, 4, 7, 4, 5, 6, 7, 7, 8, 3, 4, 1, 0};
+    for (int mutual = 0; mutual < 2; ++mutual)
+      for (int64_t budget : {(int64_t)0, (int64_t)1, (int64_t)35, (int64_t)40, (int64_t)129, (int64_t)300, (int64_t)700, MATCH_CHUNK_QUERIES}) {
+        const MatchPlan pl = check_plan(kp, pr, mutual != 0, budget);
+        if (budget == MATCH_CHUNK_QUERIES) CHECK(pl.cut.size() == 2 && pl.max_p == pr.size() / 2);
+        if (budget == 1) CHECK(pl.cut.size() == pr.size() / 2 + 1 && pl.max_p == 1 && pl.max_q == 300);  // (every pair alone)
+      }
+    {  // many pairs of one-keypoint images: every job is a block of its own, the 2 max_p term
+      std::vector<int64_t> ones{0};
+      std::vector<int32_t> chain;
+      for (int i = 0; i < 40; ++i) ones.push_back(i + 1);
+      for (int i = 0; i + 1 < 40; ++i) chain.insert(chain.end(), {i, i + 1});
+      for (int64_t budget : {(int64_t)1, (int64_t)7, (int64_t)1000}) {
+        check_plan(ones, chain, false, budget);
+        const MatchPlan pl = check_plan(ones, chain, true, budget);
+        if (budget == 1000) CHECK(pl.max_p == 39 && pl.max_q == 39 && pl.max_r == 39 && pl.max_blocks == 79);  // 78 blocks in use
+      }
+    }
+    {  // no pairs; and pairs of images that are all empty: one chunk without a query
+      const MatchPlan none = check_plan({0, 4, 9}, {}, true, 10);
+      CHECK(none.cut.size() == 1 && none.max_q == 0 && none.max_p == 0 && none.max_blocks == 1);
+      for (int mutual = 0; mutual < 2; ++mutual) {
+        const MatchPlan empty = check_plan({0, 0, 0, 0}, {0, 1, 1, 2, 2, 0}, mutual != 0, 0);
+        CHECK(empty.cut.size() == 2 && empty.max_q == 0 && empty.max_r == 0 && empty.max_p == 3 && empty.max_blocks == 7 && empty.max_dec == 0);
+      }
+    }
+    // the grid rule the matcher shares with the track builder, and the "other" slot of a call's timings
+    CHECK(trk_grid(0) == 1 && trk_grid(1) == 1 && trk_grid(256) == 1 && trk_grid(257) == 2 && trk_grid((1LL << 31) - 1) == (1u << 23));
+    CHECK(lap_rest(10.0, 3.0) == 7.0 && lap_rest(3.0, 10.0) == 0.0 && lap_rest(5.0, 5.0) == 0.0 && lap_rest(0.0, 0.0) == 0.0);
   }
   {  // its checks, with their texts, in the order the entry point looks at its arguments
     const int64_t kp[4] = {0, 2, 2, 5}, down[4] = {0, 3, 2, 5}, off[3] = {1, 2, 3}, big[2] = {0, 1LL << 31}, none[3] = {0, 0, 0};

@@ -365,7 +365,7 @@ int mvba_host_obs_math(const double *X3, const double *cam15, const double *xy2,
 #include "mvba_cov_host.h"  // mvba_covariance, as stages
 #include "mvba_debug.h"     // the snapshot log, profiling and statistics, mvba_get_info, mvba_debug_read
 
-#include "mvba_start.h"  // what the three headers below share: the Jacobi, the chunk tree, list checks and upload
+#include "mvba_start.h"  // what the headers below share: the Jacobi, the chunk tree, list checks and upload, the clock and event laps of a call
 #include "mvba_init.h"  // initial estimates: mvba_triangulate, mvba_triangulate_state, mvba_resect
 #include "mvba_twoview.h"  // two-view start: mvba_covisibility, mvba_two_view
 #include "mvba_ransac.h"  // robust two-view start: mvba_two_view_robust, mvba_ransac_sample

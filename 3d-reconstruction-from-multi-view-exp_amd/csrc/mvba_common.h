@@ -23,6 +23,9 @@ inline int fail(int code, const std::string &msg) {
       return ::mvba::fail(MVBA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
   } while (0)
 
+// the "other" slot of a call's timings_ms: its wall time less the laps its events measured, never below 0
+inline double lap_rest(double wall_ms, double kernel_ms) { return wall_ms > kernel_ms ? wall_ms - kernel_ms : 0.0; }
+
 // The engine's status word (d_flag on the device, h_flag beside the cost on the host): kernels OR bits in, the host reads them
 // after the step and clears the word.  The ranks of a distributed run exchange the word, so the values are fixed.
 enum : int {

@@ -1,7 +1,7 @@
 // Initial estimates for BA (mvba_triangulate, mvba_triangulate_state, mvba_resect) -- kernels and host code, gfx950.
 //
 // Included by mvba.hip after mvba_start.h: uses mvba_ransac_host.h's CamChunks, mvba_start.h's sym_eig_jacobi, eig_extremes, chunk_sum, init_check_list,
-// init_check_cameras, upload_list, InitClock and EvGuard, and mvba.hip's mvba_handle, DevBufs, fail and MVBA_HIP.  Nothing
+// init_check_cameras, upload_list, InitClock and EvLaps, and mvba.hip's mvba_handle, DevBufs, fail and MVBA_HIP.  Nothing
 // here runs on the LM path, and nothing on the LM path calls into here.  
 //
 // Triangulation: ONE THREAD PER POINT.  A point's observations are consecutive in the CSR list, so a thread walks them in
@@ -331,23 +331,15 @@ int launch_triangulate(hipStream_t stream, long long npts, int m, const double *
   const int lds = (int)(sizeof(double) * 12 * m);
   MVBA_HIP(hipFuncSetAttribute((const void *)k_triangulate, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   const int grid = (int)std::max<long long>(1, std::min<long long>(2048, (npts + 255) / 256));
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  EvGuard guard{ev, 2};  // (destroyed on every return)
-  hipEvent_t &ea = ev[0], &eb = ev[1];
-  if (ms) {
-    MVBA_HIP(hipEventCreate(&ea));
-    MVBA_HIP(hipEventCreate(&eb));
-    hipEventRecord(ea, stream);
-  }
+  EvLaps ev;  // (events only when the time is asked for: without them a mark records nothing)
+  if (ms)
+    if (int rc = ev.create(2)) return rc;
+  ev.mark(stream);
   hipLaunchKernelGGL(k_triangulate, dim3(grid), dim3(256), lds, stream, npts, m, K, R, t, pt_ptr, cam, xy, n_refine, X, quality, status, keep_bad);
   hipError_t e = hipGetLastError();
-  if (ms) hipEventRecord(eb, stream);
+  ev.mark(stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (ms) {
-    float f = 0.f;
-    if (e == hipSuccess) hipEventElapsedTime(&f, ea, eb);
-    *ms = f;
-  }
+  if (ms) *ms = e == hipSuccess ? ev.ms(0, 1) : 0.0;
   if (e != hipSuccess) return fail(MVBA_ERR_HIP, std::string("k_triangulate: ") + hipGetErrorString(e));
   return MVBA_OK;
 }
@@ -590,12 +582,11 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
         (rc = tmp.alloc(&dnorm, RS_NORM * (size_t)m)) || (rc = tmp.alloc(&dP, 12 * (size_t)m)))
       return rc;
     if (timings_ms) timings_ms[0] = clk.lap();
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    EvGuard guard{ev, 4};
-    for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
+    EvLaps ev;
+    if ((rc = ev.create(4))) return rc;
     const dim3 gm((m + 255) / 256), b256(256);
     auto combine = [&](int nv) { hipLaunchKernelGGL(k_resect_combine, dim3((m * nv + 255) / 256), b256, 0, 0, m, nv, w.dlc_ch, dpart, dS); };
-    hipEventRecord(ev[0], 0);
+    ev.mark();
     hipLaunchKernelGGL(k_resect_chunk<0>, dim3(n_ch), dim3(START_CHUNK), 0, 0, w.dch_cam, w.dch_start, w.dch_cnt, w.dpt, w.dxy, w.dX, (const double *)nullptr, dpart);
     combine(6);
     hipLaunchKernelGGL(k_resect_norm, gm, b256, 0, 0, m, 0, dS, dnorm);
@@ -604,7 +595,7 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
     hipLaunchKernelGGL(k_resect_norm, gm, b256, 0, 0, m, 1, dS, dnorm);
     hipLaunchKernelGGL(k_resect_chunk<2>, dim3(n_ch), dim3(START_CHUNK), 0, 0, w.dch_cam, w.dch_start, w.dch_cnt, w.dpt, w.dxy, w.dX, dnorm, dpart);
     combine(40);
-    hipEventRecord(ev[1], 0);
+    ev.mark();
     MVBA_HIP(hipGetLastError());
     MVBA_HIP(hipMemcpy(S40.data(), dS, sizeof(double) * 40 * m, hipMemcpyDeviceToHost));
     MVBA_HIP(hipMemcpy(norm.data(), dnorm, sizeof(double) * RS_NORM * m, hipMemcpyDeviceToHost));
@@ -615,16 +606,13 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
         for (int j = 0; j < 12; ++j) Pm[12 * (size_t)k + j] = NAN;
     }
     MVBA_HIP(hipMemcpy(dP, Pm.data(), sizeof(double) * 12 * m, hipMemcpyHostToDevice));
-    hipEventRecord(ev[2], 0);
+    ev.mark();
     hipLaunchKernelGGL(k_resect_chunk<3>, dim3(n_ch), dim3(START_CHUNK), 0, 0, w.dch_cam, w.dch_start, w.dch_cnt, w.dpt, w.dxy, w.dX, dP, dpart);
     combine(1);
-    hipEventRecord(ev[3], 0);
+    ev.mark();
     MVBA_HIP(hipGetLastError());
     MVBA_HIP(hipMemcpy(Sr.data(), dS, sizeof(double) * m, hipMemcpyDeviceToHost));
-    float f1 = 0.f, f2 = 0.f;
-    hipEventElapsedTime(&f1, ev[0], ev[1]);
-    hipEventElapsedTime(&f2, ev[2], ev[3]);
-    kernel_ms = (double)f1 + f2;
+    kernel_ms = ev.ms(0, 1) + ev.ms(2, 3);
   }
   for (int k = 0; k < m; ++k) {
     for (int j = 0; j < 12; ++j) P[12 * (size_t)k + j] = Pm[12 * (size_t)k + j];
@@ -636,7 +624,7 @@ int mvba_resect(const double *X, int64_t n_points, const int64_t *pt_ptr, const 
   }
   if (timings_ms) {
     timings_ms[1] = kernel_ms;
-    timings_ms[2] = std::max(0.0, clk.lap() - kernel_ms);  // the copies back, the host's eigen-solves and the second upload of P
+    timings_ms[2] = lap_rest(clk.lap(), kernel_ms);  // the copies back, the host's eigen-solves and the second upload of P
   }
   return MVBA_OK;
 }

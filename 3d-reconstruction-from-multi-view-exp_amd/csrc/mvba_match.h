@@ -1,8 +1,11 @@
 // Matching of uint8 descriptors (mvba_match_descriptors) -- kernels and host code, gfx950.
 //
-// Included by mvba.hip after mvba_tracks.h: uses its tracks_scan, trk_grid and trk_u64, mvba_start.h's InitClock and EvGuard,
-// mvba.hip's DevBufs, fail and MVBA_HIP, and mvba_match_host.h's checks, chunk rule and ratio test.  Nothing here runs on the
-// LM path.  
+// Included by mvba.hip after mvba_tracks.h: uses its tracks_scan and trk_u64, mvba_tracks_host.h's trk_grid, mvba_start.h's
+// InitClock and EvLaps, mvba.hip's DevBufs, fail and MVBA_HIP, and mvba_match_host.h's MatchBlock, checks, plan (match_plan),
+// chunk lists (match_chunk_lists) and ratio test.  Nothing here runs on the LM path.  
+//
+// The host side in stages: the plan and the lists are mvba_match_host.h's; MatchDev owns the device buffers, match_chunk_run
+// uploads and launches one chunk, match_chunk_read brings its part of the answer back; the entry point strings them together.
 //
 // Integers only, except the one double multiply and compare of the ratio test; no atomics.  A byte x becomes the signed byte
 // x - 128 by x ^ 0x80 (whole dwords at a time), which leaves every distance as it is, and
@@ -33,11 +36,6 @@ constexpr int MATCH_NONE = 0x7fffffff;      // "no distance yet"
 constexpr int MATCH_PAD_KEY = -(1 << 30);   // the key of a row beyond the image: v = MATCH_PAD_V, above every |b'|^2 - 2 a'.b' (below 2^25 in magnitude)
 constexpr int MATCH_PAD_V = 1 << 26;
 constexpr unsigned MATCH_FLIP = 0x80808080u;  // x ^ 0x80 on the four bytes of a dword: x - 128 as a signed byte
-
-// MATCH_TQ queries [q0, q0 + nq) (node ids) of one directed job against the candidates [c0, c0 + nc); results at out0 + local query
-struct MatchBlock {
-  int q0, nq, c0, nc, out0;
-};
 
 __device__ __forceinline__ match_v4 match_load16(const unsigned char *p) {
   const uint4 v = *reinterpret_cast<const uint4 *>(p);
@@ -250,10 +248,97 @@ int match_launch_nn(int n_blocks, const MatchBlock *blocks, const unsigned char 
   }
 }
 
-// the blocks of the directed job (query image q, candidate image c), its results from row `out` on
-void match_add_blocks(std::vector<MatchBlock> &blocks, const int64_t *kp_ptr, int q, int c, int out) {
-  const int q0 = (int)kp_ptr[q], nq = (int)(kp_ptr[q + 1] - kp_ptr[q]), c0 = (int)kp_ptr[c], nc = (int)(kp_ptr[c + 1] - kp_ptr[c]);
-  for (int at = 0; at < nq; at += MATCH_TQ) blocks.push_back(MatchBlock{q0 + at, std::min(MATCH_TQ, nq - at), c0, nc, out + at});
+// The device buffers of a call, each as large as the largest chunk of the plan needs it; freed when the owner goes.
+struct MatchDev {
+  DevBufs tmp;
+  unsigned char *desc = nullptr, *code = nullptr;                                        // [n][dim]; the rule of a query
+  int *norm = nullptr;                                                                   // [n]
+  int *best = nullptr, *d1 = nullptr, *d2 = nullptr, *rbest = nullptr, *rd1 = nullptr;   // per query row, forwards and backwards
+  int *qoff = nullptr, *roff = nullptr, *ncand = nullptr, *part = nullptr, *dist = nullptr;
+  int2 *kp = nullptr;
+  MatchBlock *blocks = nullptr;  // fwd, then rev
+  trk_u64 *key = nullptr, *scan = nullptr, *sums = nullptr, *total = nullptr;
+  long long *ptr = nullptr;
+  size_t max_blocks = 0;
+  int n = 0, dim = 0;
+
+  int alloc(const MatchPlan &pl, int n_nodes, int dim_) {
+    int rc;
+    n = n_nodes, dim = dim_, max_blocks = pl.max_blocks;
+    if ((rc = tmp.alloc(&desc, (size_t)n * dim)) || (rc = tmp.alloc(&norm, (size_t)n)) || (rc = tmp.alloc(&best, pl.max_q)) ||
+        (rc = tmp.alloc(&d1, pl.max_q)) || (rc = tmp.alloc(&d2, pl.max_q)) || (rc = tmp.alloc(&rbest, pl.max_r)) || (rc = tmp.alloc(&rd1, pl.max_r)) ||
+        (rc = tmp.alloc(&qoff, pl.max_p + 1)) || (rc = tmp.alloc(&roff, pl.max_p + 1)) || (rc = tmp.alloc(&ncand, pl.max_p)) ||
+        (rc = tmp.alloc(&part, 4 * pl.max_dec)) || (rc = tmp.alloc(&dist, pl.max_q)) || (rc = tmp.alloc(&kp, pl.max_q)) ||
+        (rc = tmp.alloc(&blocks, pl.max_blocks)) || (rc = tmp.alloc(&code, pl.max_q)) || (rc = tmp.alloc(&key, pl.max_q)) ||
+        (rc = tmp.alloc(&scan, pl.max_q)) || (rc = tmp.alloc(&sums, pl.max_sb)) || (rc = tmp.alloc(&total, 1)) || (rc = tmp.alloc(&ptr, pl.max_p + 1)))
+      return rc;
+    return MVBA_OK;
+  }
+};
+
+// rules 2 to 4 as the caller set them
+struct MatchRules {
+  bool use_ratio, mutual;
+  double r2;
+  long long max_dist2;
+};
+
+// One chunk on the device: its lists up, the distances (mark 1 after them), then the tests, the scan and the matches to their
+// places (mark 2).  restart: mark 0 is recorded again first -- not in the first chunk, whose lap holds the norms.
+int match_chunk_run(MatchDev &d, const MatchLists &L, const MatchRules &rules, bool restart, EvLaps &ev) {
+  int rc;
+  if (restart) ev.again(0);
+  const size_t nf = L.fwd.size(), nr = L.rev.size(), P = (size_t)L.P;
+  if (nf + nr > d.max_blocks) return fail(MVBA_ERR_STATE, "mvba_match_descriptors: " + std::to_string(nf + nr) + " blocks for " + std::to_string(d.max_blocks));
+  MVBA_HIP(hipMemcpy(d.blocks, L.fwd.data(), sizeof(MatchBlock) * nf, hipMemcpyHostToDevice));
+  if (nr) MVBA_HIP(hipMemcpy(d.blocks + nf, L.rev.data(), sizeof(MatchBlock) * nr, hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(d.qoff, L.qoff.data(), sizeof(int) * (P + 1), hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(d.roff, L.roff.data(), sizeof(int) * (P + 1), hipMemcpyHostToDevice));
+  MVBA_HIP(hipMemcpy(d.ncand, L.ncand.data(), sizeof(int) * P, hipMemcpyHostToDevice));
+  if ((rc = match_launch_nn<true>((int)nf, d.blocks, d.desc, d.dim, d.norm, d.best, d.d1, d.d2))) return rc;
+  if ((rc = match_launch_nn<false>((int)nr, d.blocks + nf, d.desc, d.dim, d.norm, d.rbest, d.rd1, nullptr))) return rc;
+  ev.mark();
+  const unsigned gq = trk_grid(L.Qc);
+  hipLaunchKernelGGL(k_match_decide, dim3(gq), dim3(256), 0, 0, L.Qc, L.P, d.qoff, d.roff, d.ncand, d.best, d.d1, d.d2, d.rbest, (int)rules.use_ratio,
+                     rules.r2, (int)rules.mutual, rules.max_dist2, d.code, d.key, d.part);
+  tracks_scan(L.Qc, d.key, d.scan, d.sums, d.total);
+  hipLaunchKernelGGL(k_match_emit, dim3(gq), dim3(256), 0, 0, L.Qc, L.P, d.qoff, d.code, d.scan, d.best, d.d1, d.kp, d.dist);
+  hipLaunchKernelGGL(k_match_pair_ptr, dim3(trk_grid((long long)P + 1)), dim3(256), 0, 0, L.Qc, L.P, d.qoff, d.scan, d.total, d.ptr);
+  ev.mark();
+  MVBA_HIP(hipGetLastError());
+  return MVBA_OK;
+}
+
+// the caller's arrays, and how far the chunks so far have filled them: m_base matches, q_base queries
+struct MatchOut {
+  int64_t *match_ptr;
+  int32_t *kp_pairs, *dist2, *nn_best, *nn_dist2, *nn_second2;
+  int64_t *counts;
+  int64_t m_base = 0, q_base = 0;
+};
+
+// A chunk's part of the answer: match_ptr of its pairs (from p0 on) rebased by the matches before it, its matches, the
+// per-query arrays that were asked for, and the workgroups' partial counts added up.
+int match_chunk_read(const MatchDev &d, const MatchLists &L, int32_t p0, MatchOut &out) {
+  static_assert(sizeof(int2) == 2 * sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "kp_pairs and match_ptr travel as they are");
+  const size_t P = (size_t)L.P, Qc = (size_t)L.Qc;
+  std::vector<long long> ptr(P + 1);
+  MVBA_HIP(hipMemcpy(ptr.data(), d.ptr, sizeof(long long) * (P + 1), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i <= P; ++i) out.match_ptr[p0 + i] = out.m_base + ptr[i];
+  const int64_t got = ptr[P];
+  if (got) {
+    MVBA_HIP(hipMemcpy(out.kp_pairs + 2 * out.m_base, d.kp, sizeof(int2) * (size_t)got, hipMemcpyDeviceToHost));
+    MVBA_HIP(hipMemcpy(out.dist2 + out.m_base, d.dist, sizeof(int) * (size_t)got, hipMemcpyDeviceToHost));
+  }
+  if (out.nn_best) MVBA_HIP(hipMemcpy(out.nn_best + out.q_base, d.best, sizeof(int) * Qc, hipMemcpyDeviceToHost));
+  if (out.nn_dist2) MVBA_HIP(hipMemcpy(out.nn_dist2 + out.q_base, d.d1, sizeof(int) * Qc, hipMemcpyDeviceToHost));
+  if (out.nn_second2) MVBA_HIP(hipMemcpy(out.nn_second2 + out.q_base, d.d2, sizeof(int) * Qc, hipMemcpyDeviceToHost));
+  std::vector<int> part(4 * (size_t)trk_grid(L.Qc));
+  MVBA_HIP(hipMemcpy(part.data(), d.part, sizeof(int) * part.size(), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < part.size(); ++i) out.counts[MATCH_C_NO_CANDIDATE + (i & 3)] += part[i];
+  out.m_base += got;
+  out.q_base += L.Qc;
+  return MVBA_OK;
 }
 
 }  // namespace
@@ -274,124 +359,38 @@ int mvba_match_descriptors(int32_t n_images, const int64_t *kp_ptr, const uint8_
   if (Q == 0) return MVBA_OK;
   if (device >= 0) MVBA_HIP(hipSetDevice(device));
   const int n = (int)kp_ptr[n_images];
-  const bool use_ratio = ratio > 0.0, both = mutual != 0;
-  const double r2 = match_ratio2(ratio);
-
-  // ---- the chunks, and the largest of each buffer any of them needs
-  std::vector<int32_t> cut{0};
-  size_t max_q = 0, max_r = 0, max_p = 0;
-  while (cut.back() < n_pairs) {
-    const int32_t p0 = cut.back(), p1 = match_chunk_end(kp_ptr, pairs, n_pairs, p0, both, MATCH_CHUNK_QUERIES);
-    size_t q = 0, r = 0;
-    for (int32_t p = p0; p < p1; ++p) {
-      q += (size_t)(kp_ptr[pairs[2 * p] + 1] - kp_ptr[pairs[2 * p]]);
-      r += (size_t)(kp_ptr[pairs[2 * p + 1] + 1] - kp_ptr[pairs[2 * p + 1]]);
-    }
-    max_q = std::max(max_q, q);
-    max_r = std::max(max_r, both ? r : 0);
-    max_p = std::max(max_p, (size_t)(p1 - p0));
-    cut.push_back(p1);
-  }
-  const size_t max_blocks = (max_q + max_r) / MATCH_TQ + 2 * max_p + 1, max_dec = (max_q + 255) / 256, max_sb = (max_q + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK;
-
-  DevBufs tmp;
-  unsigned char *ddesc = nullptr, *dcode = nullptr;
-  int *dnorm = nullptr, *dbest = nullptr, *dd1 = nullptr, *dd2 = nullptr, *drbest = nullptr, *drd1 = nullptr, *dqoff = nullptr, *droff = nullptr;
-  int *dncand = nullptr, *dpart = nullptr, *ddist = nullptr;
-  int2 *dkp = nullptr;
-  MatchBlock *dblocks = nullptr;
-  trk_u64 *dkey = nullptr, *dscan = nullptr, *dsums = nullptr, *dtotal = nullptr;
-  long long *dptr = nullptr;
-  if ((rc = tmp.alloc(&ddesc, (size_t)n * dim)) || (rc = tmp.alloc(&dnorm, (size_t)n)) || (rc = tmp.alloc(&dbest, max_q)) ||
-      (rc = tmp.alloc(&dd1, max_q)) || (rc = tmp.alloc(&dd2, max_q)) || (rc = tmp.alloc(&drbest, max_r)) || (rc = tmp.alloc(&drd1, max_r)) ||
-      (rc = tmp.alloc(&dqoff, max_p + 1)) || (rc = tmp.alloc(&droff, max_p + 1)) || (rc = tmp.alloc(&dncand, max_p)) ||
-      (rc = tmp.alloc(&dpart, 4 * max_dec)) || (rc = tmp.alloc(&ddist, max_q)) || (rc = tmp.alloc(&dkp, max_q)) ||
-      (rc = tmp.alloc(&dblocks, max_blocks)) || (rc = tmp.alloc(&dcode, max_q)) || (rc = tmp.alloc(&dkey, max_q)) ||
-      (rc = tmp.alloc(&dscan, max_q)) || (rc = tmp.alloc(&dsums, max_sb)) || (rc = tmp.alloc(&dtotal, 1)) || (rc = tmp.alloc(&dptr, max_p + 1)))
-    return rc;
-  MVBA_HIP(hipMemcpy(ddesc, desc, (size_t)n * dim, hipMemcpyHostToDevice));
+  const MatchRules rules{ratio > 0.0, mutual != 0, match_ratio2(ratio), (long long)max_dist2};
+  const MatchPlan plan = match_plan(kp_ptr, pairs, n_pairs, rules.mutual, MATCH_CHUNK_QUERIES);
+  MatchDev d;
+  if ((rc = d.alloc(plan, n, dim))) return rc;
+  MVBA_HIP(hipMemcpy(d.desc, desc, (size_t)n * dim, hipMemcpyHostToDevice));
   if (timings_ms) timings_ms[0] = clk.lap();
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  EvGuard guard{ev, 3};
-  for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
+  EvLaps ev;
+  if ((rc = ev.create(3))) return rc;
   double t_dist = 0.0, t_test = 0.0;
 
-  hipEventRecord(ev[0], 0);
-  hipLaunchKernelGGL(k_match_norm, dim3(trk_grid(n)), dim3(256), 0, 0, n, (int)dim, ddesc, dnorm);
+  ev.mark();
+  hipLaunchKernelGGL(k_match_norm, dim3(trk_grid(n)), dim3(256), 0, 0, n, (int)dim, d.desc, d.norm);
   MVBA_HIP(hipGetLastError());
 
-  std::vector<MatchBlock> fwd, rev;
-  std::vector<int> qoff, roff, ncand, part;
-  std::vector<long long> ptr;
-  int64_t m_base = 0, q_base = 0;
-  static_assert(sizeof(int2) == 2 * sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "kp_pairs and match_ptr travel as they are");
-  for (size_t ch = 0; ch + 1 < cut.size(); ++ch) {
-    const int32_t p0 = cut[ch], p1 = cut[ch + 1], P = p1 - p0;
-    fwd.clear(); rev.clear();
-    qoff.assign((size_t)P + 1, 0); roff.assign((size_t)P + 1, 0); ncand.assign((size_t)P, 0);
-    for (int32_t i = 0; i < P; ++i) {
-      const int k = pairs[2 * (p0 + i)], l = pairs[2 * (p0 + i) + 1];
-      const int nk = (int)(kp_ptr[k + 1] - kp_ptr[k]), nl = (int)(kp_ptr[l + 1] - kp_ptr[l]);
-      match_add_blocks(fwd, kp_ptr, k, l, qoff[i]);
-      if (both) match_add_blocks(rev, kp_ptr, l, k, roff[i]);
-      qoff[i + 1] = qoff[i] + nk;
-      roff[i + 1] = roff[i] + (both ? nl : 0);
-      ncand[i] = nl;
-    }
-    const int Qc = qoff[P];
-    if (Qc == 0) {  // (pairs without queries: nothing to ask)
-      for (int32_t i = 0; i <= P; ++i) match_ptr[p0 + i] = m_base;
+  MatchLists L;
+  MatchOut out{match_ptr, kp_pairs, dist2, nn_best, nn_dist2, nn_second2, counts};
+  for (size_t ch = 0; ch + 1 < plan.cut.size(); ++ch) {
+    const int32_t p0 = plan.cut[ch], p1 = plan.cut[ch + 1];
+    match_chunk_lists(kp_ptr, pairs, p0, p1, rules.mutual, L);
+    if (L.Qc == 0) {  // (pairs without queries: nothing to ask)
+      for (int32_t p = p0; p <= p1; ++p) match_ptr[p] = out.m_base;
       continue;
     }
-    if (ch > 0) hipEventRecord(ev[0], 0);  // (the first chunk's lap holds the norms)
-    // ---- distances: the nearest two forwards, the nearest backwards
-    const size_t nf = fwd.size(), nr = rev.size();
-    if (nf + nr > max_blocks) return fail(MVBA_ERR_STATE, "mvba_match_descriptors: " + std::to_string(nf + nr) + " blocks for " + std::to_string(max_blocks));
-    MVBA_HIP(hipMemcpy(dblocks, fwd.data(), sizeof(MatchBlock) * nf, hipMemcpyHostToDevice));
-    if (nr) MVBA_HIP(hipMemcpy(dblocks + nf, rev.data(), sizeof(MatchBlock) * nr, hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dqoff, qoff.data(), sizeof(int) * ((size_t)P + 1), hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(droff, roff.data(), sizeof(int) * ((size_t)P + 1), hipMemcpyHostToDevice));
-    MVBA_HIP(hipMemcpy(dncand, ncand.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice));
-    if ((rc = match_launch_nn<true>((int)nf, dblocks, ddesc, dim, dnorm, dbest, dd1, dd2))) return rc;
-    if ((rc = match_launch_nn<false>((int)nr, dblocks + nf, ddesc, dim, dnorm, drbest, drd1, nullptr))) return rc;
-    hipEventRecord(ev[1], 0);
-    // ---- the tests, the scan, the matches to their places
-    const unsigned gq = trk_grid(Qc);
-    hipLaunchKernelGGL(k_match_decide, dim3(gq), dim3(256), 0, 0, Qc, (int)P, dqoff, droff, dncand, dbest, dd1, dd2, drbest, (int)use_ratio, r2,
-                       (int)both, (long long)max_dist2, dcode, dkey, dpart);
-    tracks_scan(Qc, dkey, dscan, dsums, dtotal);
-    hipLaunchKernelGGL(k_match_emit, dim3(gq), dim3(256), 0, 0, Qc, (int)P, dqoff, dcode, dscan, dbest, dd1, dkp, ddist);
-    hipLaunchKernelGGL(k_match_pair_ptr, dim3(trk_grid((long long)P + 1)), dim3(256), 0, 0, Qc, (int)P, dqoff, dscan, dtotal, dptr);
-    hipEventRecord(ev[2], 0);
-    MVBA_HIP(hipGetLastError());
-    // ---- this chunk's part of the answer
-    ptr.resize((size_t)P + 1);
-    MVBA_HIP(hipMemcpy(ptr.data(), dptr, sizeof(long long) * ((size_t)P + 1), hipMemcpyDeviceToHost));
-    for (int32_t i = 0; i <= P; ++i) match_ptr[p0 + i] = m_base + ptr[i];
-    const int64_t got = ptr[P];
-    if (got) {
-      MVBA_HIP(hipMemcpy(kp_pairs + 2 * m_base, dkp, sizeof(int2) * (size_t)got, hipMemcpyDeviceToHost));
-      MVBA_HIP(hipMemcpy(dist2 + m_base, ddist, sizeof(int) * (size_t)got, hipMemcpyDeviceToHost));
-    }
-    if (nn_best) MVBA_HIP(hipMemcpy(nn_best + q_base, dbest, sizeof(int) * (size_t)Qc, hipMemcpyDeviceToHost));
-    if (nn_dist2) MVBA_HIP(hipMemcpy(nn_dist2 + q_base, dd1, sizeof(int) * (size_t)Qc, hipMemcpyDeviceToHost));
-    if (nn_second2) MVBA_HIP(hipMemcpy(nn_second2 + q_base, dd2, sizeof(int) * (size_t)Qc, hipMemcpyDeviceToHost));
-    part.resize(4 * (size_t)gq);
-    MVBA_HIP(hipMemcpy(part.data(), dpart, sizeof(int) * part.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < part.size(); ++i) counts[MATCH_C_NO_CANDIDATE + (i & 3)] += part[i];
-    m_base += got;
-    q_base += Qc;
-    float f1 = 0.f, f2 = 0.f;
-    hipEventElapsedTime(&f1, ev[0], ev[1]);
-    hipEventElapsedTime(&f2, ev[1], ev[2]);
-    t_dist += f1;
-    t_test += f2;
+    if ((rc = match_chunk_run(d, L, rules, ch > 0, ev)) || (rc = match_chunk_read(d, L, p0, out))) return rc;
+    t_dist += ev.ms(0, 1);
+    t_test += ev.ms(1, 2);
   }
-  counts[MATCH_C_MATCHES] = m_base;
+  counts[MATCH_C_MATCHES] = out.m_base;
   if (timings_ms) {
     timings_ms[1] = t_dist;
     timings_ms[2] = t_test;
-    timings_ms[3] = std::max(0.0, clk.lap() - t_dist - t_test);
+    timings_ms[3] = lap_rest(clk.lap(), t_dist + t_test);
   }
   return MVBA_OK;
 }

@@ -1,18 +1,30 @@
 // The host logic of mvba_match_descriptors (mvba_match.h), once: its argument checks, the rule that cuts the pair list into
-// chunks, and the two pieces of arithmetic the kernels share with the host -- the squared ratio and the ratio test itself.
-// No HIP call in it: csrc/host_check.cpp runs it under the host sanitizers.
+// chunks, the plan of a call (match_plan: the cuts and the size of every buffer), the block lists and offset tables of a chunk
+// (match_chunk_lists), and the two pieces of arithmetic the kernels share with the host -- the squared ratio and the ratio
+// test itself.  No HIP call in it: csrc/host_check.cpp runs it under the host sanitizers.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "mvba_common.h"
+#include "mvba_tracks_host.h"  // TRK_SCAN_BLOCK: the matches are compacted by the track builder's scan
 
 #if defined(__HIP__)
 #define MATCH_HD __host__ __device__ __forceinline__
 #else
 #define MATCH_HD inline
 #endif
+
+// MATCH_TQ queries [q0, q0 + nq) (node ids) of one directed job against the candidates [c0, c0 + nc); results at out0 + local
+// query.  (In the unnamed namespace of mvba_match.h's kernels: the symbol of k_match_nn carries the name of this type.)
+namespace {
+struct MatchBlock {
+  int q0, nq, c0, nc, out0;
+};
+}  // namespace
 
 namespace mvba {
 
@@ -91,6 +103,63 @@ inline int32_t match_chunk_end(const int64_t *kp_ptr, const int32_t *pairs, int3
     rows += more;
   }
   return p;
+}
+
+// The chunks of a call -- chunk c answers the pairs cut[c] .. cut[c + 1] - 1, the cuts are match_chunk_end's -- and the largest
+// of each buffer any of them needs: max_q queries, max_r reverse rows (0 without `mutual`) and max_p pairs of one chunk; from
+// these the MatchBlocks of both lists together, the workgroups of k_match_decide and the blocks of the scan.  A job of nq
+// queries has ceil(nq / MATCH_TQ) <= nq / MATCH_TQ + 1 blocks and a chunk 2 max_p jobs at most: hence max_blocks.
+struct MatchPlan {
+  std::vector<int32_t> cut{0};
+  size_t max_q = 0, max_r = 0, max_p = 0, max_blocks = 0, max_dec = 0, max_sb = 0;
+};
+
+inline MatchPlan match_plan(const int64_t *kp_ptr, const int32_t *pairs, int32_t n_pairs, bool mutual, int64_t budget) {
+  MatchPlan pl;
+  while (pl.cut.back() < n_pairs) {
+    const int32_t p0 = pl.cut.back(), p1 = match_chunk_end(kp_ptr, pairs, n_pairs, p0, mutual, budget);
+    size_t q = 0, r = 0;
+    for (int32_t p = p0; p < p1; ++p) {
+      q += (size_t)(kp_ptr[pairs[2 * p] + 1] - kp_ptr[pairs[2 * p]]);
+      r += (size_t)(kp_ptr[pairs[2 * p + 1] + 1] - kp_ptr[pairs[2 * p + 1]]);
+    }
+    pl.max_q = std::max(pl.max_q, q);
+    pl.max_r = std::max(pl.max_r, mutual ? r : 0);
+    pl.max_p = std::max(pl.max_p, (size_t)(p1 - p0));
+    pl.cut.push_back(p1);
+  }
+  pl.max_blocks = (pl.max_q + pl.max_r) / MATCH_TQ + 2 * pl.max_p + 1;
+  pl.max_dec = (pl.max_q + 255) / 256;
+  pl.max_sb = (pl.max_q + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK;
+  return pl;
+}
+
+// What the pairs p0 .. p1 - 1 of one chunk ask of the device.  fwd: the blocks of the jobs (query image k, candidate image l)
+// of its pairs (k, l), pair i's results from row qoff[i] on; rev (with `mutual`, else empty and roff all 0): those of (l, k),
+// from row roff[i] on.  qoff, roff [P + 1]; ncand [P]: the candidates of a pair's queries; Qc = qoff[P]: the chunk's queries.
+struct MatchLists {
+  std::vector<MatchBlock> fwd, rev;
+  std::vector<int> qoff, roff, ncand;
+  int P = 0, Qc = 0;
+};
+
+inline void match_chunk_lists(const int64_t *kp_ptr, const int32_t *pairs, int32_t p0, int32_t p1, bool mutual, MatchLists &L) {
+  auto add = [&](std::vector<MatchBlock> &blocks, int q, int c, int out) {  // the blocks of the job (q, c), its results from row `out` on
+    const int q0 = (int)kp_ptr[q], nq = (int)(kp_ptr[q + 1] - kp_ptr[q]), c0 = (int)kp_ptr[c], nc = (int)(kp_ptr[c + 1] - kp_ptr[c]);
+    for (int at = 0; at < nq; at += MATCH_TQ) blocks.push_back(MatchBlock{q0 + at, std::min(MATCH_TQ, nq - at), c0, nc, out + at});
+  };
+  const int P = L.P = p1 - p0;
+  L.fwd.clear(); L.rev.clear();
+  L.qoff.assign((size_t)P + 1, 0); L.roff.assign((size_t)P + 1, 0); L.ncand.assign((size_t)P, 0);
+  for (int i = 0; i < P; ++i) {
+    const int k = pairs[2 * (p0 + i)], l = pairs[2 * (p0 + i) + 1];
+    add(L.fwd, k, l, L.qoff[i]);
+    if (mutual) add(L.rev, l, k, L.roff[i]);
+    L.qoff[i + 1] = L.qoff[i] + (int)(kp_ptr[k + 1] - kp_ptr[k]);
+    L.roff[i + 1] = L.roff[i] + (mutual ? (int)(kp_ptr[l + 1] - kp_ptr[l]) : 0);
+    L.ncand[i] = (int)(kp_ptr[l + 1] - kp_ptr[l]);
+  }
+  L.Qc = L.qoff[P];
 }
 
 }  // namespace mvba

@@ -1,4 +1,4 @@
-// What the entry points that start a reconstruction share (mvba_init.h, mvba_twoview.h, mvba_ransac.h) -- gfx950.
+// What the entry points that start a reconstruction share (mvba_init.h, mvba_twoview.h, mvba_ransac.h ... mvba_match.h) -- gfx950.
 //
 // Included by mvba.hip after its C entry points and before mvba_init.h: uses mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing
 // here runs on the LM path.  
@@ -6,7 +6,7 @@
 // One copy each of: the fixed reduction tree of a 256-thread chunk (chunk_sum; the cyclic Jacobi, its eigenvalue selection and
 // INIT_REL_PIVOT are mvba_ransac_host.h's, which the host-side solves use too), the flags of a chunk counted and ranked
 // (chunk_ballot, chunk_total, chunk_rank: the compactions of mvba_ransac.h and mvba_align.h), the mask step of a robust fit
-// (mask_step), the host clock and event guard, the checks of an observation list, of a pair list and of ascending camera
+// (mask_step), the host clock and the event laps (EvLaps), the checks of an observation list, of a pair list and of ascending camera
 // runs, and the upload of a list.  Every floating-point sum of these entry points is taken in an order that the sizes alone
 // fix: chunk_sum inside a chunk, then k_resect_combine (serial, ascending chunks) or k_twoview_combine (lane-strided, then
 // the shuffle tree) over a camera's or a pair's chunks -- two orders, on purpose.
@@ -81,13 +81,32 @@ struct InitClock {
   }
 };
 
-// events of one call: whatever was created is destroyed when the owner goes
-struct EvGuard {
-  hipEvent_t *e;
-  int n;
-  ~EvGuard() {
-    for (int i = 0; i < n; ++i)
-      if (e[i]) hipEventDestroy(e[i]);
+// The event laps of one call.  create(count) makes the events; whatever was made is destroyed when the owner goes, on every
+// return.  mark(stream) records the next event -- nothing without events, so a caller that times only on request creates them
+// only then; again(k) records event k once more and goes on from there (marks taken once per chunk).  ms(a, b): the
+// milliseconds from mark a to mark b, to be read only after a copy or a hipStreamSynchronize that follows mark b.  What a call
+// reports beside its laps is the call's own rule (most of them: lap_rest of the wall time).
+struct EvLaps {
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  int n = 0, next = 0;
+  EvLaps() = default;
+  EvLaps(const EvLaps &) = delete;
+  EvLaps &operator=(const EvLaps &) = delete;
+  ~EvLaps() {
+    for (int i = 0; i < n; ++i) hipEventDestroy(e[i]);
+  }
+  int create(int count) {
+    for (; n < count && n < 4; ++n) MVBA_HIP(hipEventCreate(&e[n]));
+    return MVBA_OK;
+  }
+  void mark(hipStream_t stream = 0) {
+    if (next < n) hipEventRecord(e[next++], stream);
+  }
+  void again(int k) { next = k, mark(); }
+  double ms(int a, int b) const {
+    float f = 0.f;
+    if (a < n && b < n) hipEventElapsedTime(&f, e[a], e[b]);
+    return f;
   }
 };
 

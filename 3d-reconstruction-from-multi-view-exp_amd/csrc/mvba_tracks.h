@@ -1,7 +1,11 @@
 // Feature tracks from pairwise matches (mvba_build_tracks) -- kernels and host code, gfx950.
 //
-// Included by mvba.hip after mvba_start.h: uses its InitClock and EvGuard, mvba.hip's DevBufs, fail and MVBA_HIP, and
-// mvba_tracks_host.h's checks and tracks_classify.  Nothing here runs on the LM path.  
+// Included by mvba.hip after mvba_start.h: uses its InitClock and EvLaps, mvba.hip's DevBufs, fail and MVBA_HIP, and
+// mvba_tracks_host.h's checks, tracks_classify, trk_grid and TRK_SCAN_BLOCK.  mvba_match.h uses tracks_scan and trk_u64 of
+// this header.  Nothing here runs on the LM path.  
+//
+// The host side in stages over one TracksDev, which owns the device buffers: tracks_upload, tracks_labels, tracks_candidates,
+// tracks_survivors, tracks_download; the entry point is the checks, the five calls and the laps.
 //
 // Keypoint j of image i is node kp_ptr[i] + j; a match is an edge between two nodes; a track is a connected component of that
 // graph with at most one node per image.  Integers only, and integer atomics only (atomicMin, atomicAdd, atomicOr): every
@@ -29,8 +33,6 @@ namespace {
 typedef unsigned long long trk_u64;
 
 constexpr int TRK_LANE_MAX = 32;            // entries up to which one lane ranks a whole track
-constexpr int TRK_SCAN_ITEMS = 4;           // consecutive items per thread of k_tracks_scan_blocks
-constexpr int TRK_SCAN_BLOCK = 256 * TRK_SCAN_ITEMS;
 constexpr int TRK_HOOK_GRID = 8192;         // workgroups of the hook kernel at most (a grid stride beyond)
 
 // the root of v's tree: strictly descending, since parent[x] <= x whatever this thread gets to see of other threads' writes
@@ -277,14 +279,148 @@ __global__ __launch_bounds__(256) void k_tracks_out_nodes(int n, const int *__re
   if (threadIdx.x < TRK_N_COUNTS && s_c[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], s_c[threadIdx.x]);
 }
 
-inline unsigned trk_grid(long long n) { return (unsigned)std::max<long long>(1, (n + 255) / 256); }
-
 // the three launches of an exclusive scan of key [n] into out [n]; *total (device) = the sum of all of it
 void tracks_scan(int n, const trk_u64 *key, trk_u64 *out, trk_u64 *sums, trk_u64 *total) {
   const int nb = (int)(((long long)n + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK);
   hipLaunchKernelGGL(k_tracks_scan_blocks, dim3(nb), dim3(256), 0, 0, n, key, out, sums);
   hipLaunchKernelGGL(k_tracks_scan_sums, dim3(1), dim3(256), 0, 0, nb, sums, total);
   hipLaunchKernelGGL(k_tracks_scan_add, dim3(trk_grid(n)), dim3(256), 0, 0, n, out, sums);
+}
+
+// The device buffers of a call and the sizes the stages hand on; freed when the owner goes.
+struct TracksDev {
+  DevBufs tmp;
+  int n = 0, n_images = 0, min_length = 0;  // nodes, images, the shortest track
+  long long n_edges = 0;
+  int n_cand = 0, n_ent = 0, n_tracks = 0, n_obs = 0;  // candidates and their nodes (tracks_candidates); survivors and theirs (tracks_survivors)
+  // tracks_upload; edge and ok [n_edges] are released once the labels stand
+  int2 *edge = nullptr;
+  unsigned char *ok = nullptr;
+  int *kp = nullptr, *parent = nullptr;  // [n_images + 1]; [n]: the labels once they have settled
+  unsigned *changed = nullptr;
+  double2 *kpxy = nullptr;
+  // tracks_candidates: [n] each, then cand [n_cand] and seg, sorted, cam [n_ent]
+  int *size = nullptr, *cursor = nullptr, *track = nullptr, *cand = nullptr, *sorted = nullptr, *cam = nullptr;
+  int *seg = nullptr;  // the unsorted segments; once k_tracks_sort has read them, the cam_idx of the output (n_obs <= n_ent)
+  unsigned char *bad = nullptr;
+  trk_u64 *key = nullptr, *scan1 = nullptr, *scan2 = nullptr, *sums = nullptr, *total = nullptr, *cnt = nullptr;
+  // tracks_survivors: ptr [n_tracks + 1], obs and xy [n_obs]
+  long long *ptr = nullptr;
+  int *obs = nullptr;
+  double2 *xy = nullptr;
+};
+
+// the offsets (as int), the edges, their flags and the positions to the device
+int tracks_upload(TracksDev &d, const int64_t *kp_ptr, const double *kp_xy, const int32_t *edges, const uint8_t *edge_ok, bool want_xy) {
+  static_assert(sizeof(int2) == 2 * sizeof(int32_t), "edges travel as they are");
+  int rc;
+  const size_t ne = (size_t)d.n_edges;
+  if ((rc = d.tmp.alloc(&d.edge, ne)) || (rc = d.tmp.alloc(&d.kp, (size_t)d.n_images + 1)) || (rc = d.tmp.alloc(&d.parent, (size_t)d.n)) ||
+      (rc = d.tmp.alloc(&d.changed, 1)))
+    return rc;
+  if (edge_ok && (rc = d.tmp.alloc(&d.ok, ne))) return rc;
+  if (want_xy && (rc = d.tmp.alloc(&d.kpxy, (size_t)d.n))) return rc;
+  std::vector<int> kp32((size_t)d.n_images + 1);
+  for (int32_t i = 0; i <= d.n_images; ++i) kp32[i] = (int)kp_ptr[i];
+  MVBA_HIP(hipMemcpy(d.kp, kp32.data(), sizeof(int) * kp32.size(), hipMemcpyHostToDevice));
+  if (ne) MVBA_HIP(hipMemcpy(d.edge, edges, sizeof(int2) * ne, hipMemcpyHostToDevice));
+  if (d.ok && ne) MVBA_HIP(hipMemcpy(d.ok, edge_ok, ne, hipMemcpyHostToDevice));
+  if (d.kpxy) MVBA_HIP(hipMemcpy(d.kpxy, kp_xy, sizeof(double2) * (size_t)d.n, hipMemcpyHostToDevice));
+  return MVBA_OK;
+}
+
+// hook and flatten until a round changes nothing: d.parent is then every node's label.  *rounds: how many it took.
+int tracks_labels(TracksDev &d, int64_t *rounds) {
+  const int n = d.n;
+  hipLaunchKernelGGL(k_tracks_init, dim3(trk_grid(n)), dim3(256), 0, 0, n, d.parent);
+  *rounds = 0;
+  const unsigned hook_grid = (unsigned)std::min<long long>(TRK_HOOK_GRID, trk_grid(d.n_edges));
+  for (unsigned changed = d.n_edges > 0; changed;) {
+    if (*rounds > n)  // (every changing round costs a root: the loop cannot get here)
+      return fail(MVBA_ERR_STATE, "mvba_build_tracks: the labels did not settle in n_nodes + 1 = " + std::to_string((int64_t)n + 1) + " rounds");
+    MVBA_HIP(hipMemsetAsync(d.changed, 0, sizeof(unsigned), 0));
+    hipLaunchKernelGGL(k_tracks_hook, dim3(hook_grid), dim3(256), 0, 0, d.n_edges, d.edge, d.ok, d.parent, d.changed);
+    hipLaunchKernelGGL(k_tracks_flatten, dim3(trk_grid(n)), dim3(256), 0, 0, n, d.parent);
+    MVBA_HIP(hipGetLastError());
+    MVBA_HIP(hipMemcpy(&changed, d.changed, sizeof(unsigned), hipMemcpyDeviceToHost));
+    ++*rounds;
+  }
+  return MVBA_OK;
+}
+
+// Sizes, the candidates and their segments, sorted, and the conflicts marked.  The edges and their flags go first -- the
+// labels hold all they said -- so that they and the buffers of the layout are never there together.
+int tracks_candidates(TracksDev &d) {
+  int rc;
+  const int n = d.n;
+  const size_t nn = (size_t)n, nb = (nn + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK;
+  d.tmp.release(d.edge);
+  d.tmp.release(d.ok);
+  if ((rc = d.tmp.alloc(&d.size, nn)) || (rc = d.tmp.alloc(&d.cursor, nn)) || (rc = d.tmp.alloc(&d.bad, nn)) || (rc = d.tmp.alloc(&d.key, nn)) ||
+      (rc = d.tmp.alloc(&d.scan1, nn)) || (rc = d.tmp.alloc(&d.scan2, nn)) || (rc = d.tmp.alloc(&d.sums, nb)) || (rc = d.tmp.alloc(&d.total, 2)) ||
+      (rc = d.tmp.alloc(&d.cnt, TRK_N_COUNTS)) || (rc = d.tmp.alloc(&d.track, nn)))
+    return rc;
+  MVBA_HIP(hipMemsetAsync(d.size, 0, sizeof(int) * nn, 0));
+  MVBA_HIP(hipMemsetAsync(d.cursor, 0, sizeof(int) * nn, 0));
+  MVBA_HIP(hipMemsetAsync(d.bad, 0, nn, 0));
+  MVBA_HIP(hipMemsetAsync(d.cnt, 0, sizeof(trk_u64) * TRK_N_COUNTS, 0));
+  const int *label = d.parent;
+  hipLaunchKernelGGL(k_tracks_sizes, dim3(trk_grid(n)), dim3(256), 0, 0, n, label, d.size);
+  hipLaunchKernelGGL(k_tracks_keys, dim3(trk_grid(n)), dim3(256), 0, 0, n, label, d.size, (const unsigned char *)nullptr, d.min_length, d.n_images, d.key);
+  tracks_scan(n, d.key, d.scan1, d.sums, d.total);
+  MVBA_HIP(hipGetLastError());
+  trk_u64 total = 0;
+  MVBA_HIP(hipMemcpy(&total, d.total, sizeof(trk_u64), hipMemcpyDeviceToHost));
+  d.n_cand = (int)(total >> 32);
+  d.n_ent = (int)(unsigned)total;
+  if (!d.n_cand) return MVBA_OK;
+  if ((rc = d.tmp.alloc(&d.cand, (size_t)d.n_cand)) || (rc = d.tmp.alloc(&d.seg, (size_t)d.n_ent)) || (rc = d.tmp.alloc(&d.sorted, (size_t)d.n_ent)) ||
+      (rc = d.tmp.alloc(&d.cam, (size_t)d.n_ent)))
+    return rc;
+  hipLaunchKernelGGL(k_tracks_cands, dim3(trk_grid(n)), dim3(256), 0, 0, n, d.key, d.scan1, d.cand);
+  hipLaunchKernelGGL(k_tracks_fill, dim3(trk_grid(n)), dim3(256), 0, 0, n, label, d.key, d.scan1, d.cursor, d.seg);
+  hipLaunchKernelGGL(k_tracks_sort, dim3(trk_grid(d.n_cand)), dim3(256), 0, 0, d.n_cand, d.cand, d.scan1, d.size, d.seg, d.kp, d.n_images, d.sorted, d.cam);
+  hipLaunchKernelGGL(k_tracks_conflict, dim3(trk_grid(d.n_ent)), dim3(256), 0, 0, d.n_ent, d.sorted, d.cam, label, d.bad);
+  return MVBA_OK;
+}
+
+// the survivors numbered (the second scan) and placed: their observations, and every node's track
+int tracks_survivors(TracksDev &d, bool want_xy) {
+  int rc;
+  const int n = d.n;
+  const int *label = d.parent;
+  hipLaunchKernelGGL(k_tracks_keys, dim3(trk_grid(n)), dim3(256), 0, 0, n, label, d.size, d.bad, d.min_length, d.n_images, d.key);
+  tracks_scan(n, d.key, d.scan2, d.sums, d.total + 1);
+  MVBA_HIP(hipGetLastError());
+  trk_u64 total = 0;
+  MVBA_HIP(hipMemcpy(&total, d.total + 1, sizeof(trk_u64), hipMemcpyDeviceToHost));
+  d.n_tracks = (int)(total >> 32);
+  d.n_obs = (int)(unsigned)total;
+  if ((rc = d.tmp.alloc(&d.ptr, (size_t)d.n_tracks + 1)) || (rc = d.tmp.alloc(&d.obs, (size_t)d.n_obs))) return rc;
+  if (want_xy && (rc = d.tmp.alloc(&d.xy, (size_t)d.n_obs))) return rc;
+  if (d.n_obs)  // (cam_idx into d.seg: the unsorted segments have been read for the last time)
+    hipLaunchKernelGGL(k_tracks_out_obs, dim3(trk_grid(d.n_ent)), dim3(256), 0, 0, d.n_ent, d.sorted, d.cam, label, d.bad, d.scan1, d.scan2, d.kpxy, d.obs,
+                       d.seg, d.xy);
+  hipLaunchKernelGGL(k_tracks_out_nodes, dim3(trk_grid(n)), dim3(256), 0, 0, n, label, d.size, d.bad, d.scan2, d.min_length, d.n_images, d.track, d.ptr, d.cnt);
+  return MVBA_OK;
+}
+
+// the answer to the caller's arrays; counts [TRK_N_COUNTS] but for the rounds
+int tracks_download(const TracksDev &d, int64_t *pt_ptr, int32_t *cam_idx, int32_t *obs_node, double *xy, int32_t *node_track, int64_t *counts) {
+  static_assert(sizeof(trk_u64) == sizeof(int64_t) && sizeof(long long) == sizeof(int64_t), "the counters and pt_ptr come back as they are");
+  const size_t n_obs = (size_t)d.n_obs;
+  MVBA_HIP(hipMemcpy(counts, d.cnt, sizeof(int64_t) * TRK_N_COUNTS, hipMemcpyDeviceToHost));
+  counts[TRK_C_TRACKS] = d.n_tracks;
+  counts[TRK_C_OBS] = d.n_obs;
+  MVBA_HIP(hipMemcpy(node_track, d.track, sizeof(int) * (size_t)d.n, hipMemcpyDeviceToHost));
+  if (d.n_tracks) MVBA_HIP(hipMemcpy(pt_ptr, d.ptr, sizeof(int64_t) * (size_t)d.n_tracks, hipMemcpyDeviceToHost));
+  pt_ptr[d.n_tracks] = d.n_obs;
+  if (n_obs) {
+    MVBA_HIP(hipMemcpy(obs_node, d.obs, sizeof(int) * n_obs, hipMemcpyDeviceToHost));
+    MVBA_HIP(hipMemcpy(cam_idx, d.seg, sizeof(int) * n_obs, hipMemcpyDeviceToHost));
+    if (xy) MVBA_HIP(hipMemcpy(xy, d.xy, sizeof(double2) * n_obs, hipMemcpyDeviceToHost));
+  }
+  return MVBA_OK;
 }
 
 }  // namespace
@@ -300,120 +436,27 @@ int mvba_build_tracks(int32_t n_images, const int64_t *kp_ptr, const double *kp_
   for (int i = 0; i < TRK_N_COUNTS; ++i) counts[i] = 0;
   if (timings_ms) timings_ms[0] = timings_ms[1] = timings_ms[2] = timings_ms[3] = 0.0;
   pt_ptr[0] = 0;
-  const int n = (int)kp_ptr[n_images];
-  if (n == 0) return MVBA_OK;
+  if (kp_ptr[n_images] == 0) return MVBA_OK;
   if (device >= 0) MVBA_HIP(hipSetDevice(device));
-  DevBufs tmp;
-  static_assert(sizeof(int2) == 2 * sizeof(int32_t) && sizeof(long long) == sizeof(int64_t), "edges and pt_ptr travel as they are");
-  int2 *dedge = nullptr;
-  unsigned char *dok = nullptr, *dbad = nullptr;
-  int *dkp = nullptr, *dparent = nullptr, *dsize = nullptr, *dcursor = nullptr, *dseg = nullptr, *dsorted = nullptr, *dcam = nullptr;
-  int *dcand = nullptr, *dobs = nullptr, *dtrack = nullptr;
-  unsigned *dchanged = nullptr;
-  trk_u64 *dkey = nullptr, *dscan1 = nullptr, *dscan2 = nullptr, *dsums = nullptr, *dtotal = nullptr, *dcnt = nullptr;
-  double2 *dkpxy = nullptr, *dxy = nullptr;
-  long long *dptr = nullptr;
-  const size_t nn = (size_t)n, nb = (nn + TRK_SCAN_BLOCK - 1) / TRK_SCAN_BLOCK;
-  if ((rc = tmp.alloc(&dedge, (size_t)n_edges)) || (rc = tmp.alloc(&dkp, (size_t)n_images + 1)) || (rc = tmp.alloc(&dparent, nn)) ||
-      (rc = tmp.alloc(&dchanged, 1)))
-    return rc;
-  if (edge_ok && (rc = tmp.alloc(&dok, (size_t)n_edges))) return rc;
-  if (xy && (rc = tmp.alloc(&dkpxy, nn))) return rc;
-  {
-    std::vector<int> kp32((size_t)n_images + 1);
-    for (int32_t i = 0; i <= n_images; ++i) kp32[i] = (int)kp_ptr[i];
-    MVBA_HIP(hipMemcpy(dkp, kp32.data(), sizeof(int) * kp32.size(), hipMemcpyHostToDevice));
-  }
-  if (n_edges) MVBA_HIP(hipMemcpy(dedge, edges, sizeof(int2) * (size_t)n_edges, hipMemcpyHostToDevice));
-  if (dok && n_edges) MVBA_HIP(hipMemcpy(dok, edge_ok, (size_t)n_edges, hipMemcpyHostToDevice));
-  if (dkpxy) MVBA_HIP(hipMemcpy(dkpxy, kp_xy, sizeof(double2) * nn, hipMemcpyHostToDevice));
+  TracksDev d;
+  d.n = (int)kp_ptr[n_images]; d.n_images = n_images; d.min_length = min_length; d.n_edges = n_edges;
+  if ((rc = tracks_upload(d, kp_ptr, kp_xy, edges, edge_ok, xy != nullptr))) return rc;
   if (timings_ms) timings_ms[0] = clk.lap();
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  EvGuard guard{ev, 3};
-  for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
-
-  // ---- labels
-  hipEventRecord(ev[0], 0);
-  hipLaunchKernelGGL(k_tracks_init, dim3(trk_grid(n)), dim3(256), 0, 0, n, dparent);
+  EvLaps ev;
+  if ((rc = ev.create(3))) return rc;
   int64_t rounds = 0;
-  const unsigned hook_grid = (unsigned)std::min<long long>(TRK_HOOK_GRID, trk_grid(n_edges));
-  for (unsigned changed = n_edges > 0; changed;) {
-    if (rounds > n)  // (every changing round costs a root: the loop cannot get here)
-      return fail(MVBA_ERR_STATE, "mvba_build_tracks: the labels did not settle in n_nodes + 1 = " + std::to_string((int64_t)n + 1) + " rounds");
-    MVBA_HIP(hipMemsetAsync(dchanged, 0, sizeof(unsigned), 0));
-    hipLaunchKernelGGL(k_tracks_hook, dim3(hook_grid), dim3(256), 0, 0, (long long)n_edges, dedge, dok, dparent, dchanged);
-    hipLaunchKernelGGL(k_tracks_flatten, dim3(trk_grid(n)), dim3(256), 0, 0, n, dparent);
-    MVBA_HIP(hipGetLastError());
-    MVBA_HIP(hipMemcpy(&changed, dchanged, sizeof(unsigned), hipMemcpyDeviceToHost));
-    ++rounds;
-  }
-  hipEventRecord(ev[1], 0);
-  tmp.release(dedge);
-  tmp.release(dok);
-
-  // ---- sizes, candidates and their segments
-  if ((rc = tmp.alloc(&dsize, nn)) || (rc = tmp.alloc(&dcursor, nn)) || (rc = tmp.alloc(&dbad, nn)) || (rc = tmp.alloc(&dkey, nn)) ||
-      (rc = tmp.alloc(&dscan1, nn)) || (rc = tmp.alloc(&dscan2, nn)) || (rc = tmp.alloc(&dsums, nb)) || (rc = tmp.alloc(&dtotal, 2)) ||
-      (rc = tmp.alloc(&dcnt, TRK_N_COUNTS)) || (rc = tmp.alloc(&dtrack, nn)))
-    return rc;
-  MVBA_HIP(hipMemsetAsync(dsize, 0, sizeof(int) * nn, 0));
-  MVBA_HIP(hipMemsetAsync(dcursor, 0, sizeof(int) * nn, 0));
-  MVBA_HIP(hipMemsetAsync(dbad, 0, nn, 0));
-  MVBA_HIP(hipMemsetAsync(dcnt, 0, sizeof(trk_u64) * TRK_N_COUNTS, 0));
-  const int *dlabel = dparent;
-  hipLaunchKernelGGL(k_tracks_sizes, dim3(trk_grid(n)), dim3(256), 0, 0, n, dlabel, dsize);
-  hipLaunchKernelGGL(k_tracks_keys, dim3(trk_grid(n)), dim3(256), 0, 0, n, dlabel, dsize, (const unsigned char *)nullptr, min_length, n_images, dkey);
-  tracks_scan(n, dkey, dscan1, dsums, dtotal);
+  ev.mark();
+  if ((rc = tracks_labels(d, &rounds))) return rc;
+  ev.mark();
+  if ((rc = tracks_candidates(d)) || (rc = tracks_survivors(d, xy != nullptr))) return rc;
+  ev.mark();
   MVBA_HIP(hipGetLastError());
-  trk_u64 total[2] = {0, 0};
-  MVBA_HIP(hipMemcpy(total, dtotal, sizeof(trk_u64), hipMemcpyDeviceToHost));
-  const int n_cand = (int)(total[0] >> 32), n_ent = (int)(unsigned)total[0];
-  if (n_cand) {
-    if ((rc = tmp.alloc(&dcand, (size_t)n_cand)) || (rc = tmp.alloc(&dseg, (size_t)n_ent)) || (rc = tmp.alloc(&dsorted, (size_t)n_ent)) ||
-        (rc = tmp.alloc(&dcam, (size_t)n_ent)))
-      return rc;
-    hipLaunchKernelGGL(k_tracks_cands, dim3(trk_grid(n)), dim3(256), 0, 0, n, dkey, dscan1, dcand);
-    hipLaunchKernelGGL(k_tracks_fill, dim3(trk_grid(n)), dim3(256), 0, 0, n, dlabel, dkey, dscan1, dcursor, dseg);
-    hipLaunchKernelGGL(k_tracks_sort, dim3(trk_grid(n_cand)), dim3(256), 0, 0, n_cand, dcand, dscan1, dsize, dseg, dkp, n_images, dsorted, dcam);
-    hipLaunchKernelGGL(k_tracks_conflict, dim3(trk_grid(n_ent)), dim3(256), 0, 0, n_ent, dsorted, dcam, dlabel, dbad);
-  }
-  // ---- the survivors, numbered and placed
-  hipLaunchKernelGGL(k_tracks_keys, dim3(trk_grid(n)), dim3(256), 0, 0, n, dlabel, dsize, dbad, min_length, n_images, dkey);
-  tracks_scan(n, dkey, dscan2, dsums, dtotal + 1);
-  MVBA_HIP(hipGetLastError());
-  MVBA_HIP(hipMemcpy(total + 1, dtotal + 1, sizeof(trk_u64), hipMemcpyDeviceToHost));
-  const int n_tracks = (int)(total[1] >> 32), n_obs = (int)(unsigned)total[1];
-  if ((rc = tmp.alloc(&dptr, (size_t)n_tracks + 1)) || (rc = tmp.alloc(&dobs, (size_t)n_obs))) return rc;
-  if (xy && (rc = tmp.alloc(&dxy, (size_t)n_obs))) return rc;
-  int *dcamout = dseg;  // (the unsorted segments have been read for the last time: n_obs <= n_ent)
-  if (n_obs)
-    hipLaunchKernelGGL(k_tracks_out_obs, dim3(trk_grid(n_ent)), dim3(256), 0, 0, n_ent, dsorted, dcam, dlabel, dbad, dscan1, dscan2, dkpxy, dobs,
-                       dcamout, dxy);
-  hipLaunchKernelGGL(k_tracks_out_nodes, dim3(trk_grid(n)), dim3(256), 0, 0, n, dlabel, dsize, dbad, dscan2, min_length, n_images, dtrack, dptr, dcnt);
-  hipEventRecord(ev[2], 0);
-  MVBA_HIP(hipGetLastError());
-
-  // ---- download
-  static_assert(sizeof(trk_u64) == sizeof(int64_t), "the counters come back as they are");
-  MVBA_HIP(hipMemcpy(counts, dcnt, sizeof(int64_t) * TRK_N_COUNTS, hipMemcpyDeviceToHost));
-  counts[TRK_C_TRACKS] = n_tracks;
-  counts[TRK_C_OBS] = n_obs;
+  if ((rc = tracks_download(d, pt_ptr, cam_idx, obs_node, xy, node_track, counts))) return rc;
   counts[TRK_C_ROUNDS] = rounds;
-  MVBA_HIP(hipMemcpy(node_track, dtrack, sizeof(int) * nn, hipMemcpyDeviceToHost));
-  if (n_tracks) MVBA_HIP(hipMemcpy(pt_ptr, dptr, sizeof(int64_t) * (size_t)n_tracks, hipMemcpyDeviceToHost));
-  pt_ptr[n_tracks] = n_obs;
-  if (n_obs) {
-    MVBA_HIP(hipMemcpy(obs_node, dobs, sizeof(int) * (size_t)n_obs, hipMemcpyDeviceToHost));
-    MVBA_HIP(hipMemcpy(cam_idx, dcamout, sizeof(int) * (size_t)n_obs, hipMemcpyDeviceToHost));
-    if (xy) MVBA_HIP(hipMemcpy(xy, dxy, sizeof(double2) * (size_t)n_obs, hipMemcpyDeviceToHost));
-  }
   if (timings_ms) {
-    float f1 = 0.f, f2 = 0.f;
-    hipEventElapsedTime(&f1, ev[0], ev[1]);
-    hipEventElapsedTime(&f2, ev[1], ev[2]);
-    timings_ms[1] = f1;
-    timings_ms[2] = f2;
-    timings_ms[3] = std::max(0.0, clk.lap() - (double)f1 - (double)f2);
+    timings_ms[1] = ev.ms(0, 1);
+    timings_ms[2] = ev.ms(1, 2);
+    timings_ms[3] = lap_rest(clk.lap(), timings_ms[1] + timings_ms[2]);
   }
   return MVBA_OK;
 }

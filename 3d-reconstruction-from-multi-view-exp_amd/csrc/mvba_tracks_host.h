@@ -1,7 +1,9 @@
 // The host logic of mvba_build_tracks (mvba_tracks.h), once: its argument checks, the check of the keypoint offsets and of the
-// edge ids, and the rule that classifies a component of the match graph by its size -- the one function the kernels use too.
-// No HIP call in it: csrc/host_check.cpp runs it under the host sanitizers.
+// edge ids, the rule that classifies a component of the match graph by its size -- the one function the kernels use too --
+// and the two sizes its launches share with the matcher's (mvba_match_host.h): the grid of a one-thread-per-item kernel and
+// the block of the scan.  No HIP call in it: csrc/host_check.cpp runs it under the host sanitizers.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
 
@@ -22,6 +24,12 @@ enum {
 };
 // node_track below 0
 enum { TRK_UNMATCHED = -1, TRK_TOO_SHORT = -2, TRK_DROPPED = -3 };
+
+constexpr int TRK_SCAN_ITEMS = 4;           // consecutive items per thread of k_tracks_scan_blocks
+constexpr int TRK_SCAN_BLOCK = 256 * TRK_SCAN_ITEMS;
+
+// the workgroups of 256 threads for n items, one at least (a kernel of these headers with nothing to do still starts)
+inline unsigned trk_grid(long long n) { return (unsigned)std::max<long long>(1, (n + 255) / 256); }
 
 // A component of `size` nodes (>= 1).  Singleton: no match at all.  Short: fewer nodes than a track must have.  Oversize: more
 // nodes than images, so two of them lie in one image whatever they are -- dropped without being laid out.  Candidate: laid

@@ -2,7 +2,7 @@
 // gfx950.
 //
 // Included by mvba.hip after mvba_resect_ransac.h: uses its rr_inlier, mvba_ransac.h's rs_sample, mvba_ransac_host.h's argument checks, mvba_init.h's
-// init_camera_matrix, InitObsMasked and init_triangulate_point, mvba_start.h's checks, upload_list, InitClock, EvGuard and
+// init_camera_matrix, InitObsMasked and init_triangulate_point, mvba_start.h's checks, upload_list, InitClock, EvLaps and
 // INIT_REL_PIVOT, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on the LM path.  
 //
 // k_tri_score: a GROUP OF 16 LANES PER POINT, four points per wave.  A hypothesis is two of the point's observations; its
@@ -262,32 +262,28 @@ int mvba_triangulate_robust(const double *K, const double *R, const double *t, i
   const int lds = (int)(sizeof(double) * 12 * m);
   MVBA_HIP(hipFuncSetAttribute((const void *)k_tri_score, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   MVBA_HIP(hipFuncSetAttribute((const void *)k_tri_refit, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  EvGuard guard{ev, 3};
-  for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
+  EvLaps ev;
+  if ((rc = ev.create(3))) return rc;
   if (timings_ms) timings_ms[0] = clk.lap();
 
   // both grids stop at 2048 workgroups and stride from there, as k_triangulate's does
   const int g_score = (int)std::max<long long>(1, std::min<long long>(2048, (n_points + 256 / TR_GROUP - 1) / (256 / TR_GROUP)));
   const int g_refit = (int)std::max<long long>(1, std::min<long long>(2048, (n_points + 255) / 256));
   const double thr2 = threshold * threshold;
-  hipEventRecord(ev[0], 0);
+  ev.mark();
   hipLaunchKernelGGL(k_tri_score, dim3(g_score), dim3(256), lds, 0, (long long)n_points, m, dK, dR, dt, dptr, dcam, dxy, thr2, H,
                      (unsigned long long)seed, dX, dst, dni, dbest, dinl, dhc);
-  hipEventRecord(ev[1], 0);
+  ev.mark();
   hipLaunchKernelGGL(k_tri_refit, dim3(g_refit), dim3(256), lds, 0, (long long)n_points, m, dK, dR, dt, dptr, dcam, dxy, thr2, n_refine, n_refit,
                      dX, dq, dst, dni, dinl);
-  hipEventRecord(ev[2], 0);
+  ev.mark();
   MVBA_HIP(hipGetLastError());
   MVBA_HIP(hipStreamSynchronize(0));
   if (timings_ms) {
-    float f1 = 0.f, f2 = 0.f;
-    hipEventElapsedTime(&f1, ev[0], ev[1]);
-    hipEventElapsedTime(&f2, ev[1], ev[2]);
-    timings_ms[1] = f1;
-    timings_ms[2] = f2;
+    timings_ms[1] = ev.ms(0, 1);
+    timings_ms[2] = ev.ms(1, 2);
   }
-  clk.lap();
+  clk.lap();  // (slot 3 is the download alone, not the rest of the wall time)
   MVBA_HIP(hipMemcpy(X, dX, sizeof(double) * 3 * n_points, hipMemcpyDeviceToHost));
   if (quality) MVBA_HIP(hipMemcpy(quality, dq, sizeof(double) * 3 * n_points, hipMemcpyDeviceToHost));
   if (status) MVBA_HIP(hipMemcpy(status, dst, sizeof(int) * n_points, hipMemcpyDeviceToHost));

@@ -1,7 +1,7 @@
 // Starting a reconstruction from two views (mvba_covisibility, mvba_two_view) -- kernels and host code, gfx950.
 //
 // Included by mvba.hip after mvba_start.h and mvba_init.h: uses mvba_start.h's sym_eig_jacobi, eig_extremes, chunk_sum, the
-// list and pair checks, upload_list, InitClock and EvGuard, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on
+// list and pair checks, upload_list, InitClock and EvLaps, and mvba.hip's DevBufs, fail and MVBA_HIP.  Nothing here runs on
 // the LM path.  
 //
 // Co-visibility: ONE THREAD PER POINT walks the pairs of its own camera run (deg^2 / 2 increments) into an m x m table of
@@ -331,25 +331,22 @@ int mvba_covisibility(int64_t n_points, int32_t n_images, const int64_t *pt_ptr,
   MVBA_HIP(hipMemset(dcount, 0, sizeof(unsigned long long) * mm));
   if ((rc = upload_list(tmp, n_points, n_obs, pt_ptr, cam_idx, nullptr, &dptr, &dcam, nullptr))) return rc;
   if (timings_ms) timings_ms[0] = clk.lap();
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  EvGuard guard{ev, 2};
-  for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
+  EvLaps ev;
+  if ((rc = ev.create(2))) return rc;
   const int use_lds = m <= CV_LDS_CAMERAS;
   const int lds = use_lds ? (int)(sizeof(unsigned int) * mm) : 0;
   MVBA_HIP(hipFuncSetAttribute((const void *)k_covisibility, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   const int grid = (int)std::max<long long>(1, std::min<long long>(2048, (n_points + 255) / 256));
-  hipEventRecord(ev[0], 0);
+  ev.mark();
   hipLaunchKernelGGL(k_covisibility, dim3(grid), dim3(256), lds, 0, (long long)n_points, m, dptr, dcam, dcount, use_lds);
-  hipEventRecord(ev[1], 0);
+  ev.mark();
   MVBA_HIP(hipGetLastError());
   MVBA_HIP(hipMemcpy(count, dcount, sizeof(int64_t) * mm, hipMemcpyDeviceToHost));
   for (int k = 0; k < m; ++k)
     for (int l = k + 1; l < m; ++l) count[(size_t)l * m + k] = count[(size_t)k * m + l];
   if (timings_ms) {
-    float f = 0.f;
-    hipEventElapsedTime(&f, ev[0], ev[1]);
-    timings_ms[1] = f;
-    timings_ms[2] = std::max(0.0, clk.lap() - (double)f);
+    timings_ms[1] = ev.ms(0, 1);
+    timings_ms[2] = lap_rest(clk.lap(), timings_ms[1]);
   }
   return MVBA_OK;
 }
@@ -386,12 +383,11 @@ int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, con
       return rc;
     MVBA_HIP(hipMemcpy(dpairs, pairs, sizeof(int) * 2 * np, hipMemcpyHostToDevice));
     if (timings_ms) timings_ms[0] = clk.lap();
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    EvGuard guard{ev, 4};
-    for (auto &e : ev) MVBA_HIP(hipEventCreate(&e));
+    EvLaps ev;
+    if ((rc = ev.create(4))) return rc;
     const dim3 b256(256);
     auto combine = [&](int cnt, int nv, double *out, int stride) { tv_combine(cnt, nv, n_ch, dpart, out, stride); };
-    hipEventRecord(ev[0], 0);
+    ev.mark();
     for (int p0 = 0; p0 < np; p0 += tile) {
       const int cnt = std::min(tile, np - p0);
       const dim3 grid((unsigned)n_ch, (unsigned)cnt), gp((cnt + 255) / 256);
@@ -406,7 +402,7 @@ int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, con
       hipLaunchKernelGGL(k_twoview_chunk<2>, grid, dim3(START_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy, tp, tn, dpart);
       combine(cnt, 45, dS + 45 * (size_t)p0, 45);
     }
-    hipEventRecord(ev[1], 0);
+    ev.mark();
     MVBA_HIP(hipGetLastError());
     MVBA_HIP(hipMemcpy(S.data(), dS, sizeof(double) * 45 * np, hipMemcpyDeviceToHost));
     MVBA_HIP(hipMemcpy(norm.data(), dnorm, sizeof(double) * TV_NORM * np, hipMemcpyDeviceToHost));
@@ -417,22 +413,19 @@ int mvba_two_view(int64_t n_points, int32_t n_images, const int64_t *pt_ptr, con
         for (int j = 0; j < 9; ++j) Fm[9 * (size_t)p + j] = NAN;
     }
     MVBA_HIP(hipMemcpy(dF, Fm.data(), sizeof(double) * 9 * np, hipMemcpyHostToDevice));
-    hipEventRecord(ev[2], 0);
+    ev.mark();
     for (int p0 = 0; p0 < np; p0 += tile) {
       const int cnt = std::min(tile, np - p0);
       hipLaunchKernelGGL(k_twoview_chunk<3>, dim3((unsigned)n_ch, (unsigned)cnt), dim3(START_CHUNK), 0, 0, (long long)n_points, n_images, dptr, dcam, dxy,
                          dpairs + 2 * (size_t)p0, dF + 9 * (size_t)p0, dpart);
       combine(cnt, 1, dS + (size_t)p0, 1);
     }
-    hipEventRecord(ev[3], 0);
+    ev.mark();
     MVBA_HIP(hipGetLastError());
     MVBA_HIP(hipMemcpy(Sr.data(), dS, sizeof(double) * np, hipMemcpyDeviceToHost));
     if (timings_ms) {
-      float f1 = 0.f, f2 = 0.f;
-      hipEventElapsedTime(&f1, ev[0], ev[1]);
-      hipEventElapsedTime(&f2, ev[2], ev[3]);
-      timings_ms[1] = (double)f1 + f2;
-      timings_ms[2] = std::max(0.0, clk.lap() - timings_ms[1]);  // the copies back, the host's eigen-solves and the upload of F
+      timings_ms[1] = ev.ms(0, 1) + ev.ms(2, 3);
+      timings_ms[2] = lap_rest(clk.lap(), timings_ms[1]);  // the copies back, the host's eigen-solves and the upload of F
     }
   }
   for (int p = 0; p < np; ++p) {
