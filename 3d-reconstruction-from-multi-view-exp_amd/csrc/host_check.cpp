@@ -1,6 +1,6 @@
 // The SVD workspace's host arithmetic (mvba_host.h: select_basis, basis_block, DepthScratch, the LDS formulas), the BA engine's host
 // logic (mvba_engine_host.h: build_parameter_map, reduced_system_residual, expand_packed_A, expand_compact_record and the record_to_*
-// fills of mvba_debug_read, the cam15 row, the width rules of K5, the cost pass and the covariance) and the host logic of a RANSAC
+// fills of mvba_debug_read, the cam15 row, the lane form's packed index row and range count, the width rules of K5, the cost pass and the covariance) and the host logic of a RANSAC
 // round (mvba_ransac_host.h: rs_pick, rs_accept, rs_current and rs_other, RsTile, CamChunks, the argument checks, the homography's hg_*, align_solve) and the track
 // builder's host pieces (mvba_tracks_host.h: its argument checks, tracks_classify, trk_grid) and the matcher's (mvba_match_host.h: its
 // argument checks, the chunk rule, the ratio test, the plan of a call and the block lists of a chunk) and lap_rest on hand-made inputs.  A program of its own,
@@ -859,6 +859,75 @@ int main() {
     for (size_t by : {(size_t)0, (size_t)40961, (size_t)81921, (size_t)160 * 1024}) CHECK(in(TABLE_BLOCK_THREADS, table_block_threads(by)));
     for (double pr : {0.0, 13.0, 25.0, 49.0, 1e6}) CHECK(in(COV_LANES, cov_lanes(pr)));
     CHECK(std::size(K5_LANES) == 3 && std::size(TABLE_BLOCK_THREADS) == 3 && std::size(COV_LANES) == 4);
+  }
+  {  // the lane form's packed index row: (k, l, a) -> two words -> (k, l, a) at every edge of the three fields
+    const int ROW = (int)LANE_IDX_MAX_ROW, OFF = (int)LANE_IDX_MAX_OFF;
+    CHECK(LANE_IDX_ROW_BITS == 25 && LANE_IDX_OFF_BITS == 14 && ROW == (1 << 25) - 1 && OFF == 16383);
+    auto round_trip = [](int k, int l, int a) {
+      int k2 = -1, l2 = -1, a2 = -1;
+      const LaneIdx p = lane_idx_pack(k, l, a);
+      lane_idx_unpack(p, k2, l2, a2);
+      return k2 == k && l2 == l && a2 == a && lane_idx_k(p.w0) == k && lane_idx_l(p.w0, p.w1) == l && lane_idx_a(p.w1) == a;
+    };
+    const int ks[] = {0, 1, 127, 128, (1 << 24) + 5, ROW - OFF, ROW - 1, ROW}, as[] = {0, 1, 77, 1 << 24, ROW - 1, ROW};
+    const int ds[] = {0, 1, 63, 64, 79, 127, 128, 129, 255, 256, 8191, 8192, OFF - 1, OFF};
+    for (int k : ks)
+      for (int d : ds)
+        for (int a : as)
+          if ((long long)k + d <= ROW) CHECK(round_trip(k, k + d, a));
+    CHECK(round_trip(ROW - OFF, ROW, ROW));  // the largest record index, offset and point row at once
+    {  // the padding item (the range's first record twice, the all-zero point row N) and a diagonal item (l = k)
+      const int N = 1234567;
+      const LaneIdx pad = lane_idx_pack(0, 0, N), dg = lane_idx_pack(4711, 4711, 42);
+      CHECK(pad.w0 == 0u && pad.w1 == (unsigned)N && round_trip(0, 0, N) && round_trip(0, 0, ROW));
+      CHECK(dg.w0 == 4711u && dg.w1 == 42u && lane_idx_l(dg.w0, dg.w1) == lane_idx_k(dg.w0));
+    }
+    // the fields do not run into each other: the offset's two halves alone, and all ones
+    CHECK(lane_idx_pack(0, 127, 0).w0 == 127u << 25 && lane_idx_pack(0, 127, 0).w1 == 0u);
+    CHECK(lane_idx_pack(0, 128, 0).w0 == 0u && lane_idx_pack(0, 128, 0).w1 == 1u << 25);
+    CHECK(lane_idx_pack(ROW - OFF, ROW, ROW).w1 == 0xffffffffu);
+    static_assert(lane_idx_l(lane_idx_pack(5, 300, 9).w0, lane_idx_pack(5, 300, 9).w1) == 300, "constexpr on the host and in the kernels");
+    // what decide_schur_form asks before it takes the lane form: the byte-offset guards' largest scene fits, one more does not
+    const long long NMAX = (1LL << 32) / 128 - 2;  // the largest N with (N + 1) * 128 < 2^32
+    CHECK((NMAX + 1) * 128 < (1LL << 32) && (NMAX + 2) * 128 >= (1LL << 32));
+    CHECK(lane_idx_fits(NMAX, NMAX, 16384) && !lane_idx_fits(NMAX, NMAX, 16385) && lane_idx_fits(0, 0, 0) && lane_idx_fits(10, 20, 1));
+    CHECK(!lane_idx_fits(ROW + 1, 10, 2) && !lane_idx_fits(10, ROW + 2, 2) && lane_idx_fits(ROW, ROW + 1, 2));
+  }
+  {  // the lane form's range count: the largest nR with nR * waves <= places, capped at 8 * (1 .. 8) by the typical list, at least 1
+    const long long T = 10000;  // (the typical off-diagonal list of 1 M points at 10 %: the cap is 64)
+    CHECK(lane_ranges(1024, 95, T, 0) == 10 && lane_ranges(768, 95, T, 0) == 8);  // 100 cameras: four places per CU, three
+    CHECK(lane_ranges(1024, 78, T, 0) == 13 && lane_ranges(1024, 63, T, 0) == 16 && lane_ranges(1024, 96, T, 0) == 10);
+    CHECK(lane_ranges(1024, 1024, T, 0) == 1 && lane_ranges(1024, 1025, T, 0) == 1 && lane_ranges(1024, 513, T, 0) == 1 && lane_ranges(1024, 512, T, 0) == 2);
+    CHECK(lane_ranges(1000, 96, T, 0) == 10 && lane_ranges(959, 96, T, 0) == 9);  // places that the waves of a range do not divide
+    CHECK(lane_ranges(1024, 1, T, 0) == 64 && lane_ranges(1024, 9, 1LL << 40, 0) == 64 && lane_ranges(1024, 9, 1024, 0) == 16 && lane_ranges(1024, 9, 1023, 0) == 8);
+    CHECK(lane_ranges(1024, 9, 0, 0) == 8 && lane_ranges(1024, 200, 0, 0) == 5 && lane_ranges(0, 9, T, 0) == 1 && lane_ranges(1024, 0, T, 0) == 64);
+    CHECK(lane_ranges(1024, 95, T, 1) == 1 && lane_ranges(1024, 95, T, 3) == 3 && lane_ranges(1024, 95, T, 11) == 11 && lane_ranges(768, 95, 0, 64) == 64);
+    CHECK(lane_ranges(1024, 95, T, 65) == LANE_MAX_RANGES && lane_ranges(1024, 95, T, 1 << 30) == LANE_MAX_RANGES);
+  }
+  {  // block -> wave of the lane form's launch: a permutation of the waves; a range among the first 8 (nR / 8) keeps to XCD r % 8, the
+     // surplus ranges' waves are spread evenly; the identity for a multiple of 8 and below 8
+    for (int nR : {1, 3, 7, 8, 9, 10, 11, 15, 16, 17, 23, 64})
+      for (int rw : {1, 2, 9, 95, 96}) {
+        const int T = nR * rw, q = nR / 8;
+        std::vector<int> seen(T, 0), surplus(8, 0);
+        bool home_ok = true, same = true, order = true;
+        std::vector<int> last_w(nR, -1);
+        for (int B = 0; B < T; ++B) {
+          const int b = lane_wave_of_block(B, nR, rw);
+          if (b < 0 || b >= T) { home_ok = false; continue; }
+          ++seen[b];
+          const int r = b % nR, w = b / nR;
+          if (r < 8 * q) home_ok = home_ok && B % 8 == r % 8;
+          else ++surplus[B % 8];
+          same = same && b == B;
+          order = order && w > last_w[r];  // a range's waves are dispatched in wave order (the diagonal lists first)
+          last_w[r] = w;
+        }
+        CHECK(std::all_of(seen.begin(), seen.end(), [](int c) { return c == 1; }));
+        CHECK(home_ok && order);
+        CHECK(*std::max_element(surplus.begin(), surplus.end()) - *std::min_element(surplus.begin(), surplus.end()) <= 1);
+        CHECK(same || (nR % 8 != 0 && nR > 8));
+      }
   }
   if (failures) return 1;
   std::printf("host_check ok\n");

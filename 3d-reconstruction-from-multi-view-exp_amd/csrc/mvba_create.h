@@ -213,20 +213,22 @@ int size_pair_lists(const IndexInput &in, PairLists &L) {
 }
 
 // point ranges.  Unit form: long runs for big problems, but small ones still get ~4096 units of >= 128 items.
-// Slot form: 8 ranges (one per XCD) -- 8 j while j ranges' worth of waves fit an XCD and a list keeps >= 64 items.
+// Slot form: 8 ranges (one per XCD) -- 8 j while j ranges' worth of waves fit an XCD and a list keeps >= 64 items.  The lane form
+// (W = 64, not paced) takes `lane_nR` ranges instead: lane_ranges (mvba_engine_host.h), counted from the chip's wave places, any
+// number from 1 on; which block runs wave w of range r is the kernel's affair (lane_wave_of_block keeps a range on one XCD).
 struct PointRanges {
   int nR = 1;
   std::vector<long long> lo;  // [nR + 1] first point of every range
 };
 
-PointRanges make_ranges(const IndexInput &in, const PairLists &L, bool slots, int xcd_waves, int W) {
+PointRanges make_ranges(const IndexInput &in, const PairLists &L, bool slots, int xcd_waves, int W, int lane_nR = 0) {
   PointRanges R;
   const long long N = in.N;
   if (slots) {
     const long long j = std::max<long long>(1, std::min<long long>(xcd_waves / std::max(1LL, L.slot_waves(W)), L.target / (8 * 64)));
-    R.nR = (int)(8 * std::min<long long>(j, 8));
+    R.nR = W == LANES_W ? std::max(1, lane_nR) : (int)(8 * std::min<long long>(j, 8));
     R.lo.assign(R.nR + 1, 0);
-    // equal ITEM counts: the ranges run side by side, one per XCD
+    // equal ITEM counts: the ranges run side by side
     std::vector<long long> pre(N + 1, 0);
     for (long long a = 0; a < N; ++a) {
       const long long d = in.p->pt_ptr[a + 1] - in.p->pt_ptr[a];
@@ -247,9 +249,12 @@ PointRanges make_ranges(const IndexInput &in, const PairLists &L, bool slots, in
 // Tuning of the slot form with one lane per item (k_schur_lanes), measured at config 3 and on its camera sweep (DESIGN.md §3.1,
 // profiles/r06_lanes_product.txt)
 constexpr long long LANES_SKEW = 12288;     // bounded skew of its step merge over 64 slots (twice that: fewer padding rows, slower)
-// taken by mvba_create itself from this many waves per point range on: 1 M points x 10 %, 90 cameras (78 waves) 1.40 against 1.44 ms for k_schur_slots,
-// 80 cameras (63 waves: a third of the XCD's 96 wave places stay empty) 1.32 against 1.19
-constexpr long long LANES_MIN_WAVES = 78;
+// taken by mvba_create itself from this many waves per point range on.  With the ranges counted by wave places (lane_ranges) a
+// short range no longer leaves places empty: 1 M points x 10 %, k_schur_lanes_compact against k_schur_slots, 60 cameras (38 waves,
+// 26 ranges) 0.61 against 0.74 ms, 70: 0.74 / 1.05, 80 (63 waves, 16 ranges): 0.86 / 1.13, 90 (78, 13): 1.08 / 1.39, 100 (95, 10):
+// 1.30 / 1.57 (profiles/r09_lanes_four_waves.txt; with 8 j ranges and three waves per CU it was 78: 80 cameras lost 1.32 to 1.19).
+// Below 60 cameras nothing was measured: the bound is the smallest scene that was.  (MVBA_REC=full, an A/B knob, shares it.)
+constexpr long long LANES_MIN_WAVES = 38;
 
 // What decide_schur_form answers: the form, and for the pair-major forms the lists and ranges the index is built from
 struct SchurPlan {
@@ -258,13 +263,14 @@ struct SchurPlan {
   std::vector<int> dense_obs;  // SCHUR_DENSE with missing observations: [N][m] observation of (point, camera) or -1
   PairLists L;
   PointRanges R;
+  int lane_places = 0;         // W = LANES_W: waves of the lane kernel per CU (the occupancy query's answer) the ranges were counted from
 };
 
 // THE decision of K3's form; the only place that names a form as the engine's.  `count_pairs(cnt)` runs the counting pass of
 // the index build that create_engine chose (host threads or device): the pair-major forms are told apart by what it finds.
 template <typename CountPairs>
-int decide_schur_form(const IndexInput &in, const CreateKnobs &knobs, int loss, int device, CountPairs count_pairs, SchurPlan &plan,
-                      CreateTimer &timer) {
+int decide_schur_form(const IndexInput &in, const CreateKnobs &knobs, int loss, bool compact_rec, int device, CountPairs count_pairs,
+                      SchurPlan &plan, CreateTimer &timer) {
   const mvba_problem *p = in.p;
   const long long N = in.N, nobs = in.nobs;
   const int m = in.m;
@@ -317,17 +323,30 @@ int decide_schur_form(const IndexInput &in, const CreateKnobs &knobs, int loss, 
   // (the gathers use 32-bit byte offsets: point rows from the array's start, records from their RANGE's first
   // observation -- the latter checked per plan, once the ranges are known)
   const bool may_slots = !knobs.schur_pairs && loss == LOSS_SQUARED && (N + 1) * 128LL < (1LL << 32) && !knobs.force_big && (L.T >= 4000000 || slots_forced);
+  // The lane form's ranges are counted from the wave places of the kernel it will launch (`compact_rec`: k_schur_lanes_compact, four
+  // waves of 40 KiB per CU; else k_schur_lanes, three) as the RUNTIME counts them.  What it admits stays a range of 96 waves.
+  int lane_places = 0;
+  if (may_slots)
+    MVBA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lane_places, compact_rec ? (const void *)k_schur_lanes_compact : (const void *)k_schur_lanes, 64,
+                                                          compact_rec ? LANES_LDS_C : LANES_LDS));
+  lane_places = std::max(1, lane_places);
+  plan.lane_places = lane_places;
+  long long max_degree = 0;
+  for (long long a = 0; a < N; ++a) max_degree = std::max<long long>(max_degree, p->pt_ptr[a + 1] - p->pt_ptr[a]);
   // the slot form at W lists per wave: its point ranges, or false where it may not run
   auto slot_plan = [&](int W, PointRanges &R) {
     if (!may_slots || L.slot_waves(W) > xcd_waves(W)) return false;
-    R = make_ranges(in, L, true, xcd_waves(W), W);
+    R = make_ranges(in, L, true, xcd_waves(W), W,
+                    lane_ranges((long long)n_cu_dev * lane_places, L.slot_waves(LANES_W), L.target, knobs.slot_ranges));
     // (few cameras with dense visibility: a dozen cameras are 78 lists = 5 waves per range, 320 waves on the whole chip even with 64
     // ranges -- 1 M points x 12 cameras, all visible: 9.3 ms against 4.9 for the unit form; at 20 cameras, 704 waves, the slot form is
     // ahead again, 9.8 against 10.8: profiles/r05_sweep_few_cameras.txt)
     if (W == PSTEP && !slots_forced && R.nR * L.slot_waves(W) < 512) return false;
     long long widest = 0;
     for (int r = 0; r < R.nR; ++r) widest = std::max<long long>(widest, p->pt_ptr[R.lo[r + 1]] - p->pt_ptr[R.lo[r]]);
-    return (widest + 1) * 128LL < (1LL << 32);  // (a range's records span 4 GiB: the unit form's 64-bit-offset build)
+    if ((widest + 1) * 128LL >= (1LL << 32)) return false;  // (a range's records span 4 GiB: the unit form's 64-bit-offset build)
+    // (W = 64: an item is two packed words -- a point seen more than 16,384 times does not pack: k_schur_slots, then the unit form)
+    return W != LANES_W || lane_idx_fits(N, widest, max_degree);
   };
   // The slot form first where it may run, else the unit form.  One lane per item (W = 64) by itself only where k_schur_slots
   // would run too and a range has LANES_MIN_WAVES .. 96 waves of 64 lists; MVBA_SCHUR=lanes asks for it wherever its own
@@ -416,7 +435,8 @@ constexpr long long SLOT_SEG = 8192;    // pacing segment
 constexpr int SLOT_LAG = 4;             // a wave enters segment j only when all waves of its range have left segment j - lag
 constexpr long long slot_skew(int W) { return W == LANES_W ? LANES_SKEW : SLOT_SKEW; }
 
-// The slot form's waves: block b = nR w + r is wave w of range r and runs on XCD r % 8.  sl_beg / sl_len: the span of items
+// The slot form's waves: block b = nR w + r is wave w of range r and runs on XCD r % 8 (the lane form: WAVE b, run by the block
+// lane_wave_of_block assigns it).  sl_beg / sl_len: the span of items
 // each of its 21 slots merges (from the units); w_steps / w_beg: the steps it takes and its first step, once merged.
 struct SlotWaves {
   long long n_waves = 0;
@@ -426,7 +446,8 @@ struct SlotWaves {
   std::vector<int> sl_len;
 };
 
-// ---- waves of W = 21 (64: k_schur_lanes) lists, every wave once per range; the diagonal pairs' sub-lists come FIRST: a CU's SIMDs
+// ---- waves of W = 21 (64: k_schur_lanes, whose nR need not be a multiple of 8) lists, every wave once per range; the diagonal pairs'
+// sub-lists come FIRST: a CU's SIMDs
 // arbitrate by age, the blocks dispatched last share a SIMD three ways as its youngest wave and fall behind --
 // and a diagonal step is the dearer one
 SlotWaves make_slot_waves(const IndexInput &in, const SchurPlan &plan, const std::vector<int> &uid, SchurIndex &ix) {
@@ -840,7 +861,7 @@ int upload_schur_index(mvba_handle *h, const SchurPlan &plan, SchurIndex &ix) {
   }
   // the compact lane form: the descriptors in UNIT order -- a lane takes its pair's cameras (w = k << 16 | l) from its unit's
   if (h->rec_compact && !ix.units.empty()) MVBA_HIP(hipMemcpy(h->d_units, ix.units.data(), sizeof(int4) * ix.units.size(), hipMemcpyHostToDevice));
-  if (h->schur_mode == SCHUR_SLOTS && h->n_slot_items) {  // the three step-major arrays -> one 256-byte (768: 64 slots) row per step; they go
+  if (h->schur_mode == SCHUR_SLOTS && h->n_slot_items) {  // the three step-major arrays -> one 256-byte (64 slots: 512, packed) row per step; they go
     const int W = h->slot_w, row = slot_idx_ints(W);
     const long long n_steps = h->n_slot_items / W;
     CR(h->mem.alloc(&h->d_it_x, (size_t)n_steps * row));
@@ -958,14 +979,16 @@ int build_engine(mvba_handle *h, const mvba_problem *p, const CreateKnobs &knobs
   DeviceIndexBuild dv;  // (its temporaries go with this scope)
   SchurPlan plan;
   SchurIndex ix;
-  CR(decide_schur_form(in, knobs, h->loss, h->device, [&](std::vector<long long> &cnt) {
+  // The record layout is the engine's (DESIGN.md §2): compact exactly where K3 takes the lane form -- the one form with arithmetic to
+  // spare for the omega rows --, the loss is squared and K1 holds the camera table in LDS; MVBA_REC=full keeps the 128-byte record
+  const bool compact_rec = h->loss == LOSS_SQUARED && !h->gcam && !knobs.rec_full;
+  CR(decide_schur_form(in, knobs, h->loss, compact_rec, h->device, [&](std::vector<long long> &cnt) {
     return dev_build ? count_pairs_device(in, knobs, dv, cnt) : count_pairs_host(in, cnt);
   }, plan, timer));
   h->schur_mode = plan.mode;
   h->use_pairs = plan.mode != SCHUR_DENSE;
-  // The record layout is the engine's (DESIGN.md §2): compact exactly where K3 takes the lane form -- the one form with arithmetic to
-  // spare for the omega rows --, the loss is squared and K1 holds the camera table in LDS; MVBA_REC=full keeps the 128-byte record
-  h->rec_compact = plan.mode == SCHUR_SLOTS && plan.W == LANES_W && h->loss == LOSS_SQUARED && !h->gcam && !knobs.rec_full;
+  h->rec_compact = plan.mode == SCHUR_SLOTS && plan.W == LANES_W && compact_rec;
+  h->lane_places = plan.mode == SCHUR_SLOTS && plan.W == LANES_W ? plan.lane_places : 0;
   if (h->use_pairs) CR(dev_build ? build_index_device(in, plan, dv, h->mem, ix, timer) : build_index_host(in, plan, h->mem, ix, timer));
   timer.lap("queues / wave descriptors");
 

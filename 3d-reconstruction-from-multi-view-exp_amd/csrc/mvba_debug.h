@@ -84,8 +84,10 @@ int mvba_get_info(mvba_handle *h, int64_t *out8) {
   out8[0] = h->n_items;
   out8[1] = h->n_items_offdiag;
   out8[2] = h->n_units;
-  // bits 8..15: the slot form's step width; bit 16: the engine linearises into the compact record; bits 32..: the dense form's workgroups
+  // bits 8..15: the slot form's step width; bit 16: the engine linearises into the compact record; bits 20..27: the slot form's point
+  // ranges; bits 28..31: the lane form's wave places per CU as its plan took them; bits 32..: the dense form's workgroups
   out8[3] = h->schur_mode | (h->schur_mode == SCHUR_SLOTS ? h->slot_w << 8 : 0) | (h->rec_compact ? 1 << 16 : 0) |
+            (h->schur_mode == SCHUR_SLOTS ? (int64_t)(h->slot_nR & 0xff) << 20 | (int64_t)(h->lane_places & 0xf) << 28 : 0) |
             (h->schur_mode == SCHUR_DENSE ? (int64_t)h->dense_blocks << 32 : 0);
   out8[4] = h->rccl_version;
   out8[5] = NCCL_VERSION_CODE;
@@ -176,6 +178,15 @@ int debug_fill_index(mvba_handle *h, int which, long long cnt, double *out) {
     const long long n_steps = cnt / W;
     std::vector<int> tmp((size_t)n_steps * row);
     if (cnt) MVBA_HIP(hipMemcpy(tmp.data(), h->d_it_x, sizeof(int) * tmp.size(), hipMemcpyDeviceToHost));
+    if (W == LANES_W) {  // two packed words per item: w0[W] | w1[W]
+      for (long long st = 0; st < n_steps; ++st)
+        for (int sl = 0; sl < W; ++sl) {
+          int k, l, a;
+          lane_idx_unpack({(unsigned)tmp[(size_t)st * row + sl], (unsigned)tmp[(size_t)st * row + W + sl]}, k, l, a);
+          out[st * W + sl] = (double)(which == MVBA_BUF_INDEX_K ? k : (which == MVBA_BUF_INDEX_L ? l : a));
+        }
+      return MVBA_OK;
+    }
     const int off = which == MVBA_BUF_INDEX_K ? 0 : (which == MVBA_BUF_INDEX_L ? W : 2 * W);
     for (long long st = 0; st < n_steps; ++st)
       for (int sl = 0; sl < W; ++sl) out[st * W + sl] = (double)tmp[(size_t)st * row + off + sl];

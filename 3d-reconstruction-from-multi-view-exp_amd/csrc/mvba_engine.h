@@ -43,10 +43,11 @@ struct mvba_handle {
   // ... the slot form's waves over it
   int n_waves = 0, slot_nR = 8, slot_nseg = 0;
   int slot_w = PSTEP;                 // slot form: lists per wave = items per step (21: k_schur_slots, 64: k_schur_lanes, not paced)
+  int lane_places = 0;                // lane form: waves of its kernel a CU holds, as the occupancy query answered when the ranges were counted
   long long *d_range_o0 = nullptr;    // slot form: first observation of every point range (the record base of its waves)
   int *d_seg_end = nullptr, *d_prog = nullptr;
   int4 *d_wdesc = nullptr;
-  int *d_it_x = nullptr;              // slot form: the step-major index, 64 ints per step (k[21] | l[21] | a[21] | pad)
+  int *d_it_x = nullptr;              // slot form: the step-major index, 64 ints per step (k[21] | l[21] | a[21] | pad); lane form: 128 (w0[64] | w1[64])
   int *d_wunits = nullptr;
   // ... and the dense form, which has no index
   double *d_dense_part = nullptr;     // SCHUR_DENSE: partial tiles per workgroup
@@ -382,6 +383,7 @@ struct CreateKnobs {
   bool schur_set = false;                      // MVBA_SCHUR set at all (any value keeps a fully visible scene off the dense form
   bool schur_slots = false, schur_lanes = false, schur_pairs = false, schur_dense = false;  // ... unless it is `dense`)
   bool index_host = false, index_global = false;  // MVBA_INDEX=host | global: where the Schur index is built
+  int slot_ranges = 0;                         // MVBA_SLOT_RANGES: the lane form's point ranges (0: counted from the wave places)
   bool force_big = false;                      // MVBA_FORCE_BIG
   bool rec_full = false;                       // MVBA_REC=full: the 128-byte record on a lane-form engine too
   bool chol_launches = false;                  // MVBA_CHOL=launches
@@ -404,6 +406,7 @@ CreateKnobs read_create_knobs() {
   const char *index = getenv("MVBA_INDEX");
   k.index_host = is(index, "host");
   k.index_global = is(index, "global");
+  if (const char *ev = getenv("MVBA_SLOT_RANGES")) k.slot_ranges = std::max(0, atoi(ev));
   k.force_big = getenv("MVBA_FORCE_BIG") != nullptr;
   k.rec_full = is(getenv("MVBA_REC"), "full");
   k.chol_launches = is(getenv("MVBA_CHOL"), "launches");

@@ -1,6 +1,6 @@
 // The BA engine's host logic with no HIP call in it: the gauge predicate, the checks and tables of a parameter map, the residual of
-// the reduced system (MVBA_CHECK_SOLVE), the packed strips and the records as mvba_debug_read hands them out, the cam15 row, and
-// the width rules of K5, the cost pass and the covariance's point pass.  Plain functions over pointers and std::vectors, none
+// the reduced system (MVBA_CHECK_SOLVE), the packed strips and the records as mvba_debug_read hands them out, the cam15 row, the
+// lane form's packed index row and range count, and the width rules of K5, the cost pass and the covariance's point pass.  Plain functions over pointers and std::vectors, none
 // takes an mvba_handle: csrc/host_check.cpp runs them on hand-made inputs under the host sanitizers.
 //
 // Needs mvba_common.h alone (fail, strip_offset, CAM_IN).  Included by mvba.hip before the engine (mvba_engine.h and the headers
@@ -171,6 +171,62 @@ inline void unpack_cam15(const double *cam /*[m][CAM_IN]*/, int m, double *f, do
     for (int i = 0; i < 3; ++i) t[3 * k + i] = c[3 + i];
     for (int i = 0; i < 9; ++i) R[9 * k + i] = c[6 + i];
   }
+}
+
+// ------------------------------------------------------------------ the lane form's index row and its point ranges
+// An item of a 64-wide step (k_schur_lanes, mvba_lanes.h) is TWO words: the k-side record, the point row and the l-side record as
+// its offset from k -- k and l are observations of one point, l >= k, so l - k is below that point's degree.  Records are indexed
+// from their range's first observation and gathered with 32-bit byte offsets of 128-byte rows, point rows likewise from the
+// array's start (the padding row is row N): both are below 2^25 by the guards decide_schur_form has for those offsets.  That
+// leaves 2 x 7 bits for the offset:
+//   w0 = k | (l - k)[0..6] << 25        w1 = a | (l - k)[7..13] << 25
+// A padding item is (0, 0, N), a diagonal item has l = k.
+constexpr int LANE_IDX_ROW_BITS = 25, LANE_IDX_OFF_BITS = 2 * (32 - LANE_IDX_ROW_BITS);
+constexpr unsigned LANE_IDX_ROW_MASK = (1u << LANE_IDX_ROW_BITS) - 1, LANE_IDX_OFF_LOW = (1u << (32 - LANE_IDX_ROW_BITS)) - 1;
+constexpr long long LANE_IDX_MAX_ROW = LANE_IDX_ROW_MASK, LANE_IDX_MAX_OFF = (1LL << LANE_IDX_OFF_BITS) - 1;
+struct LaneIdx { unsigned w0, w1; };
+__host__ __device__ constexpr LaneIdx lane_idx_pack(int k, int l, int a) {
+  const unsigned d = (unsigned)(l - k);
+  return {(unsigned)k | (d & LANE_IDX_OFF_LOW) << LANE_IDX_ROW_BITS, (unsigned)a | (d >> (32 - LANE_IDX_ROW_BITS)) << LANE_IDX_ROW_BITS};
+}
+// (the kernel's gather lanes each need one of the three, of another item: the fields one by one)
+__host__ __device__ constexpr int lane_idx_k(unsigned w0) { return (int)(w0 & LANE_IDX_ROW_MASK); }
+__host__ __device__ constexpr int lane_idx_a(unsigned w1) { return (int)(w1 & LANE_IDX_ROW_MASK); }
+__host__ __device__ constexpr int lane_idx_l(unsigned w0, unsigned w1) {
+  return (int)((w0 & LANE_IDX_ROW_MASK) + (w0 >> LANE_IDX_ROW_BITS) + ((w1 >> LANE_IDX_ROW_BITS) << (32 - LANE_IDX_ROW_BITS)));
+}
+__host__ __device__ constexpr void lane_idx_unpack(LaneIdx p, int &k, int &l, int &a) {
+  k = lane_idx_k(p.w0); l = lane_idx_l(p.w0, p.w1); a = lane_idx_a(p.w1);
+}
+// What a scene must keep to for the packed row: N points (row N is the padding row), the longest range of `widest` observations,
+// the largest degree of a point.  The first two restate the byte-offset guards; the third is the packed row's own.
+constexpr bool lane_idx_fits(long long N, long long widest, long long max_degree) {
+  return N <= LANE_IDX_MAX_ROW && widest - 1 <= LANE_IDX_MAX_ROW && max_degree - 1 <= LANE_IDX_MAX_OFF;
+}
+static_assert((1LL << 32) / 128 - 2 <= LANE_IDX_MAX_ROW, "the largest N (and range) with (N + 1) * 128 < 2^32 fits the row fields");
+
+// Point ranges of the lane form.  Its launch is not paced and its waves need not be resident together, so the ranges are
+// counted by the chip's wave places (CUs x waves of the kernel per CU, from the occupancy query), not by XCDs: the largest nR
+// with nR x range_waves <= places, so that every wave starts at once and the lists are as short as that allows.  Capped as the
+// slot form caps its own (8 x (1 .. 8), while the typical list keeps 64 items per range); at least 1.  `forced` > 0
+// (MVBA_SLOT_RANGES) is taken as it is, up to the cap's ceiling: more waves than places only run later.
+constexpr int LANE_MAX_RANGES = 64;
+inline int lane_ranges(long long places, long long range_waves, long long target, int forced) {
+  if (forced > 0) return std::min(forced, LANE_MAX_RANGES);
+  const long long cap = 8 * std::max<long long>(1, std::min<long long>(LANE_MAX_RANGES / 8, target / (8 * 64)));
+  return (int)std::max<long long>(1, std::min(places / std::max<long long>(1, range_waves), cap));
+}
+
+// Which wave b = nR w + r (wave w of range r, the numbering of the index) block B of the lane form's launch is.  Blocks go to the
+// XCDs round-robin, B % 8.  A range whose waves share an XCD reads its records through ONE L2; striped over all eight, ten
+// ranges ran 18 % SLOWER than eight.  So with nR = 8 q + s the ranges x, x + 8, .. of the first 8 q are XCD x's
+// own, wave-major, and the waves of the s surplus ranges are dealt over the XCDs behind them.  For s = 0 and for nR < 8 this is
+// b = B.  `range_waves` = waves per range (blocks / nR).
+__host__ __device__ constexpr int lane_wave_of_block(int B, int nR, int range_waves) {
+  const int q = nR / 8, s = nR - 8 * q, i = B / 8, x = B % 8, home = q * range_waves;
+  if (i < home) return nR * (i / q) + x + 8 * (i % q);
+  const int j = 8 * (i - home) + x;
+  return nR * (j / s) + 8 * q + j % s;
 }
 
 // ------------------------------------------------------------------ width rules: the value a launch takes, the domain beside it

@@ -183,13 +183,20 @@ __global__ __launch_bounds__(64) void k_idx_merge(long long n_waves, int nR, int
 }
 
 // the slot kernels' index: one row of `row` ints per step, k[W] | l[W] | a[W] | pad -- ONE LDS-DMA instruction per step
-// (W = 21: 64 ints = 256 bytes with 1 int of padding; W = 64: 192 ints = 768 bytes)
+// (W = 21: 64 ints = 256 bytes with 1 int of padding; W = 64: two words per item, w0[64] | w1[64] = 512 bytes -- lane_idx_pack,
+// mvba_engine_host.h; decide_schur_form has checked that every item packs)
 __global__ void k_idx_interleave(long long n_steps, int W, int row, const int *__restrict__ st_k, const int *__restrict__ st_l,
                                  const int *__restrict__ st_a, int *__restrict__ out) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_steps * row) return;
   const long long st = t / row;
   const int e = (int)(t - st * row), which = e / W, sl = e - which * W;
+  if (W == LANES_W) {
+    const long long o = st * W + sl;
+    const LaneIdx p = lane_idx_pack(st_k[o], st_l[o], st_a[o]);
+    out[t] = (int)(which == 0 ? p.w0 : p.w1);
+    return;
+  }
   const int *src = which == 0 ? st_k : (which == 1 ? st_l : st_a);
   out[t] = which < 3 ? src[st * W + sl] : 0;
 }

@@ -4,16 +4,19 @@
 // registers (81 fp64 accumulators; the three-lanes-per-item form of k_schur_slots keeps 27 per lane and forms
 // t = J_Xk E^-1 J_Xl^T three times per item).  Per item: 272 instead of ~780 bytes of LDS reads (a lane reads its own rows
 // once), a third of the index rows and of the scalar bookkeeping; the row gathers (3 per item) are the same.  What it costs: a
-// step stages 64 x 272 B = 17,408 B, three buffers (two gathers in flight) + a two-deep index ring are 53,760 B per wave --
-// THREE waves per CU, 96 per XCD -- so every latency is hidden by the wave's own software pipeline or not at all, and a point
-// range's lists must fit 96 waves (mvba_create: ~100 cameras at 10 % visibility).  The launch is not paced: 96 waves per XCD
-// drift less than k_schur_slots' 284 (DESIGN.md §3.1 has both timings).
+// step stages 64 x 272 B = 17,408 B, three buffers (two gathers in flight) + a two-deep index ring are 53,248 B per wave --
+// THREE waves per CU (the compact record below: FOUR, one per SIMD) -- so every latency is hidden by the wave's own software
+// pipeline or not at all, and a point range's lists must fit 96 waves (mvba_create: ~100 cameras at 10 % visibility).  The
+// launch is not paced -- 96 waves per range drift less than k_schur_slots' 284 (DESIGN.md §3.1 has both timings) -- and no wave
+// waits for another: the point ranges are counted from the chip's wave places (lane_ranges), any number from 1 on, and a wave
+// that finds no place only runs later.  Block -> (wave, range): lane_wave_of_block, a range on one XCD where that can be.
 //
 // Staging buffer of a step: SchurStage<64, DIAG, packed>, one row per lane = slot = item.  Every gather instruction is a full
 // wave: 64 rows x 7 slots = 7 instructions per record side, 3 (5) for the point rows, 1 for the residuals; lane-slot
 // e = 64 j + lane of instruction j is row e / 7 (e / 3, e / 5), slot e % 7, and lands at byte 16 e of its region -- the
 // row-major layout.
-// Index row of a step: k[64] | l[64] | a[64] (768 B, one 48-lane LDS-DMA), two deep.
+// Index row of a step: w0[64] | w1[64], two packed words per item (lane_idx_pack in mvba_engine_host.h: k, l - k, a; 512 B, one
+// 32-lane LDS-DMA), two deep.  A gather lane unpacks the one field it needs, of the item whose row it fetches.
 // What the counted wait covers: iteration s sends the index row of step s + 3 into the ring slot whose indices (step s + 1)
 // were read an iteration ago, reads the indices of step s + 2 from the OTHER slot, sends the G gathers of step s + 2 (13 DIAG,
 // 17 otherwise; all unconditional, steps past the end clamped to the last one) and computes step s.  vmcnt retires in issue
@@ -25,23 +28,24 @@
 // 0..4 are ONE run of the 128-byte line read as a ring).  The lane keeps the centres t_k, t_l of its pair (12 VGPRs, loaded
 // once) and forms the omega rows of either side as (row of J_X) x (X_a - t), obs_math's expression on the stored J_X: 15 fp64
 // operations per side instead of 48 gathered bytes.  Gathers per step: 4 + 4 + 5 = 13 instead of 17 (DIAG: 4 + 1 + 7 = 12
-// instead of 13; the residual comes from its own array); a step stages 64 x 208 B = 13,312 B, a wave holds 41,472 B -- still
-// three waves per CU.  64-byte rows put the 16 lanes of a ds_read_b128 group on four bank quads; slot s of row r therefore
+// instead of 13; the residual comes from its own array); a step stages 64 x 208 B = 13,312 B, a wave holds 3 x 13,312 + 1,024 =
+// 40,960 B -- exactly 80 LDS granules, FOUR waves in a CU's 160 KiB, which the 768-byte index rows missed by 512 B a wave.  (Four
+// staging buffers at three waves -- a third step in flight, 54,272 B -- were built beside it and lost: DESIGN.md §3.3.)  64-byte rows put the 16 lanes of a ds_read_b128 group on four bank quads; slot s of row r therefore
 // sits at position s ^ ((r >> 2) & 3) of its row -- the gather fetches it there -- and the reads are conflict-free again.
 #pragma once
 
 constexpr int LANES_W = 64;                   // slots (= lanes = items) per step
-constexpr int LANES_IDX = 3 * LANES_W;        // ints per index row
+constexpr int LANES_IDX = 2 * LANES_W;        // ints per index row: w0[64] | w1[64] (lane_idx_pack, mvba_engine_host.h)
 constexpr int LANES_BUF = SchurStage<LANES_W, false, true>::SIZE;  // one staging buffer (the off-diagonal step is the larger one)
 constexpr int LANES_LDS = 3 * LANES_BUF + 2 * LANES_IDX * 4;  // three staging buffers + the index ring per wave
-static_assert(LANES_BUF == 17408 && LANES_LDS == 53760, "the launch's LDS bytes");
+static_assert(LANES_BUF == 17408 && LANES_LDS == 53248, "the launch's LDS bytes");
 static_assert(SchurStage<LANES_W, true, true>::SIZE <= LANES_BUF, "a diagonal step fits the buffer");
-static_assert(3 * ((LANES_LDS + 511) / 512 * 512) <= 160 * 1024, "three waves per CU");
+static_assert(3 * ((LANES_LDS + 511) / 512 * 512) <= 160 * 1024 && 4 * ((LANES_LDS + 511) / 512 * 512) > 160 * 1024, "three waves per CU");
 constexpr int LANES_BUF_C = SchurStage<LANES_W, false, true, true>::SIZE;  // the same on the compact record
 constexpr int LANES_LDS_C = 3 * LANES_BUF_C + 2 * LANES_IDX * 4;
-static_assert(LANES_BUF_C == 13312 && LANES_LDS_C == 41472, "the compact launch's LDS bytes");
+static_assert(LANES_BUF_C == 13312 && LANES_LDS_C == 40960, "the compact launch's LDS bytes");
 static_assert(SchurStage<LANES_W, true, true, true>::SIZE == 12288, "a compact diagonal step fits the buffer");
-static_assert(3 * ((LANES_LDS_C + 511) / 512 * 512) <= 160 * 1024 && 4 * ((LANES_LDS_C + 511) / 512 * 512) > 160 * 1024, "three waves per CU");
+static_assert(4 * ((LANES_LDS_C + 511) / 512 * 512) <= 160 * 1024 && 5 * ((LANES_LDS_C + 511) / 512 * 512) > 160 * 1024, "four waves per CU, one per SIMD");
 
 // what the compact form takes beside the records: the residuals (of the wave's range, like `rec`), the units (w = k << 16 | l)
 // and the committed cameras, for the centres
@@ -87,7 +91,7 @@ __device__ __forceinline__ void schur_lanes_run(char *wbuf, const int lane, cons
 
   const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char *)wbuf;
   const unsigned ldsx0 = lds0 + NBUF * BUFSZ;              // the index ring (two rows)
-  const int *xring = reinterpret_cast<const int *>(wbuf + NBUF * BUFSZ);
+  const unsigned *xring = reinterpret_cast<const unsigned *>(wbuf + NBUF * BUFSZ);
   const int *xbase = it_x + beg * LANES_IDX;               // (`beg` = first STEP of this wave; wave-uniform)
   const int last_st = nst - 1;
   // this lane's (row, slot) of gather instruction j: records 7 slots per row, point rows NPS; COMPACT: records 4 slots per row,
@@ -96,11 +100,11 @@ __device__ __forceinline__ void schur_lanes_run(char *wbuf, const int lane, cons
   auto rec_s16 = [&](int j) { return COMPACT ? (unsigned)((lane & 3) ^ ((lane >> 4) & 3)) << 4 : (unsigned)((64 * j + lane) % 7) << 4; };
   auto pb_row = [&](int j) { return (64 * j + lane) / NPS; };
   auto pb_s16 = [&](int j) { return (unsigned)(COMPACT ? ((64 * j + lane) % NPS + 6) & 7 : (64 * j + lane) % NPS) << 4; };
-  const unsigned lane16 = (unsigned)min(lane, 47) << 4;
-  auto index_row = [&](int st, unsigned ring_off) {  // the 768-byte index row of step st -> ring slot at byte offset ring_off
+  const unsigned lane16 = (unsigned)min(lane, 31) << 4;
+  auto index_row = [&](int st, unsigned ring_off) {  // the 512-byte index row of step st -> ring slot at byte offset ring_off
     const int *src = xbase + (size_t)min(st, last_st) * LANES_IDX;  // wave-uniform
     const unsigned dst = ldsx0 + ring_off;
-    if (lane < 48) lds_index_row(lane16, src, dst);
+    if (lane < 32) lds_index_row(lane16, src, dst);
   };
   constexpr unsigned RING_B = LANES_IDX * 4;
   // one iteration's vector-memory operations: the index row of step `st_idx` into ring slot `ring_next` (its old indices were read
@@ -108,19 +112,29 @@ __device__ __forceinline__ void schur_lanes_run(char *wbuf, const int lane, cons
   // `ring_off` (landed: the caller's wait saw to it)
   auto issue_step = [&](unsigned ring_off, unsigned ring_next, unsigned buf_off, int st_idx) {
     index_row(st_idx, ring_next);
-    const int *x = reinterpret_cast<const int *>(reinterpret_cast<const char *>(xring) + ring_off);
+    const unsigned *x = reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(xring) + ring_off);
     const unsigned buf = lds0 + buf_off;
+    // the words of the items this lane gathers for: w0 of its record rows' items, w1 of its point rows' items and -- for the l
+    // side, k + offset -- w1 of the record rows' items too (DIAG: l = k, the residual row is this lane's own item's)
+    unsigned k0[RSL], a1[NPS], l1[RSL];
+#pragma unroll
+    for (int j = 0; j < RSL; ++j) k0[j] = x[rec_row(j)];
+#pragma unroll
+    for (int j = 0; j < NPS; ++j) a1[j] = x[LANES_W + pb_row(j)];
+#pragma unroll
+    for (int j = 0; j < RSL; ++j) l1[j] = DIAG ? (j == 0 ? x[lane] : 0u) : x[LANES_W + rec_row(j)];
+#pragma unroll
+    for (int j = 0; j < RSL; ++j) asm volatile("" : "+v"(k0[j]), "+v"(l1[j]));  // (the reads are issued here, ahead of the gathers)
+#pragma unroll
+    for (int j = 0; j < NPS; ++j) asm volatile("" : "+v"(a1[j]));
     int kx[RSL], ax[NPS], lx[RSL];
 #pragma unroll
-    for (int j = 0; j < RSL; ++j) kx[j] = x[rec_row(j)];
+    for (int j = 0; j < RSL; ++j) {
+      kx[j] = lane_idx_k(k0[j]);
+      lx[j] = DIAG ? (j == 0 ? lane_idx_k(l1[0]) : 0) : lane_idx_l(k0[j], l1[j]);
+    }
 #pragma unroll
-    for (int j = 0; j < NPS; ++j) ax[j] = x[2 * LANES_W + pb_row(j)];
-#pragma unroll
-    for (int j = 0; j < RSL; ++j) lx[j] = DIAG ? (j == 0 ? x[lane] : 0) : x[LANES_W + rec_row(j)];
-#pragma unroll
-    for (int j = 0; j < RSL; ++j) asm volatile("" : "+v"(kx[j]), "+v"(lx[j]));  // (the reads are issued here, ahead of the gathers)
-#pragma unroll
-    for (int j = 0; j < NPS; ++j) asm volatile("" : "+v"(ax[j]));
+    for (int j = 0; j < NPS; ++j) ax[j] = lane_idx_a(a1[j]);
     if constexpr (COMPACT) {
 #pragma unroll
       for (int j = 0; j < RSL; ++j) {

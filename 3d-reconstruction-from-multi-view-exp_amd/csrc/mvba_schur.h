@@ -629,15 +629,17 @@ __global__ __launch_bounds__(64, 3) void k_schur_slots(MVBA_SLOTS_ARGS) {
 #include "mvba_lanes.h"  // the slot form with one lane per item: schur_lanes_run, 64 lists per wave
 constexpr int slot_idx_ints(int W) { return W == LANES_W ? LANES_IDX : SLOT_IDX; }  // ints of a step's index row at width W
 
-// The slot form at 64 lists per wave (mvba_lanes.h): block b IS wave b / nR of range b % nR as above, its index rows are
-// 768 bytes and its unit ids 64 per wave.  Not paced: no counters to clear, the pacing table of the index is not read.
+// The slot form at 64 lists per wave (mvba_lanes.h): wave b = nR w + r is wave w of range r as above, its index rows are 512 bytes
+// (two packed words per item) and its unit ids 64 per wave.  nR is any number from 1 on, so WHICH wave a block is keeps a range on
+// one XCD where that can be (lane_wave_of_block, mvba_engine_host.h; b = blockIdx.x for a multiple of 8).  Not paced: no counters
+// to clear, the pacing table of the index is not read, and no wave waits for another -- more waves than places run in turn.
 __global__ __launch_bounds__(64, 1) void k_schur_lanes(const int4 *__restrict__ wdesc, const int *__restrict__ wunits,
                                                        const int *__restrict__ it_x, const double2 *__restrict__ rec,
                                                        const double *__restrict__ PB, double c, double f0,
                                                        double *__restrict__ partial, int nR,
                                                        const long long *__restrict__ range_o0) {
   extern __shared__ char smem_pairs[];
-  const int bid = blockIdx.x;
+  const int bid = lane_wave_of_block((int)blockIdx.x, nR, (int)gridDim.x / nR);
   const int MVBA_CONST_AS *dp = as_const(reinterpret_cast<const int *>(wdesc)) + 4 * (size_t)bid;
   const int d_x = dp[0], d_y = dp[1], nsteps = dp[2], flags = dp[3];
   if (nsteps <= 0) return;  // (wave-uniform) a wave whose lists are all empty in this range
@@ -657,7 +659,7 @@ __global__ __launch_bounds__(64, 1) void k_schur_lanes_compact(const int4 *__res
                                                                const long long *__restrict__ range_o0, const double2 *__restrict__ res,
                                                                const int4 *__restrict__ units, const double *__restrict__ cam15) {
   extern __shared__ char smem_pairs[];
-  const int bid = blockIdx.x;
+  const int bid = lane_wave_of_block((int)blockIdx.x, nR, (int)gridDim.x / nR);
   const int MVBA_CONST_AS *dp = as_const(reinterpret_cast<const int *>(wdesc)) + 4 * (size_t)bid;
   const int d_x = dp[0], d_y = dp[1], nsteps = dp[2], flags = dp[3];
   if (nsteps <= 0) return;  // (wave-uniform) a wave whose lists are all empty in this range

@@ -451,6 +451,9 @@ class HipEngine:
         # (21: k_schur_slots, three lanes per item; 64: k_schur_lanes, one lane per item -- "slots" either way; 0: no slot form)
         return {"items": i[0], "offdiag_items": i[1], "units": i[2], "kernel": ("strip", "pairs", "slots", "dense")[i[3] & 0xff],
                 "slot_rows": i[7], "step_width": (i[3] >> 8) & 0xff,
+                # slot form: the point ranges of the plan; lane form (step_width 64): the waves of its kernel a CU holds, as the
+                # occupancy query answered when the ranges were counted (0 in the other forms)
+                "ranges": (i[3] >> 20) & 0xff, "places_per_cu": (i[3] >> 28) & 0xf,
                 # the linearisation record: "compact" (64 B: J_X and d/df; lane form, squared loss) or "full" (128 B)
                 "record": "compact" if (i[3] >> 16) & 1 else "full",
                 # dense form: the workgroups of k_schur_dense = min(chunks, CUs x workgroups per CU); 0 in the other forms

@@ -1,6 +1,7 @@
 """K3 (Schur) launch time of a scene shape, robust to experimental builds whose numbers are wrong (the LM loop would fail on
 them): linearize once, then `try_step` n times, errors ignored, device time from the engine's
-own hipEvents.   usage: python tools/time_schur.py [points cams vis [reps]]      (MVBA_LIBRARY picks the build)"""
+own hipEvents.   usage: python tools/time_schur.py [points cams vis [reps]]      (MVBA_LIBRARY picks the build; MVBA_SCHUR the form,
+MVBA_SLOT_RANGES the lane form's point ranges)"""
 import os
 import sys
 
@@ -29,5 +30,6 @@ st = eng.stats()
 info = eng.schur_info()
 k = st["schur"]
 print(f"{os.path.basename(os.environ.get('MVBA_LIBRARY', 'tree')):28s} {n}x{m}x{vis} {info['kernel']:6s} schur {k['ms'] / max(k['launches'], 1):.3f} ms/launch "
-      f"({k['launches']} launches) rows {info['slot_rows']} items {info['items']}")
+      f"({k['launches']} launches) rows {info['slot_rows']} items {info['items']} width {info['step_width']} ranges {info['ranges']} "
+      f"places/CU {info['places_per_cu']}")
 eng.close()
