@@ -133,6 +133,23 @@ int main() {
     }
     CHECK(dual_gram_rows(47) == 128 && dual_gram_rows(48) < 128 && dual_gram_rows(256) == 24);
   }
+  {  // the two route decisions of run() at their edges
+    // the block iteration: a wide workspace (more than WIDE_MIN columns) asked for up to WB / 2 triplets, or beyond JACOBI_MAX columns for any
+    CHECK(!wide_route(false, WIDE_MIN, 1) && !wide_route(false, WIDE_MIN, 16) && !wide_route(false, WIDE_MIN, 17));  // (create_workspace: wide = n > WIDE_MIN)
+    CHECK(wide_route(true, WIDE_MIN + 1, 1) && wide_route(true, WIDE_MIN + 1, WB / 2) && !wide_route(true, WIDE_MIN + 1, WB / 2 + 1));
+    CHECK(wide_route(true, JACOBI_MAX, 16) && !wide_route(true, JACOBI_MAX, 17) && !wide_route(true, JACOBI_MAX, JACOBI_MAX));
+    CHECK(wide_route(true, JACOBI_MAX + 1, 16) && wide_route(true, JACOBI_MAX + 1, 17));  // (run_wide refuses the 17)
+    CHECK(WB / 2 == 16 && WIDE_MIN == 64 && JACOBI_MAX == 256);
+    // the streaming rotation: even n <= 32 whose rows are whole 16-byte vectors, from 4096 rows on
+    for (int n = 1; n <= 40; ++n) {
+      CHECK(rotate_streams(8, 4096, n) == (n % 2 == 0 && n <= 32));
+      CHECK(rotate_streams(4, 4096, n) == (n % 4 == 0 && n <= 32));
+      CHECK(!rotate_streams(8, 4095, n) && !rotate_streams(4, 4095, n));
+      if (rotate_streams(8, 4096, n)) CHECK(rotate_rows_lds(8, n) <= ROTATE_LDS_MAX && (GRAM_ROWS * n) % 2 == 0);
+    }
+    CHECK(rotate_streams(8, 4096, 2) && rotate_streams(8, 4096, 32) && !rotate_streams(8, 4096, 34) && !rotate_streams(8, 4096, 31));
+    CHECK(rotate_streams(8, 1LL << 40, 32) && !rotate_streams(8, 1, 32));
+  }
   {  // the pick of a count row: ties, all degenerate, below the minimum, a small item, H = 1
     const int ON = RS_OK | RS_ACTIVE | RS_CUR;
     const int tie[5] = {3, 9, -1, 9, 2};

@@ -135,6 +135,13 @@ inline size_t jacobi_lds(int n) {
   return sizeof(double) * (3 * (np / 2) + 2) + 16 + (n <= JACOBI_LDS_ORDER ? sizeof(double) * 2 * (size_t)n * n : 0);
 }
 inline size_t rotate_rows_lds(size_t el, int n) { return (size_t)GRAM_ROWS * n * el; }
+// The two route decisions of a factorisation (run() in mvsvd.hip; restated in tests/_svd_cases.py).
+// A workspace of more than WIDE_MIN columns (`wide`) takes the block iteration for up to WB / 2 triplets, and beyond JACOBI_MAX
+// columns for any (where it refuses more); otherwise the Gram + Jacobi route.
+inline bool wide_route(bool wide, int n, int n_rank) { return wide && (n_rank <= WB / 2 || n > JACOBI_MAX); }
+// The second pass rotates a tall and narrow matrix in the streaming form (k_rotate_rows: whole 16-byte vectors per row, an even
+// number of columns on the two column tiles); every other shape goes through the 64 x 64 tiles of k_rotate.
+inline bool rotate_streams(size_t el, long long n_rows, int n) { return n <= 32 && n % 2 == 0 && (n * el) % 16 == 0 && n_rows >= 4096; }
 // k_project: 4 n doubles (unused), mu [n], four tiles of 64 rows x min(n, PC) columns at an odd stride
 inline size_t project_lds(size_t el, int n) { return sizeof(double) * (5 * (size_t)n) + el * 4 * 64 * (size_t)(std::min(n, PC) | 1) + 16; }
 // four wave tiles of 64 rows x cols elements at an odd stride: k_scale_rows_tiled (cols = n + groups), the tiled depth kernels (4 m)

@@ -298,7 +298,7 @@ int run_wide(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *m
 
 template <typename T>
 int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means, double *timings) {
-  if (h->wide && (n_rank <= WB / 2 || h->n > JACOBI_MAX)) return run_wide<T>(h, n_rank, center, M, sigma, S, means, timings);
+  if (wide_route(h->wide, h->n, n_rank)) return run_wide<T>(h, n_rank, center, M, sigma, S, means, timings);
   const int n = h->n;
   const long long n_rows = h->n_rows;
   hipStream_t st = h->st;
@@ -313,7 +313,7 @@ int run(mvsvd_handle *h, int n_rank, int center, T *M, T *sigma, T *S, T *means,
   hipEventRecord(h->ev[3], st);
   if (refine) {
     if (int rc = need_refine_b(h)) return rc;
-    if (n <= 32 && n % 2 == 0 && (n * sizeof(T)) % 16 == 0 && n_rows >= 4096)  // tall and narrow: the streaming form
+    if (rotate_streams(sizeof(T), n_rows, n))  // tall and narrow: the streaming form
       launch_rotate_rows<T>(h, dW, n_rows, n, mu, h->dV1, h->dB);
     else
       launch_rotate<T>(h, dW, n_rows, n, mu, h->dV1, h->dB);

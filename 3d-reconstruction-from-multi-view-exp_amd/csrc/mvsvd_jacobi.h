@@ -4,6 +4,16 @@
 // mvsvd.hip); the dual depth update runs k_jacobi_small as a batch, one 12 x 12 problem per image, and dominant_eigvec4
 // (mvsvd_depth.h) uses jacobi_rotation in registers.
 
+// Is a_pq worth a rotation?  Above the relative threshold tol sqrt(a_pp a_qq) (small eigenvalues keep their RELATIVE
+// accuracy) -- and above the rounding noise of the update itself, 2 eps max(a_pp, a_qq): between a large and a small
+// eigenvalue (1e9 and 0.2 in a rank-4 measurement matrix with noise) the relative threshold 1e-11 sits AT that noise
+// (1.4e-7 against ~1e-7), such pairs flicker above it for ever, and a value of that size moves the eigenvalues by
+// a_pq^2 / (λ_p - λ_q) ~ 1e-23 and the vectors by 1e-16.
+__device__ __forceinline__ bool jacobi_needs(double app, double apq, double aqq, double tol2) {
+  const double big = fmax(fabs(app), fabs(aqq)) * 4.5e-16;
+  return apq * apq > fmax(tol2 * fabs(app * aqq), big * big);
+}
+
 // Round-robin parallel Jacobi on the symmetric n x n matrix A (global memory), eigenvectors in V.
 // np = n rounded up to even (a phantom index np-1 == n is skipped).
 template <bool IN_LDS>  // IN_LDS: both n x n matrices live in LDS (n <= 64): latency ~100 ns instead of ~1.5 us
@@ -34,8 +44,14 @@ __global__ __launch_bounds__(1024) void k_jacobi(double *__restrict__ Ag, double
         const int p = min(a, b), q = max(a, b);
         double c = 1.0, s = 0.0;
         if (q < n) {
-          const double apq = A[(size_t)p * n + q], app = A[(size_t)p * n + p], aqq = A[(size_t)q * n + q];
-          if (fabs(apq) > tol * sqrt(fabs(app * aqq)) && apq != 0.0) {
+          // The pivot is the mean of its two copies.  Rows and columns are updated independently here, so the copies pick up
+          // different rounding, of the size eps x the LARGEST eigenvalue that passed through their row: next to eigenvalues that
+          // are zero (a matrix of fewer rows than columns, exact low rank) that antisymmetric part is as large as the block
+          // itself, no rotation removes it (J^T K J stays antisymmetric), and a rule that reads one copy rotated such pairs for
+          // all max_sweeps.  The symmetric part is what the rotations diagonalise, so it is what they are chosen from -- with
+          // jacobi_needs' floor at the rounding noise of the update, as in the small solver.
+          const double apq = 0.5 * (A[(size_t)p * n + q] + A[(size_t)q * n + p]), app = A[(size_t)p * n + p], aqq = A[(size_t)q * n + q];
+          if (jacobi_needs(app, apq, aqq, tol * tol)) {
             const double tau = (aqq - app) / (2.0 * apq);
             const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
             c = 1.0 / sqrt(1.0 + t * t);
@@ -105,16 +121,6 @@ __global__ __launch_bounds__(1024) void k_jacobi(double *__restrict__ Ag, double
 // After a sweep (np - 1 steps) every index is back in its seat.
 constexpr int JWS = JW + 1;  // padded LDS stride of the small solver (its max order JW: mvba_host.h)
 constexpr int JT = 768;               // its threads
-
-// Is a_pq worth a rotation?  Above the relative threshold tol sqrt(a_pp a_qq) (small eigenvalues keep their RELATIVE
-// accuracy) -- and above the rounding noise of the update itself, 2 eps max(a_pp, a_qq): between a large and a small
-// eigenvalue (1e9 and 0.2 in a rank-4 measurement matrix with noise) the relative threshold 1e-11 sits AT that noise
-// (1.4e-7 against ~1e-7), such pairs flicker above it for ever, and a value of that size moves the eigenvalues by
-// a_pq^2 / (λ_p - λ_q) ~ 1e-23 and the vectors by 1e-16.
-__device__ __forceinline__ bool jacobi_needs(double app, double apq, double aqq, double tol2) {
-  const double big = fmax(fabs(app), fabs(aqq)) * 4.5e-16;
-  return apq * apq > fmax(tol2 * fabs(app * aqq), big * big);
-}
 
 // (c, s) that annihilate a_pq; false = the pair is left alone
 __device__ __forceinline__ bool jacobi_rotation(double app, double apq, double aqq, double tol2, double &c, double &sn) {
